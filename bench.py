@@ -16,13 +16,19 @@ GPU (seeds rank*B+1 ...), each grown for `--max-iter` iterations by the HIP kern
   one fails.  Under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` the launcher's
   environment is used as it is.  One process per GPU, instances sharded with no data-path collective; the only
   collective is the final all_gather of the 16-byte per-instance result records (RCCL).
-* Time budget: a full-size C2 step takes tens of seconds.  `--max-seconds` (default 240, counted from PROCESS START:
-  allocation, CPU baseline and warm-up included) bounds the run: the loop stops after the last step that fits and the
-  JSON line reports the steps actually timed in `steps` (`steps_requested` keeps K).  The workload is never shrunk.
+* `--steps K` timed steps are run, no more and no fewer.  A full-size C2 step takes about ten seconds; `--max-seconds S`
+  (off unless given, or set by RRTX_BENCH_MAX_SECONDS; counted from PROCESS START: allocation, CPU baseline and
+  warm-up included) bounds the run instead: the loop stops after the last step that fits and the JSON line reports the
+  steps actually timed in `steps` (`steps_requested` keeps K).  The workload is never shrunk.
 * The CPU baseline (oracle/rrt_oracle.c on the host cores, single thread and one instance per core) runs BEFORE the
   timed loop, bounded to ~12 s.
 * Prints ONE JSON line (rank 0) on stdout.  If the process receives SIGTERM after at least one timed step, the line
   for the steps completed so far is printed before exiting.
+* `--dump-outputs DIR` (rank 0): after the timed steps, what the last one computed, as the caller of the planning call
+  receives it, goes to DIR/<name>.npy (float64, integer fields converted exactly): the result table of every instance
+  (results_*) and the tree and final path of a fixed, seeded sample of rank 0's instances (sample_instance, tree_*,
+  path_*; concatenated, *_offsets delimit the instances), at most 64 MB in all.  The inputs depend on the arguments
+  only, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -42,6 +48,8 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E peak (MI355X_MICROARCH.md)
+DUMP_TREES = 16             # --dump-outputs: instances of the seeded sample whose trees and paths are written
+DUMP_BYTES = 64 << 20       # --dump-outputs: bound of all files together
 
 
 def elapsed():
@@ -78,13 +86,20 @@ def parse_args(argv=None):
     ap.add_argument("--warmup-max-iter", type=int, default=3000,
                     help="iterations of a warm-up step (0 = same as a timed step); a warm-up only has to page in the "
                          "code objects and allocations, a full-size C2 pass takes tens of seconds")
-    ap.add_argument("--max-seconds", type=float, default=float(os.environ.get("RRTX_BENCH_MAX_SECONDS", "480")),
-                    help="time budget from process start (setup, CPU baseline and warm-up included); the JSON reports "
-                         "the steps actually timed")
+    env_budget = os.environ.get("RRTX_BENCH_MAX_SECONDS")
+    ap.add_argument("--max-seconds", type=float, default=float(env_budget) if env_budget else None,
+                    help="time budget from process start (setup, CPU baseline and warm-up included; default: none, "
+                         "--steps decides); the JSON reports the steps actually timed")
     ap.add_argument("--dry-run", action="store_true",
                     help="no device: every rank reports synthetic counters (gloo backend); exercises the launch, the "
                          "collectives and the report only -- the line carries \"dry_run\": true and no throughput")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (result table of every instance, "
+                         "trees and paths of a fixed sample of instances; at most 64 MB)")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------ self-launch
@@ -428,6 +443,50 @@ class DryHandle:
         pass
 
 
+# ------------------------------------------------------------------------------------------------ output dump
+def dump_outputs(out_dir, h, wl, results, np, trees=True):
+    """--dump-outputs: the last timed step's outputs as the caller of the planning call receives them -- the result
+    table (path cost, tree size, status) of every instance of every rank, and get_tree / get_path (+ the yaws of the
+    pose planners) of a fixed, seeded sample of this rank's instances -- as float64 .npy files, DUMP_BYTES at most."""
+    pc, nn, st = results
+    arrays = {"results_path_cost": np.asarray(pc, dtype=np.float64),
+              "results_n_nodes": np.asarray(nn, dtype=np.float64),
+              "results_status": np.asarray(st, dtype=np.float64)}
+    if trees:
+        pose, rs = wl.a.workload in ("c5", "c6"), wl.a.workload == "c6"
+        room = DUMP_BYTES - sum(v.nbytes for v in arrays.values())
+        sample = []                        # (instance, {name: array}) in the seeded order, while they fit
+        for i in np.random.default_rng(12345).permutation(wl.B)[:DUMP_TREES]:
+            i = int(i)
+            x, y, cost, parent = h.get_tree(i)
+            path = h.get_path(i)
+            got = {"tree_x": x, "tree_y": y, "tree_cost": cost, "tree_parent": parent,
+                   "path_xy": np.zeros((0, 2)) if path is None else path}
+            if pose:
+                got["tree_yaw"] = h.get_yaw(i)
+            if rs:
+                yaw = h.get_path_yaw(i)
+                got["path_yaw"] = np.zeros(0) if yaw is None else yaw
+            nbytes = 8 * (sum(v.size for v in got.values()) + 3)     # + the instance's index and two offsets
+            if nbytes > room:
+                break
+            room -= nbytes
+            sample.append((i, got))
+        sample.sort(key=lambda e: e[0])
+        arrays["sample_instance"] = np.array([i for i, _ in sample], dtype=np.float64)
+        arrays["tree_offsets"] = np.cumsum([0] + [len(g["tree_x"]) for _, g in sample]).astype(np.float64)
+        arrays["path_offsets"] = np.cumsum([0] + [len(g["path_xy"]) for _, g in sample]).astype(np.float64)
+        names = ["tree_x", "tree_y", "tree_cost", "tree_parent", "path_xy"] + (["tree_yaw"] if pose else []) + \
+            (["path_yaw"] if rs else [])
+        for name in names:
+            empty = np.zeros((0, 2) if name == "path_xy" else 0)
+            arrays[name] = np.concatenate([empty] + [g[name] for _, g in sample]).astype(np.float64)
+    assert sum(v.nbytes for v in arrays.values()) <= DUMP_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 # ------------------------------------------------------------------------------------------------ main
 def main():
     a = parse_args()
@@ -517,6 +576,7 @@ def main():
         else:
             tmax, tot_eu, tot_er, tot_it = dt, state["eu"], state["er"], state["iters"]
             all_pc, all_nn, all_st = np.asarray(pc), np.asarray(nn), np.asarray(st)
+        state["all_results"] = (all_pc, all_nn, all_st)
         if rank != 0:
             return None
         # roofline of the DOMINANT kernel: its own launches and HIP-event time (C2: the iteration kernel; the final
@@ -756,7 +816,8 @@ def main():
         warm_done += 1
         tw = time.perf_counter() - tw
         # a warm-up must leave room for at least one timed step (a full-size warm-up costs as much as one)
-        if not sharding.all_agree_min(dist, 1 if elapsed() + 2.5 * tw <= a.max_seconds else 0, cuda):
+        if a.max_seconds is not None and not sharding.all_agree_min(
+                dist, 1 if elapsed() + 2.5 * tw <= a.max_seconds else 0, cuda):
             break
     if hw is not h:
         hw.close()
@@ -797,8 +858,9 @@ def main():
         state["steps_done"] += 1
         state["dt"] = time.perf_counter() - state["t0"]
         last = time.perf_counter() - ts
-        # time guard (all ranks take the same decision: the slowest rank's clock decides)
-        if not sharding.all_agree_min(dist, 1 if elapsed() + 1.1 * last <= a.max_seconds else 0, cuda):
+        # time guard, when a budget is set (all ranks take the same decision: the slowest rank's clock decides)
+        if a.max_seconds is not None and not sharding.all_agree_min(
+                dist, 1 if elapsed() + 1.1 * last <= a.max_seconds else 0, cuda):
             break
     sync_all()
     state["dt"] = time.perf_counter() - state["t0"]
@@ -806,6 +868,8 @@ def main():
 
     state["native_rccl"] = native_rccl
     line = build_line(h, final=True)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, h, wl, state["all_results"], np, trees=not a.dry_run)
     if rank == 0:
         line["warmup"] = warm_done
         line["result_gather"] = ("rrtx_rccl_gather_results (ncclAllGather from librrtx.so)" if native_rccl else

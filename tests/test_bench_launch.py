@@ -78,6 +78,22 @@ def test_bench_time_budget_reports_steps_done():
     assert 1 <= j["steps"] < 500000 and j["steps_requested"] == 500000 and j["elapsed_s"] < 30
 
 
+def test_bench_times_exactly_the_requested_steps_and_dumps_the_result_table(tmp_path):
+    """Without --max-seconds, --steps K times K steps; --dump-outputs writes the last step's result table in float64."""
+    out = tmp_path / "out"
+    r = _run(["--dry-run", "--steps", "7", "--warmup", "2", "--instances", "40", "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert j["steps"] == 7 and j["steps_requested"] == 7 and j["warmup"] == 2
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["results_n_nodes.npy", "results_path_cost.npy", "results_status.npy"]
+    for name in files:
+        v = np.load(out / name)
+        assert v.dtype == np.float64 and v.shape == (40,)
+    assert np.array_equal(np.load(out / "results_n_nodes.npy"), np.full(40, float(j["config"]["max_iter"])))
+    assert _run(["--dry-run", "--steps", "0"]).returncode != 0
+
+
 def test_bench_gpus_mismatch_is_an_error():
     r = _run(["--gpus", "3", "--dry-run"], env_extra=dict(WORLD_SIZE="2", RANK="0", LOCAL_RANK="0",
                                                            MASTER_ADDR="127.0.0.1", MASTER_PORT="1"))
@@ -120,3 +136,35 @@ def test_bench_two_shards_on_one_gpu_equal_the_single_shard_run():
     for k in ("paths_found", "final_path_cost_mean", "final_path_cost_min", "mean_nodes_per_tree"):
         assert j2[k] == j1[k], k
     assert j2["iterations_per_s"] > 0 and j2["roofline"]["frac"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_equal_the_oracle_and_repeat(tmp_path):
+    """--dump-outputs of a C2 batch: the sampled trees and paths are the oracle's for those instances (seed = instance
+    + 1), the result table agrees with them, and a second run writes the same files bit for bit."""
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "0", "--instances", "48", "--max-iter", "1500",
+            "--no-cpu-baseline", "--dump-outputs"]
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = _run(args + [str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == sorted(p.name for p in dirs[1].iterdir())
+    for name in names:
+        v0, v1 = np.load(dirs[0] / name), np.load(dirs[1] / name)
+        assert v0.dtype == np.float64 and np.array_equal(v0, v1, equal_nan=True), name
+    o = {n[:-4]: np.load(dirs[0] / n) for n in names}
+    assert len(o["results_path_cost"]) == 48 and len(o["sample_instance"]) == 16
+    kw = util.c2_kwargs(1500)
+    for k, inst in enumerate(o["sample_instance"].astype(int)):
+        t0, t1 = int(o["tree_offsets"][k]), int(o["tree_offsets"][k + 1])
+        p0, p1 = int(o["path_offsets"][k]), int(o["path_offsets"][k + 1])
+        ref = util.run_oracle(kw, int(inst) + 1, exact_pow=True)
+        util.assert_tree_equal((o["tree_x"][t0:t1], o["tree_y"][t0:t1], o["tree_cost"][t0:t1],
+                                o["tree_parent"][t0:t1].astype(np.int32)),
+                               (ref["x"], ref["y"], ref["cost"], ref["parent"]), "instance %d" % inst)
+        assert o["results_n_nodes"][inst] == t1 - t0
+        if ref["path"] is None:
+            assert p1 == p0 and not np.isfinite(o["results_path_cost"][inst])
+        else:
+            assert np.array_equal(o["path_xy"][p0:p1], ref["path"]) and np.isfinite(o["results_path_cost"][inst])

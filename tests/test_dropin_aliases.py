@@ -1,15 +1,16 @@
 """Per-script drop-in modules: `rrt_amd.rrt_01` ... `rrt_amd.rrt_08` expose exactly the names the
 reference script of that number defines for its driver cell, bound to the right mirror class, with the script's
 constructor keywords and defaults.  CPU only: nothing here touches a device."""
-import ast
 import importlib
 import inspect
+import json
 import math
 import os
 
 import pytest
 
-REF = "/root/reference/src_path_planning"
+import util
+
 DEG1 = math.radians(1.0)
 
 # (module, reference file, name -> mirror class name, positional ctor args, keyword defaults in order) -- the reference's
@@ -80,26 +81,21 @@ def test_alias_module_names_classes_and_defaults(mod, ref_file, names, pos, kw):
         assert callable(getattr(m, f)) and f in m.__all__
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference sources are not present on this machine")
 @pytest.mark.parametrize("mod,ref_file,names,pos,kw", CASES, ids=[c[0] for c in CASES])
 def test_alias_signatures_equal_the_reference_sources(mod, ref_file, names, pos, kw):
-    """Where /root/reference is readable (the build container), the expected table above is itself checked against the
-    script's source text (parsed, never imported or executed)."""
-    tree = ast.parse(open(os.path.join(REF, ref_file)).read())
-    cls = "BITStar" if mod == "rrt_08" else "RRT"
-    top = {n.name: n for n in tree.body if isinstance(n, (ast.ClassDef, ast.FunctionDef))}
+    """The expected table above is itself checked against the reference scripts' interface as recorded from their
+    source text (tests/golden/ref_signatures.json, made by oracle/gen_golden_signatures.py: parsed, never imported)."""
+    with open(os.path.join(util.GOLDEN, "ref_signatures.json")) as f:
+        ref = json.load(f)[mod]
+    assert ref["file"] == ref_file
+    assert ref["class"] == ("BITStar" if mod == "rrt_08" else "RRT")
     for name in list(names) + FUNCS.get(mod, []):
-        assert name in top, (mod, name)
-    init = [f for f in top[cls].body if isinstance(f, ast.FunctionDef) and f.name == "__init__"][0]
-    args = [a.arg for a in init.args.args][1:]
-    nd = len(init.args.defaults)
-    assert args[:len(args) - nd] == pos
-    ref_kw = list(zip(args[len(args) - nd:], [ast.unparse(d) for d in init.args.defaults]))
-    assert [k for k, _ in ref_kw] == [k for k, _ in kw]
-    for (k, src), (_, v) in zip(ref_kw, kw):
-        val = DEG1 if src == "np.deg2rad(1.0)" else ast.literal_eval(src)
-        assert val == v, (mod, k, src, v)
-    assert any(isinstance(f, ast.FunctionDef) and f.name == ENTRY[mod] for f in top[cls].body)
+        assert name in ref["defines"], (mod, name)
+    assert ref["init_positional"] == pos
+    assert [k for k, _ in ref["init_keywords"]] == [k for k, _ in kw]
+    for (k, val), (_, v) in zip(ref["init_keywords"], kw):
+        assert val == v, (mod, k, val, v)
+    assert ENTRY[mod] in ref["entry_points"]
 
 
 @pytest.mark.gpu

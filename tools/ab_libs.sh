@@ -4,7 +4,7 @@
 # (boxes differ by up to 9 %, and the first run of a call pages the image in: only same-box pairs count), and prints
 # ms_per_step / kernel ms / final cost per run.  Output under gpurun_out/ab/.
 W=$1; ARGS=$2; shift 2
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 O=$REPO/gpurun_out/ab
 mkdir -p $O
 cd $REPO

@@ -4,9 +4,10 @@
 # rppk2t::rrt_star_kernel_v2<true>, the lines per slot, the scratch instructions and the full s_waitcnt vmcnt(0) drains inside it:
 # a register-allocation regression of the hot loop shows here before any GPU time is spent.
 BODY=$1; shift
-D=/tmp/chk_$$; mkdir -p $D; cp /root/repo/robotics-path-planning_amd/csrc/* $D/; cp $BODY $D/rrt_star_v2_body.inc
+REPO=$(cd "$(dirname "$0")/.." && pwd)
+D=/tmp/chk_$$; mkdir -p $D; cp $REPO/robotics-path-planning_amd/csrc/* $D/; cp $BODY $D/rrt_star_v2_body.inc
 mkdir -p $D/../include 2>/dev/null
-cd $D && sed -i 's#"../../include/rrtx.h"#"/root/repo/include/rrtx.h"#' rrtx_api.hip
+cd $D && sed -i "s#\"../../include/rrtx.h\"#\"$REPO/include/rrtx.h\"#" rrtx_api.hip
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Wno-parentheses-equality -Wno-unused-value "$@" --cuda-device-only -S -Rpass-analysis=kernel-resource-usage -o $D/o.s rrtx_api.hip 2> $D/err.txt
 grep -A7 "Function Name: _ZN6rppk2t18rrt_star_kernel_v2ILb1" $D/err.txt | grep -E "VGPRs Spill|ScratchSize|SGPRs Spill" | sed 's/.*remark: *//' | tr '\n' ' '; echo
 grep -E "error" $D/err.txt | head -3

@@ -11,7 +11,7 @@
 #   4. C3..C6: bench line + VALU PMC pass -> r3_bench_<w>.json, r3_<w>_valu.json
 # Everything is written under gpurun_out/r3/ (merged back by gpurun); copy it into profiles/ and commit.
 export RRTX_COMMIT=${RRTX_COMMIT:-unknown}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 O=$REPO/gpurun_out/r3
 mkdir -p $O
 cd $REPO

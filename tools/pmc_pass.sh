@@ -2,7 +2,7 @@
 # One rocprofv3 --pmc pass of bench.py (counters only: never combined with a trace domain), summed per kernel.
 #   bash tools/pmc_pass.sh <tag> "<COUNTER ...>" [bench args]      -> gpurun_out/pmc_<tag>.txt
 TAG=$1; CTRS=$2; shift 2
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

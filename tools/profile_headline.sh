@@ -3,7 +3,7 @@
 # PMC passes (never combined with a trace domain).  Usage (through gpurun): bash tools/profile_headline.sh <tag> [bench args]
 set -e
 TAG=${1:-r1_f32}; shift || true
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -3,7 +3,7 @@
 # to gpurun_out/ as <tag>_<workload>_kernel_stats.csv.  Usage (through gpurun): bash tools/profile_workloads.sh <tag>
 set -e
 TAG=${1:-r1}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for W in ${WORKLOADS:-c3 c4 c5 c6}; do
   OUT=$REPO/gpurun_out/prof_${TAG}_$W

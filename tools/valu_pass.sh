@@ -3,7 +3,7 @@
 # (counters only) of `bench.py --workload <w>`; writes profiles/r3_<w>_valu.json (read back by bench.py as roofline.valu).
 #   RRTX_COMMIT=$(git rev-parse --short HEAD) gpurun -- 'bash tools/valu_pass.sh c5'
 W=$1; shift
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/valu_$W
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
