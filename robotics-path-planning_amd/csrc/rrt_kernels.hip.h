@@ -106,7 +106,16 @@ struct Ctx {
   double* elen;
   // two iterations per streaming pass in the one-wave shape of the rrt_04 iteration kernel (rrt_star_v2_body.inc)
   int32_t spec2;
+  // grid index of the 16-bit mirror, one-wave shape of the rrt_04 iteration kernel (rrt_star_v2_body.inc, "grid index"):
+  // square cells of 2^gsh grid steps, gn x gn of them (gcells per instance).  Per cell an entry count, GRID_CAP0 entries
+  // {node | xq << 32} and the number (+1, 0: none) of one overflow block of GRID_CAP1 entries from the instance's pool.
+  int32_t *gcnt, *gblk;
+  uint64_t *gent, *gpool;
+  int32_t gsh, gn, gcells, gpool_blocks;
+  int32_t grid;       // 1: passes of trees of at least grid_min nodes are answered from the index (RRTX_GRID)
+  int32_t grid_min;
 };
+constexpr int GRID_CAP0 = 16, GRID_CAP1 = 16;
 
 // 16-bit mirror entry of a point (Ctx::xq)
 __device__ __forceinline__ uint32_t quant16(const Ctx& c, double px, double py) {

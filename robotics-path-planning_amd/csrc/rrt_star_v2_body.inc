@@ -694,6 +694,338 @@ __device__ __forceinline__ int scan2q(const uint32_t* __restrict__ xq, int n, ui
   return total;
 }
 
+// ---- Grid index of the 16-bit mirror (one-wave shape; DESIGN 5.1 "grid index") ----------------------------------------
+// Once the tree is dense a pass reads 4 n bytes to find a handful of nodes: the near ball holds ~8 of 10^5, the nearest
+// node is a fraction of a metre away.  The index keys every node on the top bits of its xq[] value -- the same square, the
+// same clamping as the mirror -- so a query reads the counts of the few cells that cover it (one round trip) and their
+// entries {node, xq} (a second one), and applies to them exactly the grid test of the streaming pass.  A pass over the
+// index has the contract of scan2q: the ball's hits in ascending index order with exact counts, the nearest node's
+// 4-node group with the lowest index among equals, and a runner-up that is the true one or a lower bound of it.
+// Left out of the index: the exact goal duplicates (SURVEY R6; all at the goal's xq value with indices above first_goal,
+// `excl` of them), so the goal's cell stays small; a ball that reaches them counts them like the streaming pass does.
+struct GridS {
+  int32_t* cnt;     // [gcells] entries per cell
+  int32_t* blk;     // [gcells] overflow block + 1 (0: none)
+  uint64_t* ent;    // [gcells][GRID_CAP0] {node | xq << 32}
+  uint64_t* pool;   // [pool_blocks][GRID_CAP1]
+  int sh, gn, pool_blocks, pool_next, excl, min_n;
+  uint32_t goal_q;
+  int ok;           // 0: the index is off, or incomplete for the rest of the launch -- every pass streams
+  int bytes, nodes; // what the last pass read: bytes and nodes (entries) it tested
+};
+constexpr int GRID_CAP0 = rppk::GRID_CAP0, GRID_CAP1 = rppk::GRID_CAP1, GRID_CAPT = GRID_CAP0 + GRID_CAP1;
+constexpr int GE = 4;   // entries per lane a window gathers: 256 at most
+static_assert(GRID_CAPT <= 64, "a cell's entries fit one wave");
+
+__device__ __forceinline__ int grid_cell(const GridS& g, uint32_t q) {
+  const uint32_t u = q ^ 0x80008000u;   // unsigned grid coordinates
+  return (int)((u >> (16 + g.sh)) * (uint32_t)g.gn + ((u & 0xffffu) >> g.sh));
+}
+__device__ __forceinline__ uint64_t grid_entry(int node, uint32_t q) { return (uint64_t)(uint32_t)node | ((uint64_t)q << 32); }
+
+// The index of nodes [0, n) from xq[] (every launch starts with it: resume and re-plan need nothing else).  Appends go
+// through grid_insert, a node that rewire moves through grid_remove + grid_insert.
+__device__ __forceinline__ void grid_build(GridS& g, const uint32_t* __restrict__ xq, const double* x, const double* y,
+                                           int n, double gx, double gy, int first_goal) {
+  const int lane = threadIdx.x & 63;
+  const int cells = g.gn * g.gn;
+  for (int i = lane; i < cells; i += 64) {
+    g.cnt[i] = 0;
+    g.blk[i] = 0;
+  }
+  g.pool_next = 0;
+  g.excl = 0;
+  __threadfence();
+  const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  for (int i0 = 0; i0 < n; i0 += 64) {
+    const int i = i0 + lane;
+    bool on = i < n;
+    const uint32_t q = on ? xq[i] : 0u;
+    if (on && first_goal >= 0 && q == g.goal_q && i != first_goal && x[i] == gx && y[i] == gy) on = false;
+    g.excl += __popcll(__ballot(i < n && !on));
+    const int cell = grid_cell(g, q);
+    const int k = on ? atomicAdd(&g.cnt[cell], 1) : 0;
+    const uint64_t nb = __ballot(on && k == GRID_CAP0);   // cells that need their overflow block now
+    if (on && k == GRID_CAP0) {
+      const int b = g.pool_next + __popcll(nb & lt_mask) + 1;
+      if (b <= g.pool_blocks) g.blk[cell] = b;
+    }
+    g.pool_next += __popcll(nb);
+    __threadfence();
+    if (on && k < GRID_CAP0) {
+      g.ent[(int64_t)cell * GRID_CAP0 + k] = grid_entry(i, q);
+    } else if (on && k < GRID_CAPT) {
+      const int b = g.blk[cell];
+      if (b > 0) g.pool[(int64_t)(b - 1) * GRID_CAP1 + (k - GRID_CAP0)] = grid_entry(i, q);
+    }
+  }
+  if (g.pool_next > g.pool_blocks) g.ok = 0;
+  __threadfence();
+}
+
+// Node `node` at packed position q joins its cell (every lane calls; lane 0 stores).  A cell past both blocks keeps
+// counting: the passes that need it stream.
+__device__ __forceinline__ void grid_insert(GridS& g, int node, uint32_t q) {
+  const int cell = grid_cell(g, q);
+  const int k = g.cnt[cell];
+  int b = g.blk[cell];
+  const uint64_t e = grid_entry(node, q);
+  if (k < GRID_CAP0) {
+    if (threadIdx.x == 0) g.ent[(int64_t)cell * GRID_CAP0 + k] = e;
+  } else if (k < GRID_CAPT) {
+    if (b == 0) {
+      if (g.pool_next >= g.pool_blocks) {
+        g.ok = 0;
+        return;
+      }
+      b = ++g.pool_next;
+      if (threadIdx.x == 0) g.blk[cell] = b;
+    }
+    if (threadIdx.x == 0) g.pool[(int64_t)(b - 1) * GRID_CAP1 + (k - GRID_CAP0)] = e;
+  }
+  if (threadIdx.x == 0) g.cnt[cell] = k + 1;
+}
+
+// Node `node`, at packed position q until now, leaves its cell: the cell's last entry takes its place.
+__device__ __forceinline__ void grid_remove(GridS& g, int node, uint32_t q) {
+  const int lane = threadIdx.x & 63;
+  const int cell = grid_cell(g, q);
+  const int k = g.cnt[cell], b = g.blk[cell];
+  if (k > GRID_CAPT) {
+    g.ok = 0;
+    return;
+  }
+  uint64_t* p = lane < GRID_CAP0 ? g.ent + (int64_t)cell * GRID_CAP0 + lane
+                                 : (b > 0 ? g.pool + (int64_t)(b - 1) * GRID_CAP1 + (lane - GRID_CAP0) : nullptr);
+  const bool mine = lane < k && p != nullptr;
+  const uint64_t e = mine ? *p : 0ull;
+  const uint64_t m = __ballot(mine && (int)(uint32_t)e == node);
+  if (m == 0ull) {   // not in the index (a left-out goal duplicate): the index is incomplete from here
+    g.ok = 0;
+    return;
+  }
+  const int j = __ffsll((long long)m) - 1;
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)e, k - 1), hi = (uint32_t)__shfl((int)(uint32_t)(e >> 32), k - 1);
+  if (lane == j) *p = (uint64_t)lo | ((uint64_t)hi << 32);
+  if (lane == 0) g.cnt[cell] = k - 1;
+}
+
+// One centre of a pass over the index: the cells of the square window [centre - rw, centre + rw] (at most 64, at most
+// 256 entries).  BALL: the entries with grid distance <= thr, ascending, at hits[off ..] (first `cap`) and lhit[] (first
+// HWF; nullptr: none); gz >= 0 applies the goal-cell rule of scan2q_slot (zcnt).  NEAREST: (best, runner-up, group) over
+// the window, runner-up capped at D^2 (D: distance to the nearest cell outside the window, a lower bound of any node
+// there); the answer stands only when best + 2 q_m (+ 1 step for the roundings of the caller's test) lies inside D --
+// then both the winner and every decision the caller takes on the runner-up are those of the full pass -- else the
+// window grows (twice at most).  False: the index cannot answer (the caller streams).
+__device__ __forceinline__ bool grid_centre(const GridS& g, uint32_t cq, int rw, bool ball, uint32_t thr, bool nearest,
+                                            int32_t* __restrict__ hits, int off, int cap, int32_t* lhit, int32_t* ltmp,
+                                            int gz, int& cnt, int& zcnt, uint32_t& best, uint32_t& second, int& grp,
+                                            int& bytes, int& nodes) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const int ux = (int)((cq ^ 0x80008000u) & 0xffffu), uy = (int)((cq ^ 0x80008000u) >> 16);
+  for (int attempt = 0; attempt < 3; attempt++) {
+    const int x0 = max(ux - rw, 0) >> g.sh, x1 = min(ux + rw, 65535) >> g.sh;
+    const int y0 = max(uy - rw, 0) >> g.sh, y1 = min(uy + rw, 65535) >> g.sh;
+    const int nwx = x1 - x0 + 1, nc = nwx * (y1 - y0 + 1);
+    if (nc > 64) return false;
+    int D = 32767;
+    if (x0 > 0) D = min(D, ux - (x0 << g.sh) + 1);
+    if (x1 < g.gn - 1) D = min(D, ((x1 + 1) << g.sh) - ux);
+    if (y0 > 0) D = min(D, uy - (y0 << g.sh) + 1);
+    if (y1 < g.gn - 1) D = min(D, ((y1 + 1) << g.sh) - uy);
+    int cell = 0, cn = 0, cb = 0;
+    if (lane < nc) {
+      cell = (y0 + lane / nwx) * g.gn + x0 + lane % nwx;
+      cn = g.cnt[cell];
+      cb = g.blk[cell];
+    }
+    if (__ballot(cn > GRID_CAPT) != 0ull) return false;
+    int inc = cn;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(inc, o);
+      if (lane >= o) inc += t;
+    }
+    const int tot = __shfl(inc, 63);
+    bytes += 8 * nc + 8 * tot;
+    nodes += tot;
+    if (tot > 64 * GE) return false;
+    const int pre = inc - cn;
+    const uint64_t* ptr[GE];
+#pragma unroll
+    for (int k = 0; k < GE; k++) ptr[k] = nullptr;
+    for (uint64_t nz = __ballot(cn > 0); nz != 0ull; nz &= nz - 1) {
+      const int j = __ffsll((long long)nz) - 1;
+      const int pj = __builtin_amdgcn_readlane(pre, j), cj = __builtin_amdgcn_readlane(cn, j);
+      const int ej = __builtin_amdgcn_readlane(cell, j), bj = __builtin_amdgcn_readlane(cb, j);
+#pragma unroll
+      for (int k = 0; k < GE; k++) {
+        const int r = lane + 64 * k - pj;
+        if (r >= 0 && r < cj)
+          ptr[k] = r < GRID_CAP0 ? g.ent + (int64_t)ej * GRID_CAP0 + r : g.pool + (int64_t)(bj - 1) * GRID_CAP1 + (r - GRID_CAP0);
+      }
+    }
+    uint32_t ev[GE], d[GE];
+    int ei[GE];
+#pragma unroll
+    for (int k = 0; k < GE; k++) {
+      const uint64_t e = ptr[k] ? *ptr[k] : 0ull;
+      ei[k] = ptr[k] ? (int)(uint32_t)e : 0x7fffffff;
+      ev[k] = (uint32_t)(e >> 32);
+      d[k] = ptr[k] ? qdist(ev[k], cq) : 0xffffffffu;
+    }
+    if (ball && attempt == 0) {
+      // the left-out goal duplicates lie at goal_q: counted with gz >= 0, else they would be hits the index cannot list
+      const bool zin = g.excl > 0 && qdist(g.goal_q, cq) <= thr;
+      if (zin && gz < 0) return false;
+      int z = zin ? g.excl : 0, H = 0;
+      bool hh[GE];
+#pragma unroll
+      for (int k = 0; k < GE; k++) {
+        hh[k] = d[k] <= thr;   // thr < 2^32 - 1: an empty slot never hits
+        if (gz >= 0) {
+          const bool skip = hh[k] && ev[k] == g.goal_q && ei[k] != gz;
+          z += __popcll(__ballot(skip));
+          hh[k] = hh[k] && !skip;
+        }
+        const uint64_t m = __ballot(hh[k]);
+        if (hh[k]) ltmp[H + __popcll(m & lt_mask)] = ei[k];
+        H += __popcll(m);
+      }
+      lds_barrier();
+      // ascending order: a hit's place is the number of hits with a lower index
+      for (int h0 = 0; h0 < H; h0 += 64) {
+        if (h0 + lane < H) {
+          const int me = ltmp[h0 + lane];
+          int r = 0;
+          for (int j = 0; j < H; j++) r += ltmp[j] < me ? 1 : 0;
+          if (r < cap) hits[off + r] = me;
+          if (lhit && r < HWF) lhit[r] = me;
+        }
+      }
+      lds_barrier();
+      cnt = H;
+      zcnt = z;
+    }
+    if (!nearest) return true;
+    uint32_t b = 0xffffffffu, s = 0xffffffffu;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < GE; k++) {
+      if (d[k] < b || (d[k] == b && ei[k] < bi)) {
+        s = b;
+        b = d[k];
+        bi = ei[k];
+      } else {
+        s = min(s, d[k]);
+      }
+    }
+    uint32_t wb = b;
+    int wi = bi;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const uint32_t ob = (uint32_t)__shfl_xor((int)wb, o);
+      const int oi = __shfl_xor(wi, o);
+      const bool take = ob < wb || (ob == wb && oi < wi);
+      wb = take ? ob : wb;
+      wi = take ? oi : wi;
+    }
+    uint32_t ws = bi == wi ? s : b;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) ws = min(ws, (uint32_t)__shfl_xor((int)ws, o));
+    // the left-out duplicates tie with first_goal (in the index, lower index): a runner-up at the goal's distance
+    if (g.excl > 0) ws = min(ws, qdist(g.goal_q, cq));
+    if (wb < QSAT && (double)D > __builtin_sqrt((double)wb) + 4.0) {
+      best = wb;
+      second = min(ws, (uint32_t)(D * D));
+      grp = wi & ~3;
+      return true;
+    }
+    // grow the window: past best + margin when a node was found, else threefold
+    rw = wb < QSAT ? (int)__builtin_sqrt((double)wb) + 6 : 3 * rw + 1;
+    ball = false;
+  }
+  return false;
+}
+
+// A pass of scan2q's contract (same arguments and outputs) answered from the index; false: it cannot be (the caller
+// streams, which rewrites every output).  rwn: window half-width (grid steps) to start a nearest query with.
+template <bool NEAR, bool NEAREST, int KS>
+__device__ __forceinline__ bool grid_pass(GridS& g, int rwn, uint32_t qq, uint32_t thr, uint32_t sq,
+                                          int32_t* __restrict__ hits, Sh2& sh, int& ggrp, double& gbest, double& gsecond,
+                                          int gz, int* zskip, SpecQ* sp, int& total) {
+  int32_t* lhit = reinterpret_cast<int32_t*>(sh.u.hit);
+  int32_t* ltmp = lhit + HWF;
+  static_assert(sizeof(sh.u) >= sizeof(int32_t) * (HWF + 64 * GE), "LDS scratch of a grid pass");
+  int bytes = 0, nodes = 0;
+  uint32_t b, s;
+  int gr, zc = 0, cnt = 0;
+  if (NEAR) {
+    const int rw = (int)__builtin_sqrt((double)thr) + 1;
+    if (!grid_centre(g, qq, rw, true, thr, false, hits, 0, 0x7fffffff, lhit, ltmp, gz, cnt, zc, b, s, gr, bytes, nodes))
+      return false;
+  }
+  // centre j: the nearest query of the pass (j = 0, sq) or of set j - 1 (sp[j - 1].sq), and the ball of set j about it
+#pragma unroll
+  for (int j = 0; j <= KS; j++) {
+    const uint32_t cq = j == 0 ? sq : sp[j > 0 ? j - 1 : 0].sq;
+    const bool nq = j == 0 ? NEAREST : sp[j > 0 ? j - 1 : 0].thr != 0u;   // (a set with thr 0 is unused)
+    const uint32_t bthr = j < KS ? sp[j < KS ? j : 0].thr : 0u;
+    uint32_t bb = 0xffffffffu, bs = 0xffffffffu;
+    int bg = 0x7ffffffc, bc = 0, bz = 0;
+    if (nq || bthr != 0u) {
+      const int rw = max(bthr != 0u ? (int)__builtin_sqrt((double)bthr) + 1 : 0, nq ? rwn : 0);
+      const int jo = j < KS ? j : 0;
+      if (!grid_centre(g, cq, rw, bthr != 0u, bthr, nq, hits, KS > 0 ? sp[jo].off : 0, KS > 0 ? sp[jo].cap : 0, nullptr,
+                       ltmp, -1, bc, bz, bb, bs, bg, bytes, nodes))
+        return false;
+    }
+    if (j == 0) {
+      if (NEAREST) {
+        gbest = (double)bb;
+        gsecond = (double)bs;
+        ggrp = bg;
+      }
+    } else {
+      sp[j - 1].best = (double)bb;
+      sp[j - 1].second = (double)bs;
+      sp[j - 1].grp = bg;
+    }
+    if (j < KS) sp[j < KS ? j : 0].cnt = bc;
+  }
+  if (NEAR && threadIdx.x == 0) {
+    sh.wave_cnt[0] = cnt;
+    sh.wave_start[0] = 0;
+    sh.fa = zc;
+  }
+  lds_barrier();
+  if (NEAR && zskip) *zskip = gz >= 0 ? zc : 0;
+  total = NEAR ? cnt : 0;
+  g.bytes = bytes;
+  g.nodes = nodes;
+  return true;
+}
+
+// scan2q, answered from the grid index when the instance has one (one-wave shape, trees of at least min_n nodes) and it
+// can answer exactly; g.bytes / g.nodes: what the pass read
+template <bool NEAR, bool NEAREST, int KS = 0>
+__device__ __forceinline__ int scan2g(GridS& g, int rwn, const uint32_t* __restrict__ xq, int n, uint32_t qq, uint32_t thr,
+                                      uint32_t sq, int32_t* __restrict__ hits, Sh2& sh, int& ggrp, double& gbest,
+                                      double& gsecond, uint32_t gq = 0u, int gz = -1, int* zskip = nullptr,
+                                      SpecQ* sp = nullptr) {
+  if constexpr (NW == 1) {
+    if (g.ok && n >= g.min_n) {
+      int total = 0;
+      if (grid_pass<NEAR, NEAREST, KS>(g, rwn, qq, thr, sq, hits, sh, ggrp, gbest, gsecond, gz, zskip, sp, total))
+        return total;
+    }
+  }
+  g.bytes = 4 * n;
+  g.nodes = n;
+  return scan2q<NEAR, NEAREST, KS>(xq, n, qq, thr, sq, hits, sh, ggrp, gbest, gsecond, gq, gz, zskip, sp);
+}
+
 // The node of the group [grp, grp + 4) whose grid distance to the query `sq` is `best`; lanes 0..3 of every wave hold
 // the f64 coordinates (hx, hy) of the group's nodes, lane L those of node grp + (L & 3) (n = tree size the pass saw).  False when no node matches (the
 // caller then repeats the query one stage down).
@@ -1254,6 +1586,25 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   int n = __builtin_amdgcn_readfirstlane(I->n), it = __builtin_amdgcn_readfirstlane(I->it);   // block-uniform: keep them scalar
   const double gx = I->goal[0], gy = I->goal[1];
   rpp::Sobol sob = I->sobol;
+  // grid index of the mirror (one-wave shape): rebuilt from xq[] at every launch, kept current at every xq[] write
+  GridS gs = {};
+  gs.ok = 0;
+  if constexpr (NW == 1) {
+    if (F32 && Q16 && c.grid) {
+      const int64_t gi = (int64_t)inst;
+      gs.cnt = c.gcnt + gi * c.gcells;
+      gs.blk = c.gblk + gi * c.gcells;
+      gs.ent = c.gent + gi * c.gcells * GRID_CAP0;
+      gs.pool = c.gpool + gi * c.gpool_blocks * GRID_CAP1;
+      gs.sh = c.gsh;
+      gs.gn = c.gn;
+      gs.pool_blocks = c.gpool_blocks;
+      gs.min_n = c.grid_min;
+      gs.goal_q = goal_q;
+      gs.ok = 1;
+      grid_build(gs, xq, x, y, n, gx, gy, first_goal);
+    }
+  }
   if (tid == 0)
     for (int k = 0; k < 15; k++) sh.stat[k] = 0;
 #define ST_ADD(k, v) do { if (tid == 0) sh.stat[k] += (long long)(v); } while (0)
@@ -1404,9 +1755,9 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
             bool bound = q_amb != 0;
             if (!bound) {
               int grp;
-              scan2q<false, true>(xq, n, 0u, 0u, sq, hits, sh, grp, fb, fs);
-              ST_ADD(S_SN, n);
-              ST_ADD(S_AB, 4 * (int64_t)n + 64);
+              scan2g<false, true>(gs, (int)(__builtin_sqrt(r2) * qinv) + 1, xq, n, 0u, 0u, sq, hits, sh, grp, fb, fs);
+              ST_ADD(S_SN, gs.nodes);
+              ST_ADD(S_AB, gs.bytes + 64);
               if (fb < (double)QSAT) {
                 // accepted when the winner is exact (not saturated) and the runner-up is more than 2 q_m further
                 if ((__builtin_sqrt(fs) - __builtin_sqrt(fb)) > 2.0 * qm_grid) {
@@ -1434,9 +1785,9 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
                 ST_ADD(S_QA, 1);
                 int d0;
                 double d1, d2;
-                const int kc = scan2q<true, false>(xq, n, sq, (uint32_t)tb, 0u, hits, sh, d0, d1, d2);
-                ST_ADD(S_SN, n);
-                ST_ADD(S_AB, 4 * (int64_t)n + 16 * (int64_t)kc);
+                const int kc = scan2g<true, false>(gs, 0, xq, n, sq, (uint32_t)tb, 0u, hits, sh, d0, d1, d2);
+                ST_ADD(S_SN, gs.nodes);
+                ST_ADD(S_AB, gs.bytes + 16 * (int64_t)kc);
                 double best = rpp::dinf(), second = rpp::dinf(), bx = 0.0, by = 0.0;
                 int bidx = 0x7fffffff;
                 for (int h = tid; h < kc; h += TPB) {
@@ -1654,6 +2005,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       int pf_grp = -1, pf_n = 0;         // the winner's 4-node group (unresolved while >= 0) and the tree size scanned
       bool pf_goal = false;
       const double pm = Q16 ? qm : fm;   // margin of the stage that runs the fused pass
+      int64_t pass_b = 0, pass_n = n;    // 16-bit stage: bytes and nodes its passes read
       if (use_spec) {
         // the nodes appended since that pass join the ball by the pass's own grid test, in index order
         int k2 = spec_k0;
@@ -1691,6 +2043,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
         const float thr_f = (float)(rr * rr * (1.0 + 1e-6));
         const double thr_gd = rr * rr * qinv * qinv * (1.0 + 1e-6) + 1.0;    // the same in (integer) grid units
         const uint32_t thr_gi = thr_gd < 4.0e9 ? (uint32_t)thr_gd : 4000000000u;
+        const int rw_gi = (int)__builtin_sqrt((double)thr_gi) + 1;   // its window half-width (grid index)
         if (do_pf) {
           take_next_sample();
           lds_barrier();
@@ -1763,8 +2116,10 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
                     R[5] = (double)sp[j].off;
                   }
                 }
-                kraw = scan2q<true, true, KSM>(xq, n, rppk::quant16(c, nx, ny), thr_gi, pf_sq, hits, sh, pf_ni, pf_best,
-                                               pf_second, goal_q, zgate, &zskip, sp);
+                kraw = scan2g<true, true, KSM>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, pf_sq, hits, sh, pf_ni,
+                                               pf_best, pf_second, goal_q, zgate, &zskip, sp);
+                pass_b = gs.bytes;
+                pass_n = gs.nodes;
                 did_spec = true;
                 B_n = n;
                 B_thr = uni_u(thr2);
@@ -1786,13 +2141,17 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
                 }
               }
             }
-            if (!did_spec)
-              kraw = scan2q<true, true>(xq, n, rppk::quant16(c, nx, ny), thr_gi, pf_sq, hits, sh, pf_ni, pf_best, pf_second,
-                                        goal_q, zgate, &zskip);
+            if (!did_spec) {
+              kraw = scan2g<true, true>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, pf_sq, hits, sh, pf_ni, pf_best,
+                                        pf_second, goal_q, zgate, &zskip);
+              pass_b = gs.bytes;
+              pass_n = gs.nodes;
+            }
             if (zskip > goal_dups) {   // a different node shares the goal's grid cell: record everything
-              kraw = scan2q<true, true>(xq, n, rppk::quant16(c, nx, ny), thr_gi, pf_sq, hits, sh, pf_ni, pf_best, pf_second);
+              kraw = scan2g<true, true>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, pf_sq, hits, sh, pf_ni, pf_best,
+                                        pf_second);
               zskip = 0;
-              ST_ADD(S_AB, 4 * (int64_t)n);
+              ST_ADD(S_AB, gs.bytes);
             }
             pf_bq = (uint32_t)pf_best;
             pf_grp = pf_ni;
@@ -1814,17 +2173,19 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
           int d0;
           double d1, d2;
           if (Q16) {
-            kraw = scan2q<true, false>(xq, n, rppk::quant16(c, nx, ny), thr_gi, 0u, hits, sh, d0, d1, d2, goal_q, zgate,
-                                       &zskip);
+            kraw = scan2g<true, false>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, 0u, hits, sh, d0, d1, d2, goal_q,
+                                       zgate, &zskip);
+            pass_b = gs.bytes;
+            pass_n = gs.nodes;
             if (zskip > goal_dups) {
-              kraw = scan2q<true, false>(xq, n, rppk::quant16(c, nx, ny), thr_gi, 0u, hits, sh, d0, d1, d2);
+              kraw = scan2g<true, false>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, 0u, hits, sh, d0, d1, d2);
               zskip = 0;
-              ST_ADD(S_AB, 4 * (int64_t)n);
+              ST_ADD(S_AB, gs.bytes);
             }
           } else
             kraw = scan2f<true, false>(xf, yf, n, (float)nx, (float)ny, thr_f, 0.f, 0.f, hits, sh, d0, d1, d2);
         }
-        ST_ADD(S_AB, (Q16 ? 4 : 8) * (int64_t)n + 16 * (int64_t)kraw + 16);
+        ST_ADD(S_AB, (Q16 ? pass_b : 8 * (int64_t)n) + 16 * (int64_t)kraw + 16);
       } else {
         if (do_pf) {
           take_next_sample();
@@ -1839,7 +2200,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
         }
         ST_ADD(S_AB, 16 * (int64_t)n);
       }
-      ST_ADD(S_SN, n);
+      ST_ADD(S_SN, pass_n);
       ST_ADD(S_AB2, 16 * (int64_t)n);
       // Fold of the node this iteration appends (position ax, ay, index aidx) into the pass's provisional nearest node
       // of the next sample: margin test in the distance metric, the appended node's distance is exact.  Returns 1 with
@@ -1981,6 +2342,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
             if (!(sh.uflag[es] & 4)) {
               // steer(new -> node) stopped short of the node: node_list[i] = edge_node moves it (rare; lane 0, vector path)
               moved_now = 1;
+              const uint32_t q_old = gs.ok ? rppk::quant16(c, sh.ux[es], sh.uy[es]) : 0u;   // where the index has it
               if (tid == 0) {
                 rpp::steer(&sh.e0, wx, wy, sh.ux[es], sh.uy[es], rpp::dinf(), c.res);
                 x[u] = sh.e0.ex;
@@ -2007,6 +2369,12 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
                 elen[u] = rpp::py_hypot(sh.e0.ex - wx, sh.e0.ey - wy);
                 for (int ch = sh.ufc[es]; ch >= 0; ch = next_sib[ch])
                   elen[ch] = rpp::py_hypot(x[ch] - sh.e0.ex, y[ch] - sh.e0.ey);
+              }
+              if (NW == 1 && gs.ok) {   // the moved node changes cell (the index keeps it at the new xq[] value)
+                lds_barrier();
+                grid_remove(gs, u, q_old);
+                if (gs.ok) grid_insert(gs, u, rppk::quant16(c, sh.ux[es], sh.uy[es]));
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
               }
             }
             const double ec = sh.uval[es];
@@ -2059,6 +2427,13 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
           if (f >= 0) prev_sib[f] = newidx;
           first_child[wparent] = newidx;
         }
+        // the index: an exact goal duplicate (first_goal >= 0 already) stays out of it, counted instead
+        if (gs.ok) {
+          if (first_goal >= 0 && wx == gx && wy == gy)
+            gs.excl++;
+          else
+            grid_insert(gs, newidx, rppk::quant16(c, wx, wy));
+        }
         lds_barrier();
         PH(9);
         ST_ADD(S_RW, sh.n_rw);
@@ -2081,12 +2456,19 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
           rppk::link_child(parent, first_child, next_sib, prev_sib, n, ni);
           sh.moved = 0;
         }
+        if (gs.ok) {
+          if (first_goal >= 0 && nx == gx && ny == gy)
+            gs.excl++;
+          else
+            grid_insert(gs, n, rppk::quant16(c, nx, ny));
+        }
         n++;
         lds_barrier();
       }
       const int moved = uni_i(sh.moved);
       if (F32) {
         if (moved & 2) first_goal = -2;   // a node on the goal moved (or one moved onto it): lowest index unknown
+        if ((moved & 2) && gs.excl > 0) gs.ok = 0;   // ... and the goal duplicates the index left out count as nodes again
         if (wx == gx && wy == gy) {
           if (first_goal == -1) {
             first_goal = n - 1;

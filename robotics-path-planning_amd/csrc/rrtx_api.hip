@@ -331,6 +331,19 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
   if (p->algo == RRTX_ALGO_RRT_STAR && p->search_until_max_iter) {
     if ((rc = dalloc(h, &c.elen, tot))) return rc;   // cached parent-edge lengths (cost propagation)
     if ((rc = dalloc(h, &c.xq, tot))) return rc;     // 16-bit mirror (first stage of the streaming pass)
+    // grid index of the mirror (DESIGN 5.1 "grid index"): cells sized for about 6 nodes each at the final tree size,
+    // 512 grid steps at the least (128 x 128 cells); an overflow block per 128 nodes of capacity
+    int gsh = 9;
+    while (gsh < 15 && (int64_t)(65536 >> gsh) * (65536 >> gsh) * 6 > cap) gsh++;
+    c.gsh = gsh;
+    c.gn = 65536 >> gsh;
+    c.gcells = c.gn * c.gn;
+    c.gpool_blocks = (int32_t)(cap / 128 + 16);
+    const size_t gc = (size_t)c.gcells * h->n_inst;
+    if ((rc = dalloc(h, &c.gcnt, gc))) return rc;
+    if ((rc = dalloc(h, &c.gblk, gc))) return rc;
+    if ((rc = dalloc(h, &c.gent, gc * rppk::GRID_CAP0))) return rc;
+    if ((rc = dalloc(h, &c.gpool, (size_t)c.gpool_blocks * rppk::GRID_CAP1 * h->n_inst))) return rc;
   }
   if (p->algo == RRTX_ALGO_INFORMED)
     if ((rc = dalloc(h, &c.xq, tot))) return rc;     // 16-bit mirror: the one pass per iteration of the rrt_07 kernel
@@ -635,6 +648,12 @@ int rrtx_plan_begin(rrtx_handle* h) {
   // RRTX_SPEC2=0: one pass per iteration)
   c.spec2 = 8;
   if (const char* e = getenv("RRTX_SPEC2")) c.spec2 = atoi(e) > 0 ? atoi(e) : 0;
+  // rrt_04 kernel, one-wave shape: near and nearest queries from the grid index (RRTX_GRID=0: the streaming pass only);
+  // below grid_min nodes a pass streams (RRTX_GRID_MIN: test knob, 0 = from the first node)
+  c.grid = c.gcnt != nullptr;
+  if (const char* e = getenv("RRTX_GRID")) c.grid = c.grid && atoi(e) != 0;
+  c.grid_min = 4096;
+  if (const char* e = getenv("RRTX_GRID_MIN")) c.grid_min = atoi(e) > 0 ? atoi(e) : 0;
   // The staged per-instance start state (RNG, start / goal) lives on the device too: uploaded when the host changed it,
   // copied device -> device at every plan (2.7 KB per instance: 44 MB of pageable-memory upload per plan of 16 384 instances)
   if (!h->d_inst0) {
