@@ -115,9 +115,9 @@ typedef struct rrtx_stats {
   int64_t propagated;        /* nodes rewritten by propagate_cost_to_leaves (rrt_04:1379-1384) */
   int64_t scan_nodes;        /* nodes visited by nearest/near/goal scans */
   int64_t algorithmic_bytes; /* bytes this implementation's algorithm must move: RRTX_ALGO_RRT_STAR 4*n per pass over the
-                                16-bit coordinate mirror (8*n per f32-mirror pass, 16*n per f64 pass: the fallbacks,
-                                RRTX_Q16=0 / RRTX_F32=0 and the other algorithms) + 16 per hit gathered + 48*k + 24*M +
-                                44; the near pass of iteration i also serves the nearest query of i+1 */
+                                16-bit coordinate mirror (16*n per f64 pass: its nearest-query fallbacks and the other
+                                algorithms) + 16 per hit gathered + 48*k + 24*M + 44; the near pass of iteration i also
+                                serves the nearest query of i+1 */
   int64_t exact_rescans;     /* nearest scans re-done with exact ** 2 (tie within filter margin) */
   int64_t total_nodes;
   int64_t launches;          /* kernel launches */
@@ -125,7 +125,8 @@ typedef struct rrtx_stats {
   double plan_ms;            /* host wall time of rrtx_plan */
   int64_t algorithmic_bytes_two_scan; /* SURVEY.md 8d formula as written: 32*n + 48*k + 24*M + 28 per accepted iteration */
   int64_t near_unique_max;   /* largest number of distinct near candidates any iteration of any instance produced */
-  int64_t f32_fallbacks;     /* nearest queries the f32-mirror pass could not decide (repeated with the f64 pass) */
+  int64_t f32_fallbacks;     /* RRTX_ALGO_RRT_STAR iteration kernel: nearest queries the 16-bit stage could not decide and
+                                that took the f64 pass (a saturated grid distance: the first iterations of a tree) */
   int64_t q16_fallbacks;     /* nearest queries the 16-bit first stage could not decide on grid distances (decided by a
                                 second 16-bit pass that collects the candidates + their f64 coordinates) */
   /* the DOMINANT kernel alone (RRTX_ALGO_RRT_STAR with search_until_max_iter: rrt_star_kernel_v2, whose launches a
@@ -139,7 +140,7 @@ typedef struct rrtx_stats {
   int32_t main_shape;        /* threads per workgroup (= per planning instance) of the dominant kernel as launched:
                                 RRTX_ALGO_RRT_STAR iteration kernel 64 / 128 / 256 (picked from the instance count, the
                                 obstacle count, the estimated near-set size and RRTX_TPB); the other planners' fixed shape */
-  int32_t main_f32;          /* RRTX_ALGO_RRT_STAR iteration kernel: 1 = f32-mirror instantiation (<true>), 0 = f64 passes */
+  int32_t main_f32;          /* kept for the layout: 1 whenever the RRTX_ALGO_RRT_STAR iteration kernel ran, else 0 */
   int64_t passes_shared;     /* RRTX_ALGO_RRT_STAR iteration kernel, 64-thread shape: iterations whose near query was answered
                                 by the streaming pass of an earlier iteration (the ball speculated about the sample, on which
                                 steer() snaps the new node once the tree is dense; up to three iterations ride on one pass):

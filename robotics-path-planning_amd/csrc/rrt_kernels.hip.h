@@ -92,7 +92,7 @@ struct Ctx {
   double *tr_rx, *tr_ry;
   int32_t *tr_near, *tr_nn;
   int32_t* tr_kind;   // per iteration: 0 no node appended, 1 the extension itself (rrt_01:85-96, rrt_04:1066-1067), 2 under a chosen parent (:1062-1065)
-  // f32 mirror of x[], y[] (prefilter of the streaming pass, rrt_star_v2_body.inc) and its distance margin
+  // f32 mirror of x[], y[] (prefilter of the rrt_07 kernel's streaming passes, rrt_informed.hip.h) and its distance margin
   float *xf, *yf;
   double f32_m;
   // 16-bit fixed-point mirror, 4 bytes per node: (x16 | y16 << 16), q = rint((coord - q_lo) * q_inv) - 32768; first stage of
@@ -302,10 +302,11 @@ __device__ __forceinline__ int scan_hits(const double* __restrict__ x, const dou
 }
 
 // ---------------------------------------------------------------------------
-// The same two passes over the f32 mirror xf[], yf[] (8 bytes per node; lane -> 4 adjacent nodes).  Distances from
-// the mirror differ from the true ones by less than Ctx::f32_m, so the callers treat the results as candidates:
-// the nearest index is final only if the runner-up is more than 2m further (distance metric), threshold hits are
-// re-tested from the f64 coordinates.  See scan2f in rrt_star_v2_body.inc for the bound.
+// The same two passes over the f32 mirror xf[], yf[] (8 bytes per node; lane -> 4 adjacent nodes), for the rrt_07
+// kernel (rrt_informed.hip.h).  Distances from the mirror differ from the true ones by less than Ctx::f32_m (coordinate
+// rounding 2^-24 relative to the largest coordinate magnitude, plus f32 arithmetic; the host sets f32_m = 2^-20 *
+// max|coordinate|), so the callers treat the results as candidates: the nearest index is final only if the runner-up
+// is more than 2m further (distance metric), threshold hits are re-tested from the f64 coordinates.
 typedef float v4f_k __attribute__((ext_vector_type(4)));
 constexpr int WAVE_STRIDE_F = 256 * UNROLL;
 template <class SH>

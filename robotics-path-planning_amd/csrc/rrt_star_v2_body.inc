@@ -288,104 +288,6 @@ __device__ __forceinline__ void hit_at2(const double* __restrict__ x, const doub
   }
 }
 
-// ---- f32-mirror prefilter --------------------------------------------------------------------------------------
-// The same pass over xf[], yf[] (float copies of the coordinates, 8 bytes per node instead of 16).  Distances
-// computed from the copies differ from the true ones by less than c.f32_m (coordinate rounding 2^-24 relative to
-// the largest coordinate magnitude, plus f32 arithmetic; the host sets f32_m = 2^-20 * max|coordinate|), so
-//  NEAR:    {i : d'_i <= r + m} is a superset of the ball; every hit is re-tested from the f64 coordinates with
-//           the exact replica (build_candidates), exactly as the f64 filter's hits are;
-//  NEAREST: the argmin of d' is the reference's nearest node whenever the runner-up is more than 2m further;
-//           otherwise the caller repeats the query with the f64 pass.
-// Lane -> 4 adjacent nodes (16-byte loads), wave-contiguous ranges, ascending hit order as in scan2.
-typedef float v4f __attribute__((ext_vector_type(4)));
-constexpr int WAVE_STRIDE_F = 256 * UNROLL;
-constexpr int HWF = HW * (int)(sizeof(Hit) / sizeof(int32_t));   // hit indices per wave captured in LDS
-
-template <bool NEAR, bool NEAREST>
-__device__ __forceinline__ int scan2f(const float* __restrict__ xf, const float* __restrict__ yf, int n, float qx,
-                                      float qy, float thr, float sx, float sy, int32_t* __restrict__ hits, Sh2& sh,
-                                      int& ni, double& gbest, double& gsecond) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int per = roundup_i((n + NW - 1) / NW, WAVE_STRIDE_F);
-  const int ws = w * per;
-  const int we = ws + per;
-  const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  int32_t* lhit = reinterpret_cast<int32_t*>(sh.u.hit) + w * HWF;
-  int cnt = 0;
-  float best = __builtin_inff(), second = __builtin_inff();
-  int bidx = 0x7fffffff;
-  for (int base = ws; base < we && base < n; base += WAVE_STRIDE_F) {
-    v4f xv[UNROLL], yv[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; u++) {
-      const int i0 = base + u * 256 + lane * 4;
-      xv[u] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(xf + i0));
-      yv[u] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(yf + i0));
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; u++) {
-      const int i0 = base + u * 256 + lane * 4;
-      if (NEAREST) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          const float dx = xv[u][j] - sx, dy = yv[u][j] - sy;
-          const float d = __builtin_fmaf(dx, dx, dy * dy);
-          const bool lt = d < best;
-          second = lt ? best : (d < second ? d : second);
-          bidx = lt ? i0 + j : bidx;
-          best = lt ? d : best;
-        }
-      }
-      if (NEAR) {
-        bool hh[4];
-        uint64_t mm[4];
-        uint64_t any = 0ull;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          const float dx = xv[u][j] - qx, dy = yv[u][j] - qy;
-          hh[j] = __builtin_fmaf(dx, dx, dy * dy) <= thr;
-          mm[j] = __ballot(hh[j]);
-          any |= mm[j];
-        }
-        if (any != 0ull) {
-          int pos = cnt;
-          int tot = 0;
-#pragma unroll
-          for (int j = 0; j < 4; j++) {
-            pos += __popcll(mm[j] & lt_mask);
-            tot += __popcll(mm[j]);
-          }
-#pragma unroll
-          for (int j = 0; j < 4; j++) {
-            if (hh[j]) {
-              hits[ws + pos] = i0 + j;
-              if (pos < HWF) lhit[pos] = i0 + j;
-              pos++;
-            }
-          }
-          cnt += tot;
-        }
-      }
-    }
-  }
-  if (NEAR && lane == 0) {
-    sh.wave_cnt[w] = cnt;
-    sh.wave_start[w] = ws;
-  }
-  if (NEAREST) {
-    double t0, t1;
-    block_argmin_xy((double)best, bidx, (double)second, 0.0, 0.0, sh, gbest, ni, gsecond, t0, t1);
-  } else {
-    lds_barrier();
-  }
-  int total = 0;
-  if (NEAR) {
-#pragma unroll
-    for (int k = 0; k < NW; k++) total += sh.wave_cnt[k];
-  }
-  return total;
-}
-
 // ---- 16-bit first stage (integer form) -----------------------------------------------------------------------
 // The same pass over xq[] = (x16 | y16 << 16), 4 bytes per node: q = rint((coord - q_lo) * q_inv) - 32768 as a signed
 // 16-bit value (rppk::quant16).  The query points are rounded to the same grid, so a squared distance is exact integer
@@ -396,8 +298,9 @@ __device__ __forceinline__ int scan2f(const float* __restrict__ xf, const float*
 // (more than 32767 steps: half the map) reports a LOWER bound >= 32767^2 = QSAT of the grid distance, which keeps both
 // uses sound: near-ball hits ({d2 <= (r + q_m)^2}: a superset, every hit re-tested from the f64 coordinates) never
 // saturate, and a nearest result is accepted only when best < QSAT (the winner itself is exact) and the runner-up --
-// exact or a lower bound -- is more than 2 q_m further; otherwise the f32 pass repeats the query (about 3 % of them),
-// and the f64 pass after that.
+// exact or a lower bound -- is more than 2 q_m further; otherwise a second 16-bit pass gathers every node within 2 q_m
+// of the best grid distance and decides on their f64 coordinates, and a query it cannot take (a saturated best: the
+// first iterations of a tree) goes to the f64 pass (scan2).
 // Streaming: each lane keeps QD 16-byte non-temporal loads in flight (a ring: the slot just consumed is re-issued QD
 // slots ahead), so a wave has QD KiB outstanding all through the pass instead of a load-wait-compute cadence.  QD = 6:
 // same-box A/B of 3 / 4 / 5 / 6 / 8 / 12 gave 6 the best step time twice (3..8 within 3-6 % of each other, 12 clearly
@@ -419,16 +322,13 @@ constexpr int QD1 = RRT2_QDEPTH1;   // ring depth of the pass with further query
 constexpr int QD0 = RRT2_QDEPTH;    // ... of every other pass
 constexpr int QSLOT = 256;                       // nodes per wave and ring slot
 constexpr uint32_t QSAT = 32767u * 32767u;
+constexpr int HWF = HW * (int)(sizeof(Hit) / sizeof(int32_t));   // hit indices per wave captured in LDS
 
 __device__ __forceinline__ uint32_t qdist(uint32_t node, uint32_t query) {
   const s2v d = __builtin_elementwise_sub_sat(__builtin_bit_cast(s2v, node), __builtin_bit_cast(s2v, query));
-#ifdef RRT2_DOT2_BUILTIN
-  return (uint32_t)__builtin_amdgcn_sdot2(d, d, 0, false);   // selected as v_mov 0 + v_dot2c (the accumulating VOP2 form)
-#else
   uint32_t r;
   asm("v_dot2_i32_i16 %0, %1, %1, 0" : "=v"(r) : "v"(d));    // the three-operand form: one instruction
   return r;
-#endif
 }
 __device__ __forceinline__ uint32_t umin3(uint32_t a, uint32_t b, uint32_t c) { return min(min(a, b), c); }
 __device__ __forceinline__ uint32_t umed3(uint32_t a, uint32_t b, uint32_t c) { return max(min(a, b), min(max(a, b), c)); }
@@ -1043,21 +943,9 @@ __device__ __forceinline__ bool resolve_group(const Ctx& c, int grp, int n, doub
   return true;
 }
 
-// h-th entry of the raw hit list, from the global list only (valid after the LDS capture has been overwritten)
-__device__ __forceinline__ int raw_hit_index(const int32_t* __restrict__ hits, const Sh2& sh, int h) {
-  int k = 0;
-#pragma unroll
-  for (int j = 0; j < NW - 1; j++) {
-    if (k == j && h >= sh.wave_cnt[j]) {
-      h -= sh.wave_cnt[j];
-      k = j + 1;
-    }
-  }
-  return hits[sh.wave_start[k] + h];
-}
-
-// h-th hit of the f32 pass: index from the LDS capture (else the global list), coordinates gathered in f64
-__device__ __forceinline__ void hit_at2f(const double* __restrict__ x, const double* __restrict__ y,
+// h-th hit of a 16-bit pass (scan2q, the grid index, a ride): index from the LDS capture (else the global list),
+// coordinates gathered in f64
+__device__ __forceinline__ void hit_at2q(const double* __restrict__ x, const double* __restrict__ y,
                                          const int32_t* __restrict__ hits, const Sh2& sh, int h, int& idx, double& hx,
                                          double& hy) {
   int k = 0;
@@ -1076,12 +964,11 @@ __device__ __forceinline__ void hit_at2f(const double* __restrict__ x, const dou
 // Exact re-check (dx**2 + dy**2 <= r**2 with the reference's libm pow) + the `.index` de-dup of rrt_04:1337,
 // producing the candidate records.  cost / first_child of each distinct candidate are requested here and first
 // used after the edge evaluation.
-template <bool F32>
 __device__ __forceinline__ void build_candidates(const double* __restrict__ x, const double* __restrict__ y,
                                                  const double* __restrict__ cost,
                                                  const int32_t* __restrict__ first_child, double qx, double qy,
                                                  double thr_exact, const int32_t* hits, int kraw, Sh2& sh,
-                                                 int& pend_p, double& pend_cost, int& pend_fc, long long* sub) {
+                                                 int& pend_p, double& pend_cost, int& pend_fc) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   pend_p = -1;
   pend_cost = 0.0;
@@ -1103,9 +990,6 @@ __device__ __forceinline__ void build_candidates(const double* __restrict__ x, c
   constexpr int NFAST = TPB < NU ? TPB : NU;
   {
     bool exact = false;
-#ifdef RRTX_PH_DEDUP
-    long long tq0 = __builtin_amdgcn_s_memtime();
-#endif
     for (int base = 0; base < kraw && !exact; base += NFAST) {
       const int h = base + tid;
       const bool act = tid < NFAST && h < kraw;
@@ -1113,10 +997,7 @@ __device__ __forceinline__ void build_candidates(const double* __restrict__ x, c
       double vf = 0.0, hx = 0.0, hy = 0.0;
       int st = 0;   // 0 outside, 1 inside, 2 in the band
       if (act) {
-        if (F32)
-          hit_at2f(x, y, hits, sh, h, idx, hx, hy);
-        else
-          hit_at2(x, y, hits, sh, h, idx, hx, hy);
+        hit_at2q(x, y, hits, sh, h, idx, hx, hy);
         vf = rpp::fast_d2(hx - qx, hy - qy);
         st = vf <= thr_exact * (1.0 - FILTER_EPS) ? 1 : (vf > thr_exact * (1.0 + FILTER_EPS) ? 0 : 2);
         sh.cval[tid] = vf;
@@ -1196,9 +1077,6 @@ __device__ __forceinline__ void build_candidates(const double* __restrict__ x, c
       }
       lds_barrier();
     }
-#ifdef RRTX_PH_DEDUP
-    if (tid == 0) sub[0] += __builtin_amdgcn_s_memtime() - tq0;
-#endif
     if (!exact) return;
     pend_p = -1;
     if (tid == 0) {
@@ -1213,10 +1091,7 @@ __device__ __forceinline__ void build_candidates(const double* __restrict__ x, c
     double v = 0.0, hx = 0.0, hy = 0.0;
     bool valid = false;
     if (h < kraw) {
-      if (F32)
-        hit_at2f(x, y, hits, sh, h, idx, hx, hy);
-      else
-        hit_at2(x, y, hits, sh, h, idx, hx, hy);
+      hit_at2q(x, y, hits, sh, h, idx, hx, hy);
       v = rpp::py_d2(hx - qx, hy - qy);
       valid = v <= thr_exact;
     }
@@ -1327,8 +1202,7 @@ __device__ __forceinline__ int edge_hits_obstacle_band(const rpp::Edge& e, bool 
 // An edge with either decision in doubt -- in practice the edge from the NEAREST node, whose length is 8 x 0.25 = 2.0 give
 // or take an ULP, in about every second iteration -- is evaluated again exactly as before (atan2 / cos / sin replicas, the
 // sequential additions, the exact test), by its own lane alone instead of all candidates' lanes diverging in the replicas.
-__device__ __forceinline__ void eval_edges_dual2(const Ctx& c, int nu, double nx, double ny, Sh2& sh,
-                                                 long long* sub) {
+__device__ __forceinline__ void eval_edges_dual2(const Ctx& c, int nu, double nx, double ny, Sh2& sh) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   // 4 waves: direction = w>>1 (even waves work, odd ones only take part in the pair loops); 2 waves: direction = w;
   // 1 wave: direction = lane>>5 (both half-waves run the same instruction stream)
@@ -1539,8 +1413,8 @@ __device__ __forceinline__ int propagate_scalar(double* __restrict__ cost, const
 }
 
 // ---------------------------------------------------------------------------
-// F32: stream the float mirror (scan2f) and fall back to the f64 pass when the margin test cannot decide.
-template <bool F32>
+// Near and nearest queries start at the 16-bit mirror xq[] (the grid index in the one-wave shape, else streaming:
+// scan2g); a nearest query that stage cannot decide goes to the f64 pass (scan2), then the exact ** 2 rescan.
 __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters) {
   __shared__ Sh2 sh;
   const int inst = c.inst_map ? c.inst_map[blockIdx.x] : blockIdx.x;
@@ -1557,18 +1431,14 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   int32_t* prev_sib = c.prev_sib + off;
   int32_t* hits = c.hits + off;
   int32_t* stack = c.stack + off;
-  float* __restrict__ xf = F32 ? c.xf + off : nullptr;
-  float* __restrict__ yf = F32 ? c.yf + off : nullptr;
   double* __restrict__ elen = c.elen + off;
-  uint32_t* __restrict__ xq = (F32 && c.xq) ? c.xq + off : nullptr;
-  const bool Q16 = xq != nullptr;
+  uint32_t* __restrict__ xq = c.xq + off;
   const double qm = c.q_m;
   const double qinv = c.q_inv;   // world -> grid units of the 16-bit mirror
   const double qm_grid = c.q_m * c.q_inv;
-  const uint32_t goal_q = (F32 && c.xq) ? rppk::quant16(c, I->goal[0], I->goal[1]) : 0u;   // the goal's grid cell
+  const uint32_t goal_q = rppk::quant16(c, I->goal[0], I->goal[1]);   // the goal's grid cell
   int q_amb = 0;            // the fused 16-bit pass could not decide the pending nearest query ...
   uint32_t q_amb_bq = 0u;   // ... and this bounds the nearest node's squared grid distance (candidate pass, below)
-  const double fm = c.f32_m;
   int first_goal = I->first_goal;
   int goal_dups = I->goal_dups;   // exact duplicates of node first_goal appended so far (valid while first_goal >= 0)
 
@@ -1590,7 +1460,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   GridS gs = {};
   gs.ok = 0;
   if constexpr (NW == 1) {
-    if (F32 && Q16 && c.grid) {
+    if (c.grid) {
       const int64_t gi = (int64_t)inst;
       gs.cnt = c.gcnt + gi * c.gcells;
       gs.blk = c.gblk + gi * c.gcells;
@@ -1635,7 +1505,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   constexpr int SPEC_CAPS = 2048 / (KSM > 0 ? KSM : 1);   // hits[stride - 2048, stride): the balls' hit lists
   const int spec_base = (int)c.stride - 2048;
   double* __restrict__ G = reinterpret_cast<double*>(hits + ((int)c.stride - 2560));
-  const int KS_RUN = ((NW == 1) && F32 && Q16) ? (c.spec2 < KSM ? c.spec2 : KSM) : 0;
+  const int KS_RUN = NW == 1 ? (c.spec2 < KSM ? c.spec2 : KSM) : 0;
   const bool SPEC_ON = KS_RUN > 0;
   constexpr int KA = KSM > 0 ? KSM : 1;
   static_assert(KSM <= 3, "rings of four");
@@ -1714,7 +1584,6 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
     o_bq = bq;
     return bq < QSAT ? 2 : 0;
   };
-  long long sub_[3] = {0, 0, 0};
   PH_DECL
 
   for (int step = 0; step < iters && it < c.max_iter && !stop; step++, it++) {
@@ -1735,123 +1604,105 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
     const double r2b = SPEC_ON ? c.r2tab[n + 2] : 0.0;   // ... and for the next one (speculated balls: the largest they can need)
     if (!have_nearest) {
       bool done = false;
-      if (F32) {
-        if (first_goal >= 0 && rx == gx && ry == gy) {
-          // the sample is the goal and nodes lie exactly on it: d == 0 there, min() keeps the lowest index (:1200)
-          ni = first_goal;
-          nqx = gx;
-          nqy = gy;
-          gbest = 0.0;
-          gsecond = rpp::dinf();
-          done = true;
-        } else {
-          int fi;
+      if (first_goal >= 0 && rx == gx && ry == gy) {
+        // the sample is the goal and nodes lie exactly on it: d == 0 there, min() keeps the lowest index (:1200)
+        ni = first_goal;
+        nqx = gx;
+        nqy = gy;
+        gbest = 0.0;
+        gsecond = rpp::dinf();
+        done = true;
+      } else {
+        const uint32_t sq = rppk::quant16(c, rx, ry);
+        // upper bound (squared grid units) of the nearest node's grid distance: from the fused pass of the previous
+        // iteration when it was the one that could not decide (q_amb), else from a nearest pass now
+        uint32_t bq = q_amb_bq;
+        bool bound = q_amb != 0;
+        if (!bound) {
+          int grp;
           double fb, fs;
-          if (Q16) {
-            const uint32_t sq = rppk::quant16(c, rx, ry);
-            // upper bound (squared grid units) of the nearest node's grid distance: from the fused pass of the previous
-            // iteration when it was the one that could not decide (q_amb), else from a nearest pass now
-            uint32_t bq = q_amb_bq;
-            bool bound = q_amb != 0;
-            if (!bound) {
-              int grp;
-              scan2g<false, true>(gs, (int)(__builtin_sqrt(r2) * qinv) + 1, xq, n, 0u, 0u, sq, hits, sh, grp, fb, fs);
-              ST_ADD(S_SN, gs.nodes);
-              ST_ADD(S_AB, gs.bytes + 64);
-              if (fb < (double)QSAT) {
-                // accepted when the winner is exact (not saturated) and the runner-up is more than 2 q_m further
-                if ((__builtin_sqrt(fs) - __builtin_sqrt(fb)) > 2.0 * qm_grid) {
-                  const int gl = grp + (tid & 3);
-                  const double hx = x[gl], hy = y[gl];   // the group's nodes (padding past n is readable)
-                  if (resolve_group(c, grp, n, hx, hy, sq, (uint32_t)fb, ni, nqx, nqy)) {
-                    gbest = 1.0;
-                    gsecond = rpp::dinf();
-                    done = true;
-                  }
-                }
-                if (!done) {
-                  bq = (uint32_t)fb;
-                  bound = true;
-                }
-              }
-            }
-            if (!done && bound) {
-              // Undecided at 16 bits: the true nearest node lies within 2 q_m of the best grid distance, so a second
-              // 16-bit pass collects every node inside that ball (a handful) and the decision is made on their f64
-              // coordinates -- 4 bytes per node instead of the 8 + 16 of the f32 and f64 passes.
-              const double rb = __builtin_sqrt((double)bq) + 2.0 * qm_grid;
-              const double tb = rb * rb + 1.0;
-              if (tb < (double)QSAT) {
-                ST_ADD(S_QA, 1);
-                int d0;
-                double d1, d2;
-                const int kc = scan2g<true, false>(gs, 0, xq, n, sq, (uint32_t)tb, 0u, hits, sh, d0, d1, d2);
-                ST_ADD(S_SN, gs.nodes);
-                ST_ADD(S_AB, gs.bytes + 16 * (int64_t)kc);
-                double best = rpp::dinf(), second = rpp::dinf(), bx = 0.0, by = 0.0;
-                int bidx = 0x7fffffff;
-                for (int h = tid; h < kc; h += TPB) {
-                  int idx;
-                  double hx, hy;
-                  hit_at2f(x, y, hits, sh, h, idx, hx, hy);
-                  const double d = rpp::fast_d2(hx - rx, hy - ry);
-                  if (d < best || (d == best && idx < bidx)) {
-                    second = best;
-                    best = d;
-                    bidx = idx;
-                    bx = hx;
-                    by = hy;
-                  } else if (d < second) {
-                    second = d;
-                  }
-                }
-                lds_barrier();
-                block_argmin_xy(best, bidx, second, bx, by, sh, gbest, ni, gsecond, nqx, nqy);
-                if (gbest != 0.0 && gsecond <= gbest * (1.0 + FILTER_EPS)) {
-                  // candidates inside the filter margin of the minimum: the exact ** 2 decides, lowest index on ties (:1200)
-                  ST_ADD(S_EX, 1);
-                  const double lim = gbest * (1.0 + FILTER_EPS);
-                  best = rpp::dinf();
-                  bidx = 0x7fffffff;
-                  for (int h = tid; h < kc; h += TPB) {
-                    int idx;
-                    double hx, hy;
-                    hit_at2f(x, y, hits, sh, h, idx, hx, hy);
-                    if (rpp::fast_d2(hx - rx, hy - ry) > lim) continue;
-                    const double d = rpp::py_d2(hx - rx, hy - ry);
-                    if (d < best || (d == best && idx < bidx)) {
-                      best = d;
-                      bidx = idx;
-                      bx = hx;
-                      by = hy;
-                    }
-                  }
-                  lds_barrier();
-                  block_argmin_xy(best, bidx, rpp::dinf(), bx, by, sh, d1, ni, d2, nqx, nqy);
-                }
+          scan2g<false, true>(gs, (int)(__builtin_sqrt(r2) * qinv) + 1, xq, n, 0u, 0u, sq, hits, sh, grp, fb, fs);
+          ST_ADD(S_SN, gs.nodes);
+          ST_ADD(S_AB, gs.bytes + 64);
+          if (fb < (double)QSAT) {
+            // accepted when the winner is exact (not saturated) and the runner-up is more than 2 q_m further
+            if ((__builtin_sqrt(fs) - __builtin_sqrt(fb)) > 2.0 * qm_grid) {
+              const int gl = grp + (tid & 3);
+              const double hx = x[gl], hy = y[gl];   // the group's nodes (padding past n is readable)
+              if (resolve_group(c, grp, n, hx, hy, sq, (uint32_t)fb, ni, nqx, nqy)) {
                 gbest = 1.0;
                 gsecond = rpp::dinf();
                 done = true;
               }
             }
-          }
-          if (!done) {
-            scan2f<false, true>(xf, yf, n, 0.f, 0.f, 0.f, (float)rx, (float)ry, hits, sh, fi, fb, fs);
-            ST_ADD(S_SN, n);
-            ST_ADD(S_AB, 8 * (int64_t)n + 16);
-            if (__builtin_sqrt(fs) - __builtin_sqrt(fb) > 2.0 * fm) {
-              ni = fi;
-              nqx = x[fi];
-              nqy = y[fi];
-              gbest = 1.0;
-              gsecond = rpp::dinf();
-              done = true;
+            if (!done) {
+              bq = (uint32_t)fb;
+              bound = true;
             }
+          }
+        }
+        if (!done && bound) {
+          // Undecided at 16 bits: the true nearest node lies within 2 q_m of the best grid distance, so a second
+          // 16-bit pass collects every node inside that ball (a handful) and the decision is made on their f64
+          // coordinates -- 4 bytes per node instead of the 16 of the f64 pass.
+          const double rb = __builtin_sqrt((double)bq) + 2.0 * qm_grid;
+          const double tb = rb * rb + 1.0;
+          if (tb < (double)QSAT) {
+            ST_ADD(S_QA, 1);
+            int d0;
+            double d1, d2;
+            const int kc = scan2g<true, false>(gs, 0, xq, n, sq, (uint32_t)tb, 0u, hits, sh, d0, d1, d2);
+            ST_ADD(S_SN, gs.nodes);
+            ST_ADD(S_AB, gs.bytes + 16 * (int64_t)kc);
+            double best = rpp::dinf(), second = rpp::dinf(), bx = 0.0, by = 0.0;
+            int bidx = 0x7fffffff;
+            for (int h = tid; h < kc; h += TPB) {
+              int idx;
+              double hx, hy;
+              hit_at2q(x, y, hits, sh, h, idx, hx, hy);
+              const double d = rpp::fast_d2(hx - rx, hy - ry);
+              if (d < best || (d == best && idx < bidx)) {
+                second = best;
+                best = d;
+                bidx = idx;
+                bx = hx;
+                by = hy;
+              } else if (d < second) {
+                second = d;
+              }
+            }
+            lds_barrier();
+            block_argmin_xy(best, bidx, second, bx, by, sh, gbest, ni, gsecond, nqx, nqy);
+            if (gbest != 0.0 && gsecond <= gbest * (1.0 + FILTER_EPS)) {
+              // candidates inside the filter margin of the minimum: the exact ** 2 decides, lowest index on ties (:1200)
+              ST_ADD(S_EX, 1);
+              const double lim = gbest * (1.0 + FILTER_EPS);
+              best = rpp::dinf();
+              bidx = 0x7fffffff;
+              for (int h = tid; h < kc; h += TPB) {
+                int idx;
+                double hx, hy;
+                hit_at2q(x, y, hits, sh, h, idx, hx, hy);
+                if (rpp::fast_d2(hx - rx, hy - ry) > lim) continue;
+                const double d = rpp::py_d2(hx - rx, hy - ry);
+                if (d < best || (d == best && idx < bidx)) {
+                  best = d;
+                  bidx = idx;
+                  bx = hx;
+                  by = hy;
+                }
+              }
+              lds_barrier();
+              block_argmin_xy(best, bidx, rpp::dinf(), bx, by, sh, d1, ni, d2, nqx, nqy);
+            }
+            gbest = 1.0;
+            gsecond = rpp::dinf();
+            done = true;
           }
         }
       }
       if (!done) {
-        if (F32) ST_ADD(S_FB, 1);
+        ST_ADD(S_FB, 1);
         scan2<false, true>(x, y, n, 0.0, 0.0, 0.0, rx, ry, hits, sh, ni, gbest, gsecond, nqx, nqy);
         ST_ADD(S_SN, n);
         ST_ADD(S_AB, 16 * (int64_t)n);
@@ -1892,45 +1743,42 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
     // straight line decide the collision test unless an obstacle's threshold lies within `tol` of the closest point.
     // Anything in doubt -- a nearest node further than expand_dis (the new node is then the walk's end point: cos / sin
     // needed), the remaining distance at the resolution, an obstacle in the band -- takes the exact form below.
-    bool ext_exact = true;
-    if (F32) {
-      if (tid == 0) {
-        const double dx = rx - nqx, dy = ry - nqy;
-        const double d = rpp::py_hypot(dx, dy);
-        const int ne = (int)__builtin_floor(d / c.res);
-        const bool sure = d <= c.expand_dis && d - (double)ne * c.res <= c.res * (1.0 - 1e-9);
-        const double sc = d > 0.0 ? c.res / d : 0.0;
-        sh.e0.fx = nqx; sh.e0.fy = nqy; sh.e0.tx = rx; sh.e0.ty = ry;
-        sh.e0.sx = sc * dx;
-        sh.e0.sy = sc * dy;
-        sh.e0.n_expand = ne;
-        sh.e0.ex = rx;
-        sh.e0.ey = ry;
-        sh.e0.snapped = 1;
-        sh.ecoll0 = 0;
-        sh.fb = sure ? 0 : 1;   // 1: the exact form has to decide
-        sh.nx = rx;
-        sh.ny = ry;
-        sh.flag = rpp::in_play_area(c.has_play, c.play_area, rx, ry) ? 1 : 0;
-      }
-      lds_barrier();
-      if (!sh.fb && sh.flag) {
-        for (int k = tid; k < c.m; k += TPB) {
-          const double tol = 1e-10 * (1.0 + rpp::dabs(nqx) + rpp::dabs(nqy) + rpp::dabs(sh.ox[k]) + rpp::dabs(sh.oy[k])) *
-                             (4.0 + sh.othr[k]);
-          const int r = edge_hits_obstacle_band(sh.e0, true, sh.ox[k], sh.oy[k], sh.othr[k], tol);
-          if (r == 1) sh.ecoll0 = 1;
-          if (r == 2) sh.fb = 2;   // an obstacle in the band
-        }
-      }
-      lds_barrier();
-      ext_exact = sh.fb != 0;
-      if (!ext_exact && sh.flag) {
-        ST_ADD(S_EU, 1);
-        ST_ADD(S_ER, 1);
-      }
-      lds_barrier();
+    if (tid == 0) {
+      const double dx = rx - nqx, dy = ry - nqy;
+      const double d = rpp::py_hypot(dx, dy);
+      const int ne = (int)__builtin_floor(d / c.res);
+      const bool sure = d <= c.expand_dis && d - (double)ne * c.res <= c.res * (1.0 - 1e-9);
+      const double sc = d > 0.0 ? c.res / d : 0.0;
+      sh.e0.fx = nqx; sh.e0.fy = nqy; sh.e0.tx = rx; sh.e0.ty = ry;
+      sh.e0.sx = sc * dx;
+      sh.e0.sy = sc * dy;
+      sh.e0.n_expand = ne;
+      sh.e0.ex = rx;
+      sh.e0.ey = ry;
+      sh.e0.snapped = 1;
+      sh.ecoll0 = 0;
+      sh.fb = sure ? 0 : 1;   // 1: the exact form has to decide
+      sh.nx = rx;
+      sh.ny = ry;
+      sh.flag = rpp::in_play_area(c.has_play, c.play_area, rx, ry) ? 1 : 0;
     }
+    lds_barrier();
+    if (!sh.fb && sh.flag) {
+      for (int k = tid; k < c.m; k += TPB) {
+        const double tol = 1e-10 * (1.0 + rpp::dabs(nqx) + rpp::dabs(nqy) + rpp::dabs(sh.ox[k]) + rpp::dabs(sh.oy[k])) *
+                           (4.0 + sh.othr[k]);
+        const int r = edge_hits_obstacle_band(sh.e0, true, sh.ox[k], sh.oy[k], sh.othr[k], tol);
+        if (r == 1) sh.ecoll0 = 1;
+        if (r == 2) sh.fb = 2;   // an obstacle in the band
+      }
+    }
+    lds_barrier();
+    const bool ext_exact = sh.fb != 0;
+    if (!ext_exact && sh.flag) {
+      ST_ADD(S_EU, 1);
+      ST_ADD(S_ER, 1);
+    }
+    lds_barrier();
     if (ext_exact) {
       const int w = tid >> 6, lane = tid & 63;
       // waves 0 and 1, lane 0: same distance/angle, cos on one SIMD and sin on another (one-wave shape: lane 0 both)
@@ -2000,11 +1848,10 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       int pf_ni = 0;
       double pf_best = 0.0, pf_second = 0.0, pf_x = 0.0, pf_y = 0.0;
       int zskip = 0;                     // goal duplicates inside the 16-bit ball that the pass counted instead of recording
-      const int zgate = (Q16 && first_goal >= 0 && goal_dups > 0) ? first_goal : -1;
+      const int zgate = (first_goal >= 0 && goal_dups > 0) ? first_goal : -1;
       uint32_t pf_sq = 0u, pf_bq = 0u;   // 16-bit stage: packed query, best squared grid distance,
       int pf_grp = -1, pf_n = 0;         // the winner's 4-node group (unresolved while >= 0) and the tree size scanned
       bool pf_goal = false;
-      const double pm = Q16 ? qm : fm;   // margin of the stage that runs the fused pass
       int64_t pass_b = 0, pass_n = n;    // 16-bit stage: bytes and nodes its passes read
       if (use_spec) {
         // the nodes appended since that pass join the ball by the pass's own grid test, in index order
@@ -2035,12 +1882,11 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
         kraw = k2;
         ST_ADD(S_RIDE, 1);
         ST_ADD(S_AB, 16 * (int64_t)kraw + 16);
-      } else if (F32) {
+      } else {
         ns = 0;
         na = 0;
         // ball radius r + m in the mirror's metric, rounded up
-        const double rr = __builtin_sqrt(r2) + pm;
-        const float thr_f = (float)(rr * rr * (1.0 + 1e-6));
+        const double rr = __builtin_sqrt(r2) + qm;
         const double thr_gd = rr * rr * qinv * qinv * (1.0 + 1e-6) + 1.0;    // the same in (integer) grid units
         const uint32_t thr_gi = thr_gd < 4.0e9 ? (uint32_t)thr_gd : 4000000000u;
         const int rw_gi = (int)__builtin_sqrt((double)thr_gi) + 1;   // its window half-width (grid index)
@@ -2051,161 +1897,138 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
           pf_goal = first_goal >= 0 && sh.rx == gx && sh.ry == gy;
         }
         if (do_pf && !pf_goal) {
-          if (Q16) {
-            pf_sq = rppk::quant16(c, sh.rx, sh.ry);
-            // further query sets: the following iterations' balls about their samples, up to the first that reaches the
-            // goal's grid cell (or the end of this launch)
-            int kmax = 0;
-            if (SPEC_ON && n >= 256) {
-              kmax = iters - step - 2 < c.max_iter - it - 2 ? iters - step - 2 : c.max_iter - it - 2;
-              kmax = kmax < 0 ? 0 : (kmax > KS_RUN ? KS_RUN : kmax);
+          pf_sq = rppk::quant16(c, sh.rx, sh.ry);
+          // further query sets: the following iterations' balls about their samples, up to the first that reaches the
+          // goal's grid cell (or the end of this launch)
+          int kmax = 0;
+          if (SPEC_ON && n >= 256) {
+            kmax = iters - step - 2 < c.max_iter - it - 2 ? iters - step - 2 : c.max_iter - it - 2;
+            kmax = kmax < 0 ? 0 : (kmax > KS_RUN ? KS_RUN : kmax);
+          }
+          kmax = uni_i(kmax);
+          if constexpr (NW == 1 && KSM > 0) {
+            uint32_t thr2 = 0u;
+            if (kmax > 0) {
+              const double rr2 = __builtin_sqrt(r2b) + qm;
+              const double tg2 = rr2 * rr2 * qinv * qinv * (1.0 + 1e-6) + 1.0;
+              thr2 = tg2 < 4.0e9 ? (uint32_t)tg2 : 4000000000u;
+              if (uni_i(qdist(goal_q, pf_sq) <= thr2)) kmax = 0;
             }
-            kmax = uni_i(kmax);
-            if constexpr (NW == 1 && KSM > 0) {
-              uint32_t thr2 = 0u;
-              if (kmax > 0) {
-                const double rr2 = __builtin_sqrt(r2b) + pm;
-                const double tg2 = rr2 * rr2 * qinv * qinv * (1.0 + 1e-6) + 1.0;
-                thr2 = tg2 < 4.0e9 ? (uint32_t)tg2 : 4000000000u;
-                if (uni_i(qdist(goal_q, pf_sq) <= thr2)) kmax = 0;
-              }
-              if (kmax > 0) {
-                // samples i + 2 .. i + 1 + kmax, next in the stream, behind those already queued: lane 0 draws them
-                // through sh.rx / sh.ry and puts them in the ring
-                const double p1x = sh.rx, p1y = sh.ry;
-                if (nq < kmax) {
-                  lds_barrier();
-                  if (tid == 0) {
-                    for (int j = nq; j < kmax; j++) {
-                      rppk::draw_sample(c, sh, sob, gx, gy);
-                      G[(qhead + j) & 3] = sh.rx;
-                      G[4 + ((qhead + j) & 3)] = sh.ry;
-                    }
-                    sh.rx = p1x;
-                    sh.ry = p1y;
+            if (kmax > 0) {
+              // samples i + 2 .. i + 1 + kmax, next in the stream, behind those already queued: lane 0 draws them
+              // through sh.rx / sh.ry and puts them in the ring
+              const double p1x = sh.rx, p1y = sh.ry;
+              if (nq < kmax) {
+                lds_barrier();
+                if (tid == 0) {
+                  for (int j = nq; j < kmax; j++) {
+                    rppk::draw_sample(c, sh, sob, gx, gy);
+                    G[(qhead + j) & 3] = sh.rx;
+                    G[4 + ((qhead + j) & 3)] = sh.ry;
                   }
-                  nq = kmax;
-                  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                  lds_barrier();
+                  sh.rx = p1x;
+                  sh.ry = p1y;
                 }
-                double qxv[KA], qyv[KA];
+                nq = kmax;
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                lds_barrier();
+              }
+              double qxv[KA], qyv[KA];
 #pragma unroll
-                for (int j = 0; j < KA; j++) {
-                  qxv[j] = G[(qhead + j) & 3];
-                  qyv[j] = G[4 + ((qhead + j) & 3)];
+              for (int j = 0; j < KA; j++) {
+                qxv[j] = G[(qhead + j) & 3];
+                qyv[j] = G[4 + ((qhead + j) & 3)];
+              }
+              // ball j is about sample i + 1 + j: p1 for j = 0, the queue's entry j - 1 after that
+              int ks = kmax;
+#pragma unroll
+              for (int j = 1; j < KA; j++)
+                if (uni_i(j < ks && qdist(goal_q, rppk::quant16(c, qxv[j - 1], qyv[j - 1])) <= thr2)) ks = j;
+              SpecQ sp[KA];
+#pragma unroll
+              for (int j = 0; j < KA; j++) {
+                const bool on = j < ks;
+                const double cxj = j == 0 ? p1x : qxv[j > 0 ? j - 1 : 0], cyj = j == 0 ? p1y : qyv[j > 0 ? j - 1 : 0];
+                sp[j].qq = on ? rppk::quant16(c, cxj, cyj) : pf_sq;
+                sp[j].thr = on ? thr2 : 0u;    // unused set: radius 0 about a centre whose hits nobody reads
+                sp[j].sq = rppk::quant16(c, on ? qxv[j] : p1x, on ? qyv[j] : p1y);
+                sp[j].off = spec_base + j * SPEC_CAPS;
+                sp[j].cap = SPEC_CAPS;
+                if (tid == 0) {   // the record's centre now: nothing of the queue has to stay in registers over the pass
+                  double* R = G + 16 + 8 * j;
+                  R[0] = cxj;
+                  R[1] = cyj;
+                  R[5] = (double)sp[j].off;
                 }
-                // ball j is about sample i + 1 + j: p1 for j = 0, the queue's entry j - 1 after that
-                int ks = kmax;
-#pragma unroll
-                for (int j = 1; j < KA; j++)
-                  if (uni_i(j < ks && qdist(goal_q, rppk::quant16(c, qxv[j - 1], qyv[j - 1])) <= thr2)) ks = j;
-                SpecQ sp[KA];
+              }
+              kraw = scan2g<true, true, KSM>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, pf_sq, hits, sh, pf_ni,
+                                             pf_best, pf_second, goal_q, zgate, &zskip, sp);
+              pass_b = gs.bytes;
+              pass_n = gs.nodes;
+              did_spec = true;
+              B_n = n;
+              B_thr = uni_u(thr2);
+              ns = ks;
+              shead = 0;
+              na = 0;
+              if (tid == 0) {
+                const double qs2 = c.q_step * c.q_step;
 #pragma unroll
                 for (int j = 0; j < KA; j++) {
                   const bool on = j < ks;
-                  const double cxj = j == 0 ? p1x : qxv[j > 0 ? j - 1 : 0], cyj = j == 0 ? p1y : qyv[j > 0 ? j - 1 : 0];
-                  sp[j].qq = on ? rppk::quant16(c, cxj, cyj) : pf_sq;
-                  sp[j].thr = on ? thr2 : 0u;    // unused set: radius 0 about a centre whose hits nobody reads
-                  sp[j].sq = rppk::quant16(c, on ? qxv[j] : p1x, on ? qyv[j] : p1y);
-                  sp[j].off = spec_base + j * SPEC_CAPS;
-                  sp[j].cap = SPEC_CAPS;
-                  if (tid == 0) {   // the record's centre now: nothing of the queue has to stay in registers over the pass
-                    double* R = G + 16 + 8 * j;
-                    R[0] = cxj;
-                    R[1] = cyj;
-                    R[5] = (double)sp[j].off;
-                  }
-                }
-                kraw = scan2g<true, true, KSM>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, pf_sq, hits, sh, pf_ni,
-                                               pf_best, pf_second, goal_q, zgate, &zskip, sp);
-                pass_b = gs.bytes;
-                pass_n = gs.nodes;
-                did_spec = true;
-                B_n = n;
-                B_thr = uni_u(thr2);
-                ns = ks;
-                shead = 0;
-                na = 0;
-                if (tid == 0) {
-                  const double qs2 = c.q_step * c.q_step;
-#pragma unroll
-                  for (int j = 0; j < KA; j++) {
-                    const bool on = j < ks;
-                    double* R = G + 16 + 8 * j;
-                    R[2] = sp[j].best * qs2;
-                    R[3] = sp[j].second * qs2;
-                    R[4] = (on && sp[j].cnt + j + 1 <= SPEC_CAPS) ? (double)sp[j].cnt : -1.0;   // room for the nodes appended before it is used
-                    R[6] = on ? (double)sp[j].grp : -1.0;
-                    R[7] = sp[j].best;
-                  }
+                  double* R = G + 16 + 8 * j;
+                  R[2] = sp[j].best * qs2;
+                  R[3] = sp[j].second * qs2;
+                  R[4] = (on && sp[j].cnt + j + 1 <= SPEC_CAPS) ? (double)sp[j].cnt : -1.0;   // room for the nodes appended before it is used
+                  R[6] = on ? (double)sp[j].grp : -1.0;
+                  R[7] = sp[j].best;
                 }
               }
             }
-            if (!did_spec) {
-              kraw = scan2g<true, true>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, pf_sq, hits, sh, pf_ni, pf_best,
-                                        pf_second, goal_q, zgate, &zskip);
-              pass_b = gs.bytes;
-              pass_n = gs.nodes;
-            }
-            if (zskip > goal_dups) {   // a different node shares the goal's grid cell: record everything
-              kraw = scan2g<true, true>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, pf_sq, hits, sh, pf_ni, pf_best,
-                                        pf_second);
-              zskip = 0;
-              ST_ADD(S_AB, gs.bytes);
-            }
-            pf_bq = (uint32_t)pf_best;
-            pf_grp = pf_ni;
-            pf_n = n;
-            // f64 coordinates of the provisional nearest node's 4-node group (lanes 0..3): requested now, resolved
-            // after the candidate phases
-            pf_x = x[pf_grp + (tid & 3)];
-            pf_y = y[pf_grp + (tid & 3)];
-            pf_best *= c.q_step * c.q_step;   // squared grid units -> squared world units (fold logic below)
-            pf_second *= c.q_step * c.q_step;
-          } else {
-            kraw = scan2f<true, true>(xf, yf, n, (float)nx, (float)ny, thr_f, (float)sh.rx, (float)sh.ry, hits, sh,
-                                      pf_ni, pf_best, pf_second);
-            // coordinates of the provisional nearest node: requested now, used by the next iteration
-            pf_x = x[pf_ni];
-            pf_y = y[pf_ni];
           }
+          if (!did_spec) {
+            kraw = scan2g<true, true>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, pf_sq, hits, sh, pf_ni, pf_best,
+                                      pf_second, goal_q, zgate, &zskip);
+            pass_b = gs.bytes;
+            pass_n = gs.nodes;
+          }
+          if (zskip > goal_dups) {   // a different node shares the goal's grid cell: record everything
+            kraw = scan2g<true, true>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, pf_sq, hits, sh, pf_ni, pf_best,
+                                      pf_second);
+            zskip = 0;
+            ST_ADD(S_AB, gs.bytes);
+          }
+          pf_bq = (uint32_t)pf_best;
+          pf_grp = pf_ni;
+          pf_n = n;
+          // f64 coordinates of the provisional nearest node's 4-node group (lanes 0..3): requested now, resolved
+          // after the candidate phases
+          pf_x = x[pf_grp + (tid & 3)];
+          pf_y = y[pf_grp + (tid & 3)];
+          pf_best *= c.q_step * c.q_step;   // squared grid units -> squared world units (fold logic below)
+          pf_second *= c.q_step * c.q_step;
         } else {
           int d0;
           double d1, d2;
-          if (Q16) {
-            kraw = scan2g<true, false>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, 0u, hits, sh, d0, d1, d2, goal_q,
-                                       zgate, &zskip);
-            pass_b = gs.bytes;
-            pass_n = gs.nodes;
-            if (zskip > goal_dups) {
-              kraw = scan2g<true, false>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, 0u, hits, sh, d0, d1, d2);
-              zskip = 0;
-              ST_ADD(S_AB, gs.bytes);
-            }
-          } else
-            kraw = scan2f<true, false>(xf, yf, n, (float)nx, (float)ny, thr_f, 0.f, 0.f, hits, sh, d0, d1, d2);
+          kraw = scan2g<true, false>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, 0u, hits, sh, d0, d1, d2, goal_q,
+                                     zgate, &zskip);
+          pass_b = gs.bytes;
+          pass_n = gs.nodes;
+          if (zskip > goal_dups) {
+            kraw = scan2g<true, false>(gs, rw_gi, xq, n, rppk::quant16(c, nx, ny), thr_gi, 0u, hits, sh, d0, d1, d2);
+            zskip = 0;
+            ST_ADD(S_AB, gs.bytes);
+          }
         }
-        ST_ADD(S_AB, (Q16 ? pass_b : 8 * (int64_t)n) + 16 * (int64_t)kraw + 16);
-      } else {
-        if (do_pf) {
-          take_next_sample();
-          lds_barrier();
-          kraw = scan2<true, true>(x, y, n, nx, ny, r2 * (1.0 + FILTER_EPS), sh.rx, sh.ry, hits, sh, pf_ni, pf_best,
-                                   pf_second, pf_x, pf_y);
-          have_sample = 1;
-        } else {
-          int d0;
-          double d1, d2, d3, d4;
-          kraw = scan2<true, false>(x, y, n, nx, ny, r2 * (1.0 + FILTER_EPS), 0.0, 0.0, hits, sh, d0, d1, d2, d3, d4);
-        }
-        ST_ADD(S_AB, 16 * (int64_t)n);
+        ST_ADD(S_AB, pass_b + 16 * (int64_t)kraw + 16);
       }
       ST_ADD(S_SN, pass_n);
       ST_ADD(S_AB2, 16 * (int64_t)n);
       // Fold of the node this iteration appends (position ax, ay, index aidx) into the pass's provisional nearest node
       // of the next sample: margin test in the distance metric, the appended node's distance is exact.  Returns 1 with
-      // the nearest node in (o_ni, o_x, o_y), or 0 (o_amb: the 16-bit stage could not decide -- ask one stage down).
-      auto fold_new_node = [&](double ax, double ay, int aidx, int& o_ni, double& o_x, double& o_y, int& o_amb) -> int {
+      // the nearest node in (o_ni, o_x, o_y), or 0 when the 16-bit stage could not decide (the next iteration's nearest
+      // step takes the query on).
+      auto fold_new_node = [&](double ax, double ay, int aidx, int& o_ni, double& o_x, double& o_y) -> int {
         if (pf_goal) {
           o_ni = first_goal;
           o_x = gx;
@@ -2215,31 +2038,21 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
         const double dxl = ax - sh.rx, dyl = ay - sh.ry;
         const double dl = __builtin_sqrt(dxl * dxl + dyl * dyl);
         const double db = __builtin_sqrt(pf_best), ds = __builtin_sqrt(pf_second);
-        if (dl < db - pm) {
+        if (dl < db - qm) {
           o_ni = aidx;
           o_x = ax;
           o_y = ay;
           return 1;
         }
-        if (ds - db > 2.0 * pm && dl > db + pm) {
-          if (pf_grp >= 0) {
-            // 16-bit stage: the winner is exact only below the saturation bound; find it inside its group
-            const bool ok = pf_bq < QSAT && resolve_group(c, pf_grp, pf_n, pf_x, pf_y, pf_sq, pf_bq, o_ni, o_x, o_y);
-            if (!ok) o_amb = 1;
-            return ok ? 1 : 0;
-          }
-          o_ni = pf_ni;
-          o_x = pf_x;
-          o_y = pf_y;
-          return 1;
-        }
-        if (Q16) o_amb = 1;   // the next iteration asks the f32 pass directly
+        // the winner is exact only below the saturation bound; find it inside its group
+        if (ds - db > 2.0 * qm && dl > db + qm && pf_bq < QSAT)
+          return resolve_group(c, pf_grp, pf_n, pf_x, pf_y, pf_sq, pf_bq, o_ni, o_x, o_y) ? 1 : 0;
         return 0;
       };
       PH(4);
       int pend_p, pend_fc;
       double pend_cost;
-      build_candidates<F32>(x, y, cost, first_child, nx, ny, r2, hits, kraw, sh, pend_p, pend_cost, pend_fc, sub_);
+      build_candidates(x, y, cost, first_child, nx, ny, r2, hits, kraw, sh, pend_p, pend_cost, pend_fc);
       PH(5);
       const int nu = sh.nu;
       int nvalid = sh.nvalid;
@@ -2261,7 +2074,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       if (nu > 0) {
         ST_ADD(S_EU, nu);
         ST_ADD(S_ER, nvalid);
-        eval_edges_dual2(c, nu, nx, ny, sh, sub_);
+        eval_edges_dual2(c, nu, nx, ny, sh);
         if (pend_p >= 0) {
           sh.ucur[pend_p] = pend_cost;
           sh.ufc[pend_p] = pend_fc;
@@ -2347,11 +2160,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
                 rpp::steer(&sh.e0, wx, wy, sh.ux[es], sh.uy[es], rpp::dinf(), c.res);
                 x[u] = sh.e0.ex;
                 y[u] = sh.e0.ey;
-                if (F32) {
-                  xf[u] = (float)sh.e0.ex;
-                  yf[u] = (float)sh.e0.ey;
-                  if (xq) xq[u] = rppk::quant16(c, sh.e0.ex, sh.e0.ey);
-                }
+                xq[u] = rppk::quant16(c, sh.e0.ex, sh.e0.ey);
                 // near_inds may hold an index AGAIN (nodes at equal distance collapse onto the first, :1337).  Once a
                 // node has moved, later visits are no longer void: the moved node is re-steered to where it lies now, and
                 // descendants whose cost rose may qualify on a repeated visit.  That raw-list walk lives in the general
@@ -2411,11 +2220,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
           // append :1065
           x[newidx] = wx;
           y[newidx] = wy;
-          if (F32) {
-            xf[newidx] = (float)wx;
-            yf[newidx] = (float)wy;
-            if (xq) xq[newidx] = rppk::quant16(c, wx, wy);
-          }
+          xq[newidx] = rppk::quant16(c, wx, wy);
           cost[newidx] = wcost;
           elen[newidx] = sh.uhyp[sel];   // == hypot(new - parent) from the position the node ends up at
           first_child[newidx] = sh.last_fc;
@@ -2444,11 +2249,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
         if (tid == 0) {
           x[n] = nx;
           y[n] = ny;
-          if (F32) {
-            xf[n] = (float)nx;
-            yf[n] = (float)ny;
-            if (xq) xq[n] = rppk::quant16(c, nx, ny);
-          }
+          xq[n] = rppk::quant16(c, nx, ny);
           const double el = rpp::py_hypot(nx - nqx, ny - nqy);
           elen[n] = el;
           cost[n] = cost[ni] + el;   // :1054-1056
@@ -2466,41 +2267,24 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
         lds_barrier();
       }
       const int moved = uni_i(sh.moved);
-      if (F32) {
-        if (moved & 2) first_goal = -2;   // a node on the goal moved (or one moved onto it): lowest index unknown
-        if ((moved & 2) && gs.excl > 0) gs.ok = 0;   // ... and the goal duplicates the index left out count as nodes again
-        if (wx == gx && wy == gy) {
-          if (first_goal == -1) {
-            first_goal = n - 1;
-            goal_dups = 0;
-          } else if (first_goal >= 0) {
-            goal_dups++;
-          }
+      if (moved & 2) first_goal = -2;   // a node on the goal moved (or one moved onto it): lowest index unknown
+      if ((moved & 2) && gs.excl > 0) gs.ok = 0;   // ... and the goal duplicates the index left out count as nodes again
+      if (wx == gx && wy == gy) {
+        if (first_goal == -1) {
+          first_goal = n - 1;
+          goal_dups = 0;
+        } else if (first_goal >= 0) {
+          goal_dups++;
         }
       }
-      if (F32 && do_pf && !moved) {
-        int amb = 0;
-        have_nearest = fold_new_node(wx, wy, n - 1, pf_ni, pf_x, pf_y, amb);
-        if (amb && pf_grp >= 0 && pf_bq < QSAT) {   // the best OLD node bounds the nearest distance (the new node can only be nearer)
+      if (do_pf && !moved) {
+        have_nearest = fold_new_node(wx, wy, n - 1, pf_ni, pf_x, pf_y);
+        if (!have_nearest && pf_bq < QSAT) {   // the best OLD node bounds the nearest distance (the new node can only be nearer)
           q_amb = 1;
           q_amb_bq = pf_bq;
         }
         pf_best = pf_goal ? 0.0 : 1.0;
         pf_second = rpp::dinf();
-      } else if (do_pf && !moved) {
-        // fold the node appended above (highest index: wins strict improvements only, :1200) into the argmin
-        const double dxl = wx - sh.rx, dyl = wy - sh.ry;
-        const double dl = dxl * dxl + dyl * dyl;
-        if (dl < pf_best) {
-          pf_second = pf_best;
-          pf_best = dl;
-          pf_ni = n - 1;
-          pf_x = wx;
-          pf_y = wy;
-        } else if (dl < pf_second) {
-          pf_second = dl;
-        }
-        have_nearest = 1;
       }
       if (tid == 0 && inst == c.trace_inst) {
         c.tr_rx[it] = rx;
@@ -2593,11 +2377,6 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
     I->rides += sh.stat[S_RIDE];
     if (sh.stat[S_NUMAX] > I->nu_max) I->nu_max = sh.stat[S_NUMAX];
     PH_STORE(I);
-#ifdef RRTX_PHASE_TIMERS
-    I->phase[13] += sub_[0];
-    I->phase[14] += sub_[1];
-    I->phase[10] += sub_[2];
-#endif
     c.results[inst].n_nodes = n;
     c.results[inst].status = I->status;
   }

@@ -108,7 +108,7 @@ struct rrtx_handle {
     std::chrono::steady_clock::time_point t0;
     double kms = 0.0, kms_main = -1.0;
     int64_t launches = 0, launches_main = 0, steps = 0, v2_done_it = 0;
-    bool use_v2 = false, v2_f32 = false, bit_wave = false;
+    bool use_v2 = false, bit_wave = false;
     int v2_tpb = 0;
     std::vector<Result> res;
     std::vector<int32_t> pending;   // BIT*: instances not finished yet (the device-side work queue of the next launch)
@@ -183,25 +183,15 @@ static int dalloc(rrtx_handle* h, T** p, size_t count) {
 // ---- RRT* (rrt_04, search_until_max_iter): iteration-kernel launches ------------------------------------------------
 // One pass of the latency-lean iteration kernel over `nblk` instances (c.inst_map selects them; nullptr = 0..nblk-1),
 // in chunks of h->v2_chunk_iters iterations, workgroup shape tpb in {64, 128, 256}.
-static int launch_rrt_star_v2_once(rrtx_handle* h, const Ctx& c, int nblk, int tpb, bool f32, double* kms, int64_t* launches) {
+static int launch_rrt_star_v2_once(rrtx_handle* h, const Ctx& c, int nblk, int tpb, double* kms, int64_t* launches) {
   {
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    if (tpb == 64) {
-      if (f32)
-        hipLaunchKernelGGL(rppk2t::rrt_star_kernel_v2<true>, dim3(nblk), dim3(rppk2t::TPB), 0, h->stream, c, h->v2_chunk_iters);
-      else
-        hipLaunchKernelGGL(rppk2t::rrt_star_kernel_v2<false>, dim3(nblk), dim3(rppk2t::TPB), 0, h->stream, c, h->v2_chunk_iters);
-    } else if (tpb == 128) {
-      if (f32)
-        hipLaunchKernelGGL(rppk2s::rrt_star_kernel_v2<true>, dim3(nblk), dim3(rppk2s::TPB), 0, h->stream, c, h->v2_chunk_iters);
-      else
-        hipLaunchKernelGGL(rppk2s::rrt_star_kernel_v2<false>, dim3(nblk), dim3(rppk2s::TPB), 0, h->stream, c, h->v2_chunk_iters);
-    } else {
-      if (f32)
-        hipLaunchKernelGGL(rppk2::rrt_star_kernel_v2<true>, dim3(nblk), dim3(rppk2::TPB), 0, h->stream, c, h->v2_chunk_iters);
-      else
-        hipLaunchKernelGGL(rppk2::rrt_star_kernel_v2<false>, dim3(nblk), dim3(rppk2::TPB), 0, h->stream, c, h->v2_chunk_iters);
-    }
+    if (tpb == 64)
+      hipLaunchKernelGGL(rppk2t::rrt_star_kernel_v2, dim3(nblk), dim3(rppk2t::TPB), 0, h->stream, c, h->v2_chunk_iters);
+    else if (tpb == 128)
+      hipLaunchKernelGGL(rppk2s::rrt_star_kernel_v2, dim3(nblk), dim3(rppk2s::TPB), 0, h->stream, c, h->v2_chunk_iters);
+    else
+      hipLaunchKernelGGL(rppk2::rrt_star_kernel_v2, dim3(nblk), dim3(rppk2::TPB), 0, h->stream, c, h->v2_chunk_iters);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -212,9 +202,9 @@ static int launch_rrt_star_v2_once(rrtx_handle* h, const Ctx& c, int nblk, int t
   }
   return RRTX_OK;
 }
-static int launch_rrt_star_v2(rrtx_handle* h, const Ctx& c, int nblk, int tpb, bool f32, double* kms, int64_t* launches) {
+static int launch_rrt_star_v2(rrtx_handle* h, const Ctx& c, int nblk, int tpb, double* kms, int64_t* launches) {
   for (int64_t done_it = 0; done_it < c.max_iter; done_it += h->v2_chunk_iters) {
-    int rc = launch_rrt_star_v2_once(h, c, nblk, tpb, f32, kms, launches);
+    int rc = launch_rrt_star_v2_once(h, c, nblk, tpb, kms, launches);
     if (rc) return rc;
   }
   return RRTX_OK;
@@ -323,8 +313,8 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
   if ((rc = dalloc(h, &c.prev_sib, tot))) return rc;
   if ((rc = dalloc(h, &c.hits, tot))) return rc;
   if ((rc = dalloc(h, &c.stack, tot))) return rc;
-  if ((p->algo == RRTX_ALGO_RRT_STAR && p->search_until_max_iter) || p->algo == RRTX_ALGO_INFORMED) {
-    // float mirror of the coordinates for the prefiltered streaming passes (rrt_star_v2_body.inc, rrt_informed.hip.h)
+  if (p->algo == RRTX_ALGO_INFORMED) {
+    // float mirror of the coordinates for the prefiltered streaming passes of the rrt_07 kernel (rrt_informed.hip.h)
     if ((rc = dalloc(h, &c.xf, tot))) return rc;
     if ((rc = dalloc(h, &c.yf, tot))) return rc;
   }
@@ -590,9 +580,9 @@ int rrtx_plan_begin(rrtx_handle* h) {
   double &kms = R.kms, &kms_main = R.kms_main;
   int64_t &launches = R.launches, &launches_main = R.launches_main;
   std::vector<Result>& res = R.res;
-  bool &use_v2 = R.use_v2, &v2_f32 = R.v2_f32;
+  bool& use_v2 = R.use_v2;
   int& v2_tpb = R.v2_tpb;
-  (void)kms; (void)kms_main; (void)launches; (void)launches_main; (void)res; (void)use_v2; (void)v2_f32; (void)v2_tpb;
+  (void)kms; (void)kms_main; (void)launches; (void)launches_main; (void)res; (void)use_v2; (void)v2_tpb;
   R.t0 = std::chrono::steady_clock::now();
   h->planned = false;
   HIPCHK(h, hipSetDevice(h->device));
@@ -600,8 +590,9 @@ int rrtx_plan_begin(rrtx_handle* h) {
   Ctx& c = h->c;
   const int B = h->n_inst;
   h->stats_retried = 0;
-  // f32-mirror margin = 2^-20 * the largest coordinate magnitude a node or sample is assumed to have (see scan2f);
-  // rrt_07's informed samples are not clipped to the sampling square, so twice that (the kernel checks and falls back)
+  // f32-mirror margin of the rrt_07 kernel = 2^-20 * the largest coordinate magnitude a node or sample is assumed to have
+  // (see scan_nearest_f32); its informed samples are not clipped to the sampling square, so twice that (the kernel checks
+  // and falls back)
   {
     double mag = fabs(c.rand_min) > fabs(c.rand_max) ? fabs(c.rand_min) : fabs(c.rand_max);
     for (int i = 0; i < B; i++) {
@@ -643,7 +634,7 @@ int rrtx_plan_begin(rrtx_handle* h) {
   if (const char* e = getenv("RRTX_F32"))
     if (atoi(e) == 0 && c.algo == RRTX_ALGO_INFORMED) c.xf = c.yf = nullptr;   // informed kernel: f64 passes only
   if (const char* e = getenv("RRTX_Q16"))
-    if (atoi(e) == 0) c.xq = nullptr;   // rrt_04 kernel: no 16-bit first stage (f32 mirror first)
+    if (atoi(e) == 0 && c.algo == RRTX_ALGO_INFORMED) c.xq = nullptr;   // informed kernel: no 16-bit first stage
   // rrt_04 kernel, one-wave shape: a streaming pass serves up to 1 + spec2 iterations (clamped to the kernel's RRT2_SPECK;
   // RRTX_SPEC2=0: one pass per iteration)
   c.spec2 = 8;
@@ -724,12 +715,7 @@ int rrtx_plan_begin(rrtx_handle* h) {
       const int v = atoi(e);
       tpb = (v == 64 && c.m <= rppk2t::MAX_OBS) ? 64 : (v == 128 && c.m <= rppk2s::MAX_OBS) ? 128 : 256;
     }
-    // f32-mirror prefilter (default on; RRTX_F32=0 streams the f64 arrays): margin = 2^-20 * largest coordinate
-    // magnitude any node or sample can have (see scan2f)
-    bool f32 = c.xf != nullptr;
-    if (const char* e = getenv("RRTX_F32")) f32 = f32 && atoi(e) != 0;
     v2_tpb = tpb;
-    v2_f32 = f32;
   }
   if (c.algo == RRTX_ALGO_INFORMED) {
     std::vector<double> inf(B, INFINITY);
@@ -775,9 +761,9 @@ int rrtx_plan_step(rrtx_handle* h, int32_t* n_pending) {
   double &kms = R.kms, &kms_main = R.kms_main;
   int64_t &launches = R.launches, &launches_main = R.launches_main;
   std::vector<Result>& res = R.res;
-  bool &use_v2 = R.use_v2, &v2_f32 = R.v2_f32;
+  bool& use_v2 = R.use_v2;
   int& v2_tpb = R.v2_tpb;
-  (void)kms; (void)kms_main; (void)launches; (void)launches_main; (void)res; (void)use_v2; (void)v2_f32; (void)v2_tpb;
+  (void)kms; (void)kms_main; (void)launches; (void)launches_main; (void)res; (void)use_v2; (void)v2_tpb;
   HIPCHK(h, hipSetDevice(h->device));
   Ctx& c = h->c;
   const int B = h->n_inst;
@@ -785,7 +771,7 @@ int rrtx_plan_step(rrtx_handle* h, int32_t* n_pending) {
   if (n_pending) *n_pending = B;
   if (R.stage == 1) {
     // RRT* (rrt_04, search_until_max_iter): one launch of the iteration kernel = v2_chunk_iters iterations of every instance
-    int rc2 = launch_rrt_star_v2_once(h, c, B, v2_tpb, v2_f32, &kms, &launches);
+    int rc2 = launch_rrt_star_v2_once(h, c, B, v2_tpb, &kms, &launches);
     if (rc2) return rc2;
     R.v2_done_it += h->v2_chunk_iters;
     if (R.v2_done_it >= c.max_iter) {
@@ -883,9 +869,9 @@ static int plan_finish(rrtx_handle* h) {
   double &kms = R.kms, &kms_main = R.kms_main;
   int64_t &launches = R.launches, &launches_main = R.launches_main;
   std::vector<Result>& res = R.res;
-  bool &use_v2 = R.use_v2, &v2_f32 = R.v2_f32;
+  bool& use_v2 = R.use_v2;
   int& v2_tpb = R.v2_tpb;
-  (void)kms; (void)kms_main; (void)launches; (void)launches_main; (void)res; (void)use_v2; (void)v2_f32; (void)v2_tpb;
+  (void)kms; (void)kms_main; (void)launches; (void)launches_main; (void)res; (void)use_v2; (void)v2_tpb;
   Ctx& c = h->c;
   const int B = h->n_inst;
   R.stage = 0;
@@ -911,7 +897,7 @@ static int plan_finish(rrtx_handle* h) {
       HIPCHK(h, hipGetLastError());
       HIPCHK(h, hipStreamSynchronize(h->stream));   // `redo` is read by the copies above
       if (shape) {
-        int rc2 = launch_rrt_star_v2(h, cr, nr, shape, v2_f32, &kms, &launches);
+        int rc2 = launch_rrt_star_v2(h, cr, nr, shape, &kms, &launches);
         if (rc2) return rc2;
       }
       for (int64_t guard = 0;; guard++) {
@@ -1137,7 +1123,7 @@ static int plan_finish(rrtx_handle* h) {
                         : c.algo == RRTX_ALGO_RS       ? rppr::TPB
                         : c.algo == RRTX_ALGO_BITSTAR  ? 64
                                                        : rppk::TPB;
-  s.main_f32 = use_v2 ? (v2_f32 ? 1 : 0) : 0;
+  s.main_f32 = use_v2 ? 1 : 0;   // kept for the ABI v5 layout: 1 whenever the RRT* iteration kernel ran
   s.plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - R.t0).count();
   h->planned = true;
   // Per-instance conditions are per-instance results: the status word of each instance carries them

@@ -165,8 +165,8 @@ def test_gpu_c2_20k_nodes_equals_oracle(gpu):
 
 def test_gpu_c2_full_size_equals_oracle(gpu, monkeypatch):
     """BASELINE.json's full size (C2: 105 000 iterations, ~101 k nodes) against the golden-pinned oracle, bit for bit --
-    tree, path, counters -- on the kernel shape bench.py times: the 64-thread workgroup `rppk2t::rrt_star_kernel_v2<true>`
-    with the 16-bit first stage (a 1-instance handle would pick the 256-thread shape by itself; RRTX_TPB pins it).
+    tree, path, counters -- on the kernel shape bench.py times: the 64-thread workgroup `rppk2t::rrt_star_kernel_v2`
+    (a 1-instance handle would pick the 256-thread shape by itself; RRTX_TPB pins it).
     ~2 min of oracle time on one host core."""
     monkeypatch.setenv("RRTX_TPB", "64")
     kw = util.c2_kwargs(105000)
@@ -236,31 +236,39 @@ def test_gpu_near_set_overflow_is_replanned_on_a_larger_shape(gpu, monkeypatch):
         util.run_gpu_batch(kw, seeds)
 
 
-def test_gpu_c2_full_size_kernel_variants_agree(gpu, monkeypatch):
-    """Full size, every code path of the RRT* iteration kernel: three workgroup shapes x {f32-mirror pass, f64 pass}
-    must produce identical trees (different reductions, filters and fallbacks, one reference semantics)."""
+def test_gpu_c2_full_size_kernel_shapes_agree_with_oracle(gpu, monkeypatch):
+    """Full size, every code path of the RRT* iteration kernel: three workgroup shapes x {speculated query sets per
+    pass} must produce identical trees (different reductions, filters and fallbacks, one reference semantics), and the
+    first of them equals the oracle's trees and paths."""
+    import concurrent.futures as cf
     kw = util.c2_kwargs(105000)
     seeds = [2, 3, 4]
-    base = None
-    for tpb, f32, spec2 in (("256", "0", "3"), ("256", "1", "3"), ("128", "1", "3"), ("64", "1", "3"), ("64", "1", "1"),
-                            ("64", "1", "0"), ("64", "0", "3")):
-        monkeypatch.setenv("RRTX_TPB", tpb)
-        monkeypatch.setenv("RRTX_F32", f32)
-        monkeypatch.setenv("RRTX_SPEC2", spec2)   # 64-thread shape: a streaming pass serves up to 1 + spec2 iterations
-        out = util.run_gpu_batch(kw, seeds)
-        # most iterations of a dense tree ride on an earlier pass -- and only in that configuration
-        rides = out["stats"]["passes_shared"]
-        if (tpb, f32) == ("64", "1") and spec2 != "0":
-            assert rides > (0.55 if spec2 == "3" else 0.3) * out["stats"]["iterations"], (spec2, rides)
-        else:
-            assert rides == 0
-        sig = [tuple(np.ascontiguousarray(a).tobytes() for a in t) for t in out["trees"]]
-        paths = [None if p is None else np.asarray(p).tobytes() for p in out["paths"]]
-        if base is None:
-            base = (sig, paths, out["stats"]["rewires"], out["stats"]["propagated"])
-        else:
-            assert sig == base[0] and paths == base[1], (tpb, f32, spec2)
-            assert (out["stats"]["rewires"], out["stats"]["propagated"]) == base[2:], (tpb, f32, spec2)
+    with cf.ProcessPoolExecutor(max_workers=len(seeds)) as ex:
+        orc = ex.map(_orc_c2, [(kw, s) for s in seeds])   # ~2 min of oracle time per seed, beside the GPU runs
+        base = None
+        for tpb, spec2 in (("256", "3"), ("128", "3"), ("64", "3"), ("64", "1"), ("64", "0")):
+            monkeypatch.setenv("RRTX_TPB", tpb)
+            monkeypatch.setenv("RRTX_SPEC2", spec2)   # 64-thread shape: a streaming pass serves up to 1 + spec2 iterations
+            out = util.run_gpu_batch(kw, seeds)
+            # most iterations of a dense tree ride on an earlier pass -- and only in that configuration
+            rides = out["stats"]["passes_shared"]
+            if tpb == "64" and spec2 != "0":
+                assert rides > (0.55 if spec2 == "3" else 0.3) * out["stats"]["iterations"], (spec2, rides)
+            else:
+                assert rides == 0
+            sig = [tuple(np.ascontiguousarray(a).tobytes() for a in t) for t in out["trees"]]
+            paths = [None if p is None else np.asarray(p).tobytes() for p in out["paths"]]
+            if base is None:
+                base = (sig, paths, out["stats"]["rewires"], out["stats"]["propagated"])
+                first = out
+            else:
+                assert sig == base[0] and paths == base[1], (tpb, spec2)
+                assert (out["stats"]["rewires"], out["stats"]["propagated"]) == base[2:], (tpb, spec2)
+        for i, (s, (ox, oy, oc, op, opath)) in enumerate(zip(seeds, orc)):
+            util.assert_tree_equal(first["trees"][i], (ox, oy, oc, op), "seed %d, 105k" % s)
+            assert (first["paths"][i] is None) == (opath is None)
+            if opath is not None:
+                assert np.array_equal(first["paths"][i], opath)
 
 
 def test_size_independent_invariants(gpu):

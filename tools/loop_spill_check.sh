@@ -1,7 +1,7 @@
 #!/bin/bash
 # Usage: tools/loop_spill_check.sh <path to a rrt_star_v2_body.inc> [extra hipcc flags]
 # Compiles rrtx_api.hip for gfx950 with that kernel body (CPU only, ~1 min) and reports, for every streaming loop of
-# rppk2t::rrt_star_kernel_v2<true>, the lines per slot, the scratch instructions and the full s_waitcnt vmcnt(0) drains inside it:
+# rppk2t::rrt_star_kernel_v2, the lines per slot, the scratch instructions and the full s_waitcnt vmcnt(0) drains inside it:
 # a register-allocation regression of the hot loop shows here before any GPU time is spent.
 BODY=$1; shift
 REPO=$(cd "$(dirname "$0")/.." && pwd)
@@ -9,9 +9,9 @@ D=/tmp/chk_$$; mkdir -p $D; cp $REPO/robotics-path-planning_amd/csrc/* $D/; cp $
 mkdir -p $D/../include 2>/dev/null
 cd $D && sed -i "s#\"../../include/rrtx.h\"#\"$REPO/include/rrtx.h\"#" rrtx_api.hip
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Wno-parentheses-equality -Wno-unused-value "$@" --cuda-device-only -S -Rpass-analysis=kernel-resource-usage -o $D/o.s rrtx_api.hip 2> $D/err.txt
-grep -A7 "Function Name: _ZN6rppk2t18rrt_star_kernel_v2ILb1" $D/err.txt | grep -E "VGPRs Spill|ScratchSize|SGPRs Spill" | sed 's/.*remark: *//' | tr '\n' ' '; echo
+grep -A7 "Function Name: _ZN6rppk2t18rrt_star_kernel_v2EN4rppk3CtxEi " $D/err.txt | grep -E "VGPRs Spill|ScratchSize|SGPRs Spill" | sed 's/.*remark: *//' | tr '\n' ' '; echo
 grep -E "error" $D/err.txt | head -3
-L=$(grep -n "^_ZN6rppk2t18rrt_star_kernel_v2ILb1EEEvN4rppk3CtxEi:" $D/o.s | cut -d: -f1)
+L=$(grep -n "^_ZN6rppk2t18rrt_star_kernel_v2EN4rppk3CtxEi:" $D/o.s | cut -d: -f1)
 awk -v l=$L 'NR>=l' $D/o.s | awk '/s_endpgm/{print; exit} {print}' > $D/k.s
 python3 - $D/k.s <<'PY'
 import sys,re
