@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define RRTX_ABI_VERSION 5   /* 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
+#define RRTX_ABI_VERSION 6   /* 6: rrtx_set_instance_obstacles; 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
                                 rrtx_copy_results_device, per-instance yaw and informed rotation; 4: rrtx_plan_many,
                                 rrtx_selfcheck, rrtx_stats.main_shape / main_f32, rrtx_plan_begin / _step, rrtx_set_launch_bound,
                                 RRTX_ST_REF_HANGS, rrtx_rccl_* */
@@ -154,6 +154,13 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out);
 /* obstacle_list ctor argument (rrt_04:989): m rows of (ox, oy, size), AoS in; converted to SoA + thresholds
  * (size+robot_radius)**2 (rrt_04:1227) on the host.  Shared by all instances of the handle. */
 int rrtx_set_obstacles(rrtx_handle* h, const double* oxyr, int32_t m);
+/* Per-instance obstacle lists (a batch over many maps in one handle): offsets has n_instances + 1 entries (CSR), instance i
+ * owns the rows oxyr[3*offsets[i] .. 3*offsets[i+1]) of (ox, oy, size), taken as rrtx_set_obstacles takes them.  Replaces
+ * every instance's list; a later rrtx_set_obstacles puts every instance back on one shared list.  RRTX_E_INVALID (the
+ * message names the instance) for offsets[0] != 0, decreasing offsets, oxyr == NULL with rows to read, an instance with
+ * more than 256 obstacles (RRTX_ALGO_RS: 64); RRTX_E_STATE between rrtx_plan_begin and the end of that plan.  Workgroup
+ * shapes and capacities follow the largest list; rrtx_smooth_planned smooths each path against its instance's list. */
+int rrtx_set_instance_obstacles(rrtx_handle* h, const int32_t* offsets, const double* oxyr);
 /* hand over / take back CPython's `random.getstate()[1]` (624 words + position) for one instance, so that
  * the device consumes the stream exactly as random.randint / random.uniform would (rrt_04:1133-1136). */
 int rrtx_set_rng_state(rrtx_handle* h, int32_t instance, const uint32_t* mt624, int32_t pos);

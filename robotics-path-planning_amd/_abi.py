@@ -12,7 +12,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RRTX_LIB") or os.path.join(_HERE, "librrtx.so")
 
-RRTX_ABI_VERSION = 5
+RRTX_ABI_VERSION = 6
 ALGO_RRT, ALGO_RRT_STAR, ALGO_INFORMED, ALGO_DUBINS, ALGO_BITSTAR, ALGO_RRT_DUBINS, ALGO_RS = 0, 1, 2, 3, 4, 5, 6
 SAMPLER_MT, SAMPLER_SOBOL = 0, 1
 ST_DONE, ST_PATH, ST_OVERFLOW, ST_PATH_TRUNC, ST_UNSUPPORTED, ST_REF_RAISES, ST_REF_HANGS = 1, 2, 4, 8, 16, 32, 64
@@ -21,7 +21,7 @@ RRTX_PARTIAL = 1
 ERRORS = {1: "RRTX_PARTIAL", 0: "OK", -1: "RRTX_E_INVALID", -2: "RRTX_E_NO_DEVICE", -3: "RRTX_E_HIP", -4: "RRTX_E_CAPACITY",
           -5: "RRTX_E_STATE", -6: "RRTX_E_OVERFLOW"}
 
-EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obstacles", "rrtx_set_rng_state",
+EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obstacles", "rrtx_set_instance_obstacles", "rrtx_set_rng_state",
            "rrtx_get_rng_state", "rrtx_seed_instances", "rrtx_set_instance", "rrtx_set_instance_rotation", "rrtx_plan", "rrtx_get_tree",
            "rrtx_get_path", "rrtx_get_results", "rrtx_results_device_ptr", "rrtx_copy_results_device", "rrtx_get_sobol_index", "rrtx_get_yaw", "rrtx_get_polylines", "rrtx_get_stats",
            "rrtx_enable_trace", "rrtx_get_trace", "rrtx_get_trace_kind", "rrtx_get_phase_cycles", "rrtx_last_error", "rrtx_destroy", "rrtx_selftest_math",
@@ -75,6 +75,7 @@ def load():
     L.rrtx_device_count.restype = C.c_int
     L.rrtx_create.argtypes = [C.POINTER(Params), C.POINTER(vp)]
     L.rrtx_set_obstacles.argtypes = [vp, vp, i32]
+    L.rrtx_set_instance_obstacles.argtypes = [vp, vp, vp]
     L.rrtx_set_rng_state.argtypes = [vp, i32, vp, i32]
     L.rrtx_get_rng_state.argtypes = [vp, i32, vp, C.POINTER(i32)]
     L.rrtx_seed_instances.argtypes = [vp, i32, i32, vp]
@@ -118,6 +119,26 @@ def load():
         raise RrtxError("librrtx.so ABI version mismatch")
     _lib = L
     return L
+
+
+def pack_instance_obstacles(lists):
+    """One obstacle list of (x, y, size) rows per instance -> (offsets, oxyr): CSR as rrtx_set_instance_obstacles takes
+    it, int32 offsets of len(lists) + 1 entries and float64 rows of shape (offsets[-1], 3)."""
+    rows = []
+    for i, lst in enumerate(lists):
+        r = [[float(v) for v in o] for o in lst]
+        if any(len(o) != 3 for o in r):
+            raise ValueError("instance %d: every obstacle is (x, y, size)" % i)
+        rows.append(np.array(r, dtype=np.float64).reshape(-1, 3))
+    offsets = np.zeros(len(rows) + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum([len(r) for r in rows])
+    oxyr = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 3)), dtype=np.float64)
+    return offsets, oxyr
+
+
+def unpack_instance_obstacles(offsets, oxyr):
+    """Inverse of pack_instance_obstacles: one list of (x, y, size) tuples per instance."""
+    return [[tuple(float(v) for v in r) for r in oxyr[offsets[i]:offsets[i + 1]]] for i in range(len(offsets) - 1)]
 
 
 class RrtxParityWarning(UserWarning):
@@ -228,6 +249,14 @@ class Handle:
         a = np.ascontiguousarray(np.array([[float(v) for v in o] for o in obstacle_list], dtype=np.float64)
                                  .reshape(-1, 3))
         self._chk(self.L.rrtx_set_obstacles(self._h, a.ctypes.data, len(a)), "rrtx_set_obstacles")
+
+    def set_instance_obstacles(self, lists):
+        """One obstacle list of (x, y, size) rows per instance (rrtx_set_instance_obstacles)."""
+        if len(lists) != self.n_instances:
+            raise ValueError("set_instance_obstacles: %d lists for %d instances" % (len(lists), self.n_instances))
+        offsets, oxyr = pack_instance_obstacles(lists)
+        self._chk(self.L.rrtx_set_instance_obstacles(self._h, offsets.ctypes.data, oxyr.ctypes.data if len(oxyr) else None),
+                  "rrtx_set_instance_obstacles")
 
     def set_rng_state(self, instance, pystate):
         """pystate = random.getstate()"""

@@ -23,8 +23,10 @@ struct SmoothArgs {
   int64_t in_n_stride;        // in ints (lets in_n point into an array of structs)
   rpp::MT* rng;               // job j: (rpp::MT*)((char*)rng + j * rng_stride_bytes), advanced in place
   int64_t rng_stride_bytes;
-  const double *ox, *oy, *osz;   // obstacle centres and SIZES (no robot radius here, :1441)
-  int32_t m, max_iter;
+  const double *ox, *oy, *osz;   // obstacle centres and SIZES (no robot radius here, :1441), every job's list concatenated
+  const int32_t* obs;         // job j: rows obs[j * obs_stride] .. + obs[j * obs_stride + 1] - 1 of ox / oy / osz
+  int64_t obs_stride;         // in ints (lets obs point into an array of structs; 0 = one list for every job)
+  int32_t max_iter;
   double* out_xy;             // job j: out_xy + j * out_stride * 2
   int64_t out_stride;
   int32_t *out_n, *status;
@@ -43,8 +45,10 @@ __global__ __launch_bounds__(64) void smooth_kernel(SmoothArgs a, int n_jobs) {
   if (job >= n_jobs) return;
   rpp::MT* grng = reinterpret_cast<rpp::MT*>(reinterpret_cast<char*>(a.rng) + job * a.rng_stride_bytes);
   int n = a.in_n[job * a.in_n_stride];
+  const int ob = __builtin_amdgcn_readfirstlane(a.obs[job * a.obs_stride]);
+  const int om = __builtin_amdgcn_readfirstlane(a.obs[job * a.obs_stride + 1]);
   int status = SM_OK;
-  if (n > PC || a.m > MOB) status = SM_CAPACITY;
+  if (n > PC || om > MOB) status = SM_CAPACITY;
   if (n < 2 || status) {   // nothing to smooth (or planning() returned None): the input is the output
     if (lane == 0) {
       a.out_n[job] = (status || n < 0) ? 0 : n;
@@ -59,10 +63,10 @@ __global__ __launch_bounds__(64) void smooth_kernel(SmoothArgs a, int n_jobs) {
   }
   for (int i = lane; i < 624; i += 64) sh.rng.mt[i] = grng->mt[i];
   if (lane == 0) sh.rng.pos = grng->pos;
-  for (int k = lane; k < a.m; k += 64) {
-    sh.ox[k] = a.ox[k];
-    sh.oy[k] = a.oy[k];
-    sh.osz[k] = a.osz[k];
+  for (int k = lane; k < om; k += 64) {
+    sh.ox[k] = a.ox[ob + k];
+    sh.oy[k] = a.oy[ob + k];
+    sh.osz[k] = a.osz[ob + k];
   }
   for (int i = lane; i < n; i += 64) {
     sh.x[0][i] = a.in_xy[(job * a.in_stride + i) * 2];
@@ -133,15 +137,15 @@ __global__ __launch_bounds__(64) void smooth_kernel(SmoothArgs a, int n_jobs) {
     // line_collision_check :1423-1444
     const double la = sy - fy, lb = -(sx - fx), lc = sy * (sx - fx) - sx * (sy - fy);
     const double h = rpp::py_hypot(la, lb);
-    if (a.m > 0 && h == 0.0) {
+    if (om > 0 && h == 0.0) {
       status = SM_ZERODIV;
       break;
     }
     bool blocked = false;
-    for (int base = 0; base < a.m; base += 64) {
+    for (int base = 0; base < om; base += 64) {
       const int k = base + lane;
       bool hitk = false;
-      if (k < a.m) {
+      if (k < om) {
         const double dd = rpp::dabs(la * sh.ox[k] + lb * sh.oy[k] + lc) / h;
         hitk = dd <= sh.osz[k];
       }

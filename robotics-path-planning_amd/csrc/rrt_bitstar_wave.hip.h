@@ -224,7 +224,9 @@ __global__ __launch_bounds__(64) void bitstar_wave_kernel(BitArgs a, rppk::Inst*
   double* tr_b = (I == a.trace_inst) ? a.tr_b : nullptr;
 
   for (int i = lane; i < 624; i += 64) sh.rng.mt[i] = inst[I].rng.mt[i];
-  for (int i = lane; i < c.m; i += 64) {
+  // this instance's obstacles (rpp::BitCfg points at its rows of the handle's table)
+  const int om = __builtin_amdgcn_readfirstlane(c.m);
+  for (int i = lane; i < om; i += 64) {
     sh.ox[i] = c.ox[i];
     sh.oy[i] = c.oy[i];
     sh.othr[i] = c.othr[i];
@@ -582,7 +584,7 @@ __global__ __launch_bounds__(64) void bitstar_wave_kernel(BitArgs a, rppk::Inst*
         if (i < steps) {
           double px, py;
           point(i, &px, &py);
-          for (int k = 0; k < c.m; k++) {
+          for (int k = 0; k < om; k++) {
             const double dx = sh.ox[k] - px, dy = sh.oy[k] - py;
             if (dx * dx + dy * dy <= sh.othr[k]) col = true;
           }

@@ -272,7 +272,7 @@ __device__ __forceinline__ bool build_candidates_fast(const double* __restrict__
 //     wave 0 and sine on a lane of wave 1, then the reference's expression -- a few times per 10^6 tests.
 // So a verdict costs no libm-grade call in all but those cases (before: three calls deep per batch, lanes diverging).
 template <int NUI>
-__device__ __forceinline__ void test_candidates(const Ctx& c, ShIT<NUI>& sh, int nt, double nx, double ny, double tolmul) {
+__device__ __forceinline__ void test_candidates(const Ctx& c, int om, ShIT<NUI>& sh, int nt, double nx, double ny, double tolmul) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   if (tid == 0) sh.nrw2 = 0;   // candidates that need the exact form
   __syncthreads();
@@ -282,7 +282,7 @@ __device__ __forceinline__ void test_candidates(const Ctx& c, ShIT<NUI>& sh, int
     const double mx = 0.5 * (vx + nx), my = 0.5 * (vy + ny), hl = 0.5 * d * (1.0 + 1e-9) + 1e-9;
     const double sc = 1.0 + rpp::dabs(vx) + rpp::dabs(vy) + rpp::dabs(nx) + rpp::dabs(ny);
     bool hit = false, unsure = false;
-    for (int k = lane; k < c.m; k += 64) {
+    for (int k = lane; k < om; k += 64) {
       const double ddx = sh.ox[k] - mx, ddy = sh.oy[k] - my, tt = hl + sh.orad[k];
       if (ddx * ddx + ddy * ddy <= tt * tt * (1.0 + 1e-9)) {
         const double a = seg_dist2(vx, vy, nx, ny, sh.ox[k], sh.oy[k]);
@@ -323,7 +323,7 @@ __device__ __forceinline__ void test_candidates(const Ctx& c, ShIT<NUI>& sh, int
       const int e = sh.tl[t];
       const double vx = sh.ux[e], vy = sh.uy[e], ex2 = sh.uex[e], ey2 = sh.uey[e];
       bool hit = false;
-      for (int k = lane; k < c.m; k += 64)
+      for (int k = lane; k < om; k += 64)
         if (seg_dist2(vx, vy, ex2, ey2, sh.ox[k], sh.oy[k]) <= sh.othr[k]) hit = true;
       const bool any = __ballot(hit) != 0ull;
       if (lane == 0) sh.ufree[e] = any ? 0 : 1;
@@ -344,7 +344,7 @@ __device__ __forceinline__ void test_candidates(const Ctx& c, ShIT<NUI>& sh, int
     const int e = sh.tlx[t];
     const double vx = sh.ux[e], vy = sh.uy[e], ex2 = sh.uex[e], ey2 = sh.uey[e];
     bool hit = false;
-    for (int k = lane; k < c.m; k += 64)
+    for (int k = lane; k < om; k += 64)
       if (seg_dist2(vx, vy, ex2, ey2, sh.ox[k], sh.oy[k]) <= sh.othr[k]) hit = true;
     const bool any = __ballot(hit) != 0ull;
     if (lane == 0) sh.ufree[e] = any ? 0 : 1;
@@ -600,11 +600,12 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_informed_kernel(Ctx c, const Inf
   if (!(I->start[0] >= q_glo && I->start[0] <= q_ghi && I->start[1] >= q_glo && I->start[1] <= q_ghi)) q16_ok = 0;
 
   for (int i = tid; i < 624; i += TPB) sh.rng.mt[i] = I->rng.mt[i];
-  for (int i = tid; i < c.m; i += TPB) {
-    sh.ox[i] = c.ox[i];
-    sh.oy[i] = c.oy[i];
-    sh.othr[i] = c.othr[i];
-    sh.orad[i] = __builtin_sqrt(c.othr[i] > 0.0 ? c.othr[i] : 0.0) * (1.0 + 1e-12);
+  const int ob = __builtin_amdgcn_readfirstlane(I->obs_base), om = __builtin_amdgcn_readfirstlane(I->obs_m);
+  for (int i = tid; i < om; i += TPB) {
+    sh.ox[i] = c.ox[ob + i];
+    sh.oy[i] = c.oy[ob + i];
+    sh.othr[i] = c.othr[ob + i];
+    sh.orad[i] = __builtin_sqrt(c.othr[ob + i] > 0.0 ? c.othr[ob + i] : 0.0) * (1.0 + 1e-12);
   }
   if (tid == 0) {
     sh.rng.pos = I->rng.pos;
@@ -736,8 +737,8 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_informed_kernel(Ctx c, const Inf
       }
     }
     s_sn += n;
-    s_ab += 24 * (int64_t)c.m;
-    s_ab2 += 16 * (int64_t)n + 24 * (int64_t)c.m;
+    s_ab += 24 * (int64_t)om;
+    s_ab2 += 16 * (int64_t)n + 24 * (int64_t)om;
     have_s = 0;
     have_n = 0;
 
@@ -794,7 +795,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_informed_kernel(Ctx c, const Inf
     const double nx = sh.nx, ny = sh.ny;
     s_eu++;
     s_er++;
-    for (int k = tid; k < c.m; k += TPB)
+    for (int k = tid; k < om; k += TPB)
       if (seg_dist2(sh.ux[0], sh.uy[0], sh.ex, sh.ey, sh.ox[k], sh.oy[k]) <= sh.othr[k]) sh.ecoll = 1;
     __syncthreads();
     const int accepted = !sh.ecoll;
@@ -949,7 +950,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_informed_kernel(Ctx c, const Inf
             __syncthreads();
           }
           const int nt = sh.ntl;
-          test_candidates(c, sh, nt, nx, ny, tolmul);
+          test_candidates(c, om, sh, nt, nx, ny, tolmul);
           tested += nt;
           if (tid < na && sh.ufree[sh.cflag[tid]] == 1) atomicMin(&sh.flag, tid);
           __syncthreads();
@@ -995,7 +996,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_informed_kernel(Ctx c, const Inf
           const int nt = sh.ntl;
           __syncthreads();
           if (nt > 0) {
-            test_candidates(c, sh, nt, nx, ny, tolmul);
+            test_candidates(c, om, sh, nt, nx, ny, tolmul);
             extra += nt;
             if (tid == 0) sh.ntl = 0;
             __syncthreads();
@@ -1044,7 +1045,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_informed_kernel(Ctx c, const Inf
           const double vx = sh.ux[e], vy = sh.uy[e], ex2 = sh.uex[e], ey2 = sh.uey[e];
           const double mx = 0.5 * (vx + ex2), my = 0.5 * (vy + ey2), hl = 0.5 * sh.ud[e] * (1.0 + 1e-12);
           bool hit = false;
-          for (int k = lane; k < c.m; k += 64) {
+          for (int k = lane; k < om; k += 64) {
             const double ddx = sh.ox[k] - mx, ddy = sh.oy[k] - my, t = hl + sh.orad[k];
             if (ddx * ddx + ddy * ddy <= t * t * (1.0 + 1e-9)) {
               if (seg_dist2(vx, vy, ex2, ey2, sh.ox[k], sh.oy[k]) <= sh.othr[k]) hit = true;
@@ -1116,7 +1117,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_informed_kernel(Ctx c, const Inf
       if (sh.near_goal) {   // is_near_goal :1226-1230, evaluated beside the steer (sh.ecoll is 0 here: the node was accepted)
         s_eu++;
         s_er++;
-        for (int k = tid; k < c.m; k += TPB)
+        for (int k = tid; k < om; k += TPB)
           if (seg_dist2(nx, ny, gx, gy, sh.ox[k], sh.oy[k]) <= sh.othr[k]) sh.ecoll = 1;   // check_segment_collision :1095
         __syncthreads();
         if (!sh.ecoll && tid == 0) {

@@ -56,6 +56,7 @@ struct Inst {  // persistent per-instance state (global memory)
   rpp::MT rng;
   rpp::Sobol sobol;
   double start[3], goal[3];   // x, y and (pose planners: rrt_03 / rrt_05 / rrt_06) yaw of this instance
+  int32_t obs_base, obs_m;    // this instance's obstacles: rows obs_base .. obs_base + obs_m - 1 of Ctx::ox / oy / othr
   int32_t n, it, status, goal_node, path_n;
   int32_t first_goal;   // lowest index of a node lying exactly on the goal (-1 none yet, -2 unknown); f32-mirror path only
   int32_t goal_dups;    // nodes with a higher index lying exactly on the goal too, while first_goal >= 0
@@ -79,8 +80,7 @@ struct Ctx {
   double *x, *y, *cost;
   int32_t *parent, *first_child, *next_sib, *prev_sib, *hits, *stack;
   int64_t stride;
-  const double *ox, *oy, *othr;
-  int32_t m;
+  const double *ox, *oy, *othr;   // every instance's obstacle list, concatenated (Inst::obs_base / obs_m select one)
   const double* r2tab;
   double* path_xy;
   int32_t path_cap;
@@ -575,7 +575,7 @@ __device__ __forceinline__ void exact_dedup(const double* __restrict__ x, const 
 // Steer + collision for `ne` edges.  kind 0: node uidx[e] -> (tx,ty) (choose_parent
 // :1265, goal :1295); kind 1: (tx,ty) -> node uidx[e] (rewire :1359).
 // Out per e: sh.uex/uey (edge end), sh.usafe (no collision AND end inside play area).
-__device__ __forceinline__ void eval_edges(const Ctx& c, const double* __restrict__ x, const double* __restrict__ y,
+__device__ __forceinline__ void eval_edges(const Ctx& c, int om, const double* __restrict__ x, const double* __restrict__ y,
                                            int ne, int kind, double tx, double ty, Sh& sh) {
   const int tid = threadIdx.x;
   for (int base = 0; base < ne; base += EB) {
@@ -590,8 +590,8 @@ __device__ __forceinline__ void eval_edges(const Ctx& c, const double* __restric
       sh.ecoll[tid] = 0;
     }
     __syncthreads();
-    for (int p = tid; p < nb * c.m; p += TPB) {
-      const int e = p / c.m, k = p - e * c.m;
+    for (int p = tid; p < nb * om; p += TPB) {
+      const int e = p / om, k = p - e * om;
       if (rpp::edge_hits_obstacle(sh.edge[e], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[e] = 1;
     }
     __syncthreads();
@@ -635,7 +635,7 @@ __device__ __forceinline__ int block_min_int(int v, Sh& sh) {
 // direction w>>1 and evaluates cos (w even) or sin (w odd) of the edge angle; lane = candidate.
 // Out per candidate e: uex/uey = end of the forward edge, uaux = hypot(new - node) (= hypot(node - new)),
 // usafe bit0 = forward edge safe, bit1 = backward edge safe, bit2 = backward edge ends exactly on the node.
-__device__ __forceinline__ void eval_edges_dual(const Ctx& c, const double* __restrict__ x, const double* __restrict__ y,
+__device__ __forceinline__ void eval_edges_dual(const Ctx& c, int om, const double* __restrict__ x, const double* __restrict__ y,
                                                 int nu, double nx, double ny, Sh& sh) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int kind = w >> 1, trig = w & 1;
@@ -674,8 +674,8 @@ __device__ __forceinline__ void eval_edges_dual(const Ctx& c, const double* __re
       sh.ecoll[kind * EBD + lane] = 0;
     }
     __syncthreads();
-    for (int p = tid; p < 2 * nb * c.m; p += TPB) {
-      const int q = p / c.m, k = p - q * c.m;
+    for (int p = tid; p < 2 * nb * om; p += TPB) {
+      const int q = p / om, k = p - q * om;
       const int kk = q / nb, e = q - kk * nb;
       const int slot = kk * EBD + e;
       if (rpp::edge_hits_obstacle(sh.edge[slot], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[slot] = 1;
@@ -818,7 +818,7 @@ __device__ inline void unlink_child(int32_t* parent, int32_t* first_child, int32
 // current coordinates and costs.  dist_list itself predates the loop: the entry -> index map is taken before anything
 // moves (stored over hits[], as candidate slot numbers).  Rare (needs a distance tie in the near set and an inexact
 // path_resolution); lane 0 walks, the whole workgroup builds the map.
-__device__ inline void rewire_raw_walk(const Ctx& c, double* __restrict__ x, double* __restrict__ y,
+__device__ inline void rewire_raw_walk(const Ctx& c, int om, double* __restrict__ x, double* __restrict__ y,
                                        double* __restrict__ cost, int32_t* parent, int32_t* first_child,
                                        int32_t* next_sib, int32_t* prev_sib, int32_t* hits, int32_t* stack, int kraw,
                                        int nu, double nx, double ny, double r2, double wx, double wy, double wcost,
@@ -871,7 +871,7 @@ __device__ inline void rewire_raw_walk(const Ctx& c, double* __restrict__ x, dou
       if (!(cost[u] > ec)) continue;                               // improved_cost :1366 (strict)
       rpp::steer(&sh.edge[0], wx, wy, ux, uy, rpp::dinf(), c.res);   // :1359
       bool ok = rpp::in_play_area(c.has_play, c.play_area, sh.edge[0].ex, sh.edge[0].ey);
-      for (int k = 0; k < c.m && ok; k++)
+      for (int k = 0; k < om && ok; k++)
         if (rpp::edge_hits_obstacle(sh.edge[0], sh.ox[k], sh.oy[k], sh.othr[k])) ok = false;
       if (!ok) continue;
       unlink_child(parent, first_child, next_sib, prev_sib, u);   // :1369-1371 (also when it already hangs under newidx)
@@ -922,7 +922,7 @@ __device__ inline void write_path(const Ctx& c, Inst* I, const double* x, const 
 }
 
 // search_best_goal_node (rrt_04:1284-1312): returns the goal node index or -1 (block-uniform).
-__device__ __forceinline__ int best_goal_node(const Ctx& c, Inst* I, const double* x, const double* y,
+__device__ __forceinline__ int best_goal_node(const Ctx& c, int om, Inst* I, const double* x, const double* y,
                                               const double* cost, int32_t* hits, int n, Sh& sh, int64_t& eu,
                                               int64_t& er) {
   const double gx = I->goal[0], gy = I->goal[1];
@@ -933,7 +933,7 @@ __device__ __forceinline__ int best_goal_node(const Ctx& c, Inst* I, const doubl
   eu += nu;
   er += sh.nvalid;
   if (nu == 0) return -1;
-  eval_edges(c, x, y, nu, 0, gx, gy, sh);
+  eval_edges(c, om, x, y, nu, 0, gx, gy, sh);
   for (int e = threadIdx.x; e < nu; e += TPB)
     sh.uaux[e] = sh.usafe[e] ? cost[sh.uidx[e]] + sh.uval[e] : rpp::dinf();  // cost + calc_dist_to_goal :1303-1305
   __syncthreads();
@@ -986,10 +986,11 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
 
   // stage per-instance state and the obstacle tile in LDS
   for (int i = tid; i < 624; i += TPB) sh.rng.mt[i] = I->rng.mt[i];
-  for (int i = tid; i < c.m; i += TPB) {
-    sh.ox[i] = c.ox[i];
-    sh.oy[i] = c.oy[i];
-    sh.othr[i] = c.othr[i];
+  const int ob = __builtin_amdgcn_readfirstlane(I->obs_base), om = __builtin_amdgcn_readfirstlane(I->obs_m);
+  for (int i = tid; i < om; i += TPB) {
+    sh.ox[i] = c.ox[ob + i];
+    sh.oy[i] = c.oy[ob + i];
+    sh.othr[i] = c.othr[ob + i];
   }
   if (tid == 0) {
     sh.rng.pos = I->rng.pos;
@@ -1021,8 +1022,8 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
     // ---------------- nearest :1197-1202 (already known when the previous iteration's fused pass covered it)
     int ni;
     double gbest, gsecond;
-    s_ab2 += 16 * (int64_t)n + 24 * (int64_t)c.m;
-    s_ab += 24 * (int64_t)c.m;
+    s_ab2 += 16 * (int64_t)n + 24 * (int64_t)om;
+    s_ab += 24 * (int64_t)om;
     if (have_nearest) {
       ni = pf_ni;
       gbest = pf_best;
@@ -1068,7 +1069,7 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
     if (inplay) {
       s_eu++;
       s_er++;
-      for (int k = tid; k < c.m; k += TPB)
+      for (int k = tid; k < om; k += TPB)
         if (rpp::edge_hits_obstacle(sh.edge[0], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[0] = 1;
     }
     __syncthreads();
@@ -1108,7 +1109,7 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
       if (sh.flag) {
         s_eu++;
         s_er++;
-        for (int k = tid; k < c.m; k += TPB)
+        for (int k = tid; k < om; k += TPB)
           if (rpp::edge_hits_obstacle(sh.edge[0], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[0] = 1;
         __syncthreads();
         if (!sh.ecoll[0]) {
@@ -1156,7 +1157,7 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
       if (nu > 0) {
         s_eu += nu;
         s_er += nvalid;
-        eval_edges_dual(c, x, y, nu, nx, ny, sh);
+        eval_edges_dual(c, om, x, y, nu, nx, ny, sh);
         PH(6);
         for (int e = tid; e < nu; e += TPB) {
           const int u = sh.uidx[e];
@@ -1189,7 +1190,7 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
         s_er += nvalid;
         if (wx != nx || wy != ny) {
           // the winning edge stopped short of the extension point: redo the backward edges from where it ended
-          eval_edges(c, x, y, nu, 1, wx, wy, sh);
+          eval_edges(c, om, x, y, nu, 1, wx, wy, sh);
           for (int e = tid; e < nu; e += TPB) {
             const int u = sh.uidx[e];
             sh.uaux[e] = rpp::py_hypot(x[u] - wx, y[u] - wy);
@@ -1253,7 +1254,7 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
           e0 = es + 1;
         }
         if (raw_from >= 0)
-          rewire_raw_walk(c, x, y, cost, parent, first_child, next_sib, prev_sib, hits, stack, kraw, nu, nx, ny, r2, wx,
+          rewire_raw_walk(c, om, x, y, cost, parent, first_child, next_sib, prev_sib, hits, stack, kraw, nu, nx, ny, r2, wx,
                           wy, wcost, newidx, raw_from, sh);
         if (tid == 0) {
           // append :1065
@@ -1312,7 +1313,7 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
       s_sn += n;
       s_ab += 16 * (int64_t)n;
       s_ab2 += 16 * (int64_t)n;
-      const int gi = best_goal_node(c, I, x, y, cost, hits, n, sh, s_eu, s_er);
+      const int gi = best_goal_node(c, om, I, x, y, cost, hits, n, sh, s_eu, s_er);
       if (gi >= 0) {
         if (tid == 0) write_path(c, I, x, y, parent, inst, gi);
         done = 1;
@@ -1329,7 +1330,7 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
       s_sn += n;
       s_ab += 16 * (int64_t)n;
       s_ab2 += 16 * (int64_t)n;
-      const int gi = best_goal_node(c, I, x, y, cost, hits, n, sh, s_eu, s_er);
+      const int gi = best_goal_node(c, om, I, x, y, cost, hits, n, sh, s_eu, s_er);
       if (gi >= 0 && tid == 0) write_path(c, I, x, y, parent, inst, gi);
       __syncthreads();
     }

@@ -261,13 +261,13 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
   double* pool_x = da.pool_x + pslot * da.pool_cap;
   double* pool_y = da.pool_y + pslot * da.pool_cap;
   double* pool_w = da.pool_yaw + pslot * da.pool_cap;
-  const int m = c.m;
+  const int ob = __builtin_amdgcn_readfirstlane(I->obs_base), m = __builtin_amdgcn_readfirstlane(I->obs_m);
 
   for (int i = lane; i < 624; i += TPB) sh.rng.mt[i] = I->rng.mt[i];
   for (int i = lane; i < m; i += TPB) {
-    sh.ox[i] = c.ox[i];
-    sh.oy[i] = c.oy[i];
-    sh.othr[i] = c.othr[i];
+    sh.ox[i] = c.ox[ob + i];
+    sh.oy[i] = c.oy[ob + i];
+    sh.othr[i] = c.othr[ob + i];
   }
   if (lane == 0) sh.rng.pos = I->rng.pos;
 #ifdef RRTX_PHASE_TIMERS

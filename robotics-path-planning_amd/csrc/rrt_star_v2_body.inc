@@ -69,6 +69,7 @@ struct Sh2 {
   int32_t flag, nu, nvalid, overflow, ecoll0;
   int32_t fa, fb, fover, fcount;
   int32_t n_rw, n_pr, moved, last_fc;
+  int32_t om;           // this instance's obstacle count, for the loops of the iteration body (uni_i on read)
   long long stat[15];   // per-launch counters, lane 0 only (kept out of the register file)
 };
 
@@ -1202,7 +1203,7 @@ __device__ __forceinline__ int edge_hits_obstacle_band(const rpp::Edge& e, bool 
 // An edge with either decision in doubt -- in practice the edge from the NEAREST node, whose length is 8 x 0.25 = 2.0 give
 // or take an ULP, in about every second iteration -- is evaluated again exactly as before (atan2 / cos / sin replicas, the
 // sequential additions, the exact test), by its own lane alone instead of all candidates' lanes diverging in the replicas.
-__device__ __forceinline__ void eval_edges_dual2(const Ctx& c, int nu, double nx, double ny, Sh2& sh) {
+__device__ __forceinline__ void eval_edges_dual2(const Ctx& c, int om, int nu, double nx, double ny, Sh2& sh) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   // 4 waves: direction = w>>1 (even waves work, odd ones only take part in the pair loops); 2 waves: direction = w;
   // 1 wave: direction = lane>>5 (both half-waves run the same instruction stream)
@@ -1235,8 +1236,8 @@ __device__ __forceinline__ void eval_edges_dual2(const Ctx& c, int nu, double nx
       sh.cflag[kind * EBD + el] = 0;   // collision flags of this pass
     }
     lds_barrier();
-    for (int p = tid; p < 2 * nb * c.m; p += TPB) {
-      const int q = p / c.m, k = p - q * c.m;
+    for (int p = tid; p < 2 * nb * om; p += TPB) {
+      const int q = p / om, k = p - q * om;
       const int kk = q / nb, e = q - kk * nb;
       const int slot = kk * EBD + e;
       const rpp::Edge& ed = sh.u.edge[slot];
@@ -1269,8 +1270,8 @@ __device__ __forceinline__ void eval_edges_dual2(const Ctx& c, int nu, double nx
         sh.cflag[kind * EBD + el] = 0;
       }
       lds_barrier();
-      for (int p = tid; p < 2 * nb * c.m; p += TPB) {
-        const int q = p / c.m, k = p - q * c.m;
+      for (int p = tid; p < 2 * nb * om; p += TPB) {
+        const int q = p / om, k = p - q * om;
         const int kk = q / nb, e = q - kk * nb;
         const int slot = kk * EBD + e;
         if (!(sh.u.edge[slot].snapped & 16)) continue;
@@ -1295,7 +1296,7 @@ __device__ __forceinline__ void eval_edges_dual2(const Ctx& c, int nu, double nx
 }
 
 // backward edges only, from the true new-node position (the winning edge did not snap): refresh bits 1,2 + uhyp
-__device__ __forceinline__ void eval_edges_back2(const Ctx& c, int nu, double wx, double wy, Sh2& sh) {
+__device__ __forceinline__ void eval_edges_back2(const Ctx& c, int om, int nu, double wx, double wy, Sh2& sh) {
   const int tid = threadIdx.x;
   for (int base = 0; base < nu; base += 2 * EBD) {
     const int nb = (nu - base) < 2 * EBD ? (nu - base) : 2 * EBD;
@@ -1305,8 +1306,8 @@ __device__ __forceinline__ void eval_edges_back2(const Ctx& c, int nu, double wx
       sh.cflag[tid] = 0;
     }
     lds_barrier();
-    for (int p = tid; p < nb * c.m; p += TPB) {
-      const int e = p / c.m, k = p - e * c.m;
+    for (int p = tid; p < nb * om; p += TPB) {
+      const int e = p / om, k = p - e * om;
       if (rpp::edge_hits_obstacle(sh.u.edge[e], sh.ox[k], sh.oy[k], sh.othr[k])) sh.cflag[e] = 1;
     }
     lds_barrier();
@@ -1443,14 +1444,22 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   int goal_dups = I->goal_dups;   // exact duplicates of node first_goal appended so far (valid while first_goal >= 0)
 
   for (int i = tid; i < 624; i += TPB) sh.rng.mt[i] = I->rng.mt[i];
-  for (int i = tid; i < c.m; i += TPB) {
-    sh.ox[i] = c.ox[i];
-    sh.oy[i] = c.oy[i];
-    sh.othr[i] = c.othr[i];
-  }
-  if (tid == 0) {
-    sh.rng.pos = I->rng.pos;
-    sh.overflow = 0;
+  // this instance's obstacle rows, block-uniform.  The candidate-edge helpers take the count as an argument, the two loops
+  // of the iteration body read it back from sh.om: with that split the streaming loops keep their ring of loads in flight
+  // (tools/loop_spill_check.sh) and no shape spills more SGPRs than with one shared list
+  const int om = uni_i(I->obs_m);
+  {
+    const int ob = uni_i(I->obs_base);
+    for (int i = tid; i < om; i += TPB) {
+      sh.ox[i] = c.ox[ob + i];
+      sh.oy[i] = c.oy[ob + i];
+      sh.othr[i] = c.othr[ob + i];
+    }
+    if (tid == 0) {
+      sh.rng.pos = I->rng.pos;
+      sh.overflow = 0;
+      sh.om = om;
+    }
   }
   lds_barrier();
   int n = __builtin_amdgcn_readfirstlane(I->n), it = __builtin_amdgcn_readfirstlane(I->it);   // block-uniform: keep them scalar
@@ -1598,8 +1607,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
     have_sample = 0;
     PH(0);
     // ---------------- nearest :1197-1202
-    ST_ADD(S_AB2, 16 * (int64_t)n + 24 * (int64_t)c.m);
-    ST_ADD(S_AB, 24 * (int64_t)c.m);
+    ST_ADD(S_AB2, 16 * (int64_t)n);   // + 24 per obstacle, added per iteration at the end of the launch
     const double r2 = c.r2tab[n + 1];   // find_near_nodes radius for this tree size (requested early, used later)
     const double r2b = SPEC_ON ? c.r2tab[n + 2] : 0.0;   // ... and for the next one (speculated balls: the largest they can need)
     if (!have_nearest) {
@@ -1764,7 +1772,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
     }
     lds_barrier();
     if (!sh.fb && sh.flag) {
-      for (int k = tid; k < c.m; k += TPB) {
+      for (int k = tid, mk = uni_i(sh.om); k < mk; k += TPB) {
         const double tol = 1e-10 * (1.0 + rpp::dabs(nqx) + rpp::dabs(nqy) + rpp::dabs(sh.ox[k]) + rpp::dabs(sh.oy[k])) *
                            (4.0 + sh.othr[k]);
         const int r = edge_hits_obstacle_band(sh.e0, true, sh.ox[k], sh.oy[k], sh.othr[k], tol);
@@ -1822,7 +1830,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
     if (inplay && ext_exact) {
       ST_ADD(S_EU, 1);
       ST_ADD(S_ER, 1);
-      for (int k = tid; k < c.m; k += TPB)
+      for (int k = tid, mk = uni_i(sh.om); k < mk; k += TPB)
         if (rpp::edge_hits_obstacle(sh.e0, sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll0 = 1;
     }
     lds_barrier();
@@ -2074,7 +2082,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       if (nu > 0) {
         ST_ADD(S_EU, nu);
         ST_ADD(S_ER, nvalid);
-        eval_edges_dual2(c, nu, nx, ny, sh);
+        eval_edges_dual2(c, om, nu, nx, ny, sh);
         if (pend_p >= 0) {
           sh.ucur[pend_p] = pend_cost;
           sh.ufc[pend_p] = pend_fc;
@@ -2106,7 +2114,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
         // ---------------- rewire (before append) :1340-1373
         ST_ADD(S_EU, nu);
         ST_ADD(S_ER, nvalid);
-        if (wx != nx || wy != ny) eval_edges_back2(c, nu, wx, wy, sh);
+        if (wx != nx || wy != ny) eval_edges_back2(c, om, nu, wx, wy, sh);
         for (int e = tid; e < nu; e += TPB) sh.uval[e] = wcost + sh.uhyp[e];   // edge_node.cost :1362
         if (tid == 0) {
           sh.n_rw = 0;
@@ -2369,8 +2377,9 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
     I->rewires += sh.stat[S_RW];
     I->propagated += sh.stat[S_PR];
     I->scan_nodes += sh.stat[S_SN];
-    I->alg_bytes += sh.stat[S_AB];
-    I->alg_bytes2 += sh.stat[S_AB2];
+    const int64_t tile_b = 24 * (int64_t)I->obs_m * sh.stat[S_ITER];   // the obstacle tile, read every iteration
+    I->alg_bytes += sh.stat[S_AB] + tile_b;
+    I->alg_bytes2 += sh.stat[S_AB2] + tile_b;
     I->exact_rescans += sh.stat[S_EX];
     I->f32_fallbacks += sh.stat[S_FB];
     I->q16_fallbacks += sh.stat[S_QA];

@@ -93,10 +93,13 @@ struct rrtx_handle {
   Ctx c;
   int64_t stride = 0;
   int n_inst = 0;
-  int m = 0;
+  int m_max = 0;                // largest obstacle count of any instance (capacity and workgroup-shape decisions)
   bool planned = false;
-  std::vector<Inst> host_inst;  // staging for seeds / starts before the first plan
-  std::vector<double> obst;
+  std::vector<Inst> host_inst;  // staging for seeds / starts / obstacle rows before the first plan
+  std::vector<double> obst;     // every instance's obstacle rows (x, y, size) as given, in device-table order
+  // device obstacle table: ox, oy, othr and the sizes (path smoothing) of all rows, `obs_cap` rows each, one allocation
+  double* obs_buf = nullptr;
+  int64_t obs_cap = 0;
   int trace_inst = -1;
   rrtx_stats stats;
   int64_t phase[16] = {0};
@@ -150,9 +153,10 @@ struct rrtx_handle {
   rppb::BitArgs ba;         // BIT* device arrays
   std::vector<rpp::BitCfg> bcfg;
   // path smoothing on the planned paths (rrtx_smooth_planned)
-  double* sm_osz = nullptr;   // obstacle sizes as given (no robot radius), device
+  double* sm_osz = nullptr;   // obstacle sizes as given (no robot radius), device: the fourth column of obs_buf
   double* sm_xy = nullptr;    // [inst][sm_stride][2]
   int32_t *sm_n = nullptr, *sm_status = nullptr;
+  int32_t* sm_obs = nullptr;  // [inst][2]: the rows (base, count) each path is smoothed against
   int64_t sm_stride = 0;
   bool smoothed = false;
 };
@@ -179,6 +183,42 @@ static int dalloc(rrtx_handle* h, T** p, size_t count) {
   return 0;
 }
 
+// Device obstacle table of at least `rows` rows (contents are not kept: the caller uploads every row afterwards)
+static int obs_reserve(rrtx_handle* h, int64_t rows) {
+  if (rows <= h->obs_cap) return RRTX_OK;
+  void* q = nullptr;
+  hipError_t e = hipMalloc(&q, sizeof(double) * 4 * (size_t)rows);
+  if (e != hipSuccess) {   // the handle keeps its current table and lists
+    h->err = std::string("hipMalloc: ") + hipGetErrorString(e);
+    return RRTX_E_HIP;
+  }
+  if (h->obs_buf) hipFree(h->obs_buf);
+  h->obs_buf = (double*)q;
+  h->obs_cap = rows;
+  h->c.ox = h->obs_buf;
+  h->c.oy = h->obs_buf + rows;
+  h->c.othr = h->obs_buf + 2 * rows;
+  h->sm_osz = h->obs_buf + 3 * rows;
+  return RRTX_OK;
+}
+
+// Uploads `rows` obstacle rows (AoS x, y, size) as the SoA table ox / oy / othr (+ sizes for path smoothing) and keeps
+// them in h->obst.  On failure the handle keeps its previous table and lists: the caller changes no instance.
+static int obs_upload(rrtx_handle* h, const double* oxyr, int64_t rows) {
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = obs_reserve(h, rows);
+  if (rc) return rc;
+  std::vector<double> t(4 * (size_t)h->obs_cap, 0.0);
+  for (int64_t k = 0; k < rows; k++) {
+    t[k] = oxyr[3 * k];
+    t[h->obs_cap + k] = oxyr[3 * k + 1];
+    t[2 * h->obs_cap + k] = py_sq_host(oxyr[3 * k + 2] + h->p.robot_radius);  // (size+robot_radius)**2  rrt_04:1227
+    t[3 * h->obs_cap + k] = oxyr[3 * k + 2];
+  }
+  HIPCHK(h, hipMemcpy(h->obs_buf, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
+  h->obst.assign(oxyr, oxyr + 3 * (size_t)rows);
+  return RRTX_OK;
+}
 
 // ---- RRT* (rrt_04, search_until_max_iter): iteration-kernel launches ------------------------------------------------
 // One pass of the latency-lean iteration kernel over `nblk` instances (c.inst_map selects them; nullptr = 0..nblk-1),
@@ -248,6 +288,7 @@ void rrtx_destroy(rrtx_handle* h) {
     if (a->lib) a->CommDestroy((ncclComm_t)h->rccl_comm);
   }
   for (void* q : h->allocs) hipFree(q);
+  if (h->obs_buf) hipFree(h->obs_buf);
   for (auto& bp : h->big) {
     if (bp.px) hipFree(bp.px);
     if (bp.py) hipFree(bp.py);
@@ -340,16 +381,10 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
   if ((rc = dalloc(h, &c.results, h->n_inst))) return rc;
   c.path_cap = (int32_t)(cap + 1 < 8192 ? cap + 1 : 8192);
   if ((rc = dalloc(h, &c.path_xy, (size_t)h->n_inst * c.path_cap * 2))) return rc;
-  double *dox, *doy, *dothr, *dr2;
-  if ((rc = dalloc(h, &dox, rppk::MAX_OBS))) return rc;
-  if ((rc = dalloc(h, &doy, rppk::MAX_OBS))) return rc;
-  if ((rc = dalloc(h, &dothr, rppk::MAX_OBS))) return rc;
+  double* dr2;
+  if ((rc = obs_reserve(h, rppk::MAX_OBS))) return rc;   // every instance starts on the empty shared list
   if ((rc = dalloc(h, &dr2, (size_t)cap + 2))) return rc;
-  c.ox = dox;
-  c.oy = doy;
-  c.othr = dothr;
   c.r2tab = dr2;
-  c.m = 0;
   c.stride = h->stride;
   c.algo = p->algo;
   c.sampler = p->sampler;
@@ -467,19 +502,69 @@ int rrtx_set_obstacles(rrtx_handle* h, const double* oxyr, int32_t m) {
     h->err = "RRTX_ALGO_RS: more than 64 obstacles";
     return RRTX_E_INVALID;
   }
-  std::vector<double> ox(rppk::MAX_OBS, 0.0), oy(rppk::MAX_OBS, 0.0), th(rppk::MAX_OBS, -1.0);
-  for (int k = 0; k < m; k++) {
-    ox[k] = oxyr[3 * k];
-    oy[k] = oxyr[3 * k + 1];
-    th[k] = py_sq_host(oxyr[3 * k + 2] + h->p.robot_radius);  // (size+robot_radius)**2  rrt_04:1227
+  // the shared list: every instance owns rows 0 .. m-1
+  int rc = obs_upload(h, oxyr, m);
+  if (rc) return rc;
+  for (Inst& I : h->host_inst)
+    if (I.obs_base != 0 || I.obs_m != m) {
+      I.obs_base = 0;
+      I.obs_m = m;
+      h->inst_dirty = true;
+    }
+  h->m_max = m;
+  return RRTX_OK;
+}
+
+int rrtx_set_instance_obstacles(rrtx_handle* h, const int32_t* offsets, const double* oxyr) {
+  if (!h) return RRTX_E_INVALID;
+  if (h->run.stage != 0) {
+    h->err = "rrtx_set_instance_obstacles: a plan is in progress";
+    return RRTX_E_STATE;
   }
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpy((void*)h->c.ox, ox.data(), sizeof(double) * rppk::MAX_OBS, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy((void*)h->c.oy, oy.data(), sizeof(double) * rppk::MAX_OBS, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy((void*)h->c.othr, th.data(), sizeof(double) * rppk::MAX_OBS, hipMemcpyHostToDevice));
-  h->c.m = m;
-  h->m = m;
-  h->obst.assign(oxyr, oxyr + 3 * (size_t)m);
+  if (!offsets) {
+    h->err = "rrtx_set_instance_obstacles: offsets is NULL";
+    return RRTX_E_INVALID;
+  }
+  const int B = h->n_inst;
+  const int lim = h->p.algo == RRTX_ALGO_RS ? rppr::MAX_OBS : rppk::MAX_OBS;
+  char msg[160];
+  if (offsets[0] != 0) {
+    snprintf(msg, sizeof(msg), "rrtx_set_instance_obstacles: instance 0: offsets[0] = %d, expected 0", offsets[0]);
+    h->err = msg;
+    return RRTX_E_INVALID;
+  }
+  int m_max = 0;
+  for (int i = 0; i < B; i++) {
+    const int64_t cnt = (int64_t)offsets[i + 1] - offsets[i];
+    if (cnt < 0) {
+      snprintf(msg, sizeof(msg), "rrtx_set_instance_obstacles: instance %d: offsets decrease (%d -> %d)", i, offsets[i],
+               offsets[i + 1]);
+      h->err = msg;
+      return RRTX_E_INVALID;
+    }
+    if (cnt > lim) {
+      snprintf(msg, sizeof(msg), "rrtx_set_instance_obstacles: instance %d: %lld obstacles, more than %d%s", i,
+               (long long)cnt, lim, lim == rppk::MAX_OBS ? "" : " (RRTX_ALGO_RS)");
+      h->err = msg;
+      return RRTX_E_INVALID;
+    }
+    if (cnt > m_max) m_max = (int)cnt;
+  }
+  const int64_t total = offsets[B];
+  if (total > 0 && !oxyr) {
+    snprintf(msg, sizeof(msg), "rrtx_set_instance_obstacles: oxyr is NULL, %lld rows expected", (long long)total);
+    h->err = msg;
+    return RRTX_E_INVALID;
+  }
+  int rc = obs_upload(h, oxyr, total);
+  if (rc) return rc;
+  for (int i = 0; i < B; i++) {
+    Inst& I = h->host_inst[i];
+    I.obs_base = offsets[i];
+    I.obs_m = offsets[i + 1] - offsets[i];
+  }
+  h->inst_dirty = true;
+  h->m_max = m_max;
   return RRTX_OK;
 }
 
@@ -668,10 +753,11 @@ int rrtx_plan_begin(rrtx_handle* h) {
   if (c.algo == RRTX_ALGO_BITSTAR) {
     // BIT*: one launch, one lane per instance (rrt_bitstar.hip.h); obstacle thresholds are size ** 2 (rrt_08:381)
     for (int i = 0; i < B; i++) {
-      h->bcfg[i].m = c.m;
-      h->bcfg[i].ox = c.ox;
-      h->bcfg[i].oy = c.oy;
-      h->bcfg[i].othr = c.othr;
+      const Inst& I = h->host_inst[i];
+      h->bcfg[i].m = I.obs_m;
+      h->bcfg[i].ox = c.ox + I.obs_base;
+      h->bcfg[i].oy = c.oy + I.obs_base;
+      h->bcfg[i].othr = c.othr + I.obs_base;
     }
     HIPCHK(h, hipMemcpyAsync(h->ba.cfg, h->bcfg.data(), sizeof(rpp::BitCfg) * B, hipMemcpyHostToDevice, h->stream));
     if (h->trace_inst >= 0 && !h->ba.tr_a) {
@@ -683,7 +769,7 @@ int rrtx_plan_begin(rrtx_handle* h) {
     h->ba.trace_inst = h->trace_inst;
     // one wave per instance when the per-vertex state fits LDS (rrt_bitstar_wave.hip.h); else one lane per instance
     const char* bk = getenv("RRTX_BITSTAR");
-    R.bit_wave = c.m <= rppb::OB && c.max_iter + 2 <= rppb::VL && !(bk && !strcmp(bk, "lane"));
+    R.bit_wave = h->m_max <= rppb::OB && c.max_iter + 2 <= rppb::VL && !(bk && !strcmp(bk, "lane"));
     if (!h->bit_queue) {
       int rc2;
       if ((rc2 = dalloc(h, &h->bit_queue, B))) return rc2;
@@ -709,11 +795,12 @@ int rrtx_plan_begin(rrtx_handle* h) {
     // as long as the shape's obstacle tile and near-candidate capacity fit the problem
     const int need_nu = estimate_near_capacity(h->p);
     int tpb = 256;
-    if (B > 1280 && c.m <= rppk2s::MAX_OBS && need_nu <= rppk2s::NU) tpb = 128;
-    if (B > 2560 && c.m <= rppk2t::MAX_OBS && need_nu <= rppk2t::NU) tpb = 64;
+    const int m = h->m_max;   // every instance's list must fit the shape's obstacle tile
+    if (B > 1280 && m <= rppk2s::MAX_OBS && need_nu <= rppk2s::NU) tpb = 128;
+    if (B > 2560 && m <= rppk2t::MAX_OBS && need_nu <= rppk2t::NU) tpb = 64;
     if (const char* e = getenv("RRTX_TPB")) {
       const int v = atoi(e);
-      tpb = (v == 64 && c.m <= rppk2t::MAX_OBS) ? 64 : (v == 128 && c.m <= rppk2s::MAX_OBS) ? 128 : 256;
+      tpb = (v == 64 && m <= rppk2t::MAX_OBS) ? 64 : (v == 128 && m <= rppk2s::MAX_OBS) ? 128 : 256;
     }
     v2_tpb = tpb;
   }
@@ -930,7 +1017,7 @@ static int plan_finish(rrtx_handle* h) {
         if (res[i].status & RRTX_ST_OVERFLOW) redo.push_back(i);
       if (redo.empty() || shape == 0) break;
       shape = shape == 64 ? 128 : shape == 128 ? 256 : 0;
-      if (shape && c.m > v2_shape_maxobs(shape)) continue;
+      if (shape && h->m_max > v2_shape_maxobs(shape)) continue;
       int rc2 = replan(redo, shape);
       if (rc2) return rc2;
     }
@@ -1505,7 +1592,8 @@ int rrtx_smooth_paths(int32_t device, int32_t n_jobs, const double* paths_xy, co
     osz[k] = obst_xyr[3 * k + 2];
   }
   double *d_in = nullptr, *d_out = nullptr, *d_ox = nullptr, *d_oy = nullptr, *d_osz = nullptr;
-  int32_t *d_n = nullptr, *d_on = nullptr, *d_st = nullptr;
+  int32_t *d_n = nullptr, *d_on = nullptr, *d_st = nullptr, *d_obs = nullptr;
+  const int32_t obs_rows[2] = {0, m};   // every job: rows 0 .. m-1 (obs_stride 0)
   rpp::MT* d_rng = nullptr;
   int rc = RRTX_OK;
   auto A = [&](void** q, size_t bytes) { if (rc == RRTX_OK && hipMalloc(q, bytes ? bytes : 8) != hipSuccess) rc = RRTX_E_HIP; };
@@ -1517,6 +1605,7 @@ int rrtx_smooth_paths(int32_t device, int32_t n_jobs, const double* paths_xy, co
   A((void**)&d_n, sizeof(int32_t) * n_jobs);
   A((void**)&d_on, sizeof(int32_t) * n_jobs);
   A((void**)&d_st, sizeof(int32_t) * n_jobs);
+  A((void**)&d_obs, sizeof(obs_rows));
   A((void**)&d_rng, sizeof(rpp::MT) * n_jobs);
   std::vector<int32_t> st(n_jobs, 0);
   if (rc == RRTX_OK) {
@@ -1525,10 +1614,11 @@ int rrtx_smooth_paths(int32_t device, int32_t n_jobs, const double* paths_xy, co
               hipMemcpy(d_oy, oy.data(), sizeof(double) * (m + 1), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(d_osz, osz.data(), sizeof(double) * (m + 1), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(d_n, path_n, sizeof(int32_t) * n_jobs, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d_obs, obs_rows, sizeof(obs_rows), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(d_rng, rng.data(), sizeof(rpp::MT) * n_jobs, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
-      rpps::SmoothArgs a{d_in, in_stride, d_n, 1, d_rng, (int64_t)sizeof(rpp::MT), d_ox, d_oy, d_osz, m, max_iter,
-                         d_out, out_stride, d_on, d_st};
+      rpps::SmoothArgs a{d_in, in_stride, d_n, 1, d_rng, (int64_t)sizeof(rpp::MT), d_ox, d_oy, d_osz, d_obs, 0,
+                         max_iter, d_out, out_stride, d_on, d_st};
       hipLaunchKernelGGL(rpps::smooth_kernel, dim3(n_jobs), dim3(64), 0, 0, a, n_jobs);
       ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
            hipMemcpy(out_xy, d_out, sizeof(double) * 2 * (size_t)out_stride * n_jobs, hipMemcpyDeviceToHost) == hipSuccess &&
@@ -1539,7 +1629,7 @@ int rrtx_smooth_paths(int32_t device, int32_t n_jobs, const double* paths_xy, co
     if (!ok) rc = RRTX_E_HIP;
   }
   for (void* q : {(void*)d_in, (void*)d_out, (void*)d_ox, (void*)d_oy, (void*)d_osz, (void*)d_n, (void*)d_on, (void*)d_st,
-                  (void*)d_rng})
+                  (void*)d_obs, (void*)d_rng})
     if (q) hipFree(q);
   if (rc != RRTX_OK) return rc;
   for (int j = 0; j < n_jobs; j++) {
@@ -1553,24 +1643,29 @@ int rrtx_smooth_paths(int32_t device, int32_t n_jobs, const double* paths_xy, co
 int rrtx_smooth_planned(rrtx_handle* h, int32_t max_iter) {
   if (!h || max_iter < 0) return RRTX_E_INVALID;
   if (!h->planned || (h->p.algo != RRTX_ALGO_RRT && h->p.algo != RRTX_ALGO_RRT_STAR)) return RRTX_E_STATE;
-  if (h->m > rpps::MOB) return RRTX_E_INVALID;
+  if (h->m_max > rpps::MOB) return RRTX_E_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
   const int B = h->n_inst;
   int rc;
-  if (!h->sm_osz) {
+  if (!h->sm_xy) {
     h->sm_stride = rpps::PC;
-    if ((rc = dalloc(h, &h->sm_osz, rppk::MAX_OBS))) return rc;
     if ((rc = dalloc(h, &h->sm_xy, (size_t)2 * h->sm_stride * B))) return rc;
     if ((rc = dalloc(h, &h->sm_n, B))) return rc;
     if ((rc = dalloc(h, &h->sm_status, B))) return rc;
+    if ((rc = dalloc(h, &h->sm_obs, (size_t)2 * B))) return rc;
   }
-  std::vector<double> osz(rppk::MAX_OBS, 0.0);
-  for (int k = 0; k < h->m; k++) osz[k] = h->obst[3 * k + 2];
-  HIPCHK(h, hipMemcpyAsync(h->sm_osz, osz.data(), sizeof(double) * rppk::MAX_OBS, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));   // `osz` is a local; the kernel below is ordered after it anyway
+  // each instance's path against its obstacle rows as set NOW (sizes as given: h->sm_osz) -- the table may have been
+  // replaced since the plan, and the rows the planned Inst records name are then stale
+  std::vector<int32_t> rows((size_t)2 * B);
+  for (int i = 0; i < B; i++) {
+    rows[2 * i] = h->host_inst[i].obs_base;
+    rows[2 * i + 1] = h->host_inst[i].obs_m;
+  }
+  HIPCHK(h, hipMemcpyAsync(h->sm_obs, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, h->stream));
   Ctx& c = h->c;
-  rpps::SmoothArgs a{c.path_xy, c.path_cap, &c.inst[0].path_n, (int64_t)(sizeof(Inst) / sizeof(int32_t)),
-                     &c.inst[0].rng, (int64_t)sizeof(Inst), c.ox, c.oy, h->sm_osz, h->m, max_iter,
+  const int64_t istride = (int64_t)(sizeof(Inst) / sizeof(int32_t));
+  rpps::SmoothArgs a{c.path_xy, c.path_cap, &c.inst[0].path_n, istride,
+                     &c.inst[0].rng, (int64_t)sizeof(Inst), c.ox, c.oy, h->sm_osz, h->sm_obs, 2, max_iter,
                      h->sm_xy, h->sm_stride, h->sm_n, h->sm_status};
   hipLaunchKernelGGL(rpps::smooth_kernel, dim3(B), dim3(64), 0, h->stream, a, B);
   HIPCHK(h, hipGetLastError());

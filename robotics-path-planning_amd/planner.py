@@ -646,7 +646,8 @@ class BatchPlanner:
     def __init__(self, algo, seeds, start, goal, obstacle_list, rand_area, expand_dis=3.0, path_resolution=0.5,
                  goal_sample_rate=5, max_iter=500, play_area=None, robot_radius=0.0, sobol_sampler=False,
                  connect_circle_dist=50.0, search_until_max_iter=False, device=0, starts=None, goals=None,
-                 curvature=1.0, goal_yaw_th=float(np.deg2rad(1.0)), goal_xy_th=0.5, step_size=0.2, devices=None):
+                 curvature=1.0, goal_yaw_th=float(np.deg2rad(1.0)), goal_xy_th=0.5, step_size=0.2, devices=None,
+                 instance_obstacles=None):
         """algo: "rrt" (rrt_01/02), "rrt_star" (rrt_04), "informed" (rrt_07: expand_dis, goal_sample_rate, max_iter,
         sobol_sampler as in its constructor :1029-1042), "bitstar" (rrt_08: max_iter = maxIter, rand_area = randArea
         :140-168), and the pose planners (start / goal = [x, y, yaw]; curvature, goal thresholds and, for Reeds-Shepp,
@@ -655,7 +656,9 @@ class BatchPlanner:
         `starts` / `goals`: per-instance [x, y] (pose planners: [x, y, yaw]; a missing yaw keeps `start[2]` /
         `goal[2]`).  For "informed" and "bitstar" the rotation to the world frame and c_min (rrt_07:1054-1068,
         rrt_08:189-202) are computed per instance on the host with numpy, as the reference does per planner object.
-        `devices`: HIP device ordinals to shard over (default: [device])."""
+        `devices`: HIP device ordinals to shard over (default: [device]).
+        `instance_obstacles`: one obstacle list of (x, y, size) per instance, in place of the shared `obstacle_list`
+        (which must then be None): a batch over many maps in one launch (rrtx_set_instance_obstacles)."""
         from . import sharding
         a = {"rrt": _abi.ALGO_RRT, "rrt_star": _abi.ALGO_RRT_STAR, "rrt_dubins": _abi.ALGO_RRT_DUBINS,
              "rrt_star_dubins": _abi.ALGO_DUBINS, "rrt_star_reeds_shepp": _abi.ALGO_RS, "informed": _abi.ALGO_INFORMED,
@@ -664,6 +667,15 @@ class BatchPlanner:
         self.pose = a in (_abi.ALGO_RRT_DUBINS, _abi.ALGO_DUBINS, _abi.ALGO_RS)
         self.algo = a
         n = len(self.seeds)
+        if instance_obstacles is not None:
+            if obstacle_list is not None:
+                raise ValueError("BatchPlanner: give either obstacle_list or instance_obstacles, not both")
+            instance_obstacles = [list(lst) for lst in instance_obstacles]
+            if len(instance_obstacles) != n:
+                raise ValueError("BatchPlanner: %d instance_obstacles lists for %d instances"
+                                 % (len(instance_obstacles), n))
+        self.instance_obstacles = instance_obstacles
+        self.obstacle_list = obstacle_list
         self.devices = [int(device)] if devices is None else [int(d) for d in devices]
         if not self.devices or n < len(self.devices):
             raise ValueError("BatchPlanner: %d instances cannot be sharded over %d handles" % (n, len(self.devices)))
@@ -689,7 +701,10 @@ class BatchPlanner:
                                     n_instances=hi - lo, device=dev, curvature=curvature, goal_yaw_th=goal_yaw_th,
                                     goal_xy_th=goal_xy_th, step_size=step_size)
                 self.handles.append(h)
-                h.set_obstacles(obstacle_list)
+                if instance_obstacles is None:
+                    h.set_obstacles(obstacle_list)
+                else:
+                    h.set_instance_obstacles(instance_obstacles[lo:hi])
                 h.seed_instances(self.seeds[lo:hi])
                 if starts is not None or goals is not None:
                     for i in range(lo, hi):
@@ -770,14 +785,15 @@ class BatchPlanner:
 
     def smooth(self, max_iter):
         """path_smoothing(path, max_iter, obstacle_list) (rrt_04:1447-1479) on every planned path, on the device, each
-        instance continuing its own random stream (as the driver does at :1558-1559)."""
+        instance continuing its own random stream (as the driver does at :1558-1559), against its own obstacle list."""
         for h in self.handles:
             h.smooth_planned(max_iter)
         return [self._loc(i)[0].get_smoothed_path(self._loc(i)[1]) for i in range(len(self.seeds))]
 
     def export_npz(self, filename, instances=None):
         """Compact on-disk form of the planned trees for plotting / regression diffs: per instance
-        (x, y, cost, parent) as the reference's node_list holds them, the returned path, path cost, seed."""
+        (x, y, cost, parent) as the reference's node_list holds them, the returned path, path cost, seed; with
+        `instance_obstacles`, each instance's list as `obstacles_k` ((m, 3): x, y, size)."""
         ids = list(range(len(self.seeds))) if instances is None else list(instances)
         pc, nn, st = self.results()
         out = dict(seeds=np.array([self.seeds[i] for i in ids], dtype=np.int64), path_cost=pc[ids], n_nodes=nn[ids],
@@ -788,6 +804,8 @@ class BatchPlanner:
             p = h.get_path(j)
             out["x_%d" % k], out["y_%d" % k], out["cost_%d" % k], out["parent_%d" % k] = x, y, cost, parent
             out["path_%d" % k] = np.zeros((0, 2)) if p is None else p
+            if self.instance_obstacles is not None:
+                out["obstacles_%d" % k] = np.array(self.instance_obstacles[i], dtype=np.float64).reshape(-1, 3)
         np.savez_compressed(filename, **out)
         return filename
 
