@@ -114,6 +114,10 @@ struct Ctx {
   int32_t gsh, gn, gcells, gpool_blocks;
   int32_t grid;       // 1: passes of trees of at least grid_min nodes are answered from the index (RRTX_GRID)
   int32_t grid_min;
+  // cost propagation of the same kernel and shape: after prop_vec nodes on the scalar path a walk continues with one
+  // sibling chain per lane (RRTX_PROP_VEC; < 0: scalar path only); prop_cap bounds its LDS list of pending chains
+  // (RRTX_PROP_CAP: test knob)
+  int32_t prop_vec, prop_cap;
 };
 constexpr int GRID_CAP0 = 16, GRID_CAP1 = 16;
 

@@ -730,6 +730,12 @@ int rrtx_plan_begin(rrtx_handle* h) {
   if (const char* e = getenv("RRTX_GRID")) c.grid = c.grid && atoi(e) != 0;
   c.grid_min = 4096;
   if (const char* e = getenv("RRTX_GRID_MIN")) c.grid_min = atoi(e) > 0 ? atoi(e) : 0;
+  // rrt_04 kernel, one-wave shape: a cost propagation still running after prop_vec nodes continues one sibling chain per
+  // lane (RRTX_PROP_VEC, < 0: one node per round trip throughout); RRTX_PROP_CAP: test knob, fewer pending chains in LDS
+  c.prop_vec = 8;
+  if (const char* e = getenv("RRTX_PROP_VEC")) c.prop_vec = atoi(e);
+  c.prop_cap = 1 << 30;
+  if (const char* e = getenv("RRTX_PROP_CAP")) c.prop_cap = atoi(e) > 0 ? atoi(e) : 0;
   // The staged per-instance start state (RNG, start / goal) lives on the device too: uploaded when the host changed it,
   // copied device -> device at every plan (2.7 KB per instance: 44 MB of pageable-memory upload per plan of 16 384 instances)
   if (!h->d_inst0) {

@@ -23,12 +23,15 @@ h.plan()
 s = h.get_stats()
 ph = h.get_phase_cycles()
 names = {0: "sample", 1: "nearest scan", 2: "ext steer", 3: "ext collision", 4: "near scan", 5: "exact+dedup",
-         6: "choose edges", 7: "choose cost/min", 8: "rewire edges", 9: "rewire seq+propagate+append", 11: "bookkeeping",
-         12: "goal", 15: "loop",
-         13: "  (choose edges: hypot only)", 14: "  (choose edges: atan2 only)", 10: "  (choose edges: cos|sin + stores)"}
-tot = float(ph.sum() - ph[13] - ph[14] - ph[10])
+         6: "choose edges", 7: "choose cost/min", 8: "rewire edges", 13: "rewire seq: pick+links",
+         14: "rewire seq: propagate", 9: "rewire seq: tail+append", 11: "bookkeeping", 12: "goal", 15: "loop"}
+tot = float(ph.sum() - ph[10])   # every other slot is a disjoint span of the iteration (slot 10 counts lane walks)
 print("instances", B, "max_iter", it, "kernel_ms", s["kernel_ms"], "alg GB/s", s["algorithmic_bytes"] / 1e6 / s["kernel_ms"])
-for k in sorted(names):
+for k in (15, 0, 1, 2, 3, 4, 5, 6, 7, 8, 13, 14, 9, 11, 12):
     print("  %-30s %6.2f%%  %.1f cycles/iter/inst" % (names[k], 100.0 * ph[k] / tot if tot else 0, ph[k] / max(s["iterations"], 1)))
+rw = ph[9] + ph[13] + ph[14]
+print("  %-30s %6.2f%%  %.1f cycles/iter/inst" % ("(rewire seq+propagate+append)", 100.0 * rw / tot if tot else 0,
+                                                  rw / max(s["iterations"], 1)))
 print("  total cycles/iter/inst %.1f" % (tot / max(s["iterations"], 1)))
+print("lane walks finished", int(ph[10]) & ((1 << 40) - 1), "pending list full", int(ph[10]) >> 40)
 print({k: s[k] for k in ("iterations", "edges_unique", "near_unique", "rewires", "propagated", "exact_rescans")})
