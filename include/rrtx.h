@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define RRTX_ABI_VERSION 6   /* 6: rrtx_set_instance_obstacles; 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
+#define RRTX_ABI_VERSION 6   /* 6: rrtx_set_instance_obstacles (and RRTX_ALGO_LQR_RRT_STAR: a new algo value, no layout change); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
                                 rrtx_copy_results_device, per-instance yaw and informed rotation; 4: rrtx_plan_many,
                                 rrtx_selfcheck, rrtx_stats.main_shape / main_f32, rrtx_plan_begin / _step, rrtx_set_launch_bound,
                                 RRTX_ST_REF_HANGS, rrtx_rccl_* */
@@ -54,6 +54,12 @@ enum { RRTX_ALGO_RRT = 0,       /* rrt_01 RRT.planning :71-101 */
        RRTX_ALGO_RS = 6         /* rrt_06 RRT.planning :1530-1570 (RRT*-Reeds-Shepp incl. try_goal_path :1572-1582; poses,
                                    curvature, step_size and goal thresholds; node capacity 2 * max_iter + 2; the sampler is
                                    always get_random_node :1658-1666, as in the reference's loop :1539) */ };
+/* rrt_09 LQRRRTStar.planning :1120-1155 (LQR-RRT*): steer = LQR rollout + resampling (rpp_lqr.h).  Reads step_size,
+   goal_xy_th, expand_dis, connect_circle_dist, play_area, robot_radius, sampler and search_until_max_iter (the
+   `search_until_max_iter` keyword of planning()); node capacity max_iter + 1; RRTX_ST_REF_RAISES where the reference
+   raises (an LQR rollout that never reaches its target: IndexError at :1184).  Paths: rrtx_get_path; edge polylines:
+   rrtx_get_polylines (regenerated from each node's edge endpoints). */
+#define RRTX_ALGO_LQR_RRT_STAR 7
 enum { RRTX_SAMPLER_MT = 0,     /* get_random_node        rrt_04:1132-1139 */
        RRTX_SAMPLER_SOBOL = 1   /* get_random_node_sobol  rrt_04:1142-1153 */ };
 

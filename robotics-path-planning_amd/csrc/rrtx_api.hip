@@ -25,6 +25,7 @@
 #include "rrt_bitstar.hip.h"
 #include "rrt_bitstar_wave.hip.h"
 #include "path_smooth.hip.h"
+#include "rrt_lqr.hip.h"
 
 using rppk::Ctx;
 using rppk::Inst;
@@ -151,6 +152,7 @@ struct rrtx_handle {
   rppi::InformedArgs* d_iargs = nullptr;
   rppd::DubArgs da;         // RRT*-Dubins device arrays
   rppb::BitArgs ba;         // BIT* device arrays
+  rppl::LqrArgs la;         // LQR-RRT* device arrays (edge endpoints, near-entry scratch)
   std::vector<rpp::BitCfg> bcfg;
   // path smoothing on the planned paths (rrtx_smooth_planned)
   double* sm_osz = nullptr;   // obstacle sizes as given (no robot radius), device: the fourth column of obs_buf
@@ -308,7 +310,8 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
   if (!p || !out) return RRTX_E_INVALID;
   *out = nullptr;
   if (p->abi_version != RRTX_ABI_VERSION) return RRTX_E_INVALID;
-  if (p->algo != RRTX_ALGO_RRT && p->algo != RRTX_ALGO_RRT_STAR && p->algo != RRTX_ALGO_INFORMED && p->algo != RRTX_ALGO_DUBINS && p->algo != RRTX_ALGO_BITSTAR && p->algo != RRTX_ALGO_RRT_DUBINS && p->algo != RRTX_ALGO_RS) return RRTX_E_INVALID;
+  if (p->algo != RRTX_ALGO_RRT && p->algo != RRTX_ALGO_RRT_STAR && p->algo != RRTX_ALGO_INFORMED && p->algo != RRTX_ALGO_DUBINS && p->algo != RRTX_ALGO_BITSTAR && p->algo != RRTX_ALGO_RRT_DUBINS && p->algo != RRTX_ALGO_RS && p->algo != RRTX_ALGO_LQR_RRT_STAR) return RRTX_E_INVALID;
+  if (p->algo == RRTX_ALGO_LQR_RRT_STAR && !(p->step_size > 0.0)) return RRTX_E_INVALID;
   if (p->algo == RRTX_ALGO_RS && (!(p->step_size > 0.0) || !(p->curvature > 0.0))) return RRTX_E_INVALID;
   if (p->n_instances < 1 || p->max_iter < 0 || !(p->path_resolution > 0.0) || !(p->expand_dis >= 0.0))
     return RRTX_E_INVALID;
@@ -380,6 +383,7 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
     if ((rc = dalloc(h, &c.xq, tot))) return rc;     // 16-bit mirror: the one pass per iteration of the rrt_07 kernel
   if ((rc = dalloc(h, &c.results, h->n_inst))) return rc;
   c.path_cap = (int32_t)(cap + 1 < 8192 ? cap + 1 : 8192);
+  if (p->algo == RRTX_ALGO_LQR_RRT_STAR) c.path_cap = 4096;   // paths are edge polylines (~20 points per edge)
   if ((rc = dalloc(h, &c.path_xy, (size_t)h->n_inst * c.path_cap * 2))) return rc;
   double* dr2;
   if ((rc = obs_reserve(h, rppk::MAX_OBS))) return rc;   // every instance starts on the empty shared list
@@ -443,6 +447,23 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
       c2.num_cells = std::ceil((p->rand_max - p->rand_min) / 0.01);   // RTree num_cells (rrt_08:42-44, :165-168)
       c2.max_iter = p->max_iter;
     }
+  }
+  memset(&h->la, 0, sizeof(h->la));
+  if (p->algo == RRTX_ALGO_LQR_RRT_STAR) {
+    // node capacity max_iter + 1 (one node per iteration at most, rrt_09:1133); the edge record of a node is its four
+    // endpoints, from which the polyline is regenerated (rpp_lqr.h)
+    rppl::LqrArgs& a = h->la;
+    if ((rc = dalloc(h, &a.ef, 4 * tot))) return rc;
+    if ((rc = dalloc(h, &a.nl, tot))) return rc;
+    if ((rc = dalloc(h, &a.dscr, tot))) return rc;
+    if ((rc = dalloc(h, &a.cex, tot))) return rc;
+    if ((rc = dalloc(h, &a.cey, tot))) return rc;
+    if ((rc = dalloc(h, &a.clen, tot))) return rc;
+    if ((rc = dalloc(h, &a.cflag, tot))) return rc;
+    if ((rc = dalloc(h, &a.moved, tot))) return rc;
+    a.step = p->step_size;
+    a.nt = rpp::lqr_nt(p->step_size);
+    a.goal_xy_th = p->goal_xy_th;
   }
   memset(&h->da, 0, sizeof(h->da));
   if (is_pose_tree(p->algo)) {
@@ -930,6 +951,8 @@ int rrtx_plan_step(rrtx_handle* h, int32_t* n_pending) {
       hipLaunchKernelGGL(rppd::rrt_dubins_kernel, dim3(B), dim3(rppd::TPB), 0, h->stream, c, h->da, h->chunk_iters);
     else if (c.algo == RRTX_ALGO_RS)
       hipLaunchKernelGGL(rppr::rrt_rs_kernel, dim3(B), dim3(rppr::TPB), 0, h->stream, c, h->da, h->chunk_iters);
+    else if (c.algo == RRTX_ALGO_LQR_RRT_STAR)
+      hipLaunchKernelGGL(rppl::rrt_lqr_kernel, dim3(B), dim3(rppl::TPB), 0, h->stream, c, h->la, h->chunk_iters);
     else
       hipLaunchKernelGGL(rppk::rrt_plan_kernel, dim3(B), dim3(rppk::TPB), 0, h->stream, c, h->chunk_iters);
     HIPCHK(h, hipGetLastError());
@@ -1215,6 +1238,7 @@ static int plan_finish(rrtx_handle* h) {
                         : is_dubins(c.algo)            ? rppd::TPB
                         : c.algo == RRTX_ALGO_RS       ? rppr::TPB
                         : c.algo == RRTX_ALGO_BITSTAR  ? 64
+                        : c.algo == RRTX_ALGO_LQR_RRT_STAR ? rppl::TPB
                                                        : rppk::TPB;
   s.main_f32 = use_v2 ? 1 : 0;   // kept for the ABI v5 layout: 1 whenever the RRT* iteration kernel ran
   s.plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - R.t0).count();
@@ -1230,6 +1254,9 @@ static int plan_finish(rrtx_handle* h) {
       h->err += "RRTX_ST_REF_RAISES: the reference raises inside reeds_shepp_path_planning (ZeroDivisionError "
                 "rrt_06:1183/:1207 or a math domain error); ";
     if (unsupported) h->err += "RRTX_ST_UNSUPPORTED: a reference code path the kernel does not restate was reached; ";
+    if (raises && c.algo == RRTX_ALGO_LQR_RRT_STAR)
+      h->err += "(LQR-RRT*: an LQR rollout never reached its target, IndexError rrt_09:1184, or a rewire closed a parent "
+                "cycle); ";
     h->err += "the affected instances carry the bit in their status word and have no result, all others are complete";
     return RRTX_PARTIAL;
   }
@@ -1463,11 +1490,85 @@ int rrtx_get_path_yaw(rrtx_handle* h, int32_t instance, double* yaw, int32_t cap
   return RRTX_OK;
 }
 
+// LQR-RRT*: Node.path_x / path_y regenerated on the device from each node's edge endpoints (rpp_lqr.h, the same code
+// the planner kernel runs); the root has none
+static int lqr_polylines(rrtx_handle* h, int32_t instance, int32_t* plen, int32_t cap_nodes, double* px, double* py,
+                         int64_t cap_points, int64_t* n_points_out) {
+  Result r;
+  HIPCHK(h, hipMemcpy(&r, h->c.results + instance, sizeof(r), hipMemcpyDeviceToHost));
+  const int n = r.n_nodes;
+  const int64_t off = (int64_t)instance * h->stride;
+  int32_t* dcnt = nullptr;
+  int64_t* doff = nullptr;
+  double *dx = nullptr, *dy = nullptr;
+  auto release = [&]() {
+    if (dcnt) (void)hipFree(dcnt);
+    if (doff) (void)hipFree(doff);
+    if (dx) (void)hipFree(dx);
+    if (dy) (void)hipFree(dy);
+  };
+  if (hipMalloc((void**)&dcnt, sizeof(int32_t) * (n + 1)) != hipSuccess ||
+      hipMalloc((void**)&doff, sizeof(int64_t) * (n + 1)) != hipSuccess) {
+    release();
+    h->err = "rrtx_get_polylines: device allocation failed";
+    return RRTX_E_HIP;
+  }
+  const double* ef = h->la.ef + 4 * off;
+  const int32_t* par = h->c.parent + off;
+  hipLaunchKernelGGL(rppl::lqr_polylines_kernel, dim3((n + 63) / 64), dim3(64), 0, h->stream, ef, par, n, h->la.step,
+                     h->la.nt, dcnt, (const int64_t*)nullptr, (double*)nullptr, (double*)nullptr);
+  std::vector<int32_t> cnt(n);
+  std::vector<int64_t> po(n + 1, 0);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+      hipMemcpy(cnt.data(), dcnt, sizeof(int32_t) * n, hipMemcpyDeviceToHost) != hipSuccess) {
+    release();
+    h->err = "rrtx_get_polylines: count pass failed";
+    return RRTX_E_HIP;
+  }
+  for (int i = 0; i < n; i++) po[i + 1] = po[i] + cnt[i];
+  const int64_t total = po[n];
+  *n_points_out = total;
+  if ((!plen && !px && !py) || total == 0) {
+    release();
+    if ((plen || px || py) && cap_nodes < n) return RRTX_E_CAPACITY;
+    for (int i = 0; plen && i < n; i++) plen[i] = cnt[i];
+    return RRTX_OK;
+  }
+  if (cap_nodes < n || cap_points < total) {
+    release();
+    return RRTX_E_CAPACITY;
+  }
+  std::vector<double> bx(total), by(total);
+  if (hipMalloc((void**)&dx, sizeof(double) * total) != hipSuccess || hipMalloc((void**)&dy, sizeof(double) * total) != hipSuccess ||
+      hipMemcpy(doff, po.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice) != hipSuccess) {
+    release();
+    h->err = "rrtx_get_polylines: device allocation failed";
+    return RRTX_E_HIP;
+  }
+  hipLaunchKernelGGL(rppl::lqr_polylines_kernel, dim3((n + 63) / 64), dim3(64), 0, h->stream, ef, par, n, h->la.step,
+                     h->la.nt, dcnt, (const int64_t*)doff, dx, dy);
+  const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess &&
+                  hipMemcpy(bx.data(), dx, sizeof(double) * total, hipMemcpyDeviceToHost) == hipSuccess &&
+                  hipMemcpy(by.data(), dy, sizeof(double) * total, hipMemcpyDeviceToHost) == hipSuccess;
+  release();
+  if (!ok) {
+    h->err = "rrtx_get_polylines: point pass failed";
+    return RRTX_E_HIP;
+  }
+  for (int i = 0; plen && i < n; i++) plen[i] = cnt[i];
+  for (int64_t q = 0; q < total; q++) {
+    if (px) px[q] = bx[q];
+    if (py) py[q] = by[q];
+  }
+  return RRTX_OK;
+}
+
 int rrtx_get_polylines(rrtx_handle* h, int32_t instance, int32_t* plen, int32_t cap_nodes, double* px, double* py,
                        int64_t cap_points, int64_t* n_points_out) {
   if (!h || !n_points_out || instance < 0 || instance >= h->n_inst) return RRTX_E_INVALID;
-  if (!h->planned || !is_pose_tree(h->p.algo)) return RRTX_E_STATE;
+  if (!h->planned || !(is_pose_tree(h->p.algo) || h->p.algo == RRTX_ALGO_LQR_RRT_STAR)) return RRTX_E_STATE;
   HIPCHK(h, hipSetDevice(h->device));
+  if (h->p.algo == RRTX_ALGO_LQR_RRT_STAR) return lqr_polylines(h, instance, plen, cap_nodes, px, py, cap_points, n_points_out);
   Result r;
   HIPCHK(h, hipMemcpy(&r, h->c.results + instance, sizeof(r), hipMemcpyDeviceToHost));
   const int n = r.n_nodes;
@@ -1648,7 +1749,8 @@ int rrtx_smooth_paths(int32_t device, int32_t n_jobs, const double* paths_xy, co
 
 int rrtx_smooth_planned(rrtx_handle* h, int32_t max_iter) {
   if (!h || max_iter < 0) return RRTX_E_INVALID;
-  if (!h->planned || (h->p.algo != RRTX_ALGO_RRT && h->p.algo != RRTX_ALGO_RRT_STAR)) return RRTX_E_STATE;
+  if (!h->planned || (h->p.algo != RRTX_ALGO_RRT && h->p.algo != RRTX_ALGO_RRT_STAR && h->p.algo != RRTX_ALGO_LQR_RRT_STAR))
+    return RRTX_E_STATE;
   if (h->m_max > rpps::MOB) return RRTX_E_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
   const int B = h->n_inst;

@@ -557,6 +557,162 @@ class RRTStarReedsShepp(RRTStarDubins):
         self.path_yaw = h.get_path_yaw(0)
 
 
+class LQRNode:
+    """LQRRRTStar.Node (rrt_09:1042-1051)."""
+
+    def __init__(self, x, y):
+        self.x = x
+        self.y = y
+        self.path_x = []
+        self.path_y = []
+        self.parent = None
+        self.cost = 0.0
+
+
+_lqr_checked = []
+
+
+def lqr_matmul_check():
+    """The device restates numpy's `A @ x` of the LQR model (rrt_09:960) with row 0 fused (csrc/rpp_lqr.h).  Compares
+    this host's numpy with that form on a few fixed states, once per process; warns (RrtxParityWarning) on a mismatch:
+    the planner then still runs, but matches the reference run on this host only up to those roundings."""
+    if _lqr_checked:
+        return _lqr_checked[0]
+    from fractions import Fraction
+    A = np.array([[0.1, 1.0], [0.0, 0.1]])
+    bad = 0
+    rs = np.random.RandomState(12345)
+    for _ in range(64):
+        x = rs.uniform(-20.0, 20.0, 2) * (10.0 ** rs.randint(-6, 2, 2))
+        got = (A @ x.reshape(2, 1))[0, 0]
+        want = float(Fraction(0.1) * Fraction(float(x[0])) + Fraction(float(x[1])))
+        bad += got != want
+    _lqr_checked.append(bad)
+    if bad:
+        import warnings
+        warnings.warn("this host's numpy rounds the LQR model's A @ x unfused in %d of 64 states; LQRRRTStar matches the "
+                      "reference only where it rounds fused (csrc/rpp_lqr.h)" % bad, _abi.RrtxParityWarning)
+    return bad
+
+
+class LQRRRTStar:
+    """Drop-in for rrt_09's `LQRRRTStar` (10_path_planning_01_rrt_09_lqr_rrt_star.py:1041-1450): RRT* whose steer is an
+    LQR rollout to the target, resampled at `step_size` (csrc/rpp_lqr.h).  `planning(animation, search_until_max_iter=True)`
+    as the reference defines it (:1120): the method's keyword, not the constructor's, decides the early exit.
+    `node_list` is filled lazily after planning (x, y, cost, parent, path_x / path_y regenerated from each node's edge
+    record); `draw_graph` draws after the fact.  Where the reference raises (an LQR rollout that never reaches its
+    target: IndexError at :1184) planning raises RrtxError."""
+    Node = LQRNode
+    AreaBounds = AreaBounds
+
+    def __init__(self, start, goal, obstacle_list, rand_area, expand_dis=3.0, path_resolution=0.5, goal_sample_rate=10,
+                 max_iter=500, play_area=None, robot_radius=0.0, sobol_sampler=True, connect_circle_dist=50.0,
+                 search_until_max_iter=False, curvature=1.0, goal_xy_th=0.5, step_size=0.2, device=0):
+        self.start = LQRNode(start[0], start[1])
+        self.end = LQRNode(goal[0], goal[1])
+        self.min_rand = rand_area[0]
+        self.max_rand = rand_area[1]
+        self.play_area = AreaBounds(play_area) if play_area is not None else None
+        self._play_area_arg = play_area
+        self.expand_dis = expand_dis
+        self.path_resolution = path_resolution
+        self.goal_sample_rate = goal_sample_rate
+        self.max_iter = max_iter
+        self.obstacle_list = obstacle_list
+        self.node_list = []
+        self.robot_radius = robot_radius
+        self.sobol_sampler = sobol_sampler
+        self.sobol_inter_ = 0
+        self.connect_circle_dist = connect_circle_dist
+        self.goal_node = LQRNode(goal[0], goal[1])
+        self.search_until_max_iter = search_until_max_iter
+        self.curvature = curvature
+        self.goal_xy_th = goal_xy_th
+        self.step_size = step_size
+        self.device = device
+        self.stats = None
+        self._trace = False
+        self.trace = None
+
+    def planning(self, animation=True, search_until_max_iter=True):
+        lqr_matmul_check()
+        h = _abi.Handle(_abi.ALGO_LQR_RRT_STAR, [self.start.x, self.start.y], [self.end.x, self.end.y],
+                        [self.min_rand, self.max_rand], self.expand_dis, self.path_resolution, self.goal_sample_rate,
+                        self.max_iter, play_area=self._play_area_arg, robot_radius=self.robot_radius,
+                        sampler=_abi.SAMPLER_SOBOL if self.sobol_sampler else _abi.SAMPLER_MT,
+                        connect_circle_dist=self.connect_circle_dist,
+                        search_until_max_iter=bool(search_until_max_iter), n_instances=1, device=self.device,
+                        goal_xy_th=self.goal_xy_th, step_size=self.step_size)
+        try:
+            h.set_obstacles(self.obstacle_list)
+            st = random.getstate()
+            h.set_rng_state(0, st)
+            if self._trace:
+                h.enable_trace(0)
+            h.plan(strict=True)
+            random.setstate(h.get_rng_state(0, st[2]))
+            x, y, cost, parent = h.get_tree(0)
+            plen, px, py = h.get_polylines(0)
+            self.tree = (x, y, cost, parent)
+            self.polylines = (plen, px, py)
+            self.node_list = _LQRNodeList(x, y, cost, parent, plen, px, py)
+            path = h.get_path(0)
+            self.stats = h.get_stats()
+            if self.sobol_sampler:
+                self.sobol_inter_ = h.get_sobol_index(0)
+            if self._trace:
+                self.trace = h.get_trace()
+        finally:
+            h.close()
+        if animation:  # pragma: no cover
+            self.draw_graph()
+        return None if path is None else [[float(a), float(b)] for a, b in path]
+
+    plan = planning
+
+    def draw_graph(self, rnd=None):  # pragma: no cover
+        _PlannerBase.draw_graph(self, rnd)
+
+    plot_circle = _PlannerBase.plot_circle
+
+    def calc_dist_to_goal(self, x, y):
+        return math.hypot(x - self.end.x, y - self.end.y)
+
+
+class _LQRNodeList:
+    """Lazy node_list of LQRRRTStar: LQRNode objects made on first access, parents as object references."""
+
+    def __init__(self, x, y, cost, parent, plen, px, py):
+        self._x, self._y, self._cost, self._parent = x, y, cost, parent
+        self._off = np.concatenate([[0], np.cumsum(plen)]).astype(np.int64)
+        self._px, self._py = px, py
+        self._nodes = None
+
+    def _build(self):
+        if self._nodes is None:
+            nodes = []
+            for i in range(len(self._x)):
+                nd = LQRNode(float(self._x[i]), float(self._y[i]))
+                nd.cost = float(self._cost[i])
+                a, b = int(self._off[i]), int(self._off[i + 1])
+                nd.path_x = [float(v) for v in self._px[a:b]]
+                nd.path_y = [float(v) for v in self._py[a:b]]
+                nodes.append(nd)
+            for i, nd in enumerate(nodes):
+                nd.parent = nodes[int(self._parent[i])] if self._parent[i] >= 0 else None
+            self._nodes = nodes
+        return self._nodes
+
+    def __len__(self):
+        return len(self._x)
+
+    def __getitem__(self, i):
+        return self._build()[i]
+
+    def __iter__(self):
+        return iter(self._build())
+
+
 def path_smoothing(path, max_iter, obstacle_list, device=0):
     """Drop-in for rrt_04's module function `path_smoothing(path, max_iter, obstacle_list)` (:1447-1479): random
     shortcutting of the path `planning()` returned, drawing from CPython's global `random` stream (left exactly where
@@ -652,7 +808,8 @@ class BatchPlanner:
         sobol_sampler as in its constructor :1029-1042), "bitstar" (rrt_08: max_iter = maxIter, rand_area = randArea
         :140-168), and the pose planners (start / goal = [x, y, yaw]; curvature, goal thresholds and, for Reeds-Shepp,
         step_size as in their constructors): "rrt_dubins" (rrt_03), "rrt_star_dubins" (rrt_05),
-        "rrt_star_reeds_shepp" (rrt_06).
+        "rrt_star_reeds_shepp" (rrt_06); "lqr_rrt_star" (rrt_09: step_size, goal_xy_th; `search_until_max_iter` plays
+        the part of planning()'s keyword of the same name, :1120).
         `starts` / `goals`: per-instance [x, y] (pose planners: [x, y, yaw]; a missing yaw keeps `start[2]` /
         `goal[2]`).  For "informed" and "bitstar" the rotation to the world frame and c_min (rrt_07:1054-1068,
         rrt_08:189-202) are computed per instance on the host with numpy, as the reference does per planner object.
@@ -662,8 +819,16 @@ class BatchPlanner:
         from . import sharding
         a = {"rrt": _abi.ALGO_RRT, "rrt_star": _abi.ALGO_RRT_STAR, "rrt_dubins": _abi.ALGO_RRT_DUBINS,
              "rrt_star_dubins": _abi.ALGO_DUBINS, "rrt_star_reeds_shepp": _abi.ALGO_RS, "informed": _abi.ALGO_INFORMED,
-             "bitstar": _abi.ALGO_BITSTAR}[algo]
+             "bitstar": _abi.ALGO_BITSTAR, "lqr_rrt_star": _abi.ALGO_LQR_RRT_STAR}[algo]
         self.seeds = list(seeds)
+        if a == _abi.ALGO_LQR_RRT_STAR:
+            if not step_size > 0:
+                raise ValueError("BatchPlanner(lqr_rrt_star): step_size must be > 0, got %r" % (step_size,))
+            if int(max_iter) < 0:
+                raise ValueError("BatchPlanner(lqr_rrt_star): max_iter must be >= 0, got %r" % (max_iter,))
+            if not self.seeds:
+                raise ValueError("BatchPlanner(lqr_rrt_star): no seeds")
+            lqr_matmul_check()
         self.pose = a in (_abi.ALGO_RRT_DUBINS, _abi.ALGO_DUBINS, _abi.ALGO_RS)
         self.algo = a
         n = len(self.seeds)
