@@ -191,7 +191,8 @@ int rrtx_plan(rrtx_handle* h);
  * launch is bounded by rrtx_set_launch_bound (default: RRT* iteration kernel 131072 iterations, the other tree planners
  * 32768, BIT* 20000 trips of plan()'s loop :243): an instance that has used its share stores its state on the device and is
  * carried into the next launch -- results do not depend on the bound.  Between steps rrtx_get_results is valid: an instance
- * with RRTX_ST_DONE in its status word is final, whatever the others still do.  rrtx_plan = begin + steps until 0.
+ * with RRTX_ST_DONE in its status word is final, whatever the others still do.  A negative return from rrtx_plan_step
+ * ends the plan: its results are not valid (the getters return RRTX_E_STATE).  rrtx_plan = begin + steps until 0.
  * BIT* launches run persistent waves over a device-side work queue of the pending instances (rrt_bitstar_wave.hip.h). */
 int rrtx_plan_begin(rrtx_handle* h);
 int rrtx_plan_step(rrtx_handle* h, int32_t* n_pending);

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -89,6 +90,7 @@ RcclApi* rccl_api() {
 struct rrtx_handle {
   rrtx_params p;
   int device = 0;
+  int n_cu = 0;                 // compute units of the device
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   Ctx c;
@@ -114,6 +116,7 @@ struct rrtx_handle {
     int64_t launches = 0, launches_main = 0, steps = 0, v2_done_it = 0;
     bool use_v2 = false, bit_wave = false;
     int v2_tpb = 0;
+    int bit_grid = 0;   // BIT*, one wave per instance: waves per launch at most
     std::vector<Result> res;
     std::vector<int32_t> pending;   // BIT*: instances not finished yet (the device-side work queue of the next launch)
   } run;
@@ -222,31 +225,41 @@ static int obs_upload(rrtx_handle* h, const double* oxyr, int64_t rows) {
   return RRTX_OK;
 }
 
+// One timed launch on the handle's stream: `queue` queues the kernel; with copy_results every instance's Result comes back
+// into run.res.  Waits for the launch and adds its time and count to the run.
+template <class Queue>
+static int timed_launch(rrtx_handle* h, bool copy_results, Queue&& queue) {
+  rrtx_handle::Run& R = h->run;
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  queue();
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  if (copy_results)
+    HIPCHK(h, hipMemcpyAsync(R.res.data(), h->c.results, sizeof(Result) * h->n_inst, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  R.kms += ms;
+  R.launches++;
+  return RRTX_OK;
+}
+
 // ---- RRT* (rrt_04, search_until_max_iter): iteration-kernel launches ------------------------------------------------
 // One pass of the latency-lean iteration kernel over `nblk` instances (c.inst_map selects them; nullptr = 0..nblk-1),
 // in chunks of h->v2_chunk_iters iterations, workgroup shape tpb in {64, 128, 256}.
-static int launch_rrt_star_v2_once(rrtx_handle* h, const Ctx& c, int nblk, int tpb, double* kms, int64_t* launches) {
-  {
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+static int launch_rrt_star_v2_once(rrtx_handle* h, const Ctx& c, int nblk, int tpb) {
+  return timed_launch(h, false, [&] {
     if (tpb == 64)
       hipLaunchKernelGGL(rppk2t::rrt_star_kernel_v2, dim3(nblk), dim3(rppk2t::TPB), 0, h->stream, c, h->v2_chunk_iters);
     else if (tpb == 128)
       hipLaunchKernelGGL(rppk2s::rrt_star_kernel_v2, dim3(nblk), dim3(rppk2s::TPB), 0, h->stream, c, h->v2_chunk_iters);
     else
       hipLaunchKernelGGL(rppk2::rrt_star_kernel_v2, dim3(nblk), dim3(rppk2::TPB), 0, h->stream, c, h->v2_chunk_iters);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    *kms += ms;
-    (*launches)++;
-  }
-  return RRTX_OK;
+  });
 }
-static int launch_rrt_star_v2(rrtx_handle* h, const Ctx& c, int nblk, int tpb, double* kms, int64_t* launches) {
+static int launch_rrt_star_v2(rrtx_handle* h, const Ctx& c, int nblk, int tpb) {
   for (int64_t done_it = 0; done_it < c.max_iter; done_it += h->v2_chunk_iters) {
-    int rc = launch_rrt_star_v2_once(h, c, nblk, tpb, kms, launches);
+    int rc = launch_rrt_star_v2_once(h, c, nblk, tpb);
     if (rc) return rc;
   }
   return RRTX_OK;
@@ -324,6 +337,7 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
   rrtx_handle* h = new rrtx_handle();
   h->p = *p;
   h->device = p->device;
+  h->n_cu = prop.multiProcessorCount;
   h->n_inst = p->n_instances;
   memset(&h->stats, 0, sizeof(h->stats));
   memset(&h->c, 0, sizeof(h->c));
@@ -677,18 +691,78 @@ int rrtx_enable_trace(rrtx_handle* h, int32_t instance) {
   return RRTX_OK;
 }
 
+// ---- one plan: rrtx_plan_begin, rrtx_plan_step, plan_finish ---------------------------------------------------------
+// Every tree of `nblk` instances of `c` (c.inst_map selects them; nullptr = 0..nblk-1) back to its root node, from the
+// instance's record in c.inst; waits for it.
+static int init_trees(rrtx_handle* h, const Ctx& c, int nblk) {
+  hipLaunchKernelGGL(rppk::rrt_init_kernel, dim3(64, nblk), dim3(256), 0, h->stream, c);
+  hipLaunchKernelGGL(rppk::rrt_root_kernel, dim3((nblk + 63) / 64), dim3(64), 0, h->stream, c, nblk);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return RRTX_OK;
+}
+
+// Queues one launch of the planner's main kernel (not BIT*'s) over `nblk` instances of `c`, h->chunk_iters iterations
+// each at most.  `da`: the pose planners' arrays and polyline pool (a re-plan hands in its larger pool); informed RRT*
+// runs on the 2048-slot shape when `informed_large`, else on the product shape.
+static void queue_main_kernel(rrtx_handle* h, const Ctx& c, int nblk, const rppd::DubArgs& da, bool informed_large) {
+  if (c.algo == RRTX_ALGO_INFORMED && !informed_large)
+    hipLaunchKernelGGL((rppi::rrt_informed_kernel<rppi::NUI_SMALL, 4>), dim3(nblk), dim3(rppi::TPB), 0, h->stream, c,
+                       h->d_iargs, h->cbest, h->chunk_iters, h->informed_eager);
+  else if (c.algo == RRTX_ALGO_INFORMED)
+    hipLaunchKernelGGL((rppi::rrt_informed_kernel<rppi::NUI_LARGE, 1>), dim3(nblk), dim3(rppi::TPB), 0, h->stream, c,
+                       h->d_iargs, h->cbest, h->chunk_iters, h->informed_eager);
+  else if (is_dubins(c.algo))
+    hipLaunchKernelGGL(rppd::rrt_dubins_kernel, dim3(nblk), dim3(rppd::TPB), 0, h->stream, c, da, h->chunk_iters);
+  else if (c.algo == RRTX_ALGO_RS)
+    hipLaunchKernelGGL(rppr::rrt_rs_kernel, dim3(nblk), dim3(rppr::TPB), 0, h->stream, c, da, h->chunk_iters);
+  else if (c.algo == RRTX_ALGO_LQR_RRT_STAR)
+    hipLaunchKernelGGL(rppl::rrt_lqr_kernel, dim3(nblk), dim3(rppl::TPB), 0, h->stream, c, h->la, h->chunk_iters);
+  else
+    hipLaunchKernelGGL(rppk::rrt_plan_kernel, dim3(nblk), dim3(rppk::TPB), 0, h->stream, c, h->chunk_iters);
+}
+
+// Plans the instances `ids` again, from their staged start state, after the main kernel left them with a condition that
+// a larger table or another kernel resolves (plan_finish).  `reset(i)` queues the planner's own reset of instance i;
+// `prelude(cr, nr)` runs before the main kernel, on the Ctx of the re-plan (its workgroup k plans ids[k]); the main kernel
+// (queue_main_kernel with `da`, `informed_large`) is launched until every id is RRTX_ST_DONE.  `label` names the re-plan
+// in the error of its guard.  Either hook may be empty.
+static int replan(rrtx_handle* h, const std::vector<int32_t>& ids, const char* label, const rppd::DubArgs& da,
+                  bool informed_large, const std::function<int(int32_t)>& reset,
+                  const std::function<int(const Ctx&, int)>& prelude) {
+  const int nr = (int)ids.size();
+  int rc;
+  if (!h->inst_map && (rc = dalloc(h, &h->inst_map, h->n_inst))) return rc;
+  HIPCHK(h, hipMemcpyAsync(h->inst_map, ids.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice, h->stream));
+  for (int32_t i : ids) {
+    HIPCHK(h, hipMemcpyAsync(h->c.inst + i, &h->host_inst[i], sizeof(Inst), hipMemcpyHostToDevice, h->stream));
+    if (reset && (rc = reset(i))) return rc;
+  }
+  Ctx cr = h->c;
+  cr.inst_map = h->inst_map;
+  if ((rc = init_trees(h, cr, nr))) return rc;   // also the end of the host -> device copies above
+  if (prelude && (rc = prelude(cr, nr))) return rc;
+  for (int64_t guard = 0;; guard++) {
+    if ((rc = timed_launch(h, true, [&] { queue_main_kernel(h, cr, nr, da, informed_large); }))) return rc;
+    bool all = true;
+    for (int32_t i : ids)
+      if (!(h->run.res[i].status & RRTX_ST_DONE)) all = false;
+    if (all) break;
+    if (guard > (int64_t)h->p.max_iter / h->chunk_iters + 8) {
+      h->err = std::string("planner kernel did not converge to DONE (") + label + ")";
+      return RRTX_E_STATE;
+    }
+  }
+  h->stats_retried += nr;
+  return RRTX_OK;
+}
+
 static int plan_finish(rrtx_handle* h);
 
 int rrtx_plan_begin(rrtx_handle* h) {
   if (!h) return RRTX_E_INVALID;
   h->run = rrtx_handle::Run();
   rrtx_handle::Run& R = h->run;
-  double &kms = R.kms, &kms_main = R.kms_main;
-  int64_t &launches = R.launches, &launches_main = R.launches_main;
-  std::vector<Result>& res = R.res;
-  bool& use_v2 = R.use_v2;
-  int& v2_tpb = R.v2_tpb;
-  (void)kms; (void)kms_main; (void)launches; (void)launches_main; (void)res; (void)use_v2; (void)v2_tpb;
   R.t0 = std::chrono::steady_clock::now();
   h->planned = false;
   HIPCHK(h, hipSetDevice(h->device));
@@ -769,14 +843,9 @@ int rrtx_plan_begin(rrtx_handle* h) {
     h->inst_dirty = false;
   }
   HIPCHK(h, hipMemcpyAsync(c.inst, h->d_inst0, sizeof(Inst) * B, hipMemcpyDeviceToDevice, h->stream));
-  {
-    dim3 g(64, B);
-    hipLaunchKernelGGL(rppk::rrt_init_kernel, g, dim3(256), 0, h->stream, c);
-    hipLaunchKernelGGL(rppk::rrt_root_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, c, B);
-  }
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  res.assign(B, Result());
+  int rc = init_trees(h, c, B);
+  if (rc) return rc;
+  R.res.assign(B, Result());
   if (c.algo == RRTX_ALGO_BITSTAR) {
     // BIT*: one launch, one lane per instance (rrt_bitstar.hip.h); obstacle thresholds are size ** 2 (rrt_08:381)
     for (int i = 0; i < B; i++) {
@@ -788,20 +857,21 @@ int rrtx_plan_begin(rrtx_handle* h) {
     }
     HIPCHK(h, hipMemcpyAsync(h->ba.cfg, h->bcfg.data(), sizeof(rpp::BitCfg) * B, hipMemcpyHostToDevice, h->stream));
     if (h->trace_inst >= 0 && !h->ba.tr_a) {
-      int rc2;
-      if ((rc2 = dalloc(h, &h->ba.tr_a, 1 << 16))) return rc2;
-      if ((rc2 = dalloc(h, &h->ba.tr_b, 1 << 16))) return rc2;
+      if ((rc = dalloc(h, &h->ba.tr_a, 1 << 16))) return rc;
+      if ((rc = dalloc(h, &h->ba.tr_b, 1 << 16))) return rc;
       h->ba.tr_cap = 1 << 16;
     }
     h->ba.trace_inst = h->trace_inst;
     // one wave per instance when the per-vertex state fits LDS (rrt_bitstar_wave.hip.h); else one lane per instance
     const char* bk = getenv("RRTX_BITSTAR");
     R.bit_wave = h->m_max <= rppb::OB && c.max_iter + 2 <= rppb::VL && !(bk && !strcmp(bk, "lane"));
+    // as many waves as the chip keeps resident (LDS: 9 workgroups per CU), never more than there are instances
+    R.bit_grid = h->n_cu * 9;
+    if (const char* e = getenv("RRTX_BITSTAR_GRID")) R.bit_grid = atoi(e) > 0 ? atoi(e) : R.bit_grid;
     if (!h->bit_queue) {
-      int rc2;
-      if ((rc2 = dalloc(h, &h->bit_queue, B))) return rc2;
-      if ((rc2 = dalloc(h, &h->bit_qhead, 1))) return rc2;
-      if ((rc2 = dalloc(h, &h->ba.save_i, (size_t)8 * B))) return rc2;
+      if ((rc = dalloc(h, &h->bit_queue, B))) return rc;
+      if ((rc = dalloc(h, &h->bit_qhead, 1))) return rc;
+      if ((rc = dalloc(h, &h->ba.save_i, (size_t)8 * B))) return rc;
     }
     if (const char* e = getenv("RRTX_BITSTAR_TRIPS")) h->bit_trip_bound = atoi(e) > 0 ? atoi(e) : 20000;
     R.pending.resize(B);
@@ -816,8 +886,8 @@ int rrtx_plan_begin(rrtx_handle* h) {
   // RRT* with search_until_max_iter: the latency-lean iteration kernel runs every iteration; the general kernel
   // below then only performs the final goal search (rrt_04:1080-1084).  RRTX_KERNEL=v1 forces the general kernel.
   const char* kv = getenv("RRTX_KERNEL");
-  use_v2 = c.algo == RRTX_ALGO_RRT_STAR && c.until_max && !(kv && !strcmp(kv, "v1"));
-  if (use_v2) {
+  R.use_v2 = c.algo == RRTX_ALGO_RRT_STAR && c.until_max && !(kv && !strcmp(kv, "v1"));
+  if (R.use_v2) {
     // workgroup shape: fewer threads per instance once more instances want to be resident (8 / 16 workgroups per CU),
     // as long as the shape's obstacle tile and near-candidate capacity fit the problem
     const int need_nu = estimate_near_capacity(h->p);
@@ -829,7 +899,7 @@ int rrtx_plan_begin(rrtx_handle* h) {
       const int v = atoi(e);
       tpb = (v == 64 && m <= rppk2t::MAX_OBS) ? 64 : (v == 128 && m <= rppk2s::MAX_OBS) ? 128 : 256;
     }
-    v2_tpb = tpb;
+    R.v2_tpb = tpb;
   }
   if (c.algo == RRTX_ALGO_INFORMED) {
     std::vector<double> inf(B, INFINITY);
@@ -864,20 +934,13 @@ int rrtx_plan_begin(rrtx_handle* h) {
     HIPCHK(h, hipMemcpyAsync(h->d_iargs, h->iargs.data(), sizeof(rppi::InformedArgs) * B, hipMemcpyHostToDevice, h->stream));
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  R.stage = use_v2 ? 1 : 2;
+  R.stage = R.use_v2 ? 1 : 2;
   return RRTX_OK;
 }
 
-int rrtx_plan_step(rrtx_handle* h, int32_t* n_pending) {
-  if (!h) return RRTX_E_INVALID;
-  if (h->run.stage == 0) return RRTX_E_STATE;
+// One step of the plan in progress; a negative return leaves the run to rrtx_plan_step, which ends it
+static int plan_step(rrtx_handle* h, int32_t* n_pending) {
   rrtx_handle::Run& R = h->run;
-  double &kms = R.kms, &kms_main = R.kms_main;
-  int64_t &launches = R.launches, &launches_main = R.launches_main;
-  std::vector<Result>& res = R.res;
-  bool& use_v2 = R.use_v2;
-  int& v2_tpb = R.v2_tpb;
-  (void)kms; (void)kms_main; (void)launches; (void)launches_main; (void)res; (void)use_v2; (void)v2_tpb;
   HIPCHK(h, hipSetDevice(h->device));
   Ctx& c = h->c;
   const int B = h->n_inst;
@@ -885,12 +948,12 @@ int rrtx_plan_step(rrtx_handle* h, int32_t* n_pending) {
   if (n_pending) *n_pending = B;
   if (R.stage == 1) {
     // RRT* (rrt_04, search_until_max_iter): one launch of the iteration kernel = v2_chunk_iters iterations of every instance
-    int rc2 = launch_rrt_star_v2_once(h, c, B, v2_tpb, &kms, &launches);
-    if (rc2) return rc2;
+    int rc = launch_rrt_star_v2_once(h, c, B, R.v2_tpb);
+    if (rc) return rc;
     R.v2_done_it += h->v2_chunk_iters;
     if (R.v2_done_it >= c.max_iter) {
-      kms_main = kms;
-      launches_main = launches;
+      R.kms_main = R.kms;
+      R.launches_main = R.launches;
       R.stage = 2;   // the general kernel then performs the final goal search (rrt_04:1080-1084)
     }
     return RRTX_OK;
@@ -907,158 +970,92 @@ int rrtx_plan_step(rrtx_handle* h, int32_t* n_pending) {
     ba.qhead = h->bit_qhead;
     ba.n_pending = np;
     ba.trip_bound = h->bit_trip_bound;
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    if (R.bit_wave) {
-      // as many waves as the chip keeps resident (LDS: 9 workgroups per CU), never more than there are instances
-      hipDeviceProp_t prop;
-      HIPCHK(h, hipGetDeviceProperties(&prop, h->device));
-      int grid = prop.multiProcessorCount * 9;
-      if (const char* e = getenv("RRTX_BITSTAR_GRID")) grid = atoi(e) > 0 ? atoi(e) : grid;
-      if (grid > np) grid = np;
-      hipLaunchKernelGGL(rppb::bitstar_wave_kernel, dim3(grid), dim3(64), 0, h->stream, ba, c.inst, c.results, B);
-    } else {
-      hipLaunchKernelGGL(rppb::bitstar_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, ba, c.inst, c.results, B);
-    }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipMemcpyAsync(res.data(), c.results, sizeof(Result) * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    kms += ms;
-    launches++;
+    const int grid = R.bit_grid < np ? R.bit_grid : np;
+    int rc = timed_launch(h, true, [&] {
+      if (R.bit_wave)
+        hipLaunchKernelGGL(rppb::bitstar_wave_kernel, dim3(grid), dim3(64), 0, h->stream, ba, c.inst, c.results, B);
+      else
+        hipLaunchKernelGGL(rppb::bitstar_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, ba, c.inst, c.results, B);
+    });
+    if (rc) return rc;
     std::vector<int32_t> left;
     for (int32_t i : R.pending)
-      if (!(res[i].status & RRTX_ST_DONE)) left.push_back(i);
+      if (!(R.res[i].status & RRTX_ST_DONE)) left.push_back(i);
     R.pending.swap(left);
     if (n_pending) *n_pending = (int32_t)R.pending.size();
     if (!R.pending.empty()) {
-      if (launches > 4000000LL / h->bit_trip_bound + 16) {
+      if (R.launches > 4000000LL / h->bit_trip_bound + 16) {
         h->err = "BIT* kernel did not converge to DONE";
         return RRTX_E_STATE;
       }
       return RRTX_OK;
     }
-    if (n_pending) *n_pending = 0;
     return plan_finish(h);
   }
-  {
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    if (c.algo == RRTX_ALGO_INFORMED)
-      hipLaunchKernelGGL((rppi::rrt_informed_kernel<rppi::NUI_SMALL, 4>), dim3(B), dim3(rppi::TPB), 0, h->stream, c,
-                         h->d_iargs, h->cbest, h->chunk_iters, h->informed_eager);
-    else if (is_dubins(c.algo))
-      hipLaunchKernelGGL(rppd::rrt_dubins_kernel, dim3(B), dim3(rppd::TPB), 0, h->stream, c, h->da, h->chunk_iters);
-    else if (c.algo == RRTX_ALGO_RS)
-      hipLaunchKernelGGL(rppr::rrt_rs_kernel, dim3(B), dim3(rppr::TPB), 0, h->stream, c, h->da, h->chunk_iters);
-    else if (c.algo == RRTX_ALGO_LQR_RRT_STAR)
-      hipLaunchKernelGGL(rppl::rrt_lqr_kernel, dim3(B), dim3(rppl::TPB), 0, h->stream, c, h->la, h->chunk_iters);
-    else
-      hipLaunchKernelGGL(rppk::rrt_plan_kernel, dim3(B), dim3(rppk::TPB), 0, h->stream, c, h->chunk_iters);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipMemcpyAsync(res.data(), c.results, sizeof(Result) * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    kms += ms;
-    launches++;
-    int left = 0;
-    for (int i = 0; i < B; i++)
-      if (!(res[i].status & RRTX_ST_DONE)) left++;
-    if (n_pending) *n_pending = left;
-    if (left) {
-      if (launches > (int64_t)h->p.max_iter / h->chunk_iters + 8 + launches_main) {
-        h->err = "planner kernel did not converge to DONE";
-        return RRTX_E_STATE;
-      }
-      return RRTX_OK;
+  int rc = timed_launch(h, true, [&] { queue_main_kernel(h, c, B, h->da, false); });
+  if (rc) return rc;
+  int left = 0;
+  for (int i = 0; i < B; i++)
+    if (!(R.res[i].status & RRTX_ST_DONE)) left++;
+  if (n_pending) *n_pending = left;
+  if (left) {
+    if (R.launches > (int64_t)h->p.max_iter / h->chunk_iters + 8 + R.launches_main) {
+      h->err = "planner kernel did not converge to DONE";
+      return RRTX_E_STATE;
     }
+    return RRTX_OK;
   }
   return plan_finish(h);
+}
+
+int rrtx_plan_step(rrtx_handle* h, int32_t* n_pending) {
+  if (!h) return RRTX_E_INVALID;
+  if (h->run.stage == 0) return RRTX_E_STATE;
+  const int rc = plan_step(h, n_pending);
+  if (rc < 0) {   // an error ends the plan: its results are not valid
+    h->run.stage = 0;
+    h->planned = false;
+  }
+  return rc;
 }
 
 // Everything after the last instance has finished its main kernel: re-plans of instances that outgrew a fixed table, the
 // counters, the return code
 static int plan_finish(rrtx_handle* h) {
   rrtx_handle::Run& R = h->run;
-  double &kms = R.kms, &kms_main = R.kms_main;
-  int64_t &launches = R.launches, &launches_main = R.launches_main;
-  std::vector<Result>& res = R.res;
-  bool& use_v2 = R.use_v2;
-  int& v2_tpb = R.v2_tpb;
-  (void)kms; (void)kms_main; (void)launches; (void)launches_main; (void)res; (void)use_v2; (void)v2_tpb;
   Ctx& c = h->c;
   const int B = h->n_inst;
   R.stage = 0;
+  auto with_status = [&](int32_t bit) {   // the instances whose status word carries `bit`
+    std::vector<int32_t> ids;
+    for (int i = 0; i < B; i++)
+      if (R.res[i].status & bit) ids.push_back(i);
+    return ids;
+  };
+  int rc;
   // RRT* iteration kernel: an instance whose near set outgrew the LDS candidate table of its workgroup shape
   // (RRTX_ST_OVERFLOW) is planned again, from its staged start state, on the next larger shape (44 -> 128 -> 256
   // candidates), and finally by the general kernel (512).  Same results as a first plan on that shape: every shape
   // runs the same statements.
-  if (use_v2 && !getenv("RRTX_NO_RETRY")) {
+  if (R.use_v2 && !getenv("RRTX_NO_RETRY")) {
     // plans the instances `redo` again: shape = workgroup shape of the iteration kernel, 0 = general kernel alone
-    auto replan = [&](const std::vector<int32_t>& redo, int shape) -> int {
-      const int nr = (int)redo.size();
-      if (!h->inst_map) {
-        int rc2;
-        if ((rc2 = dalloc(h, &h->inst_map, B))) return rc2;
-      }
-      HIPCHK(h, hipMemcpyAsync(h->inst_map, redo.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice, h->stream));
-      for (int k = 0; k < nr; k++)
-        HIPCHK(h, hipMemcpyAsync(c.inst + redo[k], &h->host_inst[redo[k]], sizeof(Inst), hipMemcpyHostToDevice, h->stream));
-      Ctx cr = c;
-      cr.inst_map = h->inst_map;
-      hipLaunchKernelGGL(rppk::rrt_init_kernel, dim3(64, nr), dim3(256), 0, h->stream, cr);
-      hipLaunchKernelGGL(rppk::rrt_root_kernel, dim3((nr + 63) / 64), dim3(64), 0, h->stream, cr, nr);
-      HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipStreamSynchronize(h->stream));   // `redo` is read by the copies above
-      if (shape) {
-        int rc2 = launch_rrt_star_v2(h, cr, nr, shape, &kms, &launches);
-        if (rc2) return rc2;
-      }
-      for (int64_t guard = 0;; guard++) {
-        HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-        hipLaunchKernelGGL(rppk::rrt_plan_kernel, dim3(nr), dim3(rppk::TPB), 0, h->stream, cr, h->chunk_iters);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-        HIPCHK(h, hipMemcpyAsync(res.data(), c.results, sizeof(Result) * B, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        kms += ms;
-        launches++;
-        bool all = true;
-        for (int k = 0; k < nr; k++)
-          if (!(res[redo[k]].status & RRTX_ST_DONE)) all = false;
-        if (all) break;
-        if (guard > (int64_t)h->p.max_iter / h->chunk_iters + 8) {
-          h->err = "planner kernel did not converge to DONE (retry)";
-          return RRTX_E_STATE;
-        }
-      }
-      h->stats_retried += nr;
-      return RRTX_OK;
+    auto replan_on = [&](const std::vector<int32_t>& redo, int shape) {
+      return replan(h, redo, "retry", h->da, false, nullptr, [&](const Ctx& cr, int nr) {
+        return shape ? launch_rrt_star_v2(h, cr, nr, shape) : RRTX_OK;
+      });
     };
-    int shape = v2_tpb;   // 0 = general kernel
+    int shape = R.v2_tpb;   // 0 = general kernel
     for (;;) {
-      std::vector<int32_t> redo;
-      for (int i = 0; i < B; i++)
-        if (res[i].status & RRTX_ST_OVERFLOW) redo.push_back(i);
+      const std::vector<int32_t> redo = with_status(RRTX_ST_OVERFLOW);
       if (redo.empty() || shape == 0) break;
       shape = shape == 64 ? 128 : shape == 128 ? 256 : 0;
       if (shape && h->m_max > v2_shape_maxobs(shape)) continue;
-      int rc2 = replan(redo, shape);
-      if (rc2) return rc2;
+      if ((rc = replan_on(redo, shape))) return rc;
     }
     // rewire moved a node while near_inds had repeated entries (rrt_04:1337 with :1372): the iteration kernel does not
     // walk the raw list (RRTX_ST_UNSUPPORTED in its status word), the general kernel does (rppk::rewire_raw_walk)
-    std::vector<int32_t> redo;
-    for (int i = 0; i < B; i++)
-      if (res[i].status & RRTX_ST_UNSUPPORTED) redo.push_back(i);
-    if (!redo.empty()) {
-      int rc2 = replan(redo, 0);
-      if (rc2) return rc2;
-    }
+    const std::vector<int32_t> redo = with_status(RRTX_ST_UNSUPPORTED);
+    if (!redo.empty() && (rc = replan_on(redo, 0))) return rc;
   }
   // Pose planners (rrt_03 / rrt_05 / rrt_06): an instance that ran out of polyline pool (edges replaced by rewire stay
   // allocated) is planned again, from its staged start state, with a pool four times as large -- twice if need be.
@@ -1066,9 +1063,7 @@ static int plan_finish(rrtx_handle* h) {
   if (is_pose_tree(c.algo) && !getenv("RRTX_NO_RETRY")) {
     int64_t big_cap = h->da.pool_cap;
     for (int attempt = 0; attempt < 2; attempt++) {
-      std::vector<int32_t> redo;
-      for (int i = 0; i < B; i++)
-        if (res[i].status & RRTX_ST_OVERFLOW) redo.push_back(i);
+      const std::vector<int32_t> redo = with_status(RRTX_ST_OVERFLOW);
       if (redo.empty()) break;
       const int nr = (int)redo.size();
       big_cap *= 4;
@@ -1093,114 +1088,43 @@ static int plan_finish(rrtx_handle* h) {
         bp.cap = big_cap;
         bp.slabs = nr;
       }
-      double *bx = bp.px, *by = bp.py, *bw = bp.pyaw;
-      int rc2;
-      if (!h->inst_map && (rc2 = dalloc(h, &h->inst_map, B))) return rc2;
-      if (!h->pool_slot && (rc2 = dalloc(h, &h->pool_slot, B))) return rc2;
+      if (!h->pool_slot && (rc = dalloc(h, &h->pool_slot, B))) return rc;
       std::vector<int32_t> slot(B, 0);
       for (int k = 0; k < nr; k++) slot[redo[k]] = k;
-      HIPCHK(h, hipMemcpyAsync(h->inst_map, redo.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice, h->stream));
       HIPCHK(h, hipMemcpyAsync(h->pool_slot, slot.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, h->stream));
-      for (int k = 0; k < nr; k++) {
-        HIPCHK(h, hipMemcpyAsync(c.inst + redo[k], &h->host_inst[redo[k]], sizeof(Inst), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemsetAsync(h->da.pool_used + redo[k], 0, sizeof(int64_t), h->stream));
-      }
-      Ctx cr = c;
-      cr.inst_map = h->inst_map;
       rppd::DubArgs dr = h->da;
-      dr.pool_x = bx; dr.pool_y = by; dr.pool_yaw = bw;
+      dr.pool_x = bp.px; dr.pool_y = bp.py; dr.pool_yaw = bp.pyaw;
       dr.pool_cap = big_cap;
       dr.pool_slot = h->pool_slot;
-      hipLaunchKernelGGL(rppk::rrt_init_kernel, dim3(64, nr), dim3(256), 0, h->stream, cr);
-      hipLaunchKernelGGL(rppk::rrt_root_kernel, dim3((nr + 63) / 64), dim3(64), 0, h->stream, cr, nr);
-      HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      for (int64_t guard = 0;; guard++) {
-        HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-        if (c.algo == RRTX_ALGO_RS)
-          hipLaunchKernelGGL(rppr::rrt_rs_kernel, dim3(nr), dim3(rppr::TPB), 0, h->stream, cr, dr, h->chunk_iters);
-        else
-          hipLaunchKernelGGL(rppd::rrt_dubins_kernel, dim3(nr), dim3(rppd::TPB), 0, h->stream, cr, dr, h->chunk_iters);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-        HIPCHK(h, hipMemcpyAsync(res.data(), c.results, sizeof(Result) * B, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        kms += ms;
-        launches++;
-        bool all = true;
-        for (int k = 0; k < nr; k++)
-          if (!(res[redo[k]].status & RRTX_ST_DONE)) all = false;
-        if (all) break;
-        if (guard > (int64_t)h->p.max_iter / h->chunk_iters + 8) {
-          h->err = "planner kernel did not converge to DONE (pool retry)";
-          return RRTX_E_STATE;
-        }
-      }
+      rc = replan(h, redo, "pool retry", dr, false, [&](int32_t i) {
+        HIPCHK(h, hipMemsetAsync(h->da.pool_used + i, 0, sizeof(int64_t), h->stream));
+        return RRTX_OK;
+      }, nullptr);
+      if (rc) return rc;
       for (int k = 0; k < nr; k++) {
         rrtx_handle::PoolLoc& pl = h->pool_loc[redo[k]];
-        pl.px = bx; pl.py = by; pl.pyaw = bw;
+        pl.px = bp.px; pl.py = bp.py; pl.pyaw = bp.pyaw;
         pl.cap = big_cap; pl.slab = k;
       }
-      h->stats_retried += nr;
     }
   }
   // Informed RRT*: the near radius of rrt_07:1139 is not capped, so a near set can outgrow the 512 LDS candidate slots
   // of the product shape; those instances are planned again, from their staged start state, on the 2048-slot shape
   // (one workgroup per CU).  Same statements, same results as a first plan on that shape.
   if (c.algo == RRTX_ALGO_INFORMED && !getenv("RRTX_NO_RETRY")) {
-    std::vector<int32_t> redo;
-    for (int i = 0; i < B; i++)
-      if (res[i].status & RRTX_ST_OVERFLOW) redo.push_back(i);
+    const std::vector<int32_t> redo = with_status(RRTX_ST_OVERFLOW);
     if (!redo.empty()) {
-      const int nr = (int)redo.size();
-      if (!h->inst_map) {
-        int rc2;
-        if ((rc2 = dalloc(h, &h->inst_map, B))) return rc2;
-      }
-      HIPCHK(h, hipMemcpyAsync(h->inst_map, redo.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice, h->stream));
       const double inf1 = INFINITY;
-      for (int k = 0; k < nr; k++) {
-        HIPCHK(h, hipMemcpyAsync(c.inst + redo[k], &h->host_inst[redo[k]], sizeof(Inst), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->cbest + redo[k], &inf1, sizeof(double), hipMemcpyHostToDevice, h->stream));
-      }
-      Ctx cr = c;
-      cr.inst_map = h->inst_map;
-      hipLaunchKernelGGL(rppk::rrt_init_kernel, dim3(64, nr), dim3(256), 0, h->stream, cr);
-      hipLaunchKernelGGL(rppk::rrt_root_kernel, dim3((nr + 63) / 64), dim3(64), 0, h->stream, cr, nr);
-      HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      for (int64_t guard = 0;; guard++) {
-        HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-        hipLaunchKernelGGL((rppi::rrt_informed_kernel<rppi::NUI_LARGE, 1>), dim3(nr), dim3(rppi::TPB), 0, h->stream, cr,
-                           h->d_iargs, h->cbest, h->chunk_iters, h->informed_eager);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-        HIPCHK(h, hipMemcpyAsync(res.data(), c.results, sizeof(Result) * B, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        kms += ms;
-        launches++;
-        bool all = true;
-        for (int k = 0; k < nr; k++)
-          if (!(res[redo[k]].status & RRTX_ST_DONE)) all = false;
-        if (all) break;
-        if (guard > (int64_t)h->p.max_iter / h->chunk_iters + 8) {
-          h->err = "planner kernel did not converge to DONE (overflow retry)";
-          return RRTX_E_STATE;
-        }
-      }
-      h->stats_retried += nr;
+      rc = replan(h, redo, "overflow retry", h->da, true, [&](int32_t i) {
+        HIPCHK(h, hipMemcpyAsync(h->cbest + i, &inf1, sizeof(double), hipMemcpyHostToDevice, h->stream));
+        return RRTX_OK;
+      }, nullptr);
+      if (rc) return rc;
     }
   }
   // aggregate counters
   // summed on the device (rppk::stats_reduce_kernel): one small record comes back instead of every Inst
-  if (!h->d_acc) {
-    int rc2 = dalloc(h, &h->d_acc, 1);
-    if (rc2) return rc2;
-  }
+  if (!h->d_acc && (rc = dalloc(h, &h->d_acc, 1))) return rc;
   rppk::StatsAcc acc;
   HIPCHK(h, hipMemsetAsync(h->d_acc, 0, sizeof(rppk::StatsAcc), h->stream));
   hipLaunchKernelGGL(rppk::stats_reduce_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, c.inst, B, h->d_acc);
@@ -1228,19 +1152,19 @@ static int plan_finish(rrtx_handle* h) {
   for (int k = 0; k < 16; k++) h->phase[k] = acc.phase[k];
   const bool overflow = (acc.status_or & RRTX_ST_OVERFLOW) != 0, unsupported = (acc.status_or & RRTX_ST_UNSUPPORTED) != 0,
              raises = (acc.status_or & RRTX_ST_REF_RAISES) != 0;
-  s.launches = launches;
-  s.kernel_ms = kms;
-  s.launches_main = kms_main >= 0.0 ? launches_main : launches;
-  s.kernel_ms_main = kms_main >= 0.0 ? kms_main : kms;
+  s.launches = R.launches;
+  s.kernel_ms = R.kms;
+  s.launches_main = R.kms_main >= 0.0 ? R.launches_main : R.launches;
+  s.kernel_ms_main = R.kms_main >= 0.0 ? R.kms_main : R.kms;
   s.replanned = h->stats_retried;
-  s.main_shape = use_v2 ? v2_tpb
+  s.main_shape = R.use_v2 ? R.v2_tpb
                         : c.algo == RRTX_ALGO_INFORMED ? rppi::TPB
                         : is_dubins(c.algo)            ? rppd::TPB
                         : c.algo == RRTX_ALGO_RS       ? rppr::TPB
                         : c.algo == RRTX_ALGO_BITSTAR  ? 64
                         : c.algo == RRTX_ALGO_LQR_RRT_STAR ? rppl::TPB
                                                        : rppk::TPB;
-  s.main_f32 = use_v2 ? 1 : 0;   // kept for the ABI v5 layout: 1 whenever the RRT* iteration kernel ran
+  s.main_f32 = R.use_v2 ? 1 : 0;   // kept for the ABI v5 layout: 1 whenever the RRT* iteration kernel ran
   s.plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - R.t0).count();
   h->planned = true;
   // Per-instance conditions are per-instance results: the status word of each instance carries them
@@ -1266,14 +1190,7 @@ static int plan_finish(rrtx_handle* h) {
 int rrtx_plan(rrtx_handle* h) {
   int rc = rrtx_plan_begin(h);
   if (rc < 0) return rc;
-  int32_t pending = 1;
-  while (h->run.stage != 0) {
-    rc = rrtx_plan_step(h, &pending);
-    if (rc < 0) {
-      h->run.stage = 0;
-      return rc;
-    }
-  }
+  while (h->run.stage != 0) rc = rrtx_plan_step(h, nullptr);   // a negative return ends the run
   return rc;
 }
 
