@@ -155,10 +155,29 @@ typedef struct rrtx_stats {
 
 typedef struct rrtx_handle rrtx_handle;
 
+/* Call order on a handle.  rrtx_create, then any setters, then rrtx_plan (or rrtx_plan_begin + rrtx_plan_step until it
+ * reports 0), then the getters; then setters and plans again, as often as wanted.  Every plan starts from the staged
+ * per-instance state (obstacles, start / goal, rotation, RNG state) and from nothing else: no result of an earlier plan
+ * on the handle changes a later one.
+ *  - Before the first completed plan, and from rrtx_plan_begin until the step that reports 0, the getters of a plan's
+ *    results (tree, path, path_yaw, yaw, polylines, copy_results_device, sobol_index, trace, trace_kind), rrtx_smooth_planned
+ *    and rrtx_get_smoothed_path return RRTX_E_STATE; rrtx_get_results alone is valid between steps.
+ *  - From rrtx_plan_begin until the end of that plan every setter returns RRTX_E_STATE and changes nothing:
+ *    rrtx_set_obstacles, rrtx_set_instance_obstacles, rrtx_seed_instances, rrtx_set_rng_state, rrtx_set_instance,
+ *    rrtx_set_instance_rotation, rrtx_enable_trace, rrtx_set_launch_bound (a re-plan inside the plan restarts instances
+ *    from the staged state, and device tables of the plan point into the obstacle table).
+ *  - rrtx_plan_begin (and so rrtx_plan) while a plan is in progress is accepted: it abandons that plan -- no launch of it
+ *    is in flight between two calls, its results are gone -- and begins a new one from the staged state.
+ *  - rrtx_get_smoothed_path belongs to the plan that rrtx_smooth_planned smoothed: after another rrtx_plan it returns
+ *    RRTX_E_STATE until rrtx_smooth_planned has run again.
+ *  - Getters with a capacity: when the caller's buffers are too small they return RRTX_E_CAPACITY, write nothing into them
+ *    and leave the needed size in *n_out; with every data pointer NULL they return the size and RRTX_OK. */
+
 /* replaces RRT.__init__ (rrt_04:951-1000); allocates device state for n_instances trees of max_iter+1 nodes. */
 int rrtx_create(const rrtx_params* p, rrtx_handle** out);
 /* obstacle_list ctor argument (rrt_04:989): m rows of (ox, oy, size), AoS in; converted to SoA + thresholds
- * (size+robot_radius)**2 (rrt_04:1227) on the host.  Shared by all instances of the handle. */
+ * (size+robot_radius)**2 (rrt_04:1227) on the host.  Shared by all instances of the handle.  RRTX_E_STATE between
+ * rrtx_plan_begin and the end of that plan, like every setter. */
 int rrtx_set_obstacles(rrtx_handle* h, const double* oxyr, int32_t m);
 /* Per-instance obstacle lists (a batch over many maps in one handle): offsets has n_instances + 1 entries (CSR), instance i
  * owns the rows oxyr[3*offsets[i] .. 3*offsets[i+1]) of (ox, oy, size), taken as rrtx_set_obstacles takes them.  Replaces
@@ -170,6 +189,12 @@ int rrtx_set_instance_obstacles(rrtx_handle* h, const int32_t* offsets, const do
 /* hand over / take back CPython's `random.getstate()[1]` (624 words + position) for one instance, so that
  * the device consumes the stream exactly as random.randint / random.uniform would (rrt_04:1133-1136). */
 int rrtx_set_rng_state(rrtx_handle* h, int32_t instance, const uint32_t* mt624, int32_t pos);
+/* Before the first completed plan: the staged state.  After a plan: the state that plan (and rrtx_smooth_planned after it)
+ * left on the device -- also when a new state has been staged since with rrtx_set_rng_state / rrtx_seed_instances: a staged
+ * state is what the NEXT plan starts from, and cannot be read back before that plan has run.  To continue an instance's
+ * stream over two plans (the reference's planning() called twice without reseeding), read the state after the first plan
+ * and stage it with rrtx_set_rng_state: without that, the next plan starts from the state staged last, not from where
+ * the previous plan stopped. */
 int rrtx_get_rng_state(rrtx_handle* h, int32_t instance, uint32_t* mt624, int32_t* pos);
 /* convenience: state after `random.seed(seed)` for instances first..first+count-1 */
 int rrtx_seed_instances(rrtx_handle* h, int32_t first, int32_t count, const uint64_t* seeds);
@@ -196,7 +221,8 @@ int rrtx_plan(rrtx_handle* h);
  * BIT* launches run persistent waves over a device-side work queue of the pending instances (rrt_bitstar_wave.hip.h). */
 int rrtx_plan_begin(rrtx_handle* h);
 int rrtx_plan_step(rrtx_handle* h, int32_t* n_pending);
-/* iterations (BIT*: loop trips) one launch may spend on one instance; not while a plan is in progress */
+/* iterations (BIT*: loop trips) one launch may spend on one instance; RRTX_E_STATE while a plan is in progress.  The
+ * one-lane BIT* kernel (problems whose vertex state exceeds LDS, RRTX_BITSTAR=lane) is not bounded: its plan is one launch. */
 int rrtx_set_launch_bound(rrtx_handle* h, int32_t iterations);
 /* Multi-GPU in one process ("one handle per device, driven from one process with N threads"): plans the n
  * handles concurrently, one host thread per handle (each bound to its handle's device; two handles may share a device),
@@ -234,10 +260,13 @@ int rrtx_get_yaw(rrtx_handle* h, int32_t instance, double* yaw, int32_t cap);
 int rrtx_get_path_yaw(rrtx_handle* h, int32_t instance, double* yaw, int32_t cap_points, int32_t* n_out);
 int rrtx_get_polylines(rrtx_handle* h, int32_t instance, int32_t* plen, int32_t cap_nodes, double* px, double* py,
                        int64_t cap_points, int64_t* n_points_out);
-/* Sobol index (RRT.sobol_inter_, rrt_04:995,1148) after planning */
+/* Sobol index (RRT.sobol_inter_, rrt_04:995,1148) after planning.  Every plan restarts the sequence at index 0, as a newly
+ * constructed reference planner does: the index is not carried from one plan on the handle to the next and cannot be staged. */
 int rrtx_get_sobol_index(rrtx_handle* h, int32_t instance, int64_t* index);
 int rrtx_get_stats(rrtx_handle* h, rrtx_stats* st);
-/* optional per-iteration trace of one instance (debug/parity harness): call before rrtx_plan.
+/* optional per-iteration trace of one instance (debug/parity harness): call before rrtx_plan; instance -1 switches it off.
+ * The trace getters return the rows of the instance that the last completed plan traced: after rrtx_enable_trace on a
+ * planned handle (another instance, or the first time) they return RRTX_E_STATE until the next plan has completed.
  * rows: rnd_x, rnd_y (f64), nearest, n_near_unique (i32; -1 when the iteration stopped before the near query) */
 int rrtx_enable_trace(rrtx_handle* h, int32_t instance);
 int rrtx_get_trace(rrtx_handle* h, double* rnd_x, double* rnd_y, int32_t* nearest, int32_t* n_near,

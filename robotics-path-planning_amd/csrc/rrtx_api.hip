@@ -103,7 +103,8 @@ struct rrtx_handle {
   // device obstacle table: ox, oy, othr and the sizes (path smoothing) of all rows, `obs_cap` rows each, one allocation
   double* obs_buf = nullptr;
   int64_t obs_cap = 0;
-  int trace_inst = -1;
+  int trace_inst = -1;    // instance the next plan traces (rrtx_enable_trace)
+  int traced_inst = -1;   // instance whose trace the last completed plan recorded; -1 none
   rrtx_stats stats;
   int64_t phase[16] = {0};
   std::string err;
@@ -186,6 +187,14 @@ static int dalloc(rrtx_handle* h, T** p, size_t count) {
   h->allocs.push_back(q);
   *p = (T*)q;
   return 0;
+}
+
+// Inputs of a plan are fixed from rrtx_plan_begin to the end of that plan: a re-plan inside it restarts instances from
+// host_inst, and the BIT* table uploaded by rrtx_plan_begin points into the obstacle table.  The setters refuse meanwhile.
+static int refuse_in_plan(rrtx_handle* h, const char* fn) {
+  if (h->run.stage == 0) return RRTX_OK;
+  h->err = std::string(fn) + ": a plan is in progress";
+  return RRTX_E_STATE;
 }
 
 // Device obstacle table of at least `rows` rows (contents are not kept: the caller uploads every row afterwards)
@@ -529,6 +538,7 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
 
 int rrtx_set_obstacles(rrtx_handle* h, const double* oxyr, int32_t m) {
   if (!h || m < 0 || (m > 0 && !oxyr)) return RRTX_E_INVALID;
+  if (int rc = refuse_in_plan(h, "rrtx_set_obstacles")) return rc;
   if (m > rppk::MAX_OBS) {
     h->err = "more than 256 obstacles";
     return RRTX_E_INVALID;
@@ -552,10 +562,7 @@ int rrtx_set_obstacles(rrtx_handle* h, const double* oxyr, int32_t m) {
 
 int rrtx_set_instance_obstacles(rrtx_handle* h, const int32_t* offsets, const double* oxyr) {
   if (!h) return RRTX_E_INVALID;
-  if (h->run.stage != 0) {
-    h->err = "rrtx_set_instance_obstacles: a plan is in progress";
-    return RRTX_E_STATE;
-  }
+  if (int rc = refuse_in_plan(h, "rrtx_set_instance_obstacles")) return rc;
   if (!offsets) {
     h->err = "rrtx_set_instance_obstacles: offsets is NULL";
     return RRTX_E_INVALID;
@@ -605,6 +612,7 @@ int rrtx_set_instance_obstacles(rrtx_handle* h, const int32_t* offsets, const do
 
 int rrtx_set_rng_state(rrtx_handle* h, int32_t instance, const uint32_t* mt624, int32_t pos) {
   if (!h || !mt624 || instance < 0 || instance >= h->n_inst || pos < 0 || pos > 624) return RRTX_E_INVALID;
+  if (int rc = refuse_in_plan(h, "rrtx_set_rng_state")) return rc;
   h->inst_dirty = true;
   memcpy(h->host_inst[instance].rng.mt, mt624, 624 * 4);
   h->host_inst[instance].rng.pos = pos;
@@ -628,6 +636,7 @@ int rrtx_get_rng_state(rrtx_handle* h, int32_t instance, uint32_t* mt624, int32_
 
 int rrtx_seed_instances(rrtx_handle* h, int32_t first, int32_t count, const uint64_t* seeds) {
   if (!h || !seeds || first < 0 || count < 0 || first + count > h->n_inst) return RRTX_E_INVALID;
+  if (int rc = refuse_in_plan(h, "rrtx_seed_instances")) return rc;
   h->inst_dirty = true;
   for (int i = 0; i < count; i++) rpp::mt_seed_u64(&h->host_inst[first + i].rng, seeds[i]);
   return RRTX_OK;
@@ -635,6 +644,7 @@ int rrtx_seed_instances(rrtx_handle* h, int32_t first, int32_t count, const uint
 
 int rrtx_set_instance(rrtx_handle* h, int32_t instance, const double* start3, const double* goal3) {
   if (!h || instance < 0 || instance >= h->n_inst) return RRTX_E_INVALID;
+  if (int rc = refuse_in_plan(h, "rrtx_set_instance")) return rc;
   h->inst_dirty = true;
   Inst& I = h->host_inst[instance];
   if (start3) {
@@ -660,6 +670,7 @@ int rrtx_set_instance(rrtx_handle* h, int32_t instance, const double* start3, co
 
 int rrtx_set_instance_rotation(rrtx_handle* h, int32_t instance, const double* rot4, double c_min) {
   if (!h || !rot4 || instance < 0 || instance >= h->n_inst) return RRTX_E_INVALID;
+  if (int rc = refuse_in_plan(h, "rrtx_set_instance_rotation")) return rc;
   if (h->p.algo == RRTX_ALGO_INFORMED) {
     for (int k = 0; k < 4; k++) h->iargs[instance].rot[k] = rot4[k];
     h->iargs[instance].c_min2 = py_sq_host(c_min);   // c_min ** 2 rrt_07:1147
@@ -676,6 +687,7 @@ int rrtx_set_instance_rotation(rrtx_handle* h, int32_t instance, const double* r
 
 int rrtx_enable_trace(rrtx_handle* h, int32_t instance) {
   if (!h || instance < -1 || instance >= h->n_inst) return RRTX_E_INVALID;
+  if (int rc = refuse_in_plan(h, "rrtx_enable_trace")) return rc;
   h->trace_inst = instance;
   if (instance >= 0 && !h->c.tr_rx) {
     int rc;
@@ -765,6 +777,8 @@ int rrtx_plan_begin(rrtx_handle* h) {
   rrtx_handle::Run& R = h->run;
   R.t0 = std::chrono::steady_clock::now();
   h->planned = false;
+  h->smoothed = false;     // rrtx_get_smoothed_path: the previous plan's smoothed paths are not this plan's
+  h->traced_inst = -1;     // rrtx_get_trace: nothing recorded until this plan completes
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipDeviceSynchronize());   // uploads made through the null stream (obstacles, tables) are complete
   Ctx& c = h->c;
@@ -1167,6 +1181,7 @@ static int plan_finish(rrtx_handle* h) {
   s.main_f32 = R.use_v2 ? 1 : 0;   // kept for the ABI v5 layout: 1 whenever the RRT* iteration kernel ran
   s.plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - R.t0).count();
   h->planned = true;
+  h->traced_inst = h->trace_inst;
   // Per-instance conditions are per-instance results: the status word of each instance carries them
   // (rrtx_get_results), the other instances' trees are complete and valid.
   if (overflow || raises || unsupported) {
@@ -1544,13 +1559,15 @@ int rrtx_get_phase_cycles(rrtx_handle* h, int64_t* out16) {
 int rrtx_get_trace(rrtx_handle* h, double* rnd_x, double* rnd_y, int32_t* nearest, int32_t* n_near, int32_t cap,
                    int32_t* n_out) {
   if (!h || !n_out) return RRTX_E_INVALID;
-  if (!h->planned || h->trace_inst < 0) return RRTX_E_STATE;
+  // the rows are those of the instance the last completed plan traced
+  if (!h->planned || h->trace_inst < 0 || h->traced_inst != h->trace_inst) return RRTX_E_STATE;
+  const bool want = rnd_x || rnd_y || nearest || n_near;   // all NULL: the row count alone
   HIPCHK(h, hipSetDevice(h->device));
   if (h->p.algo == RRTX_ALGO_BITSTAR) {   // rnd_x / rnd_y carry the ids of the popped edges (bestEdge[0], bestEdge[1])
     int32_t oi[8];
     HIPCHK(h, hipMemcpy(oi, h->ba.out_i + 8 * h->trace_inst, sizeof(oi), hipMemcpyDeviceToHost));
     *n_out = oi[6];
-    if (cap < oi[6] || oi[6] > h->ba.tr_cap) return RRTX_E_CAPACITY;
+    if ((want && cap < oi[6]) || oi[6] > h->ba.tr_cap) return RRTX_E_CAPACITY;
     if (rnd_x) HIPCHK(h, hipMemcpy(rnd_x, h->ba.tr_a, sizeof(double) * oi[6], hipMemcpyDeviceToHost));
     if (rnd_y) HIPCHK(h, hipMemcpy(rnd_y, h->ba.tr_b, sizeof(double) * oi[6], hipMemcpyDeviceToHost));
     return RRTX_OK;
@@ -1559,7 +1576,7 @@ int rrtx_get_trace(rrtx_handle* h, double* rnd_x, double* rnd_y, int32_t* neares
   HIPCHK(h, hipMemcpy(&I, h->c.inst + h->trace_inst, sizeof(I), hipMemcpyDeviceToHost));
   const int n = I.it;
   *n_out = n;
-  if (cap < n) return RRTX_E_CAPACITY;
+  if (want && cap < n) return RRTX_E_CAPACITY;
   if (rnd_x) HIPCHK(h, hipMemcpy(rnd_x, h->c.tr_rx, sizeof(double) * n, hipMemcpyDeviceToHost));
   if (rnd_y) HIPCHK(h, hipMemcpy(rnd_y, h->c.tr_ry, sizeof(double) * n, hipMemcpyDeviceToHost));
   if (nearest) HIPCHK(h, hipMemcpy(nearest, h->c.tr_near, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
@@ -1569,13 +1586,13 @@ int rrtx_get_trace(rrtx_handle* h, double* rnd_x, double* rnd_y, int32_t* neares
 
 int rrtx_get_trace_kind(rrtx_handle* h, int32_t* kind, int32_t cap, int32_t* n_out) {
   if (!h || !n_out) return RRTX_E_INVALID;
-  if (!h->planned || h->trace_inst < 0 || !h->c.tr_kind) return RRTX_E_STATE;
+  if (!h->planned || h->trace_inst < 0 || h->traced_inst != h->trace_inst || !h->c.tr_kind) return RRTX_E_STATE;
   if (h->p.algo != RRTX_ALGO_RRT && h->p.algo != RRTX_ALGO_RRT_STAR) return RRTX_E_STATE;
   HIPCHK(h, hipSetDevice(h->device));
   Inst I;
   HIPCHK(h, hipMemcpy(&I, h->c.inst + h->trace_inst, sizeof(I), hipMemcpyDeviceToHost));
   *n_out = I.it;
-  if (cap < I.it) return RRTX_E_CAPACITY;
+  if (kind && cap < I.it) return RRTX_E_CAPACITY;
   if (kind) HIPCHK(h, hipMemcpy(kind, h->c.tr_kind, sizeof(int32_t) * I.it, hipMemcpyDeviceToHost));
   return RRTX_OK;
 }

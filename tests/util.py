@@ -271,3 +271,23 @@ def run_gpu_bitstar(obstacles, rand_area, max_iter, seeds, starts, goals, device
     finally:
         h.close()
     return out
+
+
+def read_planned(h, n, yaws=False, polys=False, path_yaws=False, sobol=False, trace=False):
+    """Everything a planned handle holds, in the dict shape the run_gpu_* helpers return (the handle stays open)."""
+    out = dict(stats=h.get_stats(), results=h.get_results(), trees=[], paths=[], rng=[])
+    for i in range(n):
+        out["trees"].append(h.get_tree(i))
+        out["paths"].append(h.get_path(i))
+        out["rng"].append(h.get_rng_state(i))
+    if yaws:
+        out["yaws"] = [h.get_yaw(i) for i in range(n)]
+    if polys:
+        out["polys"] = [h.get_polylines(i) for i in range(n)]
+    if path_yaws:
+        out["path_yaws"] = [h.get_path_yaw(i) for i in range(n)]
+    if sobol:
+        out["sobol_index"] = [h.get_sobol_index(i) for i in range(n)]
+    if trace:
+        out["trace"] = h.get_trace()
+    return out
