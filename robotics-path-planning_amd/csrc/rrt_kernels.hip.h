@@ -118,6 +118,12 @@ struct Ctx {
   // sibling chain per lane (RRTX_PROP_VEC; < 0: scalar path only); prop_cap bounds its LDS list of pending chains
   // (RRTX_PROP_CAP: test knob)
   int32_t prop_vec, prop_cap;
+  // candidate edges of the same kernel and shape: only the obstacles that reach the near ball of the new node are tested
+  // (RRTX_OBS_CULL; 0: every edge against every obstacle of the tile)
+  int32_t obs_cull;
+  // grid index of the same kernel and shape: a pass gathers the cells and entries of all its centres in one round trip each
+  // (RRTX_GRID_MERGE; 0: centre after centre)
+  int32_t grid_merge;
 };
 constexpr int GRID_CAP0 = 16, GRID_CAP1 = 16;
 

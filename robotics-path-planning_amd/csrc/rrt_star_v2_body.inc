@@ -612,6 +612,7 @@ struct GridS {
   int sh, gn, pool_blocks, pool_next, excl, min_n;
   uint32_t goal_q;
   int ok;           // 0: the index is off, or incomplete for the rest of the launch -- every pass streams
+  int merge;        // 1: a pass gathers for all its centres together (RRTX_GRID_MERGE)
   int bytes, nodes; // what the last pass read: bytes and nodes (entries) it tested
 };
 constexpr int GRID_CAP0 = rppk::GRID_CAP0, GRID_CAP1 = rppk::GRID_CAP1, GRID_CAPT = GRID_CAP0 + GRID_CAP1;
@@ -711,30 +712,123 @@ __device__ __forceinline__ void grid_remove(GridS& g, int node, uint32_t q) {
   if (lane == 0) g.cnt[cell] = k - 1;
 }
 
-// One centre of a pass over the index: the cells of the square window [centre - rw, centre + rw] (at most 64, at most
-// 256 entries).  BALL: the entries with grid distance <= thr, ascending, at hits[off ..] (first `cap`) and lhit[] (first
-// HWF; nullptr: none); gz >= 0 applies the goal-cell rule of scan2q_slot (zcnt).  NEAREST: (best, runner-up, group) over
-// the window, runner-up capped at D^2 (D: distance to the nearest cell outside the window, a lower bound of any node
-// there); the answer stands only when best + 2 q_m (+ 1 step for the roundings of the caller's test) lies inside D --
-// then both the winner and every decision the caller takes on the runner-up are those of the full pass -- else the
-// window grows (twice at most).  False: the index cannot answer (the caller streams).
+// The tests of one centre on the entries the lanes hold for it (every other slot: d = 0xffffffff, ei = 0x7fffffff).
+// BALL: the entries with grid distance <= thr, ascending, at hits[off ..] (first `cap`) and lhit[] (first HWF; nullptr:
+// none); gz >= 0 applies the goal-cell rule of scan2q_slot (zcnt).  NEAREST: (best, runner-up, group) over the window,
+// runner-up capped at D^2 (D: distance to the nearest cell outside the window, a lower bound of any node there); the
+// answer stands only when best + 2 q_m (+ 1 step for the roundings of the caller's test) lies inside D -- then both the
+// winner and every decision the caller takes on the runner-up are those of the full pass.  Returns 1: answered, 0: the
+// index cannot answer (the caller streams), 2: the nearest query needs a wider window (wbest: the best distance seen).
+__device__ __forceinline__ int grid_tests(const GridS& g, uint32_t cq, int D, bool ball, uint32_t thr, bool nearest,
+                                          const uint32_t (&ev)[GE], const int (&ei)[GE], const uint32_t (&d)[GE],
+                                          int32_t* __restrict__ hits, int off, int cap, int32_t* lhit, int32_t* ltmp,
+                                          int gz, int& cnt, int& zcnt, uint32_t& best, uint32_t& second, int& grp,
+                                          uint32_t& wbest) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  if (ball) {
+    // the left-out goal duplicates lie at goal_q: counted with gz >= 0, else they would be hits the index cannot list
+    const bool zin = g.excl > 0 && qdist(g.goal_q, cq) <= thr;
+    if (zin && gz < 0) return 0;
+    int z = zin ? g.excl : 0, H = 0;
+    bool hh[GE];
+#pragma unroll
+    for (int k = 0; k < GE; k++) {
+      hh[k] = d[k] <= thr;   // thr < 2^32 - 1: an empty slot never hits
+      if (gz >= 0) {
+        const bool skip = hh[k] && ev[k] == g.goal_q && ei[k] != gz;
+        z += __popcll(__ballot(skip));
+        hh[k] = hh[k] && !skip;
+      }
+      const uint64_t m = __ballot(hh[k]);
+      if (hh[k]) ltmp[H + __popcll(m & lt_mask)] = ei[k];
+      H += __popcll(m);
+    }
+    lds_barrier();
+    // ascending order: a hit's place is the number of hits with a lower index
+    for (int h0 = 0; h0 < H; h0 += 64) {
+      if (h0 + lane < H) {
+        const int me = ltmp[h0 + lane];
+        int r = 0;
+        for (int j = 0; j < H; j++) r += ltmp[j] < me ? 1 : 0;
+        if (r < cap) hits[off + r] = me;
+        if (lhit && r < HWF) lhit[r] = me;
+      }
+    }
+    lds_barrier();
+    cnt = H;
+    zcnt = z;
+  }
+  if (!nearest) return 1;
+  uint32_t b = 0xffffffffu, s = 0xffffffffu;
+  int bi = 0x7fffffff;
+#pragma unroll
+  for (int k = 0; k < GE; k++) {
+    if (d[k] < b || (d[k] == b && ei[k] < bi)) {
+      s = b;
+      b = d[k];
+      bi = ei[k];
+    } else {
+      s = min(s, d[k]);
+    }
+  }
+  uint32_t wb = b;
+  int wi = bi;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const uint32_t ob = (uint32_t)__shfl_xor((int)wb, o);
+    const int oi = __shfl_xor(wi, o);
+    const bool take = ob < wb || (ob == wb && oi < wi);
+    wb = take ? ob : wb;
+    wi = take ? oi : wi;
+  }
+  uint32_t ws = bi == wi ? s : b;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) ws = min(ws, (uint32_t)__shfl_xor((int)ws, o));
+  // the left-out duplicates tie with first_goal (in the index, lower index): a runner-up at the goal's distance
+  if (g.excl > 0) ws = min(ws, qdist(g.goal_q, cq));
+  wbest = wb;
+  if (wb < QSAT && (double)D > __builtin_sqrt((double)wb) + 4.0) {
+    best = wb;
+    second = min(ws, (uint32_t)(D * D));
+    grp = wi & ~3;
+    return 1;
+  }
+  return 2;
+}
+
+// The square window [centre - rw, centre + rw] in cells: false when it holds more than 64.  D: grid_tests.
+__device__ __forceinline__ bool grid_window(const GridS& g, uint32_t cq, int rw, int& x0, int& y0, int& nwx, int& nc, int& D) {
+  const int ux = (int)((cq ^ 0x80008000u) & 0xffffu), uy = (int)((cq ^ 0x80008000u) >> 16);
+  x0 = max(ux - rw, 0) >> g.sh;
+  y0 = max(uy - rw, 0) >> g.sh;
+  const int x1 = min(ux + rw, 65535) >> g.sh, y1 = min(uy + rw, 65535) >> g.sh;
+  nwx = x1 - x0 + 1;
+  nc = nwx * (y1 - y0 + 1);
+  if (nc > 64) return false;
+  D = 32767;
+  if (x0 > 0) D = min(D, ux - (x0 << g.sh) + 1);
+  if (x1 < g.gn - 1) D = min(D, ((x1 + 1) << g.sh) - ux);
+  if (y0 > 0) D = min(D, uy - (y0 << g.sh) + 1);
+  if (y1 < g.gn - 1) D = min(D, ((y1 + 1) << g.sh) - uy);
+  return true;
+}
+
+// window half-width of the next attempt of a nearest query: past best + margin when a node was found, else threefold
+__device__ __forceinline__ int grid_grow(uint32_t wb, int rw) { return wb < QSAT ? (int)__builtin_sqrt((double)wb) + 6 : 3 * rw + 1; }
+
+// One centre of a pass over the index, by itself: the cells of its window (at most 64, at most 256 entries), one round
+// trip for their counts and one for their entries, then grid_tests; a nearest query whose window must grow tries twice
+// more (three attempts in all; first_attempt = 1: the merged gather of grid_pass made the first).  False: the index
+// cannot answer (the caller streams).
 __device__ __forceinline__ bool grid_centre(const GridS& g, uint32_t cq, int rw, bool ball, uint32_t thr, bool nearest,
                                             int32_t* __restrict__ hits, int off, int cap, int32_t* lhit, int32_t* ltmp,
                                             int gz, int& cnt, int& zcnt, uint32_t& best, uint32_t& second, int& grp,
-                                            int& bytes, int& nodes) {
+                                            int& bytes, int& nodes, int first_attempt = 0) {
   const int lane = threadIdx.x & 63;
-  const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  const int ux = (int)((cq ^ 0x80008000u) & 0xffffu), uy = (int)((cq ^ 0x80008000u) >> 16);
-  for (int attempt = 0; attempt < 3; attempt++) {
-    const int x0 = max(ux - rw, 0) >> g.sh, x1 = min(ux + rw, 65535) >> g.sh;
-    const int y0 = max(uy - rw, 0) >> g.sh, y1 = min(uy + rw, 65535) >> g.sh;
-    const int nwx = x1 - x0 + 1, nc = nwx * (y1 - y0 + 1);
-    if (nc > 64) return false;
-    int D = 32767;
-    if (x0 > 0) D = min(D, ux - (x0 << g.sh) + 1);
-    if (x1 < g.gn - 1) D = min(D, ((x1 + 1) << g.sh) - ux);
-    if (y0 > 0) D = min(D, uy - (y0 << g.sh) + 1);
-    if (y1 < g.gn - 1) D = min(D, ((y1 + 1) << g.sh) - uy);
+  for (int attempt = first_attempt; attempt < 3; attempt++) {
+    int x0, y0, nwx, nc, D;
+    if (!grid_window(g, cq, rw, x0, y0, nwx, nc, D)) return false;
     int cell = 0, cn = 0, cb = 0;
     if (lane < nc) {
       cell = (y0 + lane / nwx) * g.gn + x0 + lane % nwx;
@@ -776,78 +870,123 @@ __device__ __forceinline__ bool grid_centre(const GridS& g, uint32_t cq, int rw,
       ev[k] = (uint32_t)(e >> 32);
       d[k] = ptr[k] ? qdist(ev[k], cq) : 0xffffffffu;
     }
-    if (ball && attempt == 0) {
-      // the left-out goal duplicates lie at goal_q: counted with gz >= 0, else they would be hits the index cannot list
-      const bool zin = g.excl > 0 && qdist(g.goal_q, cq) <= thr;
-      if (zin && gz < 0) return false;
-      int z = zin ? g.excl : 0, H = 0;
-      bool hh[GE];
-#pragma unroll
-      for (int k = 0; k < GE; k++) {
-        hh[k] = d[k] <= thr;   // thr < 2^32 - 1: an empty slot never hits
-        if (gz >= 0) {
-          const bool skip = hh[k] && ev[k] == g.goal_q && ei[k] != gz;
-          z += __popcll(__ballot(skip));
-          hh[k] = hh[k] && !skip;
-        }
-        const uint64_t m = __ballot(hh[k]);
-        if (hh[k]) ltmp[H + __popcll(m & lt_mask)] = ei[k];
-        H += __popcll(m);
-      }
-      lds_barrier();
-      // ascending order: a hit's place is the number of hits with a lower index
-      for (int h0 = 0; h0 < H; h0 += 64) {
-        if (h0 + lane < H) {
-          const int me = ltmp[h0 + lane];
-          int r = 0;
-          for (int j = 0; j < H; j++) r += ltmp[j] < me ? 1 : 0;
-          if (r < cap) hits[off + r] = me;
-          if (lhit && r < HWF) lhit[r] = me;
-        }
-      }
-      lds_barrier();
-      cnt = H;
-      zcnt = z;
-    }
-    if (!nearest) return true;
-    uint32_t b = 0xffffffffu, s = 0xffffffffu;
-    int bi = 0x7fffffff;
-#pragma unroll
-    for (int k = 0; k < GE; k++) {
-      if (d[k] < b || (d[k] == b && ei[k] < bi)) {
-        s = b;
-        b = d[k];
-        bi = ei[k];
-      } else {
-        s = min(s, d[k]);
-      }
-    }
-    uint32_t wb = b;
-    int wi = bi;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const uint32_t ob = (uint32_t)__shfl_xor((int)wb, o);
-      const int oi = __shfl_xor(wi, o);
-      const bool take = ob < wb || (ob == wb && oi < wi);
-      wb = take ? ob : wb;
-      wi = take ? oi : wi;
-    }
-    uint32_t ws = bi == wi ? s : b;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) ws = min(ws, (uint32_t)__shfl_xor((int)ws, o));
-    // the left-out duplicates tie with first_goal (in the index, lower index): a runner-up at the goal's distance
-    if (g.excl > 0) ws = min(ws, qdist(g.goal_q, cq));
-    if (wb < QSAT && (double)D > __builtin_sqrt((double)wb) + 4.0) {
-      best = wb;
-      second = min(ws, (uint32_t)(D * D));
-      grp = wi & ~3;
-      return true;
-    }
-    // grow the window: past best + margin when a node was found, else threefold
-    rw = wb < QSAT ? (int)__builtin_sqrt((double)wb) + 6 : 3 * rw + 1;
+    uint32_t wb = 0xffffffffu;
+    const int r = grid_tests(g, cq, D, ball && attempt == 0, thr, nearest, ev, ei, d, hits, off, cap, lhit, ltmp, gz, cnt,
+                             zcnt, best, second, grp, wb);
+    if (r != 2) return r == 1;
+    rw = grid_grow(wb, rw);
     ball = false;
   }
   return false;
+}
+
+// A centre of a pass: what is asked about it, and the answers.
+struct GCen {
+  uint32_t cq, thr;      // packed centre; ball threshold
+  int rw;                // window half-width (grid steps)
+  bool on, ball, nearest;
+  int off, cap, gz;      // ball: list offset and room in hits[], goal-cell rule
+  int32_t* lhit;         // ball: the LDS copy of the list (nullptr: none)
+  int cnt, zcnt, grp;    // answers (grid_tests)
+  uint32_t best, second;
+};
+
+// All centres of a pass together (RRTX_GRID_MERGE): one lane per (centre, cell) pair of every window and one round trip for
+// all their counts; a prefix sum over the pairs gives every entry a slot (GE per lane, each slot remembers its centre;
+// a slot finds its pair by a binary search of the prefix array in the pass's LDS scratch) and one more round trip loads
+// them all; then each centre runs grid_tests on its own slots -- the same entries, so the same answers and the same
+// bytes as the per-centre passes.  Returns 1: every centre is answered, except the nearest queries flagged in `grow`
+// (bit c; ce[c].best = the best distance seen), whose window must grow: grid_centre goes on with them from the second
+// attempt; 0: the index cannot answer (the caller streams); -1: the windows do not fit one gather (more than 64 pairs or
+// 256 entries in all, or one window too large): nothing was answered, the per-centre passes decide.
+template <int NC>
+__device__ __forceinline__ int grid_merged(const GridS& g, GCen (&ce)[NC], int32_t* __restrict__ hits, int32_t* ltmp,
+                                           int& bytes, int& nodes, uint32_t& grow) {
+  const int lane = threadIdx.x & 63;
+  int D[NC], npairs = 0;
+  int cid = -1, cell = 0, cn = 0, cb = 0;
+#pragma unroll
+  for (int c = 0; c < NC; c++) {
+    D[c] = 0;
+    if (!ce[c].on) continue;
+    int x0, y0, nwx, nc;
+    if (!grid_window(g, ce[c].cq, ce[c].rw, x0, y0, nwx, nc, D[c])) return -1;
+    const int l = lane - npairs;
+    if (l >= 0 && l < nc) {
+      cid = c;
+      cell = (y0 + l / nwx) * g.gn + x0 + l % nwx;
+    }
+    npairs += nc;
+  }
+  if (npairs > 64) return -1;
+  if (cid >= 0) {
+    cn = g.cnt[cell];
+    cb = g.blk[cell];
+  }
+  if (__ballot(cn > GRID_CAPT) != 0ull) return 0;
+  int inc = cn;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(inc, o);
+    if (lane >= o) inc += t;
+  }
+  const int tot = __shfl(inc, 63);
+  if (tot > 64 * GE) return -1;
+  bytes += 8 * npairs + 8 * tot;
+  nodes += tot;
+  ltmp[lane] = inc;
+  ltmp[64 + lane] = cell;
+  ltmp[128 + lane] = cb;
+  ltmp[192 + lane] = cid;
+  lds_barrier();
+  uint32_t ev[GE];
+  int ei[GE], sc[GE];
+  const uint64_t* ptr[GE];
+#pragma unroll
+  for (int k = 0; k < GE; k++) {
+    const int slot = lane + 64 * k;
+    ptr[k] = nullptr;
+    sc[k] = -1;
+    if (slot < tot) {
+      int j = 0;   // the first pair whose inclusive prefix passes the slot (tot = the last prefix > slot: j <= 63)
+#pragma unroll
+      for (int st = 32; st >= 1; st >>= 1)
+        if (ltmp[j + st - 1] <= slot) j += st;
+      const int r = slot - (j > 0 ? ltmp[j - 1] : 0);
+      const int ej = ltmp[64 + j], bj = ltmp[128 + j];
+      sc[k] = ltmp[192 + j];
+      ptr[k] = r < GRID_CAP0 ? g.ent + (int64_t)ej * GRID_CAP0 + r : g.pool + (int64_t)(bj - 1) * GRID_CAP1 + (r - GRID_CAP0);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < GE; k++) {
+    const uint64_t e = ptr[k] ? *ptr[k] : 0ull;
+    ei[k] = (int)(uint32_t)e;
+    ev[k] = (uint32_t)(e >> 32);
+  }
+  lds_barrier();   // the prefix arrays are read: grid_tests takes the scratch
+  grow = 0u;
+#pragma unroll
+  for (int c = 0; c < NC; c++) {
+    if (!ce[c].on) continue;
+    uint32_t d[GE];
+    int eic[GE];
+#pragma unroll
+    for (int k = 0; k < GE; k++) {
+      const bool mine = sc[k] == c;
+      eic[k] = mine ? ei[k] : 0x7fffffff;
+      d[k] = mine ? qdist(ev[k], ce[c].cq) : 0xffffffffu;
+    }
+    uint32_t wb = 0xffffffffu;
+    const int r = grid_tests(g, ce[c].cq, D[c], ce[c].ball, ce[c].thr, ce[c].nearest, ev, eic, d, hits, ce[c].off, ce[c].cap,
+                             ce[c].lhit, ltmp, ce[c].gz, ce[c].cnt, ce[c].zcnt, ce[c].best, ce[c].second, ce[c].grp, wb);
+    if (r == 0) return 0;
+    if (r == 2) {
+      grow |= 1u << c;
+      ce[c].best = wb;
+    }
+  }
+  return 1;
 }
 
 // A pass of scan2q's contract (same arguments and outputs) answered from the index; false: it cannot be (the caller
@@ -862,6 +1001,72 @@ __device__ __forceinline__ bool grid_pass(GridS& g, int rwn, uint32_t qq, uint32
   int bytes = 0, nodes = 0;
   uint32_t b, s;
   int gr, zc = 0, cnt = 0;
+  if (g.merge) {
+    // centre 0: the pass's own ball; centre 1 + j: as in the loop below
+    GCen ce[KS + 2];
+    ce[0].on = NEAR;
+    ce[0].cq = qq; ce[0].thr = thr; ce[0].rw = (int)__builtin_sqrt((double)thr) + 1;
+    ce[0].ball = true; ce[0].nearest = false;
+    ce[0].off = 0; ce[0].cap = 0x7fffffff; ce[0].gz = gz; ce[0].lhit = lhit;
+    ce[0].cnt = 0; ce[0].zcnt = 0; ce[0].grp = 0x7ffffffc; ce[0].best = ce[0].second = 0xffffffffu;
+#pragma unroll
+    for (int j = 0; j <= KS; j++) {
+      GCen& e = ce[1 + j];
+      const int jo = j < KS ? j : 0;
+      e.cq = j == 0 ? sq : sp[j > 0 ? j - 1 : 0].sq;
+      e.nearest = j == 0 ? NEAREST : sp[j > 0 ? j - 1 : 0].thr != 0u;
+      e.thr = j < KS ? sp[jo].thr : 0u;
+      e.ball = e.thr != 0u;
+      e.on = e.nearest || e.ball;
+      e.rw = max(e.ball ? (int)__builtin_sqrt((double)e.thr) + 1 : 0, e.nearest ? rwn : 0);
+      e.off = KS > 0 ? sp[jo].off : 0;
+      e.cap = KS > 0 ? sp[jo].cap : 0;
+      e.gz = -1;
+      e.lhit = nullptr;
+      e.cnt = 0; e.zcnt = 0; e.grp = 0x7ffffffc; e.best = e.second = 0xffffffffu;
+    }
+    uint32_t grow = 0u;
+    const int r = grid_merged<KS + 2>(g, ce, hits, ltmp, bytes, nodes, grow);
+    if (r == 0) return false;
+    if (r == 1) {
+#pragma unroll
+      for (int j = 0; j <= KS; j++) {
+        GCen& e = ce[1 + j];
+        if (grow >> (1 + j) & 1u) {   // a nearest query whose window must grow: by itself, from the second attempt
+          int bc, bz;
+          const uint32_t wb = e.best;
+          e.best = e.second = 0xffffffffu;
+          if (!grid_centre(g, e.cq, grid_grow(wb, e.rw), false, 0u, true, hits, 0, 0, nullptr, ltmp, -1, bc, bz, e.best,
+                           e.second, e.grp, bytes, nodes, 1))
+            return false;
+        }
+        if (j == 0) {
+          if (NEAREST) {
+            gbest = (double)e.best;
+            gsecond = (double)e.second;
+            ggrp = e.grp;
+          }
+        } else {
+          sp[j - 1].best = (double)e.best;
+          sp[j - 1].second = (double)e.second;
+          sp[j - 1].grp = e.grp;
+        }
+        if (j < KS) sp[j < KS ? j : 0].cnt = e.cnt;
+      }
+      if (NEAR && threadIdx.x == 0) {
+        sh.wave_cnt[0] = ce[0].cnt;
+        sh.wave_start[0] = 0;
+        sh.fa = ce[0].zcnt;
+      }
+      lds_barrier();
+      if (NEAR && zskip) *zskip = gz >= 0 ? ce[0].zcnt : 0;
+      total = NEAR ? ce[0].cnt : 0;
+      g.bytes = bytes;
+      g.nodes = nodes;
+      return true;
+    }
+    // the windows do not fit one gather: per-centre passes, from the start
+  }
   if (NEAR) {
     const int rw = (int)__builtin_sqrt((double)thr) + 1;
     if (!grid_centre(g, qq, rw, true, thr, false, hits, 0, 0x7fffffff, lhit, ltmp, gz, cnt, zc, b, s, gr, bytes, nodes))
@@ -1189,6 +1394,58 @@ __device__ __forceinline__ int edge_hits_obstacle_band(const rpp::Edge& e, bool 
   return dmin <= thr - tol ? 1 : (dmin <= thr + tol ? 2 : 0);
 }
 
+// Obstacles that can matter to a candidate edge of this iteration (one-wave shape, om <= 64): bit k of the wave-uniform
+// result is CLEAR only when obstacle k gives 0 in edge_hits_obstacle_band and false in rpp::edge_hits_obstacle for every
+// edge eval_edges_dual2 / eval_edges_back2 test, so leaving it out changes no flag.  Lane k tests
+//     |n - o_k|  <=  sqrt(othr_k + tolmax) + R + slack            (a NaN anywhere keeps the obstacle)
+// about the new node n = (nx, ny), with R = sqrt(r2):
+//   * every point such an edge tests lies within R + delta of n.  A candidate u entered the list with |u - n|^2 <= r2 up
+//     to 2^-46 relative (build_candidates: vf <= r2 (1 - eps) in the fast mode, the reference's v <= r2 in the exact one;
+//     v and vf are within 2^-51 relative of the true square), so u is in the ball; n is its centre; the winner's end
+//     point w (eval_edges_back2's origin) is a point of the edge u_sel -> n; the ball is convex, so the segments u - n
+//     and w - u are inside.  The points walked are f + i s with i <= n_expand and n_expand res <= d: on the segment up to
+//     the rounding of n_expand < 2^31 additions, each below 2^-53 of a coordinate -> delta < 2^-21 (|n| + R) per axis;
+//     the exact polyline's step res (cos, sin) differs from res (dx, dy) / d by a few ULP of res, n_expand times:
+//     below 2^-50 R.  Both are far inside the relative part of the slack, 1e-5 (1 + |n| + |o| + R);
+//   * band test: non-zero needs dmin <= othr + tol with tol = 1e-10 (1 + |fx| + |fy| + |ox| + |oy|) (4 + othr); f is in
+//     the ball, |fx| + |fy| <= |nx| + |ny| + 2 (R + delta), so tol <= tolmax as written below (its factor 2 pays for delta
+//     and the roundings);
+//   * the roundings of this test and of the dd = dx dx + dy dy it stands in for are relative 2^-50: the absolute 1e-3 map
+//     units and the relative part leave them ten orders of magnitude.
+// A culled obstacle therefore has every tested point further than sqrt(othr + tolmax) + ~1e-3 from its centre.
+__device__ __forceinline__ uint64_t obstacle_mask(int om, double nx, double ny, double r2, const Sh2& sh) {
+  const int k = threadIdx.x & 63;
+  bool keep = false;
+  if (k < om) {
+    const double ox = sh.ox[k], oy = sh.oy[k], thr = sh.othr[k];
+    const double R = __builtin_sqrt(r2);
+    const double mag = 1.0 + rpp::dabs(nx) + rpp::dabs(ny) + rpp::dabs(ox) + rpp::dabs(oy);
+    const double tolmax = 2e-10 * (mag + 2.0 * R) * (4.0 + thr);
+    const double reach = __builtin_sqrt(thr + tolmax) + R + (1e-3 + 1e-5 * (mag + R));
+    const double dx = ox - nx, dy = oy - ny;
+    keep = !(__builtin_sqrt(dx * dx + dy * dy) > reach);
+  }
+  return __ballot(keep);
+}
+
+// The exact form of a candidate edge (eval_edges_dual2): the reference's atan2 / cos / sin, the sequential additions and
+// the snap test; `e` gets the exact step, end point and snap bit.
+__device__ __forceinline__ void edge_exact_steer(rpp::Edge& e, double res) {
+  const double dx = e.tx - e.fx, dy = e.ty - e.fy;
+  const double theta = rpp_glibc_atan2(dy, dx);
+  e.sx = res * rpp_glibc_cos(theta);
+  e.sy = res * rpp_glibc_sin(theta);
+  double px = e.fx, py = e.fy;
+  for (int i = 0; i < e.n_expand; i++) {
+    px += e.sx;
+    py += e.sy;
+  }
+  const int snapped = rpp::py_hypot(e.tx - px, e.ty - py) <= res;
+  e.ex = snapped ? e.tx : px;
+  e.ey = snapped ? e.ty : py;
+  e.snapped = snapped;
+}
+
 // Both directions of every candidate edge (see eval_edges_dual in v1), coordinates from the LDS records:
 // choose_parent's steer(node -> new) :1265 and rewire's steer(new -> node) :1359 with their collision tests.
 //
@@ -1203,7 +1460,12 @@ __device__ __forceinline__ int edge_hits_obstacle_band(const rpp::Edge& e, bool 
 // An edge with either decision in doubt -- in practice the edge from the NEAREST node, whose length is 8 x 0.25 = 2.0 give
 // or take an ULP, in about every second iteration -- is evaluated again exactly as before (atan2 / cos / sin replicas, the
 // sequential additions, the exact test), by its own lane alone instead of all candidates' lanes diverging in the replicas.
-__device__ __forceinline__ void eval_edges_dual2(const Ctx& c, int om, int nu, double nx, double ny, Sh2& sh) {
+//
+// `cull` (one-wave shape only, obstacle_mask above): one edge per lane, held in registers, against the obstacles of `omask`
+// alone -- no (edge, obstacle) pair decoding, no re-read of the edge, and nothing at all to test when the mask is empty
+// (an edge in doubt about its snap still takes its exact steer).  Same flags and end points as the pair loops.
+__device__ __forceinline__ void eval_edges_dual2(const Ctx& c, int om, int nu, double nx, double ny, Sh2& sh,
+                                                 bool cull, uint64_t omask) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   // 4 waves: direction = w>>1 (even waves work, odd ones only take part in the pair loops); 2 waves: direction = w;
   // 1 wave: direction = lane>>5 (both half-waves run the same instruction stream)
@@ -1235,6 +1497,41 @@ __device__ __forceinline__ void eval_edges_dual2(const Ctx& c, int om, int nu, d
       E.snapped = unsure ? 4 : 1;   // bit 2: to be evaluated exactly
       sh.cflag[kind * EBD + el] = 0;   // collision flags of this pass
     }
+    if (NW == 1 && cull) {
+      if (act) {
+        rpp::Edge ed;
+        ed.fx = E.fx; ed.fy = E.fy; ed.sx = E.sx; ed.sy = E.sy; ed.tx = E.tx; ed.ty = E.ty;
+        ed.ex = ed.tx; ed.ey = ed.ty;
+        ed.n_expand = E.n_expand;
+        ed.snapped = 1;
+        int hit = 0, band = 0;
+        if (!unsure) {
+          for (uint64_t m = omask; m; m &= m - 1) {
+            const int k = __builtin_ctzll(m);
+            const double tol = 1e-10 * (1.0 + rpp::dabs(ed.fx) + rpp::dabs(ed.fy) + rpp::dabs(sh.ox[k]) + rpp::dabs(sh.oy[k])) *
+                               (4.0 + sh.othr[k]);
+            const int r = edge_hits_obstacle_band(ed, true, sh.ox[k], sh.oy[k], sh.othr[k], tol);
+            hit |= r == 1;
+            band |= r == 2;
+          }
+        }
+        if (unsure || (band && !hit)) {
+          edge_exact_steer(ed, c.res);
+          E.sx = ed.sx;
+          E.sy = ed.sy;
+          E.ex = ed.ex;
+          E.ey = ed.ey;
+          E.snapped = ed.snapped | 16;
+          hit = 0;
+          for (uint64_t m = omask; m; m &= m - 1) {
+            const int k = __builtin_ctzll(m);
+            if (rpp::edge_hits_obstacle(ed, sh.ox[k], sh.oy[k], sh.othr[k])) hit = 1;
+          }
+        }
+        sh.cflag[kind * EBD + el] = hit;
+      }
+      lds_barrier();
+    } else {
     lds_barrier();
     for (int p = tid; p < 2 * nb * om; p += TPB) {
       const int q = p / om, k = p - q * om;
@@ -1253,20 +1550,13 @@ __device__ __forceinline__ void eval_edges_dual2(const Ctx& c, int om, int nu, d
     const bool redo = act && ((E.snapped & 4) || ((E.snapped & 8) && !sh.cflag[kind * EBD + el]));
     if (block_any(redo, sh)) {
       if (redo) {
-        const double dx = E.tx - E.fx, dy = E.ty - E.fy;
-        const double theta = rpp_glibc_atan2(dy, dx);
-        const double sx = c.res * rpp_glibc_cos(theta), sy = c.res * rpp_glibc_sin(theta);
-        double px = E.fx, py = E.fy;
-        for (int i = 0; i < E.n_expand; i++) {
-          px += sx;
-          py += sy;
-        }
-        const int snapped = rpp::py_hypot(E.tx - px, E.ty - py) <= c.res;
-        E.sx = sx;
-        E.sy = sy;
-        E.ex = snapped ? E.tx : px;
-        E.ey = snapped ? E.ty : py;
-        E.snapped = snapped | 16;   // bit 4: exact polyline in place
+        rpp::Edge ed = E;
+        edge_exact_steer(ed, c.res);
+        E.sx = ed.sx;
+        E.sy = ed.sy;
+        E.ex = ed.ex;
+        E.ey = ed.ey;
+        E.snapped = ed.snapped | 16;   // bit 4: exact polyline in place
         sh.cflag[kind * EBD + el] = 0;
       }
       lds_barrier();
@@ -1280,6 +1570,7 @@ __device__ __forceinline__ void eval_edges_dual2(const Ctx& c, int om, int nu, d
         if (rpp::edge_hits_obstacle(ee, sh.ox[k], sh.oy[k], sh.othr[k])) sh.cflag[slot] = 1;
       }
       lds_barrier();
+    }
     }
     if (tid < nb) {
       const rpp::Edge& f = sh.u.edge[tid];
@@ -1296,10 +1587,27 @@ __device__ __forceinline__ void eval_edges_dual2(const Ctx& c, int om, int nu, d
 }
 
 // backward edges only, from the true new-node position (the winning edge did not snap): refresh bits 1,2 + uhyp
-__device__ __forceinline__ void eval_edges_back2(const Ctx& c, int om, int nu, double wx, double wy, Sh2& sh) {
+// (`cull`: as in eval_edges_dual2 -- w is a point of the winning edge, inside the ball obstacle_mask covers)
+__device__ __forceinline__ void eval_edges_back2(const Ctx& c, int om, int nu, double wx, double wy, Sh2& sh,
+                                                 bool cull, uint64_t omask) {
   const int tid = threadIdx.x;
   for (int base = 0; base < nu; base += 2 * EBD) {
     const int nb = (nu - base) < 2 * EBD ? (nu - base) : 2 * EBD;
+    if (NW == 1 && cull) {
+      if (tid < nb) {
+        rpp::Edge ed;
+        rpp::steer(&ed, wx, wy, sh.ux[base + tid], sh.uy[base + tid], rpp::dinf(), c.res);
+        sh.u.edge[tid] = ed;
+        sh.uhyp[base + tid] = rpp::py_hypot(sh.ux[base + tid] - wx, sh.uy[base + tid] - wy);
+        int hit = 0;
+        for (uint64_t m = omask; m; m &= m - 1) {
+          const int k = __builtin_ctzll(m);
+          if (rpp::edge_hits_obstacle(ed, sh.ox[k], sh.oy[k], sh.othr[k])) hit = 1;
+        }
+        sh.cflag[tid] = hit;
+      }
+      lds_barrier();
+    } else {
     if (tid < nb) {
       rpp::steer(&sh.u.edge[tid], wx, wy, sh.ux[base + tid], sh.uy[base + tid], rpp::dinf(), c.res);
       sh.uhyp[base + tid] = rpp::py_hypot(sh.ux[base + tid] - wx, sh.uy[base + tid] - wy);
@@ -1311,6 +1619,7 @@ __device__ __forceinline__ void eval_edges_back2(const Ctx& c, int om, int nu, d
       if (rpp::edge_hits_obstacle(sh.u.edge[e], sh.ox[k], sh.oy[k], sh.othr[k])) sh.cflag[e] = 1;
     }
     lds_barrier();
+    }
     if (tid < nb) {
       const rpp::Edge& e = sh.u.edge[tid];
       const int s = (!sh.cflag[tid]) && rpp::in_play_area(c.has_play, c.play_area, e.ex, e.ey);
@@ -1366,6 +1675,18 @@ constexpr int CE = (NU + 63) / 64;   // near candidates per lane when a wave hol
 // Inst::phase[PROP_WALK_SLOT] (a slot no phase timer of this kernel uses) counts the walks propagate_lanes finished,
 // plus PROP_WALK_FULL for each one whose pending list ran full (rrtx_get_phase_cycles; tests and diagnostics)
 constexpr int PROP_WALK_SLOT = 10;
+// Obstacle-cull counts (diagnostic build only; this kernel stamps no phase 12 and no phase 15, their spans -- the overflow
+// check and the loop head -- fall to the next stamp, "sample"): Inst::phase[CULL_POP_SLOT] sums the popcounts of the
+// masks, Inst::phase[CULL_EVAL_SLOT] counts the iterations that evaluated candidate edges under a mask (low 32 bits) and
+// those whose mask was empty (from bit 32 on).  Both halves are at most the plan's iteration count summed over the
+// instances: tools/phase_profile.py prints them only while that sum is below 2^32 (the low half cannot have carried).
+constexpr int CULL_POP_SLOT = 12, CULL_EVAL_SLOT = 15;
+#ifdef RRTX_PHASE_TIMERS
+#define CULL_COUNT(m) do { if (threadIdx.x == 0) { ph_[CULL_POP_SLOT] += (int64_t)__popcll(m); \
+                                                   ph_[CULL_EVAL_SLOT] += 1ll + ((m) ? 0ll : (1ll << 32)); } } while (0)
+#else
+#define CULL_COUNT(m) do { } while (0)
+#endif
 constexpr unsigned long long PROP_WALK_FULL = 1ull << 40;
 // set bits of m below this lane
 __device__ __forceinline__ int lanes_below(uint64_t m) {
@@ -1553,6 +1874,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       gs.gn = c.gn;
       gs.pool_blocks = c.gpool_blocks;
       gs.min_n = c.grid_min;
+      gs.merge = c.grid_merge;
       gs.goal_q = goal_q;
       gs.ok = 1;
       grid_build(gs, xq, x, y, n, gx, gy, first_goal);
@@ -1671,7 +1993,6 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
 
   for (int step = 0; step < iters && it < c.max_iter && !stop; step++, it++) {
     ST_ADD(S_ITER, 1);
-    PH(15);
     // ---------------- sample :1132-1153
     if (!have_sample) {
       take_next_sample();
@@ -2153,10 +2474,20 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       // ---------------- choose_parent :1242-1282 (+ speculative backward edges)
       int have = 0, sel = -1;
       double min_cost = rpp::dinf();
+      // obstacles that reach the near ball (one-wave shape): the only ones this iteration's candidate edges can meet
+      bool cull = false;
+      uint64_t omask = 0;
+      if constexpr (NW == 1) {
+        if (nu > 0 && c.obs_cull && om <= 64) {
+          cull = true;
+          omask = obstacle_mask(om, nx, ny, r2, sh);
+          CULL_COUNT(omask);
+        }
+      }
       if (nu > 0) {
         ST_ADD(S_EU, nu);
         ST_ADD(S_ER, nvalid);
-        eval_edges_dual2(c, om, nu, nx, ny, sh);
+        eval_edges_dual2(c, om, nu, nx, ny, sh, cull, omask);
         if (pend_p >= 0) {
           sh.ucur[pend_p] = pend_cost;
           sh.ufc[pend_p] = pend_fc;
@@ -2188,7 +2519,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
         // ---------------- rewire (before append) :1340-1373
         ST_ADD(S_EU, nu);
         ST_ADD(S_ER, nvalid);
-        if (wx != nx || wy != ny) eval_edges_back2(c, om, nu, wx, wy, sh);
+        if (wx != nx || wy != ny) eval_edges_back2(c, om, nu, wx, wy, sh, cull, omask);
         for (int e = tid; e < nu; e += TPB) sh.uval[e] = wcost + sh.uhyp[e];   // edge_node.cost :1362
         if (tid == 0) {
           sh.n_rw = 0;
@@ -2436,7 +2767,6 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
     }
     PH(11);
     if (sh.overflow) stop = 1;
-    PH(12);
   }
 
   // write back state; the final goal search (rrt_04:1080-1084) is done by the v1 kernel
@@ -2474,4 +2804,5 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
 }
 
 #undef ST_ADD
+#undef CULL_COUNT
 }  // namespace RRT2_NS

@@ -845,6 +845,14 @@ int rrtx_plan_begin(rrtx_handle* h) {
   if (const char* e = getenv("RRTX_PROP_VEC")) c.prop_vec = atoi(e);
   c.prop_cap = 1 << 30;
   if (const char* e = getenv("RRTX_PROP_CAP")) c.prop_cap = atoi(e) > 0 ? atoi(e) : 0;
+  // rrt_04 kernel, one-wave shape: the candidate edges of an iteration are tested against the obstacles that reach the
+  // near ball of its new node only (RRTX_OBS_CULL=0: against every obstacle, in (edge, obstacle) pairs)
+  c.obs_cull = 1;
+  if (const char* e = getenv("RRTX_OBS_CULL")) c.obs_cull = atoi(e) != 0;
+  // rrt_04 kernel, one-wave shape: a pass over the grid index gathers for all its centres together (RRTX_GRID_MERGE=0:
+  // centre after centre, two round trips each)
+  c.grid_merge = 1;
+  if (const char* e = getenv("RRTX_GRID_MERGE")) c.grid_merge = atoi(e) != 0;
   // The staged per-instance start state (RNG, start / goal) lives on the device too: uploaded when the host changed it,
   // copied device -> device at every plan (2.7 KB per instance: 44 MB of pageable-memory upload per plan of 16 384 instances)
   if (!h->d_inst0) {
