@@ -307,9 +307,52 @@ int rrtx_smooth_paths(int32_t device, int32_t n_jobs, const double* paths_xy, co
 int rrtx_smooth_planned(rrtx_handle* h, int32_t max_iter);
 int rrtx_get_smoothed_path(rrtx_handle* h, int32_t instance, double* xy, int32_t cap_points, int32_t* n_out);
 
+/* ---- closed-loop RRT* (rrt_10 = 10_path_planning_01_rrt_10_closed_loop_rrt_star.py) -----------------------------------
+ * Tree phase: RRTX_ALGO_RS with expand_dis = +inf (rrt_10's class has no expand_dis attribute, so find_near_nodes
+ * :522-531 does not clamp its radius) and rrtx_set_rs_cost(h, RRTX_RS_COST_PATH): rrt_10's RRTStarReedsShepp inherits
+ * choose_parent / rewire / propagate_cost_to_leaves from RRTStar and they call ITS calc_new_cost (:1153-1161, the
+ * Reeds-Shepp length), where rrt_06's single class ends up with the Euclidean one defined last.
+ * Closed-loop stage: rrtx_track_planned after a plan of RRTX_ALGO_RS (either cost), entirely on the device
+ * (csrc/rrt_track.hip.h).  Valid again after every re-plan; the getters refer to the last rrtx_track_planned. */
+#define RRTX_RS_COST_EUCLID 0
+#define RRTX_RS_COST_PATH 1
+/* which of the tests of check_tracking_path_is_feasible (:1542-1562) refused a candidate */
+#define RRTX_TRACK_FAIL_REACH 1
+#define RRTX_TRACK_FAIL_ANGLE 2
+#define RRTX_TRACK_FAIL_LONG 4
+#define RRTX_TRACK_FAIL_COLLISION 8
+typedef struct rrtx_track_params {
+  double target_speed, yaw_th, xy_th, invalid_travel_ratio;              /* ClosedLoopRRTStar.__init__ :1458-1476 */
+  double dt, L, steer_max, accel_max, Kp, Lf, T, goal_dis, stop_speed;   /* module globals :1592-1607; steer_max <= 0.79 */
+} rrtx_track_params;
+typedef struct rrtx_track_outcome {
+  int32_t flag;      /* a feasible roll-out exists (the first element of planning()'s tuple) */
+  int32_t winner;    /* its position in the candidate list, -1 none */
+  int32_t n_cand;    /* len(get_goal_indexes()) */
+  int32_t len;       /* len(t) of the winner; x / y / yaw hold len + 1 values (goal pose appended, :1519-1521) */
+  int32_t node;      /* the winner's node index, -1 none */
+  int32_t status;    /* 0, RRTX_ST_OVERFLOW (a course longer than 960 points), RRTX_ST_REF_RAISES (the reference raises:
+                        a candidate course of fewer than 3 points, :1435) or RRTX_ST_UNSUPPORTED (tan outside the replica's
+                        domain); with any of them set the instance reports no winner */
+} rrtx_track_outcome;
+typedef struct rrtx_track_record {   /* what check_tracking_path_is_feasible returned for one candidate */
+  int32_t find_goal, len, fail, ood;
+  double t_last;
+} rrtx_track_record;
+int rrtx_set_rs_cost(rrtx_handle* h, int32_t mode);
+int rrtx_track_planned(rrtx_handle* h, const rrtx_track_params* tp);
+int rrtx_get_track_outcome(rrtx_handle* h, int32_t instance, rrtx_track_outcome* out);
+/* x, y, yaw: len + 1 doubles each; v, t, a, d: len doubles each (cap = doubles available in every array) */
+int rrtx_get_track_arrays(rrtx_handle* h, int32_t instance, double* x, double* y, double* yaw, double* v, double* t,
+                          double* a, double* d, int32_t cap);
+/* candidate node indices and their records, n_cand of each */
+int rrtx_get_track_records(rrtx_handle* h, int32_t instance, int32_t* cand, rrtx_track_record* rec, int32_t cap);
+/* HIP-event time of the kernels of the last rrtx_track_planned, and the roll-out steps they ran (both launches) */
+int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps);
+
 /* parity harness: out[i] = op(a[i], b[i]) evaluated on the device.  op 0 math.hypot, 1 x**2, 2 sin, 3 cos, 4 atan2,
  * 5 steer end x (rrt_04:1086-1115), 6 sqrt, 7 a/b, 8 acos, 9 asin, 10 checksum of the Reeds-Shepp steer
- * (0,0,0) -> (a, b, a+b) (rrt_06:1426-1441, csrc/rpp_rs.h) */
+ * (0,0,0) -> (a, b, a+b) (rrt_06:1426-1441, csrc/rpp_rs.h), 11 math.tan(a) (|a| <= 0.79), 12 np.hypot(a, b) */
 int rrtx_selftest_math(int32_t device, int32_t op, const double* a, const double* b, double* out, int64_t n);
 
 /* Run-time check of the arithmetic contract: "identical to the reference on this host" holds while

@@ -27,7 +27,11 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_get_path", "rrtx_get_results", "rrtx_results_device_ptr", "rrtx_copy_results_device", "rrtx_get_sobol_index", "rrtx_get_yaw", "rrtx_get_polylines", "rrtx_get_stats",
            "rrtx_enable_trace", "rrtx_get_trace", "rrtx_get_trace_kind", "rrtx_get_phase_cycles", "rrtx_last_error", "rrtx_destroy", "rrtx_selftest_math",
            "rrtx_smooth_paths", "rrtx_smooth_planned", "rrtx_get_smoothed_path", "rrtx_get_path_yaw", "rrtx_selfcheck", "rrtx_plan_many", "rrtx_plan_begin", "rrtx_plan_step",
-           "rrtx_set_launch_bound", "rrtx_rccl_unique_id", "rrtx_rccl_init", "rrtx_rccl_gather_results"]
+           "rrtx_set_launch_bound", "rrtx_rccl_unique_id", "rrtx_rccl_init", "rrtx_rccl_gather_results",
+           "rrtx_set_rs_cost", "rrtx_track_planned", "rrtx_get_track_outcome", "rrtx_get_track_arrays", "rrtx_get_track_records",
+           "rrtx_get_track_stats"]
+RS_COST_EUCLID, RS_COST_PATH = 0, 1     # include/rrtx.h: #define RRTX_RS_COST_*
+TRACK_FAIL_REACH, TRACK_FAIL_ANGLE, TRACK_FAIL_LONG, TRACK_FAIL_COLLISION = 1, 2, 4, 8   # #define RRTX_TRACK_FAIL_*
 
 
 class Params(C.Structure):
@@ -42,6 +46,25 @@ class Params(C.Structure):
                 ("connect_circle_dist", C.c_double), ("informed_rot", C.c_double * 4),
                 ("informed_c_min", C.c_double), ("curvature", C.c_double), ("goal_yaw_th", C.c_double),
                 ("goal_xy_th", C.c_double), ("step_size", C.c_double), ("reserved_d", C.c_double * 3)]
+
+
+class TrackParams(C.Structure):
+    """rrtx_track_params: ClosedLoopRRTStar's keywords (rrt_10:1458-1476) and the model globals (:1592-1607)."""
+    _fields_ = [(k, C.c_double) for k in ("target_speed", "yaw_th", "xy_th", "invalid_travel_ratio", "dt", "L", "steer_max",
+                                          "accel_max", "Kp", "Lf", "T", "goal_dis", "stop_speed")]
+
+
+TRACK_DEFAULTS = dict(target_speed=10.0 / 3.6, yaw_th=float(np.deg2rad(3.0)), xy_th=0.5, invalid_travel_ratio=5.0, dt=0.05,
+                      L=0.9, steer_max=float(np.deg2rad(40.0)), accel_max=5.0, Kp=2.0, Lf=0.5, T=100.0, goal_dis=0.5,
+                      stop_speed=0.5)
+
+
+class TrackOutcome(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("flag", "winner", "n_cand", "len", "node", "status")]
+
+
+TRACK_RECORD = np.dtype([("find_goal", np.int32), ("len", np.int32), ("fail", np.int32), ("ood", np.int32),
+                         ("t_last", np.float64)])
 
 
 class Stats(C.Structure):
@@ -106,6 +129,12 @@ def load():
     L.rrtx_get_smoothed_path.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
     L.rrtx_get_path_yaw.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
     L.rrtx_selfcheck.argtypes = [i32, i32, vp]
+    L.rrtx_set_rs_cost.argtypes = [vp, i32]
+    L.rrtx_track_planned.argtypes = [vp, C.POINTER(TrackParams)]
+    L.rrtx_get_track_outcome.argtypes = [vp, i32, C.POINTER(TrackOutcome)]
+    L.rrtx_get_track_arrays.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.rrtx_get_track_records.argtypes = [vp, i32, vp, vp, i32]
+    L.rrtx_get_track_stats.argtypes = [vp, C.POINTER(C.c_double), i64p]
     L.rrtx_plan_many.argtypes = [vp, i32, vp]
     L.rrtx_plan_begin.argtypes = [vp]
     L.rrtx_plan_step.argtypes = [vp, C.POINTER(i32)]
@@ -396,6 +425,51 @@ class Handle:
         self._chk(self.L.rrtx_get_polylines(self._h, instance, plen.ctypes.data, n.value, px.ctypes.data, py.ctypes.data,
                                             tot.value, C.byref(tot)), "rrtx_get_polylines")
         return plen, px, py
+
+    # ---- closed-loop stage of rrt_10 (rrtx_track_planned) on a planned RRTX_ALGO_RS handle
+    def set_rs_cost(self, mode):
+        self._chk(self.L.rrtx_set_rs_cost(self._h, mode), "rrtx_set_rs_cost")
+
+    def track_planned(self, **kw):
+        """Keywords: the fields of rrtx_track_params (defaults TRACK_DEFAULTS).  Returns 0 or RRTX_PARTIAL."""
+        p = dict(TRACK_DEFAULTS)
+        for k, v in kw.items():
+            if k not in p:
+                raise TypeError("track_planned: unknown keyword %r" % k)
+            p[k] = float(v)
+        rc = self.L.rrtx_track_planned(self._h, C.byref(TrackParams(**p)))
+        if rc != RRTX_PARTIAL:
+            self._chk(rc, "rrtx_track_planned")
+        return rc
+
+    def get_track_outcome(self, instance=0):
+        o = TrackOutcome()
+        self._chk(self.L.rrtx_get_track_outcome(self._h, instance, C.byref(o)), "rrtx_get_track_outcome")
+        return {k: int(getattr(o, k)) for k, _ in TrackOutcome._fields_}
+
+    def get_track_arrays(self, instance=0):
+        """(x, y, yaw, v, t, a, d) of the instance's best feasible roll-out, or None when there is none."""
+        o = self.get_track_outcome(instance)
+        if not o["flag"]:
+            return None
+        n = o["len"]
+        arr = [np.zeros(n + 1) for _ in range(7)]
+        self._chk(self.L.rrtx_get_track_arrays(self._h, instance, *[q.ctypes.data for q in arr], n + 1), "rrtx_get_track_arrays")
+        return tuple(q if k < 3 else q[:n] for k, q in enumerate(arr))
+
+    def get_track_records(self, instance=0):
+        """(candidate node indices, records as a TRACK_RECORD array), in candidate order."""
+        n = self.get_track_outcome(instance)["n_cand"]
+        cand = np.zeros(n, dtype=np.int32)
+        rec = np.zeros(n, dtype=TRACK_RECORD)
+        if n:
+            self._chk(self.L.rrtx_get_track_records(self._h, instance, cand.ctypes.data, rec.ctypes.data, n), "rrtx_get_track_records")
+        return cand, rec
+
+    def get_track_stats(self):
+        ms, st = C.c_double(), C.c_int64()
+        self._chk(self.L.rrtx_get_track_stats(self._h, C.byref(ms), C.byref(st)), "rrtx_get_track_stats")
+        return dict(kernel_ms=ms.value, steps=st.value)
 
     def get_sobol_index(self, instance=0):
         v = C.c_int64()

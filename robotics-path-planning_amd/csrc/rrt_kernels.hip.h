@@ -1503,6 +1503,8 @@ __global__ void selftest_kernel(int op, const double* a, const double* b, double
       rpp::rs_plan(0.0, 0.0, 0.0, a[i], b[i], a[i] + b[i], 1.0, 0.2, px, py, pyaw, 256, &R);
       r = (R.err || R.n == 0 || R.n > 256) ? (double)R.err - 1000.0 * R.n : px[R.n - 1] + py[R.n / 2] + pyaw[R.n - 1] + R.len[0];
     } break;
+    case 11: r = rpp_glibc_tan(a[i]); break;
+    case 12: r = rpp_glibc_hypot(a[i], b[i]); break;
   }
   o[i] = r;
 }

@@ -486,7 +486,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
       double min_cost = rpp::dinf();
       int min_ind = -1, npt = 0;
       s_ref += k;
-      if (da.eager) {
+      if (da.eager || da.rs_cost) {
         for (int p = 0; p < k; p++) {
           const int i = near[p];
           int cl = 0;
@@ -496,7 +496,8 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
           s_e += tk ? 1 : 0;
           s_pts += tk ? npt : 0;
           if (tk && !cl) {
-            const double cc = cost[i] + rpp::py_hypot(nx - x[i], ny - y[i]);   // Euclidean :1901-1903
+            // Euclidean :1901-1903; rrt_10: the Reeds-Shepp length of this very edge (calc_new_cost, rrt_10:1153-1161)
+            const double cc = da.rs_cost ? cost[i] + sh.cost_len : cost[i] + rpp::py_hypot(nx - x[i], ny - y[i]);
             if (cc < min_cost) {
               min_cost = cc;
               min_ind = i;
@@ -545,7 +546,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
           stop = 1;
           break;
         }
-        if (da.eager) {
+        if (da.eager || da.rs_cost) {
           // the re-steer of :1810 (not collision-checked again); in the lazy order the winner is the edge just laid out
           int cl = 0;
           const int bk = rs_edge(da, m, sh, x[min_ind], y[min_ind], yaw[min_ind], nx, ny, nyaw, pool_x + pool_used,
@@ -560,7 +561,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
         // visit; a missing or colliding edge changes nothing, :1877-1878 / :1890)
         s_ref += k;
         for (int p = 0; p < k; p++) {
-          if (!da.eager) {
+          if (!da.eager && !da.rs_cost) {
             // next list position whose node would get cheaper; costs are re-read after every rewire
             int q = p;
             for (;;) {
@@ -589,7 +590,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
           s_e += ek ? 1 : 0;
           s_pts += ek ? rn : 0;
           if (!ek) continue;
-          const double ec = cost[me] + rpp::py_hypot(x[i] - x[me], y[i] - y[me]);
+          const double ec = da.rs_cost ? cost[me] + sh.cost_len : cost[me] + rpp::py_hypot(x[i] - x[me], y[i] - y[me]);
           if (!rc2 && cost[i] > ec) {
             __syncthreads();
             if (lane == 0) {
@@ -609,24 +610,64 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
             __syncthreads();
             if (lane == 0) mark[i] = 1;
             __syncthreads();
-            for (int lvl = 1;; lvl++) {
-              int any = 0;
-              for (int j = lane; j < n; j += TPB) {
-                const int pj = parent[j];
-                if (pj >= 0 && mark[pj] == lvl) {
-                  cost[j] = cost[pj] + rpp::py_hypot(x[j] - x[pj], y[j] - y[pj]);
-                  mark[j] = lvl + 1;
-                  any++;
+            if (da.rs_cost) {
+              for (int lvl = 1;; lvl++) {
+                // rrt_10: calc_new_cost plans the Reeds-Shepp path parent -> child again (rrt_10:572-577 with :1153-1161):
+                // one cooperative edge per child, the children of a level in index order; no path -> inf
+                int cnt = 0;
+                for (int base = 0; base < n && !stop; base += TPB) {
+                  const int j = base + lane;
+                  bool ch = false;
+                  if (j < n) {
+                    const int pj = parent[j];
+                    ch = pj >= 0 && mark[pj] == lvl;
+                  }
+                  unsigned long long bm = __ballot(ch);
+                  while (bm) {
+                    const int jj = base + __ffsll((long long)bm) - 1;
+                    bm &= bm - 1ULL;
+                    const int pj = parent[jj];
+                    int pc = 0, pn = 0;
+                    const int pk = rs_edge(da, 0, sh, x[pj], y[pj], yaw[pj], x[jj], y[jj], yaw[jj], pool_x + pool_used,
+                                           pool_y + pool_used, pool_w + pool_used, da.pool_cap - pool_used, &pc, &pn);
+                    if (fatal(pk)) break;
+                    const double nc = pk ? cost[pj] + sh.cost_len : rpp::dinf();
+                    __syncthreads();
+                    if (lane == 0) {
+                      cost[jj] = nc;
+                      mark[jj] = lvl + 1;
+                    }
+                    __syncthreads();
+                    cnt++;
+                  }
+                }
+                s_pr += cnt;
+                if (!cnt || stop) break;
+                if (lvl > n) {
+                  stop = 1;
+                  break;
                 }
               }
-              const int tot = __popcll(__ballot(any != 0));
-              for (int o = 32; o >= 1; o >>= 1) any += __shfl_xor(any, o);
-              s_pr += any;
-              __syncthreads();
-              if (!tot) break;
-              if (lvl > n) {   // cannot happen on a tree (the reference would recurse for ever); never spin on the device
-                stop = 1;
-                break;
+            } else {
+              for (int lvl = 1;; lvl++) {
+                int any = 0;
+                for (int j = lane; j < n; j += TPB) {
+                  const int pj = parent[j];
+                  if (pj >= 0 && mark[pj] == lvl) {
+                    cost[j] = cost[pj] + rpp::py_hypot(x[j] - x[pj], y[j] - y[pj]);
+                    mark[j] = lvl + 1;
+                    any++;
+                  }
+                }
+                const int tot = __popcll(__ballot(any != 0));
+                for (int o = 32; o >= 1; o >>= 1) any += __shfl_xor(any, o);
+                s_pr += any;
+                __syncthreads();
+                if (!tot) break;
+                if (lvl > n) {   // cannot happen on a tree (the reference would recurse for ever); never spin on the device
+                  stop = 1;
+                  break;
+                }
               }
             }
             RS_M(11);

@@ -1,0 +1,274 @@
+// rrt_track.hip.h -- closed-loop stage of closed-loop RRT* (rrt_10) on planned Reeds-Shepp trees (gfx950).
+// Reference: /root/reference/src_path_planning/10_path_planning_01_rrt_10_closed_loop_rrt_star.py (rrt_10)
+//   ClosedLoopRRTStar.planning :1478-1493, search_best_feasible_path :1495-1524, check_tracking_path_is_feasible
+//   :1526-1564, get_goal_indexes :1566-1582; the scalar pieces are csrc/rpp_track.h.
+//
+// Three kernels on the trees the planner kernel left on the device (nothing is copied to the host in between):
+//   track_list_kernel  one wave per instance: the get_goal_indexes nodes in index order (ballot compaction), appended
+//                      as (instance, candidate) jobs to one device-wide job list;
+//   track_roll_kernel  persistent waves that take jobs from the list with an atomic counter (roll-outs differ by 10x in
+//                      length: ~200 steps when the goal is reached, 2 001 on a time-out).  A job walks the parents and
+//                      lays the course out (generate_final_course :1199-1207 reversed, then extend_path), sets the
+//                      speed profile and rolls the unicycle along it.  Per step the lanes share the np.hypot scan of
+//                      the course (first minimum, lowest index), the look-ahead walk and the state update are
+//                      wave-uniform (every lane computes them), and lane k tests the new point against obstacle k, so
+//                      check_collision is a running flag of the roll-out.  It records {find_goal, len(t), t[-1], failed
+//                      tests} per candidate;
+//   track_pick_kernel  one thread per instance: the feasible candidate with the smallest t[-1], the later one on ties.
+// A second launch of track_roll_kernel (store = 1) re-runs each winner alone and stores its seven arrays: the
+// roll-out is deterministic, so this costs one extra roll-out per instance instead of 2 002 x 7 doubles per candidate.
+//
+// Capacities: a course (with its extension) of up to LDS_PTS points is held in LDS (x, y; the speed profile always is, one
+// byte per point), up to SLAB_PTS points in the wave's global slab; a longer one sets RRTX_ST_OVERFLOW for the instance.
+// Obstacles: at most 64 per instance (the Reeds-Shepp planner's limit).
+#pragma once
+#include "rpp_track.h"
+#include "rrt_rs.hip.h"
+
+namespace rppt {
+
+constexpr int TPB = 64;
+constexpr int LDS_PTS = 512;
+constexpr int SLAB_PTS = 1024;
+constexpr int MAX_STEPS = 1 << 22;   // never spin on the device whatever T / dt is
+constexpr int ST_OVERFLOW = 4, ST_RAISES = 32, ST_OOD = 16;   // include/rrtx.h status bits (OOD reported as UNSUPPORTED)
+
+struct Outcome {      // per instance
+  int32_t flag;       // search_best_feasible_path found a feasible roll-out
+  int32_t winner;     // its position in the candidate list (-1 none)
+  int32_t n_cand;
+  int32_t len;        // len(t) of the winner (x / y / yaw hold len + 1 values: the goal pose is appended, :1519-1521)
+  int32_t node;       // the winner's node index
+  int32_t status;     // 0, or RRTX_ST_OVERFLOW / RRTX_ST_REF_RAISES / RRTX_ST_UNSUPPORTED bits
+};
+
+struct TrackArgs {
+  const rppk::Inst* inst;
+  const double *x, *y, *yaw;
+  const int32_t* parent;
+  const int64_t* poff;
+  const int32_t* plen;
+  int64_t stride;
+  const double* const* pool;   // [inst][3]: this instance's polyline pool (x, y, yaw)
+  const double *ox, *oy, *othr;
+  Params P;
+  int32_t n_inst;
+  int32_t* cand;       // [inst][stride]
+  Record* rec;         // [inst][stride]
+  int32_t* jobs;       // [2 * job]: instance, candidate position
+  int32_t* counters;   // 0: jobs listed, 1: queue head
+  double* slab;        // [block][3][SLAB_PTS]
+  Outcome* outc;       // [inst]
+  double* out;         // winners' arrays: instance i owns 7 x (len + 1) doubles at out_off[i]
+  const int64_t* out_off;
+};
+
+__global__ __launch_bounds__(TPB) void track_list_kernel(TrackArgs a) {
+  const int inst = blockIdx.x, lane = threadIdx.x;
+  const rppk::Inst* I = a.inst + inst;
+  const int64_t off = (int64_t)inst * a.stride;
+  const int n = (I->status & (ST_OVERFLOW | ST_RAISES | ST_OOD)) ? 0 : I->n;   // a tree that did not finish has no candidates
+  const double gx = I->goal[0], gy = I->goal[1], gyaw = I->goal[2];
+  int k = 0;
+  for (int base = 0; base < n; base += TPB) {
+    const int i = base + lane;
+    const bool c = i < n && is_candidate(a.x[off + i], a.y[off + i], a.yaw[off + i], gx, gy, gyaw, a.P);
+    const unsigned long long b = __ballot(c);
+    if (c) a.cand[off + k + __popcll(b & ((1ULL << lane) - 1ULL))] = i;
+    k += __popcll(b);
+  }
+  int jb = 0;
+  if (lane == 0) {
+    jb = atomicAdd(a.counters, k);
+    Outcome o = {0, -1, k, 0, -1, 0};
+    a.outc[inst] = o;
+  }
+  jb = __shfl(jb, 0);
+  for (int q = lane; q < k; q += TPB) {
+    a.jobs[2 * (jb + q)] = inst;
+    a.jobs[2 * (jb + q) + 1] = q;
+  }
+}
+
+__global__ void track_pick_kernel(TrackArgs a) {
+  const int inst = blockIdx.x * blockDim.x + threadIdx.x;
+  if (inst >= a.n_inst) return;
+  const int64_t off = (int64_t)inst * a.stride;
+  Outcome o = a.outc[inst];
+  double best_time = rpp::dinf();
+  for (int k = 0; k < o.n_cand; k++) {
+    const Record r = a.rec[off + k];
+    if (r.ood == 1) o.status |= ST_OOD;
+    if (r.ood == 2) o.status |= ST_RAISES;
+    if (r.ood == 3) o.status |= ST_OVERFLOW;
+    if (better(r.find, r.tlast, best_time)) {   // :1510
+      best_time = r.tlast;
+      o.winner = k;
+      o.len = r.n;
+      o.node = a.cand[off + k];
+    }
+  }
+  if (o.status) {   // never a wrong answer: an instance with a refused candidate reports no winner
+    o.winner = -1;
+    o.len = 0;
+    o.node = -1;
+  }
+  o.flag = o.winner >= 0;
+  a.outc[inst] = o;
+  if (o.flag) {
+    const int j = atomicAdd(a.counters + 2, 1);
+    a.jobs[2 * j] = inst;
+    a.jobs[2 * j + 1] = o.winner;
+  }
+}
+
+// store = 0: jobs are (instance, candidate), counters[0] of them, records written; store = 1: jobs are the winners
+// (counters[2] of them), arrays written
+__global__ __launch_bounds__(TPB) void track_roll_kernel(TrackArgs a, int store) {
+  __shared__ double lcx[LDS_PTS], lcy[LDS_PTS];
+  __shared__ signed char lsp[SLAB_PTS];
+  __shared__ int32_t s_job, s_n;
+  const int lane = threadIdx.x;
+  const Params P = a.P;
+  const int total_jobs = store ? a.counters[2] : a.counters[0];
+  double* gcx = a.slab + (int64_t)blockIdx.x * 3 * SLAB_PTS;
+  double* gcy = gcx + SLAB_PTS;
+  double* gcw = gcy + SLAB_PTS;
+  for (;;) {
+    __syncthreads();
+    if (lane == 0) s_job = atomicAdd(a.counters + 1, 1);
+    __syncthreads();
+    const int job = s_job;
+    if (job >= total_jobs) break;
+    const int inst = a.jobs[2 * job], k = a.jobs[2 * job + 1];
+    const int64_t off = (int64_t)inst * a.stride;
+    const rppk::Inst* I = a.inst + inst;
+    const int node = a.cand[off + k];
+    Record r = {0, 0, 0, 0, 0.0};
+    // ---- the course in driving order: start, the polylines root -> candidate, goal (generate_final_course reversed)
+    int total = 2, depth = 0;
+    for (int nd = node; a.parent[off + nd] >= 0 && depth <= (int)a.stride; nd = a.parent[off + nd], depth++) total += a.plen[off + nd];
+    if (total + EXT_MAX > SLAB_PTS || depth > (int)a.stride) r.ood = 3;
+    if (total < 3) r.ood = 2;   // cy[-3] :1435 raises IndexError
+    int n = total;
+    double *cx = gcx, *cy = gcy;
+    if (!r.ood) {
+      if (total + EXT_MAX <= LDS_PTS) {
+        cx = lcx;
+        cy = lcy;
+      }
+      const double* px = a.pool[3 * inst];
+      const double* py = a.pool[3 * inst + 1];
+      const double* pw = a.pool[3 * inst + 2];
+      int end = total - 1;
+      for (int nd = node; a.parent[off + nd] >= 0; nd = a.parent[off + nd]) {
+        const int pl = a.plen[off + nd];
+        const int64_t po = a.poff[off + nd];
+        end -= pl;
+        for (int q = lane; q < pl; q += TPB) {
+          cx[end + q] = px[po + q];
+          cy[end + q] = py[po + q];
+          gcw[end + q] = pw[po + q];
+        }
+      }
+      if (lane == 0) {
+        cx[0] = I->start[0];
+        cy[0] = I->start[1];
+        gcw[0] = I->start[2];
+        cx[total - 1] = I->goal[0];
+        cy[total - 1] = I->goal[1];
+        gcw[total - 1] = I->goal[2];
+      }
+      __syncthreads();
+      if (lane == 0) s_n = extend_path(cx, cy, gcw, total, P);
+      __syncthreads();
+      n = s_n;
+      if (n < 0) r.ood = 1;
+    }
+    if (!r.ood) {
+      for (int i = lane; i < n - 1; i += TPB) lsp[i] = (signed char)segment_flags(cx, cy, gcw, i);
+      __syncthreads();
+      if (lane == 0) stop_points(lsp, n);
+      __syncthreads();
+      // ---- closed_loop_prediction :1307-1372
+      const double gx = I->goal[0], gy = I->goal[1], gyaw = I->goal[2];
+      const int m = I->obs_m;
+      double obx = 0.0, oby = 0.0, obt = -1.0;
+      if (lane < m) {
+        obx = a.ox[I->obs_base + lane];
+        oby = a.oy[I->obs_base + lane];
+        obt = a.othr[I->obs_base + lane];
+      }
+      double* o7 = nullptr;
+      int ocap = 0;
+      if (store) {
+        ocap = a.outc[inst].len;
+        o7 = a.out + a.out_off[inst];
+      }
+      const int64_t os = (int64_t)ocap + 1;
+      State s = {-0.0, -0.0, 0.0, 0.0};
+      double time = 0.0, vsum = 0.0, last_yaw = 0.0, tlast = 0.0;
+      int cnt = 0, hit = 0, ood = 0, reached = 0;
+      auto append = [&](double ai, double di) {
+        if (o7 && lane == 0 && cnt < ocap) {
+          o7[cnt] = s.x;
+          o7[os + cnt] = s.y;
+          o7[2 * os + cnt] = rpp::angle_mod_pi(s.yaw);   // :1540
+          o7[3 * os + cnt] = s.v;
+          o7[4 * os + cnt] = time;
+          o7[5 * os + cnt] = ai;
+          o7[6 * os + cnt] = di;
+        }
+        if (lane < m) {
+          const double dx = obx - s.x, dy = oby - s.y;
+          if (dx * dx + dy * dy <= obt) hit = 1;
+        }
+        vsum = vsum + rpp::dabs(s.v);
+        last_yaw = s.yaw;
+        tlast = time;
+        cnt++;
+      };
+      // calc_target_index :1286-1293: the lanes share the np.hypot scan; first minimum, lowest index
+      auto scan = [&](double* dis) {
+        double best = rpp::dinf();
+        int bi = 0x7fffffff;
+        for (int i = lane; i < n; i += TPB) {
+          const double d = rpp_glibc_hypot(s.x - cx[i], s.y - cy[i]);
+          if (d < best) {
+            best = d;
+            bi = i;
+          }
+        }
+        rppr::wave_argmin(best, bi);
+        *dis = best;
+        return bi == 0x7fffffff ? 0 : bi;
+      };
+      append(0.0, 0.0);
+      double dis;
+      int target_ind = lookahead(cx, cy, n, scan(&dis), P.Lf);
+      while (P.T >= time && cnt < MAX_STEPS) {
+        const int ind0 = scan(&dis);
+        double ai, di;
+        if (step(s, target_ind, time, cx, cy, lsp, n, ind0, dis, gx, gy, P, &ai, &di, &ood)) {
+          reached = 1;
+          break;
+        }
+        append(ai, di);
+        if (ood) break;
+      }
+      r.n = cnt;
+      r.tlast = tlast;
+      r.ood = ood ? 1 : 0;
+      const int any_hit = __ballot(hit) != 0ULL;
+      judge(&r, reached, rpp::angle_mod_pi(last_yaw), gyaw, vsum, origin_travel(cx, cy, n), any_hit, P);
+      if (o7 && lane == 0 && r.find && cnt == ocap) {   // :1519-1521: the goal pose behind x, y, yaw only
+        o7[cnt] = gx;
+        o7[os + cnt] = gy;
+        o7[2 * os + cnt] = gyaw;
+      }
+    }
+    if (!store && lane == 0) a.rec[off + k] = r;
+  }
+}
+
+}  // namespace rppt

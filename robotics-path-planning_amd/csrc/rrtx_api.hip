@@ -27,6 +27,7 @@
 #include "rrt_bitstar_wave.hip.h"
 #include "path_smooth.hip.h"
 #include "rrt_lqr.hip.h"
+#include "rrt_track.hip.h"
 
 using rppk::Ctx;
 using rppk::Inst;
@@ -165,6 +166,22 @@ struct rrtx_handle {
   int32_t* sm_obs = nullptr;  // [inst][2]: the rows (base, count) each path is smoothed against
   int64_t sm_stride = 0;
   bool smoothed = false;
+  int rs_cost = 0;            // RRTX_ALGO_RS: RRTX_RS_COST_* of the next plan (rrtx_set_rs_cost)
+  // closed-loop stage on the planned trees (rrtx_track_planned, rrt_track.hip.h)
+  struct Track {
+    int32_t *cand = nullptr, *jobs = nullptr, *counters = nullptr;
+    rppt::Record* rec = nullptr;
+    rppt::Outcome* outc = nullptr;
+    const double** pool = nullptr;
+    double *slab = nullptr, *out = nullptr;
+    int64_t* out_off = nullptr;
+    int64_t out_cap = 0;
+    int blocks = 0;
+    bool valid = false;
+    std::vector<rppt::Outcome> h_outc;
+    std::vector<int64_t> h_off;
+    double ms = 0.0;
+  } tk;
 };
 
 #define HIPCHK(h, expr)                                                                      \
@@ -313,6 +330,7 @@ void rrtx_destroy(rrtx_handle* h) {
   }
   for (void* q : h->allocs) hipFree(q);
   if (h->obs_buf) hipFree(h->obs_buf);
+  if (h->tk.out) hipFree(h->tk.out);
   for (auto& bp : h->big) {
     if (bp.px) hipFree(bp.px);
     if (bp.py) hipFree(bp.py);
@@ -778,6 +796,7 @@ int rrtx_plan_begin(rrtx_handle* h) {
   R.t0 = std::chrono::steady_clock::now();
   h->planned = false;
   h->smoothed = false;     // rrtx_get_smoothed_path: the previous plan's smoothed paths are not this plan's
+  h->tk.valid = false;     // the same for the tracked trajectories
   h->traced_inst = -1;     // rrtx_get_trace: nothing recorded until this plan completes
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipDeviceSynchronize());   // uploads made through the null stream (obstacles, tables) are complete
@@ -940,6 +959,7 @@ int rrtx_plan_begin(rrtx_handle* h) {
     h->da.pool_slot = nullptr;
   }
   if (const char* e = getenv("RRTX_RS_EAGER")) h->da.eager = atoi(e) != 0;
+  h->da.rs_cost = h->rs_cost;
   if (const char* e = getenv("RRTX_INFORMED_EAGER")) h->informed_eager = atoi(e) != 0;   // rrt_07: test every near candidate like the reference
   if (const char* e = getenv("RRTX_INFORMED_EXACT_SEG"))   // rrt_07 test knob: no tolerance bands -- every verdict from the exact segment form, every candidate list from the exact **2 form
     h->informed_eager = (h->informed_eager & 1) | (atoi(e) != 0 ? 6 : 0);
@@ -1735,6 +1755,183 @@ int rrtx_get_smoothed_path(rrtx_handle* h, int32_t instance, double* xy, int32_t
   if (!xy || n == 0) return RRTX_OK;
   if (cap_points < n) return RRTX_E_CAPACITY;
   HIPCHK(h, hipMemcpy(xy, h->sm_xy + (size_t)2 * h->sm_stride * instance, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+// ---- closed-loop stage of rrt_10 on the planned Reeds-Shepp trees (rrt_track.hip.h) ----------------------------------
+int rrtx_set_rs_cost(rrtx_handle* h, int32_t mode) {
+  if (!h || (mode != RRTX_RS_COST_EUCLID && mode != RRTX_RS_COST_PATH)) return RRTX_E_INVALID;
+  if (h->p.algo != RRTX_ALGO_RS) return RRTX_E_STATE;
+  int rc = refuse_in_plan(h, "rrtx_set_rs_cost");
+  if (rc) return rc;
+  h->rs_cost = mode;
+  return RRTX_OK;
+}
+
+int rrtx_track_planned(rrtx_handle* h, const rrtx_track_params* tp) {
+  if (!h || !tp) return RRTX_E_INVALID;
+  if (!h->planned || h->p.algo != RRTX_ALGO_RS) return RRTX_E_STATE;
+  int rc = refuse_in_plan(h, "rrtx_track_planned");
+  if (rc) return rc;
+  if (!(tp->dt > 0.0) || !(tp->T >= 0.0) || !(tp->T / tp->dt <= 1.0e6) || !(tp->Lf > 0.0) || !(tp->L > 0.0) ||
+      !(tp->steer_max >= 0.0 && tp->steer_max <= 0.79)) {
+    h->err = "rrtx_track_planned: needs dt > 0, T / dt <= 1e6, Lf > 0, L > 0, 0 <= steer_max <= 0.79";
+    return RRTX_E_INVALID;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  rrtx_handle::Track& K = h->tk;
+  const int B = h->n_inst;
+  const size_t tot = (size_t)h->stride * B;
+  K.valid = false;
+  if (!K.cand) {
+    const int64_t want = (int64_t)h->n_cu * 16;
+    K.blocks = (int)((int64_t)tot < want ? (int64_t)tot : want);
+    if (K.blocks < 1) K.blocks = 1;
+    if ((rc = dalloc(h, &K.cand, tot))) return rc;
+    if ((rc = dalloc(h, &K.rec, tot))) return rc;
+    if ((rc = dalloc(h, &K.jobs, 2 * tot))) return rc;
+    if ((rc = dalloc(h, &K.counters, 4))) return rc;
+    if ((rc = dalloc(h, &K.outc, B))) return rc;
+    if ((rc = dalloc(h, &K.pool, (size_t)3 * B))) return rc;
+    if ((rc = dalloc(h, &K.out_off, B))) return rc;
+    if ((rc = dalloc(h, &K.slab, (size_t)K.blocks * 3 * rppt::SLAB_PTS))) return rc;
+  }
+  std::vector<const double*> pp((size_t)3 * B);
+  for (int i = 0; i < B; i++) {
+    const rrtx_handle::PoolLoc& pl = h->pool_loc[i];
+    pp[3 * i] = pl.px + pl.slab * pl.cap;
+    pp[3 * i + 1] = pl.py + pl.slab * pl.cap;
+    pp[3 * i + 2] = pl.pyaw + pl.slab * pl.cap;
+  }
+  HIPCHK(h, hipMemcpyAsync(K.pool, pp.data(), sizeof(double*) * pp.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemsetAsync(K.counters, 0, sizeof(int32_t) * 4, h->stream));
+  rppt::TrackArgs a;
+  memset(&a, 0, sizeof(a));
+  a.inst = h->c.inst;
+  a.x = h->c.x;
+  a.y = h->c.y;
+  a.yaw = h->da.yaw;
+  a.parent = h->c.parent;
+  a.poff = h->da.poff;
+  a.plen = h->da.plen;
+  a.stride = h->stride;
+  a.pool = K.pool;
+  a.ox = h->c.ox;
+  a.oy = h->c.oy;
+  a.othr = h->c.othr;
+  static_assert(sizeof(rppt::Params) == sizeof(rrtx_track_params), "rrtx_track_params mirrors rppt::Params");
+  static_assert(sizeof(rppt::Outcome) == sizeof(rrtx_track_outcome), "rrtx_track_outcome mirrors rppt::Outcome");
+  static_assert(sizeof(rppt::Record) == sizeof(rrtx_track_record), "rrtx_track_record mirrors rppt::Record");
+  memcpy(&a.P, tp, sizeof(a.P));
+  a.n_inst = B;
+  a.cand = K.cand;
+  a.rec = K.rec;
+  a.jobs = K.jobs;
+  a.counters = K.counters;
+  a.slab = K.slab;
+  a.outc = K.outc;
+  a.out_off = K.out_off;
+  K.h_outc.resize(B);
+  K.h_off.assign(B, 0);
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  hipLaunchKernelGGL(rppt::track_list_kernel, dim3(B), dim3(rppt::TPB), 0, h->stream, a);
+  hipLaunchKernelGGL(rppt::track_roll_kernel, dim3(K.blocks), dim3(rppt::TPB), 0, h->stream, a, 0);
+  hipLaunchKernelGGL(rppt::track_pick_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  HIPCHK(h, hipMemcpyAsync(K.h_outc.data(), K.outc, sizeof(rppt::Outcome) * B, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  K.ms = ms;
+  // the winners' arrays: 7 x (len + 1) doubles per instance with a feasible roll-out, packed
+  int64_t need = 0;
+  int winners = 0;
+  for (int i = 0; i < B; i++) {
+    K.h_off[i] = need;
+    if (K.h_outc[i].flag) {
+      need += 7 * ((int64_t)K.h_outc[i].len + 1);
+      winners++;
+    }
+  }
+  // K.out is the one tracking buffer whose size depends on the plan (the winners' lengths), so it is the only one that is
+  // regrown and hence not on the handle's `allocs` list: rrtx_destroy frees it by name.
+  if (need > K.out_cap) {
+    if (K.out) hipFree(K.out);
+    K.out = nullptr;
+    K.out_cap = 0;
+    void* q = nullptr;
+    HIPCHK(h, hipMalloc(&q, sizeof(double) * (size_t)need));
+    K.out = (double*)q;
+    K.out_cap = need;
+  }
+  if (winners) {
+    a.out = K.out;
+    HIPCHK(h, hipMemcpyAsync(K.out_off, K.h_off.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(K.counters + 1, 0, sizeof(int32_t), h->stream));
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(rppt::track_roll_kernel, dim3(winners < K.blocks ? winners : K.blocks), dim3(rppt::TPB), 0, h->stream, a, 1);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    K.ms += ms;
+  }
+  K.valid = true;
+  for (int i = 0; i < B; i++)
+    if (K.h_outc[i].status) return RRTX_PARTIAL;
+  return RRTX_OK;
+}
+
+int rrtx_get_track_outcome(rrtx_handle* h, int32_t instance, rrtx_track_outcome* out) {
+  if (!h || !out || instance < 0 || instance >= h->n_inst) return RRTX_E_INVALID;
+  if (!h->planned || !h->tk.valid) return RRTX_E_STATE;
+  memcpy(out, &h->tk.h_outc[instance], sizeof(*out));
+  return RRTX_OK;
+}
+
+int rrtx_get_track_arrays(rrtx_handle* h, int32_t instance, double* x, double* y, double* yaw, double* v, double* t,
+                          double* a, double* d, int32_t cap) {
+  if (!h || instance < 0 || instance >= h->n_inst || !x || !y || !yaw || !v || !t || !a || !d) return RRTX_E_INVALID;
+  if (!h->planned || !h->tk.valid) return RRTX_E_STATE;
+  const rppt::Outcome& o = h->tk.h_outc[instance];
+  if (!o.flag) return RRTX_E_STATE;
+  if (cap < o.len + 1) return RRTX_E_CAPACITY;
+  HIPCHK(h, hipSetDevice(h->device));
+  const int64_t os = (int64_t)o.len + 1;
+  std::vector<double> buf((size_t)(7 * os));
+  HIPCHK(h, hipMemcpy(buf.data(), h->tk.out + h->tk.h_off[instance], sizeof(double) * buf.size(), hipMemcpyDeviceToHost));
+  double* dst[7] = {x, y, yaw, v, t, a, d};
+  for (int k = 0; k < 7; k++) memcpy(dst[k], buf.data() + k * os, sizeof(double) * (size_t)(k < 3 ? os : os - 1));
+  return RRTX_OK;
+}
+
+int rrtx_get_track_records(rrtx_handle* h, int32_t instance, int32_t* cand, rrtx_track_record* rec, int32_t cap) {
+  if (!h || instance < 0 || instance >= h->n_inst || !cand || !rec) return RRTX_E_INVALID;
+  if (!h->planned || !h->tk.valid) return RRTX_E_STATE;
+  const int n = h->tk.h_outc[instance].n_cand;
+  if (cap < n) return RRTX_E_CAPACITY;
+  if (!n) return RRTX_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const int64_t off = (int64_t)instance * h->stride;
+  HIPCHK(h, hipMemcpy(cand, h->tk.cand + off, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(rec, h->tk.rec + off, sizeof(rrtx_track_record) * n, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps) {
+  if (!h || !kernel_ms || !steps) return RRTX_E_INVALID;
+  if (!h->planned || !h->tk.valid) return RRTX_E_STATE;
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<rppt::Record> rec((size_t)h->stride * h->n_inst);
+  HIPCHK(h, hipMemcpy(rec.data(), h->tk.rec, sizeof(rppt::Record) * rec.size(), hipMemcpyDeviceToHost));
+  int64_t s = 0;
+  for (int i = 0; i < h->n_inst; i++) {
+    for (int k = 0; k < h->tk.h_outc[i].n_cand; k++) s += rec[(size_t)i * h->stride + k].n;
+    if (h->tk.h_outc[i].flag) s += h->tk.h_outc[i].len;
+  }
+  *kernel_ms = h->tk.ms;
+  *steps = s;
   return RRTX_OK;
 }
 

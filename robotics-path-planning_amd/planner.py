@@ -557,6 +557,77 @@ class RRTStarReedsShepp(RRTStarDubins):
         self.path_yaw = h.get_path_yaw(0)
 
 
+class ClosedLoopRRTStar(RRTStarReedsShepp):
+    """Drop-in for rrt_10's `ClosedLoopRRTStar` (10_path_planning_01_rrt_10_closed_loop_rrt_star.py:1453-1582).
+
+    Tree phase: rrt_10's `RRTStarReedsShepp` (:1005-1207) on the Reeds-Shepp kernel -- always `get_random_node`, no
+    `expand_dis` (the near radius is not clamped, :522-531), curvature / goal thresholds fixed at 1.0 / 1 deg / 0.5, and
+    choose_parent / rewire / cost propagation with the Reeds-Shepp length of the edge (its calc_new_cost, :1153-1161).
+    Closed-loop stage (:1495-1582): every node within xy_th / yaw_th of the goal is tracked by the pure-pursuit / PID
+    unicycle on the device (csrc/rrt_track.hip.h) and the feasible roll-out with the smallest end time is returned.
+    `planning(animation=True)` returns `flag, x, y, yaw, v, t, a, d` as Python lists, or `(False, None, ...)`.  The model
+    constants are module globals in the reference (:1592-1607); here they are optional keywords with those defaults.
+    Consumes and leaves CPython's global `random` state exactly as the reference does.  `node_list` holds x, y, yaw,
+    cost, parent and path_x / path_y per node; `path_yaw` (which the reference's nodes also carry) is not read back."""
+
+    def __init__(self, start, goal, obstacle_list, rand_area, max_iter=200, connect_circle_dist=50.0, robot_radius=0.0,
+                 target_speed=10.0 / 3.6, yaw_th=np.deg2rad(3.0), xy_th=0.5, invalid_travel_ratio=5.0, dt=0.05, L=0.9,
+                 steer_max=np.deg2rad(40.0), accel_max=5.0, Kp=2.0, Lf=0.5, T=100.0, goal_dis=0.5, stop_speed=0.5,
+                 device=0):
+        super().__init__(start, goal, obstacle_list, rand_area, expand_dis=float("inf"), max_iter=max_iter,
+                         connect_circle_dist=connect_circle_dist, robot_radius=robot_radius, curvature=1.0,
+                         goal_yaw_th=float(np.deg2rad(1.0)), goal_xy_th=0.5, step_size=0.2, device=device)
+        del self.expand_dis    # rrt_10's class has no such attribute (:1020-1047)
+        self.target_speed = target_speed
+        self.yaw_th = yaw_th
+        self.xy_th = xy_th
+        self.invalid_travel_ratio = invalid_travel_ratio
+        self.model = dict(dt=dt, L=L, steer_max=steer_max, accel_max=accel_max, Kp=Kp, Lf=Lf, T=T, goal_dis=goal_dis,
+                          stop_speed=stop_speed)
+        self.candidates = None
+        self.records = None
+        self.outcome = None
+
+    def _make_handle(self, until_max=True):
+        h = _abi.Handle(_abi.ALGO_RS, [self.start.x, self.start.y, self.start.yaw],
+                        [self.end.x, self.end.y, self.end.yaw], [self.min_rand, self.max_rand], float("inf"), 0.5, 0,
+                        self.max_iter, robot_radius=self.robot_radius, connect_circle_dist=self.connect_circle_dist,
+                        search_until_max_iter=True, n_instances=1, device=self.device, curvature=1.0,
+                        goal_yaw_th=float(np.deg2rad(1.0)), goal_xy_th=0.5, step_size=self.step_size)
+        h.set_rs_cost(_abi.RS_COST_PATH)
+        return h
+
+    def _track_kwargs(self):
+        kw = dict(target_speed=self.target_speed, yaw_th=self.yaw_th, xy_th=self.xy_th,
+                  invalid_travel_ratio=self.invalid_travel_ratio)
+        kw.update(self.model)
+        return kw
+
+    def _after_plan(self, h):
+        self.path_yaw = h.get_path_yaw(0)
+        rc = h.track_planned(**self._track_kwargs())
+        self.outcome = h.get_track_outcome(0)
+        if rc == _abi.RRTX_PARTIAL:
+            raise _abi.RrtxError("ClosedLoopRRTStar: tracking stopped with status %d (4: a course beyond the device "
+                                 "capacity, 32: the reference raises here, 16: outside the arithmetic replicas' domain)"
+                                 % self.outcome["status"])
+        self.candidates, self.records = h.get_track_records(0)
+        self._arrays = h.get_track_arrays(0)
+
+    def planning(self, animation=True):
+        self._arrays = None
+        RRTStarDubins.planning(self, animation, True)
+        if self._arrays is None:
+            return False, None, None, None, None, None, None, None
+        x, y, yaw, v, t, a, d = ([float(q) for q in arr] for arr in self._arrays)
+        return True, x, y, yaw, v, t, a, d
+
+    plan = planning
+
+    def get_goal_indexes(self):
+        return [int(i) for i in self.candidates]
+
+
 class LQRNode:
     """LQRRRTStar.Node (rrt_09:1042-1051)."""
 
@@ -808,7 +879,9 @@ class BatchPlanner:
         sobol_sampler as in its constructor :1029-1042), "bitstar" (rrt_08: max_iter = maxIter, rand_area = randArea
         :140-168), and the pose planners (start / goal = [x, y, yaw]; curvature, goal thresholds and, for Reeds-Shepp,
         step_size as in their constructors): "rrt_dubins" (rrt_03), "rrt_star_dubins" (rrt_05),
-        "rrt_star_reeds_shepp" (rrt_06); "lqr_rrt_star" (rrt_09: step_size, goal_xy_th; `search_until_max_iter` plays
+        "rrt_star_reeds_shepp" (rrt_06); "closed_loop_rrt_star" (rrt_10: start / goal poses, max_iter,
+        connect_circle_dist, robot_radius as in its constructor :1458-1476; plan() grows the trees, track() runs the
+        closed-loop stage); "lqr_rrt_star" (rrt_09: step_size, goal_xy_th; `search_until_max_iter` plays
         the part of planning()'s keyword of the same name, :1120).
         `starts` / `goals`: per-instance [x, y] (pose planners: [x, y, yaw]; a missing yaw keeps `start[2]` /
         `goal[2]`).  For "informed" and "bitstar" the rotation to the world frame and c_min (rrt_07:1054-1068,
@@ -819,7 +892,14 @@ class BatchPlanner:
         from . import sharding
         a = {"rrt": _abi.ALGO_RRT, "rrt_star": _abi.ALGO_RRT_STAR, "rrt_dubins": _abi.ALGO_RRT_DUBINS,
              "rrt_star_dubins": _abi.ALGO_DUBINS, "rrt_star_reeds_shepp": _abi.ALGO_RS, "informed": _abi.ALGO_INFORMED,
-             "bitstar": _abi.ALGO_BITSTAR, "lqr_rrt_star": _abi.ALGO_LQR_RRT_STAR}[algo]
+             "bitstar": _abi.ALGO_BITSTAR, "lqr_rrt_star": _abi.ALGO_LQR_RRT_STAR,
+             "closed_loop_rrt_star": _abi.ALGO_RS}[algo]
+        # rrt_10: the Reeds-Shepp tree with its own cost rule and an unclamped near radius, then track() (closed-loop stage)
+        self.closed_loop = algo == "closed_loop_rrt_star"
+        if self.closed_loop:
+            expand_dis, search_until_max_iter, curvature = float("inf"), True, 1.0
+            goal_yaw_th, goal_xy_th, step_size = float(np.deg2rad(1.0)), 0.5, 0.2
+        self.tracked = False
         self.seeds = list(seeds)
         if a == _abi.ALGO_LQR_RRT_STAR:
             if not step_size > 0:
@@ -866,6 +946,8 @@ class BatchPlanner:
                                     n_instances=hi - lo, device=dev, curvature=curvature, goal_yaw_th=goal_yaw_th,
                                     goal_xy_th=goal_xy_th, step_size=step_size)
                 self.handles.append(h)
+                if self.closed_loop:
+                    h.set_rs_cost(_abi.RS_COST_PATH)
                 if instance_obstacles is None:
                     h.set_obstacles(obstacle_list)
                 else:
@@ -899,6 +981,7 @@ class BatchPlanner:
         capacity limit or where the reference would raise carries the bit in its status word (`failed()` lists
         them); the other instances are complete.  Raises only for errors of the call as a whole."""
         rcs = _abi.plan_many(self.handles)
+        self.tracked = False
         self.partial = any(r == _abi.RRTX_PARTIAL for r in rcs)
         return self.results()
 
@@ -955,6 +1038,48 @@ class BatchPlanner:
             h.smooth_planned(max_iter)
         return [self._loc(i)[0].get_smoothed_path(self._loc(i)[1]) for i in range(len(self.seeds))]
 
+    def track(self, **kw):
+        """"closed_loop_rrt_star" only, after plan(): the closed-loop stage of rrt_10 (:1495-1582) on every planned tree, on
+        the device.  Keywords: target_speed, yaw_th, xy_th, invalid_travel_ratio and the model constants (defaults: the
+        reference's, _abi.TRACK_DEFAULTS).  Returns the per-instance flags; see trajectory(i) / track_records(i)."""
+        if not self.closed_loop:
+            raise ValueError("BatchPlanner.track: only for algo=\"closed_loop_rrt_star\"")
+        if len(self.handles) == 1:
+            self.handles[0].track_planned(**kw)
+        else:   # one host thread per shard, as rrtx_plan_many does for the trees (the calls block on their own streams)
+            import threading
+            errs = []
+
+            def run(h):
+                try:
+                    h.track_planned(**kw)
+                except Exception as e:   # noqa: BLE001 -- re-raised below on the calling thread
+                    errs.append(e)
+            th = [threading.Thread(target=run, args=(h,)) for h in self.handles]
+            for t in th:
+                t.start()
+            for t in th:
+                t.join()
+            if errs:
+                raise errs[0]
+        self.tracked = True
+        return np.array([self._loc(i)[0].get_track_outcome(self._loc(i)[1])["flag"] for i in range(len(self.seeds))],
+                        dtype=bool)
+
+    def trajectory(self, i):
+        """(x, y, yaw, v, t, a, d) of instance i's best feasible roll-out (x, y, yaw one longer: the goal pose is
+        appended, rrt_10:1519-1521), or None where planning() returns (False, None, ...)."""
+        h, j = self._loc(i)
+        return h.get_track_arrays(j)
+
+    def track_outcome(self, i):
+        h, j = self._loc(i)
+        return h.get_track_outcome(j)
+
+    def track_records(self, i):
+        h, j = self._loc(i)
+        return h.get_track_records(j)
+
     def export_npz(self, filename, instances=None):
         """Compact on-disk form of the planned trees for plotting / regression diffs: per instance
         (x, y, cost, parent) as the reference's node_list holds them, the returned path, path cost, seed; with
@@ -969,6 +1094,11 @@ class BatchPlanner:
             p = h.get_path(j)
             out["x_%d" % k], out["y_%d" % k], out["cost_%d" % k], out["parent_%d" % k] = x, y, cost, parent
             out["path_%d" % k] = np.zeros((0, 2)) if p is None else p
+            if self.closed_loop and self.tracked:
+                tr = h.get_track_arrays(j)
+                out["track_flag_%d" % k] = np.array(tr is not None)
+                for name, arr in zip(("x", "y", "yaw", "v", "t", "a", "d"), tr if tr is not None else [np.zeros(0)] * 7):
+                    out["track_%s_%d" % (name, k)] = arr
             if self.instance_obstacles is not None:
                 out["obstacles_%d" % k] = np.array(self.instance_obstacles[i], dtype=np.float64).reshape(-1, 3)
         np.savez_compressed(filename, **out)

@@ -1,6 +1,6 @@
 """Importable alias of the `robotics-path-planning_amd` package (hyphenated directory name).
 
-Per-script drop-in modules: `rrt_amd.rrt_01` ... `rrt_amd.rrt_09` carry exactly the names the reference script of that
+Per-script drop-in modules: `rrt_amd.rrt_01` ... `rrt_amd.rrt_10` carry exactly the names the reference script of that
 number defines for its driver cell (`RRT`, `BITStar`, `Node`, `path_smoothing`, `get_path_length`), so a driver written
 against `10_path_planning_01_rrt_04_rrt_star.py` runs after `from rrt_amd.rrt_04 import *`."""
 import importlib
@@ -24,6 +24,7 @@ BITStar = _pkg.BITStar
 bitstar_rotation = _pkg.bitstar_rotation
 InformedRRTStar = _pkg.InformedRRTStar
 LQRRRTStar = _pkg.LQRRRTStar
+ClosedLoopRRTStar = _pkg.ClosedLoopRRTStar
 informed_rotation = _pkg.informed_rotation
 BatchPlanner = _pkg.BatchPlanner
 Node = _pkg.Node

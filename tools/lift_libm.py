@@ -26,7 +26,8 @@ save/restore (MXCSR) is dropped: callers run in round-to-nearest.
 Branches that leave the restated domain (huge-argument reduction `__branred`,
 overflow/underflow error exits of pow) return NaN and raise the `ood` flag.
 
-Output: one header with `static inline double rpp_glibc_{sin,cos,atan2,pow,acos,asin}`.
+Output: one header with `static inline double rpp_glibc_{sin,cos,atan2,pow,acos,asin,tan,hypot}`; like the others,
+`tan` and `hypot` are translations of the installed LGPL binary (see the header's provenance note).
 Verified against the live libm by tests/test_core_host.py::test_glibc_replicas_against_live_libm
 (tests/native/glibc_replica_check.c) and on the device by tests/test_gpu_parity.py::test_device_arithmetic_replicas.
 
@@ -47,6 +48,14 @@ FUNCS = [
     ("atan2", 0x78060, 0x789b0, 2),
     ("sin", 0x789b0, 0x791c0, 1),
     ("cos", 0x791c0, 0x799d0, 1),
+    # math.tan: `tan` is an ifunc (resolver at 0x2f280); with FMA and AVX2 usable it resolves to the variant at 0x799d0,
+    # the one CPython reaches next to __sin_fma / __cos_fma above.  Its only call (0x7a012, the huge-argument reduction)
+    # is an out-of-domain exit like the others.  The replica is stated for |x| <= 0.79 (the polynomial and table stages
+    # before any range reduction); rpp_glibc_tan raises the out-of-domain flag beyond that.
+    ("tan", 0x799d0, 0x7a250, 1),
+    # np.hypot: glibc's own `hypot` (hypot@@GLIBC_2.35, 0x3cc bytes, no ifunc: baseline SSE2, no FMA) -- NOT CPython's
+    # math.hypot, which is its own vector-norm routine (restated by hand in rpp_core.h: py_hypot).
+    ("hypot", 0x26210, 0x265dc, 2),
 ]
 EXPECT_SHA256 = None  # filled by --print-sha; checked when not None
 
@@ -307,6 +316,8 @@ class Lifter:
         if mn in ("addsd", "subsd", "mulsd", "divsd"):
             c = {"addsd": "+", "subsd": "-", "mulsd": "*", "divsd": "/"}[mn]
             return ["%s = B(%s %s %s);" % (dstx(), D(X(1)), c, D(X(0)))]
+        if mn in ("sqrtsd", "vsqrtsd"):
+            return ["%s = B(__builtin_sqrt(%s));" % (dstx(), D(X(0)))]
         if mn in ("addss", "subss", "mulss", "divss"):
             c = {"addss": "+", "subss": "-", "mulss": "*", "divss": "/"}[mn]
             return ["%s = (%s & ~0xffffffffULL) | BF(F(%s) %s F(%s));"
@@ -614,12 +625,14 @@ class Lifter:
                 body.append("  *ood = 1; return D(0x7ff8000000000000ULL); /* falls out of region */")
         text = "\n".join(body)
         args = "double a0" + (", double a1" if nargs == 2 else "")
-        pro = ["RPP_HD static RPP_LIBM_INLINE double rpp_glibc_%s_raw(%s, int *ood) {" % (name, args),
+        bias = 32 if name == "hypot" else 0   # red zone below %rsp
+        pro = ["#undef RPP_SB", "#define RPP_SB %d" % bias,
+               "RPP_HD static RPP_LIBM_INLINE double rpp_glibc_%s_raw(%s, int *ood) {" % (name, args),
                "  uint64_t rax=0,rbx=0,rcx=0,rdx=0,rsi=0,rdi=0,rbp=0,r8=0,r9=0,r10=0,r11=0,r12=0,r13=0,r14=0,r15=0;",
                "  uint64_t x0=B(a0),x1=%s,x2=0,x3=0,x4=0,x5=0,x6=0,x7=0,x8=0,x9=0,x10=0,x11=0,x12=0,x13=0,x14=0,x15=0;"
                % ("B(a1)" if nargs == 2 else "0"),
-               "  int zf=0,cf=0,sf=0,of=0,pf=0; uint32_t stk[32];",
-               "  for (int i_ = 0; i_ < 32; ++i_) stk[i_] = 0;",
+               "  int zf=0,cf=0,sf=0,of=0,pf=0; uint32_t stk[%d];" % (32 + bias // 4),
+               "  for (int i_ = 0; i_ < %d; ++i_) stk[i_] = 0;" % (32 + bias // 4),
                "  (void)rax;(void)rbx;(void)rcx;(void)rdx;(void)rsi;(void)rdi;(void)rbp;(void)r8;(void)r9;(void)r10;"
                "(void)r11;(void)r12;(void)r13;(void)r14;(void)r15;",
                "  (void)x1;(void)x2;(void)x3;(void)x4;(void)x5;(void)x6;(void)x7;(void)x8;(void)x9;(void)x10;(void)x11;"
@@ -635,8 +648,9 @@ HEADER = r"""// GENERATED by tools/lift_libm.py -- do not edit.
 // PROVENANCE AND LICENCE.  This file is machine-derived from the glibc BINARY installed in the build image
 // (/lib/x86_64-linux-gnu/libm.so.6, sha256 below; GNU C Library 2.35, Copyright (C) Free Software Foundation, Inc.,
 // licensed under the GNU Lesser General Public License v2.1 or later): tools/lift_libm.py walks the scalar-double
-// instruction stream of the x86-64 FMA ifunc variants of sin / cos / atan2 / pow / acos / asin (the entry points
-// CPython's math module reaches) and emits one C statement per instruction, and copies their lookup tables as data.  It is
+// instruction stream of the x86-64 FMA ifunc variants of sin / cos / atan2 / pow / acos / asin / tan (the entry points
+// CPython's math module reaches) and of the baseline `hypot` (what numpy's np.hypot calls), and emits one C statement per
+// instruction, and copies their lookup tables as data.  It is
 // therefore a translation of LGPL code and is distributed under the same terms (LGPL-2.1-or-later); it is NOT taken
 // from /root/reference, which contains no libm.  Regenerate with `python3 tools/lift_libm.py` on a host whose libm the
 // planners should reproduce.  The contract "doubles identical to the reference" holds on hosts whose libm returns
@@ -688,12 +702,13 @@ MACROS = r"""
 #define FCMP(a, b) do { double a_ = (a), b_ = (b); if (a_ != a_ || b_ != b_) { zf = 1; pf = 1; cf = 1; } \
   else if (a_ > b_) { zf = 0; pf = 0; cf = 0; } else if (a_ < b_) { zf = 0; pf = 0; cf = 1; } \
   else { zf = 1; pf = 0; cf = 0; } sf = 0; of = 0; } while (0)
-#define STK32(o) (stk[(o) >> 2])
-#define STK64(o) ((uint64_t)stk[(o) >> 2] | ((uint64_t)stk[((o) >> 2) + 1] << 32))
-#define SETSTK32(o, v) do { stk[(o) >> 2] = (uint32_t)(v); } while (0)
-#define SETSTK64(o, v) do { uint64_t v_ = (v); stk[(o) >> 2] = (uint32_t)v_; stk[((o) >> 2) + 1] = (uint32_t)(v_ >> 32); } while (0)
-#define SETSTK8(o, v) do { uint32_t s_ = ((o) & 3) * 8; stk[(o) >> 2] = (stk[(o) >> 2] & ~(0xffu << s_)) | ((uint32_t)(uint8_t)(v) << s_); } while (0)
-#define STK8(o) ((uint8_t)(stk[(o) >> 2] >> (((o) & 3) * 8)))
+// stack slots are biased by RPP_SB bytes (set per function): hypot keeps two values in the red zone below %rsp (-0x8(%rsp))
+#define STK32(o) (stk[((o) + RPP_SB) >> 2])
+#define STK64(o) ((uint64_t)stk[((o) + RPP_SB) >> 2] | ((uint64_t)stk[(((o) + RPP_SB) >> 2) + 1] << 32))
+#define SETSTK32(o, v) do { stk[((o) + RPP_SB) >> 2] = (uint32_t)(v); } while (0)
+#define SETSTK64(o, v) do { uint64_t v_ = (v); stk[((o) + RPP_SB) >> 2] = (uint32_t)v_; stk[(((o) + RPP_SB) >> 2) + 1] = (uint32_t)(v_ >> 32); } while (0)
+#define SETSTK8(o, v) do { uint32_t s_ = ((o) & 3) * 8; stk[((o) + RPP_SB) >> 2] = (stk[((o) + RPP_SB) >> 2] & ~(0xffu << s_)) | ((uint32_t)(uint8_t)(v) << s_); } while (0)
+#define STK8(o) ((uint8_t)(stk[((o) + RPP_SB) >> 2] >> (((o) & 3) * 8)))
 #define ROM64(a) rpp_glibc_rom64(a)
 #define ROMT(t, a) (rpp_glibc_rom_##t[(((a) - 0x##t##ULL) >> 3)])
 #define ROM32(a) ((uint32_t)rpp_glibc_rom64(a))
@@ -717,6 +732,7 @@ UNMACROS = """
 #undef ROM64
 #undef ROMT
 #undef ROM32
+#undef RPP_SB
 """
 
 
@@ -724,7 +740,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--libm", default="/lib/x86_64-linux-gnu/libm.so.6")
     ap.add_argument("--out", default="robotics-path-planning_amd/csrc/glibc235_fma_math.h")
-    ap.add_argument("--tables", default="aeb80:dc0,af960:870,b1b20:1048,b8bc0:e0,b8ca0:400,b90a0:5040,be0e0:34b8",
+    ap.add_argument("--tables", default="aeb80:dc0,af960:870,b1b20:1048,b8bc0:e0,b8ca0:400,b90a0:5040,be0e0:34b8,c15c0:1740",
                     help="comma list base:size (hex) of lookup tables reached through lea; printed when omitted")
     a = ap.parse_args()
     L = Lifter(a.libm)
@@ -772,6 +788,14 @@ RPP_HD static inline double rpp_glibc_atan2(double y, double x) { int o = 0; ret
 RPP_HD static inline double rpp_glibc_pow(double x, double y) { int o = 0; return rpp_glibc_pow_raw(x, y, &o); }
 RPP_HD static inline double rpp_glibc_acos(double x) { int o = 0; return rpp_glibc_acos_raw(x, &o); }
 RPP_HD static inline double rpp_glibc_asin(double x) { int o = 0; return rpp_glibc_asin_raw(x, &o); }
+// math.tan, restated for |x| <= 0.79 only (no range reduction is taken there): beyond that *ood is raised and NaN returned.
+RPP_HD static inline double rpp_glibc_tan_ood(double x, int *ood) {
+  if (!(x >= -0.79 && x <= 0.79)) { *ood = 1; return rpp_b2d(0x7ff8000000000000ULL); }
+  return rpp_glibc_tan_raw(x, ood);
+}
+RPP_HD static inline double rpp_glibc_tan(double x) { int o = 0; return rpp_glibc_tan_ood(x, &o); }
+// np.hypot == glibc hypot (SSE2 baseline build; every finite / infinite / NaN argument).
+RPP_HD static inline double rpp_glibc_hypot(double x, double y) { int o = 0; return rpp_glibc_hypot_raw(x, y, &o); }
 """)
     print("wrote", a.out)
     return 0
