@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-#define RRTX_ABI_VERSION 6   /* 6: rrtx_set_instance_obstacles (and RRTX_ALGO_LQR_RRT_STAR: a new algo value, no layout change); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
+#define RRTX_ABI_VERSION 6   /* 6: rrtx_set_instance_obstacles (and RRTX_ALGO_LQR_RRT_STAR: a new algo value, no layout change; the rrtx_steer_* entry
+                                points: new functions on an object of their own, no layout change); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
                                 rrtx_copy_results_device, per-instance yaw and informed rotation; 4: rrtx_plan_many,
                                 rrtx_selfcheck, rrtx_stats.main_shape / main_f32, rrtx_plan_begin / _step, rrtx_set_launch_bound,
                                 RRTX_ST_REF_HANGS, rrtx_rccl_* */
@@ -349,6 +350,54 @@ int rrtx_get_track_arrays(rrtx_handle* h, int32_t instance, double* x, double* y
 int rrtx_get_track_records(rrtx_handle* h, int32_t instance, int32_t* cand, rrtx_track_record* rec, int32_t cap);
 /* HIP-event time of the kernels of the last rrtx_track_planned, and the roll-out steps they ran (both launches) */
 int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps);
+
+/* ---- batched Dubins / Reeds-Shepp curves between pose pairs, without a planner (csrc/steer_batch.hip.h) -------------------
+ * Replaces plan_dubins_path (10_path_planning_00_dubins_path.py :109-197) and reeds_shepp_path_planning
+ * (10_path_planning_00_reeds_shepp_path.py :506-515) called once per pair: every double is the reference's, bit for bit.
+ * The steer object is independent of rrtx_handle; it owns the device buffers of its solves and reuses them from call to
+ * call (they grow, never shrink).  One host thread per object.  Call order: create, then solve, then the getters of that
+ * solve, then solve again, as often as wanted; a getter before the first solve returns RRTX_E_STATE. */
+typedef struct rrtx_steer rrtx_steer;
+#define RRTX_STEER_DUBINS 0
+#define RRTX_STEER_RS 1
+/* per-pair status */
+#define RRTX_STEER_OK 0
+#define RRTX_STEER_NO_PATH 1          /* RS: the reference returns (None,) * 5; Dubins: no word of the list is feasible */
+#define RRTX_STEER_RAISES_ZERODIV 2   /* RS: the reference raises ZeroDivisionError */
+#define RRTX_STEER_RAISES_VALUE 3     /* RS: the reference raises ValueError (math.asin) */
+/* A steer object on HIP device `device`.  Without a usable gfx950 device the return value is RRTX_E_NO_DEVICE and *out is
+ * still an object (to be destroyed like any other): its solves check their arguments and then return RRTX_E_NO_DEVICE. */
+int rrtx_steer_create(int32_t device, rrtx_steer** out);
+void rrtx_steer_destroy(rrtx_steer* s);
+/* The message of the last call on `s` that failed; for s == NULL the last failure of a steer call of this thread that had no object. */
+const char* rrtx_steer_last_error(rrtx_steer* s);
+/* Solves a batch.  product == 0: n pairs, pair p = (starts[p], goals[p]); ng is not read.  product == 1: the n * ng pairs
+ * of n starts and ng goals, pair p = (starts[p / ng], goals[p % ng]), formed on the device.  Poses are rows (x, y, yaw).
+ * curvature: one value (curvature_per_pair == 0) or one per pair.  step_size: RS as the reference takes it; Dubins
+ * interpolates at the reference's default 0.1 and refuses any other value.  word_order (Dubins only, else NULL):
+ * selected_types as an ordered list of n_words (0..6) indices into LSL, RSR, LSR, RSL, RLR, LRL -- the first of equal
+ * lengths wins, in list order; NULL = all six in that order.  want_points == 0: lengths only (the fast path; no
+ * polyline, no offsets).
+ * Returns RRTX_OK, or RRTX_PARTIAL when some pair's status is not RRTX_STEER_OK (the other pairs are complete).
+ * RRTX_E_INVALID, before any HIP call: a NULL pointer, n < 0 (product: ng < 0), more than 2^30 pairs, an unknown kind,
+ * step_size <= 0, a Dubins step_size != 0.1, n_words outside 0..6 or a word index outside 0..5, a word order with RS, a pose
+ * or curvature that is not finite, |x|, |y| or |yaw| above 1e6, a curvature <= 0, or poses so far apart for the
+ * curvature and step that one curve could exceed 2^22 points. */
+int rrtx_steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
+                     const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
+                     const int32_t* word_order, int32_t n_words, int32_t want_points);
+/* Pairs of the last solve, and its polyline points in all (0 after a lengths-only solve). */
+int rrtx_steer_get_counts(rrtx_steer* s, int64_t* n_pairs, int64_t* n_points);
+/* Per pair of the last solve; any pointer may be NULL.  length: the curve's length, the absolute values of
+ * its seg_len entries added up in segment order; seg_len: rows of 5 (n_seg used, lengths as the reference returns them, i.e. divided by the
+ * curvature); modes: rows of 8 chars, the mode letters NUL padded; offsets: n_pairs + 1 entries (CSR: pair p owns the points
+ * offsets[p] .. offsets[p + 1] - 1; a pair without a path owns none) -- RRTX_E_STATE after a lengths-only solve. */
+int rrtx_steer_get_summary(rrtx_steer* s, int32_t* status, double* length, int32_t* n_seg, double* seg_len, char* modes,
+                           int64_t* offsets);
+/* The flat x, y, yaw arrays of the last solve (cap = doubles available in each; RRTX_E_CAPACITY when too small). */
+int rrtx_steer_get_points(rrtx_steer* s, double* x, double* y, double* yaw, int64_t cap);
+/* HIP-event time of the kernels of the last solve (both stages; the prefix sum between them is not kernel time) */
+int rrtx_steer_get_kernel_ms(rrtx_steer* s, double* kernel_ms);
 
 /* parity harness: out[i] = op(a[i], b[i]) evaluated on the device.  op 0 math.hypot, 1 x**2, 2 sin, 3 cos, 4 atan2,
  * 5 steer end x (rrt_04:1086-1115), 6 sqrt, 7 a/b, 8 acos, 9 asin, 10 checksum of the Reeds-Shepp steer

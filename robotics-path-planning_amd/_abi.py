@@ -29,7 +29,12 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_smooth_paths", "rrtx_smooth_planned", "rrtx_get_smoothed_path", "rrtx_get_path_yaw", "rrtx_selfcheck", "rrtx_plan_many", "rrtx_plan_begin", "rrtx_plan_step",
            "rrtx_set_launch_bound", "rrtx_rccl_unique_id", "rrtx_rccl_init", "rrtx_rccl_gather_results",
            "rrtx_set_rs_cost", "rrtx_track_planned", "rrtx_get_track_outcome", "rrtx_get_track_arrays", "rrtx_get_track_records",
-           "rrtx_get_track_stats"]
+           "rrtx_get_track_stats",
+           "rrtx_steer_create", "rrtx_steer_destroy", "rrtx_steer_last_error", "rrtx_steer_solve", "rrtx_steer_get_counts",
+           "rrtx_steer_get_summary", "rrtx_steer_get_points", "rrtx_steer_get_kernel_ms"]
+STEER_DUBINS, STEER_RS = 0, 1                                                      # include/rrtx.h: #define RRTX_STEER_*
+STEER_OK, STEER_NO_PATH, STEER_RAISES_ZERODIV, STEER_RAISES_VALUE = 0, 1, 2, 3
+DUBINS_WORDS = ("LSL", "RSR", "LSR", "RSL", "RLR", "LRL")   # _PATH_TYPE_MAP order: the word indices of rrtx_steer_solve
 RS_COST_EUCLID, RS_COST_PATH = 0, 1     # include/rrtx.h: #define RRTX_RS_COST_*
 TRACK_FAIL_REACH, TRACK_FAIL_ANGLE, TRACK_FAIL_LONG, TRACK_FAIL_COLLISION = 1, 2, 4, 8   # #define RRTX_TRACK_FAIL_*
 
@@ -142,8 +147,19 @@ def load():
     L.rrtx_rccl_unique_id.argtypes = [vp]
     L.rrtx_rccl_init.argtypes = [vp, vp, i32, i32]
     L.rrtx_rccl_gather_results.argtypes = [vp, vp, vp, vp]
+    L.rrtx_steer_create.argtypes = [i32, C.POINTER(vp)]
+    L.rrtx_steer_destroy.argtypes = [vp]
+    L.rrtx_steer_destroy.restype = None
+    L.rrtx_steer_last_error.argtypes = [vp]
+    L.rrtx_steer_last_error.restype = C.c_char_p
+    L.rrtx_steer_solve.argtypes = [vp, i32, i32, C.c_int64, C.c_int64, vp, vp, vp, i32, C.c_double, vp, i32, i32]
+    L.rrtx_steer_get_counts.argtypes = [vp, i64p, i64p]
+    L.rrtx_steer_get_summary.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.rrtx_steer_get_points.argtypes = [vp, vp, vp, vp, C.c_int64]
+    L.rrtx_steer_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
     for f in EXPORTS:
-        if f not in ("rrtx_last_error", "rrtx_destroy", "rrtx_abi_version", "rrtx_device_count"):
+        if f not in ("rrtx_last_error", "rrtx_destroy", "rrtx_abi_version", "rrtx_device_count", "rrtx_steer_destroy",
+                     "rrtx_steer_last_error"):
             getattr(L, f).restype = C.c_int
     if L.rrtx_abi_version() != RRTX_ABI_VERSION:
         raise RrtxError("librrtx.so ABI version mismatch")
@@ -515,6 +531,90 @@ class Handle:
         kind = np.zeros(cap, dtype=np.int32)
         self._chk(self.L.rrtx_get_trace_kind(self._h, kind.ctypes.data, cap, C.byref(n)), "rrtx_get_trace_kind")
         return kind[:n.value]
+
+
+class Steer:
+    """Thin RAII wrapper over rrtx_steer* (batched Dubins / Reeds-Shepp curves between pose pairs); also a context
+    manager.  It owns the device buffers of its solves, so repeated solves reuse them."""
+
+    def __init__(self, device=0):
+        self.L = load()
+        self._s = C.c_void_p()
+        rc = self.L.rrtx_steer_create(int(device), C.byref(self._s))
+        if rc != 0:
+            msg = self.L.rrtx_steer_last_error(self._s).decode()
+            self.close()
+            raise RrtxError("rrtx_steer_create: %s %s" % (ERRORS.get(rc, rc), msg))
+
+    def close(self):
+        if getattr(self, "_s", None):
+            self.L.rrtx_steer_destroy(self._s)
+            self._s = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_steer_last_error(self._s).decode()))
+        return rc
+
+    def solve(self, kind, starts, goals, curvature, step_size, word_order=None, points=True, product=False):
+        """starts / goals: float64 arrays (n, 3) -- product: (ns, 3) and (ng, 3); curvature: a float or one value per pair;
+        word_order: None or a sequence of Dubins word indices.  Returns 0 or RRTX_PARTIAL."""
+        st = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        go = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
+        n_pairs = len(st) * len(go) if product else len(st)
+        if not product and len(go) != len(st):
+            raise ValueError("solve: %d starts for %d goals" % (len(st), len(go)))
+        per_pair = np.ndim(curvature) > 0   # (np.ascontiguousarray makes a scalar 1-d)
+        cv = np.ascontiguousarray(curvature, dtype=np.float64).reshape(-1)
+        if per_pair and len(cv) != n_pairs:
+            raise ValueError("solve: %d curvatures for %d pairs" % (len(cv), n_pairs))
+        wo = None if word_order is None else np.ascontiguousarray(word_order, dtype=np.int32).reshape(-1)
+        self._keep = (st, go, cv, wo)
+        return self._chk(self.L.rrtx_steer_solve(self._s, int(kind), int(bool(product)), len(st), len(go), st.ctypes.data,
+                                                 go.ctypes.data, cv.ctypes.data, int(per_pair), float(step_size),
+                                                 None if wo is None else wo.ctypes.data, 0 if wo is None else len(wo),
+                                                 int(bool(points))), "rrtx_steer_solve")
+
+    def counts(self):
+        n, m = C.c_int64(), C.c_int64()
+        self._chk(self.L.rrtx_steer_get_counts(self._s, C.byref(n), C.byref(m)), "rrtx_steer_get_counts")
+        return n.value, m.value
+
+    def summary(self, offsets=True):
+        """(status, length, n_seg, seg_len (n, 5), modes (n,) bytes, offsets (n + 1,) or None) of the last solve."""
+        n, _ = self.counts()
+        status = np.zeros(n, dtype=np.int32); length = np.zeros(n); nseg = np.zeros(n, dtype=np.int32)
+        seglen = np.zeros((n, 5)); modes = np.zeros(n, dtype="S8")
+        off = np.zeros(n + 1, dtype=np.int64) if offsets else None
+        self._chk(self.L.rrtx_steer_get_summary(self._s, status.ctypes.data, length.ctypes.data, nseg.ctypes.data,
+                                                seglen.ctypes.data, modes.ctypes.data, off.ctypes.data if offsets else None),
+                  "rrtx_steer_get_summary")
+        return status, length, nseg, seglen, modes, off
+
+    def points(self):
+        _, m = self.counts()
+        x = np.zeros(m); y = np.zeros(m); yaw = np.zeros(m)
+        self._chk(self.L.rrtx_steer_get_points(self._s, x.ctypes.data, y.ctypes.data, yaw.ctypes.data, m),
+                  "rrtx_steer_get_points")
+        return x, y, yaw
+
+    def kernel_ms(self):
+        ms = C.c_double()
+        self._chk(self.L.rrtx_steer_get_kernel_ms(self._s, C.byref(ms)), "rrtx_steer_get_kernel_ms")
+        return ms.value
 
 
 def rccl_unique_id():

@@ -238,13 +238,22 @@ struct DubinsPlan {
 };
 constexpr double kDubinsStep = 0.1;
 
+// order / n_order: the words to try as plan_dubins_path's selected_types gives them (:174-177), an ordered list of
+// _PATH_TYPE_MAP indices; nullptr = every word in map order.  With no feasible word in the list P->ok is 0.
+// zero_acc: numpy's (2,) @ (2,2) accumulates from +0.0, so a local goal of exactly (0, 0) is (+0, +0) whatever the signs
+// of the rotation's entries; the fused form below gives -0 there when both products are -0, and atan2(+-0, -0) = +-pi
+// then picks another word of the same zero length (start = goal with cos(yaw) < 0 and sin(yaw) < 0:
+// tests/golden/steer_kat.npz).  The batch kernel asks for numpy's zero; the tree kernels keep the form their goldens and
+// the oracle pin (a zero-length steer adds nothing to a tree either way).
 RPP_HD static inline void dubins_prepare(DubinsPlan* P, double sx, double sy, double syaw, double gx, double gy,
-                                         double gyaw, double curv) {
+                                         double gyaw, double curv, const int32_t* order = nullptr, int n_order = 6,
+                                         bool zero_acc = false) {
   double lr[4], lrb[4];
   rot_mat_2d_pair(syaw, lr, lrb);
   const double p0 = gx - sx, p1 = gy - sy;
-  const double lx = __builtin_fma(p1, lr[2], p0 * lr[0]);   // (2,) @ (2,2)  :1091-1093
-  const double ly = __builtin_fma(p1, lr[3], p0 * lr[1]);
+  const double q0 = zero_acc ? p0 * lr[0] + 0.0 : p0 * lr[0], q1 = zero_acc ? p0 * lr[1] + 0.0 : p0 * lr[1];
+  const double lx = __builtin_fma(p1, lr[2], q0);   // (2,) @ (2,2)  :1091-1093
+  const double ly = __builtin_fma(p1, lr[3], q1);
   const double lyaw = gyaw - syaw;
   const double d = py_hypot(lx, ly) * curv;                 // :1205
   const double theta = mod2pi(rpp_glibc_atan2(ly, lx));
@@ -260,7 +269,8 @@ RPP_HD static inline void dubins_prepare(DubinsPlan* P, double sx, double sy, do
   double best = dinf();
   int bw = -1;
   double bl0 = 0.0, bl1 = 0.0, bl2 = 0.0;
-  for (int wi = 0; wi < 6; wi++) {
+  for (int q = 0; q < n_order; q++) {
+    const int wi = order ? order[q] : q;
     double o[3];
     if (!dubins_word(wi, alpha, beta, d, tg, d2, a1, a2, a3, o)) continue;
     const double cost = dabs(o[0]) + dabs(o[1]) + dabs(o[2]);

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <new>
 #include <string>
 #include <thread>
 #include <vector>
@@ -28,6 +29,7 @@
 #include "path_smooth.hip.h"
 #include "rrt_lqr.hip.h"
 #include "rrt_track.hip.h"
+#include "steer_batch.hip.h"
 
 using rppk::Ctx;
 using rppk::Inst;
@@ -2094,6 +2096,329 @@ int rrtx_plan_many(rrtx_handle** handles, int32_t n, int32_t* rcs) {
     else if (rc[i] == RRTX_PARTIAL && worst == RRTX_OK) worst = RRTX_PARTIAL;
   }
   return worst;
+}
+
+}  // extern "C"
+
+// ---- batched Dubins / Reeds-Shepp curves between pose pairs (steer_batch.hip.h) -----------------------------------------
+struct rrtx_steer {
+  int device = 0;
+  bool usable = false;        // a gfx950 device was found at creation
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  std::string err;
+  // device buffers, grown on demand
+  struct Buf {
+    void* p = nullptr;
+    size_t bytes = 0;
+  };
+  Buf starts, goals, curv, status, nseg, total, seglen, modes, npts, plan, offsets, px, py, pyaw, flag;
+  // the last solve
+  bool solved = false, has_points = false;
+  int64_t n = 0, n_points = 0;
+  double kernel_ms = 0.0;
+  std::vector<int64_t> h_offsets;
+};
+
+namespace {
+thread_local std::string steer_null_err;
+
+int steer_fail(rrtx_steer* s, int rc, const std::string& msg) {
+  (s ? s->err : steer_null_err) = msg;
+  return rc;
+}
+#define STEERCHK(s, expr)                                                                    \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess) return steer_fail(s, RRTX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+// at least `bytes` in b; contents are not kept
+int steer_reserve(rrtx_steer* s, rrtx_steer::Buf& b, size_t bytes) {
+  if (bytes <= b.bytes) return RRTX_OK;
+  if (b.p) hipFree(b.p);
+  b.p = nullptr;
+  b.bytes = 0;
+  STEERCHK(s, hipMalloc(&b.p, bytes));
+  b.bytes = bytes;
+  return RRTX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rrtx_steer_create(int32_t device, rrtx_steer** out) {
+  if (!out) return steer_fail(nullptr, RRTX_E_INVALID, "rrtx_steer_create: out is NULL");
+  *out = nullptr;
+  if (device < 0) return steer_fail(nullptr, RRTX_E_INVALID, "rrtx_steer_create: negative device ordinal");
+  rrtx_steer* s = new (std::nothrow) rrtx_steer();
+  if (!s) return steer_fail(nullptr, RRTX_E_HIP, "rrtx_steer_create: out of host memory");
+  s->device = device;
+  *out = s;   // returned on failure too: the caller reads the message, and solves still check their arguments
+  int ndev = 0;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device >= ndev ||
+      hipGetDeviceProperties(&prop, device) != hipSuccess ||
+      (!strstr(prop.gcnArchName, "gfx950") && !getenv("RRTX_ALLOW_ANY_ARCH")))
+    return steer_fail(s, RRTX_E_NO_DEVICE, "rrtx_steer_create: no usable gfx950 device (there is no CPU fallback)");
+  STEERCHK(s, hipSetDevice(device));
+  STEERCHK(s, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  for (auto& e : s->ev) STEERCHK(s, hipEventCreate(&e));
+  s->usable = true;
+  return RRTX_OK;
+}
+
+void rrtx_steer_destroy(rrtx_steer* s) {
+  if (!s) return;
+  if (s->usable) {
+    hipSetDevice(s->device);
+    for (rrtx_steer::Buf* b : {&s->starts, &s->goals, &s->curv, &s->status, &s->nseg, &s->total, &s->seglen, &s->modes,
+                               &s->npts, &s->plan, &s->offsets, &s->px, &s->py, &s->pyaw, &s->flag})
+      if (b->p) hipFree(b->p);
+    for (auto& e : s->ev)
+      if (e) hipEventDestroy(e);
+    if (s->stream) hipStreamDestroy(s->stream);
+  }
+  delete s;
+}
+
+const char* rrtx_steer_last_error(rrtx_steer* s) { return s ? s->err.c_str() : steer_null_err.c_str(); }
+
+static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
+                       const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
+                       const int32_t* word_order, int32_t n_words, int32_t want_points) {
+  const char* fn = "rrtx_steer_solve: ";
+  auto bad = [&](const char* m) { return steer_fail(s, RRTX_E_INVALID, std::string(fn) + m); };
+  if (!s) return bad("the steer object is NULL");
+  if (kind != RRTX_STEER_DUBINS && kind != RRTX_STEER_RS) return bad("unknown kind");
+  if (!starts || !goals || !curvature) return bad("starts, goals or curvature is NULL");
+  if (n < 0 || (product && ng < 0)) return bad("a negative batch size");
+  if (!(step_size > 0.0)) return bad("step_size must be > 0");
+  if (kind == RRTX_STEER_DUBINS && step_size != rpp::kDubinsStep)
+    return bad("Dubins curves are interpolated at the reference's default step_size = 0.1; another step is not supported");
+  if (word_order) {
+    if (kind != RRTX_STEER_DUBINS) return bad("a word order applies to Dubins curves only");
+    if (n_words < 0 || n_words > 6) return bad("n_words outside 0..6");
+    for (int i = 0; i < n_words; i++)
+      if (word_order[i] < 0 || word_order[i] > 5) return bad("a word index outside 0..5");
+  }
+  const int64_t n_goals = product ? ng : n;
+  if (n > (1LL << 30) || n_goals > (1LL << 30) || (product && n && ng && n > (1LL << 30) / ng))
+    return bad("more than 2^30 pairs");
+  const int64_t np = product ? n * ng : n;
+  // Every pose and curvature is looked at once here: a curve's point count grows with distance x curvature / step, and the
+  // kernels count points in loops, so an absurd input must never reach them.
+  double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
+  for (int side = 0; side < 2; side++) {
+    const double* q = side ? goals : starts;
+    const int64_t rows = side ? n_goals : n;
+    for (int64_t i = 0; i < rows; i++)
+      for (int c = 0; c < 3; c++) {
+        const double v = q[3 * i + c];
+        if (!(fabs(v) <= 1e6)) return bad("a pose component is not finite or exceeds 1e6 in magnitude");
+        if (c < 2) {
+          lo[c] = v < lo[c] ? v : lo[c];
+          hi[c] = v > hi[c] ? v : hi[c];
+        }
+      }
+  }
+  double cmin = 1e300, cmax = 0.0;
+  const int64_t nc = curvature_per_pair ? np : 1;
+  for (int64_t i = 0; i < nc; i++) {
+    const double c = curvature[i];
+    if (!(c > 0.0) || !(c <= 1e300)) return bad("a curvature is not finite or not > 0");
+    cmin = c < cmin ? c : cmin;
+    cmax = c > cmax ? c : cmax;
+  }
+  if (np > 0) {
+    const double D = hypot(hi[0] - lo[0], hi[1] - lo[1]);
+    const double pts = kind == RRTX_STEER_DUBINS ? (D * cmax + 20.0) / rpp::kDubinsStep
+                                                 : D / step_size + 20.0 / (step_size * cmin);
+    if (!(pts <= 4194304.0)) return bad("the poses are so far apart for this curvature and step that a curve could exceed 2^22 points");
+  }
+  if (!s->usable) return steer_fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+
+  s->solved = false;
+  s->has_points = false;
+  s->n = np;
+  s->n_points = 0;
+  s->kernel_ms = 0.0;
+  s->h_offsets.clear();
+  if (np == 0) {
+    s->has_points = want_points != 0;
+    s->h_offsets.assign(1, 0);
+    s->solved = true;
+    return RRTX_OK;
+  }
+  STEERCHK(s, hipSetDevice(s->device));
+  int rc;
+  const size_t N = (size_t)np;
+  if ((rc = steer_reserve(s, s->starts, sizeof(double) * 3 * (size_t)n))) return rc;
+  if ((rc = steer_reserve(s, s->goals, sizeof(double) * 3 * (size_t)n_goals))) return rc;
+  if ((rc = steer_reserve(s, s->curv, sizeof(double) * (size_t)nc))) return rc;
+  if ((rc = steer_reserve(s, s->status, sizeof(int32_t) * N))) return rc;
+  if ((rc = steer_reserve(s, s->nseg, sizeof(int32_t) * N))) return rc;
+  if ((rc = steer_reserve(s, s->total, sizeof(double) * N))) return rc;
+  if ((rc = steer_reserve(s, s->seglen, sizeof(double) * 5 * N))) return rc;
+  if ((rc = steer_reserve(s, s->modes, 8 * N))) return rc;
+  if ((rc = steer_reserve(s, s->npts, sizeof(int32_t) * N))) return rc;
+  if ((rc = steer_reserve(s, s->flag, sizeof(int32_t)))) return rc;
+  if (want_points) {
+    const size_t rec = kind == RRTX_STEER_DUBINS ? sizeof(rpp::DubinsPlan) : sizeof(rpp::RsCourse);
+    if ((rc = steer_reserve(s, s->plan, rec * N))) return rc;
+    if ((rc = steer_reserve(s, s->offsets, sizeof(int64_t) * (N + 1)))) return rc;
+  }
+  STEERCHK(s, hipMemcpyAsync(s->starts.p, starts, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, s->stream));
+  STEERCHK(s, hipMemcpyAsync(s->goals.p, goals, sizeof(double) * 3 * (size_t)n_goals, hipMemcpyHostToDevice, s->stream));
+  STEERCHK(s, hipMemcpyAsync(s->curv.p, curvature, sizeof(double) * (size_t)nc, hipMemcpyHostToDevice, s->stream));
+  STEERCHK(s, hipMemsetAsync(s->flag.p, 0, sizeof(int32_t), s->stream));
+
+  rppsb::Args a;
+  memset(&a, 0, sizeof(a));
+  a.starts = (const double*)s->starts.p;
+  a.goals = (const double*)s->goals.p;
+  a.curv = curvature_per_pair ? (const double*)s->curv.p : nullptr;
+  a.curv0 = curvature[0];
+  a.step = step_size;
+  a.n = np;
+  a.ng = product ? ng : 1;
+  a.product = product ? 1 : 0;
+  a.want_points = want_points ? 1 : 0;
+  a.n_order = word_order ? n_words : 6;
+  for (int i = 0; i < 6; i++) a.order[i] = (word_order && i < n_words) ? word_order[i] : i;
+  a.status = (int32_t*)s->status.p;
+  a.nseg = (int32_t*)s->nseg.p;
+  a.total = (double*)s->total.p;
+  a.seglen = (double*)s->seglen.p;
+  a.modes = (char*)s->modes.p;
+  a.npts = (int32_t*)s->npts.p;
+  a.dplan = (rpp::DubinsPlan*)s->plan.p;
+  a.course = (rpp::RsCourse*)s->plan.p;
+  a.flag = (int32_t*)s->flag.p;
+
+  // stage 1
+  const unsigned blk = (unsigned)((np + rppsb::TPB - 1) / rppsb::TPB);
+  STEERCHK(s, hipEventRecord(s->ev[0], s->stream));
+  if (kind == RRTX_STEER_DUBINS) {
+    hipLaunchKernelGGL(rppsb::steer_dubins_solve, dim3(blk), dim3(rppsb::TPB), 0, s->stream, a);
+  } else {
+    hipLaunchKernelGGL(rppsb::steer_rs_solve, dim3((unsigned)((np + rppsb::RS_PAIRS - 1) / rppsb::RS_PAIRS)),
+                       dim3(rppsb::RS_TPB), 0, s->stream, a);
+    if (want_points) hipLaunchKernelGGL(rppsb::steer_rs_course, dim3(blk), dim3(rppsb::TPB), 0, s->stream, a);
+  }
+  STEERCHK(s, hipGetLastError());
+  STEERCHK(s, hipEventRecord(s->ev[1], s->stream));
+  int32_t flag = 0;
+  STEERCHK(s, hipMemcpyAsync(&flag, s->flag.p, sizeof(flag), hipMemcpyDeviceToHost, s->stream));
+  std::vector<int32_t> cnt;
+  if (want_points) {
+    cnt.resize(N);
+    STEERCHK(s, hipMemcpyAsync(cnt.data(), s->npts.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
+  }
+  STEERCHK(s, hipStreamSynchronize(s->stream));
+  float ms = 0.f;
+  STEERCHK(s, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+  s->kernel_ms = ms;
+
+  if (want_points) {
+    // offsets: exclusive prefix sum of the point counts
+    s->h_offsets.resize(N + 1);
+    int64_t tot = 0;
+    for (size_t i = 0; i < N; i++) {
+      s->h_offsets[i] = tot;
+      tot += cnt[i] > 0 ? cnt[i] : 0;
+    }
+    s->h_offsets[N] = tot;
+    s->n_points = tot;
+    if (tot > 0) {
+      if ((rc = steer_reserve(s, s->px, sizeof(double) * (size_t)tot))) return rc;
+      if ((rc = steer_reserve(s, s->py, sizeof(double) * (size_t)tot))) return rc;
+      if ((rc = steer_reserve(s, s->pyaw, sizeof(double) * (size_t)tot))) return rc;
+      if ((tot + rppsb::TPB - 1) / rppsb::TPB > 0x7fffffffLL)
+        return steer_fail(s, RRTX_E_OVERFLOW, std::string(fn) + "more polyline points than one launch can fill");
+      STEERCHK(s, hipMemcpyAsync(s->offsets.p, s->h_offsets.data(), sizeof(int64_t) * (N + 1), hipMemcpyHostToDevice, s->stream));
+      a.offsets = (const int64_t*)s->offsets.p;
+      a.px = (double*)s->px.p;
+      a.py = (double*)s->py.p;
+      a.pyaw = (double*)s->pyaw.p;
+      const unsigned fblk = (unsigned)((tot + rppsb::TPB - 1) / rppsb::TPB);
+      STEERCHK(s, hipEventRecord(s->ev[2], s->stream));
+      if (kind == RRTX_STEER_DUBINS)
+        hipLaunchKernelGGL(rppsb::steer_fill<rppsb::KIND_DUBINS>, dim3(fblk), dim3(rppsb::TPB), 0, s->stream, a);
+      else
+        hipLaunchKernelGGL(rppsb::steer_fill<rppsb::KIND_RS>, dim3(fblk), dim3(rppsb::TPB), 0, s->stream, a);
+      STEERCHK(s, hipGetLastError());
+      STEERCHK(s, hipEventRecord(s->ev[3], s->stream));
+      STEERCHK(s, hipStreamSynchronize(s->stream));
+      STEERCHK(s, hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
+      s->kernel_ms += ms;
+    }
+    s->has_points = true;
+  }
+  s->solved = true;
+  if (flag) {
+    s->err = std::string(fn) + "some pairs have no path or are cases where the reference raises (see the status column)";
+    return RRTX_PARTIAL;
+  }
+  return RRTX_OK;
+}
+
+int rrtx_steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
+                     const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
+                     const int32_t* word_order, int32_t n_words, int32_t want_points) {
+  try {   // host allocations (offsets, messages) must not throw across the ABI
+    return steer_solve(s, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size, word_order, n_words,
+                       want_points);
+  } catch (const std::exception& e) {
+    if (s) s->solved = false;
+    return steer_fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve: ") + e.what());
+  }
+}
+
+int rrtx_steer_get_counts(rrtx_steer* s, int64_t* n_pairs, int64_t* n_points) {
+  if (!s || !n_pairs || !n_points) return steer_fail(s, RRTX_E_INVALID, "rrtx_steer_get_counts: a NULL pointer");
+  if (!s->solved) return steer_fail(s, RRTX_E_STATE, "rrtx_steer_get_counts: no completed solve");
+  *n_pairs = s->n;
+  *n_points = s->n_points;
+  return RRTX_OK;
+}
+
+int rrtx_steer_get_summary(rrtx_steer* s, int32_t* status, double* length, int32_t* n_seg, double* seg_len, char* modes,
+                           int64_t* offsets) {
+  if (!s) return steer_fail(s, RRTX_E_INVALID, "rrtx_steer_get_summary: the steer object is NULL");
+  if (!s->solved) return steer_fail(s, RRTX_E_STATE, "rrtx_steer_get_summary: no completed solve");
+  if (offsets && !s->has_points)
+    return steer_fail(s, RRTX_E_STATE, "rrtx_steer_get_summary: the last solve was lengths-only, it has no offsets");
+  if (offsets) memcpy(offsets, s->h_offsets.data(), sizeof(int64_t) * s->h_offsets.size());
+  if (s->n == 0) return RRTX_OK;
+  const size_t N = (size_t)s->n;
+  STEERCHK(s, hipSetDevice(s->device));
+  if (status) STEERCHK(s, hipMemcpy(status, s->status.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  if (length) STEERCHK(s, hipMemcpy(length, s->total.p, sizeof(double) * N, hipMemcpyDeviceToHost));
+  if (n_seg) STEERCHK(s, hipMemcpy(n_seg, s->nseg.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  if (seg_len) STEERCHK(s, hipMemcpy(seg_len, s->seglen.p, sizeof(double) * 5 * N, hipMemcpyDeviceToHost));
+  if (modes) STEERCHK(s, hipMemcpy(modes, s->modes.p, 8 * N, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+int rrtx_steer_get_points(rrtx_steer* s, double* x, double* y, double* yaw, int64_t cap) {
+  if (!s) return steer_fail(s, RRTX_E_INVALID, "rrtx_steer_get_points: the steer object is NULL");
+  if (!s->solved || !s->has_points) return steer_fail(s, RRTX_E_STATE, "rrtx_steer_get_points: no completed solve with points");
+  if (cap < s->n_points) return steer_fail(s, RRTX_E_CAPACITY, "rrtx_steer_get_points: the buffers are too small");
+  if (s->n_points == 0) return RRTX_OK;
+  const size_t bytes = sizeof(double) * (size_t)s->n_points;
+  STEERCHK(s, hipSetDevice(s->device));
+  if (x) STEERCHK(s, hipMemcpy(x, s->px.p, bytes, hipMemcpyDeviceToHost));
+  if (y) STEERCHK(s, hipMemcpy(y, s->py.p, bytes, hipMemcpyDeviceToHost));
+  if (yaw) STEERCHK(s, hipMemcpy(yaw, s->pyaw.p, bytes, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+int rrtx_steer_get_kernel_ms(rrtx_steer* s, double* kernel_ms) {
+  if (!s || !kernel_ms) return steer_fail(s, RRTX_E_INVALID, "rrtx_steer_get_kernel_ms: a NULL pointer");
+  if (!s->solved) return steer_fail(s, RRTX_E_STATE, "rrtx_steer_get_kernel_ms: no completed solve");
+  *kernel_ms = s->kernel_ms;
+  return RRTX_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,248 @@
+// steer_batch.hip.h -- the two curve solvers as batch kernels of their own (gfx950): shortest Dubins / Reeds-Shepp
+// curve between many pose pairs, without a planner around them.
+// Reference: /root/reference/src_path_planning/10_path_planning_00_dubins_path.py plan_dubins_path :109-197 and
+//   10_path_planning_00_reeds_shepp_path.py reeds_shepp_path_planning :506-515 (the same functions, line for line, as the
+//   copies inside rrt_05 / rrt_06); the scalar pieces are csrc/rpp_dubins.h and csrc/rpp_rs.h.
+//
+// Path lengths differ per pair, so the work is two stages with a CSR layout between them:
+//   stage 1  steer_dubins_solve  one lane per pair: dubins_prepare over the ordered word list -> word, segment lengths,
+//                                point count; the prepared DubinsPlan goes to global memory when points are wanted.
+//            steer_rs_solve      16 lanes per pair, 4 pairs per wave: lane t evaluates the variants t, t + 16, t + 32 of the
+//                                48 (12 word families x 4 symmetries) and writes its candidate records into the pair's
+//                                table in LDS; lane 0 of the pair then runs set_path's de-duplication and
+//                                paths.index(min(...)) over that table in the reference's order.  A variant that raises or
+//                                reports "step size too large" hides every later one: the table is read in order, so
+//                                the later variants are computed speculatively and never looked at.
+//            steer_rs_course     (points wanted) one lane per pair: generate_local_course prepared for random access.
+//   offsets  exclusive prefix sum of the point counts (host, one int32 per pair down, one int64 per pair up).
+//   stage 2  steer_fill          one lane per output point: binary search of the point index in offsets, then
+//                                dubins_point / rs_point, which are random-access by point index.
+// Lengths-only is stage 1 alone (no plan, no course, no offsets).
+// Product mode: pair p of ns x ng is (start p / ng, goal p % ng), formed here; the host never builds the product.
+#pragma once
+#include "rpp_rs.h"
+
+namespace rppsb {
+
+constexpr int KIND_DUBINS = 0, KIND_RS = 1;
+constexpr int ST_OK = 0, ST_NO_PATH = 1, ST_RAISES_ZERODIV = 2, ST_RAISES_VALUE = 3;   // include/rrtx.h RRTX_STEER_*
+constexpr int TPB = 256;            // steer_dubins_solve, steer_rs_course, steer_fill
+constexpr int RS_TPB = 64;          // steer_rs_solve: one wave
+constexpr int RS_LANES = 16;        // lanes per pair
+constexpr int RS_PAIRS = RS_TPB / RS_LANES;
+constexpr int RS_KEPT = 3;          // table state: set_path kept this candidate (0 none, 1 candidate, 2 step too large)
+
+struct Args {
+  const double* starts;   // (ns, 3)
+  const double* goals;    // (ng, 3); pair mode: (n, 3)
+  const double* curv;     // one value per pair, or nullptr: curv0
+  double curv0, step;
+  int64_t n, ng;          // pairs; product mode: goals per start
+  int32_t product, want_points;
+  int32_t order[6];       // Dubins: the words to try, in this order (the first wins ties)
+  int32_t n_order;
+  int32_t* status;        // [n]
+  int32_t* nseg;          // [n]
+  double* total;          // [n]  the absolute values of seglen added up in segment order
+  double* seglen;         // [n][5] as the reference returns them (divided by the curvature)
+  char* modes;            // [n][8] letters, NUL padded
+  int32_t* npts;          // [n]
+  rpp::DubinsPlan* dplan; // [n]
+  rpp::RsCourse* course;  // [n]
+  int32_t* flag;          // set when any pair is not ST_OK
+  const int64_t* offsets; // [n + 1]
+  double *px, *py, *pyaw; // [offsets[n]]
+};
+
+__device__ inline void pair_poses(const Args& a, int64_t p, double* s, double* g) {
+  const int64_t si = a.product ? p / a.ng : p, gi = a.product ? p % a.ng : p;
+  for (int i = 0; i < 3; i++) {
+    s[i] = a.starts[3 * si + i];
+    g[i] = a.goals[3 * gi + i];
+  }
+}
+__device__ inline double pair_curv(const Args& a, int64_t p) { return a.curv ? a.curv[p] : a.curv0; }
+
+// ---- Dubins, stage 1 ----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TPB) void steer_dubins_solve(Args a) {
+  const int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (p >= a.n) return;
+  double s[3], g[3];
+  pair_poses(a, p, s, g);
+  const double curv = pair_curv(a, p);
+  rpp::DubinsPlan P;
+  rpp::dubins_prepare(&P, s[0], s[1], s[2], g[0], g[1], g[2], curv, a.order, a.n_order, true);
+  char* m = a.modes + 8 * p;
+  double* sl = a.seglen + 5 * p;
+  for (int i = 0; i < 8; i++) m[i] = 0;
+  sl[3] = sl[4] = 0.0;
+  if (!P.ok) {   // no word of the list is feasible (the reference fails on b_mode = None)
+    sl[0] = sl[1] = sl[2] = 0.0;
+    a.status[p] = ST_NO_PATH;
+    a.nseg[p] = 0;
+    a.total[p] = 0.0;
+    a.npts[p] = 0;
+    atomicOr(a.flag, 1);
+    return;
+  }
+  double tot = 0.0;
+  for (int i = 0; i < 3; i++) {
+    const double l = P.len[i] / curv;   // :315
+    sl[i] = l;
+    tot += rpp::dabs(l);
+    const int md = P.mode[i];
+    m[i] = md == 0 ? 'L' : (md == 1 ? 'S' : 'R');
+  }
+  a.status[p] = ST_OK;
+  a.nseg[p] = 3;
+  a.total[p] = tot;
+  a.npts[p] = P.total;
+  if (a.want_points) a.dplan[p] = P;
+}
+
+// ---- Reeds-Shepp, stage 1 -----------------------------------------------------------------------------------------
+// The candidate table of one pair (what rs_plan keeps as st[48], d[48][5], ct[48][6] in one lane's private memory)
+struct RsTable {
+  double d[48][5];
+  double L[48];        // sum |d| in segment order (set_path :1063)
+  int32_t st[48];      // rs_variant's return value; RS_KEPT once set_path has taken the candidate
+  int32_t n[48];
+  uint32_t code[48];   // rs_code of the word: equal codes <=> equal ctypes lists
+  char ct[48][8];
+};
+
+// set_path :1061-1080 over the variants in the reference's order + paths.index(min(paths, key=abs(L))) :1436, as
+// rpp::rs_select does it, with the kept list held in the table itself (st == RS_KEPT, L) instead of two private arrays.
+// Returns the chosen k, -1: None, < -1: the reference raises.
+__device__ inline int rs_select_lds(RsTable& T, double step, double maxc) {
+  int np = 0;
+  for (int k = 0; k < 48; k++) {
+    const int s = T.st[k];
+    if (s == 0) continue;
+    if (s < 0) return s;    // -3 / -4: raised inside this variant
+    if (s == 2) return -1;  // "Step size too large": generate_path returns [] there and then
+    const double L = T.L[k];
+    const uint32_t code = T.code[k];
+    bool skip = false;
+    for (int i = 0; i < k; i++)
+      if (T.st[i] == RS_KEPT && T.code[i] == code && (T.L[i] - L) <= step) skip = true;
+    if (skip || L <= step) continue;
+    T.st[k] = RS_KEPT;
+    np++;
+  }
+  if (np == 0) return -1;
+  int bi = -1;
+  double bl = 0.0;
+  for (int k = 0; k < 48; k++) {
+    if (T.st[k] != RS_KEPT) continue;
+    const double l = rpp::dabs(T.L[k] / maxc);
+    if (bi < 0 || l < bl) {   // strict: the first of equal lengths, as list.index finds it
+      bl = l;
+      bi = k;
+    }
+  }
+  return bi;
+}
+
+__global__ __launch_bounds__(RS_TPB) void steer_rs_solve(Args a) {
+  __shared__ RsTable tab[RS_PAIRS];
+  const int grp = threadIdx.x / RS_LANES, t = threadIdx.x % RS_LANES;
+  const int64_t p = (int64_t)blockIdx.x * RS_PAIRS + grp;
+  const bool live = p < a.n;
+  RsTable& T = tab[grp];
+  double s[3], g[3], maxc = 1.0;
+  rpp::RsFrame F;
+  if (live) {
+    pair_poses(a, p, s, g);
+    maxc = pair_curv(a, p);
+    rpp::rs_frame(s[0], s[1], s[2], g[0], g[1], g[2], maxc, a.step, &F);
+    const double sdth = rpp_glibc_sin(F.dth), cdth = rpp_glibc_cos(F.dth);
+    for (int j = 0; j < 48 / RS_LANES; j++) {
+      const int k = t + RS_LANES * j;   // k = 4 * word family + symmetry, the reference's order
+      double d[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+      char ct[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      int nn = 0;
+      const int st = rpp::rs_variant_sc(k >> 2, k & 3, F, sdth, cdth, d, ct, &nn);
+      T.st[k] = st;
+      T.n[k] = nn;
+      for (int i = 0; i < 5; i++) T.d[k][i] = d[i];
+      for (int i = 0; i < 8; i++) T.ct[k][i] = ct[i];
+      T.L[k] = st == 1 ? rpp::rs_sum_abs(d, nn) : 0.0;
+      T.code[k] = st == 1 ? rpp::rs_code(ct) : 0u;
+    }
+  }
+  __syncthreads();
+  if (!live || t != 0) return;
+  const int sel = rs_select_lds(T, F.step, maxc);
+  char* m = a.modes + 8 * p;
+  double* sl = a.seglen + 5 * p;
+  for (int i = 0; i < 8; i++) m[i] = 0;
+  for (int i = 0; i < 5; i++) sl[i] = 0.0;
+  a.npts[p] = 0;
+  if (sel < 0) {
+    a.status[p] = sel == -1 ? ST_NO_PATH : (sel == -3 ? ST_RAISES_ZERODIV : ST_RAISES_VALUE);
+    a.nseg[p] = 0;
+    a.total[p] = 0.0;
+    atomicOr(a.flag, 1);
+    return;
+  }
+  const int nl = T.n[sel];
+  double tot = 0.0;
+  for (int i = 0; i < nl; i++) {
+    const double l = T.d[sel][i] / maxc;   // :1420
+    sl[i] = l;
+    tot += rpp::dabs(l);
+    m[i] = T.ct[sel][i];
+  }
+  a.status[p] = ST_OK;
+  a.nseg[p] = nl;
+  a.total[p] = tot;
+  if (a.want_points) {   // the chosen word in curvature units, for steer_rs_course
+    rpp::RsCourse& C = a.course[p];
+    for (int i = 0; i < 5; i++) C.len[i] = T.d[sel][i];
+    for (int i = 0; i < 6; i++) C.ct[i] = T.ct[sel][i];
+    C.nl = nl;
+  }
+}
+
+__global__ __launch_bounds__(TPB) void steer_rs_course(Args a) {
+  const int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (p >= a.n || a.status[p] != ST_OK) return;
+  rpp::RsCourse& C = a.course[p];
+  double len[5];
+  char ct[6];
+  for (int i = 0; i < 5; i++) len[i] = C.len[i];
+  for (int i = 0; i < 6; i++) ct[i] = C.ct[i];
+  const int nl = C.nl;
+  double s[3], g[3];
+  pair_poses(a, p, s, g);
+  rpp::rs_course(len, ct, nl, s[0], s[1], s[2], pair_curv(a, p), a.step, &C);
+  a.npts[p] = C.total;
+}
+
+// ---- stage 2 -------------------------------------------------------------------------------------------------------
+template <int KIND>
+__global__ __launch_bounds__(TPB) void steer_fill(Args a) {
+  const int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  const int64_t total = a.offsets[a.n];
+  if (idx >= total) return;
+  int64_t lo = 0, hi = a.n;   // the pair p with offsets[p] <= idx < offsets[p + 1] (rows without points are skipped over)
+  while (hi - lo > 1) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (a.offsets[mid] <= idx)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  const int k = (int)(idx - a.offsets[lo]);
+  double x, y, yaw;
+  if (KIND == KIND_DUBINS)
+    rpp::dubins_point(a.dplan[lo], k, pair_curv(a, lo), &x, &y, &yaw);
+  else
+    rpp::rs_point(a.course[lo], k, &x, &y, &yaw);
+  a.px[idx] = x;
+  a.py[idx] = y;
+  a.pyaw[idx] = yaw;
+}
+
+}  // namespace rppsb

@@ -1,0 +1,117 @@
+"""Batched Dubins / Reeds-Shepp curves between pose pairs on the GPU, without a planner around them.
+
+    bs = BatchSteer("dubins")                       # or "rs"
+    res = bs.plan(starts, goals, curvature)         # (n, 3) poses each; res.path(i) = the reference's five-tuple
+    cost = bs.plan(starts, goals, 1.0, points=False, product=True).length_matrix()   # (ns, ng) lengths
+
+Every double is what the reference's plan_dubins_path (10_path_planning_00_dubins_path.py :109) /
+reeds_shepp_path_planning (10_path_planning_00_reeds_shepp_path.py :506) returns for that pair, bit for bit.  There is no
+CPU fallback: without a device the call raises RrtxError.
+"""
+import numpy as np
+
+from . import _abi
+
+KINDS = {"dubins": _abi.STEER_DUBINS, "rs": _abi.STEER_RS, "reeds_shepp": _abi.STEER_RS}
+DEFAULT_STEP = {_abi.STEER_DUBINS: 0.1, _abi.STEER_RS: 0.2}
+
+
+def word_order(selected_types):
+    """plan_dubins_path's selected_types (names, in order) as word indices; a repeated name cannot change the result
+    (the first of equal lengths wins), so only its first occurrence is kept.  KeyError for an unknown name, as
+    _PATH_TYPE_MAP[ptype] raises it."""
+    if selected_types is None:
+        return None
+    idx = []
+    for name in selected_types:
+        if name not in _abi.DUBINS_WORDS:
+            raise KeyError(name)
+        k = _abi.DUBINS_WORDS.index(name)
+        if k not in idx:
+            idx.append(k)
+    return idx
+
+
+class SteerResult:
+    """One solved batch.  status (n,) STEER_*; length (n,): the absolute segment lengths added up; modes: list of n strings; lengths: list of n arrays of segment
+    lengths; offsets (n + 1,) and the flat x, y, yaw when points were asked for, else None."""
+
+    def __init__(self, kind, status, length, nseg, seglen, modes, offsets, xyz, shape, rc, kernel_ms):
+        self.kind = kind
+        self.status = status
+        self.length = length
+        self.n_seg = nseg
+        self.seg_len = seglen
+        self.modes = [m.decode() for m in modes]
+        self.lengths = [seglen[i, :nseg[i]].copy() for i in range(len(nseg))]
+        self.offsets = offsets
+        self.x, self.y, self.yaw = xyz if xyz is not None else (None, None, None)
+        self.shape = shape          # (ns, ng) in product mode, else None
+        self.rc = rc                # 0 or RRTX_PARTIAL
+        self.kernel_ms = kernel_ms
+
+    def __len__(self):
+        return len(self.status)
+
+    def path(self, i):
+        """What the reference function returns for pair i: (x, y, yaw, modes, lengths) -- numpy arrays and lists for
+        Dubins, lists for Reeds-Shepp, (None,) * 5 where Reeds-Shepp finds no path; raises where the reference raises."""
+        st = int(self.status[i])
+        if st == _abi.STEER_RAISES_ZERODIV:
+            raise ZeroDivisionError("float division by zero")
+        if st == _abi.STEER_RAISES_VALUE:
+            raise ValueError("math domain error")
+        if st == _abi.STEER_NO_PATH:
+            if self.kind == _abi.STEER_DUBINS:   # b_mode stays None and _generate_local_course zips over it
+                raise TypeError("'NoneType' object is not iterable")
+            return None, None, None, None, None
+        if self.x is None:
+            raise _abi.RrtxError("path(): this batch was solved with points=False")
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        modes = list(self.modes[i])
+        lengths = [float(v) for v in self.lengths[i]]
+        if self.kind == _abi.STEER_DUBINS:
+            return self.x[a:b].copy(), self.y[a:b].copy(), self.yaw[a:b].copy(), modes, lengths
+        return self.x[a:b].tolist(), self.y[a:b].tolist(), self.yaw[a:b].tolist(), modes, lengths
+
+    def length_matrix(self):
+        if self.shape is None:
+            raise _abi.RrtxError("length_matrix(): this batch was not solved in product mode")
+        return self.length.reshape(self.shape)
+
+
+class BatchSteer:
+    """Shortest Dubins ("dubins") or Reeds-Shepp ("rs") curves for batches of pose pairs; device buffers are kept between
+    calls of plan()."""
+
+    def __init__(self, kind, device=0):
+        if kind not in KINDS:
+            raise ValueError("BatchSteer: kind is 'dubins' or 'rs', not %r" % (kind,))
+        self.kind = KINDS[kind]
+        self._steer = _abi.Steer(device)
+
+    def close(self):
+        self._steer.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def plan(self, starts, goals, curvature, step_size=None, selected_types=None, points=True, product=False):
+        """starts, goals: (n, 3) rows of (x, y, yaw) -- with product=True (ns, 3) and (ng, 3), pair p = (p // ng, p % ng).
+        curvature: a float or one per pair.  step_size: Reeds-Shepp any value > 0 (default 0.2); Dubins 0.1 only.
+        selected_types (Dubins): word names in the order to try them."""
+        if step_size is None:
+            step_size = DEFAULT_STEP[self.kind]
+        wo = word_order(selected_types)
+        st = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        go = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
+        S = self._steer
+        rc = S.solve(self.kind, st, go, curvature, step_size, word_order=wo, points=points, product=product)
+        status, length, nseg, seglen, modes, off = S.summary(offsets=bool(points))
+        xyz = S.points() if points else None
+        return SteerResult(self.kind, status, length, nseg, seglen, modes, off, xyz,
+                           (len(st), len(go)) if product else None, rc, S.kernel_ms())

@@ -2,7 +2,8 @@
 
 Per-script drop-in modules: `rrt_amd.rrt_01` ... `rrt_amd.rrt_10` carry exactly the names the reference script of that
 number defines for its driver cell (`RRT`, `BITStar`, `Node`, `path_smoothing`, `get_path_length`), so a driver written
-against `10_path_planning_01_rrt_04_rrt_star.py` runs after `from rrt_amd.rrt_04 import *`."""
+against `10_path_planning_01_rrt_04_rrt_star.py` runs after `from rrt_amd.rrt_04 import *`.  `rrt_amd.dubins_path` and `rrt_amd.reeds_shepp_path` do the same for the two
+stand-alone curve scripts (`plan_dubins_path`, `reeds_shepp_path_planning`)."""
 import importlib
 import os
 import sys
@@ -13,6 +14,7 @@ if _root not in sys.path:
 _pkg = importlib.import_module("robotics-path-planning_amd")
 _abi = _pkg._abi
 planner = importlib.import_module("robotics-path-planning_amd.planner")
+steer = importlib.import_module("robotics-path-planning_amd.steer")
 RRT = _pkg.RRT
 RRTStar = _pkg.RRTStar
 RRTSobol = _pkg.RRTSobol
@@ -27,6 +29,7 @@ LQRRRTStar = _pkg.LQRRRTStar
 ClosedLoopRRTStar = _pkg.ClosedLoopRRTStar
 informed_rotation = _pkg.informed_rotation
 BatchPlanner = _pkg.BatchPlanner
+BatchSteer = _pkg.BatchSteer
 Node = _pkg.Node
 AreaBounds = _pkg.AreaBounds
 get_path_length = _pkg.get_path_length

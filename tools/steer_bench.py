@@ -1,0 +1,76 @@
+"""Throughput of the batched Dubins / Reeds-Shepp curves (BatchSteer): pairs/s for lengths-only and for points.
+
+    python tools/steer_bench.py [--pairs 1048576] [--reps 5] [--cpu-pairs 2000]
+
+Random pairs in the pose box of the known-answer vectors ([-2, 15]^2, any yaw), curvature 1, Reeds-Shepp step 0.2.  The
+GPU figure is HIP-event kernel time (stage 1, and stage 1 + fill), the median of --reps solves after one warm-up solve;
+transfers and the host prefix sum are reported separately as wall time.  Beside it: the C oracle (oracle.dubins /
+oracle.reeds_shepp, which always builds the points) on one core over a subsample of the same pairs.  Prints one JSON
+line per kind.  Needs a device: there is no CPU fallback."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "oracle")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def pairs(n, seed):
+    rs = np.random.RandomState(seed)
+    p = np.empty((n, 6))
+    p[:, [0, 1, 3, 4]] = rs.uniform(-2, 15, (n, 4))
+    p[:, [2, 5]] = rs.uniform(-np.pi, np.pi, (n, 2))
+    return p
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=1 << 20)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--cpu-pairs", type=int, default=2000)
+    args = ap.parse_args()
+    import oracle
+    import rrt_amd
+    for kind in ("dubins", "rs"):
+        p = pairs(args.pairs, 7 if kind == "dubins" else 8)
+        out = {"kind": kind, "pairs": args.pairs, "reps": args.reps}
+        with rrt_amd.BatchSteer(kind) as bs:
+            for points in (False, True):
+                ms, wall = [], []
+                res = None
+                for rep in range(args.reps + 1):
+                    t0 = time.perf_counter()
+                    res = bs._steer.solve(bs.kind, p[:, 0:3], p[:, 3:6], 1.0, 0.1 if kind == "dubins" else 0.2, points=points)
+                    wall.append((time.perf_counter() - t0) * 1e3)
+                    ms.append(bs._steer.kernel_ms())
+                k = "points" if points else "lengths"
+                med = float(np.median(ms[1:]))
+                out[k + "_kernel_ms"] = med
+                out[k + "_pairs_per_s"] = args.pairs / (med * 1e-3)
+                out[k + "_solve_wall_ms"] = float(np.median(wall[1:]))
+                if points:
+                    out["n_points"] = bs._steer.counts()[1]
+                    out["points_per_s"] = out["n_points"] / (med * 1e-3)
+        m = min(args.cpu_pairs, args.pairs)
+        fn = oracle.dubins if kind == "dubins" else oracle.reeds_shepp
+        t0 = time.perf_counter()
+        for i in range(m):
+            a = [float(v) for v in p[i]]
+            try:
+                fn(*a, 1.0)
+            except (ZeroDivisionError, ValueError):
+                pass
+        dt = time.perf_counter() - t0
+        out["cpu_oracle_pairs"] = m
+        out["cpu_oracle_pairs_per_s_one_core"] = m / dt
+        print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
