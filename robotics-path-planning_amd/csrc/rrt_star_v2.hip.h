@@ -1,4 +1,4 @@
-// rrt_star_v2.hip.h -- instantiates the latency-lean RRT* iteration kernel (rrt_star_v2_body.inc) for two
+// rrt_star_v2.hip.h -- instantiates the latency-lean RRT* iteration kernel (rrt_star_v2_body.inc) for three
 // workgroup shapes:
 //   rppk2     256 threads / instance, 4 workgroups per CU  (<= 1024 resident instances per GPU)
 //   rppk2s    128 threads / instance, 8 workgroups per CU  (<= 2048 resident instances; smaller LDS tables)

@@ -275,15 +275,21 @@ static int timed_launch(rrtx_handle* h, bool copy_results, Queue&& queue) {
 // ---- RRT* (rrt_04, search_until_max_iter): iteration-kernel launches ------------------------------------------------
 // One pass of the latency-lean iteration kernel over `nblk` instances (c.inst_map selects them; nullptr = 0..nblk-1),
 // in chunks of h->v2_chunk_iters iterations, workgroup shape tpb in {64, 128, 256}.
+// The kernel's three shapes (rrt_star_v2.hip.h), widest first: threads per instance, near-candidate capacity (RRT2_NU), obstacle
+// tile (RRT2_MAXOBS), the batch size above which the shape is chosen (8 / 16 workgroups per CU wanted resident) and the kernel.
+struct V2Shape { int tpb, nu, max_obs, min_batch; void (*kernel)(Ctx, int); };
+static const V2Shape V2_SHAPES[3] = {
+    {rppk2::TPB, rppk2::NU, rppk2::MAX_OBS, 0, rppk2::rrt_star_kernel_v2},
+    {rppk2s::TPB, rppk2s::NU, rppk2s::MAX_OBS, 1280, rppk2s::rrt_star_kernel_v2},
+    {rppk2t::TPB, rppk2t::NU, rppk2t::MAX_OBS, 2560, rppk2t::rrt_star_kernel_v2}};
+static const V2Shape& v2_shape(int tpb) {   // any other value: the 256-thread shape
+  for (const V2Shape& s : V2_SHAPES)
+    if (s.tpb == tpb) return s;
+  return V2_SHAPES[0];
+}
 static int launch_rrt_star_v2_once(rrtx_handle* h, const Ctx& c, int nblk, int tpb) {
-  return timed_launch(h, false, [&] {
-    if (tpb == 64)
-      hipLaunchKernelGGL(rppk2t::rrt_star_kernel_v2, dim3(nblk), dim3(rppk2t::TPB), 0, h->stream, c, h->v2_chunk_iters);
-    else if (tpb == 128)
-      hipLaunchKernelGGL(rppk2s::rrt_star_kernel_v2, dim3(nblk), dim3(rppk2s::TPB), 0, h->stream, c, h->v2_chunk_iters);
-    else
-      hipLaunchKernelGGL(rppk2::rrt_star_kernel_v2, dim3(nblk), dim3(rppk2::TPB), 0, h->stream, c, h->v2_chunk_iters);
-  });
+  const V2Shape& s = v2_shape(tpb);
+  return timed_launch(h, false, [&] { hipLaunchKernelGGL(s.kernel, dim3(nblk), dim3(s.tpb), 0, h->stream, c, h->v2_chunk_iters); });
 }
 static int launch_rrt_star_v2(rrtx_handle* h, const Ctx& c, int nblk, int tpb) {
   for (int64_t done_it = 0; done_it < c.max_iter; done_it += h->v2_chunk_iters) {
@@ -293,9 +299,33 @@ static int launch_rrt_star_v2(rrtx_handle* h, const Ctx& c, int nblk, int tpb) {
   return RRTX_OK;
 }
 
-// Near-candidate capacity of a shape (rrt_star_v2.hip.h RRT2_NU) and the obstacle tile it holds
-static int v2_shape_nu(int tpb) { return tpb == 64 ? rppk2t::NU : tpb == 128 ? rppk2s::NU : rppk2::NU; }
-static int v2_shape_maxobs(int tpb) { return tpb == 64 ? rppk2t::MAX_OBS : tpb == 128 ? rppk2s::MAX_OBS : rppk2::MAX_OBS; }
+// The knobs of the rrt_04 iteration kernel's one-wave shape, from the environment into the launch context
+static void rrt_star_knobs(Ctx& c) {
+  // rrt_04 kernel, one-wave shape: a streaming pass serves up to 1 + spec2 iterations (clamped to the kernel's RRT2_SPECK;
+  // RRTX_SPEC2=0: one pass per iteration)
+  c.spec2 = 8;
+  if (const char* e = getenv("RRTX_SPEC2")) c.spec2 = atoi(e) > 0 ? atoi(e) : 0;
+  // rrt_04 kernel, one-wave shape: near and nearest queries from the grid index (RRTX_GRID=0: the streaming pass only);
+  // below grid_min nodes a pass streams (RRTX_GRID_MIN: test knob, 0 = from the first node)
+  c.grid = c.gcnt != nullptr;
+  if (const char* e = getenv("RRTX_GRID")) c.grid = c.grid && atoi(e) != 0;
+  c.grid_min = 4096;
+  if (const char* e = getenv("RRTX_GRID_MIN")) c.grid_min = atoi(e) > 0 ? atoi(e) : 0;
+  // rrt_04 kernel, one-wave shape: a cost propagation still running after prop_vec nodes continues one sibling chain per
+  // lane (RRTX_PROP_VEC, < 0: one node per round trip throughout); RRTX_PROP_CAP: test knob, fewer pending chains in LDS
+  c.prop_vec = 8;
+  if (const char* e = getenv("RRTX_PROP_VEC")) c.prop_vec = atoi(e);
+  c.prop_cap = 1 << 30;
+  if (const char* e = getenv("RRTX_PROP_CAP")) c.prop_cap = atoi(e) > 0 ? atoi(e) : 0;
+  // rrt_04 kernel, one-wave shape: the candidate edges of an iteration are tested against the obstacles that reach the
+  // near ball of its new node only (RRTX_OBS_CULL=0: against every obstacle, in (edge, obstacle) pairs)
+  c.obs_cull = 1;
+  if (const char* e = getenv("RRTX_OBS_CULL")) c.obs_cull = atoi(e) != 0;
+  // rrt_04 kernel, one-wave shape: a pass over the grid index gathers for all its centres together (RRTX_GRID_MERGE=0:
+  // centre after centre, two round trips each)
+  c.grid_merge = 1;
+  if (const char* e = getenv("RRTX_GRID_MERGE")) c.grid_merge = atoi(e) != 0;
+}
 
 // Expected size of the largest near set of a plan, for a tree that fills the sampling square evenly:
 // density * pi * r(n)^2 with r(n) of rrt_04:1329-1334 -> pi * min(ccd^2 ln n, n expand_dis^2) / area, largest at
@@ -850,30 +880,7 @@ int rrtx_plan_begin(rrtx_handle* h) {
     if (atoi(e) == 0 && c.algo == RRTX_ALGO_INFORMED) c.xf = c.yf = nullptr;   // informed kernel: f64 passes only
   if (const char* e = getenv("RRTX_Q16"))
     if (atoi(e) == 0 && c.algo == RRTX_ALGO_INFORMED) c.xq = nullptr;   // informed kernel: no 16-bit first stage
-  // rrt_04 kernel, one-wave shape: a streaming pass serves up to 1 + spec2 iterations (clamped to the kernel's RRT2_SPECK;
-  // RRTX_SPEC2=0: one pass per iteration)
-  c.spec2 = 8;
-  if (const char* e = getenv("RRTX_SPEC2")) c.spec2 = atoi(e) > 0 ? atoi(e) : 0;
-  // rrt_04 kernel, one-wave shape: near and nearest queries from the grid index (RRTX_GRID=0: the streaming pass only);
-  // below grid_min nodes a pass streams (RRTX_GRID_MIN: test knob, 0 = from the first node)
-  c.grid = c.gcnt != nullptr;
-  if (const char* e = getenv("RRTX_GRID")) c.grid = c.grid && atoi(e) != 0;
-  c.grid_min = 4096;
-  if (const char* e = getenv("RRTX_GRID_MIN")) c.grid_min = atoi(e) > 0 ? atoi(e) : 0;
-  // rrt_04 kernel, one-wave shape: a cost propagation still running after prop_vec nodes continues one sibling chain per
-  // lane (RRTX_PROP_VEC, < 0: one node per round trip throughout); RRTX_PROP_CAP: test knob, fewer pending chains in LDS
-  c.prop_vec = 8;
-  if (const char* e = getenv("RRTX_PROP_VEC")) c.prop_vec = atoi(e);
-  c.prop_cap = 1 << 30;
-  if (const char* e = getenv("RRTX_PROP_CAP")) c.prop_cap = atoi(e) > 0 ? atoi(e) : 0;
-  // rrt_04 kernel, one-wave shape: the candidate edges of an iteration are tested against the obstacles that reach the
-  // near ball of its new node only (RRTX_OBS_CULL=0: against every obstacle, in (edge, obstacle) pairs)
-  c.obs_cull = 1;
-  if (const char* e = getenv("RRTX_OBS_CULL")) c.obs_cull = atoi(e) != 0;
-  // rrt_04 kernel, one-wave shape: a pass over the grid index gathers for all its centres together (RRTX_GRID_MERGE=0:
-  // centre after centre, two round trips each)
-  c.grid_merge = 1;
-  if (const char* e = getenv("RRTX_GRID_MERGE")) c.grid_merge = atoi(e) != 0;
+  rrt_star_knobs(c);
   // The staged per-instance start state (RNG, start / goal) lives on the device too: uploaded when the host changed it,
   // copied device -> device at every plan (2.7 KB per instance: 44 MB of pageable-memory upload per plan of 16 384 instances)
   if (!h->d_inst0) {
@@ -934,13 +941,13 @@ int rrtx_plan_begin(rrtx_handle* h) {
     // workgroup shape: fewer threads per instance once more instances want to be resident (8 / 16 workgroups per CU),
     // as long as the shape's obstacle tile and near-candidate capacity fit the problem
     const int need_nu = estimate_near_capacity(h->p);
-    int tpb = 256;
+    int tpb = V2_SHAPES[0].tpb;
     const int m = h->m_max;   // every instance's list must fit the shape's obstacle tile
-    if (B > 1280 && m <= rppk2s::MAX_OBS && need_nu <= rppk2s::NU) tpb = 128;
-    if (B > 2560 && m <= rppk2t::MAX_OBS && need_nu <= rppk2t::NU) tpb = 64;
+    for (const V2Shape& s : V2_SHAPES)
+      if (B > s.min_batch && m <= s.max_obs && need_nu <= s.nu) tpb = s.tpb;
     if (const char* e = getenv("RRTX_TPB")) {
-      const int v = atoi(e);
-      tpb = (v == 64 && m <= rppk2t::MAX_OBS) ? 64 : (v == 128 && m <= rppk2s::MAX_OBS) ? 128 : 256;
+      const V2Shape& s = v2_shape(atoi(e));
+      tpb = m <= s.max_obs ? s.tpb : V2_SHAPES[0].tpb;
     }
     R.v2_tpb = tpb;
   }
@@ -1093,7 +1100,7 @@ static int plan_finish(rrtx_handle* h) {
       const std::vector<int32_t> redo = with_status(RRTX_ST_OVERFLOW);
       if (redo.empty() || shape == 0) break;
       shape = shape == 64 ? 128 : shape == 128 ? 256 : 0;
-      if (shape && h->m_max > v2_shape_maxobs(shape)) continue;
+      if (shape && h->m_max > v2_shape(shape).max_obs) continue;
       if ((rc = replan_on(redo, shape))) return rc;
     }
     // rewire moved a node while near_inds had repeated entries (rrt_04:1337 with :1372): the iteration kernel does not

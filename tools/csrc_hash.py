@@ -10,7 +10,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMMON = ["rrtx_api.hip", "rrt_kernels.hip.h", "rpp_core.h", "glibc235_fma_math.h"]
 FILES = {
-    "c2": COMMON + ["rrt_star_v2.hip.h", "rrt_star_v2_body.inc"],
+    "c2": COMMON + ["rrt_star_v2.hip.h", "rrt_star_v2_body.inc"] + ["rrt_star_v2_%s.inc" % p for p in
+                    ("shapes", "scan64", "q16", "grid", "cand", "walk", "kernel")],
     "c3": COMMON + ["rrt_informed.hip.h"],
     "c4": COMMON + ["rrt_bitstar.hip.h", "rrt_bitstar_wave.hip.h", "rpp_bitstar.h"],
     "c5": COMMON + ["rrt_dubins.hip.h", "rpp_dubins.h"],

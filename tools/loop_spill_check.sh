@@ -1,16 +1,25 @@
 #!/bin/bash
-# Usage: tools/loop_spill_check.sh <path to a rrt_star_v2_body.inc> [extra hipcc flags]
-# Compiles rrtx_api.hip for gfx950 with that kernel body (CPU only, ~1 min) and reports, for every streaming loop of
-# rppk2t::rrt_star_kernel_v2, the lines per slot, the scratch instructions and the full s_waitcnt vmcnt(0) drains inside it:
-# a register-allocation regression of the hot loop shows here before any GPU time is spent.
-BODY=$1; shift
+# Usage: tools/loop_spill_check.sh [csrc directory] [extra hipcc flags]      (default: this tree's csrc)
+# Compiles that directory's rrtx_api.hip for gfx950 (CPU only, ~1 min) and reports, for the three rrt_star_kernel_v2
+# instantiations, the resource-usage remarks, and for every streaming loop of rppk2t::rrt_star_kernel_v2 the lines per slot,
+# the scratch instructions and the full s_waitcnt vmcnt(0) drains inside it: a register-allocation regression of the hot
+# loop shows here before any GPU time is spent.  Run it on two directories (a checkout of the parent commit
+# and this tree) to compare them; KEEP_ASM=<file> keeps the device assembly.
 REPO=$(cd "$(dirname "$0")/.." && pwd)
-D=/tmp/chk_$$; mkdir -p $D; cp $REPO/robotics-path-planning_amd/csrc/* $D/; cp $BODY $D/rrt_star_v2_body.inc
-mkdir -p $D/../include 2>/dev/null
+SRC=$REPO/robotics-path-planning_amd/csrc
+if [ -n "$1" ] && [ "${1#-}" = "$1" ]; then   # a first argument that is no flag names the directory
+  [ -f "$1/rrtx_api.hip" ] || { echo "usage: $0 [csrc directory] [extra hipcc flags]   ($1 holds no rrtx_api.hip)" >&2; exit 2; }
+  SRC=$(cd "$1" && pwd); shift
+fi
+D=$(mktemp -d); trap 'rm -rf "$D"' EXIT; cp $SRC/* $D/
 cd $D && sed -i "s#\"../../include/rrtx.h\"#\"$REPO/include/rrtx.h\"#" rrtx_api.hip
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Wno-parentheses-equality -Wno-unused-value "$@" --cuda-device-only -S -Rpass-analysis=kernel-resource-usage -o $D/o.s rrtx_api.hip 2> $D/err.txt
-grep -A7 "Function Name: _ZN6rppk2t18rrt_star_kernel_v2EN4rppk3CtxEi " $D/err.txt | grep -E "VGPRs Spill|ScratchSize|SGPRs Spill" | sed 's/.*remark: *//' | tr '\n' ' '; echo
 grep -E "error" $D/err.txt | head -3
+for ns in 5rppk2 6rppk2s 6rppk2t; do
+  echo -n "${ns:1}: "
+  grep -A12 "Function Name: _ZN${ns}18rrt_star_kernel_v2EN4rppk3CtxEi " $D/err.txt | grep -E "VGPRs Spill|ScratchSize|SGPRs Spill|Occupancy|LDS Size" | sed -e 's/.*remark: *//' -e 's/ *\[-Rpass.*//' | tr '\n' ';'; echo
+done
+[ -n "$KEEP_ASM" ] && cp $D/o.s "$KEEP_ASM"
 L=$(grep -n "^_ZN6rppk2t18rrt_star_kernel_v2EN4rppk3CtxEi:" $D/o.s | cut -d: -f1)
 awk -v l=$L 'NR>=l' $D/o.s | awk '/s_endpgm/{print; exit} {print}' > $D/k.s
 python3 - $D/k.s <<'PY'
@@ -38,4 +47,3 @@ while i<len(groups):
         i=j
     else: i+=1
 PY
-rm -rf $D
