@@ -25,8 +25,8 @@
 extern "C" {
 #endif
 
-#define RRTX_ABI_VERSION 6   /* 6: rrtx_set_instance_obstacles (and RRTX_ALGO_LQR_RRT_STAR: a new algo value, no layout change; the rrtx_steer_* entry
-                                points: new functions on an object of their own, no layout change); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
+#define RRTX_ABI_VERSION 6   /* 6: rrtx_set_instance_obstacles (and RRTX_ALGO_LQR_RRT_STAR: a new algo value, no layout change; the rrtx_steer_* and
+                                rrtx_tracker_* entry points: new functions on objects of their own, no layout change); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
                                 rrtx_copy_results_device, per-instance yaw and informed rotation; 4: rrtx_plan_many,
                                 rrtx_selfcheck, rrtx_stats.main_shape / main_f32, rrtx_plan_begin / _step, rrtx_set_launch_bound,
                                 RRTX_ST_REF_HANGS, rrtx_rccl_* */
@@ -398,6 +398,57 @@ int rrtx_steer_get_summary(rrtx_steer* s, int32_t* status, double* length, int32
 int rrtx_steer_get_points(rrtx_steer* s, double* x, double* y, double* yaw, int64_t cap);
 /* HIP-event time of the kernels of the last solve (both stages; the prefix sum between them is not kernel time) */
 int rrtx_steer_get_kernel_ms(rrtx_steer* s, double* kernel_ms);
+
+/* ---- batched closed-loop tracking of courses given as data, without a planner (csrc/rrt_track.hip.h) ----------------------
+ * For every course of a batch: what ClosedLoopRRTStar.check_tracking_path_is_feasible(path) (rrt_10:1526-1564) returns,
+ * every double the reference's.  A course is given in driving order (start ... goal; the reference receives it reversed),
+ * its goal is its last point (:1531), and the roll-out starts at the reference's State(-0.0, -0.0, 0.0, 0.0) (:1309)
+ * unless start_state is given.  The tracker is independent of rrtx_handle; it owns the device buffers of its runs and
+ * reuses them from call to call (they grow, never shrink).  One host thread per object.  Call order: create, run, the
+ * getters of that run, run again, as often as wanted; a getter before the first run returns RRTX_E_STATE. */
+typedef struct rrtx_tracker rrtx_tracker;
+/* As rrtx_steer_create: without a usable gfx950 device the return value is RRTX_E_NO_DEVICE and *out is still an object
+ * (to be destroyed like any other): its runs check their arguments and then return RRTX_E_NO_DEVICE. */
+int rrtx_tracker_create(int32_t device, rrtx_tracker** out);
+void rrtx_tracker_destroy(rrtx_tracker* t);
+/* The message of the last call on `t` that failed; for t == NULL the last failure of a tracker call of this thread that had no object. */
+const char* rrtx_tracker_last_error(rrtx_tracker* t);
+typedef struct rrtx_track_batch {
+  int64_t n;                      /* courses */
+  const int64_t* offsets;         /* n + 1, CSR into x / y / yaw, driving order */
+  const double *x, *y, *yaw;
+  const double* per_course;       /* NULL, or n rows (target_speed, yaw_th, invalid_travel_ratio) overriding tp's */
+  const double* start_state;      /* NULL (the reference's -0.0, -0.0, 0, 0), or n rows (x, y, yaw, v) */
+  const double* obstacles;        /* rows (x, y, radius) */
+  const int64_t* obs_offsets;     /* NULL: one list of n_obstacles rows for every course; else n + 1 CSR entries */
+  int64_t n_obstacles;
+  const double* robot_radius;     /* one value, or n values when robot_radius_per_course != 0 */
+  int32_t robot_radius_per_course;
+  int32_t want_arrays;
+} rrtx_track_batch;
+/* Rolls every course out (tp->xy_th is not read).  Collision thresholds are (radius + robot_radius) ** 2, computed on the
+ * host as rrtx_set_obstacles computes them.  Per course a rrtx_track_record; ood: 0 complete, 1 tan outside the replica's
+ * domain, 2 the reference raises (a course of fewer than 3 points, :1435), 3 a course of more than 960 points.  With
+ * want_arrays every course with ood == 0 owns len entries in each of the seven arrays (x, y, yaw, v, t, a, d as the
+ * reference returns them; no goal pose is appended, that is search_best_feasible_path's doing); others own none.
+ * Returns RRTX_OK, or RRTX_PARTIAL when some record has ood != 0 (every other course is complete).  n == 0 is a valid
+ * empty run.  RRTX_E_INVALID, before any HIP call (also on a host without a device): a NULL pointer (obstacles may be
+ * NULL when n_obstacles is 0, and x / y / yaw when the courses hold no point in all), n_obstacles < 0, n < 0 or n > 2^30,
+ * offsets or obs_offsets that do not start at 0 or that decrease, obs_offsets[n] > n_obstacles, more than 2^31 - 1 points in all, a pose, obstacle,
+ * radius, start state or per-course value that is not finite, more than 64 obstacles in one list, or parameters outside
+ * dt > 0, 0 <= T, T / dt <= 1e6, Lf > 0, L > 0, 0 <= steer_max <= 0.79 (as rrtx_track_planned).  After these checks a host
+ * without a device gets RRTX_E_NO_DEVICE. */
+int rrtx_tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_batch* b);
+/* Courses of the last run, and the roll-out steps (the sum of len over the courses with ood == 0). */
+int rrtx_tracker_get_counts(rrtx_tracker* t, int64_t* n_courses, int64_t* n_steps);
+/* rec: n_courses records; arr_offsets (may be NULL): n_courses + 1 entries, the exclusive sum of len over the courses with ood == 0 */
+int rrtx_tracker_get_records(rrtx_tracker* t, rrtx_track_record* rec, int64_t* arr_offsets);
+/* The seven flat arrays of the last run, n_steps doubles each; any pointer may be NULL (cap = doubles available in each;
+ * RRTX_E_CAPACITY when too small).  RRTX_E_STATE after a run with want_arrays == 0. */
+int rrtx_tracker_get_arrays(rrtx_tracker* t, double* x, double* y, double* yaw, double* v, double* tt, double* a, double* d,
+                            int64_t cap);
+/* HIP-event time of the kernels of the last run (both launches) */
+int rrtx_tracker_get_kernel_ms(rrtx_tracker* t, double* kernel_ms);
 
 /* parity harness: out[i] = op(a[i], b[i]) evaluated on the device.  op 0 math.hypot, 1 x**2, 2 sin, 3 cos, 4 atan2,
  * 5 steer end x (rrt_04:1086-1115), 6 sqrt, 7 a/b, 8 acos, 9 asin, 10 checksum of the Reeds-Shepp steer

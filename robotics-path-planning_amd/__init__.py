@@ -8,12 +8,13 @@ import it with importlib, or through the `rrt_amd` shim at the repository root:
     path = rrt.planning(animation=False)
 
 Submodules: planner (RRT = rrt_01's class, RRTStar = rrt_04's class, BatchPlanner), steer (BatchSteer: batched Dubins /
-Reeds-Shepp curves between pose pairs),
+Reeds-Shepp curves between pose pairs), track (BatchTrack: batched closed-loop tracking of courses given as data),
 _abi (ctypes binding of include/rrtx.h), csrc/ (HIP kernels + C ABI sources).
 """
 from . import _abi  # noqa: F401
 from .planner import (RRT, RRTSobol, RRTStar, RRTStarDubins, RRTDubins, RRTStarReedsShepp, BITStar, bitstar_rotation, InformedRRTStar, LQRRRTStar, ClosedLoopRRTStar, BatchPlanner, Node, AreaBounds, get_path_length, path_smoothing,  # noqa: F401
                       informed_rotation)
 from .steer import BatchSteer  # noqa: F401
+from .track import BatchTrack  # noqa: F401
 
-__all__ = ["RRT", "RRTSobol", "RRTStar", "RRTStarDubins", "RRTDubins", "RRTStarReedsShepp", "BITStar", "InformedRRTStar", "LQRRRTStar", "ClosedLoopRRTStar", "BatchPlanner", "BatchSteer", "Node", "AreaBounds", "get_path_length", "path_smoothing"]
+__all__ = ["RRT", "RRTSobol", "RRTStar", "RRTStarDubins", "RRTDubins", "RRTStarReedsShepp", "BITStar", "InformedRRTStar", "LQRRRTStar", "ClosedLoopRRTStar", "BatchPlanner", "BatchSteer", "BatchTrack", "Node", "AreaBounds", "get_path_length", "path_smoothing"]

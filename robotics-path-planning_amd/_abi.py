@@ -31,7 +31,9 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_set_rs_cost", "rrtx_track_planned", "rrtx_get_track_outcome", "rrtx_get_track_arrays", "rrtx_get_track_records",
            "rrtx_get_track_stats",
            "rrtx_steer_create", "rrtx_steer_destroy", "rrtx_steer_last_error", "rrtx_steer_solve", "rrtx_steer_get_counts",
-           "rrtx_steer_get_summary", "rrtx_steer_get_points", "rrtx_steer_get_kernel_ms"]
+           "rrtx_steer_get_summary", "rrtx_steer_get_points", "rrtx_steer_get_kernel_ms",
+           "rrtx_tracker_create", "rrtx_tracker_destroy", "rrtx_tracker_last_error", "rrtx_tracker_run",
+           "rrtx_tracker_get_counts", "rrtx_tracker_get_records", "rrtx_tracker_get_arrays", "rrtx_tracker_get_kernel_ms"]
 STEER_DUBINS, STEER_RS = 0, 1                                                      # include/rrtx.h: #define RRTX_STEER_*
 STEER_OK, STEER_NO_PATH, STEER_RAISES_ZERODIV, STEER_RAISES_VALUE = 0, 1, 2, 3
 DUBINS_WORDS = ("LSL", "RSR", "LSR", "RSL", "RLR", "LRL")   # _PATH_TYPE_MAP order: the word indices of rrtx_steer_solve
@@ -70,6 +72,14 @@ class TrackOutcome(C.Structure):
 
 TRACK_RECORD = np.dtype([("find_goal", np.int32), ("len", np.int32), ("fail", np.int32), ("ood", np.int32),
                          ("t_last", np.float64)])
+
+
+class TrackBatch(C.Structure):
+    """rrtx_track_batch: the courses of one rrtx_tracker_run (pointers into arrays the caller keeps alive)."""
+    _fields_ = [("n", C.c_int64), ("offsets", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p), ("yaw", C.c_void_p),
+                ("per_course", C.c_void_p), ("start_state", C.c_void_p), ("obstacles", C.c_void_p),
+                ("obs_offsets", C.c_void_p), ("n_obstacles", C.c_int64), ("robot_radius", C.c_void_p),
+                ("robot_radius_per_course", C.c_int32), ("want_arrays", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -157,9 +167,19 @@ def load():
     L.rrtx_steer_get_summary.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.rrtx_steer_get_points.argtypes = [vp, vp, vp, vp, C.c_int64]
     L.rrtx_steer_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.rrtx_tracker_create.argtypes = [i32, C.POINTER(vp)]
+    L.rrtx_tracker_destroy.argtypes = [vp]
+    L.rrtx_tracker_destroy.restype = None
+    L.rrtx_tracker_last_error.argtypes = [vp]
+    L.rrtx_tracker_last_error.restype = C.c_char_p
+    L.rrtx_tracker_run.argtypes = [vp, C.POINTER(TrackParams), C.POINTER(TrackBatch)]
+    L.rrtx_tracker_get_counts.argtypes = [vp, i64p, i64p]
+    L.rrtx_tracker_get_records.argtypes = [vp, vp, vp]
+    L.rrtx_tracker_get_arrays.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64]
+    L.rrtx_tracker_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
     for f in EXPORTS:
         if f not in ("rrtx_last_error", "rrtx_destroy", "rrtx_abi_version", "rrtx_device_count", "rrtx_steer_destroy",
-                     "rrtx_steer_last_error"):
+                     "rrtx_steer_last_error", "rrtx_tracker_destroy", "rrtx_tracker_last_error"):
             getattr(L, f).restype = C.c_int
     if L.rrtx_abi_version() != RRTX_ABI_VERSION:
         raise RrtxError("librrtx.so ABI version mismatch")
@@ -614,6 +634,72 @@ class Steer:
     def kernel_ms(self):
         ms = C.c_double()
         self._chk(self.L.rrtx_steer_get_kernel_ms(self._s, C.byref(ms)), "rrtx_steer_get_kernel_ms")
+        return ms.value
+
+
+class Tracker:
+    """Thin RAII wrapper over rrtx_tracker* (batched closed-loop tracking of courses given as data); also a context
+    manager.  It owns the device buffers of its runs, so repeated runs reuse them."""
+
+    def __init__(self, device=0):
+        self.L = load()
+        self._t = C.c_void_p()
+        rc = self.L.rrtx_tracker_create(int(device), C.byref(self._t))
+        if rc != 0:
+            msg = self.L.rrtx_tracker_last_error(self._t).decode()
+            self.close()
+            raise RrtxError("rrtx_tracker_create: %s %s" % (ERRORS.get(rc, rc), msg))
+
+    def close(self):
+        if getattr(self, "_t", None):
+            self.L.rrtx_tracker_destroy(self._t)
+            self._t = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_tracker_last_error(self._t).decode()))
+        return rc
+
+    def run(self, params, batch):
+        """params: TrackParams; batch: TrackBatch (its arrays are kept alive by the caller).  Returns 0 or RRTX_PARTIAL."""
+        return self._chk(self.L.rrtx_tracker_run(self._t, C.byref(params), C.byref(batch)), "rrtx_tracker_run")
+
+    def counts(self):
+        n, m = C.c_int64(), C.c_int64()
+        self._chk(self.L.rrtx_tracker_get_counts(self._t, C.byref(n), C.byref(m)), "rrtx_tracker_get_counts")
+        return n.value, m.value
+
+    def records(self):
+        """(records (n,) TRACK_RECORD, arr_offsets (n + 1,)) of the last run."""
+        n, _ = self.counts()
+        rec = np.zeros(n, dtype=TRACK_RECORD)
+        off = np.zeros(n + 1, dtype=np.int64)
+        self._chk(self.L.rrtx_tracker_get_records(self._t, rec.ctypes.data, off.ctypes.data), "rrtx_tracker_get_records")
+        return rec, off
+
+    def arrays(self):
+        """The seven flat arrays x, y, yaw, v, t, a, d of the last run."""
+        _, m = self.counts()
+        arr = [np.zeros(m) for _ in range(7)]
+        self._chk(self.L.rrtx_tracker_get_arrays(self._t, *[q.ctypes.data for q in arr], m), "rrtx_tracker_get_arrays")
+        return arr
+
+    def kernel_ms(self):
+        ms = C.c_double()
+        self._chk(self.L.rrtx_tracker_get_kernel_ms(self._t, C.byref(ms)), "rrtx_tracker_get_kernel_ms")
         return ms.value
 
 

@@ -34,7 +34,8 @@ struct Record {          // what check_tracking_path_is_feasible returned for on
   int32_t find;          // find_goal as returned (:1564)
   int32_t n;             // len(t)
   int32_t fail;          // F_* bits
-  int32_t ood;           // 1: the libm replica left its stated domain (tan beyond 0.79), 2: the reference raises (course < 3 points)
+  int32_t ood;           // 1: the libm replica left its stated domain (tan beyond 0.79), 2: the reference raises (course < 3 points),
+                         // 3: the course exceeds the kernel's capacity (device only)
   double tlast;          // t[-1]
 };
 
@@ -216,10 +217,11 @@ RPP_HD static inline bool is_candidate(double x, double y, double yaw, double gx
 
 // check_tracking_path_is_feasible :1526-1564 on one thread (host tests; the kernel runs the same pieces wave-wide).
 // cx / cy / cyaw: the course in driving order (start ... goal), n points, with room for EXT_MAX more; sp: n + EXT_MAX.
-// out[7] (x, y, yaw, v, t, a, d; each `cap` doubles) may be null.  max_steps bounds the loop on the device.
+// out[7] (x, y, yaw, v, t, a, d; each `cap` doubles) may be null.  start: the state the roll-out begins in; the default
+// is the reference's hard-coded State(-0.0, -0.0, 0.0, 0.0) (:1309).
 RPP_HD static inline void track_course(double* cx, double* cy, double* cyaw, signed char* sp, int n, const double* ox,
                                        const double* oy, const double* othr, int m, const Params& P, double* const* out,
-                                       int cap, Record* r) {
+                                       int cap, Record* r, State start = State{-0.0, -0.0, 0.0, 0.0}) {
   r->find = 0;
   r->n = 0;
   r->fail = 0;
@@ -237,7 +239,7 @@ RPP_HD static inline void track_course(double* cx, double* cy, double* cyaw, sig
   }
   for (int i = 0; i < n - 1; i++) sp[i] = (signed char)segment_flags(cx, cy, cyaw, i);
   stop_points(sp, n);
-  State s = {-0.0, -0.0, 0.0, 0.0};
+  State s = start;
   double time = 0.0, vsum = 0.0, last_yaw = 0.0, tlast = 0.0;
   int cnt = 0, hit = 0, ood = 0, reached = 0;
   auto append = [&](double a, double d) {

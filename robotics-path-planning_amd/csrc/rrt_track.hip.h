@@ -18,6 +18,10 @@
 // A second launch of track_roll_kernel (store = 1) re-runs each winner alone and stores its seven arrays: the
 // roll-out is deterministic, so this costs one extra roll-out per instance instead of 2 002 x 7 doubles per candidate.
 //
+// track_courses_kernel is the same roll-out on courses given as data (rrtx_tracker_run, BatchTrack): its front end reads a
+// course from the caller's CSR arrays instead of walking a tree; everything behind the laid-out course is roll_course, one
+// text for both kernels.
+//
 // Capacities: a course (with its extension) of up to LDS_PTS points is held in LDS (x, y; the speed profile always is, one
 // byte per point), up to SLAB_PTS points in the wave's global slab; a longer one sets RRTX_ST_OVERFLOW for the instance.
 // Obstacles: at most 64 per instance (the Reeds-Shepp planner's limit).
@@ -122,6 +126,84 @@ __global__ void track_pick_kernel(TrackArgs a) {
   }
 }
 
+// Everything of one job after its course is laid out, shared by the two roll kernels: extend_path on lane 0, segment_flags one
+// lane per segment, stop_points, the closed_loop_prediction loop (:1307-1372) with the wave-shared np.hypot scan, the running
+// collision flag (lane k against obstacle k), judge, and with o7 != nullptr the store of the seven arrays (array q at
+// o7 + q * os, at most ocap entries each).  Called by the whole wave with r.ood == 0 after the lanes wrote cx / cy / gcw[0 ..
+// total - 1] (not yet synchronised); cx / cy hold total + EXT_MAX points, lsp and s_n are the block's LDS.  ob: this lane has
+// an obstacle (obx, oby, its threshold obt).  s: the state the roll-out starts in.
+__device__ __forceinline__ void roll_course(double* cx, double* cy, double* gcw, signed char* lsp, int32_t* s_n, int total,
+                                            double gx, double gy, double gyaw, bool ob, double obx, double oby, double obt,
+                                            const Params& P, State s, double* o7, int ocap, int64_t os, Record& r) {
+  const int lane = threadIdx.x;
+  __syncthreads();
+  if (lane == 0) *s_n = extend_path(cx, cy, gcw, total, P);
+  __syncthreads();
+  const int n = *s_n;
+  if (n < 0) r.ood = 1;
+  if (!r.ood) {
+    for (int i = lane; i < n - 1; i += TPB) lsp[i] = (signed char)segment_flags(cx, cy, gcw, i);
+    __syncthreads();
+    if (lane == 0) stop_points(lsp, n);
+    __syncthreads();
+    // ---- closed_loop_prediction :1307-1372
+    double time = 0.0, vsum = 0.0, last_yaw = 0.0, tlast = 0.0;
+    int cnt = 0, hit = 0, ood = 0, reached = 0;
+    auto append = [&](double ai, double di) {
+      if (o7 && lane == 0 && cnt < ocap) {
+        o7[cnt] = s.x;
+        o7[os + cnt] = s.y;
+        o7[2 * os + cnt] = rpp::angle_mod_pi(s.yaw);   // :1540
+        o7[3 * os + cnt] = s.v;
+        o7[4 * os + cnt] = time;
+        o7[5 * os + cnt] = ai;
+        o7[6 * os + cnt] = di;
+      }
+      if (ob) {
+        const double dx = obx - s.x, dy = oby - s.y;
+        if (dx * dx + dy * dy <= obt) hit = 1;
+      }
+      vsum = vsum + rpp::dabs(s.v);
+      last_yaw = s.yaw;
+      tlast = time;
+      cnt++;
+    };
+    // calc_target_index :1286-1293: the lanes share the np.hypot scan; first minimum, lowest index
+    auto scan = [&](double* dis) {
+      double best = rpp::dinf();
+      int bi = 0x7fffffff;
+      for (int i = lane; i < n; i += TPB) {
+        const double d = rpp_glibc_hypot(s.x - cx[i], s.y - cy[i]);
+        if (d < best) {
+          best = d;
+          bi = i;
+        }
+      }
+      rppr::wave_argmin(best, bi);
+      *dis = best;
+      return bi == 0x7fffffff ? 0 : bi;
+    };
+    append(0.0, 0.0);
+    double dis;
+    int target_ind = lookahead(cx, cy, n, scan(&dis), P.Lf);
+    while (P.T >= time && cnt < MAX_STEPS) {
+      const int ind0 = scan(&dis);
+      double ai, di;
+      if (step(s, target_ind, time, cx, cy, lsp, n, ind0, dis, gx, gy, P, &ai, &di, &ood)) {
+        reached = 1;
+        break;
+      }
+      append(ai, di);
+      if (ood) break;
+    }
+    r.n = cnt;
+    r.tlast = tlast;
+    r.ood = ood ? 1 : 0;
+    const int any_hit = __ballot(hit) != 0ULL;
+    judge(&r, reached, rpp::angle_mod_pi(last_yaw), gyaw, vsum, origin_travel(cx, cy, n), any_hit, P);
+  }
+}
+
 // store = 0: jobs are (instance, candidate), counters[0] of them, records written; store = 1: jobs are the winners
 // (counters[2] of them), arrays written
 __global__ __launch_bounds__(TPB) void track_roll_kernel(TrackArgs a, int store) {
@@ -150,9 +232,8 @@ __global__ __launch_bounds__(TPB) void track_roll_kernel(TrackArgs a, int store)
     for (int nd = node; a.parent[off + nd] >= 0 && depth <= (int)a.stride; nd = a.parent[off + nd], depth++) total += a.plen[off + nd];
     if (total + EXT_MAX > SLAB_PTS || depth > (int)a.stride) r.ood = 3;
     if (total < 3) r.ood = 2;   // cy[-3] :1435 raises IndexError
-    int n = total;
-    double *cx = gcx, *cy = gcy;
     if (!r.ood) {
+      double *cx = gcx, *cy = gcy;
       if (total + EXT_MAX <= LDS_PTS) {
         cx = lcx;
         cy = lcy;
@@ -179,18 +260,6 @@ __global__ __launch_bounds__(TPB) void track_roll_kernel(TrackArgs a, int store)
         cy[total - 1] = I->goal[1];
         gcw[total - 1] = I->goal[2];
       }
-      __syncthreads();
-      if (lane == 0) s_n = extend_path(cx, cy, gcw, total, P);
-      __syncthreads();
-      n = s_n;
-      if (n < 0) r.ood = 1;
-    }
-    if (!r.ood) {
-      for (int i = lane; i < n - 1; i += TPB) lsp[i] = (signed char)segment_flags(cx, cy, gcw, i);
-      __syncthreads();
-      if (lane == 0) stop_points(lsp, n);
-      __syncthreads();
-      // ---- closed_loop_prediction :1307-1372
       const double gx = I->goal[0], gy = I->goal[1], gyaw = I->goal[2];
       const int m = I->obs_m;
       double obx = 0.0, oby = 0.0, obt = -1.0;
@@ -206,68 +275,103 @@ __global__ __launch_bounds__(TPB) void track_roll_kernel(TrackArgs a, int store)
         o7 = a.out + a.out_off[inst];
       }
       const int64_t os = (int64_t)ocap + 1;
-      State s = {-0.0, -0.0, 0.0, 0.0};
-      double time = 0.0, vsum = 0.0, last_yaw = 0.0, tlast = 0.0;
-      int cnt = 0, hit = 0, ood = 0, reached = 0;
-      auto append = [&](double ai, double di) {
-        if (o7 && lane == 0 && cnt < ocap) {
-          o7[cnt] = s.x;
-          o7[os + cnt] = s.y;
-          o7[2 * os + cnt] = rpp::angle_mod_pi(s.yaw);   // :1540
-          o7[3 * os + cnt] = s.v;
-          o7[4 * os + cnt] = time;
-          o7[5 * os + cnt] = ai;
-          o7[6 * os + cnt] = di;
-        }
-        if (lane < m) {
-          const double dx = obx - s.x, dy = oby - s.y;
-          if (dx * dx + dy * dy <= obt) hit = 1;
-        }
-        vsum = vsum + rpp::dabs(s.v);
-        last_yaw = s.yaw;
-        tlast = time;
-        cnt++;
-      };
-      // calc_target_index :1286-1293: the lanes share the np.hypot scan; first minimum, lowest index
-      auto scan = [&](double* dis) {
-        double best = rpp::dinf();
-        int bi = 0x7fffffff;
-        for (int i = lane; i < n; i += TPB) {
-          const double d = rpp_glibc_hypot(s.x - cx[i], s.y - cy[i]);
-          if (d < best) {
-            best = d;
-            bi = i;
-          }
-        }
-        rppr::wave_argmin(best, bi);
-        *dis = best;
-        return bi == 0x7fffffff ? 0 : bi;
-      };
-      append(0.0, 0.0);
-      double dis;
-      int target_ind = lookahead(cx, cy, n, scan(&dis), P.Lf);
-      while (P.T >= time && cnt < MAX_STEPS) {
-        const int ind0 = scan(&dis);
-        double ai, di;
-        if (step(s, target_ind, time, cx, cy, lsp, n, ind0, dis, gx, gy, P, &ai, &di, &ood)) {
-          reached = 1;
-          break;
-        }
-        append(ai, di);
-        if (ood) break;
-      }
-      r.n = cnt;
-      r.tlast = tlast;
-      r.ood = ood ? 1 : 0;
-      const int any_hit = __ballot(hit) != 0ULL;
-      judge(&r, reached, rpp::angle_mod_pi(last_yaw), gyaw, vsum, origin_travel(cx, cy, n), any_hit, P);
-      if (o7 && lane == 0 && r.find && cnt == ocap) {   // :1519-1521: the goal pose behind x, y, yaw only
-        o7[cnt] = gx;
-        o7[os + cnt] = gy;
-        o7[2 * os + cnt] = gyaw;
+      const State s0 = {-0.0, -0.0, 0.0, 0.0};
+      roll_course(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, os, r);
+      if (o7 && lane == 0 && r.find && r.n == ocap) {   // :1519-1521: the goal pose behind x, y, yaw only
+        o7[r.n] = gx;
+        o7[os + r.n] = gy;
+        o7[2 * os + r.n] = gyaw;
       }
     }
     if (!store && lane == 0) a.rec[off + k] = r;
+  }
+}
+
+// ---- courses given as data (rrtx_tracker_run): the same roll-out on CSR courses of the caller ----------------------------
+struct CourseArgs {
+  int64_t n;                   // courses
+  const int64_t* off;          // [n + 1] CSR into x / y / yaw, driving order
+  const double *x, *y, *yaw;
+  const double* per_course;    // nullptr, or [n][3]: target_speed, yaw_th, invalid_travel_ratio
+  const double* start;         // nullptr, or [n][4]: x, y, yaw, v
+  const double *ox, *oy;       // obstacle rows
+  const double* othr;          // (radius + robot_radius) ** 2: row obs index + course * thr_stride
+  const int64_t* obs_off;      // nullptr (every course tests rows 0 .. m_shared - 1), or [n + 1] CSR into the rows
+  int64_t thr_stride;          // m_shared when one list is shared and robot_radius is per course, else 0
+  int32_t m_shared;
+  Params P;
+  Record* rec;                 // [n]
+  int32_t* counter;            // queue head
+  double* slab;                // [block][3][SLAB_PTS]
+  double* out;                 // store = 1: seven arrays of out_total doubles each, course i at arr_off[i], rec[i].n entries
+  const int64_t* arr_off;
+  int64_t out_total;
+};
+
+// store = 0: one Record per course; store = 1: every course whose record has ood == 0 is rolled out again and its seven
+// arrays are stored.  A course of fewer than 3 points reports ood = 2, one of more than SLAB_PTS - EXT_MAX points ood = 3.
+__global__ __launch_bounds__(TPB) void track_courses_kernel(CourseArgs a, int store) {
+  __shared__ double lcx[LDS_PTS], lcy[LDS_PTS];
+  __shared__ signed char lsp[SLAB_PTS];
+  __shared__ int32_t s_job, s_n;
+  const int lane = threadIdx.x;
+  double* gcx = a.slab + (int64_t)blockIdx.x * 3 * SLAB_PTS;
+  double* gcy = gcx + SLAB_PTS;
+  double* gcw = gcy + SLAB_PTS;
+  for (;;) {
+    __syncthreads();
+    if (lane == 0) s_job = atomicAdd(a.counter, 1);
+    __syncthreads();
+    const int64_t c = s_job;
+    if (c >= a.n) break;
+    if (store && a.rec[c].ood) continue;
+    Record r = {0, 0, 0, 0, 0.0};
+    const int64_t b = a.off[c], len = a.off[c + 1] - b;
+    if (len + EXT_MAX > SLAB_PTS) r.ood = 3;
+    if (len < 3) r.ood = 2;   // cy[-3] :1435 raises IndexError
+    if (!r.ood) {
+      const int total = (int)len;
+      double *cx = gcx, *cy = gcy;
+      if (total + EXT_MAX <= LDS_PTS) {
+        cx = lcx;
+        cy = lcy;
+      }
+      for (int q = lane; q < total; q += TPB) {
+        cx[q] = a.x[b + q];
+        cy[q] = a.y[b + q];
+        gcw[q] = a.yaw[b + q];
+      }
+      const double gx = a.x[b + total - 1], gy = a.y[b + total - 1], gyaw = a.yaw[b + total - 1];   // :1531
+      Params P = a.P;
+      if (a.per_course) {
+        P.target_speed = a.per_course[3 * c];
+        P.yaw_th = a.per_course[3 * c + 1];
+        P.invalid_travel_ratio = a.per_course[3 * c + 2];
+      }
+      State s0 = {-0.0, -0.0, 0.0, 0.0};   // :1309
+      if (a.start) {
+        s0.x = a.start[4 * c];
+        s0.y = a.start[4 * c + 1];
+        s0.yaw = a.start[4 * c + 2];
+        s0.v = a.start[4 * c + 3];
+      }
+      const int64_t ob = a.obs_off ? a.obs_off[c] : 0;
+      const int m = a.obs_off ? (int)(a.obs_off[c + 1] - ob) : a.m_shared;
+      double obx = 0.0, oby = 0.0, obt = -1.0;
+      if (lane < m) {
+        obx = a.ox[ob + lane];
+        oby = a.oy[ob + lane];
+        obt = a.othr[ob + c * a.thr_stride + lane];
+      }
+      double* o7 = nullptr;
+      int ocap = 0;
+      if (store) {
+        ocap = a.rec[c].n;
+        o7 = a.out + a.arr_off[c];
+      }
+      roll_course(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, a.out_total, r);
+    }
+    if (!store && lane == 0) a.rec[c] = r;
   }
 }
 

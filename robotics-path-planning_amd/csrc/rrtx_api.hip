@@ -2429,3 +2429,321 @@ int rrtx_steer_get_kernel_ms(rrtx_steer* s, double* kernel_ms) {
 }
 
 }  // extern "C"
+
+// ---- batched closed-loop tracking of courses given as data (rrt_track.hip.h, track_courses_kernel) ------------------------
+struct rrtx_tracker {
+  int device = 0;
+  bool usable = false;        // a gfx950 device was found at creation
+  int n_cu = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  std::string err;
+  // device buffers, grown on demand
+  struct Buf {
+    void* p = nullptr;
+    size_t bytes = 0;
+  };
+  Buf off, x, y, yaw, per_course, start, ox, oy, othr, obs_off, rec, counter, slab, out, arr_off;
+  // the last run
+  bool ran = false, has_arrays = false;
+  int64_t n = 0, n_steps = 0;
+  double kernel_ms = 0.0;
+  std::vector<rppt::Record> h_rec;
+  std::vector<int64_t> h_arr_off;
+};
+
+namespace {
+thread_local std::string tracker_null_err;
+
+int tracker_fail(rrtx_tracker* t, int rc, const std::string& msg) {
+  (t ? t->err : tracker_null_err) = msg;
+  return rc;
+}
+#define TRACKCHK(t, expr)                                                                      \
+  do {                                                                                         \
+    hipError_t e_ = (expr);                                                                    \
+    if (e_ != hipSuccess) return tracker_fail(t, RRTX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+// at least `bytes` in b; contents are not kept
+int tracker_reserve(rrtx_tracker* t, rrtx_tracker::Buf& b, size_t bytes) {
+  if (bytes <= b.bytes) return RRTX_OK;
+  if (b.p) hipFree(b.p);
+  b.p = nullptr;
+  b.bytes = 0;
+  TRACKCHK(t, hipMalloc(&b.p, bytes));
+  b.bytes = bytes;
+  return RRTX_OK;
+}
+
+// `bytes` of host data into b (grown as needed), queued on the tracker's stream
+int tracker_upload(rrtx_tracker* t, rrtx_tracker::Buf& b, const void* src, size_t bytes) {
+  if (!bytes) return RRTX_OK;
+  int rc = tracker_reserve(t, b, bytes);
+  if (rc) return rc;
+  TRACKCHK(t, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, t->stream));
+  return RRTX_OK;
+}
+
+bool all_finite(const double* v, int64_t count) {
+  for (int64_t i = 0; i < count; i++)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+
+// starts at 0 and never decreases
+bool csr_ok(const int64_t* off, int64_t n) {
+  if (off[0] != 0) return false;
+  for (int64_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) return false;
+  return true;
+}
+}  // namespace
+
+extern "C" {
+
+int rrtx_tracker_create(int32_t device, rrtx_tracker** out) {
+  if (!out) return tracker_fail(nullptr, RRTX_E_INVALID, "rrtx_tracker_create: out is NULL");
+  *out = nullptr;
+  if (device < 0) return tracker_fail(nullptr, RRTX_E_INVALID, "rrtx_tracker_create: negative device ordinal");
+  rrtx_tracker* t = new (std::nothrow) rrtx_tracker();
+  if (!t) return tracker_fail(nullptr, RRTX_E_HIP, "rrtx_tracker_create: out of host memory");
+  t->device = device;
+  *out = t;   // returned on failure too: the caller reads the message, and runs still check their arguments
+  int ndev = 0;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device >= ndev ||
+      hipGetDeviceProperties(&prop, device) != hipSuccess ||
+      (!strstr(prop.gcnArchName, "gfx950") && !getenv("RRTX_ALLOW_ANY_ARCH")))
+    return tracker_fail(t, RRTX_E_NO_DEVICE, "rrtx_tracker_create: no usable gfx950 device (there is no CPU fallback)");
+  t->n_cu = prop.multiProcessorCount;
+  TRACKCHK(t, hipSetDevice(device));
+  TRACKCHK(t, hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+  for (auto& e : t->ev) TRACKCHK(t, hipEventCreate(&e));
+  t->usable = true;
+  return RRTX_OK;
+}
+
+void rrtx_tracker_destroy(rrtx_tracker* t) {
+  if (!t) return;
+  if (t->usable) {
+    hipSetDevice(t->device);
+    for (rrtx_tracker::Buf* b : {&t->off, &t->x, &t->y, &t->yaw, &t->per_course, &t->start, &t->ox, &t->oy, &t->othr,
+                                 &t->obs_off, &t->rec, &t->counter, &t->slab, &t->out, &t->arr_off})
+      if (b->p) hipFree(b->p);
+    for (auto& e : t->ev)
+      if (e) hipEventDestroy(e);
+    if (t->stream) hipStreamDestroy(t->stream);
+  }
+  delete t;
+}
+
+const char* rrtx_tracker_last_error(rrtx_tracker* t) { return t ? t->err.c_str() : tracker_null_err.c_str(); }
+
+static int tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_batch* b) {
+  const char* fn = "rrtx_tracker_run: ";
+  auto bad = [&](const char* m) { return tracker_fail(t, RRTX_E_INVALID, std::string(fn) + m); };
+  if (!t) return bad("the tracker is NULL");
+  if (!tp || !b) return bad("the parameters or the batch is NULL");
+  if (b->n < 0 || b->n > (1LL << 30)) return bad("n is negative or above 2^30");
+  if (!b->offsets || !b->robot_radius) return bad("offsets or robot_radius is NULL");
+  const int64_t n = b->n;
+  if (!csr_ok(b->offsets, n)) return bad("offsets do not start at 0 or decrease");
+  const int64_t pts = b->offsets[n];
+  if (pts > 0x7fffffffLL) return bad("more than 2^31 - 1 points in all");
+  if (pts > 0 && (!b->x || !b->y || !b->yaw)) return bad("x, y or yaw is NULL");
+  if (b->n_obstacles < 0) return bad("n_obstacles is negative");
+  if (b->n_obstacles > 0 && !b->obstacles) return bad("obstacles is NULL");
+  if (b->obs_offsets) {
+    if (!csr_ok(b->obs_offsets, n)) return bad("obs_offsets do not start at 0 or decrease");
+    if (b->obs_offsets[n] > b->n_obstacles) return bad("obs_offsets end beyond n_obstacles");
+    for (int64_t i = 0; i < n; i++)
+      if (b->obs_offsets[i + 1] - b->obs_offsets[i] > rppt::TPB) return bad("more than 64 obstacles in one list");
+  } else if (b->n_obstacles > rppt::TPB) {
+    return bad("more than 64 obstacles in one list");
+  }
+  if (!(tp->dt > 0.0) || !(tp->T >= 0.0) || !(tp->T / tp->dt <= 1.0e6) || !(tp->Lf > 0.0) || !(tp->L > 0.0) ||
+      !(tp->steer_max >= 0.0 && tp->steer_max <= 0.79))
+    return bad("needs dt > 0, T / dt <= 1e6, Lf > 0, L > 0, 0 <= steer_max <= 0.79");
+  const int64_t n_rr = b->robot_radius_per_course ? n : 1;
+  if (!all_finite(b->x, pts) || !all_finite(b->y, pts) || !all_finite(b->yaw, pts)) return bad("a pose component is not finite");
+  if (!all_finite(b->obstacles, 3 * b->n_obstacles)) return bad("an obstacle component is not finite");
+  if (!all_finite(b->robot_radius, n_rr)) return bad("a robot radius is not finite");
+  if (b->start_state && !all_finite(b->start_state, 4 * n)) return bad("a start state component is not finite");
+  if (b->per_course && !all_finite(b->per_course, 3 * n)) return bad("a per-course value is not finite");
+  if (!all_finite(&tp->target_speed, sizeof(*tp) / sizeof(double))) return bad("a parameter is not finite");
+  if (!t->usable) return tracker_fail(t, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+
+  t->ran = false;
+  t->has_arrays = false;
+  t->n = n;
+  t->n_steps = 0;
+  t->kernel_ms = 0.0;
+  t->h_rec.clear();
+  t->h_arr_off.assign((size_t)n + 1, 0);
+  if (n == 0) {
+    t->has_arrays = b->want_arrays != 0;
+    t->ran = true;
+    return RRTX_OK;
+  }
+  // obstacle table: SoA x, y and the thresholds (radius + robot_radius) ** 2 by the planners' routine; one threshold row per
+  // obstacle row, or with one shared list and a radius per course n rows of the list's thresholds
+  const int64_t rows = b->obs_offsets ? b->obs_offsets[n] : b->n_obstacles;
+  const bool thr_per_course = !b->obs_offsets && b->robot_radius_per_course && rows > 0;
+  std::vector<double> ox((size_t)rows), oy((size_t)rows), othr((size_t)(thr_per_course ? rows * n : rows));
+  for (int64_t k = 0; k < rows; k++) {
+    ox[k] = b->obstacles[3 * k];
+    oy[k] = b->obstacles[3 * k + 1];
+  }
+  if (b->obs_offsets) {
+    for (int64_t i = 0; i < n; i++)
+      for (int64_t k = b->obs_offsets[i]; k < b->obs_offsets[i + 1]; k++)
+        othr[k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[b->robot_radius_per_course ? i : 0]);
+  } else if (thr_per_course) {
+    for (int64_t i = 0; i < n; i++)
+      for (int64_t k = 0; k < rows; k++) othr[i * rows + k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[i]);
+  } else {
+    for (int64_t k = 0; k < rows; k++) othr[k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[0]);
+  }
+
+  TRACKCHK(t, hipSetDevice(t->device));
+  int rc;
+  const size_t N = (size_t)n;
+  const int64_t want = (int64_t)t->n_cu * 16;   // 16 blocks of one wave per CU, as track_roll_kernel
+  int blocks = (int)(n < want ? n : want);
+  if (blocks < 1) blocks = 1;
+  if ((rc = tracker_upload(t, t->off, b->offsets, sizeof(int64_t) * (N + 1)))) return rc;
+  if ((rc = tracker_upload(t, t->x, b->x, sizeof(double) * (size_t)pts))) return rc;
+  if ((rc = tracker_upload(t, t->y, b->y, sizeof(double) * (size_t)pts))) return rc;
+  if ((rc = tracker_upload(t, t->yaw, b->yaw, sizeof(double) * (size_t)pts))) return rc;
+  if (b->per_course && (rc = tracker_upload(t, t->per_course, b->per_course, sizeof(double) * 3 * N))) return rc;
+  if (b->start_state && (rc = tracker_upload(t, t->start, b->start_state, sizeof(double) * 4 * N))) return rc;
+  if ((rc = tracker_upload(t, t->ox, ox.data(), sizeof(double) * ox.size()))) return rc;
+  if ((rc = tracker_upload(t, t->oy, oy.data(), sizeof(double) * oy.size()))) return rc;
+  if ((rc = tracker_upload(t, t->othr, othr.data(), sizeof(double) * othr.size()))) return rc;
+  if (b->obs_offsets && (rc = tracker_upload(t, t->obs_off, b->obs_offsets, sizeof(int64_t) * (N + 1)))) return rc;
+  if ((rc = tracker_reserve(t, t->rec, sizeof(rppt::Record) * N))) return rc;
+  if ((rc = tracker_reserve(t, t->counter, sizeof(int32_t)))) return rc;
+  if ((rc = tracker_reserve(t, t->slab, sizeof(double) * (size_t)blocks * 3 * rppt::SLAB_PTS))) return rc;
+  TRACKCHK(t, hipMemsetAsync(t->counter.p, 0, sizeof(int32_t), t->stream));
+
+  rppt::CourseArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n;
+  a.off = (const int64_t*)t->off.p;
+  a.x = (const double*)t->x.p;
+  a.y = (const double*)t->y.p;
+  a.yaw = (const double*)t->yaw.p;
+  a.per_course = b->per_course ? (const double*)t->per_course.p : nullptr;
+  a.start = b->start_state ? (const double*)t->start.p : nullptr;
+  a.ox = (const double*)t->ox.p;
+  a.oy = (const double*)t->oy.p;
+  a.othr = (const double*)t->othr.p;
+  a.obs_off = b->obs_offsets ? (const int64_t*)t->obs_off.p : nullptr;
+  a.thr_stride = thr_per_course ? rows : 0;
+  a.m_shared = b->obs_offsets ? 0 : (int32_t)rows;
+  static_assert(sizeof(rppt::Params) == sizeof(rrtx_track_params), "rrtx_track_params mirrors rppt::Params");
+  static_assert(sizeof(rppt::Record) == sizeof(rrtx_track_record), "rrtx_track_record mirrors rppt::Record");
+  memcpy(&a.P, tp, sizeof(a.P));
+  a.rec = (rppt::Record*)t->rec.p;
+  a.counter = (int32_t*)t->counter.p;
+  a.slab = (double*)t->slab.p;
+
+  // first launch: the records
+  TRACKCHK(t, hipEventRecord(t->ev[0], t->stream));
+  hipLaunchKernelGGL(rppt::track_courses_kernel, dim3(blocks), dim3(rppt::TPB), 0, t->stream, a, 0);
+  TRACKCHK(t, hipGetLastError());
+  TRACKCHK(t, hipEventRecord(t->ev[1], t->stream));
+  t->h_rec.resize(N);
+  TRACKCHK(t, hipMemcpyAsync(t->h_rec.data(), t->rec.p, sizeof(rppt::Record) * N, hipMemcpyDeviceToHost, t->stream));
+  TRACKCHK(t, hipStreamSynchronize(t->stream));
+  float ms = 0.f;
+  TRACKCHK(t, hipEventElapsedTime(&ms, t->ev[0], t->ev[1]));
+  t->kernel_ms = ms;
+
+  // arr_offsets: exclusive sum of len over the complete courses
+  int64_t tot = 0;
+  bool partial = false;
+  for (size_t i = 0; i < N; i++) {
+    t->h_arr_off[i] = tot;
+    if (t->h_rec[i].ood)
+      partial = true;
+    else
+      tot += t->h_rec[i].n;
+  }
+  t->h_arr_off[N] = tot;
+  t->n_steps = tot;
+
+  if (b->want_arrays) {
+    if (tot > 0) {
+      if ((rc = tracker_reserve(t, t->out, sizeof(double) * 7 * (size_t)tot))) return rc;
+      if ((rc = tracker_upload(t, t->arr_off, t->h_arr_off.data(), sizeof(int64_t) * (N + 1)))) return rc;
+      TRACKCHK(t, hipMemsetAsync(t->counter.p, 0, sizeof(int32_t), t->stream));
+      a.out = (double*)t->out.p;
+      a.arr_off = (const int64_t*)t->arr_off.p;
+      a.out_total = tot;
+      TRACKCHK(t, hipEventRecord(t->ev[2], t->stream));
+      hipLaunchKernelGGL(rppt::track_courses_kernel, dim3(blocks), dim3(rppt::TPB), 0, t->stream, a, 1);
+      TRACKCHK(t, hipGetLastError());
+      TRACKCHK(t, hipEventRecord(t->ev[3], t->stream));
+      TRACKCHK(t, hipStreamSynchronize(t->stream));
+      TRACKCHK(t, hipEventElapsedTime(&ms, t->ev[2], t->ev[3]));
+      t->kernel_ms += ms;
+    }
+    t->has_arrays = true;
+  }
+  t->ran = true;
+  if (partial) {
+    t->err = std::string(fn) + "some courses are too short, too long or left the replica's domain (see the ood column)";
+    return RRTX_PARTIAL;
+  }
+  return RRTX_OK;
+}
+
+int rrtx_tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_batch* b) {
+  try {   // host allocations (records, offsets, messages) must not throw across the ABI
+    return tracker_run(t, tp, b);
+  } catch (const std::exception& e) {
+    if (t) t->ran = false;
+    return tracker_fail(t, RRTX_E_HIP, std::string("rrtx_tracker_run: ") + e.what());
+  }
+}
+
+int rrtx_tracker_get_counts(rrtx_tracker* t, int64_t* n_courses, int64_t* n_steps) {
+  if (!t || !n_courses || !n_steps) return tracker_fail(t, RRTX_E_INVALID, "rrtx_tracker_get_counts: a NULL pointer");
+  if (!t->ran) return tracker_fail(t, RRTX_E_STATE, "rrtx_tracker_get_counts: no completed run");
+  *n_courses = t->n;
+  *n_steps = t->n_steps;
+  return RRTX_OK;
+}
+
+int rrtx_tracker_get_records(rrtx_tracker* t, rrtx_track_record* rec, int64_t* arr_offsets) {
+  if (!t || !rec) return tracker_fail(t, RRTX_E_INVALID, "rrtx_tracker_get_records: a NULL pointer");
+  if (!t->ran) return tracker_fail(t, RRTX_E_STATE, "rrtx_tracker_get_records: no completed run");
+  if (t->n) memcpy(rec, t->h_rec.data(), sizeof(rrtx_track_record) * (size_t)t->n);
+  if (arr_offsets) memcpy(arr_offsets, t->h_arr_off.data(), sizeof(int64_t) * ((size_t)t->n + 1));
+  return RRTX_OK;
+}
+
+int rrtx_tracker_get_arrays(rrtx_tracker* t, double* x, double* y, double* yaw, double* v, double* tt, double* a, double* d,
+                            int64_t cap) {
+  if (!t) return tracker_fail(t, RRTX_E_INVALID, "rrtx_tracker_get_arrays: the tracker is NULL");
+  if (!t->ran || !t->has_arrays) return tracker_fail(t, RRTX_E_STATE, "rrtx_tracker_get_arrays: no completed run with arrays");
+  if (cap < t->n_steps) return tracker_fail(t, RRTX_E_CAPACITY, "rrtx_tracker_get_arrays: the buffers are too small");
+  if (t->n_steps == 0) return RRTX_OK;
+  const size_t tot = (size_t)t->n_steps;
+  TRACKCHK(t, hipSetDevice(t->device));
+  double* dst[7] = {x, y, yaw, v, tt, a, d};
+  for (int k = 0; k < 7; k++)
+    if (dst[k]) TRACKCHK(t, hipMemcpy(dst[k], (const double*)t->out.p + k * tot, sizeof(double) * tot, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+int rrtx_tracker_get_kernel_ms(rrtx_tracker* t, double* kernel_ms) {
+  if (!t || !kernel_ms) return tracker_fail(t, RRTX_E_INVALID, "rrtx_tracker_get_kernel_ms: a NULL pointer");
+  if (!t->ran) return tracker_fail(t, RRTX_E_STATE, "rrtx_tracker_get_kernel_ms: no completed run");
+  *kernel_ms = t->kernel_ms;
+  return RRTX_OK;
+}
+
+}  // extern "C"

@@ -15,6 +15,7 @@ _pkg = importlib.import_module("robotics-path-planning_amd")
 _abi = _pkg._abi
 planner = importlib.import_module("robotics-path-planning_amd.planner")
 steer = importlib.import_module("robotics-path-planning_amd.steer")
+track = importlib.import_module("robotics-path-planning_amd.track")
 RRT = _pkg.RRT
 RRTStar = _pkg.RRTStar
 RRTSobol = _pkg.RRTSobol
@@ -30,6 +31,7 @@ ClosedLoopRRTStar = _pkg.ClosedLoopRRTStar
 informed_rotation = _pkg.informed_rotation
 BatchPlanner = _pkg.BatchPlanner
 BatchSteer = _pkg.BatchSteer
+BatchTrack = _pkg.BatchTrack
 Node = _pkg.Node
 AreaBounds = _pkg.AreaBounds
 get_path_length = _pkg.get_path_length
