@@ -7,9 +7,10 @@
 //
 // HBM layout per instance (SoA, stride `stride` nodes, padded with +inf so the
 // scans need no bounds checks):  x[], y[] f64 (the only arrays the scans read:
-// 16 B/node), cost[] f64, parent[] i32, first_child/next_sib/prev_sib i32 (child
-// lists = the identity scans of rrt_04:1369-1371 and :1381-1384 with integer
-// parents), hits[] / stack[] i32 scratch.
+// 16 B/node), cost[] f64, parent[] / prev_sib[] i32, kid[] (16-byte record Kid:
+// first child, next sibling, parent-edge length; child lists = the identity scans
+// of rrt_04:1369-1371 and :1381-1384 with integer parents), hits[] / stack[] i32
+// scratch.
 //
 // Per-iteration phases (reference: 10_path_planning_01_rrt_04_rrt_star.py)
 //   sample        lane 0, MT19937 / Sobol                     :1132-1153
@@ -75,10 +76,27 @@ struct Inst {  // persistent per-instance state (global memory)
 #define PH_STORE(I) do { } while (0)
 #endif
 
+// What a tree walk reads of a node, in one 16-byte record (four to a 64-byte line): its first child, its next sibling
+// and elen = hypot(node - its parent), exactly the value calc_new_cost (rrt_04:1375-1377) would compute now.  elen is
+// kept by the rrt_04 iteration kernel only (Ctx::has_elen), so cost propagation needs no coordinates and no hypot.
+struct alignas(16) Kid {
+  int32_t first_child, next_sib;
+  double elen;
+};
+static_assert(sizeof(Kid) == 16 && alignof(Kid) == 16, "one node record is one aligned 16-byte load");
+// Head of a grid cell (Ctx::ghead): entry count and the number (+1, 0: none) of its overflow block
+struct alignas(8) GHead {
+  int32_t cnt, blk;
+};
+static_assert(sizeof(GHead) == 8 && alignof(GHead) == 8, "one cell head is one aligned 8-byte load");
+
 struct Ctx {
   Inst* inst;
   double *x, *y, *cost;
-  int32_t *parent, *first_child, *next_sib, *prev_sib, *hits, *stack;
+  int32_t *parent, *prev_sib;
+  Kid* kid;       // per node {first child, next sibling, parent-edge length}
+  GHead* ghead;   // per cell of the grid index (below) {entry count, overflow block}; nullptr: no index
+  int32_t *hits, *stack;
   int64_t stride;
   const double *ox, *oy, *othr;   // every instance's obstacle list, concatenated (Inst::obs_base / obs_m select one)
   const double* r2tab;
@@ -101,15 +119,11 @@ struct Ctx {
   double q_lo, q_inv, q_step, q_m;
   // partial re-plan (overflow retry, rrtx_api.hip): block b works on instance inst_map[b]; nullptr = identity
   const int32_t* inst_map;
-  // elen[i] = hypot(node i - its parent), exactly the value calc_new_cost (rrt_04:1375-1377) would compute now;
-  // kept by the v2 kernel so cost propagation needs no coordinates and no hypot
-  double* elen;
   // two iterations per streaming pass in the one-wave shape of the rrt_04 iteration kernel (rrt_star_v2_body.inc)
   int32_t spec2;
   // grid index of the 16-bit mirror, one-wave shape of the rrt_04 iteration kernel (rrt_star_v2_body.inc, "grid index"):
-  // square cells of 2^gsh grid steps, gn x gn of them (gcells per instance).  Per cell an entry count, GRID_CAP0 entries
-  // {node | xq << 32} and the number (+1, 0: none) of one overflow block of GRID_CAP1 entries from the instance's pool.
-  int32_t *gcnt, *gblk;
+  // square cells of 2^gsh grid steps, gn x gn of them (gcells per instance).  Per cell a head (ghead: entry count, number
+  // (+1, 0: none) of one overflow block of GRID_CAP1 entries from the instance's pool) and GRID_CAP0 entries {node | xq << 32}.
   uint64_t *gent, *gpool;
   int32_t gsh, gn, gcells, gpool_blocks;
   int32_t grid;       // 1: passes of trees of at least grid_min nodes are answered from the index (RRTX_GRID)
@@ -124,6 +138,10 @@ struct Ctx {
   // grid index of the same kernel and shape: a pass gathers the cells and entries of all its centres in one round trip each
   // (RRTX_GRID_MERGE; 0: centre after centre)
   int32_t grid_merge;
+  // 1: kid[].elen is kept current (plans of the rrt_04 iteration kernel; no other kernel reads or writes it).  The order
+  // of the members is part of the kernels' register budget: the launch context is loaded in aligned groups, and moving
+  // a member shifts the SGPR spill counts of all three shapes (tools/loop_spill_check.sh)
+  int32_t has_elen;
 };
 constexpr int GRID_CAP0 = 16, GRID_CAP1 = 16;
 
@@ -709,8 +727,7 @@ __device__ __forceinline__ void eval_edges_dual(const Ctx& c, int om, const doub
 // workgroup (values are order independent).  Frontiers live in LDS (Sh::cval); returns the
 // number of nodes rewritten, or -1 when a level outgrew the LDS frontier (caller falls back to the one-lane walk).
 __device__ __forceinline__ int propagate_bfs(const double* __restrict__ x, const double* __restrict__ y,
-                                             double* __restrict__ cost, const int32_t* __restrict__ first_child,
-                                             const int32_t* __restrict__ next_sib, int root, Sh& sh) {
+                                             double* __restrict__ cost, const Kid* __restrict__ kid, int root, Sh& sh) {
   int32_t* A = reinterpret_cast<int32_t*>(sh.cval);
   int32_t* Bf = A + FCAP;
   const int tid = threadIdx.x;
@@ -729,10 +746,10 @@ __device__ __forceinline__ int propagate_bfs(const double* __restrict__ x, const
     for (int i = tid; i < na; i += TPB) {
       const int p = A[i];
       const double cp = cost[p], xp = x[p], yp = y[p];
-      int ch = first_child[p];
+      int ch = kid[p].first_child;
       while (ch >= 0) {
         const double xc = x[ch], yc = y[ch];
-        const int nxs = next_sib[ch];
+        const int nxs = kid[ch].next_sib;
         cost[ch] = cp + rpp::py_hypot(xc - xp, yc - yp);   // calc_new_cost :1375-1377
         const int slot = atomicAdd(&sh.fb, 1);
         if (slot < FCAP)
@@ -776,14 +793,13 @@ __device__ __forceinline__ void first_min(int ne, Sh& sh, double& mn, int& sel) 
 
 // propagate_cost_to_leaves (rrt_04:1379-1384) from `root`, one lane, explicit stack.
 __device__ inline int propagate(double* __restrict__ x, double* __restrict__ y, double* __restrict__ cost,
-                                const int32_t* __restrict__ first_child, const int32_t* __restrict__ next_sib,
-                                int32_t* __restrict__ stack, int root) {
+                                const Kid* __restrict__ kid, int32_t* __restrict__ stack, int root) {
   int sp = 0, count = 0;
   stack[sp++] = root;
   while (sp) {
     const int p = stack[--sp];
     const double cp = cost[p], xp = x[p], yp = y[p];
-    for (int ch = first_child[p]; ch >= 0; ch = next_sib[ch]) {
+    for (int ch = kid[p].first_child; ch >= 0; ch = kid[ch].next_sib) {
       cost[ch] = cp + rpp::py_hypot(x[ch] - xp, y[ch] - yp);  // calc_new_cost :1375-1377
       stack[sp++] = ch;
       count++;
@@ -792,28 +808,26 @@ __device__ inline int propagate(double* __restrict__ x, double* __restrict__ y, 
   return count;
 }
 
-__device__ inline void link_child(int32_t* parent, int32_t* first_child, int32_t* next_sib, int32_t* prev_sib, int ch,
-                                  int par) {
+__device__ inline void link_child(int32_t* parent, Kid* kid, int32_t* prev_sib, int ch, int par) {
   parent[ch] = par;
   prev_sib[ch] = -1;
   if (par >= 0) {
-    const int f = first_child[par];
-    next_sib[ch] = f;
+    const int f = kid[par].first_child;
+    kid[ch].next_sib = f;
     if (f >= 0) prev_sib[f] = ch;
-    first_child[par] = ch;
+    kid[par].first_child = ch;
   } else {
-    next_sib[ch] = -1;
+    kid[ch].next_sib = -1;
   }
 }
-__device__ inline void unlink_child(int32_t* parent, int32_t* first_child, int32_t* next_sib, int32_t* prev_sib,
-                                    int ch) {
+__device__ inline void unlink_child(int32_t* parent, Kid* kid, int32_t* prev_sib, int ch) {
   const int par = parent[ch];
   if (par < 0) return;
-  const int pv = prev_sib[ch], nx = next_sib[ch];
+  const int pv = prev_sib[ch], nx = kid[ch].next_sib;
   if (pv >= 0)
-    next_sib[pv] = nx;
+    kid[pv].next_sib = nx;
   else
-    first_child[par] = nx;
+    kid[par].first_child = nx;
   if (nx >= 0) prev_sib[nx] = pv;
 }
 
@@ -829,8 +843,8 @@ __device__ inline void unlink_child(int32_t* parent, int32_t* first_child, int32
 // moves (stored over hits[], as candidate slot numbers).  Rare (needs a distance tie in the near set and an inexact
 // path_resolution); lane 0 walks, the whole workgroup builds the map.
 __device__ inline void rewire_raw_walk(const Ctx& c, int om, double* __restrict__ x, double* __restrict__ y,
-                                       double* __restrict__ cost, int32_t* parent, int32_t* first_child,
-                                       int32_t* next_sib, int32_t* prev_sib, int32_t* hits, int32_t* stack, int kraw,
+                                       double* __restrict__ cost, int32_t* parent, Kid* kid,
+                                       int32_t* prev_sib, int32_t* hits, int32_t* stack, int kraw,
                                        int nu, double nx, double ny, double r2, double wx, double wy, double wcost,
                                        int newidx, int es0, Sh& sh) {
   const int tid = threadIdx.x;
@@ -884,16 +898,16 @@ __device__ inline void rewire_raw_walk(const Ctx& c, int om, double* __restrict_
       for (int k = 0; k < om && ok; k++)
         if (rpp::edge_hits_obstacle(sh.edge[0], sh.ox[k], sh.oy[k], sh.othr[k])) ok = false;
       if (!ok) continue;
-      unlink_child(parent, first_child, next_sib, prev_sib, u);   // :1369-1371 (also when it already hangs under newidx)
+      unlink_child(parent, kid, prev_sib, u);   // :1369-1371 (also when it already hangs under newidx)
       if (sh.edge[0].ex != ux || sh.edge[0].ey != uy) {
         x[u] = sh.edge[0].ex;   // node_list[i] = edge_node :1372
         y[u] = sh.edge[0].ey;
         moved = 1;
       }
       cost[u] = ec;
-      link_child(parent, first_child, next_sib, prev_sib, u, newidx);
+      link_child(parent, kid, prev_sib, u, newidx);
       sh.flag++;
-      sh.sel += propagate(x, y, cost, first_child, next_sib, stack, u);   // :1373
+      sh.sel += propagate(x, y, cost, kid, stack, u);   // :1373
     }
     if (moved) sh.nvalid = 1;
   }
@@ -988,8 +1002,7 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
   double* __restrict__ y = c.y + off;
   double* __restrict__ cost = c.cost + off;
   int32_t* parent = c.parent + off;
-  int32_t* first_child = c.first_child + off;
-  int32_t* next_sib = c.next_sib + off;
+  Kid* kid = c.kid + off;
   int32_t* prev_sib = c.prev_sib + off;
   int32_t* hits = c.hits + off;
   int32_t* stack = c.stack + off;
@@ -1095,8 +1108,8 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
         x[n] = nx;
         y[n] = ny;
         cost[n] = 0.0;
-        first_child[n] = -1;
-        link_child(parent, first_child, next_sib, prev_sib, n, ni);
+        kid[n].first_child = -1;
+        link_child(parent, kid, prev_sib, n, ni);
       }
       n++;
       s_ab += 28;
@@ -1212,7 +1225,7 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
           sh.uex[e] = cost[sh.uidx[e]];       // current cost of the candidate (refreshed after every propagation)
         }
         if (tid == 0) {
-          first_child[newidx] = -1;
+          kid[newidx].first_child = -1;
           sh.flag = 0;    // rewires
           sh.sel = 0;     // propagated nodes
           sh.nvalid = 0;  // a node changed coordinates
@@ -1239,7 +1252,7 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
             break;
           }
           if (tid == 0) {
-            unlink_child(parent, first_child, next_sib, prev_sib, u);
+            unlink_child(parent, kid, prev_sib, u);
             if (!(sh.usafe[es] & 4)) {
               // steer(new -> node) did not snap onto the node: node_list[i] = edge_node moves it (:1372)
               rpp::steer(&sh.edge[0], wx, wy, x[u], y[u], rpp::dinf(), c.res);
@@ -1248,13 +1261,13 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
               sh.nvalid = 1;
             }
             cost[u] = sh.uval[es];
-            link_child(parent, first_child, next_sib, prev_sib, u, newidx);
+            link_child(parent, kid, prev_sib, u, newidx);
             sh.flag++;
           }
           __syncthreads();
-          int np = propagate_bfs(x, y, cost, first_child, next_sib, u, sh);   // :1373
+          int np = propagate_bfs(x, y, cost, kid, u, sh);   // :1373
           if (np < 0) {
-            if (tid == 0) sh.fcount = propagate(x, y, cost, first_child, next_sib, stack, u);
+            if (tid == 0) sh.fcount = propagate(x, y, cost, kid, stack, u);
             __syncthreads();
             np = sh.fcount;
           }
@@ -1264,14 +1277,14 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
           e0 = es + 1;
         }
         if (raw_from >= 0)
-          rewire_raw_walk(c, om, x, y, cost, parent, first_child, next_sib, prev_sib, hits, stack, kraw, nu, nx, ny, r2, wx,
+          rewire_raw_walk(c, om, x, y, cost, parent, kid, prev_sib, hits, stack, kraw, nu, nx, ny, r2, wx,
                           wy, wcost, newidx, raw_from, sh);
         if (tid == 0) {
           // append :1065
           x[newidx] = wx;
           y[newidx] = wy;
           cost[newidx] = wcost;
-          link_child(parent, first_child, next_sib, prev_sib, newidx, min_ind);
+          link_child(parent, kid, prev_sib, newidx, min_ind);
         }
         __syncthreads();
         PH(9);
@@ -1287,8 +1300,8 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
           x[n] = nx;
           y[n] = ny;
           cost[n] = sh.ncost;
-          first_child[n] = -1;
-          link_child(parent, first_child, next_sib, prev_sib, n, ni);
+          kid[n].first_child = -1;
+          link_child(parent, kid, prev_sib, n, ni);
         }
         n++;
         __syncthreads();
@@ -1406,11 +1419,11 @@ __global__ void rrt_root_kernel(Ctx c, int ninst) {
   // a start that lies exactly on the goal is the first such node (every goal sample then duplicates the ROOT)
   I->first_goal = (I->start[0] == I->goal[0] && I->start[1] == I->goal[1]) ? 0 : -1;
   I->goal_dups = 0;
-  if (c.elen) c.elen[off] = 0.0;
+  if (c.has_elen) c.kid[off].elen = 0.0;
   c.cost[off] = 0.0;
   c.parent[off] = -1;
-  c.first_child[off] = -1;
-  c.next_sib[off] = -1;
+  c.kid[off].first_child = -1;
+  c.kid[off].next_sib = -1;
   c.prev_sib[off] = -1;
   I->n = 1;
   I->it = 0;

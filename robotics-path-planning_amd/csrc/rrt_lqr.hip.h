@@ -5,7 +5,7 @@
 //   search_best_goal_node :1357-1369, generate_final_course :1194-1203.
 //
 // One 64-lane wave per planning instance (a workgroup of one wave: __syncthreads is a wave barrier).  The tree lives in
-// global memory as SoA: x, y, cost, parent, child lists (first_child / next_sib / prev_sib) and per node the endpoints of
+// global memory as SoA: x, y, cost, parent, child lists (the records kid[] and prev_sib) and per node the endpoints of
 // the edge that created its current entry (LqrArgs::ef: from x, from y, to x, to y -- the polyline is regenerated from
 // them, rpp_lqr.h; no polyline pool).  The obstacle tile sits in LDS.
 //
@@ -109,8 +109,7 @@ __global__ __launch_bounds__(TPB) void rrt_lqr_kernel(Ctx c, LqrArgs la, int ite
   double* __restrict__ y = c.y + off;
   double* __restrict__ cost = c.cost + off;
   int32_t* parent = c.parent + off;
-  int32_t* first_child = c.first_child + off;
-  int32_t* next_sib = c.next_sib + off;
+  rppk::Kid* kid = c.kid + off;
   int32_t* prev_sib = c.prev_sib + off;
   int32_t* queue = c.stack + off;
   double* ef = la.ef + 4 * off;
@@ -288,9 +287,9 @@ __global__ __launch_bounds__(TPB) void rrt_lqr_kernel(Ctx c, LqrArgs la, int ite
             ef[4 * nn + 1] = y[p];
             ef[4 * nn + 2] = ex;
             ef[4 * nn + 3] = ey;
-            first_child[nn] = -1;
+            kid[nn].first_child = -1;
             moved[nn] = 0;
-            rppk::link_child(parent, first_child, next_sib, prev_sib, nn, p);
+            rppk::link_child(parent, kid, prev_sib, nn, p);
           }
           n++;
           __syncthreads();
@@ -328,8 +327,8 @@ __global__ __launch_bounds__(TPB) void rrt_lqr_kernel(Ctx c, LqrArgs la, int ite
             const double ox0 = x[i], oy0 = y[i];
             __syncthreads();
             if (tid == 0) {
-              rppk::unlink_child(parent, first_child, next_sib, prev_sib, i);
-              rppk::link_child(parent, first_child, next_sib, prev_sib, i, nn);
+              rppk::unlink_child(parent, kid, prev_sib, i);
+              rppk::link_child(parent, kid, prev_sib, i, nn);
               x[i] = tx;
               y[i] = ty;
               cost[i] = ecost;
@@ -347,7 +346,7 @@ __global__ __launch_bounds__(TPB) void rrt_lqr_kernel(Ctx c, LqrArgs la, int ite
             while (head < tail) {
               for (int q = head + tid; q < tail; q += TPB) {
                 const int f = queue[q];
-                for (int ch = first_child[f]; ch >= 0; ch = next_sib[ch]) {
+                for (int ch = kid[f].first_child; ch >= 0; ch = kid[ch].next_sib) {
                   const rpp::LqrEdge e = edge(x[f], y[f], x[ch], y[ch], 0);
                   cost[ch] = e.ok ? cost[f] + e.len : rpp::dinf();
                   const int slot = atomicAdd(&sh.qtail, 1);

@@ -34,11 +34,11 @@ __device__ __forceinline__ void hit_at2q(const double* __restrict__ x, const dou
 }
 
 // Exact re-check (dx**2 + dy**2 <= r**2 with the reference's libm pow) + the `.index` de-dup of rrt_04:1337,
-// producing the candidate records.  cost / first_child of each distinct candidate are requested here and first
+// producing the candidate records.  cost / first child of each distinct candidate are requested here and first
 // used after the edge evaluation.
 __device__ __forceinline__ void build_candidates(const double* __restrict__ x, const double* __restrict__ y,
-                                                 const double* __restrict__ cost,
-                                                 const int32_t* __restrict__ first_child, double qx, double qy,
+                                                 const double* __restrict__ cost, const Kid* __restrict__ kid,
+                                                 double qx, double qy,
                                                  double thr_exact, const int32_t* hits, int kraw, Sh2& sh,
                                                  int& pend_p, double& pend_cost, int& pend_fc) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -132,10 +132,10 @@ __device__ __forceinline__ void build_candidates(const double* __restrict__ x, c
             // after the edge evaluation that does not need them
             pend_p = p;
             pend_cost = cost[idx];
-            pend_fc = first_child[idx];
+            pend_fc = kid[idx].first_child;
           } else {
             sh.ucur[p] = cost[idx];
-            sh.ufc[p] = first_child[idx];
+            sh.ufc[p] = kid[idx].first_child;
           }
         }
       }
@@ -215,10 +215,10 @@ __device__ __forceinline__ void build_candidates(const double* __restrict__ x, c
           // after the edge evaluation that does not need them
           pend_p = p;
           pend_cost = cost[idx];
-          pend_fc = first_child[idx];
+          pend_fc = kid[idx].first_child;
         } else {
           sh.ucur[p] = cost[idx];
-          sh.ufc[p] = first_child[idx];
+          sh.ufc[p] = kid[idx].first_child;
         }
       }
     }

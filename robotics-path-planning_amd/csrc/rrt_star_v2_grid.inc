@@ -8,8 +8,7 @@
 // Left out of the index: the exact goal duplicates (SURVEY R6; all at the goal's xq value with indices above first_goal,
 // `excl` of them), so the goal's cell stays small; a ball that reaches them counts them like the streaming pass does.
 struct GridS {
-  int32_t* cnt;     // [gcells] entries per cell
-  int32_t* blk;     // [gcells] overflow block + 1 (0: none)
+  GHead* head;      // [gcells] {entries per cell, overflow block + 1 (0: none)}: one 8-byte load
   uint64_t* ent;    // [gcells][GRID_CAP0] {node | xq << 32}
   uint64_t* pool;   // [pool_blocks][GRID_CAP1]
   int sh, gn, pool_blocks, pool_next, excl, min_n;
@@ -22,6 +21,8 @@ constexpr int GRID_CAP0 = rppk::GRID_CAP0, GRID_CAP1 = rppk::GRID_CAP1, GRID_CAP
 constexpr int GE = 4;   // entries per lane a window gathers: 256 at most
 static_assert(GRID_CAPT <= 64, "a cell's entries fit one wave");
 
+// a cell's head: count and overflow block in one 8-byte load
+__device__ __forceinline__ GHead ld_head(const GHead* p) { return *p; }
 __device__ __forceinline__ int grid_cell(const GridS& g, uint32_t q) {
   const uint32_t u = q ^ 0x80008000u;   // unsigned grid coordinates
   return (int)((u >> (16 + g.sh)) * (uint32_t)g.gn + ((u & 0xffffu) >> g.sh));
@@ -35,8 +36,7 @@ __device__ __forceinline__ void grid_build(GridS& g, const uint32_t* __restrict_
   const int lane = threadIdx.x & 63;
   const int cells = g.gn * g.gn;
   for (int i = lane; i < cells; i += 64) {
-    g.cnt[i] = 0;
-    g.blk[i] = 0;
+    g.head[i] = GHead{0, 0};
   }
   g.pool_next = 0;
   g.excl = 0;
@@ -49,18 +49,18 @@ __device__ __forceinline__ void grid_build(GridS& g, const uint32_t* __restrict_
     if (on && first_goal >= 0 && q == g.goal_q && i != first_goal && x[i] == gx && y[i] == gy) on = false;
     g.excl += __popcll(__ballot(i < n && !on));
     const int cell = grid_cell(g, q);
-    const int k = on ? atomicAdd(&g.cnt[cell], 1) : 0;
+    const int k = on ? atomicAdd(&g.head[cell].cnt, 1) : 0;
     const uint64_t nb = __ballot(on && k == GRID_CAP0);   // cells that need their overflow block now
     if (on && k == GRID_CAP0) {
       const int b = g.pool_next + __popcll(nb & lt_mask) + 1;
-      if (b <= g.pool_blocks) g.blk[cell] = b;
+      if (b <= g.pool_blocks) g.head[cell].blk = b;
     }
     g.pool_next += __popcll(nb);
     __threadfence();
     if (on && k < GRID_CAP0) {
       g.ent[(int64_t)cell * GRID_CAP0 + k] = grid_entry(i, q);
     } else if (on && k < GRID_CAPT) {
-      const int b = g.blk[cell];
+      const int b = g.head[cell].blk;
       if (b > 0) g.pool[(int64_t)(b - 1) * GRID_CAP1 + (k - GRID_CAP0)] = grid_entry(i, q);
     }
   }
@@ -72,8 +72,9 @@ __device__ __forceinline__ void grid_build(GridS& g, const uint32_t* __restrict_
 // counting: the passes that need it stream.
 __device__ __forceinline__ void grid_insert(GridS& g, int node, uint32_t q) {
   const int cell = grid_cell(g, q);
-  const int k = g.cnt[cell];
-  int b = g.blk[cell];
+  const GHead hd = ld_head(g.head + cell);
+  const int k = hd.cnt;
+  int b = hd.blk;
   const uint64_t e = grid_entry(node, q);
   if (k < GRID_CAP0) {
     if (threadIdx.x == 0) g.ent[(int64_t)cell * GRID_CAP0 + k] = e;
@@ -84,18 +85,18 @@ __device__ __forceinline__ void grid_insert(GridS& g, int node, uint32_t q) {
         return;
       }
       b = ++g.pool_next;
-      if (threadIdx.x == 0) g.blk[cell] = b;
     }
     if (threadIdx.x == 0) g.pool[(int64_t)(b - 1) * GRID_CAP1 + (k - GRID_CAP0)] = e;
   }
-  if (threadIdx.x == 0) g.cnt[cell] = k + 1;
+  if (threadIdx.x == 0) g.head[cell] = GHead{k + 1, b};
 }
 
 // Node `node`, at packed position q until now, leaves its cell: the cell's last entry takes its place.
 __device__ __forceinline__ void grid_remove(GridS& g, int node, uint32_t q) {
   const int lane = threadIdx.x & 63;
   const int cell = grid_cell(g, q);
-  const int k = g.cnt[cell], b = g.blk[cell];
+  const GHead hd = ld_head(g.head + cell);
+  const int k = hd.cnt, b = hd.blk;
   if (k > GRID_CAPT) {
     g.ok = 0;
     return;
@@ -112,7 +113,7 @@ __device__ __forceinline__ void grid_remove(GridS& g, int node, uint32_t q) {
   const int j = __ffsll((long long)m) - 1;
   const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)e, k - 1), hi = (uint32_t)__shfl((int)(uint32_t)(e >> 32), k - 1);
   if (lane == j) *p = (uint64_t)lo | ((uint64_t)hi << 32);
-  if (lane == 0) g.cnt[cell] = k - 1;
+  if (lane == 0) g.head[cell].cnt = k - 1;
 }
 
 // The tests of one centre on the entries the lanes hold for it (every other slot: d = 0xffffffff, ei = 0x7fffffff).
@@ -235,8 +236,9 @@ __device__ __forceinline__ bool grid_centre(const GridS& g, uint32_t cq, int rw,
     int cell = 0, cn = 0, cb = 0;
     if (lane < nc) {
       cell = (y0 + lane / nwx) * g.gn + x0 + lane % nwx;
-      cn = g.cnt[cell];
-      cb = g.blk[cell];
+      const GHead hd = ld_head(g.head + cell);
+      cn = hd.cnt;
+      cb = hd.blk;
     }
     if (__ballot(cn > GRID_CAPT) != 0ull) return false;
     int inc = cn;
@@ -323,8 +325,9 @@ __device__ __forceinline__ int grid_merged(const GridS& g, GCen (&ce)[NC], int32
   }
   if (npairs > 64) return -1;
   if (cid >= 0) {
-    cn = g.cnt[cell];
-    cb = g.blk[cell];
+    const GHead hd = ld_head(g.head + cell);
+    cn = hd.cnt;
+    cb = hd.blk;
   }
   if (__ballot(cn > GRID_CAPT) != 0ull) return 0;
   int inc = cn;

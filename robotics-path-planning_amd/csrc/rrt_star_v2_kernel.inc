@@ -81,12 +81,10 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   double* __restrict__ y = c.y + off;
   double* __restrict__ cost = c.cost + off;
   int32_t* parent = c.parent + off;
-  int32_t* first_child = c.first_child + off;
-  int32_t* next_sib = c.next_sib + off;
+  Kid* kid = c.kid + off;
   int32_t* prev_sib = c.prev_sib + off;
   int32_t* hits = c.hits + off;
   int32_t* stack = c.stack + off;
-  double* __restrict__ elen = c.elen + off;
   uint32_t* __restrict__ xq = c.xq + off;
   const double qm = c.q_m;
   const double qinv = c.q_inv;   // world -> grid units of the 16-bit mirror
@@ -125,8 +123,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   if constexpr (NW == 1) {
     if (c.grid) {
       const int64_t gi = (int64_t)inst;
-      gs.cnt = c.gcnt + gi * c.gcells;
-      gs.blk = c.gblk + gi * c.gcells;
+      gs.head = c.ghead + gi * c.gcells;
       gs.ent = c.gent + gi * c.gcells * GRID_CAP0;
       gs.pool = c.gpool + gi * c.gpool_blocks * GRID_CAP1;
       gs.sh = c.gsh;
@@ -638,7 +635,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       PH(4);
       int pend_p, pend_fc;
       double pend_cost;
-      build_candidates(x, y, cost, first_child, nx, ny, r2, hits, kraw, sh, pend_p, pend_cost, pend_fc);
+      build_candidates(x, y, cost, kid, nx, ny, r2, hits, kraw, sh, pend_p, pend_cost, pend_fc);
       PH(5);
       const int nu = sh.nu;
       int nvalid = sh.nvalid;
@@ -732,13 +729,13 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
             // stores of an earlier rewire of this iteration (sibling links, child lists) have reached L2
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             int par, pv, nxs;
-            sload3(parent + u, prev_sib + u, next_sib + u, par, pv, nxs);
+            sload3(parent + u, prev_sib + u, &kid[u].next_sib, par, pv, nxs);
             if (tid == 0) {
               // the identity re-pointing of :1369-1372 with integer links: leave the old parent's child list ...
               if (pv >= 0) {
-                next_sib[pv] = nxs;
+                kid[pv].next_sib = nxs;
               } else {
-                first_child[par] = nxs;
+                kid[par].first_child = nxs;
               }
               if (nxs >= 0) prev_sib[nxs] = pv;
             }
@@ -771,9 +768,9 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
                 sh.moved = (u == first_goal || was_on_goal || (sh.e0.ex == gx && sh.e0.ey == gy))
                                ? 3 : (sh.moved | 1);   // 3: the bookkeeping of nodes lying on the goal is void
                 // its own edge and its children's edges changed length
-                elen[u] = rpp::py_hypot(sh.e0.ex - wx, sh.e0.ey - wy);
-                for (int ch = sh.ufc[es]; ch >= 0; ch = next_sib[ch])
-                  elen[ch] = rpp::py_hypot(x[ch] - sh.e0.ex, y[ch] - sh.e0.ey);
+                kid[u].elen = rpp::py_hypot(sh.e0.ex - wx, sh.e0.ey - wy);
+                for (int ch = sh.ufc[es]; ch >= 0; ch = kid[ch].next_sib)
+                  kid[ch].elen = rpp::py_hypot(x[ch] - sh.e0.ex, y[ch] - sh.e0.ey);
               }
               if (NW == 1 && gs.ok) {   // the moved node changes cell (the index keeps it at the new xq[] value)
                 lds_barrier();
@@ -785,13 +782,13 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
             const double ec = sh.uval[es];
             const int root_fc = __builtin_amdgcn_readfirstlane(sh.ufc[es]);
             if (tid == 0) {
-              if (!moved_now) elen[u] = sh.uhyp[es];
+              if (!moved_now) kid[u].elen = sh.uhyp[es];
               cost[u] = ec;
               sh.ucur[es] = ec;
               // ... and become a child of the node about to be appended
               parent[u] = newidx;
               prev_sib[u] = -1;
-              next_sib[u] = sh.last_fc;
+              kid[u].next_sib = sh.last_fc;
               if (sh.last_fc >= 0) prev_sib[sh.last_fc] = u;
               sh.last_fc = u;
               sh.n_rw++;
@@ -799,12 +796,12 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
             if (moved_now) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the children's new elen
             PH(13);
             bool reread = false;
-            int np = propagate_scalar(cost, first_child, next_sib, elen, root_fc, ec, sh, my_uidx,   // :1373
+            int np = propagate_scalar(cost, kid, root_fc, ec, sh, my_uidx,   // :1373
                                       NW == 1 ? c.prop_vec : -1, NW == 1 ? c.prop_cap : (1 << 30), reread,
                                       (unsigned long long*)&I->phase[PROP_WALK_SLOT]);
             if (np < 0) {
               asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-              if (tid == 0) sh.fcount = rppk::propagate(x, y, cost, first_child, next_sib, stack, u);
+              if (tid == 0) sh.fcount = rppk::propagate(x, y, cost, kid, stack, u);
               np = sh.fcount;
               reread = true;
             }
@@ -826,15 +823,14 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
           y[newidx] = wy;
           xq[newidx] = rppk::quant16(c, wx, wy);
           cost[newidx] = wcost;
-          elen[newidx] = sh.uhyp[sel];   // == hypot(new - parent) from the position the node ends up at
-          first_child[newidx] = sh.last_fc;
-          // link under the chosen parent; its current first child is in the LDS record (kept current above)
+          // link under the chosen parent; its current first child is in the LDS record (kept current above).  The node's
+          // own record in one store; elen == hypot(new - parent) from the position the node ends up at
           const int f = sh.ufc[sel];
+          kid[newidx] = Kid{sh.last_fc, f, sh.uhyp[sel]};
           parent[newidx] = wparent;
           prev_sib[newidx] = -1;
-          next_sib[newidx] = f;
           if (f >= 0) prev_sib[f] = newidx;
-          first_child[wparent] = newidx;
+          kid[wparent].first_child = newidx;
         }
         // the index: an exact goal duplicate (first_goal >= 0 already) stays out of it, counted instead
         if (gs.ok) {
@@ -855,10 +851,10 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
           y[n] = ny;
           xq[n] = rppk::quant16(c, nx, ny);
           const double el = rpp::py_hypot(nx - nqx, ny - nqy);
-          elen[n] = el;
+          kid[n].elen = el;
           cost[n] = cost[ni] + el;   // :1054-1056
-          first_child[n] = -1;
-          rppk::link_child(parent, first_child, next_sib, prev_sib, n, ni);
+          kid[n].first_child = -1;
+          rppk::link_child(parent, kid, prev_sib, n, ni);
           sh.moved = 0;
         }
         if (gs.ok) {

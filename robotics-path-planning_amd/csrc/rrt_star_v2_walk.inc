@@ -19,23 +19,15 @@ __device__ __forceinline__ void sload3(const int32_t* pa, const int32_t* pb, con
   b = (int)rb;
   c = (int)rc;
 }
-// {next_sib, first_child, elen} of one node: one scalar round trip
-__device__ __forceinline__ void sload_node(const int32_t* next_sib, const int32_t* first_child, const double* elen,
-                                           int node, int& nxs, int& fcc, double& el) {
-  const int32_t* pa = next_sib + node;
-  const int32_t* pb = first_child + node;
-  const double* pc = elen + node;
-  uint32_t ra, rb;
-  uint64_t rc;
-  asm volatile(
-      "s_load_dword %0, %3, 0x0 glc\n\ts_load_dword %1, %4, 0x0 glc\n\ts_load_dwordx2 %2, %5, 0x0 glc\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&s"(ra), "=&s"(rb), "=&s"(rc)
-      : "s"(pa), "s"(pb), "s"(pc)
-      : "memory");
-  nxs = (int)ra;
-  fcc = (int)rb;
-  el = rpp::b2d(rc);
+// the record of one node: one scalar load, one round trip on one line
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void sload_node(const Kid* kid, int node, int& nxs, int& fcc, double& el) {
+  const Kid* p = kid + node;
+  v4u r;
+  asm volatile("s_load_dwordx4 %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=&s"(r) : "s"(p) : "memory");
+  fcc = (int)r.x;
+  nxs = (int)r.y;
+  el = rpp::b2d((uint64_t)r.z | ((uint64_t)r.w << 32));
 }
 
 constexpr int CE = (NU + 63) / 64;   // near candidates per lane when a wave holds the candidate list in registers
@@ -60,17 +52,16 @@ constexpr unsigned long long PROP_WALK_FULL = 1ull << 40;
 __device__ __forceinline__ int lanes_below(uint64_t m) {
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
-// The rest of a cost walk with one sibling chain per lane (one-wave shape).  Every round trip gathers {next_sib,
-// first_child, elen} of up to 64 nodes, one per lane: a node's first child continues its lane's chain (at the node's new
+// The rest of a cost walk with one sibling chain per lane (one-wave shape).  Every round trip gathers the records of
+// up to 64 nodes, one 16-byte load per lane: a node's first child continues its lane's chain (at the node's new
 // cost), its next sibling joins the LDS list of pending chains (at the parent's cost), and idle lanes take pending
 // chains at the start of each round.  The rounds are bounded by the height of the first-child / next-sibling tree, not
 // by the node count: in the long tail of propagations (thousands of nodes, DESIGN 5.2) that is several times fewer
 // round trips, each a dependent vector gather.  (cur, cp) and st[0, sp) are what the scalar walk left.  Returns the nodes
 // rewritten, or -1 when more than `cap` chains are pending.  Near candidates' LDS costs are not refreshed: the caller
 // re-reads them.
-__device__ __forceinline__ int propagate_lanes(double* __restrict__ cost, const int32_t* first_child,
-                                               const int32_t* next_sib, const double* elen, int cur, double cp,
-                                               Sh2& sh, int sp, int cap) {
+__device__ __forceinline__ int propagate_lanes(double* __restrict__ cost, const Kid* kid, int cur, double cp, Sh2& sh,
+                                               int sp, int cap) {
   const int lane = threadIdx.x & 63;
   WalkEnt* st = sh.u.walk;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // lane 0's stores of this rewire, before other lanes read
@@ -92,9 +83,10 @@ __device__ __forceinline__ int propagate_lanes(double* __restrict__ cost, const 
     int nxs = -1, fcc = -1;
     double el = 0.0;
     if (vn >= 0) {
-      nxs = next_sib[(uint32_t)vn];
-      fcc = first_child[(uint32_t)vn];
-      el = elen[(uint32_t)vn];
+      const Kid k = kid[(uint32_t)vn];
+      nxs = k.next_sib;
+      fcc = k.first_child;
+      el = k.elen;
     }
     const double vcp = sh.cval[lane];
     const double nc = vcp + el;   // calc_new_cost :1375-1377
@@ -124,9 +116,8 @@ __device__ __forceinline__ int propagate_lanes(double* __restrict__ cost, const 
 // `reread` tells the caller to refresh the later candidates' LDS costs from cost[].  Returns the nodes rewritten, or -1
 // when the sibling stack (LDS, at most cap entries) is full: the caller redoes the subtree with the global-stack walk
 // (recomputation is idempotent).
-__device__ __forceinline__ int propagate_scalar(double* __restrict__ cost, const int32_t* first_child,
-                                                const int32_t* next_sib, const double* elen, int root_fc,
-                                                double root_cost, Sh2& sh, const int (&my_uidx)[CE], int vec_after,
+__device__ __forceinline__ int propagate_scalar(double* __restrict__ cost, const Kid* kid, int root_fc, double root_cost,
+                                                Sh2& sh, const int (&my_uidx)[CE], int vec_after,
                                                 int cap, bool& reread, unsigned long long* walks) {
   WalkEnt* st = sh.u.walk;
   constexpr int CAP = 2 * FCAP * (int)(sizeof(Front) / sizeof(WalkEnt));
@@ -145,13 +136,13 @@ __device__ __forceinline__ int propagate_scalar(double* __restrict__ cost, const
     }
     if (vec_after >= 0 && cnt >= vec_after) {
       reread = true;
-      const int r = propagate_lanes(cost, first_child, next_sib, elen, cur, cp, sh, sp, cap);
+      const int r = propagate_lanes(cost, kid, cur, cp, sh, sp, cap);
       if (lane == 0) atomicAdd(walks, r < 0 ? PROP_WALK_FULL : 1ull);   // no return value: nothing waits on it
       return r < 0 ? -1 : cnt + r;
     }
     int nxs, fcc;
     double el;
-    sload_node(next_sib, first_child, elen, cur, nxs, fcc, el);
+    sload_node(kid, cur, nxs, fcc, el);
     const double nc = cp + el;   // calc_new_cost :1375-1377
     if (lane == 0) cost[cur] = nc;
 #pragma unroll

@@ -307,7 +307,7 @@ static void rrt_star_knobs(Ctx& c) {
   if (const char* e = getenv("RRTX_SPEC2")) c.spec2 = atoi(e) > 0 ? atoi(e) : 0;
   // rrt_04 kernel, one-wave shape: near and nearest queries from the grid index (RRTX_GRID=0: the streaming pass only);
   // below grid_min nodes a pass streams (RRTX_GRID_MIN: test knob, 0 = from the first node)
-  c.grid = c.gcnt != nullptr;
+  c.grid = c.ghead != nullptr;
   if (const char* e = getenv("RRTX_GRID")) c.grid = c.grid && atoi(e) != 0;
   c.grid_min = 4096;
   if (const char* e = getenv("RRTX_GRID_MIN")) c.grid_min = atoi(e) > 0 ? atoi(e) : 0;
@@ -425,8 +425,7 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
   if ((rc = dalloc(h, &c.y, tot))) return rc;
   if ((rc = dalloc(h, &c.cost, tot))) return rc;
   if ((rc = dalloc(h, &c.parent, tot))) return rc;
-  if ((rc = dalloc(h, &c.first_child, tot))) return rc;
-  if ((rc = dalloc(h, &c.next_sib, tot))) return rc;
+  if ((rc = dalloc(h, &c.kid, tot))) return rc;   // {first child, next sibling, parent-edge length} per node
   if ((rc = dalloc(h, &c.prev_sib, tot))) return rc;
   if ((rc = dalloc(h, &c.hits, tot))) return rc;
   if ((rc = dalloc(h, &c.stack, tot))) return rc;
@@ -436,7 +435,7 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
     if ((rc = dalloc(h, &c.yf, tot))) return rc;
   }
   if (p->algo == RRTX_ALGO_RRT_STAR && p->search_until_max_iter) {
-    if ((rc = dalloc(h, &c.elen, tot))) return rc;   // cached parent-edge lengths (cost propagation)
+    c.has_elen = 1;   // kid[].elen: cached parent-edge lengths (cost propagation)
     if ((rc = dalloc(h, &c.xq, tot))) return rc;     // 16-bit mirror (first stage of the streaming pass)
     // grid index of the mirror (DESIGN 5.1 "grid index"): cells sized for about 6 nodes each at the final tree size,
     // 512 grid steps at the least (128 x 128 cells); an overflow block per 128 nodes of capacity
@@ -447,8 +446,7 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
     c.gcells = c.gn * c.gn;
     c.gpool_blocks = (int32_t)(cap / 128 + 16);
     const size_t gc = (size_t)c.gcells * h->n_inst;
-    if ((rc = dalloc(h, &c.gcnt, gc))) return rc;
-    if ((rc = dalloc(h, &c.gblk, gc))) return rc;
+    if ((rc = dalloc(h, &c.ghead, gc))) return rc;
     if ((rc = dalloc(h, &c.gent, gc * rppk::GRID_CAP0))) return rc;
     if ((rc = dalloc(h, &c.gpool, (size_t)c.gpool_blocks * rppk::GRID_CAP1 * h->n_inst))) return rc;
   }
