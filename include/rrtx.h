@@ -26,7 +26,8 @@ extern "C" {
 #endif
 
 #define RRTX_ABI_VERSION 6   /* 6: rrtx_set_instance_obstacles (and RRTX_ALGO_LQR_RRT_STAR: a new algo value, no layout change; the rrtx_steer_* and
-                                rrtx_tracker_* entry points: new functions on objects of their own, no layout change); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
+                                rrtx_tracker_* entry points: new functions on objects of their own, no layout change; later additions of
+                                the same kind: rrtx_steer_set_obstacles, rrtx_steer_get_hits); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
                                 rrtx_copy_results_device, per-instance yaw and informed rotation; 4: rrtx_plan_many,
                                 rrtx_selfcheck, rrtx_stats.main_shape / main_f32, rrtx_plan_begin / _step, rrtx_set_launch_bound,
                                 RRTX_ST_REF_HANGS, rrtx_rccl_* */
@@ -396,8 +397,23 @@ int rrtx_steer_get_summary(rrtx_steer* s, int32_t* status, double* length, int32
                            int64_t* offsets);
 /* The flat x, y, yaw arrays of the last solve (cap = doubles available in each; RRTX_E_CAPACITY when too small). */
 int rrtx_steer_get_points(rrtx_steer* s, double* x, double* y, double* yaw, int64_t cap);
-/* HIP-event time of the kernels of the last solve (both stages; the prefix sum between them is not kernel time) */
+/* HIP-event time of the kernels of the last solve (both stages, the obstacle check included; the prefix sum between them is
+ * not kernel time) */
 int rrtx_steer_get_kernel_ms(rrtx_steer* s, double* kernel_ms);
+/* The obstacle list every later solve on `s` tests its curves against, until it is set again: m rows (x, y, size), copied
+ * (the caller's array need not outlive the call), any m up to 2^20 -- the planners' obstacle limits do not apply here.
+ * m == 0 turns the check off.  The test is check_collision of the pose planners (rrt_05:1625-1638, rrt_06:1749-1762) on the
+ * curve's own points: for each obstacle in list order, min over the points of dx * dx + dy * dy <= (size + robot_radius) ** 2.
+ * A negative size is accepted (the reference squares it).  With a list set, a solve with want_points == 0 still computes
+ * every point on the device, but stores none: no point arrays and no offsets exist afterwards.
+ * RRTX_E_INVALID, before any HIP call: s NULL, m < 0, m > 2^20, obstacles NULL with m > 0, an entry or robot_radius that is
+ * not finite. */
+int rrtx_steer_set_obstacles(rrtx_steer* s, const double* obstacles, int64_t m, double robot_radius);
+/* Per pair of the last solve: -1 the reference's check_collision returns True for the pair's curve (free); j >= 0 the index
+ * of the obstacle at which its loop returns False (the lowest index any point of the curve touches); -2 the pair has no
+ * curve (status != RRTX_STEER_OK), nothing was tested.  RRTX_E_STATE before the first solve and when the last solve ran
+ * with no obstacle list set. */
+int rrtx_steer_get_hits(rrtx_steer* s, int32_t* hit);
 
 /* ---- batched closed-loop tracking of courses given as data, without a planner (csrc/rrt_track.hip.h) ----------------------
  * For every course of a batch: what ClosedLoopRRTStar.check_tracking_path_is_feasible(path) (rrt_10:1526-1564) returns,

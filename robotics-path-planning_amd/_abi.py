@@ -31,7 +31,8 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_set_rs_cost", "rrtx_track_planned", "rrtx_get_track_outcome", "rrtx_get_track_arrays", "rrtx_get_track_records",
            "rrtx_get_track_stats",
            "rrtx_steer_create", "rrtx_steer_destroy", "rrtx_steer_last_error", "rrtx_steer_solve", "rrtx_steer_get_counts",
-           "rrtx_steer_get_summary", "rrtx_steer_get_points", "rrtx_steer_get_kernel_ms",
+           "rrtx_steer_get_summary", "rrtx_steer_get_points", "rrtx_steer_get_kernel_ms", "rrtx_steer_set_obstacles",
+           "rrtx_steer_get_hits",
            "rrtx_tracker_create", "rrtx_tracker_destroy", "rrtx_tracker_last_error", "rrtx_tracker_run",
            "rrtx_tracker_get_counts", "rrtx_tracker_get_records", "rrtx_tracker_get_arrays", "rrtx_tracker_get_kernel_ms"]
 STEER_DUBINS, STEER_RS = 0, 1                                                      # include/rrtx.h: #define RRTX_STEER_*
@@ -167,6 +168,8 @@ def load():
     L.rrtx_steer_get_summary.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.rrtx_steer_get_points.argtypes = [vp, vp, vp, vp, C.c_int64]
     L.rrtx_steer_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.rrtx_steer_set_obstacles.argtypes = [vp, vp, C.c_int64, C.c_double]
+    L.rrtx_steer_get_hits.argtypes = [vp, vp]
     L.rrtx_tracker_create.argtypes = [i32, C.POINTER(vp)]
     L.rrtx_tracker_destroy.argtypes = [vp]
     L.rrtx_tracker_destroy.restype = None
@@ -560,6 +563,7 @@ class Steer:
     def __init__(self, device=0):
         self.L = load()
         self._s = C.c_void_p()
+        self.n_obstacles = 0
         rc = self.L.rrtx_steer_create(int(device), C.byref(self._s))
         if rc != 0:
             msg = self.L.rrtx_steer_last_error(self._s).decode()
@@ -607,6 +611,21 @@ class Steer:
                                                  go.ctypes.data, cv.ctypes.data, int(per_pair), float(step_size),
                                                  None if wo is None else wo.ctypes.data, 0 if wo is None else len(wo),
                                                  int(bool(points))), "rrtx_steer_solve")
+
+    def set_obstacles(self, obstacle_list, robot_radius=0.0):
+        """The (x, y, size) rows every later solve tests its curves against (any number up to 2^20); an empty list turns
+        the check off."""
+        ob = np.ascontiguousarray(obstacle_list, dtype=np.float64).reshape(-1, 3)
+        self._chk(self.L.rrtx_steer_set_obstacles(self._s, ob.ctypes.data if len(ob) else None, len(ob),
+                                                  float(robot_radius)), "rrtx_steer_set_obstacles")
+        self.n_obstacles = len(ob)
+
+    def hits(self):
+        """(n,) int32 of the last solve: -1 free, j >= 0 the first obstacle of the list the curve touches, -2 no curve."""
+        n, _ = self.counts()
+        hit = np.zeros(n, dtype=np.int32)
+        self._chk(self.L.rrtx_steer_get_hits(self._s, hit.ctypes.data), "rrtx_steer_get_hits")
+        return hit
 
     def counts(self):
         n, m = C.c_int64(), C.c_int64()

@@ -2117,9 +2117,12 @@ struct rrtx_steer {
     void* p = nullptr;
     size_t bytes = 0;
   };
-  Buf starts, goals, curv, status, nseg, total, seglen, modes, npts, plan, offsets, px, py, pyaw, flag;
+  Buf starts, goals, curv, status, nseg, total, seglen, modes, npts, plan, offsets, px, py, pyaw, flag, obs, hit;
+  // the obstacle list of rrtx_steer_set_obstacles: packed rows (ox, oy, thr); it goes to the device at the next solve
+  std::vector<double> h_obs;
+  bool obs_dirty = false;
   // the last solve
-  bool solved = false, has_points = false;
+  bool solved = false, has_points = false, has_hits = false;
   int64_t n = 0, n_points = 0;
   double kernel_ms = 0.0;
   std::vector<int64_t> h_offsets;
@@ -2147,6 +2150,17 @@ int steer_reserve(rrtx_steer* s, rrtx_steer::Buf& b, size_t bytes) {
   STEERCHK(s, hipMalloc(&b.p, bytes));
   b.bytes = bytes;
   return RRTX_OK;
+}
+
+// stage 2 with or without the stores and the obstacle check; one of the two is wanted
+template <int KIND>
+void steer_launch_fill(bool store, bool check, unsigned blocks, hipStream_t stream, const rppsb::Args& a) {
+  if (store && check)
+    hipLaunchKernelGGL((rppsb::steer_fill<KIND, true, true>), dim3(blocks), dim3(rppsb::TPB), 0, stream, a);
+  else if (store)
+    hipLaunchKernelGGL((rppsb::steer_fill<KIND, true, false>), dim3(blocks), dim3(rppsb::TPB), 0, stream, a);
+  else
+    hipLaunchKernelGGL((rppsb::steer_fill<KIND, false, true>), dim3(blocks), dim3(rppsb::TPB), 0, stream, a);
 }
 }  // namespace
 
@@ -2178,7 +2192,7 @@ void rrtx_steer_destroy(rrtx_steer* s) {
   if (s->usable) {
     hipSetDevice(s->device);
     for (rrtx_steer::Buf* b : {&s->starts, &s->goals, &s->curv, &s->status, &s->nseg, &s->total, &s->seglen, &s->modes,
-                               &s->npts, &s->plan, &s->offsets, &s->px, &s->py, &s->pyaw, &s->flag})
+                               &s->npts, &s->plan, &s->offsets, &s->px, &s->py, &s->pyaw, &s->flag, &s->obs, &s->hit})
       if (b->p) hipFree(b->p);
     for (auto& e : s->ev)
       if (e) hipEventDestroy(e);
@@ -2242,15 +2256,21 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
     if (!(pts <= 4194304.0)) return bad("the poses are so far apart for this curvature and step that a curve could exceed 2^22 points");
   }
   if (!s->usable) return steer_fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  // With an obstacle list the curves' points are computed (stage 1 as for points, then the fill kernel) whether or not
+  // they are stored.
+  const int64_t n_obs = (int64_t)(s->h_obs.size() / 3);
+  const bool stage2 = want_points || n_obs > 0;
 
   s->solved = false;
   s->has_points = false;
+  s->has_hits = false;
   s->n = np;
   s->n_points = 0;
   s->kernel_ms = 0.0;
   s->h_offsets.clear();
   if (np == 0) {
     s->has_points = want_points != 0;
+    s->has_hits = n_obs > 0;
     s->h_offsets.assign(1, 0);
     s->solved = true;
     return RRTX_OK;
@@ -2268,10 +2288,18 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
   if ((rc = steer_reserve(s, s->modes, 8 * N))) return rc;
   if ((rc = steer_reserve(s, s->npts, sizeof(int32_t) * N))) return rc;
   if ((rc = steer_reserve(s, s->flag, sizeof(int32_t)))) return rc;
-  if (want_points) {
+  if (stage2) {
     const size_t rec = kind == RRTX_STEER_DUBINS ? sizeof(rpp::DubinsPlan) : sizeof(rpp::RsCourse);
     if ((rc = steer_reserve(s, s->plan, rec * N))) return rc;
     if ((rc = steer_reserve(s, s->offsets, sizeof(int64_t) * (N + 1)))) return rc;
+  }
+  if (n_obs > 0) {
+    if ((rc = steer_reserve(s, s->hit, sizeof(int32_t) * N))) return rc;
+    if (s->obs_dirty) {
+      if ((rc = steer_reserve(s, s->obs, sizeof(double) * s->h_obs.size()))) return rc;
+      STEERCHK(s, hipMemcpyAsync(s->obs.p, s->h_obs.data(), sizeof(double) * s->h_obs.size(), hipMemcpyHostToDevice, s->stream));
+      s->obs_dirty = false;
+    }
   }
   STEERCHK(s, hipMemcpyAsync(s->starts.p, starts, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, s->stream));
   STEERCHK(s, hipMemcpyAsync(s->goals.p, goals, sizeof(double) * 3 * (size_t)n_goals, hipMemcpyHostToDevice, s->stream));
@@ -2288,7 +2316,7 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
   a.n = np;
   a.ng = product ? ng : 1;
   a.product = product ? 1 : 0;
-  a.want_points = want_points ? 1 : 0;
+  a.want_points = stage2 ? 1 : 0;
   a.n_order = word_order ? n_words : 6;
   for (int i = 0; i < 6; i++) a.order[i] = (word_order && i < n_words) ? word_order[i] : i;
   a.status = (int32_t*)s->status.p;
@@ -2300,6 +2328,11 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
   a.dplan = (rpp::DubinsPlan*)s->plan.p;
   a.course = (rpp::RsCourse*)s->plan.p;
   a.flag = (int32_t*)s->flag.p;
+  if (n_obs > 0) {
+    a.obs = (const double*)s->obs.p;
+    a.n_obs = n_obs;
+    a.hit = (int32_t*)s->hit.p;
+  }
 
   // stage 1
   const unsigned blk = (unsigned)((np + rppsb::TPB - 1) / rppsb::TPB);
@@ -2309,14 +2342,14 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
   } else {
     hipLaunchKernelGGL(rppsb::steer_rs_solve, dim3((unsigned)((np + rppsb::RS_PAIRS - 1) / rppsb::RS_PAIRS)),
                        dim3(rppsb::RS_TPB), 0, s->stream, a);
-    if (want_points) hipLaunchKernelGGL(rppsb::steer_rs_course, dim3(blk), dim3(rppsb::TPB), 0, s->stream, a);
+    if (stage2) hipLaunchKernelGGL(rppsb::steer_rs_course, dim3(blk), dim3(rppsb::TPB), 0, s->stream, a);
   }
   STEERCHK(s, hipGetLastError());
   STEERCHK(s, hipEventRecord(s->ev[1], s->stream));
   int32_t flag = 0;
   STEERCHK(s, hipMemcpyAsync(&flag, s->flag.p, sizeof(flag), hipMemcpyDeviceToHost, s->stream));
   std::vector<int32_t> cnt;
-  if (want_points) {
+  if (stage2) {
     cnt.resize(N);
     STEERCHK(s, hipMemcpyAsync(cnt.data(), s->npts.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
   }
@@ -2325,7 +2358,7 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
   STEERCHK(s, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
   s->kernel_ms = ms;
 
-  if (want_points) {
+  if (stage2) {
     // offsets: exclusive prefix sum of the point counts
     s->h_offsets.resize(N + 1);
     int64_t tot = 0;
@@ -2334,32 +2367,38 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
       tot += cnt[i] > 0 ? cnt[i] : 0;
     }
     s->h_offsets[N] = tot;
-    s->n_points = tot;
+    s->n_points = want_points ? tot : 0;
     if (tot > 0) {
-      if ((rc = steer_reserve(s, s->px, sizeof(double) * (size_t)tot))) return rc;
-      if ((rc = steer_reserve(s, s->py, sizeof(double) * (size_t)tot))) return rc;
-      if ((rc = steer_reserve(s, s->pyaw, sizeof(double) * (size_t)tot))) return rc;
+      if (want_points) {
+        if ((rc = steer_reserve(s, s->px, sizeof(double) * (size_t)tot))) return rc;
+        if ((rc = steer_reserve(s, s->py, sizeof(double) * (size_t)tot))) return rc;
+        if ((rc = steer_reserve(s, s->pyaw, sizeof(double) * (size_t)tot))) return rc;
+      }
       if ((tot + rppsb::TPB - 1) / rppsb::TPB > 0x7fffffffLL)
         return steer_fail(s, RRTX_E_OVERFLOW, std::string(fn) + "more polyline points than one launch can fill");
       STEERCHK(s, hipMemcpyAsync(s->offsets.p, s->h_offsets.data(), sizeof(int64_t) * (N + 1), hipMemcpyHostToDevice, s->stream));
       a.offsets = (const int64_t*)s->offsets.p;
-      a.px = (double*)s->px.p;
-      a.py = (double*)s->py.p;
-      a.pyaw = (double*)s->pyaw.p;
+      if (want_points) {
+        a.px = (double*)s->px.p;
+        a.py = (double*)s->py.p;
+        a.pyaw = (double*)s->pyaw.p;
+      }
       const unsigned fblk = (unsigned)((tot + rppsb::TPB - 1) / rppsb::TPB);
       STEERCHK(s, hipEventRecord(s->ev[2], s->stream));
       if (kind == RRTX_STEER_DUBINS)
-        hipLaunchKernelGGL(rppsb::steer_fill<rppsb::KIND_DUBINS>, dim3(fblk), dim3(rppsb::TPB), 0, s->stream, a);
+        steer_launch_fill<rppsb::KIND_DUBINS>(want_points != 0, n_obs > 0, fblk, s->stream, a);
       else
-        hipLaunchKernelGGL(rppsb::steer_fill<rppsb::KIND_RS>, dim3(fblk), dim3(rppsb::TPB), 0, s->stream, a);
+        steer_launch_fill<rppsb::KIND_RS>(want_points != 0, n_obs > 0, fblk, s->stream, a);
       STEERCHK(s, hipGetLastError());
       STEERCHK(s, hipEventRecord(s->ev[3], s->stream));
       STEERCHK(s, hipStreamSynchronize(s->stream));
       STEERCHK(s, hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
       s->kernel_ms += ms;
     }
-    s->has_points = true;
+    if (!want_points) s->h_offsets.clear();   // a lengths-only solve keeps no offsets, checked or not
+    s->has_points = want_points != 0;
   }
+  s->has_hits = n_obs > 0;
   s->solved = true;
   if (flag) {
     s->err = std::string(fn) + "some pairs have no path or are cases where the reference raises (see the status column)";
@@ -2416,6 +2455,42 @@ int rrtx_steer_get_points(rrtx_steer* s, double* x, double* y, double* yaw, int6
   if (x) STEERCHK(s, hipMemcpy(x, s->px.p, bytes, hipMemcpyDeviceToHost));
   if (y) STEERCHK(s, hipMemcpy(y, s->py.p, bytes, hipMemcpyDeviceToHost));
   if (yaw) STEERCHK(s, hipMemcpy(yaw, s->pyaw.p, bytes, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+int rrtx_steer_set_obstacles(rrtx_steer* s, const double* obstacles, int64_t m, double robot_radius) {
+  const char* fn = "rrtx_steer_set_obstacles: ";
+  auto bad = [&](const char* msg) { return steer_fail(s, RRTX_E_INVALID, std::string(fn) + msg); };
+  if (!s) return bad("the steer object is NULL");
+  if (m < 0) return bad("a negative obstacle count");
+  if (m > (1LL << 20)) return bad("more than 2^20 obstacles");
+  if (m > 0 && !obstacles) return bad("obstacles is NULL");
+  if (!std::isfinite(robot_radius)) return bad("robot_radius is not finite");
+  for (int64_t i = 0; i < 3 * m; i++)
+    if (!std::isfinite(obstacles[i])) return bad("an obstacle entry is not finite");
+  try {
+    std::vector<double> t((size_t)(3 * m));
+    for (int64_t k = 0; k < m; k++) {
+      t[3 * k] = obstacles[3 * k];
+      t[3 * k + 1] = obstacles[3 * k + 1];
+      t[3 * k + 2] = py_sq_host(obstacles[3 * k + 2] + robot_radius);   // (size+robot_radius)**2  rrt_05:1635
+    }
+    s->h_obs.swap(t);
+  } catch (const std::exception& e) {
+    return steer_fail(s, RRTX_E_HIP, std::string(fn) + e.what());
+  }
+  s->obs_dirty = true;
+  return RRTX_OK;
+}
+
+int rrtx_steer_get_hits(rrtx_steer* s, int32_t* hit) {
+  if (!s) return steer_fail(s, RRTX_E_INVALID, "rrtx_steer_get_hits: the steer object is NULL");
+  if (!s->solved) return steer_fail(s, RRTX_E_STATE, "rrtx_steer_get_hits: no completed solve");
+  if (!s->has_hits) return steer_fail(s, RRTX_E_STATE, "rrtx_steer_get_hits: the last solve ran without an obstacle list");
+  if (s->n == 0) return RRTX_OK;
+  if (!hit) return steer_fail(s, RRTX_E_INVALID, "rrtx_steer_get_hits: hit is NULL");
+  STEERCHK(s, hipSetDevice(s->device));
+  STEERCHK(s, hipMemcpy(hit, s->hit.p, sizeof(int32_t) * (size_t)s->n, hipMemcpyDeviceToHost));
   return RRTX_OK;
 }
 

@@ -16,10 +16,14 @@
 //            steer_rs_course     (points wanted) one lane per pair: generate_local_course prepared for random access.
 //   offsets  exclusive prefix sum of the point counts (host, one int32 per pair down, one int64 per pair up).
 //   stage 2  steer_fill          one lane per output point: binary search of the point index in offsets, then
-//                                dubins_point / rs_point, which are random-access by point index.
-// Lengths-only is stage 1 alone (no plan, no course, no offsets).
+//                                dubins_point / rs_point, which are random-access by point index.  STORE writes the
+//                                point; CHECK tests it against the obstacle list (rpp_collide.h) and takes the lowest
+//                                obstacle index any point of the pair touches into hit[pair].
+// Lengths-only is stage 1 alone (no plan, no course, no offsets) -- unless an obstacle list is set: then stage 1 runs as
+// for points and stage 2 runs with CHECK alone, so no point is ever written.
 // Product mode: pair p of ns x ng is (start p / ng, goal p % ng), formed here; the host never builds the product.
 #pragma once
+#include "rpp_collide.h"
 #include "rpp_rs.h"
 
 namespace rppsb {
@@ -52,6 +56,10 @@ struct Args {
   int32_t* flag;          // set when any pair is not ST_OK
   const int64_t* offsets; // [n + 1]
   double *px, *py, *pyaw; // [offsets[n]]
+  // collision check (nullptr / 0 without an obstacle list)
+  const double* obs;      // [n_obs] rows (ox, oy, thr), thr = (size + robot_radius) ** 2 from the host
+  int64_t n_obs;
+  int32_t* hit;           // [n]  stage 1: -1 (ST_OK) / -2 (no curve); stage 2: the lowest obstacle index touched
 };
 
 __device__ inline void pair_poses(const Args& a, int64_t p, double* s, double* g) {
@@ -82,6 +90,7 @@ __global__ __launch_bounds__(TPB) void steer_dubins_solve(Args a) {
     a.nseg[p] = 0;
     a.total[p] = 0.0;
     a.npts[p] = 0;
+    if (a.hit) a.hit[p] = -2;
     atomicOr(a.flag, 1);
     return;
   }
@@ -97,6 +106,7 @@ __global__ __launch_bounds__(TPB) void steer_dubins_solve(Args a) {
   a.nseg[p] = 3;
   a.total[p] = tot;
   a.npts[p] = P.total;
+  if (a.hit) a.hit[p] = -1;
   if (a.want_points) a.dplan[p] = P;
 }
 
@@ -183,6 +193,7 @@ __global__ __launch_bounds__(RS_TPB) void steer_rs_solve(Args a) {
     a.status[p] = sel == -1 ? ST_NO_PATH : (sel == -3 ? ST_RAISES_ZERODIV : ST_RAISES_VALUE);
     a.nseg[p] = 0;
     a.total[p] = 0.0;
+    if (a.hit) a.hit[p] = -2;
     atomicOr(a.flag, 1);
     return;
   }
@@ -197,6 +208,7 @@ __global__ __launch_bounds__(RS_TPB) void steer_rs_solve(Args a) {
   a.status[p] = ST_OK;
   a.nseg[p] = nl;
   a.total[p] = tot;
+  if (a.hit) a.hit[p] = -1;
   if (a.want_points) {   // the chosen word in curvature units, for steer_rs_course
     rpp::RsCourse& C = a.course[p];
     for (int i = 0; i < 5; i++) C.len[i] = T.d[sel][i];
@@ -221,11 +233,18 @@ __global__ __launch_bounds__(TPB) void steer_rs_course(Args a) {
 }
 
 // ---- stage 2 -------------------------------------------------------------------------------------------------------
-template <int KIND>
+// <KIND, true, false> is the fill kernel alone.  With CHECK a lane past the last point does not leave: it stays as a copy
+// of the last point (the same pair, the same answer), so every lane of a wave takes part in the shuffles below.
+// hit[] is read as unsigned for the minimum: -1 (free) is then the largest value, and -2 belongs to pairs without points.
+template <int KIND, bool STORE, bool CHECK>
 __global__ __launch_bounds__(TPB) void steer_fill(Args a) {
-  const int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
   const int64_t total = a.offsets[a.n];
-  if (idx >= total) return;
+  const bool live = idx < total;
+  if (!live) {
+    if (!CHECK) return;
+    idx = total - 1;   // the launch has total > 0
+  }
   int64_t lo = 0, hi = a.n;   // the pair p with offsets[p] <= idx < offsets[p + 1] (rows without points are skipped over)
   while (hi - lo > 1) {
     const int64_t mid = lo + (hi - lo) / 2;
@@ -240,9 +259,31 @@ __global__ __launch_bounds__(TPB) void steer_fill(Args a) {
     rpp::dubins_point(a.dplan[lo], k, pair_curv(a, lo), &x, &y, &yaw);
   else
     rpp::rs_point(a.course[lo], k, &x, &y, &yaw);
-  a.px[idx] = x;
-  a.py[idx] = y;
-  a.pyaw[idx] = yaw;
+  if (STORE && live) {
+    a.px[idx] = x;
+    a.py[idx] = y;
+    a.pyaw[idx] = yaw;
+  }
+  if (CHECK) {
+    // The obstacle index is the same in every lane still in first_hit's loop, and a lane leaves the loop at its first
+    // hit: the wave is done with the list as soon as all its lanes have one.
+    const uint32_t NONE = 0xffffffffu;
+    const uint32_t h = (uint32_t)rpp::first_hit(a.obs, a.n_obs, x, y);
+    if (!__any(h != NONE)) return;
+    uint32_t* out = (uint32_t*)a.hit;
+    const int pair = (int)lo;   // n <= 2^30
+    const int pair0 = __shfl(pair, 0);
+    if (__all(pair == pair0)) {   // the wave lies within one curve (the common case for long curves): one atomic
+      uint32_t m = h;
+      for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)m, off);
+        m = o < m ? o : m;
+      }
+      if ((threadIdx.x & 63) == 0) atomicMin(out + pair0, m);
+    } else if (h != NONE) {
+      atomicMin(out + pair, h);
+    }
+  }
 }
 
 }  // namespace rppsb

@@ -3,6 +3,11 @@
     bs = BatchSteer("dubins")                       # or "rs"
     res = bs.plan(starts, goals, curvature)         # (n, 3) poses each; res.path(i) = the reference's five-tuple
     cost = bs.plan(starts, goals, 1.0, points=False, product=True).length_matrix()   # (ns, ng) lengths
+    res = bs.plan(starts, goals, 1.0, points=False, product=True, obstacle_list=circles, robot_radius=0.3)
+    cost = res.length_matrix(free_only=True)        # +inf where the curve touches a circle; res.hit says which one
+
+obstacle_list: rows (x, y, size), any number of them; the test is the pose planners' check_collision (rrt_05 :1625,
+rrt_06 :1749) on the curve's own points, made in the kernel that computes them.
 
 Every double is what the reference's plan_dubins_path (10_path_planning_00_dubins_path.py :109) /
 reeds_shepp_path_planning (10_path_planning_00_reeds_shepp_path.py :506) returns for that pair, bit for bit.  There is no
@@ -34,9 +39,11 @@ def word_order(selected_types):
 
 class SteerResult:
     """One solved batch.  status (n,) STEER_*; length (n,): the absolute segment lengths added up; modes: list of n strings; lengths: list of n arrays of segment
-    lengths; offsets (n + 1,) and the flat x, y, yaw when points were asked for, else None."""
+    lengths; offsets (n + 1,) and the flat x, y, yaw when points were asked for, else None; hit (n,) int32 when the batch
+    was planned with an obstacle list (-1 free, j >= 0 the first obstacle of the list the curve touches, -2 no curve),
+    else None."""
 
-    def __init__(self, kind, status, length, nseg, seglen, modes, offsets, xyz, shape, rc, kernel_ms):
+    def __init__(self, kind, status, length, nseg, seglen, modes, offsets, xyz, shape, rc, kernel_ms, hit=None):
         self.kind = kind
         self.status = status
         self.length = length
@@ -49,6 +56,30 @@ class SteerResult:
         self.shape = shape          # (ns, ng) in product mode, else None
         self.rc = rc                # 0 or RRTX_PARTIAL
         self.kernel_ms = kernel_ms
+        self.hit = hit
+
+    @property
+    def free(self):
+        """Boolean mask of the pairs whose curve touches no obstacle (hit == -1); a pair without a curve is not free."""
+        if self.hit is None:
+            raise _abi.RrtxError("free: this batch was planned without an obstacle list")
+        return self.hit == -1
+
+    def is_free(self, i):
+        """What the reference's check_collision(node, obstacle_list, robot_radius) returns for pair i's curve; raises what
+        path(i) raises where the pair has no curve."""
+        if self.hit is None:
+            raise _abi.RrtxError("is_free(): this batch was planned without an obstacle list")
+        st = int(self.status[i])
+        if st == _abi.STEER_RAISES_ZERODIV:
+            raise ZeroDivisionError("float division by zero")
+        if st == _abi.STEER_RAISES_VALUE:
+            raise ValueError("math domain error")
+        if st == _abi.STEER_NO_PATH:
+            if self.kind == _abi.STEER_DUBINS:
+                raise TypeError("'NoneType' object is not iterable")
+            return False   # Reeds-Shepp: path(i) is (None,) * 5, and check_collision(None, ...) is False (:1751)
+        return bool(self.hit[i] == -1)
 
     def __len__(self):
         return len(self.status)
@@ -74,10 +105,13 @@ class SteerResult:
             return self.x[a:b].copy(), self.y[a:b].copy(), self.yaw[a:b].copy(), modes, lengths
         return self.x[a:b].tolist(), self.y[a:b].tolist(), self.yaw[a:b].tolist(), modes, lengths
 
-    def length_matrix(self):
+    def length_matrix(self, free_only=False):
+        """The (ns, ng) lengths of a product-mode batch; free_only: +inf where the pair is not free."""
         if self.shape is None:
             raise _abi.RrtxError("length_matrix(): this batch was not solved in product mode")
-        return self.length.reshape(self.shape)
+        if not free_only:
+            return self.length.reshape(self.shape)
+        return np.where(self.free, self.length, np.inf).reshape(self.shape)
 
 
 class BatchSteer:
@@ -100,18 +134,23 @@ class BatchSteer:
         self.close()
         return False
 
-    def plan(self, starts, goals, curvature, step_size=None, selected_types=None, points=True, product=False):
+    def plan(self, starts, goals, curvature, step_size=None, selected_types=None, points=True, product=False,
+             obstacle_list=None, robot_radius=0.0):
         """starts, goals: (n, 3) rows of (x, y, yaw) -- with product=True (ns, 3) and (ng, 3), pair p = (p // ng, p % ng).
         curvature: a float or one per pair.  step_size: Reeds-Shepp any value > 0 (default 0.2); Dubins 0.1 only.
-        selected_types (Dubins): word names in the order to try them."""
+        selected_types (Dubins): word names in the order to try them.  obstacle_list: rows (x, y, size) every curve is
+        tested against with robot_radius (result.hit / .free); None or empty: no check."""
         if step_size is None:
             step_size = DEFAULT_STEP[self.kind]
         wo = word_order(selected_types)
         st = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
         go = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
         S = self._steer
+        ob = np.zeros((0, 3)) if obstacle_list is None else np.asarray(obstacle_list, dtype=np.float64).reshape(-1, 3)
+        if len(ob) or S.n_obstacles:   # (nothing to clear when no list was ever set: today's calls, unchanged)
+            S.set_obstacles(ob, robot_radius)
         rc = S.solve(self.kind, st, go, curvature, step_size, word_order=wo, points=points, product=product)
         status, length, nseg, seglen, modes, off = S.summary(offsets=bool(points))
         xyz = S.points() if points else None
         return SteerResult(self.kind, status, length, nseg, seglen, modes, off, xyz,
-                           (len(st), len(go)) if product else None, rc, S.kernel_ms())
+                           (len(st), len(go)) if product else None, rc, S.kernel_ms(), hit=S.hits() if len(ob) else None)

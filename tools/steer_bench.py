@@ -1,12 +1,17 @@
 """Throughput of the batched Dubins / Reeds-Shepp curves (BatchSteer): pairs/s for lengths-only and for points.
 
-    python tools/steer_bench.py [--pairs 1048576] [--reps 5] [--cpu-pairs 2000]
+    python tools/steer_bench.py [--pairs 1048576] [--reps 5] [--cpu-pairs 2000] [--obstacles M]
 
 Random pairs in the pose box of the known-answer vectors ([-2, 15]^2, any yaw), curvature 1, Reeds-Shepp step 0.2.  The
 GPU figure is HIP-event kernel time (stage 1, and stage 1 + fill), the median of --reps solves after one warm-up solve;
 transfers and the host prefix sum are reported separately as wall time.  Beside it: the C oracle (oracle.dubins /
 oracle.reeds_shepp, which always builds the points) on one core over a subsample of the same pairs.  Prints one JSON
-line per kind.  Needs a device: there is no CPU fallback."""
+line per kind.  Needs a device: there is no CPU fallback.
+
+--obstacles M (default 0: the output above, unchanged) adds the obstacle check against M seeded circles in the same box
+(radius 0.2 .. 0.8): "check_lengths_*" is points=False with the list set (the collision-free cost-matrix path),
+"check_points_*" is points=True with it, "plan_wall_ms" of each variant is one whole BatchSteer.plan() call (transfers
+and result arrays included), and "free_fraction" the share of pairs whose curve touches nothing."""
 import argparse
 import json
 import os
@@ -34,6 +39,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cpu-pairs", type=int, default=2000)
+    ap.add_argument("--obstacles", type=int, default=0)
     args = ap.parse_args()
     import oracle
     import rrt_amd
@@ -57,6 +63,24 @@ def main():
                 if points:
                     out["n_points"] = bs._steer.counts()[1]
                     out["points_per_s"] = out["n_points"] / (med * 1e-3)
+            if args.obstacles > 0:
+                rs = np.random.RandomState(9)
+                circles = np.stack([rs.uniform(-2, 15, args.obstacles), rs.uniform(-2, 15, args.obstacles),
+                                    rs.uniform(0.2, 0.8, args.obstacles)], axis=1)
+                out["obstacles"] = args.obstacles
+                for k, points, obs in (("points", True, None), ("check_lengths", False, circles), ("check_points", True, circles)):
+                    ms, wall = [], []
+                    for rep in range(args.reps + 1):
+                        t0 = time.perf_counter()
+                        res = bs.plan(p[:, 0:3], p[:, 3:6], 1.0, points=points, obstacle_list=obs)
+                        wall.append((time.perf_counter() - t0) * 1e3)
+                        ms.append(res.kernel_ms)
+                    if obs is not None:
+                        out[k + "_kernel_ms"] = float(np.median(ms[1:]))
+                        out[k + "_pairs_per_s"] = args.pairs / (out[k + "_kernel_ms"] * 1e-3)
+                        out["free_fraction"] = float(np.mean(res.free))
+                    out[k + "_plan_wall_ms"] = float(np.median(wall[1:]))
+                    res = None
         m = min(args.cpu_pairs, args.pairs)
         fn = oracle.dubins if kind == "dubins" else oracle.reeds_shepp
         t0 = time.perf_counter()
