@@ -2,23 +2,15 @@
 // Owns device memory, uploads parameters / RNG state, launches the planner
 // kernel in bounded chunks of iterations on the handle's HIP stream, and copies
 // results back.  There is no CPU planning path in this library.
-#include <hip/hip_runtime.h>
-#include <dlfcn.h>
-#include <rccl/rccl.h>   // types and enums only: the functions are resolved with dlsym at first use (no link-time dependency)
-
+// This file holds the planner handle; the other objects and the handle-free calls are included at its end, one file each.
 #include <algorithm>
 #include <chrono>
-#include <cmath>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <functional>
 #include <new>
-#include <string>
-#include <thread>
 #include <vector>
 
-#include "../../include/rrtx.h"
+#include "rrtx_host.h"
 #include "rrt_kernels.hip.h"
 #include "rrt_star_v2.hip.h"
 #include "rrt_informed.hip.h"
@@ -35,67 +27,12 @@ using rppk::Ctx;
 using rppk::Inst;
 using rppk::Result;
 
-namespace {
+static_assert(sizeof(rppt::Params) == sizeof(rrtx_track_params), "rrtx_track_params mirrors rppt::Params");
+static_assert(sizeof(rppt::Outcome) == sizeof(rrtx_track_outcome), "rrtx_track_outcome mirrors rppt::Outcome");
+static_assert(sizeof(rppt::Record) == sizeof(rrtx_track_record), "rrtx_track_record mirrors rppt::Record");
 
-// libm through volatile pointers: the compiler must not fold pow(x, 2.0) into x*x
-// (glibc's pow is not correctly rounded and the reference's `**2` goes through it).
-double (*volatile libm_pow)(double, double) = pow;
-double (*volatile libm_log)(double) = log;
-double (*volatile libm_sqrt)(double) = sqrt;
-double (*volatile libm_sin)(double) = sin;
-double (*volatile libm_cos)(double) = cos;
-double (*volatile libm_atan2)(double, double) = atan2;
-double (*volatile libm_acos)(double) = acos;
-double (*volatile libm_asin)(double) = asin;
-
-inline double py_sq_host(double x) {
-  if (x == 0.0) return 0.0;
-  return libm_pow(std::fabs(x), 2.0);
-}
-
-}  // namespace
-
-// RCCL, opened with dlopen at first use (rrtx_rccl_*): no link-time dependency, nothing loaded by single-GPU users
-namespace {
-struct RcclApi {
-  void* lib = nullptr;
-  ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-  ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-  ncclResult_t (*AllGather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-  const char* (*GetErrorString)(ncclResult_t) = nullptr;
-  std::string err;
-};
-RcclApi* rccl_api() {
-  static RcclApi api;
-  if (api.lib || !api.err.empty()) return &api;
-  for (const char* nm : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-    api.lib = dlopen(nm, RTLD_NOW | RTLD_GLOBAL);
-    if (api.lib) break;
-  }
-  if (!api.lib) {
-    api.err = std::string("librccl.so not loadable: ") + (dlerror() ? dlerror() : "?");
-    return &api;
-  }
-  api.GetUniqueId = (decltype(api.GetUniqueId))dlsym(api.lib, "ncclGetUniqueId");
-  api.CommInitRank = (decltype(api.CommInitRank))dlsym(api.lib, "ncclCommInitRank");
-  api.AllGather = (decltype(api.AllGather))dlsym(api.lib, "ncclAllGather");
-  api.CommDestroy = (decltype(api.CommDestroy))dlsym(api.lib, "ncclCommDestroy");
-  api.GetErrorString = (decltype(api.GetErrorString))dlsym(api.lib, "ncclGetErrorString");
-  if (!api.GetUniqueId || !api.CommInitRank || !api.AllGather || !api.CommDestroy) {
-    api.err = "librccl.so lacks ncclGetUniqueId / ncclCommInitRank / ncclAllGather / ncclCommDestroy";
-    api.lib = nullptr;
-  }
-  return &api;
-}
-}  // namespace
-
-struct rrtx_handle {
+struct rrtx_handle : DevObj {
   rrtx_params p;
-  int device = 0;
-  int n_cu = 0;                 // compute units of the device
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   Ctx c;
   int64_t stride = 0;
   int n_inst = 0;
@@ -104,14 +41,13 @@ struct rrtx_handle {
   std::vector<Inst> host_inst;  // staging for seeds / starts / obstacle rows before the first plan
   std::vector<double> obst;     // every instance's obstacle rows (x, y, size) as given, in device-table order
   // device obstacle table: ox, oy, othr and the sizes (path smoothing) of all rows, `obs_cap` rows each, one allocation
-  double* obs_buf = nullptr;
+  DevBuf obs_buf;
   int64_t obs_cap = 0;
   int trace_inst = -1;    // instance the next plan traces (rrtx_enable_trace)
   int traced_inst = -1;   // instance whose trace the last completed plan recorded; -1 none
   rrtx_stats stats;
   int64_t phase[16] = {0};
-  std::string err;
-  std::vector<void*> allocs;
+  std::vector<void*> allocs;   // the fixed-size tables (dalloc); buffers that are regrown are DevBuf members
   // one rrtx_plan in progress (rrtx_plan_begin / rrtx_plan_step; rrtx_plan = begin + steps until nothing is pending)
   struct Run {
     int stage = 0;   // 0 none, 1 RRT* iteration-kernel launches, 2 launches of the planner's main kernel
@@ -132,7 +68,7 @@ struct rrtx_handle {
   // native RCCL gather of the result table (rrtx_rccl_*): communicator of this rank, world size, receive buffer
   void* rccl_comm = nullptr;
   int rccl_world = 0, rccl_rank = 0;
-  Result* rccl_recv = nullptr;
+  DevBuf rccl_recv;
   int chunk_iters = 32768;       // iterations per launch of the other planner kernels
   int32_t* inst_map = nullptr;   // device: instance ids of a partial re-plan (overflow retry)
   // pose planners: where an instance's edge polylines live -- the handle's pool (slab = instance), or a larger pool
@@ -140,12 +76,14 @@ struct rrtx_handle {
   struct PoolLoc {
     double *px = nullptr, *py = nullptr, *pyaw = nullptr;
     int64_t cap = 0, slab = 0;
+    // the instance's slab of column `col` (px, py or pyaw), from its point `off` on
+    const double* at(const double* col, int64_t off = 0) const { return col + slab * cap + off; }
   };
   std::vector<PoolLoc> pool_loc;
   // the enlarged pools of the overflow re-plan (x4, x16): kept on the handle and used again by later rrtx_plan calls
   // when they are large enough (slabs >= instances to re-plan), so repeated plans do not grow device memory
   struct BigPool {
-    double *px = nullptr, *py = nullptr, *pyaw = nullptr;
+    DevBuf px, py, pyaw;
     int64_t cap = 0;
     int slabs = 0;
   } big[2];
@@ -175,9 +113,9 @@ struct rrtx_handle {
     rppt::Record* rec = nullptr;
     rppt::Outcome* outc = nullptr;
     const double** pool = nullptr;
-    double *slab = nullptr, *out = nullptr;
+    double* slab = nullptr;
+    DevBuf out;   // the winners' arrays: its size depends on the plan, so it alone of the tracking buffers is regrown
     int64_t* out_off = nullptr;
-    int64_t out_cap = 0;
     int blocks = 0;
     bool valid = false;
     std::vector<rppt::Outcome> h_outc;
@@ -186,23 +124,10 @@ struct rrtx_handle {
   } tk;
 };
 
-#define HIPCHK(h, expr)                                                                      \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                          \
-      return RRTX_E_HIP;                                                                     \
-    }                                                                                        \
-  } while (0)
-
 template <class T>
 static int dalloc(rrtx_handle* h, T** p, size_t count) {
   void* q = nullptr;
-  hipError_t e = hipMalloc(&q, count * sizeof(T));
-  if (e != hipSuccess) {
-    h->err = std::string("hipMalloc: ") + hipGetErrorString(e);
-    return RRTX_E_HIP;
-  }
+  HIPCHK(h, hipMalloc(&q, count * sizeof(T)));
   h->allocs.push_back(q);
   *p = (T*)q;
   return 0;
@@ -219,19 +144,14 @@ static int refuse_in_plan(rrtx_handle* h, const char* fn) {
 // Device obstacle table of at least `rows` rows (contents are not kept: the caller uploads every row afterwards)
 static int obs_reserve(rrtx_handle* h, int64_t rows) {
   if (rows <= h->obs_cap) return RRTX_OK;
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, sizeof(double) * 4 * (size_t)rows);
-  if (e != hipSuccess) {   // the handle keeps its current table and lists
-    h->err = std::string("hipMalloc: ") + hipGetErrorString(e);
-    return RRTX_E_HIP;
-  }
-  if (h->obs_buf) hipFree(h->obs_buf);
-  h->obs_buf = (double*)q;
+  DevBuf fresh;
+  if (int rc = h->reserve(fresh, sizeof(double) * 4 * (size_t)rows)) return rc;   // the handle keeps its current table and lists
+  h->obs_buf = std::move(fresh);
   h->obs_cap = rows;
-  h->c.ox = h->obs_buf;
-  h->c.oy = h->obs_buf + rows;
-  h->c.othr = h->obs_buf + 2 * rows;
-  h->sm_osz = h->obs_buf + 3 * rows;
+  h->c.ox = h->obs_buf.as<double>();
+  h->c.oy = h->c.ox + rows;
+  h->c.othr = h->c.ox + 2 * rows;
+  h->sm_osz = h->obs_buf.as<double>() + 3 * rows;
   return RRTX_OK;
 }
 
@@ -248,7 +168,7 @@ static int obs_upload(rrtx_handle* h, const double* oxyr, int64_t rows) {
     t[2 * h->obs_cap + k] = py_sq_host(oxyr[3 * k + 2] + h->p.robot_radius);  // (size+robot_radius)**2  rrt_04:1227
     t[3 * h->obs_cap + k] = oxyr[3 * k + 2];
   }
-  HIPCHK(h, hipMemcpy(h->obs_buf, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(h->obs_buf.p, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
   h->obst.assign(oxyr, oxyr + 3 * (size_t)rows);
   return RRTX_OK;
 }
@@ -258,15 +178,13 @@ static int obs_upload(rrtx_handle* h, const double* oxyr, int64_t rows) {
 template <class Queue>
 static int timed_launch(rrtx_handle* h, bool copy_results, Queue&& queue) {
   rrtx_handle::Run& R = h->run;
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  queue();
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  if (copy_results)
-    HIPCHK(h, hipMemcpyAsync(R.res.data(), h->c.results, sizeof(Result) * h->n_inst, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
   float ms = 0.f;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  int rc = h->timed(&ms, queue, [&]() -> int {
+    if (copy_results)
+      HIPCHK(h, hipMemcpyAsync(R.res.data(), h->c.results, sizeof(Result) * h->n_inst, hipMemcpyDeviceToHost, h->stream));
+    return RRTX_OK;
+  });
+  if (rc) return rc;
   R.kms += ms;
   R.launches++;
   return RRTX_OK;
@@ -341,6 +259,8 @@ static int estimate_near_capacity(const rrtx_params& p) {
   return cap > 1e6 ? 1000000 : (int)cap;
 }
 
+static void rccl_release(rrtx_handle* h);   // rrtx_api_rccl.inc
+
 extern "C" {
 
 int rrtx_abi_version(void) { return RRTX_ABI_VERSION; }
@@ -356,22 +276,9 @@ const char* rrtx_last_error(rrtx_handle* h) { return h ? h->err.c_str() : "null 
 void rrtx_destroy(rrtx_handle* h) {
   if (!h) return;
   hipSetDevice(h->device);
-  if (h->rccl_comm) {
-    RcclApi* a = rccl_api();
-    if (a->lib) a->CommDestroy((ncclComm_t)h->rccl_comm);
-  }
+  rccl_release(h);
   for (void* q : h->allocs) hipFree(q);
-  if (h->obs_buf) hipFree(h->obs_buf);
-  if (h->tk.out) hipFree(h->tk.out);
-  for (auto& bp : h->big) {
-    if (bp.px) hipFree(bp.px);
-    if (bp.py) hipFree(bp.py);
-    if (bp.pyaw) hipFree(bp.pyaw);
-  }
-  if (h->ev0) hipEventDestroy(h->ev0);
-  if (h->ev1) hipEventDestroy(h->ev1);
-  if (h->stream) hipStreamDestroy(h->stream);
-  delete h;
+  delete h;   // the DevBuf members, then the events and the stream
 }
 
 static inline bool is_dubins(int algo) { return algo == RRTX_ALGO_DUBINS || algo == RRTX_ALGO_RRT_DUBINS; }
@@ -387,16 +294,13 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
   if (p->algo == RRTX_ALGO_RS && (!(p->step_size > 0.0) || !(p->curvature > 0.0))) return RRTX_E_INVALID;
   if (p->n_instances < 1 || p->max_iter < 0 || !(p->path_resolution > 0.0) || !(p->expand_dis >= 0.0))
     return RRTX_E_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || p->device < 0 || p->device >= ndev)
-    return RRTX_E_NO_DEVICE;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, p->device) != hipSuccess) return RRTX_E_NO_DEVICE;
-  if (!strstr(prop.gcnArchName, "gfx950") && !getenv("RRTX_ALLOW_ANY_ARCH")) return RRTX_E_NO_DEVICE;
   rrtx_handle* h = new rrtx_handle();
+  int rc = h->open(p->device, "rrtx_create");
+  if (rc == RRTX_E_NO_DEVICE) {   // no handle without a device: there is no message to read
+    delete h;
+    return rc;
+  }
   h->p = *p;
-  h->device = p->device;
-  h->n_cu = prop.multiProcessorCount;
   h->n_inst = p->n_instances;
   memset(&h->stats, 0, sizeof(h->stats));
   memset(&h->c, 0, sizeof(h->c));
@@ -408,18 +312,14 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
     h->chunk_iters = atoi(e) > 0 ? atoi(e) : 32768;
     h->v2_chunk_iters = h->chunk_iters;
   }
-  *out = h;  // returned even on failure below so the caller can read last_error, then destroy
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  HIPCHK(h, hipEventCreate(&h->ev0));
-  HIPCHK(h, hipEventCreate(&h->ev1));
+  *out = h;  // returned even on failure, of open() or below, so the caller can read last_error, then destroy
+  if (rc) return rc;
   // node capacity: start + one node per iteration; padded so each wave's 512-node stride stays inside
   // (rrt_06: try_goal_path :1572-1582 can append a second node per iteration)
   const int64_t cap = (p->algo == RRTX_ALGO_RS ? 2 : 1) * (int64_t)p->max_iter + 2;
   h->stride = (cap + 511) / 512 * 512 + 2560;
   const size_t tot = (size_t)h->stride * h->n_inst;
   Ctx& c = h->c;
-  int rc;
   if ((rc = dalloc(h, &c.inst, h->n_inst))) return rc;
   if ((rc = dalloc(h, &c.x, tot))) return rc;
   if ((rc = dalloc(h, &c.y, tot))) return rc;
@@ -1120,17 +1020,11 @@ static int plan_finish(rrtx_handle* h) {
       if (bp.cap != big_cap || bp.slabs < nr) {
         // (re)allocate this level: nothing of the CURRENT plan lives in it yet (its users are decided below), and the
         // previous plan's polylines are gone with the re-initialisation above
-        if (bp.px) hipFree(bp.px);
-        if (bp.py) hipFree(bp.py);
-        if (bp.pyaw) hipFree(bp.pyaw);
         bp = rrtx_handle::BigPool();
         const size_t bytes = sizeof(double) * (size_t)big_cap * nr;
-        if (hipMalloc((void**)&bp.px, bytes) != hipSuccess || hipMalloc((void**)&bp.py, bytes) != hipSuccess ||
-            (c.algo == RRTX_ALGO_RS && hipMalloc((void**)&bp.pyaw, bytes) != hipSuccess)) {
+        if (bp.px.reserve(bytes) != hipSuccess || bp.py.reserve(bytes) != hipSuccess ||
+            (c.algo == RRTX_ALGO_RS && bp.pyaw.reserve(bytes) != hipSuccess)) {
           (void)hipGetLastError();   // no room for the larger pool: the instances keep their RRTX_ST_OVERFLOW
-          if (bp.px) hipFree(bp.px);
-          if (bp.py) hipFree(bp.py);
-          if (bp.pyaw) hipFree(bp.pyaw);
           bp = rrtx_handle::BigPool();
           break;
         }
@@ -1142,17 +1036,17 @@ static int plan_finish(rrtx_handle* h) {
       for (int k = 0; k < nr; k++) slot[redo[k]] = k;
       HIPCHK(h, hipMemcpyAsync(h->pool_slot, slot.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, h->stream));
       rppd::DubArgs dr = h->da;
-      dr.pool_x = bp.px; dr.pool_y = bp.py; dr.pool_yaw = bp.pyaw;
+      dr.pool_x = bp.px.as<double>(); dr.pool_y = bp.py.as<double>(); dr.pool_yaw = bp.pyaw.as<double>();
       dr.pool_cap = big_cap;
       dr.pool_slot = h->pool_slot;
-      rc = replan(h, redo, "pool retry", dr, false, [&](int32_t i) {
+      rc = replan(h, redo, "pool retry", dr, false, [&](int32_t i) -> int {
         HIPCHK(h, hipMemsetAsync(h->da.pool_used + i, 0, sizeof(int64_t), h->stream));
         return RRTX_OK;
       }, nullptr);
       if (rc) return rc;
       for (int k = 0; k < nr; k++) {
         rrtx_handle::PoolLoc& pl = h->pool_loc[redo[k]];
-        pl.px = bp.px; pl.py = bp.py; pl.pyaw = bp.pyaw;
+        pl.px = dr.pool_x; pl.py = dr.pool_y; pl.pyaw = dr.pool_yaw;
         pl.cap = big_cap; pl.slab = k;
       }
     }
@@ -1164,7 +1058,7 @@ static int plan_finish(rrtx_handle* h) {
     const std::vector<int32_t> redo = with_status(RRTX_ST_OVERFLOW);
     if (!redo.empty()) {
       const double inf1 = INFINITY;
-      rc = replan(h, redo, "overflow retry", h->da, true, [&](int32_t i) {
+      rc = replan(h, redo, "overflow retry", h->da, true, [&](int32_t i) -> int {
         HIPCHK(h, hipMemcpyAsync(h->cbest + i, &inf1, sizeof(double), hipMemcpyHostToDevice, h->stream));
         return RRTX_OK;
       }, nullptr);
@@ -1295,6 +1189,38 @@ int rrtx_get_tree(rrtx_handle* h, int32_t instance, double* x, double* y, double
   return RRTX_OK;
 }
 
+// generate_final_course of the pose planners: [goal] + reversed edge polylines up the parent chain + [start], `ncol` values
+// per point: the pool columns `cols` of the instance (x and y, or yaw) and components comp0 .. of the goal and start poses.
+// `out` NULL: the point count alone.
+static int final_course(rrtx_handle* h, int32_t instance, const Inst& I, const double* const* cols, int ncol, int comp0,
+                        double* out, int32_t cap_points, int32_t* n_out) {
+  const int n = I.n;
+  const int64_t off = (int64_t)instance * h->stride;
+  std::vector<int32_t> par(n), plen(n);
+  std::vector<int64_t> poff(n);
+  HIPCHK(h, hipMemcpy(par.data(), h->c.parent + off, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(plen.data(), h->da.plen + off, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(poff.data(), h->da.poff + off, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+  int64_t total = 2;
+  for (int nd = I.goal_node; par[nd] >= 0; nd = par[nd]) total += plen[nd];
+  *n_out = (int32_t)total;
+  if (!out) return RRTX_OK;
+  if (cap_points < total) return RRTX_E_CAPACITY;
+  for (int j = 0; j < ncol; j++) out[j] = I.goal[comp0 + j];
+  int64_t k = 1;
+  std::vector<double> buf;
+  for (int nd = I.goal_node; par[nd] >= 0; nd = par[nd]) {
+    buf.resize(plen[nd]);
+    for (int j = 0; j < ncol; j++) {
+      HIPCHK(h, hipMemcpy(buf.data(), h->pool_loc[instance].at(cols[j], poff[nd]), sizeof(double) * plen[nd], hipMemcpyDeviceToHost));
+      for (int q = plen[nd] - 1; q >= 0; q--) out[ncol * (k + plen[nd] - 1 - q) + j] = buf[q];
+    }
+    k += plen[nd];
+  }
+  for (int j = 0; j < ncol; j++) out[ncol * k + j] = I.start[comp0 + j];
+  return RRTX_OK;
+}
+
 int rrtx_get_path(rrtx_handle* h, int32_t instance, double* xy, int32_t cap_points, int32_t* n_out) {
   if (!h || instance < 0 || instance >= h->n_inst || !n_out) return RRTX_E_INVALID;
   if (!h->planned) return RRTX_E_STATE;
@@ -1316,41 +1242,10 @@ int rrtx_get_path(rrtx_handle* h, int32_t instance, double* xy, int32_t cap_poin
     HIPCHK(h, hipMemcpy(xy, d, sizeof(double) * 2 * oi[3], hipMemcpyDeviceToHost));
     return RRTX_OK;
   }
-  if (is_pose_tree(h->p.algo)) {
-    // generate_final_course (rrt_05:1512-1521): [goal] + reversed edge polylines up the parent chain + [start]
-    const int n = I.n;
-    const int64_t off = (int64_t)instance * h->stride;
-    std::vector<int32_t> par(n), plen(n);
-    std::vector<int64_t> poff(n);
-    HIPCHK(h, hipMemcpy(par.data(), h->c.parent + off, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(plen.data(), h->da.plen + off, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(poff.data(), h->da.poff + off, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
-    int64_t total = 2;
-    for (int nd = I.goal_node; par[nd] >= 0; nd = par[nd]) total += plen[nd];
-    *n_out = (int32_t)total;
-    if (!xy) return RRTX_OK;
-    if (cap_points < total) return RRTX_E_CAPACITY;
-    int64_t k = 0;
-    xy[0] = I.goal[0];
-    xy[1] = I.goal[1];
-    k = 1;
-    std::vector<double> bx, by;
-    for (int nd = I.goal_node; par[nd] >= 0; nd = par[nd]) {
-      bx.resize(plen[nd]);
-      by.resize(plen[nd]);
-      HIPCHK(h, hipMemcpy(bx.data(), h->pool_loc[instance].px + h->pool_loc[instance].slab * h->pool_loc[instance].cap + poff[nd],
-                          sizeof(double) * plen[nd], hipMemcpyDeviceToHost));
-      HIPCHK(h, hipMemcpy(by.data(), h->pool_loc[instance].py + h->pool_loc[instance].slab * h->pool_loc[instance].cap + poff[nd],
-                          sizeof(double) * plen[nd], hipMemcpyDeviceToHost));
-      for (int q = plen[nd] - 1; q >= 0; q--) {
-        xy[2 * k] = bx[q];
-        xy[2 * k + 1] = by[q];
-        k++;
-      }
-    }
-    xy[2 * k] = I.start[0];
-    xy[2 * k + 1] = I.start[1];
-    return RRTX_OK;
+  if (is_pose_tree(h->p.algo)) {   // rrt_05:1512-1521
+    const rrtx_handle::PoolLoc& pl = h->pool_loc[instance];
+    const double* cols[2] = {pl.px, pl.py};
+    return final_course(h, instance, I, cols, 2, 0, xy, cap_points, n_out);
   }
   *n_out = I.path_n;
   if (!xy) return RRTX_OK;
@@ -1431,30 +1326,7 @@ int rrtx_get_path_yaw(rrtx_handle* h, int32_t instance, double* yaw, int32_t cap
   HIPCHK(h, hipMemcpy(&I, h->c.inst + instance, sizeof(I), hipMemcpyDeviceToHost));
   *n_out = 0;
   if (!(I.status & RRTX_ST_PATH)) return RRTX_OK;
-  // generate_final_course (rrt_06:1643-1651): [goal yaw] + reversed edge-polyline yaws up the parent chain + [start yaw]
-  const int n = I.n;
-  const int64_t off = (int64_t)instance * h->stride;
-  std::vector<int32_t> par(n), plen(n);
-  std::vector<int64_t> poff(n);
-  HIPCHK(h, hipMemcpy(par.data(), h->c.parent + off, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-  HIPCHK(h, hipMemcpy(plen.data(), h->da.plen + off, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-  HIPCHK(h, hipMemcpy(poff.data(), h->da.poff + off, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
-  int64_t total = 2;
-  for (int nd = I.goal_node; par[nd] >= 0; nd = par[nd]) total += plen[nd];
-  *n_out = (int32_t)total;
-  if (!yaw) return RRTX_OK;
-  if (cap_points < total) return RRTX_E_CAPACITY;
-  int64_t k = 0;
-  yaw[k++] = I.goal[2];
-  std::vector<double> bw;
-  for (int nd = I.goal_node; par[nd] >= 0; nd = par[nd]) {
-    bw.resize(plen[nd]);
-    HIPCHK(h, hipMemcpy(bw.data(), h->pool_loc[instance].pyaw + h->pool_loc[instance].slab * h->pool_loc[instance].cap + poff[nd],
-                        sizeof(double) * plen[nd], hipMemcpyDeviceToHost));
-    for (int q = plen[nd] - 1; q >= 0; q--) yaw[k++] = bw[q];
-  }
-  yaw[k] = I.start[2];
-  return RRTX_OK;
+  return final_course(h, instance, I, &h->pool_loc[instance].pyaw, 1, 2, yaw, cap_points, n_out);   // rrt_06:1643-1651
 }
 
 // LQR-RRT*: Node.path_x / path_y regenerated on the device from each node's edge endpoints (rpp_lqr.h, the same code
@@ -1554,8 +1426,8 @@ int rrtx_get_polylines(rrtx_handle* h, int32_t instance, int32_t* plen, int32_t 
   std::vector<double> bx(used), by(used);
   if (used) {
     const rrtx_handle::PoolLoc& pl = h->pool_loc[instance];
-    HIPCHK(h, hipMemcpy(bx.data(), pl.px + pl.slab * pl.cap, sizeof(double) * used, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(by.data(), pl.py + pl.slab * pl.cap, sizeof(double) * used, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(bx.data(), pl.at(pl.px), sizeof(double) * used, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(by.data(), pl.at(pl.py), sizeof(double) * used, hipMemcpyDeviceToHost));
   }
   int64_t w = 0;
   for (int i = 0; i < n; i++) {
@@ -1647,74 +1519,6 @@ static int smooth_status_rc(const std::vector<int32_t>& st, std::string* err) {
   return RRTX_OK;
 }
 
-int rrtx_smooth_paths(int32_t device, int32_t n_jobs, const double* paths_xy, const int32_t* path_n, int32_t in_stride,
-                      int32_t max_iter, const double* obst_xyr, int32_t m, uint32_t* mt_words, int32_t* mt_pos,
-                      double* out_xy, int32_t out_stride, int32_t* out_n, int32_t* status) {
-  if (n_jobs < 1 || !paths_xy || !path_n || in_stride < 1 || max_iter < 0 || m < 0 || (m && !obst_xyr) || !mt_words ||
-      !mt_pos || !out_xy || out_stride < 1 || !out_n || !status || m > rpps::MOB)
-    return RRTX_E_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return RRTX_E_NO_DEVICE;
-  if (hipSetDevice(device) != hipSuccess) return RRTX_E_HIP;
-  std::vector<rpp::MT> rng(n_jobs);
-  for (int j = 0; j < n_jobs; j++) {
-    memcpy(rng[j].mt, mt_words + (size_t)j * 624, 624 * 4);
-    rng[j].pos = mt_pos[j];
-  }
-  std::vector<double> ox(m + 1), oy(m + 1), osz(m + 1);
-  for (int k = 0; k < m; k++) {
-    ox[k] = obst_xyr[3 * k];
-    oy[k] = obst_xyr[3 * k + 1];
-    osz[k] = obst_xyr[3 * k + 2];
-  }
-  double *d_in = nullptr, *d_out = nullptr, *d_ox = nullptr, *d_oy = nullptr, *d_osz = nullptr;
-  int32_t *d_n = nullptr, *d_on = nullptr, *d_st = nullptr, *d_obs = nullptr;
-  const int32_t obs_rows[2] = {0, m};   // every job: rows 0 .. m-1 (obs_stride 0)
-  rpp::MT* d_rng = nullptr;
-  int rc = RRTX_OK;
-  auto A = [&](void** q, size_t bytes) { if (rc == RRTX_OK && hipMalloc(q, bytes ? bytes : 8) != hipSuccess) rc = RRTX_E_HIP; };
-  A((void**)&d_in, sizeof(double) * 2 * (size_t)in_stride * n_jobs);
-  A((void**)&d_out, sizeof(double) * 2 * (size_t)out_stride * n_jobs);
-  A((void**)&d_ox, sizeof(double) * (m + 1));
-  A((void**)&d_oy, sizeof(double) * (m + 1));
-  A((void**)&d_osz, sizeof(double) * (m + 1));
-  A((void**)&d_n, sizeof(int32_t) * n_jobs);
-  A((void**)&d_on, sizeof(int32_t) * n_jobs);
-  A((void**)&d_st, sizeof(int32_t) * n_jobs);
-  A((void**)&d_obs, sizeof(obs_rows));
-  A((void**)&d_rng, sizeof(rpp::MT) * n_jobs);
-  std::vector<int32_t> st(n_jobs, 0);
-  if (rc == RRTX_OK) {
-    bool ok = hipMemcpy(d_in, paths_xy, sizeof(double) * 2 * (size_t)in_stride * n_jobs, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_ox, ox.data(), sizeof(double) * (m + 1), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_oy, oy.data(), sizeof(double) * (m + 1), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_osz, osz.data(), sizeof(double) * (m + 1), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_n, path_n, sizeof(int32_t) * n_jobs, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_obs, obs_rows, sizeof(obs_rows), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_rng, rng.data(), sizeof(rpp::MT) * n_jobs, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) {
-      rpps::SmoothArgs a{d_in, in_stride, d_n, 1, d_rng, (int64_t)sizeof(rpp::MT), d_ox, d_oy, d_osz, d_obs, 0,
-                         max_iter, d_out, out_stride, d_on, d_st};
-      hipLaunchKernelGGL(rpps::smooth_kernel, dim3(n_jobs), dim3(64), 0, 0, a, n_jobs);
-      ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-           hipMemcpy(out_xy, d_out, sizeof(double) * 2 * (size_t)out_stride * n_jobs, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(out_n, d_on, sizeof(int32_t) * n_jobs, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(st.data(), d_st, sizeof(int32_t) * n_jobs, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(rng.data(), d_rng, sizeof(rpp::MT) * n_jobs, hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    if (!ok) rc = RRTX_E_HIP;
-  }
-  for (void* q : {(void*)d_in, (void*)d_out, (void*)d_ox, (void*)d_oy, (void*)d_osz, (void*)d_n, (void*)d_on, (void*)d_st,
-                  (void*)d_obs, (void*)d_rng})
-    if (q) hipFree(q);
-  if (rc != RRTX_OK) return rc;
-  for (int j = 0; j < n_jobs; j++) {
-    memcpy(mt_words + (size_t)j * 624, rng[j].mt, 624 * 4);
-    mt_pos[j] = rng[j].pos;
-    status[j] = st[j];
-  }
-  return smooth_status_rc(st, nullptr);
-}
 
 int rrtx_smooth_planned(rrtx_handle* h, int32_t max_iter) {
   if (!h || max_iter < 0) return RRTX_E_INVALID;
@@ -1780,11 +1584,7 @@ int rrtx_track_planned(rrtx_handle* h, const rrtx_track_params* tp) {
   if (!h->planned || h->p.algo != RRTX_ALGO_RS) return RRTX_E_STATE;
   int rc = refuse_in_plan(h, "rrtx_track_planned");
   if (rc) return rc;
-  if (!(tp->dt > 0.0) || !(tp->T >= 0.0) || !(tp->T / tp->dt <= 1.0e6) || !(tp->Lf > 0.0) || !(tp->L > 0.0) ||
-      !(tp->steer_max >= 0.0 && tp->steer_max <= 0.79)) {
-    h->err = "rrtx_track_planned: needs dt > 0, T / dt <= 1e6, Lf > 0, L > 0, 0 <= steer_max <= 0.79";
-    return RRTX_E_INVALID;
-  }
+  if (!track_params_ok(tp)) return fail(h, RRTX_E_INVALID, std::string("rrtx_track_planned: ") + TRACK_PARAMS_MSG);
   HIPCHK(h, hipSetDevice(h->device));
   rrtx_handle::Track& K = h->tk;
   const int B = h->n_inst;
@@ -1806,9 +1606,9 @@ int rrtx_track_planned(rrtx_handle* h, const rrtx_track_params* tp) {
   std::vector<const double*> pp((size_t)3 * B);
   for (int i = 0; i < B; i++) {
     const rrtx_handle::PoolLoc& pl = h->pool_loc[i];
-    pp[3 * i] = pl.px + pl.slab * pl.cap;
-    pp[3 * i + 1] = pl.py + pl.slab * pl.cap;
-    pp[3 * i + 2] = pl.pyaw + pl.slab * pl.cap;
+    pp[3 * i] = pl.at(pl.px);
+    pp[3 * i + 1] = pl.at(pl.py);
+    pp[3 * i + 2] = pl.at(pl.pyaw);
   }
   HIPCHK(h, hipMemcpyAsync(K.pool, pp.data(), sizeof(double*) * pp.size(), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemsetAsync(K.counters, 0, sizeof(int32_t) * 4, h->stream));
@@ -1826,9 +1626,6 @@ int rrtx_track_planned(rrtx_handle* h, const rrtx_track_params* tp) {
   a.ox = h->c.ox;
   a.oy = h->c.oy;
   a.othr = h->c.othr;
-  static_assert(sizeof(rppt::Params) == sizeof(rrtx_track_params), "rrtx_track_params mirrors rppt::Params");
-  static_assert(sizeof(rppt::Outcome) == sizeof(rrtx_track_outcome), "rrtx_track_outcome mirrors rppt::Outcome");
-  static_assert(sizeof(rppt::Record) == sizeof(rrtx_track_record), "rrtx_track_record mirrors rppt::Record");
   memcpy(&a.P, tp, sizeof(a.P));
   a.n_inst = B;
   a.cand = K.cand;
@@ -1840,16 +1637,16 @@ int rrtx_track_planned(rrtx_handle* h, const rrtx_track_params* tp) {
   a.out_off = K.out_off;
   K.h_outc.resize(B);
   K.h_off.assign(B, 0);
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  hipLaunchKernelGGL(rppt::track_list_kernel, dim3(B), dim3(rppt::TPB), 0, h->stream, a);
-  hipLaunchKernelGGL(rppt::track_roll_kernel, dim3(K.blocks), dim3(rppt::TPB), 0, h->stream, a, 0);
-  hipLaunchKernelGGL(rppt::track_pick_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, a);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  HIPCHK(h, hipMemcpyAsync(K.h_outc.data(), K.outc, sizeof(rppt::Outcome) * B, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
   float ms = 0.f;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  rc = h->timed(&ms, [&] {
+    hipLaunchKernelGGL(rppt::track_list_kernel, dim3(B), dim3(rppt::TPB), 0, h->stream, a);
+    hipLaunchKernelGGL(rppt::track_roll_kernel, dim3(K.blocks), dim3(rppt::TPB), 0, h->stream, a, 0);
+    hipLaunchKernelGGL(rppt::track_pick_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, a);
+  }, [&]() -> int {
+    HIPCHK(h, hipMemcpyAsync(K.h_outc.data(), K.outc, sizeof(rppt::Outcome) * B, hipMemcpyDeviceToHost, h->stream));
+    return RRTX_OK;
+  });
+  if (rc) return rc;
   K.ms = ms;
   // the winners' arrays: 7 x (len + 1) doubles per instance with a feasible roll-out, packed
   int64_t need = 0;
@@ -1861,27 +1658,15 @@ int rrtx_track_planned(rrtx_handle* h, const rrtx_track_params* tp) {
       winners++;
     }
   }
-  // K.out is the one tracking buffer whose size depends on the plan (the winners' lengths), so it is the only one that is
-  // regrown and hence not on the handle's `allocs` list: rrtx_destroy frees it by name.
-  if (need > K.out_cap) {
-    if (K.out) hipFree(K.out);
-    K.out = nullptr;
-    K.out_cap = 0;
-    void* q = nullptr;
-    HIPCHK(h, hipMalloc(&q, sizeof(double) * (size_t)need));
-    K.out = (double*)q;
-    K.out_cap = need;
-  }
+  if ((rc = h->reserve(K.out, sizeof(double) * (size_t)need))) return rc;
   if (winners) {
-    a.out = K.out;
+    a.out = K.out.as<double>();
     HIPCHK(h, hipMemcpyAsync(K.out_off, K.h_off.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(K.counters + 1, 0, sizeof(int32_t), h->stream));
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(rppt::track_roll_kernel, dim3(winners < K.blocks ? winners : K.blocks), dim3(rppt::TPB), 0, h->stream, a, 1);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    rc = h->timed(&ms, [&] {
+      hipLaunchKernelGGL(rppt::track_roll_kernel, dim3(winners < K.blocks ? winners : K.blocks), dim3(rppt::TPB), 0, h->stream, a, 1);
+    });
+    if (rc) return rc;
     K.ms += ms;
   }
   K.valid = true;
@@ -1907,7 +1692,7 @@ int rrtx_get_track_arrays(rrtx_handle* h, int32_t instance, double* x, double* y
   HIPCHK(h, hipSetDevice(h->device));
   const int64_t os = (int64_t)o.len + 1;
   std::vector<double> buf((size_t)(7 * os));
-  HIPCHK(h, hipMemcpy(buf.data(), h->tk.out + h->tk.h_off[instance], sizeof(double) * buf.size(), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(buf.data(), h->tk.out.as<double>() + h->tk.h_off[instance], sizeof(double) * buf.size(), hipMemcpyDeviceToHost));
   double* dst[7] = {x, y, yaw, v, t, a, d};
   for (int k = 0; k < 7; k++) memcpy(dst[k], buf.data() + k * os, sizeof(double) * (size_t)(k < 3 ? os : os - 1));
   return RRTX_OK;
@@ -1942,881 +1727,9 @@ int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps) {
   return RRTX_OK;
 }
 
-int rrtx_selftest_math(int32_t device, int32_t op, const double* a, const double* b, double* out, int64_t n) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return RRTX_E_NO_DEVICE;
-  if (!a || !b || !out || n < 0) return RRTX_E_INVALID;
-  if (hipSetDevice(device) != hipSuccess) return RRTX_E_HIP;
-  double *da = nullptr, *db = nullptr, *dout = nullptr;
-  int rc = RRTX_OK;
-  if (hipMalloc(&da, n * 8) != hipSuccess || hipMalloc(&db, n * 8) != hipSuccess ||
-      hipMalloc(&dout, n * 8) != hipSuccess)
-    rc = RRTX_E_HIP;
-  if (!rc && (hipMemcpy(da, a, n * 8, hipMemcpyHostToDevice) != hipSuccess ||
-              hipMemcpy(db, b, n * 8, hipMemcpyHostToDevice) != hipSuccess))
-    rc = RRTX_E_HIP;
-  if (!rc) {
-    hipLaunchKernelGGL(rppk::selftest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, da, db, dout, n);
-    if (hipDeviceSynchronize() != hipSuccess) rc = RRTX_E_HIP;
-  }
-  if (!rc && hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = RRTX_E_HIP;
-  hipFree(da);
-  hipFree(db);
-  hipFree(dout);
-  return rc;
-}
-
-int rrtx_selfcheck(int32_t device, int32_t n_per_fn, int64_t* mismatches8) {
-  if (!mismatches8 || n_per_fn < 1 || n_per_fn > (1 << 22)) return RRTX_E_INVALID;
-  const int64_t n = n_per_fn;
-  std::vector<double> a(n), b(n), out(n);
-  // splitmix64 -> uniform in [0, 1): the same arguments on every host
-  uint64_t sm = 0x9e3779b97f4a7c15ULL;
-  auto u01 = [&]() {
-    uint64_t z = (sm += 0x9e3779b97f4a7c15ULL);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-  };
-  // selftest op, argument ranges: coordinates differences up to a few hundred, angles within a few turns (Dubins /
-  // Reeds-Shepp sums, 2*pi*a/b of the unit-ball sample), |x| <= 1 for the inverse functions
-  struct Fn { int op; double lo_a, hi_a, lo_b, hi_b; } fns[8] = {
-      {1, -300.0, 300.0, 0.0, 1.0}, {2, -20.0, 20.0, 0.0, 1.0}, {3, -20.0, 20.0, 0.0, 1.0}, {4, -300.0, 300.0, -300.0, 300.0},
-      {8, -1.0, 1.0, 0.0, 1.0},     {9, -1.0, 1.0, 0.0, 1.0},   {6, 0.0, 1.0e5, 0.0, 1.0},  {7, -300.0, 300.0, -300.0, 300.0}};
-  for (int f = 0; f < 8; f++) {
-    for (int64_t i = 0; i < n; i++) {
-      a[i] = fns[f].lo_a + (fns[f].hi_a - fns[f].lo_a) * u01();
-      b[i] = fns[f].lo_b + (fns[f].hi_b - fns[f].lo_b) * u01();
-      if (i % 7 == 3 && (fns[f].op == 1 || fns[f].op == 4)) a[i] *= 1.0 / 1024.0;   // small arguments too
-    }
-    int rc = rrtx_selftest_math(device, fns[f].op, a.data(), b.data(), out.data(), n);
-    if (rc) return rc;
-    int64_t bad = 0;
-    for (int64_t i = 0; i < n; i++) {
-      double r;
-      switch (fns[f].op) {
-        case 1: r = py_sq_host(a[i]); break;
-        case 2: r = libm_sin(a[i]); break;
-        case 3: r = libm_cos(a[i]); break;
-        case 4: r = libm_atan2(a[i], b[i]); break;
-        case 8: r = libm_acos(a[i]); break;
-        case 9: r = libm_asin(a[i]); break;
-        case 6: r = libm_sqrt(a[i]); break;
-        default: r = a[i] / b[i]; break;
-      }
-      if (memcmp(&r, &out[i], 8) != 0) bad++;
-    }
-    mismatches8[f] = bad;
-  }
-  return RRTX_OK;
-}
-
-// ---- native RCCL: the one collective of the path (ncclAllGather of the 16-byte result records over xGMI) ----------
-
-int rrtx_rccl_unique_id(void* id128) {
-  if (!id128) return RRTX_E_INVALID;
-  RcclApi* a = rccl_api();
-  if (!a->lib) return RRTX_E_STATE;
-  ncclUniqueId id;
-  if (a->GetUniqueId(&id) != ncclSuccess) return RRTX_E_HIP;
-  memcpy(id128, &id, sizeof(id));
-  return RRTX_OK;
-}
-
-int rrtx_rccl_init(rrtx_handle* h, const void* id128, int32_t rank, int32_t world) {
-  if (!h || !id128 || world < 1 || rank < 0 || rank >= world) return RRTX_E_INVALID;
-  RcclApi* a = rccl_api();
-  if (!a->lib) {
-    h->err = a->err;
-    return RRTX_E_STATE;
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  if (h->rccl_comm) {
-    a->CommDestroy((ncclComm_t)h->rccl_comm);
-    h->rccl_comm = nullptr;
-  }
-  ncclUniqueId id;
-  memcpy(&id, id128, sizeof(id));
-  ncclComm_t comm = nullptr;
-  const ncclResult_t r = a->CommInitRank(&comm, world, id, rank);
-  if (r != ncclSuccess) {
-    h->err = std::string("ncclCommInitRank: ") + (a->GetErrorString ? a->GetErrorString(r) : "error");
-    return RRTX_E_HIP;
-  }
-  h->rccl_comm = (void*)comm;
-  h->rccl_world = world;
-  h->rccl_rank = rank;
-  if (!h->rccl_recv) {
-    int rc = dalloc(h, &h->rccl_recv, (size_t)h->n_inst * world);
-    if (rc) return rc;
-  }
-  return RRTX_OK;
-}
-
-int rrtx_rccl_gather_results(rrtx_handle* h, double* path_cost, int32_t* n_nodes, int32_t* status) {
-  if (!h) return RRTX_E_INVALID;
-  if (!h->planned || !h->rccl_comm) return RRTX_E_STATE;
-  RcclApi* a = rccl_api();
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t bytes = sizeof(Result) * (size_t)h->n_inst;
-  // device -> device: the table the planner kernels wrote is what the collective sends
-  const ncclResult_t r = a->AllGather(h->c.results, h->rccl_recv, bytes, ncclInt8, (ncclComm_t)h->rccl_comm, h->stream);
-  if (r != ncclSuccess) {
-    h->err = std::string("ncclAllGather: ") + (a->GetErrorString ? a->GetErrorString(r) : "error");
-    return RRTX_E_HIP;
-  }
-  const size_t tot = (size_t)h->n_inst * h->rccl_world;
-  std::vector<Result> all(tot);
-  HIPCHK(h, hipMemcpyAsync(all.data(), h->rccl_recv, sizeof(Result) * tot, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  for (size_t i = 0; i < tot; i++) {
-    if (path_cost) path_cost[i] = (all[i].status & RRTX_ST_PATH) ? all[i].path_cost : INFINITY;
-    if (n_nodes) n_nodes[i] = all[i].n_nodes;
-    if (status) status[i] = all[i].status;
-  }
-  return RRTX_OK;
-}
-
-int rrtx_plan_many(rrtx_handle** handles, int32_t n, int32_t* rcs) {
-  if (!handles || n < 1) return RRTX_E_INVALID;
-  for (int i = 0; i < n; i++)
-    if (!handles[i]) return RRTX_E_INVALID;
-  for (int i = 0; i < n; i++)
-    for (int j = 0; j < i; j++)
-      if (handles[i] == handles[j]) return RRTX_E_INVALID;   // a handle is not thread safe
-  std::vector<int> rc(n, RRTX_OK);
-  if (n == 1) {
-    rc[0] = rrtx_plan(handles[0]);
-  } else {
-    std::vector<std::thread> th;
-    th.reserve(n);
-    for (int i = 0; i < n; i++) th.emplace_back([&rc, handles, i]() { rc[i] = rrtx_plan(handles[i]); });
-    for (auto& t : th) t.join();
-  }
-  int worst = RRTX_OK;
-  for (int i = 0; i < n; i++) {
-    if (rcs) rcs[i] = rc[i];
-    if (rc[i] < 0 && (worst >= 0 || rc[i] < worst)) worst = rc[i];
-    else if (rc[i] == RRTX_PARTIAL && worst == RRTX_OK) worst = RRTX_PARTIAL;
-  }
-  return worst;
-}
-
 }  // extern "C"
 
-// ---- batched Dubins / Reeds-Shepp curves between pose pairs (steer_batch.hip.h) -----------------------------------------
-struct rrtx_steer {
-  int device = 0;
-  bool usable = false;        // a gfx950 device was found at creation
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  std::string err;
-  // device buffers, grown on demand
-  struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-  };
-  Buf starts, goals, curv, status, nseg, total, seglen, modes, npts, plan, offsets, px, py, pyaw, flag, obs, hit;
-  // the obstacle list of rrtx_steer_set_obstacles: packed rows (ox, oy, thr); it goes to the device at the next solve
-  std::vector<double> h_obs;
-  bool obs_dirty = false;
-  // the last solve
-  bool solved = false, has_points = false, has_hits = false;
-  int64_t n = 0, n_points = 0;
-  double kernel_ms = 0.0;
-  std::vector<int64_t> h_offsets;
-};
-
-namespace {
-thread_local std::string steer_null_err;
-
-int steer_fail(rrtx_steer* s, int rc, const std::string& msg) {
-  (s ? s->err : steer_null_err) = msg;
-  return rc;
-}
-#define STEERCHK(s, expr)                                                                    \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return steer_fail(s, RRTX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-// at least `bytes` in b; contents are not kept
-int steer_reserve(rrtx_steer* s, rrtx_steer::Buf& b, size_t bytes) {
-  if (bytes <= b.bytes) return RRTX_OK;
-  if (b.p) hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-  STEERCHK(s, hipMalloc(&b.p, bytes));
-  b.bytes = bytes;
-  return RRTX_OK;
-}
-
-// stage 2 with or without the stores and the obstacle check; one of the two is wanted
-template <int KIND>
-void steer_launch_fill(bool store, bool check, unsigned blocks, hipStream_t stream, const rppsb::Args& a) {
-  if (store && check)
-    hipLaunchKernelGGL((rppsb::steer_fill<KIND, true, true>), dim3(blocks), dim3(rppsb::TPB), 0, stream, a);
-  else if (store)
-    hipLaunchKernelGGL((rppsb::steer_fill<KIND, true, false>), dim3(blocks), dim3(rppsb::TPB), 0, stream, a);
-  else
-    hipLaunchKernelGGL((rppsb::steer_fill<KIND, false, true>), dim3(blocks), dim3(rppsb::TPB), 0, stream, a);
-}
-}  // namespace
-
-extern "C" {
-
-int rrtx_steer_create(int32_t device, rrtx_steer** out) {
-  if (!out) return steer_fail(nullptr, RRTX_E_INVALID, "rrtx_steer_create: out is NULL");
-  *out = nullptr;
-  if (device < 0) return steer_fail(nullptr, RRTX_E_INVALID, "rrtx_steer_create: negative device ordinal");
-  rrtx_steer* s = new (std::nothrow) rrtx_steer();
-  if (!s) return steer_fail(nullptr, RRTX_E_HIP, "rrtx_steer_create: out of host memory");
-  s->device = device;
-  *out = s;   // returned on failure too: the caller reads the message, and solves still check their arguments
-  int ndev = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device >= ndev ||
-      hipGetDeviceProperties(&prop, device) != hipSuccess ||
-      (!strstr(prop.gcnArchName, "gfx950") && !getenv("RRTX_ALLOW_ANY_ARCH")))
-    return steer_fail(s, RRTX_E_NO_DEVICE, "rrtx_steer_create: no usable gfx950 device (there is no CPU fallback)");
-  STEERCHK(s, hipSetDevice(device));
-  STEERCHK(s, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  for (auto& e : s->ev) STEERCHK(s, hipEventCreate(&e));
-  s->usable = true;
-  return RRTX_OK;
-}
-
-void rrtx_steer_destroy(rrtx_steer* s) {
-  if (!s) return;
-  if (s->usable) {
-    hipSetDevice(s->device);
-    for (rrtx_steer::Buf* b : {&s->starts, &s->goals, &s->curv, &s->status, &s->nseg, &s->total, &s->seglen, &s->modes,
-                               &s->npts, &s->plan, &s->offsets, &s->px, &s->py, &s->pyaw, &s->flag, &s->obs, &s->hit})
-      if (b->p) hipFree(b->p);
-    for (auto& e : s->ev)
-      if (e) hipEventDestroy(e);
-    if (s->stream) hipStreamDestroy(s->stream);
-  }
-  delete s;
-}
-
-const char* rrtx_steer_last_error(rrtx_steer* s) { return s ? s->err.c_str() : steer_null_err.c_str(); }
-
-static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
-                       const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
-                       const int32_t* word_order, int32_t n_words, int32_t want_points) {
-  const char* fn = "rrtx_steer_solve: ";
-  auto bad = [&](const char* m) { return steer_fail(s, RRTX_E_INVALID, std::string(fn) + m); };
-  if (!s) return bad("the steer object is NULL");
-  if (kind != RRTX_STEER_DUBINS && kind != RRTX_STEER_RS) return bad("unknown kind");
-  if (!starts || !goals || !curvature) return bad("starts, goals or curvature is NULL");
-  if (n < 0 || (product && ng < 0)) return bad("a negative batch size");
-  if (!(step_size > 0.0)) return bad("step_size must be > 0");
-  if (kind == RRTX_STEER_DUBINS && step_size != rpp::kDubinsStep)
-    return bad("Dubins curves are interpolated at the reference's default step_size = 0.1; another step is not supported");
-  if (word_order) {
-    if (kind != RRTX_STEER_DUBINS) return bad("a word order applies to Dubins curves only");
-    if (n_words < 0 || n_words > 6) return bad("n_words outside 0..6");
-    for (int i = 0; i < n_words; i++)
-      if (word_order[i] < 0 || word_order[i] > 5) return bad("a word index outside 0..5");
-  }
-  const int64_t n_goals = product ? ng : n;
-  if (n > (1LL << 30) || n_goals > (1LL << 30) || (product && n && ng && n > (1LL << 30) / ng))
-    return bad("more than 2^30 pairs");
-  const int64_t np = product ? n * ng : n;
-  // Every pose and curvature is looked at once here: a curve's point count grows with distance x curvature / step, and the
-  // kernels count points in loops, so an absurd input must never reach them.
-  double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
-  for (int side = 0; side < 2; side++) {
-    const double* q = side ? goals : starts;
-    const int64_t rows = side ? n_goals : n;
-    for (int64_t i = 0; i < rows; i++)
-      for (int c = 0; c < 3; c++) {
-        const double v = q[3 * i + c];
-        if (!(fabs(v) <= 1e6)) return bad("a pose component is not finite or exceeds 1e6 in magnitude");
-        if (c < 2) {
-          lo[c] = v < lo[c] ? v : lo[c];
-          hi[c] = v > hi[c] ? v : hi[c];
-        }
-      }
-  }
-  double cmin = 1e300, cmax = 0.0;
-  const int64_t nc = curvature_per_pair ? np : 1;
-  for (int64_t i = 0; i < nc; i++) {
-    const double c = curvature[i];
-    if (!(c > 0.0) || !(c <= 1e300)) return bad("a curvature is not finite or not > 0");
-    cmin = c < cmin ? c : cmin;
-    cmax = c > cmax ? c : cmax;
-  }
-  if (np > 0) {
-    const double D = hypot(hi[0] - lo[0], hi[1] - lo[1]);
-    const double pts = kind == RRTX_STEER_DUBINS ? (D * cmax + 20.0) / rpp::kDubinsStep
-                                                 : D / step_size + 20.0 / (step_size * cmin);
-    if (!(pts <= 4194304.0)) return bad("the poses are so far apart for this curvature and step that a curve could exceed 2^22 points");
-  }
-  if (!s->usable) return steer_fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
-  // With an obstacle list the curves' points are computed (stage 1 as for points, then the fill kernel) whether or not
-  // they are stored.
-  const int64_t n_obs = (int64_t)(s->h_obs.size() / 3);
-  const bool stage2 = want_points || n_obs > 0;
-
-  s->solved = false;
-  s->has_points = false;
-  s->has_hits = false;
-  s->n = np;
-  s->n_points = 0;
-  s->kernel_ms = 0.0;
-  s->h_offsets.clear();
-  if (np == 0) {
-    s->has_points = want_points != 0;
-    s->has_hits = n_obs > 0;
-    s->h_offsets.assign(1, 0);
-    s->solved = true;
-    return RRTX_OK;
-  }
-  STEERCHK(s, hipSetDevice(s->device));
-  int rc;
-  const size_t N = (size_t)np;
-  if ((rc = steer_reserve(s, s->starts, sizeof(double) * 3 * (size_t)n))) return rc;
-  if ((rc = steer_reserve(s, s->goals, sizeof(double) * 3 * (size_t)n_goals))) return rc;
-  if ((rc = steer_reserve(s, s->curv, sizeof(double) * (size_t)nc))) return rc;
-  if ((rc = steer_reserve(s, s->status, sizeof(int32_t) * N))) return rc;
-  if ((rc = steer_reserve(s, s->nseg, sizeof(int32_t) * N))) return rc;
-  if ((rc = steer_reserve(s, s->total, sizeof(double) * N))) return rc;
-  if ((rc = steer_reserve(s, s->seglen, sizeof(double) * 5 * N))) return rc;
-  if ((rc = steer_reserve(s, s->modes, 8 * N))) return rc;
-  if ((rc = steer_reserve(s, s->npts, sizeof(int32_t) * N))) return rc;
-  if ((rc = steer_reserve(s, s->flag, sizeof(int32_t)))) return rc;
-  if (stage2) {
-    const size_t rec = kind == RRTX_STEER_DUBINS ? sizeof(rpp::DubinsPlan) : sizeof(rpp::RsCourse);
-    if ((rc = steer_reserve(s, s->plan, rec * N))) return rc;
-    if ((rc = steer_reserve(s, s->offsets, sizeof(int64_t) * (N + 1)))) return rc;
-  }
-  if (n_obs > 0) {
-    if ((rc = steer_reserve(s, s->hit, sizeof(int32_t) * N))) return rc;
-    if (s->obs_dirty) {
-      if ((rc = steer_reserve(s, s->obs, sizeof(double) * s->h_obs.size()))) return rc;
-      STEERCHK(s, hipMemcpyAsync(s->obs.p, s->h_obs.data(), sizeof(double) * s->h_obs.size(), hipMemcpyHostToDevice, s->stream));
-      s->obs_dirty = false;
-    }
-  }
-  STEERCHK(s, hipMemcpyAsync(s->starts.p, starts, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, s->stream));
-  STEERCHK(s, hipMemcpyAsync(s->goals.p, goals, sizeof(double) * 3 * (size_t)n_goals, hipMemcpyHostToDevice, s->stream));
-  STEERCHK(s, hipMemcpyAsync(s->curv.p, curvature, sizeof(double) * (size_t)nc, hipMemcpyHostToDevice, s->stream));
-  STEERCHK(s, hipMemsetAsync(s->flag.p, 0, sizeof(int32_t), s->stream));
-
-  rppsb::Args a;
-  memset(&a, 0, sizeof(a));
-  a.starts = (const double*)s->starts.p;
-  a.goals = (const double*)s->goals.p;
-  a.curv = curvature_per_pair ? (const double*)s->curv.p : nullptr;
-  a.curv0 = curvature[0];
-  a.step = step_size;
-  a.n = np;
-  a.ng = product ? ng : 1;
-  a.product = product ? 1 : 0;
-  a.want_points = stage2 ? 1 : 0;
-  a.n_order = word_order ? n_words : 6;
-  for (int i = 0; i < 6; i++) a.order[i] = (word_order && i < n_words) ? word_order[i] : i;
-  a.status = (int32_t*)s->status.p;
-  a.nseg = (int32_t*)s->nseg.p;
-  a.total = (double*)s->total.p;
-  a.seglen = (double*)s->seglen.p;
-  a.modes = (char*)s->modes.p;
-  a.npts = (int32_t*)s->npts.p;
-  a.dplan = (rpp::DubinsPlan*)s->plan.p;
-  a.course = (rpp::RsCourse*)s->plan.p;
-  a.flag = (int32_t*)s->flag.p;
-  if (n_obs > 0) {
-    a.obs = (const double*)s->obs.p;
-    a.n_obs = n_obs;
-    a.hit = (int32_t*)s->hit.p;
-  }
-
-  // stage 1
-  const unsigned blk = (unsigned)((np + rppsb::TPB - 1) / rppsb::TPB);
-  STEERCHK(s, hipEventRecord(s->ev[0], s->stream));
-  if (kind == RRTX_STEER_DUBINS) {
-    hipLaunchKernelGGL(rppsb::steer_dubins_solve, dim3(blk), dim3(rppsb::TPB), 0, s->stream, a);
-  } else {
-    hipLaunchKernelGGL(rppsb::steer_rs_solve, dim3((unsigned)((np + rppsb::RS_PAIRS - 1) / rppsb::RS_PAIRS)),
-                       dim3(rppsb::RS_TPB), 0, s->stream, a);
-    if (stage2) hipLaunchKernelGGL(rppsb::steer_rs_course, dim3(blk), dim3(rppsb::TPB), 0, s->stream, a);
-  }
-  STEERCHK(s, hipGetLastError());
-  STEERCHK(s, hipEventRecord(s->ev[1], s->stream));
-  int32_t flag = 0;
-  STEERCHK(s, hipMemcpyAsync(&flag, s->flag.p, sizeof(flag), hipMemcpyDeviceToHost, s->stream));
-  std::vector<int32_t> cnt;
-  if (stage2) {
-    cnt.resize(N);
-    STEERCHK(s, hipMemcpyAsync(cnt.data(), s->npts.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
-  }
-  STEERCHK(s, hipStreamSynchronize(s->stream));
-  float ms = 0.f;
-  STEERCHK(s, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-  s->kernel_ms = ms;
-
-  if (stage2) {
-    // offsets: exclusive prefix sum of the point counts
-    s->h_offsets.resize(N + 1);
-    int64_t tot = 0;
-    for (size_t i = 0; i < N; i++) {
-      s->h_offsets[i] = tot;
-      tot += cnt[i] > 0 ? cnt[i] : 0;
-    }
-    s->h_offsets[N] = tot;
-    s->n_points = want_points ? tot : 0;
-    if (tot > 0) {
-      if (want_points) {
-        if ((rc = steer_reserve(s, s->px, sizeof(double) * (size_t)tot))) return rc;
-        if ((rc = steer_reserve(s, s->py, sizeof(double) * (size_t)tot))) return rc;
-        if ((rc = steer_reserve(s, s->pyaw, sizeof(double) * (size_t)tot))) return rc;
-      }
-      if ((tot + rppsb::TPB - 1) / rppsb::TPB > 0x7fffffffLL)
-        return steer_fail(s, RRTX_E_OVERFLOW, std::string(fn) + "more polyline points than one launch can fill");
-      STEERCHK(s, hipMemcpyAsync(s->offsets.p, s->h_offsets.data(), sizeof(int64_t) * (N + 1), hipMemcpyHostToDevice, s->stream));
-      a.offsets = (const int64_t*)s->offsets.p;
-      if (want_points) {
-        a.px = (double*)s->px.p;
-        a.py = (double*)s->py.p;
-        a.pyaw = (double*)s->pyaw.p;
-      }
-      const unsigned fblk = (unsigned)((tot + rppsb::TPB - 1) / rppsb::TPB);
-      STEERCHK(s, hipEventRecord(s->ev[2], s->stream));
-      if (kind == RRTX_STEER_DUBINS)
-        steer_launch_fill<rppsb::KIND_DUBINS>(want_points != 0, n_obs > 0, fblk, s->stream, a);
-      else
-        steer_launch_fill<rppsb::KIND_RS>(want_points != 0, n_obs > 0, fblk, s->stream, a);
-      STEERCHK(s, hipGetLastError());
-      STEERCHK(s, hipEventRecord(s->ev[3], s->stream));
-      STEERCHK(s, hipStreamSynchronize(s->stream));
-      STEERCHK(s, hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
-      s->kernel_ms += ms;
-    }
-    if (!want_points) s->h_offsets.clear();   // a lengths-only solve keeps no offsets, checked or not
-    s->has_points = want_points != 0;
-  }
-  s->has_hits = n_obs > 0;
-  s->solved = true;
-  if (flag) {
-    s->err = std::string(fn) + "some pairs have no path or are cases where the reference raises (see the status column)";
-    return RRTX_PARTIAL;
-  }
-  return RRTX_OK;
-}
-
-int rrtx_steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
-                     const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
-                     const int32_t* word_order, int32_t n_words, int32_t want_points) {
-  try {   // host allocations (offsets, messages) must not throw across the ABI
-    return steer_solve(s, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size, word_order, n_words,
-                       want_points);
-  } catch (const std::exception& e) {
-    if (s) s->solved = false;
-    return steer_fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve: ") + e.what());
-  }
-}
-
-int rrtx_steer_get_counts(rrtx_steer* s, int64_t* n_pairs, int64_t* n_points) {
-  if (!s || !n_pairs || !n_points) return steer_fail(s, RRTX_E_INVALID, "rrtx_steer_get_counts: a NULL pointer");
-  if (!s->solved) return steer_fail(s, RRTX_E_STATE, "rrtx_steer_get_counts: no completed solve");
-  *n_pairs = s->n;
-  *n_points = s->n_points;
-  return RRTX_OK;
-}
-
-int rrtx_steer_get_summary(rrtx_steer* s, int32_t* status, double* length, int32_t* n_seg, double* seg_len, char* modes,
-                           int64_t* offsets) {
-  if (!s) return steer_fail(s, RRTX_E_INVALID, "rrtx_steer_get_summary: the steer object is NULL");
-  if (!s->solved) return steer_fail(s, RRTX_E_STATE, "rrtx_steer_get_summary: no completed solve");
-  if (offsets && !s->has_points)
-    return steer_fail(s, RRTX_E_STATE, "rrtx_steer_get_summary: the last solve was lengths-only, it has no offsets");
-  if (offsets) memcpy(offsets, s->h_offsets.data(), sizeof(int64_t) * s->h_offsets.size());
-  if (s->n == 0) return RRTX_OK;
-  const size_t N = (size_t)s->n;
-  STEERCHK(s, hipSetDevice(s->device));
-  if (status) STEERCHK(s, hipMemcpy(status, s->status.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
-  if (length) STEERCHK(s, hipMemcpy(length, s->total.p, sizeof(double) * N, hipMemcpyDeviceToHost));
-  if (n_seg) STEERCHK(s, hipMemcpy(n_seg, s->nseg.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
-  if (seg_len) STEERCHK(s, hipMemcpy(seg_len, s->seglen.p, sizeof(double) * 5 * N, hipMemcpyDeviceToHost));
-  if (modes) STEERCHK(s, hipMemcpy(modes, s->modes.p, 8 * N, hipMemcpyDeviceToHost));
-  return RRTX_OK;
-}
-
-int rrtx_steer_get_points(rrtx_steer* s, double* x, double* y, double* yaw, int64_t cap) {
-  if (!s) return steer_fail(s, RRTX_E_INVALID, "rrtx_steer_get_points: the steer object is NULL");
-  if (!s->solved || !s->has_points) return steer_fail(s, RRTX_E_STATE, "rrtx_steer_get_points: no completed solve with points");
-  if (cap < s->n_points) return steer_fail(s, RRTX_E_CAPACITY, "rrtx_steer_get_points: the buffers are too small");
-  if (s->n_points == 0) return RRTX_OK;
-  const size_t bytes = sizeof(double) * (size_t)s->n_points;
-  STEERCHK(s, hipSetDevice(s->device));
-  if (x) STEERCHK(s, hipMemcpy(x, s->px.p, bytes, hipMemcpyDeviceToHost));
-  if (y) STEERCHK(s, hipMemcpy(y, s->py.p, bytes, hipMemcpyDeviceToHost));
-  if (yaw) STEERCHK(s, hipMemcpy(yaw, s->pyaw.p, bytes, hipMemcpyDeviceToHost));
-  return RRTX_OK;
-}
-
-int rrtx_steer_set_obstacles(rrtx_steer* s, const double* obstacles, int64_t m, double robot_radius) {
-  const char* fn = "rrtx_steer_set_obstacles: ";
-  auto bad = [&](const char* msg) { return steer_fail(s, RRTX_E_INVALID, std::string(fn) + msg); };
-  if (!s) return bad("the steer object is NULL");
-  if (m < 0) return bad("a negative obstacle count");
-  if (m > (1LL << 20)) return bad("more than 2^20 obstacles");
-  if (m > 0 && !obstacles) return bad("obstacles is NULL");
-  if (!std::isfinite(robot_radius)) return bad("robot_radius is not finite");
-  for (int64_t i = 0; i < 3 * m; i++)
-    if (!std::isfinite(obstacles[i])) return bad("an obstacle entry is not finite");
-  try {
-    std::vector<double> t((size_t)(3 * m));
-    for (int64_t k = 0; k < m; k++) {
-      t[3 * k] = obstacles[3 * k];
-      t[3 * k + 1] = obstacles[3 * k + 1];
-      t[3 * k + 2] = py_sq_host(obstacles[3 * k + 2] + robot_radius);   // (size+robot_radius)**2  rrt_05:1635
-    }
-    s->h_obs.swap(t);
-  } catch (const std::exception& e) {
-    return steer_fail(s, RRTX_E_HIP, std::string(fn) + e.what());
-  }
-  s->obs_dirty = true;
-  return RRTX_OK;
-}
-
-int rrtx_steer_get_hits(rrtx_steer* s, int32_t* hit) {
-  if (!s) return steer_fail(s, RRTX_E_INVALID, "rrtx_steer_get_hits: the steer object is NULL");
-  if (!s->solved) return steer_fail(s, RRTX_E_STATE, "rrtx_steer_get_hits: no completed solve");
-  if (!s->has_hits) return steer_fail(s, RRTX_E_STATE, "rrtx_steer_get_hits: the last solve ran without an obstacle list");
-  if (s->n == 0) return RRTX_OK;
-  if (!hit) return steer_fail(s, RRTX_E_INVALID, "rrtx_steer_get_hits: hit is NULL");
-  STEERCHK(s, hipSetDevice(s->device));
-  STEERCHK(s, hipMemcpy(hit, s->hit.p, sizeof(int32_t) * (size_t)s->n, hipMemcpyDeviceToHost));
-  return RRTX_OK;
-}
-
-int rrtx_steer_get_kernel_ms(rrtx_steer* s, double* kernel_ms) {
-  if (!s || !kernel_ms) return steer_fail(s, RRTX_E_INVALID, "rrtx_steer_get_kernel_ms: a NULL pointer");
-  if (!s->solved) return steer_fail(s, RRTX_E_STATE, "rrtx_steer_get_kernel_ms: no completed solve");
-  *kernel_ms = s->kernel_ms;
-  return RRTX_OK;
-}
-
-}  // extern "C"
-
-// ---- batched closed-loop tracking of courses given as data (rrt_track.hip.h, track_courses_kernel) ------------------------
-struct rrtx_tracker {
-  int device = 0;
-  bool usable = false;        // a gfx950 device was found at creation
-  int n_cu = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  std::string err;
-  // device buffers, grown on demand
-  struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-  };
-  Buf off, x, y, yaw, per_course, start, ox, oy, othr, obs_off, rec, counter, slab, out, arr_off;
-  // the last run
-  bool ran = false, has_arrays = false;
-  int64_t n = 0, n_steps = 0;
-  double kernel_ms = 0.0;
-  std::vector<rppt::Record> h_rec;
-  std::vector<int64_t> h_arr_off;
-};
-
-namespace {
-thread_local std::string tracker_null_err;
-
-int tracker_fail(rrtx_tracker* t, int rc, const std::string& msg) {
-  (t ? t->err : tracker_null_err) = msg;
-  return rc;
-}
-#define TRACKCHK(t, expr)                                                                      \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return tracker_fail(t, RRTX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-// at least `bytes` in b; contents are not kept
-int tracker_reserve(rrtx_tracker* t, rrtx_tracker::Buf& b, size_t bytes) {
-  if (bytes <= b.bytes) return RRTX_OK;
-  if (b.p) hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-  TRACKCHK(t, hipMalloc(&b.p, bytes));
-  b.bytes = bytes;
-  return RRTX_OK;
-}
-
-// `bytes` of host data into b (grown as needed), queued on the tracker's stream
-int tracker_upload(rrtx_tracker* t, rrtx_tracker::Buf& b, const void* src, size_t bytes) {
-  if (!bytes) return RRTX_OK;
-  int rc = tracker_reserve(t, b, bytes);
-  if (rc) return rc;
-  TRACKCHK(t, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, t->stream));
-  return RRTX_OK;
-}
-
-bool all_finite(const double* v, int64_t count) {
-  for (int64_t i = 0; i < count; i++)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
-// starts at 0 and never decreases
-bool csr_ok(const int64_t* off, int64_t n) {
-  if (off[0] != 0) return false;
-  for (int64_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return false;
-  return true;
-}
-}  // namespace
-
-extern "C" {
-
-int rrtx_tracker_create(int32_t device, rrtx_tracker** out) {
-  if (!out) return tracker_fail(nullptr, RRTX_E_INVALID, "rrtx_tracker_create: out is NULL");
-  *out = nullptr;
-  if (device < 0) return tracker_fail(nullptr, RRTX_E_INVALID, "rrtx_tracker_create: negative device ordinal");
-  rrtx_tracker* t = new (std::nothrow) rrtx_tracker();
-  if (!t) return tracker_fail(nullptr, RRTX_E_HIP, "rrtx_tracker_create: out of host memory");
-  t->device = device;
-  *out = t;   // returned on failure too: the caller reads the message, and runs still check their arguments
-  int ndev = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device >= ndev ||
-      hipGetDeviceProperties(&prop, device) != hipSuccess ||
-      (!strstr(prop.gcnArchName, "gfx950") && !getenv("RRTX_ALLOW_ANY_ARCH")))
-    return tracker_fail(t, RRTX_E_NO_DEVICE, "rrtx_tracker_create: no usable gfx950 device (there is no CPU fallback)");
-  t->n_cu = prop.multiProcessorCount;
-  TRACKCHK(t, hipSetDevice(device));
-  TRACKCHK(t, hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-  for (auto& e : t->ev) TRACKCHK(t, hipEventCreate(&e));
-  t->usable = true;
-  return RRTX_OK;
-}
-
-void rrtx_tracker_destroy(rrtx_tracker* t) {
-  if (!t) return;
-  if (t->usable) {
-    hipSetDevice(t->device);
-    for (rrtx_tracker::Buf* b : {&t->off, &t->x, &t->y, &t->yaw, &t->per_course, &t->start, &t->ox, &t->oy, &t->othr,
-                                 &t->obs_off, &t->rec, &t->counter, &t->slab, &t->out, &t->arr_off})
-      if (b->p) hipFree(b->p);
-    for (auto& e : t->ev)
-      if (e) hipEventDestroy(e);
-    if (t->stream) hipStreamDestroy(t->stream);
-  }
-  delete t;
-}
-
-const char* rrtx_tracker_last_error(rrtx_tracker* t) { return t ? t->err.c_str() : tracker_null_err.c_str(); }
-
-static int tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_batch* b) {
-  const char* fn = "rrtx_tracker_run: ";
-  auto bad = [&](const char* m) { return tracker_fail(t, RRTX_E_INVALID, std::string(fn) + m); };
-  if (!t) return bad("the tracker is NULL");
-  if (!tp || !b) return bad("the parameters or the batch is NULL");
-  if (b->n < 0 || b->n > (1LL << 30)) return bad("n is negative or above 2^30");
-  if (!b->offsets || !b->robot_radius) return bad("offsets or robot_radius is NULL");
-  const int64_t n = b->n;
-  if (!csr_ok(b->offsets, n)) return bad("offsets do not start at 0 or decrease");
-  const int64_t pts = b->offsets[n];
-  if (pts > 0x7fffffffLL) return bad("more than 2^31 - 1 points in all");
-  if (pts > 0 && (!b->x || !b->y || !b->yaw)) return bad("x, y or yaw is NULL");
-  if (b->n_obstacles < 0) return bad("n_obstacles is negative");
-  if (b->n_obstacles > 0 && !b->obstacles) return bad("obstacles is NULL");
-  if (b->obs_offsets) {
-    if (!csr_ok(b->obs_offsets, n)) return bad("obs_offsets do not start at 0 or decrease");
-    if (b->obs_offsets[n] > b->n_obstacles) return bad("obs_offsets end beyond n_obstacles");
-    for (int64_t i = 0; i < n; i++)
-      if (b->obs_offsets[i + 1] - b->obs_offsets[i] > rppt::TPB) return bad("more than 64 obstacles in one list");
-  } else if (b->n_obstacles > rppt::TPB) {
-    return bad("more than 64 obstacles in one list");
-  }
-  if (!(tp->dt > 0.0) || !(tp->T >= 0.0) || !(tp->T / tp->dt <= 1.0e6) || !(tp->Lf > 0.0) || !(tp->L > 0.0) ||
-      !(tp->steer_max >= 0.0 && tp->steer_max <= 0.79))
-    return bad("needs dt > 0, T / dt <= 1e6, Lf > 0, L > 0, 0 <= steer_max <= 0.79");
-  const int64_t n_rr = b->robot_radius_per_course ? n : 1;
-  if (!all_finite(b->x, pts) || !all_finite(b->y, pts) || !all_finite(b->yaw, pts)) return bad("a pose component is not finite");
-  if (!all_finite(b->obstacles, 3 * b->n_obstacles)) return bad("an obstacle component is not finite");
-  if (!all_finite(b->robot_radius, n_rr)) return bad("a robot radius is not finite");
-  if (b->start_state && !all_finite(b->start_state, 4 * n)) return bad("a start state component is not finite");
-  if (b->per_course && !all_finite(b->per_course, 3 * n)) return bad("a per-course value is not finite");
-  if (!all_finite(&tp->target_speed, sizeof(*tp) / sizeof(double))) return bad("a parameter is not finite");
-  if (!t->usable) return tracker_fail(t, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
-
-  t->ran = false;
-  t->has_arrays = false;
-  t->n = n;
-  t->n_steps = 0;
-  t->kernel_ms = 0.0;
-  t->h_rec.clear();
-  t->h_arr_off.assign((size_t)n + 1, 0);
-  if (n == 0) {
-    t->has_arrays = b->want_arrays != 0;
-    t->ran = true;
-    return RRTX_OK;
-  }
-  // obstacle table: SoA x, y and the thresholds (radius + robot_radius) ** 2 by the planners' routine; one threshold row per
-  // obstacle row, or with one shared list and a radius per course n rows of the list's thresholds
-  const int64_t rows = b->obs_offsets ? b->obs_offsets[n] : b->n_obstacles;
-  const bool thr_per_course = !b->obs_offsets && b->robot_radius_per_course && rows > 0;
-  std::vector<double> ox((size_t)rows), oy((size_t)rows), othr((size_t)(thr_per_course ? rows * n : rows));
-  for (int64_t k = 0; k < rows; k++) {
-    ox[k] = b->obstacles[3 * k];
-    oy[k] = b->obstacles[3 * k + 1];
-  }
-  if (b->obs_offsets) {
-    for (int64_t i = 0; i < n; i++)
-      for (int64_t k = b->obs_offsets[i]; k < b->obs_offsets[i + 1]; k++)
-        othr[k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[b->robot_radius_per_course ? i : 0]);
-  } else if (thr_per_course) {
-    for (int64_t i = 0; i < n; i++)
-      for (int64_t k = 0; k < rows; k++) othr[i * rows + k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[i]);
-  } else {
-    for (int64_t k = 0; k < rows; k++) othr[k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[0]);
-  }
-
-  TRACKCHK(t, hipSetDevice(t->device));
-  int rc;
-  const size_t N = (size_t)n;
-  const int64_t want = (int64_t)t->n_cu * 16;   // 16 blocks of one wave per CU, as track_roll_kernel
-  int blocks = (int)(n < want ? n : want);
-  if (blocks < 1) blocks = 1;
-  if ((rc = tracker_upload(t, t->off, b->offsets, sizeof(int64_t) * (N + 1)))) return rc;
-  if ((rc = tracker_upload(t, t->x, b->x, sizeof(double) * (size_t)pts))) return rc;
-  if ((rc = tracker_upload(t, t->y, b->y, sizeof(double) * (size_t)pts))) return rc;
-  if ((rc = tracker_upload(t, t->yaw, b->yaw, sizeof(double) * (size_t)pts))) return rc;
-  if (b->per_course && (rc = tracker_upload(t, t->per_course, b->per_course, sizeof(double) * 3 * N))) return rc;
-  if (b->start_state && (rc = tracker_upload(t, t->start, b->start_state, sizeof(double) * 4 * N))) return rc;
-  if ((rc = tracker_upload(t, t->ox, ox.data(), sizeof(double) * ox.size()))) return rc;
-  if ((rc = tracker_upload(t, t->oy, oy.data(), sizeof(double) * oy.size()))) return rc;
-  if ((rc = tracker_upload(t, t->othr, othr.data(), sizeof(double) * othr.size()))) return rc;
-  if (b->obs_offsets && (rc = tracker_upload(t, t->obs_off, b->obs_offsets, sizeof(int64_t) * (N + 1)))) return rc;
-  if ((rc = tracker_reserve(t, t->rec, sizeof(rppt::Record) * N))) return rc;
-  if ((rc = tracker_reserve(t, t->counter, sizeof(int32_t)))) return rc;
-  if ((rc = tracker_reserve(t, t->slab, sizeof(double) * (size_t)blocks * 3 * rppt::SLAB_PTS))) return rc;
-  TRACKCHK(t, hipMemsetAsync(t->counter.p, 0, sizeof(int32_t), t->stream));
-
-  rppt::CourseArgs a;
-  memset(&a, 0, sizeof(a));
-  a.n = n;
-  a.off = (const int64_t*)t->off.p;
-  a.x = (const double*)t->x.p;
-  a.y = (const double*)t->y.p;
-  a.yaw = (const double*)t->yaw.p;
-  a.per_course = b->per_course ? (const double*)t->per_course.p : nullptr;
-  a.start = b->start_state ? (const double*)t->start.p : nullptr;
-  a.ox = (const double*)t->ox.p;
-  a.oy = (const double*)t->oy.p;
-  a.othr = (const double*)t->othr.p;
-  a.obs_off = b->obs_offsets ? (const int64_t*)t->obs_off.p : nullptr;
-  a.thr_stride = thr_per_course ? rows : 0;
-  a.m_shared = b->obs_offsets ? 0 : (int32_t)rows;
-  static_assert(sizeof(rppt::Params) == sizeof(rrtx_track_params), "rrtx_track_params mirrors rppt::Params");
-  static_assert(sizeof(rppt::Record) == sizeof(rrtx_track_record), "rrtx_track_record mirrors rppt::Record");
-  memcpy(&a.P, tp, sizeof(a.P));
-  a.rec = (rppt::Record*)t->rec.p;
-  a.counter = (int32_t*)t->counter.p;
-  a.slab = (double*)t->slab.p;
-
-  // first launch: the records
-  TRACKCHK(t, hipEventRecord(t->ev[0], t->stream));
-  hipLaunchKernelGGL(rppt::track_courses_kernel, dim3(blocks), dim3(rppt::TPB), 0, t->stream, a, 0);
-  TRACKCHK(t, hipGetLastError());
-  TRACKCHK(t, hipEventRecord(t->ev[1], t->stream));
-  t->h_rec.resize(N);
-  TRACKCHK(t, hipMemcpyAsync(t->h_rec.data(), t->rec.p, sizeof(rppt::Record) * N, hipMemcpyDeviceToHost, t->stream));
-  TRACKCHK(t, hipStreamSynchronize(t->stream));
-  float ms = 0.f;
-  TRACKCHK(t, hipEventElapsedTime(&ms, t->ev[0], t->ev[1]));
-  t->kernel_ms = ms;
-
-  // arr_offsets: exclusive sum of len over the complete courses
-  int64_t tot = 0;
-  bool partial = false;
-  for (size_t i = 0; i < N; i++) {
-    t->h_arr_off[i] = tot;
-    if (t->h_rec[i].ood)
-      partial = true;
-    else
-      tot += t->h_rec[i].n;
-  }
-  t->h_arr_off[N] = tot;
-  t->n_steps = tot;
-
-  if (b->want_arrays) {
-    if (tot > 0) {
-      if ((rc = tracker_reserve(t, t->out, sizeof(double) * 7 * (size_t)tot))) return rc;
-      if ((rc = tracker_upload(t, t->arr_off, t->h_arr_off.data(), sizeof(int64_t) * (N + 1)))) return rc;
-      TRACKCHK(t, hipMemsetAsync(t->counter.p, 0, sizeof(int32_t), t->stream));
-      a.out = (double*)t->out.p;
-      a.arr_off = (const int64_t*)t->arr_off.p;
-      a.out_total = tot;
-      TRACKCHK(t, hipEventRecord(t->ev[2], t->stream));
-      hipLaunchKernelGGL(rppt::track_courses_kernel, dim3(blocks), dim3(rppt::TPB), 0, t->stream, a, 1);
-      TRACKCHK(t, hipGetLastError());
-      TRACKCHK(t, hipEventRecord(t->ev[3], t->stream));
-      TRACKCHK(t, hipStreamSynchronize(t->stream));
-      TRACKCHK(t, hipEventElapsedTime(&ms, t->ev[2], t->ev[3]));
-      t->kernel_ms += ms;
-    }
-    t->has_arrays = true;
-  }
-  t->ran = true;
-  if (partial) {
-    t->err = std::string(fn) + "some courses are too short, too long or left the replica's domain (see the ood column)";
-    return RRTX_PARTIAL;
-  }
-  return RRTX_OK;
-}
-
-int rrtx_tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_batch* b) {
-  try {   // host allocations (records, offsets, messages) must not throw across the ABI
-    return tracker_run(t, tp, b);
-  } catch (const std::exception& e) {
-    if (t) t->ran = false;
-    return tracker_fail(t, RRTX_E_HIP, std::string("rrtx_tracker_run: ") + e.what());
-  }
-}
-
-int rrtx_tracker_get_counts(rrtx_tracker* t, int64_t* n_courses, int64_t* n_steps) {
-  if (!t || !n_courses || !n_steps) return tracker_fail(t, RRTX_E_INVALID, "rrtx_tracker_get_counts: a NULL pointer");
-  if (!t->ran) return tracker_fail(t, RRTX_E_STATE, "rrtx_tracker_get_counts: no completed run");
-  *n_courses = t->n;
-  *n_steps = t->n_steps;
-  return RRTX_OK;
-}
-
-int rrtx_tracker_get_records(rrtx_tracker* t, rrtx_track_record* rec, int64_t* arr_offsets) {
-  if (!t || !rec) return tracker_fail(t, RRTX_E_INVALID, "rrtx_tracker_get_records: a NULL pointer");
-  if (!t->ran) return tracker_fail(t, RRTX_E_STATE, "rrtx_tracker_get_records: no completed run");
-  if (t->n) memcpy(rec, t->h_rec.data(), sizeof(rrtx_track_record) * (size_t)t->n);
-  if (arr_offsets) memcpy(arr_offsets, t->h_arr_off.data(), sizeof(int64_t) * ((size_t)t->n + 1));
-  return RRTX_OK;
-}
-
-int rrtx_tracker_get_arrays(rrtx_tracker* t, double* x, double* y, double* yaw, double* v, double* tt, double* a, double* d,
-                            int64_t cap) {
-  if (!t) return tracker_fail(t, RRTX_E_INVALID, "rrtx_tracker_get_arrays: the tracker is NULL");
-  if (!t->ran || !t->has_arrays) return tracker_fail(t, RRTX_E_STATE, "rrtx_tracker_get_arrays: no completed run with arrays");
-  if (cap < t->n_steps) return tracker_fail(t, RRTX_E_CAPACITY, "rrtx_tracker_get_arrays: the buffers are too small");
-  if (t->n_steps == 0) return RRTX_OK;
-  const size_t tot = (size_t)t->n_steps;
-  TRACKCHK(t, hipSetDevice(t->device));
-  double* dst[7] = {x, y, yaw, v, tt, a, d};
-  for (int k = 0; k < 7; k++)
-    if (dst[k]) TRACKCHK(t, hipMemcpy(dst[k], (const double*)t->out.p + k * tot, sizeof(double) * tot, hipMemcpyDeviceToHost));
-  return RRTX_OK;
-}
-
-int rrtx_tracker_get_kernel_ms(rrtx_tracker* t, double* kernel_ms) {
-  if (!t || !kernel_ms) return tracker_fail(t, RRTX_E_INVALID, "rrtx_tracker_get_kernel_ms: a NULL pointer");
-  if (!t->ran) return tracker_fail(t, RRTX_E_STATE, "rrtx_tracker_get_kernel_ms: no completed run");
-  *kernel_ms = t->kernel_ms;
-  return RRTX_OK;
-}
-
-}  // extern "C"
+#include "rrtx_api_tools.inc"
+#include "rrtx_api_rccl.inc"
+#include "rrtx_api_steer.inc"
+#include "rrtx_api_tracker.inc"

@@ -1,0 +1,341 @@
+// rrtx_api_steer.inc -- rrtx_steer_*: batched Dubins / Reeds-Shepp curves between pose pairs (steer_batch.hip.h);
+// included by rrtx_api.hip
+struct rrtx_steer : DevObj {
+  // device buffers, grown on demand
+  DevBuf starts, goals, curv, status, nseg, total, seglen, modes, npts, plan, offsets, px, py, pyaw, flag, obs, hit;
+  // the obstacle list of rrtx_steer_set_obstacles: packed rows (ox, oy, thr); it goes to the device at the next solve
+  std::vector<double> h_obs;
+  bool obs_dirty = false;
+  // the last solve
+  bool solved = false, has_points = false, has_hits = false;
+  int64_t n = 0, n_points = 0;
+  double kernel_ms = 0.0;
+  std::vector<int64_t> h_offsets;
+};
+
+namespace {
+// stage 2 with or without the stores and the obstacle check; one of the two is wanted
+template <int KIND>
+void steer_launch_fill(bool store, bool check, unsigned blocks, hipStream_t stream, const rppsb::Args& a) {
+  if (store && check)
+    hipLaunchKernelGGL((rppsb::steer_fill<KIND, true, true>), dim3(blocks), dim3(rppsb::TPB), 0, stream, a);
+  else if (store)
+    hipLaunchKernelGGL((rppsb::steer_fill<KIND, true, false>), dim3(blocks), dim3(rppsb::TPB), 0, stream, a);
+  else
+    hipLaunchKernelGGL((rppsb::steer_fill<KIND, false, true>), dim3(blocks), dim3(rppsb::TPB), 0, stream, a);
+}
+}  // namespace
+
+extern "C" {
+
+int rrtx_steer_create(int32_t device, rrtx_steer** out) {
+  if (!out) return fail<rrtx_steer>(nullptr, RRTX_E_INVALID, "rrtx_steer_create: out is NULL");
+  *out = nullptr;
+  if (device < 0) return fail<rrtx_steer>(nullptr, RRTX_E_INVALID, "rrtx_steer_create: negative device ordinal");
+  rrtx_steer* s = new (std::nothrow) rrtx_steer();
+  if (!s) return fail<rrtx_steer>(nullptr, RRTX_E_HIP, "rrtx_steer_create: out of host memory");
+  *out = s;   // returned on failure too: the caller reads the message, and solves still check their arguments
+  return s->open(device, "rrtx_steer_create");
+}
+
+void rrtx_steer_destroy(rrtx_steer* s) {
+  if (!s) return;
+  if (s->usable) hipSetDevice(s->device);
+  delete s;   // the buffers, then the events and the stream
+}
+
+const char* rrtx_steer_last_error(rrtx_steer* s) { return s ? s->err.c_str() : null_object_err.c_str(); }
+
+static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
+                       const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
+                       const int32_t* word_order, int32_t n_words, int32_t want_points) {
+  const char* fn = "rrtx_steer_solve: ";
+  auto bad = [&](const char* m) { return fail(s, RRTX_E_INVALID, std::string(fn) + m); };
+  if (!s) return bad("the steer object is NULL");
+  if (kind != RRTX_STEER_DUBINS && kind != RRTX_STEER_RS) return bad("unknown kind");
+  if (!starts || !goals || !curvature) return bad("starts, goals or curvature is NULL");
+  if (n < 0 || (product && ng < 0)) return bad("a negative batch size");
+  if (!(step_size > 0.0)) return bad("step_size must be > 0");
+  if (kind == RRTX_STEER_DUBINS && step_size != rpp::kDubinsStep)
+    return bad("Dubins curves are interpolated at the reference's default step_size = 0.1; another step is not supported");
+  if (word_order) {
+    if (kind != RRTX_STEER_DUBINS) return bad("a word order applies to Dubins curves only");
+    if (n_words < 0 || n_words > 6) return bad("n_words outside 0..6");
+    for (int i = 0; i < n_words; i++)
+      if (word_order[i] < 0 || word_order[i] > 5) return bad("a word index outside 0..5");
+  }
+  const int64_t n_goals = product ? ng : n;
+  if (n > (1LL << 30) || n_goals > (1LL << 30) || (product && n && ng && n > (1LL << 30) / ng))
+    return bad("more than 2^30 pairs");
+  const int64_t np = product ? n * ng : n;
+  // Every pose and curvature is looked at once here: a curve's point count grows with distance x curvature / step, and the
+  // kernels count points in loops, so an absurd input must never reach them.
+  double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
+  for (int side = 0; side < 2; side++) {
+    const double* q = side ? goals : starts;
+    const int64_t rows = side ? n_goals : n;
+    for (int64_t i = 0; i < rows; i++)
+      for (int c = 0; c < 3; c++) {
+        const double v = q[3 * i + c];
+        if (!(fabs(v) <= 1e6)) return bad("a pose component is not finite or exceeds 1e6 in magnitude");
+        if (c < 2) {
+          lo[c] = v < lo[c] ? v : lo[c];
+          hi[c] = v > hi[c] ? v : hi[c];
+        }
+      }
+  }
+  double cmin = 1e300, cmax = 0.0;
+  const int64_t nc = curvature_per_pair ? np : 1;
+  for (int64_t i = 0; i < nc; i++) {
+    const double c = curvature[i];
+    if (!(c > 0.0) || !(c <= 1e300)) return bad("a curvature is not finite or not > 0");
+    cmin = c < cmin ? c : cmin;
+    cmax = c > cmax ? c : cmax;
+  }
+  if (np > 0) {
+    const double D = hypot(hi[0] - lo[0], hi[1] - lo[1]);
+    const double pts = kind == RRTX_STEER_DUBINS ? (D * cmax + 20.0) / rpp::kDubinsStep
+                                                 : D / step_size + 20.0 / (step_size * cmin);
+    if (!(pts <= 4194304.0)) return bad("the poses are so far apart for this curvature and step that a curve could exceed 2^22 points");
+  }
+  if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  // With an obstacle list the curves' points are computed (stage 1 as for points, then the fill kernel) whether or not
+  // they are stored.
+  const int64_t n_obs = (int64_t)(s->h_obs.size() / 3);
+  const bool stage2 = want_points || n_obs > 0;
+
+  s->solved = false;
+  s->has_points = false;
+  s->has_hits = false;
+  s->n = np;
+  s->n_points = 0;
+  s->kernel_ms = 0.0;
+  s->h_offsets.clear();
+  if (np == 0) {
+    s->has_points = want_points != 0;
+    s->has_hits = n_obs > 0;
+    s->h_offsets.assign(1, 0);
+    s->solved = true;
+    return RRTX_OK;
+  }
+  HIPCHK(s, hipSetDevice(s->device));
+  int rc;
+  const size_t N = (size_t)np;
+  if ((rc = s->reserve(s->starts, sizeof(double) * 3 * (size_t)n))) return rc;
+  if ((rc = s->reserve(s->goals, sizeof(double) * 3 * (size_t)n_goals))) return rc;
+  if ((rc = s->reserve(s->curv, sizeof(double) * (size_t)nc))) return rc;
+  if ((rc = s->reserve(s->status, sizeof(int32_t) * N))) return rc;
+  if ((rc = s->reserve(s->nseg, sizeof(int32_t) * N))) return rc;
+  if ((rc = s->reserve(s->total, sizeof(double) * N))) return rc;
+  if ((rc = s->reserve(s->seglen, sizeof(double) * 5 * N))) return rc;
+  if ((rc = s->reserve(s->modes, 8 * N))) return rc;
+  if ((rc = s->reserve(s->npts, sizeof(int32_t) * N))) return rc;
+  if ((rc = s->reserve(s->flag, sizeof(int32_t)))) return rc;
+  if (stage2) {
+    const size_t rec = kind == RRTX_STEER_DUBINS ? sizeof(rpp::DubinsPlan) : sizeof(rpp::RsCourse);
+    if ((rc = s->reserve(s->plan, rec * N))) return rc;
+    if ((rc = s->reserve(s->offsets, sizeof(int64_t) * (N + 1)))) return rc;
+  }
+  if (n_obs > 0) {
+    if ((rc = s->reserve(s->hit, sizeof(int32_t) * N))) return rc;
+    if (s->obs_dirty) {
+      if ((rc = s->reserve(s->obs, sizeof(double) * s->h_obs.size()))) return rc;
+      HIPCHK(s, hipMemcpyAsync(s->obs.p, s->h_obs.data(), sizeof(double) * s->h_obs.size(), hipMemcpyHostToDevice, s->stream));
+      s->obs_dirty = false;
+    }
+  }
+  HIPCHK(s, hipMemcpyAsync(s->starts.p, starts, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(s, hipMemcpyAsync(s->goals.p, goals, sizeof(double) * 3 * (size_t)n_goals, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(s, hipMemcpyAsync(s->curv.p, curvature, sizeof(double) * (size_t)nc, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(s, hipMemsetAsync(s->flag.p, 0, sizeof(int32_t), s->stream));
+
+  rppsb::Args a;
+  memset(&a, 0, sizeof(a));
+  a.starts = s->starts.as<const double>();
+  a.goals = s->goals.as<const double>();
+  a.curv = curvature_per_pair ? s->curv.as<const double>() : nullptr;
+  a.curv0 = curvature[0];
+  a.step = step_size;
+  a.n = np;
+  a.ng = product ? ng : 1;
+  a.product = product ? 1 : 0;
+  a.want_points = stage2 ? 1 : 0;
+  a.n_order = word_order ? n_words : 6;
+  for (int i = 0; i < 6; i++) a.order[i] = (word_order && i < n_words) ? word_order[i] : i;
+  a.status = s->status.as<int32_t>();
+  a.nseg = s->nseg.as<int32_t>();
+  a.total = s->total.as<double>();
+  a.seglen = s->seglen.as<double>();
+  a.modes = s->modes.as<char>();
+  a.npts = s->npts.as<int32_t>();
+  a.dplan = s->plan.as<rpp::DubinsPlan>();
+  a.course = s->plan.as<rpp::RsCourse>();
+  a.flag = s->flag.as<int32_t>();
+  if (n_obs > 0) {
+    a.obs = s->obs.as<const double>();
+    a.n_obs = n_obs;
+    a.hit = s->hit.as<int32_t>();
+  }
+
+  // stage 1
+  const unsigned blk = (unsigned)((np + rppsb::TPB - 1) / rppsb::TPB);
+  int32_t flag = 0;
+  std::vector<int32_t> cnt(stage2 ? N : 0);
+  float ms = 0.f;
+  rc = s->timed(&ms, [&] {
+    if (kind == RRTX_STEER_DUBINS) {
+      hipLaunchKernelGGL(rppsb::steer_dubins_solve, dim3(blk), dim3(rppsb::TPB), 0, s->stream, a);
+    } else {
+      hipLaunchKernelGGL(rppsb::steer_rs_solve, dim3((unsigned)((np + rppsb::RS_PAIRS - 1) / rppsb::RS_PAIRS)),
+                         dim3(rppsb::RS_TPB), 0, s->stream, a);
+      if (stage2) hipLaunchKernelGGL(rppsb::steer_rs_course, dim3(blk), dim3(rppsb::TPB), 0, s->stream, a);
+    }
+  }, [&]() -> int {
+    HIPCHK(s, hipMemcpyAsync(&flag, s->flag.p, sizeof(flag), hipMemcpyDeviceToHost, s->stream));
+    if (stage2) HIPCHK(s, hipMemcpyAsync(cnt.data(), s->npts.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
+    return RRTX_OK;
+  });
+  if (rc) return rc;
+  s->kernel_ms = ms;
+
+  if (stage2) {
+    // offsets: exclusive prefix sum of the point counts
+    s->h_offsets.resize(N + 1);
+    int64_t tot = 0;
+    for (size_t i = 0; i < N; i++) {
+      s->h_offsets[i] = tot;
+      tot += cnt[i] > 0 ? cnt[i] : 0;
+    }
+    s->h_offsets[N] = tot;
+    s->n_points = want_points ? tot : 0;
+    if (tot > 0) {
+      if (want_points) {
+        if ((rc = s->reserve(s->px, sizeof(double) * (size_t)tot))) return rc;
+        if ((rc = s->reserve(s->py, sizeof(double) * (size_t)tot))) return rc;
+        if ((rc = s->reserve(s->pyaw, sizeof(double) * (size_t)tot))) return rc;
+      }
+      if ((tot + rppsb::TPB - 1) / rppsb::TPB > 0x7fffffffLL)
+        return fail(s, RRTX_E_OVERFLOW, std::string(fn) + "more polyline points than one launch can fill");
+      HIPCHK(s, hipMemcpyAsync(s->offsets.p, s->h_offsets.data(), sizeof(int64_t) * (N + 1), hipMemcpyHostToDevice, s->stream));
+      a.offsets = s->offsets.as<const int64_t>();
+      if (want_points) {
+        a.px = s->px.as<double>();
+        a.py = s->py.as<double>();
+        a.pyaw = s->pyaw.as<double>();
+      }
+      const unsigned fblk = (unsigned)((tot + rppsb::TPB - 1) / rppsb::TPB);
+      rc = s->timed(&ms, [&] {
+        if (kind == RRTX_STEER_DUBINS)
+          steer_launch_fill<rppsb::KIND_DUBINS>(want_points != 0, n_obs > 0, fblk, s->stream, a);
+        else
+          steer_launch_fill<rppsb::KIND_RS>(want_points != 0, n_obs > 0, fblk, s->stream, a);
+      });
+      if (rc) return rc;
+      s->kernel_ms += ms;
+    }
+    if (!want_points) s->h_offsets.clear();   // a lengths-only solve keeps no offsets, checked or not
+    s->has_points = want_points != 0;
+  }
+  s->has_hits = n_obs > 0;
+  s->solved = true;
+  if (flag) {
+    s->err = std::string(fn) + "some pairs have no path or are cases where the reference raises (see the status column)";
+    return RRTX_PARTIAL;
+  }
+  return RRTX_OK;
+}
+
+int rrtx_steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
+                     const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
+                     const int32_t* word_order, int32_t n_words, int32_t want_points) {
+  try {   // host allocations (offsets, messages) must not throw across the ABI
+    return steer_solve(s, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size, word_order, n_words,
+                       want_points);
+  } catch (const std::exception& e) {
+    if (s) s->solved = false;
+    return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve: ") + e.what());
+  }
+}
+
+int rrtx_steer_get_counts(rrtx_steer* s, int64_t* n_pairs, int64_t* n_points) {
+  if (!s || !n_pairs || !n_points) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_counts: a NULL pointer");
+  if (!s->solved) return fail(s, RRTX_E_STATE, "rrtx_steer_get_counts: no completed solve");
+  *n_pairs = s->n;
+  *n_points = s->n_points;
+  return RRTX_OK;
+}
+
+int rrtx_steer_get_summary(rrtx_steer* s, int32_t* status, double* length, int32_t* n_seg, double* seg_len, char* modes,
+                           int64_t* offsets) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_summary: the steer object is NULL");
+  if (!s->solved) return fail(s, RRTX_E_STATE, "rrtx_steer_get_summary: no completed solve");
+  if (offsets && !s->has_points)
+    return fail(s, RRTX_E_STATE, "rrtx_steer_get_summary: the last solve was lengths-only, it has no offsets");
+  if (offsets) memcpy(offsets, s->h_offsets.data(), sizeof(int64_t) * s->h_offsets.size());
+  if (s->n == 0) return RRTX_OK;
+  const size_t N = (size_t)s->n;
+  HIPCHK(s, hipSetDevice(s->device));
+  if (status) HIPCHK(s, hipMemcpy(status, s->status.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  if (length) HIPCHK(s, hipMemcpy(length, s->total.p, sizeof(double) * N, hipMemcpyDeviceToHost));
+  if (n_seg) HIPCHK(s, hipMemcpy(n_seg, s->nseg.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  if (seg_len) HIPCHK(s, hipMemcpy(seg_len, s->seglen.p, sizeof(double) * 5 * N, hipMemcpyDeviceToHost));
+  if (modes) HIPCHK(s, hipMemcpy(modes, s->modes.p, 8 * N, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+int rrtx_steer_get_points(rrtx_steer* s, double* x, double* y, double* yaw, int64_t cap) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_points: the steer object is NULL");
+  if (!s->solved || !s->has_points) return fail(s, RRTX_E_STATE, "rrtx_steer_get_points: no completed solve with points");
+  if (cap < s->n_points) return fail(s, RRTX_E_CAPACITY, "rrtx_steer_get_points: the buffers are too small");
+  if (s->n_points == 0) return RRTX_OK;
+  const size_t bytes = sizeof(double) * (size_t)s->n_points;
+  HIPCHK(s, hipSetDevice(s->device));
+  if (x) HIPCHK(s, hipMemcpy(x, s->px.p, bytes, hipMemcpyDeviceToHost));
+  if (y) HIPCHK(s, hipMemcpy(y, s->py.p, bytes, hipMemcpyDeviceToHost));
+  if (yaw) HIPCHK(s, hipMemcpy(yaw, s->pyaw.p, bytes, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+int rrtx_steer_set_obstacles(rrtx_steer* s, const double* obstacles, int64_t m, double robot_radius) {
+  const char* fn = "rrtx_steer_set_obstacles: ";
+  auto bad = [&](const char* msg) { return fail(s, RRTX_E_INVALID, std::string(fn) + msg); };
+  if (!s) return bad("the steer object is NULL");
+  if (m < 0) return bad("a negative obstacle count");
+  if (m > (1LL << 20)) return bad("more than 2^20 obstacles");
+  if (m > 0 && !obstacles) return bad("obstacles is NULL");
+  if (!std::isfinite(robot_radius)) return bad("robot_radius is not finite");
+  if (!all_finite(obstacles, 3 * m)) return bad("an obstacle entry is not finite");
+  try {
+    std::vector<double> t((size_t)(3 * m));
+    for (int64_t k = 0; k < m; k++) {
+      t[3 * k] = obstacles[3 * k];
+      t[3 * k + 1] = obstacles[3 * k + 1];
+      t[3 * k + 2] = py_sq_host(obstacles[3 * k + 2] + robot_radius);   // (size+robot_radius)**2  rrt_05:1635
+    }
+    s->h_obs.swap(t);
+  } catch (const std::exception& e) {
+    return fail(s, RRTX_E_HIP, std::string(fn) + e.what());
+  }
+  s->obs_dirty = true;
+  return RRTX_OK;
+}
+
+int rrtx_steer_get_hits(rrtx_steer* s, int32_t* hit) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_hits: the steer object is NULL");
+  if (!s->solved) return fail(s, RRTX_E_STATE, "rrtx_steer_get_hits: no completed solve");
+  if (!s->has_hits) return fail(s, RRTX_E_STATE, "rrtx_steer_get_hits: the last solve ran without an obstacle list");
+  if (s->n == 0) return RRTX_OK;
+  if (!hit) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_hits: hit is NULL");
+  HIPCHK(s, hipSetDevice(s->device));
+  HIPCHK(s, hipMemcpy(hit, s->hit.p, sizeof(int32_t) * (size_t)s->n, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+int rrtx_steer_get_kernel_ms(rrtx_steer* s, double* kernel_ms) {
+  if (!s || !kernel_ms) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_kernel_ms: a NULL pointer");
+  if (!s->solved) return fail(s, RRTX_E_STATE, "rrtx_steer_get_kernel_ms: no completed solve");
+  *kernel_ms = s->kernel_ms;
+  return RRTX_OK;
+}
+
+}  // extern "C"

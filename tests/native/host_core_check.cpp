@@ -1,0 +1,179 @@
+// csrc/rrtx_host.h against the fake runtime of tests/native/fake_hip: the allocation- and creation-failure paths of the
+// device buffer, the device-object base and the timed section, which no GPU run can reach.  Built by tests/test_host_core.py
+// with ASan + UBSan; prints "ok" and exits 0, or names the first check that failed.
+#include <cstdio>
+
+#include "rrtx_host.h"
+
+static int failures = 0;
+#define CHECK(cond)                                                  \
+  do {                                                               \
+    if (!(cond)) {                                                   \
+      printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);      \
+      failures++;                                                    \
+    }                                                                \
+  } while (0)
+
+static bool starts_with(const std::string& s, const char* prefix) { return s.rfind(prefix, 0) == 0; }
+
+// the calls logged since `from`, joined with spaces
+static std::string calls_since(size_t from) {
+  std::string r;
+  for (size_t i = from; i < fake_hip.log.size(); i++) r += (i > from ? " " : "") + fake_hip.log[i];
+  return r;
+}
+
+static void reserve_happy_path() {
+  DevObj o;
+  DevBuf b;
+  CHECK(o.reserve(b, 0) == RRTX_OK && fake_hip.mallocs == 0 && b.p == nullptr);   // nothing asked of an empty buffer
+  CHECK(o.reserve(b, 64) == RRTX_OK && b.bytes == 64 && fake_hip.live_allocs == 1);
+  void* p64 = b.p;
+  CHECK(o.reserve(b, 32) == RRTX_OK && b.p == p64 && b.bytes == 64 && fake_hip.mallocs == 1);   // large enough: untouched
+  const size_t at = fake_hip.log.size();
+  CHECK(o.reserve(b, 128) == RRTX_OK && b.bytes == 128);
+  CHECK(calls_since(at) == "hipFree hipMalloc");   // frees first, then allocates
+  CHECK(fake_hip.live_allocs == 1 && fake_hip.mallocs == 2 && fake_hip.frees == 1);
+  CHECK(b.as<double>() == (double*)b.p);
+}
+
+static void reserve_with_a_failing_allocation() {
+  DevObj o;
+  DevBuf b;
+  CHECK(o.reserve(b, 64) == RRTX_OK);
+  fake_hip.fail_malloc = 1;
+  CHECK(o.reserve(b, 128) == RRTX_E_HIP);
+  CHECK(starts_with(o.err, "hipMalloc"));
+  CHECK(b.p == nullptr && b.bytes == 0 && fake_hip.live_allocs == 0);   // left empty, the old memory released
+  CHECK(o.reserve(b, 128) == RRTX_OK && b.bytes == 128 && fake_hip.live_allocs == 1);   // and usable again
+}
+
+static void reserve_fresh_then_move_keeps_the_old_buffer_on_failure() {
+  DevObj o;
+  DevBuf b;
+  CHECK(o.reserve(b, 64) == RRTX_OK);
+  void* const p = b.p;
+  for (int failing = 1; failing >= 0; failing--) {
+    fake_hip.fail_malloc = failing;
+    DevBuf fresh;
+    const int rc = o.reserve(fresh, 128);
+    if (rc == RRTX_OK) b = std::move(fresh);
+    if (failing) CHECK(rc == RRTX_E_HIP && b.p == p && b.bytes == 64 && fake_hip.live_allocs == 1);
+    else CHECK(rc == RRTX_OK && b.bytes == 128 && fresh.p == nullptr && fake_hip.live_allocs == 1);
+  }
+}
+
+static void moved_from_buffer_frees_nothing() {
+  DevObj o;
+  const int frees = fake_hip.frees;
+  {
+    DevBuf a;
+    CHECK(o.reserve(a, 16) == RRTX_OK);
+    DevBuf b(std::move(a));
+    CHECK(a.p == nullptr && a.bytes == 0 && b.bytes == 16);
+  }
+  CHECK(fake_hip.frees == frees + 1 && fake_hip.live_allocs == 0);   // once, by the buffer that took it over
+}
+
+// open() with the n-th creation failing: close() releases exactly what was created, a second close() nothing
+static void open_fails(int fail_stream, int fail_event, int streams_made, int events_made) {
+  DevObj o;
+  fake_hip.fail_stream = fail_stream;
+  fake_hip.fail_event = fail_event;
+  CHECK(o.open(0, "check") == RRTX_E_HIP);
+  CHECK(!o.usable && starts_with(o.err, fail_stream ? "hipStreamCreateWithFlags" : "hipEventCreate"));
+  CHECK(fake_hip.live_streams == streams_made && fake_hip.live_events == events_made);
+  size_t at = fake_hip.log.size();
+  o.close();
+  CHECK(fake_hip.live_streams == 0 && fake_hip.live_events == 0);
+  CHECK((int)(fake_hip.log.size() - at) == streams_made + events_made);
+  at = fake_hip.log.size();
+  o.close();
+  CHECK(fake_hip.log.size() == at && !o.usable);
+  fake_hip.fail_stream = fake_hip.fail_event = 0;
+}
+
+static void open_and_the_device_probe() {
+  {
+    DevObj o;
+    CHECK(o.open(0, "check") == RRTX_OK && o.usable && o.n_cu == 256 && o.device == 0);
+    CHECK(fake_hip.live_streams == 1 && fake_hip.live_events == 2);
+  }   // the destructor closes
+  CHECK(fake_hip.live_streams == 0 && fake_hip.live_events == 0);
+  DevObj o;
+  CHECK(o.open(1, "check") == RRTX_E_NO_DEVICE && !o.usable);   // one device: ordinal 1 is out of range
+  CHECK(o.err == "check: no usable gfx950 device (there is no CPU fallback)");
+  fake_hip.arch = "gfx942";
+  CHECK(o.open(0, "check") == RRTX_E_NO_DEVICE && fake_hip.live_streams == 0);
+  fake_hip.arch = "gfx950";
+  fake_hip.devices = 0;
+  CHECK(o.open(0, "check") == RRTX_E_NO_DEVICE);
+  fake_hip.devices = 1;
+}
+
+static void timed_section() {
+  DevObj o;
+  CHECK(o.open(0, "check") == RRTX_OK);
+  float ms = 0.f;
+  size_t at = fake_hip.log.size();
+  int rc = o.timed(&ms, [] { fake_hip.log.push_back("queue"); }, []() -> int {
+    fake_hip.log.push_back("copies");
+    return RRTX_OK;
+  });
+  CHECK(rc == RRTX_OK && ms == 1.5f);
+  CHECK(calls_since(at) == "hipEventRecord queue hipGetLastError hipEventRecord copies hipStreamSynchronize hipEventElapsedTime");
+  at = fake_hip.log.size();
+  CHECK(o.timed(&ms, [] { fake_hip.log.push_back("queue"); }) == RRTX_OK);   // without copies: the same order
+  CHECK(calls_since(at) == "hipEventRecord queue hipGetLastError hipEventRecord hipStreamSynchronize hipEventElapsedTime");
+  // a launch error: the section ends there
+  at = fake_hip.log.size();
+  bool copied = false;
+  rc = o.timed(&ms, [] { fake_hip.last_error = hipErrorLaunchFailure; }, [&]() -> int {
+    copied = true;
+    return RRTX_OK;
+  });
+  CHECK(rc == RRTX_E_HIP && !copied && starts_with(o.err, "hipGetLastError()"));
+  CHECK(calls_since(at) == "hipEventRecord hipGetLastError");
+  // a failing copy callback ends it with its code
+  CHECK(o.timed(&ms, [] {}, []() -> int { return RRTX_E_STATE; }) == RRTX_E_STATE);
+  // upload: grows the buffer, copies the bytes, does nothing for none
+  DevBuf b;
+  const double src[3] = {1.0, 2.0, 3.0};
+  CHECK(o.upload(b, src, 0) == RRTX_OK && b.p == nullptr);
+  CHECK(o.upload(b, src, sizeof(src)) == RRTX_OK && b.bytes == sizeof(src) && memcmp(b.p, src, sizeof(src)) == 0);
+  fake_hip.fail_malloc = 1;
+  CHECK(o.upload(b, src, 2 * sizeof(src)) == RRTX_E_HIP && b.p == nullptr);
+}
+
+static void the_shared_helpers() {
+  CHECK(fail<DevObj>(nullptr, RRTX_E_INVALID, "no object") == RRTX_E_INVALID && null_object_err == "no object");
+  const double v[3] = {0.0, -1.0, INFINITY};
+  CHECK(all_finite(v, 2) && !all_finite(v, 3) && all_finite(nullptr, 0));
+  const int64_t up[3] = {0, 2, 2}, down[3] = {0, 2, 1}, late[2] = {1, 2};
+  CHECK(csr_ok(up, 2) && !csr_ok(down, 2) && !csr_ok(late, 1));
+  CHECK(py_sq_host(-3.0) == 9.0 && py_sq_host(0.0) == 0.0);
+  rrtx_track_params tp;
+  memset(&tp, 0, sizeof(tp));
+  tp.dt = 0.1, tp.T = 100.0, tp.Lf = 2.0, tp.L = 2.9, tp.steer_max = 0.785;
+  CHECK(track_params_ok(&tp));
+  tp.steer_max = 0.8;
+  CHECK(!track_params_ok(&tp));
+  tp.steer_max = 0.785, tp.dt = NAN;
+  CHECK(!track_params_ok(&tp));
+}
+
+int main() {
+  reserve_happy_path();
+  reserve_with_a_failing_allocation();
+  reserve_fresh_then_move_keeps_the_old_buffer_on_failure();
+  moved_from_buffer_frees_nothing();
+  open_fails(1, 0, 0, 0);   // the stream
+  open_fails(0, 2, 1, 1);   // the second event
+  open_and_the_device_probe();
+  timed_section();
+  the_shared_helpers();
+  CHECK(fake_hip.live_allocs == 0 && fake_hip.live_streams == 0 && fake_hip.live_events == 0);
+  CHECK(fake_hip.mallocs == fake_hip.frees);
+  if (!failures) printf("ok\n");
+  return failures ? 1 : 0;
+}

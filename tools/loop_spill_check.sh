@@ -12,7 +12,7 @@ if [ -n "$1" ] && [ "${1#-}" = "$1" ]; then   # a first argument that is no flag
   SRC=$(cd "$1" && pwd); shift
 fi
 D=$(mktemp -d); trap 'rm -rf "$D"' EXIT; cp $SRC/* $D/
-cd $D && sed -i "s#\"../../include/rrtx.h\"#\"$REPO/include/rrtx.h\"#" rrtx_api.hip
+cd $D && sed -i "s#\"../../include/rrtx.h\"#\"$REPO/include/rrtx.h\"#" rrtx_api.hip $(ls rrtx_host.h 2>/dev/null)
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Wno-parentheses-equality -Wno-unused-value "$@" --cuda-device-only -S -Rpass-analysis=kernel-resource-usage -o $D/o.s rrtx_api.hip 2> $D/err.txt
 grep -E "error" $D/err.txt | head -3
 for ns in 5rppk2 6rppk2s 6rppk2t; do
