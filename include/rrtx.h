@@ -27,7 +27,7 @@ extern "C" {
 
 #define RRTX_ABI_VERSION 6   /* 6: rrtx_set_instance_obstacles (and RRTX_ALGO_LQR_RRT_STAR: a new algo value, no layout change; the rrtx_steer_* and
                                 rrtx_tracker_* entry points: new functions on objects of their own, no layout change; later additions of
-                                the same kind: rrtx_steer_set_obstacles, rrtx_steer_get_hits); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
+                                the same kind: rrtx_steer_set_obstacles, rrtx_steer_get_hits, rrtx_steer_solve_lqr, rrtx_steer_get_ends); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
                                 rrtx_copy_results_device, per-instance yaw and informed rotation; 4: rrtx_plan_many,
                                 rrtx_selfcheck, rrtx_stats.main_shape / main_f32, rrtx_plan_begin / _step, rrtx_set_launch_bound,
                                 RRTX_ST_REF_HANGS, rrtx_rccl_* */
@@ -355,6 +355,7 @@ int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps);
 /* ---- batched Dubins / Reeds-Shepp curves between pose pairs, without a planner (csrc/steer_batch.hip.h) -------------------
  * Replaces plan_dubins_path (10_path_planning_00_dubins_path.py :109-197) and reeds_shepp_path_planning
  * (10_path_planning_00_reeds_shepp_path.py :506-515) called once per pair: every double is the reference's, bit for bit.
+ * (The LQR steer, the reference's third, is served by the same object: rrtx_steer_solve_lqr below.)
  * The steer object is independent of rrtx_handle; it owns the device buffers of its solves and reuses them from call to
  * call (they grow, never shrink).  One host thread per object.  Call order: create, then solve, then the getters of that
  * solve, then solve again, as often as wanted; a getter before the first solve returns RRTX_E_STATE. */
@@ -414,6 +415,32 @@ int rrtx_steer_set_obstacles(rrtx_steer* s, const double* obstacles, int64_t m, 
  * curve (status != RRTX_STEER_OK), nothing was tested.  RRTX_E_STATE before the first solve and when the last solve ran
  * with no obstacle list set. */
 int rrtx_steer_get_hits(rrtx_steer* s, int32_t* hit);
+
+/* ---- the third steering function on the same object: LQR rollouts between point pairs (csrc/steer_batch.hip.h, csrc/rpp_lqr.h)
+ * Replaces LQRPlanner.lqr_planning (10_path_planning_00_lqr_path.py :24-66, the same lines as rrt_09 :944-986) called once per
+ * pair, and rrt_09's edge around it: sample_path :1157-1172, the cost of steer :1189 / calc_new_cost :1432-1442 and
+ * check_collision :1292-1305.  Every double is the reference's, bit for bit, for the reference's model (DT = 0.1, Q = R = I:
+ * the gain is the constant [0, 0.05]).  It has an entry point of its own and no kind value: rrtx_steer_solve goes on refusing
+ * any kind but the two above.  Rows of starts and goals are (x, y); product as for rrtx_steer_solve.
+ * step_size > 0: the resampled rollout of rrt_09 -- ceil(1 / step_size) points per rollout segment, the last rollout point
+ * left out; the end point is the last resampled point and the length Python's left-to-right sum of math.hypot over
+ * consecutive resampled points.  step_size == 0: the raw rollout rx, ry; the end point is its last point and the length the
+ * same sum over consecutive rollout points (the script returns no length: this one is this library's definition).
+ * max_time, goal_dist: the planner's MAX_TIME and GOAL_DIST (100.0 and 0.1 in the reference).
+ * Per-pair status: RRTX_STEER_OK, or RRTX_STEER_NO_PATH where the reference prints "Cannot found path" and returns [], [].
+ * The getters above serve the result: n_seg is the number of rollout points len(rx), seg_len and modes are zero-filled,
+ * offsets / points and hits as for the other kinds (with a list set by rrtx_steer_set_obstacles: -1 free, j >= 0, -2 no
+ * path); a rollout has no yaw, so rrtx_steer_get_points with a non-NULL yaw returns RRTX_E_STATE after this solve.
+ * Returns RRTX_OK or RRTX_PARTIAL as rrtx_steer_solve does.  RRTX_E_INVALID, before any HIP call: a NULL pointer, n < 0
+ * (product: ng < 0), more than 2^30 pairs, a coordinate that is not finite or above 1e6 in magnitude, step_size NaN, negative
+ * or in (0, 1e-3) (a segment has at most 1000 points), max_time NaN, negative or above 100.0 (a rollout has at most 1002
+ * points), goal_dist NaN (a negative one is legal: every pair is RRTX_STEER_NO_PATH). */
+int rrtx_steer_solve_lqr(rrtx_steer* s, int32_t product, int64_t n, int64_t ng, const double* starts /* (n, 2) */,
+                         const double* goals /* (n or ng, 2) */, double step_size, double max_time, double goal_dist,
+                         int32_t want_points);
+/* The end point of every pair of the last solve, rows (x, y); zeros where the pair has no path.  RRTX_E_STATE unless the
+ * last solve was rrtx_steer_solve_lqr. */
+int rrtx_steer_get_ends(rrtx_steer* s, double* ends /* (n, 2) */);
 
 /* ---- batched closed-loop tracking of courses given as data, without a planner (csrc/rrt_track.hip.h) ----------------------
  * For every course of a batch: what ClosedLoopRRTStar.check_tracking_path_is_feasible(path) (rrt_10:1526-1564) returns,

@@ -32,10 +32,11 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_get_track_stats",
            "rrtx_steer_create", "rrtx_steer_destroy", "rrtx_steer_last_error", "rrtx_steer_solve", "rrtx_steer_get_counts",
            "rrtx_steer_get_summary", "rrtx_steer_get_points", "rrtx_steer_get_kernel_ms", "rrtx_steer_set_obstacles",
-           "rrtx_steer_get_hits",
+           "rrtx_steer_get_hits", "rrtx_steer_solve_lqr", "rrtx_steer_get_ends",
            "rrtx_tracker_create", "rrtx_tracker_destroy", "rrtx_tracker_last_error", "rrtx_tracker_run",
            "rrtx_tracker_get_counts", "rrtx_tracker_get_records", "rrtx_tracker_get_arrays", "rrtx_tracker_get_kernel_ms"]
 STEER_DUBINS, STEER_RS = 0, 1                                                      # include/rrtx.h: #define RRTX_STEER_*
+STEER_LQR = 2   # this binding's own name for "solved by rrtx_steer_solve_lqr": the C ABI has an entry point, not a kind value
 STEER_OK, STEER_NO_PATH, STEER_RAISES_ZERODIV, STEER_RAISES_VALUE = 0, 1, 2, 3
 DUBINS_WORDS = ("LSL", "RSR", "LSR", "RSL", "RLR", "LRL")   # _PATH_TYPE_MAP order: the word indices of rrtx_steer_solve
 RS_COST_EUCLID, RS_COST_PATH = 0, 1     # include/rrtx.h: #define RRTX_RS_COST_*
@@ -170,6 +171,8 @@ def load():
     L.rrtx_steer_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.rrtx_steer_set_obstacles.argtypes = [vp, vp, C.c_int64, C.c_double]
     L.rrtx_steer_get_hits.argtypes = [vp, vp]
+    L.rrtx_steer_solve_lqr.argtypes = [vp, i32, C.c_int64, C.c_int64, vp, vp, C.c_double, C.c_double, C.c_double, i32]
+    L.rrtx_steer_get_ends.argtypes = [vp, vp]
     L.rrtx_tracker_create.argtypes = [i32, C.POINTER(vp)]
     L.rrtx_tracker_destroy.argtypes = [vp]
     L.rrtx_tracker_destroy.restype = None
@@ -557,8 +560,9 @@ class Handle:
 
 
 class Steer:
-    """Thin RAII wrapper over rrtx_steer* (batched Dubins / Reeds-Shepp curves between pose pairs); also a context
-    manager.  It owns the device buffers of its solves, so repeated solves reuse them."""
+    """Thin RAII wrapper over rrtx_steer* (batched Dubins / Reeds-Shepp curves between pose pairs, LQR rollouts between
+    point pairs); also a context manager.  It owns the device buffers of its solves, so repeated solves of any kind
+    reuse them."""
 
     def __init__(self, device=0):
         self.L = load()
@@ -612,6 +616,25 @@ class Steer:
                                                  None if wo is None else wo.ctypes.data, 0 if wo is None else len(wo),
                                                  int(bool(points))), "rrtx_steer_solve")
 
+    def solve_lqr(self, starts, goals, step_size, max_time=100.0, goal_dist=0.1, points=True, product=False):
+        """starts / goals: float64 arrays (n, 2) -- product: (ns, 2) and (ng, 2); step_size > 0: the resampled rollout,
+        0: the raw one.  Returns 0 or RRTX_PARTIAL."""
+        st = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 2)
+        go = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 2)
+        if not product and len(go) != len(st):
+            raise ValueError("solve_lqr: %d starts for %d goals" % (len(st), len(go)))
+        self._keep = (st, go)
+        return self._chk(self.L.rrtx_steer_solve_lqr(self._s, int(bool(product)), len(st), len(go), st.ctypes.data,
+                                                     go.ctypes.data, float(step_size), float(max_time), float(goal_dist),
+                                                     int(bool(points))), "rrtx_steer_solve_lqr")
+
+    def ends(self):
+        """(n, 2) end points of the last solve, an LQR one."""
+        n, _ = self.counts()
+        e = np.zeros((n, 2))
+        self._chk(self.L.rrtx_steer_get_ends(self._s, e.ctypes.data), "rrtx_steer_get_ends")
+        return e
+
     def set_obstacles(self, obstacle_list, robot_radius=0.0):
         """The (x, y, size) rows every later solve tests its curves against (any number up to 2^20); an empty list turns
         the check off."""
@@ -643,12 +666,13 @@ class Steer:
                   "rrtx_steer_get_summary")
         return status, length, nseg, seglen, modes, off
 
-    def points(self):
+    def points(self, yaw=True):
+        """The flat (x, y, yaw) of the last solve; yaw=False (an LQR solve has none): (x, y, None)."""
         _, m = self.counts()
-        x = np.zeros(m); y = np.zeros(m); yaw = np.zeros(m)
-        self._chk(self.L.rrtx_steer_get_points(self._s, x.ctypes.data, y.ctypes.data, yaw.ctypes.data, m),
+        x = np.zeros(m); y = np.zeros(m); w = np.zeros(m) if yaw else None
+        self._chk(self.L.rrtx_steer_get_points(self._s, x.ctypes.data, y.ctypes.data, w.ctypes.data if yaw else None, m),
                   "rrtx_steer_get_points")
-        return x, y, yaw
+        return x, y, w
 
     def kernel_ms(self):
         ms = C.c_double()

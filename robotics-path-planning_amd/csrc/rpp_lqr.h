@@ -1,5 +1,6 @@
 // rpp_lqr.h -- LQR steer of LQR-RRT* (rrt_09), host + device source like rpp_core.h.
-// Reference: /root/reference/src_path_planning/10_path_planning_01_rrt_09_lqr_rrt_star.py (rrt_09)
+// Reference: /root/reference/src_path_planning/10_path_planning_01_rrt_09_lqr_rrt_star.py (rrt_09); its LQRPlanner is,
+//   line for line, the one of 10_path_planning_00_lqr_path.py :15-114 (the batch form: steer_batch.hip.h)
 //   LQRPlanner.lqr_planning :944-986, solve_dare / dlqr :988-1018, get_system_model :1020-1026,
 //   sample_path :1157-1172, steer :1174-1192, check_collision :1292-1305, calc_new_cost :1432-1442.
 //
@@ -31,34 +32,80 @@ static inline int lqr_nt(double step) {
   return n;
 }
 
-// One LQR rollout from (sx, sy) to (gx, gy), resampled with `nt` points per segment of parameter step `step`.
-// Calls pt(k, px, py) for every resampled point in order (k = 0 ..), returns the number of rollout points
-// (len(wx): >= 2), or 0 when the rollout never gets within GOAL_DIST (lqr_planning returns [], []).
-template <class F>
-RPP_HD static inline int lqr_walk(double sx, double sy, double gx, double gy, double step, int nt, F&& pt) {
+// One step of the closed loop x' = A x + B u with u = -K x, rounded as above.  The one copy of the recurrence.
+RPP_HD static inline void lqr_step(double* x0, double* x1) {
+  const double u = -(kLqrK0 * *x0 + kLqrK1 * *x1);
+  const double n0 = __builtin_fma(0.1, *x0, *x1) + 0.0 * u;
+  const double n1 = (0.0 * *x0 + 0.1 * *x1) + u;
+  *x0 = n0;
+  *x1 = n1;
+}
+
+// lqr_planning :944-986 (= 10_path_planning_00_lqr_path.py :24-66) with MAX_TIME and GOAL_DIST as arguments.  Calls
+// seg(wx, wy, rx, ry) for every rollout segment, previous point -> new point, in order; returns the number of rollout
+// points (len(rx): >= 2), or 0 when the rollout never gets within goal_dist (lqr_planning returns [], []).  `time`
+// gains 0.1 per pass, so max_time <= 100.0 bounds the rollout at 1001 segments.
+template <class S>
+RPP_HD static inline int lqr_rollout(double sx, double sy, double gx, double gy, double max_time, double goal_dist,
+                                     S&& seg) {
   double x0 = sx - gx, x1 = sy - gy;
   double wx = sx, wy = sy;   // previous rollout point
-  int nw = 1, k = 0;
+  int nw = 1;
   double time = 0.0;
-  while (time <= kLqrMaxTime) {
+  while (time <= max_time) {
     time += kLqrDt;
-    const double u = -(kLqrK0 * x0 + kLqrK1 * x1);
-    const double n0 = __builtin_fma(0.1, x0, x1) + 0.0 * u;
-    const double n1 = (0.0 * x0 + 0.1 * x1) + u;
-    x0 = n0;
-    x1 = n1;
+    lqr_step(&x0, &x1);
     const double rx = x0 + gx, ry = x1 + gy;
+    seg(wx, wy, rx, ry);
+    wx = rx;
+    wy = ry;
+    nw++;
+    if (py_hypot(gx - rx, gy - ry) <= goal_dist) return nw;
+  }
+  return 0;
+}
+
+// One LQR rollout from (sx, sy) to (gx, gy), resampled with `nt` points per segment of parameter step `step`.
+// Calls pt(k, px, py) for every resampled point in order (k = 0 ..), returns the number of rollout points
+// (len(wx): >= 2), or 0 when the rollout never gets within goal_dist (lqr_planning returns [], []).
+template <class F>
+RPP_HD static inline int lqr_walk(double sx, double sy, double gx, double gy, double step, int nt, double max_time,
+                                  double goal_dist, F&& pt) {
+  int k = 0;
+  return lqr_rollout(sx, sy, gx, gy, max_time, goal_dist, [&](double wx, double wy, double rx, double ry) {
     // segment (wx, wy) -> (rx, ry) of sample_path :1161-1165
     for (int j = 0; j < nt; j++) {
       const double t = (double)j * step;
       pt(k++, t * rx + (1.0 - t) * wx, t * ry + (1.0 - t) * wy);
     }
-    wx = rx;
-    wy = ry;
-    nw++;
-    if (py_hypot(gx - rx, gy - ry) <= kLqrGoalDist) return nw;
+  });
+}
+
+// rrt_09's own LQRPlanner: MAX_TIME = 100.0, GOAL_DIST = 0.1 (:938-940)
+template <class F>
+RPP_HD static inline int lqr_walk(double sx, double sy, double gx, double gy, double step, int nt, F&& pt) {
+  return lqr_walk(sx, sy, gx, gy, step, nt, kLqrMaxTime, kLqrGoalDist, pt);
+}
+
+// Point k of a rollout's polyline on its own, for a caller that knows the point count from lqr_walk / lqr_rollout: the
+// recurrence is run to rollout segment k / nt without the goal test, then interpolated as sample_path does.  nt == 0:
+// the rollout's own point k (rx[k], ry[k]).
+RPP_HD static inline void lqr_point(double sx, double sy, double gx, double gy, double step, int nt, int k, double* x,
+                                    double* y) {
+  double x0 = sx - gx, x1 = sy - gy;
+  const int seg = nt > 0 ? k / nt : k;
+  for (int i = 0; i < seg; i++) lqr_step(&x0, &x1);
+  const double wx = seg > 0 ? x0 + gx : sx, wy = seg > 0 ? x1 + gy : sy;
+  if (nt == 0) {
+    *x = wx;
+    *y = wy;
+    return;
   }
-  return 0;
+  lqr_step(&x0, &x1);
+  const double rx = x0 + gx, ry = x1 + gy;
+  const double t = (double)(k - seg * nt) * step;
+  *x = t * rx + (1.0 - t) * wx;
+  *y = t * ry + (1.0 - t) * wy;
 }
 
 // What every caller of steer / calc_new_cost needs from one edge, nothing stored: point count, endpoint px[-1],

@@ -1,13 +1,14 @@
-// rrtx_api_steer.inc -- rrtx_steer_*: batched Dubins / Reeds-Shepp curves between pose pairs (steer_batch.hip.h);
-// included by rrtx_api.hip
+// rrtx_api_steer.inc -- rrtx_steer_*: batched Dubins / Reeds-Shepp curves between pose pairs and LQR rollouts between
+// point pairs (steer_batch.hip.h); included by rrtx_api.hip
 struct rrtx_steer : DevObj {
-  // device buffers, grown on demand
-  DevBuf starts, goals, curv, status, nseg, total, seglen, modes, npts, plan, offsets, px, py, pyaw, flag, obs, hit;
+  // device buffers, grown on demand and shared by the kinds: a solve writes every entry it later serves
+  DevBuf starts, goals, curv, status, nseg, total, seglen, modes, npts, plan, offsets, px, py, pyaw, flag, obs, hit, ends;
   // the obstacle list of rrtx_steer_set_obstacles: packed rows (ox, oy, thr); it goes to the device at the next solve
   std::vector<double> h_obs;
   bool obs_dirty = false;
   // the last solve
   bool solved = false, has_points = false, has_hits = false;
+  int kind = rppsb::KIND_DUBINS;
   int64_t n = 0, n_points = 0;
   double kernel_ms = 0.0;
   std::vector<int64_t> h_offsets;
@@ -24,6 +25,21 @@ void steer_launch_fill(bool store, bool check, unsigned blocks, hipStream_t stre
   else
     hipLaunchKernelGGL((rppsb::steer_fill<KIND, false, true>), dim3(blocks), dim3(rppsb::TPB), 0, stream, a);
 }
+
+// One solve, its arguments already checked by its entry point
+struct SteerJob {
+  const char* fn;
+  int kind;   // rppsb::KIND_*
+  int32_t product;
+  int64_t n, ng;
+  const double *starts, *goals;   // rows of 3 (x, y, yaw); LQR: rows of 2
+  const double* curvature;        // not LQR
+  int32_t curvature_per_pair;
+  double step_size;               // LQR: 0 = the raw rollout
+  const int32_t* word_order;
+  int32_t n_words, want_points;
+  double max_time, goal_dist;     // LQR
+};
 }  // namespace
 
 extern "C" {
@@ -45,6 +61,8 @@ void rrtx_steer_destroy(rrtx_steer* s) {
 }
 
 const char* rrtx_steer_last_error(rrtx_steer* s) { return s ? s->err.c_str() : null_object_err.c_str(); }
+
+static int steer_run(rrtx_steer* s, const SteerJob& j);
 
 static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
                        const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
@@ -98,6 +116,21 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
                                                  : D / step_size + 20.0 / (step_size * cmin);
     if (!(pts <= 4194304.0)) return bad("the poses are so far apart for this curvature and step that a curve could exceed 2^22 points");
   }
+  const SteerJob job = {fn, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size, word_order, n_words,
+                        want_points, 0.0, 0.0};
+  return steer_run(s, job);
+}
+
+// What every solve does once its arguments are checked: buffers, stage 1, the prefix sum, stage 2.
+static int steer_run(rrtx_steer* s, const SteerJob& j) {
+  const char* fn = j.fn;
+  const int kind = j.kind;
+  const bool lqr = kind == rppsb::KIND_LQR;
+  const int32_t product = j.product, want_points = j.want_points;
+  const int64_t n = j.n, ng = j.ng, n_goals = product ? ng : n, np = product ? n * ng : n;
+  const int64_t nc = lqr ? 0 : (j.curvature_per_pair ? np : 1);
+  const size_t row = sizeof(double) * (lqr ? 2 : 3);
+  const double *starts = j.starts, *goals = j.goals, *curvature = j.curvature;
   if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
   // With an obstacle list the curves' points are computed (stage 1 as for points, then the fill kernel) whether or not
   // they are stored.
@@ -107,6 +140,7 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
   s->solved = false;
   s->has_points = false;
   s->has_hits = false;
+  s->kind = kind;
   s->n = np;
   s->n_points = 0;
   s->kernel_ms = 0.0;
@@ -121,19 +155,23 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
   HIPCHK(s, hipSetDevice(s->device));
   int rc;
   const size_t N = (size_t)np;
-  if ((rc = s->reserve(s->starts, sizeof(double) * 3 * (size_t)n))) return rc;
-  if ((rc = s->reserve(s->goals, sizeof(double) * 3 * (size_t)n_goals))) return rc;
-  if ((rc = s->reserve(s->curv, sizeof(double) * (size_t)nc))) return rc;
+  if ((rc = s->reserve(s->starts, row * (size_t)n))) return rc;
+  if ((rc = s->reserve(s->goals, row * (size_t)n_goals))) return rc;
   if ((rc = s->reserve(s->status, sizeof(int32_t) * N))) return rc;
   if ((rc = s->reserve(s->nseg, sizeof(int32_t) * N))) return rc;
   if ((rc = s->reserve(s->total, sizeof(double) * N))) return rc;
-  if ((rc = s->reserve(s->seglen, sizeof(double) * 5 * N))) return rc;
-  if ((rc = s->reserve(s->modes, 8 * N))) return rc;
+  if (lqr) {   // no curvature, segments or modes; and no stage-2 record: a pair's two points are the record
+    if ((rc = s->reserve(s->ends, sizeof(double) * 2 * N))) return rc;
+  } else {
+    if ((rc = s->reserve(s->curv, sizeof(double) * (size_t)nc))) return rc;
+    if ((rc = s->reserve(s->seglen, sizeof(double) * 5 * N))) return rc;
+    if ((rc = s->reserve(s->modes, 8 * N))) return rc;
+  }
   if ((rc = s->reserve(s->npts, sizeof(int32_t) * N))) return rc;
   if ((rc = s->reserve(s->flag, sizeof(int32_t)))) return rc;
   if (stage2) {
-    const size_t rec = kind == RRTX_STEER_DUBINS ? sizeof(rpp::DubinsPlan) : sizeof(rpp::RsCourse);
-    if ((rc = s->reserve(s->plan, rec * N))) return rc;
+    const size_t rec = kind == rppsb::KIND_DUBINS ? sizeof(rpp::DubinsPlan) : sizeof(rpp::RsCourse);
+    if (!lqr && (rc = s->reserve(s->plan, rec * N))) return rc;
     if ((rc = s->reserve(s->offsets, sizeof(int64_t) * (N + 1)))) return rc;
   }
   if (n_obs > 0) {
@@ -144,24 +182,31 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
       s->obs_dirty = false;
     }
   }
-  HIPCHK(s, hipMemcpyAsync(s->starts.p, starts, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, s->stream));
-  HIPCHK(s, hipMemcpyAsync(s->goals.p, goals, sizeof(double) * 3 * (size_t)n_goals, hipMemcpyHostToDevice, s->stream));
-  HIPCHK(s, hipMemcpyAsync(s->curv.p, curvature, sizeof(double) * (size_t)nc, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(s, hipMemcpyAsync(s->starts.p, starts, row * (size_t)n, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(s, hipMemcpyAsync(s->goals.p, goals, row * (size_t)n_goals, hipMemcpyHostToDevice, s->stream));
+  if (!lqr) HIPCHK(s, hipMemcpyAsync(s->curv.p, curvature, sizeof(double) * (size_t)nc, hipMemcpyHostToDevice, s->stream));
   HIPCHK(s, hipMemsetAsync(s->flag.p, 0, sizeof(int32_t), s->stream));
 
   rppsb::Args a;
   memset(&a, 0, sizeof(a));
   a.starts = s->starts.as<const double>();
   a.goals = s->goals.as<const double>();
-  a.curv = curvature_per_pair ? s->curv.as<const double>() : nullptr;
-  a.curv0 = curvature[0];
-  a.step = step_size;
+  if (lqr) {
+    a.max_time = j.max_time;
+    a.goal_dist = j.goal_dist;
+    a.nt = j.step_size > 0.0 ? rpp::lqr_nt(j.step_size) : 0;
+    a.ends = s->ends.as<double>();
+  } else {
+    a.curv = j.curvature_per_pair ? s->curv.as<const double>() : nullptr;
+    a.curv0 = curvature[0];
+  }
+  a.step = j.step_size;
   a.n = np;
   a.ng = product ? ng : 1;
   a.product = product ? 1 : 0;
   a.want_points = stage2 ? 1 : 0;
-  a.n_order = word_order ? n_words : 6;
-  for (int i = 0; i < 6; i++) a.order[i] = (word_order && i < n_words) ? word_order[i] : i;
+  a.n_order = j.word_order ? j.n_words : 6;
+  for (int i = 0; i < 6; i++) a.order[i] = (j.word_order && i < j.n_words) ? j.word_order[i] : i;
   a.status = s->status.as<int32_t>();
   a.nseg = s->nseg.as<int32_t>();
   a.total = s->total.as<double>();
@@ -183,7 +228,9 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
   std::vector<int32_t> cnt(stage2 ? N : 0);
   float ms = 0.f;
   rc = s->timed(&ms, [&] {
-    if (kind == RRTX_STEER_DUBINS) {
+    if (lqr) {
+      hipLaunchKernelGGL(rppsb::steer_lqr_solve, dim3(blk), dim3(rppsb::TPB), 0, s->stream, a);
+    } else if (kind == rppsb::KIND_DUBINS) {
       hipLaunchKernelGGL(rppsb::steer_dubins_solve, dim3(blk), dim3(rppsb::TPB), 0, s->stream, a);
     } else {
       hipLaunchKernelGGL(rppsb::steer_rs_solve, dim3((unsigned)((np + rppsb::RS_PAIRS - 1) / rppsb::RS_PAIRS)),
@@ -212,7 +259,7 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
       if (want_points) {
         if ((rc = s->reserve(s->px, sizeof(double) * (size_t)tot))) return rc;
         if ((rc = s->reserve(s->py, sizeof(double) * (size_t)tot))) return rc;
-        if ((rc = s->reserve(s->pyaw, sizeof(double) * (size_t)tot))) return rc;
+        if (!lqr && (rc = s->reserve(s->pyaw, sizeof(double) * (size_t)tot))) return rc;
       }
       if ((tot + rppsb::TPB - 1) / rppsb::TPB > 0x7fffffffLL)
         return fail(s, RRTX_E_OVERFLOW, std::string(fn) + "more polyline points than one launch can fill");
@@ -221,11 +268,13 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
       if (want_points) {
         a.px = s->px.as<double>();
         a.py = s->py.as<double>();
-        a.pyaw = s->pyaw.as<double>();
+        a.pyaw = lqr ? nullptr : s->pyaw.as<double>();
       }
       const unsigned fblk = (unsigned)((tot + rppsb::TPB - 1) / rppsb::TPB);
       rc = s->timed(&ms, [&] {
-        if (kind == RRTX_STEER_DUBINS)
+        if (lqr)
+          steer_launch_fill<rppsb::KIND_LQR>(want_points != 0, n_obs > 0, fblk, s->stream, a);
+        else if (kind == rppsb::KIND_DUBINS)
           steer_launch_fill<rppsb::KIND_DUBINS>(want_points != 0, n_obs > 0, fblk, s->stream, a);
         else
           steer_launch_fill<rppsb::KIND_RS>(want_points != 0, n_obs > 0, fblk, s->stream, a);
@@ -245,6 +294,33 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
   return RRTX_OK;
 }
 
+static int steer_solve_lqr(rrtx_steer* s, int32_t product, int64_t n, int64_t ng, const double* starts, const double* goals,
+                           double step_size, double max_time, double goal_dist, int32_t want_points) {
+  const char* fn = "rrtx_steer_solve_lqr: ";
+  auto bad = [&](const char* m) { return fail(s, RRTX_E_INVALID, std::string(fn) + m); };
+  if (!s) return bad("the steer object is NULL");
+  if (!starts || !goals) return bad("starts or goals is NULL");
+  if (n < 0 || (product && ng < 0)) return bad("a negative batch size");
+  const int64_t n_goals = product ? ng : n;
+  if (n > (1LL << 30) || n_goals > (1LL << 30) || (product && n && ng && n > (1LL << 30) / ng))
+    return bad("more than 2^30 pairs");
+  for (int side = 0; side < 2; side++) {
+    const double* q = side ? goals : starts;
+    const int64_t vals = 2 * (side ? n_goals : n);
+    for (int64_t i = 0; i < vals; i++)
+      if (!(fabs(q[i]) <= 1e6)) return bad("a coordinate is not finite or exceeds 1e6 in magnitude");
+  }
+  // a segment is resampled at ceil(1 / step_size) parameters: the bound keeps it at <= 1000 points
+  if (!(step_size >= 0.0) || (step_size > 0.0 && step_size < 1e-3))
+    return bad("step_size must be 0 (the raw rollout) or >= 1e-3");
+  // the rollout loop runs while time <= max_time: the reference's 100.0 bounds it at 1001 steps
+  if (!(max_time >= 0.0 && max_time <= rpp::kLqrMaxTime)) return bad("max_time must lie in 0 .. 100");
+  if (goal_dist != goal_dist) return bad("goal_dist is NaN");   // a negative one is legal: no rollout ever arrives
+  const SteerJob job = {fn, rppsb::KIND_LQR, product, n, ng, starts, goals, nullptr, 0, step_size, nullptr, 0, want_points,
+                        max_time, goal_dist};
+  return steer_run(s, job);
+}
+
 int rrtx_steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
                      const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
                      const int32_t* word_order, int32_t n_words, int32_t want_points) {
@@ -255,6 +331,27 @@ int rrtx_steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, in
     if (s) s->solved = false;
     return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve: ") + e.what());
   }
+}
+
+int rrtx_steer_solve_lqr(rrtx_steer* s, int32_t product, int64_t n, int64_t ng, const double* starts, const double* goals,
+                         double step_size, double max_time, double goal_dist, int32_t want_points) {
+  try {
+    return steer_solve_lqr(s, product, n, ng, starts, goals, step_size, max_time, goal_dist, want_points);
+  } catch (const std::exception& e) {
+    if (s) s->solved = false;
+    return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve_lqr: ") + e.what());
+  }
+}
+
+int rrtx_steer_get_ends(rrtx_steer* s, double* ends) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_ends: the steer object is NULL");
+  if (!s->solved) return fail(s, RRTX_E_STATE, "rrtx_steer_get_ends: no completed solve");
+  if (s->kind != rppsb::KIND_LQR) return fail(s, RRTX_E_STATE, "rrtx_steer_get_ends: the last solve was not an LQR solve");
+  if (s->n == 0) return RRTX_OK;
+  if (!ends) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_ends: ends is NULL");
+  HIPCHK(s, hipSetDevice(s->device));
+  HIPCHK(s, hipMemcpy(ends, s->ends.p, sizeof(double) * 2 * (size_t)s->n, hipMemcpyDeviceToHost));
+  return RRTX_OK;
 }
 
 int rrtx_steer_get_counts(rrtx_steer* s, int64_t* n_pairs, int64_t* n_points) {
@@ -278,6 +375,11 @@ int rrtx_steer_get_summary(rrtx_steer* s, int32_t* status, double* length, int32
   if (status) HIPCHK(s, hipMemcpy(status, s->status.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
   if (length) HIPCHK(s, hipMemcpy(length, s->total.p, sizeof(double) * N, hipMemcpyDeviceToHost));
   if (n_seg) HIPCHK(s, hipMemcpy(n_seg, s->nseg.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  if (s->kind == rppsb::KIND_LQR) {   // a rollout has neither: zero-filled
+    if (seg_len) memset(seg_len, 0, sizeof(double) * 5 * N);
+    if (modes) memset(modes, 0, 8 * N);
+    return RRTX_OK;
+  }
   if (seg_len) HIPCHK(s, hipMemcpy(seg_len, s->seglen.p, sizeof(double) * 5 * N, hipMemcpyDeviceToHost));
   if (modes) HIPCHK(s, hipMemcpy(modes, s->modes.p, 8 * N, hipMemcpyDeviceToHost));
   return RRTX_OK;
@@ -286,6 +388,7 @@ int rrtx_steer_get_summary(rrtx_steer* s, int32_t* status, double* length, int32
 int rrtx_steer_get_points(rrtx_steer* s, double* x, double* y, double* yaw, int64_t cap) {
   if (!s) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_points: the steer object is NULL");
   if (!s->solved || !s->has_points) return fail(s, RRTX_E_STATE, "rrtx_steer_get_points: no completed solve with points");
+  if (yaw && s->kind == rppsb::KIND_LQR) return fail(s, RRTX_E_STATE, "rrtx_steer_get_points: an LQR rollout has no yaw, pass NULL");
   if (cap < s->n_points) return fail(s, RRTX_E_CAPACITY, "rrtx_steer_get_points: the buffers are too small");
   if (s->n_points == 0) return RRTX_OK;
   const size_t bytes = sizeof(double) * (size_t)s->n_points;

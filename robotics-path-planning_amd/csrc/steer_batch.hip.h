@@ -1,8 +1,10 @@
-// steer_batch.hip.h -- the two curve solvers as batch kernels of their own (gfx950): shortest Dubins / Reeds-Shepp
-// curve between many pose pairs, without a planner around them.
+// steer_batch.hip.h -- the steering functions as batch kernels of their own (gfx950): shortest Dubins / Reeds-Shepp
+// curve between many pose pairs, and the LQR rollout between many point pairs, without a planner around them.
 // Reference: /root/reference/src_path_planning/10_path_planning_00_dubins_path.py plan_dubins_path :109-197 and
 //   10_path_planning_00_reeds_shepp_path.py reeds_shepp_path_planning :506-515 (the same functions, line for line, as the
 //   copies inside rrt_05 / rrt_06); the scalar pieces are csrc/rpp_dubins.h and csrc/rpp_rs.h.
+//   10_path_planning_00_lqr_path.py LQRPlanner.lqr_planning :24-66 (= rrt_09 :944-986) with rrt_09's sample_path
+//   :1157-1172, steer :1174-1192, check_collision :1292-1305 and calc_new_cost :1432-1442; scalar pieces csrc/rpp_lqr.h.
 //
 // Path lengths differ per pair, so the work is two stages with a CSR layout between them:
 //   stage 1  steer_dubins_solve  one lane per pair: dubins_prepare over the ordered word list -> word, segment lengths,
@@ -14,9 +16,14 @@
 //                                reports "step size too large" hides every later one: the table is read in order, so
 //                                the later variants are computed speculatively and never looked at.
 //            steer_rs_course     (points wanted) one lane per pair: generate_local_course prepared for random access.
+//            steer_lqr_solve     one lane per pair: the rollout once for its point count (a rollout that fails costs its
+//                                1001 steps and nothing else), then once more for the end point and the length.  No
+//                                per-pair record goes to stage 2: the pair's two points are the record.
 //   offsets  exclusive prefix sum of the point counts (host, one int32 per pair down, one int64 per pair up).
 //   stage 2  steer_fill          one lane per output point: binary search of the point index in offsets, then
-//                                dubins_point / rs_point, which are random-access by point index.  STORE writes the
+//                                dubins_point / rs_point / lqr_point, which are random-access by point index (lqr_point
+//                                re-runs the recurrence to the point's segment: <= 10 steps at the reference's
+//                                settings, 19 with goal_dist = 0).  STORE writes the
 //                                point; CHECK tests it against the obstacle list (rpp_collide.h) and takes the lowest
 //                                obstacle index any point of the pair touches into hit[pair].
 // Lengths-only is stage 1 alone (no plan, no course, no offsets) -- unless an obstacle list is set: then stage 1 runs as
@@ -24,11 +31,13 @@
 // Product mode: pair p of ns x ng is (start p / ng, goal p % ng), formed here; the host never builds the product.
 #pragma once
 #include "rpp_collide.h"
+#include "rpp_lqr.h"
 #include "rpp_rs.h"
 
 namespace rppsb {
 
-constexpr int KIND_DUBINS = 0, KIND_RS = 1;
+constexpr int KIND_DUBINS = 0, KIND_RS = 1;   // include/rrtx.h RRTX_STEER_DUBINS / RRTX_STEER_RS
+constexpr int KIND_LQR = 2;                   // not a value of the ABI: rrtx_steer_solve_lqr is this kind's entry point
 constexpr int ST_OK = 0, ST_NO_PATH = 1, ST_RAISES_ZERODIV = 2, ST_RAISES_VALUE = 3;   // include/rrtx.h RRTX_STEER_*
 constexpr int TPB = 256;            // steer_dubins_solve, steer_rs_course, steer_fill
 constexpr int RS_TPB = 64;          // steer_rs_solve: one wave
@@ -37,22 +46,25 @@ constexpr int RS_PAIRS = RS_TPB / RS_LANES;
 constexpr int RS_KEPT = 3;          // table state: set_path kept this candidate (0 none, 1 candidate, 2 step too large)
 
 struct Args {
-  const double* starts;   // (ns, 3)
-  const double* goals;    // (ng, 3); pair mode: (n, 3)
+  const double* starts;   // (ns, 3); LQR: (ns, 2)
+  const double* goals;    // (ng, 3); pair mode: (n, 3); LQR: 2 columns
   const double* curv;     // one value per pair, or nullptr: curv0
   double curv0, step;
+  double max_time, goal_dist;   // LQR: MAX_TIME, GOAL_DIST of the LQRPlanner
+  int32_t nt;             // LQR: resampling parameters per rollout segment (rpp::lqr_nt), 0 = the raw rollout
   int64_t n, ng;          // pairs; product mode: goals per start
   int32_t product, want_points;
   int32_t order[6];       // Dubins: the words to try, in this order (the first wins ties)
   int32_t n_order;
   int32_t* status;        // [n]
-  int32_t* nseg;          // [n]
-  double* total;          // [n]  the absolute values of seglen added up in segment order
+  int32_t* nseg;          // [n]  LQR: rollout points len(rx)
+  double* total;          // [n]  the absolute values of seglen added up in segment order; LQR: see steer_lqr_solve
   double* seglen;         // [n][5] as the reference returns them (divided by the curvature)
   char* modes;            // [n][8] letters, NUL padded
   int32_t* npts;          // [n]
   rpp::DubinsPlan* dplan; // [n]
   rpp::RsCourse* course;  // [n]
+  double* ends;           // [n][2]  LQR: the last point
   int32_t* flag;          // set when any pair is not ST_OK
   const int64_t* offsets; // [n + 1]
   double *px, *py, *pyaw; // [offsets[n]]
@@ -70,6 +82,13 @@ __device__ inline void pair_poses(const Args& a, int64_t p, double* s, double* g
   }
 }
 __device__ inline double pair_curv(const Args& a, int64_t p) { return a.curv ? a.curv[p] : a.curv0; }
+__device__ inline void pair_xy(const Args& a, int64_t p, double* s, double* g) {   // LQR: rows (x, y)
+  const int64_t si = a.product ? p / a.ng : p, gi = a.product ? p % a.ng : p;
+  for (int i = 0; i < 2; i++) {
+    s[i] = a.starts[2 * si + i];
+    g[i] = a.goals[2 * gi + i];
+  }
+}
 
 // ---- Dubins, stage 1 ----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(TPB) void steer_dubins_solve(Args a) {
@@ -232,6 +251,49 @@ __global__ __launch_bounds__(TPB) void steer_rs_course(Args a) {
   a.npts[p] = C.total;
 }
 
+// ---- LQR, stage 1 -------------------------------------------------------------------------------------------------
+// total[p] is Python's left-to-right sum of math.hypot over consecutive points: of the resampled points (nt > 0; what
+// steer :1189 adds to the cost and calc_new_cost :1440 returns), or of the rollout points themselves (nt == 0; the
+// lqr_path script returns no length, this one is the project's definition).  ends[p] is px[-1], py[-1] -- the last
+// resampled point, which is not the last rollout point (sample_path leaves that one out) -- or rx[-1], ry[-1].
+__global__ __launch_bounds__(TPB) void steer_lqr_solve(Args a) {
+  const int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (p >= a.n) return;
+  double s[2], g[2];
+  pair_xy(a, p, s, g);
+  const int nw = rpp::lqr_rollout(s[0], s[1], g[0], g[1], a.max_time, a.goal_dist, [](double, double, double, double) {});
+  a.nseg[p] = nw;
+  if (nw == 0) {   // "Cannot found path": lqr_planning returns [], []
+    a.status[p] = ST_NO_PATH;
+    a.total[p] = 0.0;
+    a.npts[p] = 0;
+    a.ends[2 * p] = a.ends[2 * p + 1] = 0.0;
+    if (a.hit) a.hit[p] = -2;
+    atomicOr(a.flag, 1);
+    return;
+  }
+  double len = 0.0, ex = 0.0, ey = 0.0;
+  if (a.nt > 0) {
+    rpp::lqr_walk(s[0], s[1], g[0], g[1], a.step, a.nt, a.max_time, a.goal_dist, [&](int k, double qx, double qy) {
+      if (k > 0) len += rpp::py_hypot(qx - ex, qy - ey);
+      ex = qx;
+      ey = qy;
+    });
+  } else {
+    rpp::lqr_rollout(s[0], s[1], g[0], g[1], a.max_time, a.goal_dist, [&](double wx, double wy, double rx, double ry) {
+      len += rpp::py_hypot(rx - wx, ry - wy);
+      ex = rx;
+      ey = ry;
+    });
+  }
+  a.status[p] = ST_OK;
+  a.total[p] = len;
+  a.npts[p] = a.nt > 0 ? (nw - 1) * a.nt : nw;
+  a.ends[2 * p] = ex;
+  a.ends[2 * p + 1] = ey;
+  if (a.hit) a.hit[p] = -1;
+}
+
 // ---- stage 2 -------------------------------------------------------------------------------------------------------
 // <KIND, true, false> is the fill kernel alone.  With CHECK a lane past the last point does not leave: it stays as a copy
 // of the last point (the same pair, the same answer), so every lane of a wave takes part in the shuffles below.
@@ -254,15 +316,20 @@ __global__ __launch_bounds__(TPB) void steer_fill(Args a) {
       hi = mid;
   }
   const int k = (int)(idx - a.offsets[lo]);
-  double x, y, yaw;
-  if (KIND == KIND_DUBINS)
+  double x, y, yaw = 0.0;
+  if (KIND == KIND_DUBINS) {
     rpp::dubins_point(a.dplan[lo], k, pair_curv(a, lo), &x, &y, &yaw);
-  else
+  } else if (KIND == KIND_RS) {
     rpp::rs_point(a.course[lo], k, &x, &y, &yaw);
+  } else {
+    double s[2], g[2];
+    pair_xy(a, lo, s, g);
+    rpp::lqr_point(s[0], s[1], g[0], g[1], a.step, a.nt, k, &x, &y);
+  }
   if (STORE && live) {
     a.px[idx] = x;
     a.py[idx] = y;
-    a.pyaw[idx] = yaw;
+    if (KIND != KIND_LQR) a.pyaw[idx] = yaw;   // an LQR course has no yaw
   }
   if (CHECK) {
     // The obstacle index is the same in every lane still in first_hit's loop, and a lane leaves the loop at its first

@@ -1,4 +1,5 @@
-"""Batched Dubins / Reeds-Shepp curves between pose pairs on the GPU, without a planner around them.
+"""Batched Dubins / Reeds-Shepp curves between pose pairs, and LQR rollouts between point pairs, on the GPU, without a
+planner around them.
 
     bs = BatchSteer("dubins")                       # or "rs"
     res = bs.plan(starts, goals, curvature)         # (n, 3) poses each; res.path(i) = the reference's five-tuple
@@ -12,13 +13,25 @@ rrt_06 :1749) on the curve's own points, made in the kernel that computes them.
 Every double is what the reference's plan_dubins_path (10_path_planning_00_dubins_path.py :109) /
 reeds_shepp_path_planning (10_path_planning_00_reeds_shepp_path.py :506) returns for that pair, bit for bit.  There is no
 CPU fallback: without a device the call raises RrtxError.
+
+    bs = BatchSteer("lqr")                          # rows (x, y); no curvature
+    res = bs.plan(starts, goals)                    # rrt_09's edges: res.path(i) = sample_path's (px, py, course_lens),
+                                                    # res.end[i] = (px[-1], py[-1]), res.length[i] = sum(course_lens)
+    rx, ry = bs.plan(starts, goals, resample=False).path(i)    # LQRPlanner.lqr_planning's rollout itself
+    cost = bs.plan(starts, goals, points=False, product=True, obstacle_list=circles).length_matrix(free_only=True)
+
+"lqr" is LQRPlanner.lqr_planning (10_path_planning_00_lqr_path.py :24-66 = rrt_09 :944-986) for the reference's model
+(DT = 0.1, Q = R = I), with rrt_09's sample_path :1157-1172, edge cost (steer :1189, calc_new_cost :1432-1442) and
+check_collision :1292-1305 around it; max_time and goal_dist are the planner's MAX_TIME and GOAL_DIST.
 """
+import math
+
 import numpy as np
 
 from . import _abi
 
-KINDS = {"dubins": _abi.STEER_DUBINS, "rs": _abi.STEER_RS, "reeds_shepp": _abi.STEER_RS}
-DEFAULT_STEP = {_abi.STEER_DUBINS: 0.1, _abi.STEER_RS: 0.2}
+KINDS = {"dubins": _abi.STEER_DUBINS, "rs": _abi.STEER_RS, "reeds_shepp": _abi.STEER_RS, "lqr": _abi.STEER_LQR}
+DEFAULT_STEP = {_abi.STEER_DUBINS: 0.1, _abi.STEER_RS: 0.2, _abi.STEER_LQR: 0.2}   # LQR: rrt_09's step_size (:1063)
 
 
 def word_order(selected_types):
@@ -41,22 +54,30 @@ class SteerResult:
     """One solved batch.  status (n,) STEER_*; length (n,): the absolute segment lengths added up; modes: list of n strings; lengths: list of n arrays of segment
     lengths; offsets (n + 1,) and the flat x, y, yaw when points were asked for, else None; hit (n,) int32 when the batch
     was planned with an obstacle list (-1 free, j >= 0 the first obstacle of the list the curve touches, -2 no curve),
-    else None."""
+    else None.
+    An "lqr" batch: n_seg is the number of rollout points len(rx), end (n, 2) the last point, length the sum of
+    math.hypot over consecutive points, left to right -- of the resampled points (rrt_09's edge cost), or with
+    resample=False of the rollout points (the lqr_path script returns no length: this one is this package's definition);
+    yaw is None, modes and lengths are empty."""
 
-    def __init__(self, kind, status, length, nseg, seglen, modes, offsets, xyz, shape, rc, kernel_ms, hit=None):
+    def __init__(self, kind, status, length, nseg, seglen, modes, offsets, xyz, shape, rc, kernel_ms, hit=None, end=None,
+                 resampled=True):
         self.kind = kind
         self.status = status
         self.length = length
         self.n_seg = nseg
         self.seg_len = seglen
         self.modes = [m.decode() for m in modes]
-        self.lengths = [seglen[i, :nseg[i]].copy() for i in range(len(nseg))]
+        nl = np.zeros_like(nseg) if kind == _abi.STEER_LQR else nseg   # a rollout has no segment lengths
+        self.lengths = [seglen[i, :nl[i]].copy() for i in range(len(nseg))]
         self.offsets = offsets
         self.x, self.y, self.yaw = xyz if xyz is not None else (None, None, None)
         self.shape = shape          # (ns, ng) in product mode, else None
         self.rc = rc                # 0 or RRTX_PARTIAL
         self.kernel_ms = kernel_ms
         self.hit = hit
+        self.end = end              # "lqr": (n, 2); else None
+        self.resampled = resampled  # "lqr": path(i) is sample_path's triple, not the rollout
 
     @property
     def free(self):
@@ -78,6 +99,8 @@ class SteerResult:
         if st == _abi.STEER_NO_PATH:
             if self.kind == _abi.STEER_DUBINS:
                 raise TypeError("'NoneType' object is not iterable")
+            if self.kind == _abi.STEER_LQR:   # rrt_09's steer fails at px[-1] (:1185) before any check
+                raise IndexError("list index out of range")
             return False   # Reeds-Shepp: path(i) is (None,) * 5, and check_collision(None, ...) is False (:1751)
         return bool(self.hit[i] == -1)
 
@@ -86,8 +109,12 @@ class SteerResult:
 
     def path(self, i):
         """What the reference function returns for pair i: (x, y, yaw, modes, lengths) -- numpy arrays and lists for
-        Dubins, lists for Reeds-Shepp, (None,) * 5 where Reeds-Shepp finds no path; raises where the reference raises."""
+        Dubins, lists for Reeds-Shepp, (None,) * 5 where Reeds-Shepp finds no path; raises where the reference raises.
+        "lqr": sample_path's (px, py, course_lens) as lists, or with resample=False lqr_planning's (rx, ry); empty lists
+        where the rollout never arrives."""
         st = int(self.status[i])
+        if self.kind == _abi.STEER_LQR:
+            return self._lqr_path(i, st)
         if st == _abi.STEER_RAISES_ZERODIV:
             raise ZeroDivisionError("float division by zero")
         if st == _abi.STEER_RAISES_VALUE:
@@ -105,6 +132,18 @@ class SteerResult:
             return self.x[a:b].copy(), self.y[a:b].copy(), self.yaw[a:b].copy(), modes, lengths
         return self.x[a:b].tolist(), self.y[a:b].tolist(), self.yaw[a:b].tolist(), modes, lengths
 
+    def _lqr_path(self, i, st):
+        if st == _abi.STEER_NO_PATH:
+            return ([], [], []) if self.resampled else ([], [])
+        if self.x is None:
+            raise _abi.RrtxError("path(): this batch was solved with points=False")
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        px, py = self.x[a:b].tolist(), self.y[a:b].tolist()
+        if not self.resampled:
+            return px, py
+        dx, dy = np.diff(px), np.diff(py)   # :1167-1170, on the host as the reference does it
+        return px, py, [math.hypot(idx, idy) for (idx, idy) in zip(dx, dy)]
+
     def length_matrix(self, free_only=False):
         """The (ns, ng) lengths of a product-mode batch; free_only: +inf where the pair is not free."""
         if self.shape is None:
@@ -115,12 +154,12 @@ class SteerResult:
 
 
 class BatchSteer:
-    """Shortest Dubins ("dubins") or Reeds-Shepp ("rs") curves for batches of pose pairs; device buffers are kept between
-    calls of plan()."""
+    """Shortest Dubins ("dubins") or Reeds-Shepp ("rs") curves for batches of pose pairs, or LQR rollouts ("lqr") for
+    batches of point pairs; device buffers are kept between calls of plan()."""
 
     def __init__(self, kind, device=0):
         if kind not in KINDS:
-            raise ValueError("BatchSteer: kind is 'dubins' or 'rs', not %r" % (kind,))
+            raise ValueError("BatchSteer: kind is 'dubins', 'rs' or 'lqr', not %r" % (kind,))
         self.kind = KINDS[kind]
         self._steer = _abi.Steer(device)
 
@@ -134,23 +173,55 @@ class BatchSteer:
         self.close()
         return False
 
-    def plan(self, starts, goals, curvature, step_size=None, selected_types=None, points=True, product=False,
-             obstacle_list=None, robot_radius=0.0):
+    def plan(self, starts, goals, curvature=None, step_size=None, selected_types=None, points=True, product=False,
+             obstacle_list=None, robot_radius=0.0, resample=True, max_time=100.0, goal_dist=0.1):
         """starts, goals: (n, 3) rows of (x, y, yaw) -- with product=True (ns, 3) and (ng, 3), pair p = (p // ng, p % ng).
         curvature: a float or one per pair.  step_size: Reeds-Shepp any value > 0 (default 0.2); Dubins 0.1 only.
         selected_types (Dubins): word names in the order to try them.  obstacle_list: rows (x, y, size) every curve is
-        tested against with robot_radius (result.hit / .free); None or empty: no check."""
+        tested against with robot_radius (result.hit / .free); None or empty: no check.
+        "lqr": rows are (x, y); curvature and selected_types must stay None; step_size >= 1e-3 (default rrt_09's 0.2) is
+        sample_path's step, resample=False gives the rollout itself; max_time <= 100.0 and goal_dist are the planner's
+        MAX_TIME and GOAL_DIST (these three keywords belong to this kind alone)."""
         if step_size is None:
             step_size = DEFAULT_STEP[self.kind]
+        if self.kind == _abi.STEER_LQR:
+            return self._plan_lqr(starts, goals, curvature, step_size, selected_types, points, product, obstacle_list,
+                                  robot_radius, resample, max_time, goal_dist)
+        if curvature is None:
+            raise TypeError("BatchSteer.plan: curvature is required for Dubins and Reeds-Shepp curves")
+        if resample is not True or max_time != 100.0 or goal_dist != 0.1:
+            raise ValueError("BatchSteer.plan: resample, max_time and goal_dist belong to kind 'lqr'")
         wo = word_order(selected_types)
         st = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
         go = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
         S = self._steer
-        ob = np.zeros((0, 3)) if obstacle_list is None else np.asarray(obstacle_list, dtype=np.float64).reshape(-1, 3)
-        if len(ob) or S.n_obstacles:   # (nothing to clear when no list was ever set: today's calls, unchanged)
-            S.set_obstacles(ob, robot_radius)
+        ob = self._set_obstacles(obstacle_list, robot_radius)   # (nothing to clear when no list was ever set)
         rc = S.solve(self.kind, st, go, curvature, step_size, word_order=wo, points=points, product=product)
         status, length, nseg, seglen, modes, off = S.summary(offsets=bool(points))
         xyz = S.points() if points else None
         return SteerResult(self.kind, status, length, nseg, seglen, modes, off, xyz,
                            (len(st), len(go)) if product else None, rc, S.kernel_ms(), hit=S.hits() if len(ob) else None)
+
+    def _set_obstacles(self, obstacle_list, robot_radius):
+        S = self._steer
+        ob = np.zeros((0, 3)) if obstacle_list is None else np.asarray(obstacle_list, dtype=np.float64).reshape(-1, 3)
+        if len(ob) or S.n_obstacles:
+            S.set_obstacles(ob, robot_radius)
+        return ob
+
+    def _plan_lqr(self, starts, goals, curvature, step_size, selected_types, points, product, obstacle_list, robot_radius,
+                  resample, max_time, goal_dist):
+        if curvature is not None or selected_types is not None:
+            raise ValueError("BatchSteer('lqr').plan: an LQR rollout has no curvature and no selected_types")
+        if resample and not float(step_size) > 0.0:
+            raise ValueError("BatchSteer('lqr').plan: step_size must be > 0 (resample=False gives the raw rollout)")
+        st = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 2)
+        go = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 2)
+        S = self._steer
+        ob = self._set_obstacles(obstacle_list, robot_radius)
+        rc = S.solve_lqr(st, go, step_size if resample else 0.0, max_time, goal_dist, points=points, product=product)
+        status, length, nseg, seglen, modes, off = S.summary(offsets=bool(points))
+        xyz = S.points(yaw=False) if points else None
+        return SteerResult(self.kind, status, length, nseg, seglen, modes, off, xyz,
+                           (len(st), len(go)) if product else None, rc, S.kernel_ms(), hit=S.hits() if len(ob) else None,
+                           end=S.ends(), resampled=bool(resample))

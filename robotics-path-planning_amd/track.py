@@ -26,6 +26,8 @@ def _csr(courses):
     """(offsets, x, y, yaw) of `courses`: a SteerResult (or anything with its offsets / x / y / yaw), a CSR tuple, or a list
     of (cx, cy, cyaw) triples."""
     if hasattr(courses, "offsets") and hasattr(courses, "yaw"):
+        if getattr(courses, "kind", None) == _abi.STEER_LQR:
+            raise ValueError("BatchTrack: an LQR SteerResult has no yaw, the tracker needs courses of (x, y, yaw)")
         if courses.offsets is None or courses.x is None:
             raise ValueError("BatchTrack: the SteerResult was solved with points=False, it holds no courses")
         courses = (courses.offsets, courses.x, courses.y, courses.yaw)

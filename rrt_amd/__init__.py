@@ -2,8 +2,9 @@
 
 Per-script drop-in modules: `rrt_amd.rrt_01` ... `rrt_amd.rrt_10` carry exactly the names the reference script of that
 number defines for its driver cell (`RRT`, `BITStar`, `Node`, `path_smoothing`, `get_path_length`), so a driver written
-against `10_path_planning_01_rrt_04_rrt_star.py` runs after `from rrt_amd.rrt_04 import *`.  `rrt_amd.dubins_path` and `rrt_amd.reeds_shepp_path` do the same for the two
-stand-alone curve scripts (`plan_dubins_path`, `reeds_shepp_path_planning`)."""
+against `10_path_planning_01_rrt_04_rrt_star.py` runs after `from rrt_amd.rrt_04 import *`.  `rrt_amd.dubins_path`, `rrt_amd.reeds_shepp_path`
+and `rrt_amd.lqr_path` do the same for the three stand-alone steering scripts (`plan_dubins_path`, `reeds_shepp_path_planning`,
+`LQRPlanner`)."""
 import importlib
 import os
 import sys

@@ -1,6 +1,6 @@
 """Throughput of the batched Dubins / Reeds-Shepp curves (BatchSteer): pairs/s for lengths-only and for points.
 
-    python tools/steer_bench.py [--pairs 1048576] [--reps 5] [--cpu-pairs 2000] [--obstacles M]
+    python tools/steer_bench.py [--pairs 1048576] [--reps 5] [--cpu-pairs 2000] [--obstacles M] [--kind lqr]
 
 Random pairs in the pose box of the known-answer vectors ([-2, 15]^2, any yaw), curvature 1, Reeds-Shepp step 0.2.  The
 GPU figure is HIP-event kernel time (stage 1, and stage 1 + fill), the median of --reps solves after one warm-up solve;
@@ -11,7 +11,11 @@ line per kind.  Needs a device: there is no CPU fallback.
 --obstacles M (default 0: the output above, unchanged) adds the obstacle check against M seeded circles in the same box
 (radius 0.2 .. 0.8): "check_lengths_*" is points=False with the list set (the collision-free cost-matrix path),
 "check_points_*" is points=True with it, "plan_wall_ms" of each variant is one whole BatchSteer.plan() call (transfers
-and result arrays included), and "free_fraction" the share of pairs whose curve touches nothing."""
+and result arrays included), and "free_fraction" the share of pairs whose curve touches nothing.
+
+--kind lqr (default: the two curve kinds, the output above, unchanged) measures BatchSteer("lqr") alone: random point pairs
+in the same box, rrt_09's step 0.2, the same variants; the one-core figure beside it is tests/lqr_oracle.edge (pure Python)
+on a subsample of the same pairs."""
 import argparse
 import json
 import os
@@ -40,11 +44,15 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cpu-pairs", type=int, default=2000)
     ap.add_argument("--obstacles", type=int, default=0)
+    ap.add_argument("--kind", choices=("curves", "lqr"), default="curves")
     args = ap.parse_args()
     import oracle
     import rrt_amd
-    for kind in ("dubins", "rs"):
-        p = pairs(args.pairs, 7 if kind == "dubins" else 8)
+    lqr = args.kind == "lqr"
+    for kind in (("lqr",) if lqr else ("dubins", "rs")):
+        p = pairs(args.pairs, {"dubins": 7, "rs": 8, "lqr": 10}[kind])
+        cols = (slice(0, 2), slice(3, 5)) if lqr else (slice(0, 3), slice(3, 6))   # LQR rows are (x, y): no yaw
+        curv = () if lqr else (1.0,)
         out = {"kind": kind, "pairs": args.pairs, "reps": args.reps}
         with rrt_amd.BatchSteer(kind) as bs:
             for points in (False, True):
@@ -52,7 +60,10 @@ def main():
                 res = None
                 for rep in range(args.reps + 1):
                     t0 = time.perf_counter()
-                    res = bs._steer.solve(bs.kind, p[:, 0:3], p[:, 3:6], 1.0, 0.1 if kind == "dubins" else 0.2, points=points)
+                    if lqr:
+                        res = bs._steer.solve_lqr(p[:, cols[0]], p[:, cols[1]], 0.2, points=points)
+                    else:
+                        res = bs._steer.solve(bs.kind, p[:, 0:3], p[:, 3:6], 1.0, 0.1 if kind == "dubins" else 0.2, points=points)
                     wall.append((time.perf_counter() - t0) * 1e3)
                     ms.append(bs._steer.kernel_ms())
                 k = "points" if points else "lengths"
@@ -72,7 +83,7 @@ def main():
                     ms, wall = [], []
                     for rep in range(args.reps + 1):
                         t0 = time.perf_counter()
-                        res = bs.plan(p[:, 0:3], p[:, 3:6], 1.0, points=points, obstacle_list=obs)
+                        res = bs.plan(p[:, cols[0]], p[:, cols[1]], *curv, points=points, obstacle_list=obs)
                         wall.append((time.perf_counter() - t0) * 1e3)
                         ms.append(res.kernel_ms)
                     if obs is not None:
@@ -82,15 +93,24 @@ def main():
                     out[k + "_plan_wall_ms"] = float(np.median(wall[1:]))
                     res = None
         m = min(args.cpu_pairs, args.pairs)
-        fn = oracle.dubins if kind == "dubins" else oracle.reeds_shepp
-        t0 = time.perf_counter()
-        for i in range(m):
-            a = [float(v) for v in p[i]]
-            try:
-                fn(*a, 1.0)
-            except (ZeroDivisionError, ValueError):
-                pass
-        dt = time.perf_counter() - t0
+        if lqr:
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import lqr_oracle
+            t0 = time.perf_counter()
+            for i in range(m):
+                lqr_oracle.edge(float(p[i, 0]), float(p[i, 1]), float(p[i, 3]), float(p[i, 4]), 0.2)
+            dt = time.perf_counter() - t0
+            out["cpu_oracle"] = "tests/lqr_oracle.edge (pure Python)"
+        else:
+            fn = oracle.dubins if kind == "dubins" else oracle.reeds_shepp
+            t0 = time.perf_counter()
+            for i in range(m):
+                a = [float(v) for v in p[i]]
+                try:
+                    fn(*a, 1.0)
+                except (ZeroDivisionError, ValueError):
+                    pass
+            dt = time.perf_counter() - t0
         out["cpu_oracle_pairs"] = m
         out["cpu_oracle_pairs_per_s_one_core"] = m / dt
         print(json.dumps(out), flush=True)
