@@ -493,6 +493,78 @@ int rrtx_tracker_get_arrays(rrtx_tracker* t, double* x, double* y, double* yaw, 
 /* HIP-event time of the kernels of the last run (both launches) */
 int rrtx_tracker_get_kernel_ms(rrtx_tracker* t, double* kernel_ms);
 
+/* ---- batched cubic-spline courses through waypoints, without a planner (csrc/spline_batch.hip.h, csrc/rpp_spline.h) ---------
+ * For every course of a batch: what calc_spline_course(x, y, ds) (10_path_planning_00_cubic_spline_path.py :313-325) returns --
+ * rx, ry, ryaw, rk, s: a natural cubic spline over the chord length, sampled every ds.  Point counts, offsets and s are the
+ * reference's bit for bit.  With the spline coefficient c given (cx, cy: the reference's sx.c and sy.c) x, y, yaw and k are
+ * the reference's doubles bit for bit as well.  Without it c is this library's own definition: the Thomas recurrence of
+ * csrc/rpp_spline.h over the interior rows, because the reference's np.linalg.solve is not one arithmetic; the
+ * result then agrees with the reference to rounding (about 1e-13 in position), not bit for bit.
+ * The spline object is independent of rrtx_handle; it owns the device buffers of its runs and reuses them from call to call
+ * (they grow, never shrink).  One host thread per object.  Call order: create, run, the getters of that run, run again, as
+ * often as wanted; a getter before the first run returns RRTX_E_STATE. */
+typedef struct rrtx_spline rrtx_spline;
+/* per-course status */
+#define RRTX_SPLINE_OK 0
+#define RRTX_SPLINE_DEGENERATE 1   /* two consecutive waypoints coincide (h[i] == 0): the reference divides by zero and returns
+                                      inf / nan garbage.  The course owns no points. */
+#define RRTX_SPLINE_REF_RAISES 2   /* the last sample parameter (len - 1) * ds rounds onto s[-1]: bisect lands on the last knot
+                                      and the reference raises IndexError at self.b[i].  The course owns no points. */
+#define RRTX_SPLINE_MAX_WAYPOINTS 4096       /* per course */
+#define RRTX_SPLINE_MAX_POINTS 268435456LL   /* per call (2^28), over all courses */
+typedef struct rrtx_spline_record {
+  int32_t status;     /* RRTX_SPLINE_* */
+  int32_t reserved;
+  int64_t n_points;   /* len(np.arange(0, s[-1], ds)); 0 unless status is RRTX_SPLINE_OK */
+  double length;      /* s[-1] */
+} rrtx_spline_record;
+typedef struct rrtx_spline_batch {
+  int64_t n;                  /* courses */
+  const int64_t* offsets;     /* n + 1, CSR into x / y (and cx / cy) */
+  const double *x, *y;        /* the waypoints */
+  const double* ds;           /* one value, or n values when ds_per_course != 0 */
+  int32_t ds_per_course;
+  int32_t want_arrays;        /* 0: records (and hits) only, no point is stored */
+  const double *cx, *cy;      /* both NULL: c by the Thomas recurrence on the device; else n_c values each, c as data */
+  int64_t n_c;                /* must equal offsets[n] when cx / cy are given */
+  const double* obstacles;    /* rows (x, y, size) */
+  int64_t n_obstacles;        /* 0: no collision check; at most 2^20 */
+  double robot_radius;
+} rrtx_spline_batch;
+/* As rrtx_steer_create: without a usable gfx950 device the return value is RRTX_E_NO_DEVICE and *out is still an object
+ * (to be destroyed like any other): its runs check their arguments and then return RRTX_E_NO_DEVICE. */
+int rrtx_spline_create(int32_t device, rrtx_spline** out);
+void rrtx_spline_destroy(rrtx_spline* s);
+/* The message of the last call on `s` that failed; for s == NULL the last failure of a spline call of this thread that had no object. */
+const char* rrtx_spline_last_error(rrtx_spline* s);
+/* Fits and samples every course.  With obstacles every point is tested by check_collision of the pose planners (rrt_05:1625-1638,
+ * the form rrtx_steer_set_obstacles describes); thresholds are (size + robot_radius) ** 2, computed on the host.
+ * Returns RRTX_OK, or RRTX_PARTIAL when some record's status is not RRTX_SPLINE_OK (every other course is complete).  n == 0 is
+ * a valid empty run.  RRTX_E_INVALID, before any HIP call (also on a host without a device): a NULL pointer (obstacles may be
+ * NULL when n_obstacles is 0), n < 0 or n > 2^30, offsets that do not start at 0 or that decrease, a course of fewer than 2 or
+ * more than RRTX_SPLINE_MAX_WAYPOINTS waypoints, one of cx / cy without the other, n_c != offsets[n], n_obstacles < 0 or
+ * > 2^20, a coordinate, c, obstacle entry or robot_radius that is not finite, a coordinate above 1e6 in magnitude, a ds that
+ * is not finite or not > 0, or more than RRTX_SPLINE_MAX_POINTS points in all -- estimated before the run from the host's own
+ * hypot (one point of slack per course), and checked again on the counts the device returns.  After these checks a host
+ * without a device gets RRTX_E_NO_DEVICE. */
+int rrtx_spline_run(rrtx_spline* s, const rrtx_spline_batch* b);
+/* rec: the n records of the last run; offsets (may be NULL): n + 1 entries, the exclusive sum of n_points; n_courses, n_points,
+ * kernel_ms (each may be NULL): the course count, offsets[n], and the HIP-event time of the kernels of the run (fit and
+ * evaluation; the prefix sum between them is not kernel time).  rec may be NULL to read the counts alone. */
+int rrtx_spline_get_records(rrtx_spline* s, rrtx_spline_record* rec, int64_t* offsets, int64_t* n_courses, int64_t* n_points,
+                            double* kernel_ms);
+/* The flat arrays of the last run, n_points doubles each, any pointer may be NULL: what calc_spline_course returns as rx, ry,
+ * ryaw, rk and s, course after course (cap = doubles available in each; RRTX_E_CAPACITY when too small).  RRTX_E_STATE
+ * after a run with want_arrays == 0. */
+int rrtx_spline_get_points(rrtx_spline* s, double* x, double* y, double* yaw, double* k, double* t, int64_t cap);
+/* c as the last run used it, offsets[n] doubles per axis in the waypoint layout (zeros for a course whose status is
+ * RRTX_SPLINE_DEGENERATE); cap = doubles available in each. */
+int rrtx_spline_get_c(rrtx_spline* s, double* cx, double* cy, int64_t cap);
+/* Per course of the last run: -1 no point of the course touches an obstacle (free); j >= 0 the lowest index of the list any
+ * point touches; -2 the course owns no points (status != RRTX_SPLINE_OK, or no sample), nothing was tested.  RRTX_E_STATE when
+ * the last run had no obstacle list. */
+int rrtx_spline_get_hits(rrtx_spline* s, int32_t* hit);
+
 /* parity harness: out[i] = op(a[i], b[i]) evaluated on the device.  op 0 math.hypot, 1 x**2, 2 sin, 3 cos, 4 atan2,
  * 5 steer end x (rrt_04:1086-1115), 6 sqrt, 7 a/b, 8 acos, 9 asin, 10 checksum of the Reeds-Shepp steer
  * (0,0,0) -> (a, b, a+b) (rrt_06:1426-1441, csrc/rpp_rs.h), 11 math.tan(a) (|a| <= 0.79), 12 np.hypot(a, b) */

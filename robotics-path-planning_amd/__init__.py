@@ -9,6 +9,7 @@ import it with importlib, or through the `rrt_amd` shim at the repository root:
 
 Submodules: planner (RRT = rrt_01's class, RRTStar = rrt_04's class, BatchPlanner), steer (BatchSteer: batched Dubins /
 Reeds-Shepp curves between pose pairs), track (BatchTrack: batched closed-loop tracking of courses given as data),
+spline (BatchSpline: batched cubic-spline courses through waypoints, the step from a path to a course),
 _abi (ctypes binding of include/rrtx.h), csrc/ (HIP kernels + C ABI sources).
 """
 from . import _abi  # noqa: F401
@@ -16,5 +17,6 @@ from .planner import (RRT, RRTSobol, RRTStar, RRTStarDubins, RRTDubins, RRTStarR
                       informed_rotation)
 from .steer import BatchSteer  # noqa: F401
 from .track import BatchTrack  # noqa: F401
+from .spline import BatchSpline  # noqa: F401
 
-__all__ = ["RRT", "RRTSobol", "RRTStar", "RRTStarDubins", "RRTDubins", "RRTStarReedsShepp", "BITStar", "InformedRRTStar", "LQRRRTStar", "ClosedLoopRRTStar", "BatchPlanner", "BatchSteer", "BatchTrack", "Node", "AreaBounds", "get_path_length", "path_smoothing"]
+__all__ = ["RRT", "RRTSobol", "RRTStar", "RRTStarDubins", "RRTDubins", "RRTStarReedsShepp", "BITStar", "InformedRRTStar", "LQRRRTStar", "ClosedLoopRRTStar", "BatchPlanner", "BatchSteer", "BatchTrack", "BatchSpline", "Node", "AreaBounds", "get_path_length", "path_smoothing"]

@@ -34,13 +34,17 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_steer_get_summary", "rrtx_steer_get_points", "rrtx_steer_get_kernel_ms", "rrtx_steer_set_obstacles",
            "rrtx_steer_get_hits", "rrtx_steer_solve_lqr", "rrtx_steer_get_ends",
            "rrtx_tracker_create", "rrtx_tracker_destroy", "rrtx_tracker_last_error", "rrtx_tracker_run",
-           "rrtx_tracker_get_counts", "rrtx_tracker_get_records", "rrtx_tracker_get_arrays", "rrtx_tracker_get_kernel_ms"]
+           "rrtx_tracker_get_counts", "rrtx_tracker_get_records", "rrtx_tracker_get_arrays", "rrtx_tracker_get_kernel_ms",
+           "rrtx_spline_create", "rrtx_spline_destroy", "rrtx_spline_last_error", "rrtx_spline_run", "rrtx_spline_get_records",
+           "rrtx_spline_get_points", "rrtx_spline_get_c", "rrtx_spline_get_hits"]
 STEER_DUBINS, STEER_RS = 0, 1                                                      # include/rrtx.h: #define RRTX_STEER_*
 STEER_LQR = 2   # this binding's own name for "solved by rrtx_steer_solve_lqr": the C ABI has an entry point, not a kind value
 STEER_OK, STEER_NO_PATH, STEER_RAISES_ZERODIV, STEER_RAISES_VALUE = 0, 1, 2, 3
 DUBINS_WORDS = ("LSL", "RSR", "LSR", "RSL", "RLR", "LRL")   # _PATH_TYPE_MAP order: the word indices of rrtx_steer_solve
 RS_COST_EUCLID, RS_COST_PATH = 0, 1     # include/rrtx.h: #define RRTX_RS_COST_*
 TRACK_FAIL_REACH, TRACK_FAIL_ANGLE, TRACK_FAIL_LONG, TRACK_FAIL_COLLISION = 1, 2, 4, 8   # #define RRTX_TRACK_FAIL_*
+SPLINE_OK, SPLINE_DEGENERATE, SPLINE_REF_RAISES = 0, 1, 2                                # #define RRTX_SPLINE_*
+SPLINE_MAX_WAYPOINTS, SPLINE_MAX_POINTS = 4096, 1 << 28
 
 
 class Params(C.Structure):
@@ -82,6 +86,16 @@ class TrackBatch(C.Structure):
                 ("per_course", C.c_void_p), ("start_state", C.c_void_p), ("obstacles", C.c_void_p),
                 ("obs_offsets", C.c_void_p), ("n_obstacles", C.c_int64), ("robot_radius", C.c_void_p),
                 ("robot_radius_per_course", C.c_int32), ("want_arrays", C.c_int32)]
+
+
+SPLINE_RECORD = np.dtype([("status", np.int32), ("reserved", np.int32), ("n_points", np.int64), ("length", np.float64)])
+
+
+class SplineBatch(C.Structure):
+    """rrtx_spline_batch: the courses of one rrtx_spline_run (pointers into arrays the caller keeps alive)."""
+    _fields_ = [("n", C.c_int64), ("offsets", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p), ("ds", C.c_void_p),
+                ("ds_per_course", C.c_int32), ("want_arrays", C.c_int32), ("cx", C.c_void_p), ("cy", C.c_void_p),
+                ("n_c", C.c_int64), ("obstacles", C.c_void_p), ("n_obstacles", C.c_int64), ("robot_radius", C.c_double)]
 
 
 class Stats(C.Structure):
@@ -183,9 +197,20 @@ def load():
     L.rrtx_tracker_get_records.argtypes = [vp, vp, vp]
     L.rrtx_tracker_get_arrays.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64]
     L.rrtx_tracker_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.rrtx_spline_create.argtypes = [i32, C.POINTER(vp)]
+    L.rrtx_spline_destroy.argtypes = [vp]
+    L.rrtx_spline_destroy.restype = None
+    L.rrtx_spline_last_error.argtypes = [vp]
+    L.rrtx_spline_last_error.restype = C.c_char_p
+    L.rrtx_spline_run.argtypes = [vp, C.POINTER(SplineBatch)]
+    L.rrtx_spline_get_records.argtypes = [vp, vp, vp, i64p, i64p, C.POINTER(C.c_double)]
+    L.rrtx_spline_get_points.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64]
+    L.rrtx_spline_get_c.argtypes = [vp, vp, vp, C.c_int64]
+    L.rrtx_spline_get_hits.argtypes = [vp, vp]
     for f in EXPORTS:
         if f not in ("rrtx_last_error", "rrtx_destroy", "rrtx_abi_version", "rrtx_device_count", "rrtx_steer_destroy",
-                     "rrtx_steer_last_error", "rrtx_tracker_destroy", "rrtx_tracker_last_error"):
+                     "rrtx_steer_last_error", "rrtx_tracker_destroy", "rrtx_tracker_last_error", "rrtx_spline_destroy",
+                     "rrtx_spline_last_error"):
             getattr(L, f).restype = C.c_int
     if L.rrtx_abi_version() != RRTX_ABI_VERSION:
         raise RrtxError("librrtx.so ABI version mismatch")
@@ -744,6 +769,75 @@ class Tracker:
         ms = C.c_double()
         self._chk(self.L.rrtx_tracker_get_kernel_ms(self._t, C.byref(ms)), "rrtx_tracker_get_kernel_ms")
         return ms.value
+
+
+class Spline:
+    """Thin RAII wrapper over rrtx_spline* (batched cubic-spline courses through waypoints); also a context manager.  It
+    owns the device buffers of its runs, so repeated runs reuse them."""
+
+    def __init__(self, device=0):
+        self.L = load()
+        self._s = C.c_void_p()
+        rc = self.L.rrtx_spline_create(int(device), C.byref(self._s))
+        if rc != 0:
+            msg = self.L.rrtx_spline_last_error(self._s).decode()
+            self.close()
+            raise RrtxError("rrtx_spline_create: %s %s" % (ERRORS.get(rc, rc), msg))
+
+    def close(self):
+        if getattr(self, "_s", None):
+            self.L.rrtx_spline_destroy(self._s)
+            self._s = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_spline_last_error(self._s).decode()))
+        return rc
+
+    def run(self, batch):
+        """batch: SplineBatch (its arrays are kept alive by the caller).  Returns 0 or RRTX_PARTIAL."""
+        return self._chk(self.L.rrtx_spline_run(self._s, C.byref(batch)), "rrtx_spline_run")
+
+    def records(self):
+        """(records (n,) SPLINE_RECORD, offsets (n + 1,), kernel_ms) of the last run."""
+        n, m, ms = C.c_int64(), C.c_int64(), C.c_double()
+        self._chk(self.L.rrtx_spline_get_records(self._s, None, None, C.byref(n), C.byref(m), C.byref(ms)),
+                  "rrtx_spline_get_records")
+        rec = np.zeros(n.value, dtype=SPLINE_RECORD)
+        off = np.zeros(n.value + 1, dtype=np.int64)
+        self._chk(self.L.rrtx_spline_get_records(self._s, rec.ctypes.data, off.ctypes.data, None, None, None),
+                  "rrtx_spline_get_records")
+        return rec, off, ms.value
+
+    def points(self, m):
+        """The five flat arrays x, y, yaw, k, s of the last run, m = offsets[-1] doubles each."""
+        arr = [np.zeros(m) for _ in range(5)]
+        self._chk(self.L.rrtx_spline_get_points(self._s, *[q.ctypes.data for q in arr], m), "rrtx_spline_get_points")
+        return arr
+
+    def c(self, w):
+        """(cx, cy) as the last run used them, w = waypoints of the batch."""
+        cx, cy = np.zeros(w), np.zeros(w)
+        self._chk(self.L.rrtx_spline_get_c(self._s, cx.ctypes.data, cy.ctypes.data, w), "rrtx_spline_get_c")
+        return cx, cy
+
+    def hits(self, n):
+        hit = np.zeros(n, dtype=np.int32)
+        self._chk(self.L.rrtx_spline_get_hits(self._s, hit.ctypes.data), "rrtx_spline_get_hits")
+        return hit
 
 
 def rccl_unique_id():

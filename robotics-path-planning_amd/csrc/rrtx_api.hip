@@ -22,6 +22,7 @@
 #include "rrt_lqr.hip.h"
 #include "rrt_track.hip.h"
 #include "steer_batch.hip.h"
+#include "spline_batch.hip.h"
 
 using rppk::Ctx;
 using rppk::Inst;
@@ -1733,3 +1734,4 @@ int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps) {
 #include "rrtx_api_rccl.inc"
 #include "rrtx_api_steer.inc"
 #include "rrtx_api_tracker.inc"
+#include "rrtx_api_spline.inc"

@@ -1,0 +1,259 @@
+// rrtx_api_spline.inc -- rrtx_spline_*: batched cubic-spline courses through waypoints (spline_batch.hip.h:
+// spline_fit_kernel, spline_eval_kernel); included by rrtx_api.hip
+struct rrtx_spline : DevObj {
+  // device buffers, grown on demand
+  DevBuf wp_off, x, y, ds, cx, cy, tab, rec, pt_off, out, obs, hit;
+  // the last run
+  bool ran = false, has_arrays = false, has_hits = false;
+  int64_t n = 0, n_wp = 0, n_points = 0;
+  double kernel_ms = 0.0;
+  std::vector<rppsp::Record> h_rec;
+  std::vector<int64_t> h_off;
+  std::vector<int32_t> h_hit;
+};
+
+static_assert(sizeof(rppsp::Record) == sizeof(rrtx_spline_record), "rrtx_spline_record mirrors rppsp::Record");
+static_assert(rppsp::MAX_WAYPOINTS == RRTX_SPLINE_MAX_WAYPOINTS, "the waypoint limit of the header is the kernel's");
+
+inline double (*volatile libm_hypot)(double, double) = hypot;
+
+template <bool STORE, bool CHECK>
+static void spline_launch_eval(int64_t total, hipStream_t stream, const rppsp::Args& a) {
+  const unsigned blocks = (unsigned)((total + rppsp::TPB - 1) / rppsp::TPB);
+  hipLaunchKernelGGL((rppsp::spline_eval_kernel<STORE, CHECK>), dim3(blocks), dim3(rppsp::TPB), 0, stream, a);
+}
+
+static int spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
+  const char* fn = "rrtx_spline_run: ";
+  auto bad = [&](const char* m) { return fail(s, RRTX_E_INVALID, std::string(fn) + m); };
+  if (!s) return bad("the spline object is NULL");
+  if (!b) return bad("the batch is NULL");
+  if (b->n < 0 || b->n > (1LL << 30)) return bad("n is negative or above 2^30");
+  if (!b->offsets || !b->ds) return bad("offsets or ds is NULL");
+  const int64_t n = b->n;
+  if (!csr_ok(b->offsets, n)) return bad("offsets do not start at 0 or decrease");
+  const int64_t W = b->offsets[n];
+  if (W > 0 && (!b->x || !b->y)) return bad("x or y is NULL");
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t m = b->offsets[i + 1] - b->offsets[i];
+    if (m < 2) return bad("a course of fewer than 2 waypoints");
+    if (m > RRTX_SPLINE_MAX_WAYPOINTS) return bad("a course of more than 4096 waypoints");
+  }
+  if ((b->cx != nullptr) != (b->cy != nullptr)) return bad("one of cx, cy is NULL and the other is not");
+  if (b->cx && b->n_c != W) return bad("n_c is not the number of waypoints");
+  if (b->n_obstacles < 0 || b->n_obstacles > (1LL << 20)) return bad("n_obstacles is negative or above 2^20");
+  if (b->n_obstacles > 0 && !b->obstacles) return bad("obstacles is NULL");
+  if (!all_finite(b->x, W) || !all_finite(b->y, W)) return bad("a coordinate is not finite");
+  for (int64_t i = 0; i < W; i++)
+    if (std::fabs(b->x[i]) > 1.0e6 || std::fabs(b->y[i]) > 1.0e6) return bad("a coordinate is above 1e6 in magnitude");
+  if (b->cx && (!all_finite(b->cx, W) || !all_finite(b->cy, W))) return bad("a c value is not finite");
+  if (!all_finite(b->obstacles, 3 * b->n_obstacles)) return bad("an obstacle entry is not finite");
+  if (!std::isfinite(b->robot_radius)) return bad("robot_radius is not finite");
+  const int64_t n_ds = b->ds_per_course ? n : 1;
+  for (int64_t i = 0; i < n_ds; i++)
+    if (!std::isfinite(b->ds[i]) || !(b->ds[i] > 0.0)) return bad("a ds is not finite or not > 0");
+  // the points in all, from the host's own hypot: one point of slack per course against the device's knots
+  double est = 0.0;
+  for (int64_t i = 0; i < n; i++) {
+    double len = 0.0;
+    for (int64_t k = b->offsets[i]; k + 1 < b->offsets[i + 1]; k++) len += libm_hypot(b->x[k + 1] - b->x[k], b->y[k + 1] - b->y[k]);
+    est += std::ceil(len / b->ds[b->ds_per_course ? i : 0]) + 1.0;
+    if (est > (double)RRTX_SPLINE_MAX_POINTS + (double)n) return bad("more than 2^28 points in all");
+  }
+  if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+
+  s->ran = false;
+  s->has_arrays = false;
+  s->has_hits = false;
+  s->n = n;
+  s->n_wp = W;
+  s->n_points = 0;
+  s->kernel_ms = 0.0;
+  s->h_rec.clear();
+  s->h_hit.clear();
+  s->h_off.assign((size_t)n + 1, 0);
+  if (n == 0) {
+    s->has_arrays = b->want_arrays != 0;
+    s->has_hits = b->n_obstacles > 0;
+    s->ran = true;
+    return RRTX_OK;
+  }
+  // obstacle table: packed rows (ox, oy, thr), thr = (size + robot_radius) ** 2 by the planners' routine
+  const int64_t n_obs = b->n_obstacles;
+  std::vector<double> rows(3 * (size_t)n_obs);
+  for (int64_t k = 0; k < n_obs; k++) {
+    rows[3 * k] = b->obstacles[3 * k];
+    rows[3 * k + 1] = b->obstacles[3 * k + 1];
+    rows[3 * k + 2] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius);
+  }
+
+  HIPCHK(s, hipSetDevice(s->device));
+  int rc;
+  const size_t N = (size_t)n;
+  if ((rc = s->upload(s->wp_off, b->offsets, sizeof(int64_t) * (N + 1)))) return rc;
+  if ((rc = s->upload(s->x, b->x, sizeof(double) * (size_t)W))) return rc;
+  if ((rc = s->upload(s->y, b->y, sizeof(double) * (size_t)W))) return rc;
+  if ((rc = s->upload(s->ds, b->ds, sizeof(double) * (size_t)n_ds))) return rc;
+  if (b->cx) {
+    if ((rc = s->upload(s->cx, b->cx, sizeof(double) * (size_t)W))) return rc;
+    if ((rc = s->upload(s->cy, b->cy, sizeof(double) * (size_t)W))) return rc;
+  }
+  if ((rc = s->upload(s->obs, rows.data(), sizeof(double) * rows.size()))) return rc;
+  if ((rc = s->reserve(s->tab, sizeof(double) * 8 * (size_t)W))) return rc;
+  if ((rc = s->reserve(s->rec, sizeof(rppsp::Record) * N))) return rc;
+  if (n_obs > 0 && (rc = s->reserve(s->hit, sizeof(int32_t) * N))) return rc;
+
+  rppsp::Args a;
+  memset(&a, 0, sizeof(a));
+  a.n = n;
+  a.W = W;
+  a.wp_off = s->wp_off.as<const int64_t>();
+  a.x = s->x.as<const double>();
+  a.y = s->y.as<const double>();
+  a.ds = s->ds.as<const double>();
+  a.ds_per_course = b->ds_per_course != 0;
+  a.cx = b->cx ? s->cx.as<const double>() : nullptr;
+  a.cy = b->cx ? s->cy.as<const double>() : nullptr;
+  a.tab = s->tab.as<double>();
+  a.rec = s->rec.as<rppsp::Record>();
+  a.hit = n_obs > 0 ? s->hit.as<int32_t>() : nullptr;
+
+  // the fit, and its records
+  s->h_rec.resize(N);
+  float ms = 0.f;
+  const unsigned fit_blocks = (unsigned)((2 * n + rppsp::TPB - 1) / rppsp::TPB);
+  rc = s->timed(&ms, [&] { hipLaunchKernelGGL(rppsp::spline_fit_kernel, dim3(fit_blocks), dim3(rppsp::TPB), 0, s->stream, a); },
+                [&]() -> int {
+                  HIPCHK(s, hipMemcpyAsync(s->h_rec.data(), s->rec.p, sizeof(rppsp::Record) * N, hipMemcpyDeviceToHost, s->stream));
+                  return RRTX_OK;
+                });
+  if (rc) return rc;
+  s->kernel_ms = ms;
+
+  // offsets: exclusive sum of the point counts
+  int64_t tot = 0;
+  bool partial = false;
+  for (size_t i = 0; i < N; i++) {
+    s->h_off[i] = tot;
+    if (s->h_rec[i].status != RRTX_SPLINE_OK) partial = true;
+    tot += s->h_rec[i].n_points;
+    if (tot > RRTX_SPLINE_MAX_POINTS) return bad("more than 2^28 points in all");
+  }
+  s->h_off[N] = tot;
+  s->n_points = tot;
+
+  const bool store = b->want_arrays != 0, check = n_obs > 0;
+  if (check) s->h_hit.resize(N);
+  if (tot > 0 && (store || check)) {
+    if (store && (rc = s->reserve(s->out, sizeof(double) * 5 * (size_t)tot))) return rc;
+    if ((rc = s->upload(s->pt_off, s->h_off.data(), sizeof(int64_t) * (N + 1)))) return rc;
+    a.pt_off = s->pt_off.as<const int64_t>();
+    a.out = store ? s->out.as<double>() : nullptr;
+    a.obs = check ? s->obs.as<const double>() : nullptr;
+    a.n_obs = n_obs;
+    rc = s->timed(&ms, [&] {
+      if (store && check)
+        spline_launch_eval<true, true>(tot, s->stream, a);
+      else if (store)
+        spline_launch_eval<true, false>(tot, s->stream, a);
+      else
+        spline_launch_eval<false, true>(tot, s->stream, a);
+    }, [&]() -> int {
+      if (check) HIPCHK(s, hipMemcpyAsync(s->h_hit.data(), s->hit.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
+      return RRTX_OK;
+    });
+    if (rc) return rc;
+    s->kernel_ms += ms;
+  } else if (check) {
+    HIPCHK(s, hipMemcpy(s->h_hit.data(), s->hit.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  }
+  // a course with no sample (s[-1] / ds underflows to 0) was tested against nothing
+  for (size_t i = 0; check && i < N; i++)
+    if (s->h_rec[i].n_points == 0) s->h_hit[i] = -2;
+  s->has_arrays = store;
+  s->has_hits = check;
+  s->ran = true;
+  if (partial) {
+    s->err = std::string(fn) + "some courses have coinciding waypoints, or a last sample on the last knot (see the status column)";
+    return RRTX_PARTIAL;
+  }
+  return RRTX_OK;
+}
+
+extern "C" {
+
+int rrtx_spline_create(int32_t device, rrtx_spline** out) {
+  if (!out) return fail<rrtx_spline>(nullptr, RRTX_E_INVALID, "rrtx_spline_create: out is NULL");
+  *out = nullptr;
+  if (device < 0) return fail<rrtx_spline>(nullptr, RRTX_E_INVALID, "rrtx_spline_create: negative device ordinal");
+  rrtx_spline* s = new (std::nothrow) rrtx_spline();
+  if (!s) return fail<rrtx_spline>(nullptr, RRTX_E_HIP, "rrtx_spline_create: out of host memory");
+  *out = s;   // returned on failure too: the caller reads the message, and runs still check their arguments
+  return s->open(device, "rrtx_spline_create");
+}
+
+void rrtx_spline_destroy(rrtx_spline* s) {
+  if (!s) return;
+  if (s->usable) hipSetDevice(s->device);
+  delete s;   // the buffers, then the events and the stream
+}
+
+const char* rrtx_spline_last_error(rrtx_spline* s) { return s ? s->err.c_str() : null_object_err.c_str(); }
+
+int rrtx_spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
+  try {   // host allocations (records, offsets, messages) must not throw across the ABI
+    return spline_run(s, b);
+  } catch (const std::exception& e) {
+    if (s) s->ran = false;
+    return fail(s, RRTX_E_HIP, std::string("rrtx_spline_run: ") + e.what());
+  }
+}
+
+int rrtx_spline_get_records(rrtx_spline* s, rrtx_spline_record* rec, int64_t* offsets, int64_t* n_courses, int64_t* n_points,
+                            double* kernel_ms) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_spline_get_records: the spline object is NULL");
+  if (!s->ran) return fail(s, RRTX_E_STATE, "rrtx_spline_get_records: no completed run");
+  if (rec && s->n) memcpy(rec, s->h_rec.data(), sizeof(rrtx_spline_record) * (size_t)s->n);
+  if (offsets) memcpy(offsets, s->h_off.data(), sizeof(int64_t) * ((size_t)s->n + 1));
+  if (n_courses) *n_courses = s->n;
+  if (n_points) *n_points = s->n_points;
+  if (kernel_ms) *kernel_ms = s->kernel_ms;
+  return RRTX_OK;
+}
+
+int rrtx_spline_get_points(rrtx_spline* s, double* x, double* y, double* yaw, double* k, double* t, int64_t cap) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_spline_get_points: the spline object is NULL");
+  if (!s->ran || !s->has_arrays) return fail(s, RRTX_E_STATE, "rrtx_spline_get_points: no completed run with arrays");
+  if (cap < s->n_points) return fail(s, RRTX_E_CAPACITY, "rrtx_spline_get_points: the buffers are too small");
+  if (s->n_points == 0) return RRTX_OK;
+  const size_t tot = (size_t)s->n_points;
+  HIPCHK(s, hipSetDevice(s->device));
+  double* dst[5] = {x, y, yaw, k, t};
+  for (int q = 0; q < 5; q++)
+    if (dst[q]) HIPCHK(s, hipMemcpy(dst[q], s->out.as<const double>() + q * tot, sizeof(double) * tot, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+int rrtx_spline_get_c(rrtx_spline* s, double* cx, double* cy, int64_t cap) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_spline_get_c: the spline object is NULL");
+  if (!s->ran) return fail(s, RRTX_E_STATE, "rrtx_spline_get_c: no completed run");
+  if (cap < s->n_wp) return fail(s, RRTX_E_CAPACITY, "rrtx_spline_get_c: the buffers are too small");
+  if (s->n_wp == 0) return RRTX_OK;
+  const size_t W = (size_t)s->n_wp;
+  HIPCHK(s, hipSetDevice(s->device));
+  if (cx) HIPCHK(s, hipMemcpy(cx, s->tab.as<const double>() + 3 * W, sizeof(double) * W, hipMemcpyDeviceToHost));
+  if (cy) HIPCHK(s, hipMemcpy(cy, s->tab.as<const double>() + 6 * W, sizeof(double) * W, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+int rrtx_spline_get_hits(rrtx_spline* s, int32_t* hit) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_spline_get_hits: the spline object is NULL");
+  if (!s->ran) return fail(s, RRTX_E_STATE, "rrtx_spline_get_hits: no completed run");
+  if (!s->has_hits) return fail(s, RRTX_E_STATE, "rrtx_spline_get_hits: the last run had no obstacle list");
+  if (s->n == 0) return RRTX_OK;
+  if (!hit) return fail(s, RRTX_E_INVALID, "rrtx_spline_get_hits: hit is NULL");
+  memcpy(hit, s->h_hit.data(), sizeof(int32_t) * (size_t)s->n);
+  return RRTX_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,127 @@
+// spline_batch.hip.h -- cubic-spline courses through batches of waypoint lists (gfx950): for every course what
+// calc_spline_course(x, y, ds) of 10_path_planning_00_cubic_spline_path.py :313-325 returns.  Scalar pieces: csrc/rpp_spline.h.
+//
+// Courses differ in waypoints and in points, so the work is two kernels with a CSR layout on each side:
+//   spline_fit_kernel   one lane per (course, axis): the knots s (np.hypot, left-to-right sum), c by the Thomas recurrence or
+//                       copied from the caller's, b and d; the axis-0 lane also writes the course's record -- status, point
+//                       count len(np.arange(0, s[-1], ds)), s[-1] -- and resets its hit word.  The recurrences are sequential
+//                       per course and axis; the two lanes of a course run the same trip counts.  Each axis keeps a knot
+//                       plane of its own, so no lane reads what another wrote.
+//   offsets             exclusive sum of the point counts into int64 offsets (host).
+//   spline_eval_kernel  one lane per output point: binary search of the point index in the offsets, t = k * ds,
+//                       bisect_right over the course's knots, then position, derivatives, yaw and curvature (spline_eval).
+//                       STORE writes x, y, yaw, k, t; CHECK tests the point against the obstacle list (rpp_collide.h) and
+//                       takes the lowest obstacle index any point of the course touches into hit[course].
+// The coefficient table is eight planes of W doubles (W = waypoints of the batch), waypoint CSR layout:
+//   0 s (axis x's), 1 s (axis y's copy), 2 bx, 3 cx, 4 dx, 5 by, 6 cy, 7 dy;  a = the waypoints themselves.
+#pragma once
+#include "rpp_collide.h"
+#include "rpp_spline.h"
+
+namespace rppsp {
+
+constexpr int TPB = 256;
+constexpr int MAX_WAYPOINTS = 4096;   // per course: bounds one lane's sequential sweep (include/rrtx.h)
+
+struct Record {   // rrtx_spline_record
+  int32_t status, reserved;
+  int64_t n_points;
+  double length;   // s[-1]
+};
+
+struct Args {
+  int64_t n;               // courses
+  int64_t W;               // waypoints in all = wp_off[n]
+  const int64_t* wp_off;   // [n + 1]
+  const double *x, *y;     // [W]
+  const double* ds;        // [n] or [1]
+  int32_t ds_per_course;
+  const double *cx, *cy;   // [W] the caller's c, or nullptr: the Thomas recurrence
+  double* tab;             // [8][W]
+  Record* rec;             // [n]
+  const int64_t* pt_off;   // [n + 1]
+  double* out;             // [5][pt_off[n]]: x, y, yaw, k, s
+  const double* obs;       // [n_obs] rows (ox, oy, thr), thr = (size + robot_radius) ** 2 from the host
+  int64_t n_obs;
+  int32_t* hit;            // [n]  fit: -1 (RRTX_SPLINE_OK) / -2 (no points); eval: the lowest obstacle index touched
+};
+
+__device__ inline double course_ds(const Args& a, int64_t c) { return a.ds[a.ds_per_course ? c : 0]; }
+
+__global__ __launch_bounds__(TPB) void spline_fit_kernel(Args a) {
+  const int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (idx >= 2 * a.n) return;
+  const int64_t c = idx >> 1;
+  const int axis = (int)(idx & 1);
+  const int64_t w0 = a.wp_off[c];
+  const int n = (int)(a.wp_off[c + 1] - w0);   // 2 <= n <= MAX_WAYPOINTS (host)
+  const double* wa = (axis ? a.y : a.x) + w0;
+  const double* cin = a.cx ? (axis ? a.cy : a.cx) + w0 : nullptr;
+  double* s = a.tab + (int64_t)axis * a.W + w0;
+  double* b = a.tab + (int64_t)(2 + 3 * axis) * a.W + w0;
+  int st = rpp::spline_fit_axis(a.x + w0, a.y + w0, wa, n, cin, s, b, b + a.W, b + 2 * a.W);
+  if (st != rpp::kSplineOk)   // no spline: the c a caller reads back is zero
+    for (int i = 0; i < n; i++) b[a.W + i] = 0.0;
+  if (axis) return;
+  Record r;
+  r.status = st;
+  r.reserved = 0;
+  r.length = s[n - 1];
+  r.n_points = st == rpp::kSplineOk ? rpp::spline_count(r.length, course_ds(a, c), &st) : 0;
+  r.status = st;
+  a.rec[c] = r;
+  if (a.hit) a.hit[c] = st == rpp::kSplineOk ? -1 : -2;
+}
+
+// With CHECK a lane past the last point does not leave: it stays as a copy of the last point (the same course, the same
+// answer), so every lane of a wave takes part in the shuffles below.  hit[] is read as unsigned for the minimum: -1
+// (free) is then the largest value, and -2 belongs to courses without points.
+template <bool STORE, bool CHECK>
+__global__ __launch_bounds__(TPB) void spline_eval_kernel(Args a) {
+  int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  const int64_t total = a.pt_off[a.n];
+  const bool live = idx < total;
+  if (!live) {
+    if (!CHECK) return;
+    idx = total - 1;   // the launch has total > 0
+  }
+  int64_t lo = 0, hi = a.n;   // the course c with pt_off[c] <= idx < pt_off[c + 1] (courses without points are skipped over)
+  while (hi - lo > 1) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (a.pt_off[mid] <= idx)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  const int64_t w0 = a.wp_off[lo];
+  const int n = (int)(a.wp_off[lo + 1] - w0);
+  const double t = (double)(idx - a.pt_off[lo]) * course_ds(a, lo);
+  const double* tb = a.tab + w0;
+  double p[4];
+  rpp::spline_eval(tb, a.x + w0, tb + 2 * a.W, tb + 3 * a.W, tb + 4 * a.W, a.y + w0, tb + 5 * a.W, tb + 6 * a.W, tb + 7 * a.W,
+                   n, t, p);
+  if (STORE && live) {
+    for (int q = 0; q < 4; q++) a.out[q * total + idx] = p[q];
+    a.out[4 * total + idx] = t;
+  }
+  if (CHECK) {
+    const uint32_t NONE = 0xffffffffu;
+    const uint32_t h = (uint32_t)rpp::first_hit(a.obs, a.n_obs, p[0], p[1]);
+    if (!__any(h != NONE)) return;
+    uint32_t* out = (uint32_t*)a.hit;
+    const int course = (int)lo;   // n <= 2^30
+    const int course0 = __shfl(course, 0);
+    if (__all(course == course0)) {   // the wave lies within one course: one atomic
+      uint32_t m = h;
+      for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)m, off);
+        m = o < m ? o : m;
+      }
+      if ((threadIdx.x & 63) == 0) atomicMin(out + course0, m);
+    } else if (h != NONE) {
+      atomicMin(out + course, h);
+    }
+  }
+}
+
+}  // namespace rppsp
