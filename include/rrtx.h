@@ -27,7 +27,9 @@ extern "C" {
 
 #define RRTX_ABI_VERSION 6   /* 6: rrtx_set_instance_obstacles (and RRTX_ALGO_LQR_RRT_STAR: a new algo value, no layout change; the rrtx_steer_* and
                                 rrtx_tracker_* entry points: new functions on objects of their own, no layout change; later additions of
-                                the same kind: rrtx_steer_set_obstacles, rrtx_steer_get_hits, rrtx_steer_solve_lqr, rrtx_steer_get_ends); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
+                                the same kind: rrtx_steer_set_obstacles, rrtx_steer_get_hits, rrtx_steer_solve_lqr, rrtx_steer_get_ends,
+                                rrtx_steer_solve_bezier, rrtx_steer_solve_bezier_cp, rrtx_steer_get_curvature, rrtx_steer_get_kmax,
+                                rrtx_steer_get_control_points); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
                                 rrtx_copy_results_device, per-instance yaw and informed rotation; 4: rrtx_plan_many,
                                 rrtx_selfcheck, rrtx_stats.main_shape / main_f32, rrtx_plan_begin / _step, rrtx_set_launch_bound,
                                 RRTX_ST_REF_HANGS, rrtx_rccl_* */
@@ -355,7 +357,8 @@ int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps);
 /* ---- batched Dubins / Reeds-Shepp curves between pose pairs, without a planner (csrc/steer_batch.hip.h) -------------------
  * Replaces plan_dubins_path (10_path_planning_00_dubins_path.py :109-197) and reeds_shepp_path_planning
  * (10_path_planning_00_reeds_shepp_path.py :506-515) called once per pair: every double is the reference's, bit for bit.
- * (The LQR steer, the reference's third, is served by the same object: rrtx_steer_solve_lqr below.)
+ * (The LQR steer, the reference's third, is served by the same object: rrtx_steer_solve_lqr below; so are Bezier curves,
+ * the fourth way of joining two poses: rrtx_steer_solve_bezier and rrtx_steer_solve_bezier_cp further below.)
  * The steer object is independent of rrtx_handle; it owns the device buffers of its solves and reuses them from call to
  * call (they grow, never shrink).  One host thread per object.  Call order: create, then solve, then the getters of that
  * solve, then solve again, as often as wanted; a getter before the first solve returns RRTX_E_STATE. */
@@ -396,7 +399,8 @@ int rrtx_steer_get_counts(rrtx_steer* s, int64_t* n_pairs, int64_t* n_points);
  * offsets[p] .. offsets[p + 1] - 1; a pair without a path owns none) -- RRTX_E_STATE after a lengths-only solve. */
 int rrtx_steer_get_summary(rrtx_steer* s, int32_t* status, double* length, int32_t* n_seg, double* seg_len, char* modes,
                            int64_t* offsets);
-/* The flat x, y, yaw arrays of the last solve (cap = doubles available in each; RRTX_E_CAPACITY when too small). */
+/* The flat x, y, yaw arrays of the last solve (cap = doubles available in each; RRTX_E_CAPACITY when too small); a Bezier
+ * solve has the curvature beside them: rrtx_steer_get_curvature. */
 int rrtx_steer_get_points(rrtx_steer* s, double* x, double* y, double* yaw, int64_t cap);
 /* HIP-event time of the kernels of the last solve (both stages, the obstacle check included; the prefix sum between them is
  * not kernel time) */
@@ -441,6 +445,41 @@ int rrtx_steer_solve_lqr(rrtx_steer* s, int32_t product, int64_t n, int64_t ng, 
 /* The end point of every pair of the last solve, rows (x, y); zeros where the pair has no path.  RRTX_E_STATE unless the
  * last solve was rrtx_steer_solve_lqr. */
 int rrtx_steer_get_ends(rrtx_steer* s, double* ends /* (n, 2) */);
+
+/* ---- the fourth way of joining two poses on the same object: Bezier curves (csrc/steer_batch.hip.h, csrc/rpp_bezier.h) -----
+ * Replaces calc_4points_bezier_path (10_path_planning_00_bazier_path.py :12-34) and calc_bezier_path :37-49 called once per
+ * curve, with bezier :64-73 on the derivative control points :76-94 and curvature :97-107 at every point.  Every double of
+ * the control points, the points, the derivatives and the curvature is the reference's, bit for bit (scipy.special.comb is
+ * the exact binomial coefficient; no scipy is involved).  Entry points of their own and no kind value, as for LQR.
+ * rrtx_steer_solve_bezier: poses are rows (x, y, yaw), product as for rrtx_steer_solve; the four control points are
+ * start, start + dist * (cos, sin)(start yaw), goal - dist * (cos, sin)(goal yaw), goal with dist = hypot(start - goal) /
+ * offset; offsets: one offset per pair, or NULL: offset0 for all.  A negative offset is legal, as in the reference.
+ * rrtx_steer_solve_bezier_cp: n curves of m control points each, rows (x, y): calc_bezier_path for any degree m - 1.
+ * Every curve has n_points points at the parameters np.linspace(0, 1, n_points) (the reference's 100).
+ * This library's own definitions (the script returns none of them): yaw = atan2(dy, dx) of the first derivative; length =
+ * Python's left-to-right sum of math.hypot over consecutive points; kmax = the largest |curvature| over the curve's points,
+ * NaN if any is NaN (coinciding control points: a zero first derivative gives numpy's nan or inf, not an error).
+ * Per-pair status is always RRTX_STEER_OK, so the return value is RRTX_OK.  The getters above serve the result: n_seg is m,
+ * seg_len and modes are zero-filled, offsets[p] = p * n_points, points with yaw, hits as for the other kinds.
+ * want_points == 0: length (and kmax) only; with an obstacle list set the points are computed and tested but not stored.
+ * want_curvature != 0: kmax per curve, and with want_points the curvature per point.
+ * RRTX_E_INVALID, before any HIP call (so also without a device): a NULL pointer, n < 0 (product: ng < 0), more than 2^30
+ * pairs, n_points outside 2..4096, n * n_points above 2^28, m outside 3..16 (degree 1 makes the reference's
+ * second-derivative call raise), a coordinate or yaw that is not finite or above 1e6 in magnitude, an offset that is not
+ * finite or below 1e-6 in magnitude. */
+int rrtx_steer_solve_bezier(rrtx_steer* s, int32_t product, int64_t n, int64_t ng, const double* starts /* (n, 3) */,
+                            const double* goals /* (n or ng, 3) */, double offset0, const double* offsets /* or NULL */,
+                            int32_t n_points, int32_t want_points, int32_t want_curvature);
+int rrtx_steer_solve_bezier_cp(rrtx_steer* s, int64_t n, int32_t m, const double* control_points /* (n, m, 2) */,
+                               int32_t n_points, int32_t want_points, int32_t want_curvature);
+/* The flat curvature array of the last solve, parallel to rrtx_steer_get_points (cap as there).  RRTX_E_STATE unless the
+ * last solve was a Bezier solve with want_points and want_curvature. */
+int rrtx_steer_get_curvature(rrtx_steer* s, double* k, int64_t cap);
+/* kmax of every curve of the last solve.  RRTX_E_STATE unless the last solve was a Bezier solve with want_curvature. */
+int rrtx_steer_get_kmax(rrtx_steer* s, double* kmax /* (n,) */);
+/* The control points of every curve of the last solve, as the device computed (or received) them, and their number per
+ * curve; either pointer may be NULL.  RRTX_E_STATE unless the last solve was a Bezier solve. */
+int rrtx_steer_get_control_points(rrtx_steer* s, double* control_points /* (n, m, 2) */, int32_t* m);
 
 /* ---- batched closed-loop tracking of courses given as data, without a planner (csrc/rrt_track.hip.h) ----------------------
  * For every course of a batch: what ClosedLoopRRTStar.check_tracking_path_is_feasible(path) (rrt_10:1526-1564) returns,

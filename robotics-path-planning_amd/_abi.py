@@ -33,12 +33,16 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_steer_create", "rrtx_steer_destroy", "rrtx_steer_last_error", "rrtx_steer_solve", "rrtx_steer_get_counts",
            "rrtx_steer_get_summary", "rrtx_steer_get_points", "rrtx_steer_get_kernel_ms", "rrtx_steer_set_obstacles",
            "rrtx_steer_get_hits", "rrtx_steer_solve_lqr", "rrtx_steer_get_ends",
+           "rrtx_steer_solve_bezier", "rrtx_steer_solve_bezier_cp", "rrtx_steer_get_curvature", "rrtx_steer_get_kmax",
+           "rrtx_steer_get_control_points",
            "rrtx_tracker_create", "rrtx_tracker_destroy", "rrtx_tracker_last_error", "rrtx_tracker_run",
            "rrtx_tracker_get_counts", "rrtx_tracker_get_records", "rrtx_tracker_get_arrays", "rrtx_tracker_get_kernel_ms",
            "rrtx_spline_create", "rrtx_spline_destroy", "rrtx_spline_last_error", "rrtx_spline_run", "rrtx_spline_get_records",
            "rrtx_spline_get_points", "rrtx_spline_get_c", "rrtx_spline_get_hits"]
 STEER_DUBINS, STEER_RS = 0, 1                                                      # include/rrtx.h: #define RRTX_STEER_*
 STEER_LQR = 2   # this binding's own name for "solved by rrtx_steer_solve_lqr": the C ABI has an entry point, not a kind value
+STEER_BEZIER = 3   # likewise: rrtx_steer_solve_bezier / rrtx_steer_solve_bezier_cp
+BEZIER_MIN_CP, BEZIER_MAX_CP, BEZIER_MAX_POINTS = 3, 16, 4096   # csrc/rpp_bezier.h
 STEER_OK, STEER_NO_PATH, STEER_RAISES_ZERODIV, STEER_RAISES_VALUE = 0, 1, 2, 3
 DUBINS_WORDS = ("LSL", "RSR", "LSR", "RSL", "RLR", "LRL")   # _PATH_TYPE_MAP order: the word indices of rrtx_steer_solve
 RS_COST_EUCLID, RS_COST_PATH = 0, 1     # include/rrtx.h: #define RRTX_RS_COST_*
@@ -187,6 +191,11 @@ def load():
     L.rrtx_steer_get_hits.argtypes = [vp, vp]
     L.rrtx_steer_solve_lqr.argtypes = [vp, i32, C.c_int64, C.c_int64, vp, vp, C.c_double, C.c_double, C.c_double, i32]
     L.rrtx_steer_get_ends.argtypes = [vp, vp]
+    L.rrtx_steer_solve_bezier.argtypes = [vp, i32, C.c_int64, C.c_int64, vp, vp, C.c_double, vp, i32, i32, i32]
+    L.rrtx_steer_solve_bezier_cp.argtypes = [vp, C.c_int64, i32, vp, i32, i32, i32]
+    L.rrtx_steer_get_curvature.argtypes = [vp, vp, C.c_int64]
+    L.rrtx_steer_get_kmax.argtypes = [vp, vp]
+    L.rrtx_steer_get_control_points.argtypes = [vp, vp, C.POINTER(i32)]
     L.rrtx_tracker_create.argtypes = [i32, C.POINTER(vp)]
     L.rrtx_tracker_destroy.argtypes = [vp]
     L.rrtx_tracker_destroy.restype = None
@@ -652,6 +661,58 @@ class Steer:
         return self._chk(self.L.rrtx_steer_solve_lqr(self._s, int(bool(product)), len(st), len(go), st.ctypes.data,
                                                      go.ctypes.data, float(step_size), float(max_time), float(goal_dist),
                                                      int(bool(points))), "rrtx_steer_solve_lqr")
+
+    def solve_bezier(self, starts, goals, offset, n_points=100, points=True, curvature=True, product=False):
+        """starts / goals: float64 arrays (n, 3) -- product: (ns, 3) and (ng, 3); offset: a float or one value per pair."""
+        st = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        go = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
+        n_pairs = len(st) * len(go) if product else len(st)
+        if not product and len(go) != len(st):
+            raise ValueError("solve_bezier: %d starts for %d goals" % (len(st), len(go)))
+        per_pair = np.ndim(offset) > 0
+        of = np.ascontiguousarray(offset, dtype=np.float64).reshape(-1)
+        if per_pair and len(of) != n_pairs:
+            raise ValueError("solve_bezier: %d offsets for %d pairs" % (len(of), n_pairs))
+        self._keep = (st, go, of)
+        return self._chk(self.L.rrtx_steer_solve_bezier(self._s, int(bool(product)), len(st), len(go), st.ctypes.data,
+                                                        go.ctypes.data, float(of[0]) if len(of) else 0.0,
+                                                        of.ctypes.data if per_pair else None, int(n_points),
+                                                        int(bool(points)), int(bool(curvature))), "rrtx_steer_solve_bezier")
+
+    def solve_bezier_cp(self, control_points, n_points=100, points=True, curvature=True):
+        """control_points: float64 array (n, m, 2), or (m, 2) for one curve."""
+        cp = np.ascontiguousarray(control_points, dtype=np.float64)
+        if cp.ndim == 2:
+            cp = cp[None]
+        if cp.ndim != 3 or cp.shape[2] != 2:
+            raise ValueError("solve_bezier_cp: control_points is (n, m, 2), not %r" % (cp.shape,))
+        self._keep = (cp,)
+        return self._chk(self.L.rrtx_steer_solve_bezier_cp(self._s, cp.shape[0], cp.shape[1], cp.ctypes.data, int(n_points),
+                                                           int(bool(points)), int(bool(curvature))),
+                         "rrtx_steer_solve_bezier_cp")
+
+    def curvature(self):
+        """The flat curvature per point of the last solve, a Bezier one with points and curvature."""
+        _, m = self.counts()
+        k = np.zeros(m)
+        self._chk(self.L.rrtx_steer_get_curvature(self._s, k.ctypes.data, m), "rrtx_steer_get_curvature")
+        return k
+
+    def kmax(self):
+        """(n,) largest |curvature| per curve of the last solve, a Bezier one with curvature."""
+        n, _ = self.counts()
+        km = np.zeros(n)
+        self._chk(self.L.rrtx_steer_get_kmax(self._s, km.ctypes.data), "rrtx_steer_get_kmax")
+        return km
+
+    def control_points(self):
+        """(n, m, 2) control points of the last solve, a Bezier one."""
+        n, _ = self.counts()
+        m = C.c_int32()
+        self._chk(self.L.rrtx_steer_get_control_points(self._s, None, C.byref(m)), "rrtx_steer_get_control_points")
+        cp = np.zeros((n, m.value, 2))
+        self._chk(self.L.rrtx_steer_get_control_points(self._s, cp.ctypes.data, None), "rrtx_steer_get_control_points")
+        return cp
 
     def ends(self):
         """(n, 2) end points of the last solve, an LQR one."""

@@ -1,13 +1,16 @@
-// rrtx_api_steer.inc -- rrtx_steer_*: batched Dubins / Reeds-Shepp curves between pose pairs and LQR rollouts between
-// point pairs (steer_batch.hip.h); included by rrtx_api.hip
+// rrtx_api_steer.inc -- rrtx_steer_*: batched Dubins / Reeds-Shepp / Bezier curves between pose pairs and LQR rollouts
+// between point pairs (steer_batch.hip.h); included by rrtx_api.hip
 struct rrtx_steer : DevObj {
   // device buffers, grown on demand and shared by the kinds: a solve writes every entry it later serves
   DevBuf starts, goals, curv, status, nseg, total, seglen, modes, npts, plan, offsets, px, py, pyaw, flag, obs, hit, ends;
+  DevBuf bez_w, bez_cp, pk, kmax;   // Bezier: weight table, control points (n, m, 2), curvature per point, max |curvature|
   // the obstacle list of rrtx_steer_set_obstacles: packed rows (ox, oy, thr); it goes to the device at the next solve
   std::vector<double> h_obs;
   bool obs_dirty = false;
   // the last solve
   bool solved = false, has_points = false, has_hits = false;
+  bool has_k = false;   // a Bezier solve with want_curvature
+  int bez_m = 0;        // a Bezier solve: control points per curve
   int kind = rppsb::KIND_DUBINS;
   int64_t n = 0, n_points = 0;
   double kernel_ms = 0.0;
@@ -140,6 +143,7 @@ static int steer_run(rrtx_steer* s, const SteerJob& j) {
   s->solved = false;
   s->has_points = false;
   s->has_hits = false;
+  s->has_k = false;
   s->kind = kind;
   s->n = np;
   s->n_points = 0;
@@ -343,6 +347,249 @@ int rrtx_steer_solve_lqr(rrtx_steer* s, int32_t product, int64_t n, int64_t ng, 
   }
 }
 
+// ---- Bezier ---------------------------------------------------------------------------------------------------------
+namespace {
+struct BezierJob {
+  const char* fn;
+  int32_t product;
+  int64_t n, ng;
+  const double *starts, *goals;   // rows (x, y, yaw); nullptr with control points
+  double offset0;
+  const double* offsets;          // one per pair, or nullptr: offset0
+  const double* cp;               // (n, m, 2), or nullptr with poses
+  int32_t m, n_points, want_points, want_curvature;
+};
+}  // namespace
+
+// The weight table and stage 1, then stage 2 over offsets[p] = p * n_points
+static int steer_run_bezier(rrtx_steer* s, const BezierJob& j) {
+  const char* fn = j.fn;
+  const int64_t n_goals = j.product ? j.ng : j.n, np = j.product ? j.n * j.ng : j.n;
+  const int32_t m = j.m, n_points = j.n_points;
+  if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  const int64_t n_obs = (int64_t)(s->h_obs.size() / 3);
+  const bool want_points = j.want_points != 0, want_k = j.want_curvature != 0, stage2 = want_points || n_obs > 0;
+
+  s->solved = false;
+  s->has_points = false;
+  s->has_hits = false;
+  s->has_k = false;
+  s->kind = rppsb::KIND_BEZIER;
+  s->bez_m = m;
+  s->n = np;
+  s->n_points = 0;
+  s->kernel_ms = 0.0;
+  s->h_offsets.clear();
+  if (np == 0) {
+    s->has_points = want_points;
+    s->has_hits = n_obs > 0;
+    s->has_k = want_k;
+    s->h_offsets.assign(1, 0);
+    s->solved = true;
+    return RRTX_OK;
+  }
+  HIPCHK(s, hipSetDevice(s->device));
+  int rc;
+  const size_t N = (size_t)np, row = (size_t)rpp::bezier_row_len(m);
+  const int64_t tot = np * (int64_t)n_points;   // <= 2^28
+  if ((rc = s->reserve(s->status, sizeof(int32_t) * N))) return rc;
+  if ((rc = s->reserve(s->nseg, sizeof(int32_t) * N))) return rc;
+  if ((rc = s->reserve(s->total, sizeof(double) * N))) return rc;
+  if ((rc = s->reserve(s->npts, sizeof(int32_t) * N))) return rc;
+  if ((rc = s->reserve(s->bez_cp, sizeof(double) * 2 * (size_t)m * N))) return rc;
+  if ((rc = s->reserve(s->bez_w, sizeof(double) * row * (size_t)n_points))) return rc;
+  if (want_k && (rc = s->reserve(s->kmax, sizeof(double) * N))) return rc;
+  if (n_obs > 0) {
+    if ((rc = s->reserve(s->hit, sizeof(int32_t) * N))) return rc;
+    if (s->obs_dirty) {
+      if ((rc = s->upload(s->obs, s->h_obs.data(), sizeof(double) * s->h_obs.size()))) return rc;
+      s->obs_dirty = false;
+    }
+  }
+  if (j.cp) {
+    if ((rc = s->upload(s->bez_cp, j.cp, sizeof(double) * 2 * (size_t)m * N))) return rc;
+  } else {
+    if ((rc = s->upload(s->starts, j.starts, sizeof(double) * 3 * (size_t)j.n))) return rc;
+    if ((rc = s->upload(s->goals, j.goals, sizeof(double) * 3 * (size_t)n_goals))) return rc;
+    if (j.offsets && (rc = s->upload(s->curv, j.offsets, sizeof(double) * N))) return rc;
+  }
+
+  rppsb::Args a;
+  memset(&a, 0, sizeof(a));
+  a.starts = s->starts.as<const double>();
+  a.goals = s->goals.as<const double>();
+  a.curv = j.offsets ? s->curv.as<const double>() : nullptr;
+  a.curv0 = j.offset0;
+  a.n = np;
+  a.ng = j.product ? j.ng : 1;
+  a.product = j.product ? 1 : 0;
+  a.want_points = stage2 ? 1 : 0;
+  a.status = s->status.as<int32_t>();
+  a.nseg = s->nseg.as<int32_t>();
+  a.total = s->total.as<double>();
+  a.npts = s->npts.as<int32_t>();
+  a.bez_w = s->bez_w.as<const double>();
+  a.bez_cp = s->bez_cp.as<double>();
+  a.kmax = want_k ? s->kmax.as<double>() : nullptr;
+  a.bez_m = m;
+  a.bez_np = n_points;
+  a.bez_given = j.cp ? 1 : 0;
+  if (n_obs > 0) {
+    a.obs = s->obs.as<const double>();
+    a.n_obs = n_obs;
+    a.hit = s->hit.as<int32_t>();
+  }
+
+  const unsigned blk = (unsigned)((np + rppsb::TPB - 1) / rppsb::TPB);
+  const unsigned wblk = (unsigned)(((size_t)n_points * row + rppsb::TPB - 1) / rppsb::TPB);
+  float ms = 0.f;
+  rc = s->timed(&ms, [&] {
+    hipLaunchKernelGGL(rppsb::bezier_weights_kernel, dim3(wblk), dim3(rppsb::TPB), 0, s->stream, s->bez_w.as<double>(),
+                       n_points, m);
+    if (m == 4)
+      hipLaunchKernelGGL(rppsb::steer_bezier_solve<4>, dim3(blk), dim3(rppsb::TPB), 0, s->stream, a);
+    else
+      hipLaunchKernelGGL(rppsb::steer_bezier_solve<0>, dim3(blk), dim3(rppsb::TPB), 0, s->stream, a);
+  });
+  if (rc) return rc;
+  s->kernel_ms = ms;
+
+  if (stage2) {
+    s->h_offsets.resize(N + 1);
+    for (size_t i = 0; i <= N; i++) s->h_offsets[i] = (int64_t)i * n_points;   // every curve has n_points points
+    s->n_points = want_points ? tot : 0;
+    if (want_points) {
+      if ((rc = s->reserve(s->px, sizeof(double) * (size_t)tot))) return rc;
+      if ((rc = s->reserve(s->py, sizeof(double) * (size_t)tot))) return rc;
+      if ((rc = s->reserve(s->pyaw, sizeof(double) * (size_t)tot))) return rc;
+      if (want_k && (rc = s->reserve(s->pk, sizeof(double) * (size_t)tot))) return rc;
+      a.px = s->px.as<double>();
+      a.py = s->py.as<double>();
+      a.pyaw = s->pyaw.as<double>();
+      a.pk = want_k ? s->pk.as<double>() : nullptr;
+    }
+    if ((rc = s->upload(s->offsets, s->h_offsets.data(), sizeof(int64_t) * (N + 1)))) return rc;
+    a.offsets = s->offsets.as<const int64_t>();
+    const unsigned fblk = (unsigned)((tot + rppsb::TPB - 1) / rppsb::TPB);
+    rc = s->timed(&ms, [&] { steer_launch_fill<rppsb::KIND_BEZIER>(want_points, n_obs > 0, fblk, s->stream, a); });
+    if (rc) return rc;
+    s->kernel_ms += ms;
+    if (!want_points) s->h_offsets.clear();
+    s->has_points = want_points;
+  }
+  s->has_hits = n_obs > 0;
+  s->has_k = want_k;
+  s->solved = true;
+  return RRTX_OK;
+}
+
+// what both Bezier entry points check of their shared arguments; nullptr: fine
+static const char* bezier_shape_bad(int64_t np, int32_t n_points) {
+  if (n_points < 2 || n_points > rpp::kBezierMaxPoints) return "n_points outside 2..4096";
+  if (np > (1LL << 28) / n_points) return "more than 2^28 points (n * n_points)";
+  return nullptr;
+}
+
+static int steer_solve_bezier(rrtx_steer* s, int32_t product, int64_t n, int64_t ng, const double* starts,
+                              const double* goals, double offset0, const double* offsets, int32_t n_points,
+                              int32_t want_points, int32_t want_curvature) {
+  const char* fn = "rrtx_steer_solve_bezier: ";
+  auto bad = [&](const char* m) { return fail(s, RRTX_E_INVALID, std::string(fn) + m); };
+  if (!s) return bad("the steer object is NULL");
+  if (!starts || !goals) return bad("starts or goals is NULL");
+  if (n < 0 || (product && ng < 0)) return bad("a negative batch size");
+  const int64_t n_goals = product ? ng : n;
+  if (n > (1LL << 30) || n_goals > (1LL << 30) || (product && n && ng && n > (1LL << 30) / ng))
+    return bad("more than 2^30 pairs");
+  const int64_t np = product ? n * ng : n;
+  if (const char* m = bezier_shape_bad(np, n_points)) return bad(m);
+  for (int side = 0; side < 2; side++) {
+    const double* q = side ? goals : starts;
+    const int64_t vals = 3 * (side ? n_goals : n);
+    for (int64_t i = 0; i < vals; i++)
+      if (!(fabs(q[i]) <= 1e6)) return bad("a pose component is not finite or exceeds 1e6 in magnitude");
+  }
+  // dist = hypot / offset: a negative offset is legal in the reference (the control points move the other way)
+  const int64_t no = offsets ? np : 1;
+  for (int64_t i = 0; i < no; i++) {
+    const double o = offsets ? offsets[i] : offset0;
+    if (!std::isfinite(o) || fabs(o) < 1e-6) return bad("an offset is not finite or smaller than 1e-6 in magnitude");
+  }
+  const BezierJob job = {fn, product, n, ng, starts, goals, offset0, offsets, nullptr, 4, n_points, want_points, want_curvature};
+  return steer_run_bezier(s, job);
+}
+
+static int steer_solve_bezier_cp(rrtx_steer* s, int64_t n, int32_t m, const double* control_points, int32_t n_points,
+                                 int32_t want_points, int32_t want_curvature) {
+  const char* fn = "rrtx_steer_solve_bezier_cp: ";
+  auto bad = [&](const char* msg) { return fail(s, RRTX_E_INVALID, std::string(fn) + msg); };
+  if (!s) return bad("the steer object is NULL");
+  if (!control_points) return bad("control_points is NULL");
+  if (n < 0) return bad("a negative batch size");
+  if (n > (1LL << 30)) return bad("more than 2^30 curves");
+  if (m < rpp::kBezierMinCp || m > rpp::kBezierMaxCp) return bad("m (control points per curve) outside 3..16");
+  if (const char* msg = bezier_shape_bad(n, n_points)) return bad(msg);
+  for (int64_t i = 0; i < 2 * (int64_t)m * n; i++)
+    if (!(fabs(control_points[i]) <= 1e6)) return bad("a coordinate is not finite or exceeds 1e6 in magnitude");
+  const BezierJob job = {fn, 0, n, 0, nullptr, nullptr, 0.0, nullptr, control_points, m, n_points, want_points, want_curvature};
+  return steer_run_bezier(s, job);
+}
+
+int rrtx_steer_solve_bezier(rrtx_steer* s, int32_t product, int64_t n, int64_t ng, const double* starts, const double* goals,
+                            double offset0, const double* offsets, int32_t n_points, int32_t want_points,
+                            int32_t want_curvature) {
+  try {
+    return steer_solve_bezier(s, product, n, ng, starts, goals, offset0, offsets, n_points, want_points, want_curvature);
+  } catch (const std::exception& e) {
+    if (s) s->solved = false;
+    return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve_bezier: ") + e.what());
+  }
+}
+
+int rrtx_steer_solve_bezier_cp(rrtx_steer* s, int64_t n, int32_t m, const double* control_points, int32_t n_points,
+                               int32_t want_points, int32_t want_curvature) {
+  try {
+    return steer_solve_bezier_cp(s, n, m, control_points, n_points, want_points, want_curvature);
+  } catch (const std::exception& e) {
+    if (s) s->solved = false;
+    return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve_bezier_cp: ") + e.what());
+  }
+}
+
+int rrtx_steer_get_curvature(rrtx_steer* s, double* k, int64_t cap) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_curvature: the steer object is NULL");
+  if (!s->solved || s->kind != rppsb::KIND_BEZIER || !s->has_k || !s->has_points)
+    return fail(s, RRTX_E_STATE, "rrtx_steer_get_curvature: no completed Bezier solve with points and curvature");
+  if (cap < s->n_points) return fail(s, RRTX_E_CAPACITY, "rrtx_steer_get_curvature: the buffer is too small");
+  if (s->n_points == 0) return RRTX_OK;
+  if (!k) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_curvature: k is NULL");
+  HIPCHK(s, hipSetDevice(s->device));
+  HIPCHK(s, hipMemcpy(k, s->pk.p, sizeof(double) * (size_t)s->n_points, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+int rrtx_steer_get_kmax(rrtx_steer* s, double* kmax) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_kmax: the steer object is NULL");
+  if (!s->solved || s->kind != rppsb::KIND_BEZIER || !s->has_k)
+    return fail(s, RRTX_E_STATE, "rrtx_steer_get_kmax: no completed Bezier solve with curvature");
+  if (s->n == 0) return RRTX_OK;
+  if (!kmax) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_kmax: kmax is NULL");
+  HIPCHK(s, hipSetDevice(s->device));
+  HIPCHK(s, hipMemcpy(kmax, s->kmax.p, sizeof(double) * (size_t)s->n, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+int rrtx_steer_get_control_points(rrtx_steer* s, double* control_points, int32_t* m) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_control_points: the steer object is NULL");
+  if (!s->solved || s->kind != rppsb::KIND_BEZIER)
+    return fail(s, RRTX_E_STATE, "rrtx_steer_get_control_points: no completed Bezier solve");
+  if (m) *m = s->bez_m;
+  if (s->n == 0 || !control_points) return RRTX_OK;
+  HIPCHK(s, hipSetDevice(s->device));
+  HIPCHK(s, hipMemcpy(control_points, s->bez_cp.p, sizeof(double) * 2 * (size_t)s->bez_m * (size_t)s->n, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
 int rrtx_steer_get_ends(rrtx_steer* s, double* ends) {
   if (!s) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_ends: the steer object is NULL");
   if (!s->solved) return fail(s, RRTX_E_STATE, "rrtx_steer_get_ends: no completed solve");
@@ -375,7 +622,7 @@ int rrtx_steer_get_summary(rrtx_steer* s, int32_t* status, double* length, int32
   if (status) HIPCHK(s, hipMemcpy(status, s->status.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
   if (length) HIPCHK(s, hipMemcpy(length, s->total.p, sizeof(double) * N, hipMemcpyDeviceToHost));
   if (n_seg) HIPCHK(s, hipMemcpy(n_seg, s->nseg.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
-  if (s->kind == rppsb::KIND_LQR) {   // a rollout has neither: zero-filled
+  if (s->kind == rppsb::KIND_LQR || s->kind == rppsb::KIND_BEZIER) {   // a rollout or a Bezier curve has neither: zero-filled
     if (seg_len) memset(seg_len, 0, sizeof(double) * 5 * N);
     if (modes) memset(modes, 0, 8 * N);
     return RRTX_OK;

@@ -24,12 +24,20 @@
 //                                dubins_point / rs_point / lqr_point, which are random-access by point index (lqr_point
 //                                re-runs the recurrence to the point's segment: <= 10 steps at the reference's
 //                                settings, 19 with goal_dist = 0).  STORE writes the
-//                                point; CHECK tests it against the obstacle list (rpp_collide.h) and takes the lowest
+//                                point (a Bezier point with its curvature when that is wanted: bezier_eval on row k of
+//                                the weight table, which neighbouring lanes read at neighbouring rows); CHECK tests it against the obstacle list (rpp_collide.h) and takes the lowest
 //                                obstacle index any point of the pair touches into hit[pair].
+//            steer_bezier_solve  one lane per pair, after bezier_weights_kernel has filled the solve's weight table
+//                                (rpp_bezier.h): the control points from the poses (or as given), written as the pair's
+//                                stage-2 record; then the walk over the n_points points -- the same trip count in every
+//                                lane, the table row at a wave-uniform address -- for the length and, when curvature is
+//                                wanted, the largest |curvature|.  <4> keeps the control points in registers; <0> (any
+//                                other number of given control points) reads them back from the record.
 // Lengths-only is stage 1 alone (no plan, no course, no offsets) -- unless an obstacle list is set: then stage 1 runs as
 // for points and stage 2 runs with CHECK alone, so no point is ever written.
 // Product mode: pair p of ns x ng is (start p / ng, goal p % ng), formed here; the host never builds the product.
 #pragma once
+#include "rpp_bezier.h"
 #include "rpp_collide.h"
 #include "rpp_lqr.h"
 #include "rpp_rs.h"
@@ -38,6 +46,7 @@ namespace rppsb {
 
 constexpr int KIND_DUBINS = 0, KIND_RS = 1;   // include/rrtx.h RRTX_STEER_DUBINS / RRTX_STEER_RS
 constexpr int KIND_LQR = 2;                   // not a value of the ABI: rrtx_steer_solve_lqr is this kind's entry point
+constexpr int KIND_BEZIER = 3;                // neither: rrtx_steer_solve_bezier / rrtx_steer_solve_bezier_cp
 constexpr int ST_OK = 0, ST_NO_PATH = 1, ST_RAISES_ZERODIV = 2, ST_RAISES_VALUE = 3;   // include/rrtx.h RRTX_STEER_*
 constexpr int TPB = 256;            // steer_dubins_solve, steer_rs_course, steer_fill
 constexpr int RS_TPB = 64;          // steer_rs_solve: one wave
@@ -72,6 +81,13 @@ struct Args {
   const double* obs;      // [n_obs] rows (ox, oy, thr), thr = (size + robot_radius) ** 2 from the host
   int64_t n_obs;
   int32_t* hit;           // [n]  stage 1: -1 (ST_OK) / -2 (no curve); stage 2: the lowest obstacle index touched
+  // Bezier (curv / curv0 hold the offset per pair / of all pairs)
+  const double* bez_w;    // [bez_np][3 bez_m - 3] the weight table of this solve
+  double* bez_cp;         // [n][bez_m][2] control points: stage 1 writes them, or finds them there (bez_given)
+  double* pk;             // [offsets[n]] curvature per point, or nullptr
+  double* kmax;           // [n] max |curvature| over the curve's points, or nullptr
+  int32_t bez_m, bez_np;  // control points per curve, points per curve
+  int32_t bez_given;      // the control points came from the host
 };
 
 __device__ inline void pair_poses(const Args& a, int64_t p, double* s, double* g) {
@@ -294,6 +310,48 @@ __global__ __launch_bounds__(TPB) void steer_lqr_solve(Args a) {
   if (a.hit) a.hit[p] = -1;
 }
 
+// ---- Bezier, the weight table and stage 1 ----------------------------------------------------------------------------
+// One entry per thread, with the pow replica, so that no curve ever calls pow for a weight and the table does not depend on
+// the host's libm.  At the reference's sizes (100 points, 4 control points) it is 900 doubles; it stays in global memory:
+// stage 1 reads a row at a wave-uniform address through the constant address space (scalar loads), stage 2 reads 9 to 45
+// doubles of a table the L2 holds whole (<= 1.4 MB at 4096 points x 16 control points, 7.2 KB at the reference's).
+__global__ __launch_bounds__(TPB) void bezier_weights_kernel(double* w, int32_t n_points, int32_t m) {
+  const int row = rpp::bezier_row_len(m);
+  const int idx = blockIdx.x * TPB + threadIdx.x;   // n_points * row <= 4096 * 45
+  if (idx >= n_points * row) return;
+  w[idx] = rpp::bezier_table_entry(n_points, m, idx / row, idx % row);
+}
+
+template <int M>
+__global__ __launch_bounds__(TPB) void steer_bezier_solve(Args a) {
+  const int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (p >= a.n) return;
+  const int m = M ? M : a.bez_m;
+  double* rec = a.bez_cp + 2 * (int64_t)m * p;
+  const rpp::BezierRow table = (rpp::BezierRow)a.bez_w;
+  double len, km;
+  if (M == 4) {
+    double P[8];
+    if (a.bez_given) {
+      for (int i = 0; i < 8; i++) P[i] = rec[i];
+    } else {
+      double s[3], g[3];
+      pair_poses(a, p, s, g);
+      rpp::bezier_cp4(s[0], s[1], s[2], g[0], g[1], g[2], pair_curv(a, p), P);
+      for (int i = 0; i < 8; i++) rec[i] = P[i];
+    }
+    rpp::bezier_walk<4>(P, 4, table, a.bez_np, a.kmax != nullptr, &len, &km);
+  } else {
+    rpp::bezier_walk<0>(rec, m, table, a.bez_np, a.kmax != nullptr, &len, &km);
+  }
+  a.status[p] = ST_OK;
+  a.nseg[p] = m;
+  a.total[p] = len;
+  a.npts[p] = a.bez_np;
+  if (a.kmax) a.kmax[p] = km;
+  if (a.hit) a.hit[p] = -1;
+}
+
 // ---- stage 2 -------------------------------------------------------------------------------------------------------
 // <KIND, true, false> is the fill kernel alone.  With CHECK a lane past the last point does not leave: it stays as a copy
 // of the last point (the same pair, the same answer), so every lane of a wave takes part in the shuffles below.
@@ -316,20 +374,32 @@ __global__ __launch_bounds__(TPB) void steer_fill(Args a) {
       hi = mid;
   }
   const int k = (int)(idx - a.offsets[lo]);
-  double x, y, yaw = 0.0;
+  double x, y, yaw = 0.0, kk = 0.0;
   if (KIND == KIND_DUBINS) {
     rpp::dubins_point(a.dplan[lo], k, pair_curv(a, lo), &x, &y, &yaw);
   } else if (KIND == KIND_RS) {
     rpp::rs_point(a.course[lo], k, &x, &y, &yaw);
-  } else {
+  } else if (KIND == KIND_LQR) {
     double s[2], g[2];
     pair_xy(a, lo, s, g);
     rpp::lqr_point(s[0], s[1], g[0], g[1], a.step, a.nt, k, &x, &y);
+  } else {
+    const int m = a.bez_m;
+    double o[6];
+    rpp::bezier_eval<0>(a.bez_cp + 2 * (int64_t)m * lo, m, a.bez_w + (int64_t)k * rpp::bezier_row_len(m),
+                        STORE ? (a.pk ? 2 : 1) : 0, o);
+    x = o[0];
+    y = o[1];
+    if (STORE) {
+      yaw = rpp_glibc_atan2(o[3], o[2]);
+      if (a.pk) kk = rpp::bezier_curvature(o[2], o[3], o[4], o[5]);
+    }
   }
   if (STORE && live) {
     a.px[idx] = x;
     a.py[idx] = y;
     if (KIND != KIND_LQR) a.pyaw[idx] = yaw;   // an LQR course has no yaw
+    if (KIND == KIND_BEZIER && a.pk) a.pk[idx] = kk;
   }
   if (CHECK) {
     // The obstacle index is the same in every lane still in first_hit's loop, and a lane leaves the loop at its first

@@ -20,6 +20,17 @@ CPU fallback: without a device the call raises RrtxError.
     rx, ry = bs.plan(starts, goals, resample=False).path(i)    # LQRPlanner.lqr_planning's rollout itself
     cost = bs.plan(starts, goals, points=False, product=True, obstacle_list=circles).length_matrix(free_only=True)
 
+    bs = BatchSteer("bezier")                       # rows (x, y, yaw); no curvature argument: a Bezier curve has no bound
+    res = bs.plan(starts, goals, offset=3.0)        # res.path(i) = calc_4points_bezier_path's (path, control_points)
+    x, y, yaw, k = res.course(i)                    # res.kmax[i] = max |k|; BatchTrack().run(res) drives the courses
+    cost = bs.plan(starts, goals, points=False, product=True, obstacle_list=circles).length_matrix(
+        free_only=True, max_curvature=0.5)          # +inf where the curve touches a circle or bends harder than 0.5
+    res = bs.plan_control_points(cps, n_points=50)  # calc_bezier_path for (n, m, 2) control points, 3 <= m <= 16
+
+"bezier" is 10_path_planning_00_bazier_path.py: control points, points, bezier() on the derivative control points and
+curvature() are the script's doubles, bit for bit.  yaw (atan2 of the first derivative), length (the left-to-right sum of
+math.hypot over consecutive points) and kmax are this package's own definitions: the script returns none of them.
+
 "lqr" is LQRPlanner.lqr_planning (10_path_planning_00_lqr_path.py :24-66 = rrt_09 :944-986) for the reference's model
 (DT = 0.1, Q = R = I), with rrt_09's sample_path :1157-1172, edge cost (steer :1189, calc_new_cost :1432-1442) and
 check_collision :1292-1305 around it; max_time and goal_dist are the planner's MAX_TIME and GOAL_DIST.
@@ -30,7 +41,8 @@ import numpy as np
 
 from . import _abi
 
-KINDS = {"dubins": _abi.STEER_DUBINS, "rs": _abi.STEER_RS, "reeds_shepp": _abi.STEER_RS, "lqr": _abi.STEER_LQR}
+KINDS = {"dubins": _abi.STEER_DUBINS, "rs": _abi.STEER_RS, "reeds_shepp": _abi.STEER_RS, "lqr": _abi.STEER_LQR,
+         "bezier": _abi.STEER_BEZIER}
 DEFAULT_STEP = {_abi.STEER_DUBINS: 0.1, _abi.STEER_RS: 0.2, _abi.STEER_LQR: 0.2}   # LQR: rrt_09's step_size (:1063)
 
 
@@ -58,18 +70,27 @@ class SteerResult:
     An "lqr" batch: n_seg is the number of rollout points len(rx), end (n, 2) the last point, length the sum of
     math.hypot over consecutive points, left to right -- of the resampled points (rrt_09's edge cost), or with
     resample=False of the rollout points (the lqr_path script returns no length: this one is this package's definition);
-    yaw is None, modes and lengths are empty."""
+    yaw is None, modes and lengths are empty.
+    A "bezier" batch: every status is STEER_OK and every curve has n_points points; n_seg is the number of control points,
+    control_points (n, m, 2) what the device computed from the poses (or was given); k the flat curvature per point and
+    kmax (n,) the largest |k| per curve (NaN if any k is NaN) when curvature was asked for, else None.  yaw, length and
+    kmax are this package's definitions (the bazier_path script returns none of them): yaw = atan2(dy, dx) of the first
+    derivative, length the left-to-right sum of math.hypot over consecutive points.  modes and lengths are empty."""
 
     def __init__(self, kind, status, length, nseg, seglen, modes, offsets, xyz, shape, rc, kernel_ms, hit=None, end=None,
-                 resampled=True):
+                 resampled=True, k=None, kmax=None, control_points=None):
         self.kind = kind
         self.status = status
         self.length = length
         self.n_seg = nseg
         self.seg_len = seglen
-        self.modes = [m.decode() for m in modes]
-        nl = np.zeros_like(nseg) if kind == _abi.STEER_LQR else nseg   # a rollout has no segment lengths
-        self.lengths = [seglen[i, :nl[i]].copy() for i in range(len(nseg))]
+        if kind == _abi.STEER_BEZIER:   # neither modes nor segment lengths: no loop over what can be 2^20 curves
+            self.modes = [""] * len(nseg)
+            self.lengths = [seglen[:0, 0]] * len(nseg)
+        else:
+            self.modes = [m.decode() for m in modes]
+            nl = np.zeros_like(nseg) if kind == _abi.STEER_LQR else nseg   # a rollout has no segment lengths
+            self.lengths = [seglen[i, :nl[i]].copy() for i in range(len(nseg))]
         self.offsets = offsets
         self.x, self.y, self.yaw = xyz if xyz is not None else (None, None, None)
         self.shape = shape          # (ns, ng) in product mode, else None
@@ -78,6 +99,9 @@ class SteerResult:
         self.hit = hit
         self.end = end              # "lqr": (n, 2); else None
         self.resampled = resampled  # "lqr": path(i) is sample_path's triple, not the rollout
+        self.k = k                  # "bezier": flat curvature per point, or None
+        self.kmax = kmax            # "bezier": (n,), or None
+        self.control_points = control_points   # "bezier": (n, m, 2)
 
     @property
     def free(self):
@@ -111,10 +135,16 @@ class SteerResult:
         """What the reference function returns for pair i: (x, y, yaw, modes, lengths) -- numpy arrays and lists for
         Dubins, lists for Reeds-Shepp, (None,) * 5 where Reeds-Shepp finds no path; raises where the reference raises.
         "lqr": sample_path's (px, py, course_lens) as lists, or with resample=False lqr_planning's (rx, ry); empty lists
-        where the rollout never arrives."""
+        where the rollout never arrives.
+        "bezier": calc_4points_bezier_path's (path (n_points, 2) array, control_points (m, 2) array)."""
         st = int(self.status[i])
         if self.kind == _abi.STEER_LQR:
             return self._lqr_path(i, st)
+        if self.kind == _abi.STEER_BEZIER:
+            if self.x is None:
+                raise _abi.RrtxError("path(): this batch was solved with points=False")
+            a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+            return np.stack([self.x[a:b], self.y[a:b]], axis=1), self.control_points[i].copy()
         if st == _abi.STEER_RAISES_ZERODIV:
             raise ZeroDivisionError("float division by zero")
         if st == _abi.STEER_RAISES_VALUE:
@@ -144,22 +174,38 @@ class SteerResult:
         dx, dy = np.diff(px), np.diff(py)   # :1167-1170, on the host as the reference does it
         return px, py, [math.hypot(idx, idy) for (idx, idy) in zip(dx, dy)]
 
-    def length_matrix(self, free_only=False):
-        """The (ns, ng) lengths of a product-mode batch; free_only: +inf where the pair is not free."""
+    def course(self, i):
+        """"bezier": (x, y, yaw, k) arrays of curve i; k is None when curvature was not asked for."""
+        if self.kind != _abi.STEER_BEZIER:
+            raise _abi.RrtxError("course(): a Bezier batch has courses; use path(i)")
+        if self.x is None:
+            raise _abi.RrtxError("course(): this batch was solved with points=False")
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        return (self.x[a:b].copy(), self.y[a:b].copy(), self.yaw[a:b].copy(),
+                None if self.k is None else self.k[a:b].copy())
+
+    def length_matrix(self, free_only=False, max_curvature=None):
+        """The (ns, ng) lengths of a product-mode batch; free_only: +inf where the pair is not free; max_curvature
+        ("bezier"): +inf where kmax > max_curvature or kmax is NaN."""
         if self.shape is None:
             raise _abi.RrtxError("length_matrix(): this batch was not solved in product mode")
-        if not free_only:
-            return self.length.reshape(self.shape)
-        return np.where(self.free, self.length, np.inf).reshape(self.shape)
+        cost = self.length
+        if free_only:
+            cost = np.where(self.free, cost, np.inf)
+        if max_curvature is not None:
+            if self.kmax is None:
+                raise _abi.RrtxError("length_matrix(): max_curvature needs a Bezier batch planned with curvature=True")
+            cost = np.where(self.kmax <= max_curvature, cost, np.inf)   # a NaN compares False
+        return cost.reshape(self.shape)
 
 
 class BatchSteer:
-    """Shortest Dubins ("dubins") or Reeds-Shepp ("rs") curves for batches of pose pairs, or LQR rollouts ("lqr") for
-    batches of point pairs; device buffers are kept between calls of plan()."""
+    """Shortest Dubins ("dubins") or Reeds-Shepp ("rs") curves or Bezier curves ("bezier") for batches of pose pairs, or
+    LQR rollouts ("lqr") for batches of point pairs; device buffers are kept between calls of plan()."""
 
     def __init__(self, kind, device=0):
         if kind not in KINDS:
-            raise ValueError("BatchSteer: kind is 'dubins', 'rs' or 'lqr', not %r" % (kind,))
+            raise ValueError("BatchSteer: kind is 'dubins', 'rs', 'lqr' or 'bezier', not %r" % (kind,))
         self.kind = KINDS[kind]
         self._steer = _abi.Steer(device)
 
@@ -174,14 +220,30 @@ class BatchSteer:
         return False
 
     def plan(self, starts, goals, curvature=None, step_size=None, selected_types=None, points=True, product=False,
-             obstacle_list=None, robot_radius=0.0, resample=True, max_time=100.0, goal_dist=0.1):
+             obstacle_list=None, robot_radius=0.0, resample=True, max_time=100.0, goal_dist=0.1, offset=3.0, n_points=100):
         """starts, goals: (n, 3) rows of (x, y, yaw) -- with product=True (ns, 3) and (ng, 3), pair p = (p // ng, p % ng).
         curvature: a float or one per pair.  step_size: Reeds-Shepp any value > 0 (default 0.2); Dubins 0.1 only.
         selected_types (Dubins): word names in the order to try them.  obstacle_list: rows (x, y, size) every curve is
         tested against with robot_radius (result.hit / .free); None or empty: no check.
         "lqr": rows are (x, y); curvature and selected_types must stay None; step_size >= 1e-3 (default rrt_09's 0.2) is
         sample_path's step, resample=False gives the rollout itself; max_time <= 100.0 and goal_dist are the planner's
-        MAX_TIME and GOAL_DIST (these three keywords belong to this kind alone)."""
+        MAX_TIME and GOAL_DIST (these three keywords belong to this kind alone).
+        "bezier": plan(starts, goals, offset=3.0, n_points=100, curvature=True, points=True, product=False,
+        obstacle_list=None, robot_radius=0.0) -- offset is calc_4points_bezier_path's, a float or one per pair; n_points
+        (2..4096) the points per curve; curvature is a flag here (default True): k per point and kmax per curve."""
+        if self.kind == _abi.STEER_BEZIER:
+            if step_size is not None or selected_types is not None or resample is not True or max_time != 100.0 \
+                    or goal_dist != 0.1:
+                raise ValueError("BatchSteer('bezier').plan: takes offset, n_points, curvature, points, product, "
+                                 "obstacle_list and robot_radius")
+            if curvature is not None and not isinstance(curvature, (bool, np.bool_)):
+                if offset != 3.0:   # the third positional argument of this kind is the offset
+                    raise ValueError("BatchSteer('bezier').plan: two offsets (curvature is a flag for this kind)")
+                offset, curvature = curvature, True
+            return self._plan_bezier(starts, goals, None, offset, n_points, True if curvature is None else curvature,
+                                     points, product, obstacle_list, robot_radius)
+        if offset != 3.0 or n_points != 100:
+            raise ValueError("BatchSteer.plan: offset and n_points belong to kind 'bezier'")
         if step_size is None:
             step_size = DEFAULT_STEP[self.kind]
         if self.kind == _abi.STEER_LQR:
@@ -201,6 +263,31 @@ class BatchSteer:
         xyz = S.points() if points else None
         return SteerResult(self.kind, status, length, nseg, seglen, modes, off, xyz,
                            (len(st), len(go)) if product else None, rc, S.kernel_ms(), hit=S.hits() if len(ob) else None)
+
+    def plan_control_points(self, control_points, n_points=100, curvature=True, points=True, obstacle_list=None,
+                            robot_radius=0.0):
+        """"bezier": calc_bezier_path for a batch of control-point sets (n, m, 2) -- or one (m, 2) -- with 3 <= m <= 16."""
+        if self.kind != _abi.STEER_BEZIER:
+            raise ValueError("BatchSteer.plan_control_points belongs to kind 'bezier'")
+        return self._plan_bezier(None, None, control_points, None, n_points, curvature, points, False, obstacle_list,
+                                 robot_radius)
+
+    def _plan_bezier(self, starts, goals, cps, offset, n_points, curvature, points, product, obstacle_list, robot_radius):
+        S = self._steer
+        ob = self._set_obstacles(obstacle_list, robot_radius)
+        shape = None
+        if cps is not None:
+            rc = S.solve_bezier_cp(cps, n_points, points=points, curvature=curvature)
+        else:
+            st = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+            go = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
+            rc = S.solve_bezier(st, go, offset, n_points, points=points, curvature=curvature, product=product)
+            shape = (len(st), len(go)) if product else None
+        status, length, nseg, seglen, modes, off = S.summary(offsets=bool(points))
+        xyz = S.points() if points else None
+        return SteerResult(self.kind, status, length, nseg, seglen, modes, off, xyz, shape, rc, S.kernel_ms(),
+                           hit=S.hits() if len(ob) else None, k=S.curvature() if points and curvature else None,
+                           kmax=S.kmax() if curvature else None, control_points=S.control_points())
 
     def _set_obstacles(self, obstacle_list, robot_radius):
         S = self._steer

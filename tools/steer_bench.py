@@ -1,6 +1,6 @@
 """Throughput of the batched Dubins / Reeds-Shepp curves (BatchSteer): pairs/s for lengths-only and for points.
 
-    python tools/steer_bench.py [--pairs 1048576] [--reps 5] [--cpu-pairs 2000] [--obstacles M] [--kind lqr]
+    python tools/steer_bench.py [--pairs 1048576] [--reps 5] [--cpu-pairs 2000] [--obstacles M] [--kind lqr|bezier]
 
 Random pairs in the pose box of the known-answer vectors ([-2, 15]^2, any yaw), curvature 1, Reeds-Shepp step 0.2.  The
 GPU figure is HIP-event kernel time (stage 1, and stage 1 + fill), the median of --reps solves after one warm-up solve;
@@ -15,7 +15,13 @@ and result arrays included), and "free_fraction" the share of pairs whose curve 
 
 --kind lqr (default: the two curve kinds, the output above, unchanged) measures BatchSteer("lqr") alone: random point pairs
 in the same box, rrt_09's step 0.2, the same variants; the one-core figure beside it is tests/lqr_oracle.edge (pure Python)
-on a subsample of the same pairs."""
+on a subsample of the same pairs.
+
+--kind bezier measures BatchSteer("bezier") alone: the same pose pairs, offset 3.0, 100 points per curve.  One JSON line
+with a row per variant -- "lengths" (points=False, curvature=False), "lengths_kmax" (points=False), "points" (x, y, yaw
+and k per point), and with --obstacles M "check_lengths" and "check_points" -- each with the HIP-event kernel time (weight
+table, stage 1, fill; the median of --reps calls after one warm-up) and the wall time of the whole BatchSteer.plan() call
+beside it; then tests/bezier_oracle.curve4 (pure Python) on one core over a subsample of the same pairs."""
 import argparse
 import json
 import os
@@ -38,14 +44,55 @@ def pairs(n, seed):
     return p
 
 
+def bench_bezier(args):
+    import rrt_amd
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bezier_oracle
+    p = pairs(args.pairs, 11)
+    out = {"kind": "bezier", "pairs": args.pairs, "reps": args.reps, "n_points": 100, "offset": 3.0}
+    rows = [("lengths", dict(points=False, curvature=False)), ("lengths_kmax", dict(points=False)), ("points", dict())]
+    if args.obstacles > 0:
+        rs = np.random.RandomState(9)
+        circles = np.stack([rs.uniform(-2, 15, args.obstacles), rs.uniform(-2, 15, args.obstacles),
+                            rs.uniform(0.2, 0.8, args.obstacles)], axis=1)
+        out["obstacles"] = args.obstacles
+        rows += [("check_lengths", dict(points=False, obstacle_list=circles)), ("check_points", dict(obstacle_list=circles))]
+    with rrt_amd.BatchSteer("bezier") as bs:
+        for name, kw in rows:
+            ms, wall = [], []
+            for rep in range(args.reps + 1):
+                t0 = time.perf_counter()
+                res = bs.plan(p[:, 0:3], p[:, 3:6], offset=3.0, n_points=100, **kw)
+                wall.append((time.perf_counter() - t0) * 1e3)
+                ms.append(res.kernel_ms)
+                if "obstacle_list" in kw:
+                    out["free_fraction"] = float(np.mean(res.free))
+                res = None
+            med = float(np.median(ms[1:]))
+            out[name + "_kernel_ms"] = med
+            out[name + "_pairs_per_s"] = args.pairs / (med * 1e-3)
+            out[name + "_plan_wall_ms"] = float(np.median(wall[1:]))
+    m = min(args.cpu_pairs, args.pairs)
+    t0 = time.perf_counter()
+    for i in range(m):
+        bezier_oracle.curve4(*[float(v) for v in p[i]], 3.0, n_points=100)
+    dt = time.perf_counter() - t0
+    out["cpu_oracle"] = "tests/bezier_oracle.curve4 (pure Python)"
+    out["cpu_oracle_pairs"] = m
+    out["cpu_oracle_pairs_per_s_one_core"] = m / dt
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cpu-pairs", type=int, default=2000)
     ap.add_argument("--obstacles", type=int, default=0)
-    ap.add_argument("--kind", choices=("curves", "lqr"), default="curves")
+    ap.add_argument("--kind", choices=("curves", "lqr", "bezier"), default="curves")
     args = ap.parse_args()
+    if args.kind == "bezier":
+        return bench_bezier(args)
     import oracle
     import rrt_amd
     lqr = args.kind == "lqr"
