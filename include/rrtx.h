@@ -604,6 +604,70 @@ int rrtx_spline_get_c(rrtx_spline* s, double* cx, double* cy, int64_t cap);
  * the last run had no obstacle list. */
 int rrtx_spline_get_hits(rrtx_spline* s, int32_t* hit);
 
+/* ---- batched arm navigation: joint-space occupancy grids and searches on the torus grid, without a planner
+ * (csrc/armnav_batch.hip.h, csrc/rpp_armnav.h) ---------------------------------------------------------------------------------
+ * The two functions of 02_arm_obstacle_navigation.py for many scenes and many queries in one call: get_occupancy_grid (:79-110)
+ * marks every cell (i, j) of the M x M joint space of a planar N-link arm where a link touches a circle, and astar_torus
+ * (:113-184) runs a greedy best-first search with 4-neighbour wrap-around from a start cell to a goal cell.  Everything returned
+ * is integers -- grid cells 0 / 1, route cells, the marks 0..6 the search leaves in its grid, the number of cells it closed --
+ * and every one of them is the reference's.
+ * The object is independent of rrtx_handle; it owns its device buffers, keeps the grids of the last rrtx_armnav_occupancy or
+ * rrtx_armnav_set_grids on the device and reuses everything from call to call.  One object serves one thread at a time. */
+typedef struct rrtx_armnav rrtx_armnav;
+
+#define RRTX_ARMNAV_ROUTE 0      /* a route was found */
+#define RRTX_ARMNAV_NO_ROUTE 1   /* the goal was never opened: the reference prints "No route found." and returns [] (:165-167) */
+#define RRTX_ARMNAV_MIN_M 2
+#define RRTX_ARMNAV_MAX_M 128              /* the search state of one query lives in the LDS of one wave */
+#define RRTX_ARMNAV_MAX_LINKS 16           /* per scene */
+#define RRTX_ARMNAV_MAX_CIRCLES 1024       /* per scene */
+#define RRTX_ARMNAV_MAX_CELLS 268435456LL  /* scenes x M^2 per call (2^28) */
+#define RRTX_ARMNAV_MAX_QUERIES 1048576LL  /* per call (2^20) */
+
+/* The object is handed out on RRTX_E_NO_DEVICE too (destroy it as usual): its calls then check their arguments and fail. */
+int rrtx_armnav_create(int32_t device, rrtx_armnav** out);
+void rrtx_armnav_destroy(rrtx_armnav* a);
+/* The message of the last call on `a` that failed; for a == NULL the last failure of a call of this thread that had no object. */
+const char* rrtx_armnav_last_error(rrtx_armnav* a);
+
+/* get_occupancy_grid(arm, obstacles, M) (:79-110, with NLinkArm.update_points :257-262 and detect_collision :46-76) for n_scenes
+ * scenes at once.  Scene s has the link lengths link_len[link_off[s] .. link_off[s + 1]) and the circles, rows (x, y, radius),
+ * obs_xyr[3 * obs_off[s] .. 3 * obs_off[s + 1]).  As in the reference the grid varies the first two joint angles and leaves the
+ * others at what the two-element angle list gives them: link 1 at theta_list[i], every later link at theta_list[i] + theta_list[j].
+ * The grids stay on the device for rrtx_armnav_search; rrtx_armnav_get_grids reads them.
+ * RRTX_E_INVALID, before any device call and also without a device: M outside 2..128, n_scenes < 1 or n_scenes * M * M > 2^28, a
+ * NULL array, offsets that do not start at 0 or decrease, a scene with no link or more than 16, a length that is not finite, is
+ * zero (the reference divides by it) or above 1e6 in magnitude (negative lengths are legal), more than 1024 circles in a scene, a
+ * circle entry that is not finite, a negative radius. */
+int rrtx_armnav_occupancy(rrtx_armnav* a, int32_t M, int64_t n_scenes, const int64_t* link_off, const double* link_len,
+                          const int64_t* obs_off, const double* obs_xyr);
+/* Grids given as data, n_scenes * M * M bytes, as astar_torus (:113) takes any ndarray: 0 free, 1 obstacle, 2..6 the marks of an
+ * earlier search.  RRTX_E_INVALID: the shape as above, bytes NULL, a byte above 6. */
+int rrtx_armnav_set_grids(rrtx_armnav* a, int32_t M, int64_t n_scenes, const uint8_t* bytes);
+/* The grids on the device, n_scenes * M * M bytes (cap = bytes available).  RRTX_E_STATE before a call that brought grids. */
+int rrtx_armnav_get_grids(rrtx_armnav* a, uint8_t* bytes, int64_t cap);
+
+/* astar_torus(grid, start_node, goal_node) (:113-184, with find_neighbors :187-209 and calc_heuristic_map :221-233) for
+ * n_queries queries at once: query q searches a copy of grid scene[q] (scene == NULL: grid 0) from the cell start_ij[2 q],
+ * start_ij[2 q + 1] to the cell goal_ij[2 q], goal_ij[2 q + 1].  The grids themselves are not changed; with want_marks the
+ * grid each query leaves behind (marks 0..6) is kept for rrtx_armnav_get_marks.
+ * RRTX_E_INVALID, also without a device: n_queries < 0 or > 2^20, a NULL array, a start or goal index outside [0, M) (numpy would
+ * wrap a negative index; this call refuses it), a scene index outside the scenes.  RRTX_E_STATE: no grids. */
+int rrtx_armnav_search(rrtx_armnav* a, int64_t n_queries, const int32_t* scene, const int32_t* start_ij, const int32_t* goal_ij,
+                       int32_t want_marks);
+/* Per query of the last search, any pointer may be NULL: status RRTX_ARMNAV_*, the cells of the route (0 without one), the cells
+ * the search closed (trips of the loop :141 that did not end it); n_queries and n_cells, the cells of all routes. */
+int rrtx_armnav_get_counts(rrtx_armnav* a, int32_t* status, int32_t* n_route, int32_t* pops, int64_t* n_queries, int64_t* n_cells);
+/* The routes of the last search, start first and goal last as the reference returns them (:169-171): offsets[n_queries + 1] into
+ * the rows (i, j) of cells_ij (cap = rows available); either pointer may be NULL. */
+int rrtx_armnav_get_routes(rrtx_armnav* a, int64_t* offsets, int32_t* cells_ij, int64_t cap);
+/* The grid every query left behind, n_queries * M * M bytes (cap = bytes available): 0 free, 1 obstacle, 2 closed (:151),
+ * 3 opened (:163), 4 the start, 5 the goal (:142-143), 6 the route after its first cell (:175).  RRTX_E_STATE after a search
+ * with want_marks = 0. */
+int rrtx_armnav_get_marks(rrtx_armnav* a, uint8_t* marks, int64_t cap);
+/* HIP-event time of the kernels of the last rrtx_armnav_occupancy and of the last rrtx_armnav_search. */
+int rrtx_armnav_get_kernel_ms(rrtx_armnav* a, double* grid_ms, double* search_ms);
+
 /* parity harness: out[i] = op(a[i], b[i]) evaluated on the device.  op 0 math.hypot, 1 x**2, 2 sin, 3 cos, 4 atan2,
  * 5 steer end x (rrt_04:1086-1115), 6 sqrt, 7 a/b, 8 acos, 9 asin, 10 checksum of the Reeds-Shepp steer
  * (0,0,0) -> (a, b, a+b) (rrt_06:1426-1441, csrc/rpp_rs.h), 11 math.tan(a) (|a| <= 0.79), 12 np.hypot(a, b) */

@@ -38,7 +38,10 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_tracker_create", "rrtx_tracker_destroy", "rrtx_tracker_last_error", "rrtx_tracker_run",
            "rrtx_tracker_get_counts", "rrtx_tracker_get_records", "rrtx_tracker_get_arrays", "rrtx_tracker_get_kernel_ms",
            "rrtx_spline_create", "rrtx_spline_destroy", "rrtx_spline_last_error", "rrtx_spline_run", "rrtx_spline_get_records",
-           "rrtx_spline_get_points", "rrtx_spline_get_c", "rrtx_spline_get_hits"]
+           "rrtx_spline_get_points", "rrtx_spline_get_c", "rrtx_spline_get_hits",
+           "rrtx_armnav_create", "rrtx_armnav_destroy", "rrtx_armnav_last_error", "rrtx_armnav_occupancy", "rrtx_armnav_set_grids",
+           "rrtx_armnav_get_grids", "rrtx_armnav_search", "rrtx_armnav_get_counts", "rrtx_armnav_get_routes",
+           "rrtx_armnav_get_marks", "rrtx_armnav_get_kernel_ms"]
 STEER_DUBINS, STEER_RS = 0, 1                                                      # include/rrtx.h: #define RRTX_STEER_*
 STEER_LQR = 2   # this binding's own name for "solved by rrtx_steer_solve_lqr": the C ABI has an entry point, not a kind value
 STEER_BEZIER = 3   # likewise: rrtx_steer_solve_bezier / rrtx_steer_solve_bezier_cp
@@ -49,6 +52,9 @@ RS_COST_EUCLID, RS_COST_PATH = 0, 1     # include/rrtx.h: #define RRTX_RS_COST_*
 TRACK_FAIL_REACH, TRACK_FAIL_ANGLE, TRACK_FAIL_LONG, TRACK_FAIL_COLLISION = 1, 2, 4, 8   # #define RRTX_TRACK_FAIL_*
 SPLINE_OK, SPLINE_DEGENERATE, SPLINE_REF_RAISES = 0, 1, 2                                # #define RRTX_SPLINE_*
 SPLINE_MAX_WAYPOINTS, SPLINE_MAX_POINTS = 4096, 1 << 28
+ARMNAV_ROUTE, ARMNAV_NO_ROUTE = 0, 1                                                     # #define RRTX_ARMNAV_*
+ARMNAV_MIN_M, ARMNAV_MAX_M, ARMNAV_MAX_LINKS, ARMNAV_MAX_CIRCLES = 2, 128, 16, 1024
+ARMNAV_MAX_CELLS, ARMNAV_MAX_QUERIES = 1 << 28, 1 << 20
 
 
 class Params(C.Structure):
@@ -216,10 +222,23 @@ def load():
     L.rrtx_spline_get_points.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64]
     L.rrtx_spline_get_c.argtypes = [vp, vp, vp, C.c_int64]
     L.rrtx_spline_get_hits.argtypes = [vp, vp]
+    L.rrtx_armnav_create.argtypes = [i32, C.POINTER(vp)]
+    L.rrtx_armnav_destroy.argtypes = [vp]
+    L.rrtx_armnav_destroy.restype = None
+    L.rrtx_armnav_last_error.argtypes = [vp]
+    L.rrtx_armnav_last_error.restype = C.c_char_p
+    L.rrtx_armnav_occupancy.argtypes = [vp, i32, C.c_int64, vp, vp, vp, vp]
+    L.rrtx_armnav_set_grids.argtypes = [vp, i32, C.c_int64, vp]
+    L.rrtx_armnav_get_grids.argtypes = [vp, vp, C.c_int64]
+    L.rrtx_armnav_search.argtypes = [vp, C.c_int64, vp, vp, vp, i32]
+    L.rrtx_armnav_get_counts.argtypes = [vp, vp, vp, vp, i64p, i64p]
+    L.rrtx_armnav_get_routes.argtypes = [vp, vp, vp, C.c_int64]
+    L.rrtx_armnav_get_marks.argtypes = [vp, vp, C.c_int64]
+    L.rrtx_armnav_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     for f in EXPORTS:
         if f not in ("rrtx_last_error", "rrtx_destroy", "rrtx_abi_version", "rrtx_device_count", "rrtx_steer_destroy",
                      "rrtx_steer_last_error", "rrtx_tracker_destroy", "rrtx_tracker_last_error", "rrtx_spline_destroy",
-                     "rrtx_spline_last_error"):
+                     "rrtx_spline_last_error", "rrtx_armnav_destroy", "rrtx_armnav_last_error"):
             getattr(L, f).restype = C.c_int
     if L.rrtx_abi_version() != RRTX_ABI_VERSION:
         raise RrtxError("librrtx.so ABI version mismatch")
@@ -899,6 +918,90 @@ class Spline:
         hit = np.zeros(n, dtype=np.int32)
         self._chk(self.L.rrtx_spline_get_hits(self._s, hit.ctypes.data), "rrtx_spline_get_hits")
         return hit
+
+
+class ArmNav:
+    """Thin RAII wrapper over rrtx_armnav* (batched joint-space occupancy grids of a planar arm and searches on them); also a
+    context manager.  It owns the device buffers of its calls and keeps the grids of the last occupancy() / set_grids()."""
+
+    def __init__(self, device=0):
+        self.L = load()
+        self._a = C.c_void_p()
+        rc = self.L.rrtx_armnav_create(int(device), C.byref(self._a))
+        if rc != 0:
+            msg = self.L.rrtx_armnav_last_error(self._a).decode()
+            self.close()
+            raise RrtxError("rrtx_armnav_create: %s %s" % (ERRORS.get(rc, rc), msg))
+
+    def close(self):
+        if getattr(self, "_a", None):
+            self.L.rrtx_armnav_destroy(self._a)
+            self._a = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_armnav_last_error(self._a).decode()))
+        return rc
+
+    def occupancy(self, M, link_off, link_len, obs_off, obs_xyr):
+        """CSR scenes: int64 offsets of n_scenes + 1 entries, float64 lengths, float64 rows (x, y, radius)."""
+        self._chk(self.L.rrtx_armnav_occupancy(self._a, int(M), len(link_off) - 1, link_off.ctypes.data, link_len.ctypes.data,
+                                               obs_off.ctypes.data, obs_xyr.ctypes.data if len(obs_xyr) else None),
+                  "rrtx_armnav_occupancy")
+
+    def set_grids(self, grids):
+        """grids: contiguous uint8 (n_scenes, M, M)."""
+        self._chk(self.L.rrtx_armnav_set_grids(self._a, grids.shape[1], grids.shape[0], grids.ctypes.data), "rrtx_armnav_set_grids")
+
+    def grids(self, n_scenes, M):
+        out = np.zeros((n_scenes, M, M), dtype=np.uint8)
+        self._chk(self.L.rrtx_armnav_get_grids(self._a, out.ctypes.data, out.size), "rrtx_armnav_get_grids")
+        return out
+
+    def search(self, scene, starts, goals, want_marks):
+        """scene: int32 (n,) or None; starts / goals: contiguous int32 (n, 2)."""
+        self._chk(self.L.rrtx_armnav_search(self._a, len(starts), None if scene is None else scene.ctypes.data,
+                                            starts.ctypes.data if len(starts) else None, goals.ctypes.data if len(goals) else None,
+                                            int(bool(want_marks))), "rrtx_armnav_search")
+
+    def counts(self):
+        """(status, n_route, pops) int32 (n,) each, of the last search."""
+        n, m = C.c_int64(), C.c_int64()
+        self._chk(self.L.rrtx_armnav_get_counts(self._a, None, None, None, C.byref(n), C.byref(m)), "rrtx_armnav_get_counts")
+        out = [np.zeros(n.value, dtype=np.int32) for _ in range(3)]
+        self._chk(self.L.rrtx_armnav_get_counts(self._a, *[q.ctypes.data for q in out], None, None), "rrtx_armnav_get_counts")
+        return tuple(out) + (m.value,)
+
+    def routes(self, n, n_cells):
+        """(offsets (n + 1,) int64, cells (n_cells, 2) int32) of the last search."""
+        off = np.zeros(n + 1, dtype=np.int64)
+        cells = np.zeros((n_cells, 2), dtype=np.int32)
+        self._chk(self.L.rrtx_armnav_get_routes(self._a, off.ctypes.data, cells.ctypes.data if n_cells else None, n_cells),
+                  "rrtx_armnav_get_routes")
+        return off, cells
+
+    def marks(self, n, M):
+        out = np.zeros((n, M, M), dtype=np.uint8)
+        self._chk(self.L.rrtx_armnav_get_marks(self._a, out.ctypes.data, out.size), "rrtx_armnav_get_marks")
+        return out
+
+    def kernel_ms(self):
+        g, s = C.c_double(), C.c_double()
+        self._chk(self.L.rrtx_armnav_get_kernel_ms(self._a, C.byref(g), C.byref(s)), "rrtx_armnav_get_kernel_ms")
+        return g.value, s.value
 
 
 def rccl_unique_id():

@@ -23,6 +23,7 @@
 #include "rrt_track.hip.h"
 #include "steer_batch.hip.h"
 #include "spline_batch.hip.h"
+#include "armnav_batch.hip.h"
 
 using rppk::Ctx;
 using rppk::Inst;
@@ -1735,3 +1736,4 @@ int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps) {
 #include "rrtx_api_steer.inc"
 #include "rrtx_api_tracker.inc"
 #include "rrtx_api_spline.inc"
+#include "rrtx_api_armnav.inc"
