@@ -668,6 +668,76 @@ int rrtx_armnav_get_marks(rrtx_armnav* a, uint8_t* marks, int64_t cap);
 /* HIP-event time of the kernels of the last rrtx_armnav_occupancy and of the last rrtx_armnav_search. */
 int rrtx_armnav_get_kernel_ms(rrtx_armnav* a, double* grid_ms, double* search_ms);
 
+/* ---- batched inverse kinematics of planar arms: the Jacobian inverse method and the driver's P-control loop, without a planner
+ * (csrc/armik_batch.hip.h, csrc/rpp_armik.h) -----------------------------------------------------------------------------------
+ * inverse_kinematics (:71-85) of 00_simple_2d_inverse_kinematics_01.py and the loop of its driver cell (:189-200) for many
+ * queries in one call; every query has its own arm (1..16 links), start angles and Cartesian goal.  Forward kinematics, the
+ * Jacobian, the distance test and the whole P-control loop are the reference's doubles; the step pinv(J) @ errors is this
+ * library's own closed form with a stated rank rule, so solves agree with the reference's LAPACK step to a measured
+ * tolerance where the iteration is short, and not at all where it is chaotic.
+ * The object is independent of the others; it owns its device buffers and reuses them.  One object serves one thread at a time. */
+typedef struct rrtx_armik rrtx_armik;
+
+#define RRTX_ARMIK_FOUND 0       /* solve: distance < goal_dist; move: the loop ended, distance <= goal_dist */
+#define RRTX_ARMIK_NOT_FOUND 1   /* solve: max_iterations trips without it; the angles are returned as they stand (:85) */
+#define RRTX_ARMIK_NONFINITE 2   /* solve: a step made an angle NaN or infinite, or a sum of angles reached 105 414 357 rad, where the \
+                                    device's sin / cos end; the lane stopped there with the angles as they stand, iterations = \
+                                    max_iterations, end and distance those of the last trip that computed them; \
+                                    move: the same bound on a sum of angles, which only a huge Kp * dt can reach -- the \
+                                    loop stopped there, n_steps counts the step that left */
+#define RRTX_ARMIK_STEP_CAP 3    /* move: max_steps steps and still distance > goal_dist (the reference would not return) */
+#define RRTX_ARMIK_MAX_LINKS 16
+#define RRTX_ARMIK_MAX_QUERIES 1048576LL       /* per call (2^20) */
+#define RRTX_ARMIK_MAX_ITERATIONS 1000000
+#define RRTX_ARMIK_MAX_STEPS 10000000
+#define RRTX_ARMIK_MAX_WAVES 65536             /* an explicit `waves` of rrtx_armik_solve */
+#define RRTX_ARMIK_MAX_TRAJECTORY 268435456LL  /* doubles of all trajectories of one move (2^28) */
+
+typedef struct rrtx_armik_batch {
+  int64_t n_arms;
+  const int64_t* link_off;     /* n_arms + 1, CSR into link_len */
+  const double* link_len;      /* zero and negative lengths are legal: nothing divides by a length */
+  int64_t n;                   /* queries */
+  const int32_t* arm;          /* n, the arm of each query; NULL: arm 0 */
+  const double* angles;        /* the start angles, query after query, as many as the query's arm has links */
+  const double* goals;         /* n rows (x, y) */
+  const double* goal_angles;   /* rrtx_armik_move only: joint_goal_angles in the layout of angles */
+  double goal_dist;            /* 0.1 in the script */
+} rrtx_armik_batch;
+
+/* The object is handed out on RRTX_E_NO_DEVICE too (destroy it as usual): its calls then check their arguments and fail. */
+int rrtx_armik_create(int32_t device, rrtx_armik** out);
+void rrtx_armik_destroy(rrtx_armik* a);
+/* The message of the last call on `a` that failed; for a == NULL the last failure of a call of this thread that had no object. */
+const char* rrtx_armik_last_error(rrtx_armik* a);
+/* inverse_kinematics(link_lengths, joint_angles, goal_pos) with N_ITERATIONS = max_iterations for every query.  waves: the
+ * number of persistent waves launched, exactly (each lane takes queries from a cursor until it is spent; a wave that finds it
+ * spent at once leaves); 0: as many as the device holds, never more than ceil(n / 64).  The results do not depend on it.  Returns RRTX_OK, or RRTX_PARTIAL when some status is not
+ * RRTX_ARMIK_FOUND (every query is complete).  RRTX_E_INVALID, before any HIP call and also without a device: a NULL pointer
+ * (arm may be NULL), n_arms < 1, an arm of no link or more than 16, a length, angle or goal coordinate that is not finite or
+ * above 1e6 in magnitude, n < 0 or > 2^20, arm[q] outside the arms, goal_dist not > 0, max_iterations outside 1..1e6,
+ * waves < 0 or > 65536. */
+int rrtx_armik_solve(rrtx_armik* a, const rrtx_armik_batch* b, int32_t max_iterations, int32_t waves);
+/* The driver's loop for every query: while distance > goal_dist: angles += Kp * ang_diff(goal_angles, angles) * dt.  A query that
+ * starts within goal_dist takes no step.  With want_arrays the angles and the distance after every step are kept for
+ * rrtx_armik_get_trajectory: a first pass counts the steps, a second fills; nothing is truncated (RRTX_E_CAPACITY above 2^28
+ * doubles).  Returns RRTX_OK, or RRTX_PARTIAL when some status is RRTX_ARMIK_STEP_CAP or RRTX_ARMIK_NONFINITE.  RRTX_E_INVALID as above, and for
+ * max_steps outside 1..1e7, Kp or dt not finite. */
+int rrtx_armik_move(rrtx_armik* a, const rrtx_armik_batch* b, double Kp, double dt, int32_t max_steps, int32_t want_arrays);
+/* Per query of the last solve or move, any pointer may be NULL: status RRTX_ARMIK_*; count: the value of `iteration` at the
+ * return (max_iterations when not found), or the steps of the move; end_xy rows (x, y): the last current_pos / end effector
+ * computed; distance: its distance to the goal; n_queries and n_angles, the doubles of rrtx_armik_get_angles. */
+int rrtx_armik_get_records(rrtx_armik* a, int32_t* status, int32_t* count, double* end_xy, double* distance, int64_t* n_queries,
+                           int64_t* n_angles);
+/* The angles each query ended with: offsets[n_queries + 1] into angles (cap = doubles available); either may be NULL. */
+int rrtx_armik_get_angles(rrtx_armik* a, int64_t* offsets, double* angles, int64_t cap);
+/* The trajectories of the last move: step_offsets[n + 1] into distance, angle_offsets[n + 1] into angles (step after step, N
+ * angles each); any pointer may be NULL.  RRTX_E_STATE after a move with want_arrays = 0 or after a solve. */
+int rrtx_armik_get_trajectory(rrtx_armik* a, int64_t* step_offsets, int64_t* angle_offsets, double* angles, double* distance,
+                              int64_t cap_steps, int64_t cap_angles);
+/* HIP-event time of the kernels of the last run (both passes of a move with arrays) and the waves it launched. */
+int rrtx_armik_get_kernel_ms(rrtx_armik* a, double* kernel_ms, int32_t* waves);
+
 /* parity harness: out[i] = op(a[i], b[i]) evaluated on the device.  op 0 math.hypot, 1 x**2, 2 sin, 3 cos, 4 atan2,
  * 5 steer end x (rrt_04:1086-1115), 6 sqrt, 7 a/b, 8 acos, 9 asin, 10 checksum of the Reeds-Shepp steer
  * (0,0,0) -> (a, b, a+b) (rrt_06:1426-1441, csrc/rpp_rs.h), 11 math.tan(a) (|a| <= 0.79), 12 np.hypot(a, b) */

@@ -41,7 +41,9 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_spline_get_points", "rrtx_spline_get_c", "rrtx_spline_get_hits",
            "rrtx_armnav_create", "rrtx_armnav_destroy", "rrtx_armnav_last_error", "rrtx_armnav_occupancy", "rrtx_armnav_set_grids",
            "rrtx_armnav_get_grids", "rrtx_armnav_search", "rrtx_armnav_get_counts", "rrtx_armnav_get_routes",
-           "rrtx_armnav_get_marks", "rrtx_armnav_get_kernel_ms"]
+           "rrtx_armnav_get_marks", "rrtx_armnav_get_kernel_ms",
+           "rrtx_armik_create", "rrtx_armik_destroy", "rrtx_armik_last_error", "rrtx_armik_solve", "rrtx_armik_move",
+           "rrtx_armik_get_records", "rrtx_armik_get_angles", "rrtx_armik_get_trajectory", "rrtx_armik_get_kernel_ms"]
 STEER_DUBINS, STEER_RS = 0, 1                                                      # include/rrtx.h: #define RRTX_STEER_*
 STEER_LQR = 2   # this binding's own name for "solved by rrtx_steer_solve_lqr": the C ABI has an entry point, not a kind value
 STEER_BEZIER = 3   # likewise: rrtx_steer_solve_bezier / rrtx_steer_solve_bezier_cp
@@ -55,6 +57,9 @@ SPLINE_MAX_WAYPOINTS, SPLINE_MAX_POINTS = 4096, 1 << 28
 ARMNAV_ROUTE, ARMNAV_NO_ROUTE = 0, 1                                                     # #define RRTX_ARMNAV_*
 ARMNAV_MIN_M, ARMNAV_MAX_M, ARMNAV_MAX_LINKS, ARMNAV_MAX_CIRCLES = 2, 128, 16, 1024
 ARMNAV_MAX_CELLS, ARMNAV_MAX_QUERIES = 1 << 28, 1 << 20
+ARMIK_FOUND, ARMIK_NOT_FOUND, ARMIK_NONFINITE, ARMIK_STEP_CAP = 0, 1, 2, 3                # #define RRTX_ARMIK_*
+ARMIK_MAX_LINKS, ARMIK_MAX_QUERIES, ARMIK_MAX_ITERATIONS, ARMIK_MAX_STEPS, ARMIK_MAX_TRAJECTORY = 16, 1 << 20, 1000000, 10000000, 1 << 28
+ARMIK_MAX_WAVES = 1 << 16
 
 
 class Params(C.Structure):
@@ -106,6 +111,12 @@ class SplineBatch(C.Structure):
     _fields_ = [("n", C.c_int64), ("offsets", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p), ("ds", C.c_void_p),
                 ("ds_per_course", C.c_int32), ("want_arrays", C.c_int32), ("cx", C.c_void_p), ("cy", C.c_void_p),
                 ("n_c", C.c_int64), ("obstacles", C.c_void_p), ("n_obstacles", C.c_int64), ("robot_radius", C.c_double)]
+
+
+class ArmIKBatch(C.Structure):
+    """rrtx_armik_batch: the queries of one rrtx_armik_solve / rrtx_armik_move (pointers into arrays the caller keeps alive)."""
+    _fields_ = [("n_arms", C.c_int64), ("link_off", C.c_void_p), ("link_len", C.c_void_p), ("n", C.c_int64), ("arm", C.c_void_p),
+                ("angles", C.c_void_p), ("goals", C.c_void_p), ("goal_angles", C.c_void_p), ("goal_dist", C.c_double)]
 
 
 class Stats(C.Structure):
@@ -235,8 +246,19 @@ def load():
     L.rrtx_armnav_get_routes.argtypes = [vp, vp, vp, C.c_int64]
     L.rrtx_armnav_get_marks.argtypes = [vp, vp, C.c_int64]
     L.rrtx_armnav_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.rrtx_armik_create.argtypes = [i32, C.POINTER(vp)]
+    L.rrtx_armik_destroy.argtypes = [vp]
+    L.rrtx_armik_destroy.restype = None
+    L.rrtx_armik_last_error.argtypes = [vp]
+    L.rrtx_armik_last_error.restype = C.c_char_p
+    L.rrtx_armik_solve.argtypes = [vp, C.POINTER(ArmIKBatch), i32, i32]
+    L.rrtx_armik_move.argtypes = [vp, C.POINTER(ArmIKBatch), C.c_double, C.c_double, i32, i32]
+    L.rrtx_armik_get_records.argtypes = [vp, vp, vp, vp, vp, i64p, i64p]
+    L.rrtx_armik_get_angles.argtypes = [vp, vp, vp, C.c_int64]
+    L.rrtx_armik_get_trajectory.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int64]
+    L.rrtx_armik_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i32)]
     for f in EXPORTS:
-        if f not in ("rrtx_last_error", "rrtx_destroy", "rrtx_abi_version", "rrtx_device_count", "rrtx_steer_destroy",
+        if f not in ("rrtx_armik_destroy", "rrtx_armik_last_error", "rrtx_last_error", "rrtx_destroy", "rrtx_abi_version", "rrtx_device_count", "rrtx_steer_destroy",
                      "rrtx_steer_last_error", "rrtx_tracker_destroy", "rrtx_tracker_last_error", "rrtx_spline_destroy",
                      "rrtx_spline_last_error", "rrtx_armnav_destroy", "rrtx_armnav_last_error"):
             getattr(L, f).restype = C.c_int
@@ -1002,6 +1024,97 @@ class ArmNav:
         g, s = C.c_double(), C.c_double()
         self._chk(self.L.rrtx_armnav_get_kernel_ms(self._a, C.byref(g), C.byref(s)), "rrtx_armnav_get_kernel_ms")
         return g.value, s.value
+
+
+class ArmIK:
+    """Thin RAII wrapper over rrtx_armik* (batched inverse kinematics of planar arms and the driver's P-control loop); also a
+    context manager.  It owns the device buffers of its calls."""
+
+    def __init__(self, device=0):
+        self.L = load()
+        self._a = C.c_void_p()
+        rc = self.L.rrtx_armik_create(int(device), C.byref(self._a))
+        if rc != 0:
+            msg = self.L.rrtx_armik_last_error(self._a).decode()
+            self.close()
+            raise RrtxError("rrtx_armik_create: %s %s" % (ERRORS.get(rc, rc), msg))
+
+    def close(self):
+        if getattr(self, "_a", None):
+            self.L.rrtx_armik_destroy(self._a)
+            self._a = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_armik_last_error(self._a).decode()))
+        return rc
+
+    @staticmethod
+    def _batch(link_off, link_len, arm, angles, goals, goal_angles, goal_dist):
+        """Contiguous arrays: int64 link_off (n_arms + 1,), float64 link_len, int32 arm (n,) or None, float64 angles (flat, query
+        after query), float64 goals (n, 2), float64 goal_angles (flat) or None."""
+        b = ArmIKBatch()
+        b.n_arms, b.link_off, b.link_len = len(link_off) - 1, link_off.ctypes.data, link_len.ctypes.data
+        b.n, b.arm = len(goals), None if arm is None else arm.ctypes.data
+        b.angles, b.goals = angles.ctypes.data, goals.ctypes.data
+        b.goal_angles = None if goal_angles is None else goal_angles.ctypes.data
+        b.goal_dist = float(goal_dist)
+        return b
+
+    def solve(self, link_off, link_len, arm, angles, goals, goal_dist, max_iterations, waves):
+        """Returns the call's code: 0, or RRTX_PARTIAL when some query was not found."""
+        b = self._batch(link_off, link_len, arm, angles, goals, None, goal_dist)
+        return self._chk(self.L.rrtx_armik_solve(self._a, C.byref(b), int(max_iterations), int(waves)), "rrtx_armik_solve")
+
+    def move(self, link_off, link_len, arm, angles, goal_angles, goals, goal_dist, Kp, dt, max_steps, want_arrays):
+        b = self._batch(link_off, link_len, arm, angles, goals, goal_angles, goal_dist)
+        return self._chk(self.L.rrtx_armik_move(self._a, C.byref(b), float(Kp), float(dt), int(max_steps), int(bool(want_arrays))),
+                         "rrtx_armik_move")
+
+    def records(self):
+        """(status int32 (n,), count int32 (n,), end (n, 2), distance (n,)) of the last run."""
+        n, m = C.c_int64(), C.c_int64()
+        self._chk(self.L.rrtx_armik_get_records(self._a, None, None, None, None, C.byref(n), C.byref(m)), "rrtx_armik_get_records")
+        status, count = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.int32)
+        end, dist = np.zeros((n.value, 2)), np.zeros(n.value)
+        self._chk(self.L.rrtx_armik_get_records(self._a, status.ctypes.data, count.ctypes.data, end.ctypes.data, dist.ctypes.data,
+                                                None, None), "rrtx_armik_get_records")
+        return status, count, end, dist, m.value
+
+    def angles(self, n, n_angles):
+        """(offsets (n + 1,) int64, angles (n_angles,)) of the last run."""
+        off, ang = np.zeros(n + 1, dtype=np.int64), np.zeros(n_angles)
+        self._chk(self.L.rrtx_armik_get_angles(self._a, off.ctypes.data, ang.ctypes.data if n_angles else None, n_angles),
+                  "rrtx_armik_get_angles")
+        return off, ang
+
+    def trajectory(self, n):
+        """(step offsets (n + 1,), angle offsets (n + 1,), angles, distance) of the last move with arrays."""
+        so, ao = np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+        self._chk(self.L.rrtx_armik_get_trajectory(self._a, so.ctypes.data, ao.ctypes.data, None, None, 0, 0), "rrtx_armik_get_trajectory")
+        ang, dist = np.zeros(int(ao[n])), np.zeros(int(so[n]))
+        if len(dist):
+            self._chk(self.L.rrtx_armik_get_trajectory(self._a, None, None, ang.ctypes.data, dist.ctypes.data, len(dist), len(ang)),
+                      "rrtx_armik_get_trajectory")
+        return so, ao, ang, dist
+
+    def kernel_ms(self):
+        ms, w = C.c_double(), C.c_int32()
+        self._chk(self.L.rrtx_armik_get_kernel_ms(self._a, C.byref(ms), C.byref(w)), "rrtx_armik_get_kernel_ms")
+        return ms.value, w.value
 
 
 def rccl_unique_id():

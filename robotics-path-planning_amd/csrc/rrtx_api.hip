@@ -24,6 +24,7 @@
 #include "steer_batch.hip.h"
 #include "spline_batch.hip.h"
 #include "armnav_batch.hip.h"
+#include "armik_batch.hip.h"
 
 using rppk::Ctx;
 using rppk::Inst;
@@ -1737,3 +1738,4 @@ int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps) {
 #include "rrtx_api_tracker.inc"
 #include "rrtx_api_spline.inc"
 #include "rrtx_api_armnav.inc"
+#include "rrtx_api_armik.inc"

@@ -6,7 +6,8 @@ against `10_path_planning_01_rrt_04_rrt_star.py` runs after `from rrt_amd.rrt_04
 and `rrt_amd.lqr_path` do the same for the three stand-alone steering scripts (`plan_dubins_path`, `reeds_shepp_path_planning`,
 `LQRPlanner`), `rrt_amd.cubic_spline_path` for the cubic-spline script (`calc_spline_course`), `rrt_amd.bazier_path` for the
 Bezier script (`calc_4points_bezier_path`, `calc_bezier_path` and its pointwise helpers), `rrt_amd.arm_obstacle_navigation` for the
-arm script (`NLinkArm`, `get_occupancy_grid`, `astar_torus` and its helpers)."""
+arm script (`NLinkArm`, `get_occupancy_grid`, `astar_torus` and its helpers), `rrt_amd.simple_2d_inverse_kinematics` for the two
+planar inverse-kinematics scripts (`inverse_kinematics`, `forward_kinematics`, `jacobian_inverse`, `NLinkArm` and their helpers)."""
 import importlib
 import os
 import sys
@@ -21,6 +22,7 @@ steer = importlib.import_module("robotics-path-planning_amd.steer")
 track = importlib.import_module("robotics-path-planning_amd.track")
 spline = importlib.import_module("robotics-path-planning_amd.spline")
 armnav = importlib.import_module("robotics-path-planning_amd.armnav")
+armik = importlib.import_module("robotics-path-planning_amd.armik")
 RRT = _pkg.RRT
 RRTStar = _pkg.RRTStar
 RRTSobol = _pkg.RRTSobol
@@ -39,6 +41,9 @@ BatchSteer = _pkg.BatchSteer
 BatchTrack = _pkg.BatchTrack
 BatchSpline = _pkg.BatchSpline
 BatchArmNav = _pkg.BatchArmNav
+BatchArmIK = _pkg.BatchArmIK
+ArmIKResult = _pkg.ArmIKResult
+ArmMoveResult = _pkg.ArmMoveResult
 Node = _pkg.Node
 AreaBounds = _pkg.AreaBounds
 get_path_length = _pkg.get_path_length
