@@ -10,7 +10,8 @@
 // 16 B/node), cost[] f64, parent[] / prev_sib[] i32, kid[] (16-byte record Kid:
 // first child, next sibling, parent-edge length; child lists = the identity scans
 // of rrt_04:1369-1371 and :1381-1384 with integer parents), hits[] / stack[] i32
-// scratch.
+// scratch.  Plans of the rrt_04 iteration kernel add node[]: one 64-byte line per
+// node (rpp_node.h), that kernel's working format during a launch.
 //
 // Per-iteration phases (reference: 10_path_planning_01_rrt_04_rrt_star.py)
 //   sample        lane 0, MT19937 / Sobol                     :1132-1153
@@ -32,6 +33,7 @@
 #include <stdint.h>
 
 #include "rpp_core.h"
+#include "rpp_node.h"
 #include "rpp_rs.h"
 
 namespace rppk {
@@ -76,14 +78,6 @@ struct Inst {  // persistent per-instance state (global memory)
 #define PH_STORE(I) do { } while (0)
 #endif
 
-// What a tree walk reads of a node, in one 16-byte record (four to a 64-byte line): its first child, its next sibling
-// and elen = hypot(node - its parent), exactly the value calc_new_cost (rrt_04:1375-1377) would compute now.  elen is
-// kept by the rrt_04 iteration kernel only (Ctx::has_elen), so cost propagation needs no coordinates and no hypot.
-struct alignas(16) Kid {
-  int32_t first_child, next_sib;
-  double elen;
-};
-static_assert(sizeof(Kid) == 16 && alignof(Kid) == 16, "one node record is one aligned 16-byte load");
 // Head of a grid cell (Ctx::ghead): entry count and the number (+1, 0: none) of its overflow block
 struct alignas(8) GHead {
   int32_t cnt, blk;
@@ -142,6 +136,9 @@ struct Ctx {
   // of the members is part of the kernels' register budget: the launch context is loaded in aligned groups, and moving
   // a member shifts the SGPR spill counts of all three shapes (tools/loop_spill_check.sh)
   int32_t has_elen;
+  // one 64-byte line per node, stride x n_instances of them: plans of the rrt_04 iteration kernel only (allocated where
+  // has_elen is set; nullptr elsewhere).  No other kernel and no host getter sees it
+  Node* node;
 };
 constexpr int GRID_CAP0 = 16, GRID_CAP1 = 16;
 

@@ -16,10 +16,9 @@ __device__ __forceinline__ bool resolve_group(const Ctx& c, int grp, int n, doub
 }
 
 // h-th hit of a 16-bit pass (scan2q, the grid index, a ride): index from the LDS capture (else the global list),
-// coordinates gathered in f64
-__device__ __forceinline__ void hit_at2q(const double* __restrict__ x, const double* __restrict__ y,
-                                         const int32_t* __restrict__ hits, const Sh2& sh, int h, int& idx, double& hx,
-                                         double& hy) {
+// coordinates gathered in f64 from the node's line, one 16-byte load
+__device__ __forceinline__ void hit_at2q(const Node* nd, const int32_t* __restrict__ hits, const Sh2& sh, int h, int& idx,
+                                         double& hx, double& hy) {
   int k = 0;
 #pragma unroll
   for (int j = 0; j < NW - 1; j++) {
@@ -29,16 +28,15 @@ __device__ __forceinline__ void hit_at2q(const double* __restrict__ x, const dou
     }
   }
   idx = (h < HWF) ? reinterpret_cast<const int32_t*>(sh.u.hit)[k * HWF + h] : hits[sh.wave_start[k] + h];
-  hx = x[idx];
-  hy = y[idx];
+  const v2d xy = *reinterpret_cast<const v2d*>(&nd[idx].x);
+  hx = xy.x;
+  hy = xy.y;
 }
 
 // Exact re-check (dx**2 + dy**2 <= r**2 with the reference's libm pow) + the `.index` de-dup of rrt_04:1337,
-// producing the candidate records.  cost / first child of each distinct candidate are requested here and first
-// used after the edge evaluation.
-__device__ __forceinline__ void build_candidates(const double* __restrict__ x, const double* __restrict__ y,
-                                                 const double* __restrict__ cost, const Kid* __restrict__ kid,
-                                                 double qx, double qy,
+// producing the candidate records.  cost / first child of each distinct candidate are requested here (from the line the
+// coordinates came from) and first used after the edge evaluation.
+__device__ __forceinline__ void build_candidates(const Node* nd, double qx, double qy,
                                                  double thr_exact, const int32_t* hits, int kraw, Sh2& sh,
                                                  int& pend_p, double& pend_cost, int& pend_fc) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -69,7 +67,7 @@ __device__ __forceinline__ void build_candidates(const double* __restrict__ x, c
       double vf = 0.0, hx = 0.0, hy = 0.0;
       int st = 0;   // 0 outside, 1 inside, 2 in the band
       if (act) {
-        hit_at2q(x, y, hits, sh, h, idx, hx, hy);
+        hit_at2q(nd, hits, sh, h, idx, hx, hy);
         vf = rpp::fast_d2(hx - qx, hy - qy);
         st = vf <= thr_exact * (1.0 - FILTER_EPS) ? 1 : (vf > thr_exact * (1.0 + FILTER_EPS) ? 0 : 2);
         sh.cval[tid] = vf;
@@ -131,11 +129,11 @@ __device__ __forceinline__ void build_candidates(const double* __restrict__ x, c
             // single chunk (the common case): keep the two loads in flight, the caller stores them into the record
             // after the edge evaluation that does not need them
             pend_p = p;
-            pend_cost = cost[idx];
-            pend_fc = kid[idx].first_child;
+            pend_cost = nd[idx].cost;
+            pend_fc = nd[idx].k.first_child;
           } else {
-            sh.ucur[p] = cost[idx];
-            sh.ufc[p] = kid[idx].first_child;
+            sh.ucur[p] = nd[idx].cost;
+            sh.ufc[p] = nd[idx].k.first_child;
           }
         }
       }
@@ -163,7 +161,7 @@ __device__ __forceinline__ void build_candidates(const double* __restrict__ x, c
     double v = 0.0, hx = 0.0, hy = 0.0;
     bool valid = false;
     if (h < kraw) {
-      hit_at2q(x, y, hits, sh, h, idx, hx, hy);
+      hit_at2q(nd, hits, sh, h, idx, hx, hy);
       v = rpp::py_d2(hx - qx, hy - qy);
       valid = v <= thr_exact;
     }
@@ -214,11 +212,11 @@ __device__ __forceinline__ void build_candidates(const double* __restrict__ x, c
           // single chunk (the common case): keep the two loads in flight, the caller stores them into the record
           // after the edge evaluation that does not need them
           pend_p = p;
-          pend_cost = cost[idx];
-          pend_fc = kid[idx].first_child;
+          pend_cost = nd[idx].cost;
+          pend_fc = nd[idx].k.first_child;
         } else {
-          sh.ucur[p] = cost[idx];
-          sh.ufc[p] = kid[idx].first_child;
+          sh.ucur[p] = nd[idx].cost;
+          sh.ufc[p] = nd[idx].k.first_child;
         }
       }
     }

@@ -79,10 +79,9 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   const int64_t off = (int64_t)inst * c.stride;
   double* __restrict__ x = c.x + off;
   double* __restrict__ y = c.y + off;
-  double* __restrict__ cost = c.cost + off;
-  int32_t* parent = c.parent + off;
-  Kid* kid = c.kid + off;
-  int32_t* prev_sib = c.prev_sib + off;
+  // one line per node: cost, the links and elen live here during the launch (built from cost[], kid[], parent[],
+  // prev_sib[] below, written back to them at the end); x[], y[], xq[] stay current as arrays at every write too
+  Node* nd = c.node + off;
   int32_t* hits = c.hits + off;
   int32_t* stack = c.stack + off;
   uint32_t* __restrict__ xq = c.xq + off;
@@ -135,6 +134,28 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       gs.ok = 1;
       grid_build(gs, xq, x, y, n, gx, gy, first_goal);
     }
+  }
+  // the records of nodes [0, n) from the arrays, 64 nodes per wave and round (like the index: resume and re-plan need
+  // nothing else)
+  {
+    const double* cost = c.cost + off;
+    const Kid* kid = c.kid + off;
+    const int32_t* parent = c.parent + off;
+    const int32_t* prev_sib = c.prev_sib + off;
+    for (int i = tid; i < n; i += TPB) {
+      Node r;
+      r.k = kid[i];
+      r.cost = cost[i];
+      r.parent = parent[i];
+      r.prev_sib = prev_sib[i];
+      r.x = x[i];
+      r.y = y[i];
+      r.xq = xq[i];
+      r.pad[0] = r.pad[1] = r.pad[2] = 0u;
+      nd[i] = r;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // in L2 before a scalar load of another wave asks for them
+    lds_barrier();
   }
   if (tid == 0)
     for (int k = 0; k < 15; k++) sh.stat[k] = 0;
@@ -296,7 +317,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
             const int kc = scan2g<true, false>(gs, 0, xq, n, sq, (uint32_t)tb, 0u, hits, sh, d0, d1, d2);
             ST_ADD(S_SN, gs.nodes);
             ST_ADD(S_AB, gs.bytes + 16 * (int64_t)kc);
-            const auto at = [&](int h, int& idx, double& hx, double& hy) { hit_at2q(x, y, hits, sh, h, idx, hx, hy); };
+            const auto at = [&](int h, int& idx, double& hx, double& hy) { hit_at2q(nd, hits, sh, h, idx, hx, hy); };
             hit_argmin<true>(kc, at, [](double, double) { return true; },
                              [=](double hx, double hy) { return rpp::fast_d2(hx - rx, hy - ry); }, sh, gbest, ni, gsecond, nqx, nqy);
             if (gbest != 0.0 && gsecond <= gbest * (1.0 + FILTER_EPS)) {
@@ -635,7 +656,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       PH(4);
       int pend_p, pend_fc;
       double pend_cost;
-      build_candidates(x, y, cost, kid, nx, ny, r2, hits, kraw, sh, pend_p, pend_cost, pend_fc);
+      build_candidates(nd, nx, ny, r2, hits, kraw, sh, pend_p, pend_cost, pend_fc);
       PH(5);
       const int nu = sh.nu;
       int nvalid = sh.nvalid;
@@ -729,15 +750,15 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
             // stores of an earlier rewire of this iteration (sibling links, child lists) have reached L2
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             int par, pv, nxs;
-            sload3(parent + u, prev_sib + u, &kid[u].next_sib, par, pv, nxs);
+            sload_links(nd, u, par, pv, nxs);
             if (tid == 0) {
               // the identity re-pointing of :1369-1372 with integer links: leave the old parent's child list ...
               if (pv >= 0) {
-                kid[pv].next_sib = nxs;
+                nd[pv].k.next_sib = nxs;
               } else {
-                kid[par].first_child = nxs;
+                nd[par].k.first_child = nxs;
               }
-              if (nxs >= 0) prev_sib[nxs] = pv;
+              if (nxs >= 0) nd[nxs].prev_sib = pv;
             }
             if (pv < 0) {
 #pragma unroll
@@ -754,6 +775,9 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
                 x[u] = sh.e0.ex;
                 y[u] = sh.e0.ey;
                 xq[u] = rppk::quant16(c, sh.e0.ex, sh.e0.ey);
+                nd[u].x = sh.e0.ex;
+                nd[u].y = sh.e0.ey;
+                nd[u].xq = rppk::quant16(c, sh.e0.ex, sh.e0.ey);
                 // near_inds may hold an index AGAIN (nodes at equal distance collapse onto the first, :1337).  Once a
                 // node has moved, later visits are no longer void: the moved node is re-steered to where it lies now, and
                 // descendants whose cost rose may qualify on a repeated visit.  That raw-list walk lives in the general
@@ -768,9 +792,9 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
                 sh.moved = (u == first_goal || was_on_goal || (sh.e0.ex == gx && sh.e0.ey == gy))
                                ? 3 : (sh.moved | 1);   // 3: the bookkeeping of nodes lying on the goal is void
                 // its own edge and its children's edges changed length
-                kid[u].elen = rpp::py_hypot(sh.e0.ex - wx, sh.e0.ey - wy);
-                for (int ch = sh.ufc[es]; ch >= 0; ch = kid[ch].next_sib)
-                  kid[ch].elen = rpp::py_hypot(x[ch] - sh.e0.ex, y[ch] - sh.e0.ey);
+                nd[u].k.elen = rpp::py_hypot(sh.e0.ex - wx, sh.e0.ey - wy);
+                for (int ch = sh.ufc[es]; ch >= 0; ch = nd[ch].k.next_sib)
+                  nd[ch].k.elen = rpp::py_hypot(nd[ch].x - sh.e0.ex, nd[ch].y - sh.e0.ey);
               }
               if (NW == 1 && gs.ok) {   // the moved node changes cell (the index keeps it at the new xq[] value)
                 lds_barrier();
@@ -782,26 +806,26 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
             const double ec = sh.uval[es];
             const int root_fc = __builtin_amdgcn_readfirstlane(sh.ufc[es]);
             if (tid == 0) {
-              if (!moved_now) kid[u].elen = sh.uhyp[es];
-              cost[u] = ec;
+              if (!moved_now) nd[u].k.elen = sh.uhyp[es];
+              nd[u].cost = ec;
               sh.ucur[es] = ec;
               // ... and become a child of the node about to be appended
-              parent[u] = newidx;
-              prev_sib[u] = -1;
-              kid[u].next_sib = sh.last_fc;
-              if (sh.last_fc >= 0) prev_sib[sh.last_fc] = u;
+              nd[u].parent = newidx;
+              nd[u].prev_sib = -1;
+              nd[u].k.next_sib = sh.last_fc;
+              if (sh.last_fc >= 0) nd[sh.last_fc].prev_sib = u;
               sh.last_fc = u;
               sh.n_rw++;
             }
             if (moved_now) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the children's new elen
             PH(13);
             bool reread = false;
-            int np = propagate_scalar(cost, kid, root_fc, ec, sh, my_uidx,   // :1373
+            int np = propagate_scalar(nd, root_fc, ec, sh, my_uidx,   // :1373
                                       NW == 1 ? c.prop_vec : -1, NW == 1 ? c.prop_cap : (1 << 30), reread,
                                       (unsigned long long*)&I->phase[PROP_WALK_SLOT]);
             if (np < 0) {
               asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-              if (tid == 0) sh.fcount = rppk::propagate(x, y, cost, kid, stack, u);
+              if (tid == 0) sh.fcount = propagate_rec(nd, stack, u);
               np = sh.fcount;
               reread = true;
             }
@@ -809,7 +833,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
               // later candidates may be descendants of the node just rewired: refresh their costs
               asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
               for (int e = es + 1 + tid; e < nu; e += 64)
-                if (sh.uflag[e] & 2) sh.ucur[e] = cost[sh.uidx[e]];
+                if (sh.uflag[e] & 2) sh.ucur[e] = nd[sh.uidx[e]].cost;
             }
             if (tid == 0) sh.n_pr += np;
             PH(14);
@@ -822,15 +846,21 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
           x[newidx] = wx;
           y[newidx] = wy;
           xq[newidx] = rppk::quant16(c, wx, wy);
-          cost[newidx] = wcost;
           // link under the chosen parent; its current first child is in the LDS record (kept current above).  The node's
-          // own record in one store; elen == hypot(new - parent) from the position the node ends up at
+          // own line in one go; elen == hypot(new - parent) from the position the node ends up at
           const int f = sh.ufc[sel];
-          kid[newidx] = Kid{sh.last_fc, f, sh.uhyp[sel]};
-          parent[newidx] = wparent;
-          prev_sib[newidx] = -1;
-          if (f >= 0) prev_sib[f] = newidx;
-          kid[wparent].first_child = newidx;
+          Node r;
+          r.k = Kid{sh.last_fc, f, sh.uhyp[sel]};
+          r.cost = wcost;
+          r.parent = wparent;
+          r.prev_sib = -1;
+          r.x = wx;
+          r.y = wy;
+          r.xq = rppk::quant16(c, wx, wy);
+          r.pad[0] = r.pad[1] = r.pad[2] = 0u;
+          nd[newidx] = r;
+          if (f >= 0) nd[f].prev_sib = newidx;
+          nd[wparent].k.first_child = newidx;
         }
         // the index: an exact goal duplicate (first_goal >= 0 already) stays out of it, counted instead
         if (gs.ok) {
@@ -851,10 +881,13 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
           y[n] = ny;
           xq[n] = rppk::quant16(c, nx, ny);
           const double el = rpp::py_hypot(nx - nqx, ny - nqy);
-          kid[n].elen = el;
-          cost[n] = cost[ni] + el;   // :1054-1056
-          kid[n].first_child = -1;
-          rppk::link_child(parent, kid, prev_sib, n, ni);
+          nd[n].k.elen = el;
+          nd[n].cost = nd[ni].cost + el;   // :1054-1056
+          nd[n].k.first_child = -1;
+          nd[n].x = nx;
+          nd[n].y = ny;
+          nd[n].xq = rppk::quant16(c, nx, ny);
+          link_child_rec(nd, n, ni);
           sh.moved = 0;
         }
         if (gs.ok) {
@@ -949,7 +982,25 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   }
 
   // write back state; the final goal search (rrt_04:1080-1084) is done by the v1 kernel
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // lane 0's last stores into the records, before any lane reads them
   lds_barrier();
+  // cost, the links and elen of nodes [0, n) from the records to the arrays, whichever way the loop ended: the general
+  // kernel, the getters and a next launch read the arrays
+  {
+    double* __restrict__ cost = c.cost + off;
+    Kid* __restrict__ kid = c.kid + off;
+    int32_t* __restrict__ parent = c.parent + off;
+    int32_t* __restrict__ prev_sib = c.prev_sib + off;
+    for (int i = tid; i < n; i += TPB) {
+      const Kid k = nd[i].k;
+      const double ci = nd[i].cost;
+      const int pa = nd[i].parent, ps = nd[i].prev_sib;
+      kid[i] = k;
+      cost[i] = ci;
+      parent[i] = pa;
+      prev_sib[i] = ps;
+    }
+  }
   for (int i = tid; i < 624; i += TPB) I->rng.mt[i] = sh.rng.mt[i];
   if (tid == 0) {
     I->rng.pos = sh.rng.pos;

@@ -1,6 +1,7 @@
 using rppk::Ctx;
 using rppk::Inst;
 using rppk::Kid;
+using rppk::Node;
 using rppk::GHead;
 using rppk::FILTER_EPS;
 using rppk::v2d;

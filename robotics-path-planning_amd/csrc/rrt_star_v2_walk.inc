@@ -4,25 +4,23 @@
 // 0.35 - 0.4 us under the same load (tools/ubench/lat_ubench.hip, profiles/r2_lat_ubench.txt).  The pointer chases of
 // rewire -- a node's sibling links, the cost propagation over its subtree -- read one address at a time, so they run
 // on the scalar unit: s_load with glc (served by L2, never by a stale scalar-cache line; the scalar cache is not
-// coherent with vector stores).  The arrays are written by THIS wave's vector stores only, which reach L2 before
+// coherent with vector stores).  The records are written by THIS wave's vector stores only, which reach L2 before
 // `s_waitcnt vmcnt(0)` returns; the callers place that wait where an earlier store of the iteration could be read.
-__device__ __forceinline__ void sload3(const int32_t* pa, const int32_t* pb, const int32_t* pc, int& a, int& b,
-                                       int& c) {
-  uint32_t ra, rb, rc;
-  asm volatile(
-      "s_load_dword %0, %3, 0x0 glc\n\ts_load_dword %1, %4, 0x0 glc\n\ts_load_dword %2, %5, 0x0 glc\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&s"(ra), "=&s"(rb), "=&s"(rc)
-      : "s"(pa), "s"(pb), "s"(pc)
-      : "memory");
-  a = (int)ra;
-  b = (int)rb;
-  c = (int)rc;
+// the links of one node for a rewire -- parent, previous and next sibling -- in one scalar load of the 32-byte half that
+// holds them: one round trip on one line
+typedef uint32_t v8u __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void sload_links(const Node* nd, int node, int& par, int& pv, int& nxs) {
+  const Node* p = nd + node;
+  v8u r;
+  asm volatile("s_load_dwordx8 %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=&s"(r) : "s"(p) : "memory");
+  nxs = (int)r[1];
+  par = (int)r[6];
+  pv = (int)r[7];
 }
-// the record of one node: one scalar load, one round trip on one line
+// the walk record of one node (the first 16 bytes of its line): one scalar load, one round trip on one line
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void sload_node(const Kid* kid, int node, int& nxs, int& fcc, double& el) {
-  const Kid* p = kid + node;
+__device__ __forceinline__ void sload_node(const Node* nd, int node, int& nxs, int& fcc, double& el) {
+  const Node* p = nd + node;
   v4u r;
   asm volatile("s_load_dwordx4 %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=&s"(r) : "s"(p) : "memory");
   fcc = (int)r.x;
@@ -60,8 +58,7 @@ __device__ __forceinline__ int lanes_below(uint64_t m) {
 // round trips, each a dependent vector gather.  (cur, cp) and st[0, sp) are what the scalar walk left.  Returns the nodes
 // rewritten, or -1 when more than `cap` chains are pending.  Near candidates' LDS costs are not refreshed: the caller
 // re-reads them.
-__device__ __forceinline__ int propagate_lanes(double* __restrict__ cost, const Kid* kid, int cur, double cp, Sh2& sh,
-                                               int sp, int cap) {
+__device__ __forceinline__ int propagate_lanes(Node* nd, int cur, double cp, Sh2& sh, int sp, int cap) {
   const int lane = threadIdx.x & 63;
   WalkEnt* st = sh.u.walk;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // lane 0's stores of this rewire, before other lanes read
@@ -83,14 +80,14 @@ __device__ __forceinline__ int propagate_lanes(double* __restrict__ cost, const 
     int nxs = -1, fcc = -1;
     double el = 0.0;
     if (vn >= 0) {
-      const Kid k = kid[(uint32_t)vn];
+      const Kid k = nd[(uint32_t)vn].k;
       nxs = k.next_sib;
       fcc = k.first_child;
       el = k.elen;
     }
     const double vcp = sh.cval[lane];
     const double nc = vcp + el;   // calc_new_cost :1375-1377
-    if (vn >= 0) cost[(uint32_t)vn] = nc;
+    if (vn >= 0) nd[(uint32_t)vn].cost = nc;
     cnt += __popcll(act);
     const bool fork = fcc >= 0 && nxs >= 0;
     const uint64_t fm = __ballot(fork);
@@ -113,12 +110,12 @@ __device__ __forceinline__ int propagate_lanes(double* __restrict__ cost, const 
 // calc_new_cost :1375-1377), written by lane 0.  A descendant that is itself a near candidate of this iteration has
 // its LDS cost refreshed on the way (the sequential order of :1357-1373 reads it later); my_uidx[k] = index of the
 // candidate lane + 64 k (or -1).  A walk still running after vec_after nodes (>= 0) goes on with propagate_lanes, and
-// `reread` tells the caller to refresh the later candidates' LDS costs from cost[].  Returns the nodes rewritten, or -1
+// `reread` tells the caller to refresh the later candidates' LDS costs from the records.  Returns the nodes rewritten, or -1
 // when the sibling stack (LDS, at most cap entries) is full: the caller redoes the subtree with the global-stack walk
 // (recomputation is idempotent).
-__device__ __forceinline__ int propagate_scalar(double* __restrict__ cost, const Kid* kid, int root_fc, double root_cost,
-                                                Sh2& sh, const int (&my_uidx)[CE], int vec_after,
-                                                int cap, bool& reread, unsigned long long* walks) {
+__device__ __forceinline__ int propagate_scalar(Node* nd, int root_fc, double root_cost, Sh2& sh,
+                                                const int (&my_uidx)[CE], int vec_after, int cap, bool& reread,
+                                                unsigned long long* walks) {
   WalkEnt* st = sh.u.walk;
   constexpr int CAP = 2 * FCAP * (int)(sizeof(Front) / sizeof(WalkEnt));
   cap = min(cap, CAP);
@@ -136,15 +133,15 @@ __device__ __forceinline__ int propagate_scalar(double* __restrict__ cost, const
     }
     if (vec_after >= 0 && cnt >= vec_after) {
       reread = true;
-      const int r = propagate_lanes(cost, kid, cur, cp, sh, sp, cap);
+      const int r = propagate_lanes(nd, cur, cp, sh, sp, cap);
       if (lane == 0) atomicAdd(walks, r < 0 ? PROP_WALK_FULL : 1ull);   // no return value: nothing waits on it
       return r < 0 ? -1 : cnt + r;
     }
     int nxs, fcc;
     double el;
-    sload_node(kid, cur, nxs, fcc, el);
+    sload_node(nd, cur, nxs, fcc, el);
     const double nc = cp + el;   // calc_new_cost :1375-1377
-    if (lane == 0) cost[cur] = nc;
+    if (lane == 0) nd[cur].cost = nc;
 #pragma unroll
     for (int k = 0; k < CE; k++)
       if (my_uidx[k] == cur) sh.ucur[lane + 64 * k] = nc;
@@ -165,4 +162,34 @@ __device__ __forceinline__ int propagate_scalar(double* __restrict__ cost, const
     }
   }
   return cnt;
+}
+
+// The record forms of rppk::propagate and rppk::link_child (the general kernel and the other planners keep the array
+// forms).  The global-stack walk that redoes a subtree whose sibling stack ran full: one lane, explicit stack, every
+// descendant of `root` gets cost = parent cost + elen, the value calc_new_cost (rrt_04:1375-1377) computes.
+__device__ inline int propagate_rec(Node* nd, int32_t* __restrict__ stack, int root) {
+  int sp = 0, count = 0;
+  stack[sp++] = root;
+  while (sp) {
+    const int p = stack[--sp];
+    const double cp = nd[p].cost;
+    for (int ch = nd[p].k.first_child; ch >= 0; ch = nd[ch].k.next_sib) {
+      nd[ch].cost = cp + nd[ch].k.elen;
+      stack[sp++] = ch;
+      count++;
+    }
+  }
+  return count;
+}
+__device__ inline void link_child_rec(Node* nd, int ch, int par) {
+  nd[ch].parent = par;
+  nd[ch].prev_sib = -1;
+  if (par >= 0) {
+    const int f = nd[par].k.first_child;
+    nd[ch].k.next_sib = f;
+    if (f >= 0) nd[f].prev_sib = ch;
+    nd[par].k.first_child = ch;
+  } else {
+    nd[ch].k.next_sib = -1;
+  }
 }

@@ -340,6 +340,7 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
   if (p->algo == RRTX_ALGO_RRT_STAR && p->search_until_max_iter) {
     c.has_elen = 1;   // kid[].elen: cached parent-edge lengths (cost propagation)
     if ((rc = dalloc(h, &c.xq, tot))) return rc;     // 16-bit mirror (first stage of the streaming pass)
+    if ((rc = dalloc(h, &c.node, tot))) return rc;   // one 64-byte line per node: the iteration kernel's working format
     // grid index of the mirror (DESIGN 5.1 "grid index"): cells sized for about 6 nodes each at the final tree size,
     // 512 grid steps at the least (128 x 128 cells); an overflow block per 128 nodes of capacity
     int gsh = 9;

@@ -9,7 +9,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMMON = ["rrtx_api.hip", "rrtx_host.h", "rrtx_api_tools.inc", "rrtx_api_rccl.inc", "rrtx_api_steer.inc", "rrtx_api_tracker.inc",
-          "rrt_kernels.hip.h", "rpp_core.h", "glibc235_fma_math.h"]
+          "rrt_kernels.hip.h", "rpp_core.h", "rpp_node.h", "glibc235_fma_math.h"]
 FILES = {
     "c2": COMMON + ["rrt_star_v2.hip.h", "rrt_star_v2_body.inc"] + ["rrt_star_v2_%s.inc" % p for p in
                     ("shapes", "scan64", "q16", "grid", "cand", "walk", "kernel")],
