@@ -738,6 +738,76 @@ int rrtx_armik_get_trajectory(rrtx_armik* a, int64_t* step_offsets, int64_t* ang
 /* HIP-event time of the kernels of the last run (both passes of a move with arrays) and the waves it launched. */
 int rrtx_armik_get_kernel_ms(rrtx_armik* a, double* kernel_ms, int32_t* waves);
 
+/* ---- batched kinematics of n-link arms in 3-D given by Denavit-Hartenberg rows: forward kinematics with the Jacobian and the
+ * pose functions, and the Newton-Raphson / Levenberg-Marquardt inverse kinematics, without a planner
+ * (csrc/armdh_batch.hip.h, csrc/rpp_armdh.h) -----------------------------------------------------------------------------------
+ * forward_kinematics, rot2euler2, rot2euler, rot2quat, quat2rpy and inverse_kinematics of 01_forward_inverse_kinematics.py (and
+ * of its class-style twin 01_forward_inverse_kinematics_orig.py) for many queries in one call; every query has its own arm (1..8
+ * rows [theta, alpha, a, d], the classic DH matrix), joint angles and reference pose.  Forward kinematics, the Jacobian, the pose
+ * functions, diff_pose, K_zyz and the update are the reference's doubles; the step is this library's own definition (one-sided
+ * Jacobi SVD with numpy's cut for newton, Cholesky for lm), so solves agree with the reference's LAPACK steps to a
+ * measured tolerance away from singular poses and the fold of rot2euler2.
+ * The object is independent of the others; it owns its device buffers and reuses them.  One object serves one thread at a time. */
+typedef struct rrtx_armdh rrtx_armdh;
+
+#define RRTX_ARMDH_OK 0
+#define RRTX_ARMDH_NONFINITE 1        /* an angle became NaN or infinite, or a theta reached 105 414 357 rad, where the device's \
+                                         sin / cos end; the lane stopped there with the angles as they stand (forward: the \
+                                         record, the transforms and the Jacobian of the query are zero) */
+#define RRTX_ARMDH_NO_CONVERGENCE 2   /* newton: 30 Jacobi sweeps that all rotated; lm: a Cholesky pivot that is not > 0; the \
+                                         lane stopped before that step */
+#define RRTX_ARMDH_NEWTON 0
+#define RRTX_ARMDH_LM 1
+#define RRTX_ARMDH_MAX_LINKS 8
+#define RRTX_ARMDH_MAX_QUERIES 1048576LL   /* per call (2^20) */
+#define RRTX_ARMDH_MAX_ITERATIONS 1000000
+
+typedef struct rrtx_armdh_batch {
+  int64_t n_arms;
+  const int64_t* link_off;   /* n_arms + 1, CSR in links into dh */
+  const double* dh;          /* 4 doubles per link: theta, alpha, a, d */
+  int64_t n;                 /* queries */
+  const int32_t* arm;        /* n, the arm of each query; NULL: arm 0 */
+  const double* angles;      /* the joint angles that replace column 0, query after query, as many as the query's arm has links;
+                                NULL: the arms' own column 0 */
+  const double* ref_pose;    /* rrtx_armdh_solve only: n rows x, y, z, alpha, beta, gamma */
+} rrtx_armdh_batch;
+
+/* The object is handed out on RRTX_E_NO_DEVICE too (destroy it as usual): its calls then check their arguments and fail. */
+int rrtx_armdh_create(int32_t device, rrtx_armdh** out);
+void rrtx_armdh_destroy(rrtx_armdh* a);
+/* The message of the last call on `a` that failed; for a == NULL the last failure of a call of this thread that had no object. */
+const char* rrtx_armdh_last_error(rrtx_armdh* a);
+/* forward_kinematics(link_list) and the pose functions of the last transform for every query.  Returns RRTX_OK, or RRTX_PARTIAL
+ * when some status is not RRTX_ARMDH_OK (every other query is complete).  RRTX_E_INVALID, before any HIP call and also without a
+ * device: a NULL pointer (arm and angles may be NULL), n_arms < 1, an arm of no link or more than 8, a DH entry or angle that is
+ * not finite or above 1e6 in magnitude, n < 0 or > 2^20, arm[q] outside the arms. */
+int rrtx_armdh_forward(rrtx_armdh* a, const rrtx_armdh_batch* b);
+/* inverse_kinematics(iter_cnt, link_list, ref_ee_pose) without the drawing for every query: exactly iter_cnt trips of
+ * theta += step / step_div (200 in the script, 100 in its twin), method RRTX_ARMDH_NEWTON (the live code) or RRTX_ARMDH_LM (the
+ * variant of :423-428, eps its damping), then one more forward pass for the pose.  There is no convergence test, as in the
+ * reference.  Returns as rrtx_armdh_forward; RRTX_E_INVALID also for ref_pose NULL or an entry not finite or above 1e6,
+ * iter_cnt outside 1..1e6, step_div zero or not finite, a method other than the two, eps not > 0 or not finite with lm. */
+int rrtx_armdh_solve(rrtx_armdh* a, const rrtx_armdh_batch* b, int32_t iter_cnt, double step_div, int32_t method, double eps);
+/* Per query of the last call, any pointer may be NULL: status RRTX_ARMDH_*; values 16 doubles a query -- after a forward the
+ * position (3), rot2euler2 (3), rot2euler (3), rot2quat (4) and quat2rpy of it (3); after a solve the pose x, y, z, alpha, beta,
+ * gamma of the returned angles (6), pose_error = ref - pose (6) and 4 zeros; kappa_max (the largest sigma_1 / smallest kept
+ * sigma the solve met) and n_cut (the trips on which a singular value was cut), both of newton solves and 0 otherwise;
+ * n_queries and n_links, the number of links of all queries. */
+int rrtx_armdh_get_records(rrtx_armdh* a, int32_t* status, double* values, double* kappa_max, int32_t* n_cut, int64_t* n_queries,
+                           int64_t* n_links);
+/* The angles each query of the last solve ended with, as the script leaves them in link_list: offsets[n_queries + 1] into
+ * angles (cap = doubles available); either may be NULL.  After a forward only the offsets exist (angles: RRTX_E_STATE). */
+int rrtx_armdh_get_angles(rrtx_armdh* a, int64_t* offsets, double* angles, int64_t cap);
+/* The global transforms of the last forward, 16 doubles (4 x 4 row-major) per link, query after query in the offsets of
+ * rrtx_armdh_get_angles (cap = doubles available).  RRTX_E_STATE after a solve. */
+int rrtx_armdh_get_transforms(rrtx_armdh* a, double* transforms, int64_t cap);
+/* The Jacobians of the last forward: for query q the (6, N) matrix row-major at 6 * offsets[q] (cap = doubles available).
+ * RRTX_E_STATE after a solve. */
+int rrtx_armdh_get_jacobians(rrtx_armdh* a, double* jacobians, int64_t cap);
+/* HIP-event time of the kernel of the last call and the waves it launched. */
+int rrtx_armdh_get_kernel_ms(rrtx_armdh* a, double* kernel_ms, int32_t* waves);
+
 /* parity harness: out[i] = op(a[i], b[i]) evaluated on the device.  op 0 math.hypot, 1 x**2, 2 sin, 3 cos, 4 atan2,
  * 5 steer end x (rrt_04:1086-1115), 6 sqrt, 7 a/b, 8 acos, 9 asin, 10 checksum of the Reeds-Shepp steer
  * (0,0,0) -> (a, b, a+b) (rrt_06:1426-1441, csrc/rpp_rs.h), 11 math.tan(a) (|a| <= 0.79), 12 np.hypot(a, b) */

@@ -12,6 +12,7 @@ Reeds-Shepp curves between pose pairs), track (BatchTrack: batched closed-loop t
 spline (BatchSpline: batched cubic-spline courses through waypoints, the step from a path to a course),
 armnav (BatchArmNav: batched joint-space occupancy grids of a planar arm and searches on the torus grid),
 armik (BatchArmIK: batched Jacobian inverse kinematics of planar arms and the P-control move to the angles found),
+armdh (BatchArmDH: batched forward kinematics, Jacobians and 6-DoF inverse kinematics of DH arms in 3-D),
 _abi (ctypes binding of include/rrtx.h), csrc/ (HIP kernels + C ABI sources).
 """
 from . import _abi  # noqa: F401
@@ -22,5 +23,6 @@ from .track import BatchTrack  # noqa: F401
 from .spline import BatchSpline  # noqa: F401
 from .armnav import BatchArmNav  # noqa: F401
 from .armik import BatchArmIK, ArmIKResult, ArmMoveResult  # noqa: F401
+from .armdh import BatchArmDH, ArmDHResult, ArmDHForward  # noqa: F401
 
-__all__ = ["RRT", "RRTSobol", "RRTStar", "RRTStarDubins", "RRTDubins", "RRTStarReedsShepp", "BITStar", "InformedRRTStar", "LQRRRTStar", "ClosedLoopRRTStar", "BatchPlanner", "BatchSteer", "BatchTrack", "BatchSpline", "BatchArmNav", "BatchArmIK", "ArmIKResult", "ArmMoveResult", "Node", "AreaBounds", "get_path_length", "path_smoothing"]
+__all__ = ["RRT", "RRTSobol", "RRTStar", "RRTStarDubins", "RRTDubins", "RRTStarReedsShepp", "BITStar", "InformedRRTStar", "LQRRRTStar", "ClosedLoopRRTStar", "BatchPlanner", "BatchSteer", "BatchTrack", "BatchSpline", "BatchArmNav", "BatchArmIK", "ArmIKResult", "ArmMoveResult", "BatchArmDH", "ArmDHResult", "ArmDHForward", "Node", "AreaBounds", "get_path_length", "path_smoothing"]

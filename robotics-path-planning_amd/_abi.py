@@ -43,7 +43,10 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_armnav_get_grids", "rrtx_armnav_search", "rrtx_armnav_get_counts", "rrtx_armnav_get_routes",
            "rrtx_armnav_get_marks", "rrtx_armnav_get_kernel_ms",
            "rrtx_armik_create", "rrtx_armik_destroy", "rrtx_armik_last_error", "rrtx_armik_solve", "rrtx_armik_move",
-           "rrtx_armik_get_records", "rrtx_armik_get_angles", "rrtx_armik_get_trajectory", "rrtx_armik_get_kernel_ms"]
+           "rrtx_armik_get_records", "rrtx_armik_get_angles", "rrtx_armik_get_trajectory", "rrtx_armik_get_kernel_ms",
+           "rrtx_armdh_create", "rrtx_armdh_destroy", "rrtx_armdh_last_error", "rrtx_armdh_forward", "rrtx_armdh_solve",
+           "rrtx_armdh_get_records", "rrtx_armdh_get_angles", "rrtx_armdh_get_transforms", "rrtx_armdh_get_jacobians",
+           "rrtx_armdh_get_kernel_ms"]
 STEER_DUBINS, STEER_RS = 0, 1                                                      # include/rrtx.h: #define RRTX_STEER_*
 STEER_LQR = 2   # this binding's own name for "solved by rrtx_steer_solve_lqr": the C ABI has an entry point, not a kind value
 STEER_BEZIER = 3   # likewise: rrtx_steer_solve_bezier / rrtx_steer_solve_bezier_cp
@@ -60,6 +63,9 @@ ARMNAV_MAX_CELLS, ARMNAV_MAX_QUERIES = 1 << 28, 1 << 20
 ARMIK_FOUND, ARMIK_NOT_FOUND, ARMIK_NONFINITE, ARMIK_STEP_CAP = 0, 1, 2, 3                # #define RRTX_ARMIK_*
 ARMIK_MAX_LINKS, ARMIK_MAX_QUERIES, ARMIK_MAX_ITERATIONS, ARMIK_MAX_STEPS, ARMIK_MAX_TRAJECTORY = 16, 1 << 20, 1000000, 10000000, 1 << 28
 ARMIK_MAX_WAVES = 1 << 16
+ARMDH_OK, ARMDH_NONFINITE, ARMDH_NO_CONVERGENCE = 0, 1, 2                                 # #define RRTX_ARMDH_*
+ARMDH_NEWTON, ARMDH_LM = 0, 1
+ARMDH_MAX_LINKS, ARMDH_MAX_QUERIES, ARMDH_MAX_ITERATIONS = 8, 1 << 20, 1000000
 
 
 class Params(C.Structure):
@@ -117,6 +123,12 @@ class ArmIKBatch(C.Structure):
     """rrtx_armik_batch: the queries of one rrtx_armik_solve / rrtx_armik_move (pointers into arrays the caller keeps alive)."""
     _fields_ = [("n_arms", C.c_int64), ("link_off", C.c_void_p), ("link_len", C.c_void_p), ("n", C.c_int64), ("arm", C.c_void_p),
                 ("angles", C.c_void_p), ("goals", C.c_void_p), ("goal_angles", C.c_void_p), ("goal_dist", C.c_double)]
+
+
+class ArmDHBatch(C.Structure):
+    """rrtx_armdh_batch: the queries of one rrtx_armdh_forward / rrtx_armdh_solve (pointers into arrays the caller keeps alive)."""
+    _fields_ = [("n_arms", C.c_int64), ("link_off", C.c_void_p), ("dh", C.c_void_p), ("n", C.c_int64), ("arm", C.c_void_p),
+                ("angles", C.c_void_p), ("ref_pose", C.c_void_p)]
 
 
 class Stats(C.Structure):
@@ -257,8 +269,20 @@ def load():
     L.rrtx_armik_get_angles.argtypes = [vp, vp, vp, C.c_int64]
     L.rrtx_armik_get_trajectory.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int64]
     L.rrtx_armik_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i32)]
+    L.rrtx_armdh_create.argtypes = [i32, C.POINTER(vp)]
+    L.rrtx_armdh_destroy.argtypes = [vp]
+    L.rrtx_armdh_destroy.restype = None
+    L.rrtx_armdh_last_error.argtypes = [vp]
+    L.rrtx_armdh_last_error.restype = C.c_char_p
+    L.rrtx_armdh_forward.argtypes = [vp, C.POINTER(ArmDHBatch)]
+    L.rrtx_armdh_solve.argtypes = [vp, C.POINTER(ArmDHBatch), i32, C.c_double, i32, C.c_double]
+    L.rrtx_armdh_get_records.argtypes = [vp, vp, vp, vp, vp, i64p, i64p]
+    L.rrtx_armdh_get_angles.argtypes = [vp, vp, vp, C.c_int64]
+    L.rrtx_armdh_get_transforms.argtypes = [vp, vp, C.c_int64]
+    L.rrtx_armdh_get_jacobians.argtypes = [vp, vp, C.c_int64]
+    L.rrtx_armdh_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i32)]
     for f in EXPORTS:
-        if f not in ("rrtx_armik_destroy", "rrtx_armik_last_error", "rrtx_last_error", "rrtx_destroy", "rrtx_abi_version", "rrtx_device_count", "rrtx_steer_destroy",
+        if f not in ("rrtx_armdh_destroy", "rrtx_armdh_last_error", "rrtx_armik_destroy", "rrtx_armik_last_error", "rrtx_last_error", "rrtx_destroy", "rrtx_abi_version", "rrtx_device_count", "rrtx_steer_destroy",
                      "rrtx_steer_last_error", "rrtx_tracker_destroy", "rrtx_tracker_last_error", "rrtx_spline_destroy",
                      "rrtx_spline_last_error", "rrtx_armnav_destroy", "rrtx_armnav_last_error"):
             getattr(L, f).restype = C.c_int
@@ -1114,6 +1138,97 @@ class ArmIK:
     def kernel_ms(self):
         ms, w = C.c_double(), C.c_int32()
         self._chk(self.L.rrtx_armik_get_kernel_ms(self._a, C.byref(ms), C.byref(w)), "rrtx_armik_get_kernel_ms")
+        return ms.value, w.value
+
+
+class ArmDH:
+    """Thin RAII wrapper over rrtx_armdh* (batched forward and inverse kinematics of DH arms in 3-D); also a context manager.
+    It owns the device buffers of its calls."""
+
+    def __init__(self, device=0):
+        self.L = load()
+        self._a = C.c_void_p()
+        rc = self.L.rrtx_armdh_create(int(device), C.byref(self._a))
+        if rc != 0:
+            msg = self.L.rrtx_armdh_last_error(self._a).decode()
+            self.close()
+            raise RrtxError("rrtx_armdh_create: %s %s" % (ERRORS.get(rc, rc), msg))
+
+    def close(self):
+        if getattr(self, "_a", None):
+            self.L.rrtx_armdh_destroy(self._a)
+            self._a = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_armdh_last_error(self._a).decode()))
+        return rc
+
+    @staticmethod
+    def _batch(link_off, dh, arm, angles, n, ref_pose):
+        """Contiguous arrays: int64 link_off (n_arms + 1,), float64 dh (links, 4), int32 arm (n,) or None, float64 angles (flat,
+        query after query) or None, float64 ref_pose (n, 6) or None."""
+        b = ArmDHBatch()
+        b.n_arms, b.link_off, b.dh = len(link_off) - 1, link_off.ctypes.data, dh.ctypes.data
+        b.n, b.arm = int(n), None if arm is None else arm.ctypes.data
+        b.angles = None if angles is None else angles.ctypes.data
+        b.ref_pose = None if ref_pose is None else ref_pose.ctypes.data
+        return b
+
+    def forward(self, link_off, dh, arm, angles, n):
+        """Returns the call's code: 0, or RRTX_PARTIAL when some status is not ARMDH_OK."""
+        b = self._batch(link_off, dh, arm, angles, n, None)
+        return self._chk(self.L.rrtx_armdh_forward(self._a, C.byref(b)), "rrtx_armdh_forward")
+
+    def solve(self, link_off, dh, arm, angles, ref_pose, iter_cnt, step_div, method, eps):
+        b = self._batch(link_off, dh, arm, angles, len(ref_pose), ref_pose)
+        return self._chk(self.L.rrtx_armdh_solve(self._a, C.byref(b), int(iter_cnt), float(step_div), int(method), float(eps)),
+                         "rrtx_armdh_solve")
+
+    def records(self):
+        """(status int32 (n,), values (n, 16), kappa_max (n,), n_cut int32 (n,), n_links) of the last run."""
+        n, m = C.c_int64(), C.c_int64()
+        self._chk(self.L.rrtx_armdh_get_records(self._a, None, None, None, None, C.byref(n), C.byref(m)), "rrtx_armdh_get_records")
+        status, n_cut = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.int32)
+        values, kappa = np.zeros((n.value, 16)), np.zeros(n.value)
+        self._chk(self.L.rrtx_armdh_get_records(self._a, status.ctypes.data, values.ctypes.data, kappa.ctypes.data, n_cut.ctypes.data,
+                                                None, None), "rrtx_armdh_get_records")
+        return status, values, kappa, n_cut, m.value
+
+    def angles(self, n, n_links, want_angles=True):
+        """(offsets (n + 1,) int64, angles (n_links,) or None) of the last run."""
+        off = np.zeros(n + 1, dtype=np.int64)
+        ang = np.zeros(n_links) if want_angles else None
+        self._chk(self.L.rrtx_armdh_get_angles(self._a, off.ctypes.data, ang.ctypes.data if (want_angles and n_links) else None, n_links),
+                  "rrtx_armdh_get_angles")
+        return off, ang
+
+    def transforms(self, n_links):
+        t = np.zeros((n_links, 4, 4))
+        self._chk(self.L.rrtx_armdh_get_transforms(self._a, t.ctypes.data if n_links else None, t.size), "rrtx_armdh_get_transforms")
+        return t
+
+    def jacobians(self, n_links):
+        j = np.zeros(6 * n_links)
+        self._chk(self.L.rrtx_armdh_get_jacobians(self._a, j.ctypes.data if n_links else None, j.size), "rrtx_armdh_get_jacobians")
+        return j
+
+    def kernel_ms(self):
+        ms, w = C.c_double(), C.c_int32()
+        self._chk(self.L.rrtx_armdh_get_kernel_ms(self._a, C.byref(ms), C.byref(w)), "rrtx_armdh_get_kernel_ms")
         return ms.value, w.value
 
 

@@ -25,6 +25,7 @@
 #include "spline_batch.hip.h"
 #include "armnav_batch.hip.h"
 #include "armik_batch.hip.h"
+#include "armdh_batch.hip.h"
 
 using rppk::Ctx;
 using rppk::Inst;
@@ -1740,3 +1741,4 @@ int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps) {
 #include "rrtx_api_spline.inc"
 #include "rrtx_api_armnav.inc"
 #include "rrtx_api_armik.inc"
+#include "rrtx_api_armdh.inc"

@@ -7,7 +7,9 @@ and `rrt_amd.lqr_path` do the same for the three stand-alone steering scripts (`
 `LQRPlanner`), `rrt_amd.cubic_spline_path` for the cubic-spline script (`calc_spline_course`), `rrt_amd.bazier_path` for the
 Bezier script (`calc_4points_bezier_path`, `calc_bezier_path` and its pointwise helpers), `rrt_amd.arm_obstacle_navigation` for the
 arm script (`NLinkArm`, `get_occupancy_grid`, `astar_torus` and its helpers), `rrt_amd.simple_2d_inverse_kinematics` for the two
-planar inverse-kinematics scripts (`inverse_kinematics`, `forward_kinematics`, `jacobian_inverse`, `NLinkArm` and their helpers)."""
+planar inverse-kinematics scripts (`inverse_kinematics`, `forward_kinematics`, `jacobian_inverse`, `NLinkArm` and their helpers),
+`rrt_amd.forward_inverse_kinematics` and `rrt_amd.forward_inverse_kinematics_orig` for the two DH-arm scripts (`forward_kinematics`,
+`inverse_kinematics`, the pose functions; `Link`, `NLinkArm`)."""
 import importlib
 import os
 import sys
@@ -23,6 +25,7 @@ track = importlib.import_module("robotics-path-planning_amd.track")
 spline = importlib.import_module("robotics-path-planning_amd.spline")
 armnav = importlib.import_module("robotics-path-planning_amd.armnav")
 armik = importlib.import_module("robotics-path-planning_amd.armik")
+armdh = importlib.import_module("robotics-path-planning_amd.armdh")
 RRT = _pkg.RRT
 RRTStar = _pkg.RRTStar
 RRTSobol = _pkg.RRTSobol
@@ -44,6 +47,9 @@ BatchArmNav = _pkg.BatchArmNav
 BatchArmIK = _pkg.BatchArmIK
 ArmIKResult = _pkg.ArmIKResult
 ArmMoveResult = _pkg.ArmMoveResult
+BatchArmDH = _pkg.BatchArmDH
+ArmDHResult = _pkg.ArmDHResult
+ArmDHForward = _pkg.ArmDHForward
 Node = _pkg.Node
 AreaBounds = _pkg.AreaBounds
 get_path_length = _pkg.get_path_length
