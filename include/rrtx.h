@@ -604,6 +604,96 @@ int rrtx_spline_get_c(rrtx_spline* s, double* cx, double* cy, int64_t cap);
  * the last run had no obstacle list. */
 int rrtx_spline_get_hits(rrtx_spline* s, int32_t* hit);
 
+/* ---- batched interpolating B-spline courses of degree 1 .. 5 through waypoints (csrc/bspline_batch.hip.h, csrc/rpp_bspline.h)
+ * For every course of a batch: what interpolate_b_spline_path(x, y, n_path_points, degree) of 10_path_planning_00_bspline_path.py
+ * :59-108 returns -- x, y, heading, curvature -- (param NORMALISED, sample LINSPACE), or what the driver loop of
+ * 10_path_planning_00_spline_2d.py :45-54 collects from Spline2D(x, y, kind) (param CHORD, sample ARANGE, degree 1 / 2 / 3 for
+ * "linear" / "quadratic" / "cubic").  The reference's bit for bit: the waypoint parameter, the knot vector, the sample
+ * parameters, counts and offsets, and x and y of the linear kind.  The B-spline coefficients and the evaluation are this
+ * library's own definition (banded elimination without pivoting, Cox-de Boor recurrences in a stated order: csrc/rpp_bspline.h),
+ * because scipy's FITPACK is not one arithmetic; they agree with the reference to rounding.  The curvature keeps
+ * the script's exponent 2.0 / 3.0 (:107).  The smoothing fit (approximate_b_spline_path with s != 0) is not provided.
+ * The object is independent of rrtx_handle; it owns the device buffers of its runs and reuses them from call to call (they
+ * grow, never shrink).  One host thread per object.  Call order: create, run, the getters of that run, run again, as often as
+ * wanted; a getter before the first run returns RRTX_E_STATE. */
+typedef struct rrtx_bspline rrtx_bspline;
+/* per-course status */
+#define RRTX_BSPLINE_OK 0
+#define RRTX_BSPLINE_DEGENERATE 1   /* the waypoint parameter is not strictly increasing: two consecutive waypoints coincide (or
+                                       all do).  FITPACK and interp1d both raise.  The course owns no points. */
+#define RRTX_BSPLINE_TOO_FEW 2      /* waypoints <= degree: the reference raises.  The course owns no points. */
+#define RRTX_BSPLINE_PARAM_NORMALISED 0   /* _calc_distance_vector: scalar np.hypot per chord, np.cumsum, divided by the last */
+#define RRTX_BSPLINE_PARAM_CHORD 1        /* Spline2D.__calc_s: the chord length; degree 1 is interp1d's linear kind */
+#define RRTX_BSPLINE_SAMPLE_LINSPACE 0    /* np.linspace(0.0, u[-1], count) */
+#define RRTX_BSPLINE_SAMPLE_ARANGE 1      /* np.arange(0, s[-1], ds) */
+#define RRTX_BSPLINE_SAMPLE_EXPLICIT 2    /* the caller's sample parameters, a CSR list per course */
+#define RRTX_BSPLINE_MAX_DEGREE 5
+#define RRTX_BSPLINE_MAX_WAYPOINTS 4096       /* per course */
+#define RRTX_BSPLINE_MAX_POINTS 268435456LL   /* per call (2^28), over all courses */
+typedef struct rrtx_bspline_record {
+  int32_t status;     /* RRTX_BSPLINE_* */
+  int32_t degree;
+  int64_t n_points;   /* 0 unless status is RRTX_BSPLINE_OK */
+  double length;      /* the last waypoint parameter: 1.0 (NORMALISED) or s[-1] (CHORD); 0.0 unless status is RRTX_BSPLINE_OK */
+} rrtx_bspline_record;
+typedef struct rrtx_bspline_batch {
+  int64_t n;                    /* courses */
+  const int64_t* offsets;       /* n + 1, CSR into x / y */
+  const double *x, *y;          /* the waypoints */
+  const int32_t* degree;        /* one value, or n values when degree_per_course != 0; each 1 .. RRTX_BSPLINE_MAX_DEGREE */
+  int32_t degree_per_course;
+  int32_t param;                /* RRTX_BSPLINE_PARAM_* */
+  int32_t sample;               /* RRTX_BSPLINE_SAMPLE_*: the sampling mode of every course, unless sample_of is given */
+  int32_t sample_per_course;    /* count / ds: n values, else one */
+  const int32_t* sample_of;     /* NULL, or n values RRTX_BSPLINE_SAMPLE_*: a sampling mode per course (count, ds and u_offsets
+                                   are read only for the courses whose mode uses them) */
+  const int64_t* count;         /* LINSPACE: the number of points, each >= 1 */
+  const double* ds;             /* ARANGE: the step, each finite and > 0 */
+  const int64_t* u_offsets;     /* EXPLICIT: n + 1, CSR into u */
+  const double* u;              /* EXPLICIT: the sample parameters, finite; outside [0, length] the end piece is extended */
+  int32_t want_arrays;          /* 0: records (and hits) only, no point is stored */
+  int32_t reserved;
+  const double* obstacles;      /* rows (x, y, size) */
+  int64_t n_obstacles;          /* 0: no collision check; at most 2^20 */
+  double robot_radius;
+} rrtx_bspline_batch;
+/* As rrtx_spline_create: without a usable gfx950 device the return value is RRTX_E_NO_DEVICE and *out is still an object
+ * (to be destroyed like any other): its runs check their arguments and then return RRTX_E_NO_DEVICE. */
+int rrtx_bspline_create(int32_t device, rrtx_bspline** out);
+void rrtx_bspline_destroy(rrtx_bspline* s);
+/* The message of the last call on `s` that failed; for s == NULL the last failure of a call of this thread that had no object. */
+const char* rrtx_bspline_last_error(rrtx_bspline* s);
+/* Fits and samples every course.  With obstacles every point is tested as rrtx_spline_run tests it.  Returns RRTX_OK, or
+ * RRTX_PARTIAL when some record's status is not RRTX_BSPLINE_OK (every other course is complete).  n == 0 is a valid empty run.
+ * RRTX_E_INVALID, before any HIP call (also on a host without a device): a NULL pointer that the mode needs (obstacles may be
+ * NULL when n_obstacles is 0), n < 0 or n > 2^30, offsets (or u_offsets) that do not start at 0 or that decrease, a course of
+ * fewer than 2 or more than RRTX_BSPLINE_MAX_WAYPOINTS waypoints, a degree outside 1 .. 5, param or sample not one of the
+ * values above, a count < 1, a ds that is not finite or not > 0, a coordinate, sample parameter, obstacle entry or
+ * robot_radius that is not finite, a coordinate above 1e6 in magnitude, n_obstacles < 0 or > 2^20, or more than
+ * RRTX_BSPLINE_MAX_POINTS points in all (for ARANGE estimated before the run from the host's own hypot, one point of slack per
+ * course, and checked again on the counts the device returns).  After these checks a host without a device gets
+ * RRTX_E_NO_DEVICE. */
+int rrtx_bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b);
+/* rec: the n records of the last run; offsets (may be NULL): n + 1 entries, the exclusive sum of n_points; n_courses, n_points,
+ * n_knots (each may be NULL): the course count, offsets[n], and the knots of all courses.  rec may be NULL. */
+int rrtx_bspline_get_records(rrtx_bspline* s, rrtx_bspline_record* rec, int64_t* offsets, int64_t* n_courses, int64_t* n_points,
+                             int64_t* n_knots);
+/* The flat arrays of the last run, n_points doubles each, any pointer may be NULL: x, y, heading, curvature and the sample
+ * parameter, course after course (cap = doubles available in each; RRTX_E_CAPACITY when too small).  RRTX_E_STATE after a
+ * run with want_arrays == 0. */
+int rrtx_bspline_get_points(rrtx_bspline* s, double* x, double* y, double* yaw, double* k, double* u, int64_t cap);
+/* The splines of the last run, any pointer may be NULL.  knot_offsets: n + 1 entries, CSR into knots; a course whose status is
+ * RRTX_BSPLINE_OK has waypoints + degree + 1 knots, any other none (cap_knots = doubles available in knots).  cx, cy: the
+ * B-spline coefficients in the waypoint layout, offsets[n] doubles per axis, zeros for a course without a spline (cap_wp =
+ * doubles available in each). */
+int rrtx_bspline_get_coefficients(rrtx_bspline* s, int64_t* knot_offsets, double* knots, int64_t cap_knots, double* cx, double* cy,
+                                  int64_t cap_wp);
+/* Per course of the last run: -1 no point of the course touches an obstacle (free); j >= 0 the lowest index of the list any
+ * point touches; -2 the course owns no points, nothing was tested.  RRTX_E_STATE when the last run had no obstacle list. */
+int rrtx_bspline_get_hits(rrtx_bspline* s, int32_t* hit);
+/* HIP-event time of the kernels of the last run (fit and evaluation; the prefix sum between them is not kernel time) */
+int rrtx_bspline_get_kernel_ms(rrtx_bspline* s, double* kernel_ms);
+
 /* ---- batched arm navigation: joint-space occupancy grids and searches on the torus grid, without a planner
  * (csrc/armnav_batch.hip.h, csrc/rpp_armnav.h) ---------------------------------------------------------------------------------
  * The two functions of 02_arm_obstacle_navigation.py for many scenes and many queries in one call: get_occupancy_grid (:79-110)

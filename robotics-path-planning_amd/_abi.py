@@ -39,6 +39,8 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_tracker_get_counts", "rrtx_tracker_get_records", "rrtx_tracker_get_arrays", "rrtx_tracker_get_kernel_ms",
            "rrtx_spline_create", "rrtx_spline_destroy", "rrtx_spline_last_error", "rrtx_spline_run", "rrtx_spline_get_records",
            "rrtx_spline_get_points", "rrtx_spline_get_c", "rrtx_spline_get_hits",
+           "rrtx_bspline_create", "rrtx_bspline_destroy", "rrtx_bspline_last_error", "rrtx_bspline_run", "rrtx_bspline_get_records",
+           "rrtx_bspline_get_points", "rrtx_bspline_get_coefficients", "rrtx_bspline_get_hits", "rrtx_bspline_get_kernel_ms",
            "rrtx_armnav_create", "rrtx_armnav_destroy", "rrtx_armnav_last_error", "rrtx_armnav_occupancy", "rrtx_armnav_set_grids",
            "rrtx_armnav_get_grids", "rrtx_armnav_search", "rrtx_armnav_get_counts", "rrtx_armnav_get_routes",
            "rrtx_armnav_get_marks", "rrtx_armnav_get_kernel_ms",
@@ -57,6 +59,10 @@ RS_COST_EUCLID, RS_COST_PATH = 0, 1     # include/rrtx.h: #define RRTX_RS_COST_*
 TRACK_FAIL_REACH, TRACK_FAIL_ANGLE, TRACK_FAIL_LONG, TRACK_FAIL_COLLISION = 1, 2, 4, 8   # #define RRTX_TRACK_FAIL_*
 SPLINE_OK, SPLINE_DEGENERATE, SPLINE_REF_RAISES = 0, 1, 2                                # #define RRTX_SPLINE_*
 SPLINE_MAX_WAYPOINTS, SPLINE_MAX_POINTS = 4096, 1 << 28
+BSPLINE_OK, BSPLINE_DEGENERATE, BSPLINE_TOO_FEW = 0, 1, 2                                 # #define RRTX_BSPLINE_*
+BSPLINE_PARAM_NORMALISED, BSPLINE_PARAM_CHORD = 0, 1
+BSPLINE_SAMPLE_LINSPACE, BSPLINE_SAMPLE_ARANGE, BSPLINE_SAMPLE_EXPLICIT = 0, 1, 2
+BSPLINE_MAX_DEGREE, BSPLINE_MAX_WAYPOINTS, BSPLINE_MAX_POINTS = 5, 4096, 1 << 28
 ARMNAV_ROUTE, ARMNAV_NO_ROUTE = 0, 1                                                     # #define RRTX_ARMNAV_*
 ARMNAV_MIN_M, ARMNAV_MAX_M, ARMNAV_MAX_LINKS, ARMNAV_MAX_CIRCLES = 2, 128, 16, 1024
 ARMNAV_MAX_CELLS, ARMNAV_MAX_QUERIES = 1 << 28, 1 << 20
@@ -117,6 +123,18 @@ class SplineBatch(C.Structure):
     _fields_ = [("n", C.c_int64), ("offsets", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p), ("ds", C.c_void_p),
                 ("ds_per_course", C.c_int32), ("want_arrays", C.c_int32), ("cx", C.c_void_p), ("cy", C.c_void_p),
                 ("n_c", C.c_int64), ("obstacles", C.c_void_p), ("n_obstacles", C.c_int64), ("robot_radius", C.c_double)]
+
+
+BSPLINE_RECORD = np.dtype([("status", np.int32), ("degree", np.int32), ("n_points", np.int64), ("length", np.float64)])
+
+
+class BSplineBatch(C.Structure):
+    """rrtx_bspline_batch: the courses of one rrtx_bspline_run (pointers into arrays the caller keeps alive)."""
+    _fields_ = [("n", C.c_int64), ("offsets", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p), ("degree", C.c_void_p),
+                ("degree_per_course", C.c_int32), ("param", C.c_int32), ("sample", C.c_int32), ("sample_per_course", C.c_int32),
+                ("sample_of", C.c_void_p), ("count", C.c_void_p), ("ds", C.c_void_p), ("u_offsets", C.c_void_p), ("u", C.c_void_p),
+                ("want_arrays", C.c_int32), ("reserved", C.c_int32), ("obstacles", C.c_void_p), ("n_obstacles", C.c_int64),
+                ("robot_radius", C.c_double)]
 
 
 class ArmIKBatch(C.Structure):
@@ -245,6 +263,17 @@ def load():
     L.rrtx_spline_get_points.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64]
     L.rrtx_spline_get_c.argtypes = [vp, vp, vp, C.c_int64]
     L.rrtx_spline_get_hits.argtypes = [vp, vp]
+    L.rrtx_bspline_create.argtypes = [i32, C.POINTER(vp)]
+    L.rrtx_bspline_destroy.argtypes = [vp]
+    L.rrtx_bspline_destroy.restype = None
+    L.rrtx_bspline_last_error.argtypes = [vp]
+    L.rrtx_bspline_last_error.restype = C.c_char_p
+    L.rrtx_bspline_run.argtypes = [vp, C.POINTER(BSplineBatch)]
+    L.rrtx_bspline_get_records.argtypes = [vp, vp, vp, i64p, i64p, i64p]
+    L.rrtx_bspline_get_points.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64]
+    L.rrtx_bspline_get_coefficients.argtypes = [vp, vp, vp, C.c_int64, vp, vp, C.c_int64]
+    L.rrtx_bspline_get_hits.argtypes = [vp, vp]
+    L.rrtx_bspline_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.rrtx_armnav_create.argtypes = [i32, C.POINTER(vp)]
     L.rrtx_armnav_destroy.argtypes = [vp]
     L.rrtx_armnav_destroy.restype = None
@@ -284,7 +313,8 @@ def load():
     for f in EXPORTS:
         if f not in ("rrtx_armdh_destroy", "rrtx_armdh_last_error", "rrtx_armik_destroy", "rrtx_armik_last_error", "rrtx_last_error", "rrtx_destroy", "rrtx_abi_version", "rrtx_device_count", "rrtx_steer_destroy",
                      "rrtx_steer_last_error", "rrtx_tracker_destroy", "rrtx_tracker_last_error", "rrtx_spline_destroy",
-                     "rrtx_spline_last_error", "rrtx_armnav_destroy", "rrtx_armnav_last_error"):
+                     "rrtx_spline_last_error", "rrtx_armnav_destroy", "rrtx_armnav_last_error", "rrtx_bspline_destroy",
+                     "rrtx_bspline_last_error"):
             getattr(L, f).restype = C.c_int
     if L.rrtx_abi_version() != RRTX_ABI_VERSION:
         raise RrtxError("librrtx.so ABI version mismatch")
@@ -963,6 +993,78 @@ class Spline:
     def hits(self, n):
         hit = np.zeros(n, dtype=np.int32)
         self._chk(self.L.rrtx_spline_get_hits(self._s, hit.ctypes.data), "rrtx_spline_get_hits")
+        return hit
+
+
+class BSpline:
+    """Thin RAII wrapper over rrtx_bspline* (batched interpolating B-spline courses through waypoints); also a context
+    manager.  It owns the device buffers of its runs, so repeated runs reuse them."""
+
+    def __init__(self, device=0):
+        self.L = load()
+        self._s = C.c_void_p()
+        rc = self.L.rrtx_bspline_create(int(device), C.byref(self._s))
+        if rc != 0:
+            msg = self.L.rrtx_bspline_last_error(self._s).decode()
+            self.close()
+            raise RrtxError("rrtx_bspline_create: %s %s" % (ERRORS.get(rc, rc), msg))
+
+    def close(self):
+        if getattr(self, "_s", None):
+            self.L.rrtx_bspline_destroy(self._s)
+            self._s = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_bspline_last_error(self._s).decode()))
+        return rc
+
+    def run(self, batch):
+        """batch: BSplineBatch (its arrays are kept alive by the caller).  Returns 0 or RRTX_PARTIAL."""
+        return self._chk(self.L.rrtx_bspline_run(self._s, C.byref(batch)), "rrtx_bspline_run")
+
+    def records(self):
+        """(records (n,) BSPLINE_RECORD, offsets (n + 1,), n_knots, kernel_ms) of the last run."""
+        n, m, nk, ms = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
+        self._chk(self.L.rrtx_bspline_get_records(self._s, None, None, C.byref(n), C.byref(m), C.byref(nk)),
+                  "rrtx_bspline_get_records")
+        rec = np.zeros(n.value, dtype=BSPLINE_RECORD)
+        off = np.zeros(n.value + 1, dtype=np.int64)
+        self._chk(self.L.rrtx_bspline_get_records(self._s, rec.ctypes.data, off.ctypes.data, None, None, None),
+                  "rrtx_bspline_get_records")
+        self._chk(self.L.rrtx_bspline_get_kernel_ms(self._s, C.byref(ms)), "rrtx_bspline_get_kernel_ms")
+        return rec, off, nk.value, ms.value
+
+    def points(self, m):
+        """The five flat arrays x, y, yaw, k, u of the last run, m = offsets[-1] doubles each."""
+        arr = [np.zeros(m) for _ in range(5)]
+        self._chk(self.L.rrtx_bspline_get_points(self._s, *[q.ctypes.data for q in arr], m), "rrtx_bspline_get_points")
+        return arr
+
+    def coefficients(self, n, n_knots, w):
+        """(knot_offsets (n + 1,), knots, cx, cy) of the last run; w = waypoints of the batch."""
+        koff = np.zeros(n + 1, dtype=np.int64)
+        knots, cx, cy = np.zeros(n_knots), np.zeros(w), np.zeros(w)
+        self._chk(self.L.rrtx_bspline_get_coefficients(self._s, koff.ctypes.data, knots.ctypes.data, n_knots, cx.ctypes.data,
+                                                       cy.ctypes.data, w), "rrtx_bspline_get_coefficients")
+        return koff, knots, cx, cy
+
+    def hits(self, n):
+        hit = np.zeros(n, dtype=np.int32)
+        self._chk(self.L.rrtx_bspline_get_hits(self._s, hit.ctypes.data), "rrtx_bspline_get_hits")
         return hit
 
 

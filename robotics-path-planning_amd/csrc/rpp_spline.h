@@ -34,19 +34,32 @@ RPP_HD static inline double spline_pow(double x, double y) {
   return rpp_glibc_pow(x, y);
 }
 
-// One axis `a` (x or y) of one course of n >= 2 waypoints: the knots s (CubicSpline2D.__calc_s), then c -- copied from
-// c_in when given, else the Thomas recurrence above -- then b and d (:69-71).  s, b, c, d hold n doubles each; b[n-1]
-// and d[n-1] are zeroed (the reference's lists have n - 1 entries).  The forward sweep keeps cp in d and dp in c.
-// Returns kSplineOk or kSplineDegenerate (nothing but s is valid then).
-RPP_HD static inline int spline_fit_axis(const double* x, const double* y, const double* a, int n, const double* c_in,
-                                         double* s, double* b, double* c, double* d) {
-  // s = [0] + np.cumsum(np.hypot(np.diff(x), np.diff(y)))
+// s = [0] + np.cumsum(np.hypot(np.diff(x), np.diff(y))) of n >= 1 waypoints (CubicSpline2D.__calc_s; Spline2D.__calc_s of
+// 10_path_planning_00_spline_2d.py :19-23 is the same statement, and rpp_bspline.h takes it from here)
+RPP_HD static inline void spline_chord_sum(const double* x, const double* y, int n, double* s) {
   double acc = 0.0;
   s[0] = 0.0;
   for (int i = 0; i + 1 < n; i++) {
     acc = acc + rpp_glibc_hypot(x[i + 1] - x[i], y[i + 1] - y[i]);
     s[i + 1] = acc;
   }
+}
+
+// len(np.arange(0, s_end, ds)) for s_end > 0, ds > 0: ceil(s_end / ds) of the rounded quotient
+RPP_HD static inline int64_t arange_count(double s_end, double ds) {
+  const double q = s_end / ds;
+  int64_t k = (int64_t)q;
+  if ((double)k < q) k++;
+  return k;
+}
+
+// One axis `a` (x or y) of one course of n >= 2 waypoints: the knots s (CubicSpline2D.__calc_s), then c -- copied from
+// c_in when given, else the Thomas recurrence above -- then b and d (:69-71).  s, b, c, d hold n doubles each; b[n-1]
+// and d[n-1] are zeroed (the reference's lists have n - 1 entries).  The forward sweep keeps cp in d and dp in c.
+// Returns kSplineOk or kSplineDegenerate (nothing but s is valid then).
+RPP_HD static inline int spline_fit_axis(const double* x, const double* y, const double* a, int n, const double* c_in,
+                                         double* s, double* b, double* c, double* d) {
+  spline_chord_sum(x, y, n, s);
   for (int i = 0; i + 1 < n; i++)
     if (s[i + 1] - s[i] == 0.0) return kSplineDegenerate;
   if (c_in) {
@@ -81,13 +94,11 @@ RPP_HD static inline int spline_fit_axis(const double* x, const double* y, const
   return kSplineOk;
 }
 
-// len(np.arange(0, s_end, ds)) for s_end > 0, ds > 0: ceil(s_end / ds) of the rounded quotient.  Sample k is
+// arange_count, with the reference's failure: sample k is
 // 0 + k * ds (numpy fills start + i * delta with delta = (0 + ds) - 0).  *status becomes kSplineRefRaises, and the
 // count 0, when the last sample is not below s_end: bisect then lands on the last knot and the reference's b[i] raises.
 RPP_HD static inline int64_t spline_count(double s_end, double ds, int* status) {
-  const double q = s_end / ds;
-  int64_t k = (int64_t)q;
-  if ((double)k < q) k++;
+  const int64_t k = arange_count(s_end, ds);
   if (k > 0 && (double)(k - 1) * ds >= s_end) {
     *status = kSplineRefRaises;
     return 0;

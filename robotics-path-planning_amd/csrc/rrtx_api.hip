@@ -23,6 +23,7 @@
 #include "rrt_track.hip.h"
 #include "steer_batch.hip.h"
 #include "spline_batch.hip.h"
+#include "bspline_batch.hip.h"
 #include "armnav_batch.hip.h"
 #include "armik_batch.hip.h"
 #include "armdh_batch.hip.h"
@@ -1739,6 +1740,7 @@ int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps) {
 #include "rrtx_api_steer.inc"
 #include "rrtx_api_tracker.inc"
 #include "rrtx_api_spline.inc"
+#include "rrtx_api_bspline.inc"
 #include "rrtx_api_armnav.inc"
 #include "rrtx_api_armik.inc"
 #include "rrtx_api_armdh.inc"

@@ -1,0 +1,336 @@
+// rrtx_api_bspline.inc -- rrtx_bspline_*: batched interpolating B-spline courses through waypoints (bspline_batch.hip.h:
+// bspline_fit_kernel, bspline_eval_kernel); included by rrtx_api.hip
+struct rrtx_bspline : DevObj {
+  // device buffers, grown on demand
+  DevBuf wp_off, x, y, degree, mode_of, count, ds, us_off, us, tab, knots, rec, pt_off, out, obs, hit;
+  // the last run
+  bool ran = false, has_arrays = false, has_hits = false;
+  int64_t n = 0, n_wp = 0, n_points = 0, n_knots = 0;
+  double kernel_ms = 0.0;
+  std::vector<rppbs::Record> h_rec;
+  std::vector<int64_t> h_off, h_wp_off, h_knot_off;
+  std::vector<int32_t> h_hit;
+};
+
+static_assert(sizeof(rppbs::Record) == sizeof(rrtx_bspline_record), "rrtx_bspline_record mirrors rppbs::Record");
+static_assert(rppbs::MAX_WAYPOINTS == RRTX_BSPLINE_MAX_WAYPOINTS, "the waypoint limit of the header is the kernel's");
+static_assert(rpp::kBsplineMaxDegree == RRTX_BSPLINE_MAX_DEGREE, "the degree limit of the header is the core's");
+static_assert(rpp::kBsplineOk == RRTX_BSPLINE_OK && rpp::kBsplineDegenerate == RRTX_BSPLINE_DEGENERATE &&
+                  rpp::kBsplineTooFew == RRTX_BSPLINE_TOO_FEW,
+              "the statuses of the header are the core's");
+static_assert(rpp::kBsplineNormalised == RRTX_BSPLINE_PARAM_NORMALISED && rpp::kBsplineChord == RRTX_BSPLINE_PARAM_CHORD &&
+                  rpp::kBsplineLinspace == RRTX_BSPLINE_SAMPLE_LINSPACE && rpp::kBsplineArange == RRTX_BSPLINE_SAMPLE_ARANGE &&
+                  rpp::kBsplineExplicit == RRTX_BSPLINE_SAMPLE_EXPLICIT,
+              "the modes of the header are the core's");
+
+template <bool STORE, bool CHECK>
+static void bspline_launch_eval(int64_t total, hipStream_t stream, const rppbs::Args& a) {
+  const unsigned blocks = (unsigned)((total + rppbs::TPB - 1) / rppbs::TPB);
+  hipLaunchKernelGGL((rppbs::bspline_eval_kernel<STORE, CHECK>), dim3(blocks), dim3(rppbs::TPB), 0, stream, a);
+}
+
+static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b) {
+  const char* fn = "rrtx_bspline_run: ";
+  auto bad = [&](const char* m) { return fail(s, RRTX_E_INVALID, std::string(fn) + m); };
+  if (!s) return bad("the bspline object is NULL");
+  if (!b) return bad("the batch is NULL");
+  if (b->n < 0 || b->n > (1LL << 30)) return bad("n is negative or above 2^30");
+  if (!b->offsets || !b->degree) return bad("offsets or degree is NULL");
+  if (b->param != RRTX_BSPLINE_PARAM_NORMALISED && b->param != RRTX_BSPLINE_PARAM_CHORD) return bad("param is not RRTX_BSPLINE_PARAM_*");
+  if (b->sample < RRTX_BSPLINE_SAMPLE_LINSPACE || b->sample > RRTX_BSPLINE_SAMPLE_EXPLICIT) return bad("sample is not RRTX_BSPLINE_SAMPLE_*");
+  const int64_t n = b->n;
+  if (!csr_ok(b->offsets, n)) return bad("offsets do not start at 0 or decrease");
+  const int64_t W = b->offsets[n];
+  if (W > 0 && (!b->x || !b->y)) return bad("x or y is NULL");
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t m = b->offsets[i + 1] - b->offsets[i];
+    if (m < 2) return bad("a course of fewer than 2 waypoints");
+    if (m > RRTX_BSPLINE_MAX_WAYPOINTS) return bad("a course of more than 4096 waypoints");
+  }
+  const int64_t n_deg = b->degree_per_course ? n : 1;
+  for (int64_t i = 0; i < n_deg; i++)
+    if (b->degree[i] < 1 || b->degree[i] > RRTX_BSPLINE_MAX_DEGREE) return bad("a degree is not 1 .. 5");
+  if (b->n_obstacles < 0 || b->n_obstacles > (1LL << 20)) return bad("n_obstacles is negative or above 2^20");
+  if (b->n_obstacles > 0 && !b->obstacles) return bad("obstacles is NULL");
+  if (!all_finite(b->x, W) || !all_finite(b->y, W)) return bad("a coordinate is not finite");
+  for (int64_t i = 0; i < W; i++)
+    if (std::fabs(b->x[i]) > 1.0e6 || std::fabs(b->y[i]) > 1.0e6) return bad("a coordinate is above 1e6 in magnitude");
+  if (!all_finite(b->obstacles, 3 * b->n_obstacles)) return bad("an obstacle entry is not finite");
+  if (!std::isfinite(b->robot_radius)) return bad("robot_radius is not finite");
+  // the sampling modes' own arguments, and the points in all
+  auto mode_of = [&](int64_t i) { return b->sample_of ? b->sample_of[i] : b->sample; };
+  bool any_lin = false, any_ara = false, any_exp = false;
+  for (int64_t i = 0; i < n; i++) {
+    const int mo = mode_of(i);
+    if (mo < RRTX_BSPLINE_SAMPLE_LINSPACE || mo > RRTX_BSPLINE_SAMPLE_EXPLICIT) return bad("a sample_of entry is not RRTX_BSPLINE_SAMPLE_*");
+    any_lin |= mo == RRTX_BSPLINE_SAMPLE_LINSPACE;
+    any_ara |= mo == RRTX_BSPLINE_SAMPLE_ARANGE;
+    any_exp |= mo == RRTX_BSPLINE_SAMPLE_EXPLICIT;
+  }
+  if (any_lin && !b->count) return bad("count is NULL");
+  if (any_ara && !b->ds) return bad("ds is NULL");
+  if (any_exp && !b->u_offsets) return bad("u_offsets is NULL");
+  const int64_t n_smp = b->sample_per_course ? n : 1;
+  int64_t n_us = 0;
+  if (any_exp) {
+    if (!csr_ok(b->u_offsets, n)) return bad("u_offsets do not start at 0 or decrease");
+    n_us = b->u_offsets[n];
+    if (n_us > RRTX_BSPLINE_MAX_POINTS) return bad("more than 2^28 points in all");
+    if (n_us > 0 && !b->u) return bad("u is NULL");
+    if (!all_finite(b->u, n_us)) return bad("a sample parameter is not finite");
+  }
+  double est = 0.0;
+  const char* many = "more than 2^28 points in all";
+  for (int64_t i = 0; i < n; i++) {
+    const int mo = mode_of(i);
+    const int64_t j = b->sample_per_course ? i : 0;
+    if (mo == RRTX_BSPLINE_SAMPLE_LINSPACE) {
+      if (b->count[j] < 1) return bad("an n_path_points (count) is below 1");
+      est += (double)b->count[j];
+    } else if (mo == RRTX_BSPLINE_SAMPLE_ARANGE) {
+      if (!std::isfinite(b->ds[j]) || !(b->ds[j] > 0.0)) return bad("a ds is not finite or not > 0");
+      double len = 0.0;   // from the host's own hypot: one point of slack per course against the device's sum
+      for (int64_t k = b->offsets[i]; k + 1 < b->offsets[i + 1]; k++) len += libm_hypot(b->x[k + 1] - b->x[k], b->y[k + 1] - b->y[k]);
+      if (b->param == RRTX_BSPLINE_PARAM_NORMALISED) len = 1.0;
+      est += std::ceil(len / b->ds[j]) + 1.0;
+    } else {
+      est += (double)(b->u_offsets[i + 1] - b->u_offsets[i]);
+    }
+    if (est > (double)RRTX_BSPLINE_MAX_POINTS + (double)n) return bad(many);
+  }
+  if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+
+  s->ran = false;
+  s->has_arrays = false;
+  s->has_hits = false;
+  s->n = n;
+  s->n_wp = W;
+  s->n_points = 0;
+  s->n_knots = 0;
+  s->kernel_ms = 0.0;
+  s->h_rec.clear();
+  s->h_hit.clear();
+  s->h_off.assign((size_t)n + 1, 0);
+  s->h_knot_off.assign((size_t)n + 1, 0);
+  s->h_wp_off.assign(b->offsets, b->offsets + n + 1);
+  if (n == 0) {
+    s->has_arrays = b->want_arrays != 0;
+    s->has_hits = b->n_obstacles > 0;
+    s->ran = true;
+    return RRTX_OK;
+  }
+  // obstacle table: packed rows (ox, oy, thr), thr = (size + robot_radius) ** 2 by the planners' routine
+  const int64_t n_obs = b->n_obstacles;
+  std::vector<double> rows(3 * (size_t)n_obs);
+  for (int64_t k = 0; k < n_obs; k++) {
+    rows[3 * k] = b->obstacles[3 * k];
+    rows[3 * k + 1] = b->obstacles[3 * k + 1];
+    rows[3 * k + 2] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius);
+  }
+
+  HIPCHK(s, hipSetDevice(s->device));
+  int rc;
+  const size_t N = (size_t)n;
+  if ((rc = s->upload(s->wp_off, b->offsets, sizeof(int64_t) * (N + 1)))) return rc;
+  if ((rc = s->upload(s->x, b->x, sizeof(double) * (size_t)W))) return rc;
+  if ((rc = s->upload(s->y, b->y, sizeof(double) * (size_t)W))) return rc;
+  if ((rc = s->upload(s->degree, b->degree, sizeof(int32_t) * (size_t)n_deg))) return rc;
+  if (b->sample_of && (rc = s->upload(s->mode_of, b->sample_of, sizeof(int32_t) * N))) return rc;
+  if (any_lin && (rc = s->upload(s->count, b->count, sizeof(int64_t) * (size_t)n_smp))) return rc;
+  if (any_ara && (rc = s->upload(s->ds, b->ds, sizeof(double) * (size_t)n_smp))) return rc;
+  if (any_exp) {
+    if ((rc = s->upload(s->us_off, b->u_offsets, sizeof(int64_t) * (N + 1)))) return rc;
+    if ((rc = s->upload(s->us, b->u, sizeof(double) * (size_t)n_us))) return rc;
+  }
+  if ((rc = s->upload(s->obs, rows.data(), sizeof(double) * rows.size()))) return rc;
+  if ((rc = s->reserve(s->tab, sizeof(double) * rppbs::TAB_PLANES * (size_t)W))) return rc;
+  if ((rc = s->reserve(s->knots, sizeof(double) * ((size_t)W + rppbs::KNOT_SLACK * N)))) return rc;
+  if ((rc = s->reserve(s->rec, sizeof(rppbs::Record) * N))) return rc;
+  if (n_obs > 0 && (rc = s->reserve(s->hit, sizeof(int32_t) * N))) return rc;
+
+  rppbs::Args a;
+  memset(&a, 0, sizeof(a));
+  a.n = n;
+  a.W = W;
+  a.wp_off = s->wp_off.as<const int64_t>();
+  a.x = s->x.as<const double>();
+  a.y = s->y.as<const double>();
+  a.degree = s->degree.as<const int32_t>();
+  a.degree_per_course = b->degree_per_course != 0;
+  a.param = b->param;
+  a.mode = b->sample;
+  a.mode_of = b->sample_of ? s->mode_of.as<const int32_t>() : nullptr;
+  a.per_course = b->sample_per_course != 0;
+  a.count = s->count.as<const int64_t>();
+  a.ds = s->ds.as<const double>();
+  a.us_off = s->us_off.as<const int64_t>();
+  a.us = s->us.as<const double>();
+  a.tab = s->tab.as<double>();
+  a.knots = s->knots.as<double>();
+  a.rec = s->rec.as<rppbs::Record>();
+  a.hit = n_obs > 0 ? s->hit.as<int32_t>() : nullptr;
+
+  // the fit, and its records
+  s->h_rec.resize(N);
+  float ms = 0.f;
+  const unsigned fit_blocks = (unsigned)((n + rppbs::FIT_TPB - 1) / rppbs::FIT_TPB);
+  rc = s->timed(&ms, [&] { hipLaunchKernelGGL(rppbs::bspline_fit_kernel, dim3(fit_blocks), dim3(rppbs::FIT_TPB), 0, s->stream, a); },
+                [&]() -> int {
+                  HIPCHK(s, hipMemcpyAsync(s->h_rec.data(), s->rec.p, sizeof(rppbs::Record) * N, hipMemcpyDeviceToHost, s->stream));
+                  return RRTX_OK;
+                });
+  if (rc) return rc;
+  s->kernel_ms = ms;
+
+  // offsets: exclusive sums of the point counts and of the knot counts
+  int64_t tot = 0, knots = 0;
+  bool partial = false;
+  for (size_t i = 0; i < N; i++) {
+    s->h_off[i] = tot;
+    s->h_knot_off[i] = knots;
+    if (s->h_rec[i].status != RRTX_BSPLINE_OK) partial = true;
+    else knots += (b->offsets[i + 1] - b->offsets[i]) + s->h_rec[i].degree + 1;
+    tot += s->h_rec[i].n_points;
+    if (tot > RRTX_BSPLINE_MAX_POINTS) return bad(many);
+  }
+  s->h_off[N] = tot;
+  s->h_knot_off[N] = knots;
+  s->n_points = tot;
+  s->n_knots = knots;
+
+  const bool store = b->want_arrays != 0, check = n_obs > 0;
+  if (check) s->h_hit.resize(N);
+  if (tot > 0 && (store || check)) {
+    if (store && (rc = s->reserve(s->out, sizeof(double) * 5 * (size_t)tot))) return rc;
+    if ((rc = s->upload(s->pt_off, s->h_off.data(), sizeof(int64_t) * (N + 1)))) return rc;
+    a.pt_off = s->pt_off.as<const int64_t>();
+    a.out = store ? s->out.as<double>() : nullptr;
+    a.obs = check ? s->obs.as<const double>() : nullptr;
+    a.n_obs = n_obs;
+    rc = s->timed(&ms, [&] {
+      if (store && check)
+        bspline_launch_eval<true, true>(tot, s->stream, a);
+      else if (store)
+        bspline_launch_eval<true, false>(tot, s->stream, a);
+      else
+        bspline_launch_eval<false, true>(tot, s->stream, a);
+    }, [&]() -> int {
+      if (check) HIPCHK(s, hipMemcpyAsync(s->h_hit.data(), s->hit.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
+      return RRTX_OK;
+    });
+    if (rc) return rc;
+    s->kernel_ms += ms;
+  } else if (check) {
+    HIPCHK(s, hipMemcpy(s->h_hit.data(), s->hit.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  }
+  s->has_arrays = store;
+  s->has_hits = check;
+  s->ran = true;
+  if (partial) {
+    s->err = std::string(fn) + "some courses have coinciding waypoints, or no more waypoints than their degree (see the status column)";
+    return RRTX_PARTIAL;
+  }
+  return RRTX_OK;
+}
+
+extern "C" {
+
+int rrtx_bspline_create(int32_t device, rrtx_bspline** out) {
+  if (!out) return fail<rrtx_bspline>(nullptr, RRTX_E_INVALID, "rrtx_bspline_create: out is NULL");
+  *out = nullptr;
+  if (device < 0) return fail<rrtx_bspline>(nullptr, RRTX_E_INVALID, "rrtx_bspline_create: negative device ordinal");
+  rrtx_bspline* s = new (std::nothrow) rrtx_bspline();
+  if (!s) return fail<rrtx_bspline>(nullptr, RRTX_E_HIP, "rrtx_bspline_create: out of host memory");
+  *out = s;   // returned on failure too: the caller reads the message, and runs still check their arguments
+  return s->open(device, "rrtx_bspline_create");
+}
+
+void rrtx_bspline_destroy(rrtx_bspline* s) {
+  if (!s) return;
+  if (s->usable) hipSetDevice(s->device);
+  delete s;   // the buffers, then the events and the stream
+}
+
+const char* rrtx_bspline_last_error(rrtx_bspline* s) { return s ? s->err.c_str() : null_object_err.c_str(); }
+
+int rrtx_bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b) {
+  try {   // host allocations (records, offsets, messages) must not throw across the ABI
+    return bspline_run(s, b);
+  } catch (const std::exception& e) {
+    if (s) s->ran = false;
+    return fail(s, RRTX_E_HIP, std::string("rrtx_bspline_run: ") + e.what());
+  }
+}
+
+int rrtx_bspline_get_records(rrtx_bspline* s, rrtx_bspline_record* rec, int64_t* offsets, int64_t* n_courses, int64_t* n_points,
+                             int64_t* n_knots) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_bspline_get_records: the bspline object is NULL");
+  if (!s->ran) return fail(s, RRTX_E_STATE, "rrtx_bspline_get_records: no completed run");
+  if (rec && s->n) memcpy(rec, s->h_rec.data(), sizeof(rrtx_bspline_record) * (size_t)s->n);
+  if (offsets) memcpy(offsets, s->h_off.data(), sizeof(int64_t) * ((size_t)s->n + 1));
+  if (n_courses) *n_courses = s->n;
+  if (n_points) *n_points = s->n_points;
+  if (n_knots) *n_knots = s->n_knots;
+  return RRTX_OK;
+}
+
+int rrtx_bspline_get_points(rrtx_bspline* s, double* x, double* y, double* yaw, double* k, double* u, int64_t cap) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_bspline_get_points: the bspline object is NULL");
+  if (!s->ran || !s->has_arrays) return fail(s, RRTX_E_STATE, "rrtx_bspline_get_points: no completed run with arrays");
+  if (cap < s->n_points) return fail(s, RRTX_E_CAPACITY, "rrtx_bspline_get_points: the buffers are too small");
+  if (s->n_points == 0) return RRTX_OK;
+  const size_t tot = (size_t)s->n_points;
+  HIPCHK(s, hipSetDevice(s->device));
+  double* dst[5] = {x, y, yaw, k, u};
+  for (int q = 0; q < 5; q++)
+    if (dst[q]) HIPCHK(s, hipMemcpy(dst[q], s->out.as<const double>() + q * tot, sizeof(double) * tot, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+int rrtx_bspline_get_coefficients(rrtx_bspline* s, int64_t* knot_offsets, double* knots, int64_t cap_knots, double* cx, double* cy,
+                                  int64_t cap_wp) {
+  const char* fn = "rrtx_bspline_get_coefficients: ";
+  if (!s) return fail(s, RRTX_E_INVALID, std::string(fn) + "the bspline object is NULL");
+  if (!s->ran) return fail(s, RRTX_E_STATE, std::string(fn) + "no completed run");
+  if (knots && cap_knots < s->n_knots) return fail(s, RRTX_E_CAPACITY, std::string(fn) + "the knot buffer is too small");
+  if ((cx || cy) && cap_wp < s->n_wp) return fail(s, RRTX_E_CAPACITY, std::string(fn) + "the coefficient buffers are too small");
+  if (knot_offsets) memcpy(knot_offsets, s->h_knot_off.data(), sizeof(int64_t) * ((size_t)s->n + 1));
+  if (s->n_wp == 0) return RRTX_OK;
+  const size_t W = (size_t)s->n_wp, N = (size_t)s->n;
+  try {
+    HIPCHK(s, hipSetDevice(s->device));
+    if (knots && s->n_knots > 0) {   // the device keeps a course's knots at wp_off + 6 c: packed here
+      std::vector<double> raw(W + rppbs::KNOT_SLACK * N);
+      HIPCHK(s, hipMemcpy(raw.data(), s->knots.p, sizeof(double) * raw.size(), hipMemcpyDeviceToHost));
+      for (size_t c = 0; c < N; c++) {
+        const int64_t cnt = s->h_knot_off[c + 1] - s->h_knot_off[c];
+        if (cnt > 0) memcpy(knots + s->h_knot_off[c], raw.data() + s->h_wp_off[c] + rppbs::KNOT_SLACK * c, sizeof(double) * (size_t)cnt);
+      }
+    }
+    if (cx) HIPCHK(s, hipMemcpy(cx, s->tab.as<const double>() + W, sizeof(double) * W, hipMemcpyDeviceToHost));
+    if (cy) HIPCHK(s, hipMemcpy(cy, s->tab.as<const double>() + 2 * W, sizeof(double) * W, hipMemcpyDeviceToHost));
+  } catch (const std::exception& e) {
+    return fail(s, RRTX_E_HIP, std::string(fn) + e.what());
+  }
+  return RRTX_OK;
+}
+
+int rrtx_bspline_get_hits(rrtx_bspline* s, int32_t* hit) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_bspline_get_hits: the bspline object is NULL");
+  if (!s->ran) return fail(s, RRTX_E_STATE, "rrtx_bspline_get_hits: no completed run");
+  if (!s->has_hits) return fail(s, RRTX_E_STATE, "rrtx_bspline_get_hits: the last run had no obstacle list");
+  if (s->n == 0) return RRTX_OK;
+  if (!hit) return fail(s, RRTX_E_INVALID, "rrtx_bspline_get_hits: hit is NULL");
+  memcpy(hit, s->h_hit.data(), sizeof(int32_t) * (size_t)s->n);
+  return RRTX_OK;
+}
+
+int rrtx_bspline_get_kernel_ms(rrtx_bspline* s, double* kernel_ms) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_bspline_get_kernel_ms: the bspline object is NULL");
+  if (!s->ran) return fail(s, RRTX_E_STATE, "rrtx_bspline_get_kernel_ms: no completed run");
+  if (!kernel_ms) return fail(s, RRTX_E_INVALID, "rrtx_bspline_get_kernel_ms: kernel_ms is NULL");
+  *kernel_ms = s->kernel_ms;
+  return RRTX_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // rrtx_host.h -- the host-only core under the six opaque objects of include/rrtx.h (rrtx_handle, rrtx_steer,
-// rrtx_tracker, rrtx_spline, rrtx_armnav, rrtx_armik, rrtx_armdh): one check macro, one device buffer, one device probe, one timed section, and the host helpers more than
+// rrtx_tracker, rrtx_spline, rrtx_bspline, rrtx_armnav, rrtx_armik, rrtx_armdh): one check macro, one device buffer, one device probe, one timed section, and the host helpers more than
 // one object uses.  No kernels and no rpp* types: tests/native/host_core_check.cpp compiles it for the CPU against a fake
 // HIP runtime and reaches the failure paths no GPU run can.
 #pragma once

@@ -4,7 +4,8 @@ Per-script drop-in modules: `rrt_amd.rrt_01` ... `rrt_amd.rrt_10` carry exactly 
 number defines for its driver cell (`RRT`, `BITStar`, `Node`, `path_smoothing`, `get_path_length`), so a driver written
 against `10_path_planning_01_rrt_04_rrt_star.py` runs after `from rrt_amd.rrt_04 import *`.  `rrt_amd.dubins_path`, `rrt_amd.reeds_shepp_path`
 and `rrt_amd.lqr_path` do the same for the three stand-alone steering scripts (`plan_dubins_path`, `reeds_shepp_path_planning`,
-`LQRPlanner`), `rrt_amd.cubic_spline_path` for the cubic-spline script (`calc_spline_course`), `rrt_amd.bazier_path` for the
+`LQRPlanner`), `rrt_amd.cubic_spline_path` for the cubic-spline script (`calc_spline_course`), `rrt_amd.bspline_path` and
+`rrt_amd.spline_2d` for the two scipy spline scripts (`interpolate_b_spline_path` and its helpers; `Spline2D`), `rrt_amd.bazier_path` for the
 Bezier script (`calc_4points_bezier_path`, `calc_bezier_path` and its pointwise helpers), `rrt_amd.arm_obstacle_navigation` for the
 arm script (`NLinkArm`, `get_occupancy_grid`, `astar_torus` and its helpers), `rrt_amd.simple_2d_inverse_kinematics` for the two
 planar inverse-kinematics scripts (`inverse_kinematics`, `forward_kinematics`, `jacobian_inverse`, `NLinkArm` and their helpers),
@@ -23,6 +24,7 @@ planner = importlib.import_module("robotics-path-planning_amd.planner")
 steer = importlib.import_module("robotics-path-planning_amd.steer")
 track = importlib.import_module("robotics-path-planning_amd.track")
 spline = importlib.import_module("robotics-path-planning_amd.spline")
+bspline = importlib.import_module("robotics-path-planning_amd.bspline")
 armnav = importlib.import_module("robotics-path-planning_amd.armnav")
 armik = importlib.import_module("robotics-path-planning_amd.armik")
 armdh = importlib.import_module("robotics-path-planning_amd.armdh")
@@ -43,6 +45,8 @@ BatchPlanner = _pkg.BatchPlanner
 BatchSteer = _pkg.BatchSteer
 BatchTrack = _pkg.BatchTrack
 BatchSpline = _pkg.BatchSpline
+BatchBSpline = _pkg.BatchBSpline
+BSplineResult = _pkg.BSplineResult
 BatchArmNav = _pkg.BatchArmNav
 BatchArmIK = _pkg.BatchArmIK
 ArmIKResult = _pkg.ArmIKResult
