@@ -25,7 +25,7 @@ ERRORS = {1: "RRTX_PARTIAL", 0: "OK", -1: "RRTX_E_INVALID", -2: "RRTX_E_NO_DEVIC
 EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obstacles", "rrtx_set_instance_obstacles", "rrtx_set_rng_state",
            "rrtx_get_rng_state", "rrtx_seed_instances", "rrtx_set_instance", "rrtx_set_instance_rotation", "rrtx_plan", "rrtx_get_tree",
            "rrtx_get_path", "rrtx_get_results", "rrtx_results_device_ptr", "rrtx_copy_results_device", "rrtx_get_sobol_index", "rrtx_get_yaw", "rrtx_get_polylines", "rrtx_get_stats",
-           "rrtx_enable_trace", "rrtx_get_trace", "rrtx_get_trace_kind", "rrtx_get_phase_cycles", "rrtx_last_error", "rrtx_destroy", "rrtx_selftest_math",
+           "rrtx_enable_trace", "rrtx_get_trace", "rrtx_get_trace_kind", "rrtx_get_sample_stream", "rrtx_get_phase_cycles", "rrtx_last_error", "rrtx_destroy", "rrtx_selftest_math",
            "rrtx_smooth_paths", "rrtx_smooth_planned", "rrtx_get_smoothed_path", "rrtx_get_path_yaw", "rrtx_selfcheck", "rrtx_plan_many", "rrtx_plan_begin", "rrtx_plan_step",
            "rrtx_set_launch_bound", "rrtx_rccl_unique_id", "rrtx_rccl_init", "rrtx_rccl_gather_results",
            "rrtx_set_rs_cost", "rrtx_track_planned", "rrtx_get_track_outcome", "rrtx_get_track_arrays", "rrtx_get_track_records",
@@ -200,6 +200,7 @@ def load():
     L.rrtx_enable_trace.argtypes = [vp, i32]
     L.rrtx_get_trace.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(i32)]
     L.rrtx_get_trace_kind.argtypes = [vp, vp, i32, C.POINTER(i32)]
+    L.rrtx_get_sample_stream.argtypes = [vp, i32, i32, i32, vp]
     L.rrtx_get_phase_cycles.argtypes = [vp, vp]
     L.rrtx_last_error.argtypes = [vp]
     L.rrtx_last_error.restype = C.c_char_p
@@ -686,6 +687,13 @@ class Handle:
         kind = np.zeros(cap, dtype=np.int32)
         self._chk(self.L.rrtx_get_trace_kind(self._h, kind.ctypes.data, cap, C.byref(n)), "rrtx_get_trace_kind")
         return kind[:n.value]
+
+    def get_sample_stream(self, instance, first, count):
+        """(count, 2) samples first .. first + count - 1 of the stream the last plan of the RRT* iteration kernel drew for
+        `instance` (sample i is the one iteration i consumed)."""
+        out = np.zeros((count, 2))
+        self._chk(self.L.rrtx_get_sample_stream(self._h, instance, first, count, out.ctypes.data), "rrtx_get_sample_stream")
+        return out
 
 
 class Steer:

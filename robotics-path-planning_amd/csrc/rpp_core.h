@@ -52,18 +52,21 @@ RPP_HD static inline void mt_twist(uint32_t* mt) {
   mt[623] = mt[396] ^ (y >> 1) ^ ((y & 1U) ? 0x9908b0dfU : 0U);
 }
 
+// genrand_uint32's tempering of one state word
+RPP_HD static inline uint32_t mt_temper(uint32_t y) {
+  y ^= (y >> 11);
+  y ^= (y << 7) & 0x9d2c5680U;
+  y ^= (y << 15) & 0xefc60000U;
+  y ^= (y >> 18);
+  return y;
+}
 template <class S>
 RPP_HD static inline uint32_t mt_next(S* s) {
   if (s->pos >= 624) {
     mt_twist(s->mt);
     s->pos = 0;
   }
-  uint32_t y = s->mt[s->pos++];
-  y ^= (y >> 11);
-  y ^= (y << 7) & 0x9d2c5680U;
-  y ^= (y << 15) & 0xefc60000U;
-  y ^= (y >> 18);
-  return y;
+  return mt_temper(s->mt[s->pos++]);
 }
 template <class S>
 RPP_HD static inline double mt_random(S* s) {

@@ -139,6 +139,9 @@ struct Ctx {
   // one 64-byte line per node, stride x n_instances of them: plans of the rrt_04 iteration kernel only (allocated where
   // has_elen is set; nullptr elsewhere).  No other kernel and no host getter sees it
   Node* node;
+  // the sample stream of those plans, drawn before the first iteration launch (rrt_samples.hip.h): max_iter samples
+  // (x, y) per instance, 16 bytes each; sample `it` is the one iteration `it` consumes.  nullptr elsewhere
+  double* samp;
 };
 constexpr int GRID_CAP0 = 16, GRID_CAP1 = 16;
 

@@ -94,7 +94,6 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   int first_goal = I->first_goal;
   int goal_dups = I->goal_dups;   // exact duplicates of node first_goal appended so far (valid while first_goal >= 0)
 
-  for (int i = tid; i < 624; i += TPB) sh.rng.mt[i] = I->rng.mt[i];
   // this instance's obstacle rows, block-uniform.  The candidate-edge helpers take the count as an argument, the two loops
   // of the iteration body read it back from sh.om: with that split the streaming loops keep their ring of loads in flight
   // (tools/loop_spill_check.sh) and no shape spills more SGPRs than with one shared list
@@ -107,7 +106,6 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       sh.othr[i] = c.othr[ob + i];
     }
     if (tid == 0) {
-      sh.rng.pos = I->rng.pos;
       sh.overflow = 0;
       sh.om = om;
     }
@@ -115,7 +113,8 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   lds_barrier();
   int n = __builtin_amdgcn_readfirstlane(I->n), it = __builtin_amdgcn_readfirstlane(I->it);   // block-uniform: keep them scalar
   const double gx = I->goal[0], gy = I->goal[1];
-  rpp::Sobol sob = I->sobol;
+  // the samples of this instance, drawn before the plan's first launch (rrt_samples.hip.h): iteration `it` consumes S[it]
+  const v2d* S = reinterpret_cast<const v2d*>(c.samp) + (int64_t)inst * c.max_iter;
   // grid index of the mirror (one-wave shape): rebuilt from xq[] at every launch, kept current at every xq[] write
   GridS gs = {};
   gs.ok = 0;
@@ -159,7 +158,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   }
   if (tid == 0)
     for (int k = 0; k < 15; k++) sh.stat[k] = 0;
-  int have_sample = 0, have_nearest = 0, ni = 0;
+  int have_nearest = 0, ni = 0;
   double gbest = 0.0, gsecond = 0.0, nqx = 0.0, nqy = 0.0;   // nearest node of the current sample (block-uniform)
   int stop = 0;
   // ---- Several iterations per pass (one-wave shape, 16-bit stage; Ctx::spec2 = RRTX_SPEC2: 0 switches it off, 1..KSM
@@ -174,52 +173,38 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   // applies, in index order, and are folded into the nearest answer of the next sample.  A rejected extension in
   // between costs nothing (one node fewer to fold).  Anything else -- an unsnapped extension, a moved node, a ball that
   // reaches the goal's grid cell (the duplicate counting of scan2q_slot), a full list -- falls back to a pass of its own,
-  // which starts the scheme again; samples are drawn ahead in stream order and used in that order whatever happens.
+  // which starts the scheme again; the samples ahead are S[it + 1 ..], read where they are needed.
   // Bytes per iteration: 4 n -> 4 n / (1 + ks) while every iteration rides.
-  // What the scheme carries from iteration to iteration lives in the instance's own global memory (the free tail of
-  // hits[]: 256 doubles at hits[stride - 2560]), written by lane 0 and read back with wave-uniform loads -- a few loads
-  // per iteration against a register file that the streaming loop needs whole: G[0..3 | 4..7] ring of samples drawn
-  // ahead (x | y), G[8..11 | 12..15] nodes appended since the pass, G[16 + 8 e ..] set record e of a ring of four:
-  // {centre x, y, nearest best, runner-up (world units squared), ball hits (-1: no ball), list offset, nearest group
-  // (-1: none), best squared grid distance}.  Registers keep the ring heads and counts only.
+  // What the scheme carries from iteration to iteration lives in LDS (Sh2, in the room the generator's state left),
+  // written by lane 0 and read by every lane of the one wave -- no global round trip, and nothing of it in a register
+  // file that the streaming loop needs whole: sh.ax / sh.ay nodes appended since the pass, sh.set[e] set record e of a
+  // ring of four: {centre x, y, nearest best, runner-up (world units squared), ball hits (-1: no ball), list offset,
+  // nearest group (-1: none), best squared grid distance}.  Registers keep the ring head and counts only.  The balls'
+  // hit lists stay in the free tail of hits[].
   constexpr int SPEC_CAPS = 2048 / (KSM > 0 ? KSM : 1);   // hits[stride - 2048, stride): the balls' hit lists
   const int spec_base = (int)c.stride - 2048;
-  double* __restrict__ G = reinterpret_cast<double*>(hits + ((int)c.stride - 2560));
   const int KS_RUN = NW == 1 ? (c.spec2 < KSM ? c.spec2 : KSM) : 0;
   const bool SPEC_ON = KS_RUN > 0;
   constexpr int KA = KSM > 0 ? KSM : 1;
   static_assert(KSM <= 3, "rings of four");
-  int nq = 0, qhead = 0;                               // samples drawn ahead beyond the one in sh.rx / sh.ry
   int ns = 0, shead = 0;                               // query sets not yet used
   int na = 0;                                          // nodes appended since the pass: indices B_n .. B_n + na - 1
   int B_n = 0;                                         // tree size the pass scanned
   uint32_t B_thr = 0u;
-  // the sample of the next iteration into sh.rx / sh.ry (the front of the queue, else a new draw); tid 0 writes
-  auto take_next_sample = [&]() {
-    if (nq > 0) {
-      if (tid == 0) {
-        sh.rx = G[qhead];
-        sh.ry = G[4 + qhead];
-      }
-      qhead = (qhead + 1) & 3;
-      nq--;
-    } else if (tid == 0) {
-      rppk::draw_sample(c, sh, sob, gx, gy);
-    }
-  };
-  // Nearest node of the queue's front sample: the pass's answer (set record at shead) over [0, B_n) + the na nodes
+  // Nearest node of the next iteration's sample: the pass's answer (set record at shead) over [0, B_n) + the na nodes
   // appended since (indices B_n ..; the lowest index wins among equals, :1200).  margin_fold with the nearest of
   // the new nodes.  Returns 1 with the node in (ni, nqx, nqy), 2 when the 16-bit stage cannot
   // decide (o_bq bounds the squared grid distance), else 0.
   auto fold_n2 = [&](uint32_t& o_bq) -> int {
-    const double* R = G + 16 + 8 * shead;
-    const double s2x = G[qhead], s2y = G[4 + qhead];
+    const double* R = sh.set[shead];
+    double s2x, s2y;
+    sload_sample(S, it + 1, s2x, s2y);
     const double nb = R[2], nsec = R[3], grpd = R[6], bqd = R[7];
     double axv[4], ayv[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      axv[j] = G[8 + j];
-      ayv[j] = G[12 + j];
+      axv[j] = sh.ax[j];
+      ayv[j] = sh.ay[j];
     }
     o_bq = 0xffffffffu;
     if (grpd < 0.0) return 0;
@@ -259,12 +244,8 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   for (int step = 0; step < iters && it < c.max_iter && !stop; step++, it++) {
     ST_ADD(S_ITER, 1);
     // ---------------- sample :1132-1153
-    if (!have_sample) {
-      take_next_sample();
-      lds_barrier();
-    }
-    const double rx = sh.rx, ry = sh.ry;
-    have_sample = 0;
+    double rx, ry;
+    sload_sample(S, it, rx, ry);
     PH(0);
     // ---------------- nearest :1197-1202
     ST_ADD(S_AB2, 16 * (int64_t)n);   // + 24 per obstacle, added per iteration at the end of the launch
@@ -455,7 +436,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       bool use_spec = false;
       int spec_k0 = 0, spec_off0 = 0;
       if (SPEC_ON && ns > 0) {
-        const double* R = G + 16 + 8 * shead;
+        const double* R = sh.set[shead];
         const double cx0 = R[0], cy0 = R[1], k0 = R[4], o0 = R[5];
         use_spec = uni_i(k0 >= 0.0 && nx == cx0 && ny == cy0) != 0;
         spec_k0 = uni_i((int)k0);
@@ -471,6 +452,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       uint32_t pf_sq = 0u, pf_bq = 0u;   // 16-bit stage: packed query, best squared grid distance,
       int pf_grp = -1, pf_n = 0;         // the winner's 4-node group (unresolved while >= 0) and the tree size scanned
       bool pf_goal = false;
+      double p1x = 0.0, p1y = 0.0;       // the next iteration's sample (read with do_pf)
       int64_t pass_b = 0, pass_n = n;    // 16-bit stage: bytes and nodes its passes read
       if (use_spec) {
         // the nodes appended since that pass join the ball by the pass's own grid test, in index order
@@ -480,8 +462,8 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
         double axv[KA], ayv[KA];
 #pragma unroll
         for (int j = 0; j < KA; j++) {
-          axv[j] = G[8 + j];
-          ayv[j] = G[12 + j];
+          axv[j] = sh.ax[j];
+          ayv[j] = sh.ay[j];
         }
 #pragma unroll
         for (int j = 0; j < KA; j++) {
@@ -507,13 +489,11 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
         const uint32_t thr_gi = ball_thr_grid(r2, qm, qinv);
         const int rw_gi = (int)__builtin_sqrt((double)thr_gi) + 1;   // its window half-width (grid index)
         if (do_pf) {
-          take_next_sample();
-          lds_barrier();
-          have_sample = 1;
-          pf_goal = on_goal(first_goal, gx, gy, sh.rx, sh.ry);
+          sload_sample(S, it + 1, p1x, p1y);
+          pf_goal = on_goal(first_goal, gx, gy, p1x, p1y);
         }
         if (do_pf && !pf_goal) {
-          pf_sq = rppk::quant16(c, sh.rx, sh.ry);
+          pf_sq = rppk::quant16(c, p1x, p1y);
           // further query sets: the following iterations' balls about their samples, up to the first that reaches the
           // goal's grid cell (or the end of this launch)
           int kmax = 0;
@@ -529,31 +509,17 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
               if (uni_i(qdist(goal_q, pf_sq) <= thr2)) kmax = 0;
             }
             if (kmax > 0) {
-              // samples i + 2 .. i + 1 + kmax, next in the stream, behind those already queued: lane 0 draws them
-              // through sh.rx / sh.ry and puts them in the ring
-              const double p1x = sh.rx, p1y = sh.ry;
-              if (nq < kmax) {
-                lds_barrier();
-                if (tid == 0) {
-                  for (int j = nq; j < kmax; j++) {
-                    rppk::draw_sample(c, sh, sob, gx, gy);
-                    G[(qhead + j) & 3] = sh.rx;
-                    G[4 + ((qhead + j) & 3)] = sh.ry;
-                  }
-                  sh.rx = p1x;
-                  sh.ry = p1y;
-                }
-                nq = kmax;
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                lds_barrier();
-              }
+              // samples i + 2 .. i + 1 + kmax, next in the stream (an entry past kmax is read nowhere: the last sample's copy)
               double qxv[KA], qyv[KA];
 #pragma unroll
-              for (int j = 0; j < KA; j++) {
-                qxv[j] = G[(qhead + j) & 3];
-                qyv[j] = G[4 + ((qhead + j) & 3)];
+              for (int j = 0; j < KA; j++) qxv[j] = qyv[j] = 0.0;
+              if constexpr (KA == 3) {
+                sload_samples3(S, it + 2, it + 2 + (1 < kmax ? 1 : kmax - 1), it + 2 + (2 < kmax ? 2 : kmax - 1), qxv, qyv);
+              } else {
+#pragma unroll
+                for (int j = 0; j < KA; j++) sload_sample(S, it + 2 + (j < kmax ? j : kmax - 1), qxv[j], qyv[j]);
               }
-              // ball j is about sample i + 1 + j: p1 for j = 0, the queue's entry j - 1 after that
+              // ball j is about sample i + 1 + j: p1 for j = 0, entry j - 1 of those after that
               int ks = kmax;
 #pragma unroll
               for (int j = 1; j < KA; j++)
@@ -569,7 +535,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
                 sp[j].off = spec_base + j * SPEC_CAPS;
                 sp[j].cap = SPEC_CAPS;
                 if (tid == 0) {   // the record's centre now: nothing of the queue has to stay in registers over the pass
-                  double* R = G + 16 + 8 * j;
+                  double* R = sh.set[j];
                   R[0] = cxj;
                   R[1] = cyj;
                   R[5] = (double)sp[j].off;
@@ -590,7 +556,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
 #pragma unroll
                 for (int j = 0; j < KA; j++) {
                   const bool on = j < ks;
-                  double* R = G + 16 + 8 * j;
+                  double* R = sh.set[j];
                   R[2] = sp[j].best * qs2;
                   R[3] = sp[j].second * qs2;
                   R[4] = (on && sp[j].cnt + j + 1 <= SPEC_CAPS) ? (double)sp[j].cnt : -1.0;   // room for the nodes appended before it is used
@@ -647,7 +613,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
           nearest_on_goal(first_goal, gx, gy, o_ni, o_x, o_y, pf_best, pf_second);
           return 1;
         }
-        const double dxl = ax - sh.rx, dyl = ay - sh.ry;
+        const double dxl = ax - p1x, dyl = ay - p1y;
         const double dl = __builtin_sqrt(dxl * dxl + dyl * dyl);
         const double db = __builtin_sqrt(pf_best), ds = __builtin_sqrt(pf_second);
         return margin_fold(c, qm, dl, aidx, ax, ay, db, ds, pf_bq, pf_grp, pf_n, pf_sq,
@@ -938,8 +904,8 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
         } else if ((use_spec || did_spec) && na < 4) {
           // the node just appended joins the list of nodes the pass has not seen
           if (tid == 0) {
-            G[8 + na] = wx;
-            G[12 + na] = wy;
+            sh.ax[na] = wx;
+            sh.ay[na] = wy;
           }
           na++;
         }
@@ -1001,10 +967,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       prev_sib[i] = ps;
     }
   }
-  for (int i = tid; i < 624; i += TPB) I->rng.mt[i] = sh.rng.mt[i];
   if (tid == 0) {
-    I->rng.pos = sh.rng.pos;
-    I->sobol = sob;
     I->first_goal = first_goal;
     I->goal_dups = goal_dups;
     I->n = n;

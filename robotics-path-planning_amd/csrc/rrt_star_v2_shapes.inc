@@ -36,7 +36,6 @@ struct WalkEnt {   // sibling stack of the depth-first cost walk (propagate_scal
 };
 
 struct Sh2 {
-  rpp::MT rng;
   double ox[MAX_OBS], oy[MAX_OBS], othr[MAX_OBS];
   union {
     Hit hit[NW * HW];          // scan -> de-dup
@@ -50,12 +49,16 @@ struct Sh2 {
   double ux[NU], uy[NU], ucur[NU], uval[NU], uhyp[NU], uex[NU], uey[NU];
   double red_best[NW], red_second[NW], red_x[NW], red_y[NW];
   int32_t red_idx[NW], wave_cnt[NW], wave_start[NW];
-  double rx, ry, nx, ny;
+  double nx, ny;
   int32_t flag, nu, nvalid, overflow, ecoll0;
   int32_t fa, fb, fover, fcount;
   int32_t n_rw, n_pr, moved, last_fc;
   int32_t om;           // this instance's obstacle count, for the loops of the iteration body (uni_i on read)
   long long stat[15];   // per-launch counters, lane 0 only (kept out of the register file)
+  // one-wave shape, several iterations per pass (rrt_star_v2_kernel.inc): the nodes appended since the pass and the
+  // ring of four set records; lane 0 writes, every lane reads
+  double ax[4], ay[4];
+  double set[4][8];
 };
 
 __device__ __forceinline__ void lds_barrier() { __syncthreads(); }  // lowers to s_waitcnt lgkmcnt(0); s_barrier

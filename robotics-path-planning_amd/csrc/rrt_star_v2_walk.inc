@@ -27,8 +27,33 @@ __device__ __forceinline__ void sload_node(const Node* nd, int node, int& nxs, i
   nxs = (int)r.y;
   el = rpp::b2d((uint64_t)r.z | ((uint64_t)r.w << 32));
 }
+// Sample i of the instance's stream S (Ctx::samp, rrt_samples.hip.h), a block-uniform value: the stream was written
+// before the launch and is constant during it, so the scalar cache may serve it (no glc); four samples share a line
+__device__ __forceinline__ void sload_sample(const v2d* S, int i, double& sx, double& sy) {
+  const v2d* p = S + __builtin_amdgcn_readfirstlane(i);
+  v4u r;
+  asm volatile("s_load_dwordx4 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(r) : "s"(p) : "memory");
+  sx = rpp::b2d((uint64_t)r.x | ((uint64_t)r.y << 32));
+  sy = rpp::b2d((uint64_t)r.z | ((uint64_t)r.w << 32));
+}
+// ... and three of them in one round trip
+__device__ __forceinline__ void sload_samples3(const v2d* S, int i0, int i1, int i2, double* sx, double* sy) {
+  const v2d *p0 = S + __builtin_amdgcn_readfirstlane(i0), *p1 = S + __builtin_amdgcn_readfirstlane(i1),
+            *p2 = S + __builtin_amdgcn_readfirstlane(i2);
+  v4u a, b, d;
+  asm volatile("s_load_dwordx4 %0, %3, 0x0\n\ts_load_dwordx4 %1, %4, 0x0\n\ts_load_dwordx4 %2, %5, 0x0\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(a), "=&s"(b), "=&s"(d)
+               : "s"(p0), "s"(p1), "s"(p2)
+               : "memory");
+  sx[0] = rpp::b2d((uint64_t)a.x | ((uint64_t)a.y << 32));
+  sy[0] = rpp::b2d((uint64_t)a.z | ((uint64_t)a.w << 32));
+  sx[1] = rpp::b2d((uint64_t)b.x | ((uint64_t)b.y << 32));
+  sy[1] = rpp::b2d((uint64_t)b.z | ((uint64_t)b.w << 32));
+  sx[2] = rpp::b2d((uint64_t)d.x | ((uint64_t)d.y << 32));
+  sy[2] = rpp::b2d((uint64_t)d.z | ((uint64_t)d.w << 32));
+}
 
-constexpr int CE = (NU + 63) / 64;   // near candidates per lane when a wave holds the candidate list in registers
+constexpr int CE = (NU + 63) / 64;  // near candidates per lane when a wave holds the candidate list in registers
 
 // Inst::phase[PROP_WALK_SLOT] (a slot no phase timer of this kernel uses) counts the walks propagate_lanes finished,
 // plus PROP_WALK_FULL for each one whose pending list ran full (rrtx_get_phase_cycles; tests and diagnostics)

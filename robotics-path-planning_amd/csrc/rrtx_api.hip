@@ -13,6 +13,7 @@
 #include "rrtx_host.h"
 #include "rrt_kernels.hip.h"
 #include "rrt_star_v2.hip.h"
+#include "rrt_samples.hip.h"
 #include "rrt_informed.hip.h"
 #include "rrt_dubins.hip.h"
 #include "rrt_rs.hip.h"
@@ -214,6 +215,15 @@ static int launch_rrt_star_v2_once(rrtx_handle* h, const Ctx& c, int nblk, int t
   const V2Shape& s = v2_shape(tpb);
   return timed_launch(h, false, [&] { hipLaunchKernelGGL(s.kernel, dim3(nblk), dim3(s.tpb), 0, h->stream, c, h->v2_chunk_iters); });
 }
+// The sample stream of `nblk` instances of `c` (c.inst_map selects them), from their staged start state: every sample of
+// the plan into c.samp, the generators' end state into c.inst.  Timed with the plan's kernels, not counted as a launch.
+static int launch_sample_stream(rrtx_handle* h, const Ctx& c, int nblk) {
+  float ms = 0.f;
+  int rc = h->timed(&ms, [&] { hipLaunchKernelGGL(rppss::rrt_sample_stream_kernel, dim3(nblk), dim3(64), 0, h->stream, c); });
+  if (rc) return rc;
+  h->run.kms += ms;
+  return RRTX_OK;
+}
 static int launch_rrt_star_v2(rrtx_handle* h, const Ctx& c, int nblk, int tpb) {
   for (int64_t done_it = 0; done_it < c.max_iter; done_it += h->v2_chunk_iters) {
     int rc = launch_rrt_star_v2_once(h, c, nblk, tpb);
@@ -343,6 +353,8 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
     c.has_elen = 1;   // kid[].elen: cached parent-edge lengths (cost propagation)
     if ((rc = dalloc(h, &c.xq, tot))) return rc;     // 16-bit mirror (first stage of the streaming pass)
     if ((rc = dalloc(h, &c.node, tot))) return rc;   // one 64-byte line per node: the iteration kernel's working format
+    // the sample stream (rrt_samples.hip.h): 16 bytes per instance and iteration
+    if ((rc = dalloc(h, &c.samp, 2 * (size_t)(p->max_iter > 0 ? p->max_iter : 1) * h->n_inst))) return rc;
     // grid index of the mirror (DESIGN 5.1 "grid index"): cells sized for about 6 nodes each at the final tree size,
     // 512 grid steps at the least (128 x 128 cells); an overflow block per 128 nodes of capacity
     int gsh = 9;
@@ -889,6 +901,9 @@ int rrtx_plan_begin(rrtx_handle* h) {
     HIPCHK(h, hipMemcpyAsync(h->d_iargs, h->iargs.data(), sizeof(rppi::InformedArgs) * B, hipMemcpyHostToDevice, h->stream));
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  // RRT* iteration kernel: every sample of the plan is drawn now, from the staged generators (part of the plan's time:
+  // the stream depends on the seeds)
+  if (R.use_v2 && (rc = launch_sample_stream(h, c, B))) return rc;
   R.stage = R.use_v2 ? 1 : 2;
   return RRTX_OK;
 }
@@ -996,7 +1011,10 @@ static int plan_finish(rrtx_handle* h) {
     // plans the instances `redo` again: shape = workgroup shape of the iteration kernel, 0 = general kernel alone
     auto replan_on = [&](const std::vector<int32_t>& redo, int shape) {
       return replan(h, redo, "retry", h->da, false, nullptr, [&](const Ctx& cr, int nr) {
-        return shape ? launch_rrt_star_v2(h, cr, nr, shape) : RRTX_OK;
+        if (!shape) return (int)RRTX_OK;   // the general kernel draws its own samples
+        // replan() staged the generators again: the same stream, and their end state back into the instances
+        if (int rs = launch_sample_stream(h, cr, nr)) return rs;
+        return launch_rrt_star_v2(h, cr, nr, shape);
       });
     };
     int shape = R.v2_tpb;   // 0 = general kernel
@@ -1466,6 +1484,17 @@ int rrtx_get_stats(rrtx_handle* h, rrtx_stats* st) {
 int rrtx_get_phase_cycles(rrtx_handle* h, int64_t* out16) {
   if (!h || !out16) return RRTX_E_INVALID;
   memcpy(out16, h->phase, sizeof(h->phase));
+  return RRTX_OK;
+}
+
+int rrtx_get_sample_stream(rrtx_handle* h, int32_t instance, int32_t first, int32_t count, double* out_xy) {
+  if (!h || instance < 0 || instance >= h->n_inst || first < 0 || count < 0 || (count > 0 && !out_xy)) return RRTX_E_INVALID;
+  if (!h->planned || !h->c.samp || h->stats.main_f32 != 1) return RRTX_E_STATE;   // no plan of the iteration kernel to read
+  if ((int64_t)first + count > h->c.max_iter) return RRTX_E_INVALID;
+  if (!count) return RRTX_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpy(out_xy, h->c.samp + 2 * ((int64_t)instance * h->c.max_iter + first), sizeof(double) * 2 * (size_t)count,
+                      hipMemcpyDeviceToHost));
   return RRTX_OK;
 }
 
