@@ -608,6 +608,58 @@ int rrtx_spline_get_c(rrtx_spline* s, double* cx, double* cy, int64_t cap);
  * the last run had no obstacle list. */
 int rrtx_spline_get_hits(rrtx_spline* s, int32_t* hit);
 
+/* -- pointwise queries at the caller's parameters: the methods of CubicSpline1D (:75-140) and CubicSpline2D (:248-310) --
+ * The splines of the last completed rrtx_spline_run or rrtx_spline_fit1d stay on the device and answer, per spline, a list
+ * of parameters of the caller's choosing (csrc/spline_batch.hip.h: spline_query_kernel, one lane per query).  With c given,
+ * every value is the reference's double bit for bit; a parameter of -0.0 is accepted as the reference accepts it. */
+/* per-query status */
+#define RRTX_SPLINE_Q_OK 0
+#define RRTX_SPLINE_Q_OUTSIDE 1      /* t < s[0] or t > s[-1] (+-inf too): the reference returns None */
+#define RRTX_SPLINE_Q_REF_RAISES 2   /* t == s[-1], or t is NaN: both range tests are false, bisect lands on the last knot and
+                                        the reference raises IndexError at self.b[i] */
+#define RRTX_SPLINE_Q_NO_SPLINE 3    /* the spline's status is RRTX_SPLINE_DEGENERATE */
+typedef struct rrtx_spline_fit1d_batch {
+  int64_t n;                /* splines */
+  const int64_t* offsets;   /* n + 1, CSR into knots / values (and c) */
+  const double* knots;      /* CubicSpline1D's x: ascending within a spline */
+  const double* values;     /* CubicSpline1D's y */
+  const double* c;          /* NULL: c by the Thomas recurrence on the device; else n_c values, c as data */
+  int64_t n_c;              /* must equal offsets[n] when c is given */
+} rrtx_spline_fit1d_batch;
+typedef struct rrtx_spline_query_batch {
+  int64_t n;                  /* must be the number of splines of the last run / fit1d */
+  const int64_t* q_offsets;   /* n + 1, CSR into t: the queries of each spline (a spline may have none) */
+  const double* t;            /* the parameters: any double */
+  int32_t want_derivatives;   /* != 0: the first and second derivatives are stored as well */
+  int32_t reserved;
+} rrtx_spline_query_batch;
+/* Fits one-dimensional splines (CubicSpline1D(knots, values)) of 2 .. RRTX_SPLINE_MAX_WAYPOINTS knots each, and replaces the
+ * splines of the object as a rrtx_spline_run does.  Afterwards rrtx_spline_get_records gives n_points 0 and length =
+ * the last knot, rrtx_spline_get_c gives c in cx and leaves cy untouched, and rrtx_spline_get_points and
+ * rrtx_spline_get_hits return RRTX_E_STATE.  Returns RRTX_OK, or RRTX_PARTIAL when some spline is RRTX_SPLINE_DEGENERATE (two equal
+ * consecutive knots).  RRTX_E_INVALID, before any HIP call and with a message that names the spline: a knot below its
+ * predecessor (the reference's ValueError), a knot, value or c that is not finite, a knot or value above 1e6 in magnitude;
+ * and as rrtx_spline_run: NULL pointers, n, offsets, the knot counts, n_c. */
+int rrtx_spline_fit1d(rrtx_spline* s, const rrtx_spline_fit1d_batch* b);
+/* Answers Q = q_offsets[n] queries against the splines of the last completed rrtx_spline_run or rrtx_spline_fit1d (a course
+ * whose record says RRTX_SPLINE_REF_RAISES has a spline and answers: that status speaks about ds).  Q == 0 is a valid empty
+ * call.  Returns RRTX_OK, or RRTX_PARTIAL when some query's status is not RRTX_SPLINE_Q_OK.  Checked in this order, before any
+ * HIP call: what the batch alone shows (RRTX_E_INVALID: a NULL pointer -- t may be NULL when Q is 0 --, n < 0 or > 2^30,
+ * q_offsets that do not start at 0 or that decrease, more than RRTX_SPLINE_MAX_POINTS queries), then RRTX_E_STATE without a
+ * completed run, then RRTX_E_INVALID when n is not the number of splines of that run. */
+int rrtx_spline_query(rrtx_spline* s, const rrtx_spline_query_batch* b);
+/* The planes of the last rrtx_spline_query, Q entries each in the order of t, any pointer may be NULL (cap = entries available
+ * in each; RRTX_E_CAPACITY when too small).  After rrtx_spline_run: x, y (calc_position), yaw (calc_yaw), k (calc_curvature),
+ * and dx, dy, ddx, ddy (sx / sy.calc_first_derivative, calc_second_derivative).  After rrtx_spline_fit1d: y, dy, ddy
+ * (calc_position, calc_first_derivative, calc_second_derivative); x, yaw, k, dx, ddx must be NULL (RRTX_E_STATE otherwise).
+ * Every value of a query whose status is not RRTX_SPLINE_Q_OK is NaN.  A derivative plane asked of a query made with
+ * want_derivatives == 0 returns RRTX_E_STATE, as does a call without a completed query. */
+int rrtx_spline_get_query(rrtx_spline* s, double* x, double* y, double* yaw, double* k, double* dx, double* dy, double* ddx,
+                          double* ddy, int32_t* status, int64_t cap);
+/* n_queries, axes (2 after rrtx_spline_run, 1 after rrtx_spline_fit1d), has_derivatives and the HIP-event time of the kernel
+ * of the last rrtx_spline_query; each may be NULL. */
+int rrtx_spline_get_query_info(rrtx_spline* s, int64_t* n_queries, int32_t* axes, int32_t* has_derivatives, double* kernel_ms);
+
 /* ---- batched interpolating B-spline courses of degree 1 .. 5 through waypoints (csrc/bspline_batch.hip.h, csrc/rpp_bspline.h)
  * For every course of a batch: what interpolate_b_spline_path(x, y, n_path_points, degree) of 10_path_planning_00_bspline_path.py
  * :59-108 returns -- x, y, heading, curvature -- (param NORMALISED, sample LINSPACE), or what the driver loop of

@@ -39,6 +39,7 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_tracker_get_counts", "rrtx_tracker_get_records", "rrtx_tracker_get_arrays", "rrtx_tracker_get_kernel_ms",
            "rrtx_spline_create", "rrtx_spline_destroy", "rrtx_spline_last_error", "rrtx_spline_run", "rrtx_spline_get_records",
            "rrtx_spline_get_points", "rrtx_spline_get_c", "rrtx_spline_get_hits",
+           "rrtx_spline_fit1d", "rrtx_spline_query", "rrtx_spline_get_query", "rrtx_spline_get_query_info",
            "rrtx_bspline_create", "rrtx_bspline_destroy", "rrtx_bspline_last_error", "rrtx_bspline_run", "rrtx_bspline_get_records",
            "rrtx_bspline_get_points", "rrtx_bspline_get_coefficients", "rrtx_bspline_get_hits", "rrtx_bspline_get_kernel_ms",
            "rrtx_armnav_create", "rrtx_armnav_destroy", "rrtx_armnav_last_error", "rrtx_armnav_occupancy", "rrtx_armnav_set_grids",
@@ -59,6 +60,7 @@ RS_COST_EUCLID, RS_COST_PATH = 0, 1     # include/rrtx.h: #define RRTX_RS_COST_*
 TRACK_FAIL_REACH, TRACK_FAIL_ANGLE, TRACK_FAIL_LONG, TRACK_FAIL_COLLISION = 1, 2, 4, 8   # #define RRTX_TRACK_FAIL_*
 SPLINE_OK, SPLINE_DEGENERATE, SPLINE_REF_RAISES = 0, 1, 2                                # #define RRTX_SPLINE_*
 SPLINE_MAX_WAYPOINTS, SPLINE_MAX_POINTS = 4096, 1 << 28
+SPLINE_Q_OK, SPLINE_Q_OUTSIDE, SPLINE_Q_REF_RAISES, SPLINE_Q_NO_SPLINE = 0, 1, 2, 3        # #define RRTX_SPLINE_Q_*
 BSPLINE_OK, BSPLINE_DEGENERATE, BSPLINE_TOO_FEW = 0, 1, 2                                 # #define RRTX_BSPLINE_*
 BSPLINE_PARAM_NORMALISED, BSPLINE_PARAM_CHORD = 0, 1
 BSPLINE_SAMPLE_LINSPACE, BSPLINE_SAMPLE_ARANGE, BSPLINE_SAMPLE_EXPLICIT = 0, 1, 2
@@ -123,6 +125,18 @@ class SplineBatch(C.Structure):
     _fields_ = [("n", C.c_int64), ("offsets", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p), ("ds", C.c_void_p),
                 ("ds_per_course", C.c_int32), ("want_arrays", C.c_int32), ("cx", C.c_void_p), ("cy", C.c_void_p),
                 ("n_c", C.c_int64), ("obstacles", C.c_void_p), ("n_obstacles", C.c_int64), ("robot_radius", C.c_double)]
+
+
+class SplineFit1dBatch(C.Structure):
+    """rrtx_spline_fit1d_batch: the one-dimensional splines of one rrtx_spline_fit1d."""
+    _fields_ = [("n", C.c_int64), ("offsets", C.c_void_p), ("knots", C.c_void_p), ("values", C.c_void_p), ("c", C.c_void_p),
+                ("n_c", C.c_int64)]
+
+
+class SplineQueryBatch(C.Structure):
+    """rrtx_spline_query_batch: the parameters of one rrtx_spline_query, a CSR list per spline."""
+    _fields_ = [("n", C.c_int64), ("q_offsets", C.c_void_p), ("t", C.c_void_p), ("want_derivatives", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 BSPLINE_RECORD = np.dtype([("status", np.int32), ("degree", np.int32), ("n_points", np.int64), ("length", np.float64)])
@@ -264,6 +278,10 @@ def load():
     L.rrtx_spline_get_points.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64]
     L.rrtx_spline_get_c.argtypes = [vp, vp, vp, C.c_int64]
     L.rrtx_spline_get_hits.argtypes = [vp, vp]
+    L.rrtx_spline_fit1d.argtypes = [vp, C.POINTER(SplineFit1dBatch)]
+    L.rrtx_spline_query.argtypes = [vp, C.POINTER(SplineQueryBatch)]
+    L.rrtx_spline_get_query.argtypes = [vp] + [vp] * 8 + [vp, C.c_int64]
+    L.rrtx_spline_get_query_info.argtypes = [vp, i64p, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_double)]
     L.rrtx_bspline_create.argtypes = [i32, C.POINTER(vp)]
     L.rrtx_bspline_destroy.argtypes = [vp]
     L.rrtx_bspline_destroy.restype = None
@@ -1002,6 +1020,35 @@ class Spline:
         hit = np.zeros(n, dtype=np.int32)
         self._chk(self.L.rrtx_spline_get_hits(self._s, hit.ctypes.data), "rrtx_spline_get_hits")
         return hit
+
+    def fit1d(self, batch):
+        """batch: SplineFit1dBatch (its arrays are kept alive by the caller).  Returns 0 or RRTX_PARTIAL."""
+        return self._chk(self.L.rrtx_spline_fit1d(self._s, C.byref(batch)), "rrtx_spline_fit1d")
+
+    def c1d(self, w):
+        """c of the last fit1d, w = knots of the batch."""
+        c = np.zeros(w)
+        self._chk(self.L.rrtx_spline_get_c(self._s, c.ctypes.data, None, w), "rrtx_spline_get_c")
+        return c
+
+    def query(self, batch):
+        """batch: SplineQueryBatch (its arrays are kept alive by the caller).  Returns 0 or RRTX_PARTIAL."""
+        return self._chk(self.L.rrtx_spline_query(self._s, C.byref(batch)), "rrtx_spline_query")
+
+    def query_planes(self):
+        """(planes, status, kernel_ms) of the last query: planes is a dict of (Q,) arrays -- x, y, yaw, k and, when asked
+        for, dx, dy, ddx, ddy; y and dy, ddy after a fit1d -- and status (Q,) int32."""
+        q, axes, der, ms = C.c_int64(), C.c_int32(), C.c_int32(), C.c_double()
+        self._chk(self.L.rrtx_spline_get_query_info(self._s, C.byref(q), C.byref(axes), C.byref(der), C.byref(ms)),
+                  "rrtx_spline_get_query_info")
+        names = ("x", "y", "yaw", "k", "dx", "dy", "ddx", "ddy")
+        want = (("x", "y", "yaw", "k") if axes.value == 2 else ("y",)) + \
+            ((("dx", "dy", "ddx", "ddy") if axes.value == 2 else ("dy", "ddy")) if der.value else ())
+        planes = {k: np.zeros(q.value) for k in want}
+        status = np.zeros(q.value, dtype=np.int32)
+        self._chk(self.L.rrtx_spline_get_query(self._s, *[planes[k].ctypes.data if k in planes else None for k in names],
+                                               status.ctypes.data, q.value), "rrtx_spline_get_query")
+        return planes, status, ms.value
 
 
 class BSpline:

@@ -2,7 +2,8 @@
 // Reference: 10_path_planning_00_cubic_spline_path.py
 //   CubicSpline1D.__init__ :48-73 (b and d :69-71), calc_position :93-94, calc_first_derivative :117,
 //   calc_second_derivative :139, __search_index :146, __calc_B :171-172,
-//   CubicSpline2D.__calc_s :240-246, calc_curvature :289, calc_yaw :309, calc_spline_course :313-325.
+//   CubicSpline2D.__calc_s :240-246, calc_curvature :289, calc_yaw :309, calc_spline_course :313-325; the range tests of the
+//   pointwise methods :86-89.
 //
 // Arithmetic: every double outside the solve of `c` is the reference's on glibc 2.35 + numpy: np.hypot = rpp_glibc_hypot,
 // np.cumsum = a left-to-right sum, `** 2.0`, `** 3.0`, `** 2` and `** (3 / 2)` on numpy doubles = libm pow
@@ -53,13 +54,12 @@ RPP_HD static inline int64_t arange_count(double s_end, double ds) {
   return k;
 }
 
-// One axis `a` (x or y) of one course of n >= 2 waypoints: the knots s (CubicSpline2D.__calc_s), then c -- copied from
-// c_in when given, else the Thomas recurrence above -- then b and d (:69-71).  s, b, c, d hold n doubles each; b[n-1]
-// and d[n-1] are zeroed (the reference's lists have n - 1 entries).  The forward sweep keeps cp in d and dp in c.
-// Returns kSplineOk or kSplineDegenerate (nothing but s is valid then).
-RPP_HD static inline int spline_fit_axis(const double* x, const double* y, const double* a, int n, const double* c_in,
-                                         double* s, double* b, double* c, double* d) {
-  spline_chord_sum(x, y, n, s);
+// One spline over knots the caller supplies (CubicSpline1D.__init__ :48-73; s strictly increasing is the caller's to report,
+// an equal pair is found here): c -- copied from c_in when given, else the Thomas recurrence above -- then b and d
+// (:69-71).  b, c, d hold n doubles each; b[n-1] and d[n-1] are zeroed (the reference's lists have n - 1 entries).  The
+// forward sweep keeps cp in d and dp in c.  Returns kSplineOk or kSplineDegenerate (some h[i] == 0: nothing is valid then).
+RPP_HD static inline int spline_fit_knots(const double* s, const double* a, int n, const double* c_in, double* b, double* c,
+                                          double* d) {
   for (int i = 0; i + 1 < n; i++)
     if (s[i + 1] - s[i] == 0.0) return kSplineDegenerate;
   if (c_in) {
@@ -94,6 +94,14 @@ RPP_HD static inline int spline_fit_axis(const double* x, const double* y, const
   return kSplineOk;
 }
 
+// One axis `a` (x or y) of one course of n >= 2 waypoints: the knots s (CubicSpline2D.__calc_s), then spline_fit_knots over
+// them.  s, b, c, d hold n doubles each.  Returns kSplineOk or kSplineDegenerate (nothing but s is valid then).
+RPP_HD static inline int spline_fit_axis(const double* x, const double* y, const double* a, int n, const double* c_in,
+                                         double* s, double* b, double* c, double* d) {
+  spline_chord_sum(x, y, n, s);
+  return spline_fit_knots(s, a, n, c_in, b, c, d);
+}
+
 // arange_count, with the reference's failure: sample k is
 // 0 + k * ds (numpy fills start + i * delta with delta = (0 + ds) - 0).  *status becomes kSplineRefRaises, and the
 // count 0, when the last sample is not below s_end: bisect then lands on the last knot and the reference's b[i] raises.
@@ -106,11 +114,8 @@ RPP_HD static inline int64_t spline_count(double s_end, double ds, int* status) 
   return k;
 }
 
-// The course's point at parameter t (0 <= t < s[n-1]): out = {x, y, yaw, curvature}
-RPP_HD static inline void spline_eval(const double* s, const double* ax, const double* bx, const double* cx,
-                                      const double* dx, const double* ay, const double* by, const double* cy,
-                                      const double* dy, int n, double t, double* out) {
-  // bisect.bisect(s, t) - 1 (:146)
+// bisect.bisect(s, t) - 1 (:146) for s[0] <= t < s[n-1]: the segment 0 .. n-2 that holds t
+RPP_HD static inline int spline_segment(const double* s, int n, double t) {
   int lo = 0, hi = n;
   while (lo < hi) {
     const int mid = (lo + hi) / 2;
@@ -119,17 +124,97 @@ RPP_HD static inline void spline_eval(const double* s, const double* ax, const d
     else
       lo = mid + 1;
   }
-  const int i = lo - 1;
+  return lo - 1;
+}
+
+// One axis on segment i at u = t - s[i], u2 = u ** 2.0, u3 = u ** 3.0: p = {position :93-94, first derivative :117, second
+// derivative :139}
+RPP_HD static inline void spline_axis_forms(const double* a, const double* b, const double* c, const double* d, int i, double u,
+                                            double u2, double u3, double* p) {
+  p[0] = a[i] + b[i] * u + c[i] * u2 + d[i] * u3;
+  p[1] = b[i] + 2.0 * c[i] * u + 3.0 * d[i] * u2;
+  p[2] = 2.0 * c[i] + 6.0 * d[i] * u;
+}
+
+// calc_curvature :289 of the first (x1, y1) and second (x2, y2) derivatives
+RPP_HD static inline double spline_curvature(double x1, double y1, double x2, double y2) {
+  return (y2 * x1 - x2 * y1) / spline_pow(py_sq(x1) + py_sq(y1), 1.5);
+}
+
+// The course's point at parameter t (0 <= t < s[n-1]): out = {x, y, yaw, curvature}
+RPP_HD static inline void spline_eval(const double* s, const double* ax, const double* bx, const double* cx,
+                                      const double* dx, const double* ay, const double* by, const double* cy,
+                                      const double* dy, int n, double t, double* out) {
+  const int i = spline_segment(s, n, t);
   const double u = t - s[i];
   const double u2 = spline_pow(u, 2.0), u3 = spline_pow(u, 3.0);
-  out[0] = ax[i] + bx[i] * u + cx[i] * u2 + dx[i] * u3;                  // :93-94
-  out[1] = ay[i] + by[i] * u + cy[i] * u2 + dy[i] * u3;
-  const double x1 = bx[i] + 2.0 * cx[i] * u + 3.0 * dx[i] * u2;          // :117
-  const double y1 = by[i] + 2.0 * cy[i] * u + 3.0 * dy[i] * u2;
-  const double x2 = 2.0 * cx[i] + 6.0 * dx[i] * u;                       // :139
-  const double y2 = 2.0 * cy[i] + 6.0 * dy[i] * u;
-  out[2] = rpp_glibc_atan2(y1, x1);                                      // :309
-  out[3] = (y2 * x1 - x2 * y1) / spline_pow(py_sq(x1) + py_sq(y1), 1.5);   // :289
+  double px[3], py[3];
+  spline_axis_forms(ax, bx, cx, dx, i, u, u2, u3, px);
+  spline_axis_forms(ay, by, cy, dy, i, u, u2, u3, py);
+  out[0] = px[0];
+  out[1] = py[0];
+  out[2] = rpp_glibc_atan2(py[1], px[1]);   // :309
+  out[3] = spline_curvature(px[1], py[1], px[2], py[2]);
+}
+
+// ---- pointwise queries at a caller's parameter (the classes' calc_* methods :75-140, :248-310) ----
+constexpr int kSplineQOk = 0;          // RRTX_SPLINE_Q_OK
+constexpr int kSplineQOutside = 1;     // RRTX_SPLINE_Q_OUTSIDE: t < s[0] or t > s[n-1] (+-inf too): the reference returns None
+constexpr int kSplineQRefRaises = 2;   // RRTX_SPLINE_Q_REF_RAISES: t == s[n-1] or t is NaN: both range tests are false, bisect
+                                       // lands on the last knot and the reference's self.b[i] raises IndexError
+constexpr int kSplineQNoSpline = 3;    // RRTX_SPLINE_Q_NO_SPLINE: the course is kSplineDegenerate (the caller's to tell)
+
+// What the reference does with parameter t on a spline over the knots s (:86-91); only kSplineQOk may be evaluated
+RPP_HD static inline int spline_query_class(const double* s, int n, double t) {
+  if (t < s[0] || t > s[n - 1]) return kSplineQOutside;
+  if (!(t < s[n - 1])) return kSplineQRefRaises;
+  return kSplineQOk;
+}
+
+// u ** y of a query, y = 2.0 or 3.0 and u >= 0: libm pow as spline_pow takes it.  A caller's parameter can lie one ulp above a
+// knot at 0, which a sampled k * ds does not: where libm's result is below 2^-1022 (u < 2^-511 for y = 2.0, u < 2^-340.7 for
+// 3.0) it leaves through its underflow handlers, which rpp_glibc_pow does not restate (it raises its flag and returns NaN).
+// There the power is the product u * u (* u) as the hardware rounds it: 0.0 wherever libm's is 0.0 (u < 2^-537.5 / 2^-358.4),
+// and in the subnormal window between the two within one unit of the last place of libm's.
+RPP_HD static inline double spline_query_pow(double u, double y) {
+  if (u == 0.0) return 0.0;
+  int underflow = 0;
+  const double r = rpp_glibc_pow_raw(u, y, &underflow);
+  if (!underflow) return r;
+  return y == 2.0 ? u * u : u * u * u;
+}
+
+// The spline at a parameter t that spline_query_class answers with kSplineQOk.
+//   AXES == 2: out = {x, y, yaw, curvature, dx, dy, ddx, ddy} (ay .. dy: the second axis)
+//   AXES == 1: out = {y, dy, ddy} of the axis ax .. dx (ay .. dy are not read)
+// The forms are spline_eval's; the powers are spline_query_pow's.  t may be -0.0 (the reference's -0.0 < s[0] is false):
+// u = -0.0 then, and numpy's u ** 2.0 is +0.0 but u ** 3.0 is -0.0, so u3 takes the sign of u here; a sampled parameter
+// k * ds is never a negative zero.
+template <int AXES>
+RPP_HD static inline void spline_query(const double* s, const double* ax, const double* bx, const double* cx, const double* dx,
+                                       const double* ay, const double* by, const double* cy, const double* dy, int n, double t,
+                                       double* out) {
+  const int i = spline_segment(s, n, t);
+  const double u = t - s[i];
+  const double u2 = spline_query_pow(u, 2.0), u3 = __builtin_copysign(spline_query_pow(u, 3.0), u);
+  double px[3];
+  spline_axis_forms(ax, bx, cx, dx, i, u, u2, u3, px);
+  if (AXES == 1) {
+    out[0] = px[0];
+    out[1] = px[1];
+    out[2] = px[2];
+    return;
+  }
+  double py[3];
+  spline_axis_forms(ay, by, cy, dy, i, u, u2, u3, py);
+  out[0] = px[0];
+  out[1] = py[0];
+  out[2] = rpp_glibc_atan2(py[1], px[1]);
+  out[3] = spline_curvature(px[1], py[1], px[2], py[2]);
+  out[4] = px[1];
+  out[5] = py[1];
+  out[6] = px[2];
+  out[7] = py[2];
 }
 
 }  // namespace rpp

@@ -1,19 +1,28 @@
 // rrtx_api_spline.inc -- rrtx_spline_*: batched cubic-spline courses through waypoints (spline_batch.hip.h:
-// spline_fit_kernel, spline_eval_kernel); included by rrtx_api.hip
+// spline_fit_kernel, spline_eval_kernel), one-dimensional splines over the caller's knots (spline_fit1d_kernel) and
+// pointwise queries against either (spline_query_kernel); included by rrtx_api.hip
 struct rrtx_spline : DevObj {
   // device buffers, grown on demand
-  DevBuf wp_off, x, y, ds, cx, cy, tab, rec, pt_off, out, obs, hit;
-  // the last run
+  DevBuf wp_off, x, y, ds, cx, cy, tab, rec, pt_off, out, obs, hit, q_off, q_t, q_out, q_status;
+  // the last run (or fit1d: axes == 1)
   bool ran = false, has_arrays = false, has_hits = false;
+  int axes = 2;
   int64_t n = 0, n_wp = 0, n_points = 0;
   double kernel_ms = 0.0;
+  // the last query against it
+  bool queried = false, q_deriv = false;
+  int64_t n_q = 0;
+  double query_ms = 0.0;
   std::vector<rppsp::Record> h_rec;
   std::vector<int64_t> h_off;
-  std::vector<int32_t> h_hit;
+  std::vector<int32_t> h_hit, h_qst;
 };
 
 static_assert(sizeof(rppsp::Record) == sizeof(rrtx_spline_record), "rrtx_spline_record mirrors rppsp::Record");
 static_assert(rppsp::MAX_WAYPOINTS == RRTX_SPLINE_MAX_WAYPOINTS, "the waypoint limit of the header is the kernel's");
+static_assert(rpp::kSplineQOk == RRTX_SPLINE_Q_OK && rpp::kSplineQOutside == RRTX_SPLINE_Q_OUTSIDE &&
+                  rpp::kSplineQRefRaises == RRTX_SPLINE_Q_REF_RAISES && rpp::kSplineQNoSpline == RRTX_SPLINE_Q_NO_SPLINE,
+              "the query statuses of the header are the core's");
 
 inline double (*volatile libm_hypot)(double, double) = hypot;
 
@@ -63,6 +72,8 @@ static int spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
   if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
 
   s->ran = false;
+  s->queried = false;
+  s->axes = 2;
   s->has_arrays = false;
   s->has_hits = false;
   s->n = n;
@@ -180,6 +191,171 @@ static int spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
   return RRTX_OK;
 }
 
+static int spline_fit1d(rrtx_spline* s, const rrtx_spline_fit1d_batch* b) {
+  const char* fn = "rrtx_spline_fit1d: ";
+  auto bad = [&](const std::string& m) { return fail(s, RRTX_E_INVALID, std::string(fn) + m); };
+  if (!s) return bad("the spline object is NULL");
+  if (!b) return bad("the batch is NULL");
+  if (b->n < 0 || b->n > (1LL << 30)) return bad("n is negative or above 2^30");
+  if (!b->offsets) return bad("offsets is NULL");
+  const int64_t n = b->n;
+  if (!csr_ok(b->offsets, n)) return bad("offsets do not start at 0 or decrease");
+  const int64_t W = b->offsets[n];
+  if (W > 0 && (!b->knots || !b->values)) return bad("knots or values is NULL");
+  if (b->c && b->n_c != W) return bad("n_c is not the number of knots");
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t w0 = b->offsets[i], m = b->offsets[i + 1] - w0;
+    const std::string who = "spline " + std::to_string(i);
+    if (m < 2) return bad(who + " has fewer than 2 knots");
+    if (m > RRTX_SPLINE_MAX_WAYPOINTS) return bad(who + " has more than 4096 knots");
+    if (!all_finite(b->knots + w0, m) || !all_finite(b->values + w0, m)) return bad(who + ": a knot or a value is not finite");
+    for (int64_t k = 0; k < m; k++)
+      if (std::fabs(b->knots[w0 + k]) > 1.0e6 || std::fabs(b->values[w0 + k]) > 1.0e6)
+        return bad(who + ": a knot or a value is above 1e6 in magnitude");
+    for (int64_t k = 0; k + 1 < m; k++)
+      if (b->knots[w0 + k + 1] < b->knots[w0 + k]) return bad(who + ": the knots must be sorted in ascending order");
+    if (b->c && !all_finite(b->c + w0, m)) return bad(who + ": a c value is not finite");
+  }
+  if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+
+  s->ran = false;
+  s->queried = false;
+  s->axes = 1;
+  s->has_arrays = false;
+  s->has_hits = false;
+  s->n = n;
+  s->n_wp = W;
+  s->n_points = 0;
+  s->kernel_ms = 0.0;
+  s->h_rec.clear();
+  s->h_hit.clear();
+  s->h_off.assign((size_t)n + 1, 0);
+  if (n == 0) {
+    s->ran = true;
+    return RRTX_OK;
+  }
+  HIPCHK(s, hipSetDevice(s->device));
+  int rc;
+  const size_t N = (size_t)n;
+  if ((rc = s->upload(s->wp_off, b->offsets, sizeof(int64_t) * (N + 1)))) return rc;
+  if ((rc = s->upload(s->x, b->values, sizeof(double) * (size_t)W))) return rc;
+  if (b->c && (rc = s->upload(s->cx, b->c, sizeof(double) * (size_t)W))) return rc;
+  if ((rc = s->reserve(s->tab, sizeof(double) * 8 * (size_t)W))) return rc;
+  if ((rc = s->reserve(s->rec, sizeof(rppsp::Record) * N))) return rc;
+  // the knots are plane 0 of the table, where the two-axis fit puts its chord sums
+  HIPCHK(s, hipMemcpyAsync(s->tab.p, b->knots, sizeof(double) * (size_t)W, hipMemcpyHostToDevice, s->stream));
+
+  rppsp::Fit1dArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n;
+  a.W = W;
+  a.wp_off = s->wp_off.as<const int64_t>();
+  a.a = s->x.as<const double>();
+  a.c = b->c ? s->cx.as<const double>() : nullptr;
+  a.tab = s->tab.as<double>();
+  a.rec = s->rec.as<rppsp::Record>();
+  s->h_rec.resize(N);
+  float ms = 0.f;
+  const unsigned blocks = (unsigned)((n + rppsp::TPB - 1) / rppsp::TPB);
+  rc = s->timed(&ms, [&] { hipLaunchKernelGGL(rppsp::spline_fit1d_kernel, dim3(blocks), dim3(rppsp::TPB), 0, s->stream, a); },
+                [&]() -> int {
+                  HIPCHK(s, hipMemcpyAsync(s->h_rec.data(), s->rec.p, sizeof(rppsp::Record) * N, hipMemcpyDeviceToHost, s->stream));
+                  return RRTX_OK;
+                });
+  if (rc) return rc;
+  s->kernel_ms = ms;
+  s->ran = true;
+  for (size_t i = 0; i < N; i++)
+    if (s->h_rec[i].status != RRTX_SPLINE_OK) {
+      s->err = std::string(fn) + "some splines have two equal consecutive knots (see the status column)";
+      return RRTX_PARTIAL;
+    }
+  return RRTX_OK;
+}
+
+template <int AXES, bool DERIV>
+static void spline_launch_query(int64_t total, hipStream_t stream, const rppsp::QueryArgs& a) {
+  const unsigned blocks = (unsigned)((total + rppsp::TPB - 1) / rppsp::TPB);
+  hipLaunchKernelGGL((rppsp::spline_query_kernel<AXES, DERIV>), dim3(blocks), dim3(rppsp::TPB), 0, stream, a);
+}
+
+// planes of one query: x, y, yaw, k (+ dx, dy, ddx, ddy), or y (+ dy, ddy)
+static int spline_query_planes(int axes, bool deriv) { return axes == 2 ? (deriv ? 8 : 4) : (deriv ? 3 : 1); }
+
+static int spline_query(rrtx_spline* s, const rrtx_spline_query_batch* b) {
+  const char* fn = "rrtx_spline_query: ";
+  auto bad = [&](const char* m) { return fail(s, RRTX_E_INVALID, std::string(fn) + m); };
+  if (!s) return bad("the spline object is NULL");
+  if (!b) return bad("the batch is NULL");
+  // what can be said of the batch alone, then the state, then the batch against the state
+  if (b->n < 0 || b->n > (1LL << 30)) return bad("n is negative or above 2^30");
+  if (!b->q_offsets) return bad("q_offsets is NULL");
+  const int64_t n = b->n;
+  if (!csr_ok(b->q_offsets, n)) return bad("q_offsets do not start at 0 or decrease");
+  const int64_t Q = b->q_offsets[n];
+  if (Q > RRTX_SPLINE_MAX_POINTS) return bad("more than 2^28 queries");
+  if (Q > 0 && !b->t) return bad("t is NULL");
+  if (!s->ran) return fail(s, RRTX_E_STATE, std::string(fn) + "no completed run or fit1d");
+  if (n != s->n) return bad("n is not the number of splines of the last run");
+  if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+
+  s->queried = false;
+  s->q_deriv = b->want_derivatives != 0;
+  s->n_q = Q;
+  s->query_ms = 0.0;
+  s->h_qst.clear();
+  if (Q == 0) {
+    s->queried = true;
+    return RRTX_OK;
+  }
+  HIPCHK(s, hipSetDevice(s->device));
+  int rc;
+  const int planes = spline_query_planes(s->axes, s->q_deriv);
+  if ((rc = s->upload(s->q_off, b->q_offsets, sizeof(int64_t) * ((size_t)n + 1)))) return rc;
+  if ((rc = s->upload(s->q_t, b->t, sizeof(double) * (size_t)Q))) return rc;
+  if ((rc = s->reserve(s->q_out, sizeof(double) * (size_t)planes * (size_t)Q))) return rc;
+  if ((rc = s->reserve(s->q_status, sizeof(int32_t) * (size_t)Q))) return rc;
+
+  rppsp::QueryArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n;
+  a.W = s->n_wp;
+  a.Q = Q;
+  a.wp_off = s->wp_off.as<const int64_t>();
+  a.q_off = s->q_off.as<const int64_t>();
+  a.t = s->q_t.as<const double>();
+  a.x = s->x.as<const double>();
+  a.y = s->axes == 2 ? s->y.as<const double>() : a.x;
+  a.tab = s->tab.as<const double>();
+  a.rec = s->rec.as<const rppsp::Record>();
+  a.out = s->q_out.as<double>();
+  a.status = s->q_status.as<int32_t>();
+  s->h_qst.resize((size_t)Q);
+  float ms = 0.f;
+  rc = s->timed(&ms, [&] {
+    if (s->axes == 2 && s->q_deriv)
+      spline_launch_query<2, true>(Q, s->stream, a);
+    else if (s->axes == 2)
+      spline_launch_query<2, false>(Q, s->stream, a);
+    else if (s->q_deriv)
+      spline_launch_query<1, true>(Q, s->stream, a);
+    else
+      spline_launch_query<1, false>(Q, s->stream, a);
+  }, [&]() -> int {
+    HIPCHK(s, hipMemcpyAsync(s->h_qst.data(), s->q_status.p, sizeof(int32_t) * (size_t)Q, hipMemcpyDeviceToHost, s->stream));
+    return RRTX_OK;
+  });
+  if (rc) return rc;
+  s->query_ms = ms;
+  s->queried = true;
+  for (int64_t i = 0; i < Q; i++)
+    if (s->h_qst[(size_t)i] != RRTX_SPLINE_Q_OK) {
+      s->err = std::string(fn) + "some queries are outside their spline, on its last knot, NaN, or have no spline (see the status plane)";
+      return RRTX_PARTIAL;
+    }
+  return RRTX_OK;
+}
+
 extern "C" {
 
 int rrtx_spline_create(int32_t device, rrtx_spline** out) {
@@ -242,7 +418,7 @@ int rrtx_spline_get_c(rrtx_spline* s, double* cx, double* cy, int64_t cap) {
   const size_t W = (size_t)s->n_wp;
   HIPCHK(s, hipSetDevice(s->device));
   if (cx) HIPCHK(s, hipMemcpy(cx, s->tab.as<const double>() + 3 * W, sizeof(double) * W, hipMemcpyDeviceToHost));
-  if (cy) HIPCHK(s, hipMemcpy(cy, s->tab.as<const double>() + 6 * W, sizeof(double) * W, hipMemcpyDeviceToHost));
+  if (cy && s->axes == 2) HIPCHK(s, hipMemcpy(cy, s->tab.as<const double>() + 6 * W, sizeof(double) * W, hipMemcpyDeviceToHost));
   return RRTX_OK;
 }
 
@@ -253,6 +429,57 @@ int rrtx_spline_get_hits(rrtx_spline* s, int32_t* hit) {
   if (s->n == 0) return RRTX_OK;
   if (!hit) return fail(s, RRTX_E_INVALID, "rrtx_spline_get_hits: hit is NULL");
   memcpy(hit, s->h_hit.data(), sizeof(int32_t) * (size_t)s->n);
+  return RRTX_OK;
+}
+
+int rrtx_spline_fit1d(rrtx_spline* s, const rrtx_spline_fit1d_batch* b) {
+  try {
+    return spline_fit1d(s, b);
+  } catch (const std::exception& e) {
+    if (s) s->ran = false;
+    return fail(s, RRTX_E_HIP, std::string("rrtx_spline_fit1d: ") + e.what());
+  }
+}
+
+int rrtx_spline_query(rrtx_spline* s, const rrtx_spline_query_batch* b) {
+  try {
+    return spline_query(s, b);
+  } catch (const std::exception& e) {
+    if (s) s->queried = false;
+    return fail(s, RRTX_E_HIP, std::string("rrtx_spline_query: ") + e.what());
+  }
+}
+
+int rrtx_spline_get_query(rrtx_spline* s, double* x, double* y, double* yaw, double* k, double* dx, double* dy, double* ddx,
+                          double* ddy, int32_t* status, int64_t cap) {
+  const char* fn = "rrtx_spline_get_query: ";
+  if (!s) return fail(s, RRTX_E_INVALID, std::string(fn) + "the spline object is NULL");
+  if (!s->ran || !s->queried) return fail(s, RRTX_E_STATE, std::string(fn) + "no completed query");
+  if (s->axes == 1 && (x || yaw || k || dx || ddx))
+    return fail(s, RRTX_E_STATE, std::string(fn) + "one-dimensional splines have the planes y, dy and ddy only");
+  if (!s->q_deriv && (dx || dy || ddx || ddy))
+    return fail(s, RRTX_E_STATE, std::string(fn) + "the query was made without derivatives");
+  if (cap < s->n_q) return fail(s, RRTX_E_CAPACITY, std::string(fn) + "the buffers are too small");
+  if (s->n_q == 0) return RRTX_OK;
+  const size_t Q = (size_t)s->n_q;
+  HIPCHK(s, hipSetDevice(s->device));
+  double* two[8] = {x, y, yaw, k, dx, dy, ddx, ddy};
+  double* one[3] = {y, dy, ddy};
+  double** dst = s->axes == 2 ? two : one;
+  const int planes = spline_query_planes(s->axes, s->q_deriv);
+  for (int q = 0; q < planes; q++)
+    if (dst[q]) HIPCHK(s, hipMemcpy(dst[q], s->q_out.as<const double>() + q * Q, sizeof(double) * Q, hipMemcpyDeviceToHost));
+  if (status) memcpy(status, s->h_qst.data(), sizeof(int32_t) * Q);
+  return RRTX_OK;
+}
+
+int rrtx_spline_get_query_info(rrtx_spline* s, int64_t* n_queries, int32_t* axes, int32_t* has_derivatives, double* kernel_ms) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_spline_get_query_info: the spline object is NULL");
+  if (!s->ran || !s->queried) return fail(s, RRTX_E_STATE, "rrtx_spline_get_query_info: no completed query");
+  if (n_queries) *n_queries = s->n_q;
+  if (axes) *axes = s->axes;
+  if (has_derivatives) *has_derivatives = s->q_deriv ? 1 : 0;
+  if (kernel_ms) *kernel_ms = s->query_ms;
   return RRTX_OK;
 }
 

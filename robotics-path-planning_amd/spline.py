@@ -15,6 +15,18 @@ in every mode.  The spline coefficient c, which the reference takes from np.lina
                     down: bit-identical to the reference running on this host.  Slow (one dense solve per course and axis).
     c=(cx, cy)      c as data, flat over all waypoints (e.g. a recorded sx.c, sy.c): x, y, yaw, k are the reference's doubles
 
+The fitted splines stay on the device and answer at parameters of the caller's choosing -- the pointwise methods of the
+reference's classes (CubicSpline2D.calc_position / calc_yaw / calc_curvature :248-310, CubicSpline1D.calc_position /
+calc_first_derivative / calc_second_derivative :75-140), one kernel lane per query:
+
+    bs.fit(paths)                               # or run(...): the splines of the last of them answer
+    q = bs.query(s_of_my_controller)            # one array for every course, a list per course, or CSR (offsets, t)
+    q.x, q.y, q.yaw, q.k, q.status              # flat over the queries; q.of(i): the slices of course i
+    bs.fit1d(knots, values)                     # CubicSpline1D over the caller's knots; query() then gives y (dy, ddy)
+
+A query outside the knots (the reference returns None), on the last knot or NaN (the reference raises IndexError) or of a
+course without a spline is NaN in every plane and says so in status (SPLINE_Q_*).
+
 There is no CPU fallback: without a device BatchSpline raises RrtxError.
 """
 import numpy as np
@@ -58,13 +70,39 @@ def _csr(waypoints):
     return off, x, y
 
 
+def _csr1(seqs):
+    """(offsets, flat) of `seqs`: a CSR tuple (offsets, flat), a list of one sequence per spline, or one sequence of
+    numbers (a batch of one)."""
+    if (isinstance(seqs, tuple) and len(seqs) == 2 and np.ndim(seqs[0]) == 1 and np.ndim(seqs[1]) == 1
+            and np.issubdtype(np.asarray(seqs[0]).dtype, np.integer) and len(seqs[0]) >= 1
+            and int(np.asarray(seqs[0])[-1]) == len(seqs[1])):
+        return np.ascontiguousarray(seqs[0], dtype=np.int64), _f64(seqs[1]).reshape(-1)
+    if len(seqs) and all(np.ndim(v) == 0 for v in seqs):
+        seqs = [seqs]
+    rows = [_f64(v).reshape(-1) for v in seqs]
+    off = np.zeros(len(rows) + 1, dtype=np.int64)
+    if rows:
+        off[1:] = np.cumsum([len(r) for r in rows])
+    return off, (_f64(np.concatenate(rows)) if rows else np.zeros(0))
+
+
+def solve_numpy_1d(knots, values):
+    """c of one CubicSpline1D(knots, values) as the reference makes it on this host: h = np.diff(x) (:50), A and B
+    (:148-173), np.linalg.solve (:65)."""
+    return _solve_numpy(np.diff(knots), [[float(v) for v in values]])[0]
+
+
 def solve_numpy(x, y):
     """(cx, cy) of one course as the reference makes them on this host: s of CubicSpline2D.__calc_s (:240-246), A and B of
     CubicSpline1D (:148-173), np.linalg.solve (:65)."""
     s = [0]
     s.extend(np.cumsum(np.hypot(np.diff(x), np.diff(y))))
-    h = np.diff(s)
-    nx = len(x)
+    out = _solve_numpy(np.diff(s), ([float(v) for v in x], [float(v) for v in y]))
+    return out[0], out[1]
+
+
+def _solve_numpy(h, axes):
+    nx = len(h) + 1
     A = np.zeros((nx, nx))
     A[0, 0] = 1.0
     for i in range(nx - 1):
@@ -76,12 +114,12 @@ def solve_numpy(x, y):
     A[nx - 1, nx - 2] = 0.0
     A[nx - 1, nx - 1] = 1.0
     out = []
-    for a in ([float(v) for v in x], [float(v) for v in y]):
+    for a in axes:
         B = np.zeros(nx)
         for i in range(nx - 2):
             B[i + 1] = 3.0 * (a[i + 2] - a[i + 1]) / h[i + 1] - 3.0 * (a[i + 1] - a[i]) / h[i]
         out.append(np.linalg.solve(A, B))
-    return out[0], out[1]
+    return out
 
 
 def pack_batch(waypoints, ds=0.1, c=None, obstacle_list=None, robot_radius=0.0, arrays=True):
@@ -165,12 +203,48 @@ class SplineResult:
         return bool(self.hit[i] == -1)
 
 
+class SplineQueryResult:
+    """The answers of one BatchSpline.query, flat over the queries in the order given.  offsets (n + 1,) into them, one row
+    per spline; s the parameters; status (Q,) int32 SPLINE_Q_OK / _OUTSIDE / _REF_RAISES / _NO_SPLINE.  After run() or fit():
+    x, y, yaw, k and, with derivatives=True, dx, dy, ddx, ddy.  After fit1d(): y and, with derivatives=True, dy, ddy.  A plane
+    that was not made is None; every value of a query whose status is not SPLINE_Q_OK is NaN.  rc 0 or RRTX_PARTIAL;
+    kernel_ms the HIP-event time of the query kernel."""
+    PLANES = ("x", "y", "yaw", "k", "dx", "dy", "ddx", "ddy")
+
+    def __init__(self, offsets, s, status, planes, rc=0, kernel_ms=0.0):
+        self.offsets = offsets
+        self.s = s
+        self.status = status
+        for key in self.PLANES:
+            setattr(self, key, planes.get(key))
+        self.rc = rc
+        self.kernel_ms = kernel_ms
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    @property
+    def valid(self):
+        """Boolean mask of the queries that were answered (status == SPLINE_Q_OK)"""
+        return self.status == _abi.SPLINE_Q_OK
+
+    def of(self, i):
+        """The slices of spline i: a dict of s, status and every plane that was made"""
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        out = dict(s=self.s[a:b], status=self.status[a:b])
+        for key in self.PLANES:
+            if getattr(self, key) is not None:
+                out[key] = getattr(self, key)[a:b]
+        return out
+
+
 class BatchSpline:
     """Natural cubic splines through batches of waypoint lists, sampled every ds; device buffers are kept between calls of
-    run()."""
+    run().  The splines of the last run(), fit() or fit1d() answer query()."""
 
     def __init__(self, device=0):
         self._spline = _abi.Spline(device)
+        self._n = None   # splines of the last completed run / fit / fit1d
 
     def close(self):
         self._spline.close()
@@ -205,8 +279,75 @@ class BatchSpline:
             waypoints = (off, x, y)
         b, keep = pack_batch(waypoints, ds, c, obstacle_list, robot_radius, arrays)
         S = self._spline
+        self._n = None
         rc = S.run(b)
         rec, off, ms = S.records()
+        self._n = len(rec)
         w = int(keep["offsets"][-1])
         return SplineResult(rec, off, S.points(int(off[-1])) if arrays else None, S.c(w), keep["offsets"],
                             S.hits(len(rec)) if keep["obstacles"] is not None else None, rc, ms)
+
+    def fit(self, waypoints, solve="device", c=None):
+        """The splines of run() without a sample: fits every course and keeps it on the device for query().  Returns the
+        SplineResult (status, total_length, c; no arrays)."""
+        return self.run(waypoints, ds=1.0, solve=solve, c=c, arrays=False)
+
+    def fit1d(self, knots, values, solve="device", c=None):
+        """One-dimensional splines CubicSpline1D(knots_i, values_i): knots (ascending; integers become float64) and values
+        as lists of one sequence per spline, CSR tuples (offsets, flat), or one sequence each (a batch of one); 2 .. 4096
+        knots per spline.  solve and c as run() takes them, c flat over all knots.  Returns a SplineResult whose c is
+        (c, None); n_points is 0 and total_length the last knot."""
+        if solve not in ("device", "numpy"):
+            raise ValueError("BatchSpline: solve is 'device' or 'numpy'")
+        off, kn = _csr1(knots)
+        off_v, va = _csr1(values)
+        if not np.array_equal(off, off_v):
+            raise ValueError("BatchSpline: knots and values differ in shape")
+        n = len(off) - 1
+        if c is None and solve == "numpy":
+            if n and np.min(np.diff(off)) < 2:
+                raise _abi.RrtxError("rrtx_spline_fit1d: RRTX_E_INVALID a spline of fewer than 2 knots")
+            cs = []
+            with np.errstate(all="ignore"):   # equal knots: the device reports them, whatever the solve made of them
+                for i in range(n):
+                    try:
+                        cs.append(solve_numpy_1d(kn[off[i]:off[i + 1]], va[off[i]:off[i + 1]]))
+                    except np.linalg.LinAlgError:
+                        cs.append(np.zeros(off[i + 1] - off[i]))
+            c = np.nan_to_num(np.concatenate(cs)) if cs else np.zeros(0)
+        ca = None if c is None else _f64(c).reshape(-1)
+        b = _abi.SplineFit1dBatch(n=n, offsets=off.ctypes.data, knots=kn.ctypes.data, values=va.ctypes.data,
+                                  c=None if ca is None else ca.ctypes.data, n_c=0 if ca is None else len(ca))
+        S = self._spline
+        self._n = None
+        rc = S.fit1d(b)
+        rec, _, ms = S.records()
+        self._n = len(rec)
+        return SplineResult(rec, np.zeros(n + 1, dtype=np.int64), None, (S.c1d(int(off[-1])), None), off, None, rc, ms)
+
+    def query(self, s, derivatives=False):
+        """The splines of the last run(), fit() or fit1d() at the caller's parameters.  s: a list of one sequence per spline, a
+        CSR tuple (offsets, t), or one 1-D array applied to every spline; any double is taken.  Returns a
+        SplineQueryResult."""
+        if self._n is None:
+            raise _abi.RrtxError("rrtx_spline_query: RRTX_E_STATE no completed run or fit1d")
+        n = self._n
+        is_csr = (isinstance(s, tuple) and len(s) == 2 and np.ndim(s[0]) == 1 and np.ndim(s[1]) == 1
+                  and np.issubdtype(np.asarray(s[0]).dtype, np.integer) and len(s[0]) == n + 1)
+        if is_csr:
+            off, t = np.ascontiguousarray(s[0], dtype=np.int64), _f64(s[1]).reshape(-1)
+            if off[-1] != len(t):
+                raise ValueError("BatchSpline: the offsets do not describe the parameters")
+        elif isinstance(s, np.ndarray) and s.ndim == 1 or (len(s) and all(np.ndim(v) == 0 for v in s)):
+            one = _f64(s).reshape(-1)
+            off, t = np.arange(n + 1, dtype=np.int64) * len(one), np.tile(one, n)
+        else:
+            if len(s) != n:
+                raise ValueError("BatchSpline: %d lists of parameters for %d splines" % (len(s), n))
+            off, t = _csr1(list(s))
+        b = _abi.SplineQueryBatch(n=n, q_offsets=off.ctypes.data, t=t.ctypes.data if len(t) else None,
+                                  want_derivatives=int(bool(derivatives)), reserved=0)
+        S = self._spline
+        rc = S.query(b)
+        planes, status, ms = S.query_planes()
+        return SplineQueryResult(off, t, status, planes, rc, ms)
