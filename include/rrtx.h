@@ -668,7 +668,8 @@ int rrtx_spline_get_query_info(rrtx_spline* s, int64_t* n_queries, int32_t* axes
  * parameters, counts and offsets, and x and y of the linear kind.  The B-spline coefficients and the evaluation are this
  * library's own definition (banded elimination without pivoting, Cox-de Boor recurrences in a stated order: csrc/rpp_bspline.h),
  * because scipy's FITPACK is not one arithmetic; they agree with the reference to rounding.  The curvature keeps
- * the script's exponent 2.0 / 3.0 (:107).  The smoothing fit (approximate_b_spline_path with s != 0) is not provided.
+ * the script's exponent 2.0 / 3.0 (:107).  The smoothing fit (approximate_b_spline_path with s != 0) is
+ * rrtx_bspline_approximate on the same object, below.
  * The object is independent of rrtx_handle; it owns the device buffers of its runs and reuses them from call to call (they
  * grow, never shrink).  One host thread per object.  Call order: create, run, the getters of that run, run again, as often as
  * wanted; a getter before the first run returns RRTX_E_STATE. */
@@ -731,7 +732,8 @@ const char* rrtx_bspline_last_error(rrtx_bspline* s);
  * RRTX_E_NO_DEVICE. */
 int rrtx_bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b);
 /* rec: the n records of the last run; offsets (may be NULL): n + 1 entries, the exclusive sum of n_points; n_courses, n_points,
- * n_knots (each may be NULL): the course count, offsets[n], and the knots of all courses.  rec may be NULL. */
+ * n_knots (each may be NULL): the course count, offsets[n], and the knots of all courses (after rrtx_bspline_approximate: of
+ * both axes of all courses).  rec may be NULL. */
 int rrtx_bspline_get_records(rrtx_bspline* s, rrtx_bspline_record* rec, int64_t* offsets, int64_t* n_courses, int64_t* n_points,
                              int64_t* n_knots);
 /* The flat arrays of the last run, n_points doubles each, any pointer may be NULL: x, y, heading, curvature and the sample
@@ -749,6 +751,44 @@ int rrtx_bspline_get_coefficients(rrtx_bspline* s, int64_t* knot_offsets, double
 int rrtx_bspline_get_hits(rrtx_bspline* s, int32_t* hit);
 /* HIP-event time of the kernels of the last run (fit and evaluation; the prefix sum between them is not kernel time) */
 int rrtx_bspline_get_kernel_ms(rrtx_bspline* s, double* kernel_ms);
+
+/* ---- the smoothing fit of approximate_b_spline_path (csrc/bspline_smooth.hip.h, csrc/rpp_bspline_smooth.h) -------------------
+ * approximate_b_spline_path(x, y, n_path_points, degree, s) of 10_path_planning_00_bspline_path.py :12-56 for every course:
+ * UnivariateSpline(distances, x, k=degree, s=s) and the same for y -- Dierckx's fpcurf as scipy drives it, adaptive knots at data
+ * sites and a root search on the smoothing parameter --, then _evaluate_spline.  The two axes of a course have knot vectors
+ * of their own.  The knot vectors are FITPACK's; the coefficients are this library's own arithmetic (Givens rotations in a stated
+ * order) and agree with scipy to a measured tolerance.  A course with s == 0 gets the interpolating spline of
+ * rrtx_bspline_run, bit for bit. */
+#define RRTX_BSPLINE_SINGULAR 3     /* a coefficient of the smoothing fit is not finite.  The course owns no points. */
+typedef struct rrtx_bspline_axis_record {
+  int32_t n_knots;    /* knots of this axis' spline; it has n_knots - degree - 1 coefficients.  0 without a spline */
+  int32_t ier;        /* FITPACK's: 0 the smoothing spline, -1 the interpolating spline, -2 the least-squares polynomial, 2 the
+                         root search met non-monotone values, 3 it took its 20 steps; with 2 and 3 the last approximation is
+                         kept, as scipy keeps it (it warns); 1 no interval could take a further knot (FITPACK leaves that case
+                         undefined): the least-squares spline on the knots so far */
+  double fp;          /* the sum of squared residuals */
+  double p;           /* the smoothing parameter; +inf where no root search ran (ier -1, -2, or a least-squares spline) */
+  int32_t rounds;     /* knot rounds: least-squares fits */
+  int32_t iters;      /* root-search steps */
+} rrtx_bspline_axis_record;
+typedef struct rrtx_bspline_smooth_batch {
+  rrtx_bspline_batch run;       /* as for rrtx_bspline_run; param must be RRTX_BSPLINE_PARAM_NORMALISED */
+  const double* s;              /* the smoothing factor: one value, or n values when s_per_course != 0; finite and >= 0 */
+  int32_t s_per_course;
+  int32_t reserved;
+} rrtx_bspline_smooth_batch;
+/* As rrtx_bspline_run, with its argument checks and these: sb->s not NULL, every s finite and >= 0, param NORMALISED.  Returns
+ * RRTX_OK or RRTX_PARTIAL.  Afterwards rrtx_bspline_get_records, _get_points, _get_hits and _get_kernel_ms answer as after
+ * rrtx_bspline_run, except that n_knots of rrtx_bspline_get_records is the sum over both axes of every course; rrtx_bspline_get_coefficients returns RRTX_E_STATE (there is no one knot vector per course); the splines
+ * come from the two getters below, which in turn return RRTX_E_STATE after rrtx_bspline_run. */
+int rrtx_bspline_approximate(rrtx_bspline* s, const rrtx_bspline_smooth_batch* sb);
+/* rec: 2 n records of the last approximate run, axis-major: n of x, then n of y. */
+int rrtx_bspline_get_axis_records(rrtx_bspline* s, rrtx_bspline_axis_record* rec, int64_t cap);
+/* The splines of one axis (0 x, 1 y) of the last approximate run, any pointer may be NULL.  knot_offsets, coef_offsets: n + 1
+ * entries each, CSR into knots and coefficients; n_knots, n_coefs: their last entries.  cap_knots / cap_coefs: doubles
+ * available (RRTX_E_CAPACITY when too small).  A course without a spline has none of either. */
+int rrtx_bspline_get_axis_splines(rrtx_bspline* s, int32_t axis, int64_t* knot_offsets, double* knots, int64_t cap_knots,
+                                  int64_t* coef_offsets, double* coefficients, int64_t cap_coefs, int64_t* n_knots, int64_t* n_coefs);
 
 /* ---- batched arm navigation: joint-space occupancy grids and searches on the torus grid, without a planner
  * (csrc/armnav_batch.hip.h, csrc/rpp_armnav.h) ---------------------------------------------------------------------------------

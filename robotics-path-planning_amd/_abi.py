@@ -42,6 +42,7 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_spline_fit1d", "rrtx_spline_query", "rrtx_spline_get_query", "rrtx_spline_get_query_info",
            "rrtx_bspline_create", "rrtx_bspline_destroy", "rrtx_bspline_last_error", "rrtx_bspline_run", "rrtx_bspline_get_records",
            "rrtx_bspline_get_points", "rrtx_bspline_get_coefficients", "rrtx_bspline_get_hits", "rrtx_bspline_get_kernel_ms",
+           "rrtx_bspline_approximate", "rrtx_bspline_get_axis_records", "rrtx_bspline_get_axis_splines",
            "rrtx_armnav_create", "rrtx_armnav_destroy", "rrtx_armnav_last_error", "rrtx_armnav_occupancy", "rrtx_armnav_set_grids",
            "rrtx_armnav_get_grids", "rrtx_armnav_search", "rrtx_armnav_get_counts", "rrtx_armnav_get_routes",
            "rrtx_armnav_get_marks", "rrtx_armnav_get_kernel_ms",
@@ -62,6 +63,7 @@ SPLINE_OK, SPLINE_DEGENERATE, SPLINE_REF_RAISES = 0, 1, 2                       
 SPLINE_MAX_WAYPOINTS, SPLINE_MAX_POINTS = 4096, 1 << 28
 SPLINE_Q_OK, SPLINE_Q_OUTSIDE, SPLINE_Q_REF_RAISES, SPLINE_Q_NO_SPLINE = 0, 1, 2, 3        # #define RRTX_SPLINE_Q_*
 BSPLINE_OK, BSPLINE_DEGENERATE, BSPLINE_TOO_FEW = 0, 1, 2                                 # #define RRTX_BSPLINE_*
+BSPLINE_SINGULAR = 3                                                                     # rrtx_bspline_approximate only
 BSPLINE_PARAM_NORMALISED, BSPLINE_PARAM_CHORD = 0, 1
 BSPLINE_SAMPLE_LINSPACE, BSPLINE_SAMPLE_ARANGE, BSPLINE_SAMPLE_EXPLICIT = 0, 1, 2
 BSPLINE_MAX_DEGREE, BSPLINE_MAX_WAYPOINTS, BSPLINE_MAX_POINTS = 5, 4096, 1 << 28
@@ -149,6 +151,15 @@ class BSplineBatch(C.Structure):
                 ("sample_of", C.c_void_p), ("count", C.c_void_p), ("ds", C.c_void_p), ("u_offsets", C.c_void_p), ("u", C.c_void_p),
                 ("want_arrays", C.c_int32), ("reserved", C.c_int32), ("obstacles", C.c_void_p), ("n_obstacles", C.c_int64),
                 ("robot_radius", C.c_double)]
+
+
+BSPLINE_AXIS_RECORD = np.dtype([("n_knots", np.int32), ("ier", np.int32), ("fp", np.float64), ("p", np.float64),
+                                ("rounds", np.int32), ("iters", np.int32)])
+
+
+class BSplineSmoothBatch(C.Structure):
+    """rrtx_bspline_smooth_batch: the courses of one rrtx_bspline_approximate -- the run batch, and the smoothing factors."""
+    _fields_ = [("run", BSplineBatch), ("s", C.c_void_p), ("s_per_course", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ArmIKBatch(C.Structure):
@@ -293,6 +304,9 @@ def load():
     L.rrtx_bspline_get_coefficients.argtypes = [vp, vp, vp, C.c_int64, vp, vp, C.c_int64]
     L.rrtx_bspline_get_hits.argtypes = [vp, vp]
     L.rrtx_bspline_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.rrtx_bspline_approximate.argtypes = [vp, C.POINTER(BSplineSmoothBatch)]
+    L.rrtx_bspline_get_axis_records.argtypes = [vp, vp, C.c_int64]
+    L.rrtx_bspline_get_axis_splines.argtypes = [vp, i32, vp, vp, C.c_int64, vp, vp, C.c_int64, i64p, i64p]
     L.rrtx_armnav_create.argtypes = [i32, C.POINTER(vp)]
     L.rrtx_armnav_destroy.argtypes = [vp]
     L.rrtx_armnav_destroy.restype = None
@@ -1121,6 +1135,27 @@ class BSpline:
         hit = np.zeros(n, dtype=np.int32)
         self._chk(self.L.rrtx_bspline_get_hits(self._s, hit.ctypes.data), "rrtx_bspline_get_hits")
         return hit
+
+    def approximate(self, batch):
+        """batch: BSplineSmoothBatch (its arrays are kept alive by the caller).  Returns 0 or RRTX_PARTIAL."""
+        return self._chk(self.L.rrtx_bspline_approximate(self._s, C.byref(batch)), "rrtx_bspline_approximate")
+
+    def axis_records(self, n):
+        """(2, n) BSPLINE_AXIS_RECORD of the last approximate run: row 0 the x axis, row 1 the y axis."""
+        rec = np.zeros((2, n), dtype=BSPLINE_AXIS_RECORD)
+        self._chk(self.L.rrtx_bspline_get_axis_records(self._s, rec.ctypes.data, 2 * n), "rrtx_bspline_get_axis_records")
+        return rec
+
+    def axis_splines(self, axis, n):
+        """(knot_offsets (n + 1,), knots, coef_offsets (n + 1,), coefficients) of one axis of the last approximate run."""
+        nk, nc = C.c_int64(), C.c_int64()
+        what = "rrtx_bspline_get_axis_splines"
+        self._chk(self.L.rrtx_bspline_get_axis_splines(self._s, axis, None, None, 0, None, None, 0, C.byref(nk), C.byref(nc)), what)
+        koff, coff = np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+        knots, coefs = np.zeros(nk.value), np.zeros(nc.value)
+        self._chk(self.L.rrtx_bspline_get_axis_splines(self._s, axis, koff.ctypes.data, knots.ctypes.data, nk.value, coff.ctypes.data,
+                                                       coefs.ctypes.data, nc.value, None, None), what)
+        return koff, knots, coff, coefs
 
 
 class ArmNav:

@@ -13,10 +13,17 @@ offsets, and x and y of spline2d's linear kind.  This package's own definition, 
 B-spline coefficients (banded elimination without pivoting) and the evaluation (Cox-de Boor recurrences in a stated order);
 they agree with scipy to a measured tolerance.  scipy is not imported.
 
-Not provided: the smoothing fit, approximate_b_spline_path with s other than 0 -- FITPACK's adaptive knot insertion makes
-discrete decisions on residuals and is no fixed linear solve.  There is no CPU fallback: without a device BatchBSpline raises
-RrtxError.
+The smoothing fit, approximate_b_spline_path with s other than 0 (s=None included), is approximate():
+
+    res = bb.approximate(paths, 50, degree=3, s=0.5)   # approximate_b_spline_path(x_i, y_i, 50, 3, s=0.5) for every course
+
+FITPACK's adaptive knot insertion and its root search on the smoothing parameter, restated: the knot vectors are
+scipy's, the coefficients this package's own arithmetic, bit-identical to tests/bspline_smooth_oracle.py and within a measured
+tolerance of scipy.  The drop-in module rrt_amd.bspline_path_smoothing calls it; rrt_amd.bspline_path still refuses s != 0.
+There is no CPU fallback: without a device BatchBSpline raises RrtxError.
 """
+import warnings
+
 import numpy as np
 
 from . import _abi
@@ -95,6 +102,26 @@ def pack_batch(waypoints, degree=3, param=_abi.BSPLINE_PARAM_NORMALISED, n_path_
     return b, keep
 
 
+def pack_smooth_batch(waypoints, s=None, **kw):
+    """The rrtx_bspline_smooth_batch of one approximate run: (batch, keep); kw as pack_batch without param.  s: a scalar, one
+    value per course, or None (an entry None likewise): the course's waypoint count."""
+    b, keep = pack_batch(waypoints, param=_abi.BSPLINE_PARAM_NORMALISED, **kw)
+    n = int(b.n)
+    m = np.diff(keep["offsets"]).astype(np.float64)
+    if s is None:
+        sv, s_per = m, True
+    elif np.ndim(s) == 0:
+        sv, s_per = [float(s)], False
+    else:
+        if len(s) != n:
+            raise ValueError("BatchBSpline: %d values of s for %d courses" % (len(s), n))
+        sv, s_per = [m[i] if q is None else float(q) for i, q in enumerate(s)], True
+    keep["s"] = np.ascontiguousarray(sv, dtype=np.float64).reshape(-1)
+    if s_per and n == 0:
+        keep["s"] = np.zeros(1)
+    return _abi.BSplineSmoothBatch(run=b, s=keep["s"].ctypes.data, s_per_course=int(s_per), reserved=0), keep
+
+
 class BSplineResult:
     """One batch of B-spline courses.  Per course: status (BSPLINE_OK, BSPLINE_DEGENERATE coinciding waypoints, BSPLINE_TOO_FEW
     no more waypoints than the degree), n_points, degree, length (the last waypoint parameter: 1.0 from interpolate(), s[-1]
@@ -153,6 +180,28 @@ class BSplineResult:
         return bool(self.hit[i] == -1)
 
 
+class BSplineSmoothResult(BSplineResult):
+    """One batch of smoothing B-spline courses (BatchBSpline.approximate).  status, n_points, degree, length, offsets, x, y,
+    yaw, k, u, hit / free / is_free(i), course(i), rc and kernel_ms as BSplineResult (status may also be BSPLINE_SINGULAR: a
+    coefficient is not finite; such a course owns no points).  The two axes of a course have splines of their own, so these
+    are pairs (x axis, y axis): knots with knot_offsets (n + 1,), coefficients with coef_offsets (n + 1,), and per course
+    ier (FITPACK's: 0 smoothing spline, -1 interpolating, -2 least-squares polynomial, 2 / 3 the root search stopped early
+    and the last approximation is kept; 1 no knot could be added, the least-squares spline on the knots so far), fp (the sum of squared residuals), p (the smoothing parameter, +inf without a root
+    search), rounds (knot rounds) and iters (root-search steps).  wp_offsets: the waypoint CSR of the batch."""
+
+    def __init__(self, records, offsets, arrays, axes, axis_records, wp_offsets, hit=None, rc=0, kernel_ms=0.0):
+        BSplineResult.__init__(self, records, offsets, arrays, tuple(a[1] for a in axes), tuple(a[0] for a in axes),
+                               tuple(a[3] for a in axes), wp_offsets, hit, rc, kernel_ms)
+        self.coef_offsets = tuple(a[2] for a in axes)
+        for key in ("ier", "fp", "p", "rounds", "iters"):
+            setattr(self, key, tuple(axis_records[a][key].copy() for a in (0, 1)))
+
+    def _raise_for(self, i, who):
+        if int(self.status[i]) == _abi.BSPLINE_SINGULAR:
+            raise _abi.RrtxError("%s: the smoothing fit of course %d has a coefficient that is not finite" % (who, i))
+        BSplineResult._raise_for(self, i, who)
+
+
 def _check_range(u_offsets, u, status, length):
     """interp1d's bounds check for explicit samples: ValueError outside [0, length] of a course that has a spline"""
     for i in np.nonzero(status == _abi.BSPLINE_OK)[0]:
@@ -166,7 +215,8 @@ def _check_range(u_offsets, u, status, length):
 
 
 class BatchBSpline:
-    """Interpolating B-splines of degree 1 .. 5 through batches of waypoint lists; device buffers are kept between calls."""
+    """Interpolating and smoothing B-splines of degree 1 .. 5 through batches of waypoint lists; device buffers are kept
+    between calls."""
 
     def __init__(self, device=0):
         self._bs = _abi.BSpline(device)
@@ -207,6 +257,33 @@ class BatchBSpline:
         and hits only."""
         return self._run(waypoints, arrays, degree=degree, param=_abi.BSPLINE_PARAM_NORMALISED, n_path_points=n_path_points,
                          u=u, obstacle_list=obstacle_list, robot_radius=robot_radius)
+
+    def approximate(self, waypoints, n_path_points=None, degree=3, s=None, u=None, obstacle_list=None, robot_radius=0.0,
+                    arrays=True):
+        """approximate_b_spline_path(x, y, n_path_points, degree, s) (10_path_planning_00_bspline_path.py :12-56) for every
+        course: UnivariateSpline(distances, x, k=degree, s=s) and the same for y, then _evaluate_spline at
+        np.linspace(0.0, 1.0, n_path_points).  s: a scalar, one value per course, or None -- the script's default, each
+        course's waypoint count (an entry None of a list means the same); finite and >= 0.  A course with s == 0 is
+        interpolate()'s, bit for bit.  The knot vectors are scipy's; the coefficients agree with scipy to a measured
+        tolerance.  Where FITPACK's root search stops early (ier 2 or 3) the last approximation is kept, as
+        scipy keeps it, and one RuntimeWarning per call names how many axes.  The other arguments as interpolate().
+        Returns a BSplineSmoothResult."""
+        sb, keep = pack_smooth_batch(waypoints, s, arrays=arrays, degree=degree, n_path_points=n_path_points, u=u,
+                                     obstacle_list=obstacle_list, robot_radius=robot_radius)
+        S = self._bs
+        rc = S.approximate(sb)
+        rec, off, _, ms = S.records()
+        if keep["u"] is not None:
+            _check_range(keep["u_offsets"], keep["u"], rec["status"], rec["length"])
+        arec = S.axis_records(len(rec))
+        axes = [S.axis_splines(a, len(rec)) for a in (0, 1)]
+        early = int(np.sum((arec["ier"] > 0) & (rec["status"] == _abi.BSPLINE_OK)[None, :]))
+        if early:
+            warnings.warn("BatchBSpline.approximate: the fit stopped early on %d axes (ier 2 or 3: the root search on the "
+                          "smoothing parameter; ier 1: no knot could be added); their last approximation is kept" % early,
+                          RuntimeWarning, stacklevel=2)
+        return BSplineSmoothResult(rec, off, S.points(int(off[-1])) if arrays else None, axes, arec, keep["offsets"],
+                                   S.hits(len(rec)) if keep["obstacles"] is not None else None, rc, ms)
 
     def spline2d(self, waypoints, ds=0.1, kind="cubic", obstacle_list=None, robot_radius=0.0, arrays=True, u=None):
         """The driver loop of 10_path_planning_00_spline_2d.py (:45-54) for every course: Spline2D(x, y, kind), s of

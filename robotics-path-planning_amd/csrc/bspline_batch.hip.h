@@ -100,6 +100,27 @@ __global__ __launch_bounds__(FIT_TPB) void bspline_fit_kernel(Args a) {
   if (a.hit) a.hit[c] = r.n_points > 0 ? -1 : -2;
 }
 
+// The obstacle test of one point (px, py) of course `lo`, by every lane of the wave: the lowest index touched goes into
+// hit[lo], with one atomic where the wave lies within one course.  Shared with bspline_smooth.hip.h.
+__device__ inline void check_point(const Args& a, int64_t lo, double px, double py) {
+  const uint32_t NONE = 0xffffffffu;
+  const uint32_t h = (uint32_t)rpp::first_hit(a.obs, a.n_obs, px, py);
+  if (!__any(h != NONE)) return;
+  uint32_t* out = (uint32_t*)a.hit;
+  const int course = (int)lo;   // n <= 2^30
+  const int course0 = __shfl(course, 0);
+  if (__all(course == course0)) {   // the wave lies within one course: one atomic
+    uint32_t mn = h;
+    for (int off = 32; off > 0; off >>= 1) {
+      const uint32_t o = (uint32_t)__shfl_xor((int)mn, off);
+      mn = o < mn ? o : mn;
+    }
+    if ((threadIdx.x & 63) == 0) atomicMin(out + course0, mn);
+  } else if (h != NONE) {
+    atomicMin(out + course, h);
+  }
+}
+
 // With CHECK a lane past the last point does not leave: it stays as a copy of the last point (the same course, the same
 // answer), so every lane of a wave takes part in the shuffles below.  hit[] is read as unsigned for the minimum: -1
 // (free) is then the largest value, and -2 belongs to courses without points.
@@ -135,24 +156,7 @@ __global__ __launch_bounds__(TPB) void bspline_eval_kernel(Args a) {
     for (int q = 0; q < 4; q++) a.out[q * total + idx] = p[q];
     a.out[4 * total + idx] = v;
   }
-  if (CHECK) {
-    const uint32_t NONE = 0xffffffffu;
-    const uint32_t h = (uint32_t)rpp::first_hit(a.obs, a.n_obs, p[0], p[1]);
-    if (!__any(h != NONE)) return;
-    uint32_t* out = (uint32_t*)a.hit;
-    const int course = (int)lo;   // n <= 2^30
-    const int course0 = __shfl(course, 0);
-    if (__all(course == course0)) {   // the wave lies within one course: one atomic
-      uint32_t mn = h;
-      for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)mn, off);
-        mn = o < mn ? o : mn;
-      }
-      if ((threadIdx.x & 63) == 0) atomicMin(out + course0, mn);
-    } else if (h != NONE) {
-      atomicMin(out + course, h);
-    }
-  }
+  if (CHECK) check_point(a, lo, p[0], p[1]);
 }
 
 }  // namespace rppbs

@@ -210,8 +210,16 @@ RPP_HD static inline void bspline_eval_linear(const double* s, const double* ax,
   q[5] = 0.0;
 }
 
-// The course's point at parameter v: out = {x, y, heading, curvature}.  The curvature keeps the script's exponent
+// out = {x, y, heading, curvature} from q = {x, y, dx, dy, ddx, ddy}.  The curvature keeps the script's exponent
 // (:107, np.power(dx * dx + dy * dy, 2.0 / 3.0)): it is not the geometric 3 / 2.
+RPP_HD static inline void bspline_point(const double* q, double* out) {
+  out[0] = q[0];
+  out[1] = q[1];
+  out[2] = rpp_glibc_atan2(q[3], q[2]);
+  out[3] = (q[5] * q[2] - q[4] * q[3]) / spline_pow(q[2] * q[2] + q[3] * q[3], 2.0 / 3.0);
+}
+
+// The course's point at parameter v: out = {x, y, heading, curvature}
 RPP_HD static inline void bspline_eval(const double* u, const double* ax, const double* ay, const double* t, const double* cx,
                                        const double* cy, int m, int k, int param, double v, double* out) {
   double q[6];
@@ -226,10 +234,7 @@ RPP_HD static inline void bspline_eval(const double* u, const double* ax, const 
       default: bspline_eval_k<5>(t, m, cx, cy, v, q); break;
     }
   }
-  out[0] = q[0];
-  out[1] = q[1];
-  out[2] = rpp_glibc_atan2(q[3], q[2]);
-  out[3] = (q[5] * q[2] - q[4] * q[3]) / spline_pow(q[2] * q[2] + q[3] * q[3], 2.0 / 3.0);
+  bspline_point(q, out);
 }
 
 // Coefficients of one course of m > k waypoints: the band matrix in ab -- plane d = j - i + k of row i at ab[d * stride + i],

@@ -25,6 +25,7 @@
 #include "steer_batch.hip.h"
 #include "spline_batch.hip.h"
 #include "bspline_batch.hip.h"
+#include "bspline_smooth.hip.h"
 #include "armnav_batch.hip.h"
 #include "armik_batch.hip.h"
 #include "armdh_batch.hip.h"

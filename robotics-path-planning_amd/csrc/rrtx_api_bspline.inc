@@ -1,22 +1,25 @@
-// rrtx_api_bspline.inc -- rrtx_bspline_*: batched interpolating B-spline courses through waypoints (bspline_batch.hip.h:
-// bspline_fit_kernel, bspline_eval_kernel); included by rrtx_api.hip
+// rrtx_api_bspline.inc -- rrtx_bspline_*: batched B-spline courses through waypoints, interpolating (bspline_batch.hip.h:
+// bspline_fit_kernel, bspline_eval_kernel) and smoothing (bspline_smooth.hip.h: bspline_smooth_fit_kernel,
+// bspline_smooth_eval_kernel); included by rrtx_api.hip
 struct rrtx_bspline : DevObj {
   // device buffers, grown on demand
-  DevBuf wp_off, x, y, degree, mode_of, count, ds, us_off, us, tab, knots, rec, pt_off, out, obs, hit;
+  DevBuf wp_off, x, y, degree, mode_of, count, ds, us_off, us, tab, knots, rec, pt_off, out, obs, hit, sm, arec;
   // the last run
-  bool ran = false, has_arrays = false, has_hits = false;
+  bool ran = false, has_arrays = false, has_hits = false, smooth = false;   // smooth: the last run was rrtx_bspline_approximate
   int64_t n = 0, n_wp = 0, n_points = 0, n_knots = 0;
   double kernel_ms = 0.0;
   std::vector<rppbs::Record> h_rec;
   std::vector<int64_t> h_off, h_wp_off, h_knot_off;
   std::vector<int32_t> h_hit;
+  std::vector<rpp::SmoothInfo> h_arec;   // [2][n], axis-major
 };
 
 static_assert(sizeof(rppbs::Record) == sizeof(rrtx_bspline_record), "rrtx_bspline_record mirrors rppbs::Record");
 static_assert(rppbs::MAX_WAYPOINTS == RRTX_BSPLINE_MAX_WAYPOINTS, "the waypoint limit of the header is the kernel's");
 static_assert(rpp::kBsplineMaxDegree == RRTX_BSPLINE_MAX_DEGREE, "the degree limit of the header is the core's");
+static_assert(sizeof(rpp::SmoothInfo) == sizeof(rrtx_bspline_axis_record), "rrtx_bspline_axis_record mirrors rpp::SmoothInfo");
 static_assert(rpp::kBsplineOk == RRTX_BSPLINE_OK && rpp::kBsplineDegenerate == RRTX_BSPLINE_DEGENERATE &&
-                  rpp::kBsplineTooFew == RRTX_BSPLINE_TOO_FEW,
+                  rpp::kBsplineTooFew == RRTX_BSPLINE_TOO_FEW && rpp::kBsplineSingular == RRTX_BSPLINE_SINGULAR,
               "the statuses of the header are the core's");
 static_assert(rpp::kBsplineNormalised == RRTX_BSPLINE_PARAM_NORMALISED && rpp::kBsplineChord == RRTX_BSPLINE_PARAM_CHORD &&
                   rpp::kBsplineLinspace == RRTX_BSPLINE_SAMPLE_LINSPACE && rpp::kBsplineArange == RRTX_BSPLINE_SAMPLE_ARANGE &&
@@ -29,8 +32,14 @@ static void bspline_launch_eval(int64_t total, hipStream_t stream, const rppbs::
   hipLaunchKernelGGL((rppbs::bspline_eval_kernel<STORE, CHECK>), dim3(blocks), dim3(rppbs::TPB), 0, stream, a);
 }
 
-static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b) {
-  const char* fn = "rrtx_bspline_run: ";
+template <bool STORE, bool CHECK>
+static void bspline_launch_smooth_eval(int64_t total, hipStream_t stream, const rppbs::SmoothArgs& a) {
+  const unsigned blocks = (unsigned)((total + rppbs::TPB - 1) / rppbs::TPB);
+  hipLaunchKernelGGL((rppbs::bspline_smooth_eval_kernel<STORE, CHECK>), dim3(blocks), dim3(rppbs::TPB), 0, stream, a);
+}
+
+// rrtx_bspline_run (sb NULL) and rrtx_bspline_approximate (sb the smoothing batch, b its run part)
+static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b, const rrtx_bspline_smooth_batch* sb, const char* fn) {
   auto bad = [&](const char* m) { return fail(s, RRTX_E_INVALID, std::string(fn) + m); };
   if (!s) return bad("the bspline object is NULL");
   if (!b) return bad("the batch is NULL");
@@ -57,6 +66,13 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b) {
     if (std::fabs(b->x[i]) > 1.0e6 || std::fabs(b->y[i]) > 1.0e6) return bad("a coordinate is above 1e6 in magnitude");
   if (!all_finite(b->obstacles, 3 * b->n_obstacles)) return bad("an obstacle entry is not finite");
   if (!std::isfinite(b->robot_radius)) return bad("robot_radius is not finite");
+  const int64_t n_s = sb && sb->s_per_course ? n : 1;
+  if (sb) {
+    if (!sb->s) return bad("s is NULL");
+    if (b->param != RRTX_BSPLINE_PARAM_NORMALISED) return bad("param is not RRTX_BSPLINE_PARAM_NORMALISED");
+    for (int64_t i = 0; i < n_s; i++)
+      if (!std::isfinite(sb->s[i]) || !(sb->s[i] >= 0.0)) return bad("an s is not finite or negative");
+  }
   // the sampling modes' own arguments, and the points in all
   auto mode_of = [&](int64_t i) { return b->sample_of ? b->sample_of[i] : b->sample; };
   bool any_lin = false, any_ara = false, any_exp = false;
@@ -103,6 +119,8 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b) {
   s->ran = false;
   s->has_arrays = false;
   s->has_hits = false;
+  s->smooth = sb != nullptr;
+  s->h_arec.clear();
   s->n = n;
   s->n_wp = W;
   s->n_points = 0;
@@ -143,8 +161,13 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b) {
     if ((rc = s->upload(s->us, b->u, sizeof(double) * (size_t)n_us))) return rc;
   }
   if ((rc = s->upload(s->obs, rows.data(), sizeof(double) * rows.size()))) return rc;
-  if ((rc = s->reserve(s->tab, sizeof(double) * rppbs::TAB_PLANES * (size_t)W))) return rc;
-  if ((rc = s->reserve(s->knots, sizeof(double) * ((size_t)W + rppbs::KNOT_SLACK * N)))) return rc;
+  const size_t planes = sb ? rppbs::SMOOTH_TAB_PLANES : rppbs::TAB_PLANES, knot_planes = sb ? 2 : 1;
+  if ((rc = s->reserve(s->tab, sizeof(double) * planes * (size_t)W))) return rc;
+  if ((rc = s->reserve(s->knots, sizeof(double) * knot_planes * ((size_t)W + rppbs::KNOT_SLACK * N)))) return rc;
+  if (sb) {
+    if ((rc = s->upload(s->sm, sb->s, sizeof(double) * (size_t)n_s))) return rc;
+    if ((rc = s->reserve(s->arec, sizeof(rpp::SmoothInfo) * 2 * N))) return rc;
+  }
   if ((rc = s->reserve(s->rec, sizeof(rppbs::Record) * N))) return rc;
   if (n_obs > 0 && (rc = s->reserve(s->hit, sizeof(int32_t) * N))) return rc;
 
@@ -169,16 +192,31 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b) {
   a.knots = s->knots.as<double>();
   a.rec = s->rec.as<rppbs::Record>();
   a.hit = n_obs > 0 ? s->hit.as<int32_t>() : nullptr;
+  rppbs::SmoothArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  if (sb) {
+    sa.s = s->sm.as<const double>();
+    sa.s_per_course = sb->s_per_course != 0;
+    sa.arec = s->arec.as<rpp::SmoothInfo>();
+    s->h_arec.resize(2 * N);
+  }
 
   // the fit, and its records
   s->h_rec.resize(N);
   float ms = 0.f;
-  const unsigned fit_blocks = (unsigned)((n + rppbs::FIT_TPB - 1) / rppbs::FIT_TPB);
-  rc = s->timed(&ms, [&] { hipLaunchKernelGGL(rppbs::bspline_fit_kernel, dim3(fit_blocks), dim3(rppbs::FIT_TPB), 0, s->stream, a); },
-                [&]() -> int {
-                  HIPCHK(s, hipMemcpyAsync(s->h_rec.data(), s->rec.p, sizeof(rppbs::Record) * N, hipMemcpyDeviceToHost, s->stream));
-                  return RRTX_OK;
-                });
+  const unsigned fit_blocks = (unsigned)(((sb ? 2 * n : n) + rppbs::FIT_TPB - 1) / rppbs::FIT_TPB);
+  rc = s->timed(&ms, [&] {
+    if (sb) {
+      sa.a = a;
+      hipLaunchKernelGGL(rppbs::bspline_smooth_fit_kernel, dim3(fit_blocks), dim3(rppbs::FIT_TPB), 0, s->stream, sa);
+    } else {
+      hipLaunchKernelGGL(rppbs::bspline_fit_kernel, dim3(fit_blocks), dim3(rppbs::FIT_TPB), 0, s->stream, a);
+    }
+  }, [&]() -> int {
+    HIPCHK(s, hipMemcpyAsync(s->h_rec.data(), s->rec.p, sizeof(rppbs::Record) * N, hipMemcpyDeviceToHost, s->stream));
+    if (sb) HIPCHK(s, hipMemcpyAsync(s->h_arec.data(), s->arec.p, sizeof(rpp::SmoothInfo) * 2 * N, hipMemcpyDeviceToHost, s->stream));
+    return RRTX_OK;
+  });
   if (rc) return rc;
   s->kernel_ms = ms;
 
@@ -189,7 +227,8 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b) {
     s->h_off[i] = tot;
     s->h_knot_off[i] = knots;
     if (s->h_rec[i].status != RRTX_BSPLINE_OK) partial = true;
-    else knots += (b->offsets[i + 1] - b->offsets[i]) + s->h_rec[i].degree + 1;
+    else if (!sb) knots += (b->offsets[i + 1] - b->offsets[i]) + s->h_rec[i].degree + 1;
+    if (sb) knots += s->h_arec[i].n_knots + s->h_arec[N + i].n_knots;
     tot += s->h_rec[i].n_points;
     if (tot > RRTX_BSPLINE_MAX_POINTS) return bad(many);
   }
@@ -207,8 +246,15 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b) {
     a.out = store ? s->out.as<double>() : nullptr;
     a.obs = check ? s->obs.as<const double>() : nullptr;
     a.n_obs = n_obs;
+    sa.a = a;
     rc = s->timed(&ms, [&] {
-      if (store && check)
+      if (sb && store && check)
+        bspline_launch_smooth_eval<true, true>(tot, s->stream, sa);
+      else if (sb && store)
+        bspline_launch_smooth_eval<true, false>(tot, s->stream, sa);
+      else if (sb)
+        bspline_launch_smooth_eval<false, true>(tot, s->stream, sa);
+      else if (store && check)
         bspline_launch_eval<true, true>(tot, s->stream, a);
       else if (store)
         bspline_launch_eval<true, false>(tot, s->stream, a);
@@ -227,7 +273,7 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b) {
   s->has_hits = check;
   s->ran = true;
   if (partial) {
-    s->err = std::string(fn) + "some courses have coinciding waypoints, or no more waypoints than their degree (see the status column)";
+    s->err = std::string(fn) + "some courses have coinciding waypoints, no more waypoints than their degree, or no finite fit (see the status column)";
     return RRTX_PARTIAL;
   }
   return RRTX_OK;
@@ -255,11 +301,74 @@ const char* rrtx_bspline_last_error(rrtx_bspline* s) { return s ? s->err.c_str()
 
 int rrtx_bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b) {
   try {   // host allocations (records, offsets, messages) must not throw across the ABI
-    return bspline_run(s, b);
+    return bspline_run(s, b, nullptr, "rrtx_bspline_run: ");
   } catch (const std::exception& e) {
     if (s) s->ran = false;
     return fail(s, RRTX_E_HIP, std::string("rrtx_bspline_run: ") + e.what());
   }
+}
+
+int rrtx_bspline_approximate(rrtx_bspline* s, const rrtx_bspline_smooth_batch* sb) {
+  try {
+    return bspline_run(s, sb ? &sb->run : nullptr, sb, "rrtx_bspline_approximate: ");
+  } catch (const std::exception& e) {
+    if (s) s->ran = false;
+    return fail(s, RRTX_E_HIP, std::string("rrtx_bspline_approximate: ") + e.what());
+  }
+}
+
+int rrtx_bspline_get_axis_records(rrtx_bspline* s, rrtx_bspline_axis_record* rec, int64_t cap) {
+  const char* fn = "rrtx_bspline_get_axis_records: ";
+  if (!s) return fail(s, RRTX_E_INVALID, std::string(fn) + "the bspline object is NULL");
+  if (!s->ran || !s->smooth) return fail(s, RRTX_E_STATE, std::string(fn) + "no completed rrtx_bspline_approximate");
+  if (s->n == 0) return RRTX_OK;
+  if (!rec) return fail(s, RRTX_E_INVALID, std::string(fn) + "rec is NULL");
+  if (cap < 2 * s->n) return fail(s, RRTX_E_CAPACITY, std::string(fn) + "the buffer is too small");
+  memcpy(rec, s->h_arec.data(), sizeof(rrtx_bspline_axis_record) * 2 * (size_t)s->n);
+  return RRTX_OK;
+}
+
+int rrtx_bspline_get_axis_splines(rrtx_bspline* s, int32_t axis, int64_t* knot_offsets, double* knots, int64_t cap_knots,
+                                  int64_t* coef_offsets, double* coefficients, int64_t cap_coefs, int64_t* n_knots, int64_t* n_coefs) {
+  const char* fn = "rrtx_bspline_get_axis_splines: ";
+  if (!s) return fail(s, RRTX_E_INVALID, std::string(fn) + "the bspline object is NULL");
+  if (!s->ran || !s->smooth) return fail(s, RRTX_E_STATE, std::string(fn) + "no completed rrtx_bspline_approximate");
+  if (axis != 0 && axis != 1) return fail(s, RRTX_E_INVALID, std::string(fn) + "axis is not 0 or 1");
+  try {
+    const size_t W = (size_t)s->n_wp, N = (size_t)s->n;
+    std::vector<int64_t> koff(N + 1, 0), coff(N + 1, 0);
+    for (size_t c = 0; c < N; c++) {
+      const int nk = s->h_arec[axis * N + c].n_knots;
+      koff[c + 1] = koff[c] + nk;
+      coff[c + 1] = coff[c] + (nk > 0 ? nk - s->h_rec[c].degree - 1 : 0);
+    }
+    if (n_knots) *n_knots = koff[N];
+    if (n_coefs) *n_coefs = coff[N];
+    if (knots && cap_knots < koff[N]) return fail(s, RRTX_E_CAPACITY, std::string(fn) + "the knot buffer is too small");
+    if (coefficients && cap_coefs < coff[N]) return fail(s, RRTX_E_CAPACITY, std::string(fn) + "the coefficient buffer is too small");
+    if (knot_offsets) memcpy(knot_offsets, koff.data(), sizeof(int64_t) * (N + 1));
+    if (coef_offsets) memcpy(coef_offsets, coff.data(), sizeof(int64_t) * (N + 1));
+    if (W == 0 || (!knots && !coefficients)) return RRTX_OK;
+    HIPCHK(s, hipSetDevice(s->device));
+    const size_t plane = W + rppbs::KNOT_SLACK * N;
+    std::vector<double> raw(plane > W ? plane : W);
+    if (knots && koff[N] > 0) {   // the device keeps a course's knots at wp_off + 6 c of the axis' plane: packed here
+      HIPCHK(s, hipMemcpy(raw.data(), s->knots.as<const double>() + axis * plane, sizeof(double) * plane, hipMemcpyDeviceToHost));
+      for (size_t c = 0; c < N; c++)
+        if (koff[c + 1] > koff[c])
+          memcpy(knots + koff[c], raw.data() + s->h_wp_off[c] + rppbs::KNOT_SLACK * c, sizeof(double) * (size_t)(koff[c + 1] - koff[c]));
+    }
+    if (coefficients && coff[N] > 0) {
+      HIPCHK(s, hipMemcpy(raw.data(), s->tab.as<const double>() + ((size_t)axis * rppbs::SMOOTH_AXIS_PLANES + 1) * W, sizeof(double) * W,
+                          hipMemcpyDeviceToHost));
+      for (size_t c = 0; c < N; c++)
+        if (coff[c + 1] > coff[c])
+          memcpy(coefficients + coff[c], raw.data() + s->h_wp_off[c], sizeof(double) * (size_t)(coff[c + 1] - coff[c]));
+    }
+  } catch (const std::exception& e) {
+    return fail(s, RRTX_E_HIP, std::string(fn) + e.what());
+  }
+  return RRTX_OK;
 }
 
 int rrtx_bspline_get_records(rrtx_bspline* s, rrtx_bspline_record* rec, int64_t* offsets, int64_t* n_courses, int64_t* n_points,
@@ -292,6 +401,7 @@ int rrtx_bspline_get_coefficients(rrtx_bspline* s, int64_t* knot_offsets, double
   const char* fn = "rrtx_bspline_get_coefficients: ";
   if (!s) return fail(s, RRTX_E_INVALID, std::string(fn) + "the bspline object is NULL");
   if (!s->ran) return fail(s, RRTX_E_STATE, std::string(fn) + "no completed run");
+  if (s->smooth) return fail(s, RRTX_E_STATE, std::string(fn) + "the last run was rrtx_bspline_approximate: its axes have knot vectors of their own (rrtx_bspline_get_axis_splines)");
   if (knots && cap_knots < s->n_knots) return fail(s, RRTX_E_CAPACITY, std::string(fn) + "the knot buffer is too small");
   if ((cx || cy) && cap_wp < s->n_wp) return fail(s, RRTX_E_CAPACITY, std::string(fn) + "the coefficient buffers are too small");
   if (knot_offsets) memcpy(knot_offsets, s->h_knot_off.data(), sizeof(int64_t) * ((size_t)s->n + 1));

@@ -5,7 +5,8 @@ number defines for its driver cell (`RRT`, `BITStar`, `Node`, `path_smoothing`, 
 against `10_path_planning_01_rrt_04_rrt_star.py` runs after `from rrt_amd.rrt_04 import *`.  `rrt_amd.dubins_path`, `rrt_amd.reeds_shepp_path`
 and `rrt_amd.lqr_path` do the same for the three stand-alone steering scripts (`plan_dubins_path`, `reeds_shepp_path_planning`,
 `LQRPlanner`), `rrt_amd.cubic_spline_path` for the cubic-spline script (`calc_spline_course`, `CubicSpline1D`, `CubicSpline2D`), `rrt_amd.bspline_path` and
-`rrt_amd.spline_2d` for the two scipy spline scripts (`interpolate_b_spline_path` and its helpers; `Spline2D`), `rrt_amd.bazier_path` for the
+`rrt_amd.spline_2d` for the two scipy spline scripts (`interpolate_b_spline_path` and its helpers; `Spline2D`), `rrt_amd.bspline_path_smoothing`
+for the same B-spline script with its smoothing fit (`approximate_b_spline_path` for any `s`), `rrt_amd.bazier_path` for the
 Bezier script (`calc_4points_bezier_path`, `calc_bezier_path` and its pointwise helpers), `rrt_amd.arm_obstacle_navigation` for the
 arm script (`NLinkArm`, `get_occupancy_grid`, `astar_torus` and its helpers), `rrt_amd.simple_2d_inverse_kinematics` for the two
 planar inverse-kinematics scripts (`inverse_kinematics`, `forward_kinematics`, `jacobian_inverse`, `NLinkArm` and their helpers),
@@ -48,6 +49,7 @@ BatchSpline = _pkg.BatchSpline
 SplineQueryResult = _pkg.SplineQueryResult
 BatchBSpline = _pkg.BatchBSpline
 BSplineResult = _pkg.BSplineResult
+BSplineSmoothResult = _pkg.BSplineSmoothResult
 BatchArmNav = _pkg.BatchArmNav
 BatchArmIK = _pkg.BatchArmIK
 ArmIKResult = _pkg.ArmIKResult

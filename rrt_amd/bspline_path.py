@@ -3,10 +3,13 @@ interpolate_b_spline_path :59-88, _calc_distance_vector :91-96, _evaluate_spline
 The MI355X mirror: every call is a batch of one on robotics-path-planning_amd/bspline.py; no CPU fallback, no scipy.
 
 Interpolation only.  The smoothing fit -- approximate_b_spline_path with s other than 0.0, s=None (the script's default, meaning
-s = len(x)) included -- is FITPACK's adaptive knot insertion with a root search on the smoothing parameter: it makes discrete
-decisions on residuals, so it is no fixed linear solve and has no device counterpart; such a call raises NotImplementedError.
+s = len(x)) included -- is FITPACK's adaptive knot insertion with a root search on the smoothing parameter; this module does not
+serve it: such a call raises NotImplementedError here.
 s=0.0 is the interpolation.  The curvature keeps the script's exponent 2.0 / 3.0 (:107).  Degree 1, where the script raises in
-derivative(2), returns a zero curvature.  plot_curvature is refused: nothing is drawn, and no matplotlib is imported."""
+derivative(2), returns a zero curvature.  plot_curvature is refused: nothing is drawn, and no matplotlib is imported.
+
+Which module does what: this module is the interpolating half and keeps refusing s other than 0.0; rrt_amd.bspline_path_smoothing
+is the whole script, its approximate_b_spline_path running the smoothing fit on the device (BatchBSpline.approximate)."""
 import numpy as np
 
 from . import bspline as _bs
