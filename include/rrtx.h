@@ -29,7 +29,8 @@ extern "C" {
                                 rrtx_tracker_* entry points: new functions on objects of their own, no layout change; later additions of
                                 the same kind: rrtx_steer_set_obstacles, rrtx_steer_get_hits, rrtx_steer_solve_lqr, rrtx_steer_get_ends,
                                 rrtx_steer_solve_bezier, rrtx_steer_solve_bezier_cp, rrtx_steer_get_curvature, rrtx_steer_get_kmax,
-                                rrtx_steer_get_control_points); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
+                                rrtx_steer_get_control_points, rrtx_steer_solve_all, rrtx_steer_get_cand_counts,
+                                rrtx_steer_get_cand_summary, rrtx_steer_get_cand_points, rrtx_steer_select_free); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
                                 rrtx_copy_results_device, per-instance yaw and informed rotation; 4: rrtx_plan_many,
                                 rrtx_selfcheck, rrtx_stats.main_shape / main_f32, rrtx_plan_begin / _step, rrtx_set_launch_bound,
                                 RRTX_ST_REF_HANGS, rrtx_rccl_* */
@@ -423,6 +424,46 @@ int rrtx_steer_set_obstacles(rrtx_steer* s, const double* obstacles, int64_t m, 
  * curve (status != RRTX_STEER_OK), nothing was tested.  RRTX_E_STATE before the first solve and when the last solve ran
  * with no obstacle list set. */
 int rrtx_steer_get_hits(rrtx_steer* s, int32_t* hit);
+
+/* ---- every candidate curve of a pair, and the shortest one that is free (csrc/steer_batch.hip.h steer_*_all) ---------------
+ * rrtx_steer_solve_all restates calc_paths (10_path_planning_00_reeds_shepp_path.py :483-503): for RRTX_STEER_RS every Path
+ * that set_path :141-159 kept for the pair, in the list's order -- reeds_shepp_path_planning :506-515, which rrtx_steer_solve
+ * serves, is the minimum over that list.  For RRTX_STEER_DUBINS the candidates are one per entry of the word list, in list
+ * order, where the word is feasible: candidate w is what plan_dubins_path (10_path_planning_00_dubins_path.py :109-197)
+ * returns with selected_types=[w], bit for bit; a word listed twice is two candidates.
+ * Arguments, checks and return values are those of rrtx_steer_solve, except that the word list may hold up to 16 entries.
+ * A pair whose status is not RRTX_STEER_OK has no candidates.  The result is CSR twice -- pairs -> candidates -> points -- and
+ * sized from the counts; more than 2^31 - 1 candidates in all is RRTX_E_OVERFLOW.  With a list set by
+ * rrtx_steer_set_obstacles every candidate is tested as rrtx_steer_solve tests the one curve.  The solve replaces the
+ * result of an earlier rrtx_steer_solve* on `s` (its getters return RRTX_E_STATE until rrtx_steer_select_free or another
+ * solve), and a later rrtx_steer_solve* replaces the candidates. */
+int rrtx_steer_solve_all(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
+                         const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
+                         const int32_t* word_order, int32_t n_words, int32_t want_points);
+/* Pairs, candidates and candidate points (0 without points) of the last rrtx_steer_solve_all and the HIP-event time of its
+ * kernels; any pointer may be NULL. */
+int rrtx_steer_get_cand_counts(rrtx_steer* s, int64_t* n_pairs, int64_t* n_candidates, int64_t* n_points, double* kernel_ms);
+/* Any pointer may be NULL.  Per pair: status, cand_offsets (n_pairs + 1: pair p owns the candidates cand_offsets[p] ..
+ * cand_offsets[p + 1] - 1).  Per candidate, in the reference's list order: pair; variant (RS: 4 * word family + symmetry of
+ * generate_path :366-421, 0..47; Dubins: the position in the word list); n_seg, seg_len (rows of 5), modes (rows of 8) and
+ * length as rrtx_steer_get_summary gives them for one curve (Path.lengths, Path.ctypes after :500); key: what the kind's
+ * planner minimises -- RS abs(L / maxc), which is Path.L after :501; Dubins the cost of :1220 in curvature units; hit as
+ * rrtx_steer_get_hits (RRTX_E_STATE without an obstacle list); offsets (n_candidates + 1) into the point arrays
+ * (RRTX_E_STATE without points). */
+int rrtx_steer_get_cand_summary(rrtx_steer* s, int32_t* status, int64_t* cand_offsets, int32_t* pair, int32_t* variant,
+                                int32_t* n_seg, double* seg_len, char* modes, double* length, double* key, int32_t* hit,
+                                int64_t* offsets);
+/* The flat x, y, yaw of all candidates and Path.directions (+1 / -1 per point, interpolate :480; Dubins: all +1). */
+int rrtx_steer_get_cand_points(rrtx_steer* s, double* x, double* y, double* yaw, int8_t* directions, int64_t cap);
+/* After an rrtx_steer_solve_all with an obstacle list (else RRTX_E_STATE): per pair, the free candidate (hit == -1) with
+ * the smallest key, the first in list order among equal keys; where no candidate is free, the same choice among all of
+ * them, which is the curve of rrtx_steer_solve with its hit; a pair without candidates keeps the row rrtx_steer_solve
+ * gives it.  The chosen curves become the result of `s` as if rrtx_steer_solve had found them: rrtx_steer_get_counts,
+ * _get_summary, _get_points (when the candidates have points), _get_hits and _get_kernel_ms (all launches since the
+ * rrtx_steer_solve_all) serve them.  chosen (the candidate's index, -1 where the pair has none), rank (the position of the
+ * chosen candidate among the pair's candidates ordered by key, list order among equal keys: 0 <=> the curve of
+ * rrtx_steer_solve) and n_free are (n_pairs,) arrays, any may be NULL.  Returns RRTX_OK or RRTX_PARTIAL as rrtx_steer_solve. */
+int rrtx_steer_select_free(rrtx_steer* s, int32_t* chosen, int32_t* rank, int32_t* n_free);
 
 /* ---- the third steering function on the same object: LQR rollouts between point pairs (csrc/steer_batch.hip.h, csrc/rpp_lqr.h)
  * Replaces LQRPlanner.lqr_planning (10_path_planning_00_lqr_path.py :24-66, the same lines as rrt_09 :944-986) called once per

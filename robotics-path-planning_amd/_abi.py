@@ -35,6 +35,8 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_steer_get_hits", "rrtx_steer_solve_lqr", "rrtx_steer_get_ends",
            "rrtx_steer_solve_bezier", "rrtx_steer_solve_bezier_cp", "rrtx_steer_get_curvature", "rrtx_steer_get_kmax",
            "rrtx_steer_get_control_points",
+           "rrtx_steer_solve_all", "rrtx_steer_get_cand_counts", "rrtx_steer_get_cand_summary", "rrtx_steer_get_cand_points",
+           "rrtx_steer_select_free",
            "rrtx_tracker_create", "rrtx_tracker_destroy", "rrtx_tracker_last_error", "rrtx_tracker_run",
            "rrtx_tracker_get_counts", "rrtx_tracker_get_records", "rrtx_tracker_get_arrays", "rrtx_tracker_get_kernel_ms",
            "rrtx_spline_create", "rrtx_spline_destroy", "rrtx_spline_last_error", "rrtx_spline_run", "rrtx_spline_get_records",
@@ -269,6 +271,11 @@ def load():
     L.rrtx_steer_get_curvature.argtypes = [vp, vp, C.c_int64]
     L.rrtx_steer_get_kmax.argtypes = [vp, vp]
     L.rrtx_steer_get_control_points.argtypes = [vp, vp, C.POINTER(i32)]
+    L.rrtx_steer_solve_all.argtypes = L.rrtx_steer_solve.argtypes
+    L.rrtx_steer_get_cand_counts.argtypes = [vp, i64p, i64p, i64p, C.POINTER(C.c_double)]
+    L.rrtx_steer_get_cand_summary.argtypes = [vp] * 12
+    L.rrtx_steer_get_cand_points.argtypes = [vp, vp, vp, vp, vp, C.c_int64]
+    L.rrtx_steer_select_free.argtypes = [vp, vp, vp, vp]
     L.rrtx_tracker_create.argtypes = [i32, C.POINTER(vp)]
     L.rrtx_tracker_destroy.argtypes = [vp]
     L.rrtx_tracker_destroy.restype = None
@@ -766,7 +773,8 @@ class Steer:
             raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_steer_last_error(self._s).decode()))
         return rc
 
-    def solve(self, kind, starts, goals, curvature, step_size, word_order=None, points=True, product=False):
+    def solve(self, kind, starts, goals, curvature, step_size, word_order=None, points=True, product=False,
+              _fn="rrtx_steer_solve"):
         """starts / goals: float64 arrays (n, 3) -- product: (ns, 3) and (ng, 3); curvature: a float or one value per pair;
         word_order: None or a sequence of Dubins word indices.  Returns 0 or RRTX_PARTIAL."""
         st = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
@@ -780,10 +788,60 @@ class Steer:
             raise ValueError("solve: %d curvatures for %d pairs" % (len(cv), n_pairs))
         wo = None if word_order is None else np.ascontiguousarray(word_order, dtype=np.int32).reshape(-1)
         self._keep = (st, go, cv, wo)
-        return self._chk(self.L.rrtx_steer_solve(self._s, int(kind), int(bool(product)), len(st), len(go), st.ctypes.data,
-                                                 go.ctypes.data, cv.ctypes.data, int(per_pair), float(step_size),
-                                                 None if wo is None else wo.ctypes.data, 0 if wo is None else len(wo),
-                                                 int(bool(points))), "rrtx_steer_solve")
+        return self._chk(getattr(self.L, _fn)(self._s, int(kind), int(bool(product)), len(st), len(go), st.ctypes.data,
+                                              go.ctypes.data, cv.ctypes.data, int(per_pair), float(step_size),
+                                              None if wo is None else wo.ctypes.data, 0 if wo is None else len(wo),
+                                              int(bool(points))), _fn)
+
+    def solve_all(self, kind, starts, goals, curvature, step_size, word_order=None, points=True, product=False):
+        """As solve(), for every candidate curve of every pair (rrtx_steer_solve_all); word_order may repeat a word."""
+        return self.solve(kind, starts, goals, curvature, step_size, word_order=word_order, points=points, product=product,
+                          _fn="rrtx_steer_solve_all")
+
+    def cand_counts(self):
+        """(pairs, candidates, candidate points, kernel ms) of the last solve_all."""
+        n, m, k, ms = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
+        self._chk(self.L.rrtx_steer_get_cand_counts(self._s, C.byref(n), C.byref(m), C.byref(k), C.byref(ms)),
+                  "rrtx_steer_get_cand_counts")
+        return n.value, m.value, k.value, ms.value
+
+    def cand_summary(self, hits=False, offsets=True):
+        """dict of the last solve_all: status (n,), cand_offsets (n + 1,); per candidate pair, variant, n_seg, seg_len (m, 5),
+        modes (m,) bytes, length, key; hit with hits=True and offsets (m + 1,) with offsets=True, else None."""
+        n, m, _, _ = self.cand_counts()
+        d = dict(status=np.zeros(n, dtype=np.int32), cand_offsets=np.zeros(n + 1, dtype=np.int64),
+                 pair=np.zeros(m, dtype=np.int32), variant=np.zeros(m, dtype=np.int32), n_seg=np.zeros(m, dtype=np.int32),
+                 seg_len=np.zeros((m, 5)), modes=np.zeros(m, dtype="S8"), length=np.zeros(m), key=np.zeros(m),
+                 hit=np.zeros(m, dtype=np.int32) if hits else None, offsets=np.zeros(m + 1, dtype=np.int64) if offsets else None)
+        order = ("status", "cand_offsets", "pair", "variant", "n_seg", "seg_len", "modes", "length", "key", "hit", "offsets")
+        self._chk(self.L.rrtx_steer_get_cand_summary(self._s, *[None if d[k] is None else d[k].ctypes.data for k in order]),
+                  "rrtx_steer_get_cand_summary")
+        return d
+
+    def cand_offsets(self):
+        """(n + 1,) int64: pair p owns the candidates cand_offsets[p] .. cand_offsets[p + 1] - 1 (no device copy)."""
+        n, _, _, _ = self.cand_counts()
+        off = np.zeros(n + 1, dtype=np.int64)
+        self._chk(self.L.rrtx_steer_get_cand_summary(self._s, None, off.ctypes.data, *([None] * 9)),
+                  "rrtx_steer_get_cand_summary")
+        return off
+
+    def cand_points(self):
+        """The flat (x, y, yaw, directions int8) of the last solve_all."""
+        _, _, k, _ = self.cand_counts()
+        x = np.zeros(k); y = np.zeros(k); w = np.zeros(k); d = np.zeros(k, dtype=np.int8)
+        self._chk(self.L.rrtx_steer_get_cand_points(self._s, x.ctypes.data, y.ctypes.data, w.ctypes.data, d.ctypes.data, k),
+                  "rrtx_steer_get_cand_points")
+        return x, y, w, d
+
+    def select_free(self):
+        """rrtx_steer_select_free on the last solve_all: (rc, chosen, rank, n_free); the chosen curves are then the result
+        summary(), points() and hits() serve."""
+        n, _, _, _ = self.cand_counts()
+        ch = np.zeros(n, dtype=np.int32); rk = np.zeros(n, dtype=np.int32); nf = np.zeros(n, dtype=np.int32)
+        rc = self._chk(self.L.rrtx_steer_select_free(self._s, ch.ctypes.data, rk.ctypes.data, nf.ctypes.data),
+                       "rrtx_steer_select_free")
+        return rc, ch, rk, nf
 
     def solve_lqr(self, starts, goals, step_size, max_time=100.0, goal_dist=0.1, points=True, product=False):
         """starts / goals: float64 arrays (n, 2) -- product: (ns, 2) and (ng, 2); step_size > 0: the resampled rollout,

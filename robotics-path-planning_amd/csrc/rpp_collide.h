@@ -27,4 +27,26 @@ RPP_HD inline int32_t first_hit(const double* rows, int64_t m, double x, double 
   return -1;
 }
 
+// The choice among the n >= 1 candidate curves of one pair (steer_batch.hip.h steer_select_free): key[i] is what the kind's
+// own planner minimises, hit[i] the candidate's first_hit minimum (-1: free).  *chosen: the free candidate with the smallest
+// key, the first in list order among equal keys (a strict <, as paths.index(min(...)) and `best > cost` pick it); where
+// none is free, the same choice over all candidates: the planner's own curve.  *rank: the position of the chosen candidate
+// when the candidates are ordered by key, list order among equal keys (0 <=> it is the planner's own curve).
+RPP_HD inline void pick_free(const double* key, const int32_t* hit, int n, int* chosen, int* rank, int* n_free) {
+  int best = 0, bfree = -1, nf = 0;
+  for (int i = 0; i < n; i++) {
+    if (key[i] < key[best]) best = i;
+    if (hit[i] != -1) continue;
+    nf++;
+    if (bfree < 0 || key[i] < key[bfree]) bfree = i;
+  }
+  const int ch = bfree >= 0 ? bfree : best;
+  int r = 0;
+  for (int i = 0; i < n; i++)
+    if (key[i] < key[ch] || (key[i] == key[ch] && i < ch)) r++;
+  *chosen = ch;
+  *rank = r;
+  *n_free = nf;
+}
+
 }  // namespace rpp

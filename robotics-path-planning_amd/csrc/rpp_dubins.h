@@ -323,6 +323,14 @@ RPP_HD static inline void dubins_prepare(DubinsPlan* P, double sx, double sy, do
   P->total = total;
 }
 
+// The candidate of one word: what plan_dubins_path(..., selected_types=[word]) prepares (numpy's zero, as the batch kernels
+// ask for it); P->ok is 0 where the word is not feasible.  dubins_key: the cost dubins_prepare compares between words :1220.
+RPP_HD static inline void dubins_candidate(DubinsPlan* P, double sx, double sy, double syaw, double gx, double gy,
+                                           double gyaw, double curv, int32_t word) {
+  dubins_prepare(P, sx, sy, syaw, gx, gy, gyaw, curv, &word, 1, true);
+}
+RPP_HD static inline double dubins_key(const DubinsPlan& P) { return dabs(P.len[0]) + dabs(P.len[1]) + dabs(P.len[2]); }
+
 // local-frame point j (0-based) of segment s; sl/cl = sin/cos of the interpolation length when the caller has them
 // tabulated (arc, inner point), else computed here
 RPP_HD static inline void dubins_seg_point(const DubinsPlan& P, int s, int j, double curv, double* lx, double* ly,

@@ -267,18 +267,18 @@ RPP_HD static inline uint32_t rs_code(const char* ct) {
   for (int i = 0; ct[i]; i++) c |= (uint32_t)(ct[i] == 'L' ? 1 : (ct[i] == 'S' ? 2 : 3)) << (2 * i);
   return c;
 }
-// set_path :1061-1080 over the variants in the reference's order + `paths.index(min(...))` :1436.
-// st[k], d[k][5], ct[k][6], n[k] for k = 4 * w + var.  Returns the chosen k, -1: None, < -1: the reference raises.
+// set_path :1061-1080 over the variants in the reference's order: the list generate_path returns (and calc_paths of the
+// stand-alone script, 10_path_planning_00_reeds_shepp_path.py :483-503, hands on whole), as the variants kept[0 .. np - 1]
+// in list order with their L in curvature units.  st[k], d[k][5], ct[k][6], n[k] for k = 4 * w + var.  Returns np; 0 also
+// where the reference returns [] at "Step size too large"; < 0: the reference raises.
 template <typename D5, typename C6>
-RPP_HD static inline int rs_select(const int32_t* st, const D5* d, const C6* ct, const int32_t* n, double step,
-                                   double maxc) {
-  int kept[RS_MAXP];
-  double keptL[RS_MAXP];
+RPP_HD static inline int rs_kept(const int32_t* st, const D5* d, const C6* ct, const int32_t* n, double step, int* kept,
+                                 double* keptL) {
   int np = 0;
   for (int k = 0; k < 48; k++) {
     if (st[k] == 0) continue;
     if (st[k] < 0) return st[k];   // -3 / -4
-    if (st[k] == 2) return -1;
+    if (st[k] == 2) return 0;
     const double L = rs_sum_abs(d[k], n[k]);
     bool skip = false;
     for (int i = 0; i < np; i++)
@@ -288,6 +288,16 @@ RPP_HD static inline int rs_select(const int32_t* st, const D5* d, const C6* ct,
     keptL[np] = L;
     np++;
   }
+  return np;
+}
+// rs_kept + `paths.index(min(...))` :1436.  Returns the chosen k, -1: None, < -1: the reference raises.
+template <typename D5, typename C6>
+RPP_HD static inline int rs_select(const int32_t* st, const D5* d, const C6* ct, const int32_t* n, double step,
+                                   double maxc) {
+  int kept[RS_MAXP];
+  double keptL[RS_MAXP];
+  const int np = rs_kept(st, d, ct, n, step, kept, keptL);
+  if (np < 0) return np;
   if (np == 0) return -1;
   int bi = 0;
   double bl = dabs(keptL[0] / maxc);
@@ -361,6 +371,42 @@ RPP_HD static inline void rs_point(const RsCourse& C, int k, double* wx, double*
   *wy = -C.sg * lx + C.cg * ly + C.sy;
   *wyaw = angle_mod_pi(lyaw + C.syaw);
 }
+// `1 if length > 0.0 else -1` of interpolate :1401 for point k of the course (length: the segment's, in curvature units)
+RPP_HD static inline int rs_point_dir(const RsCourse& C, int k) {
+  int sgm = 0;
+  while (sgm + 1 < C.nl && k >= C.first[sgm + 1]) sgm++;
+  return C.len[sgm] > 0.0 ? 1 : -1;
+}
+// the 48 variants of generate_path :1298-1340 in the reference's order, on one thread
+RPP_HD static inline void rs_variants(const RsFrame& F, int32_t* st, int32_t* n, double (*d)[5], char (*ct)[6]) {
+  for (int k = 0; k < 48; k++) {
+    int nn = 0;
+    st[k] = rs_variant(k >> 2, k & 3, F, d[k], ct[k], &nn);
+    n[k] = nn;
+    if (st[k] < 0 || st[k] == 2) {   // the reference stops here; nothing later is looked at
+      for (int q = k + 1; q < 48; q++) st[q] = 0;
+      break;
+    }
+  }
+}
+// calc_paths of the stand-alone script (10_path_planning_00_reeds_shepp_path.py :483-503) up to the courses: every path
+// generate_path returns, in list order.  Candidate i is variant kept[i] (4 * word family + symmetry) with the segment
+// lengths d[kept[i]] in curvature units (Path.lengths = d / maxc) and Path.L = L[i] / maxc.  np < 0: the reference raises.
+struct RsPaths {
+  int32_t st[48], n[48];
+  double d[48][5];
+  char ct[48][6];
+  int kept[RS_MAXP];
+  double L[RS_MAXP];
+  int np;
+};
+RPP_HD static inline void rs_calc_paths(double sx, double sy, double syaw, double gx, double gy, double gyaw, double maxc,
+                                        double step_size, RsPaths* S) {
+  RsFrame F;
+  rs_frame(sx, sy, syaw, gx, gy, gyaw, maxc, step_size, &F);
+  rs_variants(F, S->st, S->n, S->d, S->ct);
+  S->np = rs_kept(S->st, S->d, S->ct, S->n, F.step, S->kept, S->L);
+}
 // reeds_shepp_path_planning :1426-1441; writes at most cap points
 RPP_HD static inline void rs_plan(double sx, double sy, double syaw, double gx, double gy, double gyaw, double maxc,
                                   double step_size, double* px, double* py, double* pyaw, int cap, RsResult* R) {
@@ -372,15 +418,7 @@ RPP_HD static inline void rs_plan(double sx, double sy, double syaw, double gx, 
   int32_t st[48], n[48];
   double d[48][5];
   char ct[48][6];
-  for (int k = 0; k < 48; k++) {
-    int nn = 0;
-    st[k] = rs_variant(k >> 2, k & 3, F, d[k], ct[k], &nn);
-    n[k] = nn;
-    if (st[k] < 0 || st[k] == 2) {   // the reference stops here; nothing later is looked at
-      for (int q = k + 1; q < 48; q++) st[q] = 0;
-      break;
-    }
-  }
+  rs_variants(F, st, n, d, ct);
   const int sel = rs_select(st, d, ct, n, F.step, maxc);
   if (sel < -1) {
     R->err = sel;

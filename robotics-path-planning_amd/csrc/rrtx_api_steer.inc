@@ -15,6 +15,17 @@ struct rrtx_steer : DevObj {
   int64_t n = 0, n_points = 0;
   double kernel_ms = 0.0;
   std::vector<int64_t> h_offsets;
+  // the last rrtx_steer_solve_all: every candidate of every pair.  Pair-level status is `status` above; everything per
+  // candidate lives in buffers of its own, so that rrtx_steer_select_free can write an ordinary result beside them.
+  DevBuf c_ncand, c_off, c_pair, c_variant, c_key, c_nseg, c_total, c_seglen, c_modes, c_npts, c_plan, c_hit, c_poff, c_px, c_py,
+      c_pyaw, c_pdir, c_chosen, c_rank, c_nfree;
+  bool cand_solved = false, cand_points = false, cand_hits = false;
+  int cand_kind = rppsb::KIND_DUBINS, cand_flag = 0;
+  int64_t cand_pairs = 0, n_cand = 0, cand_n_points = 0;
+  double cand_ms = 0.0;
+  rppsb::Args cand_args;    // the candidates' Args of that solve (device pointers into the buffers above)
+  rppsb::CandArgs cand_c;
+  std::vector<int64_t> h_cand_off, h_cand_poff;
 };
 
 namespace {
@@ -67,10 +78,11 @@ const char* rrtx_steer_last_error(rrtx_steer* s) { return s ? s->err.c_str() : n
 
 static int steer_run(rrtx_steer* s, const SteerJob& j);
 
-static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
+// What rrtx_steer_solve and rrtx_steer_solve_all check of their arguments, before any HIP call; max_words: the longest word
+// list the entry point takes
+static int steer_check(rrtx_steer* s, const char* fn, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
                        const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
-                       const int32_t* word_order, int32_t n_words, int32_t want_points) {
-  const char* fn = "rrtx_steer_solve: ";
+                       const int32_t* word_order, int32_t n_words, int32_t max_words) {
   auto bad = [&](const char* m) { return fail(s, RRTX_E_INVALID, std::string(fn) + m); };
   if (!s) return bad("the steer object is NULL");
   if (kind != RRTX_STEER_DUBINS && kind != RRTX_STEER_RS) return bad("unknown kind");
@@ -81,7 +93,7 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
     return bad("Dubins curves are interpolated at the reference's default step_size = 0.1; another step is not supported");
   if (word_order) {
     if (kind != RRTX_STEER_DUBINS) return bad("a word order applies to Dubins curves only");
-    if (n_words < 0 || n_words > 6) return bad("n_words outside 0..6");
+    if (n_words < 0 || n_words > max_words) return bad(max_words == 6 ? "n_words outside 0..6" : "n_words outside 0..16");
     for (int i = 0; i < n_words; i++)
       if (word_order[i] < 0 || word_order[i] > 5) return bad("a word index outside 0..5");
   }
@@ -119,6 +131,16 @@ static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, 
                                                  : D / step_size + 20.0 / (step_size * cmin);
     if (!(pts <= 4194304.0)) return bad("the poses are so far apart for this curvature and step that a curve could exceed 2^22 points");
   }
+  return RRTX_OK;
+}
+
+static int steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
+                       const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
+                       const int32_t* word_order, int32_t n_words, int32_t want_points) {
+  const char* fn = "rrtx_steer_solve: ";
+  if (int rc = steer_check(s, fn, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size, word_order,
+                           n_words, 6))
+    return rc;
   const SteerJob job = {fn, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size, word_order, n_words,
                         want_points, 0.0, 0.0};
   return steer_run(s, job);
@@ -144,6 +166,7 @@ static int steer_run(rrtx_steer* s, const SteerJob& j) {
   s->has_points = false;
   s->has_hits = false;
   s->has_k = false;
+  s->cand_solved = false;   // the inputs the candidates point into are overwritten
   s->kind = kind;
   s->n = np;
   s->n_points = 0;
@@ -374,6 +397,7 @@ static int steer_run_bezier(rrtx_steer* s, const BezierJob& j) {
   s->has_points = false;
   s->has_hits = false;
   s->has_k = false;
+  s->cand_solved = false;   // the inputs the candidates point into are overwritten
   s->kind = rppsb::KIND_BEZIER;
   s->bez_m = m;
   s->n = np;
@@ -679,6 +703,367 @@ int rrtx_steer_get_hits(rrtx_steer* s, int32_t* hit) {
   HIPCHK(s, hipSetDevice(s->device));
   HIPCHK(s, hipMemcpy(hit, s->hit.p, sizeof(int32_t) * (size_t)s->n, hipMemcpyDeviceToHost));
   return RRTX_OK;
+}
+
+// ---- every candidate curve of a pair, and the shortest one that is free ----------------------------------------------------
+// exclusive prefix sum of counts (negative ones count as none) into off[0 .. n]; returns the total
+static int64_t steer_prefix(const std::vector<int32_t>& cnt, std::vector<int64_t>& off) {
+  off.resize(cnt.size() + 1);
+  int64_t tot = 0;
+  for (size_t i = 0; i < cnt.size(); i++) {
+    off[i] = tot;
+    tot += cnt[i] > 0 ? cnt[i] : 0;
+  }
+  off[cnt.size()] = tot;
+  return tot;
+}
+
+static int steer_solve_all(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
+                           const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
+                           const int32_t* word_order, int32_t n_words, int32_t want_points) {
+  const char* fn = "rrtx_steer_solve_all: ";
+  if (int rc = steer_check(s, fn, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size, word_order,
+                           n_words, rppsb::CAND_MAX_WORDS))
+    return rc;
+  if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  const int64_t n_goals = product ? ng : n, np = product ? n * ng : n;
+  const int64_t nc = curvature_per_pair ? np : 1;
+  const int64_t n_obs = (int64_t)(s->h_obs.size() / 3);
+  const bool stage2 = want_points || n_obs > 0;
+  const bool dubins = kind == RRTX_STEER_DUBINS;
+
+  s->solved = false;   // `status` and the inputs are this solve's now
+  s->cand_solved = false;
+  s->cand_points = want_points != 0;
+  s->cand_hits = n_obs > 0;
+  s->cand_kind = kind;
+  s->cand_flag = 0;
+  s->cand_pairs = np;
+  s->n_cand = 0;
+  s->cand_n_points = 0;
+  s->cand_ms = 0.0;
+  s->h_cand_off.assign(1, 0);
+  s->h_cand_poff.assign(1, 0);
+  if (np == 0) {
+    s->cand_solved = true;
+    return RRTX_OK;
+  }
+  HIPCHK(s, hipSetDevice(s->device));
+  int rc;
+  const size_t N = (size_t)np;
+  if ((rc = s->reserve(s->status, sizeof(int32_t) * N))) return rc;
+  if ((rc = s->reserve(s->c_ncand, sizeof(int32_t) * N))) return rc;
+  if ((rc = s->reserve(s->c_off, sizeof(int64_t) * (N + 1)))) return rc;
+  if ((rc = s->reserve(s->flag, sizeof(int32_t)))) return rc;
+  if (n_obs > 0 && s->obs_dirty) {
+    if ((rc = s->upload(s->obs, s->h_obs.data(), sizeof(double) * s->h_obs.size()))) return rc;
+    s->obs_dirty = false;
+  }
+  if ((rc = s->upload(s->starts, starts, sizeof(double) * 3 * (size_t)n))) return rc;
+  if ((rc = s->upload(s->goals, goals, sizeof(double) * 3 * (size_t)n_goals))) return rc;
+  if ((rc = s->upload(s->curv, curvature, sizeof(double) * (size_t)nc))) return rc;
+  HIPCHK(s, hipMemsetAsync(s->flag.p, 0, sizeof(int32_t), s->stream));
+
+  rppsb::Args& a = s->cand_args;
+  rppsb::CandArgs& c = s->cand_c;
+  memset(&a, 0, sizeof(a));
+  memset(&c, 0, sizeof(c));
+  a.starts = s->starts.as<const double>();
+  a.goals = s->goals.as<const double>();
+  a.curv = curvature_per_pair ? s->curv.as<const double>() : nullptr;
+  a.curv0 = curvature[0];
+  a.step = step_size;
+  a.ng = product ? ng : 1;
+  a.product = product ? 1 : 0;
+  a.want_points = stage2 ? 1 : 0;
+  a.flag = s->flag.as<int32_t>();
+  c.n_pairs = np;
+  c.n_order = word_order ? n_words : 6;
+  for (int i = 0; i < rppsb::CAND_MAX_WORDS; i++) c.order[i] = (word_order && i < n_words) ? word_order[i] : (i < 6 ? i : 0);
+  c.status = s->status.as<int32_t>();
+  c.ncand = s->c_ncand.as<int32_t>();
+
+  // count, prefix sum, emit
+  const unsigned blk = (unsigned)((np + rppsb::TPB - 1) / rppsb::TPB);
+  const unsigned rblk = (unsigned)((np + rppsb::RS_PAIRS - 1) / rppsb::RS_PAIRS);
+  std::vector<int32_t> cnt(N);
+  int32_t flag = 0;
+  float ms = 0.f;
+  rc = s->timed(&ms, [&] {
+    if (dubins)
+      hipLaunchKernelGGL(rppsb::steer_dubins_all<false>, dim3(blk), dim3(rppsb::TPB), 0, s->stream, a, c);
+    else
+      hipLaunchKernelGGL(rppsb::steer_rs_all<false>, dim3(rblk), dim3(rppsb::RS_TPB), 0, s->stream, a, c);
+  }, [&]() -> int {
+    HIPCHK(s, hipMemcpyAsync(&flag, s->flag.p, sizeof(flag), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(s, hipMemcpyAsync(cnt.data(), s->c_ncand.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
+    return RRTX_OK;
+  });
+  if (rc) return rc;
+  s->cand_ms = ms;
+  s->cand_flag = flag;
+  const int64_t NC = steer_prefix(cnt, s->h_cand_off);
+  if (NC > 0x7fffffffLL) return fail(s, RRTX_E_OVERFLOW, std::string(fn) + "more than 2^31 - 1 candidates");
+  s->n_cand = NC;
+  s->h_cand_poff.assign((size_t)NC + 1, 0);
+  if (NC > 0) {
+    const size_t M = (size_t)NC;
+    if ((rc = s->upload(s->c_off, s->h_cand_off.data(), sizeof(int64_t) * (N + 1)))) return rc;
+    if ((rc = s->reserve(s->c_pair, sizeof(int32_t) * M))) return rc;
+    if ((rc = s->reserve(s->c_variant, sizeof(int32_t) * M))) return rc;
+    if ((rc = s->reserve(s->c_key, sizeof(double) * M))) return rc;
+    if ((rc = s->reserve(s->c_nseg, sizeof(int32_t) * M))) return rc;
+    if ((rc = s->reserve(s->c_total, sizeof(double) * M))) return rc;
+    if ((rc = s->reserve(s->c_seglen, sizeof(double) * 5 * M))) return rc;
+    if ((rc = s->reserve(s->c_modes, 8 * M))) return rc;
+    if ((rc = s->reserve(s->c_npts, sizeof(int32_t) * M))) return rc;
+    if (n_obs > 0 && (rc = s->reserve(s->c_hit, sizeof(int32_t) * M))) return rc;
+    if (stage2) {
+      if ((rc = s->reserve(s->c_plan, (dubins ? sizeof(rpp::DubinsPlan) : sizeof(rpp::RsCourse)) * M))) return rc;
+      if ((rc = s->reserve(s->c_poff, sizeof(int64_t) * (M + 1)))) return rc;
+    }
+    c.cand_off = s->c_off.as<const int64_t>();
+    c.pair = s->c_pair.as<int32_t>();
+    c.variant = s->c_variant.as<int32_t>();
+    c.key = s->c_key.as<double>();
+    a.n = NC;
+    a.cand_pair = s->c_pair.as<const int32_t>();
+    a.nseg = s->c_nseg.as<int32_t>();
+    a.total = s->c_total.as<double>();
+    a.seglen = s->c_seglen.as<double>();
+    a.modes = s->c_modes.as<char>();
+    a.npts = s->c_npts.as<int32_t>();
+    a.dplan = s->c_plan.as<rpp::DubinsPlan>();
+    a.course = s->c_plan.as<rpp::RsCourse>();
+    if (n_obs > 0) {
+      a.obs = s->obs.as<const double>();
+      a.n_obs = n_obs;
+      a.hit = s->c_hit.as<int32_t>();
+    }
+    const unsigned cblk = (unsigned)((NC + rppsb::TPB - 1) / rppsb::TPB);
+    std::vector<int32_t> pcnt(stage2 ? M : 0);
+    rc = s->timed(&ms, [&] {
+      if (dubins) {
+        hipLaunchKernelGGL(rppsb::steer_dubins_all<true>, dim3(blk), dim3(rppsb::TPB), 0, s->stream, a, c);
+      } else {
+        hipLaunchKernelGGL(rppsb::steer_rs_all<true>, dim3(rblk), dim3(rppsb::RS_TPB), 0, s->stream, a, c);
+        if (stage2) hipLaunchKernelGGL(rppsb::steer_rs_course, dim3(cblk), dim3(rppsb::TPB), 0, s->stream, a);
+      }
+    }, [&]() -> int {
+      if (stage2) HIPCHK(s, hipMemcpyAsync(pcnt.data(), s->c_npts.p, sizeof(int32_t) * M, hipMemcpyDeviceToHost, s->stream));
+      return RRTX_OK;
+    });
+    if (rc) return rc;
+    s->cand_ms += ms;
+    if (stage2) {
+      const int64_t tot = steer_prefix(pcnt, s->h_cand_poff);
+      s->cand_n_points = want_points ? tot : 0;
+      if (tot > 0) {
+        if ((tot + rppsb::TPB - 1) / rppsb::TPB > 0x7fffffffLL)
+          return fail(s, RRTX_E_OVERFLOW, std::string(fn) + "more polyline points than one launch can fill");
+        if (want_points) {
+          if ((rc = s->reserve(s->c_px, sizeof(double) * (size_t)tot))) return rc;
+          if ((rc = s->reserve(s->c_py, sizeof(double) * (size_t)tot))) return rc;
+          if ((rc = s->reserve(s->c_pyaw, sizeof(double) * (size_t)tot))) return rc;
+          if (!dubins && (rc = s->reserve(s->c_pdir, (size_t)tot))) return rc;
+          a.px = s->c_px.as<double>();
+          a.py = s->c_py.as<double>();
+          a.pyaw = s->c_pyaw.as<double>();
+          a.pdir = dubins ? nullptr : s->c_pdir.as<int8_t>();
+        }
+        if ((rc = s->upload(s->c_poff, s->h_cand_poff.data(), sizeof(int64_t) * (M + 1)))) return rc;
+        a.offsets = s->c_poff.as<const int64_t>();
+        const unsigned fblk = (unsigned)((tot + rppsb::TPB - 1) / rppsb::TPB);
+        rc = s->timed(&ms, [&] {
+          if (dubins)
+            steer_launch_fill<rppsb::KIND_DUBINS>(want_points != 0, n_obs > 0, fblk, s->stream, a);
+          else
+            steer_launch_fill<rppsb::KIND_RS>(want_points != 0, n_obs > 0, fblk, s->stream, a);
+        });
+        if (rc) return rc;
+        s->cand_ms += ms;
+      }
+    }
+  }
+  if (!want_points) s->h_cand_poff.assign(1, 0);   // as a lengths-only solve: no offsets are kept
+  s->cand_solved = true;
+  if (flag) {
+    s->err = std::string(fn) + "some pairs have no candidate: no path, or cases where the reference raises (see the status column)";
+    return RRTX_PARTIAL;
+  }
+  return RRTX_OK;
+}
+
+int rrtx_steer_solve_all(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
+                         const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
+                         const int32_t* word_order, int32_t n_words, int32_t want_points) {
+  try {
+    return steer_solve_all(s, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size, word_order,
+                           n_words, want_points);
+  } catch (const std::exception& e) {
+    if (s) s->cand_solved = false;
+    return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve_all: ") + e.what());
+  }
+}
+
+int rrtx_steer_get_cand_counts(rrtx_steer* s, int64_t* n_pairs, int64_t* n_candidates, int64_t* n_points, double* kernel_ms) {
+  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_cand_counts: the steer object is NULL");
+  if (!s->cand_solved) return fail(s, RRTX_E_STATE, "rrtx_steer_get_cand_counts: no completed rrtx_steer_solve_all");
+  if (n_pairs) *n_pairs = s->cand_pairs;
+  if (n_candidates) *n_candidates = s->n_cand;
+  if (n_points) *n_points = s->cand_n_points;
+  if (kernel_ms) *kernel_ms = s->cand_ms;
+  return RRTX_OK;
+}
+
+int rrtx_steer_get_cand_summary(rrtx_steer* s, int32_t* status, int64_t* cand_offsets, int32_t* pair, int32_t* variant,
+                                int32_t* n_seg, double* seg_len, char* modes, double* length, double* key, int32_t* hit,
+                                int64_t* offsets) {
+  const char* fn = "rrtx_steer_get_cand_summary: ";
+  if (!s) return fail(s, RRTX_E_INVALID, std::string(fn) + "the steer object is NULL");
+  if (!s->cand_solved) return fail(s, RRTX_E_STATE, std::string(fn) + "no completed rrtx_steer_solve_all");
+  if (offsets && !s->cand_points) return fail(s, RRTX_E_STATE, std::string(fn) + "the last solve was without points, it has no offsets");
+  if (hit && !s->cand_hits) return fail(s, RRTX_E_STATE, std::string(fn) + "the last solve ran without an obstacle list");
+  if (cand_offsets) memcpy(cand_offsets, s->h_cand_off.data(), sizeof(int64_t) * s->h_cand_off.size());
+  if (offsets) memcpy(offsets, s->h_cand_poff.data(), sizeof(int64_t) * s->h_cand_poff.size());
+  if (s->cand_pairs == 0) return RRTX_OK;
+  HIPCHK(s, hipSetDevice(s->device));
+  if (status) HIPCHK(s, hipMemcpy(status, s->status.p, sizeof(int32_t) * (size_t)s->cand_pairs, hipMemcpyDeviceToHost));
+  const size_t M = (size_t)s->n_cand;
+  if (M == 0) return RRTX_OK;
+  if (pair) HIPCHK(s, hipMemcpy(pair, s->c_pair.p, sizeof(int32_t) * M, hipMemcpyDeviceToHost));
+  if (variant) HIPCHK(s, hipMemcpy(variant, s->c_variant.p, sizeof(int32_t) * M, hipMemcpyDeviceToHost));
+  if (n_seg) HIPCHK(s, hipMemcpy(n_seg, s->c_nseg.p, sizeof(int32_t) * M, hipMemcpyDeviceToHost));
+  if (seg_len) HIPCHK(s, hipMemcpy(seg_len, s->c_seglen.p, sizeof(double) * 5 * M, hipMemcpyDeviceToHost));
+  if (modes) HIPCHK(s, hipMemcpy(modes, s->c_modes.p, 8 * M, hipMemcpyDeviceToHost));
+  if (length) HIPCHK(s, hipMemcpy(length, s->c_total.p, sizeof(double) * M, hipMemcpyDeviceToHost));
+  if (key) HIPCHK(s, hipMemcpy(key, s->c_key.p, sizeof(double) * M, hipMemcpyDeviceToHost));
+  if (hit) HIPCHK(s, hipMemcpy(hit, s->c_hit.p, sizeof(int32_t) * M, hipMemcpyDeviceToHost));
+  return RRTX_OK;
+}
+
+int rrtx_steer_get_cand_points(rrtx_steer* s, double* x, double* y, double* yaw, int8_t* directions, int64_t cap) {
+  const char* fn = "rrtx_steer_get_cand_points: ";
+  if (!s) return fail(s, RRTX_E_INVALID, std::string(fn) + "the steer object is NULL");
+  if (!s->cand_solved || !s->cand_points) return fail(s, RRTX_E_STATE, std::string(fn) + "no completed rrtx_steer_solve_all with points");
+  if (cap < s->cand_n_points) return fail(s, RRTX_E_CAPACITY, std::string(fn) + "the buffers are too small");
+  if (s->cand_n_points == 0) return RRTX_OK;
+  const size_t cnt = (size_t)s->cand_n_points;
+  HIPCHK(s, hipSetDevice(s->device));
+  if (x) HIPCHK(s, hipMemcpy(x, s->c_px.p, sizeof(double) * cnt, hipMemcpyDeviceToHost));
+  if (y) HIPCHK(s, hipMemcpy(y, s->c_py.p, sizeof(double) * cnt, hipMemcpyDeviceToHost));
+  if (yaw) HIPCHK(s, hipMemcpy(yaw, s->c_pyaw.p, sizeof(double) * cnt, hipMemcpyDeviceToHost));
+  if (directions) {
+    if (s->cand_kind == RRTX_STEER_DUBINS)
+      memset(directions, 1, cnt);   // a Dubins curve is driven forwards throughout
+    else
+      HIPCHK(s, hipMemcpy(directions, s->c_pdir.p, cnt, hipMemcpyDeviceToHost));
+  }
+  return RRTX_OK;
+}
+
+static int steer_select_free(rrtx_steer* s, int32_t* chosen, int32_t* rank, int32_t* n_free) {
+  const char* fn = "rrtx_steer_select_free: ";
+  if (!s) return fail(s, RRTX_E_INVALID, std::string(fn) + "the steer object is NULL");
+  if (!s->cand_solved) return fail(s, RRTX_E_STATE, std::string(fn) + "no completed rrtx_steer_solve_all");
+  if (!s->cand_hits) return fail(s, RRTX_E_STATE, std::string(fn) + "the candidates were solved without an obstacle list");
+  const int64_t np = s->cand_pairs;
+  const bool want_points = s->cand_points;
+  s->solved = false;
+  s->has_points = false;
+  s->has_hits = false;
+  s->has_k = false;
+  s->kind = s->cand_kind;
+  s->n = np;
+  s->n_points = 0;
+  s->kernel_ms = s->cand_ms;
+  s->h_offsets.clear();
+  if (np == 0) {
+    s->has_points = want_points;
+    s->has_hits = true;
+    s->h_offsets.assign(1, 0);
+    s->solved = true;
+    return RRTX_OK;
+  }
+  HIPCHK(s, hipSetDevice(s->device));
+  int rc;
+  const size_t N = (size_t)np;
+  if ((rc = s->reserve(s->nseg, sizeof(int32_t) * N))) return rc;
+  if ((rc = s->reserve(s->total, sizeof(double) * N))) return rc;
+  if ((rc = s->reserve(s->seglen, sizeof(double) * 5 * N))) return rc;
+  if ((rc = s->reserve(s->modes, 8 * N))) return rc;
+  if ((rc = s->reserve(s->npts, sizeof(int32_t) * N))) return rc;
+  if ((rc = s->reserve(s->hit, sizeof(int32_t) * N))) return rc;
+  if ((rc = s->reserve(s->c_chosen, sizeof(int32_t) * N))) return rc;
+  if ((rc = s->reserve(s->c_rank, sizeof(int32_t) * N))) return rc;
+  if ((rc = s->reserve(s->c_nfree, sizeof(int32_t) * N))) return rc;
+  if (s->n_cand == 0 && (rc = s->upload(s->c_off, s->h_cand_off.data(), sizeof(int64_t) * (N + 1)))) return rc;
+  rppsb::Args pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.n = np;
+  pa.nseg = s->nseg.as<int32_t>();
+  pa.total = s->total.as<double>();
+  pa.seglen = s->seglen.as<double>();
+  pa.modes = s->modes.as<char>();
+  pa.npts = s->npts.as<int32_t>();
+  pa.hit = s->hit.as<int32_t>();
+  rppsb::CandArgs c = s->cand_c;
+  c.cand_off = s->c_off.as<const int64_t>();
+  c.chosen = s->c_chosen.as<int32_t>();
+  c.rank = s->c_rank.as<int32_t>();
+  c.nfree = s->c_nfree.as<int32_t>();
+  const rppsb::Args& ca = s->cand_args;
+  const unsigned blk = (unsigned)((np + rppsb::TPB - 1) / rppsb::TPB);
+  std::vector<int32_t> cnt(want_points ? N : 0);
+  float ms = 0.f;
+  rc = s->timed(&ms, [&] {
+    hipLaunchKernelGGL(rppsb::steer_select_free, dim3(blk), dim3(rppsb::TPB), 0, s->stream, pa, ca, c);
+  }, [&]() -> int {
+    if (want_points) HIPCHK(s, hipMemcpyAsync(cnt.data(), s->npts.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
+    if (chosen) HIPCHK(s, hipMemcpyAsync(chosen, s->c_chosen.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
+    if (rank) HIPCHK(s, hipMemcpyAsync(rank, s->c_rank.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
+    if (n_free) HIPCHK(s, hipMemcpyAsync(n_free, s->c_nfree.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
+    return RRTX_OK;
+  });
+  if (rc) return rc;
+  s->kernel_ms += ms;
+  if (want_points) {
+    const int64_t tot = steer_prefix(cnt, s->h_offsets);
+    s->n_points = tot;
+    if (tot > 0) {
+      if ((rc = s->reserve(s->px, sizeof(double) * (size_t)tot))) return rc;
+      if ((rc = s->reserve(s->py, sizeof(double) * (size_t)tot))) return rc;
+      if ((rc = s->reserve(s->pyaw, sizeof(double) * (size_t)tot))) return rc;
+      if ((rc = s->upload(s->offsets, s->h_offsets.data(), sizeof(int64_t) * (N + 1)))) return rc;
+      pa.offsets = s->offsets.as<const int64_t>();
+      pa.px = s->px.as<double>();
+      pa.py = s->py.as<double>();
+      pa.pyaw = s->pyaw.as<double>();
+      const unsigned fblk = (unsigned)((tot + rppsb::TPB - 1) / rppsb::TPB);   // <= the candidates' fill launch
+      rc = s->timed(&ms, [&] {
+        hipLaunchKernelGGL(rppsb::steer_gather_points, dim3(fblk), dim3(rppsb::TPB), 0, s->stream, pa, ca, c);
+      });
+      if (rc) return rc;
+      s->kernel_ms += ms;
+    }
+    s->has_points = true;
+  }
+  s->has_hits = true;
+  s->solved = true;
+  if (s->cand_flag) {
+    s->err = std::string(fn) + "some pairs have no path or are cases where the reference raises (see the status column)";
+    return RRTX_PARTIAL;
+  }
+  return RRTX_OK;
+}
+
+int rrtx_steer_select_free(rrtx_steer* s, int32_t* chosen, int32_t* rank, int32_t* n_free) {
+  try {
+    return steer_select_free(s, chosen, rank, n_free);
+  } catch (const std::exception& e) {
+    if (s) s->solved = false;
+    return fail(s, RRTX_E_HIP, std::string("rrtx_steer_select_free: ") + e.what());
+  }
 }
 
 int rrtx_steer_get_kernel_ms(rrtx_steer* s, double* kernel_ms) {

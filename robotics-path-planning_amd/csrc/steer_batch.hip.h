@@ -33,6 +33,10 @@
 //                                lane, the table row at a wave-uniform address -- for the length and, when curvature is
 //                                wanted, the largest |curvature|.  <4> keeps the control points in registers; <0> (any
 //                                other number of given control points) reads them back from the record.
+//   candidates  steer_rs_all / steer_dubins_all, steer_select_free, steer_gather_points (at the end of this file): every
+//                                candidate curve of a pair instead of the shortest one -- calc_paths :483-503 of the
+//                                Reeds-Shepp script -- through the same course and fill kernels, and the choice of the
+//                                shortest candidate that touches no obstacle.
 // Lengths-only is stage 1 alone (no plan, no course, no offsets) -- unless an obstacle list is set: then stage 1 runs as
 // for points and stage 2 runs with CHECK alone, so no point is ever written.
 // Product mode: pair p of ns x ng is (start p / ng, goal p % ng), formed here; the host never builds the product.
@@ -88,6 +92,10 @@ struct Args {
   double* kmax;           // [n] max |curvature| over the curve's points, or nullptr
   int32_t bez_m, bez_np;  // control points per curve, points per curve
   int32_t bez_given;      // the control points came from the host
+  // every candidate of a pair (steer_*_all below): the records, counts, offsets and hits above are then per candidate, n
+  // counts candidates, and poses and curvature are those of the candidate's pair
+  const int32_t* cand_pair;   // [n] the pair of each candidate, or nullptr: a record per pair
+  int8_t* pdir;               // [offsets[n]] Reeds-Shepp: Path.directions per point, or nullptr
 };
 
 __device__ inline void pair_poses(const Args& a, int64_t p, double* s, double* g) {
@@ -98,6 +106,20 @@ __device__ inline void pair_poses(const Args& a, int64_t p, double* s, double* g
   }
 }
 __device__ inline double pair_curv(const Args& a, int64_t p) { return a.curv ? a.curv[p] : a.curv0; }
+// the pair whose poses and curvature record r is built from
+__device__ inline int64_t record_pair(const Args& a, int64_t r) { return a.cand_pair ? a.cand_pair[r] : r; }
+// the row r of a CSR offset array with off[r] <= idx < off[r + 1] (rows without entries are skipped over)
+__device__ inline int64_t csr_row(const int64_t* off, int64_t n, int64_t idx) {
+  int64_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (off[mid] <= idx)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
 __device__ inline void pair_xy(const Args& a, int64_t p, double* s, double* g) {   // LQR: rows (x, y)
   const int64_t si = a.product ? p / a.ng : p, gi = a.product ? p % a.ng : p;
   for (int i = 0; i < 2; i++) {
@@ -254,7 +276,7 @@ __global__ __launch_bounds__(RS_TPB) void steer_rs_solve(Args a) {
 
 __global__ __launch_bounds__(TPB) void steer_rs_course(Args a) {
   const int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x;
-  if (p >= a.n || a.status[p] != ST_OK) return;
+  if (p >= a.n || (!a.cand_pair && a.status[p] != ST_OK)) return;   // (every candidate has a word)
   rpp::RsCourse& C = a.course[p];
   double len[5];
   char ct[6];
@@ -262,8 +284,9 @@ __global__ __launch_bounds__(TPB) void steer_rs_course(Args a) {
   for (int i = 0; i < 6; i++) ct[i] = C.ct[i];
   const int nl = C.nl;
   double s[3], g[3];
-  pair_poses(a, p, s, g);
-  rpp::rs_course(len, ct, nl, s[0], s[1], s[2], pair_curv(a, p), a.step, &C);
+  const int64_t pr = record_pair(a, p);
+  pair_poses(a, pr, s, g);
+  rpp::rs_course(len, ct, nl, s[0], s[1], s[2], pair_curv(a, pr), a.step, &C);
   a.npts[p] = C.total;
 }
 
@@ -365,20 +388,14 @@ __global__ __launch_bounds__(TPB) void steer_fill(Args a) {
     if (!CHECK) return;
     idx = total - 1;   // the launch has total > 0
   }
-  int64_t lo = 0, hi = a.n;   // the pair p with offsets[p] <= idx < offsets[p + 1] (rows without points are skipped over)
-  while (hi - lo > 1) {
-    const int64_t mid = lo + (hi - lo) / 2;
-    if (a.offsets[mid] <= idx)
-      lo = mid;
-    else
-      hi = mid;
-  }
+  const int64_t lo = csr_row(a.offsets, a.n, idx);   // the pair (or candidate) the point belongs to
   const int k = (int)(idx - a.offsets[lo]);
   double x, y, yaw = 0.0, kk = 0.0;
   if (KIND == KIND_DUBINS) {
-    rpp::dubins_point(a.dplan[lo], k, pair_curv(a, lo), &x, &y, &yaw);
+    rpp::dubins_point(a.dplan[lo], k, pair_curv(a, record_pair(a, lo)), &x, &y, &yaw);
   } else if (KIND == KIND_RS) {
     rpp::rs_point(a.course[lo], k, &x, &y, &yaw);
+    if (STORE && live && a.pdir) a.pdir[idx] = (int8_t)rpp::rs_point_dir(a.course[lo], k);
   } else if (KIND == KIND_LQR) {
     double s[2], g[2];
     pair_xy(a, lo, s, g);
@@ -421,6 +438,203 @@ __global__ __launch_bounds__(TPB) void steer_fill(Args a) {
       atomicMin(out + pair, h);
     }
   }
+}
+
+// ---- every candidate curve of a pair, and the shortest one that is free -------------------------------------------------
+// Reference: 10_path_planning_00_reeds_shepp_path.py calc_paths :483-503 -- the whole list set_path :141-159 kept, of which
+//   reeds_shepp_path_planning :506-515 is the minimum; for Dubins the candidate of list entry w is what plan_dubins_path
+//   (10_path_planning_00_dubins_path.py :109-197) returns with selected_types=[w].
+// The layout is CSR twice: pairs -> candidates (cand_off) and candidates -> points (Args::offsets).
+//   count   steer_rs_all<false> / steer_dubins_all<false>: status and the number of candidates per pair.
+//   emit    <true>, after the host's prefix sum: one record per candidate at cand_off[pair] + its place in the list, in the
+//           per-candidate arrays of an Args whose n is the number of candidates and whose cand_pair leads back to the pair.
+//   course, fill   steer_rs_course and steer_fill over those Args: a candidate is a curve like any other.
+//   select  steer_select_free: one lane per pair walks its candidates' keys and hits (rpp::pick_free) and writes the chosen
+//           candidate's record as the pair's row of an ordinary result; steer_gather_points then copies its points.
+constexpr int CAND_MAX_WORDS = 16;   // entries of a Dubins word list (duplicates are candidates of their own)
+
+struct CandArgs {
+  int64_t n_pairs;
+  int32_t order[CAND_MAX_WORDS];   // Dubins: the word list
+  int32_t n_order;
+  int32_t* status;           // [n_pairs]
+  int32_t* ncand;            // [n_pairs]
+  const int64_t* cand_off;   // [n_pairs + 1]
+  int32_t* pair;             // [n candidates] = Args::cand_pair
+  int32_t* variant;          // RS: 4 * word family + symmetry; Dubins: the position in the word list
+  double* key;               // what the kind's planner minimises: RS abs(L / maxc) (= Path.L), Dubins the cost of :1220
+  int32_t *chosen, *rank, *nfree;   // [n_pairs] steer_select_free; chosen: a candidate index, -1 where the pair has none
+};
+
+// 16 lanes per pair evaluate the 48 variants into the pair's table and lane 0 runs set_path's walk, as in steer_rs_solve;
+// then every RS_KEPT entry is a candidate, in table order (the order set_path appended them in).  The emit pass evaluates
+// the table again instead of keeping 48 entries per pair between the passes: nothing is sized by the worst case.
+template <bool EMIT>
+__global__ __launch_bounds__(RS_TPB) void steer_rs_all(Args a, CandArgs c) {
+  __shared__ RsTable tab[RS_PAIRS];
+  __shared__ int32_t sel_of[RS_PAIRS];
+  const int grp = threadIdx.x / RS_LANES, t = threadIdx.x % RS_LANES;
+  const int64_t p = (int64_t)blockIdx.x * RS_PAIRS + grp;
+  const bool live = p < c.n_pairs;
+  RsTable& T = tab[grp];
+  double s[3], g[3], maxc = 1.0;
+  rpp::RsFrame F;
+  if (live) {
+    pair_poses(a, p, s, g);
+    maxc = pair_curv(a, p);
+    rpp::rs_frame(s[0], s[1], s[2], g[0], g[1], g[2], maxc, a.step, &F);
+    const double sdth = rpp_glibc_sin(F.dth), cdth = rpp_glibc_cos(F.dth);
+    for (int j = 0; j < 48 / RS_LANES; j++) {
+      const int k = t + RS_LANES * j;
+      double d[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+      char ct[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      int nn = 0;
+      const int st = rpp::rs_variant_sc(k >> 2, k & 3, F, sdth, cdth, d, ct, &nn);
+      T.st[k] = st;
+      T.n[k] = nn;
+      for (int i = 0; i < 5; i++) T.d[k][i] = d[i];
+      for (int i = 0; i < 8; i++) T.ct[k][i] = ct[i];
+      T.L[k] = st == 1 ? rpp::rs_sum_abs(d, nn) : 0.0;
+      T.code[k] = st == 1 ? rpp::rs_code(ct) : 0u;
+    }
+  }
+  __syncthreads();
+  if (live && t == 0) {
+    const int sel = rs_select_lds(T, F.step, maxc);   // < 0: raised or [] -- whatever was kept before is hidden
+    sel_of[grp] = sel;
+    if (!EMIT) {
+      int nc = 0;
+      if (sel >= 0)
+        for (int k = 0; k < 48; k++) nc += T.st[k] == RS_KEPT;
+      c.ncand[p] = nc;
+      c.status[p] = sel >= 0 ? ST_OK : (sel == -1 ? ST_NO_PATH : (sel == -3 ? ST_RAISES_ZERODIV : ST_RAISES_VALUE));
+      if (sel < 0) atomicOr(a.flag, 1);
+    }
+  }
+  if (!EMIT) return;
+  __syncthreads();
+  if (!live || sel_of[grp] < 0) return;
+  for (int j = 0; j < 48 / RS_LANES; j++) {   // lane t emits the kept ones of its own three variants
+    const int k = t + RS_LANES * j;
+    if (T.st[k] != RS_KEPT) continue;
+    int place = 0;
+    for (int i = 0; i < k; i++) place += T.st[i] == RS_KEPT;
+    const int64_t ci = c.cand_off[p] + place;
+    const int nl = T.n[k];
+    char* m = a.modes + 8 * ci;
+    double* sl = a.seglen + 5 * ci;
+    double tot = 0.0;
+    for (int i = 0; i < 8; i++) m[i] = i < nl ? T.ct[k][i] : 0;
+    for (int i = 0; i < 5; i++) {
+      const double l = i < nl ? T.d[k][i] / maxc : 0.0;   // :500
+      sl[i] = l;
+      tot += rpp::dabs(l);
+    }
+    c.pair[ci] = (int32_t)p;
+    c.variant[ci] = k;
+    c.key[ci] = rpp::dabs(T.L[k] / maxc);   // :501, and the key of :512
+    a.nseg[ci] = nl;
+    a.total[ci] = tot;
+    a.npts[ci] = 0;
+    if (a.hit) a.hit[ci] = -1;
+    if (a.want_points) {
+      rpp::RsCourse& C = a.course[ci];
+      for (int i = 0; i < 5; i++) C.len[i] = T.d[k][i];
+      for (int i = 0; i < 6; i++) C.ct[i] = T.ct[k][i];
+      C.nl = nl;
+    }
+  }
+}
+
+// One lane per pair: one DubinsPlan per feasible entry of the word list, each prepared as a list of that one word.
+template <bool EMIT>
+__global__ __launch_bounds__(TPB) void steer_dubins_all(Args a, CandArgs c) {
+  const int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (p >= c.n_pairs) return;
+  double s[3], g[3];
+  pair_poses(a, p, s, g);
+  const double curv = pair_curv(a, p);
+  int nc = 0;
+  for (int q = 0; q < c.n_order; q++) {
+    rpp::DubinsPlan P;
+    rpp::dubins_candidate(&P, s[0], s[1], s[2], g[0], g[1], g[2], curv, c.order[q]);
+    if (!P.ok) continue;
+    if (EMIT) {
+      const int64_t ci = c.cand_off[p] + nc;
+      char* m = a.modes + 8 * ci;
+      double* sl = a.seglen + 5 * ci;
+      for (int i = 0; i < 8; i++) m[i] = 0;
+      sl[3] = sl[4] = 0.0;
+      double tot = 0.0;
+      for (int i = 0; i < 3; i++) {
+        const double l = P.len[i] / curv;   // :315
+        sl[i] = l;
+        tot += rpp::dabs(l);
+        const int md = P.mode[i];
+        m[i] = md == 0 ? 'L' : (md == 1 ? 'S' : 'R');
+      }
+      c.pair[ci] = (int32_t)p;
+      c.variant[ci] = q;
+      c.key[ci] = rpp::dubins_key(P);
+      a.nseg[ci] = 3;
+      a.total[ci] = tot;
+      a.npts[ci] = P.total;
+      if (a.hit) a.hit[ci] = -1;
+      if (a.want_points) a.dplan[ci] = P;
+    }
+    nc++;
+  }
+  if (!EMIT) {
+    c.ncand[p] = nc;
+    c.status[p] = nc ? ST_OK : ST_NO_PATH;
+    if (!nc) atomicOr(a.flag, 1);
+  }
+}
+
+// One lane per pair.  ca: the candidates' Args (records and hits in); pa: an ordinary per-pair result (row out).  A pair
+// without candidates gets the row steer_*_solve writes for its status.
+__global__ __launch_bounds__(TPB) void steer_select_free(Args pa, Args ca, CandArgs c) {
+  const int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (p >= c.n_pairs) return;
+  const int64_t c0 = c.cand_off[p];
+  const int nc = (int)(c.cand_off[p + 1] - c0);
+  char* m = pa.modes + 8 * p;
+  double* sl = pa.seglen + 5 * p;
+  c.rank[p] = 0;
+  c.nfree[p] = 0;
+  if (nc == 0) {
+    c.chosen[p] = -1;
+    for (int i = 0; i < 8; i++) m[i] = 0;
+    for (int i = 0; i < 5; i++) sl[i] = 0.0;
+    pa.nseg[p] = 0;
+    pa.total[p] = 0.0;
+    pa.npts[p] = 0;
+    pa.hit[p] = -2;
+    return;
+  }
+  int ch, rank, nfree;
+  rpp::pick_free(c.key + c0, ca.hit + c0, nc, &ch, &rank, &nfree);
+  const int64_t ci = c0 + ch;
+  c.chosen[p] = (int32_t)ci;
+  c.rank[p] = rank;
+  c.nfree[p] = nfree;
+  for (int i = 0; i < 8; i++) m[i] = ca.modes[8 * ci + i];
+  for (int i = 0; i < 5; i++) sl[i] = ca.seglen[5 * ci + i];
+  pa.nseg[p] = ca.nseg[ci];
+  pa.total[p] = ca.total[ci];
+  pa.npts[p] = ca.npts[ci];
+  pa.hit[p] = ca.hit[ci];
+}
+
+// One lane per point of the chosen curves: the point the candidates' fill launch already computed
+__global__ __launch_bounds__(TPB) void steer_gather_points(Args pa, Args ca, CandArgs c) {
+  const int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (idx >= pa.offsets[pa.n]) return;
+  const int64_t p = csr_row(pa.offsets, pa.n, idx);
+  const int64_t src = ca.offsets[c.chosen[p]] + (idx - pa.offsets[p]);
+  pa.px[idx] = ca.px[src];
+  pa.py[idx] = ca.py[src];
+  pa.pyaw[idx] = ca.pyaw[src];
 }
 
 }  // namespace rppsb

@@ -14,6 +14,11 @@ Every double is what the reference's plan_dubins_path (10_path_planning_00_dubin
 reeds_shepp_path_planning (10_path_planning_00_reeds_shepp_path.py :506) returns for that pair, bit for bit.  There is no
 CPU fallback: without a device the call raises RrtxError.
 
+    cands = bs.candidates(starts, goals, curvature, obstacle_list=circles)   # "dubins" / "rs": EVERY candidate curve of
+                                                    # every pair, CSR: cands.of(i), cands.paths(i) = calc_paths' list
+    res = bs.plan_free(starts, goals, curvature, obstacle_list=circles)      # plan(), but the shortest candidate that
+                                                    # touches no circle (plan()'s row where none is free); res.rank, res.n_free
+
     bs = BatchSteer("lqr")                          # rows (x, y); no curvature
     res = bs.plan(starts, goals)                    # rrt_09's edges: res.path(i) = sample_path's (px, py, course_lens),
                                                     # res.end[i] = (px[-1], py[-1]), res.length[i] = sum(course_lens)
@@ -62,6 +67,93 @@ def word_order(selected_types):
     return idx
 
 
+def word_list(selected_types):
+    """selected_types as word indices with every entry kept: in BatchSteer.candidates a repeated name is a candidate of its
+    own.  None: the six words in DUBINS_WORDS order."""
+    if selected_types is None:
+        return None
+    for name in selected_types:
+        if name not in _abi.DUBINS_WORDS:
+            raise KeyError(name)
+    return [_abi.DUBINS_WORDS.index(name) for name in selected_types]
+
+
+class Path:
+    """The reeds_shepp_path script's Path container (10_path_planning_00_reeds_shepp_path.py :101-115), as calc_paths
+    leaves it: lengths and L divided by the curvature."""
+
+    def __init__(self):
+        self.lengths = []
+        self.ctypes = []
+        self.L = 0.0
+        self.x = []
+        self.y = []
+        self.yaw = []
+        self.directions = []
+
+
+class SteerCandidates:
+    """Every candidate curve of a batch, CSR twice.  Per pair: status (n,) STEER_*, n_candidates (n,), cand_offsets
+    (n + 1,) int64 -- of(i) is pair i's candidate range; a pair whose status is not STEER_OK has none.  Per candidate, in
+    the reference's list order: pair; variant ("rs": 4 * word family + symmetry of generate_path, 0..47; "dubins": the
+    position in the word list); modes (list of strings), n_seg, seg_len (m, 5), length (the column SteerResult.length
+    holds); key, what the kind's planner minimises ("rs": Path.L; "dubins": the cost plan_dubins_path compares, in
+    curvature units); hit (m,) int32 with an obstacle list (-1 free, else the lowest obstacle index touched), else None.
+    Per point, with points=True: offsets (m + 1,) int64 over candidates, x, y, yaw and directions (int8, +1 / -1: "rs"
+    Path.directions, "dubins" all +1); else None."""
+
+    def __init__(self, kind, summary, pts, shape, rc, kernel_ms):
+        self.kind = kind
+        for k in ("status", "cand_offsets", "pair", "variant", "n_seg", "seg_len", "length", "key", "hit", "offsets"):
+            setattr(self, k, summary[k])
+        self.n_candidates = np.diff(self.cand_offsets).astype(np.int32)
+        self.modes = [m.decode() for m in summary["modes"]]
+        self.x, self.y, self.yaw, self.directions = pts if pts is not None else (None,) * 4
+        self.shape = shape
+        self.rc = rc
+        self.kernel_ms = kernel_ms
+
+    def __len__(self):
+        return len(self.status)
+
+    def of(self, i):
+        """range of the candidate indices of pair i"""
+        return range(int(self.cand_offsets[i]), int(self.cand_offsets[i + 1]))
+
+    @property
+    def free(self):
+        """Boolean mask over candidates: the curve touches no obstacle."""
+        if self.hit is None:
+            raise _abi.RrtxError("free: these candidates were solved without an obstacle list")
+        return self.hit == -1
+
+    def paths(self, i):
+        """"rs": what calc_paths returns for pair i -- a list of Path objects (lengths, ctypes, L, x, y, yaw, directions as
+        Python lists and floats), [] where it returns []; raises where it raises.  "dubins": the list of
+        plan_dubins_path(..., selected_types=[w]) five-tuples of the feasible list entries."""
+        st = int(self.status[i])
+        if st == _abi.STEER_RAISES_ZERODIV:
+            raise ZeroDivisionError("float division by zero")
+        if st == _abi.STEER_RAISES_VALUE:
+            raise ValueError("math domain error")
+        if self.x is None:
+            raise _abi.RrtxError("paths(): these candidates were solved with points=False")
+        out = []
+        for c in self.of(i):
+            a, b = int(self.offsets[c]), int(self.offsets[c + 1])
+            modes = list(self.modes[c])
+            lengths = [float(v) for v in self.seg_len[c, :self.n_seg[c]]]
+            if self.kind == _abi.STEER_DUBINS:
+                out.append((self.x[a:b].copy(), self.y[a:b].copy(), self.yaw[a:b].copy(), modes, lengths))
+                continue
+            p = Path()
+            p.lengths, p.ctypes, p.L = lengths, modes, float(self.key[c])
+            p.x, p.y, p.yaw = self.x[a:b].tolist(), self.y[a:b].tolist(), self.yaw[a:b].tolist()
+            p.directions = self.directions[a:b].tolist()
+            out.append(p)
+        return out
+
+
 class SteerResult:
     """One solved batch.  status (n,) STEER_*; length (n,): the absolute segment lengths added up; modes: list of n strings; lengths: list of n arrays of segment
     lengths; offsets (n + 1,) and the flat x, y, yaw when points were asked for, else None; hit (n,) int32 when the batch
@@ -75,7 +167,9 @@ class SteerResult:
     control_points (n, m, 2) what the device computed from the poses (or was given); k the flat curvature per point and
     kmax (n,) the largest |k| per curve (NaN if any k is NaN) when curvature was asked for, else None.  yaw, length and
     kmax are this package's definitions (the bazier_path script returns none of them): yaw = atan2(dy, dx) of the first
-    derivative, length the left-to-right sum of math.hypot over consecutive points.  modes and lengths are empty."""
+    derivative, length the left-to-right sum of math.hypot over consecutive points.  modes and lengths are empty.
+    A batch of BatchSteer.plan_free has three more (n,) int32 columns (None otherwise): rank, the position of the chosen
+    candidate among the pair's candidates ordered by the kind's ranking key (0: plan()'s curve); n_candidates; n_free."""
 
     def __init__(self, kind, status, length, nseg, seglen, modes, offsets, xyz, shape, rc, kernel_ms, hit=None, end=None,
                  resampled=True, k=None, kmax=None, control_points=None):
@@ -102,6 +196,7 @@ class SteerResult:
         self.k = k                  # "bezier": flat curvature per point, or None
         self.kmax = kmax            # "bezier": (n,), or None
         self.control_points = control_points   # "bezier": (n, m, 2)
+        self.rank = self.n_candidates = self.n_free = None   # plan_free()
 
     @property
     def free(self):
@@ -263,6 +358,52 @@ class BatchSteer:
         xyz = S.points() if points else None
         return SteerResult(self.kind, status, length, nseg, seglen, modes, off, xyz,
                            (len(st), len(go)) if product else None, rc, S.kernel_ms(), hit=S.hits() if len(ob) else None)
+
+    def _solve_all(self, what, starts, goals, curvature, step_size, selected_types, points, product, obstacle_list,
+                   robot_radius):
+        """plan()'s checks and defaults for the two curve kinds, then rrtx_steer_solve_all: (rc, shape, obstacle rows)."""
+        if self.kind not in (_abi.STEER_DUBINS, _abi.STEER_RS):
+            raise ValueError("BatchSteer.%s belongs to the kinds 'dubins' and 'rs'" % what)
+        if curvature is None:
+            raise TypeError("BatchSteer.%s: curvature is required" % what)
+        if step_size is None:
+            step_size = DEFAULT_STEP[self.kind]
+        wl = word_list(selected_types)
+        if wl is not None and len(wl) > 16:
+            raise ValueError("BatchSteer.%s: at most 16 entries in selected_types" % what)
+        st = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        go = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
+        ob = self._set_obstacles(obstacle_list, robot_radius)
+        rc = self._steer.solve_all(self.kind, st, go, curvature, step_size, word_order=wl, points=points, product=product)
+        return rc, ((len(st), len(go)) if product else None), ob
+
+    def candidates(self, starts, goals, curvature, step_size=None, selected_types=None, points=True, product=False,
+                   obstacle_list=None, robot_radius=0.0):
+        """Every candidate curve of every pair ("rs": calc_paths' list; "dubins": one per feasible entry of the word list,
+        a repeated word repeated), arguments as plan(): a SteerCandidates."""
+        rc, shape, ob = self._solve_all("candidates", starts, goals, curvature, step_size, selected_types, points, product,
+                                        obstacle_list, robot_radius)
+        S = self._steer
+        summary = S.cand_summary(hits=len(ob) > 0, offsets=bool(points))
+        return SteerCandidates(self.kind, summary, S.cand_points() if points else None, shape, rc, S.cand_counts()[3])
+
+    def plan_free(self, starts, goals, curvature, step_size=None, selected_types=None, points=True, product=False,
+                  obstacle_list=None, robot_radius=0.0):
+        """As plan(obstacle_list=...), but every row is the shortest candidate curve that touches no obstacle -- smallest
+        by the key plan() minimises, the first in list order among equal keys; where no candidate is free (or the pair has
+        none) the row is plan()'s.  The SteerResult has rank, n_candidates and n_free beside plan()'s columns."""
+        if obstacle_list is None or len(np.asarray(obstacle_list).reshape(-1)) == 0:
+            raise ValueError("BatchSteer.plan_free: an obstacle list is required")
+        rc, shape, _ = self._solve_all("plan_free", starts, goals, curvature, step_size, selected_types, points, product,
+                                       obstacle_list, robot_radius)
+        S = self._steer
+        rc, _, rank, n_free = S.select_free()
+        status, length, nseg, seglen, modes, off = S.summary(offsets=bool(points))
+        res = SteerResult(self.kind, status, length, nseg, seglen, modes, off, S.points() if points else None, shape, rc,
+                          S.kernel_ms(), hit=S.hits())
+        res.rank, res.n_free = rank, n_free
+        res.n_candidates = np.diff(S.cand_offsets()).astype(np.int32)
+        return res
 
     def plan_control_points(self, control_points, n_points=100, curvature=True, points=True, obstacle_list=None,
                             robot_radius=0.0):

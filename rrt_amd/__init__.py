@@ -4,7 +4,7 @@ Per-script drop-in modules: `rrt_amd.rrt_01` ... `rrt_amd.rrt_10` carry exactly 
 number defines for its driver cell (`RRT`, `BITStar`, `Node`, `path_smoothing`, `get_path_length`), so a driver written
 against `10_path_planning_01_rrt_04_rrt_star.py` runs after `from rrt_amd.rrt_04 import *`.  `rrt_amd.dubins_path`, `rrt_amd.reeds_shepp_path`
 and `rrt_amd.lqr_path` do the same for the three stand-alone steering scripts (`plan_dubins_path`, `reeds_shepp_path_planning`,
-`LQRPlanner`), `rrt_amd.cubic_spline_path` for the cubic-spline script (`calc_spline_course`, `CubicSpline1D`, `CubicSpline2D`), `rrt_amd.bspline_path` and
+`LQRPlanner`), `rrt_amd.reeds_shepp_calc_paths` for the Reeds-Shepp script's `calc_paths` and `Path` (every candidate curve), `rrt_amd.cubic_spline_path` for the cubic-spline script (`calc_spline_course`, `CubicSpline1D`, `CubicSpline2D`), `rrt_amd.bspline_path` and
 `rrt_amd.spline_2d` for the two scipy spline scripts (`interpolate_b_spline_path` and its helpers; `Spline2D`), `rrt_amd.bspline_path_smoothing`
 for the same B-spline script with its smoothing fit (`approximate_b_spline_path` for any `s`), `rrt_amd.bazier_path` for the
 Bezier script (`calc_4points_bezier_path`, `calc_bezier_path` and its pointwise helpers), `rrt_amd.arm_obstacle_navigation` for the
@@ -44,6 +44,7 @@ ClosedLoopRRTStar = _pkg.ClosedLoopRRTStar
 informed_rotation = _pkg.informed_rotation
 BatchPlanner = _pkg.BatchPlanner
 BatchSteer = _pkg.BatchSteer
+SteerCandidates = _pkg.SteerCandidates
 BatchTrack = _pkg.BatchTrack
 BatchSpline = _pkg.BatchSpline
 SplineQueryResult = _pkg.SplineQueryResult

@@ -1,6 +1,6 @@
 """Throughput of the batched Dubins / Reeds-Shepp curves (BatchSteer): pairs/s for lengths-only and for points.
 
-    python tools/steer_bench.py [--pairs 1048576] [--reps 5] [--cpu-pairs 2000] [--obstacles M] [--kind lqr|bezier]
+    python tools/steer_bench.py [--pairs 1048576] [--reps 5] [--cpu-pairs 2000] [--obstacles M] [--kind lqr|bezier] [--all]
 
 Random pairs in the pose box of the known-answer vectors ([-2, 15]^2, any yaw), curvature 1, Reeds-Shepp step 0.2.  The
 GPU figure is HIP-event kernel time (stage 1, and stage 1 + fill), the median of --reps solves after one warm-up solve;
@@ -21,7 +21,15 @@ on a subsample of the same pairs.
 with a row per variant -- "lengths" (points=False, curvature=False), "lengths_kmax" (points=False), "points" (x, y, yaw
 and k per point), and with --obstacles M "check_lengths" and "check_points" -- each with the HIP-event kernel time (weight
 table, stage 1, fill; the median of --reps calls after one warm-up) and the wall time of the whole BatchSteer.plan() call
-beside it; then tests/bezier_oracle.curve4 (pure Python) on one core over a subsample of the same pairs."""
+beside it; then tests/bezier_oracle.curve4 (pure Python) on one core over a subsample of the same pairs.
+
+--all measures every candidate curve of a pair (BatchSteer.candidates / plan_free) for the two curve kinds, against
+--obstacles M circles (default 12 in this mode): "candidates_lengths" (points=False, no list), "candidates_check" (points=False
+with the list: every candidate's points computed and tested, none stored), "candidates_points" (stored and tested),
+"plan_free" and "plan_free_points" (the same two plus the selection and the gather), and "plan_check" (plan(points=False)
+with the list) for comparison -- HIP-event kernel time, the median of --reps solves after one warm-up, on the binding's
+solve calls (no result arrays are copied back).  Beside them the candidates and points per pair, "free_fraction" of plan(),
+"free_fraction_plan_free", and "rows_changed": the share of pairs whose row plan_free moved to another candidate."""
 import argparse
 import json
 import os
@@ -83,6 +91,52 @@ def bench_bezier(args):
     print(json.dumps(out), flush=True)
 
 
+def bench_all(args):
+    import rrt_amd
+    m = args.obstacles or 12
+    rs = np.random.RandomState(9)
+    circles = np.stack([rs.uniform(-2, 15, m), rs.uniform(-2, 15, m), rs.uniform(0.2, 0.8, m)], axis=1)
+    for kind in ("dubins", "rs"):
+        p = pairs(args.pairs, {"dubins": 7, "rs": 8}[kind])
+        step = 0.1 if kind == "dubins" else 0.2
+        out = {"kind": kind, "mode": "all", "pairs": args.pairs, "reps": args.reps, "obstacles": m}
+        with rrt_amd.BatchSteer(kind) as bs:
+            S = bs._steer
+            rows = [("candidates_lengths", "all", False, None), ("candidates_check", "all", False, circles),
+                    ("candidates_points", "all", True, circles), ("plan_free", "free", False, circles),
+                    ("plan_free_points", "free", True, circles), ("plan_check", "plan", False, circles)]
+            for name, what, points, obs in rows:
+                S.set_obstacles(np.zeros((0, 3)) if obs is None else obs)
+                ms, wall = [], []
+                for rep in range(args.reps + 1):
+                    t0 = time.perf_counter()
+                    if what == "plan":
+                        S.solve(bs.kind, p[:, 0:3], p[:, 3:6], 1.0, step, points=points)
+                        ms.append(S.kernel_ms())
+                    else:
+                        S.solve_all(bs.kind, p[:, 0:3], p[:, 3:6], 1.0, step, points=points)
+                        if what == "free":
+                            _, _, rank, n_free = S.select_free()
+                            ms.append(S.kernel_ms())
+                        else:
+                            ms.append(S.cand_counts()[3])
+                    wall.append((time.perf_counter() - t0) * 1e3)
+                med = float(np.median(ms[1:]))
+                out[name + "_kernel_ms"] = med
+                out[name + "_pairs_per_s"] = args.pairs / (med * 1e-3)
+                out[name + "_solve_wall_ms"] = float(np.median(wall[1:]))
+                if name == "candidates_points":
+                    _, nc, npts, _ = S.cand_counts()
+                    out["candidates_per_pair"] = nc / args.pairs
+                    out["candidate_points_per_pair"] = npts / args.pairs
+                if name == "plan_free":
+                    out["rows_changed"] = float(np.mean(rank > 0))
+                    out["free_fraction_plan_free"] = float(np.mean(n_free > 0))
+                if what == "plan":
+                    out["free_fraction"] = float(np.mean(S.hits() == -1))
+        print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=1 << 20)
@@ -90,7 +144,10 @@ def main():
     ap.add_argument("--cpu-pairs", type=int, default=2000)
     ap.add_argument("--obstacles", type=int, default=0)
     ap.add_argument("--kind", choices=("curves", "lqr", "bezier"), default="curves")
+    ap.add_argument("--all", action="store_true")
     args = ap.parse_args()
+    if args.all:
+        return bench_all(args)
     if args.kind == "bezier":
         return bench_bezier(args)
     import oracle
