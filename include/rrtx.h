@@ -30,7 +30,8 @@ extern "C" {
                                 the same kind: rrtx_steer_set_obstacles, rrtx_steer_get_hits, rrtx_steer_solve_lqr, rrtx_steer_get_ends,
                                 rrtx_steer_solve_bezier, rrtx_steer_solve_bezier_cp, rrtx_steer_get_curvature, rrtx_steer_get_kmax,
                                 rrtx_steer_get_control_points, rrtx_steer_solve_all, rrtx_steer_get_cand_counts,
-                                rrtx_steer_get_cand_summary, rrtx_steer_get_cand_points, rrtx_steer_select_free); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
+                                rrtx_steer_get_cand_summary, rrtx_steer_get_cand_points, rrtx_steer_select_free, rrtx_tracker_run_from,
+                                rrtx_tracker_get_winners, rrtx_tracker_get_goals, rrtx_*_get_generation); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
                                 rrtx_copy_results_device, per-instance yaw and informed rotation; 4: rrtx_plan_many,
                                 rrtx_selfcheck, rrtx_stats.main_shape / main_f32, rrtx_plan_begin / _step, rrtx_set_launch_bound,
                                 RRTX_ST_REF_HANGS, rrtx_rccl_* */
@@ -577,6 +578,56 @@ int rrtx_tracker_get_arrays(rrtx_tracker* t, double* x, double* y, double* yaw, 
 /* HIP-event time of the kernels of the last run (both launches) */
 int rrtx_tracker_get_kernel_ms(rrtx_tracker* t, double* kernel_ms);
 
+/* ---- tracking the courses a producer left on the device (csrc/rrt_track.hip.h: track_source_kernel) ----------------------
+ * rrt_10 keeps its whole chain on the device for its own tree: candidates, roll-outs, search_best_feasible_path
+ * (:1495-1524), then only the winner's arrays.  rrtx_tracker_run_from gives the batch objects the same shape: the tracker
+ * reads the points of the last solve of an rrtx_steer, rrtx_spline or rrtx_bspline where they lie, during the call only
+ * (it returns after its own stream has synchronised, so the producer may be reused or destroyed afterwards).
+ * Every completed solve / run of a producer increments its generation; the getters below read it (RRTX_E_INVALID for a
+ * NULL pointer; 0 before the first completed solve). */
+int rrtx_steer_get_generation(rrtx_steer* s, uint64_t* generation);
+#define RRTX_SRC_STEER 1
+#define RRTX_SRC_SPLINE 2
+#define RRTX_SRC_BSPLINE 3
+#define RRTX_SELECT_ALL 0
+#define RRTX_SELECT_FREE 1   /* courses whose hit == -1; RRTX_E_STATE if the source ran without an obstacle list */
+#define RRTX_SELECT_MASK 2   /* mask[i] != 0 */
+typedef struct rrtx_track_source {
+  int32_t kind, select;     /* RRTX_SRC_*, RRTX_SELECT_* */
+  const void* object;       /* rrtx_steer* / rrtx_spline* / rrtx_bspline* */
+  uint64_t generation;      /* must equal the object's: else RRTX_E_STATE, nothing launched */
+  const uint8_t* mask;      /* host, n bytes, RRTX_SELECT_MASK only */
+  int64_t group;            /* 0, or a group size g >= 1 with n % g == 0: courses [j g, (j + 1) g) are group j */
+  int32_t arrays_of;        /* 0 every complete course (as rrtx_tracker_run), 1 the group winners only (group > 0) */
+} rrtx_track_source;
+/* As rrtx_tracker_run on the courses of `src`: b carries everything but the courses (b->offsets, x, y, yaw must be NULL and
+ * b->n the source's course count).  Records, arr_offsets, arrays, counts and the kernel time come from the getters above.
+ * ood takes two more values: 4 a pose component of the course is not finite (the host path refuses such a batch; here the
+ * host never sees the points), 5 the selection left the course out (its points were not read).  Neither owns entries.
+ * Returns RRTX_OK, or RRTX_PARTIAL when some ood is 1 .. 4; ood = 5 alone is RRTX_OK.
+ * With group = g one decision per group follows the records on the device: search_best_feasible_path (:1504-1513) over the
+ * group's courses in order -- among the records with ood == 0 and find_goal set the smallest t_last, the later course of
+ * equal times, -1 none.  Courses with ood != 0 are passed over.  With arrays_of = 1 only the winners are rolled out again:
+ * arr_offsets is the exclusive sum of len over the winners, every other course owns no entries.
+ * Checked in this order.  RRTX_E_INVALID before any HIP call: a NULL pointer, an unknown kind, select or arrays_of,
+ * non-NULL course pointers in b, group < 0 or n % group != 0, arrays_of = 1 without a group, a mask missing or given
+ * without RRTX_SELECT_MASK, and everything rrtx_tracker_run checks of the remaining fields.  RRTX_E_NO_DEVICE for a
+ * tracker without a device.  RRTX_E_INVALID when the source is on another device.  RRTX_E_STATE: the source has no
+ * completed run, the generation is stale, the source ran without points (lengths-only, records-only, one-dimensional
+ * splines), the last steer solve was an LQR solve (a rollout has no yaw) or an rrtx_steer_solve_all not followed by
+ * rrtx_steer_select_free, RRTX_SELECT_FREE on a source without hits.  Then RRTX_E_INVALID when b->n is not the source's
+ * course count.  Nothing is launched before all of them passed. */
+int rrtx_tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_source* src,
+                          const rrtx_track_batch* b);
+/* The winners of the last rrtx_tracker_run_from with a group: winner (may be NULL) n / g course indices, -1 where a group
+ * has none.  RRTX_E_STATE after a run without a group. */
+int rrtx_tracker_get_winners(rrtx_tracker* t, int32_t* winner, int64_t* n_groups);
+/* The goal poses (:1531) of the last rrtx_tracker_run_from, rows (x, y, yaw): with a group the last point of every
+ * winner (n / g rows), without one the last point of every course (n rows); NaN where there is no winner, or the course
+ * has ood 2 .. 5.  search_best_feasible_path appends the winner's row to x, y, yaw (:1519-1521).  RRTX_E_STATE after
+ * rrtx_tracker_run. */
+int rrtx_tracker_get_goals(rrtx_tracker* t, double* goals);
+
 /* ---- batched cubic-spline courses through waypoints, without a planner (csrc/spline_batch.hip.h, csrc/rpp_spline.h) ---------
  * For every course of a batch: what calc_spline_course(x, y, ds) (10_path_planning_00_cubic_spline_path.py :313-325) returns --
  * rx, ry, ryaw, rk, s: a natural cubic spline over the chord length, sampled every ds.  Point counts, offsets and s are the
@@ -648,6 +699,8 @@ int rrtx_spline_get_c(rrtx_spline* s, double* cx, double* cy, int64_t cap);
  * point touches; -2 the course owns no points (status != RRTX_SPLINE_OK, or no sample), nothing was tested.  RRTX_E_STATE when
  * the last run had no obstacle list. */
 int rrtx_spline_get_hits(rrtx_spline* s, int32_t* hit);
+/* Completed rrtx_spline_run / rrtx_spline_fit1d calls on `s` so far (rrtx_track_source.generation) */
+int rrtx_spline_get_generation(rrtx_spline* s, uint64_t* generation);
 
 /* -- pointwise queries at the caller's parameters: the methods of CubicSpline1D (:75-140) and CubicSpline2D (:248-310) --
  * The splines of the last completed rrtx_spline_run or rrtx_spline_fit1d stay on the device and answer, per spline, a list
@@ -792,6 +845,8 @@ int rrtx_bspline_get_coefficients(rrtx_bspline* s, int64_t* knot_offsets, double
 int rrtx_bspline_get_hits(rrtx_bspline* s, int32_t* hit);
 /* HIP-event time of the kernels of the last run (fit and evaluation; the prefix sum between them is not kernel time) */
 int rrtx_bspline_get_kernel_ms(rrtx_bspline* s, double* kernel_ms);
+/* Completed rrtx_bspline_run / rrtx_bspline_approximate calls on `s` so far (rrtx_track_source.generation) */
+int rrtx_bspline_get_generation(rrtx_bspline* s, uint64_t* generation);
 
 /* ---- the smoothing fit of approximate_b_spline_path (csrc/bspline_smooth.hip.h, csrc/rpp_bspline_smooth.h) -------------------
  * approximate_b_spline_path(x, y, n_path_points, degree, s) of 10_path_planning_00_bspline_path.py :12-56 for every course:

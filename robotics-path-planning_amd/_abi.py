@@ -39,6 +39,8 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_steer_select_free",
            "rrtx_tracker_create", "rrtx_tracker_destroy", "rrtx_tracker_last_error", "rrtx_tracker_run",
            "rrtx_tracker_get_counts", "rrtx_tracker_get_records", "rrtx_tracker_get_arrays", "rrtx_tracker_get_kernel_ms",
+           "rrtx_tracker_run_from", "rrtx_tracker_get_winners", "rrtx_tracker_get_goals", "rrtx_steer_get_generation",
+           "rrtx_spline_get_generation", "rrtx_bspline_get_generation",
            "rrtx_spline_create", "rrtx_spline_destroy", "rrtx_spline_last_error", "rrtx_spline_run", "rrtx_spline_get_records",
            "rrtx_spline_get_points", "rrtx_spline_get_c", "rrtx_spline_get_hits",
            "rrtx_spline_fit1d", "rrtx_spline_query", "rrtx_spline_get_query", "rrtx_spline_get_query_info",
@@ -61,6 +63,9 @@ STEER_OK, STEER_NO_PATH, STEER_RAISES_ZERODIV, STEER_RAISES_VALUE = 0, 1, 2, 3
 DUBINS_WORDS = ("LSL", "RSR", "LSR", "RSL", "RLR", "LRL")   # _PATH_TYPE_MAP order: the word indices of rrtx_steer_solve
 RS_COST_EUCLID, RS_COST_PATH = 0, 1     # include/rrtx.h: #define RRTX_RS_COST_*
 TRACK_FAIL_REACH, TRACK_FAIL_ANGLE, TRACK_FAIL_LONG, TRACK_FAIL_COLLISION = 1, 2, 4, 8   # #define RRTX_TRACK_FAIL_*
+OOD_DOMAIN, OOD_RAISES, OOD_OVERFLOW, OOD_NOT_FINITE, OOD_SKIPPED = 1, 2, 3, 4, 5        # rrtx_track_record.ood
+SRC_STEER, SRC_SPLINE, SRC_BSPLINE = 1, 2, 3                                             # #define RRTX_SRC_*
+SELECT_ALL, SELECT_FREE, SELECT_MASK = 0, 1, 2                                           # #define RRTX_SELECT_*
 SPLINE_OK, SPLINE_DEGENERATE, SPLINE_REF_RAISES = 0, 1, 2                                # #define RRTX_SPLINE_*
 SPLINE_MAX_WAYPOINTS, SPLINE_MAX_POINTS = 4096, 1 << 28
 SPLINE_Q_OK, SPLINE_Q_OUTSIDE, SPLINE_Q_REF_RAISES, SPLINE_Q_NO_SPLINE = 0, 1, 2, 3        # #define RRTX_SPLINE_Q_*
@@ -119,6 +124,26 @@ class TrackBatch(C.Structure):
                 ("per_course", C.c_void_p), ("start_state", C.c_void_p), ("obstacles", C.c_void_p),
                 ("obs_offsets", C.c_void_p), ("n_obstacles", C.c_int64), ("robot_radius", C.c_void_p),
                 ("robot_radius_per_course", C.c_int32), ("want_arrays", C.c_int32)]
+
+
+class TrackSource(C.Structure):
+    """rrtx_track_source: the producer whose device-resident courses one rrtx_tracker_run_from tracks."""
+    _fields_ = [("kind", C.c_int32), ("select", C.c_int32), ("object", C.c_void_p), ("generation", C.c_uint64),
+                ("mask", C.c_void_p), ("group", C.c_int64), ("arrays_of", C.c_int32)]
+
+
+def on_device(v):
+    """points="device" / arrays="device": solve as with True, fetch no point array, leave the courses to BatchTrack.run."""
+    return isinstance(v, str) and v == "device"
+
+
+class DeviceCourses:
+    """The courses a producer's solve left on the device: the owning native object (Steer, Spline or BSpline), its
+    RRTX_SRC_* kind and the generation of that solve.  BatchTrack.run reads them where they lie; the native call refuses
+    them (RRTX_E_STATE) once the owner has solved again."""
+
+    def __init__(self, kind, owner):
+        self.kind, self.owner, self.generation = kind, owner, owner.generation()
 
 
 SPLINE_RECORD = np.dtype([("status", np.int32), ("reserved", np.int32), ("n_points", np.int64), ("length", np.float64)])
@@ -286,6 +311,11 @@ def load():
     L.rrtx_tracker_get_records.argtypes = [vp, vp, vp]
     L.rrtx_tracker_get_arrays.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64]
     L.rrtx_tracker_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.rrtx_tracker_run_from.argtypes = [vp, C.POINTER(TrackParams), C.POINTER(TrackSource), C.POINTER(TrackBatch)]
+    L.rrtx_tracker_get_winners.argtypes = [vp, vp, i64p]
+    L.rrtx_tracker_get_goals.argtypes = [vp, vp]
+    for obj in ("steer", "spline", "bspline"):
+        getattr(L, "rrtx_%s_get_generation" % obj).argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rrtx_spline_create.argtypes = [i32, C.POINTER(vp)]
     L.rrtx_spline_destroy.argtypes = [vp]
     L.rrtx_spline_destroy.restype = None
@@ -773,6 +803,12 @@ class Steer:
             raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_steer_last_error(self._s).decode()))
         return rc
 
+    def generation(self):
+        """Completed solves of this object so far: what a DeviceCourses of its last solve carries."""
+        g = C.c_uint64()
+        self._chk(self.L.rrtx_steer_get_generation(self._s, C.byref(g)), "rrtx_steer_get_generation")
+        return g.value
+
     def solve(self, kind, starts, goals, curvature, step_size, word_order=None, points=True, product=False,
               _fn="rrtx_steer_solve"):
         """starts / goals: float64 arrays (n, 3) -- product: (ns, 3) and (ng, 3); curvature: a float or one value per pair;
@@ -999,6 +1035,25 @@ class Tracker:
         """params: TrackParams; batch: TrackBatch (its arrays are kept alive by the caller).  Returns 0 or RRTX_PARTIAL."""
         return self._chk(self.L.rrtx_tracker_run(self._t, C.byref(params), C.byref(batch)), "rrtx_tracker_run")
 
+    def run_from(self, params, source, batch):
+        """params: TrackParams; source: TrackSource; batch: TrackBatch without courses.  Returns 0 or RRTX_PARTIAL."""
+        return self._chk(self.L.rrtx_tracker_run_from(self._t, C.byref(params), C.byref(source), C.byref(batch)),
+                         "rrtx_tracker_run_from")
+
+    def winners(self):
+        """(n / group,) int32: the winning course of every group of the last run_from, -1 none."""
+        g = C.c_int64()
+        self._chk(self.L.rrtx_tracker_get_winners(self._t, None, C.byref(g)), "rrtx_tracker_get_winners")
+        w = np.zeros(g.value, dtype=np.int32)
+        self._chk(self.L.rrtx_tracker_get_winners(self._t, w.ctypes.data, None), "rrtx_tracker_get_winners")
+        return w
+
+    def goals(self, rows):
+        """(rows, 3): the goal poses of the last run_from -- one per group with a group, else one per course."""
+        go = np.full((rows, 3), np.nan)
+        self._chk(self.L.rrtx_tracker_get_goals(self._t, go.ctypes.data), "rrtx_tracker_get_goals")
+        return go
+
     def counts(self):
         n, m = C.c_int64(), C.c_int64()
         self._chk(self.L.rrtx_tracker_get_counts(self._t, C.byref(n), C.byref(m)), "rrtx_tracker_get_counts")
@@ -1060,6 +1115,12 @@ class Spline:
         if rc < 0:
             raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_spline_last_error(self._s).decode()))
         return rc
+
+    def generation(self):
+        """Completed solves of this object so far: what a DeviceCourses of its last solve carries."""
+        g = C.c_uint64()
+        self._chk(self.L.rrtx_spline_get_generation(self._s, C.byref(g)), "rrtx_spline_get_generation")
+        return g.value
 
     def run(self, batch):
         """batch: SplineBatch (its arrays are kept alive by the caller).  Returns 0 or RRTX_PARTIAL."""
@@ -1158,6 +1219,12 @@ class BSpline:
         if rc < 0:
             raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_bspline_last_error(self._s).decode()))
         return rc
+
+    def generation(self):
+        """Completed solves of this object so far: what a DeviceCourses of its last solve carries."""
+        g = C.c_uint64()
+        self._chk(self.L.rrtx_bspline_get_generation(self._s, C.byref(g)), "rrtx_bspline_get_generation")
+        return g.value
 
     def run(self, batch):
         """batch: BSplineBatch (its arrays are kept alive by the caller).  Returns 0 or RRTX_PARTIAL."""

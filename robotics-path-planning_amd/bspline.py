@@ -138,6 +138,7 @@ class BSplineResult:
         self.length = records["length"].copy()
         self.offsets = offsets
         self.x, self.y, self.yaw, self.k, self.u = arrays if arrays is not None else (None,) * 5
+        self.device_courses = None   # arrays="device": an _abi.DeviceCourses, and the five arrays are None
         self.knots = knots
         self.knot_offsets = knot_offsets
         self.coefficients = coefficients
@@ -239,8 +240,11 @@ class BatchBSpline:
         if keep["u"] is not None:
             _check_range(keep["u_offsets"], keep["u"], rec["status"], rec["length"])
         koff, knots, cx, cy = S.coefficients(len(rec), n_knots, int(keep["offsets"][-1]))
-        return BSplineResult(rec, off, S.points(int(off[-1])) if arrays else None, knots, koff, (cx, cy), keep["offsets"],
-                             S.hits(len(rec)) if keep["obstacles"] is not None else None, rc, ms)
+        res = BSplineResult(rec, off, S.points(int(off[-1])) if arrays and not _abi.on_device(arrays) else None, knots, koff,
+                            (cx, cy), keep["offsets"], S.hits(len(rec)) if keep["obstacles"] is not None else None, rc, ms)
+        if _abi.on_device(arrays):
+            res.device_courses = _abi.DeviceCourses(_abi.SRC_BSPLINE, S)
+        return res
 
     def interpolate(self, waypoints, n_path_points=None, degree=3, obstacle_list=None, robot_radius=0.0, arrays=True, u=None):
         """interpolate_b_spline_path(x, y, n_path_points, degree) (10_path_planning_00_bspline_path.py :59-108) for every
@@ -254,7 +258,8 @@ class BatchBSpline:
         values), instead of n_path_points -- or beside it, as a list with None for the courses that keep n_path_points;
         ValueError outside the range, as scipy's interp1d raises.  obstacle_list: rows
         (x, y, size) every point is tested against with robot_radius (result.hit / .free).  arrays=False: records, splines
-        and hits only."""
+        and hits only; arrays="device" (here, in spline2d and in approximate): the points stay on the device for
+        BatchTrack.run (result.device_courses), none is fetched."""
         return self._run(waypoints, arrays, degree=degree, param=_abi.BSPLINE_PARAM_NORMALISED, n_path_points=n_path_points,
                          u=u, obstacle_list=obstacle_list, robot_radius=robot_radius)
 
@@ -282,8 +287,11 @@ class BatchBSpline:
             warnings.warn("BatchBSpline.approximate: the fit stopped early on %d axes (ier 2 or 3: the root search on the "
                           "smoothing parameter; ier 1: no knot could be added); their last approximation is kept" % early,
                           RuntimeWarning, stacklevel=2)
-        return BSplineSmoothResult(rec, off, S.points(int(off[-1])) if arrays else None, axes, arec, keep["offsets"],
-                                   S.hits(len(rec)) if keep["obstacles"] is not None else None, rc, ms)
+        res = BSplineSmoothResult(rec, off, S.points(int(off[-1])) if arrays and not _abi.on_device(arrays) else None, axes,
+                                  arec, keep["offsets"], S.hits(len(rec)) if keep["obstacles"] is not None else None, rc, ms)
+        if _abi.on_device(arrays):
+            res.device_courses = _abi.DeviceCourses(_abi.SRC_BSPLINE, S)
+        return res
 
     def spline2d(self, waypoints, ds=0.1, kind="cubic", obstacle_list=None, robot_radius=0.0, arrays=True, u=None):
         """The driver loop of 10_path_planning_00_spline_2d.py (:45-54) for every course: Spline2D(x, y, kind), s of

@@ -210,6 +210,53 @@ RPP_HD static inline void judge(Record* r, int reached, double last_yaw_mod, dou
 // selection rule of search_best_feasible_path :1504-1513: `best_time >= t[-1]` lets a later candidate win a tie
 RPP_HD static inline bool better(int find, double tlast, double best_time) { return find && best_time >= tlast; }
 
+// ---- courses read in place from a producer's device buffers (rrtx_tracker_run_from) ------------------------------------
+// Record::ood there also takes 4: a pose component of the course is not finite (the host path refuses the whole batch for
+// this; here the host never sees the points), and 5: the selection left the course out, its points were not read.
+constexpr int OOD_NOT_FINITE = 4, OOD_SKIPPED = 5;
+constexpr int SEL_ALL = 0, SEL_FREE = 1, SEL_MASK = 2;   // include/rrtx.h RRTX_SELECT_*
+
+// NaN or +-inf
+RPP_HD static inline bool not_finite(double v) { return (rpp::d2b(v) & 0x7ff0000000000000ULL) == 0x7ff0000000000000ULL; }
+
+// Whether `select` keeps a course: hit is its entry of the producer's hits (SEL_FREE), mask its byte (SEL_MASK)
+RPP_HD static inline bool course_selected(int select, int32_t hit, uint8_t mask) {
+  return select == SEL_ALL || (select == SEL_FREE ? hit == -1 : mask != 0);
+}
+
+// The ood code of one course of `len` points, `cap` the longest course the kernel holds.  Asked twice: before the points
+// are read (any_not_finite = false; non-zero: they are not read) and after, with what reading them found.
+RPP_HD static inline int course_ood(bool selected, int64_t len, int64_t cap, bool any_not_finite) {
+  if (!selected) return OOD_SKIPPED;
+  if (len < 3) return 2;   // cy[-3] :1435 raises IndexError
+  if (len > cap) return 3;
+  return any_not_finite ? OOD_NOT_FINITE : 0;
+}
+
+// The same decision on one thread, reading the points only when the first answer is 0 (host checks)
+RPP_HD static inline int course_ood_scan(bool selected, int64_t len, int64_t cap, const double* x, const double* y,
+                                         const double* yaw) {
+  const int gate = course_ood(selected, len, cap, false);
+  if (gate) return gate;
+  bool bad = false;
+  for (int64_t q = 0; q < len; q++) bad = bad || not_finite(x[q]) || not_finite(y[q]) || not_finite(yaw[q]);
+  return course_ood(selected, len, cap, bad);
+}
+
+// search_best_feasible_path :1504-1513 over the g records of one group, in order: the position of the complete (ood == 0)
+// feasible record with the smallest t[-1], the later one of equal times; -1 none.  Records with ood != 0 are passed over
+// (TrackResult.best() raises on them instead).
+RPP_HD static inline int64_t group_pick(const Record* rec, int64_t g) {
+  double best_time = rpp::dinf();
+  int64_t win = -1;
+  for (int64_t k = 0; k < g; k++)
+    if (rec[k].ood == 0 && better(rec[k].find, rec[k].tlast, best_time)) {
+      best_time = rec[k].tlast;
+      win = k;
+    }
+  return win;
+}
+
 // get_goal_indexes :1566-1582 for one node
 RPP_HD static inline bool is_candidate(double x, double y, double yaw, double gx, double gy, double gyaw, const Params& P) {
   return rpp::py_hypot(x - gx, y - gy) <= P.xy_th && rpp::dabs(yaw - gyaw) <= P.yaw_th;

@@ -375,4 +375,116 @@ __global__ __launch_bounds__(TPB) void track_courses_kernel(CourseArgs a, int st
   }
 }
 
+// ---- courses read in place from a producer's device buffers (rrtx_tracker_run_from) -----------------------------------------
+struct SourceArgs {
+  CourseArgs c;            // off / x / y / yaw point into the producer's buffers; everything else is the tracker's
+  int32_t select;          // SEL_*
+  const int32_t* hit;      // SEL_FREE: the producer's hits, [n]
+  const uint8_t* mask;     // SEL_MASK: [n]
+  double* goal;            // [n][3]: the last point of every complete course (NaN otherwise), store = 0
+  int64_t group;           // 0, or the courses per group
+  int32_t* winner;         // [n / group]: track_group_pick_kernel's answer, a course index or -1
+  double* wgoal;           // [n / group][3]: the winner's last point (NaN without one)
+  int32_t winners_only;    // store = 1: only the group winners are rolled out again
+};
+
+// track_courses_kernel on a producer's points: the same queue, LDS / slab split, roll_course and store pass.  What differs: a
+// course the selection leaves out reports ood = 5 and its offsets and points are not read; while a course is copied into
+// LDS / the slab every x, y and yaw is tested for finiteness (one wave-wide OR, no second pass over the points), and a
+// course with a non-finite component reports ood = 4.  The host path refuses such a batch whole; here the host never sees
+// the points.
+__global__ __launch_bounds__(TPB) void track_source_kernel(SourceArgs s, int store) {
+  __shared__ double lcx[LDS_PTS], lcy[LDS_PTS];
+  __shared__ signed char lsp[SLAB_PTS];
+  __shared__ int32_t s_job, s_n;
+  const CourseArgs& a = s.c;
+  const int lane = threadIdx.x;
+  double* gcx = a.slab + (int64_t)blockIdx.x * 3 * SLAB_PTS;
+  double* gcy = gcx + SLAB_PTS;
+  double* gcw = gcy + SLAB_PTS;
+  for (;;) {
+    __syncthreads();
+    if (lane == 0) s_job = atomicAdd(a.counter, 1);
+    __syncthreads();
+    const int64_t c = s_job;
+    if (c >= a.n) break;
+    if (store && a.rec[c].ood) continue;
+    if (store && s.winners_only && s.winner[c / s.group] != (int32_t)c) continue;
+    Record r = {0, 0, 0, 0, 0.0};
+    const bool sel = course_selected(s.select, s.select == SEL_FREE ? s.hit[c] : 0, s.select == SEL_MASK ? s.mask[c] : 0);
+    int64_t b = 0, len = 0;
+    if (sel) {
+      b = a.off[c];
+      len = a.off[c + 1] - b;
+    }
+    constexpr int64_t CAP = SLAB_PTS - EXT_MAX;
+    r.ood = course_ood(sel, len, CAP, false);
+    const int total = (int)len;
+    double *cx = gcx, *cy = gcy;
+    if (!r.ood) {
+      if (total + EXT_MAX <= LDS_PTS) {
+        cx = lcx;
+        cy = lcy;
+      }
+      bool bad = false;
+      for (int q = lane; q < total; q += TPB) {
+        const double vx = a.x[b + q], vy = a.y[b + q], vw = a.yaw[b + q];
+        bad = bad || not_finite(vx) || not_finite(vy) || not_finite(vw);
+        cx[q] = vx;
+        cy[q] = vy;
+        gcw[q] = vw;
+      }
+      r.ood = course_ood(sel, len, CAP, __ballot(bad) != 0ULL);
+    }
+    double gx = rpp::b2d(0x7ff8000000000000ULL), gy = gx, gyaw = gx;
+    if (!r.ood) {
+      gx = a.x[b + total - 1], gy = a.y[b + total - 1], gyaw = a.yaw[b + total - 1];   // :1531
+      Params P = a.P;
+      if (a.per_course) {
+        P.target_speed = a.per_course[3 * c];
+        P.yaw_th = a.per_course[3 * c + 1];
+        P.invalid_travel_ratio = a.per_course[3 * c + 2];
+      }
+      State s0 = {-0.0, -0.0, 0.0, 0.0};   // :1309
+      if (a.start) {
+        s0.x = a.start[4 * c];
+        s0.y = a.start[4 * c + 1];
+        s0.yaw = a.start[4 * c + 2];
+        s0.v = a.start[4 * c + 3];
+      }
+      const int64_t ob = a.obs_off ? a.obs_off[c] : 0;
+      const int m = a.obs_off ? (int)(a.obs_off[c + 1] - ob) : a.m_shared;
+      double obx = 0.0, oby = 0.0, obt = -1.0;
+      if (lane < m) {
+        obx = a.ox[ob + lane];
+        oby = a.oy[ob + lane];
+        obt = a.othr[ob + c * a.thr_stride + lane];
+      }
+      double* o7 = nullptr;
+      int ocap = 0;
+      if (store) {
+        ocap = a.rec[c].n;
+        o7 = a.out + a.arr_off[c];
+      }
+      roll_course(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, a.out_total, r);
+    }
+    if (!store && lane == 0) {
+      a.rec[c] = r;
+      s.goal[3 * c] = gx;
+      s.goal[3 * c + 1] = gy;
+      s.goal[3 * c + 2] = gyaw;
+    }
+  }
+}
+
+// One thread per group of s.group consecutive courses: group_pick over its records, and the winner's last point
+__global__ void track_group_pick_kernel(SourceArgs s) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= s.c.n / s.group) return;
+  const int64_t k = group_pick(s.c.rec + j * s.group, s.group);
+  const int64_t w = k < 0 ? -1 : j * s.group + k;
+  s.winner[j] = (int32_t)w;
+  for (int q = 0; q < 3; q++) s.wgoal[3 * j + q] = w < 0 ? rpp::b2d(0x7ff8000000000000ULL) : s.goal[3 * w + q];
+}
+
 }  // namespace rppt

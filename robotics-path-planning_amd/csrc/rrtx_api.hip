@@ -1768,9 +1768,9 @@ int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps) {
 #include "rrtx_api_tools.inc"
 #include "rrtx_api_rccl.inc"
 #include "rrtx_api_steer.inc"
-#include "rrtx_api_tracker.inc"
 #include "rrtx_api_spline.inc"
 #include "rrtx_api_bspline.inc"
+#include "rrtx_api_tracker.inc"   // after the three producers: rrtx_tracker_run_from reads their objects
 #include "rrtx_api_armnav.inc"
 #include "rrtx_api_armik.inc"
 #include "rrtx_api_armdh.inc"

@@ -8,6 +8,7 @@ struct rrtx_bspline : DevObj {
   bool ran = false, has_arrays = false, has_hits = false, smooth = false;   // smooth: the last run was rrtx_bspline_approximate
   int64_t n = 0, n_wp = 0, n_points = 0, n_knots = 0;
   double kernel_ms = 0.0;
+  uint64_t generation = 0;   // completed runs and approximations, rrtx_bspline_get_generation
   std::vector<rppbs::Record> h_rec;
   std::vector<int64_t> h_off, h_wp_off, h_knot_off;
   std::vector<int32_t> h_hit;
@@ -301,7 +302,7 @@ const char* rrtx_bspline_last_error(rrtx_bspline* s) { return s ? s->err.c_str()
 
 int rrtx_bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b) {
   try {   // host allocations (records, offsets, messages) must not throw across the ABI
-    return bspline_run(s, b, nullptr, "rrtx_bspline_run: ");
+    return new_generation(s, bspline_run(s, b, nullptr, "rrtx_bspline_run: "));
   } catch (const std::exception& e) {
     if (s) s->ran = false;
     return fail(s, RRTX_E_HIP, std::string("rrtx_bspline_run: ") + e.what());
@@ -310,7 +311,7 @@ int rrtx_bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b) {
 
 int rrtx_bspline_approximate(rrtx_bspline* s, const rrtx_bspline_smooth_batch* sb) {
   try {
-    return bspline_run(s, sb ? &sb->run : nullptr, sb, "rrtx_bspline_approximate: ");
+    return new_generation(s, bspline_run(s, sb ? &sb->run : nullptr, sb, "rrtx_bspline_approximate: "));
   } catch (const std::exception& e) {
     if (s) s->ran = false;
     return fail(s, RRTX_E_HIP, std::string("rrtx_bspline_approximate: ") + e.what());
@@ -432,6 +433,12 @@ int rrtx_bspline_get_hits(rrtx_bspline* s, int32_t* hit) {
   if (s->n == 0) return RRTX_OK;
   if (!hit) return fail(s, RRTX_E_INVALID, "rrtx_bspline_get_hits: hit is NULL");
   memcpy(hit, s->h_hit.data(), sizeof(int32_t) * (size_t)s->n);
+  return RRTX_OK;
+}
+
+int rrtx_bspline_get_generation(rrtx_bspline* s, uint64_t* generation) {
+  if (!s || !generation) return fail(s, RRTX_E_INVALID, "rrtx_bspline_get_generation: a NULL pointer");
+  *generation = s->generation;
   return RRTX_OK;
 }
 

@@ -9,6 +9,7 @@ struct rrtx_spline : DevObj {
   int axes = 2;
   int64_t n = 0, n_wp = 0, n_points = 0;
   double kernel_ms = 0.0;
+  uint64_t generation = 0;   // completed runs and fit1d calls, rrtx_spline_get_generation
   // the last query against it
   bool queried = false, q_deriv = false;
   int64_t n_q = 0;
@@ -378,7 +379,7 @@ const char* rrtx_spline_last_error(rrtx_spline* s) { return s ? s->err.c_str() :
 
 int rrtx_spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
   try {   // host allocations (records, offsets, messages) must not throw across the ABI
-    return spline_run(s, b);
+    return new_generation(s, spline_run(s, b));
   } catch (const std::exception& e) {
     if (s) s->ran = false;
     return fail(s, RRTX_E_HIP, std::string("rrtx_spline_run: ") + e.what());
@@ -432,9 +433,15 @@ int rrtx_spline_get_hits(rrtx_spline* s, int32_t* hit) {
   return RRTX_OK;
 }
 
+int rrtx_spline_get_generation(rrtx_spline* s, uint64_t* generation) {
+  if (!s || !generation) return fail(s, RRTX_E_INVALID, "rrtx_spline_get_generation: a NULL pointer");
+  *generation = s->generation;
+  return RRTX_OK;
+}
+
 int rrtx_spline_fit1d(rrtx_spline* s, const rrtx_spline_fit1d_batch* b) {
   try {
-    return spline_fit1d(s, b);
+    return new_generation(s, spline_fit1d(s, b));
   } catch (const std::exception& e) {
     if (s) s->ran = false;
     return fail(s, RRTX_E_HIP, std::string("rrtx_spline_fit1d: ") + e.what());

@@ -14,6 +14,7 @@ struct rrtx_steer : DevObj {
   int kind = rppsb::KIND_DUBINS;
   int64_t n = 0, n_points = 0;
   double kernel_ms = 0.0;
+  uint64_t generation = 0;   // completed solves (every entry point that writes the buffers above), rrtx_steer_get_generation
   std::vector<int64_t> h_offsets;
   // the last rrtx_steer_solve_all: every candidate of every pair.  Pair-level status is `status` above; everything per
   // candidate lives in buffers of its own, so that rrtx_steer_select_free can write an ordinary result beside them.
@@ -352,8 +353,8 @@ int rrtx_steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, in
                      const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
                      const int32_t* word_order, int32_t n_words, int32_t want_points) {
   try {   // host allocations (offsets, messages) must not throw across the ABI
-    return steer_solve(s, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size, word_order, n_words,
-                       want_points);
+    return new_generation(s, steer_solve(s, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size,
+                                         word_order, n_words, want_points));
   } catch (const std::exception& e) {
     if (s) s->solved = false;
     return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve: ") + e.what());
@@ -363,7 +364,7 @@ int rrtx_steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, in
 int rrtx_steer_solve_lqr(rrtx_steer* s, int32_t product, int64_t n, int64_t ng, const double* starts, const double* goals,
                          double step_size, double max_time, double goal_dist, int32_t want_points) {
   try {
-    return steer_solve_lqr(s, product, n, ng, starts, goals, step_size, max_time, goal_dist, want_points);
+    return new_generation(s, steer_solve_lqr(s, product, n, ng, starts, goals, step_size, max_time, goal_dist, want_points));
   } catch (const std::exception& e) {
     if (s) s->solved = false;
     return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve_lqr: ") + e.what());
@@ -563,7 +564,8 @@ int rrtx_steer_solve_bezier(rrtx_steer* s, int32_t product, int64_t n, int64_t n
                             double offset0, const double* offsets, int32_t n_points, int32_t want_points,
                             int32_t want_curvature) {
   try {
-    return steer_solve_bezier(s, product, n, ng, starts, goals, offset0, offsets, n_points, want_points, want_curvature);
+    return new_generation(s, steer_solve_bezier(s, product, n, ng, starts, goals, offset0, offsets, n_points, want_points,
+                                                want_curvature));
   } catch (const std::exception& e) {
     if (s) s->solved = false;
     return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve_bezier: ") + e.what());
@@ -573,7 +575,7 @@ int rrtx_steer_solve_bezier(rrtx_steer* s, int32_t product, int64_t n, int64_t n
 int rrtx_steer_solve_bezier_cp(rrtx_steer* s, int64_t n, int32_t m, const double* control_points, int32_t n_points,
                                int32_t want_points, int32_t want_curvature) {
   try {
-    return steer_solve_bezier_cp(s, n, m, control_points, n_points, want_points, want_curvature);
+    return new_generation(s, steer_solve_bezier_cp(s, n, m, control_points, n_points, want_points, want_curvature));
   } catch (const std::exception& e) {
     if (s) s->solved = false;
     return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve_bezier_cp: ") + e.what());
@@ -898,8 +900,8 @@ int rrtx_steer_solve_all(rrtx_steer* s, int32_t kind, int32_t product, int64_t n
                          const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
                          const int32_t* word_order, int32_t n_words, int32_t want_points) {
   try {
-    return steer_solve_all(s, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size, word_order,
-                           n_words, want_points);
+    return new_generation(s, steer_solve_all(s, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size,
+                                             word_order, n_words, want_points));
   } catch (const std::exception& e) {
     if (s) s->cand_solved = false;
     return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve_all: ") + e.what());
@@ -1059,11 +1061,17 @@ static int steer_select_free(rrtx_steer* s, int32_t* chosen, int32_t* rank, int3
 
 int rrtx_steer_select_free(rrtx_steer* s, int32_t* chosen, int32_t* rank, int32_t* n_free) {
   try {
-    return steer_select_free(s, chosen, rank, n_free);
+    return new_generation(s, steer_select_free(s, chosen, rank, n_free));
   } catch (const std::exception& e) {
     if (s) s->solved = false;
     return fail(s, RRTX_E_HIP, std::string("rrtx_steer_select_free: ") + e.what());
   }
+}
+
+int rrtx_steer_get_generation(rrtx_steer* s, uint64_t* generation) {
+  if (!s || !generation) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_generation: a NULL pointer");
+  *generation = s->generation;
+  return RRTX_OK;
 }
 
 int rrtx_steer_get_kernel_ms(rrtx_steer* s, double* kernel_ms) {

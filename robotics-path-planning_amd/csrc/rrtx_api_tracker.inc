@@ -1,5 +1,6 @@
 // rrtx_api_tracker.inc -- rrtx_tracker_*: batched closed-loop tracking of courses given as data (rrt_track.hip.h,
-// track_courses_kernel); included by rrtx_api.hip
+// track_courses_kernel) or left on the device by a producer (track_source_kernel, track_group_pick_kernel); included by
+// rrtx_api.hip after the producers' files
 struct rrtx_tracker : DevObj {
   // device buffers, grown on demand
   DevBuf off, x, y, yaw, per_course, start, ox, oy, othr, obs_off, rec, counter, slab, out, arr_off;
@@ -9,7 +10,15 @@ struct rrtx_tracker : DevObj {
   double kernel_ms = 0.0;
   std::vector<rppt::Record> h_rec;
   std::vector<int64_t> h_arr_off;
+  // the last run when it was rrtx_tracker_run_from
+  DevBuf mask, goal, winner, wgoal;
+  bool from = false;
+  int64_t group = 0;
+  std::vector<int32_t> h_winner;
 };
+
+static_assert(rppt::SEL_ALL == RRTX_SELECT_ALL && rppt::SEL_FREE == RRTX_SELECT_FREE && rppt::SEL_MASK == RRTX_SELECT_MASK,
+              "the selections of the header are the core's");
 
 extern "C" {
 
@@ -183,11 +192,312 @@ static int tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_
 
 int rrtx_tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_batch* b) {
   try {   // host allocations (records, offsets, messages) must not throw across the ABI
-    return tracker_run(t, tp, b);
+    const int rc = tracker_run(t, tp, b);
+    if (t && rc >= 0) t->from = false, t->group = 0;   // this run has no winners and no goals to serve
+    return rc;
   } catch (const std::exception& e) {
     if (t) t->ran = false;
     return fail(t, RRTX_E_HIP, std::string("rrtx_tracker_run: ") + e.what());
   }
+}
+
+}  // extern "C"
+
+// ---- rrtx_tracker_run_from: the courses of a producer's last solve, read where they lie ----------------------------------------
+namespace {
+// What the tracker needs of a producer's last solve, whichever of the three objects it is
+struct TrackSourceView {
+  int device = 0;
+  bool ran = false, has_points = false, has_hits = false;
+  const char* no_run = "the source has no completed run";
+  const char* no_points = "the source ran without points";
+  uint64_t generation = 0;
+  int64_t n = 0, n_points = 0;
+  const int64_t* off = nullptr;                              // device, n + 1
+  const double *x = nullptr, *y = nullptr, *yaw = nullptr;   // device, n_points each
+  const int32_t* d_hit = nullptr;                            // device (steer) ...
+  const int32_t* h_hit = nullptr;                            // ... or host (spline, bspline), n
+};
+
+TrackSourceView track_source_view(int32_t kind, const void* object) {
+  TrackSourceView v;
+  if (kind == RRTX_SRC_STEER) {
+    const rrtx_steer* s = (const rrtx_steer*)object;
+    v.device = s->device;
+    v.ran = s->solved;
+    if (s->cand_solved) v.no_run = "the last steer solve was rrtx_steer_solve_all and rrtx_steer_select_free has not followed";
+    v.has_points = s->has_points && s->kind != rppsb::KIND_LQR;
+    if (s->kind == rppsb::KIND_LQR) v.no_points = "the last steer solve was an LQR solve: a rollout has no yaw";
+    else v.no_points = "the last steer solve was lengths-only, it has no points";
+    v.has_hits = s->has_hits;
+    v.generation = s->generation;
+    v.n = s->n;
+    v.n_points = s->n_points;
+    v.off = s->offsets.as<const int64_t>();
+    v.x = s->px.as<const double>();
+    v.y = s->py.as<const double>();
+    v.yaw = s->pyaw.as<const double>();
+    v.d_hit = s->hit.as<const int32_t>();
+  } else if (kind == RRTX_SRC_SPLINE) {
+    const rrtx_spline* s = (const rrtx_spline*)object;
+    v.device = s->device;
+    v.ran = s->ran;
+    v.has_points = s->has_arrays && s->axes == 2;
+    v.no_points = s->axes == 2 ? "the last spline run was records-only, it has no points" : "one-dimensional splines are no courses";
+    v.has_hits = s->has_hits;
+    v.generation = s->generation;
+    v.n = s->n;
+    v.n_points = s->n_points;
+    v.off = s->pt_off.as<const int64_t>();
+    v.x = s->out.as<const double>();
+    v.y = v.x + s->n_points;
+    v.yaw = v.x + 2 * s->n_points;
+    v.h_hit = s->h_hit.data();
+  } else {
+    const rrtx_bspline* s = (const rrtx_bspline*)object;
+    v.device = s->device;
+    v.ran = s->ran;
+    v.has_points = s->has_arrays;
+    v.no_points = "the last B-spline run was records-only, it has no points";
+    v.has_hits = s->has_hits;
+    v.generation = s->generation;
+    v.n = s->n;
+    v.n_points = s->n_points;
+    v.off = s->pt_off.as<const int64_t>();
+    v.x = s->out.as<const double>();
+    v.y = v.x + s->n_points;
+    v.yaw = v.x + 2 * s->n_points;
+    v.h_hit = s->h_hit.data();
+  }
+  return v;
+}
+}  // namespace
+
+static int tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_source* src, const rrtx_track_batch* b) {
+  const char* fn = "rrtx_tracker_run_from: ";
+  auto bad = [&](const char* m) { return fail(t, RRTX_E_INVALID, std::string(fn) + m); };
+  auto state = [&](const char* m) { return fail(t, RRTX_E_STATE, std::string(fn) + m); };
+  if (!t) return bad("the tracker is NULL");
+  if (!tp || !src || !b) return bad("the parameters, the source or the batch is NULL");
+  if (src->kind != RRTX_SRC_STEER && src->kind != RRTX_SRC_SPLINE && src->kind != RRTX_SRC_BSPLINE) return bad("unknown source kind");
+  if (src->select != RRTX_SELECT_ALL && src->select != RRTX_SELECT_FREE && src->select != RRTX_SELECT_MASK) return bad("unknown select");
+  if (src->arrays_of != 0 && src->arrays_of != 1) return bad("unknown arrays_of");
+  if (!src->object) return bad("the source object is NULL");
+  if (b->offsets || b->x || b->y || b->yaw) return bad("offsets, x, y and yaw must be NULL: the courses are the source's");
+  if (b->n < 0 || b->n > (1LL << 30)) return bad("n is negative or above 2^30");
+  const int64_t n = b->n;
+  if (src->group < 0) return bad("group is negative");
+  if (src->group > 0 && n % src->group != 0) return bad("n is not a multiple of group");
+  if (src->arrays_of == 1 && src->group == 0) return bad("arrays_of = 1 needs a group");
+  if (src->select == RRTX_SELECT_MASK && !src->mask) return bad("mask is NULL");
+  if (src->select != RRTX_SELECT_MASK && src->mask) return bad("a mask is given without RRTX_SELECT_MASK");
+  // as rrtx_tracker_run, of the fields that remain
+  if (!b->robot_radius) return bad("robot_radius is NULL");
+  if (b->n_obstacles < 0) return bad("n_obstacles is negative");
+  if (b->n_obstacles > 0 && !b->obstacles) return bad("obstacles is NULL");
+  if (b->obs_offsets) {
+    if (!csr_ok(b->obs_offsets, n)) return bad("obs_offsets do not start at 0 or decrease");
+    if (b->obs_offsets[n] > b->n_obstacles) return bad("obs_offsets end beyond n_obstacles");
+    for (int64_t i = 0; i < n; i++)
+      if (b->obs_offsets[i + 1] - b->obs_offsets[i] > rppt::TPB) return bad("more than 64 obstacles in one list");
+  } else if (b->n_obstacles > rppt::TPB) {
+    return bad("more than 64 obstacles in one list");
+  }
+  if (!track_params_ok(tp)) return bad(TRACK_PARAMS_MSG);
+  const int64_t n_rr = b->robot_radius_per_course ? n : 1;
+  if (!all_finite(b->obstacles, 3 * b->n_obstacles)) return bad("an obstacle component is not finite");
+  if (!all_finite(b->robot_radius, n_rr)) return bad("a robot radius is not finite");
+  if (b->start_state && !all_finite(b->start_state, 4 * n)) return bad("a start state component is not finite");
+  if (b->per_course && !all_finite(b->per_course, 3 * n)) return bad("a per-course value is not finite");
+  if (!all_finite(&tp->target_speed, sizeof(*tp) / sizeof(double))) return bad("a parameter is not finite");
+  if (!t->usable) return fail(t, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  const TrackSourceView v = track_source_view(src->kind, src->object);
+  if (v.device != t->device) return bad("the source is on another device");
+  if (!v.ran) return state(v.no_run);
+  if (v.generation != src->generation) return state("the generation is stale: the source has solved again since");
+  if (!v.has_points) return state(v.no_points);
+  if (src->select == RRTX_SELECT_FREE && !v.has_hits) return state("RRTX_SELECT_FREE, but the source ran without an obstacle list");
+  if (n != v.n) return bad("n is not the source's course count");
+
+  const int64_t g = src->group, n_groups = g ? n / g : 0;
+  const bool winners_only = src->arrays_of == 1;
+  t->ran = false;
+  t->has_arrays = false;
+  t->from = true;
+  t->group = g;
+  t->n = n;
+  t->n_steps = 0;
+  t->kernel_ms = 0.0;
+  t->h_rec.clear();
+  t->h_arr_off.assign((size_t)n + 1, 0);
+  t->h_winner.assign((size_t)n_groups, -1);
+  if (n == 0) {
+    t->has_arrays = b->want_arrays != 0;
+    t->ran = true;
+    return RRTX_OK;
+  }
+  // obstacle table, as rrtx_tracker_run builds it
+  const int64_t rows = b->obs_offsets ? b->obs_offsets[n] : b->n_obstacles;
+  const bool thr_per_course = !b->obs_offsets && b->robot_radius_per_course && rows > 0;
+  std::vector<double> ox((size_t)rows), oy((size_t)rows), othr((size_t)(thr_per_course ? rows * n : rows));
+  for (int64_t k = 0; k < rows; k++) {
+    ox[k] = b->obstacles[3 * k];
+    oy[k] = b->obstacles[3 * k + 1];
+  }
+  if (b->obs_offsets) {
+    for (int64_t i = 0; i < n; i++)
+      for (int64_t k = b->obs_offsets[i]; k < b->obs_offsets[i + 1]; k++)
+        othr[k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[b->robot_radius_per_course ? i : 0]);
+  } else if (thr_per_course) {
+    for (int64_t i = 0; i < n; i++)
+      for (int64_t k = 0; k < rows; k++) othr[i * rows + k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[i]);
+  } else {
+    for (int64_t k = 0; k < rows; k++) othr[k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[0]);
+  }
+  // the selection as the kernel reads it: the caller's mask, a steer's hits on the device, or a mask made of a spline's
+  // hits (they live on the host, where a course without a sample is marked -2)
+  int select = src->select;
+  std::vector<uint8_t> free_mask;
+  const uint8_t* h_mask = src->mask;
+  if (select == RRTX_SELECT_FREE && !v.d_hit) {
+    free_mask.resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) free_mask[(size_t)i] = v.h_hit[i] == -1;
+    h_mask = free_mask.data();
+    select = RRTX_SELECT_MASK;
+  }
+
+  HIPCHK(t, hipSetDevice(t->device));
+  int rc;
+  const size_t N = (size_t)n;
+  const int64_t want = (int64_t)t->n_cu * 16;   // 16 blocks of one wave per CU, as track_roll_kernel
+  int blocks = (int)(n < want ? n : want);
+  if (blocks < 1) blocks = 1;
+  // a source without a single point never put its offsets on the device: every course is empty
+  const int64_t* d_off = v.off;
+  if (v.n_points == 0) {
+    if ((rc = t->reserve(t->off, sizeof(int64_t) * (N + 1)))) return rc;
+    HIPCHK(t, hipMemsetAsync(t->off.p, 0, sizeof(int64_t) * (N + 1), t->stream));
+    d_off = t->off.as<const int64_t>();
+  }
+  if (select == RRTX_SELECT_MASK && (rc = t->upload(t->mask, h_mask, N))) return rc;
+  if (b->per_course && (rc = t->upload(t->per_course, b->per_course, sizeof(double) * 3 * N))) return rc;
+  if (b->start_state && (rc = t->upload(t->start, b->start_state, sizeof(double) * 4 * N))) return rc;
+  if ((rc = t->upload(t->ox, ox.data(), sizeof(double) * ox.size()))) return rc;
+  if ((rc = t->upload(t->oy, oy.data(), sizeof(double) * oy.size()))) return rc;
+  if ((rc = t->upload(t->othr, othr.data(), sizeof(double) * othr.size()))) return rc;
+  if (b->obs_offsets && (rc = t->upload(t->obs_off, b->obs_offsets, sizeof(int64_t) * (N + 1)))) return rc;
+  if ((rc = t->reserve(t->rec, sizeof(rppt::Record) * N))) return rc;
+  if ((rc = t->reserve(t->goal, sizeof(double) * 3 * N))) return rc;
+  if (g && (rc = t->reserve(t->winner, sizeof(int32_t) * (size_t)n_groups))) return rc;
+  if (g && (rc = t->reserve(t->wgoal, sizeof(double) * 3 * (size_t)n_groups))) return rc;
+  if ((rc = t->reserve(t->counter, sizeof(int32_t)))) return rc;
+  if ((rc = t->reserve(t->slab, sizeof(double) * (size_t)blocks * 3 * rppt::SLAB_PTS))) return rc;
+  HIPCHK(t, hipMemsetAsync(t->counter.p, 0, sizeof(int32_t), t->stream));
+
+  rppt::SourceArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  rppt::CourseArgs& a = sa.c;
+  a.n = n;
+  a.off = d_off;
+  a.x = v.x;
+  a.y = v.y;
+  a.yaw = v.yaw;
+  a.per_course = b->per_course ? t->per_course.as<const double>() : nullptr;
+  a.start = b->start_state ? t->start.as<const double>() : nullptr;
+  a.ox = t->ox.as<const double>();
+  a.oy = t->oy.as<const double>();
+  a.othr = t->othr.as<const double>();
+  a.obs_off = b->obs_offsets ? t->obs_off.as<const int64_t>() : nullptr;
+  a.thr_stride = thr_per_course ? rows : 0;
+  a.m_shared = b->obs_offsets ? 0 : (int32_t)rows;
+  memcpy(&a.P, tp, sizeof(a.P));
+  a.rec = t->rec.as<rppt::Record>();
+  a.counter = t->counter.as<int32_t>();
+  a.slab = t->slab.as<double>();
+  sa.select = select;
+  sa.hit = select == RRTX_SELECT_FREE ? v.d_hit : nullptr;
+  sa.mask = select == RRTX_SELECT_MASK ? t->mask.as<const uint8_t>() : nullptr;
+  sa.goal = t->goal.as<double>();
+  sa.group = g;
+  sa.winner = g ? t->winner.as<int32_t>() : nullptr;
+  sa.wgoal = g ? t->wgoal.as<double>() : nullptr;
+
+  // first launch: the records, and with a group the pick over them
+  t->h_rec.resize(N);
+  float ms = 0.f;
+  rc = t->timed(&ms, [&] {
+    hipLaunchKernelGGL(rppt::track_source_kernel, dim3(blocks), dim3(rppt::TPB), 0, t->stream, sa, 0);
+    if (g) hipLaunchKernelGGL(rppt::track_group_pick_kernel, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, t->stream, sa);
+  }, [&]() -> int {
+    HIPCHK(t, hipMemcpyAsync(t->h_rec.data(), t->rec.p, sizeof(rppt::Record) * N, hipMemcpyDeviceToHost, t->stream));
+    if (g) HIPCHK(t, hipMemcpyAsync(t->h_winner.data(), t->winner.p, sizeof(int32_t) * (size_t)n_groups, hipMemcpyDeviceToHost, t->stream));
+    return RRTX_OK;
+  });
+  if (rc) return rc;
+  t->kernel_ms = ms;
+
+  // arr_offsets: exclusive sum of len over the courses that own entries (the complete ones, or of those the winners)
+  int64_t tot = 0;
+  bool partial = false;
+  for (size_t i = 0; i < N; i++) {
+    t->h_arr_off[i] = tot;
+    const int ood = t->h_rec[i].ood;
+    if (ood && ood != rppt::OOD_SKIPPED) partial = true;
+    if (!ood && (!winners_only || t->h_winner[i / (size_t)g] == (int32_t)i)) tot += t->h_rec[i].n;
+  }
+  t->h_arr_off[N] = tot;
+  t->n_steps = tot;
+
+  if (b->want_arrays) {
+    if (tot > 0) {
+      if ((rc = t->reserve(t->out, sizeof(double) * 7 * (size_t)tot))) return rc;
+      if ((rc = t->upload(t->arr_off, t->h_arr_off.data(), sizeof(int64_t) * (N + 1)))) return rc;
+      HIPCHK(t, hipMemsetAsync(t->counter.p, 0, sizeof(int32_t), t->stream));
+      a.out = t->out.as<double>();
+      a.arr_off = t->arr_off.as<const int64_t>();
+      a.out_total = tot;
+      sa.winners_only = winners_only ? 1 : 0;
+      rc = t->timed(&ms, [&] { hipLaunchKernelGGL(rppt::track_source_kernel, dim3(blocks), dim3(rppt::TPB), 0, t->stream, sa, 1); });
+      if (rc) return rc;
+      t->kernel_ms += ms;
+    }
+    t->has_arrays = true;
+  }
+  t->ran = true;
+  if (partial) {
+    t->err = std::string(fn) + "some courses are too short, too long, not finite or left the replica's domain (see the ood column)";
+    return RRTX_PARTIAL;
+  }
+  return RRTX_OK;
+}
+
+extern "C" {
+
+int rrtx_tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_source* src, const rrtx_track_batch* b) {
+  try {
+    return tracker_run_from(t, tp, src, b);
+  } catch (const std::exception& e) {
+    if (t) t->ran = false;
+    return fail(t, RRTX_E_HIP, std::string("rrtx_tracker_run_from: ") + e.what());
+  }
+}
+
+int rrtx_tracker_get_winners(rrtx_tracker* t, int32_t* winner, int64_t* n_groups) {
+  if (!t) return fail(t, RRTX_E_INVALID, "rrtx_tracker_get_winners: the tracker is NULL");
+  if (!t->ran || !t->from || t->group == 0) return fail(t, RRTX_E_STATE, "rrtx_tracker_get_winners: no completed run with a group");
+  if (n_groups) *n_groups = (int64_t)t->h_winner.size();
+  if (winner && !t->h_winner.empty()) memcpy(winner, t->h_winner.data(), sizeof(int32_t) * t->h_winner.size());
+  return RRTX_OK;
+}
+
+int rrtx_tracker_get_goals(rrtx_tracker* t, double* goals) {
+  if (!t || !goals) return fail(t, RRTX_E_INVALID, "rrtx_tracker_get_goals: a NULL pointer");
+  if (!t->ran || !t->from) return fail(t, RRTX_E_STATE, "rrtx_tracker_get_goals: no completed rrtx_tracker_run_from");
+  const size_t rows = t->group ? t->h_winner.size() : (size_t)t->n;
+  if (rows == 0) return RRTX_OK;
+  HIPCHK(t, hipSetDevice(t->device));
+  HIPCHK(t, hipMemcpy(goals, t->group ? t->wgoal.p : t->goal.p, sizeof(double) * 3 * rows, hipMemcpyDeviceToHost));
+  return RRTX_OK;
 }
 
 int rrtx_tracker_get_counts(rrtx_tracker* t, int64_t* n_courses, int64_t* n_steps) {

@@ -61,6 +61,14 @@ int fail(Obj* o, int rc, const std::string& msg) {
   return rc;
 }
 
+// A solve or run that completed (RRTX_OK or RRTX_PARTIAL) wrote the object's device buffers anew: what an
+// rrtx_track_source names by its generation.  Returns rc.
+template <class Obj>
+int new_generation(Obj* o, int rc) {
+  if (o && rc >= 0) o->generation++;
+  return rc;
+}
+
 // Calls HIP; on an error records `#expr: message` on the object and returns RRTX_E_HIP from the calling function
 #define HIPCHK(obj, expr)                                                                              \
   do {                                                                                                 \

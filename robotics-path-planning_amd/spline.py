@@ -163,6 +163,7 @@ class SplineResult:
         self.total_length = records["length"].copy()
         self.offsets = offsets
         self.x, self.y, self.yaw, self.k, self.s = arrays if arrays is not None else (None,) * 5
+        self.device_courses = None   # arrays="device": an _abi.DeviceCourses, and the five arrays are None
         self.c = c
         self.wp_offsets = wp_offsets
         self.hit = hit
@@ -260,7 +261,8 @@ class BatchSpline:
         """waypoints: a list of (x, y) pairs of sequences, a CSR tuple (offsets, x, y), or a list of (n_i, 2) arrays such as
         planner paths (2 .. 4096 waypoints per course).  ds: a scalar or one value per course.  solve: "device" or "numpy"
         (see the module docstring); c=(cx, cy), flat over all waypoints, overrides it.  obstacle_list: rows (x, y, size)
-        every point is tested against with robot_radius (result.hit / .free).  arrays=False: records and hits only."""
+        every point is tested against with robot_radius (result.hit / .free).  arrays=False: records and hits only;
+        arrays="device": the points stay on the device for BatchTrack.run (result.device_courses), none is fetched."""
         if solve not in ("device", "numpy"):
             raise ValueError("BatchSpline: solve is 'device' or 'numpy'")
         if c is None and solve == "numpy":
@@ -284,8 +286,11 @@ class BatchSpline:
         rec, off, ms = S.records()
         self._n = len(rec)
         w = int(keep["offsets"][-1])
-        return SplineResult(rec, off, S.points(int(off[-1])) if arrays else None, S.c(w), keep["offsets"],
-                            S.hits(len(rec)) if keep["obstacles"] is not None else None, rc, ms)
+        res = SplineResult(rec, off, S.points(int(off[-1])) if arrays and not _abi.on_device(arrays) else None, S.c(w),
+                           keep["offsets"], S.hits(len(rec)) if keep["obstacles"] is not None else None, rc, ms)
+        if _abi.on_device(arrays):
+            res.device_courses = _abi.DeviceCourses(_abi.SRC_SPLINE, S)
+        return res
 
     def fit(self, waypoints, solve="device", c=None):
         """The splines of run() without a sample: fits every course and keeps it on the device for query().  Returns the

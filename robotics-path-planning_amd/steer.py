@@ -197,6 +197,7 @@ class SteerResult:
         self.kmax = kmax            # "bezier": (n,), or None
         self.control_points = control_points   # "bezier": (n, m, 2)
         self.rank = self.n_candidates = self.n_free = None   # plan_free()
+        self.device_courses = None   # points="device": an _abi.DeviceCourses, and x, y, yaw are None
 
     @property
     def free(self):
@@ -326,6 +327,8 @@ class BatchSteer:
         "bezier": plan(starts, goals, offset=3.0, n_points=100, curvature=True, points=True, product=False,
         obstacle_list=None, robot_radius=0.0) -- offset is calc_4points_bezier_path's, a float or one per pair; n_points
         (2..4096) the points per curve; curvature is a flag here (default True): k per point and kmax per curve."""
+        if _abi.on_device(points) and self.kind == _abi.STEER_LQR:
+            raise ValueError("BatchSteer('lqr').plan: points='device' is for courses of (x, y, yaw), a rollout has no yaw")
         if self.kind == _abi.STEER_BEZIER:
             if step_size is not None or selected_types is not None or resample is not True or max_time != 100.0 \
                     or goal_dist != 0.1:
@@ -355,9 +358,12 @@ class BatchSteer:
         ob = self._set_obstacles(obstacle_list, robot_radius)   # (nothing to clear when no list was ever set)
         rc = S.solve(self.kind, st, go, curvature, step_size, word_order=wo, points=points, product=product)
         status, length, nseg, seglen, modes, off = S.summary(offsets=bool(points))
-        xyz = S.points() if points else None
-        return SteerResult(self.kind, status, length, nseg, seglen, modes, off, xyz,
-                           (len(st), len(go)) if product else None, rc, S.kernel_ms(), hit=S.hits() if len(ob) else None)
+        xyz = S.points() if points and not _abi.on_device(points) else None
+        res = SteerResult(self.kind, status, length, nseg, seglen, modes, off, xyz,
+                          (len(st), len(go)) if product else None, rc, S.kernel_ms(), hit=S.hits() if len(ob) else None)
+        if _abi.on_device(points):
+            res.device_courses = _abi.DeviceCourses(_abi.SRC_STEER, S)
+        return res
 
     def _solve_all(self, what, starts, goals, curvature, step_size, selected_types, points, product, obstacle_list,
                    robot_radius):
@@ -381,6 +387,9 @@ class BatchSteer:
                    obstacle_list=None, robot_radius=0.0):
         """Every candidate curve of every pair ("rs": calc_paths' list; "dubins": one per feasible entry of the word list,
         a repeated word repeated), arguments as plan(): a SteerCandidates."""
+        if _abi.on_device(points):
+            raise ValueError("BatchSteer.candidates: points='device' is not supported, only the chosen curves of plan_free "
+                             "are a source of courses")
         rc, shape, ob = self._solve_all("candidates", starts, goals, curvature, step_size, selected_types, points, product,
                                         obstacle_list, robot_radius)
         S = self._steer
@@ -399,8 +408,10 @@ class BatchSteer:
         S = self._steer
         rc, _, rank, n_free = S.select_free()
         status, length, nseg, seglen, modes, off = S.summary(offsets=bool(points))
-        res = SteerResult(self.kind, status, length, nseg, seglen, modes, off, S.points() if points else None, shape, rc,
-                          S.kernel_ms(), hit=S.hits())
+        res = SteerResult(self.kind, status, length, nseg, seglen, modes, off,
+                          S.points() if points and not _abi.on_device(points) else None, shape, rc, S.kernel_ms(), hit=S.hits())
+        if _abi.on_device(points):
+            res.device_courses = _abi.DeviceCourses(_abi.SRC_STEER, S)
         res.rank, res.n_free = rank, n_free
         res.n_candidates = np.diff(S.cand_offsets()).astype(np.int32)
         return res
@@ -425,10 +436,14 @@ class BatchSteer:
             rc = S.solve_bezier(st, go, offset, n_points, points=points, curvature=curvature, product=product)
             shape = (len(st), len(go)) if product else None
         status, length, nseg, seglen, modes, off = S.summary(offsets=bool(points))
-        xyz = S.points() if points else None
-        return SteerResult(self.kind, status, length, nseg, seglen, modes, off, xyz, shape, rc, S.kernel_ms(),
-                           hit=S.hits() if len(ob) else None, k=S.curvature() if points and curvature else None,
-                           kmax=S.kmax() if curvature else None, control_points=S.control_points())
+        fetch = points and not _abi.on_device(points)
+        xyz = S.points() if fetch else None
+        res = SteerResult(self.kind, status, length, nseg, seglen, modes, off, xyz, shape, rc, S.kernel_ms(),
+                          hit=S.hits() if len(ob) else None, k=S.curvature() if fetch and curvature else None,
+                          kmax=S.kmax() if curvature else None, control_points=S.control_points())
+        if _abi.on_device(points):
+            res.device_courses = _abi.DeviceCourses(_abi.SRC_STEER, S)
+        return res
 
     def _set_obstacles(self, obstacle_list, robot_radius):
         S = self._steer
