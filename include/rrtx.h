@@ -31,7 +31,8 @@ extern "C" {
                                 rrtx_steer_solve_bezier, rrtx_steer_solve_bezier_cp, rrtx_steer_get_curvature, rrtx_steer_get_kmax,
                                 rrtx_steer_get_control_points, rrtx_steer_solve_all, rrtx_steer_get_cand_counts,
                                 rrtx_steer_get_cand_summary, rrtx_steer_get_cand_points, rrtx_steer_select_free, rrtx_tracker_run_from,
-                                rrtx_tracker_get_winners, rrtx_tracker_get_goals, rrtx_*_get_generation); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
+                                rrtx_tracker_get_winners, rrtx_tracker_get_goals, rrtx_*_get_generation, rrtx_gather_courses, rrtx_get_course_counts,
+                                rrtx_get_courses, rrtx_get_course_generation, RRTX_SRC_PLANNER); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
                                 rrtx_copy_results_device, per-instance yaw and informed rotation; 4: rrtx_plan_many,
                                 rrtx_selfcheck, rrtx_stats.main_shape / main_f32, rrtx_plan_begin / _step, rrtx_set_launch_bound,
                                 RRTX_ST_REF_HANGS, rrtx_rccl_* */
@@ -317,6 +318,34 @@ int rrtx_smooth_paths(int32_t device, int32_t n_jobs, const double* paths_xy, co
 int rrtx_smooth_planned(rrtx_handle* h, int32_t max_iter);
 int rrtx_get_smoothed_path(rrtx_handle* h, int32_t instance, double* xy, int32_t cap_points, int32_t* n_out);
 
+/* ---- every course of the batch in one gather on the device (csrc/course_gather.hip.h, csrc/rpp_course.h) ------------------
+ * rrtx_get_path, rrtx_get_path_yaw and rrtx_get_smoothed_path serve one instance per call.  rrtx_gather_courses builds the
+ * courses of ALL instances on the device as one CSR result -- offsets (n_instances + 1) into flat x, y (and yaw) -- with two
+ * kernel launches and a number of host <-> device copies that depends neither on the batch size nor on the depth of a
+ * tree; the getters below fetch it in one copy per column, and rrtx_tracker_run_from reads it where it lies
+ * (RRTX_SRC_PLANNER).  Every double is the one the per-instance getters return.
+ * which: RRTX_COURSE_PLANNED for every planner rrtx_get_path serves (a path the plan marked RRTX_ST_PATH_TRUNC is walked up
+ * the parent array on the device); RRTX_COURSE_SMOOTHED needs a completed rrtx_smooth_planned since the plan.  An instance
+ * without RRTX_ST_PATH owns no points.  Only RRTX_ALGO_RS planned courses have a yaw column.
+ * The buffers live on the handle and are reused (they grow, never shrink); every completed gather increments the
+ * generation (0 before the first).  More than 2^28 points in all: RRTX_E_CAPACITY.
+ * Checked before any launch: RRTX_E_INVALID for a NULL handle or an unknown which / order; RRTX_E_STATE without a
+ * completed plan, between rrtx_plan_begin and the end of that plan, and for RRTX_COURSE_SMOOTHED without a smoothing run.
+ * A new plan (for RRTX_COURSE_SMOOTHED also a new smoothing run) invalidates the gathered courses: the two getters then
+ * return RRTX_E_STATE until the next gather. */
+#define RRTX_COURSE_PLANNED 0    /* what rrtx_get_path (+ rrtx_get_path_yaw for RRTX_ALGO_RS) returns */
+#define RRTX_COURSE_SMOOTHED 1   /* what rrtx_get_smoothed_path returns */
+#define RRTX_ORDER_PLANNING 0    /* goal -> start, as planning() returns it */
+#define RRTX_ORDER_DRIVING 1     /* the same rows reversed */
+int rrtx_gather_courses(rrtx_handle* h, int32_t which, int32_t order);
+/* Of the last gather: offsets (n_instances + 1 entries, may be NULL), the point count, whether there is a yaw column, the
+ * HIP-event time of the two kernels; any pointer may be NULL. */
+int rrtx_get_course_counts(rrtx_handle* h, int64_t* offsets, int64_t* n_points, int32_t* has_yaw, double* kernel_ms);
+/* The flat columns of the last gather (cap = doubles available in each; RRTX_E_CAPACITY when too small); any pointer may be
+ * NULL, and yaw must be NULL when the gather has no yaw column (RRTX_E_STATE otherwise). */
+int rrtx_get_courses(rrtx_handle* h, double* x, double* y, double* yaw, int64_t cap);
+int rrtx_get_course_generation(rrtx_handle* h, uint64_t* generation);
+
 /* ---- closed-loop RRT* (rrt_10 = 10_path_planning_01_rrt_10_closed_loop_rrt_star.py) -----------------------------------
  * Tree phase: RRTX_ALGO_RS with expand_dis = +inf (rrt_10's class has no expand_dis attribute, so find_near_nodes
  * :522-531 does not clamp its radius) and rrtx_set_rs_cost(h, RRTX_RS_COST_PATH): rrt_10's RRTStarReedsShepp inherits
@@ -589,12 +618,13 @@ int rrtx_steer_get_generation(rrtx_steer* s, uint64_t* generation);
 #define RRTX_SRC_STEER 1
 #define RRTX_SRC_SPLINE 2
 #define RRTX_SRC_BSPLINE 3
+#define RRTX_SRC_PLANNER 4      /* object = rrtx_handle*: the courses of its last rrtx_gather_courses */
 #define RRTX_SELECT_ALL 0
 #define RRTX_SELECT_FREE 1   /* courses whose hit == -1; RRTX_E_STATE if the source ran without an obstacle list */
 #define RRTX_SELECT_MASK 2   /* mask[i] != 0 */
 typedef struct rrtx_track_source {
   int32_t kind, select;     /* RRTX_SRC_*, RRTX_SELECT_* */
-  const void* object;       /* rrtx_steer* / rrtx_spline* / rrtx_bspline* */
+  const void* object;       /* rrtx_steer* / rrtx_spline* / rrtx_bspline* / rrtx_handle* */
   uint64_t generation;      /* must equal the object's: else RRTX_E_STATE, nothing launched */
   const uint8_t* mask;      /* host, n bytes, RRTX_SELECT_MASK only */
   int64_t group;            /* 0, or a group size g >= 1 with n % g == 0: courses [j g, (j + 1) g) are group j */
@@ -616,7 +646,12 @@ typedef struct rrtx_track_source {
  * completed run, the generation is stale, the source ran without points (lengths-only, records-only, one-dimensional
  * splines), the last steer solve was an LQR solve (a rollout has no yaw) or an rrtx_steer_solve_all not followed by
  * rrtx_steer_select_free, RRTX_SELECT_FREE on a source without hits.  Then RRTX_E_INVALID when b->n is not the source's
- * course count.  Nothing is launched before all of them passed. */
+ * course count.  Nothing is launched before all of them passed.
+ * RRTX_SRC_PLANNER: the object must be a planner handle alive in this process (RRTX_E_INVALID otherwise, with the argument
+ * checks), b->n its instance count and generation that of rrtx_get_course_generation.  RRTX_E_STATE when there is no gather,
+ * when the handle has planned (or, for smoothed courses, smoothed) again since, when the gather has no yaw column or was
+ * made in RRTX_ORDER_PLANNING (the tracker drives the course), and for RRTX_SELECT_FREE (a planner's courses carry no
+ * hits).  An instance without a path is a course of length 0: ood = 2, or 5 when the mask leaves it out. */
 int rrtx_tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_source* src,
                           const rrtx_track_batch* b);
 /* The winners of the last rrtx_tracker_run_from with a group: winner (may be NULL) n / g course indices, -1 where a group

@@ -41,6 +41,7 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_tracker_get_counts", "rrtx_tracker_get_records", "rrtx_tracker_get_arrays", "rrtx_tracker_get_kernel_ms",
            "rrtx_tracker_run_from", "rrtx_tracker_get_winners", "rrtx_tracker_get_goals", "rrtx_steer_get_generation",
            "rrtx_spline_get_generation", "rrtx_bspline_get_generation",
+           "rrtx_gather_courses", "rrtx_get_course_counts", "rrtx_get_courses", "rrtx_get_course_generation",
            "rrtx_spline_create", "rrtx_spline_destroy", "rrtx_spline_last_error", "rrtx_spline_run", "rrtx_spline_get_records",
            "rrtx_spline_get_points", "rrtx_spline_get_c", "rrtx_spline_get_hits",
            "rrtx_spline_fit1d", "rrtx_spline_query", "rrtx_spline_get_query", "rrtx_spline_get_query_info",
@@ -64,7 +65,9 @@ DUBINS_WORDS = ("LSL", "RSR", "LSR", "RSL", "RLR", "LRL")   # _PATH_TYPE_MAP ord
 RS_COST_EUCLID, RS_COST_PATH = 0, 1     # include/rrtx.h: #define RRTX_RS_COST_*
 TRACK_FAIL_REACH, TRACK_FAIL_ANGLE, TRACK_FAIL_LONG, TRACK_FAIL_COLLISION = 1, 2, 4, 8   # #define RRTX_TRACK_FAIL_*
 OOD_DOMAIN, OOD_RAISES, OOD_OVERFLOW, OOD_NOT_FINITE, OOD_SKIPPED = 1, 2, 3, 4, 5        # rrtx_track_record.ood
-SRC_STEER, SRC_SPLINE, SRC_BSPLINE = 1, 2, 3                                             # #define RRTX_SRC_*
+SRC_STEER, SRC_SPLINE, SRC_BSPLINE, SRC_PLANNER = 1, 2, 3, 4                             # #define RRTX_SRC_*
+COURSE_PLANNED, COURSE_SMOOTHED = 0, 1                                                   # #define RRTX_COURSE_*
+ORDER_PLANNING, ORDER_DRIVING = 0, 1                                                     # #define RRTX_ORDER_*
 SELECT_ALL, SELECT_FREE, SELECT_MASK = 0, 1, 2                                           # #define RRTX_SELECT_*
 SPLINE_OK, SPLINE_DEGENERATE, SPLINE_REF_RAISES = 0, 1, 2                                # #define RRTX_SPLINE_*
 SPLINE_MAX_WAYPOINTS, SPLINE_MAX_POINTS = 4096, 1 << 28
@@ -138,8 +141,8 @@ def on_device(v):
 
 
 class DeviceCourses:
-    """The courses a producer's solve left on the device: the owning native object (Steer, Spline or BSpline), its
-    RRTX_SRC_* kind and the generation of that solve.  BatchTrack.run reads them where they lie; the native call refuses
+    """The courses a producer's solve left on the device: the owning native object (Steer, Spline, BSpline, or a planner
+    Handle after gather_courses), its RRTX_SRC_* kind and the generation of that solve.  BatchTrack.run reads them where they lie; the native call refuses
     them (RRTX_E_STATE) once the owner has solved again."""
 
     def __init__(self, kind, owner):
@@ -316,6 +319,10 @@ def load():
     L.rrtx_tracker_get_goals.argtypes = [vp, vp]
     for obj in ("steer", "spline", "bspline"):
         getattr(L, "rrtx_%s_get_generation" % obj).argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.rrtx_gather_courses.argtypes = [vp, i32, i32]
+    L.rrtx_get_course_counts.argtypes = [vp, vp, i64p, C.POINTER(i32), C.POINTER(C.c_double)]
+    L.rrtx_get_courses.argtypes = [vp, vp, vp, vp, C.c_int64]
+    L.rrtx_get_course_generation.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rrtx_spline_create.argtypes = [i32, C.POINTER(vp)]
     L.rrtx_spline_destroy.argtypes = [vp]
     L.rrtx_spline_destroy.restype = None
@@ -729,6 +736,37 @@ class Handle:
         self._chk(self.L.rrtx_get_smoothed_path(self._h, instance, xy.ctypes.data, n.value, C.byref(n)),
                   "rrtx_get_smoothed_path")
         return xy
+
+    # ---- every course of the batch in one gather on the device (rrtx_gather_courses)
+    @property
+    def _s(self):
+        """The native object, under the name the other producers of device-resident courses use (track.pack_source)."""
+        return self._h
+
+    def gather_courses(self, which=COURSE_PLANNED, order=ORDER_PLANNING):
+        self._chk(self.L.rrtx_gather_courses(self._h, int(which), int(order)), "rrtx_gather_courses")
+
+    def generation(self):
+        """Completed gathers on this handle so far (rrtx_track_source.generation)."""
+        g = C.c_uint64()
+        self._chk(self.L.rrtx_get_course_generation(self._h, C.byref(g)), "rrtx_get_course_generation")
+        return g.value
+
+    def get_course_counts(self):
+        """(offsets (n_instances + 1,), n_points, has_yaw, kernel_ms) of the last gather."""
+        off = np.zeros(self.n_instances + 1, dtype=np.int64)
+        n, hy, ms = C.c_int64(), C.c_int32(), C.c_double()
+        self._chk(self.L.rrtx_get_course_counts(self._h, off.ctypes.data, C.byref(n), C.byref(hy), C.byref(ms)),
+                  "rrtx_get_course_counts")
+        return off, n.value, bool(hy.value), ms.value
+
+    def get_courses(self, n_points, has_yaw):
+        """The flat (x, y, yaw) of the last gather; yaw is None without a yaw column."""
+        x, y = np.zeros(n_points), np.zeros(n_points)
+        yaw = np.zeros(n_points) if has_yaw else None
+        self._chk(self.L.rrtx_get_courses(self._h, x.ctypes.data, y.ctypes.data, None if yaw is None else yaw.ctypes.data,
+                                          n_points), "rrtx_get_courses")
+        return x, y, yaw
 
     def get_stats(self):
         s = Stats()

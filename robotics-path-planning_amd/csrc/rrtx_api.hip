@@ -7,7 +7,9 @@
 #include <chrono>
 #include <cstdio>
 #include <functional>
+#include <mutex>
 #include <new>
+#include <set>
 #include <vector>
 
 #include "rrtx_host.h"
@@ -22,6 +24,7 @@
 #include "path_smooth.hip.h"
 #include "rrt_lqr.hip.h"
 #include "rrt_track.hip.h"
+#include "course_gather.hip.h"
 #include "steer_batch.hip.h"
 #include "spline_batch.hip.h"
 #include "bspline_batch.hip.h"
@@ -129,6 +132,17 @@ struct rrtx_handle : DevObj {
     std::vector<int64_t> h_off;
     double ms = 0.0;
   } tk;
+  // the courses of the current plan, gathered into one CSR result (rrtx_gather_courses, course_gather.hip.h); the
+  // buffers grow and never shrink
+  struct Courses {
+    DevBuf count, off, x, y, yaw, pool;
+    bool valid = false, has_yaw = false;
+    int which = 0, order = 0;
+    int64_t n_points = 0;
+    uint64_t generation = 0;   // completed gathers so far: what an rrtx_track_source of RRTX_SRC_PLANNER names
+    std::vector<int64_t> h_off;
+    double kernel_ms = 0.0;
+  } cs;
 };
 
 template <class T>
@@ -276,6 +290,8 @@ static int estimate_near_capacity(const rrtx_params& p) {
 }
 
 static void rccl_release(rrtx_handle* h);   // rrtx_api_rccl.inc
+static void handle_register(const rrtx_handle* h);     // rrtx_api_courses.inc
+static void handle_unregister(const rrtx_handle* h);
 
 extern "C" {
 
@@ -291,6 +307,7 @@ const char* rrtx_last_error(rrtx_handle* h) { return h ? h->err.c_str() : "null 
 
 void rrtx_destroy(rrtx_handle* h) {
   if (!h) return;
+  handle_unregister(h);
   hipSetDevice(h->device);
   rccl_release(h);
   for (void* q : h->allocs) hipFree(q);
@@ -329,6 +346,7 @@ int rrtx_create(const rrtx_params* p, rrtx_handle** out) {
     h->v2_chunk_iters = h->chunk_iters;
   }
   *out = h;  // returned even on failure, of open() or below, so the caller can read last_error, then destroy
+  handle_register(h);
   if (rc) return rc;
   // node capacity: start + one node per iteration; padded so each wave's 512-node stride stays inside
   // (rrt_06: try_goal_path :1572-1582 can append a second node per iteration)
@@ -746,6 +764,7 @@ int rrtx_plan_begin(rrtx_handle* h) {
   h->planned = false;
   h->smoothed = false;     // rrtx_get_smoothed_path: the previous plan's smoothed paths are not this plan's
   h->tk.valid = false;     // the same for the tracked trajectories
+  h->cs.valid = false;     // and for the gathered courses (rrtx_gather_courses)
   h->traced_inst = -1;     // rrtx_get_trace: nothing recorded until this plan completes
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipDeviceSynchronize());   // uploads made through the null stream (obstacles, tables) are complete
@@ -1590,6 +1609,7 @@ int rrtx_smooth_planned(rrtx_handle* h, int32_t max_iter) {
   std::vector<int32_t> st(B);
   HIPCHK(h, hipMemcpy(st.data(), h->sm_status, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
   h->smoothed = true;
+  if (h->cs.which == RRTX_COURSE_SMOOTHED) h->cs.valid = false;   // gathered from the previous smoothing run
   return smooth_status_rc(st, &h->err);
 }
 
@@ -1770,7 +1790,8 @@ int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps) {
 #include "rrtx_api_steer.inc"
 #include "rrtx_api_spline.inc"
 #include "rrtx_api_bspline.inc"
-#include "rrtx_api_tracker.inc"   // after the three producers: rrtx_tracker_run_from reads their objects
+#include "rrtx_api_courses.inc"
+#include "rrtx_api_tracker.inc"   // after the four producers: rrtx_tracker_run_from reads their objects
 #include "rrtx_api_armnav.inc"
 #include "rrtx_api_armik.inc"
 #include "rrtx_api_armdh.inc"

@@ -205,7 +205,7 @@ int rrtx_tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_tr
 
 // ---- rrtx_tracker_run_from: the courses of a producer's last solve, read where they lie ----------------------------------------
 namespace {
-// What the tracker needs of a producer's last solve, whichever of the three objects it is
+// What the tracker needs of a producer's last solve, whichever of the four objects it is
 struct TrackSourceView {
   int device = 0;
   bool ran = false, has_points = false, has_hits = false;
@@ -253,6 +253,23 @@ TrackSourceView track_source_view(int32_t kind, const void* object) {
     v.y = v.x + s->n_points;
     v.yaw = v.x + 2 * s->n_points;
     v.h_hit = s->h_hit.data();
+  } else if (kind == RRTX_SRC_PLANNER) {
+    const rrtx_handle* h = (const rrtx_handle*)object;
+    v.device = h->device;
+    v.ran = h->planned && h->run.stage == 0 && h->cs.generation > 0;
+    v.no_run = "the planner has no completed plan with gathered courses (rrtx_gather_courses)";
+    // a gather of another plan (or smoothing run) is stale whatever its number
+    v.generation = courses_current(h) ? h->cs.generation : ~h->cs.generation;
+    v.has_points = h->cs.has_yaw && h->cs.order == RRTX_ORDER_DRIVING;
+    v.no_points = !h->cs.has_yaw ? "the gathered courses have no yaw (only RRTX_ALGO_RS planned courses do)"
+                                 : "the courses were gathered in planning order, the tracker drives them: gather RRTX_ORDER_DRIVING";
+    v.has_hits = false;
+    v.n = h->n_inst;
+    v.n_points = h->cs.n_points;
+    v.off = h->cs.off.as<const int64_t>();
+    v.x = h->cs.x.as<const double>();
+    v.y = h->cs.y.as<const double>();
+    v.yaw = h->cs.yaw.as<const double>();
   } else {
     const rrtx_bspline* s = (const rrtx_bspline*)object;
     v.device = s->device;
@@ -279,10 +296,12 @@ static int tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const 
   auto state = [&](const char* m) { return fail(t, RRTX_E_STATE, std::string(fn) + m); };
   if (!t) return bad("the tracker is NULL");
   if (!tp || !src || !b) return bad("the parameters, the source or the batch is NULL");
-  if (src->kind != RRTX_SRC_STEER && src->kind != RRTX_SRC_SPLINE && src->kind != RRTX_SRC_BSPLINE) return bad("unknown source kind");
+  if (src->kind != RRTX_SRC_STEER && src->kind != RRTX_SRC_SPLINE && src->kind != RRTX_SRC_BSPLINE && src->kind != RRTX_SRC_PLANNER)
+    return bad("unknown source kind");
   if (src->select != RRTX_SELECT_ALL && src->select != RRTX_SELECT_FREE && src->select != RRTX_SELECT_MASK) return bad("unknown select");
   if (src->arrays_of != 0 && src->arrays_of != 1) return bad("unknown arrays_of");
   if (!src->object) return bad("the source object is NULL");
+  if (src->kind == RRTX_SRC_PLANNER && !handle_is_live(src->object)) return bad("the source object is no planner handle of this process");
   if (b->offsets || b->x || b->y || b->yaw) return bad("offsets, x, y and yaw must be NULL: the courses are the source's");
   if (b->n < 0 || b->n > (1LL << 30)) return bad("n is negative or above 2^30");
   const int64_t n = b->n;
@@ -316,7 +335,9 @@ static int tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const 
   if (!v.ran) return state(v.no_run);
   if (v.generation != src->generation) return state("the generation is stale: the source has solved again since");
   if (!v.has_points) return state(v.no_points);
-  if (src->select == RRTX_SELECT_FREE && !v.has_hits) return state("RRTX_SELECT_FREE, but the source ran without an obstacle list");
+  if (src->select == RRTX_SELECT_FREE && !v.has_hits)
+    return state(src->kind == RRTX_SRC_PLANNER ? "RRTX_SELECT_FREE, but a planner's courses carry no hits"
+                                               : "RRTX_SELECT_FREE, but the source ran without an obstacle list");
   if (n != v.n) return bad("n is not the source's course count");
 
   const int64_t g = src->group, n_groups = g ? n / g : 0;

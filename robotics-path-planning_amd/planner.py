@@ -849,12 +849,64 @@ class BITStar:
         return [] if path is None else [[float(a), float(b)] for a, b in path]
 
 
+def check_device_courses(n_handles, has_yaw, order):
+    """The ValueErrors of BatchPlanner.courses(arrays="device"): what the tracker could not read on the device."""
+    if n_handles != 1:
+        raise ValueError("BatchPlanner.courses(arrays='device'): the batch is sharded over %d handles, the tracker reads "
+                         "one handle's courses" % n_handles)
+    if not has_yaw:
+        raise ValueError("BatchPlanner.courses(arrays='device'): these courses have no yaw (only the planned courses of "
+                         "'rrt_star_reeds_shepp' / 'closed_loop_rrt_star' do), the tracker needs (x, y, yaw)")
+    if order != "driving":
+        raise ValueError("BatchPlanner.courses(arrays='device'): the tracker drives the course, gather order='driving'")
+
+
 def get_path_length(path):
     """rrt_04:1391-1399."""
     le = 0
     for i in range(len(path) - 1):
         le += math.hypot(path[i + 1][0] - path[i][0], path[i + 1][1] - path[i][1])
     return le
+
+
+class PlannerCourses:
+    """Every course of a planned batch as one CSR result (BatchPlanner.courses): course i owns rows offsets[i] ..
+    offsets[i + 1] - 1 of the flat x, y and yaw (yaw is None unless the planner is "rrt_star_reeds_shepp" /
+    "closed_loop_rrt_star" and the courses are the planned ones).  n_points (n,) is np.diff(offsets), found the mask
+    n_points > 0, status (n,) 0 for an instance with a course and 1 (as RRTX_STEER_NO_PATH) for one without, kernel_ms the
+    HIP-event time of the gather (sharded planners: the slowest handle's).
+    With arrays="device" x, y and yaw are None and device_courses names the handle whose device buffers hold them:
+    BatchTrack.run reads them there."""
+
+    def __init__(self, offsets, x, y, yaw, order="planning", kernel_ms=0.0, device_courses=None):
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        self.x, self.y, self.yaw = x, y, yaw
+        self.order = order
+        self.kernel_ms = kernel_ms
+        self.n_points = np.diff(self.offsets)
+        self.found = self.n_points > 0
+        self.status = np.where(self.found, 0, 1).astype(np.int32)
+        if device_courses is not None:
+            self.device_courses = device_courses
+
+    def __len__(self):
+        return len(self.n_points)
+
+    def course(self, i):
+        """What BatchPlanner.path(i) returns -- (n, 2), or (n, 3) with the yaw column -- in this result's order, or None."""
+        if self.x is None:
+            raise ValueError("PlannerCourses.course: made with arrays='device', the points were not fetched")
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        if a == b:
+            return None
+        cols = [self.x[a:b], self.y[a:b]] + ([] if self.yaw is None else [self.yaw[a:b]])
+        return np.column_stack(cols)
+
+    def as_csr(self):
+        """(offsets, x, y): the waypoint form BatchSpline.run and BatchBSpline accept."""
+        if self.x is None:
+            raise ValueError("PlannerCourses.as_csr: made with arrays='device', the points were not fetched")
+        return self.offsets, self.x, self.y
 
 
 class BatchPlanner:
@@ -1031,12 +1083,44 @@ class BatchPlanner:
         h, j = self._loc(i)
         return h.get_rng_state(j)
 
+    def courses(self, which="planned", order="planning", arrays=True):
+        """Every course of the batch from one gather per handle on the device (rrtx_gather_courses): a PlannerCourses.
+        which: "planned" (what path(i) returns) or "smoothed" (what smooth() returned; after smooth()); order: "planning"
+        (goal -> start, as planning() returns it) or "driving" (the same rows reversed, what BatchTrack drives).
+        arrays="device": only the counts are fetched and the result carries device_courses for BatchTrack.run -- one
+        handle only, and only courses with a yaw in driving order (ValueError otherwise)."""
+        w = {"planned": _abi.COURSE_PLANNED, "smoothed": _abi.COURSE_SMOOTHED}.get(which)
+        o = {"planning": _abi.ORDER_PLANNING, "driving": _abi.ORDER_DRIVING}.get(order)
+        if w is None or o is None:
+            raise ValueError("BatchPlanner.courses: which is 'planned' or 'smoothed', order 'planning' or 'driving'")
+        device = _abi.on_device(arrays)
+        if device:
+            check_device_courses(len(self.handles), w == _abi.COURSE_PLANNED and self.algo == _abi.ALGO_RS, order)
+        elif arrays is not True:
+            raise ValueError("BatchPlanner.courses: arrays is True or 'device'")
+        offs, cols, ms, base = [np.zeros(1, dtype=np.int64)], [], 0.0, 0
+        for h in self.handles:
+            h.gather_courses(w, o)
+            off, n, has_yaw, kms = h.get_course_counts()
+            offs.append(off[1:] + base)
+            base += n
+            ms = max(ms, kms)
+            if not device:
+                cols.append(h.get_courses(n, has_yaw))
+        offsets = np.concatenate(offs)
+        if device:
+            return PlannerCourses(offsets, None, None, None, order, ms, _abi.DeviceCourses(_abi.SRC_PLANNER, self.handles[0]))
+        x, y = (np.concatenate([c[k] for c in cols]) for k in range(2))
+        yaw = None if cols[0][2] is None else np.concatenate([c[2] for c in cols])
+        return PlannerCourses(offsets, x, y, yaw, order, ms)
+
     def smooth(self, max_iter):
         """path_smoothing(path, max_iter, obstacle_list) (rrt_04:1447-1479) on every planned path, on the device, each
         instance continuing its own random stream (as the driver does at :1558-1559), against its own obstacle list."""
         for h in self.handles:
             h.smooth_planned(max_iter)
-        return [self._loc(i)[0].get_smoothed_path(self._loc(i)[1]) for i in range(len(self.seeds))]
+        c = self.courses("smoothed")
+        return [c.course(i) for i in range(len(self.seeds))]
 
     def track(self, **kw):
         """"closed_loop_rrt_star" only, after plan(): the closed-loop stage of rrt_10 (:1495-1582) on every planned tree, on
@@ -1086,14 +1170,15 @@ class BatchPlanner:
         `instance_obstacles`, each instance's list as `obstacles_k` ((m, 3): x, y, size)."""
         ids = list(range(len(self.seeds))) if instances is None else list(instances)
         pc, nn, st = self.results()
+        paths = self.courses()      # one gather per handle; the yaw column is not part of the file
         out = dict(seeds=np.array([self.seeds[i] for i in ids], dtype=np.int64), path_cost=pc[ids], n_nodes=nn[ids],
                    status=st[ids])
         for k, i in enumerate(ids):
             h, j = self._loc(i)
             x, y, cost, parent = h.get_tree(j)
-            p = h.get_path(j)
+            p = paths.course(i)
             out["x_%d" % k], out["y_%d" % k], out["cost_%d" % k], out["parent_%d" % k] = x, y, cost, parent
-            out["path_%d" % k] = np.zeros((0, 2)) if p is None else p
+            out["path_%d" % k] = np.zeros((0, 2)) if p is None else np.ascontiguousarray(p[:, :2])
             if self.closed_loop and self.tracked:
                 tr = h.get_track_arrays(j)
                 out["track_flag_%d" % k] = np.array(tr is not None)

@@ -38,6 +38,10 @@ def _csr(courses):
             raise ValueError("BatchTrack: an LQR SteerResult has no yaw, the tracker needs courses of (x, y, yaw)")
         if courses.offsets is None or courses.x is None:
             raise ValueError("BatchTrack: the SteerResult was solved with points=False, it holds no courses")
+        if courses.yaw is None:
+            raise ValueError("BatchTrack: these courses have no yaw, the tracker needs courses of (x, y, yaw)")
+        if getattr(courses, "order", "driving") != "driving":
+            raise ValueError("BatchTrack: the courses are in planning order, the tracker drives them: order='driving'")
         courses = (courses.offsets, courses.x, courses.y, courses.yaw)
     if isinstance(courses, tuple) and len(courses) == 4 and np.ndim(courses[0]) == 1 and np.ndim(courses[1]) == 1:
         off = np.ascontiguousarray(courses[0], dtype=np.int64)
@@ -251,6 +255,9 @@ class BatchTrack:
         course, or course_obstacles: one such list per course (at most 64 rows in a list).  robot_radius, target_speed,
         yaw_th, invalid_travel_ratio: a scalar or one value per course.  start_state: None, one (x, y, yaw, v) or one
         row per course.
+        courses may also be a PlannerCourses (BatchPlanner.courses(order="driving")): with host arrays it is tracked like
+        any CSR tuple (leave out the instances without a course yourself), with arrays="device" as below, where
+        select=courses.found leaves them out on the device.
         courses may also be a SteerResult, SplineResult or BSplineResult made with points="device" / arrays="device": the
         tracker then reads the points where the producer left them (a result whose producer has solved again since raises
         RrtxError).  For those alone: select -- None, "free" (the courses with hit == -1) or a boolean array; the others

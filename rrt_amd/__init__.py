@@ -43,6 +43,7 @@ LQRRRTStar = _pkg.LQRRRTStar
 ClosedLoopRRTStar = _pkg.ClosedLoopRRTStar
 informed_rotation = _pkg.informed_rotation
 BatchPlanner = _pkg.BatchPlanner
+PlannerCourses = _pkg.PlannerCourses
 BatchSteer = _pkg.BatchSteer
 SteerCandidates = _pkg.SteerCandidates
 BatchTrack = _pkg.BatchTrack
