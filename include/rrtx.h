@@ -32,7 +32,7 @@ extern "C" {
                                 rrtx_steer_get_control_points, rrtx_steer_solve_all, rrtx_steer_get_cand_counts,
                                 rrtx_steer_get_cand_summary, rrtx_steer_get_cand_points, rrtx_steer_select_free, rrtx_tracker_run_from,
                                 rrtx_tracker_get_winners, rrtx_tracker_get_goals, rrtx_*_get_generation, rrtx_gather_courses, rrtx_get_course_counts,
-                                rrtx_get_courses, rrtx_get_course_generation, RRTX_SRC_PLANNER); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
+                                rrtx_get_courses, rrtx_get_course_generation, RRTX_SRC_PLANNER, rrtx_query_goals and its getters); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
                                 rrtx_copy_results_device, per-instance yaw and informed rotation; 4: rrtx_plan_many,
                                 rrtx_selfcheck, rrtx_stats.main_shape / main_f32, rrtx_plan_begin / _step, rrtx_set_launch_bound,
                                 RRTX_ST_REF_HANGS, rrtx_rccl_* */
@@ -345,6 +345,44 @@ int rrtx_get_course_counts(rrtx_handle* h, int64_t* offsets, int64_t* n_points, 
  * NULL, and yaw must be NULL when the gather has no yaw column (RRTX_E_STATE otherwise). */
 int rrtx_get_courses(rrtx_handle* h, double* x, double* y, double* yaw, int64_t cap);
 int rrtx_get_course_generation(rrtx_handle* h, uint64_t* generation);
+
+/* ---- the best path to many goals from the planned trees (csrc/goal_query.hip.h, csrc/rpp_goalq.h) ----------------------
+ * After a plan every node of a tree carries the cost of the best known route from the instance's start.  rrtx_query_goals
+ * asks every instance's finished tree for the path to n_goals goals: for instance i and goal g the answer is what the tail
+ * of the reference's planning() computes on that tree with self.end (rrt_04: and self.goal_node) replaced by g --
+ *   RRTX_ALGO_RRT_STAR         search_best_goal_node rrt_04:1284-1312 + generate_final_course :1117-1125; node 0 can answer
+ *   RRTX_ALGO_DUBINS / _RS     search_best_goal_node rrt_05:1691-1712 / rrt_06:1815-1836 with `if last_index:` (node 0 is
+ *                              no answer) + generate_final_course rrt_05:1512-1521 / rrt_06:1643-1651 (RS: a yaw column)
+ * bit for bit.  Nothing of the plan changes: tree, RNG state, goal, path, results and the gathered courses of
+ * rrtx_gather_courses stay what they are.  Every other algo (RRTX_ALGO_RS with RRTX_RS_COST_PATH, rrt_10, included: its
+ * goal rule is get_goal_indexes): RRTX_E_INVALID.
+ * goals: rows (x, y, yaw), n_goals of them shared by all instances (per_instance = 0) or n_instances * n_goals, instance
+ * major (per_instance = 1); any double is accepted (NaN and +-inf find nothing).  xy_th / yaw_th: the pose planners'
+ * goal_xy_th / goal_yaw_th for this call; NaN = the handle's own.  Queries are (instance, goal) pairs in row-major order.
+ * Returns RRTX_OK, or RRTX_PARTIAL when a query has RRTX_GOALQ_OVERFLOW (more than 512 distinct candidates inside
+ * expand_dis of the goal: that query has no node, every other query is answered).  Checked before any HIP call:
+ * RRTX_E_INVALID for a NULL handle / goals, an unserved algo, n_goals < 1, per_instance not 0 / 1, more than
+ * RRTX_GOALQ_MAX_QUERIES queries; RRTX_E_STATE without a completed plan or while one is in progress.  A new plan drops the
+ * answers: the getters return RRTX_E_STATE, rrtx_gather_goal_courses RRTX_E_INVALID, until the next query. */
+#define RRTX_GOALQ_OK 0        /* node >= 0, cost = the answer's key */
+#define RRTX_GOALQ_NONE 1      /* the reference finds no path to this goal on this tree */
+#define RRTX_GOALQ_NO_TREE 2   /* the instance is not RRTX_ST_DONE or carries RRTX_ST_OVERFLOW / _UNSUPPORTED / _REF_RAISES */
+#define RRTX_GOALQ_OVERFLOW 3
+#define RRTX_GOALQ_MAX_QUERIES (1 << 24)
+int rrtx_query_goals(rrtx_handle* h, int32_t n_goals, int32_t per_instance, const double* goals, double xy_th, double yaw_th);
+/* The records of the last query, n_instances * n_goals of each: the answer node (-1 none), its cost (rrt_04: cost +
+ * distance to the goal; +inf without a node), the number of distinct candidates, of safe ones (rrt_04; else 0), the status.
+ * Any pointer may be NULL; with all five NULL only *n_queries is written.  cap = entries available in each. */
+int rrtx_get_goal_query(rrtx_handle* h, int32_t* node, double* cost, int32_t* n_near, int32_t* n_safe, int32_t* status,
+                        int64_t cap, int64_t* n_queries);
+/* The courses of the last query as one CSR result over the queries, in RRTX_ORDER_PLANNING (goal -> start) or _DRIVING:
+ * count, the host's exclusive sum, gather -- the pattern and the limits of rrtx_gather_courses, in buffers of their own. */
+int rrtx_gather_goal_courses(rrtx_handle* h, int32_t order);
+/* offsets: n_instances * n_goals + 1 entries */
+int rrtx_get_goal_course_counts(rrtx_handle* h, int64_t* offsets, int64_t* n_points, int32_t* has_yaw);
+int rrtx_get_goal_courses(rrtx_handle* h, double* x, double* y, double* yaw, int64_t cap);
+/* HIP-event time of the last query's solve launch and of its last gather's two launches (0 without a gather) */
+int rrtx_get_goal_query_kernel_ms(rrtx_handle* h, double* solve_ms, double* gather_ms);
 
 /* ---- closed-loop RRT* (rrt_10 = 10_path_planning_01_rrt_10_closed_loop_rrt_star.py) -----------------------------------
  * Tree phase: RRTX_ALGO_RS with expand_dis = +inf (rrt_10's class has no expand_dis attribute, so find_near_nodes

@@ -42,6 +42,8 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_tracker_run_from", "rrtx_tracker_get_winners", "rrtx_tracker_get_goals", "rrtx_steer_get_generation",
            "rrtx_spline_get_generation", "rrtx_bspline_get_generation",
            "rrtx_gather_courses", "rrtx_get_course_counts", "rrtx_get_courses", "rrtx_get_course_generation",
+           "rrtx_query_goals", "rrtx_get_goal_query", "rrtx_gather_goal_courses", "rrtx_get_goal_course_counts",
+           "rrtx_get_goal_courses", "rrtx_get_goal_query_kernel_ms",
            "rrtx_spline_create", "rrtx_spline_destroy", "rrtx_spline_last_error", "rrtx_spline_run", "rrtx_spline_get_records",
            "rrtx_spline_get_points", "rrtx_spline_get_c", "rrtx_spline_get_hits",
            "rrtx_spline_fit1d", "rrtx_spline_query", "rrtx_spline_get_query", "rrtx_spline_get_query_info",
@@ -68,7 +70,9 @@ OOD_DOMAIN, OOD_RAISES, OOD_OVERFLOW, OOD_NOT_FINITE, OOD_SKIPPED = 1, 2, 3, 4, 
 SRC_STEER, SRC_SPLINE, SRC_BSPLINE, SRC_PLANNER = 1, 2, 3, 4                             # #define RRTX_SRC_*
 COURSE_PLANNED, COURSE_SMOOTHED = 0, 1                                                   # #define RRTX_COURSE_*
 ORDER_PLANNING, ORDER_DRIVING = 0, 1                                                     # #define RRTX_ORDER_*
-SELECT_ALL, SELECT_FREE, SELECT_MASK = 0, 1, 2                                           # #define RRTX_SELECT_*
+GOALQ_OK, GOALQ_NONE, GOALQ_NO_TREE, GOALQ_OVERFLOW = 0, 1, 2, 3                           # #define RRTX_GOALQ_*
+GOALQ_MAX_QUERIES, GOALQ_MAX_CANDIDATES = 1 << 24, 512                                   # the second: csrc NU_MAX
+SELECT_ALL, SELECT_FREE, SELECT_MASK = 0, 1, 2                                          # #define RRTX_SELECT_*
 SPLINE_OK, SPLINE_DEGENERATE, SPLINE_REF_RAISES = 0, 1, 2                                # #define RRTX_SPLINE_*
 SPLINE_MAX_WAYPOINTS, SPLINE_MAX_POINTS = 4096, 1 << 28
 SPLINE_Q_OK, SPLINE_Q_OUTSIDE, SPLINE_Q_REF_RAISES, SPLINE_Q_NO_SPLINE = 0, 1, 2, 3        # #define RRTX_SPLINE_Q_*
@@ -323,6 +327,12 @@ def load():
     L.rrtx_get_course_counts.argtypes = [vp, vp, i64p, C.POINTER(i32), C.POINTER(C.c_double)]
     L.rrtx_get_courses.argtypes = [vp, vp, vp, vp, C.c_int64]
     L.rrtx_get_course_generation.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.rrtx_query_goals.argtypes = [vp, i32, i32, vp, C.c_double, C.c_double]
+    L.rrtx_get_goal_query.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, i64p]
+    L.rrtx_gather_goal_courses.argtypes = [vp, i32]
+    L.rrtx_get_goal_course_counts.argtypes = [vp, vp, i64p, C.POINTER(i32)]
+    L.rrtx_get_goal_courses.argtypes = [vp, vp, vp, vp, C.c_int64]
+    L.rrtx_get_goal_query_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.rrtx_spline_create.argtypes = [i32, C.POINTER(vp)]
     L.rrtx_spline_destroy.argtypes = [vp]
     L.rrtx_spline_destroy.restype = None
@@ -767,6 +777,47 @@ class Handle:
         self._chk(self.L.rrtx_get_courses(self._h, x.ctypes.data, y.ctypes.data, None if yaw is None else yaw.ctypes.data,
                                           n_points), "rrtx_get_courses")
         return x, y, yaw
+
+    # ---- the best path to many goals from the planned trees (rrtx_query_goals)
+    def query_goals(self, goals, per_instance, xy_th=None, yaw_th=None):
+        """goals: (g, 3) shared, or (n_instances, g, 3) with per_instance; thresholds None = the handle's own.  Returns
+        (rc, n_goals): rc 0 or RRTX_PARTIAL (a query with GOALQ_OVERFLOW)."""
+        g = np.ascontiguousarray(goals, dtype=np.float64)
+        n_goals = g.shape[-2]
+        nan = float("nan")
+        rc = self.L.rrtx_query_goals(self._h, int(n_goals), 1 if per_instance else 0, g.ctypes.data,
+                                     nan if xy_th is None else float(xy_th), nan if yaw_th is None else float(yaw_th))
+        self._chk(rc, "rrtx_query_goals")
+        return rc, n_goals
+
+    def get_goal_query(self, n_goals):
+        """(node, cost, n_near, n_safe, status) of the last query, each (n_instances, n_goals)."""
+        nq = self.n_instances * int(n_goals)
+        node, near, safe, st = (np.zeros(nq, dtype=np.int32) for _ in range(4))
+        cost, n = np.zeros(nq), C.c_int64()
+        self._chk(self.L.rrtx_get_goal_query(self._h, node.ctypes.data, cost.ctypes.data, near.ctypes.data, safe.ctypes.data,
+                                             st.ctypes.data, nq, C.byref(n)), "rrtx_get_goal_query")
+        return tuple(a.reshape(self.n_instances, int(n_goals)) for a in (node, cost, near, safe, st))
+
+    def gather_goal_courses(self, order=ORDER_PLANNING):
+        self._chk(self.L.rrtx_gather_goal_courses(self._h, int(order)), "rrtx_gather_goal_courses")
+
+    def get_goal_courses(self, n_goals):
+        """(offsets (n_instances * n_goals + 1,), x, y, yaw or None) of the last gather."""
+        off = np.zeros(self.n_instances * int(n_goals) + 1, dtype=np.int64)
+        n, hy = C.c_int64(), C.c_int32()
+        self._chk(self.L.rrtx_get_goal_course_counts(self._h, off.ctypes.data, C.byref(n), C.byref(hy)),
+                  "rrtx_get_goal_course_counts")
+        x, y = np.zeros(n.value), np.zeros(n.value)
+        yaw = np.zeros(n.value) if hy.value else None
+        self._chk(self.L.rrtx_get_goal_courses(self._h, x.ctypes.data, y.ctypes.data, None if yaw is None else yaw.ctypes.data,
+                                               n.value), "rrtx_get_goal_courses")
+        return off, x, y, yaw
+
+    def get_goal_query_kernel_ms(self):
+        s, g = C.c_double(), C.c_double()
+        self._chk(self.L.rrtx_get_goal_query_kernel_ms(self._h, C.byref(s), C.byref(g)), "rrtx_get_goal_query_kernel_ms")
+        return s.value, g.value
 
     def get_stats(self):
         s = Stats()

@@ -80,6 +80,25 @@ __global__ __launch_bounds__(256) void course_count_kernel(GatherArgs a) {
   a.count[i] = (int32_t)(n > 0x7fffffffLL ? 0x7fffffffLL : n);
 }
 
+// One pose course by one wave: the two end rows, then the chain from `goal_node` in rounds of ROUND nodes listed through
+// `round` (LDS) and copied with all lanes.  Block-uniform arguments.
+__device__ inline void pose_course(const Chain& c, const double* const* src, double* const* dst, int ncol, int order,
+                                   int64_t total, const double* goal, const double* start, int32_t goal_node, Round& round,
+                                   int lane) {
+  if (lane == 0) pose_ends(goal, start, dst, ncol, order, total);
+  int32_t nd = goal_node;
+  int64_t k = 1, steps = 0;
+  while (nd >= 0) {   // block-uniform: every lane reads the same round
+    if (lane == 0) pose_round_fill(c, nd, k, steps, round);
+    __syncthreads();
+    pose_round_copy(round, src, dst, ncol, order, total, lane, TPB);
+    nd = round.next;
+    k = round.k_next;
+    steps = round.steps;
+    __syncthreads();   // the next fill overwrites the round
+  }
+}
+
 __global__ __launch_bounds__(TPB) void course_gather_kernel(GatherArgs a) {
   __shared__ Round round;
   const int i = blockIdx.x, lane = threadIdx.x;
@@ -103,18 +122,7 @@ __global__ __launch_bounds__(TPB) void course_gather_kernel(GatherArgs a) {
   const Chain c = chain_of(a, i);
   const double* src[3] = {a.pool[3 * i], a.pool[3 * i + 1], a.pool[3 * i + 2]};
   double* dst[3] = {a.ox + o, a.oy + o, a.ncol == 3 ? a.oyaw + o : nullptr};
-  if (lane == 0) pose_ends(a.inst[i].goal, a.inst[i].start, dst, a.ncol, a.order, total);
-  int32_t nd = a.inst[i].goal_node;
-  int64_t k = 1, steps = 0;
-  while (nd >= 0) {   // block-uniform: every lane reads the same round
-    if (lane == 0) pose_round_fill(c, nd, k, steps, round);
-    __syncthreads();
-    pose_round_copy(round, src, dst, a.ncol, a.order, total, lane, TPB);
-    nd = round.next;
-    k = round.k_next;
-    steps = round.steps;
-    __syncthreads();   // the next fill overwrites the round
-  }
+  pose_course(c, src, dst, a.ncol, a.order, total, a.inst[i].goal, a.inst[i].start, a.inst[i].goal_node, round, lane);
 }
 
 }  // namespace rppc

@@ -25,6 +25,7 @@
 #include "rrt_lqr.hip.h"
 #include "rrt_track.hip.h"
 #include "course_gather.hip.h"
+#include "goal_query.hip.h"
 #include "steer_batch.hip.h"
 #include "spline_batch.hip.h"
 #include "bspline_batch.hip.h"
@@ -143,6 +144,19 @@ struct rrtx_handle : DevObj {
     std::vector<int64_t> h_off;
     double kernel_ms = 0.0;
   } cs;
+  // the last rrtx_query_goals on the current plan and the courses gathered from it (goal_query.hip.h): buffers of their
+  // own, so that the gathered courses of rrtx_gather_courses stay what they are; they grow and never shrink
+  struct GoalQ {
+    DevBuf goals, rec, scratch, count, off, x, y, yaw, pool;
+    bool valid = false, gathered = false, has_yaw = false;
+    int n_goals = 0, per_instance = 0, order = 0;
+    double xy_th = 0.0, yaw_th = 0.0;
+    int64_t n_points = 0;
+    uint64_t generation = 0;   // completed queries so far
+    std::vector<rppq::Record> h_rec;
+    std::vector<int64_t> h_off;
+    double solve_ms = 0.0, gather_ms = 0.0;
+  } gq;
 };
 
 template <class T>
@@ -765,6 +779,7 @@ int rrtx_plan_begin(rrtx_handle* h) {
   h->smoothed = false;     // rrtx_get_smoothed_path: the previous plan's smoothed paths are not this plan's
   h->tk.valid = false;     // the same for the tracked trajectories
   h->cs.valid = false;     // and for the gathered courses (rrtx_gather_courses)
+  h->gq.valid = false;     // and for the goal queries asked of the previous plan's trees (rrtx_query_goals)
   h->traced_inst = -1;     // rrtx_get_trace: nothing recorded until this plan completes
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipDeviceSynchronize());   // uploads made through the null stream (obstacles, tables) are complete
@@ -1791,6 +1806,7 @@ int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps) {
 #include "rrtx_api_spline.inc"
 #include "rrtx_api_bspline.inc"
 #include "rrtx_api_courses.inc"
+#include "rrtx_api_goalq.inc"
 #include "rrtx_api_tracker.inc"   // after the four producers: rrtx_tracker_run_from reads their objects
 #include "rrtx_api_armnav.inc"
 #include "rrtx_api_armik.inc"

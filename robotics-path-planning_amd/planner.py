@@ -909,6 +909,75 @@ class PlannerCourses:
         return self.offsets, self.x, self.y
 
 
+GOAL_QUERY_ALGOS = ("rrt_star", "rrt_star_dubins", "rrt_star_reeds_shepp")
+
+
+def goal_query_table(goals, n, pose, goal_yaw):
+    """The (g, 3) or (n, g, 3) table of rows (x, y, yaw) rrtx_query_goals reads, from `goals` of shape (g, 2 | 3) or
+    (n, g, 2 | 3); a missing yaw column is `goal_yaw`.  Returns (table, per_instance)."""
+    g = np.asarray(goals, dtype=np.float64)
+    if g.ndim not in (2, 3) or g.shape[-1] not in (2, 3) or g.shape[-2] < 1:
+        raise ValueError("BatchPlanner.query_goals: goals has shape (g, 2 | 3) or (n, g, 2 | 3) with g >= 1, got %r"
+                         % (g.shape,))
+    if g.ndim == 3 and g.shape[0] != n:
+        raise ValueError("BatchPlanner.query_goals: per-instance goals for %d instances, the batch has %d" % (g.shape[0], n))
+    if g.shape[-1] == 3 and not pose:
+        raise ValueError("BatchPlanner.query_goals: 'rrt_star' goals are (x, y)")
+    if n * g.shape[-2] > _abi.GOALQ_MAX_QUERIES:
+        raise ValueError("BatchPlanner.query_goals: more than %d queries (instances x goals)" % _abi.GOALQ_MAX_QUERIES)
+    t = np.empty(g.shape[:-1] + (3,), dtype=np.float64)
+    t[..., :g.shape[-1]] = g
+    if g.shape[-1] == 2:
+        t[..., 2] = float(goal_yaw) if pose else 0.0
+    return np.ascontiguousarray(t), g.ndim == 3
+
+
+class GoalQueryResult:
+    """What BatchPlanner.query_goals returns: for instance i and goal j the best path from i's start to goal j that i's
+    planned tree holds.  node, cost, n_near, n_safe, status and found are (n, g): the answer node (-1 none), its cost
+    ("rrt_star": node cost + distance to the goal; +inf without a node), the number of distinct candidates, of safe ones
+    ("rrt_star" only, else 0), _abi.GOALQ_* and status == GOALQ_OK.  With paths, the courses are one CSR result over the
+    n * g queries in row-major order: query i * g + j owns rows offsets[q] .. offsets[q + 1] - 1 of the flat x, y and yaw
+    (yaw None unless the planner is "rrt_star_reeds_shepp"), in `order`; without, offsets, x, y and yaw are None.
+    kernel_ms: HIP-event time of the solve and gather launches (sharded planners: the slowest handle's)."""
+
+    def __init__(self, node, cost, n_near, n_safe, status, offsets=None, x=None, y=None, yaw=None, order="planning",
+                 kernel_ms=0.0):
+        self.node, self.cost, self.n_near, self.n_safe, self.status = node, cost, n_near, n_safe, status
+        self.found = status == _abi.GOALQ_OK
+        self.partial = bool(np.any(status == _abi.GOALQ_OVERFLOW))   # rrtx_query_goals returned RRTX_PARTIAL
+        self.offsets = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        self.x, self.y, self.yaw = x, y, yaw
+        self.order = order
+        self.kernel_ms = kernel_ms
+
+    @property
+    def shape(self):
+        return self.node.shape
+
+    def _need_paths(self, who):
+        if self.offsets is None:
+            raise ValueError("GoalQueryResult.%s: made with paths=False, the courses were not gathered" % who)
+
+    def course(self, i, j):
+        """The course to goal j on instance i's tree, shaped as BatchPlanner.path(i) is, in this result's order, or None."""
+        self._need_paths("course")
+        n, g = self.node.shape
+        if not (-n <= i < n and -g <= j < g):
+            raise IndexError((i, j))
+        q = (i % n) * g + (j % g)
+        a, b = int(self.offsets[q]), int(self.offsets[q + 1])
+        if a == b:
+            return None
+        cols = [self.x[a:b], self.y[a:b]] + ([] if self.yaw is None else [self.yaw[a:b]])
+        return np.column_stack(cols)
+
+    def as_csr(self):
+        """(offsets, x, y) over the n * g queries: the waypoint form BatchSpline.run and BatchBSpline accept."""
+        self._need_paths("as_csr")
+        return self.offsets, self.x, self.y
+
+
 class BatchPlanner:
     """Many independent planning instances (seeds / start-goal pairs) on one GPU or sharded over several.
 
@@ -1113,6 +1182,42 @@ class BatchPlanner:
         x, y = (np.concatenate([c[k] for c in cols]) for k in range(2))
         yaw = None if cols[0][2] is None else np.concatenate([c[2] for c in cols])
         return PlannerCourses(offsets, x, y, yaw, order, ms)
+
+    def query_goals(self, goals, goal_xy_th=None, goal_yaw_th=None, paths=True, order="planning"):
+        """After plan(): the best path from every instance's start to MANY goals, read off the planned trees on the device
+        (rrtx_query_goals) -- for instance i and goal g what the tail of the reference's planning() returns on i's
+        finished node_list with `end` (rrt_04: and `goal_node`) set to g.  Nothing of the plan changes.
+        goals: (g, 2 | 3) shared by all instances, or (n, g, 2 | 3); a missing yaw is the planner's goal yaw.
+        goal_xy_th / goal_yaw_th: the pose planners' thresholds for this call (default: the planner's).  paths=False:
+        only the records, no gather.  order: "planning" (goal -> start) or "driving".  Returns a GoalQueryResult; a query
+        with more than _abi.GOALQ_MAX_CANDIDATES distinct candidates has status GOALQ_OVERFLOW and no node (the
+        result's `partial` is then True).  Served for "rrt_star", "rrt_star_dubins" and "rrt_star_reeds_shepp" (ValueError otherwise)."""
+        if self.algo not in (_abi.ALGO_RRT_STAR, _abi.ALGO_DUBINS, _abi.ALGO_RS) or getattr(self, "closed_loop", False):
+            raise ValueError("BatchPlanner.query_goals: served for %s only (every other planner has another goal rule)"
+                             % ", ".join(repr(a) for a in GOAL_QUERY_ALGOS))
+        o = {"planning": _abi.ORDER_PLANNING, "driving": _abi.ORDER_DRIVING}.get(order)
+        if o is None:
+            raise ValueError("BatchPlanner.query_goals: order is 'planning' or 'driving'")
+        n = len(self.seeds)
+        pose = self.algo != _abi.ALGO_RRT_STAR
+        table, per_instance = goal_query_table(goals, n, pose, self.handles[0].params.goal[2] if pose else 0.0)
+        recs, offs, cols, ms, base = [], [np.zeros(1, dtype=np.int64)], [], 0.0, 0
+        for h, (lo, hi) in zip(self.handles, self.shards):
+            rc, g = h.query_goals(table[lo:hi] if per_instance else table, per_instance, goal_xy_th, goal_yaw_th)
+            recs.append(h.get_goal_query(g))
+            if paths:
+                h.gather_goal_courses(o)
+                off, x, y, yaw = h.get_goal_courses(g)
+                offs.append(off[1:] + base)
+                base += int(off[-1])
+                cols.append((x, y, yaw))
+            ms = max(ms, sum(h.get_goal_query_kernel_ms()))
+        node, cost, near, safe, st = (np.concatenate([r[k] for r in recs]) for k in range(5))
+        if not paths:
+            return GoalQueryResult(node, cost, near, safe, st, order=order, kernel_ms=ms)
+        x, y = (np.concatenate([c[k] for c in cols]) for k in range(2))
+        yaw = None if cols[0][2] is None else np.concatenate([c[2] for c in cols])
+        return GoalQueryResult(node, cost, near, safe, st, np.concatenate(offs), x, y, yaw, order, ms)
 
     def smooth(self, max_iter):
         """path_smoothing(path, max_iter, obstacle_list) (rrt_04:1447-1479) on every planned path, on the device, each

@@ -44,6 +44,7 @@ ClosedLoopRRTStar = _pkg.ClosedLoopRRTStar
 informed_rotation = _pkg.informed_rotation
 BatchPlanner = _pkg.BatchPlanner
 PlannerCourses = _pkg.PlannerCourses
+GoalQueryResult = _pkg.GoalQueryResult
 BatchSteer = _pkg.BatchSteer
 SteerCandidates = _pkg.SteerCandidates
 BatchTrack = _pkg.BatchTrack
