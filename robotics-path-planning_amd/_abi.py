@@ -219,6 +219,10 @@ class Stats(C.Structure):
                 ("main_shape", C.c_int32), ("main_f32", C.c_int32), ("passes_shared", C.c_int64)]
 
 
+# the C prefixes of the device objects besides the planner handle: rrtx_<prefix>_create / _destroy / _last_error
+DEVICE_OBJECTS = ("steer", "tracker", "spline", "bspline", "armnav", "armik", "armdh")
+
+
 class RrtxError(RuntimeError):
     pass
 
@@ -284,11 +288,6 @@ def load():
     L.rrtx_rccl_unique_id.argtypes = [vp]
     L.rrtx_rccl_init.argtypes = [vp, vp, i32, i32]
     L.rrtx_rccl_gather_results.argtypes = [vp, vp, vp, vp]
-    L.rrtx_steer_create.argtypes = [i32, C.POINTER(vp)]
-    L.rrtx_steer_destroy.argtypes = [vp]
-    L.rrtx_steer_destroy.restype = None
-    L.rrtx_steer_last_error.argtypes = [vp]
-    L.rrtx_steer_last_error.restype = C.c_char_p
     L.rrtx_steer_solve.argtypes = [vp, i32, i32, C.c_int64, C.c_int64, vp, vp, vp, i32, C.c_double, vp, i32, i32]
     L.rrtx_steer_get_counts.argtypes = [vp, i64p, i64p]
     L.rrtx_steer_get_summary.argtypes = [vp, vp, vp, vp, vp, vp, vp]
@@ -308,11 +307,6 @@ def load():
     L.rrtx_steer_get_cand_summary.argtypes = [vp] * 12
     L.rrtx_steer_get_cand_points.argtypes = [vp, vp, vp, vp, vp, C.c_int64]
     L.rrtx_steer_select_free.argtypes = [vp, vp, vp, vp]
-    L.rrtx_tracker_create.argtypes = [i32, C.POINTER(vp)]
-    L.rrtx_tracker_destroy.argtypes = [vp]
-    L.rrtx_tracker_destroy.restype = None
-    L.rrtx_tracker_last_error.argtypes = [vp]
-    L.rrtx_tracker_last_error.restype = C.c_char_p
     L.rrtx_tracker_run.argtypes = [vp, C.POINTER(TrackParams), C.POINTER(TrackBatch)]
     L.rrtx_tracker_get_counts.argtypes = [vp, i64p, i64p]
     L.rrtx_tracker_get_records.argtypes = [vp, vp, vp]
@@ -321,8 +315,6 @@ def load():
     L.rrtx_tracker_run_from.argtypes = [vp, C.POINTER(TrackParams), C.POINTER(TrackSource), C.POINTER(TrackBatch)]
     L.rrtx_tracker_get_winners.argtypes = [vp, vp, i64p]
     L.rrtx_tracker_get_goals.argtypes = [vp, vp]
-    for obj in ("steer", "spline", "bspline"):
-        getattr(L, "rrtx_%s_get_generation" % obj).argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rrtx_gather_courses.argtypes = [vp, i32, i32]
     L.rrtx_get_course_counts.argtypes = [vp, vp, i64p, C.POINTER(i32), C.POINTER(C.c_double)]
     L.rrtx_get_courses.argtypes = [vp, vp, vp, vp, C.c_int64]
@@ -333,11 +325,6 @@ def load():
     L.rrtx_get_goal_course_counts.argtypes = [vp, vp, i64p, C.POINTER(i32)]
     L.rrtx_get_goal_courses.argtypes = [vp, vp, vp, vp, C.c_int64]
     L.rrtx_get_goal_query_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.rrtx_spline_create.argtypes = [i32, C.POINTER(vp)]
-    L.rrtx_spline_destroy.argtypes = [vp]
-    L.rrtx_spline_destroy.restype = None
-    L.rrtx_spline_last_error.argtypes = [vp]
-    L.rrtx_spline_last_error.restype = C.c_char_p
     L.rrtx_spline_run.argtypes = [vp, C.POINTER(SplineBatch)]
     L.rrtx_spline_get_records.argtypes = [vp, vp, vp, i64p, i64p, C.POINTER(C.c_double)]
     L.rrtx_spline_get_points.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64]
@@ -347,11 +334,6 @@ def load():
     L.rrtx_spline_query.argtypes = [vp, C.POINTER(SplineQueryBatch)]
     L.rrtx_spline_get_query.argtypes = [vp] + [vp] * 8 + [vp, C.c_int64]
     L.rrtx_spline_get_query_info.argtypes = [vp, i64p, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_double)]
-    L.rrtx_bspline_create.argtypes = [i32, C.POINTER(vp)]
-    L.rrtx_bspline_destroy.argtypes = [vp]
-    L.rrtx_bspline_destroy.restype = None
-    L.rrtx_bspline_last_error.argtypes = [vp]
-    L.rrtx_bspline_last_error.restype = C.c_char_p
     L.rrtx_bspline_run.argtypes = [vp, C.POINTER(BSplineBatch)]
     L.rrtx_bspline_get_records.argtypes = [vp, vp, vp, i64p, i64p, i64p]
     L.rrtx_bspline_get_points.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64]
@@ -361,11 +343,6 @@ def load():
     L.rrtx_bspline_approximate.argtypes = [vp, C.POINTER(BSplineSmoothBatch)]
     L.rrtx_bspline_get_axis_records.argtypes = [vp, vp, C.c_int64]
     L.rrtx_bspline_get_axis_splines.argtypes = [vp, i32, vp, vp, C.c_int64, vp, vp, C.c_int64, i64p, i64p]
-    L.rrtx_armnav_create.argtypes = [i32, C.POINTER(vp)]
-    L.rrtx_armnav_destroy.argtypes = [vp]
-    L.rrtx_armnav_destroy.restype = None
-    L.rrtx_armnav_last_error.argtypes = [vp]
-    L.rrtx_armnav_last_error.restype = C.c_char_p
     L.rrtx_armnav_occupancy.argtypes = [vp, i32, C.c_int64, vp, vp, vp, vp]
     L.rrtx_armnav_set_grids.argtypes = [vp, i32, C.c_int64, vp]
     L.rrtx_armnav_get_grids.argtypes = [vp, vp, C.c_int64]
@@ -374,22 +351,12 @@ def load():
     L.rrtx_armnav_get_routes.argtypes = [vp, vp, vp, C.c_int64]
     L.rrtx_armnav_get_marks.argtypes = [vp, vp, C.c_int64]
     L.rrtx_armnav_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.rrtx_armik_create.argtypes = [i32, C.POINTER(vp)]
-    L.rrtx_armik_destroy.argtypes = [vp]
-    L.rrtx_armik_destroy.restype = None
-    L.rrtx_armik_last_error.argtypes = [vp]
-    L.rrtx_armik_last_error.restype = C.c_char_p
     L.rrtx_armik_solve.argtypes = [vp, C.POINTER(ArmIKBatch), i32, i32]
     L.rrtx_armik_move.argtypes = [vp, C.POINTER(ArmIKBatch), C.c_double, C.c_double, i32, i32]
     L.rrtx_armik_get_records.argtypes = [vp, vp, vp, vp, vp, i64p, i64p]
     L.rrtx_armik_get_angles.argtypes = [vp, vp, vp, C.c_int64]
     L.rrtx_armik_get_trajectory.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int64]
     L.rrtx_armik_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i32)]
-    L.rrtx_armdh_create.argtypes = [i32, C.POINTER(vp)]
-    L.rrtx_armdh_destroy.argtypes = [vp]
-    L.rrtx_armdh_destroy.restype = None
-    L.rrtx_armdh_last_error.argtypes = [vp]
-    L.rrtx_armdh_last_error.restype = C.c_char_p
     L.rrtx_armdh_forward.argtypes = [vp, C.POINTER(ArmDHBatch)]
     L.rrtx_armdh_solve.argtypes = [vp, C.POINTER(ArmDHBatch), i32, C.c_double, i32, C.c_double]
     L.rrtx_armdh_get_records.argtypes = [vp, vp, vp, vp, vp, i64p, i64p]
@@ -397,11 +364,19 @@ def load():
     L.rrtx_armdh_get_transforms.argtypes = [vp, vp, C.c_int64]
     L.rrtx_armdh_get_jacobians.argtypes = [vp, vp, C.c_int64]
     L.rrtx_armdh_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i32)]
+    not_int = {"rrtx_destroy", "rrtx_last_error", "rrtx_abi_version", "rrtx_device_count"}   # the last two are set above
+    for obj in DEVICE_OBJECTS:
+        create, destroy, last_error, get_generation = ("rrtx_%s_%s" % (obj, f) for f in ("create", "destroy", "last_error", "get_generation"))
+        getattr(L, create).argtypes = [i32, C.POINTER(vp)]
+        getattr(L, destroy).argtypes = [vp]
+        getattr(L, destroy).restype = None
+        getattr(L, last_error).argtypes = [vp]
+        getattr(L, last_error).restype = C.c_char_p
+        not_int |= {destroy, last_error}
+        if get_generation in EXPORTS:
+            getattr(L, get_generation).argtypes = [vp, C.POINTER(C.c_uint64)]
     for f in EXPORTS:
-        if f not in ("rrtx_armdh_destroy", "rrtx_armdh_last_error", "rrtx_armik_destroy", "rrtx_armik_last_error", "rrtx_last_error", "rrtx_destroy", "rrtx_abi_version", "rrtx_device_count", "rrtx_steer_destroy",
-                     "rrtx_steer_last_error", "rrtx_tracker_destroy", "rrtx_tracker_last_error", "rrtx_spline_destroy",
-                     "rrtx_spline_last_error", "rrtx_armnav_destroy", "rrtx_armnav_last_error", "rrtx_bspline_destroy",
-                     "rrtx_bspline_last_error"):
+        if f not in not_int:
             getattr(L, f).restype = C.c_int
     if L.rrtx_abi_version() != RRTX_ABI_VERSION:
         raise RrtxError("librrtx.so ABI version mismatch")
@@ -854,24 +829,27 @@ class Handle:
         return out
 
 
-class Steer:
-    """Thin RAII wrapper over rrtx_steer* (batched Dubins / Reeds-Shepp curves between pose pairs, LQR rollouts between
-    point pairs); also a context manager.  It owns the device buffers of its solves, so repeated solves of any kind
-    reuse them."""
+class _DevObject:
+    """What the wrappers of the device objects besides the planner handle share: the native pointer self._s, created by
+    rrtx_<_prefix>_create and destroyed by close(), and the check that turns a negative return code into an RrtxError with
+    the object's last message.  Also a context manager."""
+    _prefix = None   # the C prefix: "steer" for rrtx_steer_*
 
     def __init__(self, device=0):
         self.L = load()
         self._s = C.c_void_p()
-        self.n_obstacles = 0
-        rc = self.L.rrtx_steer_create(int(device), C.byref(self._s))
+        rc = self._fn("create")(int(device), C.byref(self._s))
         if rc != 0:
-            msg = self.L.rrtx_steer_last_error(self._s).decode()
+            msg = self._fn("last_error")(self._s).decode()
             self.close()
-            raise RrtxError("rrtx_steer_create: %s %s" % (ERRORS.get(rc, rc), msg))
+            raise RrtxError("rrtx_%s_create: %s %s" % (self._prefix, ERRORS.get(rc, rc), msg))
+
+    def _fn(self, name):
+        return getattr(self.L, "rrtx_%s_%s" % (self._prefix, name))
 
     def close(self):
         if getattr(self, "_s", None):
-            self.L.rrtx_steer_destroy(self._s)
+            self._fn("destroy")(self._s)
             self._s = C.c_void_p()
 
     def __enter__(self):
@@ -889,8 +867,20 @@ class Steer:
 
     def _chk(self, rc, what):
         if rc < 0:
-            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_steer_last_error(self._s).decode()))
+            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self._fn("last_error")(self._s).decode()))
         return rc
+
+
+class Steer(_DevObject):
+    """Thin RAII wrapper over rrtx_steer* (batched Dubins / Reeds-Shepp curves between pose pairs, LQR rollouts between
+    point pairs); also a context manager.  It owns the device buffers of its solves, so repeated solves of any kind
+    reuse them."""
+
+    _prefix = "steer"
+
+    def __init__(self, device=0):
+        self.n_obstacles = 0
+        super().__init__(device)
 
     def generation(self):
         """Completed solves of this object so far: what a DeviceCourses of its last solve carries."""
@@ -1084,68 +1074,38 @@ class Steer:
         return ms.value
 
 
-class Tracker:
+class Tracker(_DevObject):
     """Thin RAII wrapper over rrtx_tracker* (batched closed-loop tracking of courses given as data); also a context
     manager.  It owns the device buffers of its runs, so repeated runs reuse them."""
 
-    def __init__(self, device=0):
-        self.L = load()
-        self._t = C.c_void_p()
-        rc = self.L.rrtx_tracker_create(int(device), C.byref(self._t))
-        if rc != 0:
-            msg = self.L.rrtx_tracker_last_error(self._t).decode()
-            self.close()
-            raise RrtxError("rrtx_tracker_create: %s %s" % (ERRORS.get(rc, rc), msg))
-
-    def close(self):
-        if getattr(self, "_t", None):
-            self.L.rrtx_tracker_destroy(self._t)
-            self._t = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_tracker_last_error(self._t).decode()))
-        return rc
+    _prefix = "tracker"
 
     def run(self, params, batch):
         """params: TrackParams; batch: TrackBatch (its arrays are kept alive by the caller).  Returns 0 or RRTX_PARTIAL."""
-        return self._chk(self.L.rrtx_tracker_run(self._t, C.byref(params), C.byref(batch)), "rrtx_tracker_run")
+        return self._chk(self.L.rrtx_tracker_run(self._s, C.byref(params), C.byref(batch)), "rrtx_tracker_run")
 
     def run_from(self, params, source, batch):
         """params: TrackParams; source: TrackSource; batch: TrackBatch without courses.  Returns 0 or RRTX_PARTIAL."""
-        return self._chk(self.L.rrtx_tracker_run_from(self._t, C.byref(params), C.byref(source), C.byref(batch)),
+        return self._chk(self.L.rrtx_tracker_run_from(self._s, C.byref(params), C.byref(source), C.byref(batch)),
                          "rrtx_tracker_run_from")
 
     def winners(self):
         """(n / group,) int32: the winning course of every group of the last run_from, -1 none."""
         g = C.c_int64()
-        self._chk(self.L.rrtx_tracker_get_winners(self._t, None, C.byref(g)), "rrtx_tracker_get_winners")
+        self._chk(self.L.rrtx_tracker_get_winners(self._s, None, C.byref(g)), "rrtx_tracker_get_winners")
         w = np.zeros(g.value, dtype=np.int32)
-        self._chk(self.L.rrtx_tracker_get_winners(self._t, w.ctypes.data, None), "rrtx_tracker_get_winners")
+        self._chk(self.L.rrtx_tracker_get_winners(self._s, w.ctypes.data, None), "rrtx_tracker_get_winners")
         return w
 
     def goals(self, rows):
         """(rows, 3): the goal poses of the last run_from -- one per group with a group, else one per course."""
         go = np.full((rows, 3), np.nan)
-        self._chk(self.L.rrtx_tracker_get_goals(self._t, go.ctypes.data), "rrtx_tracker_get_goals")
+        self._chk(self.L.rrtx_tracker_get_goals(self._s, go.ctypes.data), "rrtx_tracker_get_goals")
         return go
 
     def counts(self):
         n, m = C.c_int64(), C.c_int64()
-        self._chk(self.L.rrtx_tracker_get_counts(self._t, C.byref(n), C.byref(m)), "rrtx_tracker_get_counts")
+        self._chk(self.L.rrtx_tracker_get_counts(self._s, C.byref(n), C.byref(m)), "rrtx_tracker_get_counts")
         return n.value, m.value
 
     def records(self):
@@ -1153,57 +1113,27 @@ class Tracker:
         n, _ = self.counts()
         rec = np.zeros(n, dtype=TRACK_RECORD)
         off = np.zeros(n + 1, dtype=np.int64)
-        self._chk(self.L.rrtx_tracker_get_records(self._t, rec.ctypes.data, off.ctypes.data), "rrtx_tracker_get_records")
+        self._chk(self.L.rrtx_tracker_get_records(self._s, rec.ctypes.data, off.ctypes.data), "rrtx_tracker_get_records")
         return rec, off
 
     def arrays(self):
         """The seven flat arrays x, y, yaw, v, t, a, d of the last run."""
         _, m = self.counts()
         arr = [np.zeros(m) for _ in range(7)]
-        self._chk(self.L.rrtx_tracker_get_arrays(self._t, *[q.ctypes.data for q in arr], m), "rrtx_tracker_get_arrays")
+        self._chk(self.L.rrtx_tracker_get_arrays(self._s, *[q.ctypes.data for q in arr], m), "rrtx_tracker_get_arrays")
         return arr
 
     def kernel_ms(self):
         ms = C.c_double()
-        self._chk(self.L.rrtx_tracker_get_kernel_ms(self._t, C.byref(ms)), "rrtx_tracker_get_kernel_ms")
+        self._chk(self.L.rrtx_tracker_get_kernel_ms(self._s, C.byref(ms)), "rrtx_tracker_get_kernel_ms")
         return ms.value
 
 
-class Spline:
+class Spline(_DevObject):
     """Thin RAII wrapper over rrtx_spline* (batched cubic-spline courses through waypoints); also a context manager.  It
     owns the device buffers of its runs, so repeated runs reuse them."""
 
-    def __init__(self, device=0):
-        self.L = load()
-        self._s = C.c_void_p()
-        rc = self.L.rrtx_spline_create(int(device), C.byref(self._s))
-        if rc != 0:
-            msg = self.L.rrtx_spline_last_error(self._s).decode()
-            self.close()
-            raise RrtxError("rrtx_spline_create: %s %s" % (ERRORS.get(rc, rc), msg))
-
-    def close(self):
-        if getattr(self, "_s", None):
-            self.L.rrtx_spline_destroy(self._s)
-            self._s = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_spline_last_error(self._s).decode()))
-        return rc
+    _prefix = "spline"
 
     def generation(self):
         """Completed solves of this object so far: what a DeviceCourses of its last solve carries."""
@@ -1273,41 +1203,11 @@ class Spline:
         return planes, status, ms.value
 
 
-class BSpline:
+class BSpline(_DevObject):
     """Thin RAII wrapper over rrtx_bspline* (batched interpolating B-spline courses through waypoints); also a context
     manager.  It owns the device buffers of its runs, so repeated runs reuse them."""
 
-    def __init__(self, device=0):
-        self.L = load()
-        self._s = C.c_void_p()
-        rc = self.L.rrtx_bspline_create(int(device), C.byref(self._s))
-        if rc != 0:
-            msg = self.L.rrtx_bspline_last_error(self._s).decode()
-            self.close()
-            raise RrtxError("rrtx_bspline_create: %s %s" % (ERRORS.get(rc, rc), msg))
-
-    def close(self):
-        if getattr(self, "_s", None):
-            self.L.rrtx_bspline_destroy(self._s)
-            self._s = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_bspline_last_error(self._s).decode()))
-        return rc
+    _prefix = "bspline"
 
     def generation(self):
         """Completed solves of this object so far: what a DeviceCourses of its last solve carries."""
@@ -1372,125 +1272,65 @@ class BSpline:
         return koff, knots, coff, coefs
 
 
-class ArmNav:
+class ArmNav(_DevObject):
     """Thin RAII wrapper over rrtx_armnav* (batched joint-space occupancy grids of a planar arm and searches on them); also a
     context manager.  It owns the device buffers of its calls and keeps the grids of the last occupancy() / set_grids()."""
 
-    def __init__(self, device=0):
-        self.L = load()
-        self._a = C.c_void_p()
-        rc = self.L.rrtx_armnav_create(int(device), C.byref(self._a))
-        if rc != 0:
-            msg = self.L.rrtx_armnav_last_error(self._a).decode()
-            self.close()
-            raise RrtxError("rrtx_armnav_create: %s %s" % (ERRORS.get(rc, rc), msg))
-
-    def close(self):
-        if getattr(self, "_a", None):
-            self.L.rrtx_armnav_destroy(self._a)
-            self._a = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_armnav_last_error(self._a).decode()))
-        return rc
+    _prefix = "armnav"
 
     def occupancy(self, M, link_off, link_len, obs_off, obs_xyr):
         """CSR scenes: int64 offsets of n_scenes + 1 entries, float64 lengths, float64 rows (x, y, radius)."""
-        self._chk(self.L.rrtx_armnav_occupancy(self._a, int(M), len(link_off) - 1, link_off.ctypes.data, link_len.ctypes.data,
+        self._chk(self.L.rrtx_armnav_occupancy(self._s, int(M), len(link_off) - 1, link_off.ctypes.data, link_len.ctypes.data,
                                                obs_off.ctypes.data, obs_xyr.ctypes.data if len(obs_xyr) else None),
                   "rrtx_armnav_occupancy")
 
     def set_grids(self, grids):
         """grids: contiguous uint8 (n_scenes, M, M)."""
-        self._chk(self.L.rrtx_armnav_set_grids(self._a, grids.shape[1], grids.shape[0], grids.ctypes.data), "rrtx_armnav_set_grids")
+        self._chk(self.L.rrtx_armnav_set_grids(self._s, grids.shape[1], grids.shape[0], grids.ctypes.data), "rrtx_armnav_set_grids")
 
     def grids(self, n_scenes, M):
         out = np.zeros((n_scenes, M, M), dtype=np.uint8)
-        self._chk(self.L.rrtx_armnav_get_grids(self._a, out.ctypes.data, out.size), "rrtx_armnav_get_grids")
+        self._chk(self.L.rrtx_armnav_get_grids(self._s, out.ctypes.data, out.size), "rrtx_armnav_get_grids")
         return out
 
     def search(self, scene, starts, goals, want_marks):
         """scene: int32 (n,) or None; starts / goals: contiguous int32 (n, 2)."""
-        self._chk(self.L.rrtx_armnav_search(self._a, len(starts), None if scene is None else scene.ctypes.data,
+        self._chk(self.L.rrtx_armnav_search(self._s, len(starts), None if scene is None else scene.ctypes.data,
                                             starts.ctypes.data if len(starts) else None, goals.ctypes.data if len(goals) else None,
                                             int(bool(want_marks))), "rrtx_armnav_search")
 
     def counts(self):
         """(status, n_route, pops) int32 (n,) each, of the last search."""
         n, m = C.c_int64(), C.c_int64()
-        self._chk(self.L.rrtx_armnav_get_counts(self._a, None, None, None, C.byref(n), C.byref(m)), "rrtx_armnav_get_counts")
+        self._chk(self.L.rrtx_armnav_get_counts(self._s, None, None, None, C.byref(n), C.byref(m)), "rrtx_armnav_get_counts")
         out = [np.zeros(n.value, dtype=np.int32) for _ in range(3)]
-        self._chk(self.L.rrtx_armnav_get_counts(self._a, *[q.ctypes.data for q in out], None, None), "rrtx_armnav_get_counts")
+        self._chk(self.L.rrtx_armnav_get_counts(self._s, *[q.ctypes.data for q in out], None, None), "rrtx_armnav_get_counts")
         return tuple(out) + (m.value,)
 
     def routes(self, n, n_cells):
         """(offsets (n + 1,) int64, cells (n_cells, 2) int32) of the last search."""
         off = np.zeros(n + 1, dtype=np.int64)
         cells = np.zeros((n_cells, 2), dtype=np.int32)
-        self._chk(self.L.rrtx_armnav_get_routes(self._a, off.ctypes.data, cells.ctypes.data if n_cells else None, n_cells),
+        self._chk(self.L.rrtx_armnav_get_routes(self._s, off.ctypes.data, cells.ctypes.data if n_cells else None, n_cells),
                   "rrtx_armnav_get_routes")
         return off, cells
 
     def marks(self, n, M):
         out = np.zeros((n, M, M), dtype=np.uint8)
-        self._chk(self.L.rrtx_armnav_get_marks(self._a, out.ctypes.data, out.size), "rrtx_armnav_get_marks")
+        self._chk(self.L.rrtx_armnav_get_marks(self._s, out.ctypes.data, out.size), "rrtx_armnav_get_marks")
         return out
 
     def kernel_ms(self):
         g, s = C.c_double(), C.c_double()
-        self._chk(self.L.rrtx_armnav_get_kernel_ms(self._a, C.byref(g), C.byref(s)), "rrtx_armnav_get_kernel_ms")
+        self._chk(self.L.rrtx_armnav_get_kernel_ms(self._s, C.byref(g), C.byref(s)), "rrtx_armnav_get_kernel_ms")
         return g.value, s.value
 
 
-class ArmIK:
+class ArmIK(_DevObject):
     """Thin RAII wrapper over rrtx_armik* (batched inverse kinematics of planar arms and the driver's P-control loop); also a
     context manager.  It owns the device buffers of its calls."""
 
-    def __init__(self, device=0):
-        self.L = load()
-        self._a = C.c_void_p()
-        rc = self.L.rrtx_armik_create(int(device), C.byref(self._a))
-        if rc != 0:
-            msg = self.L.rrtx_armik_last_error(self._a).decode()
-            self.close()
-            raise RrtxError("rrtx_armik_create: %s %s" % (ERRORS.get(rc, rc), msg))
-
-    def close(self):
-        if getattr(self, "_a", None):
-            self.L.rrtx_armik_destroy(self._a)
-            self._a = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_armik_last_error(self._a).decode()))
-        return rc
+    _prefix = "armik"
 
     @staticmethod
     def _batch(link_off, link_len, arm, angles, goals, goal_angles, goal_dist):
@@ -1507,81 +1347,51 @@ class ArmIK:
     def solve(self, link_off, link_len, arm, angles, goals, goal_dist, max_iterations, waves):
         """Returns the call's code: 0, or RRTX_PARTIAL when some query was not found."""
         b = self._batch(link_off, link_len, arm, angles, goals, None, goal_dist)
-        return self._chk(self.L.rrtx_armik_solve(self._a, C.byref(b), int(max_iterations), int(waves)), "rrtx_armik_solve")
+        return self._chk(self.L.rrtx_armik_solve(self._s, C.byref(b), int(max_iterations), int(waves)), "rrtx_armik_solve")
 
     def move(self, link_off, link_len, arm, angles, goal_angles, goals, goal_dist, Kp, dt, max_steps, want_arrays):
         b = self._batch(link_off, link_len, arm, angles, goals, goal_angles, goal_dist)
-        return self._chk(self.L.rrtx_armik_move(self._a, C.byref(b), float(Kp), float(dt), int(max_steps), int(bool(want_arrays))),
+        return self._chk(self.L.rrtx_armik_move(self._s, C.byref(b), float(Kp), float(dt), int(max_steps), int(bool(want_arrays))),
                          "rrtx_armik_move")
 
     def records(self):
         """(status int32 (n,), count int32 (n,), end (n, 2), distance (n,)) of the last run."""
         n, m = C.c_int64(), C.c_int64()
-        self._chk(self.L.rrtx_armik_get_records(self._a, None, None, None, None, C.byref(n), C.byref(m)), "rrtx_armik_get_records")
+        self._chk(self.L.rrtx_armik_get_records(self._s, None, None, None, None, C.byref(n), C.byref(m)), "rrtx_armik_get_records")
         status, count = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.int32)
         end, dist = np.zeros((n.value, 2)), np.zeros(n.value)
-        self._chk(self.L.rrtx_armik_get_records(self._a, status.ctypes.data, count.ctypes.data, end.ctypes.data, dist.ctypes.data,
+        self._chk(self.L.rrtx_armik_get_records(self._s, status.ctypes.data, count.ctypes.data, end.ctypes.data, dist.ctypes.data,
                                                 None, None), "rrtx_armik_get_records")
         return status, count, end, dist, m.value
 
     def angles(self, n, n_angles):
         """(offsets (n + 1,) int64, angles (n_angles,)) of the last run."""
         off, ang = np.zeros(n + 1, dtype=np.int64), np.zeros(n_angles)
-        self._chk(self.L.rrtx_armik_get_angles(self._a, off.ctypes.data, ang.ctypes.data if n_angles else None, n_angles),
+        self._chk(self.L.rrtx_armik_get_angles(self._s, off.ctypes.data, ang.ctypes.data if n_angles else None, n_angles),
                   "rrtx_armik_get_angles")
         return off, ang
 
     def trajectory(self, n):
         """(step offsets (n + 1,), angle offsets (n + 1,), angles, distance) of the last move with arrays."""
         so, ao = np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
-        self._chk(self.L.rrtx_armik_get_trajectory(self._a, so.ctypes.data, ao.ctypes.data, None, None, 0, 0), "rrtx_armik_get_trajectory")
+        self._chk(self.L.rrtx_armik_get_trajectory(self._s, so.ctypes.data, ao.ctypes.data, None, None, 0, 0), "rrtx_armik_get_trajectory")
         ang, dist = np.zeros(int(ao[n])), np.zeros(int(so[n]))
         if len(dist):
-            self._chk(self.L.rrtx_armik_get_trajectory(self._a, None, None, ang.ctypes.data, dist.ctypes.data, len(dist), len(ang)),
+            self._chk(self.L.rrtx_armik_get_trajectory(self._s, None, None, ang.ctypes.data, dist.ctypes.data, len(dist), len(ang)),
                       "rrtx_armik_get_trajectory")
         return so, ao, ang, dist
 
     def kernel_ms(self):
         ms, w = C.c_double(), C.c_int32()
-        self._chk(self.L.rrtx_armik_get_kernel_ms(self._a, C.byref(ms), C.byref(w)), "rrtx_armik_get_kernel_ms")
+        self._chk(self.L.rrtx_armik_get_kernel_ms(self._s, C.byref(ms), C.byref(w)), "rrtx_armik_get_kernel_ms")
         return ms.value, w.value
 
 
-class ArmDH:
+class ArmDH(_DevObject):
     """Thin RAII wrapper over rrtx_armdh* (batched forward and inverse kinematics of DH arms in 3-D); also a context manager.
     It owns the device buffers of its calls."""
 
-    def __init__(self, device=0):
-        self.L = load()
-        self._a = C.c_void_p()
-        rc = self.L.rrtx_armdh_create(int(device), C.byref(self._a))
-        if rc != 0:
-            msg = self.L.rrtx_armdh_last_error(self._a).decode()
-            self.close()
-            raise RrtxError("rrtx_armdh_create: %s %s" % (ERRORS.get(rc, rc), msg))
-
-    def close(self):
-        if getattr(self, "_a", None):
-            self.L.rrtx_armdh_destroy(self._a)
-            self._a = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self.L.rrtx_armdh_last_error(self._a).decode()))
-        return rc
+    _prefix = "armdh"
 
     @staticmethod
     def _batch(link_off, dh, arm, angles, n, ref_pose):
@@ -1597,20 +1407,20 @@ class ArmDH:
     def forward(self, link_off, dh, arm, angles, n):
         """Returns the call's code: 0, or RRTX_PARTIAL when some status is not ARMDH_OK."""
         b = self._batch(link_off, dh, arm, angles, n, None)
-        return self._chk(self.L.rrtx_armdh_forward(self._a, C.byref(b)), "rrtx_armdh_forward")
+        return self._chk(self.L.rrtx_armdh_forward(self._s, C.byref(b)), "rrtx_armdh_forward")
 
     def solve(self, link_off, dh, arm, angles, ref_pose, iter_cnt, step_div, method, eps):
         b = self._batch(link_off, dh, arm, angles, len(ref_pose), ref_pose)
-        return self._chk(self.L.rrtx_armdh_solve(self._a, C.byref(b), int(iter_cnt), float(step_div), int(method), float(eps)),
+        return self._chk(self.L.rrtx_armdh_solve(self._s, C.byref(b), int(iter_cnt), float(step_div), int(method), float(eps)),
                          "rrtx_armdh_solve")
 
     def records(self):
         """(status int32 (n,), values (n, 16), kappa_max (n,), n_cut int32 (n,), n_links) of the last run."""
         n, m = C.c_int64(), C.c_int64()
-        self._chk(self.L.rrtx_armdh_get_records(self._a, None, None, None, None, C.byref(n), C.byref(m)), "rrtx_armdh_get_records")
+        self._chk(self.L.rrtx_armdh_get_records(self._s, None, None, None, None, C.byref(n), C.byref(m)), "rrtx_armdh_get_records")
         status, n_cut = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.int32)
         values, kappa = np.zeros((n.value, 16)), np.zeros(n.value)
-        self._chk(self.L.rrtx_armdh_get_records(self._a, status.ctypes.data, values.ctypes.data, kappa.ctypes.data, n_cut.ctypes.data,
+        self._chk(self.L.rrtx_armdh_get_records(self._s, status.ctypes.data, values.ctypes.data, kappa.ctypes.data, n_cut.ctypes.data,
                                                 None, None), "rrtx_armdh_get_records")
         return status, values, kappa, n_cut, m.value
 
@@ -1618,23 +1428,23 @@ class ArmDH:
         """(offsets (n + 1,) int64, angles (n_links,) or None) of the last run."""
         off = np.zeros(n + 1, dtype=np.int64)
         ang = np.zeros(n_links) if want_angles else None
-        self._chk(self.L.rrtx_armdh_get_angles(self._a, off.ctypes.data, ang.ctypes.data if (want_angles and n_links) else None, n_links),
+        self._chk(self.L.rrtx_armdh_get_angles(self._s, off.ctypes.data, ang.ctypes.data if (want_angles and n_links) else None, n_links),
                   "rrtx_armdh_get_angles")
         return off, ang
 
     def transforms(self, n_links):
         t = np.zeros((n_links, 4, 4))
-        self._chk(self.L.rrtx_armdh_get_transforms(self._a, t.ctypes.data if n_links else None, t.size), "rrtx_armdh_get_transforms")
+        self._chk(self.L.rrtx_armdh_get_transforms(self._s, t.ctypes.data if n_links else None, t.size), "rrtx_armdh_get_transforms")
         return t
 
     def jacobians(self, n_links):
         j = np.zeros(6 * n_links)
-        self._chk(self.L.rrtx_armdh_get_jacobians(self._a, j.ctypes.data if n_links else None, j.size), "rrtx_armdh_get_jacobians")
+        self._chk(self.L.rrtx_armdh_get_jacobians(self._s, j.ctypes.data if n_links else None, j.size), "rrtx_armdh_get_jacobians")
         return j
 
     def kernel_ms(self):
         ms, w = C.c_double(), C.c_int32()
-        self._chk(self.L.rrtx_armdh_get_kernel_ms(self._a, C.byref(ms), C.byref(w)), "rrtx_armdh_get_kernel_ms")
+        self._chk(self.L.rrtx_armdh_get_kernel_ms(self._s, C.byref(ms), C.byref(w)), "rrtx_armdh_get_kernel_ms")
         return ms.value, w.value
 
 

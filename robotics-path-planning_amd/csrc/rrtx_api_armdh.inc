@@ -88,7 +88,7 @@ static int armdh_run(rrtx_armdh* a, const rrtx_armdh_batch* b, bool solve, int32
     if (method != RRTX_ARMDH_NEWTON && method != RRTX_ARMDH_LM) return bad("method is neither RRTX_ARMDH_NEWTON nor RRTX_ARMDH_LM");
     if (method == RRTX_ARMDH_LM && (!(eps > 0.0) || !std::isfinite(eps))) return bad("eps is not a finite number above 0");
   }
-  if (!a->usable) return fail(a, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = a->need_device(fn)) return nd;
 
   a->kind = 0;
   a->n = b->n;
@@ -135,15 +135,6 @@ static int armdh_run(rrtx_armdh* a, const rrtx_armdh_batch* b, bool solve, int32
   return RRTX_OK;
 }
 
-template <class Body>
-static int armdh_guard(rrtx_armdh* a, const char* fn, Body&& body) {
-  try {
-    return body();
-  } catch (const std::exception& e) {
-    return fail(a, RRTX_E_HIP, std::string(fn) + ": " + e.what());
-  }
-}
-
 // one device array of the last run into the caller's buffer
 static int armdh_fetch(rrtx_armdh* a, const char* fn, int kind, const char* state_msg, DevBuf rrtx_armdh::*src, double* dst, int64_t per_link,
                        int64_t cap) {
@@ -152,40 +143,25 @@ static int armdh_fetch(rrtx_armdh* a, const char* fn, int kind, const char* stat
   const int64_t count = per_link * a->n_links;
   if (dst && count > 0) {
     if (cap < count) return fail(a, RRTX_E_CAPACITY, std::string(fn) + ": the buffer is too small");
-    HIPCHK(a, hipSetDevice(a->device));
-    HIPCHK(a, hipMemcpy(dst, (a->*src).p, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
+    return a->fetch(dst, (a->*src).p, sizeof(double) * (size_t)count);
   }
   return RRTX_OK;
 }
 
 extern "C" {
 
-int rrtx_armdh_create(int32_t device, rrtx_armdh** out) {
-  if (!out) return fail<rrtx_armdh>(nullptr, RRTX_E_INVALID, "rrtx_armdh_create: out is NULL");
-  *out = nullptr;
-  if (device < 0) return fail<rrtx_armdh>(nullptr, RRTX_E_INVALID, "rrtx_armdh_create: negative device ordinal");
-  rrtx_armdh* a = new (std::nothrow) rrtx_armdh();
-  if (!a) return fail<rrtx_armdh>(nullptr, RRTX_E_HIP, "rrtx_armdh_create: out of host memory");
-  *out = a;   // returned on failure too: the caller reads the message, and calls still check their arguments
-  return a->open(device, "rrtx_armdh_create");
-}
-
-void rrtx_armdh_destroy(rrtx_armdh* a) {
-  if (!a) return;
-  if (a->usable) hipSetDevice(a->device);
-  delete a;   // the buffers, then the events and the stream
-}
-
-const char* rrtx_armdh_last_error(rrtx_armdh* a) { return a ? a->err.c_str() : null_object_err.c_str(); }
+int rrtx_armdh_create(int32_t device, rrtx_armdh** out) { return create_object(device, out, "rrtx_armdh_create"); }
+void rrtx_armdh_destroy(rrtx_armdh* a) { destroy_object(a); }
+const char* rrtx_armdh_last_error(rrtx_armdh* a) { return last_error_of(a); }
 
 int rrtx_armdh_forward(rrtx_armdh* a, const rrtx_armdh_batch* b) {
-  const int rc = armdh_guard(a, "rrtx_armdh_forward", [&] { return armdh_run(a, b, false, 0, 0.0, 0, 0.0); });
+  const int rc = guarded(a, "rrtx_armdh_forward", [&] { return armdh_run(a, b, false, 0, 0.0, 0, 0.0); });
   if (rc < 0 && a) a->kind = 0;
   return rc;
 }
 
 int rrtx_armdh_solve(rrtx_armdh* a, const rrtx_armdh_batch* b, int32_t iter_cnt, double step_div, int32_t method, double eps) {
-  const int rc = armdh_guard(a, "rrtx_armdh_solve", [&] { return armdh_run(a, b, true, iter_cnt, step_div, method, eps); });
+  const int rc = guarded(a, "rrtx_armdh_solve", [&] { return armdh_run(a, b, true, iter_cnt, step_div, method, eps); });
   if (rc < 0 && a) a->kind = 0;
   return rc;
 }

@@ -107,7 +107,7 @@ static int armik_solve(rrtx_armik* a, const rrtx_armik_batch* b, int32_t max_ite
   if (const char* m = armik_batch_msg(a, b, false)) return bad(m);
   if (max_iterations < 1 || max_iterations > RRTX_ARMIK_MAX_ITERATIONS) return bad("max_iterations is outside 1..1e6");
   if (waves < 0 || waves > RRTX_ARMIK_MAX_WAVES) return bad("waves is below 1 or above 2^16");
-  if (!a->usable) return fail(a, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = a->need_device(fn)) return nd;
 
   armik_begin(a, b->n);
   if (b->n == 0) {
@@ -151,7 +151,7 @@ static int armik_move(rrtx_armik* a, const rrtx_armik_batch* b, double Kp, doubl
   if (const char* m = armik_batch_msg(a, b, true)) return bad(m);
   if (max_steps < 1 || max_steps > RRTX_ARMIK_MAX_STEPS) return bad("max_steps is outside 1..1e7");
   if (!std::isfinite(Kp) || !std::isfinite(dt)) return bad("Kp or dt is not finite");
-  if (!a->usable) return fail(a, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = a->need_device(fn)) return nd;
 
   armik_begin(a, b->n);
   a->h_step_off.assign((size_t)b->n + 1, 0);
@@ -213,43 +213,20 @@ static int armik_move(rrtx_armik* a, const rrtx_armik_batch* b, double Kp, doubl
   return armik_partial(a, fn, "some queries reached max_steps or left the domain of sin / cos (see the status column)");
 }
 
-template <class Body>
-static int armik_guard(rrtx_armik* a, const char* fn, Body&& body) {
-  try {
-    return body();
-  } catch (const std::exception& e) {
-    return fail(a, RRTX_E_HIP, std::string(fn) + ": " + e.what());
-  }
-}
-
 extern "C" {
 
-int rrtx_armik_create(int32_t device, rrtx_armik** out) {
-  if (!out) return fail<rrtx_armik>(nullptr, RRTX_E_INVALID, "rrtx_armik_create: out is NULL");
-  *out = nullptr;
-  if (device < 0) return fail<rrtx_armik>(nullptr, RRTX_E_INVALID, "rrtx_armik_create: negative device ordinal");
-  rrtx_armik* a = new (std::nothrow) rrtx_armik();
-  if (!a) return fail<rrtx_armik>(nullptr, RRTX_E_HIP, "rrtx_armik_create: out of host memory");
-  *out = a;   // returned on failure too: the caller reads the message, and calls still check their arguments
-  return a->open(device, "rrtx_armik_create");
-}
-
-void rrtx_armik_destroy(rrtx_armik* a) {
-  if (!a) return;
-  if (a->usable) hipSetDevice(a->device);
-  delete a;   // the buffers, then the events and the stream
-}
-
-const char* rrtx_armik_last_error(rrtx_armik* a) { return a ? a->err.c_str() : null_object_err.c_str(); }
+int rrtx_armik_create(int32_t device, rrtx_armik** out) { return create_object(device, out, "rrtx_armik_create"); }
+void rrtx_armik_destroy(rrtx_armik* a) { destroy_object(a); }
+const char* rrtx_armik_last_error(rrtx_armik* a) { return last_error_of(a); }
 
 int rrtx_armik_solve(rrtx_armik* a, const rrtx_armik_batch* b, int32_t max_iterations, int32_t waves) {
-  const int rc = armik_guard(a, "rrtx_armik_solve", [&] { return armik_solve(a, b, max_iterations, waves); });
+  const int rc = guarded(a, "rrtx_armik_solve", [&] { return armik_solve(a, b, max_iterations, waves); });
   if (rc < 0 && a) a->kind = 0;
   return rc;
 }
 
 int rrtx_armik_move(rrtx_armik* a, const rrtx_armik_batch* b, double Kp, double dt, int32_t max_steps, int32_t want_arrays) {
-  const int rc = armik_guard(a, "rrtx_armik_move", [&] { return armik_move(a, b, Kp, dt, max_steps, want_arrays); });
+  const int rc = guarded(a, "rrtx_armik_move", [&] { return armik_move(a, b, Kp, dt, max_steps, want_arrays); });
   if (rc < 0 && a) a->kind = 0;
   return rc;
 }
@@ -276,8 +253,7 @@ int rrtx_armik_get_angles(rrtx_armik* a, int64_t* offsets, double* angles, int64
   if (offsets) memcpy(offsets, a->h_ang_off.data(), sizeof(int64_t) * ((size_t)a->n + 1));
   if (angles && a->n_angles > 0) {
     if (cap < a->n_angles) return fail(a, RRTX_E_CAPACITY, "rrtx_armik_get_angles: the buffer is too small");
-    HIPCHK(a, hipSetDevice(a->device));
-    HIPCHK(a, hipMemcpy(angles, a->ang_out.p, sizeof(double) * (size_t)a->n_angles, hipMemcpyDeviceToHost));
+    return a->fetch(angles, a->ang_out.p, sizeof(double) * (size_t)a->n_angles);
   }
   return RRTX_OK;
 }
@@ -291,10 +267,10 @@ int rrtx_armik_get_trajectory(rrtx_armik* a, int64_t* step_offsets, int64_t* ang
   if (angle_offsets) memcpy(angle_offsets, a->h_tang_off.data(), sizeof(int64_t) * ((size_t)a->n + 1));
   if ((angles && cap_angles < a->n_tang) || (distance && cap_steps < a->n_steps))
     return fail(a, RRTX_E_CAPACITY, "rrtx_armik_get_trajectory: a buffer is too small");
-  if (a->n_steps > 0 && (angles || distance)) {
-    HIPCHK(a, hipSetDevice(a->device));
-    if (angles) HIPCHK(a, hipMemcpy(angles, a->traj_ang.p, sizeof(double) * (size_t)a->n_tang, hipMemcpyDeviceToHost));
-    if (distance) HIPCHK(a, hipMemcpy(distance, a->traj_dist.p, sizeof(double) * (size_t)a->n_steps, hipMemcpyDeviceToHost));
+  if (a->n_steps > 0) {
+    int rc;
+    if (angles && (rc = a->fetch(angles, a->traj_ang.p, sizeof(double) * (size_t)a->n_tang))) return rc;
+    if (distance && (rc = a->fetch(distance, a->traj_dist.p, sizeof(double) * (size_t)a->n_steps))) return rc;
   }
   return RRTX_OK;
 }

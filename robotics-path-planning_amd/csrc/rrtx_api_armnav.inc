@@ -52,7 +52,7 @@ static int armnav_occupancy(rrtx_armnav* a, int32_t M, int64_t n_scenes, const i
   a->n_scenes = n_scenes;
   a->has_grids = false;
   a->grid_ms = 0.0;
-  if (!a->usable) return fail(a, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = a->need_device(fn)) return nd;
 
   HIPCHK(a, hipSetDevice(a->device));
   int rc;
@@ -99,7 +99,7 @@ static int armnav_set_grids(rrtx_armnav* a, int32_t M, int64_t n_scenes, const u
   a->n_scenes = n_scenes;
   a->has_grids = false;
   a->grid_ms = 0.0;
-  if (!a->usable) return fail(a, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = a->need_device(fn)) return nd;
   HIPCHK(a, hipSetDevice(a->device));
   if (int rc = a->upload(a->grids, bytes, total)) return rc;
   HIPCHK(a, hipStreamSynchronize(a->stream));   // the caller's bytes are free again
@@ -120,7 +120,7 @@ static int armnav_search(rrtx_armnav* a, int64_t n, const int32_t* scene, const 
     if (start_ij[k] < 0 || start_ij[k] >= M || goal_ij[k] < 0 || goal_ij[k] >= M) return bad("a start or goal index outside [0, M)");
   for (int64_t k = 0; scene && k < n; k++)
     if (scene[k] < 0 || scene[k] >= a->n_scenes) return bad("a scene index outside the scenes");
-  if (!a->usable) return fail(a, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = a->need_device(fn)) return nd;
   if (!a->has_grids) return fail(a, RRTX_E_STATE, std::string(fn) + "the last call that brought grids failed");
 
   a->ran = false;
@@ -188,43 +188,19 @@ static int armnav_search(rrtx_armnav* a, int64_t n, const int32_t* scene, const 
   return RRTX_OK;
 }
 
-// `body` with host allocation failures turned into a return code: nothing may throw across the ABI
-template <class Body>
-static int armnav_guard(rrtx_armnav* a, const char* fn, Body&& body) {
-  try {
-    return body();
-  } catch (const std::exception& e) {
-    return fail(a, RRTX_E_HIP, std::string(fn) + ": " + e.what());
-  }
-}
-
 extern "C" {
 
-int rrtx_armnav_create(int32_t device, rrtx_armnav** out) {
-  if (!out) return fail<rrtx_armnav>(nullptr, RRTX_E_INVALID, "rrtx_armnav_create: out is NULL");
-  *out = nullptr;
-  if (device < 0) return fail<rrtx_armnav>(nullptr, RRTX_E_INVALID, "rrtx_armnav_create: negative device ordinal");
-  rrtx_armnav* a = new (std::nothrow) rrtx_armnav();
-  if (!a) return fail<rrtx_armnav>(nullptr, RRTX_E_HIP, "rrtx_armnav_create: out of host memory");
-  *out = a;   // returned on failure too: the caller reads the message, and calls still check their arguments
-  return a->open(device, "rrtx_armnav_create");
-}
-
-void rrtx_armnav_destroy(rrtx_armnav* a) {
-  if (!a) return;
-  if (a->usable) hipSetDevice(a->device);
-  delete a;   // the buffers, then the events and the stream
-}
-
-const char* rrtx_armnav_last_error(rrtx_armnav* a) { return a ? a->err.c_str() : null_object_err.c_str(); }
+int rrtx_armnav_create(int32_t device, rrtx_armnav** out) { return create_object(device, out, "rrtx_armnav_create"); }
+void rrtx_armnav_destroy(rrtx_armnav* a) { destroy_object(a); }
+const char* rrtx_armnav_last_error(rrtx_armnav* a) { return last_error_of(a); }
 
 int rrtx_armnav_occupancy(rrtx_armnav* a, int32_t M, int64_t n_scenes, const int64_t* link_off, const double* link_len,
                           const int64_t* obs_off, const double* obs_xyr) {
-  return armnav_guard(a, "rrtx_armnav_occupancy", [&] { return armnav_occupancy(a, M, n_scenes, link_off, link_len, obs_off, obs_xyr); });
+  return guarded(a, "rrtx_armnav_occupancy", [&] { return armnav_occupancy(a, M, n_scenes, link_off, link_len, obs_off, obs_xyr); });
 }
 
 int rrtx_armnav_set_grids(rrtx_armnav* a, int32_t M, int64_t n_scenes, const uint8_t* bytes) {
-  return armnav_guard(a, "rrtx_armnav_set_grids", [&] { return armnav_set_grids(a, M, n_scenes, bytes); });
+  return guarded(a, "rrtx_armnav_set_grids", [&] { return armnav_set_grids(a, M, n_scenes, bytes); });
 }
 
 int rrtx_armnav_get_grids(rrtx_armnav* a, uint8_t* bytes, int64_t cap) {
@@ -233,14 +209,12 @@ int rrtx_armnav_get_grids(rrtx_armnav* a, uint8_t* bytes, int64_t cap) {
   const int64_t total = a->n_scenes * (int64_t)a->M * a->M;
   if (!bytes) return fail(a, RRTX_E_INVALID, "rrtx_armnav_get_grids: bytes is NULL");
   if (cap < total) return fail(a, RRTX_E_CAPACITY, "rrtx_armnav_get_grids: the buffer is too small");
-  HIPCHK(a, hipSetDevice(a->device));
-  HIPCHK(a, hipMemcpy(bytes, a->grids.p, (size_t)total, hipMemcpyDeviceToHost));
-  return RRTX_OK;
+  return a->fetch(bytes, a->grids.p, (size_t)total);
 }
 
 int rrtx_armnav_search(rrtx_armnav* a, int64_t n_queries, const int32_t* scene, const int32_t* start_ij, const int32_t* goal_ij,
                        int32_t want_marks) {
-  const int rc = armnav_guard(a, "rrtx_armnav_search", [&] { return armnav_search(a, n_queries, scene, start_ij, goal_ij, want_marks); });
+  const int rc = guarded(a, "rrtx_armnav_search", [&] { return armnav_search(a, n_queries, scene, start_ij, goal_ij, want_marks); });
   if (rc == RRTX_E_HIP && a) a->ran = false;
   return rc;
 }
@@ -260,15 +234,14 @@ int rrtx_armnav_get_counts(rrtx_armnav* a, int32_t* status, int32_t* n_route, in
 }
 
 int rrtx_armnav_get_routes(rrtx_armnav* a, int64_t* offsets, int32_t* cells_ij, int64_t cap) {
-  return armnav_guard(a, "rrtx_armnav_get_routes", [&]() -> int {
+  return guarded(a, "rrtx_armnav_get_routes", [&]() -> int {
     if (!a) return fail(a, RRTX_E_INVALID, "rrtx_armnav_get_routes: the arm navigation object is NULL");
     if (!a->ran) return fail(a, RRTX_E_STATE, "rrtx_armnav_get_routes: no completed search");
     if (cells_ij && cap < a->n_cells) return fail(a, RRTX_E_CAPACITY, "rrtx_armnav_get_routes: the buffer is too small");
     std::vector<uint16_t> pool;
     if (cells_ij && a->n_cells > 0) {
       pool.resize((size_t)a->n_cells);
-      HIPCHK(a, hipSetDevice(a->device));
-      HIPCHK(a, hipMemcpy(pool.data(), a->pool.p, sizeof(uint16_t) * pool.size(), hipMemcpyDeviceToHost));
+      if (int rc = a->fetch(pool.data(), a->pool.p, sizeof(uint16_t) * pool.size())) return rc;
     }
     // the pool holds the routes in the order the waves finished; the rows go out in query order
     int64_t tot = 0;
@@ -296,9 +269,7 @@ int rrtx_armnav_get_marks(rrtx_armnav* a, uint8_t* marks, int64_t cap) {
   if (total == 0) return RRTX_OK;
   if (!marks) return fail(a, RRTX_E_INVALID, "rrtx_armnav_get_marks: marks is NULL");
   if (cap < total) return fail(a, RRTX_E_CAPACITY, "rrtx_armnav_get_marks: the buffer is too small");
-  HIPCHK(a, hipSetDevice(a->device));
-  HIPCHK(a, hipMemcpy(marks, a->marks.p, (size_t)total, hipMemcpyDeviceToHost));
-  return RRTX_OK;
+  return a->fetch(marks, a->marks.p, (size_t)total);
 }
 
 int rrtx_armnav_get_kernel_ms(rrtx_armnav* a, double* grid_ms, double* search_ms) {

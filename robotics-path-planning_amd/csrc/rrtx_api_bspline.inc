@@ -115,7 +115,7 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b, const rrtx_
     }
     if (est > (double)RRTX_BSPLINE_MAX_POINTS + (double)n) return bad(many);
   }
-  if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = s->need_device(fn)) return nd;
 
   s->ran = false;
   s->has_arrays = false;
@@ -282,40 +282,19 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b, const rrtx_
 
 extern "C" {
 
-int rrtx_bspline_create(int32_t device, rrtx_bspline** out) {
-  if (!out) return fail<rrtx_bspline>(nullptr, RRTX_E_INVALID, "rrtx_bspline_create: out is NULL");
-  *out = nullptr;
-  if (device < 0) return fail<rrtx_bspline>(nullptr, RRTX_E_INVALID, "rrtx_bspline_create: negative device ordinal");
-  rrtx_bspline* s = new (std::nothrow) rrtx_bspline();
-  if (!s) return fail<rrtx_bspline>(nullptr, RRTX_E_HIP, "rrtx_bspline_create: out of host memory");
-  *out = s;   // returned on failure too: the caller reads the message, and runs still check their arguments
-  return s->open(device, "rrtx_bspline_create");
-}
-
-void rrtx_bspline_destroy(rrtx_bspline* s) {
-  if (!s) return;
-  if (s->usable) hipSetDevice(s->device);
-  delete s;   // the buffers, then the events and the stream
-}
-
-const char* rrtx_bspline_last_error(rrtx_bspline* s) { return s ? s->err.c_str() : null_object_err.c_str(); }
+int rrtx_bspline_create(int32_t device, rrtx_bspline** out) { return create_object(device, out, "rrtx_bspline_create"); }
+void rrtx_bspline_destroy(rrtx_bspline* s) { destroy_object(s); }
+const char* rrtx_bspline_last_error(rrtx_bspline* s) { return last_error_of(s); }
 
 int rrtx_bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b) {
-  try {   // host allocations (records, offsets, messages) must not throw across the ABI
-    return new_generation(s, bspline_run(s, b, nullptr, "rrtx_bspline_run: "));
-  } catch (const std::exception& e) {
-    if (s) s->ran = false;
-    return fail(s, RRTX_E_HIP, std::string("rrtx_bspline_run: ") + e.what());
-  }
+  return guarded(s, "rrtx_bspline_run", [&] { return new_generation(s, bspline_run(s, b, nullptr, "rrtx_bspline_run: ")); },
+                 [&] { if (s) s->ran = false; });
 }
 
 int rrtx_bspline_approximate(rrtx_bspline* s, const rrtx_bspline_smooth_batch* sb) {
-  try {
+  return guarded(s, "rrtx_bspline_approximate", [&] {
     return new_generation(s, bspline_run(s, sb ? &sb->run : nullptr, sb, "rrtx_bspline_approximate: "));
-  } catch (const std::exception& e) {
-    if (s) s->ran = false;
-    return fail(s, RRTX_E_HIP, std::string("rrtx_bspline_approximate: ") + e.what());
-  }
+  }, [&] { if (s) s->ran = false; });
 }
 
 int rrtx_bspline_get_axis_records(rrtx_bspline* s, rrtx_bspline_axis_record* rec, int64_t cap) {
@@ -335,7 +314,7 @@ int rrtx_bspline_get_axis_splines(rrtx_bspline* s, int32_t axis, int64_t* knot_o
   if (!s) return fail(s, RRTX_E_INVALID, std::string(fn) + "the bspline object is NULL");
   if (!s->ran || !s->smooth) return fail(s, RRTX_E_STATE, std::string(fn) + "no completed rrtx_bspline_approximate");
   if (axis != 0 && axis != 1) return fail(s, RRTX_E_INVALID, std::string(fn) + "axis is not 0 or 1");
-  try {
+  return guarded(s, "rrtx_bspline_get_axis_splines", [&]() -> int {
     const size_t W = (size_t)s->n_wp, N = (size_t)s->n;
     std::vector<int64_t> koff(N + 1, 0), coff(N + 1, 0);
     for (size_t c = 0; c < N; c++) {
@@ -350,26 +329,23 @@ int rrtx_bspline_get_axis_splines(rrtx_bspline* s, int32_t axis, int64_t* knot_o
     if (knot_offsets) memcpy(knot_offsets, koff.data(), sizeof(int64_t) * (N + 1));
     if (coef_offsets) memcpy(coef_offsets, coff.data(), sizeof(int64_t) * (N + 1));
     if (W == 0 || (!knots && !coefficients)) return RRTX_OK;
-    HIPCHK(s, hipSetDevice(s->device));
     const size_t plane = W + rppbs::KNOT_SLACK * N;
     std::vector<double> raw(plane > W ? plane : W);
     if (knots && koff[N] > 0) {   // the device keeps a course's knots at wp_off + 6 c of the axis' plane: packed here
-      HIPCHK(s, hipMemcpy(raw.data(), s->knots.as<const double>() + axis * plane, sizeof(double) * plane, hipMemcpyDeviceToHost));
+      if (int rc = s->fetch(raw.data(), s->knots.as<const double>() + axis * plane, sizeof(double) * plane)) return rc;
       for (size_t c = 0; c < N; c++)
         if (koff[c + 1] > koff[c])
           memcpy(knots + koff[c], raw.data() + s->h_wp_off[c] + rppbs::KNOT_SLACK * c, sizeof(double) * (size_t)(koff[c + 1] - koff[c]));
     }
     if (coefficients && coff[N] > 0) {
-      HIPCHK(s, hipMemcpy(raw.data(), s->tab.as<const double>() + ((size_t)axis * rppbs::SMOOTH_AXIS_PLANES + 1) * W, sizeof(double) * W,
-                          hipMemcpyDeviceToHost));
+      if (int rc = s->fetch(raw.data(), s->tab.as<const double>() + ((size_t)axis * rppbs::SMOOTH_AXIS_PLANES + 1) * W, sizeof(double) * W))
+        return rc;
       for (size_t c = 0; c < N; c++)
         if (coff[c + 1] > coff[c])
           memcpy(coefficients + coff[c], raw.data() + s->h_wp_off[c], sizeof(double) * (size_t)(coff[c + 1] - coff[c]));
     }
-  } catch (const std::exception& e) {
-    return fail(s, RRTX_E_HIP, std::string(fn) + e.what());
-  }
-  return RRTX_OK;
+    return RRTX_OK;
+  });
 }
 
 int rrtx_bspline_get_records(rrtx_bspline* s, rrtx_bspline_record* rec, int64_t* offsets, int64_t* n_courses, int64_t* n_points,
@@ -390,10 +366,10 @@ int rrtx_bspline_get_points(rrtx_bspline* s, double* x, double* y, double* yaw, 
   if (cap < s->n_points) return fail(s, RRTX_E_CAPACITY, "rrtx_bspline_get_points: the buffers are too small");
   if (s->n_points == 0) return RRTX_OK;
   const size_t tot = (size_t)s->n_points;
-  HIPCHK(s, hipSetDevice(s->device));
   double* dst[5] = {x, y, yaw, k, u};
   for (int q = 0; q < 5; q++)
-    if (dst[q]) HIPCHK(s, hipMemcpy(dst[q], s->out.as<const double>() + q * tot, sizeof(double) * tot, hipMemcpyDeviceToHost));
+    if (dst[q])
+      if (int rc = s->fetch(dst[q], s->out.as<const double>() + q * tot, sizeof(double) * tot)) return rc;
   return RRTX_OK;
 }
 
@@ -408,22 +384,20 @@ int rrtx_bspline_get_coefficients(rrtx_bspline* s, int64_t* knot_offsets, double
   if (knot_offsets) memcpy(knot_offsets, s->h_knot_off.data(), sizeof(int64_t) * ((size_t)s->n + 1));
   if (s->n_wp == 0) return RRTX_OK;
   const size_t W = (size_t)s->n_wp, N = (size_t)s->n;
-  try {
-    HIPCHK(s, hipSetDevice(s->device));
+  return guarded(s, "rrtx_bspline_get_coefficients", [&]() -> int {
+    int rc;
     if (knots && s->n_knots > 0) {   // the device keeps a course's knots at wp_off + 6 c: packed here
       std::vector<double> raw(W + rppbs::KNOT_SLACK * N);
-      HIPCHK(s, hipMemcpy(raw.data(), s->knots.p, sizeof(double) * raw.size(), hipMemcpyDeviceToHost));
+      if ((rc = s->fetch(raw.data(), s->knots.p, sizeof(double) * raw.size()))) return rc;
       for (size_t c = 0; c < N; c++) {
         const int64_t cnt = s->h_knot_off[c + 1] - s->h_knot_off[c];
         if (cnt > 0) memcpy(knots + s->h_knot_off[c], raw.data() + s->h_wp_off[c] + rppbs::KNOT_SLACK * c, sizeof(double) * (size_t)cnt);
       }
     }
-    if (cx) HIPCHK(s, hipMemcpy(cx, s->tab.as<const double>() + W, sizeof(double) * W, hipMemcpyDeviceToHost));
-    if (cy) HIPCHK(s, hipMemcpy(cy, s->tab.as<const double>() + 2 * W, sizeof(double) * W, hipMemcpyDeviceToHost));
-  } catch (const std::exception& e) {
-    return fail(s, RRTX_E_HIP, std::string(fn) + e.what());
-  }
-  return RRTX_OK;
+    if (cx && (rc = s->fetch(cx, s->tab.as<const double>() + W, sizeof(double) * W))) return rc;
+    if (cy && (rc = s->fetch(cy, s->tab.as<const double>() + 2 * W, sizeof(double) * W))) return rc;
+    return RRTX_OK;
+  });
 }
 
 int rrtx_bspline_get_hits(rrtx_bspline* s, int32_t* hit) {

@@ -157,12 +157,7 @@ static bool courses_current(const rrtx_handle* h) {
 extern "C" {
 
 int rrtx_gather_courses(rrtx_handle* h, int32_t which, int32_t order) {
-  try {   // host allocations (offsets, messages) must not throw across the ABI
-    return gather_courses(h, which, order);
-  } catch (const std::exception& e) {
-    if (h) h->cs.valid = false;
-    return fail(h, RRTX_E_HIP, std::string("rrtx_gather_courses: ") + e.what());
-  }
+  return guarded(h, "rrtx_gather_courses", [&] { return gather_courses(h, which, order); }, [&] { if (h) h->cs.valid = false; });
 }
 
 int rrtx_get_course_counts(rrtx_handle* h, int64_t* offsets, int64_t* n_points, int32_t* has_yaw, double* kernel_ms) {
@@ -182,10 +177,10 @@ int rrtx_get_courses(rrtx_handle* h, double* x, double* y, double* yaw, int64_t 
   if (cap < h->cs.n_points) return fail(h, RRTX_E_CAPACITY, "rrtx_get_courses: the buffers are too small");
   if (h->cs.n_points == 0) return RRTX_OK;
   const size_t bytes = sizeof(double) * (size_t)h->cs.n_points;
-  HIPCHK(h, hipSetDevice(h->device));
-  if (x) HIPCHK(h, hipMemcpy(x, h->cs.x.p, bytes, hipMemcpyDeviceToHost));
-  if (y) HIPCHK(h, hipMemcpy(y, h->cs.y.p, bytes, hipMemcpyDeviceToHost));
-  if (yaw) HIPCHK(h, hipMemcpy(yaw, h->cs.yaw.p, bytes, hipMemcpyDeviceToHost));
+  int rc;
+  if (x && (rc = h->fetch(x, h->cs.x.p, bytes))) return rc;
+  if (y && (rc = h->fetch(y, h->cs.y.p, bytes))) return rc;
+  if (yaw && (rc = h->fetch(yaw, h->cs.yaw.p, bytes))) return rc;
   return RRTX_OK;
 }
 

@@ -181,12 +181,8 @@ static int gather_goal_courses(rrtx_handle* h, int32_t order) {
 extern "C" {
 
 int rrtx_query_goals(rrtx_handle* h, int32_t n_goals, int32_t per_instance, const double* goals, double xy_th, double yaw_th) {
-  try {   // host allocations must not throw across the ABI
-    return query_goals(h, n_goals, per_instance, goals, xy_th, yaw_th);
-  } catch (const std::exception& e) {
-    if (h) h->gq.valid = false;
-    return fail(h, RRTX_E_HIP, std::string("rrtx_query_goals: ") + e.what());
-  }
+  return guarded(h, "rrtx_query_goals", [&] { return query_goals(h, n_goals, per_instance, goals, xy_th, yaw_th); },
+                 [&] { if (h) h->gq.valid = false; });
 }
 
 int rrtx_get_goal_query(rrtx_handle* h, int32_t* node, double* cost, int32_t* n_near, int32_t* n_safe, int32_t* status,
@@ -210,12 +206,7 @@ int rrtx_get_goal_query(rrtx_handle* h, int32_t* node, double* cost, int32_t* n_
 }
 
 int rrtx_gather_goal_courses(rrtx_handle* h, int32_t order) {
-  try {
-    return gather_goal_courses(h, order);
-  } catch (const std::exception& e) {
-    if (h) h->gq.gathered = false;
-    return fail(h, RRTX_E_HIP, std::string("rrtx_gather_goal_courses: ") + e.what());
-  }
+  return guarded(h, "rrtx_gather_goal_courses", [&] { return gather_goal_courses(h, order); }, [&] { if (h) h->gq.gathered = false; });
 }
 
 int rrtx_get_goal_course_counts(rrtx_handle* h, int64_t* offsets, int64_t* n_points, int32_t* has_yaw) {
@@ -236,10 +227,10 @@ int rrtx_get_goal_courses(rrtx_handle* h, double* x, double* y, double* yaw, int
   if (cap < h->gq.n_points) return fail(h, RRTX_E_CAPACITY, std::string(fn) + "the buffers are too small");
   if (h->gq.n_points == 0) return RRTX_OK;
   const size_t bytes = sizeof(double) * (size_t)h->gq.n_points;
-  HIPCHK(h, hipSetDevice(h->device));
-  if (x) HIPCHK(h, hipMemcpy(x, h->gq.x.p, bytes, hipMemcpyDeviceToHost));
-  if (y) HIPCHK(h, hipMemcpy(y, h->gq.y.p, bytes, hipMemcpyDeviceToHost));
-  if (yaw) HIPCHK(h, hipMemcpy(yaw, h->gq.yaw.p, bytes, hipMemcpyDeviceToHost));
+  int rc;
+  if (x && (rc = h->fetch(x, h->gq.x.p, bytes))) return rc;
+  if (y && (rc = h->fetch(y, h->gq.y.p, bytes))) return rc;
+  if (yaw && (rc = h->fetch(yaw, h->gq.yaw.p, bytes))) return rc;
   return RRTX_OK;
 }
 

@@ -70,7 +70,7 @@ static int spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
     est += std::ceil(len / b->ds[b->ds_per_course ? i : 0]) + 1.0;
     if (est > (double)RRTX_SPLINE_MAX_POINTS + (double)n) return bad("more than 2^28 points in all");
   }
-  if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = s->need_device(fn)) return nd;
 
   s->ran = false;
   s->queried = false;
@@ -217,7 +217,7 @@ static int spline_fit1d(rrtx_spline* s, const rrtx_spline_fit1d_batch* b) {
       if (b->knots[w0 + k + 1] < b->knots[w0 + k]) return bad(who + ": the knots must be sorted in ascending order");
     if (b->c && !all_finite(b->c + w0, m)) return bad(who + ": a c value is not finite");
   }
-  if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = s->need_device(fn)) return nd;
 
   s->ran = false;
   s->queried = false;
@@ -298,7 +298,7 @@ static int spline_query(rrtx_spline* s, const rrtx_spline_query_batch* b) {
   if (Q > 0 && !b->t) return bad("t is NULL");
   if (!s->ran) return fail(s, RRTX_E_STATE, std::string(fn) + "no completed run or fit1d");
   if (n != s->n) return bad("n is not the number of splines of the last run");
-  if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = s->need_device(fn)) return nd;
 
   s->queried = false;
   s->q_deriv = b->want_derivatives != 0;
@@ -359,31 +359,12 @@ static int spline_query(rrtx_spline* s, const rrtx_spline_query_batch* b) {
 
 extern "C" {
 
-int rrtx_spline_create(int32_t device, rrtx_spline** out) {
-  if (!out) return fail<rrtx_spline>(nullptr, RRTX_E_INVALID, "rrtx_spline_create: out is NULL");
-  *out = nullptr;
-  if (device < 0) return fail<rrtx_spline>(nullptr, RRTX_E_INVALID, "rrtx_spline_create: negative device ordinal");
-  rrtx_spline* s = new (std::nothrow) rrtx_spline();
-  if (!s) return fail<rrtx_spline>(nullptr, RRTX_E_HIP, "rrtx_spline_create: out of host memory");
-  *out = s;   // returned on failure too: the caller reads the message, and runs still check their arguments
-  return s->open(device, "rrtx_spline_create");
-}
-
-void rrtx_spline_destroy(rrtx_spline* s) {
-  if (!s) return;
-  if (s->usable) hipSetDevice(s->device);
-  delete s;   // the buffers, then the events and the stream
-}
-
-const char* rrtx_spline_last_error(rrtx_spline* s) { return s ? s->err.c_str() : null_object_err.c_str(); }
+int rrtx_spline_create(int32_t device, rrtx_spline** out) { return create_object(device, out, "rrtx_spline_create"); }
+void rrtx_spline_destroy(rrtx_spline* s) { destroy_object(s); }
+const char* rrtx_spline_last_error(rrtx_spline* s) { return last_error_of(s); }
 
 int rrtx_spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
-  try {   // host allocations (records, offsets, messages) must not throw across the ABI
-    return new_generation(s, spline_run(s, b));
-  } catch (const std::exception& e) {
-    if (s) s->ran = false;
-    return fail(s, RRTX_E_HIP, std::string("rrtx_spline_run: ") + e.what());
-  }
+  return guarded(s, "rrtx_spline_run", [&] { return new_generation(s, spline_run(s, b)); }, [&] { if (s) s->ran = false; });
 }
 
 int rrtx_spline_get_records(rrtx_spline* s, rrtx_spline_record* rec, int64_t* offsets, int64_t* n_courses, int64_t* n_points,
@@ -404,10 +385,10 @@ int rrtx_spline_get_points(rrtx_spline* s, double* x, double* y, double* yaw, do
   if (cap < s->n_points) return fail(s, RRTX_E_CAPACITY, "rrtx_spline_get_points: the buffers are too small");
   if (s->n_points == 0) return RRTX_OK;
   const size_t tot = (size_t)s->n_points;
-  HIPCHK(s, hipSetDevice(s->device));
   double* dst[5] = {x, y, yaw, k, t};
   for (int q = 0; q < 5; q++)
-    if (dst[q]) HIPCHK(s, hipMemcpy(dst[q], s->out.as<const double>() + q * tot, sizeof(double) * tot, hipMemcpyDeviceToHost));
+    if (dst[q])
+      if (int rc = s->fetch(dst[q], s->out.as<const double>() + q * tot, sizeof(double) * tot)) return rc;
   return RRTX_OK;
 }
 
@@ -417,9 +398,9 @@ int rrtx_spline_get_c(rrtx_spline* s, double* cx, double* cy, int64_t cap) {
   if (cap < s->n_wp) return fail(s, RRTX_E_CAPACITY, "rrtx_spline_get_c: the buffers are too small");
   if (s->n_wp == 0) return RRTX_OK;
   const size_t W = (size_t)s->n_wp;
-  HIPCHK(s, hipSetDevice(s->device));
-  if (cx) HIPCHK(s, hipMemcpy(cx, s->tab.as<const double>() + 3 * W, sizeof(double) * W, hipMemcpyDeviceToHost));
-  if (cy && s->axes == 2) HIPCHK(s, hipMemcpy(cy, s->tab.as<const double>() + 6 * W, sizeof(double) * W, hipMemcpyDeviceToHost));
+  int rc;
+  if (cx && (rc = s->fetch(cx, s->tab.as<const double>() + 3 * W, sizeof(double) * W))) return rc;
+  if (cy && s->axes == 2 && (rc = s->fetch(cy, s->tab.as<const double>() + 6 * W, sizeof(double) * W))) return rc;
   return RRTX_OK;
 }
 
@@ -440,21 +421,11 @@ int rrtx_spline_get_generation(rrtx_spline* s, uint64_t* generation) {
 }
 
 int rrtx_spline_fit1d(rrtx_spline* s, const rrtx_spline_fit1d_batch* b) {
-  try {
-    return new_generation(s, spline_fit1d(s, b));
-  } catch (const std::exception& e) {
-    if (s) s->ran = false;
-    return fail(s, RRTX_E_HIP, std::string("rrtx_spline_fit1d: ") + e.what());
-  }
+  return guarded(s, "rrtx_spline_fit1d", [&] { return new_generation(s, spline_fit1d(s, b)); }, [&] { if (s) s->ran = false; });
 }
 
 int rrtx_spline_query(rrtx_spline* s, const rrtx_spline_query_batch* b) {
-  try {
-    return spline_query(s, b);
-  } catch (const std::exception& e) {
-    if (s) s->queried = false;
-    return fail(s, RRTX_E_HIP, std::string("rrtx_spline_query: ") + e.what());
-  }
+  return guarded(s, "rrtx_spline_query", [&] { return spline_query(s, b); }, [&] { if (s) s->queried = false; });
 }
 
 int rrtx_spline_get_query(rrtx_spline* s, double* x, double* y, double* yaw, double* k, double* dx, double* dy, double* ddx,
@@ -469,13 +440,13 @@ int rrtx_spline_get_query(rrtx_spline* s, double* x, double* y, double* yaw, dou
   if (cap < s->n_q) return fail(s, RRTX_E_CAPACITY, std::string(fn) + "the buffers are too small");
   if (s->n_q == 0) return RRTX_OK;
   const size_t Q = (size_t)s->n_q;
-  HIPCHK(s, hipSetDevice(s->device));
   double* two[8] = {x, y, yaw, k, dx, dy, ddx, ddy};
   double* one[3] = {y, dy, ddy};
   double** dst = s->axes == 2 ? two : one;
   const int planes = spline_query_planes(s->axes, s->q_deriv);
   for (int q = 0; q < planes; q++)
-    if (dst[q]) HIPCHK(s, hipMemcpy(dst[q], s->q_out.as<const double>() + q * Q, sizeof(double) * Q, hipMemcpyDeviceToHost));
+    if (dst[q])
+      if (int rc = s->fetch(dst[q], s->q_out.as<const double>() + q * Q, sizeof(double) * Q)) return rc;
   if (status) memcpy(status, s->h_qst.data(), sizeof(int32_t) * Q);
   return RRTX_OK;
 }

@@ -59,23 +59,9 @@ struct SteerJob {
 
 extern "C" {
 
-int rrtx_steer_create(int32_t device, rrtx_steer** out) {
-  if (!out) return fail<rrtx_steer>(nullptr, RRTX_E_INVALID, "rrtx_steer_create: out is NULL");
-  *out = nullptr;
-  if (device < 0) return fail<rrtx_steer>(nullptr, RRTX_E_INVALID, "rrtx_steer_create: negative device ordinal");
-  rrtx_steer* s = new (std::nothrow) rrtx_steer();
-  if (!s) return fail<rrtx_steer>(nullptr, RRTX_E_HIP, "rrtx_steer_create: out of host memory");
-  *out = s;   // returned on failure too: the caller reads the message, and solves still check their arguments
-  return s->open(device, "rrtx_steer_create");
-}
-
-void rrtx_steer_destroy(rrtx_steer* s) {
-  if (!s) return;
-  if (s->usable) hipSetDevice(s->device);
-  delete s;   // the buffers, then the events and the stream
-}
-
-const char* rrtx_steer_last_error(rrtx_steer* s) { return s ? s->err.c_str() : null_object_err.c_str(); }
+int rrtx_steer_create(int32_t device, rrtx_steer** out) { return create_object(device, out, "rrtx_steer_create"); }
+void rrtx_steer_destroy(rrtx_steer* s) { destroy_object(s); }
+const char* rrtx_steer_last_error(rrtx_steer* s) { return last_error_of(s); }
 
 static int steer_run(rrtx_steer* s, const SteerJob& j);
 
@@ -157,7 +143,7 @@ static int steer_run(rrtx_steer* s, const SteerJob& j) {
   const int64_t nc = lqr ? 0 : (j.curvature_per_pair ? np : 1);
   const size_t row = sizeof(double) * (lqr ? 2 : 3);
   const double *starts = j.starts, *goals = j.goals, *curvature = j.curvature;
-  if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = s->need_device(fn)) return nd;
   // With an obstacle list the curves' points are computed (stage 1 as for points, then the fill kernel) whether or not
   // they are stored.
   const int64_t n_obs = (int64_t)(s->h_obs.size() / 3);
@@ -352,23 +338,17 @@ static int steer_solve_lqr(rrtx_steer* s, int32_t product, int64_t n, int64_t ng
 int rrtx_steer_solve(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
                      const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
                      const int32_t* word_order, int32_t n_words, int32_t want_points) {
-  try {   // host allocations (offsets, messages) must not throw across the ABI
+  return guarded(s, "rrtx_steer_solve", [&] {
     return new_generation(s, steer_solve(s, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size,
                                          word_order, n_words, want_points));
-  } catch (const std::exception& e) {
-    if (s) s->solved = false;
-    return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve: ") + e.what());
-  }
+  }, [&] { if (s) s->solved = false; });
 }
 
 int rrtx_steer_solve_lqr(rrtx_steer* s, int32_t product, int64_t n, int64_t ng, const double* starts, const double* goals,
                          double step_size, double max_time, double goal_dist, int32_t want_points) {
-  try {
+  return guarded(s, "rrtx_steer_solve_lqr", [&] {
     return new_generation(s, steer_solve_lqr(s, product, n, ng, starts, goals, step_size, max_time, goal_dist, want_points));
-  } catch (const std::exception& e) {
-    if (s) s->solved = false;
-    return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve_lqr: ") + e.what());
-  }
+  }, [&] { if (s) s->solved = false; });
 }
 
 // ---- Bezier ---------------------------------------------------------------------------------------------------------
@@ -390,7 +370,7 @@ static int steer_run_bezier(rrtx_steer* s, const BezierJob& j) {
   const char* fn = j.fn;
   const int64_t n_goals = j.product ? j.ng : j.n, np = j.product ? j.n * j.ng : j.n;
   const int32_t m = j.m, n_points = j.n_points;
-  if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = s->need_device(fn)) return nd;
   const int64_t n_obs = (int64_t)(s->h_obs.size() / 3);
   const bool want_points = j.want_points != 0, want_k = j.want_curvature != 0, stage2 = want_points || n_obs > 0;
 
@@ -563,23 +543,17 @@ static int steer_solve_bezier_cp(rrtx_steer* s, int64_t n, int32_t m, const doub
 int rrtx_steer_solve_bezier(rrtx_steer* s, int32_t product, int64_t n, int64_t ng, const double* starts, const double* goals,
                             double offset0, const double* offsets, int32_t n_points, int32_t want_points,
                             int32_t want_curvature) {
-  try {
+  return guarded(s, "rrtx_steer_solve_bezier", [&] {
     return new_generation(s, steer_solve_bezier(s, product, n, ng, starts, goals, offset0, offsets, n_points, want_points,
                                                 want_curvature));
-  } catch (const std::exception& e) {
-    if (s) s->solved = false;
-    return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve_bezier: ") + e.what());
-  }
+  }, [&] { if (s) s->solved = false; });
 }
 
 int rrtx_steer_solve_bezier_cp(rrtx_steer* s, int64_t n, int32_t m, const double* control_points, int32_t n_points,
                                int32_t want_points, int32_t want_curvature) {
-  try {
+  return guarded(s, "rrtx_steer_solve_bezier_cp", [&] {
     return new_generation(s, steer_solve_bezier_cp(s, n, m, control_points, n_points, want_points, want_curvature));
-  } catch (const std::exception& e) {
-    if (s) s->solved = false;
-    return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve_bezier_cp: ") + e.what());
-  }
+  }, [&] { if (s) s->solved = false; });
 }
 
 int rrtx_steer_get_curvature(rrtx_steer* s, double* k, int64_t cap) {
@@ -589,9 +563,7 @@ int rrtx_steer_get_curvature(rrtx_steer* s, double* k, int64_t cap) {
   if (cap < s->n_points) return fail(s, RRTX_E_CAPACITY, "rrtx_steer_get_curvature: the buffer is too small");
   if (s->n_points == 0) return RRTX_OK;
   if (!k) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_curvature: k is NULL");
-  HIPCHK(s, hipSetDevice(s->device));
-  HIPCHK(s, hipMemcpy(k, s->pk.p, sizeof(double) * (size_t)s->n_points, hipMemcpyDeviceToHost));
-  return RRTX_OK;
+  return s->fetch(k, s->pk.p, sizeof(double) * (size_t)s->n_points);
 }
 
 int rrtx_steer_get_kmax(rrtx_steer* s, double* kmax) {
@@ -600,9 +572,7 @@ int rrtx_steer_get_kmax(rrtx_steer* s, double* kmax) {
     return fail(s, RRTX_E_STATE, "rrtx_steer_get_kmax: no completed Bezier solve with curvature");
   if (s->n == 0) return RRTX_OK;
   if (!kmax) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_kmax: kmax is NULL");
-  HIPCHK(s, hipSetDevice(s->device));
-  HIPCHK(s, hipMemcpy(kmax, s->kmax.p, sizeof(double) * (size_t)s->n, hipMemcpyDeviceToHost));
-  return RRTX_OK;
+  return s->fetch(kmax, s->kmax.p, sizeof(double) * (size_t)s->n);
 }
 
 int rrtx_steer_get_control_points(rrtx_steer* s, double* control_points, int32_t* m) {
@@ -611,9 +581,7 @@ int rrtx_steer_get_control_points(rrtx_steer* s, double* control_points, int32_t
     return fail(s, RRTX_E_STATE, "rrtx_steer_get_control_points: no completed Bezier solve");
   if (m) *m = s->bez_m;
   if (s->n == 0 || !control_points) return RRTX_OK;
-  HIPCHK(s, hipSetDevice(s->device));
-  HIPCHK(s, hipMemcpy(control_points, s->bez_cp.p, sizeof(double) * 2 * (size_t)s->bez_m * (size_t)s->n, hipMemcpyDeviceToHost));
-  return RRTX_OK;
+  return s->fetch(control_points, s->bez_cp.p, sizeof(double) * 2 * (size_t)s->bez_m * (size_t)s->n);
 }
 
 int rrtx_steer_get_ends(rrtx_steer* s, double* ends) {
@@ -622,9 +590,7 @@ int rrtx_steer_get_ends(rrtx_steer* s, double* ends) {
   if (s->kind != rppsb::KIND_LQR) return fail(s, RRTX_E_STATE, "rrtx_steer_get_ends: the last solve was not an LQR solve");
   if (s->n == 0) return RRTX_OK;
   if (!ends) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_ends: ends is NULL");
-  HIPCHK(s, hipSetDevice(s->device));
-  HIPCHK(s, hipMemcpy(ends, s->ends.p, sizeof(double) * 2 * (size_t)s->n, hipMemcpyDeviceToHost));
-  return RRTX_OK;
+  return s->fetch(ends, s->ends.p, sizeof(double) * 2 * (size_t)s->n);
 }
 
 int rrtx_steer_get_counts(rrtx_steer* s, int64_t* n_pairs, int64_t* n_points) {
@@ -644,17 +610,17 @@ int rrtx_steer_get_summary(rrtx_steer* s, int32_t* status, double* length, int32
   if (offsets) memcpy(offsets, s->h_offsets.data(), sizeof(int64_t) * s->h_offsets.size());
   if (s->n == 0) return RRTX_OK;
   const size_t N = (size_t)s->n;
-  HIPCHK(s, hipSetDevice(s->device));
-  if (status) HIPCHK(s, hipMemcpy(status, s->status.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
-  if (length) HIPCHK(s, hipMemcpy(length, s->total.p, sizeof(double) * N, hipMemcpyDeviceToHost));
-  if (n_seg) HIPCHK(s, hipMemcpy(n_seg, s->nseg.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  int rc;
+  if (status && (rc = s->fetch(status, s->status.p, sizeof(int32_t) * N))) return rc;
+  if (length && (rc = s->fetch(length, s->total.p, sizeof(double) * N))) return rc;
+  if (n_seg && (rc = s->fetch(n_seg, s->nseg.p, sizeof(int32_t) * N))) return rc;
   if (s->kind == rppsb::KIND_LQR || s->kind == rppsb::KIND_BEZIER) {   // a rollout or a Bezier curve has neither: zero-filled
     if (seg_len) memset(seg_len, 0, sizeof(double) * 5 * N);
     if (modes) memset(modes, 0, 8 * N);
     return RRTX_OK;
   }
-  if (seg_len) HIPCHK(s, hipMemcpy(seg_len, s->seglen.p, sizeof(double) * 5 * N, hipMemcpyDeviceToHost));
-  if (modes) HIPCHK(s, hipMemcpy(modes, s->modes.p, 8 * N, hipMemcpyDeviceToHost));
+  if (seg_len && (rc = s->fetch(seg_len, s->seglen.p, sizeof(double) * 5 * N))) return rc;
+  if (modes && (rc = s->fetch(modes, s->modes.p, 8 * N))) return rc;
   return RRTX_OK;
 }
 
@@ -665,10 +631,10 @@ int rrtx_steer_get_points(rrtx_steer* s, double* x, double* y, double* yaw, int6
   if (cap < s->n_points) return fail(s, RRTX_E_CAPACITY, "rrtx_steer_get_points: the buffers are too small");
   if (s->n_points == 0) return RRTX_OK;
   const size_t bytes = sizeof(double) * (size_t)s->n_points;
-  HIPCHK(s, hipSetDevice(s->device));
-  if (x) HIPCHK(s, hipMemcpy(x, s->px.p, bytes, hipMemcpyDeviceToHost));
-  if (y) HIPCHK(s, hipMemcpy(y, s->py.p, bytes, hipMemcpyDeviceToHost));
-  if (yaw) HIPCHK(s, hipMemcpy(yaw, s->pyaw.p, bytes, hipMemcpyDeviceToHost));
+  int rc;
+  if (x && (rc = s->fetch(x, s->px.p, bytes))) return rc;
+  if (y && (rc = s->fetch(y, s->py.p, bytes))) return rc;
+  if (yaw && (rc = s->fetch(yaw, s->pyaw.p, bytes))) return rc;
   return RRTX_OK;
 }
 
@@ -681,7 +647,7 @@ int rrtx_steer_set_obstacles(rrtx_steer* s, const double* obstacles, int64_t m, 
   if (m > 0 && !obstacles) return bad("obstacles is NULL");
   if (!std::isfinite(robot_radius)) return bad("robot_radius is not finite");
   if (!all_finite(obstacles, 3 * m)) return bad("an obstacle entry is not finite");
-  try {
+  return guarded(s, "rrtx_steer_set_obstacles", [&] {
     std::vector<double> t((size_t)(3 * m));
     for (int64_t k = 0; k < m; k++) {
       t[3 * k] = obstacles[3 * k];
@@ -689,11 +655,9 @@ int rrtx_steer_set_obstacles(rrtx_steer* s, const double* obstacles, int64_t m, 
       t[3 * k + 2] = py_sq_host(obstacles[3 * k + 2] + robot_radius);   // (size+robot_radius)**2  rrt_05:1635
     }
     s->h_obs.swap(t);
-  } catch (const std::exception& e) {
-    return fail(s, RRTX_E_HIP, std::string(fn) + e.what());
-  }
-  s->obs_dirty = true;
-  return RRTX_OK;
+    s->obs_dirty = true;
+    return RRTX_OK;
+  });
 }
 
 int rrtx_steer_get_hits(rrtx_steer* s, int32_t* hit) {
@@ -702,9 +666,7 @@ int rrtx_steer_get_hits(rrtx_steer* s, int32_t* hit) {
   if (!s->has_hits) return fail(s, RRTX_E_STATE, "rrtx_steer_get_hits: the last solve ran without an obstacle list");
   if (s->n == 0) return RRTX_OK;
   if (!hit) return fail(s, RRTX_E_INVALID, "rrtx_steer_get_hits: hit is NULL");
-  HIPCHK(s, hipSetDevice(s->device));
-  HIPCHK(s, hipMemcpy(hit, s->hit.p, sizeof(int32_t) * (size_t)s->n, hipMemcpyDeviceToHost));
-  return RRTX_OK;
+  return s->fetch(hit, s->hit.p, sizeof(int32_t) * (size_t)s->n);
 }
 
 // ---- every candidate curve of a pair, and the shortest one that is free ----------------------------------------------------
@@ -727,7 +689,7 @@ static int steer_solve_all(rrtx_steer* s, int32_t kind, int32_t product, int64_t
   if (int rc = steer_check(s, fn, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size, word_order,
                            n_words, rppsb::CAND_MAX_WORDS))
     return rc;
-  if (!s->usable) return fail(s, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = s->need_device(fn)) return nd;
   const int64_t n_goals = product ? ng : n, np = product ? n * ng : n;
   const int64_t nc = curvature_per_pair ? np : 1;
   const int64_t n_obs = (int64_t)(s->h_obs.size() / 3);
@@ -899,13 +861,10 @@ static int steer_solve_all(rrtx_steer* s, int32_t kind, int32_t product, int64_t
 int rrtx_steer_solve_all(rrtx_steer* s, int32_t kind, int32_t product, int64_t n, int64_t ng, const double* starts,
                          const double* goals, const double* curvature, int32_t curvature_per_pair, double step_size,
                          const int32_t* word_order, int32_t n_words, int32_t want_points) {
-  try {
+  return guarded(s, "rrtx_steer_solve_all", [&] {
     return new_generation(s, steer_solve_all(s, kind, product, n, ng, starts, goals, curvature, curvature_per_pair, step_size,
                                              word_order, n_words, want_points));
-  } catch (const std::exception& e) {
-    if (s) s->cand_solved = false;
-    return fail(s, RRTX_E_HIP, std::string("rrtx_steer_solve_all: ") + e.what());
-  }
+  }, [&] { if (s) s->cand_solved = false; });
 }
 
 int rrtx_steer_get_cand_counts(rrtx_steer* s, int64_t* n_pairs, int64_t* n_candidates, int64_t* n_points, double* kernel_ms) {
@@ -929,18 +888,18 @@ int rrtx_steer_get_cand_summary(rrtx_steer* s, int32_t* status, int64_t* cand_of
   if (cand_offsets) memcpy(cand_offsets, s->h_cand_off.data(), sizeof(int64_t) * s->h_cand_off.size());
   if (offsets) memcpy(offsets, s->h_cand_poff.data(), sizeof(int64_t) * s->h_cand_poff.size());
   if (s->cand_pairs == 0) return RRTX_OK;
-  HIPCHK(s, hipSetDevice(s->device));
-  if (status) HIPCHK(s, hipMemcpy(status, s->status.p, sizeof(int32_t) * (size_t)s->cand_pairs, hipMemcpyDeviceToHost));
+  int rc;
+  if (status && (rc = s->fetch(status, s->status.p, sizeof(int32_t) * (size_t)s->cand_pairs))) return rc;
   const size_t M = (size_t)s->n_cand;
   if (M == 0) return RRTX_OK;
-  if (pair) HIPCHK(s, hipMemcpy(pair, s->c_pair.p, sizeof(int32_t) * M, hipMemcpyDeviceToHost));
-  if (variant) HIPCHK(s, hipMemcpy(variant, s->c_variant.p, sizeof(int32_t) * M, hipMemcpyDeviceToHost));
-  if (n_seg) HIPCHK(s, hipMemcpy(n_seg, s->c_nseg.p, sizeof(int32_t) * M, hipMemcpyDeviceToHost));
-  if (seg_len) HIPCHK(s, hipMemcpy(seg_len, s->c_seglen.p, sizeof(double) * 5 * M, hipMemcpyDeviceToHost));
-  if (modes) HIPCHK(s, hipMemcpy(modes, s->c_modes.p, 8 * M, hipMemcpyDeviceToHost));
-  if (length) HIPCHK(s, hipMemcpy(length, s->c_total.p, sizeof(double) * M, hipMemcpyDeviceToHost));
-  if (key) HIPCHK(s, hipMemcpy(key, s->c_key.p, sizeof(double) * M, hipMemcpyDeviceToHost));
-  if (hit) HIPCHK(s, hipMemcpy(hit, s->c_hit.p, sizeof(int32_t) * M, hipMemcpyDeviceToHost));
+  if (pair && (rc = s->fetch(pair, s->c_pair.p, sizeof(int32_t) * M))) return rc;
+  if (variant && (rc = s->fetch(variant, s->c_variant.p, sizeof(int32_t) * M))) return rc;
+  if (n_seg && (rc = s->fetch(n_seg, s->c_nseg.p, sizeof(int32_t) * M))) return rc;
+  if (seg_len && (rc = s->fetch(seg_len, s->c_seglen.p, sizeof(double) * 5 * M))) return rc;
+  if (modes && (rc = s->fetch(modes, s->c_modes.p, 8 * M))) return rc;
+  if (length && (rc = s->fetch(length, s->c_total.p, sizeof(double) * M))) return rc;
+  if (key && (rc = s->fetch(key, s->c_key.p, sizeof(double) * M))) return rc;
+  if (hit && (rc = s->fetch(hit, s->c_hit.p, sizeof(int32_t) * M))) return rc;
   return RRTX_OK;
 }
 
@@ -951,15 +910,15 @@ int rrtx_steer_get_cand_points(rrtx_steer* s, double* x, double* y, double* yaw,
   if (cap < s->cand_n_points) return fail(s, RRTX_E_CAPACITY, std::string(fn) + "the buffers are too small");
   if (s->cand_n_points == 0) return RRTX_OK;
   const size_t cnt = (size_t)s->cand_n_points;
-  HIPCHK(s, hipSetDevice(s->device));
-  if (x) HIPCHK(s, hipMemcpy(x, s->c_px.p, sizeof(double) * cnt, hipMemcpyDeviceToHost));
-  if (y) HIPCHK(s, hipMemcpy(y, s->c_py.p, sizeof(double) * cnt, hipMemcpyDeviceToHost));
-  if (yaw) HIPCHK(s, hipMemcpy(yaw, s->c_pyaw.p, sizeof(double) * cnt, hipMemcpyDeviceToHost));
+  int rc;
+  if (x && (rc = s->fetch(x, s->c_px.p, sizeof(double) * cnt))) return rc;
+  if (y && (rc = s->fetch(y, s->c_py.p, sizeof(double) * cnt))) return rc;
+  if (yaw && (rc = s->fetch(yaw, s->c_pyaw.p, sizeof(double) * cnt))) return rc;
   if (directions) {
     if (s->cand_kind == RRTX_STEER_DUBINS)
       memset(directions, 1, cnt);   // a Dubins curve is driven forwards throughout
-    else
-      HIPCHK(s, hipMemcpy(directions, s->c_pdir.p, cnt, hipMemcpyDeviceToHost));
+    else if ((rc = s->fetch(directions, s->c_pdir.p, cnt)))
+      return rc;
   }
   return RRTX_OK;
 }
@@ -1060,12 +1019,8 @@ static int steer_select_free(rrtx_steer* s, int32_t* chosen, int32_t* rank, int3
 }
 
 int rrtx_steer_select_free(rrtx_steer* s, int32_t* chosen, int32_t* rank, int32_t* n_free) {
-  try {
-    return new_generation(s, steer_select_free(s, chosen, rank, n_free));
-  } catch (const std::exception& e) {
-    if (s) s->solved = false;
-    return fail(s, RRTX_E_HIP, std::string("rrtx_steer_select_free: ") + e.what());
-  }
+  return guarded(s, "rrtx_steer_select_free", [&] { return new_generation(s, steer_select_free(s, chosen, rank, n_free)); },
+                 [&] { if (s) s->solved = false; });
 }
 
 int rrtx_steer_get_generation(rrtx_steer* s, uint64_t* generation) {

@@ -22,23 +22,9 @@ static_assert(rppt::SEL_ALL == RRTX_SELECT_ALL && rppt::SEL_FREE == RRTX_SELECT_
 
 extern "C" {
 
-int rrtx_tracker_create(int32_t device, rrtx_tracker** out) {
-  if (!out) return fail<rrtx_tracker>(nullptr, RRTX_E_INVALID, "rrtx_tracker_create: out is NULL");
-  *out = nullptr;
-  if (device < 0) return fail<rrtx_tracker>(nullptr, RRTX_E_INVALID, "rrtx_tracker_create: negative device ordinal");
-  rrtx_tracker* t = new (std::nothrow) rrtx_tracker();
-  if (!t) return fail<rrtx_tracker>(nullptr, RRTX_E_HIP, "rrtx_tracker_create: out of host memory");
-  *out = t;   // returned on failure too: the caller reads the message, and runs still check their arguments
-  return t->open(device, "rrtx_tracker_create");
-}
-
-void rrtx_tracker_destroy(rrtx_tracker* t) {
-  if (!t) return;
-  if (t->usable) hipSetDevice(t->device);
-  delete t;   // the buffers, then the events and the stream
-}
-
-const char* rrtx_tracker_last_error(rrtx_tracker* t) { return t ? t->err.c_str() : null_object_err.c_str(); }
+int rrtx_tracker_create(int32_t device, rrtx_tracker** out) { return create_object(device, out, "rrtx_tracker_create"); }
+void rrtx_tracker_destroy(rrtx_tracker* t) { destroy_object(t); }
+const char* rrtx_tracker_last_error(rrtx_tracker* t) { return last_error_of(t); }
 
 static int tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_batch* b) {
   const char* fn = "rrtx_tracker_run: ";
@@ -70,7 +56,7 @@ static int tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_
   if (b->start_state && !all_finite(b->start_state, 4 * n)) return bad("a start state component is not finite");
   if (b->per_course && !all_finite(b->per_course, 3 * n)) return bad("a per-course value is not finite");
   if (!all_finite(&tp->target_speed, sizeof(*tp) / sizeof(double))) return bad("a parameter is not finite");
-  if (!t->usable) return fail(t, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = t->need_device(fn)) return nd;
 
   t->ran = false;
   t->has_arrays = false;
@@ -191,14 +177,11 @@ static int tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_
 }
 
 int rrtx_tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_batch* b) {
-  try {   // host allocations (records, offsets, messages) must not throw across the ABI
+  return guarded(t, "rrtx_tracker_run", [&] {
     const int rc = tracker_run(t, tp, b);
     if (t && rc >= 0) t->from = false, t->group = 0;   // this run has no winners and no goals to serve
     return rc;
-  } catch (const std::exception& e) {
-    if (t) t->ran = false;
-    return fail(t, RRTX_E_HIP, std::string("rrtx_tracker_run: ") + e.what());
-  }
+  }, [&] { if (t) t->ran = false; });
 }
 
 }  // extern "C"
@@ -329,7 +312,7 @@ static int tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const 
   if (b->start_state && !all_finite(b->start_state, 4 * n)) return bad("a start state component is not finite");
   if (b->per_course && !all_finite(b->per_course, 3 * n)) return bad("a per-course value is not finite");
   if (!all_finite(&tp->target_speed, sizeof(*tp) / sizeof(double))) return bad("a parameter is not finite");
-  if (!t->usable) return fail(t, RRTX_E_NO_DEVICE, std::string(fn) + "no usable gfx950 device (there is no CPU fallback)");
+  if (int nd = t->need_device(fn)) return nd;
   const TrackSourceView v = track_source_view(src->kind, src->object);
   if (v.device != t->device) return bad("the source is on another device");
   if (!v.ran) return state(v.no_run);
@@ -495,12 +478,7 @@ static int tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const 
 extern "C" {
 
 int rrtx_tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_source* src, const rrtx_track_batch* b) {
-  try {
-    return tracker_run_from(t, tp, src, b);
-  } catch (const std::exception& e) {
-    if (t) t->ran = false;
-    return fail(t, RRTX_E_HIP, std::string("rrtx_tracker_run_from: ") + e.what());
-  }
+  return guarded(t, "rrtx_tracker_run_from", [&] { return tracker_run_from(t, tp, src, b); }, [&] { if (t) t->ran = false; });
 }
 
 int rrtx_tracker_get_winners(rrtx_tracker* t, int32_t* winner, int64_t* n_groups) {
@@ -516,9 +494,7 @@ int rrtx_tracker_get_goals(rrtx_tracker* t, double* goals) {
   if (!t->ran || !t->from) return fail(t, RRTX_E_STATE, "rrtx_tracker_get_goals: no completed rrtx_tracker_run_from");
   const size_t rows = t->group ? t->h_winner.size() : (size_t)t->n;
   if (rows == 0) return RRTX_OK;
-  HIPCHK(t, hipSetDevice(t->device));
-  HIPCHK(t, hipMemcpy(goals, t->group ? t->wgoal.p : t->goal.p, sizeof(double) * 3 * rows, hipMemcpyDeviceToHost));
-  return RRTX_OK;
+  return t->fetch(goals, t->group ? t->wgoal.p : t->goal.p, sizeof(double) * 3 * rows);
 }
 
 int rrtx_tracker_get_counts(rrtx_tracker* t, int64_t* n_courses, int64_t* n_steps) {
@@ -544,10 +520,10 @@ int rrtx_tracker_get_arrays(rrtx_tracker* t, double* x, double* y, double* yaw, 
   if (cap < t->n_steps) return fail(t, RRTX_E_CAPACITY, "rrtx_tracker_get_arrays: the buffers are too small");
   if (t->n_steps == 0) return RRTX_OK;
   const size_t tot = (size_t)t->n_steps;
-  HIPCHK(t, hipSetDevice(t->device));
   double* dst[7] = {x, y, yaw, v, tt, a, d};
   for (int k = 0; k < 7; k++)
-    if (dst[k]) HIPCHK(t, hipMemcpy(dst[k], t->out.as<const double>() + k * tot, sizeof(double) * tot, hipMemcpyDeviceToHost));
+    if (dst[k])
+      if (int rc = t->fetch(dst[k], t->out.as<const double>() + k * tot, sizeof(double) * tot)) return rc;
   return RRTX_OK;
 }
 

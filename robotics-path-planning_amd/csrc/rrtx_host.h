@@ -1,7 +1,9 @@
-// rrtx_host.h -- the host-only core under the six opaque objects of include/rrtx.h (rrtx_handle, rrtx_steer,
-// rrtx_tracker, rrtx_spline, rrtx_bspline, rrtx_armnav, rrtx_armik, rrtx_armdh): one check macro, one device buffer, one device probe, one timed section, and the host helpers more than
-// one object uses.  No kernels and no rpp* types: tests/native/host_core_check.cpp compiles it for the CPU against a fake
-// HIP runtime and reaches the failure paths no GPU run can.
+// rrtx_host.h -- the host-only core under the eight opaque objects of include/rrtx.h (rrtx_handle, rrtx_steer,
+// rrtx_tracker, rrtx_spline, rrtx_bspline, rrtx_armnav, rrtx_armik, rrtx_armdh): one check macro, one device buffer, one
+// device probe, one timed section, one lifecycle (create_object, destroy_object, last_error_of) and one guard against
+// exceptions for the seven objects besides the planner handle, and the host helpers more than one object uses.  No kernels
+// and no rpp* types: tests/native/host_core_check.cpp compiles it for the CPU against a fake HIP runtime and reaches the
+// failure paths no GPU run can.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +11,8 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
+#include <new>
 #include <string>
 #include <utility>
 
@@ -167,6 +171,20 @@ struct DevObj {
     return RRTX_OK;
   }
 
+  // `bytes` of device memory into host memory, blocking
+  int fetch(void* dst, const void* src, size_t bytes) {
+    if (!bytes) return RRTX_OK;
+    HIPCHK(this, hipSetDevice(device));
+    HIPCHK(this, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return RRTX_OK;
+  }
+
+  // What a run or solve answers on an object whose open() found no device, 0 otherwise; `fn_colon`: "rrtx_x_run: "
+  int need_device(const char* fn_colon) {
+    if (usable) return RRTX_OK;
+    return fail(this, RRTX_E_NO_DEVICE, std::string(fn_colon) + "no usable gfx950 device (there is no CPU fallback)");
+  }
+
   // One timed section on the stream: `queue` queues the kernels between the two events, `copies` the device -> host copies
   // that ride the same synchronisation (it returns a code; non-zero ends the section).  Waits, then *ms = the kernels' time.
   template <class Queue, class Copies>
@@ -185,3 +203,45 @@ struct DevObj {
     return timed(ms, queue, []() -> int { return RRTX_OK; });
   }
 };
+
+// ---- the lifecycle of the seven objects besides the planner handle: rrtx_X_create, rrtx_X_destroy, rrtx_X_last_error --------
+// `fn`: the entry point's name, without a colon
+template <class T>
+int create_object(int32_t device, T** out, const char* fn) {
+  if (!out) return fail<T>(nullptr, RRTX_E_INVALID, std::string(fn) + ": out is NULL");
+  *out = nullptr;
+  if (device < 0) return fail<T>(nullptr, RRTX_E_INVALID, std::string(fn) + ": negative device ordinal");
+  T* o = new (std::nothrow) T();
+  if (!o) return fail<T>(nullptr, RRTX_E_HIP, std::string(fn) + ": out of host memory");
+  *out = o;   // returned on failure too: the caller reads the message, and calls still check their arguments
+  return o->open(device, fn);
+}
+
+template <class T>
+void destroy_object(T* o) {
+  if (!o) return;
+  if (o->usable) (void)hipSetDevice(o->device);
+  delete o;   // the buffers, then the events and the stream
+}
+
+template <class T>
+const char* last_error_of(T* o) {
+  return o ? o->err.c_str() : null_object_err.c_str();
+}
+
+// Nothing may throw across the ABI (host allocations: records, offsets, messages).  Returns body(); a std::exception becomes
+// RRTX_E_HIP with the message "<fn>: <what>", after on_throw() has taken away what the failed call may have half written.
+// What a returned error code invalidates is the entry point's own business.
+template <class Obj, class Body, class OnThrow>
+int guarded(Obj* o, const char* fn, Body&& body, OnThrow&& on_throw) {
+  try {
+    return body();
+  } catch (const std::exception& e) {
+    on_throw();
+    return fail(o, RRTX_E_HIP, std::string(fn) + ": " + e.what());
+  }
+}
+template <class Obj, class Body>
+int guarded(Obj* o, const char* fn, Body&& body) {
+  return guarded(o, fn, body, [] {});
+}

@@ -72,6 +72,11 @@ inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMe
   memcpy(dst, src, bytes);
   return hipSuccess;
 }
+inline hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) {
+  fake_hip.log.push_back("hipMemcpy");
+  memcpy(dst, src, bytes);
+  return hipSuccess;
+}
 inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
   fake_hip.log.push_back("hipStreamCreateWithFlags");
   if (fake_hip_trips(fake_hip.fail_stream)) return hipErrorOutOfMemory;

@@ -1,5 +1,6 @@
 // csrc/rrtx_host.h against the fake runtime of tests/native/fake_hip: the allocation- and creation-failure paths of the
-// device buffer, the device-object base and the timed section, which no GPU run can reach.  Built by tests/test_host_core.py
+// device buffer, the device-object base, the timed section, the objects' shared lifecycle and the guard against exceptions,
+// which no GPU run can reach.  Built by tests/test_host_core.py
 // with ASan + UBSan; prints "ok" and exits 0, or names the first check that failed.
 #include <cstdio>
 
@@ -162,6 +163,107 @@ static void the_shared_helpers() {
   CHECK(!track_params_ok(&tp));
 }
 
+// what an object of the C ABI looks like to the shared lifecycle: a DevObj with buffers and a result flag
+struct Probe : DevObj {
+  DevBuf b;
+  bool ran = true;
+  // host memory that can be told to run out
+  static inline bool fail_new = false;
+  static void* operator new(size_t n, const std::nothrow_t&) noexcept { return fail_new ? nullptr : malloc(n); }
+  static void operator delete(void* p, const std::nothrow_t&) noexcept { free(p); }
+  static void operator delete(void* p) noexcept { free(p); }
+};
+
+static void create_object_refuses_and_creates() {
+  Probe* p = (Probe*)0x1;
+  CHECK(create_object<Probe>(0, nullptr, "probe_create") == RRTX_E_INVALID);
+  CHECK(std::string(last_error_of<Probe>(nullptr)) == "probe_create: out is NULL");
+  CHECK(create_object(-1, &p, "probe_create") == RRTX_E_INVALID && p == nullptr);
+  CHECK(std::string(last_error_of<Probe>(nullptr)) == "probe_create: negative device ordinal");
+  Probe::fail_new = true;
+  CHECK(create_object(0, &p, "probe_create") == RRTX_E_HIP && p == nullptr);
+  Probe::fail_new = false;
+  CHECK(std::string(last_error_of<Probe>(nullptr)) == "probe_create: out of host memory");
+
+  CHECK(create_object(0, &p, "probe_create") == RRTX_OK && p && p->usable && p->device == 0);
+  CHECK(std::string(last_error_of(p)).empty());
+  CHECK(fake_hip.live_streams == 1 && fake_hip.live_events == 2);
+  destroy_object(p);
+  CHECK(fake_hip.live_streams == 0 && fake_hip.live_events == 0);
+
+  // a failing stream creation, then a failing second event creation: the object comes back with the message
+  for (int second_event = 0; second_event < 2; second_event++) {
+    fake_hip.fail_stream = second_event ? 0 : 1;
+    fake_hip.fail_event = second_event ? 2 : 0;
+    p = nullptr;
+    CHECK(create_object(0, &p, "probe_create") == RRTX_E_HIP && p != nullptr && !p->usable);
+    CHECK(starts_with(last_error_of(p), second_event ? "hipEventCreate" : "hipStreamCreateWithFlags"));
+    destroy_object(p);
+    CHECK(fake_hip.live_streams == 0 && fake_hip.live_events == 0 && fake_hip.live_allocs == 0);
+    fake_hip.fail_stream = fake_hip.fail_event = 0;
+  }
+
+  // no device: still an object, whose calls check their arguments and then refuse
+  fake_hip.devices = 0;
+  p = nullptr;
+  CHECK(create_object(0, &p, "probe_create") == RRTX_E_NO_DEVICE && p != nullptr && !p->usable);
+  CHECK(std::string(last_error_of(p)) == "probe_create: no usable gfx950 device (there is no CPU fallback)");
+  CHECK(p->need_device("probe_run: ") == RRTX_E_NO_DEVICE);
+  CHECK(p->err == "probe_run: no usable gfx950 device (there is no CPU fallback)");
+  const size_t at = fake_hip.log.size();
+  destroy_object(p);
+  CHECK(calls_since(at).find("hipSetDevice") == std::string::npos);   // an unusable object never selects a device
+  fake_hip.devices = 1;
+}
+
+static void destroy_object_releases_in_order() {
+  size_t at = fake_hip.log.size();
+  destroy_object<Probe>(nullptr);
+  CHECK(fake_hip.log.size() == at);
+  Probe* p = nullptr;
+  CHECK(create_object(0, &p, "probe_create") == RRTX_OK);
+  CHECK(p->need_device("probe_run: ") == RRTX_OK && p->err.empty());
+  CHECK(p->reserve(p->b, 32) == RRTX_OK);
+  at = fake_hip.log.size();
+  destroy_object(p);   // the device, the buffers, then the events and the stream
+  CHECK(calls_since(at) == "hipSetDevice hipFree hipEventDestroy hipEventDestroy hipStreamDestroy");
+  CHECK(fake_hip.live_allocs == 0 && fake_hip.live_streams == 0 && fake_hip.live_events == 0);
+}
+
+static void guarded_entry_points() {
+  Probe o;
+  int thrown = 0;
+  auto on_throw = [&] { thrown++, o.ran = false; };
+  // a body's code passes through, and nothing is taken away
+  CHECK(guarded(&o, "fn", [] { return (int)RRTX_OK; }, on_throw) == RRTX_OK);
+  CHECK(guarded(&o, "fn", [] { return (int)RRTX_PARTIAL; }, on_throw) == RRTX_PARTIAL);
+  CHECK(guarded(&o, "fn", [] { return (int)RRTX_E_STATE; }, on_throw) == RRTX_E_STATE);
+  CHECK(guarded(&o, "fn", [&] { return fail(&o, RRTX_E_HIP, "the body's own"); }, on_throw) == RRTX_E_HIP);
+  CHECK(thrown == 0 && o.ran && o.err == "the body's own");
+  // a throw becomes a code and a message, after on_throw has run once
+  CHECK(guarded(&o, "fn", []() -> int { throw std::bad_alloc(); }, on_throw) == RRTX_E_HIP);
+  CHECK(thrown == 1 && !o.ran && o.err == "fn: std::bad_alloc");
+  // without on_throw, and without an object
+  o.err.clear();
+  CHECK(guarded(&o, "fn2", []() -> int { throw std::bad_alloc(); }) == RRTX_E_HIP && o.err == "fn2: std::bad_alloc");
+  CHECK(guarded((Probe*)nullptr, "fn3", []() -> int { throw std::bad_alloc(); }) == RRTX_E_HIP);
+  CHECK(std::string(last_error_of<Probe>(nullptr)) == "fn3: std::bad_alloc");
+  CHECK(guarded((Probe*)nullptr, "fn3", [] { return (int)RRTX_PARTIAL; }) == RRTX_PARTIAL);
+}
+
+static void fetch_copies_device_memory() {
+  Probe o;
+  CHECK(o.open(0, "check") == RRTX_OK);
+  const double src[3] = {1.0, 2.0, 3.0};
+  CHECK(o.upload(o.b, src, sizeof(src)) == RRTX_OK);
+  double dst[3] = {0.0, 0.0, 0.0};
+  size_t at = fake_hip.log.size();
+  CHECK(o.fetch(dst, o.b.p, sizeof(dst)) == RRTX_OK && memcmp(dst, src, sizeof(src)) == 0);
+  CHECK(calls_since(at) == "hipSetDevice hipMemcpy");
+  at = fake_hip.log.size();
+  CHECK(o.fetch(nullptr, nullptr, 0) == RRTX_OK && fake_hip.log.size() == at);   // nothing to copy: no call at all
+}
+
 int main() {
   reserve_happy_path();
   reserve_with_a_failing_allocation();
@@ -172,6 +274,10 @@ int main() {
   open_and_the_device_probe();
   timed_section();
   the_shared_helpers();
+  create_object_refuses_and_creates();
+  destroy_object_releases_in_order();
+  guarded_entry_points();
+  fetch_copies_device_memory();
   CHECK(fake_hip.live_allocs == 0 && fake_hip.live_streams == 0 && fake_hip.live_events == 0);
   CHECK(fake_hip.mallocs == fake_hip.frees);
   if (!failures) printf("ok\n");
