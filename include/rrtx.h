@@ -427,6 +427,52 @@ int rrtx_get_track_records(rrtx_handle* h, int32_t instance, int32_t* cand, rrtx
 /* HIP-event time of the kernels of the last rrtx_track_planned, and the roll-out steps they ran (both launches) */
 int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps);
 
+/* ---- the closed-loop stage for MANY goals from the planned trees (csrc/goal_track.hip.h, csrc/rpp_goaltrack.h) ---------------
+ * After a plan of RRTX_ALGO_RS (either cost): for every instance i and goal g = (x, y, yaw) what
+ *   path_indexs = self.get_goal_indexes(); self.search_best_feasible_path(path_indexs)          (rrt_10 :1488-1493)
+ * returns on i's finished node_list with self.end = Node(*g) and tp's tracking parameters (xy_th / yaw_th select the
+ * candidates): candidates in ascending node index, each one's course (start pose, polylines root -> candidate, g) rolled out
+ * towards g against the instance's own obstacle rows, the feasible roll-out with the smallest t[-1] wins, the later candidate
+ * among equal times.  A goal is any double; one with a NaN or an infinity finds no candidate.  Nothing of the plan changes, and
+ * neither do the answers of rrtx_track_planned or rrtx_query_goals; the buffers are this call's own.
+ * Queries are (instance, goal) pairs, row major; `goals` is (n_goals, 3) shared (per_instance = 0) or (n_instances, n_goals, 3).
+ * A query with a refused candidate has no winner and carries the status bit (as rrtx_track_outcome.status); its records stay
+ * readable.  An instance whose tree did not finish (RRTX_GOALQ_NO_TREE's condition) answers no_tree = 1.
+ * Returns RRTX_OK, or RRTX_PARTIAL when some query carries a status.  Checked in this order before any device call:
+ * RRTX_E_INVALID for a NULL handle / tp / goals, n_goals < 1, per_instance not 0 / 1, more than RRTX_GOALQ_MAX_QUERIES queries
+ * or track parameters rrtx_track_planned refuses; RRTX_E_STATE for another algo, without a completed plan or while one is in
+ * progress.  RRTX_E_CAPACITY for more than 2^24 candidates in all.  A new plan drops the answers (getters: RRTX_E_STATE).
+ * Launches and copies per call do not depend on the number of instances, goals, candidates or on the depth of a tree. */
+typedef struct rrtx_goal_track_outcome {
+  int32_t flag;      /* a feasible roll-out exists (the first element of the tuple) */
+  int32_t winner;    /* its position in the query's candidate list, -1 none */
+  int32_t n_cand;    /* len(get_goal_indexes()) */
+  int32_t len;       /* len(t) of the winner; x / y / yaw hold len + 1 values (goal pose appended, :1519-1521) */
+  int32_t node;      /* the winner's node index, -1 none */
+  int32_t status;    /* 0, or RRTX_ST_OVERFLOW / RRTX_ST_REF_RAISES / RRTX_ST_UNSUPPORTED as rrtx_track_outcome.status */
+  int32_t no_tree;   /* 1: the instance's tree did not finish, nothing was asked of it */
+  int32_t reserved;
+  double t_last;     /* t[-1] of the winner, +inf without one */
+} rrtx_goal_track_outcome;
+/* want_arrays = 0: records and outcomes only (no store launch; rrtx_get_goal_track_arrays then returns RRTX_E_STATE) */
+int rrtx_track_goals(rrtx_handle* h, const rrtx_track_params* tp, int32_t n_goals, int32_t per_instance, const double* goals,
+                     int32_t want_arrays);
+/* out: one outcome per query; cand_offsets: n_queries + 1 entries into the candidate records; arr_offsets: n_queries + 1,
+ * the exclusive sum of len + 1 over the queries with a flag (cap = queries the buffers hold; NULL buffers are skipped).
+ * n_steps = arr_offsets[n_queries]. */
+int rrtx_get_goal_track(rrtx_handle* h, rrtx_goal_track_outcome* out, int64_t* cand_offsets, int64_t* arr_offsets, int64_t cap,
+                        int64_t* n_queries, int64_t* n_candidates, int64_t* n_steps);
+/* candidate node indices and their records, n_candidates of each, query after query */
+int rrtx_get_goal_track_records(rrtx_handle* h, int32_t* cand_node, rrtx_track_record* rec, int64_t cap);
+/* n_steps doubles each: a flagged query owns len + 1 entries at its arr_offset; x, y, yaw fill them (the goal pose last),
+ * v, t, a, d fill len and leave the last one NaN */
+int rrtx_get_goal_track_arrays(rrtx_handle* h, double* x, double* y, double* yaw, double* v, double* t, double* a, double* d,
+                               int64_t cap);
+/* RRTX_ALGO_RS: the yaw column of the stored edge polylines (Node.path_yaw), the points of rrtx_get_polylines in its order */
+int rrtx_get_polyline_yaw(rrtx_handle* h, int32_t instance, double* pyaw, int64_t cap_points);
+/* HIP-event times of the last call: the two candidate launches, roll + pick, and the store launch (0 without one) */
+int rrtx_get_goal_track_kernel_ms(rrtx_handle* h, double* list_ms, double* roll_ms, double* store_ms);
+
 /* ---- batched Dubins / Reeds-Shepp curves between pose pairs, without a planner (csrc/steer_batch.hip.h) -------------------
  * Replaces plan_dubins_path (10_path_planning_00_dubins_path.py :109-197) and reeds_shepp_path_planning
  * (10_path_planning_00_reeds_shepp_path.py :506-515) called once per pair: every double is the reference's, bit for bit.

@@ -18,7 +18,7 @@ armdh (BatchArmDH: batched forward kinematics, Jacobians and 6-DoF inverse kinem
 _abi (ctypes binding of include/rrtx.h), csrc/ (HIP kernels + C ABI sources).
 """
 from . import _abi  # noqa: F401
-from .planner import (RRT, RRTSobol, RRTStar, RRTStarDubins, RRTDubins, RRTStarReedsShepp, BITStar, bitstar_rotation, InformedRRTStar, LQRRRTStar, ClosedLoopRRTStar, BatchPlanner, PlannerCourses, GoalQueryResult, Node, AreaBounds, get_path_length, path_smoothing,  # noqa: F401
+from .planner import (RRT, RRTSobol, RRTStar, RRTStarDubins, RRTDubins, RRTStarReedsShepp, BITStar, bitstar_rotation, InformedRRTStar, LQRRRTStar, ClosedLoopRRTStar, BatchPlanner, PlannerCourses, GoalQueryResult, GoalTrackResult, Node, AreaBounds, get_path_length, path_smoothing,  # noqa: F401
                       informed_rotation)
 from .steer import BatchSteer, SteerCandidates  # noqa: F401
 from .track import BatchTrack  # noqa: F401
@@ -28,4 +28,4 @@ from .armnav import BatchArmNav  # noqa: F401
 from .armik import BatchArmIK, ArmIKResult, ArmMoveResult  # noqa: F401
 from .armdh import BatchArmDH, ArmDHResult, ArmDHForward  # noqa: F401
 
-__all__ = ["RRT", "RRTSobol", "RRTStar", "RRTStarDubins", "RRTDubins", "RRTStarReedsShepp", "BITStar", "InformedRRTStar", "LQRRRTStar", "ClosedLoopRRTStar", "BatchPlanner", "PlannerCourses", "GoalQueryResult", "BatchSteer", "SteerCandidates", "BatchTrack", "BatchSpline", "SplineQueryResult", "BatchBSpline", "BSplineResult", "BSplineSmoothResult", "BatchArmNav", "BatchArmIK", "ArmIKResult", "ArmMoveResult", "BatchArmDH", "ArmDHResult", "ArmDHForward", "Node", "AreaBounds", "get_path_length", "path_smoothing"]
+__all__ = ["RRT", "RRTSobol", "RRTStar", "RRTStarDubins", "RRTDubins", "RRTStarReedsShepp", "BITStar", "InformedRRTStar", "LQRRRTStar", "ClosedLoopRRTStar", "BatchPlanner", "PlannerCourses", "GoalQueryResult", "GoalTrackResult", "BatchSteer", "SteerCandidates", "BatchTrack", "BatchSpline", "SplineQueryResult", "BatchBSpline", "BSplineResult", "BSplineSmoothResult", "BatchArmNav", "BatchArmIK", "ArmIKResult", "ArmMoveResult", "BatchArmDH", "ArmDHResult", "ArmDHForward", "Node", "AreaBounds", "get_path_length", "path_smoothing"]

@@ -44,6 +44,8 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_gather_courses", "rrtx_get_course_counts", "rrtx_get_courses", "rrtx_get_course_generation",
            "rrtx_query_goals", "rrtx_get_goal_query", "rrtx_gather_goal_courses", "rrtx_get_goal_course_counts",
            "rrtx_get_goal_courses", "rrtx_get_goal_query_kernel_ms",
+           "rrtx_track_goals", "rrtx_get_goal_track", "rrtx_get_goal_track_records", "rrtx_get_goal_track_arrays",
+           "rrtx_get_goal_track_kernel_ms", "rrtx_get_polyline_yaw",
            "rrtx_spline_create", "rrtx_spline_destroy", "rrtx_spline_last_error", "rrtx_spline_run", "rrtx_spline_get_records",
            "rrtx_spline_get_points", "rrtx_spline_get_c", "rrtx_spline_get_hits",
            "rrtx_spline_fit1d", "rrtx_spline_query", "rrtx_spline_get_query", "rrtx_spline_get_query_info",
@@ -123,6 +125,16 @@ class TrackOutcome(C.Structure):
 
 TRACK_RECORD = np.dtype([("find_goal", np.int32), ("len", np.int32), ("fail", np.int32), ("ood", np.int32),
                          ("t_last", np.float64)])
+
+
+class GoalTrackOutcome(C.Structure):
+    """rrtx_goal_track_outcome: the answer of one (instance, goal) query of rrtx_track_goals."""
+    _fields_ = [(k, C.c_int32) for k in ("flag", "winner", "n_cand", "len", "node", "status", "no_tree", "reserved")] + \
+               [("t_last", C.c_double)]
+
+
+GOAL_TRACK_OUTCOME = np.dtype([(k, np.int32) for k in ("flag", "winner", "n_cand", "len", "node", "status", "no_tree", "reserved")] +
+                              [("t_last", np.float64)])
 
 
 class TrackBatch(C.Structure):
@@ -325,6 +337,12 @@ def load():
     L.rrtx_get_goal_course_counts.argtypes = [vp, vp, i64p, C.POINTER(i32)]
     L.rrtx_get_goal_courses.argtypes = [vp, vp, vp, vp, C.c_int64]
     L.rrtx_get_goal_query_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.rrtx_track_goals.argtypes = [vp, C.POINTER(TrackParams), i32, i32, vp, i32]
+    L.rrtx_get_goal_track.argtypes = [vp, vp, vp, vp, C.c_int64, i64p, i64p, i64p]
+    L.rrtx_get_goal_track_records.argtypes = [vp, vp, vp, C.c_int64]
+    L.rrtx_get_goal_track_arrays.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64]
+    L.rrtx_get_polyline_yaw.argtypes = [vp, i32, vp, C.c_int64]
+    L.rrtx_get_goal_track_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.rrtx_spline_run.argtypes = [vp, C.POINTER(SplineBatch)]
     L.rrtx_spline_get_records.argtypes = [vp, vp, vp, i64p, i64p, C.POINTER(C.c_double)]
     L.rrtx_spline_get_points.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64]
@@ -659,6 +677,14 @@ class Handle:
                                             tot.value, C.byref(tot)), "rrtx_get_polylines")
         return plen, px, py
 
+    def get_polyline_yaw(self, instance=0):
+        """RRTX_ALGO_RS: Node.path_yaw of every node, concatenated as get_polylines concatenates path_x / path_y."""
+        tot = C.c_int64()
+        self._chk(self.L.rrtx_get_polylines(self._h, instance, None, 0, None, None, 0, C.byref(tot)), "rrtx_get_polylines")
+        pyaw = np.zeros(tot.value)
+        self._chk(self.L.rrtx_get_polyline_yaw(self._h, instance, pyaw.ctypes.data, tot.value), "rrtx_get_polyline_yaw")
+        return pyaw
+
     # ---- closed-loop stage of rrt_10 (rrtx_track_planned) on a planned RRTX_ALGO_RS handle
     def set_rs_cost(self, mode):
         self._chk(self.L.rrtx_set_rs_cost(self._h, mode), "rrtx_set_rs_cost")
@@ -788,6 +814,54 @@ class Handle:
         self._chk(self.L.rrtx_get_goal_courses(self._h, x.ctypes.data, y.ctypes.data, None if yaw is None else yaw.ctypes.data,
                                                n.value), "rrtx_get_goal_courses")
         return off, x, y, yaw
+
+    # ---- rrt_10's closed-loop stage for many goals from the planned trees (rrtx_track_goals)
+    def track_goals(self, goals, per_instance, arrays=True, **kw):
+        """goals: (g, 3) shared, or (n_instances, g, 3) with per_instance; keywords: the fields of rrtx_track_params
+        (defaults TRACK_DEFAULTS).  Returns (rc, n_goals): rc 0 or RRTX_PARTIAL (a query with a refused candidate)."""
+        p = dict(TRACK_DEFAULTS)
+        for k, v in kw.items():
+            if k not in p:
+                raise TypeError("track_goals: unknown keyword %r" % k)
+            p[k] = float(v)
+        g = np.ascontiguousarray(goals, dtype=np.float64)
+        n_goals = g.shape[-2]
+        rc = self.L.rrtx_track_goals(self._h, C.byref(TrackParams(**p)), int(n_goals), 1 if per_instance else 0, g.ctypes.data,
+                                     1 if arrays else 0)
+        if rc != RRTX_PARTIAL:
+            self._chk(rc, "rrtx_track_goals")
+        return rc, n_goals
+
+    def get_goal_track(self):
+        """(outcomes (nq,) GOAL_TRACK_OUTCOME, cand_offsets (nq + 1,), arr_offsets (nq + 1,)) of the last track_goals."""
+        nq, nc, ns = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.rrtx_get_goal_track(self._h, None, None, None, 0, C.byref(nq), C.byref(nc), C.byref(ns)),
+                  "rrtx_get_goal_track")
+        out = np.zeros(nq.value, dtype=GOAL_TRACK_OUTCOME)
+        co, ao = np.zeros(nq.value + 1, dtype=np.int64), np.zeros(nq.value + 1, dtype=np.int64)
+        self._chk(self.L.rrtx_get_goal_track(self._h, out.ctypes.data, co.ctypes.data, ao.ctypes.data, nq.value, None, None, None),
+                  "rrtx_get_goal_track")
+        return out, co, ao
+
+    def get_goal_track_records(self, n_candidates):
+        """(candidate node indices, records as a TRACK_RECORD array) of the last track_goals, query after query."""
+        cand = np.zeros(int(n_candidates), dtype=np.int32)
+        rec = np.zeros(int(n_candidates), dtype=TRACK_RECORD)
+        self._chk(self.L.rrtx_get_goal_track_records(self._h, cand.ctypes.data, rec.ctypes.data, int(n_candidates)),
+                  "rrtx_get_goal_track_records")
+        return cand, rec
+
+    def get_goal_track_arrays(self, n_steps):
+        """x, y, yaw, v, t, a, d of the last track_goals, n_steps doubles each (a query's len + 1 entries at its arr_offset)."""
+        arr = [np.full(int(n_steps), np.nan, dtype=np.float64) for _ in range(7)]
+        self._chk(self.L.rrtx_get_goal_track_arrays(self._h, *[q.ctypes.data for q in arr], int(n_steps)),
+                  "rrtx_get_goal_track_arrays")
+        return arr
+
+    def get_goal_track_kernel_ms(self):
+        a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._chk(self.L.rrtx_get_goal_track_kernel_ms(self._h, C.byref(a), C.byref(b), C.byref(c)), "rrtx_get_goal_track_kernel_ms")
+        return a.value, b.value, c.value
 
     def get_goal_query_kernel_ms(self):
         s, g = C.c_double(), C.c_double()

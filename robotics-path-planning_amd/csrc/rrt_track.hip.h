@@ -20,7 +20,8 @@
 //
 // track_courses_kernel is the same roll-out on courses given as data (rrtx_tracker_run, BatchTrack): its front end reads a
 // course from the caller's CSR arrays instead of walking a tree; everything behind the laid-out course is roll_course, one
-// text for both kernels.
+// text for both kernels.  The tree front end itself (the parent walk and the copy of the polylines) is lay_course, which
+// goal_roll_kernel (goal_track.hip.h: the same stage for many goals per tree) calls as well.
 //
 // Capacities: a course (with its extension) of up to LDS_PTS points is held in LDS (x, y; the speed profile always is, one
 // byte per point), up to SLAB_PTS points in the wave's global slab; a longer one sets RRTX_ST_OVERFLOW for the instance.
@@ -204,6 +205,47 @@ __device__ __forceinline__ void roll_course(double* cx, double* cy, double* gcw,
   }
 }
 
+// The course of one candidate node in driving order (generate_final_course :1199-1207 reversed): the start pose, the
+// polylines root -> node, the goal pose; shared by track_roll_kernel and goal_roll_kernel (goal_track.hip.h).  Called by the
+// whole wave.  Returns the number of points and sets r.ood (3: more than the slab holds, 2: fewer than 3 points, cy[-3]
+// :1435 raises IndexError); with r.ood == 0 the points are written (not yet synchronised) to cx / cy -- on entry the slab's
+// columns, switched here to the LDS columns lcx / lcy when the extended course fits them -- and the yaws to gcw.
+__device__ __forceinline__ int lay_course(const int32_t* parent, const int64_t* poff, const int32_t* plen, int64_t off, int stride,
+                                          const double* px, const double* py, const double* pw, int node, const double* start,
+                                          double gx, double gy, double gyaw, double* lcx, double* lcy, double* gcw, double*& cx,
+                                          double*& cy, Record& r) {
+  const int lane = threadIdx.x;
+  int total = 2, depth = 0;
+  for (int nd = node; parent[off + nd] >= 0 && depth <= stride; nd = parent[off + nd], depth++) total += plen[off + nd];
+  if (total + EXT_MAX > SLAB_PTS || depth > stride) r.ood = 3;
+  if (total < 3) r.ood = 2;   // cy[-3] :1435 raises IndexError
+  if (r.ood) return total;
+  if (total + EXT_MAX <= LDS_PTS) {
+    cx = lcx;
+    cy = lcy;
+  }
+  int end = total - 1;
+  for (int nd = node; parent[off + nd] >= 0; nd = parent[off + nd]) {
+    const int pl = plen[off + nd];
+    const int64_t po = poff[off + nd];
+    end -= pl;
+    for (int q = lane; q < pl; q += TPB) {
+      cx[end + q] = px[po + q];
+      cy[end + q] = py[po + q];
+      gcw[end + q] = pw[po + q];
+    }
+  }
+  if (lane == 0) {
+    cx[0] = start[0];
+    cy[0] = start[1];
+    gcw[0] = start[2];
+    cx[total - 1] = gx;
+    cy[total - 1] = gy;
+    gcw[total - 1] = gyaw;
+  }
+  return total;
+}
+
 // store = 0: jobs are (instance, candidate), counters[0] of them, records written; store = 1: jobs are the winners
 // (counters[2] of them), arrays written
 __global__ __launch_bounds__(TPB) void track_roll_kernel(TrackArgs a, int store) {
@@ -227,40 +269,11 @@ __global__ __launch_bounds__(TPB) void track_roll_kernel(TrackArgs a, int store)
     const rppk::Inst* I = a.inst + inst;
     const int node = a.cand[off + k];
     Record r = {0, 0, 0, 0, 0.0};
-    // ---- the course in driving order: start, the polylines root -> candidate, goal (generate_final_course reversed)
-    int total = 2, depth = 0;
-    for (int nd = node; a.parent[off + nd] >= 0 && depth <= (int)a.stride; nd = a.parent[off + nd], depth++) total += a.plen[off + nd];
-    if (total + EXT_MAX > SLAB_PTS || depth > (int)a.stride) r.ood = 3;
-    if (total < 3) r.ood = 2;   // cy[-3] :1435 raises IndexError
+    const double gx = I->goal[0], gy = I->goal[1], gyaw = I->goal[2];
+    double *cx = gcx, *cy = gcy;
+    const int total = lay_course(a.parent, a.poff, a.plen, off, (int)a.stride, a.pool[3 * inst], a.pool[3 * inst + 1], a.pool[3 * inst + 2],
+                                 node, I->start, gx, gy, gyaw, lcx, lcy, gcw, cx, cy, r);
     if (!r.ood) {
-      double *cx = gcx, *cy = gcy;
-      if (total + EXT_MAX <= LDS_PTS) {
-        cx = lcx;
-        cy = lcy;
-      }
-      const double* px = a.pool[3 * inst];
-      const double* py = a.pool[3 * inst + 1];
-      const double* pw = a.pool[3 * inst + 2];
-      int end = total - 1;
-      for (int nd = node; a.parent[off + nd] >= 0; nd = a.parent[off + nd]) {
-        const int pl = a.plen[off + nd];
-        const int64_t po = a.poff[off + nd];
-        end -= pl;
-        for (int q = lane; q < pl; q += TPB) {
-          cx[end + q] = px[po + q];
-          cy[end + q] = py[po + q];
-          gcw[end + q] = pw[po + q];
-        }
-      }
-      if (lane == 0) {
-        cx[0] = I->start[0];
-        cy[0] = I->start[1];
-        gcw[0] = I->start[2];
-        cx[total - 1] = I->goal[0];
-        cy[total - 1] = I->goal[1];
-        gcw[total - 1] = I->goal[2];
-      }
-      const double gx = I->goal[0], gy = I->goal[1], gyaw = I->goal[2];
       const int m = I->obs_m;
       double obx = 0.0, oby = 0.0, obt = -1.0;
       if (lane < m) {

@@ -26,6 +26,7 @@
 #include "rrt_track.hip.h"
 #include "course_gather.hip.h"
 #include "goal_query.hip.h"
+#include "goal_track.hip.h"
 #include "steer_batch.hip.h"
 #include "spline_batch.hip.h"
 #include "bspline_batch.hip.h"
@@ -41,6 +42,7 @@ using rppk::Result;
 static_assert(sizeof(rppt::Params) == sizeof(rrtx_track_params), "rrtx_track_params mirrors rppt::Params");
 static_assert(sizeof(rppt::Outcome) == sizeof(rrtx_track_outcome), "rrtx_track_outcome mirrors rppt::Outcome");
 static_assert(sizeof(rppt::Record) == sizeof(rrtx_track_record), "rrtx_track_record mirrors rppt::Record");
+static_assert(sizeof(rppgt::Outcome) == sizeof(rrtx_goal_track_outcome), "rrtx_goal_track_outcome mirrors rppgt::Outcome");
 
 struct rrtx_handle : DevObj {
   rrtx_params p;
@@ -157,6 +159,17 @@ struct rrtx_handle : DevObj {
     std::vector<int64_t> h_off;
     double solve_ms = 0.0, gather_ms = 0.0;
   } gq;
+  // the last rrtx_track_goals on the current plan (goal_track.hip.h): buffers of its own, neither tk's nor gq's; they grow and
+  // never shrink
+  struct GoalTrack {
+    DevBuf goals, count, cand_off, cand, job_query, rec, counters, win_query, slab, outc, out, arr_off, pool;
+    bool valid = false, has_arrays = false;
+    int n_goals = 0;
+    int64_t n_cand = 0, n_steps = 0;
+    std::vector<rppgt::Outcome> h_outc;
+    std::vector<int64_t> h_cand_off, h_arr_off;
+    double list_ms = 0.0, roll_ms = 0.0, store_ms = 0.0;
+  } gt;
 };
 
 template <class T>
@@ -780,6 +793,7 @@ int rrtx_plan_begin(rrtx_handle* h) {
   h->tk.valid = false;     // the same for the tracked trajectories
   h->cs.valid = false;     // and for the gathered courses (rrtx_gather_courses)
   h->gq.valid = false;     // and for the goal queries asked of the previous plan's trees (rrtx_query_goals)
+  h->gt.valid = false;     // and for the closed-loop answers to many goals (rrtx_track_goals)
   h->traced_inst = -1;     // rrtx_get_trace: nothing recorded until this plan completes
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipDeviceSynchronize());   // uploads made through the null stream (obstacles, tables) are complete
@@ -1807,6 +1821,7 @@ int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps) {
 #include "rrtx_api_bspline.inc"
 #include "rrtx_api_courses.inc"
 #include "rrtx_api_goalq.inc"
+#include "rrtx_api_goaltrack.inc"
 #include "rrtx_api_tracker.inc"   // after the four producers: rrtx_tracker_run_from reads their objects
 #include "rrtx_api_armnav.inc"
 #include "rrtx_api_armik.inc"

@@ -978,6 +978,69 @@ class GoalQueryResult:
         return self.offsets, self.x, self.y
 
 
+class GoalTrackResult:
+    """What BatchPlanner.track_goals returns: for instance i and goal j what the tail of rrt_10's planning() returns on i's
+    planned tree with `end` set to goal j.  flag, winner, node, n_cand, len, t_last, status and no_tree are (n, g): whether a
+    feasible roll-out exists, the winner's position in the query's candidate list and its node (-1 none), the number of
+    candidates, len(t) and t[-1] of the winner (0 and +inf without one), the RRTX_ST_* bits of a refused candidate (such a
+    query has no winner) and whether the instance's tree did not finish.
+    The candidates of the n * g queries (row major) are one CSR table: query q = i * g + j owns rows cand_offsets[q] ..
+    cand_offsets[q + 1] - 1 of cand_node, cand_find, cand_len, cand_fail, cand_ood and cand_t_last (what
+    check_tracking_path_is_feasible returned per candidate, _abi.TRACK_RECORD's columns).
+    With arrays, a flagged query owns len + 1 entries at arr_offsets[q] of the flat x, y, yaw, v, t, a, d: x, y, yaw fill them
+    (the goal pose last), v, t, a, d fill len and leave the last NaN; without, arr_offsets and the seven are None.
+    kernel_ms: HIP-event times (list, roll + pick, store) of the launches (sharded planners: the slowest handle's).
+    partial: some query carries a status (rrtx_track_goals returned RRTX_PARTIAL)."""
+    ARRAYS = ("x", "y", "yaw", "v", "t", "a", "d")
+
+    def __init__(self, outcomes, shape, cand_offsets, cand_node, records, arr_offsets=None, arrays=None, kernel_ms=(0.0, 0.0, 0.0)):
+        for k in ("flag", "winner", "node", "n_cand", "len", "t_last", "status", "no_tree"):
+            setattr(self, k, np.ascontiguousarray(outcomes[k]).reshape(shape))
+        self.flag = self.flag.astype(bool)
+        self.no_tree = self.no_tree.astype(bool)
+        self.cand_offsets = np.ascontiguousarray(cand_offsets, dtype=np.int64)
+        self.cand_node = cand_node
+        self.cand_find, self.cand_len, self.cand_fail, self.cand_ood, self.cand_t_last = (
+            np.ascontiguousarray(records[k]) for k in ("find_goal", "len", "fail", "ood", "t_last"))
+        self._records = records
+        self.arr_offsets = None if arr_offsets is None else np.ascontiguousarray(arr_offsets, dtype=np.int64)
+        for k, name in enumerate(self.ARRAYS):
+            setattr(self, name, None if arrays is None else arrays[k])
+        self.kernel_ms = kernel_ms
+        self.partial = bool(np.any(self.status != 0))
+
+    @property
+    def shape(self):
+        return self.flag.shape
+
+    def _query(self, i, j):
+        n, g = self.flag.shape
+        if not (-n <= i < n and -g <= j < g):
+            raise IndexError((i, j))
+        return (i % n) * g + (j % g)
+
+    def trajectory(self, i, j):
+        """(x, y, yaw, v, t, a, d) of the best feasible roll-out of instance i towards goal j (x, y, yaw one longer: the goal
+        pose is appended, rrt_10:1519-1521), or None where the reference returns (False, None, ...)."""
+        if self.arr_offsets is None:
+            raise ValueError("GoalTrackResult.trajectory: made with arrays=False, the arrays were not stored")
+        q = self._query(i, j)
+        if not self.flag.reshape(-1)[q]:
+            return None
+        a, b = int(self.arr_offsets[q]), int(self.arr_offsets[q + 1])
+        return tuple(getattr(self, name)[a:b if k < 3 else b - 1] for k, name in enumerate(self.ARRAYS))
+
+    def records(self, i, j):
+        """(candidate node indices, records as a TRACK_RECORD array) of query (i, j), in candidate order."""
+        q = self._query(i, j)
+        a, b = int(self.cand_offsets[q]), int(self.cand_offsets[q + 1])
+        return self.cand_node[a:b], self._records[a:b]
+
+    def best_goal(self):
+        """Per instance the first goal with the smallest t_last among the flagged ones, -1 if none."""
+        return np.where(self.flag.any(axis=1), np.argmin(np.where(self.flag, self.t_last, np.inf), axis=1), -1)
+
+
 class BatchPlanner:
     """Many independent planning instances (seeds / start-goal pairs) on one GPU or sharded over several.
 
@@ -1254,6 +1317,68 @@ class BatchPlanner:
         self.tracked = True
         return np.array([self._loc(i)[0].get_track_outcome(self._loc(i)[1])["flag"] for i in range(len(self.seeds))],
                         dtype=bool)
+
+    def track_goals(self, goals, arrays=True, **kw):
+        """"closed_loop_rrt_star" only, after plan(): the closed-loop stage of rrt_10 for MANY goals, read off the planned
+        trees on the device (rrtx_track_goals) -- for instance i and goal g what get_goal_indexes() +
+        search_best_feasible_path() (:1488-1493) return on i's finished node_list with `end` set to g.  Nothing of the plan
+        changes, nor do the answers of track().
+        goals: (g, 2 | 3) shared by all instances, or (n, g, 2 | 3); a missing yaw is the planner's goal yaw.  arrays=False:
+        records and outcomes only.  Keywords and defaults: those of track() (_abi.TRACK_DEFAULTS); xy_th / yaw_th select the
+        candidates.  Returns a GoalTrackResult."""
+        if not self.closed_loop:
+            raise ValueError("BatchPlanner.track_goals: only for algo=\"closed_loop_rrt_star\"")
+        for k in kw:
+            if k not in _abi.TRACK_DEFAULTS:
+                raise TypeError("BatchPlanner.track_goals: unknown keyword %r" % k)
+        n = len(self.seeds)
+        table, per_instance = goal_query_table(goals, n, True, self.handles[0].params.goal[2])
+        parts = [None] * len(self.handles)
+
+        def run(k, h, lo, hi):
+            h.track_goals(table[lo:hi] if per_instance else table, per_instance, arrays=arrays, **kw)
+            out, co, ao = h.get_goal_track()
+            cand, rec = h.get_goal_track_records(int(co[-1]))
+            arr = h.get_goal_track_arrays(int(ao[-1])) if arrays else None
+            parts[k] = (out, co, ao, cand, rec, arr, h.get_goal_track_kernel_ms())
+        if len(self.handles) == 1:
+            run(0, self.handles[0], *self.shards[0])
+        else:   # one host thread per shard, as track()
+            import threading
+            errs = []
+
+            def guarded(*a):
+                try:
+                    run(*a)
+                except Exception as e:   # noqa: BLE001 -- re-raised below on the calling thread
+                    errs.append(e)
+            th = [threading.Thread(target=guarded, args=(k, h, lo, hi)) for k, (h, (lo, hi)) in enumerate(zip(self.handles, self.shards))]
+            for t in th:
+                t.start()
+            for t in th:
+                t.join()
+            if errs:
+                raise errs[0]
+        out = np.concatenate([p[0] for p in parts])
+        cand, rec = np.concatenate([p[3] for p in parts]), np.concatenate([p[4] for p in parts])
+        co, ao, cb, ab = [np.zeros(1, dtype=np.int64)], [np.zeros(1, dtype=np.int64)], 0, 0
+        for p in parts:
+            co.append(p[1][1:] + cb)
+            ao.append(p[2][1:] + ab)
+            cb += int(p[1][-1])
+            ab += int(p[2][-1])
+        ms = tuple(max(p[6][k] for p in parts) for k in range(3))
+        shape = (n, table.shape[-2])
+        if not arrays:
+            return GoalTrackResult(out, shape, np.concatenate(co), cand, rec, kernel_ms=ms)
+        arr = [np.concatenate([p[5][k] for p in parts]) for k in range(7)]
+        return GoalTrackResult(out, shape, np.concatenate(co), cand, rec, np.concatenate(ao), arr, ms)
+
+    def polyline_yaw(self, i):
+        """The pose planners on Reeds-Shepp edges: Node.path_yaw of every node of instance i, concatenated as polylines(i)
+        concatenates path_x / path_y."""
+        h, j = self._loc(i)
+        return h.get_polyline_yaw(j)
 
     def trajectory(self, i):
         """(x, y, yaw, v, t, a, d) of instance i's best feasible roll-out (x, y, yaw one longer: the goal pose is

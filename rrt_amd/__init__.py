@@ -45,6 +45,7 @@ informed_rotation = _pkg.informed_rotation
 BatchPlanner = _pkg.BatchPlanner
 PlannerCourses = _pkg.PlannerCourses
 GoalQueryResult = _pkg.GoalQueryResult
+GoalTrackResult = _pkg.GoalTrackResult
 BatchSteer = _pkg.BatchSteer
 SteerCandidates = _pkg.SteerCandidates
 BatchTrack = _pkg.BatchTrack
