@@ -23,9 +23,48 @@ class Params(C.Structure):
                 ("connect_circle_dist", C.c_double)]
 
 
+# call sites of a collision test, in the order of rrt_oracle.c's ORC_SITE_*
+GRAZE_SITES = ("ext_short", "ext_long", "choose_parent", "rewire", "goal")
+# columns of an edge-log row (rrt_oracle.c elog_row)
+EDGE_LOG_COLS = ("site", "iteration", "fx", "fy", "tx", "ty", "extend", "points", "free", "grazing")
+
+
 class Stats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("edges_ref", "edges_unique", "near_hits", "near_unique", "rewires",
-                                         "propagated", "iterations", "scan_nodes", "pow_slow", "sobol_index")]
+                                         "propagated", "iterations", "scan_nodes", "pow_slow", "sobol_index")
+                + tuple("graze_%s_%s" % (k, s) for k in ("in", "out", "exact") for s in GRAZE_SITES)]
+
+
+class _Graze:
+    """`with _Graze(graze, edge_log) as g:` around one oracle call: switches the grazing-pair counters (and the edge log)
+    of rrt_oracle.c on for that call alone; g.rows() is the log afterwards."""
+
+    def __init__(self, graze, edge_log, max_iter):
+        self.on = bool(graze or edge_log)
+        self.buf = np.zeros((64 * (int(max_iter) + 8), len(EDGE_LOG_COLS))) if edge_log else None
+
+    def __enter__(self):
+        if self.on:
+            L = lib()
+            L.orc_graze_config.argtypes = [C.c_int, C.c_void_p, C.c_int64]
+            L.orc_graze_config.restype = None
+            L.orc_edge_log_rows.restype = C.c_int64
+            L.orc_graze_config(1, self.buf.ctypes.data if self.buf is not None else None,
+                               len(self.buf) if self.buf is not None else 0)
+        return self
+
+    def __exit__(self, *exc):
+        if self.on:
+            self.n = int(lib().orc_edge_log_rows())
+            lib().orc_graze_config(0, None, 0)
+        return False
+
+    def rows(self):
+        if self.buf is None:
+            return None
+        if self.n > len(self.buf):
+            raise RuntimeError("edge log overflow: %d rows" % self.n)
+        return self.buf[:self.n].copy()
 
 
 class MT(C.Structure):
@@ -74,8 +113,10 @@ def mt_from_pystate(state):
 
 def plan(algo="rrt_star", start=(0, 0), goal=(6, 10), obstacles=(), rand_area=(-2, 15), expand_dis=3.0,
          path_resolution=0.5, goal_sample_rate=5, max_iter=500, play_area=None, robot_radius=0.0, sobol=False,
-         connect_circle_dist=50.0, search_until_max_iter=False, seed=None, rng=None, exact_pow=True, trace=False):
-    """Run one planning() call on the oracle; returns dict(x,y,cost,parent,path,stats,rng,trace...)."""
+         connect_circle_dist=50.0, search_until_max_iter=False, seed=None, rng=None, exact_pow=True, trace=False,
+         graze=False, edge_log=False):
+    """Run one planning() call on the oracle; returns dict(x,y,cost,parent,path,stats,rng,trace...).  graze: fill the
+    graze_* counters of stats (zero otherwise); edge_log: also return `edges`, one EDGE_LOG_COLS row per collision test."""
     L = lib()
     p = Params()
     p.algo = {"rrt": 0, "rrt_star": 1}[algo]
@@ -110,14 +151,17 @@ def plan(algo="rrt_star", start=(0, 0), goal=(6, 10), obstacles=(), rand_area=(-
         o.tr_rnd_x, o.tr_rnd_y, o.tr_nearest, o.tr_n_near = trx.ctypes.data, try_.ctypes.data, trn.ctypes.data, trk.ctypes.data
         o.tr_cap = int(max_iter)
     st = Stats()
-    rc = L.orc_plan(C.byref(p), obst.ctypes.data_as(C.c_void_p), C.c_int(len(obst)), C.byref(rng), C.byref(o),
-                    C.byref(st))
+    with _Graze(graze, edge_log, max_iter * 8) as gz:
+        rc = L.orc_plan(C.byref(p), obst.ctypes.data_as(C.c_void_p), C.c_int(len(obst)), C.byref(rng), C.byref(o),
+                        C.byref(st))
     if rc != 0:
         raise RuntimeError("orc_plan failed: %d" % rc)
     n = o.n
     res = dict(x=x[:n].copy(), y=y[:n].copy(), cost=cost[:n].copy(), parent=parent[:n].copy(),
                path=path[:o.path_n].copy() if o.path_n else None,
                stats={k: getattr(st, k) for k, _ in Stats._fields_}, rng=rng)
+    if edge_log:
+        res["edges"] = gz.rows()
     if trace:
         t = o.tr_n
         res.update(tr_rnd_x=trx[:t].copy(), tr_rnd_y=try_[:t].copy(), tr_nearest=trn[:t].copy(), tr_n_near=trk[:t].copy())
@@ -136,8 +180,8 @@ def rotation_to_world(start, goal):
 
 
 def plan_informed(start, goal, obstacles, rand_area, expand_dis=0.5, goal_sample_rate=10, max_iter=200, sobol=False,
-                  seed=None, rng=None, exact_pow=True, trace=False, rot_c=None):
-    """One RRT.informed_rrt_star_search() call of rrt_07 on the oracle."""
+                  seed=None, rng=None, exact_pow=True, trace=False, rot_c=None, graze=False, edge_log=False):
+    """One RRT.informed_rrt_star_search() call of rrt_07 on the oracle (graze, edge_log: as in plan())."""
     L = lib()
     L.orc_plan_informed.restype = C.c_int
     p = Params()
@@ -168,14 +212,17 @@ def plan_informed(start, goal, obstacles, rand_area, expand_dis=0.5, goal_sample
         o.tr_cap = int(max_iter)
     st = Stats()
     cb = C.c_double()
-    rc = L.orc_plan_informed(C.byref(p), obst.ctypes.data_as(C.c_void_p), C.c_int(len(obst)),
-                             rc_.ctypes.data_as(C.c_void_p), C.byref(rng), C.byref(o), C.byref(st), C.byref(cb))
+    with _Graze(graze, edge_log, max_iter * 8) as gz:
+        rc = L.orc_plan_informed(C.byref(p), obst.ctypes.data_as(C.c_void_p), C.c_int(len(obst)),
+                                 rc_.ctypes.data_as(C.c_void_p), C.byref(rng), C.byref(o), C.byref(st), C.byref(cb))
     if rc != 0:
         raise RuntimeError("orc_plan_informed failed: %d" % rc)
     n = o.n
     res = dict(x=x[:n].copy(), y=y[:n].copy(), cost=cost[:n].copy(), parent=parent[:n].copy(),
                path=path[:o.path_n].copy() if o.path_n else None, c_best=cb.value,
                stats={k: getattr(st, k) for k, _ in Stats._fields_}, rng=rng)
+    if edge_log:
+        res["edges"] = gz.rows()
     if trace:
         t = o.tr_n
         res.update(tr_rnd_x=trx[:t].copy(), tr_rnd_y=try_[:t].copy(), tr_nearest=trn[:t].copy(), tr_n_near=trk[:t].copy())
