@@ -1211,7 +1211,11 @@ int rrtx_armdh_get_kernel_ms(rrtx_armdh* a, double* kernel_ms, int32_t* waves);
 
 /* parity harness: out[i] = op(a[i], b[i]) evaluated on the device.  op 0 math.hypot, 1 x**2, 2 sin, 3 cos, 4 atan2,
  * 5 steer end x (rrt_04:1086-1115), 6 sqrt, 7 a/b, 8 acos, 9 asin, 10 checksum of the Reeds-Shepp steer
- * (0,0,0) -> (a, b, a+b) (rrt_06:1426-1441, csrc/rpp_rs.h), 11 math.tan(a) (|a| <= 0.79), 12 np.hypot(a, b) */
+ * (0,0,0) -> (a, b, a+b) (rrt_06:1426-1441, csrc/rpp_rs.h), 11 math.tan(a) (|a| <= 0.79), 12 np.hypot(a, b).
+ * op 13: the cross-lane integer helpers of the one-wave RRT* kernel (csrc/rrt_star_v2_shapes.inc), each 64-lane group of
+ * the input by itself: a[i] a uint32 value, b[i] an int32 index, n a multiple of 64, and out holds 5 n doubles:
+ * out[i] the inclusive prefix sum of a over the group (mod 2^32, as int32), out[n + i] the group's total, out[2 n + i] and
+ * out[3 n + i] value and index of the argmin of (a, b) with the lowest index among equal values, out[4 n + i] min(a). */
 int rrtx_selftest_math(int32_t device, int32_t op, const double* a, const double* b, double* out, int64_t n);
 
 /* Run-time check of the arithmetic contract: "identical to the reference on this host" holds while

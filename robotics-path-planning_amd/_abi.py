@@ -1581,7 +1581,7 @@ def selftest_math(op, a, b, device=0):
     L = load()
     a = np.ascontiguousarray(a, dtype=np.float64)
     b = np.ascontiguousarray(b, dtype=np.float64)
-    out = np.zeros_like(a)
+    out = np.zeros((5,) + a.shape if op == 13 else a.shape, dtype=np.float64)   # op 13: five results per element (rrtx.h)
     rc = L.rrtx_selftest_math(device, op, a.ctypes.data, b.ctypes.data, out.ctypes.data, a.size)
     if rc != 0:
         raise RrtxError("rrtx_selftest_math: %s" % ERRORS.get(rc, rc))

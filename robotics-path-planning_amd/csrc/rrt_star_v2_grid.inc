@@ -176,19 +176,10 @@ __device__ __forceinline__ int grid_tests(const GridS& g, uint32_t cq, int D, bo
       s = min(s, d[k]);
     }
   }
-  uint32_t wb = b;
-  int wi = bi;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint32_t ob = (uint32_t)__shfl_xor((int)wb, o);
-    const int oi = __shfl_xor(wi, o);
-    const bool take = ob < wb || (ob == wb && oi < wi);
-    wb = take ? ob : wb;
-    wi = take ? oi : wi;
-  }
-  uint32_t ws = bi == wi ? s : b;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) ws = min(ws, (uint32_t)__shfl_xor((int)ws, o));
+  uint32_t wb;
+  int wi;
+  wave_argmin(b, bi, wb, wi);
+  uint32_t ws = wave_umin(bi == wi ? s : b);
   // the left-out duplicates tie with first_goal (in the index, lower index): a runner-up at the goal's distance
   if (g.excl > 0) ws = min(ws, qdist(g.goal_q, cq));
   wbest = wb;
@@ -230,9 +221,13 @@ __device__ __forceinline__ bool grid_centre(const GridS& g, uint32_t cq, int rw,
                                             int gz, int& cnt, int& zcnt, uint32_t& best, uint32_t& second, int& grp,
                                             int& bytes, int& nodes, int first_attempt = 0) {
   const int lane = threadIdx.x & 63;
+  cq = uni_u(cq);
+  thr = uni_u(thr);
   for (int attempt = first_attempt; attempt < 3; attempt++) {
     int x0, y0, nwx, nc, D;
+    rw = uni_i(rw);
     if (!grid_window(g, cq, rw, x0, y0, nwx, nc, D)) return false;
+    D = uni_i(D);
     int cell = 0, cn = 0, cb = 0;
     if (lane < nc) {
       cell = (y0 + lane / nwx) * g.gn + x0 + lane % nwx;
@@ -241,13 +236,8 @@ __device__ __forceinline__ bool grid_centre(const GridS& g, uint32_t cq, int rw,
       cb = hd.blk;
     }
     if (__ballot(cn > GRID_CAPT) != 0ull) return false;
-    int inc = cn;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o);
-      if (lane >= o) inc += t;
-    }
-    const int tot = __shfl(inc, 63);
+    const int inc = wave_prefix_sum(cn);
+    const int tot = wave_total(inc);
     bytes += 8 * nc + 8 * tot;
     nodes += tot;
     if (tot > 64 * GE) return false;
@@ -316,6 +306,7 @@ __device__ __forceinline__ int grid_merged(const GridS& g, GCen (&ce)[NC], int32
     if (!ce[c].on) continue;
     int x0, y0, nwx, nc;
     if (!grid_window(g, ce[c].cq, ce[c].rw, x0, y0, nwx, nc, D[c])) return -1;
+    D[c] = uni_i(D[c]);
     const int l = lane - npairs;
     if (l >= 0 && l < nc) {
       cid = c;
@@ -330,13 +321,8 @@ __device__ __forceinline__ int grid_merged(const GridS& g, GCen (&ce)[NC], int32
     cb = hd.blk;
   }
   if (__ballot(cn > GRID_CAPT) != 0ull) return 0;
-  int inc = cn;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  const int tot = __shfl(inc, 63);
+  const int inc = wave_prefix_sum(cn);
+  const int tot = wave_total(inc);
   if (tot > 64 * GE) return -1;
   bytes += 8 * npairs + 8 * tot;
   nodes += tot;
@@ -404,6 +390,12 @@ __device__ __forceinline__ bool grid_pass(GridS& g, int rwn, uint32_t qq, uint32
   int32_t* lhit = reinterpret_cast<int32_t*>(sh.u.hit);
   int32_t* ltmp = lhit + HWF;
   static_assert(sizeof(sh.u) >= sizeof(int32_t) * (HWF + 64 * GE), "LDS scratch of a grid pass");
+  // the pass's own centres, threshold and window are wave-uniform: as scalars they are operands of every qdist and
+  // compare below, not registers that live (or go to scratch) across the centres
+  qq = uni_u(qq);
+  thr = uni_u(thr);
+  sq = uni_u(sq);
+  rwn = uni_i(rwn);
   int bytes = 0, nodes = 0;
   uint32_t b, s;
   int gr, zc = 0, cnt = 0;

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   const double qm = c.q_m;
   const double qinv = c.q_inv;   // world -> grid units of the 16-bit mirror
   const double qm_grid = c.q_m * c.q_inv;
-  const uint32_t goal_q = rppk::quant16(c, I->goal[0], I->goal[1]);   // the goal's grid cell
+  const uint32_t goal_q = uni_u(rppk::quant16(c, I->goal[0], I->goal[1]));   // the goal's grid cell (a scalar: every qdist and compare takes it as an operand)
   int q_amb = 0;            // the fused 16-bit pass could not decide the pending nearest query ...
   uint32_t q_amb_bq = 0u;   // ... and this bounds the nearest node's squared grid distance (candidate pass, below)
   int first_goal = I->first_goal;
@@ -156,8 +156,11 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // in L2 before a scalar load of another wave asks for them
     lds_barrier();
   }
-  if (tid == 0)
+  if (tid == 0) {
     for (int k = 0; k < 15; k++) sh.stat[k] = 0;
+    sh.b_n = 0;
+    sh.b_thr = 0u;
+  }
   int have_nearest = 0, ni = 0;
   double gbest = 0.0, gsecond = 0.0, nqx = 0.0, nqy = 0.0;   // nearest node of the current sample (block-uniform)
   int stop = 0;
@@ -189,8 +192,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
   static_assert(KSM <= 3, "rings of four");
   int ns = 0, shead = 0;                               // query sets not yet used
   int na = 0;                                          // nodes appended since the pass: indices B_n .. B_n + na - 1
-  int B_n = 0;                                         // tree size the pass scanned
-  uint32_t B_thr = 0u;
+  // the tree size the pass scanned and the balls' threshold: Sh2::b_n / b_thr (lane 0 writes at the pass, read where used)
   // Nearest node of the next iteration's sample: the pass's answer (set record at shead) over [0, B_n) + the na nodes
   // appended since (indices B_n ..; the lowest index wins among equals, :1200).  margin_fold with the nearest of
   // the new nodes.  Returns 1 with the node in (ni, nqx, nqy), 2 when the 16-bit stage cannot
@@ -200,6 +202,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
     double s2x, s2y;
     sload_sample(S, it + 1, s2x, s2y);
     const double nb = R[2], nsec = R[3], grpd = R[6], bqd = R[7];
+    const int B_n = uni_i(sh.b_n);
     double axv[4], ayv[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -458,6 +461,8 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
         // the nodes appended since that pass join the ball by the pass's own grid test, in index order
         int k2 = spec_k0;
         const int off0 = spec_off0;
+        const int B_n = uni_i(sh.b_n);
+        const uint32_t B_thr = uni_u(sh.b_thr);
         const uint32_t cq = rppk::quant16(c, nx, ny);
         double axv[KA], ayv[KA];
 #pragma unroll
@@ -486,14 +491,14 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       } else {
         ns = 0;
         na = 0;
-        const uint32_t thr_gi = ball_thr_grid(r2, qm, qinv);
+        const uint32_t thr_gi = uni1_u(ball_thr_grid(r2, qm, qinv));
         const int rw_gi = (int)__builtin_sqrt((double)thr_gi) + 1;   // its window half-width (grid index)
         if (do_pf) {
           sload_sample(S, it + 1, p1x, p1y);
           pf_goal = on_goal(first_goal, gx, gy, p1x, p1y);
         }
         if (do_pf && !pf_goal) {
-          pf_sq = rppk::quant16(c, p1x, p1y);
+          pf_sq = uni1_u(rppk::quant16(c, p1x, p1y));
           // further query sets: the following iterations' balls about their samples, up to the first that reaches the
           // goal's grid cell (or the end of this launch)
           int kmax = 0;
@@ -505,7 +510,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
           if constexpr (NW == 1 && KSM > 0) {
             uint32_t thr2 = 0u;
             if (kmax > 0) {
-              thr2 = ball_thr_grid(r2b, qm, qinv);
+              thr2 = uni_u(ball_thr_grid(r2b, qm, qinv));
               if (uni_i(qdist(goal_q, pf_sq) <= thr2)) kmax = 0;
             }
             if (kmax > 0) {
@@ -529,9 +534,9 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
               for (int j = 0; j < KA; j++) {
                 const bool on = j < ks;
                 const double cxj = j == 0 ? p1x : qxv[j > 0 ? j - 1 : 0], cyj = j == 0 ? p1y : qyv[j > 0 ? j - 1 : 0];
-                sp[j].qq = on ? rppk::quant16(c, cxj, cyj) : pf_sq;
+                sp[j].qq = uni_u(on ? rppk::quant16(c, cxj, cyj) : pf_sq);   // wave-uniform: scalars (the pass reads them as operands)
                 sp[j].thr = on ? thr2 : 0u;    // unused set: radius 0 about a centre whose hits nobody reads
-                sp[j].sq = rppk::quant16(c, on ? qxv[j] : p1x, on ? qyv[j] : p1y);
+                sp[j].sq = uni_u(rppk::quant16(c, on ? qxv[j] : p1x, on ? qyv[j] : p1y));
                 sp[j].off = spec_base + j * SPEC_CAPS;
                 sp[j].cap = SPEC_CAPS;
                 if (tid == 0) {   // the record's centre now: nothing of the queue has to stay in registers over the pass
@@ -546,12 +551,12 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
               pass_b = gs.bytes;
               pass_n = gs.nodes;
               did_spec = true;
-              B_n = n;
-              B_thr = uni_u(thr2);
               ns = ks;
               shead = 0;
               na = 0;
               if (tid == 0) {
+                sh.b_n = n;
+                sh.b_thr = thr2;
                 const double qs2 = c.q_step * c.q_step;
 #pragma unroll
                 for (int j = 0; j < KA; j++) {

@@ -59,16 +59,55 @@ struct Sh2 {
   // ring of four set records; lane 0 writes, every lane reads
   double ax[4], ay[4];
   double set[4][8];
+  int32_t b_n;      // tree size the pass scanned: the nodes appended since have the indices b_n ..
+  uint32_t b_thr;   // threshold of the speculated balls (grid units)
 };
 
 __device__ __forceinline__ void lds_barrier() { __syncthreads(); }  // lowers to s_waitcnt lgkmcnt(0); s_barrier
 // a block-uniform value moved to the scalar register file (state carried across iterations must not cost VGPRs)
 __device__ __forceinline__ int uni_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ uint32_t uni_u(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+// ... in the one-wave shape only (the larger shapes' register tables are better off with the value where it is)
+__device__ __forceinline__ uint32_t uni1_u(uint32_t v) { return NW == 1 ? uni_u(v) : v; }
 __device__ __forceinline__ double uni_d(double v) {
   const uint64_t b = rpp::d2b(v);
   const uint32_t lo = uni_u((uint32_t)b), hi = uni_u((uint32_t)(b >> 32));
   return rpp::b2d(((uint64_t)hi << 32) | lo);
+}
+
+// ---- Integer operations across the 64 lanes of a wave that take no address register ------------------------------------
+// __shfl* lowers to ds_bpermute_b32, whose lane-constant byte address ((lane +- o) << 2) is one more VGPR live across
+// whatever surrounds the call: in the one-wave kernel it went to scratch and came back in front of every use (DESIGN
+// 6.0h).  A DPP operand needs none: four row shifts scan the 16 lanes of a row, two row broadcasts carry the rows' last
+// lanes on, and lane 63 then holds the reduction of the wave (v_readlane: the answer is a scalar).  Lanes that a step
+// does not reach take the operation's identity (the `old` operand).  Every lane of the wave must be active.  All of them
+// are integer operations under a total order: whatever the reduction tree, the bits are the same.
+template <class Op>
+__device__ __forceinline__ int wave_scan(int v, const int id, Op op) {
+  v = op(v, __builtin_amdgcn_update_dpp(id, v, 0x111, 0xf, 0xf, false));   // row_shr:1
+  v = op(v, __builtin_amdgcn_update_dpp(id, v, 0x112, 0xf, 0xf, false));   // row_shr:2
+  v = op(v, __builtin_amdgcn_update_dpp(id, v, 0x114, 0xf, 0xf, false));   // row_shr:4
+  v = op(v, __builtin_amdgcn_update_dpp(id, v, 0x118, 0xf, 0xf, false));   // row_shr:8
+  v = op(v, __builtin_amdgcn_update_dpp(id, v, 0x142, 0xa, 0xf, false));   // row_bcast:15 into rows 1 and 3
+  v = op(v, __builtin_amdgcn_update_dpp(id, v, 0x143, 0xc, 0xf, false));   // row_bcast:31 into rows 2 and 3
+  return v;
+}
+// inclusive prefix sum over the lanes, and the wave's total from it
+__device__ __forceinline__ int wave_prefix_sum(int v) {
+  return wave_scan(v, 0, [](int a, int b) { return a + b; });
+}
+__device__ __forceinline__ int wave_total(int inclusive) { return __builtin_amdgcn_readlane(inclusive, 63); }
+__device__ __forceinline__ uint32_t wave_umin(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_readlane(
+      wave_scan((int)v, -1, [](int a, int b) { return (int)min((uint32_t)a, (uint32_t)b); }), 63);
+}
+__device__ __forceinline__ int wave_imin(int v) {
+  return __builtin_amdgcn_readlane(wave_scan(v, 0x7fffffff, [](int a, int b) { return min(a, b); }), 63);
+}
+// argmin of (value, index): the lowest index wins among equal values
+__device__ __forceinline__ void wave_argmin(uint32_t v, int idx, uint32_t& wv, int& wi) {
+  wv = wave_umin(v);
+  wi = wave_imin(v == wv ? idx : 0x7fffffff);
 }
 
 // block-wide argmin of (value, index) with lowest-index tie break, carrying the winner's coordinates

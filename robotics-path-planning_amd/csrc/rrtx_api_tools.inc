@@ -58,24 +58,50 @@ int rrtx_smooth_paths(int32_t device, int32_t n_jobs, const double* paths_xy, co
   return smooth_status_rc(st, nullptr);
 }
 
+}  // extern "C"
+
+// op 13 of rrtx_selftest_math: one 64-thread workgroup per 64-lane group (n is a multiple of 64: every lane is active)
+__global__ __launch_bounds__(64) void selftest_wave_ops_kernel(const double* a, const double* b, double* o, int64_t n) {
+  const int64_t i = blockIdx.x * (int64_t)64 + threadIdx.x;
+  const uint32_t v = (uint32_t)a[i];
+  const int idx = (int)b[i];
+  const int inc = rppk2t::wave_prefix_sum((int)v);
+  uint32_t wv;
+  int wi;
+  rppk2t::wave_argmin(v, idx, wv, wi);
+  o[i] = (double)inc;
+  o[n + i] = (double)rppk2t::wave_total(inc);
+  o[2 * n + i] = (double)wv;
+  o[3 * n + i] = (double)wi;
+  o[4 * n + i] = (double)rppk2t::wave_umin(v);
+}
+
+extern "C" {
+
 int rrtx_selftest_math(int32_t device, int32_t op, const double* a, const double* b, double* out, int64_t n) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return RRTX_E_NO_DEVICE;
   if (!a || !b || !out || n < 0) return RRTX_E_INVALID;
+  const bool wave_ops = op == 13;
+  if (wave_ops && n % 64 != 0) return RRTX_E_INVALID;
+  const int64_t n_out = wave_ops ? 5 * n : n;
   if (hipSetDevice(device) != hipSuccess) return RRTX_E_HIP;
   double *da = nullptr, *db = nullptr, *dout = nullptr;
   int rc = RRTX_OK;
   if (hipMalloc(&da, n * 8) != hipSuccess || hipMalloc(&db, n * 8) != hipSuccess ||
-      hipMalloc(&dout, n * 8) != hipSuccess)
+      hipMalloc(&dout, n_out * 8) != hipSuccess)
     rc = RRTX_E_HIP;
   if (!rc && (hipMemcpy(da, a, n * 8, hipMemcpyHostToDevice) != hipSuccess ||
               hipMemcpy(db, b, n * 8, hipMemcpyHostToDevice) != hipSuccess))
     rc = RRTX_E_HIP;
-  if (!rc) {
+  if (!rc && wave_ops) {
+    if (n > 0) hipLaunchKernelGGL(selftest_wave_ops_kernel, dim3((unsigned)(n / 64)), dim3(64), 0, 0, da, db, dout, n);
+    if (hipDeviceSynchronize() != hipSuccess) rc = RRTX_E_HIP;
+  } else if (!rc) {
     hipLaunchKernelGGL(rppk::selftest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, da, db, dout, n);
     if (hipDeviceSynchronize() != hipSuccess) rc = RRTX_E_HIP;
   }
-  if (!rc && hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = RRTX_E_HIP;
+  if (!rc && hipMemcpy(out, dout, n_out * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = RRTX_E_HIP;
   hipFree(da);
   hipFree(db);
   hipFree(dout);
