@@ -32,7 +32,8 @@ extern "C" {
                                 rrtx_steer_get_control_points, rrtx_steer_solve_all, rrtx_steer_get_cand_counts,
                                 rrtx_steer_get_cand_summary, rrtx_steer_get_cand_points, rrtx_steer_select_free, rrtx_tracker_run_from,
                                 rrtx_tracker_get_winners, rrtx_tracker_get_goals, rrtx_*_get_generation, rrtx_gather_courses, rrtx_get_course_counts,
-                                rrtx_get_courses, rrtx_get_course_generation, RRTX_SRC_PLANNER, rrtx_query_goals and its getters); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
+                                rrtx_get_courses, rrtx_get_course_generation, RRTX_SRC_PLANNER, rrtx_query_goals and its getters,
+                                rrtx_set_obstacle_map and its getters); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
                                 rrtx_copy_results_device, per-instance yaw and informed rotation; 4: rrtx_plan_many,
                                 rrtx_selfcheck, rrtx_stats.main_shape / main_f32, rrtx_plan_begin / _step, rrtx_set_launch_bound,
                                 RRTX_ST_REF_HANGS, rrtx_rccl_* */
@@ -170,7 +171,7 @@ typedef struct rrtx_handle rrtx_handle;
  *    results (tree, path, path_yaw, yaw, polylines, copy_results_device, sobol_index, trace, trace_kind), rrtx_smooth_planned
  *    and rrtx_get_smoothed_path return RRTX_E_STATE; rrtx_get_results alone is valid between steps.
  *  - From rrtx_plan_begin until the end of that plan every setter returns RRTX_E_STATE and changes nothing:
- *    rrtx_set_obstacles, rrtx_set_instance_obstacles, rrtx_seed_instances, rrtx_set_rng_state, rrtx_set_instance,
+ *    rrtx_set_obstacles, rrtx_set_instance_obstacles, rrtx_set_obstacle_map, rrtx_seed_instances, rrtx_set_rng_state, rrtx_set_instance,
  *    rrtx_set_instance_rotation, rrtx_enable_trace, rrtx_set_launch_bound (a re-plan inside the plan restarts instances
  *    from the staged state, and device tables of the plan point into the obstacle table).
  *  - rrtx_plan_begin (and so rrtx_plan) while a plan is in progress is accepted: it abandons that plan -- no launch of it
@@ -193,6 +194,44 @@ int rrtx_set_obstacles(rrtx_handle* h, const double* oxyr, int32_t m);
  * more than 256 obstacles (RRTX_ALGO_RS: 64); RRTX_E_STATE between rrtx_plan_begin and the end of that plan.  Workgroup
  * shapes and capacities follow the largest list; rrtx_smooth_planned smooths each path against its instance's list. */
 int rrtx_set_instance_obstacles(rrtx_handle* h, const int32_t* offsets, const double* oxyr);
+/* The obstacle map: any number of circles up to 2^20 for RRTX_ALGO_RRT and RRTX_ALGO_RRT_STAR (rrt_01 / rrt_02 / rrt_04),
+ * shared by all instances.  rrtx_set_obstacles and rrtx_set_instance_obstacles keep their limits (256, RRTX_ALGO_RS 64): they
+ * stage the list in the kernels' obstacle tile.  This call builds, on the device, a uniform grid over the list instead (cells
+ * over the sampling square of rand_min / rand_max, about one circle per cell; a circle is listed in every cell its square
+ * [ox +- rho] x [oy +- rho] overlaps, rho = |size + robot_radius| rounded up, and in a "wide" list once it would cover more than
+ * 32 cells), and rrtx_plan, rrtx_plan_begin / _step and rrtx_plan_many then run a variant of the general planner kernel that
+ * refills its tile, for every group of edges, from the cells the group's bounding box covers.  The verdict of check_collision
+ * is "any circle hit", so trees, paths, results, trace, RNG state, Sobol index and the decision counters of rrtx_stats are those
+ * of a plan that tested every circle; rrtx_stats.algorithmic_bytes counts the records the gathers read, main_shape is the general
+ * kernel's.  m <= 256 is allowed.  A later rrtx_set_obstacles or rrtx_set_instance_obstacles drops the map and returns the
+ * handle to the tile; a map cannot be combined with per-instance lists.
+ * RRTX_E_INVALID (the message names which) for a NULL handle, oxyr == NULL with m > 0, m < 0 or m > 2^20, an entry that is not
+ * finite, and a handle of another algo; RRTX_E_STATE between rrtx_plan_begin and the end of that plan; all of them before any
+ * device call.  A failure leaves the handle, and the map or lists it holds, as they were.
+ * Not served while the handle holds a map (RRTX_E_STATE, the message names the map): rrtx_smooth_planned and rrtx_query_goals,
+ * which read the obstacle table.  Test knobs: RRTX_OBSMAP_CELLS (cells per axis; 1 = every box streams the whole list),
+ * RRTX_OBSMAP_TILE (records per tile, below 256). */
+int rrtx_set_obstacle_map(rrtx_handle* h, const double* oxyr, int64_t m);
+typedef struct rrtx_obstacle_map_info {
+  double x0, y0, cell;   /* origin of the grid and side of a cell */
+  int32_t nx, ny;        /* cells per axis */
+  int64_t n_circles;     /* m */
+  int64_t n_items;       /* records in the cells (a circle counts once per cell it is listed in) */
+  int64_t n_wide;        /* circles in the wide list */
+  double build_ms;       /* device time of the three build kernels */
+} rrtx_obstacle_map_info;
+/* one record of the map, 32 bytes: the circle, its threshold (size + robot_radius) ** 2 and its row in the caller's list */
+typedef struct rrtx_obstacle_item {
+  double ox, oy, thr;
+  int64_t index;
+} rrtx_obstacle_item;
+/* RRTX_E_STATE without a map */
+int rrtx_get_obstacle_map_info(rrtx_handle* h, rrtx_obstacle_map_info* info);
+/* The map as built: cell_start[nx * ny + 1] (CSR over the cells, row-major: cell = cy * nx + cx), the n_items records of the
+ * cells (a cell's records are contiguous and in ascending `index`) and the n_wide records of the wide list (ascending
+ * `index`).  Any pointer may be NULL; RRTX_E_CAPACITY when a buffer is smaller than the info says; RRTX_E_STATE without a map. */
+int rrtx_get_obstacle_map(rrtx_handle* h, int32_t* cell_start, rrtx_obstacle_item* items, int64_t cap_items,
+                          rrtx_obstacle_item* wide, int64_t cap_wide);
 /* hand over / take back CPython's `random.getstate()[1]` (624 words + position) for one instance, so that
  * the device consumes the stream exactly as random.randint / random.uniform would (rrt_04:1133-1136). */
 int rrtx_set_rng_state(rrtx_handle* h, int32_t instance, const uint32_t* mt624, int32_t pos);

@@ -59,7 +59,10 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_armik_get_records", "rrtx_armik_get_angles", "rrtx_armik_get_trajectory", "rrtx_armik_get_kernel_ms",
            "rrtx_armdh_create", "rrtx_armdh_destroy", "rrtx_armdh_last_error", "rrtx_armdh_forward", "rrtx_armdh_solve",
            "rrtx_armdh_get_records", "rrtx_armdh_get_angles", "rrtx_armdh_get_transforms", "rrtx_armdh_get_jacobians",
-           "rrtx_armdh_get_kernel_ms"]
+           "rrtx_armdh_get_kernel_ms",
+           "rrtx_set_obstacle_map", "rrtx_get_obstacle_map_info", "rrtx_get_obstacle_map"]
+OBSTACLE_TILE_MAX, OBSTACLE_MAP_MAX = 256, 1 << 20   # csrc MAX_OBS (rrtx_set_obstacles), rpp_obsgrid.h M_MAX (rrtx_set_obstacle_map)
+OBSTACLE_MAP_ALGOS = (0, 1)                          # RRTX_ALGO_RRT, RRTX_ALGO_RRT_STAR
 STEER_DUBINS, STEER_RS = 0, 1                                                      # include/rrtx.h: #define RRTX_STEER_*
 STEER_LQR = 2   # this binding's own name for "solved by rrtx_steer_solve_lqr": the C ABI has an entry point, not a kind value
 STEER_BEZIER = 3   # likewise: rrtx_steer_solve_bezier / rrtx_steer_solve_bezier_cp
@@ -239,6 +242,25 @@ class RrtxError(RuntimeError):
     pass
 
 
+class ObstacleMapInfo(C.Structure):
+    """rrtx_obstacle_map_info"""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32),
+                ("n_circles", C.c_int64), ("n_items", C.c_int64), ("n_wide", C.c_int64), ("build_ms", C.c_double)]
+
+
+# rrtx_obstacle_item: one 32-byte record of the obstacle map
+OBSTACLE_ITEM = np.dtype([("ox", np.float64), ("oy", np.float64), ("thr", np.float64), ("index", np.int64)])
+
+
+def use_obstacle_map(obstacle_map, n_obstacles):
+    """The `obstacle_map` keyword of the planners: None = the map when the list does not fit the tile, True, False."""
+    if obstacle_map is None:
+        return n_obstacles > OBSTACLE_TILE_MAX
+    if obstacle_map is True or obstacle_map is False:
+        return obstacle_map
+    raise ValueError("obstacle_map is None, True or False, got %r" % (obstacle_map,))
+
+
 _lib = None
 
 
@@ -257,6 +279,9 @@ def load():
     L.rrtx_create.argtypes = [C.POINTER(Params), C.POINTER(vp)]
     L.rrtx_set_obstacles.argtypes = [vp, vp, i32]
     L.rrtx_set_instance_obstacles.argtypes = [vp, vp, vp]
+    L.rrtx_set_obstacle_map.argtypes = [vp, vp, C.c_int64]
+    L.rrtx_get_obstacle_map_info.argtypes = [vp, C.POINTER(ObstacleMapInfo)]
+    L.rrtx_get_obstacle_map.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int64]
     L.rrtx_set_rng_state.argtypes = [vp, i32, vp, i32]
     L.rrtx_get_rng_state.argtypes = [vp, i32, vp, C.POINTER(i32)]
     L.rrtx_seed_instances.argtypes = [vp, i32, i32, vp]
@@ -530,6 +555,39 @@ class Handle:
         a = np.ascontiguousarray(np.array([[float(v) for v in o] for o in obstacle_list], dtype=np.float64)
                                  .reshape(-1, 3))
         self._chk(self.L.rrtx_set_obstacles(self._h, a.ctypes.data, len(a)), "rrtx_set_obstacles")
+
+    def set_obstacle_map(self, obstacle_list):
+        """Any number of circles up to 2**20 through the obstacle map (rrtx_set_obstacle_map); "rrt" / "rrt_star" only."""
+        a = np.ascontiguousarray(np.array([[float(v) for v in o] for o in obstacle_list], dtype=np.float64)
+                                 .reshape(-1, 3))
+        self._chk(self.L.rrtx_set_obstacle_map(self._h, a.ctypes.data if len(a) else None, len(a)), "rrtx_set_obstacle_map")
+
+    def load_obstacles(self, obstacle_list, obstacle_map=None):
+        """set_obstacle_map or set_obstacles as the planners' `obstacle_map` keyword says (use_obstacle_map); returns
+        whether the handle holds a map now."""
+        use = use_obstacle_map(obstacle_map, len(obstacle_list))
+        if use:
+            self.set_obstacle_map(obstacle_list)
+        else:
+            self.set_obstacles(obstacle_list)
+        return use
+
+    def obstacle_map_info(self):
+        """rrtx_get_obstacle_map_info as a dict."""
+        info = ObstacleMapInfo()
+        self._chk(self.L.rrtx_get_obstacle_map_info(self._h, C.byref(info)), "rrtx_get_obstacle_map_info")
+        return {k: getattr(info, k) for k, _ in ObstacleMapInfo._fields_}
+
+    def obstacle_map(self):
+        """(cell_start[nx * ny + 1], items, wide): the map as built; items and wide are OBSTACLE_ITEM records."""
+        info = self.obstacle_map_info()
+        cell_start = np.zeros(info["nx"] * info["ny"] + 1, dtype=np.int32)
+        items = np.zeros(info["n_items"], dtype=OBSTACLE_ITEM)
+        wide = np.zeros(info["n_wide"], dtype=OBSTACLE_ITEM)
+        self._chk(self.L.rrtx_get_obstacle_map(self._h, cell_start.ctypes.data, items.ctypes.data if len(items) else None,
+                                               len(items), wide.ctypes.data if len(wide) else None, len(wide)),
+                  "rrtx_get_obstacle_map")
+        return cell_start, items, wide
 
     def set_instance_obstacles(self, lists):
         """One obstacle list of (x, y, size) rows per instance (rrtx_set_instance_obstacles)."""

@@ -34,6 +34,7 @@
 
 #include "rpp_core.h"
 #include "rpp_node.h"
+#include "rpp_obsgrid.h"
 #include "rpp_rs.h"
 
 namespace rppk {
@@ -600,11 +601,118 @@ __device__ __forceinline__ void exact_dedup(const double* __restrict__ x, const 
 }
 
 // ---------------------------------------------------------------------------
+// The obstacle map (rrtx_set_obstacle_map; rules and the conservativeness argument: rpp_obsgrid.h): launch argument of
+// rrt_plan_map_kernel.  items[]: every cell's records as one contiguous run, cell after cell in row-major order, the wide
+// list behind the last cell (run number `cells`); cell_start[cells + 2]: the runs.  tile: records per LDS tile
+// (RRTX_OBSMAP_TILE: test knob; MAX_OBS otherwise).
+struct ObsMap {
+  const rppo::Item* items;
+  const int32_t* cell_start;
+  rppo::Geom g;
+  int32_t cells, tile;
+};
+// The box of an edge group and the records its walks have read.  Every sampled point of an edge lies on its segment up
+// to accumulated rounding, so the end points widened by path_resolution hold them all with a generous margin.
+struct MapBox {
+  const ObsMap* mp;
+  double xlo, xhi, ylo, yhi;
+  int64_t gathered;
+};
+__device__ __forceinline__ void box_around(MapBox& b, double cx, double cy, double half) {
+  b.xlo = cx - half;
+  b.xhi = cx + half;
+  b.ylo = cy - half;
+  b.yhi = cy + half;
+}
+__device__ __forceinline__ void box_of_edge(MapBox& b, const rpp::Edge& e, double margin) {
+  b.xlo = (e.fx < e.ex ? e.fx : e.ex) - margin;
+  b.xhi = (e.fx < e.ex ? e.ex : e.fx) + margin;
+  b.ylo = (e.fy < e.ey ? e.fy : e.ey) - margin;
+  b.yhi = (e.fy < e.ey ? e.ey : e.fy) + margin;
+}
+// Walk over the runs of a box: the cells cx0 .. cx1 of one grid row are adjacent in items[], so a box is one run per
+// row, then the wide list.  A circle listed in several cells of the box is met once per cell: harmless, the verdict
+// is "any circle hit".
+struct BoxWalk {
+  int32_t cx0, cx1, row, row_end, pos, end, wide;
+};
+__device__ __forceinline__ BoxWalk box_begin(const MapBox& b) {
+  const rppo::Range r = rppo::range_of(b.mp->g, b.xlo, b.xhi, b.ylo, b.yhi);
+  return BoxWalk{r.cx0, r.cx1, r.cy0, r.cy1, 0, 0, 1};
+}
+// the next run of the walk into w.pos / w.end; false: the box is exhausted
+__device__ __forceinline__ bool box_next_run(const ObsMap& mp, BoxWalk& w) {
+  if (w.row <= w.row_end) {
+    const int32_t base = w.row * mp.g.nx;
+    w.pos = mp.cell_start[base + w.cx0];
+    w.end = mp.cell_start[base + w.cx1 + 1];
+    w.row++;
+    return true;
+  }
+  if (w.wide) {
+    w.pos = mp.cell_start[mp.cells];
+    w.end = mp.cell_start[mp.cells + 1];
+    w.wide = 0;
+    return true;
+  }
+  return false;
+}
+// Fills the LDS tile (sh.ox / oy / othr) with the next records of the walk, until it is full or the box is exhausted;
+// returns their number, 0: nothing left.  Block-uniform; the tile's previous readers are done when it is written, its
+// new contents are visible on return.
+template <class SH>
+__device__ __forceinline__ int box_fill(MapBox& b, BoxWalk& w, SH& sh) {
+  const ObsMap& mp = *b.mp;
+  __syncthreads();
+  int fill = 0;
+  while (fill < mp.tile) {
+    if (w.pos >= w.end) {
+      if (!box_next_run(mp, w)) break;
+      continue;
+    }
+    const int take = (w.end - w.pos) < (mp.tile - fill) ? (w.end - w.pos) : (mp.tile - fill);
+    for (int i = threadIdx.x; i < take; i += SH::kTPB) {
+      const rppo::Item it = mp.items[w.pos + i];
+      sh.ox[fill + i] = it.ox;
+      sh.oy[fill + i] = it.oy;
+      sh.othr[fill + i] = it.thr;
+    }
+    fill += take;
+    w.pos += take;
+  }
+  __syncthreads();
+  b.gathered += fill;
+  return fill;
+}
+// one edge against every record of the box, by one lane, straight from the item array (rewire_raw_walk)
+__device__ inline bool box_hits_edge(MapBox& b, const rpp::Edge& e) {
+  BoxWalk w = box_begin(b);
+  while (box_next_run(*b.mp, w)) {
+    b.gathered += w.end - w.pos;
+    for (int32_t i = w.pos; i < w.end; i++) {
+      const rppo::Item it = b.mp->items[i];
+      if (rpp::edge_hits_obstacle(e, it.ox, it.oy, it.thr)) return true;
+    }
+  }
+  return false;
+}
+// edge sh.edge[0] against the box of `b` by the whole workgroup: sh.ecoll[0] = 1 on a hit
+template <class SH>
+__device__ __forceinline__ void box_test_edge0(MapBox& b, SH& sh) {
+  BoxWalk w = box_begin(b);
+  for (int nt; (nt = box_fill(b, w, sh)) > 0;)
+    for (int k = threadIdx.x; k < nt; k += SH::kTPB)
+      if (rpp::edge_hits_obstacle(sh.edge[0], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[0] = 1;
+}
+
+// ---------------------------------------------------------------------------
 // Steer + collision for `ne` edges.  kind 0: node uidx[e] -> (tx,ty) (choose_parent
 // :1265, goal :1295); kind 1: (tx,ty) -> node uidx[e] (rewire :1359).
 // Out per e: sh.uex/uey (edge end), sh.usafe (no collision AND end inside play area).
+// MAP: the obstacles are the records of the box `mb`, one tile after the other, in place of sh.ox[0 .. om).
+template <bool MAP = false>
 __device__ __forceinline__ void eval_edges(const Ctx& c, int om, const double* __restrict__ x, const double* __restrict__ y,
-                                           int ne, int kind, double tx, double ty, Sh& sh) {
+                                           int ne, int kind, double tx, double ty, Sh& sh, MapBox* mb = nullptr) {
   const int tid = threadIdx.x;
   for (int base = 0; base < ne; base += EB) {
     const int nb = (ne - base) < EB ? (ne - base) : EB;
@@ -618,9 +726,18 @@ __device__ __forceinline__ void eval_edges(const Ctx& c, int om, const double* _
       sh.ecoll[tid] = 0;
     }
     __syncthreads();
-    for (int p = tid; p < nb * om; p += TPB) {
-      const int e = p / om, k = p - e * om;
-      if (rpp::edge_hits_obstacle(sh.edge[e], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[e] = 1;
+    if constexpr (MAP) {
+      BoxWalk w = box_begin(*mb);
+      for (int nt; (nt = box_fill(*mb, w, sh)) > 0;)
+        for (int p = tid; p < nb * nt; p += TPB) {
+          const int e = p / nt, k = p - e * nt;
+          if (rpp::edge_hits_obstacle(sh.edge[e], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[e] = 1;
+        }
+    } else {
+      for (int p = tid; p < nb * om; p += TPB) {
+        const int e = p / om, k = p - e * om;
+        if (rpp::edge_hits_obstacle(sh.edge[e], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[e] = 1;
+      }
     }
     __syncthreads();
     if (tid < nb) {
@@ -663,8 +780,9 @@ __device__ __forceinline__ int block_min_int(int v, Sh& sh) {
 // direction w>>1 and evaluates cos (w even) or sin (w odd) of the edge angle; lane = candidate.
 // Out per candidate e: uex/uey = end of the forward edge, uaux = hypot(new - node) (= hypot(node - new)),
 // usafe bit0 = forward edge safe, bit1 = backward edge safe, bit2 = backward edge ends exactly on the node.
+template <bool MAP = false>
 __device__ __forceinline__ void eval_edges_dual(const Ctx& c, int om, const double* __restrict__ x, const double* __restrict__ y,
-                                                int nu, double nx, double ny, Sh& sh) {
+                                                int nu, double nx, double ny, Sh& sh, MapBox* mb = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int kind = w >> 1, trig = w & 1;
   for (int base = 0; base < nu; base += EBD) {
@@ -702,11 +820,22 @@ __device__ __forceinline__ void eval_edges_dual(const Ctx& c, int om, const doub
       sh.ecoll[kind * EBD + lane] = 0;
     }
     __syncthreads();
-    for (int p = tid; p < 2 * nb * om; p += TPB) {
-      const int q = p / om, k = p - q * om;
-      const int kk = q / nb, e = q - kk * nb;
-      const int slot = kk * EBD + e;
-      if (rpp::edge_hits_obstacle(sh.edge[slot], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[slot] = 1;
+    if constexpr (MAP) {
+      BoxWalk w = box_begin(*mb);
+      for (int nt; (nt = box_fill(*mb, w, sh)) > 0;)
+        for (int p = tid; p < 2 * nb * nt; p += TPB) {
+          const int q = p / nt, k = p - q * nt;
+          const int kk = q / nb, e = q - kk * nb;
+          const int slot = kk * EBD + e;
+          if (rpp::edge_hits_obstacle(sh.edge[slot], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[slot] = 1;
+        }
+    } else {
+      for (int p = tid; p < 2 * nb * om; p += TPB) {
+        const int q = p / om, k = p - q * om;
+        const int kk = q / nb, e = q - kk * nb;
+        const int slot = kk * EBD + e;
+        if (rpp::edge_hits_obstacle(sh.edge[slot], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[slot] = 1;
+      }
     }
     __syncthreads();
     if (tid < nb) {
@@ -842,11 +971,12 @@ __device__ inline void unlink_child(int32_t* parent, Kid* kid, int32_t* prev_sib
 // current coordinates and costs.  dist_list itself predates the loop: the entry -> index map is taken before anything
 // moves (stored over hits[], as candidate slot numbers).  Rare (needs a distance tie in the near set and an inexact
 // path_resolution); lane 0 walks, the whole workgroup builds the map.
+template <bool MAP = false>
 __device__ inline void rewire_raw_walk(const Ctx& c, int om, double* __restrict__ x, double* __restrict__ y,
                                        double* __restrict__ cost, int32_t* parent, Kid* kid,
                                        int32_t* prev_sib, int32_t* hits, int32_t* stack, int kraw,
                                        int nu, double nx, double ny, double r2, double wx, double wy, double wcost,
-                                       int newidx, int es0, Sh& sh) {
+                                       int newidx, int es0, Sh& sh, MapBox* mb = nullptr) {
   const int tid = threadIdx.x;
   for (int base = 0; base < kraw; base += TPB) {
     const int h = base + tid;
@@ -895,8 +1025,12 @@ __device__ inline void rewire_raw_walk(const Ctx& c, int om, double* __restrict_
       if (!(cost[u] > ec)) continue;                               // improved_cost :1366 (strict)
       rpp::steer(&sh.edge[0], wx, wy, ux, uy, rpp::dinf(), c.res);   // :1359
       bool ok = rpp::in_play_area(c.has_play, c.play_area, sh.edge[0].ex, sh.edge[0].ey);
-      for (int k = 0; k < om && ok; k++)
-        if (rpp::edge_hits_obstacle(sh.edge[0], sh.ox[k], sh.oy[k], sh.othr[k])) ok = false;
+      if constexpr (MAP) {
+        if (ok && box_hits_edge(*mb, sh.edge[0])) ok = false;
+      } else {
+        for (int k = 0; k < om && ok; k++)
+          if (rpp::edge_hits_obstacle(sh.edge[0], sh.ox[k], sh.oy[k], sh.othr[k])) ok = false;
+      }
       if (!ok) continue;
       unlink_child(parent, kid, prev_sib, u);   // :1369-1371 (also when it already hangs under newidx)
       if (sh.edge[0].ex != ux || sh.edge[0].ey != uy) {
@@ -946,9 +1080,10 @@ __device__ inline void write_path(const Ctx& c, Inst* I, const double* x, const 
 }
 
 // search_best_goal_node (rrt_04:1284-1312): returns the goal node index or -1 (block-uniform).
+template <bool MAP = false>
 __device__ __forceinline__ int best_goal_node(const Ctx& c, int om, Inst* I, const double* x, const double* y,
                                               const double* cost, int32_t* hits, int n, Sh& sh, int64_t& eu,
-                                              int64_t& er) {
+                                              int64_t& er, MapBox* mb = nullptr) {
   const double gx = I->goal[0], gy = I->goal[1];
   const double thr = c.expand_dis * c.expand_dis * (1.0 + FILTER_EPS);
   const int kraw = scan_hits(x, y, n, gx, gy, thr, hits, sh);
@@ -957,7 +1092,8 @@ __device__ __forceinline__ int best_goal_node(const Ctx& c, int om, Inst* I, con
   eu += nu;
   er += sh.nvalid;
   if (nu == 0) return -1;
-  eval_edges(c, om, x, y, nu, 0, gx, gy, sh);
+  if constexpr (MAP) box_around(*mb, gx, gy, c.expand_dis + c.expand_dis * 0x1p-40 + c.res);   // candidates lie within expand_dis (:1290)
+  eval_edges<MAP>(c, om, x, y, nu, 0, gx, gy, sh, mb);
   for (int e = threadIdx.x; e < nu; e += TPB)
     sh.uaux[e] = sh.usafe[e] ? cost[sh.uidx[e]] + sh.uval[e] : rpp::dinf();  // cost + calc_dist_to_goal :1303-1305
   __syncthreads();
@@ -991,8 +1127,13 @@ __device__ __forceinline__ void draw_sample(const Ctx& c, SH& sh, rpp::Sobol& so
 }
 
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
+// The body of rrt_plan_kernel (MAP = false: the obstacles of an instance are its rows of the table, staged in the LDS
+// tile once) and of rrt_plan_map_kernel (MAP = true: every edge group refills the tile from the cells of the obstacle map
+// its box covers, as often as the box has records for; the instances' own rows are empty).
+template <bool MAP>
+__device__ __forceinline__ void rrt_plan_body(const Ctx& c, int iters, const ObsMap* mp) {
   __shared__ Sh sh;
+  MapBox mb{mp, 0.0, 0.0, 0.0, 0.0, 0};
   const int inst = c.inst_map ? c.inst_map[blockIdx.x] : blockIdx.x;
   const int tid = threadIdx.x;
   Inst* I = c.inst + inst;
@@ -1092,8 +1233,13 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
     if (inplay) {
       s_eu++;
       s_er++;
-      for (int k = tid; k < om; k += TPB)
-        if (rpp::edge_hits_obstacle(sh.edge[0], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[0] = 1;
+      if constexpr (MAP) {
+        box_of_edge(mb, sh.edge[0], c.res);
+        box_test_edge0(mb, sh);
+      } else {
+        for (int k = tid; k < om; k += TPB)
+          if (rpp::edge_hits_obstacle(sh.edge[0], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[0] = 1;
+      }
     }
     __syncthreads();
     const int accepted = inplay && !sh.ecoll[0];
@@ -1132,8 +1278,13 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
       if (sh.flag) {
         s_eu++;
         s_er++;
-        for (int k = tid; k < om; k += TPB)
-          if (rpp::edge_hits_obstacle(sh.edge[0], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[0] = 1;
+        if constexpr (MAP) {
+          box_of_edge(mb, sh.edge[0], c.res);
+          box_test_edge0(mb, sh);
+        } else {
+          for (int k = tid; k < om; k += TPB)
+            if (rpp::edge_hits_obstacle(sh.edge[0], sh.ox[k], sh.oy[k], sh.othr[k])) sh.ecoll[0] = 1;
+        }
         __syncthreads();
         if (!sh.ecoll[0]) {
           if (tid == 0) write_path(c, I, x, y, parent, inst, n - 1);
@@ -1180,7 +1331,10 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
       if (nu > 0) {
         s_eu += nu;
         s_er += nvalid;
-        eval_edges_dual(c, om, x, y, nu, nx, ny, sh);
+        // one box around the new node serves choose_parent and rewire: every candidate lies within sqrt(r2) of it
+        // (:1337), and so does the end of the winning edge
+        if constexpr (MAP) box_around(mb, nx, ny, __builtin_sqrt(r2) * (1.0 + 0x1p-40) + c.res);
+        eval_edges_dual<MAP>(c, om, x, y, nu, nx, ny, sh, &mb);
         PH(6);
         for (int e = tid; e < nu; e += TPB) {
           const int u = sh.uidx[e];
@@ -1213,7 +1367,7 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
         s_er += nvalid;
         if (wx != nx || wy != ny) {
           // the winning edge stopped short of the extension point: redo the backward edges from where it ended
-          eval_edges(c, om, x, y, nu, 1, wx, wy, sh);
+          eval_edges<MAP>(c, om, x, y, nu, 1, wx, wy, sh, &mb);
           for (int e = tid; e < nu; e += TPB) {
             const int u = sh.uidx[e];
             sh.uaux[e] = rpp::py_hypot(x[u] - wx, y[u] - wy);
@@ -1277,8 +1431,8 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
           e0 = es + 1;
         }
         if (raw_from >= 0)
-          rewire_raw_walk(c, om, x, y, cost, parent, kid, prev_sib, hits, stack, kraw, nu, nx, ny, r2, wx,
-                          wy, wcost, newidx, raw_from, sh);
+          rewire_raw_walk<MAP>(c, om, x, y, cost, parent, kid, prev_sib, hits, stack, kraw, nu, nx, ny, r2, wx,
+                               wy, wcost, newidx, raw_from, sh, &mb);
         if (tid == 0) {
           // append :1065
           x[newidx] = wx;
@@ -1336,7 +1490,7 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
       s_sn += n;
       s_ab += 16 * (int64_t)n;
       s_ab2 += 16 * (int64_t)n;
-      const int gi = best_goal_node(c, om, I, x, y, cost, hits, n, sh, s_eu, s_er);
+      const int gi = best_goal_node<MAP>(c, om, I, x, y, cost, hits, n, sh, s_eu, s_er, &mb);
       if (gi >= 0) {
         if (tid == 0) write_path(c, I, x, y, parent, inst, gi);
         done = 1;
@@ -1353,7 +1507,7 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
       s_sn += n;
       s_ab += 16 * (int64_t)n;
       s_ab2 += 16 * (int64_t)n;
-      const int gi = best_goal_node(c, om, I, x, y, cost, hits, n, sh, s_eu, s_er);
+      const int gi = best_goal_node<MAP>(c, om, I, x, y, cost, hits, n, sh, s_eu, s_er, &mb);
       if (gi >= 0 && tid == 0) write_path(c, I, x, y, parent, inst, gi);
       __syncthreads();
     }
@@ -1379,14 +1533,17 @@ __global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) {
     I->rewires += s_rw;
     I->propagated += s_pr;
     I->scan_nodes += s_sn;
-    I->alg_bytes += s_ab;
+    I->alg_bytes += s_ab + (MAP ? 32 * mb.gathered : 0);   // MAP: the 32-byte records the gathers read
     I->exact_rescans += s_ex;
-    I->alg_bytes2 += s_ab2;
+    I->alg_bytes2 += s_ab2 + (MAP ? 32 * mb.gathered : 0);
     PH_STORE(I);
     c.results[inst].n_nodes = n;
     c.results[inst].status = I->status;
   }
 }
+
+__global__ __launch_bounds__(TPB, 4) void rrt_plan_kernel(Ctx c, int iters) { rrt_plan_body<false>(c, iters, nullptr); }
+__global__ __launch_bounds__(TPB, 4) void rrt_plan_map_kernel(Ctx c, int iters, ObsMap mp) { rrt_plan_body<true>(c, iters, &mp); }
 
 // initialise one instance's arrays: +inf padding, root node (rrt_04:1043)
 __global__ void rrt_init_kernel(Ctx c) {

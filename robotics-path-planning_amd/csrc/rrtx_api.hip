@@ -14,6 +14,7 @@
 
 #include "rrtx_host.h"
 #include "rrt_kernels.hip.h"
+#include "obstacle_map.hip.h"
 #include "rrt_star_v2.hip.h"
 #include "rrt_samples.hip.h"
 #include "rrt_informed.hip.h"
@@ -56,6 +57,16 @@ struct rrtx_handle : DevObj {
   // device obstacle table: ox, oy, othr and the sizes (path smoothing) of all rows, `obs_cap` rows each, one allocation
   DevBuf obs_buf;
   int64_t obs_cap = 0;
+  // the obstacle map (rrtx_set_obstacle_map, rrtx_api_obsmap.inc): while `on`, every instance's rows of the table are empty
+  // and the plans run rppk::rrt_plan_map_kernel on `items`
+  struct ObsMapState {
+    bool on = false;
+    DevBuf cell_start, items;
+    rppo::Geom g = {0.0, 0.0, 1.0, 0, 0};
+    int64_t m = 0, n_items = 0, n_wide = 0;
+    int tile = rppk::MAX_OBS;
+    double build_ms = 0.0;
+  } om;
   int trace_inst = -1;    // instance the next plan traces (rrtx_enable_trace)
   int traced_inst = -1;   // instance whose trace the last completed plan recorded; -1 none
   rrtx_stats stats;
@@ -186,6 +197,13 @@ static int dalloc(rrtx_handle* h, T** p, size_t count) {
 static int refuse_in_plan(rrtx_handle* h, const char* fn) {
   if (h->run.stage == 0) return RRTX_OK;
   h->err = std::string(fn) + ": a plan is in progress";
+  return RRTX_E_STATE;
+}
+
+// The entry points that read the handle's obstacle table (path smoothing, goal queries) do not read the obstacle map
+static int refuse_with_map(rrtx_handle* h, const char* fn) {
+  if (!h->om.on) return RRTX_OK;
+  h->err = std::string(fn) + ": the handle holds an obstacle map (rrtx_set_obstacle_map), which this call does not read";
   return RRTX_E_STATE;
 }
 
@@ -569,6 +587,7 @@ int rrtx_set_obstacles(rrtx_handle* h, const double* oxyr, int32_t m) {
       h->inst_dirty = true;
     }
   h->m_max = m;
+  h->om.on = false;   // back on the tile
   return RRTX_OK;
 }
 
@@ -619,6 +638,7 @@ int rrtx_set_instance_obstacles(rrtx_handle* h, const int32_t* offsets, const do
   }
   h->inst_dirty = true;
   h->m_max = m_max;
+  h->om.on = false;   // back on the tile
   return RRTX_OK;
 }
 
@@ -742,6 +762,10 @@ static void queue_main_kernel(rrtx_handle* h, const Ctx& c, int nblk, const rppd
     hipLaunchKernelGGL(rppr::rrt_rs_kernel, dim3(nblk), dim3(rppr::TPB), 0, h->stream, c, da, h->chunk_iters);
   else if (c.algo == RRTX_ALGO_LQR_RRT_STAR)
     hipLaunchKernelGGL(rppl::rrt_lqr_kernel, dim3(nblk), dim3(rppl::TPB), 0, h->stream, c, h->la, h->chunk_iters);
+  else if (h->om.on)
+    hipLaunchKernelGGL(rppk::rrt_plan_map_kernel, dim3(nblk), dim3(rppk::TPB), 0, h->stream, c, h->chunk_iters,
+                       rppk::ObsMap{h->om.items.as<const rppo::Item>(), h->om.cell_start.as<const int32_t>(), h->om.g,
+                                    h->om.g.nx * h->om.g.ny, h->om.tile});
   else
     hipLaunchKernelGGL(rppk::rrt_plan_kernel, dim3(nblk), dim3(rppk::TPB), 0, h->stream, c, h->chunk_iters);
 }
@@ -901,7 +925,8 @@ int rrtx_plan_begin(rrtx_handle* h) {
   // RRT* with search_until_max_iter: the latency-lean iteration kernel runs every iteration; the general kernel
   // below then only performs the final goal search (rrt_04:1080-1084).  RRTX_KERNEL=v1 forces the general kernel.
   const char* kv = getenv("RRTX_KERNEL");
-  R.use_v2 = c.algo == RRTX_ALGO_RRT_STAR && c.until_max && !(kv && !strcmp(kv, "v1"));
+  // With an obstacle map the map variant of the general kernel runs every iteration: no iteration kernel, no shape retry.
+  R.use_v2 = c.algo == RRTX_ALGO_RRT_STAR && c.until_max && !(kv && !strcmp(kv, "v1")) && !h->om.on;
   if (R.use_v2) {
     // workgroup shape: fewer threads per instance once more instances want to be resident (8 / 16 workgroups per CU),
     // as long as the shape's obstacle tile and near-candidate capacity fit the problem
@@ -1608,6 +1633,7 @@ int rrtx_smooth_planned(rrtx_handle* h, int32_t max_iter) {
   if (!h || max_iter < 0) return RRTX_E_INVALID;
   if (!h->planned || (h->p.algo != RRTX_ALGO_RRT && h->p.algo != RRTX_ALGO_RRT_STAR && h->p.algo != RRTX_ALGO_LQR_RRT_STAR))
     return RRTX_E_STATE;
+  if (int rc = refuse_with_map(h, "rrtx_smooth_planned")) return rc;
   if (h->m_max > rpps::MOB) return RRTX_E_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
   const int B = h->n_inst;
@@ -1814,6 +1840,7 @@ int rrtx_get_track_stats(rrtx_handle* h, double* kernel_ms, int64_t* steps) {
 
 }  // extern "C"
 
+#include "rrtx_api_obsmap.inc"
 #include "rrtx_api_tools.inc"
 #include "rrtx_api_rccl.inc"
 #include "rrtx_api_steer.inc"

@@ -43,6 +43,7 @@ static int query_goals(rrtx_handle* h, int32_t n_goals, int32_t per_instance, co
   if (nq > RRTX_GOALQ_MAX_QUERIES) return fail(h, RRTX_E_INVALID, fn + "more than 2^24 queries (instances x goals)");
   if (int rc = refuse_in_plan(h, "rrtx_query_goals")) return rc;
   if (!h->planned) return fail(h, RRTX_E_STATE, fn + "no completed plan");
+  if (int rc = refuse_with_map(h, "rrtx_query_goals")) return rc;
   rrtx_handle::GoalQ& Q = h->gq;
   Q.valid = Q.gathered = false;
   HIPCHK(h, hipSetDevice(h->device));

@@ -179,6 +179,10 @@ class _PlannerBase:
         self.node_list = []
         self.robot_radius = robot_radius
         self.device = device
+        # How planning() hands over obstacle_list (rrt_01 / rrt_02 / rrt_04): None = through the obstacle map when the list
+        # has more than 256 circles (rrtx_set_obstacle_map: any number up to 2**20), True = always, False = never, which
+        # fails beyond 256.  An attribute, set after construction: the constructors keep the reference's signatures.
+        self.obstacle_map = None
         self.stats = None
         self._trace = False
         self.trace = None
@@ -189,7 +193,7 @@ class _PlannerBase:
                         self.max_iter, play_area=self._play_area_arg, robot_radius=self.robot_radius, sampler=sampler,
                         connect_circle_dist=ccd, search_until_max_iter=until_max, n_instances=1, device=self.device)
         try:
-            h.set_obstacles(self.obstacle_list)
+            h.load_obstacles(self.obstacle_list, self.obstacle_map)
             st = random.getstate()
             h.set_rng_state(0, st)
             h.enable_trace(0)   # per-iteration (sample, nearest, what was appended): Node.path_x / path_y need it
@@ -1058,7 +1062,7 @@ class BatchPlanner:
                  goal_sample_rate=5, max_iter=500, play_area=None, robot_radius=0.0, sobol_sampler=False,
                  connect_circle_dist=50.0, search_until_max_iter=False, device=0, starts=None, goals=None,
                  curvature=1.0, goal_yaw_th=float(np.deg2rad(1.0)), goal_xy_th=0.5, step_size=0.2, devices=None,
-                 instance_obstacles=None):
+                 instance_obstacles=None, obstacle_map=None):
         """algo: "rrt" (rrt_01/02), "rrt_star" (rrt_04), "informed" (rrt_07: expand_dis, goal_sample_rate, max_iter,
         sobol_sampler as in its constructor :1029-1042), "bitstar" (rrt_08: max_iter = maxIter, rand_area = randArea
         :140-168), and the pose planners (start / goal = [x, y, yaw]; curvature, goal thresholds and, for Reeds-Shepp,
@@ -1072,7 +1076,10 @@ class BatchPlanner:
         rrt_08:189-202) are computed per instance on the host with numpy, as the reference does per planner object.
         `devices`: HIP device ordinals to shard over (default: [device]).
         `instance_obstacles`: one obstacle list of (x, y, size) per instance, in place of the shared `obstacle_list`
-        (which must then be None): a batch over many maps in one launch (rrtx_set_instance_obstacles)."""
+        (which must then be None): a batch over many maps in one launch (rrtx_set_instance_obstacles).
+        `obstacle_map` ("rrt" and "rrt_star" only): None = the shared list goes through the obstacle map when it has more
+        than 256 circles (rrtx_set_obstacle_map: any number up to 2**20), True = always, False = never; every shard
+        builds its own map.  smooth() and query_goals() are not served with a map."""
         from . import sharding
         a = {"rrt": _abi.ALGO_RRT, "rrt_star": _abi.ALGO_RRT_STAR, "rrt_dubins": _abi.ALGO_RRT_DUBINS,
              "rrt_star_dubins": _abi.ALGO_DUBINS, "rrt_star_reeds_shepp": _abi.ALGO_RS, "informed": _abi.ALGO_INFORMED,
@@ -1105,6 +1112,11 @@ class BatchPlanner:
                                  % (len(instance_obstacles), n))
         self.instance_obstacles = instance_obstacles
         self.obstacle_list = obstacle_list
+        self.has_obstacle_map = False
+        if a in _abi.OBSTACLE_MAP_ALGOS and instance_obstacles is None:
+            self.has_obstacle_map = _abi.use_obstacle_map(obstacle_map, len(obstacle_list))
+        elif obstacle_map:
+            raise ValueError("BatchPlanner: obstacle_map serves the shared obstacle_list of \"rrt\" and \"rrt_star\" only")
         self.devices = [int(device)] if devices is None else [int(d) for d in devices]
         if not self.devices or n < len(self.devices):
             raise ValueError("BatchPlanner: %d instances cannot be sharded over %d handles" % (n, len(self.devices)))
@@ -1133,7 +1145,7 @@ class BatchPlanner:
                 if self.closed_loop:
                     h.set_rs_cost(_abi.RS_COST_PATH)
                 if instance_obstacles is None:
-                    h.set_obstacles(obstacle_list)
+                    h.load_obstacles(obstacle_list, self.has_obstacle_map)
                 else:
                     h.set_instance_obstacles(instance_obstacles[lo:hi])
                 h.seed_instances(self.seeds[lo:hi])
@@ -1255,6 +1267,9 @@ class BatchPlanner:
         only the records, no gather.  order: "planning" (goal -> start) or "driving".  Returns a GoalQueryResult; a query
         with more than _abi.GOALQ_MAX_CANDIDATES distinct candidates has status GOALQ_OVERFLOW and no node (the
         result's `partial` is then True).  Served for "rrt_star", "rrt_star_dubins" and "rrt_star_reeds_shepp" (ValueError otherwise)."""
+        if getattr(self, "has_obstacle_map", False):
+            raise ValueError("BatchPlanner.query_goals: not served with an obstacle map (more than %d obstacles, or "
+                             "obstacle_map=True): it reads the obstacle tile" % _abi.OBSTACLE_TILE_MAX)
         if self.algo not in (_abi.ALGO_RRT_STAR, _abi.ALGO_DUBINS, _abi.ALGO_RS) or getattr(self, "closed_loop", False):
             raise ValueError("BatchPlanner.query_goals: served for %s only (every other planner has another goal rule)"
                              % ", ".join(repr(a) for a in GOAL_QUERY_ALGOS))
@@ -1285,6 +1300,9 @@ class BatchPlanner:
     def smooth(self, max_iter):
         """path_smoothing(path, max_iter, obstacle_list) (rrt_04:1447-1479) on every planned path, on the device, each
         instance continuing its own random stream (as the driver does at :1558-1559), against its own obstacle list."""
+        if getattr(self, "has_obstacle_map", False):
+            raise ValueError("BatchPlanner.smooth: not served with an obstacle map (more than %d obstacles, or "
+                             "obstacle_map=True): it reads the obstacle tile" % _abi.OBSTACLE_TILE_MAX)
         for h in self.handles:
             h.smooth_planned(max_iter)
         c = self.courses("smoothed")
