@@ -258,6 +258,26 @@ RPP_HD static inline void steer(Edge* e, double fx, double fy, double tx, double
   e->snapped = snapped;
 }
 
+// The libm-free snap decision of the rrt_04 iteration kernel, the one copy its three callers share:
+// the extension edge, the candidate edges, and through them the cull path.  d = py_hypot(tx - fx, ty - fy),
+// ne = floor(d / res).  steer() above snaps when hypot(target - p_ne) <= res after ne sequential additions of
+// res (cos theta, sin theta); without the walk that distance is d - ne res up to
+//   * the ne additions per axis, each within half an ULP of the largest coordinate the walk passes -- and the SAME
+//     half ULP every time (same addend, same binade), so they add up, they do not average out: <= ne ulp(M);
+//   * res (cos theta, sin theta) against res (dx, dy) / d: atan2, cos, sin and the product within an ULP each,
+//     under 2^-49 of a step, ne steps: <= 2^-49 d;
+//   * the roundings of tx - fx, of d, of ne res and of the final differences and hypot: <= 2^-51 d + 2^-50 res.
+// true = certainly snapped (the walk's end point IS the target and ne is steer's n_expand); false = in doubt, the
+// exact form (atan2 / cos / sin, the additions) has to decide.  M is taken as |fx| + |fy| + |tx| + |ty| (>= the largest
+// coordinate, no compares), ulp(M) <= 2^-52 M, and both counts are doubled: slack = (2 ne M + 16 d) 2^-52 on top of the
+// 1e-9 res the rule had alone before -- which, fixed, is too little once ne ulp(M) passes it (res = 0.001 on a 100 x 100
+// map: 3000 steps x 1.4e-14 = 4e-11 against 1e-12).
+RPP_HD static inline bool snap_certain(double d, int ne, double res, double fx, double fy, double tx, double ty) {
+  const double m = dabs(fx) + dabs(fy) + dabs(tx) + dabs(ty);
+  const double slack = (2.0 * (double)ne * m + 16.0 * d) * 0x1p-52;
+  return d - (double)ne * res <= res * (1.0 - 1e-9) - slack;
+}
+
 // check_collision (rrt_04:1216-1230) for ONE obstacle: true when some polyline
 // point lies within the inflated radius, `dx*dx + dy*dy <= (size+robot_radius)**2`
 // (min over points <= thr  <=>  any point <= thr).

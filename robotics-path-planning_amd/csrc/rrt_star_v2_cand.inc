@@ -318,7 +318,8 @@ __device__ __forceinline__ void edge_exact_steer(rpp::Edge& e, double res) {
 // (b) n_expand = floor(d / res) (no libm), (c) whether the walk ends snapped on the target -- hypot(target - p_n) <= res,
 // i.e. d - n res <= res up to the roundings of the n additions -- and then the end point IS the target, (d) the collision
 // verdict over the points.  (res cos theta, res sin theta) equals res (dx, dy) / d to a few ULP, so:
-//   * d - n res <= res (1 - 1e-9) decides "snapped" (the reference's sum differs from n res d-hat by ~n ULP);
+//   * rpp::snap_certain (rpp_core.h) decides "snapped": d - n res <= res less a slack that grows with n and with the
+//     coordinates (the reference's sum differs from n res d-hat by up to n ULP of the largest coordinate);
 //   * the points along the straight line decide the collision test against an obstacle unless the closest point lies
 //     within `tol` (~1e-7: 10^6 times the differences in play) of the obstacle's threshold (edge_hits_obstacle_band).
 // An edge with either decision in doubt -- in practice the edge from the NEAREST node, whose length is 8 x 0.25 = 2.0 give
@@ -354,8 +355,8 @@ __device__ __forceinline__ void eval_edges_dual2(const Ctx& c, int om, int nu, d
       E.fx = fx; E.fy = fy; E.tx = tx; E.ty = ty;
       E.n_expand = ne;
       if (kind == 0) sh.uhyp[base + el] = d;
-      // snapped unless the remaining distance is within 1e-9 res of res (then only the exact additions can tell)
-      unsure = !(d - (double)ne * c.res <= c.res * (1.0 - 1e-9));
+      // snapped unless the remaining distance is within the rule's slack of res (then only the exact additions can tell)
+      unsure = !rpp::snap_certain(d, ne, c.res, fx, fy, tx, ty);
       E.ex = tx;
       E.ey = ty;
       E.snapped = unsure ? 4 : 1;   // bit 2: to be evaluated exactly

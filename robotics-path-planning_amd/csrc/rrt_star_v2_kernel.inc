@@ -342,7 +342,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
     // ---------------- steer + collision of the extension :1051-1059
     // Without libm calls in the usual case, like the candidate edges (eval_edges_dual2): once the tree is dense the nearest
     // node is closer than expand_dis, the walk of :1100-1106 ends within one resolution of the sample and :1108-1113 snaps
-    // the new node ONTO the sample.  "Snapped" is certain when d - n res <= res (1 - 1e-9), and the points along the
+    // the new node ONTO the sample.  "Snapped" is certain when rpp::snap_certain says so (rpp_core.h), and the points along the
     // straight line decide the collision test unless an obstacle's threshold lies within `tol` of the closest point.
     // Anything in doubt -- a nearest node further than expand_dis (the new node is then the walk's end point: cos / sin
     // needed), the remaining distance at the resolution, an obstacle in the band -- takes the exact form below.
@@ -350,7 +350,7 @@ __global__ __launch_bounds__(TPB, WPS) void rrt_star_kernel_v2(Ctx c, int iters)
       const double dx = rx - nqx, dy = ry - nqy;
       const double d = rpp::py_hypot(dx, dy);
       const int ne = (int)__builtin_floor(d / c.res);
-      const bool sure = d <= c.expand_dis && d - (double)ne * c.res <= c.res * (1.0 - 1e-9);
+      const bool sure = d <= c.expand_dis && rpp::snap_certain(d, ne, c.res, nqx, nqy, rx, ry);
       const double sc = d > 0.0 ? c.res / d : 0.0;
       sh.e0.fx = nqx; sh.e0.fy = nqy; sh.e0.tx = rx; sh.e0.ty = ry;
       sh.e0.sx = sc * dx;

@@ -31,6 +31,20 @@ def test_core_against_oracle(builddir):
     assert r.returncode == 0, r.stdout + r.stderr
 
 
+def test_snap_rule_against_oracle(builddir):
+    """rpp::snap_certain, the libm-free snap decision of the rrt_04 iteration kernel: wherever it answers "certainly
+    snapped" the oracle's steer snaps after the same number of steps -- path resolutions 0.25 to 1e-4, offsets to 1e6,
+    walk-made and forged lengths at the limit (on which the fixed 1e-9 res it replaces must be caught misjudging) -- and at
+    C2 scale it leaves no more edges in doubt than that did (tests/native/snap_rule_check.cpp)."""
+    import oracle
+    oracle.lib()
+    exe = os.path.join(builddir, "snap_rule_check")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma"] + SAN + ["-I", CSRC,
+                    os.path.join(util.ROOT, "tests", "native", "snap_rule_check.cpp"), "-o", exe, "-ldl"], check=True)
+    r = subprocess.run([exe, os.path.join(util.ROOT, "oracle", "liboracle.so"), "1000"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
 def test_glibc_replicas_against_live_libm(builddir):
     src = os.path.join(util.ROOT, "tests", "native", "glibc_replica_check.c")
     exe = os.path.join(builddir, "glibc_check")
