@@ -577,6 +577,46 @@ int rrtx_steer_set_obstacles(rrtx_steer* s, const double* obstacles, int64_t m, 
  * curve (status != RRTX_STEER_OK), nothing was tested.  RRTX_E_STATE before the first solve and when the last solve ran
  * with no obstacle list set. */
 int rrtx_steer_get_hits(rrtx_steer* s, int32_t* hit);
+/* ---- the obstacle index of the curve objects (csrc/rpp_obsgrid.h point_first_hit) ----------------------------------------------
+ * rrtx_steer_*, rrtx_spline_run and rrtx_bspline_run / _approximate test every curve point against the obstacle list.  The
+ * linear loop reads all m rows per point; the index is the uniform grid of rrtx_set_obstacle_map built over the list itself
+ * (the box of the circle centres, about one circle per cell, the same build kernels), and a point then reads the run of its
+ * own cell and the wide list only.  Every run is in ascending row order, so the answer is the same int32 as the linear loop's,
+ * bit for bit: hits, candidates' hits and rrtx_steer_select_free's choice do not depend on the mode.
+ * Mode per object: RRTX_OBSIDX_AUTO (the default) uses the index when the list has more than RRTX_OBSIDX_MIN rows, _ON always,
+ * _OFF never.  The linear loop serves a list whatever the mode -- never an error -- when the list is empty, when a circle's
+ * (size + robot_radius) ** 2 or reach is not finite, and when a cell or the wide list would hold more than 4096 records
+ * (coincident circles; the build ranks a run with run^2 comparisons).
+ * A steer object builds the index in rrtx_steer_set_obstacles (and in rrtx_steer_set_obstacle_index when the mode asks for one
+ * that was not built), not per solve; setting the same rows with the same robot_radius again keeps the build.  The spline
+ * objects get their list per run and build per run; equal rows and radius reuse the last build.
+ * Test knob: RRTX_OBSMAP_CELLS (cells per axis), as for rrtx_set_obstacle_map. */
+#define RRTX_OBSIDX_AUTO 0
+#define RRTX_OBSIDX_ON 1
+#define RRTX_OBSIDX_OFF 2
+#define RRTX_OBSIDX_MIN 256
+/* rrtx_obstacle_index_info.reason: why the list of the object is served as it is */
+#define RRTX_OBSIDX_REASON_USED 0           /* the index serves it */
+#define RRTX_OBSIDX_REASON_OFF 1            /* the mode is RRTX_OBSIDX_OFF */
+#define RRTX_OBSIDX_REASON_BELOW 2          /* RRTX_OBSIDX_AUTO and no more than RRTX_OBSIDX_MIN rows */
+#define RRTX_OBSIDX_REASON_RUN_TOO_LONG 3   /* a cell or the wide list of more than 4096 records */
+#define RRTX_OBSIDX_REASON_NOT_FINITE 4     /* a threshold or reach that is not finite */
+#define RRTX_OBSIDX_REASON_EMPTY 5          /* no list */
+typedef struct rrtx_obstacle_index_info {
+  int32_t mode;     /* RRTX_OBSIDX_* */
+  int32_t used;     /* 1: the index serves the object's list, 0: the linear loop */
+  int32_t reason;   /* RRTX_OBSIDX_REASON_* */
+  int32_t reserved;
+  rrtx_obstacle_map_info map;   /* the grid when used, zero otherwise */
+} rrtx_obstacle_index_info;
+/* RRTX_E_INVALID for a NULL object or a mode that is not RRTX_OBSIDX_*.  Takes effect at once for the list a steer object
+ * holds, and at the next run of a spline object. */
+int rrtx_steer_set_obstacle_index(rrtx_steer* s, int32_t mode);
+/* For the list the object holds (steer) or the last run's list (spline objects; reason RRTX_OBSIDX_REASON_EMPTY before one) */
+int rrtx_steer_get_obstacle_index_info(rrtx_steer* s, rrtx_obstacle_index_info* info);
+/* The index as built, shaped like rrtx_get_obstacle_map; RRTX_E_STATE when the index does not serve the list */
+int rrtx_steer_get_obstacle_index(rrtx_steer* s, int32_t* cell_start, rrtx_obstacle_item* items, int64_t cap_items,
+                                  rrtx_obstacle_item* wide, int64_t cap_wide);
 
 /* ---- every candidate curve of a pair, and the shortest one that is free (csrc/steer_batch.hip.h steer_*_all) ---------------
  * rrtx_steer_solve_all restates calc_paths (10_path_planning_00_reeds_shepp_path.py :483-503): for RRTX_STEER_RS every Path
@@ -857,6 +897,9 @@ int rrtx_spline_get_c(rrtx_spline* s, double* cx, double* cy, int64_t cap);
  * point touches; -2 the course owns no points (status != RRTX_SPLINE_OK, or no sample), nothing was tested.  RRTX_E_STATE when
  * the last run had no obstacle list. */
 int rrtx_spline_get_hits(rrtx_spline* s, int32_t* hit);
+/* The obstacle index (see rrtx_steer_set_obstacle_index) of rrtx_spline_run */
+int rrtx_spline_set_obstacle_index(rrtx_spline* s, int32_t mode);
+int rrtx_spline_get_obstacle_index_info(rrtx_spline* s, rrtx_obstacle_index_info* info);
 /* Completed rrtx_spline_run / rrtx_spline_fit1d calls on `s` so far (rrtx_track_source.generation) */
 int rrtx_spline_get_generation(rrtx_spline* s, uint64_t* generation);
 
@@ -1001,6 +1044,9 @@ int rrtx_bspline_get_coefficients(rrtx_bspline* s, int64_t* knot_offsets, double
 /* Per course of the last run: -1 no point of the course touches an obstacle (free); j >= 0 the lowest index of the list any
  * point touches; -2 the course owns no points, nothing was tested.  RRTX_E_STATE when the last run had no obstacle list. */
 int rrtx_bspline_get_hits(rrtx_bspline* s, int32_t* hit);
+/* The obstacle index (see rrtx_steer_set_obstacle_index) of rrtx_bspline_run and rrtx_bspline_approximate */
+int rrtx_bspline_set_obstacle_index(rrtx_bspline* s, int32_t mode);
+int rrtx_bspline_get_obstacle_index_info(rrtx_bspline* s, rrtx_obstacle_index_info* info);
 /* HIP-event time of the kernels of the last run (fit and evaluation; the prefix sum between them is not kernel time) */
 int rrtx_bspline_get_kernel_ms(rrtx_bspline* s, double* kernel_ms);
 /* Completed rrtx_bspline_run / rrtx_bspline_approximate calls on `s` so far (rrtx_track_source.generation) */

@@ -60,7 +60,12 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_armdh_create", "rrtx_armdh_destroy", "rrtx_armdh_last_error", "rrtx_armdh_forward", "rrtx_armdh_solve",
            "rrtx_armdh_get_records", "rrtx_armdh_get_angles", "rrtx_armdh_get_transforms", "rrtx_armdh_get_jacobians",
            "rrtx_armdh_get_kernel_ms",
-           "rrtx_set_obstacle_map", "rrtx_get_obstacle_map_info", "rrtx_get_obstacle_map"]
+           "rrtx_set_obstacle_map", "rrtx_get_obstacle_map_info", "rrtx_get_obstacle_map",
+           "rrtx_steer_set_obstacle_index", "rrtx_steer_get_obstacle_index_info", "rrtx_steer_get_obstacle_index",
+           "rrtx_spline_set_obstacle_index", "rrtx_spline_get_obstacle_index_info",
+           "rrtx_bspline_set_obstacle_index", "rrtx_bspline_get_obstacle_index_info"]
+OBSIDX_AUTO, OBSIDX_ON, OBSIDX_OFF, OBSIDX_MIN = 0, 1, 2, 256                          # include/rrtx.h: #define RRTX_OBSIDX_*
+OBSIDX_REASONS = ("used", "off", "below the threshold", "run too long", "non-finite reach", "empty")   # RRTX_OBSIDX_REASON_*
 OBSTACLE_TILE_MAX, OBSTACLE_MAP_MAX = 256, 1 << 20   # csrc MAX_OBS (rrtx_set_obstacles), rpp_obsgrid.h M_MAX (rrtx_set_obstacle_map)
 OBSTACLE_MAP_ALGOS = (0, 1)                          # RRTX_ALGO_RRT, RRTX_ALGO_RRT_STAR
 STEER_DUBINS, STEER_RS = 0, 1                                                      # include/rrtx.h: #define RRTX_STEER_*
@@ -248,6 +253,22 @@ class ObstacleMapInfo(C.Structure):
                 ("n_circles", C.c_int64), ("n_items", C.c_int64), ("n_wide", C.c_int64), ("build_ms", C.c_double)]
 
 
+class ObstacleIndexInfo(C.Structure):
+    """rrtx_obstacle_index_info"""
+    _fields_ = [("mode", C.c_int32), ("used", C.c_int32), ("reason", C.c_int32), ("reserved", C.c_int32),
+                ("map", ObstacleMapInfo)]
+
+
+def obstacle_index_mode(obstacle_index):
+    """The `obstacle_index` keyword of BatchSteer, BatchSpline and BatchBSpline as an RRTX_OBSIDX_* mode: None = the index
+    when the list has more than OBSIDX_MIN circles, True = always, False = never."""
+    if obstacle_index is None:
+        return OBSIDX_AUTO
+    if obstacle_index is True or obstacle_index is False:
+        return OBSIDX_ON if obstacle_index else OBSIDX_OFF
+    raise ValueError("obstacle_index is None, True or False, got %r" % (obstacle_index,))
+
+
 # rrtx_obstacle_item: one 32-byte record of the obstacle map
 OBSTACLE_ITEM = np.dtype([("ox", np.float64), ("oy", np.float64), ("thr", np.float64), ("index", np.int64)])
 
@@ -282,6 +303,10 @@ def load():
     L.rrtx_set_obstacle_map.argtypes = [vp, vp, C.c_int64]
     L.rrtx_get_obstacle_map_info.argtypes = [vp, C.POINTER(ObstacleMapInfo)]
     L.rrtx_get_obstacle_map.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int64]
+    for obj in ("steer", "spline", "bspline"):
+        getattr(L, "rrtx_%s_set_obstacle_index" % obj).argtypes = [vp, i32]
+        getattr(L, "rrtx_%s_get_obstacle_index_info" % obj).argtypes = [vp, C.POINTER(ObstacleIndexInfo)]
+    L.rrtx_steer_get_obstacle_index.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int64]
     L.rrtx_set_rng_state.argtypes = [vp, i32, vp, i32]
     L.rrtx_get_rng_state.argtypes = [vp, i32, vp, C.POINTER(i32)]
     L.rrtx_seed_instances.argtypes = [vp, i32, i32, vp]
@@ -1002,6 +1027,21 @@ class _DevObject:
             raise RrtxError("%s: %s %s" % (what, ERRORS.get(rc, rc), self._fn("last_error")(self._s).decode()))
         return rc
 
+    # the obstacle index of the steer, spline and bspline objects (rrtx_<prefix>_set_obstacle_index)
+    def set_obstacle_index(self, obstacle_index):
+        """None, True or False (obstacle_index_mode)."""
+        self._chk(self._fn("set_obstacle_index")(self._s, obstacle_index_mode(obstacle_index)),
+                  "rrtx_%s_set_obstacle_index" % self._prefix)
+
+    def obstacle_index_info(self):
+        """rrtx_<prefix>_get_obstacle_index_info as a dict: mode, used (bool), reason (one of OBSIDX_REASONS) and the fields
+        of rrtx_obstacle_map_info (zero unless used)."""
+        info = ObstacleIndexInfo()
+        self._chk(self._fn("get_obstacle_index_info")(self._s, C.byref(info)), "rrtx_%s_get_obstacle_index_info" % self._prefix)
+        out = {"mode": info.mode, "used": bool(info.used), "reason": OBSIDX_REASONS[info.reason]}
+        out.update({k: getattr(info.map, k) for k, _ in ObstacleMapInfo._fields_})
+        return out
+
 
 class Steer(_DevObject):
     """Thin RAII wrapper over rrtx_steer* (batched Dubins / Reeds-Shepp curves between pose pairs, LQR rollouts between
@@ -1168,6 +1208,16 @@ class Steer(_DevObject):
         self._chk(self.L.rrtx_steer_set_obstacles(self._s, ob.ctypes.data if len(ob) else None, len(ob),
                                                   float(robot_radius)), "rrtx_steer_set_obstacles")
         self.n_obstacles = len(ob)
+
+    def obstacle_index(self):
+        """(info, cell_start, items, wide) of the index over the object's list, as Handle.obstacle_map gives the planners'."""
+        info = self.obstacle_index_info()
+        cell_start = np.zeros(info["nx"] * info["ny"] + 1, dtype=np.int32)
+        items, wide = np.zeros(info["n_items"], dtype=OBSTACLE_ITEM), np.zeros(info["n_wide"], dtype=OBSTACLE_ITEM)
+        self._chk(self.L.rrtx_steer_get_obstacle_index(self._s, cell_start.ctypes.data, items.ctypes.data if len(items) else None,
+                                                       len(items), wide.ctypes.data if len(wide) else None, len(wide)),
+                  "rrtx_steer_get_obstacle_index")
+        return info, cell_start, items, wide
 
     def hits(self):
         """(n,) int32 of the last solve: -1 free, j >= 0 the first obstacle of the list the curve touches, -2 no curve."""

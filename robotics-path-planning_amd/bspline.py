@@ -144,6 +144,7 @@ class BSplineResult:
         self.coefficients = coefficients
         self.wp_offsets = wp_offsets
         self.hit = hit
+        self.obstacle_index = None   # with an obstacle list: what tested it (the obstacle_index keyword), a dict
         self.rc = rc
         self.kernel_ms = kernel_ms
 
@@ -219,8 +220,22 @@ class BatchBSpline:
     """Interpolating and smoothing B-splines of degree 1 .. 5 through batches of waypoint lists; device buffers are kept
     between calls."""
 
-    def __init__(self, device=0):
+    def __init__(self, device=0, obstacle_index=None):
+        """obstacle_index: None, True or False, as BatchSteer's (also a settable attribute); result.obstacle_index says what
+        tested a run's obstacle list."""
+        _abi.obstacle_index_mode(obstacle_index)   # a ValueError comes before any device call
         self._bs = _abi.BSpline(device)
+        self.obstacle_index = obstacle_index
+
+    @property
+    def obstacle_index(self):
+        return self._obstacle_index
+
+    @obstacle_index.setter
+    def obstacle_index(self, v):
+        _abi.obstacle_index_mode(v)
+        self._bs.set_obstacle_index(v)
+        self._obstacle_index = v
 
     def close(self):
         self._bs.close()
@@ -244,6 +259,7 @@ class BatchBSpline:
                             (cx, cy), keep["offsets"], S.hits(len(rec)) if keep["obstacles"] is not None else None, rc, ms)
         if _abi.on_device(arrays):
             res.device_courses = _abi.DeviceCourses(_abi.SRC_BSPLINE, S)
+        res.obstacle_index = S.obstacle_index_info() if keep["obstacles"] is not None else None
         return res
 
     def interpolate(self, waypoints, n_path_points=None, degree=3, obstacle_list=None, robot_radius=0.0, arrays=True, u=None):
@@ -291,6 +307,7 @@ class BatchBSpline:
                                   arec, keep["offsets"], S.hits(len(rec)) if keep["obstacles"] is not None else None, rc, ms)
         if _abi.on_device(arrays):
             res.device_courses = _abi.DeviceCourses(_abi.SRC_BSPLINE, S)
+        res.obstacle_index = S.obstacle_index_info() if keep["obstacles"] is not None else None
         return res
 
     def spline2d(self, waypoints, ds=0.1, kind="cubic", obstacle_list=None, robot_radius=0.0, arrays=True, u=None):

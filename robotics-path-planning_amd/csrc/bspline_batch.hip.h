@@ -19,6 +19,7 @@
 #pragma once
 #include "rpp_bspline.h"
 #include "rpp_collide.h"
+#include "rpp_obsgrid.h"
 
 namespace rppbs {
 
@@ -27,6 +28,9 @@ constexpr int FIT_TPB = 64;           // one lane per course and long sequential
 constexpr int MAX_WAYPOINTS = 4096;   // per course: bounds one lane's sequential sweep (include/rrtx.h)
 constexpr int TAB_PLANES = 3 + 2 * rpp::kBsplineMaxDegree + 1;
 constexpr int KNOT_SLACK = rpp::kBsplineMaxDegree + 1;
+// the eval kernels' CHECK: no obstacle test, the linear loop (rpp::first_hit), or the obstacle index
+// (rppo::point_first_hit); a template parameter, so that a launch without the index carries none of its registers
+constexpr int CHECK_NONE = 0, CHECK_LINEAR = 1, CHECK_INDEX = 2;
 
 struct Record {   // rrtx_bspline_record
   int32_t status, degree;
@@ -57,6 +61,7 @@ struct Args {
   const double* obs;         // [n_obs] rows (ox, oy, thr), thr = (size + robot_radius) ** 2 from the host
   int64_t n_obs;
   int32_t* hit;              // [n]  fit: -1 (OK) / -2 (no points); eval: the lowest obstacle index touched
+  rppo::Map omap;            // CHECK_INDEX: the grid over the same list
 };
 
 __device__ inline int course_degree(const Args& a, int64_t c) { return a.degree[a.degree_per_course ? c : 0]; }
@@ -102,9 +107,10 @@ __global__ __launch_bounds__(FIT_TPB) void bspline_fit_kernel(Args a) {
 
 // The obstacle test of one point (px, py) of course `lo`, by every lane of the wave: the lowest index touched goes into
 // hit[lo], with one atomic where the wave lies within one course.  Shared with bspline_smooth.hip.h.
+template <int CHECK>
 __device__ inline void check_point(const Args& a, int64_t lo, double px, double py) {
   const uint32_t NONE = 0xffffffffu;
-  const uint32_t h = (uint32_t)rpp::first_hit(a.obs, a.n_obs, px, py);
+  const uint32_t h = (uint32_t)(CHECK == CHECK_INDEX ? rppo::point_first_hit(a.omap, px, py) : rpp::first_hit(a.obs, a.n_obs, px, py));
   if (!__any(h != NONE)) return;
   uint32_t* out = (uint32_t*)a.hit;
   const int course = (int)lo;   // n <= 2^30
@@ -124,7 +130,7 @@ __device__ inline void check_point(const Args& a, int64_t lo, double px, double 
 // With CHECK a lane past the last point does not leave: it stays as a copy of the last point (the same course, the same
 // answer), so every lane of a wave takes part in the shuffles below.  hit[] is read as unsigned for the minimum: -1
 // (free) is then the largest value, and -2 belongs to courses without points.
-template <bool STORE, bool CHECK>
+template <bool STORE, int CHECK>
 __global__ __launch_bounds__(TPB) void bspline_eval_kernel(Args a) {
   int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
   const int64_t total = a.pt_off[a.n];
@@ -156,7 +162,7 @@ __global__ __launch_bounds__(TPB) void bspline_eval_kernel(Args a) {
     for (int q = 0; q < 4; q++) a.out[q * total + idx] = p[q];
     a.out[4 * total + idx] = v;
   }
-  if (CHECK) check_point(a, lo, p[0], p[1]);
+  if (CHECK) check_point<CHECK>(a, lo, p[0], p[1]);
 }
 
 }  // namespace rppbs

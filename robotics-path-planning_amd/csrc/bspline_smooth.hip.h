@@ -101,7 +101,7 @@ __global__ __launch_bounds__(FIT_TPB) void bspline_smooth_fit_kernel(SmoothArgs 
 }
 
 // The lanes past the last point, and hit[], as in bspline_eval_kernel
-template <bool STORE, bool CHECK>
+template <bool STORE, int CHECK>
 __global__ __launch_bounds__(TPB) void bspline_smooth_eval_kernel(SmoothArgs sa) {
   const Args& a = sa.a;
   int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(TPB) void bspline_smooth_eval_kernel(SmoothArgs sa)
     for (int q = 0; q < 4; q++) a.out[q * total + idx] = p[q];
     a.out[4 * total + idx] = v;
   }
-  if (CHECK) check_point(a, lo, p[0], p[1]);
+  if (CHECK) check_point<CHECK>(a, lo, p[0], p[1]);
 }
 
 }  // namespace rppbs

@@ -106,4 +106,89 @@ RPPO_HD bool is_wide(const Range& r) { return range_cells(r) > WIDE_CELLS; }
 // row-major cell number
 RPPO_HD int64_t cell_id(const Geom& g, int32_t cx, int32_t cy) { return (int64_t)cy * g.nx + cx; }
 
+// ---- the obstacle index of the curve objects (rrtx_steer / rrtx_spline / rrtx_bspline): one point against the same grid ------
+// The linear loop rpp::first_hit (rpp_collide.h) answers "the lowest row of the list that the point touches".  The grid answers
+// the same question from two runs, because every run is in ascending circle index (obstacle_map.hip.h sorts them):
+//   geometry_box   a circle list has no rand_area, so the grid lies over the box of the circle centres: origin (xmin, ymin),
+//                  n = axis_cells(m, forced) cells per axis of side max(xmax - xmin, ymax - ymin) / n, repaired to 1 where that
+//                  is not a positive finite number (a box of zero width: all centres equal; a difference that overflows).
+//                  Circles register as above (reach, circle_range, is_wide), by the same build kernels.
+//   query          a point p hit by circle j gives cell(p) in j's range (the argument above), so j is listed in the run of
+//                  cell(p) or, being wide, in the wide run.  Every circle that hits p is therefore in one of the two runs, and
+//                  the lowest index among them is min(first hit of cell(p)'s run, first hit of the wide run): a run in
+//                  ascending index gives its lowest hitting index at its first hit.  The wide walk may stop at the first
+//                  record whose index exceeds the best so far: nothing behind it is lower.
+//   outside        the clamp of cell_of puts a point outside the box into an edge cell c.  cell_of is monotone, so
+//                  cell(fl(ox - rho)) <= cell(p) <= cell(fl(ox + rho)) still holds for a hit point, clamped values included:
+//                  the circle's clamped range contains c.  Nothing in the argument needs p inside the grid.
+//   not finite     a NaN coordinate gives q = NaN and cell 0, +-inf gives an edge cell; dx is then NaN or +-inf, dx * dx + dy * dy
+//                  is NaN or +inf, and `<= thr` is false for every finite thr: no record hits, as in the linear loop.
+//   -0.0           cell_of sends -0.0 (and every q <= 0) to cell 0 as before; the test itself only squares differences.
+//   test           first_hit's own: dx = ox - x, dy = oy - y, dx * dx + dy * dy <= thr (no contraction: -ffp-contract=off), with
+//                  Item.thr the very double of the linear rows, the host's (size + robot_radius) ** 2.
+// The linear loop serves a list instead -- never an error, these lists are accepted as they are -- when
+//   a circle's thr or reach is not finite (an infinite thr hits points the reach cannot bound),
+//   a run is longer than RUN_MAX: obsmap_sort_kernel ranks a run with run^2 comparisons by one wave, so 2^20 coincident circles
+//     would cost 10^12 of them; 4096 bounds a run at 1.7 * 10^7.  The host has every count after the first build launch and
+//     decides before the fill,
+//   the list is empty.
+constexpr int32_t RUN_MAX = 4096;
+
+// Which of the two serves a list of m circles (include/rrtx.h RRTX_OBSIDX_*, RRTX_OBSIDX_REASON_*): `finite` -- every thr and
+// reach is; `longest_run` -- the records of the fullest cell or of the wide list, whichever is more (0 while unknown)
+constexpr int32_t IDX_AUTO = 0, IDX_ON = 1, IDX_OFF = 2, IDX_MIN = 256;
+constexpr int32_t WHY_USED = 0, WHY_OFF = 1, WHY_BELOW = 2, WHY_RUN_TOO_LONG = 3, WHY_NOT_FINITE = 4, WHY_EMPTY = 5;
+RPPO_HD int32_t index_reason(int32_t mode, int64_t m, bool finite, int64_t longest_run) {
+  if (m <= 0) return WHY_EMPTY;
+  if (mode == IDX_OFF) return WHY_OFF;
+  if (mode == IDX_AUTO && m <= IDX_MIN) return WHY_BELOW;
+  if (!finite) return WHY_NOT_FINITE;
+  if (longest_run > RUN_MAX) return WHY_RUN_TOO_LONG;
+  return WHY_USED;
+}
+
+RPPO_HD Geom geometry_box(double xmin, double xmax, double ymin, double ymax, int64_t m, int32_t forced) {
+  Geom g;
+  g.nx = g.ny = axis_cells(m, forced);
+  g.x0 = xmin;
+  g.y0 = ymin;
+  const double wx = xmax - xmin, wy = ymax - ymin;
+  g.cell = (wx > wy ? wx : wy) / (double)g.nx;
+  if (!(g.cell > 0.0) || !(g.cell < __builtin_inf())) g.cell = 1.0;
+  return g;
+}
+
+// the built grid as a kernel reads it: cell_start has nx * ny + 2 entries, run nx * ny is the wide list
+struct Map {
+  Geom g;
+  const int32_t* cell_start;
+  const Item* items;
+};
+
+// The lowest circle index whose circle the point (x, y) touches, or -1: what rpp::first_hit returns for the list the map
+// was built from.  Every lane walks the run of its own cell; an Item is 32 aligned bytes (two 16-byte loads).
+RPPO_HD int32_t point_first_hit(const Map& mp, double x, double y) {
+  const int64_t cells = (int64_t)mp.g.nx * mp.g.ny;
+  const int64_t id = cell_id(mp.g, cell_of(x, mp.g.x0, mp.g.cell, mp.g.nx), cell_of(y, mp.g.y0, mp.g.cell, mp.g.ny));
+  int64_t best = -1;
+  for (int32_t i = mp.cell_start[id], e = mp.cell_start[id + 1]; i < e; i++) {
+    const Item it = mp.items[i];
+    const double dx = it.ox - x, dy = it.oy - y;
+    if (dx * dx + dy * dy <= it.thr) {
+      best = it.index;
+      break;
+    }
+  }
+  for (int32_t i = mp.cell_start[cells], e = mp.cell_start[cells + 1]; i < e; i++) {
+    const Item it = mp.items[i];
+    if (best >= 0 && it.index > best) break;
+    const double dx = it.ox - x, dy = it.oy - y;
+    if (dx * dx + dy * dy <= it.thr) {
+      best = it.index;
+      break;
+    }
+  }
+  return (int32_t)best;
+}
+
 }  // namespace rppo

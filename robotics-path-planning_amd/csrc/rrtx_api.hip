@@ -45,6 +45,15 @@ static_assert(sizeof(rppt::Outcome) == sizeof(rrtx_track_outcome), "rrtx_track_o
 static_assert(sizeof(rppt::Record) == sizeof(rrtx_track_record), "rrtx_track_record mirrors rppt::Record");
 static_assert(sizeof(rppgt::Outcome) == sizeof(rrtx_goal_track_outcome), "rrtx_goal_track_outcome mirrors rppgt::Outcome");
 
+// What a build of the obstacle grid leaves on the device (build_obstacle_grid, rrtx_api_obsmap.inc): cell_start (cells + 2
+// entries, the last run is the wide list) and the sorted records
+struct ObsGrid {
+  DevBuf cell_start, items;
+  rppo::Geom g = {0.0, 0.0, 1.0, 0, 0};
+  int64_t m = 0, n_items = 0, n_wide = 0;
+  double build_ms = 0.0;
+};
+
 struct rrtx_handle : DevObj {
   rrtx_params p;
   Ctx c;
@@ -61,11 +70,8 @@ struct rrtx_handle : DevObj {
   // and the plans run rppk::rrt_plan_map_kernel on `items`
   struct ObsMapState {
     bool on = false;
-    DevBuf cell_start, items;
-    rppo::Geom g = {0.0, 0.0, 1.0, 0, 0};
-    int64_t m = 0, n_items = 0, n_wide = 0;
+    ObsGrid grid;
     int tile = rppk::MAX_OBS;
-    double build_ms = 0.0;
   } om;
   int trace_inst = -1;    // instance the next plan traces (rrtx_enable_trace)
   int traced_inst = -1;   // instance whose trace the last completed plan recorded; -1 none
@@ -764,8 +770,8 @@ static void queue_main_kernel(rrtx_handle* h, const Ctx& c, int nblk, const rppd
     hipLaunchKernelGGL(rppl::rrt_lqr_kernel, dim3(nblk), dim3(rppl::TPB), 0, h->stream, c, h->la, h->chunk_iters);
   else if (h->om.on)
     hipLaunchKernelGGL(rppk::rrt_plan_map_kernel, dim3(nblk), dim3(rppk::TPB), 0, h->stream, c, h->chunk_iters,
-                       rppk::ObsMap{h->om.items.as<const rppo::Item>(), h->om.cell_start.as<const int32_t>(), h->om.g,
-                                    h->om.g.nx * h->om.g.ny, h->om.tile});
+                       rppk::ObsMap{h->om.grid.items.as<const rppo::Item>(), h->om.grid.cell_start.as<const int32_t>(), h->om.grid.g,
+                                    h->om.grid.g.nx * h->om.grid.g.ny, h->om.tile});
   else
     hipLaunchKernelGGL(rppk::rrt_plan_kernel, dim3(nblk), dim3(rppk::TPB), 0, h->stream, c, h->chunk_iters);
 }

@@ -11,6 +11,7 @@ struct rrtx_bspline : DevObj {
   uint64_t generation = 0;   // completed runs and approximations, rrtx_bspline_get_generation
   std::vector<rppbs::Record> h_rec;
   std::vector<int64_t> h_off, h_wp_off, h_knot_off;
+  ObsIndex oi;   // the obstacle index over the last run's list
   std::vector<int32_t> h_hit;
   std::vector<rpp::SmoothInfo> h_arec;   // [2][n], axis-major
 };
@@ -27,13 +28,13 @@ static_assert(rpp::kBsplineNormalised == RRTX_BSPLINE_PARAM_NORMALISED && rpp::k
                   rpp::kBsplineExplicit == RRTX_BSPLINE_SAMPLE_EXPLICIT,
               "the modes of the header are the core's");
 
-template <bool STORE, bool CHECK>
+template <bool STORE, int CHECK>
 static void bspline_launch_eval(int64_t total, hipStream_t stream, const rppbs::Args& a) {
   const unsigned blocks = (unsigned)((total + rppbs::TPB - 1) / rppbs::TPB);
   hipLaunchKernelGGL((rppbs::bspline_eval_kernel<STORE, CHECK>), dim3(blocks), dim3(rppbs::TPB), 0, stream, a);
 }
 
-template <bool STORE, bool CHECK>
+template <bool STORE, int CHECK>
 static void bspline_launch_smooth_eval(int64_t total, hipStream_t stream, const rppbs::SmoothArgs& a) {
   const unsigned blocks = (unsigned)((total + rppbs::TPB - 1) / rppbs::TPB);
   hipLaunchKernelGGL((rppbs::bspline_smooth_eval_kernel<STORE, CHECK>), dim3(blocks), dim3(rppbs::TPB), 0, stream, a);
@@ -146,6 +147,9 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b, const rrtx_
     rows[3 * k + 1] = b->obstacles[3 * k + 1];
     rows[3 * k + 2] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius);
   }
+  // the obstacle index over the same list (rpp_obsgrid.h): built per run, kept while the rows and the radius stay
+  if (int irc = obsindex_set_list(s, s->oi, b->obstacles, n_obs, b->robot_radius)) return irc;
+  const bool indexed = s->oi.used != 0;
 
   HIPCHK(s, hipSetDevice(s->device));
   int rc;
@@ -247,20 +251,31 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b, const rrtx_
     a.out = store ? s->out.as<double>() : nullptr;
     a.obs = check ? s->obs.as<const double>() : nullptr;
     a.n_obs = n_obs;
+    if (check && indexed) a.omap = s->oi.map();
     sa.a = a;
     rc = s->timed(&ms, [&] {
-      if (sb && store && check)
-        bspline_launch_smooth_eval<true, true>(tot, s->stream, sa);
+      using namespace rppbs;
+      const int ck = !check ? CHECK_NONE : (indexed ? CHECK_INDEX : CHECK_LINEAR);
+      if (sb && store && ck == CHECK_INDEX)
+        bspline_launch_smooth_eval<true, CHECK_INDEX>(tot, s->stream, sa);
+      else if (sb && store && ck)
+        bspline_launch_smooth_eval<true, CHECK_LINEAR>(tot, s->stream, sa);
       else if (sb && store)
-        bspline_launch_smooth_eval<true, false>(tot, s->stream, sa);
+        bspline_launch_smooth_eval<true, CHECK_NONE>(tot, s->stream, sa);
+      else if (sb && ck == CHECK_INDEX)
+        bspline_launch_smooth_eval<false, CHECK_INDEX>(tot, s->stream, sa);
       else if (sb)
-        bspline_launch_smooth_eval<false, true>(tot, s->stream, sa);
-      else if (store && check)
-        bspline_launch_eval<true, true>(tot, s->stream, a);
+        bspline_launch_smooth_eval<false, CHECK_LINEAR>(tot, s->stream, sa);
+      else if (store && ck == CHECK_INDEX)
+        bspline_launch_eval<true, CHECK_INDEX>(tot, s->stream, a);
+      else if (store && ck)
+        bspline_launch_eval<true, CHECK_LINEAR>(tot, s->stream, a);
       else if (store)
-        bspline_launch_eval<true, false>(tot, s->stream, a);
+        bspline_launch_eval<true, CHECK_NONE>(tot, s->stream, a);
+      else if (ck == CHECK_INDEX)
+        bspline_launch_eval<false, CHECK_INDEX>(tot, s->stream, a);
       else
-        bspline_launch_eval<false, true>(tot, s->stream, a);
+        bspline_launch_eval<false, CHECK_LINEAR>(tot, s->stream, a);
     }, [&]() -> int {
       if (check) HIPCHK(s, hipMemcpyAsync(s->h_hit.data(), s->hit.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
       return RRTX_OK;
@@ -398,6 +413,14 @@ int rrtx_bspline_get_coefficients(rrtx_bspline* s, int64_t* knot_offsets, double
     if (cy && (rc = s->fetch(cy, s->tab.as<const double>() + 2 * W, sizeof(double) * W))) return rc;
     return RRTX_OK;
   });
+}
+
+int rrtx_bspline_set_obstacle_index(rrtx_bspline* s, int32_t mode) {
+  return obsindex_set_mode(s, s ? &s->oi : nullptr, mode, "rrtx_bspline_set_obstacle_index: ", false);
+}
+
+int rrtx_bspline_get_obstacle_index_info(rrtx_bspline* s, rrtx_obstacle_index_info* info) {
+  return obsindex_get_info(s, s ? &s->oi : nullptr, info, "rrtx_bspline_get_obstacle_index_info: ");
 }
 
 int rrtx_bspline_get_hits(rrtx_bspline* s, int32_t* hit) {

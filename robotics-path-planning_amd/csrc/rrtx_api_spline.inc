@@ -16,6 +16,7 @@ struct rrtx_spline : DevObj {
   double query_ms = 0.0;
   std::vector<rppsp::Record> h_rec;
   std::vector<int64_t> h_off;
+  ObsIndex oi;   // the obstacle index over the last run's list
   std::vector<int32_t> h_hit, h_qst;
 };
 
@@ -27,7 +28,7 @@ static_assert(rpp::kSplineQOk == RRTX_SPLINE_Q_OK && rpp::kSplineQOutside == RRT
 
 inline double (*volatile libm_hypot)(double, double) = hypot;
 
-template <bool STORE, bool CHECK>
+template <bool STORE, int CHECK>
 static void spline_launch_eval(int64_t total, hipStream_t stream, const rppsp::Args& a) {
   const unsigned blocks = (unsigned)((total + rppsp::TPB - 1) / rppsp::TPB);
   hipLaunchKernelGGL((rppsp::spline_eval_kernel<STORE, CHECK>), dim3(blocks), dim3(rppsp::TPB), 0, stream, a);
@@ -98,6 +99,9 @@ static int spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
     rows[3 * k + 1] = b->obstacles[3 * k + 1];
     rows[3 * k + 2] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius);
   }
+  // the obstacle index over the same list (rpp_obsgrid.h): built per run, kept while the rows and the radius stay
+  if (int irc = obsindex_set_list(s, s->oi, b->obstacles, n_obs, b->robot_radius)) return irc;
+  const bool indexed = s->oi.used != 0;
 
   HIPCHK(s, hipSetDevice(s->device));
   int rc;
@@ -163,13 +167,19 @@ static int spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
     a.out = store ? s->out.as<double>() : nullptr;
     a.obs = check ? s->obs.as<const double>() : nullptr;
     a.n_obs = n_obs;
+    if (check && indexed) a.omap = s->oi.map();
     rc = s->timed(&ms, [&] {
-      if (store && check)
-        spline_launch_eval<true, true>(tot, s->stream, a);
+      using namespace rppsp;
+      if (store && check && indexed)
+        spline_launch_eval<true, CHECK_INDEX>(tot, s->stream, a);
+      else if (store && check)
+        spline_launch_eval<true, CHECK_LINEAR>(tot, s->stream, a);
       else if (store)
-        spline_launch_eval<true, false>(tot, s->stream, a);
+        spline_launch_eval<true, CHECK_NONE>(tot, s->stream, a);
+      else if (indexed)
+        spline_launch_eval<false, CHECK_INDEX>(tot, s->stream, a);
       else
-        spline_launch_eval<false, true>(tot, s->stream, a);
+        spline_launch_eval<false, CHECK_LINEAR>(tot, s->stream, a);
     }, [&]() -> int {
       if (check) HIPCHK(s, hipMemcpyAsync(s->h_hit.data(), s->hit.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
       return RRTX_OK;
@@ -402,6 +412,14 @@ int rrtx_spline_get_c(rrtx_spline* s, double* cx, double* cy, int64_t cap) {
   if (cx && (rc = s->fetch(cx, s->tab.as<const double>() + 3 * W, sizeof(double) * W))) return rc;
   if (cy && s->axes == 2 && (rc = s->fetch(cy, s->tab.as<const double>() + 6 * W, sizeof(double) * W))) return rc;
   return RRTX_OK;
+}
+
+int rrtx_spline_set_obstacle_index(rrtx_spline* s, int32_t mode) {
+  return obsindex_set_mode(s, s ? &s->oi : nullptr, mode, "rrtx_spline_set_obstacle_index: ", false);
+}
+
+int rrtx_spline_get_obstacle_index_info(rrtx_spline* s, rrtx_obstacle_index_info* info) {
+  return obsindex_get_info(s, s ? &s->oi : nullptr, info, "rrtx_spline_get_obstacle_index_info: ");
 }
 
 int rrtx_spline_get_hits(rrtx_spline* s, int32_t* hit) {

@@ -7,6 +7,7 @@ struct rrtx_steer : DevObj {
   // the obstacle list of rrtx_steer_set_obstacles: packed rows (ox, oy, thr); it goes to the device at the next solve
   std::vector<double> h_obs;
   bool obs_dirty = false;
+  ObsIndex oi;   // the obstacle index over the same list, built by rrtx_steer_set_obstacles
   // the last solve
   bool solved = false, has_points = false, has_hits = false;
   bool has_k = false;   // a Bezier solve with want_curvature
@@ -31,14 +32,28 @@ struct rrtx_steer : DevObj {
 
 namespace {
 // stage 2 with or without the stores and the obstacle check; one of the two is wanted
+// check: rppsb::CHECK_*
 template <int KIND>
-void steer_launch_fill(bool store, bool check, unsigned blocks, hipStream_t stream, const rppsb::Args& a) {
-  if (store && check)
-    hipLaunchKernelGGL((rppsb::steer_fill<KIND, true, true>), dim3(blocks), dim3(rppsb::TPB), 0, stream, a);
+void steer_launch_fill(bool store, int check, unsigned blocks, hipStream_t stream, const rppsb::Args& a) {
+  using namespace rppsb;
+  if (store && check == CHECK_INDEX)
+    hipLaunchKernelGGL((steer_fill<KIND, true, CHECK_INDEX>), dim3(blocks), dim3(TPB), 0, stream, a);
+  else if (store && check)
+    hipLaunchKernelGGL((steer_fill<KIND, true, CHECK_LINEAR>), dim3(blocks), dim3(TPB), 0, stream, a);
   else if (store)
-    hipLaunchKernelGGL((rppsb::steer_fill<KIND, true, false>), dim3(blocks), dim3(rppsb::TPB), 0, stream, a);
+    hipLaunchKernelGGL((steer_fill<KIND, true, CHECK_NONE>), dim3(blocks), dim3(TPB), 0, stream, a);
+  else if (check == CHECK_INDEX)
+    hipLaunchKernelGGL((steer_fill<KIND, false, CHECK_INDEX>), dim3(blocks), dim3(TPB), 0, stream, a);
   else
-    hipLaunchKernelGGL((rppsb::steer_fill<KIND, false, true>), dim3(blocks), dim3(rppsb::TPB), 0, stream, a);
+    hipLaunchKernelGGL((steer_fill<KIND, false, CHECK_LINEAR>), dim3(blocks), dim3(TPB), 0, stream, a);
+}
+
+// how a fill launch of `s` tests its points: the object's list and, where it serves the list, the index, into a
+int steer_check_mode(const rrtx_steer* s, int64_t n_obs, rppsb::Args& a) {
+  if (n_obs <= 0) return rppsb::CHECK_NONE;
+  if (!s->oi.used) return rppsb::CHECK_LINEAR;
+  a.omap = s->oi.map();
+  return rppsb::CHECK_INDEX;
 }
 
 // One solve, its arguments already checked by its entry point
@@ -287,11 +302,11 @@ static int steer_run(rrtx_steer* s, const SteerJob& j) {
       const unsigned fblk = (unsigned)((tot + rppsb::TPB - 1) / rppsb::TPB);
       rc = s->timed(&ms, [&] {
         if (lqr)
-          steer_launch_fill<rppsb::KIND_LQR>(want_points != 0, n_obs > 0, fblk, s->stream, a);
+          steer_launch_fill<rppsb::KIND_LQR>(want_points != 0, steer_check_mode(s, n_obs, a), fblk, s->stream, a);
         else if (kind == rppsb::KIND_DUBINS)
-          steer_launch_fill<rppsb::KIND_DUBINS>(want_points != 0, n_obs > 0, fblk, s->stream, a);
+          steer_launch_fill<rppsb::KIND_DUBINS>(want_points != 0, steer_check_mode(s, n_obs, a), fblk, s->stream, a);
         else
-          steer_launch_fill<rppsb::KIND_RS>(want_points != 0, n_obs > 0, fblk, s->stream, a);
+          steer_launch_fill<rppsb::KIND_RS>(want_points != 0, steer_check_mode(s, n_obs, a), fblk, s->stream, a);
       });
       if (rc) return rc;
       s->kernel_ms += ms;
@@ -476,7 +491,7 @@ static int steer_run_bezier(rrtx_steer* s, const BezierJob& j) {
     if ((rc = s->upload(s->offsets, s->h_offsets.data(), sizeof(int64_t) * (N + 1)))) return rc;
     a.offsets = s->offsets.as<const int64_t>();
     const unsigned fblk = (unsigned)((tot + rppsb::TPB - 1) / rppsb::TPB);
-    rc = s->timed(&ms, [&] { steer_launch_fill<rppsb::KIND_BEZIER>(want_points, n_obs > 0, fblk, s->stream, a); });
+    rc = s->timed(&ms, [&] { steer_launch_fill<rppsb::KIND_BEZIER>(want_points, steer_check_mode(s, n_obs, a), fblk, s->stream, a); });
     if (rc) return rc;
     s->kernel_ms += ms;
     if (!want_points) s->h_offsets.clear();
@@ -656,8 +671,24 @@ int rrtx_steer_set_obstacles(rrtx_steer* s, const double* obstacles, int64_t m, 
     }
     s->h_obs.swap(t);
     s->obs_dirty = true;
-    return RRTX_OK;
+    return obsindex_set_list(s, s->oi, obstacles, m, robot_radius);
   });
+}
+
+int rrtx_steer_set_obstacle_index(rrtx_steer* s, int32_t mode) {
+  return obsindex_set_mode(s, s ? &s->oi : nullptr, mode, "rrtx_steer_set_obstacle_index: ", true);
+}
+
+int rrtx_steer_get_obstacle_index_info(rrtx_steer* s, rrtx_obstacle_index_info* info) {
+  return obsindex_get_info(s, s ? &s->oi : nullptr, info, "rrtx_steer_get_obstacle_index_info: ");
+}
+
+int rrtx_steer_get_obstacle_index(rrtx_steer* s, int32_t* cell_start, rrtx_obstacle_item* items, int64_t cap_items,
+                                  rrtx_obstacle_item* wide, int64_t cap_wide) {
+  const char* fn = "rrtx_steer_get_obstacle_index: ";
+  if (!s) return fail(s, RRTX_E_INVALID, std::string(fn) + "the steer object is NULL");
+  if (!s->oi.used) return fail(s, RRTX_E_STATE, std::string(fn) + "the obstacle index does not serve the object's list");
+  return obstacle_grid_fetch(s, s->oi.grid, fn, cell_start, items, cap_items, wide, cap_wide);
 }
 
 int rrtx_steer_get_hits(rrtx_steer* s, int32_t* hit) {
@@ -840,9 +871,9 @@ static int steer_solve_all(rrtx_steer* s, int32_t kind, int32_t product, int64_t
         const unsigned fblk = (unsigned)((tot + rppsb::TPB - 1) / rppsb::TPB);
         rc = s->timed(&ms, [&] {
           if (dubins)
-            steer_launch_fill<rppsb::KIND_DUBINS>(want_points != 0, n_obs > 0, fblk, s->stream, a);
+            steer_launch_fill<rppsb::KIND_DUBINS>(want_points != 0, steer_check_mode(s, n_obs, a), fblk, s->stream, a);
           else
-            steer_launch_fill<rppsb::KIND_RS>(want_points != 0, n_obs > 0, fblk, s->stream, a);
+            steer_launch_fill<rppsb::KIND_RS>(want_points != 0, steer_check_mode(s, n_obs, a), fblk, s->stream, a);
         });
         if (rc) return rc;
         s->cand_ms += ms;

@@ -25,12 +25,16 @@
 //   0 s (axis x's), 1 s (axis y's copy), 2 bx, 3 cx, 4 dx, 5 by, 6 cy, 7 dy;  a = the waypoints themselves.
 #pragma once
 #include "rpp_collide.h"
+#include "rpp_obsgrid.h"
 #include "rpp_spline.h"
 
 namespace rppsp {
 
 constexpr int TPB = 256;
 constexpr int MAX_WAYPOINTS = 4096;   // per course: bounds one lane's sequential sweep (include/rrtx.h)
+// spline_eval_kernel's CHECK: no obstacle test, the linear loop (rpp::first_hit), or the obstacle index
+// (rppo::point_first_hit); a template parameter, so that a launch without the index carries none of its registers
+constexpr int CHECK_NONE = 0, CHECK_LINEAR = 1, CHECK_INDEX = 2;
 
 struct Record {   // rrtx_spline_record
   int32_t status, reserved;
@@ -53,6 +57,7 @@ struct Args {
   const double* obs;       // [n_obs] rows (ox, oy, thr), thr = (size + robot_radius) ** 2 from the host
   int64_t n_obs;
   int32_t* hit;            // [n]  fit: -1 (RRTX_SPLINE_OK) / -2 (no points); eval: the lowest obstacle index touched
+  rppo::Map omap;          // CHECK_INDEX: the grid over the same list
 };
 
 __device__ inline double course_ds(const Args& a, int64_t c) { return a.ds[a.ds_per_course ? c : 0]; }
@@ -98,7 +103,7 @@ __global__ __launch_bounds__(TPB) void spline_fit_kernel(Args a) {
 // With CHECK a lane past the last point does not leave: it stays as a copy of the last point (the same course, the same
 // answer), so every lane of a wave takes part in the shuffles below.  hit[] is read as unsigned for the minimum: -1
 // (free) is then the largest value, and -2 belongs to courses without points.
-template <bool STORE, bool CHECK>
+template <bool STORE, int CHECK>
 __global__ __launch_bounds__(TPB) void spline_eval_kernel(Args a) {
   int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
   const int64_t total = a.pt_off[a.n];
@@ -121,7 +126,8 @@ __global__ __launch_bounds__(TPB) void spline_eval_kernel(Args a) {
   }
   if (CHECK) {
     const uint32_t NONE = 0xffffffffu;
-    const uint32_t h = (uint32_t)rpp::first_hit(a.obs, a.n_obs, p[0], p[1]);
+    const uint32_t h =
+        (uint32_t)(CHECK == CHECK_INDEX ? rppo::point_first_hit(a.omap, p[0], p[1]) : rpp::first_hit(a.obs, a.n_obs, p[0], p[1]));
     if (!__any(h != NONE)) return;
     uint32_t* out = (uint32_t*)a.hit;
     const int course = (int)lo;   // n <= 2^30

@@ -44,6 +44,7 @@
 #include "rpp_bezier.h"
 #include "rpp_collide.h"
 #include "rpp_lqr.h"
+#include "rpp_obsgrid.h"
 #include "rpp_rs.h"
 
 namespace rppsb {
@@ -56,6 +57,9 @@ constexpr int TPB = 256;            // steer_dubins_solve, steer_rs_course, stee
 constexpr int RS_TPB = 64;          // steer_rs_solve: one wave
 constexpr int RS_LANES = 16;        // lanes per pair
 constexpr int RS_PAIRS = RS_TPB / RS_LANES;
+// steer_fill's CHECK: no obstacle test, the linear loop over the rows (rpp::first_hit), or the obstacle index
+// (rppo::point_first_hit).  A template parameter and not a branch: a launch without the index carries none of its registers.
+constexpr int CHECK_NONE = 0, CHECK_LINEAR = 1, CHECK_INDEX = 2;
 constexpr int RS_KEPT = 3;          // table state: set_path kept this candidate (0 none, 1 candidate, 2 step too large)
 
 struct Args {
@@ -85,6 +89,7 @@ struct Args {
   const double* obs;      // [n_obs] rows (ox, oy, thr), thr = (size + robot_radius) ** 2 from the host
   int64_t n_obs;
   int32_t* hit;           // [n]  stage 1: -1 (ST_OK) / -2 (no curve); stage 2: the lowest obstacle index touched
+  rppo::Map omap;         // CHECK_INDEX: the grid over the same list
   // Bezier (curv / curv0 hold the offset per pair / of all pairs)
   const double* bez_w;    // [bez_np][3 bez_m - 3] the weight table of this solve
   double* bez_cp;         // [n][bez_m][2] control points: stage 1 writes them, or finds them there (bez_given)
@@ -376,10 +381,10 @@ __global__ __launch_bounds__(TPB) void steer_bezier_solve(Args a) {
 }
 
 // ---- stage 2 -------------------------------------------------------------------------------------------------------
-// <KIND, true, false> is the fill kernel alone.  With CHECK a lane past the last point does not leave: it stays as a copy
+// <KIND, true, CHECK_NONE> is the fill kernel alone.  With CHECK a lane past the last point does not leave: it stays as a copy
 // of the last point (the same pair, the same answer), so every lane of a wave takes part in the shuffles below.
 // hit[] is read as unsigned for the minimum: -1 (free) is then the largest value, and -2 belongs to pairs without points.
-template <int KIND, bool STORE, bool CHECK>
+template <int KIND, bool STORE, int CHECK>
 __global__ __launch_bounds__(TPB) void steer_fill(Args a) {
   int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
   const int64_t total = a.offsets[a.n];
@@ -422,7 +427,8 @@ __global__ __launch_bounds__(TPB) void steer_fill(Args a) {
     // The obstacle index is the same in every lane still in first_hit's loop, and a lane leaves the loop at its first
     // hit: the wave is done with the list as soon as all its lanes have one.
     const uint32_t NONE = 0xffffffffu;
-    const uint32_t h = (uint32_t)rpp::first_hit(a.obs, a.n_obs, x, y);
+    // With the index every lane walks the run of its own cell instead: the answer is the same int32.
+    const uint32_t h = (uint32_t)(CHECK == CHECK_INDEX ? rppo::point_first_hit(a.omap, x, y) : rpp::first_hit(a.obs, a.n_obs, x, y));
     if (!__any(h != NONE)) return;
     uint32_t* out = (uint32_t*)a.hit;
     const int pair = (int)lo;   // n <= 2^30

@@ -167,6 +167,7 @@ class SplineResult:
         self.c = c
         self.wp_offsets = wp_offsets
         self.hit = hit
+        self.obstacle_index = None   # with an obstacle list: what tested it (the obstacle_index keyword), a dict
         self.rc = rc
         self.kernel_ms = kernel_ms
 
@@ -243,9 +244,23 @@ class BatchSpline:
     """Natural cubic splines through batches of waypoint lists, sampled every ds; device buffers are kept between calls of
     run().  The splines of the last run(), fit() or fit1d() answer query()."""
 
-    def __init__(self, device=0):
+    def __init__(self, device=0, obstacle_index=None):
+        """obstacle_index: None, True or False, as BatchSteer's (also a settable attribute); result.obstacle_index says what
+        tested a run's obstacle list."""
+        _abi.obstacle_index_mode(obstacle_index)   # a ValueError comes before any device call
         self._spline = _abi.Spline(device)
         self._n = None   # splines of the last completed run / fit / fit1d
+        self.obstacle_index = obstacle_index
+
+    @property
+    def obstacle_index(self):
+        return self._obstacle_index
+
+    @obstacle_index.setter
+    def obstacle_index(self, v):
+        _abi.obstacle_index_mode(v)
+        self._spline.set_obstacle_index(v)
+        self._obstacle_index = v
 
     def close(self):
         self._spline.close()
@@ -290,6 +305,7 @@ class BatchSpline:
                            keep["offsets"], S.hits(len(rec)) if keep["obstacles"] is not None else None, rc, ms)
         if _abi.on_device(arrays):
             res.device_courses = _abi.DeviceCourses(_abi.SRC_SPLINE, S)
+        res.obstacle_index = S.obstacle_index_info() if keep["obstacles"] is not None else None
         return res
 
     def fit(self, waypoints, solve="device", c=None):

@@ -112,6 +112,7 @@ class SteerCandidates:
         self.shape = shape
         self.rc = rc
         self.kernel_ms = kernel_ms
+        self.obstacle_index = None   # with an obstacle list: what tested it (BatchSteer's obstacle_index), a dict
 
     def __len__(self):
         return len(self.status)
@@ -198,6 +199,7 @@ class SteerResult:
         self.control_points = control_points   # "bezier": (n, m, 2)
         self.rank = self.n_candidates = self.n_free = None   # plan_free()
         self.device_courses = None   # points="device": an _abi.DeviceCourses, and x, y, yaw are None
+        self.obstacle_index = None   # with an obstacle list: what tested it (BatchSteer's obstacle_index), a dict
 
     @property
     def free(self):
@@ -299,11 +301,27 @@ class BatchSteer:
     """Shortest Dubins ("dubins") or Reeds-Shepp ("rs") curves or Bezier curves ("bezier") for batches of pose pairs, or
     LQR rollouts ("lqr") for batches of point pairs; device buffers are kept between calls of plan()."""
 
-    def __init__(self, kind, device=0):
+    def __init__(self, kind, device=0, obstacle_index=None):
+        """obstacle_index: how a list of circles is tested -- None: through the obstacle index (a grid over the list, a
+        point reads its own cell) when the list has more than 256 circles, True: always, False: never (every point against
+        every circle).  hit is the same either way; also a settable attribute.  result.obstacle_index says what served a
+        batch: {"mode", "used", "reason", and the grid's fields}, or None without a list."""
         if kind not in KINDS:
             raise ValueError("BatchSteer: kind is 'dubins', 'rs', 'lqr' or 'bezier', not %r" % (kind,))
+        _abi.obstacle_index_mode(obstacle_index)   # a ValueError comes before any device call
         self.kind = KINDS[kind]
         self._steer = _abi.Steer(device)
+        self.obstacle_index = obstacle_index
+
+    @property
+    def obstacle_index(self):
+        return self._obstacle_index
+
+    @obstacle_index.setter
+    def obstacle_index(self, v):
+        _abi.obstacle_index_mode(v)
+        self._steer.set_obstacle_index(v)
+        self._obstacle_index = v
 
     def close(self):
         self._steer.close()
@@ -363,7 +381,7 @@ class BatchSteer:
                           (len(st), len(go)) if product else None, rc, S.kernel_ms(), hit=S.hits() if len(ob) else None)
         if _abi.on_device(points):
             res.device_courses = _abi.DeviceCourses(_abi.SRC_STEER, S)
-        return res
+        return self._served(res, ob)
 
     def _solve_all(self, what, starts, goals, curvature, step_size, selected_types, points, product, obstacle_list,
                    robot_radius):
@@ -394,7 +412,8 @@ class BatchSteer:
                                         obstacle_list, robot_radius)
         S = self._steer
         summary = S.cand_summary(hits=len(ob) > 0, offsets=bool(points))
-        return SteerCandidates(self.kind, summary, S.cand_points() if points else None, shape, rc, S.cand_counts()[3])
+        return self._served(SteerCandidates(self.kind, summary, S.cand_points() if points else None, shape, rc,
+                                            S.cand_counts()[3]), ob)
 
     def plan_free(self, starts, goals, curvature, step_size=None, selected_types=None, points=True, product=False,
                   obstacle_list=None, robot_radius=0.0):
@@ -403,7 +422,7 @@ class BatchSteer:
         none) the row is plan()'s.  The SteerResult has rank, n_candidates and n_free beside plan()'s columns."""
         if obstacle_list is None or len(np.asarray(obstacle_list).reshape(-1)) == 0:
             raise ValueError("BatchSteer.plan_free: an obstacle list is required")
-        rc, shape, _ = self._solve_all("plan_free", starts, goals, curvature, step_size, selected_types, points, product,
+        rc, shape, ob = self._solve_all("plan_free", starts, goals, curvature, step_size, selected_types, points, product,
                                        obstacle_list, robot_radius)
         S = self._steer
         rc, _, rank, n_free = S.select_free()
@@ -414,7 +433,7 @@ class BatchSteer:
             res.device_courses = _abi.DeviceCourses(_abi.SRC_STEER, S)
         res.rank, res.n_free = rank, n_free
         res.n_candidates = np.diff(S.cand_offsets()).astype(np.int32)
-        return res
+        return self._served(res, ob)
 
     def plan_control_points(self, control_points, n_points=100, curvature=True, points=True, obstacle_list=None,
                             robot_radius=0.0):
@@ -443,7 +462,7 @@ class BatchSteer:
                           kmax=S.kmax() if curvature else None, control_points=S.control_points())
         if _abi.on_device(points):
             res.device_courses = _abi.DeviceCourses(_abi.SRC_STEER, S)
-        return res
+        return self._served(res, ob)
 
     def _set_obstacles(self, obstacle_list, robot_radius):
         S = self._steer
@@ -451,6 +470,12 @@ class BatchSteer:
         if len(ob) or S.n_obstacles:
             S.set_obstacles(ob, robot_radius)
         return ob
+
+    def _served(self, res, ob):
+        """res with the obstacle index info of the list it was tested against"""
+        info = getattr(self._steer, "obstacle_index_info", None)   # (a stand-in for _abi.Steer may have none)
+        res.obstacle_index = info() if len(ob) and info else None
+        return res
 
     def _plan_lqr(self, starts, goals, curvature, step_size, selected_types, points, product, obstacle_list, robot_radius,
                   resample, max_time, goal_dist):
@@ -465,6 +490,6 @@ class BatchSteer:
         rc = S.solve_lqr(st, go, step_size if resample else 0.0, max_time, goal_dist, points=points, product=product)
         status, length, nseg, seglen, modes, off = S.summary(offsets=bool(points))
         xyz = S.points(yaw=False) if points else None
-        return SteerResult(self.kind, status, length, nseg, seglen, modes, off, xyz,
-                           (len(st), len(go)) if product else None, rc, S.kernel_ms(), hit=S.hits() if len(ob) else None,
-                           end=S.ends(), resampled=bool(resample))
+        return self._served(SteerResult(self.kind, status, length, nseg, seglen, modes, off, xyz,
+                                        (len(st), len(go)) if product else None, rc, S.kernel_ms(),
+                                        hit=S.hits() if len(ob) else None, end=S.ends(), resampled=bool(resample)), ob)
