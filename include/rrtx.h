@@ -33,7 +33,7 @@ extern "C" {
                                 rrtx_steer_get_cand_summary, rrtx_steer_get_cand_points, rrtx_steer_select_free, rrtx_tracker_run_from,
                                 rrtx_tracker_get_winners, rrtx_tracker_get_goals, rrtx_*_get_generation, rrtx_gather_courses, rrtx_get_course_counts,
                                 rrtx_get_courses, rrtx_get_course_generation, RRTX_SRC_PLANNER, rrtx_query_goals and its getters,
-                                rrtx_set_obstacle_map and its getters); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
+                                rrtx_set_obstacle_map and its getters, rrtx_*_set_obstacle_index and their getters, the tracker's included); 5: rrtx_stats.passes_shared; 2: rrtx_params.step_size, RRTX_ALGO_RS, rrtx_get_path_yaw; 3: RRTX_PARTIAL,
                                 rrtx_copy_results_device, per-instance yaw and informed rotation; 4: rrtx_plan_many,
                                 rrtx_selfcheck, rrtx_stats.main_shape / main_f32, rrtx_plan_begin / _step, rrtx_set_launch_bound,
                                 RRTX_ST_REF_HANGS, rrtx_rccl_* */
@@ -755,7 +755,8 @@ typedef struct rrtx_track_batch {
  * empty run.  RRTX_E_INVALID, before any HIP call (also on a host without a device): a NULL pointer (obstacles may be
  * NULL when n_obstacles is 0, and x / y / yaw when the courses hold no point in all), n_obstacles < 0, n < 0 or n > 2^30,
  * offsets or obs_offsets that do not start at 0 or that decrease, obs_offsets[n] > n_obstacles, more than 2^31 - 1 points in all, a pose, obstacle,
- * radius, start state or per-course value that is not finite, more than 64 obstacles in one list, or parameters outside
+ * radius, start state or per-course value that is not finite, more than 64 obstacles in one list (unless the tracker's
+ * obstacle index is on, rrtx_tracker_set_obstacle_index below), or parameters outside
  * dt > 0, 0 <= T, T / dt <= 1e6, Lf > 0, L > 0, 0 <= steer_max <= 0.79 (as rrtx_track_planned).  After these checks a host
  * without a device gets RRTX_E_NO_DEVICE. */
 int rrtx_tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_batch* b);
@@ -769,6 +770,29 @@ int rrtx_tracker_get_arrays(rrtx_tracker* t, double* x, double* y, double* yaw, 
                             int64_t cap);
 /* HIP-event time of the kernels of the last run (both launches) */
 int rrtx_tracker_get_kernel_ms(rrtx_tracker* t, double* kernel_ms);
+/* ---- the obstacle index of the tracker (csrc/rpp_obsgrid.h point_first_hit, csrc/rpp_track.h pend_*) -------------------------
+ * A tracker on which nothing is set tests lane k of a wave against obstacle k: at most 64 obstacles in one list, more is
+ * RRTX_E_INVALID.  With RRTX_OBSIDX_ON the shared list of rrtx_tracker_run and rrtx_tracker_run_from goes through the index
+ * of rrtx_steer_set_obstacle_index instead (the same build, the same rules) and may hold 0 .. 2^20 rows.  The TRACK_FAIL_COLL
+ * bit is an OR over the trajectory points of "some circle touches this point", and the index answers that per point for the
+ * whole list, so every record and array is what the 64-lane form gives where both apply, bit for bit.
+ * Mode: RRTX_OBSIDX_OFF (the state of a new tracker) or RRTX_OBSIDX_ON.  RRTX_OBSIDX_AUTO is refused: it would have to accept
+ * lists that a tracker with nothing set refuses today, so the choice is the caller's.  RRTX_E_INVALID for AUTO, any other
+ * value and a NULL tracker.  Takes effect at the next run.
+ * In mode ON, among the argument checks of a run (before any HIP call, also on a host without a device): RRTX_E_INVALID for
+ * obs_offsets != NULL (the index serves the shared list only), for more than 2^20 rows, and for
+ * robot_radius_per_course != 0 with n_obstacles > 0 (an item holds one threshold per circle).  Then by list: no rows --
+ * reason RRTX_OBSIDX_REASON_EMPTY, nothing is tested; the index is usable -- used = 1; it is not (RRTX_OBSIDX_REASON_NOT_FINITE,
+ * _RUN_TOO_LONG) and the list has at most 64 rows -- the lane-per-obstacle form runs, used = 0 with that reason; it is not
+ * and the list has more rows -- RRTX_E_INVALID naming the reason, nothing is launched and the last run and its getters
+ * stay as they were.  The build is kept while the rows, the radius and RRTX_OBSMAP_CELLS stay what they were. */
+int rrtx_tracker_set_obstacle_index(rrtx_tracker* t, int32_t mode);
+/* What served the list of the last completed run (reason RRTX_OBSIDX_REASON_EMPTY before one), and the mode as set */
+int rrtx_tracker_get_obstacle_index_info(rrtx_tracker* t, rrtx_obstacle_index_info* info);
+/* The index of the last completed run as built, shaped like rrtx_steer_get_obstacle_index; RRTX_E_STATE when the index did
+ * not serve it */
+int rrtx_tracker_get_obstacle_index(rrtx_tracker* t, int32_t* cell_start, rrtx_obstacle_item* items, int64_t cap_items,
+                                    rrtx_obstacle_item* wide, int64_t cap_wide);
 
 /* ---- tracking the courses a producer left on the device (csrc/rrt_track.hip.h: track_source_kernel) ----------------------
  * rrt_10 keeps its whole chain on the device for its own tree: candidates, roll-outs, search_best_feasible_path

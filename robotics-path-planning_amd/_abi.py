@@ -63,7 +63,8 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
            "rrtx_set_obstacle_map", "rrtx_get_obstacle_map_info", "rrtx_get_obstacle_map",
            "rrtx_steer_set_obstacle_index", "rrtx_steer_get_obstacle_index_info", "rrtx_steer_get_obstacle_index",
            "rrtx_spline_set_obstacle_index", "rrtx_spline_get_obstacle_index_info",
-           "rrtx_bspline_set_obstacle_index", "rrtx_bspline_get_obstacle_index_info"]
+           "rrtx_bspline_set_obstacle_index", "rrtx_bspline_get_obstacle_index_info",
+           "rrtx_tracker_set_obstacle_index", "rrtx_tracker_get_obstacle_index_info", "rrtx_tracker_get_obstacle_index"]
 OBSIDX_AUTO, OBSIDX_ON, OBSIDX_OFF, OBSIDX_MIN = 0, 1, 2, 256                          # include/rrtx.h: #define RRTX_OBSIDX_*
 OBSIDX_REASONS = ("used", "off", "below the threshold", "run too long", "non-finite reach", "empty")   # RRTX_OBSIDX_REASON_*
 OBSTACLE_TILE_MAX, OBSTACLE_MAP_MAX = 256, 1 << 20   # csrc MAX_OBS (rrtx_set_obstacles), rpp_obsgrid.h M_MAX (rrtx_set_obstacle_map)
@@ -253,6 +254,14 @@ class ObstacleMapInfo(C.Structure):
                 ("n_circles", C.c_int64), ("n_items", C.c_int64), ("n_wide", C.c_int64), ("build_ms", C.c_double)]
 
 
+def tracker_obstacle_index_mode(obstacle_index):
+    """The `obstacle_index` keyword of BatchTrack as an RRTX_OBSIDX_* mode: True or False.  None (automatic) is refused: it
+    would have to accept lists that a tracker with nothing set refuses."""
+    if obstacle_index is True or obstacle_index is False:
+        return OBSIDX_ON if obstacle_index else OBSIDX_OFF
+    raise ValueError("BatchTrack: obstacle_index is True or False, got %r" % (obstacle_index,))
+
+
 class ObstacleIndexInfo(C.Structure):
     """rrtx_obstacle_index_info"""
     _fields_ = [("mode", C.c_int32), ("used", C.c_int32), ("reason", C.c_int32), ("reserved", C.c_int32),
@@ -377,6 +386,9 @@ def load():
     L.rrtx_tracker_run_from.argtypes = [vp, C.POINTER(TrackParams), C.POINTER(TrackSource), C.POINTER(TrackBatch)]
     L.rrtx_tracker_get_winners.argtypes = [vp, vp, i64p]
     L.rrtx_tracker_get_goals.argtypes = [vp, vp]
+    L.rrtx_tracker_set_obstacle_index.argtypes = [vp, i32]
+    L.rrtx_tracker_get_obstacle_index_info.argtypes = [vp, C.POINTER(ObstacleIndexInfo)]
+    L.rrtx_tracker_get_obstacle_index.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int64]
     L.rrtx_gather_courses.argtypes = [vp, i32, i32]
     L.rrtx_get_course_counts.argtypes = [vp, vp, i64p, C.POINTER(i32), C.POINTER(C.c_double)]
     L.rrtx_get_courses.argtypes = [vp, vp, vp, vp, C.c_int64]
@@ -1261,6 +1273,21 @@ class Tracker(_DevObject):
     manager.  It owns the device buffers of its runs, so repeated runs reuse them."""
 
     _prefix = "tracker"
+
+    def set_obstacle_index(self, obstacle_index):
+        """True or False (tracker_obstacle_index_mode): rrtx_tracker_set_obstacle_index takes RRTX_OBSIDX_ON and _OFF only."""
+        self._chk(self.L.rrtx_tracker_set_obstacle_index(self._s, tracker_obstacle_index_mode(obstacle_index)),
+                  "rrtx_tracker_set_obstacle_index")
+
+    def obstacle_index(self):
+        """(info, cell_start, items, wide) of the index that served the last run, as Steer.obstacle_index gives a steer's."""
+        info = self.obstacle_index_info()
+        cell_start = np.zeros(info["nx"] * info["ny"] + 1, dtype=np.int32)
+        items, wide = np.zeros(info["n_items"], dtype=OBSTACLE_ITEM), np.zeros(info["n_wide"], dtype=OBSTACLE_ITEM)
+        self._chk(self.L.rrtx_tracker_get_obstacle_index(self._s, cell_start.ctypes.data, items.ctypes.data if len(items) else None,
+                                                         len(items), wide.ctypes.data if len(wide) else None, len(wide)),
+                  "rrtx_tracker_get_obstacle_index")
+        return info, cell_start, items, wide
 
     def run(self, params, batch):
         """params: TrackParams; batch: TrackBatch (its arrays are kept alive by the caller).  Returns 0 or RRTX_PARTIAL."""

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(TPB) void goal_roll_kernel(GoalTrackArgs a, int sto
         o7 = a.out + a.arr_off[q];
       }
       const rppt::State s0 = {-0.0, -0.0, 0.0, 0.0};   // :1309
-      rppt::roll_course(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, a.out_total, r);
+      rppt::roll_course<rppt::CHECK_LINEAR>(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, a.out_total, r);
       if (o7 && lane == 0 && r.find && r.n == ocap) {   // :1519-1521: the goal pose behind x, y, yaw; the other four end in NaN
         const double nan = rpp::b2d(0x7ff8000000000000ULL);
         o7[r.n] = gx;

@@ -12,6 +12,7 @@
 #pragma once
 #include "rpp_core.h"
 #include "rpp_dubins.h"
+#include "rpp_obsgrid.h"
 
 namespace rppt {
 
@@ -262,13 +263,62 @@ RPP_HD static inline bool is_candidate(double x, double y, double yaw, double gx
   return rpp::py_hypot(x - gx, y - gy) <= P.xy_th && rpp::dabs(yaw - gyaw) <= P.yaw_th;
 }
 
+// ---- the collision test of a roll-out (F_COLL): "some circle touches some appended point", an OR over the points -------------
+// The OR does not depend on the order the points are tested in, nor on when.  The kernels' lane-per-obstacle form (at most 64
+// circles) tests every point as it is appended; the obstacle-index form (rrt_track.hip.h CHECK_INDEX, any number of circles)
+// defers: the point of step cnt is parked in lane pend_lane(cnt), and a wave-wide flush -- every lane asks
+// rppo::point_first_hit for its own parked point -- runs when the 64 lanes are full and once behind the loop for the rest.
+// The index's dependent loads (cell_start, then the items) so leave the serial step loop: one flush per 64 steps.
+constexpr int PEND = 64;   // parked points of a wave, one per lane
+// the lane that parks the point of step cnt (cnt = 0 is the start state)
+RPP_HD static inline int pend_lane(int cnt) { return cnt & (PEND - 1); }
+// whether a flush of all PEND lanes is due once `cnt` points have been appended
+RPP_HD static inline bool pend_flush_due(int cnt) { return cnt > 0 && (cnt & (PEND - 1)) == 0; }
+// whether `lane` still parks an untested point behind a loop that appended cnt points (the final flush)
+RPP_HD static inline bool pend_final(int lane, int cnt) { return lane < (cnt & (PEND - 1)); }
+
+// every circle of the list against the point at once: the reference's check_collision :321-334 per point
+struct LinearCheck {
+  const double *ox, *oy, *othr;
+  int m;
+  RPP_HD void point(int, double x, double y, int* hit) const {
+    for (int o = 0; o < m; o++) {
+      const double dx = ox[o] - x, dy = oy[o] - y;
+      if (dx * dx + dy * dy <= othr[o]) *hit = 1;
+    }
+  }
+  RPP_HD void finish(int, int*) const {}
+};
+
+// the deferred form on one thread, lane by lane as the kernel does it wave-wide
+struct DeferredIndexCheck {
+  rppo::Map map;
+  double px[PEND], py[PEND];
+  RPP_HD void flush(int lanes, int* hit) const {
+    for (int l = 0; l < lanes; l++)
+      if (rppo::point_first_hit(map, px[l], py[l]) >= 0) *hit = 1;
+  }
+  RPP_HD void point(int cnt, double x, double y, int* hit) {
+    px[pend_lane(cnt)] = x;
+    py[pend_lane(cnt)] = y;
+    if (pend_flush_due(cnt + 1)) flush(PEND, hit);
+  }
+  RPP_HD void finish(int cnt, int* hit) const {
+    for (int l = 0; l < PEND; l++)
+      if (pend_final(l, cnt) && rppo::point_first_hit(map, px[l], py[l]) >= 0) *hit = 1;
+  }
+};
+
 // check_tracking_path_is_feasible :1526-1564 on one thread (host tests; the kernel runs the same pieces wave-wide).
 // cx / cy / cyaw: the course in driving order (start ... goal), n points, with room for EXT_MAX more; sp: n + EXT_MAX.
 // out[7] (x, y, yaw, v, t, a, d; each `cap` doubles) may be null.  start: the state the roll-out begins in; the default
 // is the reference's hard-coded State(-0.0, -0.0, 0.0, 0.0) (:1309).
-RPP_HD static inline void track_course(double* cx, double* cy, double* cyaw, signed char* sp, int n, const double* ox,
-                                       const double* oy, const double* othr, int m, const Params& P, double* const* out,
-                                       int cap, Record* r, State start = State{-0.0, -0.0, 0.0, 0.0}) {
+// `check` answers the collision test: check.point(cnt, x, y, &hit) per appended point, check.finish(cnt, &hit) once behind
+// the loop (LinearCheck, DeferredIndexCheck above).
+template <class Check>
+RPP_HD static inline void track_course_with(double* cx, double* cy, double* cyaw, signed char* sp, int n, Check& check,
+                                            const Params& P, double* const* out, int cap, Record* r,
+                                            State start = State{-0.0, -0.0, 0.0, 0.0}) {
   r->find = 0;
   r->n = 0;
   r->fail = 0;
@@ -299,10 +349,7 @@ RPP_HD static inline void track_course(double* cx, double* cy, double* cyaw, sig
       out[5][cnt] = a;
       out[6][cnt] = d;
     }
-    for (int o = 0; o < m; o++) {
-      const double dx = ox[o] - s.x, dy = oy[o] - s.y;
-      if (dx * dx + dy * dy <= othr[o]) hit = 1;
-    }
+    check.point(cnt, s.x, s.y, &hit);
     vsum = vsum + rpp::dabs(s.v);
     last_yaw = s.yaw;
     tlast = time;
@@ -321,10 +368,18 @@ RPP_HD static inline void track_course(double* cx, double* cy, double* cyaw, sig
     append(ai, di);
     if (ood) break;
   }
+  check.finish(cnt, &hit);
   r->n = cnt;
   r->tlast = tlast;
   r->ood = ood;
   judge(r, reached, rpp::angle_mod_pi(last_yaw), gyaw, vsum, origin_travel(cx, cy, n), hit, P);
+}
+
+RPP_HD static inline void track_course(double* cx, double* cy, double* cyaw, signed char* sp, int n, const double* ox,
+                                       const double* oy, const double* othr, int m, const Params& P, double* const* out,
+                                       int cap, Record* r, State start = State{-0.0, -0.0, 0.0, 0.0}) {
+  LinearCheck check = {ox, oy, othr, m};
+  track_course_with(cx, cy, cyaw, sp, n, check, P, out, cap, r, start);
 }
 
 }  // namespace rppt

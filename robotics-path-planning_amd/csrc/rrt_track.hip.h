@@ -25,7 +25,8 @@
 //
 // Capacities: a course (with its extension) of up to LDS_PTS points is held in LDS (x, y; the speed profile always is, one
 // byte per point), up to SLAB_PTS points in the wave's global slab; a longer one sets RRTX_ST_OVERFLOW for the instance.
-// Obstacles: at most 64 per instance (the Reeds-Shepp planner's limit).
+// Obstacles: at most 64 per instance (the Reeds-Shepp planner's limit) in the lane-per-obstacle form (CHECK_LINEAR); the two
+// data kernels also come in an obstacle-index form (CHECK_INDEX) that takes a shared list of up to 2^20 circles.
 #pragma once
 #include "rpp_track.h"
 #include "rrt_rs.hip.h"
@@ -37,6 +38,9 @@ constexpr int LDS_PTS = 512;
 constexpr int SLAB_PTS = 1024;
 constexpr int MAX_STEPS = 1 << 22;   // never spin on the device whatever T / dt is
 constexpr int ST_OVERFLOW = 4, ST_RAISES = 32, ST_OOD = 16;   // include/rrtx.h status bits (OOD reported as UNSUPPORTED)
+// how a roll-out tests its points against the circles: lane k against circle k (at most 64), or every lane's parked point
+// through the obstacle index (rpp_obsgrid.h point_first_hit, rpp_track.h pend_*: any number of circles)
+constexpr int CHECK_LINEAR = 1, CHECK_INDEX = 2;
 
 struct Outcome {      // per instance
   int32_t flag;       // search_best_feasible_path found a feasible roll-out
@@ -133,9 +137,14 @@ __global__ void track_pick_kernel(TrackArgs a) {
 // o7 + q * os, at most ocap entries each).  Called by the whole wave with r.ood == 0 after the lanes wrote cx / cy / gcw[0 ..
 // total - 1] (not yet synchronised); cx / cy hold total + EXT_MAX points, lsp and s_n are the block's LDS.  ob: this lane has
 // an obstacle (obx, oby, its threshold obt).  s: the state the roll-out starts in.
+// CHECK_INDEX: ob / obx / oby / obt are not read; mp is the index over the list.  Lane pend_lane(cnt) parks the point of step
+// cnt (s is wave-uniform: one select per coordinate), every 64 steps and once behind the loop -- however it ended -- each lane
+// asks point_first_hit for its own parked point.  The store pass (o7 != nullptr) writes no record and tests nothing.
+template <int CHECK>
 __device__ __forceinline__ void roll_course(double* cx, double* cy, double* gcw, signed char* lsp, int32_t* s_n, int total,
                                             double gx, double gy, double gyaw, bool ob, double obx, double oby, double obt,
-                                            const Params& P, State s, double* o7, int ocap, int64_t os, Record& r) {
+                                            const Params& P, State s, double* o7, int ocap, int64_t os, Record& r,
+                                            const rppo::Map* mp = nullptr) {
   const int lane = threadIdx.x;
   __syncthreads();
   if (lane == 0) *s_n = extend_path(cx, cy, gcw, total, P);
@@ -150,6 +159,7 @@ __device__ __forceinline__ void roll_course(double* cx, double* cy, double* gcw,
     // ---- closed_loop_prediction :1307-1372
     double time = 0.0, vsum = 0.0, last_yaw = 0.0, tlast = 0.0;
     int cnt = 0, hit = 0, ood = 0, reached = 0;
+    double ppx = 0.0, ppy = 0.0;   // CHECK_INDEX: the point this lane parks
     auto append = [&](double ai, double di) {
       if (o7 && lane == 0 && cnt < ocap) {
         o7[cnt] = s.x;
@@ -160,14 +170,23 @@ __device__ __forceinline__ void roll_course(double* cx, double* cy, double* gcw,
         o7[5 * os + cnt] = ai;
         o7[6 * os + cnt] = di;
       }
-      if (ob) {
-        const double dx = obx - s.x, dy = oby - s.y;
-        if (dx * dx + dy * dy <= obt) hit = 1;
+      if constexpr (CHECK == CHECK_LINEAR) {
+        if (ob) {
+          const double dx = obx - s.x, dy = oby - s.y;
+          if (dx * dx + dy * dy <= obt) hit = 1;
+        }
+      } else if (!o7) {
+        const bool mine = lane == pend_lane(cnt);
+        ppx = mine ? s.x : ppx;
+        ppy = mine ? s.y : ppy;
       }
       vsum = vsum + rpp::dabs(s.v);
       last_yaw = s.yaw;
       tlast = time;
       cnt++;
+      if constexpr (CHECK == CHECK_INDEX) {
+        if (!o7 && pend_flush_due(cnt) && rppo::point_first_hit(*mp, ppx, ppy) >= 0) hit = 1;
+      }
     };
     // calc_target_index :1286-1293: the lanes share the np.hypot scan; first minimum, lowest index
     auto scan = [&](double* dis) {
@@ -200,6 +219,9 @@ __device__ __forceinline__ void roll_course(double* cx, double* cy, double* gcw,
     r.n = cnt;
     r.tlast = tlast;
     r.ood = ood ? 1 : 0;
+    if constexpr (CHECK == CHECK_INDEX) {   // the final flush: reached, ood, time-out and MAX_STEPS all come through here
+      if (!o7 && pend_final(lane, cnt) && rppo::point_first_hit(*mp, ppx, ppy) >= 0) hit = 1;
+    }
     const int any_hit = __ballot(hit) != 0ULL;
     judge(&r, reached, rpp::angle_mod_pi(last_yaw), gyaw, vsum, origin_travel(cx, cy, n), any_hit, P);
   }
@@ -289,7 +311,7 @@ __global__ __launch_bounds__(TPB) void track_roll_kernel(TrackArgs a, int store)
       }
       const int64_t os = (int64_t)ocap + 1;
       const State s0 = {-0.0, -0.0, 0.0, 0.0};
-      roll_course(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, os, r);
+      roll_course<CHECK_LINEAR>(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, os, r);
       if (o7 && lane == 0 && r.find && r.n == ocap) {   // :1519-1521: the goal pose behind x, y, yaw only
         o7[r.n] = gx;
         o7[os + r.n] = gy;
@@ -323,7 +345,9 @@ struct CourseArgs {
 
 // store = 0: one Record per course; store = 1: every course whose record has ood == 0 is rolled out again and its seven
 // arrays are stored.  A course of fewer than 3 points reports ood = 2, one of more than SLAB_PTS - EXT_MAX points ood = 3.
-__global__ __launch_bounds__(TPB) void track_courses_kernel(CourseArgs a, int store) {
+// CHECK_INDEX: mp is the index over the shared list; a.ox / oy / othr / obs_off are not read.
+template <int CHECK>
+__global__ __launch_bounds__(TPB) void track_courses_kernel(CourseArgs a, int store, rppo::Map mp) {
   __shared__ double lcx[LDS_PTS], lcy[LDS_PTS];
   __shared__ signed char lsp[SLAB_PTS];
   __shared__ int32_t s_job, s_n;
@@ -368,13 +392,16 @@ __global__ __launch_bounds__(TPB) void track_courses_kernel(CourseArgs a, int st
         s0.yaw = a.start[4 * c + 2];
         s0.v = a.start[4 * c + 3];
       }
-      const int64_t ob = a.obs_off ? a.obs_off[c] : 0;
-      const int m = a.obs_off ? (int)(a.obs_off[c + 1] - ob) : a.m_shared;
+      int m = 0;
       double obx = 0.0, oby = 0.0, obt = -1.0;
-      if (lane < m) {
-        obx = a.ox[ob + lane];
-        oby = a.oy[ob + lane];
-        obt = a.othr[ob + c * a.thr_stride + lane];
+      if constexpr (CHECK == CHECK_LINEAR) {
+        const int64_t ob = a.obs_off ? a.obs_off[c] : 0;
+        m = a.obs_off ? (int)(a.obs_off[c + 1] - ob) : a.m_shared;
+        if (lane < m) {
+          obx = a.ox[ob + lane];
+          oby = a.oy[ob + lane];
+          obt = a.othr[ob + c * a.thr_stride + lane];
+        }
       }
       double* o7 = nullptr;
       int ocap = 0;
@@ -382,7 +409,7 @@ __global__ __launch_bounds__(TPB) void track_courses_kernel(CourseArgs a, int st
         ocap = a.rec[c].n;
         o7 = a.out + a.arr_off[c];
       }
-      roll_course(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, a.out_total, r);
+      roll_course<CHECK>(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, a.out_total, r, &mp);
     }
     if (!store && lane == 0) a.rec[c] = r;
   }
@@ -405,8 +432,9 @@ struct SourceArgs {
 // course the selection leaves out reports ood = 5 and its offsets and points are not read; while a course is copied into
 // LDS / the slab every x, y and yaw is tested for finiteness (one wave-wide OR, no second pass over the points), and a
 // course with a non-finite component reports ood = 4.  The host path refuses such a batch whole; here the host never sees
-// the points.
-__global__ __launch_bounds__(TPB) void track_source_kernel(SourceArgs s, int store) {
+// the points.  CHECK as track_courses_kernel.
+template <int CHECK>
+__global__ __launch_bounds__(TPB) void track_source_kernel(SourceArgs s, int store, rppo::Map mp) {
   __shared__ double lcx[LDS_PTS], lcy[LDS_PTS];
   __shared__ signed char lsp[SLAB_PTS];
   __shared__ int32_t s_job, s_n;
@@ -465,13 +493,16 @@ __global__ __launch_bounds__(TPB) void track_source_kernel(SourceArgs s, int sto
         s0.yaw = a.start[4 * c + 2];
         s0.v = a.start[4 * c + 3];
       }
-      const int64_t ob = a.obs_off ? a.obs_off[c] : 0;
-      const int m = a.obs_off ? (int)(a.obs_off[c + 1] - ob) : a.m_shared;
+      int m = 0;
       double obx = 0.0, oby = 0.0, obt = -1.0;
-      if (lane < m) {
-        obx = a.ox[ob + lane];
-        oby = a.oy[ob + lane];
-        obt = a.othr[ob + c * a.thr_stride + lane];
+      if constexpr (CHECK == CHECK_LINEAR) {
+        const int64_t ob = a.obs_off ? a.obs_off[c] : 0;
+        m = a.obs_off ? (int)(a.obs_off[c + 1] - ob) : a.m_shared;
+        if (lane < m) {
+          obx = a.ox[ob + lane];
+          oby = a.oy[ob + lane];
+          obt = a.othr[ob + c * a.thr_stride + lane];
+        }
       }
       double* o7 = nullptr;
       int ocap = 0;
@@ -479,7 +510,7 @@ __global__ __launch_bounds__(TPB) void track_source_kernel(SourceArgs s, int sto
         ocap = a.rec[c].n;
         o7 = a.out + a.arr_off[c];
       }
-      roll_course(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, a.out_total, r);
+      roll_course<CHECK>(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, a.out_total, r, &mp);
     }
     if (!store && lane == 0) {
       a.rec[c] = r;

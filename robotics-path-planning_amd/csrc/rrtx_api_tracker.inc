@@ -15,7 +15,41 @@ struct rrtx_tracker : DevObj {
   bool from = false;
   int64_t group = 0;
   std::vector<int32_t> h_winner;
+  // the obstacle index (rrtx_tracker_set_obstacle_index): the build over the last list given in mode ON, and what served the
+  // last completed run -- a refused run leaves ix_used / ix_reason, and with them the getters, as they were
+  ObsIndex oi;
+  int ix_used = 0, ix_reason = RRTX_OBSIDX_REASON_EMPTY;
+  rrtx_tracker() { oi.mode = RRTX_OBSIDX_OFF; }
 };
+
+// Mode ON, among the argument checks (before any HIP call): what the index cannot take, or nullptr
+static const char* tracker_index_refusal(const rrtx_track_batch* b) {
+  if (b->obs_offsets) return "the obstacle index serves the shared list only (obs_offsets must be NULL)";
+  if (b->n_obstacles > rppo::M_MAX) return "more than 2^20 obstacles in the shared list";
+  if (b->robot_radius_per_course && b->n_obstacles > 0)
+    return "the obstacle index holds one threshold per circle: a robot radius per course cannot go with an obstacle list";
+  return nullptr;
+}
+
+// After every check of a run, before anything of the last run is touched: the index over the shared list in mode ON.
+// *indexed: CHECK_INDEX serves the run.  A list of more than 64 rows that the index cannot serve is RRTX_E_INVALID.
+static int tracker_index_decide(rrtx_tracker* t, const rrtx_track_batch* b, const char* fn, bool* indexed, int* reason) {
+  *indexed = false;
+  if (t->oi.mode != RRTX_OBSIDX_ON) {
+    *reason = rppo::index_reason(rppo::IDX_OFF, b->obs_offsets ? b->obs_offsets[b->n] : b->n_obstacles, true, 0);
+    return RRTX_OK;
+  }
+  if (int rc = obsindex_set_list(t, t->oi, b->obstacles, b->n_obstacles, b->robot_radius[0])) return rc;
+  *reason = t->oi.reason;
+  *indexed = t->oi.used != 0;
+  if (!*indexed && b->n_obstacles > rppt::TPB)
+    return fail(t, RRTX_E_INVALID,
+                std::string(fn) + "the obstacle index cannot serve this list (" +
+                    (*reason == RRTX_OBSIDX_REASON_RUN_TOO_LONG ? "run too long: a cell or the wide list would hold more than 4096 records"
+                                                                : "a threshold or reach of a circle is not finite") +
+                    ") and the lane-per-obstacle check takes at most 64 obstacles");
+  return RRTX_OK;
+}
 
 static_assert(rppt::SEL_ALL == RRTX_SELECT_ALL && rppt::SEL_FREE == RRTX_SELECT_FREE && rppt::SEL_MASK == RRTX_SELECT_MASK,
               "the selections of the header are the core's");
@@ -40,7 +74,9 @@ static int tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_
   if (pts > 0 && (!b->x || !b->y || !b->yaw)) return bad("x, y or yaw is NULL");
   if (b->n_obstacles < 0) return bad("n_obstacles is negative");
   if (b->n_obstacles > 0 && !b->obstacles) return bad("obstacles is NULL");
-  if (b->obs_offsets) {
+  if (t->oi.mode == RRTX_OBSIDX_ON) {
+    if (const char* m = tracker_index_refusal(b)) return bad(m);
+  } else if (b->obs_offsets) {
     if (!csr_ok(b->obs_offsets, n)) return bad("obs_offsets do not start at 0 or decrease");
     if (b->obs_offsets[n] > b->n_obstacles) return bad("obs_offsets end beyond n_obstacles");
     for (int64_t i = 0; i < n; i++)
@@ -57,9 +93,14 @@ static int tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_
   if (b->per_course && !all_finite(b->per_course, 3 * n)) return bad("a per-course value is not finite");
   if (!all_finite(&tp->target_speed, sizeof(*tp) / sizeof(double))) return bad("a parameter is not finite");
   if (int nd = t->need_device(fn)) return nd;
+  bool indexed = false;
+  int ix_reason = 0;
+  if (int irc = tracker_index_decide(t, b, fn, &indexed, &ix_reason)) return irc;
 
   t->ran = false;
   t->has_arrays = false;
+  t->ix_used = indexed;
+  t->ix_reason = ix_reason;
   t->n = n;
   t->n_steps = 0;
   t->kernel_ms = 0.0;
@@ -72,7 +113,8 @@ static int tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_
   }
   // obstacle table: SoA x, y and the thresholds (radius + robot_radius) ** 2 by the planners' routine; one threshold row per
   // obstacle row, or with one shared list and a radius per course n rows of the list's thresholds
-  const int64_t rows = b->obs_offsets ? b->obs_offsets[n] : b->n_obstacles;
+  // (the index form reads none of it: its items hold the circles)
+  const int64_t rows = indexed ? 0 : b->obs_offsets ? b->obs_offsets[n] : b->n_obstacles;
   const bool thr_per_course = !b->obs_offsets && b->robot_radius_per_course && rows > 0;
   std::vector<double> ox((size_t)rows), oy((size_t)rows), othr((size_t)(thr_per_course ? rows * n : rows));
   for (int64_t k = 0; k < rows; k++) {
@@ -134,7 +176,14 @@ static int tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_
   // first launch: the records
   t->h_rec.resize(N);
   float ms = 0.f;
-  rc = t->timed(&ms, [&] { hipLaunchKernelGGL(rppt::track_courses_kernel, dim3(blocks), dim3(rppt::TPB), 0, t->stream, a, 0); }, [&]() -> int {
+  const rppo::Map mp = indexed ? t->oi.map() : rppo::Map{};
+  auto roll = [&](int store) {
+    if (indexed)
+      hipLaunchKernelGGL((rppt::track_courses_kernel<rppt::CHECK_INDEX>), dim3(blocks), dim3(rppt::TPB), 0, t->stream, a, store, mp);
+    else
+      hipLaunchKernelGGL((rppt::track_courses_kernel<rppt::CHECK_LINEAR>), dim3(blocks), dim3(rppt::TPB), 0, t->stream, a, store, mp);
+  };
+  rc = t->timed(&ms, [&] { roll(0); }, [&]() -> int {
     HIPCHK(t, hipMemcpyAsync(t->h_rec.data(), t->rec.p, sizeof(rppt::Record) * N, hipMemcpyDeviceToHost, t->stream));
     return RRTX_OK;
   });
@@ -162,7 +211,7 @@ static int tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_
       a.out = t->out.as<double>();
       a.arr_off = t->arr_off.as<const int64_t>();
       a.out_total = tot;
-      rc = t->timed(&ms, [&] { hipLaunchKernelGGL(rppt::track_courses_kernel, dim3(blocks), dim3(rppt::TPB), 0, t->stream, a, 1); });
+      rc = t->timed(&ms, [&] { roll(1); });
       if (rc) return rc;
       t->kernel_ms += ms;
     }
@@ -297,7 +346,9 @@ static int tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const 
   if (!b->robot_radius) return bad("robot_radius is NULL");
   if (b->n_obstacles < 0) return bad("n_obstacles is negative");
   if (b->n_obstacles > 0 && !b->obstacles) return bad("obstacles is NULL");
-  if (b->obs_offsets) {
+  if (t->oi.mode == RRTX_OBSIDX_ON) {
+    if (const char* m = tracker_index_refusal(b)) return bad(m);
+  } else if (b->obs_offsets) {
     if (!csr_ok(b->obs_offsets, n)) return bad("obs_offsets do not start at 0 or decrease");
     if (b->obs_offsets[n] > b->n_obstacles) return bad("obs_offsets end beyond n_obstacles");
     for (int64_t i = 0; i < n; i++)
@@ -322,11 +373,16 @@ static int tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const 
     return state(src->kind == RRTX_SRC_PLANNER ? "RRTX_SELECT_FREE, but a planner's courses carry no hits"
                                                : "RRTX_SELECT_FREE, but the source ran without an obstacle list");
   if (n != v.n) return bad("n is not the source's course count");
+  bool indexed = false;
+  int ix_reason = 0;
+  if (int irc = tracker_index_decide(t, b, fn, &indexed, &ix_reason)) return irc;
 
   const int64_t g = src->group, n_groups = g ? n / g : 0;
   const bool winners_only = src->arrays_of == 1;
   t->ran = false;
   t->has_arrays = false;
+  t->ix_used = indexed;
+  t->ix_reason = ix_reason;
   t->from = true;
   t->group = g;
   t->n = n;
@@ -341,7 +397,8 @@ static int tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const 
     return RRTX_OK;
   }
   // obstacle table, as rrtx_tracker_run builds it
-  const int64_t rows = b->obs_offsets ? b->obs_offsets[n] : b->n_obstacles;
+  // (the index form reads none of it: its items hold the circles)
+  const int64_t rows = indexed ? 0 : b->obs_offsets ? b->obs_offsets[n] : b->n_obstacles;
   const bool thr_per_course = !b->obs_offsets && b->robot_radius_per_course && rows > 0;
   std::vector<double> ox((size_t)rows), oy((size_t)rows), othr((size_t)(thr_per_course ? rows * n : rows));
   for (int64_t k = 0; k < rows; k++) {
@@ -429,8 +486,15 @@ static int tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const 
   // first launch: the records, and with a group the pick over them
   t->h_rec.resize(N);
   float ms = 0.f;
+  const rppo::Map mp = indexed ? t->oi.map() : rppo::Map{};
+  auto roll = [&](int store) {
+    if (indexed)
+      hipLaunchKernelGGL((rppt::track_source_kernel<rppt::CHECK_INDEX>), dim3(blocks), dim3(rppt::TPB), 0, t->stream, sa, store, mp);
+    else
+      hipLaunchKernelGGL((rppt::track_source_kernel<rppt::CHECK_LINEAR>), dim3(blocks), dim3(rppt::TPB), 0, t->stream, sa, store, mp);
+  };
   rc = t->timed(&ms, [&] {
-    hipLaunchKernelGGL(rppt::track_source_kernel, dim3(blocks), dim3(rppt::TPB), 0, t->stream, sa, 0);
+    roll(0);
     if (g) hipLaunchKernelGGL(rppt::track_group_pick_kernel, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, t->stream, sa);
   }, [&]() -> int {
     HIPCHK(t, hipMemcpyAsync(t->h_rec.data(), t->rec.p, sizeof(rppt::Record) * N, hipMemcpyDeviceToHost, t->stream));
@@ -461,7 +525,7 @@ static int tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const 
       a.arr_off = t->arr_off.as<const int64_t>();
       a.out_total = tot;
       sa.winners_only = winners_only ? 1 : 0;
-      rc = t->timed(&ms, [&] { hipLaunchKernelGGL(rppt::track_source_kernel, dim3(blocks), dim3(rppt::TPB), 0, t->stream, sa, 1); });
+      rc = t->timed(&ms, [&] { roll(1); });
       if (rc) return rc;
       t->kernel_ms += ms;
     }
@@ -525,6 +589,34 @@ int rrtx_tracker_get_arrays(rrtx_tracker* t, double* x, double* y, double* yaw, 
     if (dst[k])
       if (int rc = t->fetch(dst[k], t->out.as<const double>() + k * tot, sizeof(double) * tot)) return rc;
   return RRTX_OK;
+}
+
+int rrtx_tracker_set_obstacle_index(rrtx_tracker* t, int32_t mode) {
+  const char* fn = "rrtx_tracker_set_obstacle_index: ";
+  if (!t) return fail(t, RRTX_E_INVALID, std::string(fn) + "the tracker is NULL");
+  if (mode != RRTX_OBSIDX_ON && mode != RRTX_OBSIDX_OFF)
+    return fail(t, RRTX_E_INVALID, std::string(fn) + "mode is RRTX_OBSIDX_ON or RRTX_OBSIDX_OFF (RRTX_OBSIDX_AUTO would have to "
+                                                     "accept lists that the default refuses)");
+  t->oi.mode = mode;
+  return RRTX_OK;
+}
+
+int rrtx_tracker_get_obstacle_index_info(rrtx_tracker* t, rrtx_obstacle_index_info* info) {
+  if (!t || !info) return fail(t, RRTX_E_INVALID, "rrtx_tracker_get_obstacle_index_info: a NULL pointer");
+  memset(info, 0, sizeof(*info));
+  info->mode = t->oi.mode;
+  info->used = t->ix_used;
+  info->reason = t->ix_reason;
+  if (t->ix_used) obstacle_grid_info(t->oi.grid, &info->map);
+  return RRTX_OK;
+}
+
+int rrtx_tracker_get_obstacle_index(rrtx_tracker* t, int32_t* cell_start, rrtx_obstacle_item* items, int64_t cap_items,
+                                    rrtx_obstacle_item* wide, int64_t cap_wide) {
+  const char* fn = "rrtx_tracker_get_obstacle_index: ";
+  if (!t) return fail(t, RRTX_E_INVALID, std::string(fn) + "the tracker is NULL");
+  if (!t->ix_used) return fail(t, RRTX_E_STATE, std::string(fn) + "the obstacle index did not serve the last run");
+  return obstacle_grid_fetch(t, t->oi.grid, fn, cell_start, items, cap_items, wide, cap_wide);
 }
 
 int rrtx_tracker_get_kernel_ms(rrtx_tracker* t, double* kernel_ms) {

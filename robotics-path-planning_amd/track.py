@@ -151,7 +151,8 @@ class TrackResult:
     all rows on first use -- which must come before the tracker's next run, or goals, best() and best_of() raise
     RrtxError.  A result of host courses holds everything it needs."""
 
-    def __init__(self, records, offsets, arrays, goals, rc=0, kernel_ms=0.0, course_len=None, winner=None, group=0):
+    def __init__(self, records, offsets, arrays, goals, rc=0, kernel_ms=0.0, course_len=None, winner=None, group=0,
+                 obstacle_index=None):
         self.find_goal = records["find_goal"].copy()
         self.length = records["len"].copy()
         self.fail = records["fail"].copy()
@@ -166,6 +167,7 @@ class TrackResult:
         self.rc = rc                # 0 or RRTX_PARTIAL
         self.kernel_ms = kernel_ms
         self.steps = int(offsets[-1])
+        self.obstacle_index = obstacle_index   # with an obstacle list: what tested it (BatchTrack's obstacle_index), a dict
 
     def __len__(self):
         return len(self.status)
@@ -231,12 +233,46 @@ class BatchTrack:
     """Pure-pursuit / PID tracking of batches of courses on the unicycle model and the four feasibility tests of
     check_tracking_path_is_feasible; device buffers are kept between calls of run()."""
 
+    _obstacle_index = False   # the state of a new tracker (rrtx_tracker_set_obstacle_index: RRTX_OBSIDX_OFF)
+
     def __init__(self, device=0, dt=0.05, L=0.9, steer_max=np.deg2rad(40.0), accel_max=5.0, Kp=2.0, Lf=0.5, T=100.0,
-                 goal_dis=0.5, stop_speed=0.5):
+                 goal_dis=0.5, stop_speed=0.5, obstacle_index=False):
+        """obstacle_index: False -- lane k of a wave tests obstacle k, at most 64 rows in a list; True -- the shared
+        obstacle_list goes through the obstacle index (a grid over the list, a trajectory point reads its own cell) and may
+        hold up to 2**20 rows; course_obstacles and a per-course robot_radius with a list are then refused.  Records and
+        arrays are the same either way; also a settable attribute.  result.obstacle_index says what served a batch:
+        {"mode", "used", "reason", and the grid's fields}, or None without a list."""
+        _abi.tracker_obstacle_index_mode(obstacle_index)   # a ValueError comes before any device call
         self.model = dict(dt=dt, L=L, steer_max=steer_max, accel_max=accel_max, Kp=Kp, Lf=Lf, T=T, goal_dis=goal_dis,
                           stop_speed=stop_speed)
         self._tracker = _abi.Tracker(device)
         self._runs_from = 0   # runs over device-resident courses so far: a result's unfetched goals are its own run's only
+        if obstacle_index:
+            self.obstacle_index = True
+
+    @property
+    def obstacle_index(self):
+        return self._obstacle_index
+
+    @obstacle_index.setter
+    def obstacle_index(self, v):
+        _abi.tracker_obstacle_index_mode(v)
+        self._tracker.set_obstacle_index(v)
+        self._obstacle_index = v
+
+    def _index_checks(self, obstacle_list, course_obstacles, robot_radius):
+        """With the obstacle index on: what it cannot take, before any device call."""
+        if not self._obstacle_index:
+            return
+        if course_obstacles is not None:
+            raise ValueError("BatchTrack: the obstacle index serves the shared obstacle_list only, not course_obstacles")
+        if np.ndim(robot_radius) != 0 and len(obstacle_list):
+            raise ValueError("BatchTrack: the obstacle index takes one robot_radius for the obstacle_list, not one per course")
+
+    def _served(self, n_obstacles):
+        """The obstacle index info of the run just made, None without a list"""
+        info = getattr(self._tracker, "obstacle_index_info", None)   # (a stand-in for _abi.Tracker may have none)
+        return info() if n_obstacles and info else None
 
     def close(self):
         self._tracker.close()
@@ -252,7 +288,8 @@ class BatchTrack:
             yaw_th=np.deg2rad(3.0), invalid_travel_ratio=5.0, start_state=None, arrays=True, select=None, group=None):
         """courses: a list of (cx, cy, cyaw) triples, a CSR tuple (offsets, x, y, yaw), or a SteerResult solved with
         points (a pair without a path is an empty course: status 2).  obstacle_list: rows (x, y, radius) for every
-        course, or course_obstacles: one such list per course (at most 64 rows in a list).  robot_radius, target_speed,
+        course, or course_obstacles: one such list per course (at most 64 rows in a list; with obstacle_index=True the shared
+        obstacle_list may hold up to 2**20 rows).  robot_radius, target_speed,
         yaw_th, invalid_travel_ratio: a scalar or one value per course.  start_state: None, one (x, y, yaw, v) or one
         row per course.
         courses may also be a PlannerCourses (BatchPlanner.courses(order="driving")): with host arrays it is tracked like
@@ -265,6 +302,7 @@ class BatchTrack:
         group's best (TrackResult.winner, best_of); True: ng of a product-mode steer result.  arrays="best": only the
         winners' seven arrays are produced.  The goal poses of such a result are fetched from the tracker on first use
         (with a group: the winners' at once), so use best() or goals before this tracker runs again."""
+        self._index_checks(obstacle_list, course_obstacles, robot_radius)
         dc = getattr(courses, "device_courses", None)
         if dc is not None:
             return self._run_from(courses, dc, obstacle_list, course_obstacles, robot_radius, target_speed, yaw_th,
@@ -281,7 +319,7 @@ class BatchTrack:
         rc = T.run(_abi.TrackParams(**p), b)
         rec, off = T.records()
         return TrackResult(rec, off, T.arrays() if arrays else None, keep["goals"], rc, T.kernel_ms(),
-                           np.diff(keep["offsets"]))
+                           np.diff(keep["offsets"]), obstacle_index=self._served(b.n_obstacles))
 
     def _run_from(self, result, dc, obstacle_list, course_obstacles, robot_radius, target_speed, yaw_th,
                   invalid_travel_ratio, start_state, arrays, select, group):
@@ -316,4 +354,4 @@ class BatchTrack:
                     raise _abi.RrtxError("goals: the tracker has run again, the goal poses of this run were not fetched")
                 return T.goals(n)
         return TrackResult(rec, off, T.arrays() if arrays else None, goals, rc, T.kernel_ms(), np.diff(result.offsets),
-                           winner, int(src.group))
+                           winner, int(src.group), self._served(b.n_obstacles))
