@@ -17,9 +17,8 @@
 // 1 cx, 2 cy, 3 .. 13 the band planes d = j - i + k (2 k + 1 of them are used) --; the knots of course c, m + k + 1 <= m + 6
 // doubles, start at knots[wp_off[c] + 6 c].
 #pragma once
+#include "curve_check.hip.h"
 #include "rpp_bspline.h"
-#include "rpp_collide.h"
-#include "rpp_obsgrid.h"
 
 namespace rppbs {
 
@@ -28,9 +27,7 @@ constexpr int FIT_TPB = 64;           // one lane per course and long sequential
 constexpr int MAX_WAYPOINTS = 4096;   // per course: bounds one lane's sequential sweep (include/rrtx.h)
 constexpr int TAB_PLANES = 3 + 2 * rpp::kBsplineMaxDegree + 1;
 constexpr int KNOT_SLACK = rpp::kBsplineMaxDegree + 1;
-// the eval kernels' CHECK: no obstacle test, the linear loop (rpp::first_hit), or the obstacle index
-// (rppo::point_first_hit); a template parameter, so that a launch without the index carries none of its registers
-constexpr int CHECK_NONE = 0, CHECK_LINEAR = 1, CHECK_INDEX = 2;
+using rppc::CHECK_NONE, rppc::CHECK_LINEAR, rppc::CHECK_INDEX;   // the eval kernels' CHECK (curve_check.hip.h)
 
 struct Record {   // rrtx_bspline_record
   int32_t status, degree;
@@ -105,31 +102,7 @@ __global__ __launch_bounds__(FIT_TPB) void bspline_fit_kernel(Args a) {
   if (a.hit) a.hit[c] = r.n_points > 0 ? -1 : -2;
 }
 
-// The obstacle test of one point (px, py) of course `lo`, by every lane of the wave: the lowest index touched goes into
-// hit[lo], with one atomic where the wave lies within one course.  Shared with bspline_smooth.hip.h.
-template <int CHECK>
-__device__ inline void check_point(const Args& a, int64_t lo, double px, double py) {
-  const uint32_t NONE = 0xffffffffu;
-  const uint32_t h = (uint32_t)(CHECK == CHECK_INDEX ? rppo::point_first_hit(a.omap, px, py) : rpp::first_hit(a.obs, a.n_obs, px, py));
-  if (!__any(h != NONE)) return;
-  uint32_t* out = (uint32_t*)a.hit;
-  const int course = (int)lo;   // n <= 2^30
-  const int course0 = __shfl(course, 0);
-  if (__all(course == course0)) {   // the wave lies within one course: one atomic
-    uint32_t mn = h;
-    for (int off = 32; off > 0; off >>= 1) {
-      const uint32_t o = (uint32_t)__shfl_xor((int)mn, off);
-      mn = o < mn ? o : mn;
-    }
-    if ((threadIdx.x & 63) == 0) atomicMin(out + course0, mn);
-  } else if (h != NONE) {
-    atomicMin(out + course, h);
-  }
-}
-
-// With CHECK a lane past the last point does not leave: it stays as a copy of the last point (the same course, the same
-// answer), so every lane of a wave takes part in the shuffles below.  hit[] is read as unsigned for the minimum: -1
-// (free) is then the largest value, and -2 belongs to courses without points.
+// The lanes past the last point, and hit[]: curve_check.hip.h
 template <bool STORE, int CHECK>
 __global__ __launch_bounds__(TPB) void bspline_eval_kernel(Args a) {
   int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -139,14 +112,7 @@ __global__ __launch_bounds__(TPB) void bspline_eval_kernel(Args a) {
     if (!CHECK) return;
     idx = total - 1;   // the launch has total > 0
   }
-  int64_t lo = 0, hi = a.n;   // the course c with pt_off[c] <= idx < pt_off[c + 1] (courses without points are skipped over)
-  while (hi - lo > 1) {
-    const int64_t mid = lo + (hi - lo) / 2;
-    if (a.pt_off[mid] <= idx)
-      lo = mid;
-    else
-      hi = mid;
-  }
+  const int64_t lo = rppc::csr_row(a.pt_off, a.n, idx);   // the course of this point
   const int64_t w0 = a.wp_off[lo];
   const int m = (int)(a.wp_off[lo + 1] - w0);
   const int k = course_degree(a, lo);
@@ -162,7 +128,7 @@ __global__ __launch_bounds__(TPB) void bspline_eval_kernel(Args a) {
     for (int q = 0; q < 4; q++) a.out[q * total + idx] = p[q];
     a.out[4 * total + idx] = v;
   }
-  if (CHECK) check_point<CHECK>(a, lo, p[0], p[1]);
+  if (CHECK) rppc::check_point<CHECK>(a.obs, a.n_obs, a.omap, a.hit, lo, p[0], p[1]);
 }
 
 }  // namespace rppbs

@@ -111,14 +111,7 @@ __global__ __launch_bounds__(TPB) void bspline_smooth_eval_kernel(SmoothArgs sa)
     if (!CHECK) return;
     idx = total - 1;   // the launch has total > 0
   }
-  int64_t lo = 0, hi = a.n;   // the course c with pt_off[c] <= idx < pt_off[c + 1] (courses without points are skipped over)
-  while (hi - lo > 1) {
-    const int64_t mid = lo + (hi - lo) / 2;
-    if (a.pt_off[mid] <= idx)
-      lo = mid;
-    else
-      hi = mid;
-  }
+  const int64_t lo = rppc::csr_row(a.pt_off, a.n, idx);   // the course of this point
   const int64_t w0 = a.wp_off[lo];
   const int m = (int)(a.wp_off[lo + 1] - w0);
   const int k = course_degree(a, lo);
@@ -138,7 +131,7 @@ __global__ __launch_bounds__(TPB) void bspline_smooth_eval_kernel(SmoothArgs sa)
     for (int q = 0; q < 4; q++) a.out[q * total + idx] = p[q];
     a.out[4 * total + idx] = v;
   }
-  if (CHECK) check_point<CHECK>(a, lo, p[0], p[1]);
+  if (CHECK) rppc::check_point<CHECK>(a.obs, a.n_obs, a.omap, a.hit, lo, p[0], p[1]);
 }
 
 }  // namespace rppbs

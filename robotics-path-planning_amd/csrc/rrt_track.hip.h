@@ -28,6 +28,7 @@
 // Obstacles: at most 64 per instance (the Reeds-Shepp planner's limit) in the lane-per-obstacle form (CHECK_LINEAR); the two
 // data kernels also come in an obstacle-index form (CHECK_INDEX) that takes a shared list of up to 2^20 circles.
 #pragma once
+#include "curve_check.hip.h"
 #include "rpp_track.h"
 #include "rrt_rs.hip.h"
 
@@ -40,7 +41,7 @@ constexpr int MAX_STEPS = 1 << 22;   // never spin on the device whatever T / dt
 constexpr int ST_OVERFLOW = 4, ST_RAISES = 32, ST_OOD = 16;   // include/rrtx.h status bits (OOD reported as UNSUPPORTED)
 // how a roll-out tests its points against the circles: lane k against circle k (at most 64), or every lane's parked point
 // through the obstacle index (rpp_obsgrid.h point_first_hit, rpp_track.h pend_*: any number of circles)
-constexpr int CHECK_LINEAR = 1, CHECK_INDEX = 2;
+using rppc::CHECK_LINEAR, rppc::CHECK_INDEX;
 
 struct Outcome {      // per instance
   int32_t flag;       // search_best_feasible_path found a feasible roll-out

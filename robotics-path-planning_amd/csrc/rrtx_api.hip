@@ -44,6 +44,7 @@ static_assert(sizeof(rppt::Params) == sizeof(rrtx_track_params), "rrtx_track_par
 static_assert(sizeof(rppt::Outcome) == sizeof(rrtx_track_outcome), "rrtx_track_outcome mirrors rppt::Outcome");
 static_assert(sizeof(rppt::Record) == sizeof(rrtx_track_record), "rrtx_track_record mirrors rppt::Record");
 static_assert(sizeof(rppgt::Outcome) == sizeof(rrtx_goal_track_outcome), "rrtx_goal_track_outcome mirrors rppgt::Outcome");
+static_assert(rppc::CHECK_NONE == 0 && rppc::CHECK_LINEAR == 1 && rppc::CHECK_INDEX == 2, "with_store_check (rrtx_host.h) counts as the kernels do");
 
 // What a build of the obstacle grid leaves on the device (build_obstacle_grid, rrtx_api_obsmap.inc): cell_start (cells + 2
 // entries, the last run is the wide list) and the sorted records

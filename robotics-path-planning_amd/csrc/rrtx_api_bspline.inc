@@ -1,18 +1,12 @@
 // rrtx_api_bspline.inc -- rrtx_bspline_*: batched B-spline courses through waypoints, interpolating (bspline_batch.hip.h:
 // bspline_fit_kernel, bspline_eval_kernel) and smoothing (bspline_smooth.hip.h: bspline_smooth_fit_kernel,
 // bspline_smooth_eval_kernel); included by rrtx_api.hip
-struct rrtx_bspline : DevObj {
-  // device buffers, grown on demand
-  DevBuf wp_off, x, y, degree, mode_of, count, ds, us_off, us, tab, knots, rec, pt_off, out, obs, hit, sm, arec;
-  // the last run
-  bool ran = false, has_arrays = false, has_hits = false, smooth = false;   // smooth: the last run was rrtx_bspline_approximate
-  int64_t n = 0, n_wp = 0, n_points = 0, n_knots = 0;
-  double kernel_ms = 0.0;
-  uint64_t generation = 0;   // completed runs and approximations, rrtx_bspline_get_generation
+struct rrtx_bspline : CourseObj {   // rrtx_api_spline.inc; generation counts runs and approximations
+  DevBuf wp_off, x, y, degree, mode_of, count, ds, us_off, us, tab, knots, rec, sm, arec;   // device buffers, grown on demand
+  bool smooth = false;   // the last run was rrtx_bspline_approximate
+  int64_t n_knots = 0;
   std::vector<rppbs::Record> h_rec;
-  std::vector<int64_t> h_off, h_wp_off, h_knot_off;
-  ObsIndex oi;   // the obstacle index over the last run's list
-  std::vector<int32_t> h_hit;
+  std::vector<int64_t> h_wp_off, h_knot_off;
   std::vector<rpp::SmoothInfo> h_arec;   // [2][n], axis-major
 };
 
@@ -27,18 +21,6 @@ static_assert(rpp::kBsplineNormalised == RRTX_BSPLINE_PARAM_NORMALISED && rpp::k
                   rpp::kBsplineLinspace == RRTX_BSPLINE_SAMPLE_LINSPACE && rpp::kBsplineArange == RRTX_BSPLINE_SAMPLE_ARANGE &&
                   rpp::kBsplineExplicit == RRTX_BSPLINE_SAMPLE_EXPLICIT,
               "the modes of the header are the core's");
-
-template <bool STORE, int CHECK>
-static void bspline_launch_eval(int64_t total, hipStream_t stream, const rppbs::Args& a) {
-  const unsigned blocks = (unsigned)((total + rppbs::TPB - 1) / rppbs::TPB);
-  hipLaunchKernelGGL((rppbs::bspline_eval_kernel<STORE, CHECK>), dim3(blocks), dim3(rppbs::TPB), 0, stream, a);
-}
-
-template <bool STORE, int CHECK>
-static void bspline_launch_smooth_eval(int64_t total, hipStream_t stream, const rppbs::SmoothArgs& a) {
-  const unsigned blocks = (unsigned)((total + rppbs::TPB - 1) / rppbs::TPB);
-  hipLaunchKernelGGL((rppbs::bspline_smooth_eval_kernel<STORE, CHECK>), dim3(blocks), dim3(rppbs::TPB), 0, stream, a);
-}
 
 // rrtx_bspline_run (sb NULL) and rrtx_bspline_approximate (sb the smoothing batch, b its run part)
 static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b, const rrtx_bspline_smooth_batch* sb, const char* fn) {
@@ -61,13 +43,11 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b, const rrtx_
   const int64_t n_deg = b->degree_per_course ? n : 1;
   for (int64_t i = 0; i < n_deg; i++)
     if (b->degree[i] < 1 || b->degree[i] > RRTX_BSPLINE_MAX_DEGREE) return bad("a degree is not 1 .. 5");
-  if (b->n_obstacles < 0 || b->n_obstacles > (1LL << 20)) return bad("n_obstacles is negative or above 2^20");
-  if (b->n_obstacles > 0 && !b->obstacles) return bad("obstacles is NULL");
+  if (const char* m = obstacle_list_shape_error(b->obstacles, b->n_obstacles, 1LL << 20, COURSE_OBS_TEXT)) return bad(m);
   if (!all_finite(b->x, W) || !all_finite(b->y, W)) return bad("a coordinate is not finite");
   for (int64_t i = 0; i < W; i++)
     if (std::fabs(b->x[i]) > 1.0e6 || std::fabs(b->y[i]) > 1.0e6) return bad("a coordinate is above 1e6 in magnitude");
-  if (!all_finite(b->obstacles, 3 * b->n_obstacles)) return bad("an obstacle entry is not finite");
-  if (!std::isfinite(b->robot_radius)) return bad("robot_radius is not finite");
+  if (const char* m = obstacle_list_value_error(b->obstacles, b->n_obstacles, &b->robot_radius, 1, COURSE_OBS_TEXT)) return bad(m);
   const int64_t n_s = sb && sb->s_per_course ? n : 1;
   if (sb) {
     if (!sb->s) return bad("s is NULL");
@@ -118,19 +98,11 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b, const rrtx_
   }
   if (int nd = s->need_device(fn)) return nd;
 
-  s->ran = false;
-  s->has_arrays = false;
-  s->has_hits = false;
+  s->begin_run(n, W);
   s->smooth = sb != nullptr;
   s->h_arec.clear();
-  s->n = n;
-  s->n_wp = W;
-  s->n_points = 0;
   s->n_knots = 0;
-  s->kernel_ms = 0.0;
   s->h_rec.clear();
-  s->h_hit.clear();
-  s->h_off.assign((size_t)n + 1, 0);
   s->h_knot_off.assign((size_t)n + 1, 0);
   s->h_wp_off.assign(b->offsets, b->offsets + n + 1);
   if (n == 0) {
@@ -141,15 +113,10 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b, const rrtx_
   }
   // obstacle table: packed rows (ox, oy, thr), thr = (size + robot_radius) ** 2 by the planners' routine
   const int64_t n_obs = b->n_obstacles;
-  std::vector<double> rows(3 * (size_t)n_obs);
-  for (int64_t k = 0; k < n_obs; k++) {
-    rows[3 * k] = b->obstacles[3 * k];
-    rows[3 * k + 1] = b->obstacles[3 * k + 1];
-    rows[3 * k + 2] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius);
-  }
+  std::vector<double> rows;
+  pack_obstacle_rows(b->obstacles, n_obs, b->robot_radius, rows);
   // the obstacle index over the same list (rpp_obsgrid.h): built per run, kept while the rows and the radius stay
   if (int irc = obsindex_set_list(s, s->oi, b->obstacles, n_obs, b->robot_radius)) return irc;
-  const bool indexed = s->oi.used != 0;
 
   HIPCHK(s, hipSetDevice(s->device));
   int rc;
@@ -242,52 +209,19 @@ static int bspline_run(rrtx_bspline* s, const rrtx_bspline_batch* b, const rrtx_
   s->n_points = tot;
   s->n_knots = knots;
 
-  const bool store = b->want_arrays != 0, check = n_obs > 0;
-  if (check) s->h_hit.resize(N);
-  if (tot > 0 && (store || check)) {
-    if (store && (rc = s->reserve(s->out, sizeof(double) * 5 * (size_t)tot))) return rc;
-    if ((rc = s->upload(s->pt_off, s->h_off.data(), sizeof(int64_t) * (N + 1)))) return rc;
-    a.pt_off = s->pt_off.as<const int64_t>();
-    a.out = store ? s->out.as<double>() : nullptr;
-    a.obs = check ? s->obs.as<const double>() : nullptr;
-    a.n_obs = n_obs;
-    if (check && indexed) a.omap = s->oi.map();
+  rc = s->eval_stage(a, b->want_arrays != 0, n_obs, [&](bool store, int check) {
+    const unsigned blocks = (unsigned)((tot + rppbs::TPB - 1) / rppbs::TPB);
     sa.a = a;
-    rc = s->timed(&ms, [&] {
-      using namespace rppbs;
-      const int ck = !check ? CHECK_NONE : (indexed ? CHECK_INDEX : CHECK_LINEAR);
-      if (sb && store && ck == CHECK_INDEX)
-        bspline_launch_smooth_eval<true, CHECK_INDEX>(tot, s->stream, sa);
-      else if (sb && store && ck)
-        bspline_launch_smooth_eval<true, CHECK_LINEAR>(tot, s->stream, sa);
-      else if (sb && store)
-        bspline_launch_smooth_eval<true, CHECK_NONE>(tot, s->stream, sa);
-      else if (sb && ck == CHECK_INDEX)
-        bspline_launch_smooth_eval<false, CHECK_INDEX>(tot, s->stream, sa);
-      else if (sb)
-        bspline_launch_smooth_eval<false, CHECK_LINEAR>(tot, s->stream, sa);
-      else if (store && ck == CHECK_INDEX)
-        bspline_launch_eval<true, CHECK_INDEX>(tot, s->stream, a);
-      else if (store && ck)
-        bspline_launch_eval<true, CHECK_LINEAR>(tot, s->stream, a);
-      else if (store)
-        bspline_launch_eval<true, CHECK_NONE>(tot, s->stream, a);
-      else if (ck == CHECK_INDEX)
-        bspline_launch_eval<false, CHECK_INDEX>(tot, s->stream, a);
+    with_store_check(store, check, [&](auto st, auto ck) {
+      constexpr bool STORE = decltype(st)::value;
+      constexpr int CHECK = decltype(ck)::value;
+      if (sb)
+        hipLaunchKernelGGL((rppbs::bspline_smooth_eval_kernel<STORE, CHECK>), dim3(blocks), dim3(rppbs::TPB), 0, s->stream, sa);
       else
-        bspline_launch_eval<false, CHECK_LINEAR>(tot, s->stream, a);
-    }, [&]() -> int {
-      if (check) HIPCHK(s, hipMemcpyAsync(s->h_hit.data(), s->hit.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
-      return RRTX_OK;
+        hipLaunchKernelGGL((rppbs::bspline_eval_kernel<STORE, CHECK>), dim3(blocks), dim3(rppbs::TPB), 0, s->stream, a);
     });
-    if (rc) return rc;
-    s->kernel_ms += ms;
-  } else if (check) {
-    HIPCHK(s, hipMemcpy(s->h_hit.data(), s->hit.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
-  }
-  s->has_arrays = store;
-  s->has_hits = check;
-  s->ran = true;
+  });
+  if (rc) return rc;
   if (partial) {
     s->err = std::string(fn) + "some courses have coinciding waypoints, no more waypoints than their degree, or no finite fit (see the status column)";
     return RRTX_PARTIAL;
@@ -365,27 +299,14 @@ int rrtx_bspline_get_axis_splines(rrtx_bspline* s, int32_t axis, int64_t* knot_o
 
 int rrtx_bspline_get_records(rrtx_bspline* s, rrtx_bspline_record* rec, int64_t* offsets, int64_t* n_courses, int64_t* n_points,
                              int64_t* n_knots) {
-  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_bspline_get_records: the bspline object is NULL");
-  if (!s->ran) return fail(s, RRTX_E_STATE, "rrtx_bspline_get_records: no completed run");
+  if (int rc = course_get_counts(s, "rrtx_bspline_get_records: ", "bspline", offsets, n_courses, n_points)) return rc;
   if (rec && s->n) memcpy(rec, s->h_rec.data(), sizeof(rrtx_bspline_record) * (size_t)s->n);
-  if (offsets) memcpy(offsets, s->h_off.data(), sizeof(int64_t) * ((size_t)s->n + 1));
-  if (n_courses) *n_courses = s->n;
-  if (n_points) *n_points = s->n_points;
   if (n_knots) *n_knots = s->n_knots;
   return RRTX_OK;
 }
 
 int rrtx_bspline_get_points(rrtx_bspline* s, double* x, double* y, double* yaw, double* k, double* u, int64_t cap) {
-  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_bspline_get_points: the bspline object is NULL");
-  if (!s->ran || !s->has_arrays) return fail(s, RRTX_E_STATE, "rrtx_bspline_get_points: no completed run with arrays");
-  if (cap < s->n_points) return fail(s, RRTX_E_CAPACITY, "rrtx_bspline_get_points: the buffers are too small");
-  if (s->n_points == 0) return RRTX_OK;
-  const size_t tot = (size_t)s->n_points;
-  double* dst[5] = {x, y, yaw, k, u};
-  for (int q = 0; q < 5; q++)
-    if (dst[q])
-      if (int rc = s->fetch(dst[q], s->out.as<const double>() + q * tot, sizeof(double) * tot)) return rc;
-  return RRTX_OK;
+  return course_get_points(s, "rrtx_bspline_get_points: ", "bspline", x, y, yaw, k, u, cap);
 }
 
 int rrtx_bspline_get_coefficients(rrtx_bspline* s, int64_t* knot_offsets, double* knots, int64_t cap_knots, double* cx, double* cy,
@@ -423,20 +344,10 @@ int rrtx_bspline_get_obstacle_index_info(rrtx_bspline* s, rrtx_obstacle_index_in
   return obsindex_get_info(s, s ? &s->oi : nullptr, info, "rrtx_bspline_get_obstacle_index_info: ");
 }
 
-int rrtx_bspline_get_hits(rrtx_bspline* s, int32_t* hit) {
-  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_bspline_get_hits: the bspline object is NULL");
-  if (!s->ran) return fail(s, RRTX_E_STATE, "rrtx_bspline_get_hits: no completed run");
-  if (!s->has_hits) return fail(s, RRTX_E_STATE, "rrtx_bspline_get_hits: the last run had no obstacle list");
-  if (s->n == 0) return RRTX_OK;
-  if (!hit) return fail(s, RRTX_E_INVALID, "rrtx_bspline_get_hits: hit is NULL");
-  memcpy(hit, s->h_hit.data(), sizeof(int32_t) * (size_t)s->n);
-  return RRTX_OK;
-}
+int rrtx_bspline_get_hits(rrtx_bspline* s, int32_t* hit) { return course_get_hits(s, "rrtx_bspline_get_hits: ", "bspline", hit); }
 
 int rrtx_bspline_get_generation(rrtx_bspline* s, uint64_t* generation) {
-  if (!s || !generation) return fail(s, RRTX_E_INVALID, "rrtx_bspline_get_generation: a NULL pointer");
-  *generation = s->generation;
-  return RRTX_OK;
+  return course_get_generation(s, "rrtx_bspline_get_generation: ", generation);
 }
 
 int rrtx_bspline_get_kernel_ms(rrtx_bspline* s, double* kernel_ms) {

@@ -129,12 +129,14 @@ static int obsindex_decide(DevObj* o, ObsIndex& X) {
   if (X.reason != rppo::WHY_USED) return RRTX_OK;
   if (!X.tried) {
     std::vector<rppo::Circle> in((size_t)m);
+    std::vector<double> rows;
+    pack_obstacle_rows(X.raw.data(), m, X.radius, rows);
     double lo[2] = {X.raw[0], X.raw[1]}, hi[2] = {X.raw[0], X.raw[1]};
     bool finite = true;
     for (int64_t k = 0; k < m; k++) {
-      in[k].ox = X.raw[3 * k];
-      in[k].oy = X.raw[3 * k + 1];
-      in[k].thr = py_sq_host(X.raw[3 * k + 2] + X.radius);
+      in[k].ox = rows[3 * k];
+      in[k].oy = rows[3 * k + 1];
+      in[k].thr = rows[3 * k + 2];
       in[k].rho = rppo::reach(X.raw[3 * k + 2], X.radius);
       finite = finite && std::isfinite(in[k].rho) && std::isfinite(in[k].thr);
       lo[0] = in[k].ox < lo[0] ? in[k].ox : lo[0];

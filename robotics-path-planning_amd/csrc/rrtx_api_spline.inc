@@ -1,23 +1,124 @@
 // rrtx_api_spline.inc -- rrtx_spline_*: batched cubic-spline courses through waypoints (spline_batch.hip.h:
 // spline_fit_kernel, spline_eval_kernel), one-dimensional splines over the caller's knots (spline_fit1d_kernel) and
 // pointwise queries against either (spline_query_kernel); included by rrtx_api.hip
-struct rrtx_spline : DevObj {
-  // device buffers, grown on demand
-  DevBuf wp_off, x, y, ds, cx, cy, tab, rec, pt_off, out, obs, hit, q_off, q_t, q_out, q_status;
-  // the last run (or fit1d: axes == 1)
+
+// ---- what rrtx_spline and rrtx_bspline share: courses fitted through waypoints, then sampled into a CSR list of points --------
+struct CourseObj : DevObj {
+  DevBuf pt_off, out, obs, hit;   // device buffers, grown on demand
+  // the last run
   bool ran = false, has_arrays = false, has_hits = false;
-  int axes = 2;
   int64_t n = 0, n_wp = 0, n_points = 0;
   double kernel_ms = 0.0;
-  uint64_t generation = 0;   // completed runs and fit1d calls, rrtx_spline_get_generation
+  uint64_t generation = 0;   // completed runs, rrtx_*_get_generation
+  std::vector<int64_t> h_off;
+  std::vector<int32_t> h_hit;
+  ObsIndex oi;   // the obstacle index over the last run's list
+
+  // a run begins, its arguments checked: nothing of the last one is served any more
+  void begin_run(int64_t n_courses, int64_t n_waypoints) {
+    ran = has_arrays = has_hits = false;
+    n = n_courses;
+    n_wp = n_waypoints;
+    n_points = 0;
+    kernel_ms = 0.0;
+    h_hit.clear();
+    h_off.assign((size_t)n + 1, 0);
+  }
+
+  // The second stage of a run, once the fit's records gave h_off and n_points: launch(store, check) queues the eval kernel
+  // over `a` (check: rppc::CHECK_*), whose point offsets, output planes and obstacle list are set here; the hits come back
+  // with it.  Without a point or without anything to do for one, the hits are what the fit left.
+  template <class Args, class Launch>
+  int eval_stage(Args& a, bool store, int64_t n_obs, Launch&& launch) {
+    const size_t N = (size_t)n;
+    const bool check = n_obs > 0;
+    const int ck = !check ? rppc::CHECK_NONE : oi.used ? rppc::CHECK_INDEX : rppc::CHECK_LINEAR;
+    int rc;
+    if (check) h_hit.resize(N);
+    if (n_points > 0 && (store || check)) {
+      if (store && (rc = reserve(out, sizeof(double) * 5 * (size_t)n_points))) return rc;
+      if ((rc = upload(pt_off, h_off.data(), sizeof(int64_t) * (N + 1)))) return rc;
+      a.pt_off = pt_off.as<const int64_t>();
+      a.out = store ? out.as<double>() : nullptr;
+      a.obs = check ? obs.as<const double>() : nullptr;
+      a.n_obs = n_obs;
+      if (ck == rppc::CHECK_INDEX) a.omap = oi.map();
+      float ms = 0.f;
+      rc = timed(&ms, [&] { launch(store, ck); }, [&]() -> int {
+        if (check) HIPCHK(this, hipMemcpyAsync(h_hit.data(), hit.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, stream));
+        return RRTX_OK;
+      });
+      if (rc) return rc;
+      kernel_ms += ms;
+    } else if (check) {
+      HIPCHK(this, hipMemcpy(h_hit.data(), hit.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+    }
+    has_arrays = store;
+    has_hits = check;
+    ran = true;
+    return RRTX_OK;
+  }
+};
+
+// What both objects say of an obstacle list that is wrong (rrtx_host.h)
+static const ObsListText COURSE_OBS_TEXT = {"n_obstacles is negative or above 2^20", "n_obstacles is negative or above 2^20",
+                                            "obstacles is NULL", "an obstacle entry is not finite", "robot_radius is not finite"};
+
+// The getters of both; fn: "rrtx_spline_get_points: ", noun: "spline" or "bspline"
+static int course_null(const char* fn, const char* noun) {
+  return fail<CourseObj>(nullptr, RRTX_E_INVALID, std::string(fn) + "the " + noun + " object is NULL");
+}
+
+// the checks of rrtx_*_get_records, and what both return: offsets and counts (any may be NULL)
+static int course_get_counts(CourseObj* s, const char* fn, const char* noun, int64_t* offsets, int64_t* n_courses, int64_t* n_points) {
+  if (!s) return course_null(fn, noun);
+  if (!s->ran) return fail(s, RRTX_E_STATE, std::string(fn) + "no completed run");
+  if (offsets) memcpy(offsets, s->h_off.data(), sizeof(int64_t) * ((size_t)s->n + 1));
+  if (n_courses) *n_courses = s->n;
+  if (n_points) *n_points = s->n_points;
+  return RRTX_OK;
+}
+
+// the five planes of the points: x, y, yaw, k and the parameter (any may be NULL)
+static int course_get_points(CourseObj* s, const char* fn, const char* noun, double* x, double* y, double* yaw, double* k, double* t,
+                             int64_t cap) {
+  if (!s) return course_null(fn, noun);
+  if (!s->ran || !s->has_arrays) return fail(s, RRTX_E_STATE, std::string(fn) + "no completed run with arrays");
+  if (cap < s->n_points) return fail(s, RRTX_E_CAPACITY, std::string(fn) + "the buffers are too small");
+  if (s->n_points == 0) return RRTX_OK;
+  const size_t tot = (size_t)s->n_points;
+  double* dst[5] = {x, y, yaw, k, t};
+  for (int q = 0; q < 5; q++)
+    if (dst[q])
+      if (int rc = s->fetch(dst[q], s->out.as<const double>() + q * tot, sizeof(double) * tot)) return rc;
+  return RRTX_OK;
+}
+
+static int course_get_hits(CourseObj* s, const char* fn, const char* noun, int32_t* hit) {
+  if (!s) return course_null(fn, noun);
+  if (!s->ran) return fail(s, RRTX_E_STATE, std::string(fn) + "no completed run");
+  if (!s->has_hits) return fail(s, RRTX_E_STATE, std::string(fn) + "the last run had no obstacle list");
+  if (s->n == 0) return RRTX_OK;
+  if (!hit) return fail(s, RRTX_E_INVALID, std::string(fn) + "hit is NULL");
+  memcpy(hit, s->h_hit.data(), sizeof(int32_t) * (size_t)s->n);
+  return RRTX_OK;
+}
+
+static int course_get_generation(CourseObj* s, const char* fn, uint64_t* generation) {
+  if (!s || !generation) return fail(s, RRTX_E_INVALID, std::string(fn) + "a NULL pointer");
+  *generation = s->generation;
+  return RRTX_OK;
+}
+
+struct rrtx_spline : CourseObj {
+  DevBuf wp_off, x, y, ds, cx, cy, tab, rec, q_off, q_t, q_out, q_status;   // device buffers, grown on demand
+  int axes = 2;   // the last run, or fit1d: axes == 1 (generation counts both)
   // the last query against it
   bool queried = false, q_deriv = false;
   int64_t n_q = 0;
   double query_ms = 0.0;
   std::vector<rppsp::Record> h_rec;
-  std::vector<int64_t> h_off;
-  ObsIndex oi;   // the obstacle index over the last run's list
-  std::vector<int32_t> h_hit, h_qst;
+  std::vector<int32_t> h_qst;
 };
 
 static_assert(sizeof(rppsp::Record) == sizeof(rrtx_spline_record), "rrtx_spline_record mirrors rppsp::Record");
@@ -27,12 +128,6 @@ static_assert(rpp::kSplineQOk == RRTX_SPLINE_Q_OK && rpp::kSplineQOutside == RRT
               "the query statuses of the header are the core's");
 
 inline double (*volatile libm_hypot)(double, double) = hypot;
-
-template <bool STORE, int CHECK>
-static void spline_launch_eval(int64_t total, hipStream_t stream, const rppsp::Args& a) {
-  const unsigned blocks = (unsigned)((total + rppsp::TPB - 1) / rppsp::TPB);
-  hipLaunchKernelGGL((rppsp::spline_eval_kernel<STORE, CHECK>), dim3(blocks), dim3(rppsp::TPB), 0, stream, a);
-}
 
 static int spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
   const char* fn = "rrtx_spline_run: ";
@@ -52,14 +147,12 @@ static int spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
   }
   if ((b->cx != nullptr) != (b->cy != nullptr)) return bad("one of cx, cy is NULL and the other is not");
   if (b->cx && b->n_c != W) return bad("n_c is not the number of waypoints");
-  if (b->n_obstacles < 0 || b->n_obstacles > (1LL << 20)) return bad("n_obstacles is negative or above 2^20");
-  if (b->n_obstacles > 0 && !b->obstacles) return bad("obstacles is NULL");
+  if (const char* m = obstacle_list_shape_error(b->obstacles, b->n_obstacles, 1LL << 20, COURSE_OBS_TEXT)) return bad(m);
   if (!all_finite(b->x, W) || !all_finite(b->y, W)) return bad("a coordinate is not finite");
   for (int64_t i = 0; i < W; i++)
     if (std::fabs(b->x[i]) > 1.0e6 || std::fabs(b->y[i]) > 1.0e6) return bad("a coordinate is above 1e6 in magnitude");
   if (b->cx && (!all_finite(b->cx, W) || !all_finite(b->cy, W))) return bad("a c value is not finite");
-  if (!all_finite(b->obstacles, 3 * b->n_obstacles)) return bad("an obstacle entry is not finite");
-  if (!std::isfinite(b->robot_radius)) return bad("robot_radius is not finite");
+  if (const char* m = obstacle_list_value_error(b->obstacles, b->n_obstacles, &b->robot_radius, 1, COURSE_OBS_TEXT)) return bad(m);
   const int64_t n_ds = b->ds_per_course ? n : 1;
   for (int64_t i = 0; i < n_ds; i++)
     if (!std::isfinite(b->ds[i]) || !(b->ds[i] > 0.0)) return bad("a ds is not finite or not > 0");
@@ -73,18 +166,10 @@ static int spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
   }
   if (int nd = s->need_device(fn)) return nd;
 
-  s->ran = false;
+  s->begin_run(n, W);
   s->queried = false;
   s->axes = 2;
-  s->has_arrays = false;
-  s->has_hits = false;
-  s->n = n;
-  s->n_wp = W;
-  s->n_points = 0;
-  s->kernel_ms = 0.0;
   s->h_rec.clear();
-  s->h_hit.clear();
-  s->h_off.assign((size_t)n + 1, 0);
   if (n == 0) {
     s->has_arrays = b->want_arrays != 0;
     s->has_hits = b->n_obstacles > 0;
@@ -93,15 +178,10 @@ static int spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
   }
   // obstacle table: packed rows (ox, oy, thr), thr = (size + robot_radius) ** 2 by the planners' routine
   const int64_t n_obs = b->n_obstacles;
-  std::vector<double> rows(3 * (size_t)n_obs);
-  for (int64_t k = 0; k < n_obs; k++) {
-    rows[3 * k] = b->obstacles[3 * k];
-    rows[3 * k + 1] = b->obstacles[3 * k + 1];
-    rows[3 * k + 2] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius);
-  }
+  std::vector<double> rows;
+  pack_obstacle_rows(b->obstacles, n_obs, b->robot_radius, rows);
   // the obstacle index over the same list (rpp_obsgrid.h): built per run, kept while the rows and the radius stay
   if (int irc = obsindex_set_list(s, s->oi, b->obstacles, n_obs, b->robot_radius)) return irc;
-  const bool indexed = s->oi.used != 0;
 
   HIPCHK(s, hipSetDevice(s->device));
   int rc;
@@ -158,43 +238,17 @@ static int spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
   s->h_off[N] = tot;
   s->n_points = tot;
 
-  const bool store = b->want_arrays != 0, check = n_obs > 0;
-  if (check) s->h_hit.resize(N);
-  if (tot > 0 && (store || check)) {
-    if (store && (rc = s->reserve(s->out, sizeof(double) * 5 * (size_t)tot))) return rc;
-    if ((rc = s->upload(s->pt_off, s->h_off.data(), sizeof(int64_t) * (N + 1)))) return rc;
-    a.pt_off = s->pt_off.as<const int64_t>();
-    a.out = store ? s->out.as<double>() : nullptr;
-    a.obs = check ? s->obs.as<const double>() : nullptr;
-    a.n_obs = n_obs;
-    if (check && indexed) a.omap = s->oi.map();
-    rc = s->timed(&ms, [&] {
-      using namespace rppsp;
-      if (store && check && indexed)
-        spline_launch_eval<true, CHECK_INDEX>(tot, s->stream, a);
-      else if (store && check)
-        spline_launch_eval<true, CHECK_LINEAR>(tot, s->stream, a);
-      else if (store)
-        spline_launch_eval<true, CHECK_NONE>(tot, s->stream, a);
-      else if (indexed)
-        spline_launch_eval<false, CHECK_INDEX>(tot, s->stream, a);
-      else
-        spline_launch_eval<false, CHECK_LINEAR>(tot, s->stream, a);
-    }, [&]() -> int {
-      if (check) HIPCHK(s, hipMemcpyAsync(s->h_hit.data(), s->hit.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
-      return RRTX_OK;
+  rc = s->eval_stage(a, b->want_arrays != 0, n_obs, [&](bool store, int check) {
+    with_store_check(store, check, [&](auto st, auto ck) {
+      const unsigned blocks = (unsigned)((tot + rppsp::TPB - 1) / rppsp::TPB);
+      hipLaunchKernelGGL((rppsp::spline_eval_kernel<decltype(st)::value, decltype(ck)::value>), dim3(blocks), dim3(rppsp::TPB), 0,
+                         s->stream, a);
     });
-    if (rc) return rc;
-    s->kernel_ms += ms;
-  } else if (check) {
-    HIPCHK(s, hipMemcpy(s->h_hit.data(), s->hit.p, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
-  }
+  });
+  if (rc) return rc;
   // a course with no sample (s[-1] / ds underflows to 0) was tested against nothing
-  for (size_t i = 0; check && i < N; i++)
+  for (size_t i = 0; s->has_hits && i < N; i++)
     if (s->h_rec[i].n_points == 0) s->h_hit[i] = -2;
-  s->has_arrays = store;
-  s->has_hits = check;
-  s->ran = true;
   if (partial) {
     s->err = std::string(fn) + "some courses have coinciding waypoints, or a last sample on the last knot (see the status column)";
     return RRTX_PARTIAL;
@@ -229,18 +283,10 @@ static int spline_fit1d(rrtx_spline* s, const rrtx_spline_fit1d_batch* b) {
   }
   if (int nd = s->need_device(fn)) return nd;
 
-  s->ran = false;
+  s->begin_run(n, W);
   s->queried = false;
   s->axes = 1;
-  s->has_arrays = false;
-  s->has_hits = false;
-  s->n = n;
-  s->n_wp = W;
-  s->n_points = 0;
-  s->kernel_ms = 0.0;
   s->h_rec.clear();
-  s->h_hit.clear();
-  s->h_off.assign((size_t)n + 1, 0);
   if (n == 0) {
     s->ran = true;
     return RRTX_OK;
@@ -379,27 +425,14 @@ int rrtx_spline_run(rrtx_spline* s, const rrtx_spline_batch* b) {
 
 int rrtx_spline_get_records(rrtx_spline* s, rrtx_spline_record* rec, int64_t* offsets, int64_t* n_courses, int64_t* n_points,
                             double* kernel_ms) {
-  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_spline_get_records: the spline object is NULL");
-  if (!s->ran) return fail(s, RRTX_E_STATE, "rrtx_spline_get_records: no completed run");
+  if (int rc = course_get_counts(s, "rrtx_spline_get_records: ", "spline", offsets, n_courses, n_points)) return rc;
   if (rec && s->n) memcpy(rec, s->h_rec.data(), sizeof(rrtx_spline_record) * (size_t)s->n);
-  if (offsets) memcpy(offsets, s->h_off.data(), sizeof(int64_t) * ((size_t)s->n + 1));
-  if (n_courses) *n_courses = s->n;
-  if (n_points) *n_points = s->n_points;
   if (kernel_ms) *kernel_ms = s->kernel_ms;
   return RRTX_OK;
 }
 
 int rrtx_spline_get_points(rrtx_spline* s, double* x, double* y, double* yaw, double* k, double* t, int64_t cap) {
-  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_spline_get_points: the spline object is NULL");
-  if (!s->ran || !s->has_arrays) return fail(s, RRTX_E_STATE, "rrtx_spline_get_points: no completed run with arrays");
-  if (cap < s->n_points) return fail(s, RRTX_E_CAPACITY, "rrtx_spline_get_points: the buffers are too small");
-  if (s->n_points == 0) return RRTX_OK;
-  const size_t tot = (size_t)s->n_points;
-  double* dst[5] = {x, y, yaw, k, t};
-  for (int q = 0; q < 5; q++)
-    if (dst[q])
-      if (int rc = s->fetch(dst[q], s->out.as<const double>() + q * tot, sizeof(double) * tot)) return rc;
-  return RRTX_OK;
+  return course_get_points(s, "rrtx_spline_get_points: ", "spline", x, y, yaw, k, t, cap);
 }
 
 int rrtx_spline_get_c(rrtx_spline* s, double* cx, double* cy, int64_t cap) {
@@ -422,20 +455,10 @@ int rrtx_spline_get_obstacle_index_info(rrtx_spline* s, rrtx_obstacle_index_info
   return obsindex_get_info(s, s ? &s->oi : nullptr, info, "rrtx_spline_get_obstacle_index_info: ");
 }
 
-int rrtx_spline_get_hits(rrtx_spline* s, int32_t* hit) {
-  if (!s) return fail(s, RRTX_E_INVALID, "rrtx_spline_get_hits: the spline object is NULL");
-  if (!s->ran) return fail(s, RRTX_E_STATE, "rrtx_spline_get_hits: no completed run");
-  if (!s->has_hits) return fail(s, RRTX_E_STATE, "rrtx_spline_get_hits: the last run had no obstacle list");
-  if (s->n == 0) return RRTX_OK;
-  if (!hit) return fail(s, RRTX_E_INVALID, "rrtx_spline_get_hits: hit is NULL");
-  memcpy(hit, s->h_hit.data(), sizeof(int32_t) * (size_t)s->n);
-  return RRTX_OK;
-}
+int rrtx_spline_get_hits(rrtx_spline* s, int32_t* hit) { return course_get_hits(s, "rrtx_spline_get_hits: ", "spline", hit); }
 
 int rrtx_spline_get_generation(rrtx_spline* s, uint64_t* generation) {
-  if (!s || !generation) return fail(s, RRTX_E_INVALID, "rrtx_spline_get_generation: a NULL pointer");
-  *generation = s->generation;
-  return RRTX_OK;
+  return course_get_generation(s, "rrtx_spline_get_generation: ", generation);
 }
 
 int rrtx_spline_fit1d(rrtx_spline* s, const rrtx_spline_fit1d_batch* b) {

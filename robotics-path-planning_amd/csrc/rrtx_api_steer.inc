@@ -35,17 +35,9 @@ namespace {
 // check: rppsb::CHECK_*
 template <int KIND>
 void steer_launch_fill(bool store, int check, unsigned blocks, hipStream_t stream, const rppsb::Args& a) {
-  using namespace rppsb;
-  if (store && check == CHECK_INDEX)
-    hipLaunchKernelGGL((steer_fill<KIND, true, CHECK_INDEX>), dim3(blocks), dim3(TPB), 0, stream, a);
-  else if (store && check)
-    hipLaunchKernelGGL((steer_fill<KIND, true, CHECK_LINEAR>), dim3(blocks), dim3(TPB), 0, stream, a);
-  else if (store)
-    hipLaunchKernelGGL((steer_fill<KIND, true, CHECK_NONE>), dim3(blocks), dim3(TPB), 0, stream, a);
-  else if (check == CHECK_INDEX)
-    hipLaunchKernelGGL((steer_fill<KIND, false, CHECK_INDEX>), dim3(blocks), dim3(TPB), 0, stream, a);
-  else
-    hipLaunchKernelGGL((steer_fill<KIND, false, CHECK_LINEAR>), dim3(blocks), dim3(TPB), 0, stream, a);
+  with_store_check(store, check, [&](auto st, auto ck) {
+    hipLaunchKernelGGL((rppsb::steer_fill<KIND, decltype(st)::value, decltype(ck)::value>), dim3(blocks), dim3(rppsb::TPB), 0, stream, a);
+  });
 }
 
 // how a fill launch of `s` tests its points: the object's list and, where it serves the list, the index, into a
@@ -657,18 +649,13 @@ int rrtx_steer_set_obstacles(rrtx_steer* s, const double* obstacles, int64_t m, 
   const char* fn = "rrtx_steer_set_obstacles: ";
   auto bad = [&](const char* msg) { return fail(s, RRTX_E_INVALID, std::string(fn) + msg); };
   if (!s) return bad("the steer object is NULL");
-  if (m < 0) return bad("a negative obstacle count");
-  if (m > (1LL << 20)) return bad("more than 2^20 obstacles");
-  if (m > 0 && !obstacles) return bad("obstacles is NULL");
-  if (!std::isfinite(robot_radius)) return bad("robot_radius is not finite");
-  if (!all_finite(obstacles, 3 * m)) return bad("an obstacle entry is not finite");
+  static const ObsListText text = {"a negative obstacle count", "more than 2^20 obstacles", "obstacles is NULL",
+                                   "an obstacle entry is not finite", "robot_radius is not finite"};
+  if (const char* e = obstacle_list_shape_error(obstacles, m, 1LL << 20, text)) return bad(e);
+  if (const char* e = obstacle_list_value_error(obstacles, m, &robot_radius, 1, text, true)) return bad(e);
   return guarded(s, "rrtx_steer_set_obstacles", [&] {
-    std::vector<double> t((size_t)(3 * m));
-    for (int64_t k = 0; k < m; k++) {
-      t[3 * k] = obstacles[3 * k];
-      t[3 * k + 1] = obstacles[3 * k + 1];
-      t[3 * k + 2] = py_sq_host(obstacles[3 * k + 2] + robot_radius);   // (size+robot_radius)**2  rrt_05:1635
-    }
+    std::vector<double> t;
+    pack_obstacle_rows(obstacles, m, robot_radius, t);   // (size+robot_radius)**2  rrt_05:1635
     s->h_obs.swap(t);
     s->obs_dirty = true;
     return obsindex_set_list(s, s->oi, obstacles, m, robot_radius);

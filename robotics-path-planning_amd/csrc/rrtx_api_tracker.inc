@@ -51,6 +51,86 @@ static int tracker_index_decide(rrtx_tracker* t, const rrtx_track_batch* b, cons
   return RRTX_OK;
 }
 
+// What both runs say of an obstacle list that is wrong (rrtx_host.h; the count has no limit of its own here)
+static const ObsListText TRACK_OBS_TEXT = {"n_obstacles is negative", nullptr, "obstacles is NULL", "an obstacle component is not finite",
+                                           "a robot radius is not finite"};
+
+// The shape of a run's obstacle lists, among the argument checks: the list itself, then what the index takes in mode ON or
+// the lane-per-obstacle check otherwise.  bad(text) records the refusal and returns its code.
+template <class Bad>
+static int tracker_check_obstacles(const rrtx_tracker* t, const rrtx_track_batch* b, int64_t n, Bad&& bad) {
+  if (const char* m = obstacle_list_shape_error(b->obstacles, b->n_obstacles, INT64_MAX, TRACK_OBS_TEXT)) return bad(m);
+  if (t->oi.mode == RRTX_OBSIDX_ON) {
+    if (const char* m = tracker_index_refusal(b)) return bad(m);
+  } else if (b->obs_offsets) {
+    if (!csr_ok(b->obs_offsets, n)) return bad("obs_offsets do not start at 0 or decrease");
+    if (b->obs_offsets[n] > b->n_obstacles) return bad("obs_offsets end beyond n_obstacles");
+    for (int64_t i = 0; i < n; i++)
+      if (b->obs_offsets[i + 1] - b->obs_offsets[i] > rppt::TPB) return bad("more than 64 obstacles in one list");
+  } else if (b->n_obstacles > rppt::TPB) {
+    return bad("more than 64 obstacles in one list");
+  }
+  return RRTX_OK;
+}
+
+// The obstacle table of a run, built, uploaded and entered into a: SoA x, y and the thresholds (radius + robot_radius) ** 2 by
+// the planners' routine; one threshold row per obstacle row, or with one shared list and a radius per course n rows of the
+// list's thresholds (the index form reads none of it: its items hold the circles)
+static int tracker_obstacle_table(rrtx_tracker* t, const rrtx_track_batch* b, int64_t n, bool indexed, rppt::CourseArgs& a) {
+  const int64_t rows = indexed ? 0 : b->obs_offsets ? b->obs_offsets[n] : b->n_obstacles;
+  const bool thr_per_course = !b->obs_offsets && b->robot_radius_per_course && rows > 0;
+  std::vector<double> ox((size_t)rows), oy((size_t)rows), othr((size_t)(thr_per_course ? rows * n : rows));
+  for (int64_t k = 0; k < rows; k++) {
+    ox[k] = b->obstacles[3 * k];
+    oy[k] = b->obstacles[3 * k + 1];
+  }
+  if (b->obs_offsets) {
+    for (int64_t i = 0; i < n; i++)
+      for (int64_t k = b->obs_offsets[i]; k < b->obs_offsets[i + 1]; k++)
+        othr[k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[b->robot_radius_per_course ? i : 0]);
+  } else if (thr_per_course) {
+    for (int64_t i = 0; i < n; i++)
+      for (int64_t k = 0; k < rows; k++) othr[i * rows + k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[i]);
+  } else {
+    for (int64_t k = 0; k < rows; k++) othr[k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[0]);
+  }
+  int rc;
+  if ((rc = t->upload(t->ox, ox.data(), sizeof(double) * ox.size()))) return rc;
+  if ((rc = t->upload(t->oy, oy.data(), sizeof(double) * oy.size()))) return rc;
+  if ((rc = t->upload(t->othr, othr.data(), sizeof(double) * othr.size()))) return rc;
+  if (b->obs_offsets && (rc = t->upload(t->obs_off, b->obs_offsets, sizeof(int64_t) * ((size_t)n + 1)))) return rc;
+  a.ox = t->ox.as<const double>();
+  a.oy = t->oy.as<const double>();
+  a.othr = t->othr.as<const double>();
+  a.obs_off = b->obs_offsets ? t->obs_off.as<const int64_t>() : nullptr;
+  a.thr_stride = thr_per_course ? rows : 0;
+  a.m_shared = b->obs_offsets ? 0 : (int32_t)rows;
+  return RRTX_OK;
+}
+
+// What else both runs put into a besides the courses: the per-course values, the parameters, the obstacle table, and the
+// records and workspace of `blocks` waves (the counter cleared)
+static int tracker_common_args(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_track_batch* b, int64_t n, bool indexed,
+                               int blocks, rppt::CourseArgs& a) {
+  const size_t N = (size_t)n;
+  int rc;
+  if (b->per_course && (rc = t->upload(t->per_course, b->per_course, sizeof(double) * 3 * N))) return rc;
+  if (b->start_state && (rc = t->upload(t->start, b->start_state, sizeof(double) * 4 * N))) return rc;
+  if ((rc = tracker_obstacle_table(t, b, n, indexed, a))) return rc;
+  if ((rc = t->reserve(t->rec, sizeof(rppt::Record) * N))) return rc;
+  if ((rc = t->reserve(t->counter, sizeof(int32_t)))) return rc;
+  if ((rc = t->reserve(t->slab, sizeof(double) * (size_t)blocks * 3 * rppt::SLAB_PTS))) return rc;
+  HIPCHK(t, hipMemsetAsync(t->counter.p, 0, sizeof(int32_t), t->stream));
+  a.n = n;
+  a.per_course = b->per_course ? t->per_course.as<const double>() : nullptr;
+  a.start = b->start_state ? t->start.as<const double>() : nullptr;
+  memcpy(&a.P, tp, sizeof(a.P));
+  a.rec = t->rec.as<rppt::Record>();
+  a.counter = t->counter.as<int32_t>();
+  a.slab = t->slab.as<double>();
+  return RRTX_OK;
+}
+
 static_assert(rppt::SEL_ALL == RRTX_SELECT_ALL && rppt::SEL_FREE == RRTX_SELECT_FREE && rppt::SEL_MASK == RRTX_SELECT_MASK,
               "the selections of the header are the core's");
 
@@ -72,23 +152,11 @@ static int tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_
   const int64_t pts = b->offsets[n];
   if (pts > 0x7fffffffLL) return bad("more than 2^31 - 1 points in all");
   if (pts > 0 && (!b->x || !b->y || !b->yaw)) return bad("x, y or yaw is NULL");
-  if (b->n_obstacles < 0) return bad("n_obstacles is negative");
-  if (b->n_obstacles > 0 && !b->obstacles) return bad("obstacles is NULL");
-  if (t->oi.mode == RRTX_OBSIDX_ON) {
-    if (const char* m = tracker_index_refusal(b)) return bad(m);
-  } else if (b->obs_offsets) {
-    if (!csr_ok(b->obs_offsets, n)) return bad("obs_offsets do not start at 0 or decrease");
-    if (b->obs_offsets[n] > b->n_obstacles) return bad("obs_offsets end beyond n_obstacles");
-    for (int64_t i = 0; i < n; i++)
-      if (b->obs_offsets[i + 1] - b->obs_offsets[i] > rppt::TPB) return bad("more than 64 obstacles in one list");
-  } else if (b->n_obstacles > rppt::TPB) {
-    return bad("more than 64 obstacles in one list");
-  }
+  if (int orc = tracker_check_obstacles(t, b, n, bad)) return orc;
   if (!track_params_ok(tp)) return bad(TRACK_PARAMS_MSG);
   const int64_t n_rr = b->robot_radius_per_course ? n : 1;
   if (!all_finite(b->x, pts) || !all_finite(b->y, pts) || !all_finite(b->yaw, pts)) return bad("a pose component is not finite");
-  if (!all_finite(b->obstacles, 3 * b->n_obstacles)) return bad("an obstacle component is not finite");
-  if (!all_finite(b->robot_radius, n_rr)) return bad("a robot radius is not finite");
+  if (const char* m = obstacle_list_value_error(b->obstacles, b->n_obstacles, b->robot_radius, n_rr, TRACK_OBS_TEXT)) return bad(m);
   if (b->start_state && !all_finite(b->start_state, 4 * n)) return bad("a start state component is not finite");
   if (b->per_course && !all_finite(b->per_course, 3 * n)) return bad("a per-course value is not finite");
   if (!all_finite(&tp->target_speed, sizeof(*tp) / sizeof(double))) return bad("a parameter is not finite");
@@ -111,27 +179,6 @@ static int tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_
     t->ran = true;
     return RRTX_OK;
   }
-  // obstacle table: SoA x, y and the thresholds (radius + robot_radius) ** 2 by the planners' routine; one threshold row per
-  // obstacle row, or with one shared list and a radius per course n rows of the list's thresholds
-  // (the index form reads none of it: its items hold the circles)
-  const int64_t rows = indexed ? 0 : b->obs_offsets ? b->obs_offsets[n] : b->n_obstacles;
-  const bool thr_per_course = !b->obs_offsets && b->robot_radius_per_course && rows > 0;
-  std::vector<double> ox((size_t)rows), oy((size_t)rows), othr((size_t)(thr_per_course ? rows * n : rows));
-  for (int64_t k = 0; k < rows; k++) {
-    ox[k] = b->obstacles[3 * k];
-    oy[k] = b->obstacles[3 * k + 1];
-  }
-  if (b->obs_offsets) {
-    for (int64_t i = 0; i < n; i++)
-      for (int64_t k = b->obs_offsets[i]; k < b->obs_offsets[i + 1]; k++)
-        othr[k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[b->robot_radius_per_course ? i : 0]);
-  } else if (thr_per_course) {
-    for (int64_t i = 0; i < n; i++)
-      for (int64_t k = 0; k < rows; k++) othr[i * rows + k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[i]);
-  } else {
-    for (int64_t k = 0; k < rows; k++) othr[k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[0]);
-  }
-
   HIPCHK(t, hipSetDevice(t->device));
   int rc;
   const size_t N = (size_t)n;
@@ -142,36 +189,14 @@ static int tracker_run(rrtx_tracker* t, const rrtx_track_params* tp, const rrtx_
   if ((rc = t->upload(t->x, b->x, sizeof(double) * (size_t)pts))) return rc;
   if ((rc = t->upload(t->y, b->y, sizeof(double) * (size_t)pts))) return rc;
   if ((rc = t->upload(t->yaw, b->yaw, sizeof(double) * (size_t)pts))) return rc;
-  if (b->per_course && (rc = t->upload(t->per_course, b->per_course, sizeof(double) * 3 * N))) return rc;
-  if (b->start_state && (rc = t->upload(t->start, b->start_state, sizeof(double) * 4 * N))) return rc;
-  if ((rc = t->upload(t->ox, ox.data(), sizeof(double) * ox.size()))) return rc;
-  if ((rc = t->upload(t->oy, oy.data(), sizeof(double) * oy.size()))) return rc;
-  if ((rc = t->upload(t->othr, othr.data(), sizeof(double) * othr.size()))) return rc;
-  if (b->obs_offsets && (rc = t->upload(t->obs_off, b->obs_offsets, sizeof(int64_t) * (N + 1)))) return rc;
-  if ((rc = t->reserve(t->rec, sizeof(rppt::Record) * N))) return rc;
-  if ((rc = t->reserve(t->counter, sizeof(int32_t)))) return rc;
-  if ((rc = t->reserve(t->slab, sizeof(double) * (size_t)blocks * 3 * rppt::SLAB_PTS))) return rc;
-  HIPCHK(t, hipMemsetAsync(t->counter.p, 0, sizeof(int32_t), t->stream));
 
   rppt::CourseArgs a;
   memset(&a, 0, sizeof(a));
-  a.n = n;
+  if ((rc = tracker_common_args(t, tp, b, n, indexed, blocks, a))) return rc;
   a.off = t->off.as<const int64_t>();
   a.x = t->x.as<const double>();
   a.y = t->y.as<const double>();
   a.yaw = t->yaw.as<const double>();
-  a.per_course = b->per_course ? t->per_course.as<const double>() : nullptr;
-  a.start = b->start_state ? t->start.as<const double>() : nullptr;
-  a.ox = t->ox.as<const double>();
-  a.oy = t->oy.as<const double>();
-  a.othr = t->othr.as<const double>();
-  a.obs_off = b->obs_offsets ? t->obs_off.as<const int64_t>() : nullptr;
-  a.thr_stride = thr_per_course ? rows : 0;
-  a.m_shared = b->obs_offsets ? 0 : (int32_t)rows;
-  memcpy(&a.P, tp, sizeof(a.P));
-  a.rec = t->rec.as<rppt::Record>();
-  a.counter = t->counter.as<int32_t>();
-  a.slab = t->slab.as<double>();
 
   // first launch: the records
   t->h_rec.resize(N);
@@ -344,22 +369,10 @@ static int tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const 
   if (src->select != RRTX_SELECT_MASK && src->mask) return bad("a mask is given without RRTX_SELECT_MASK");
   // as rrtx_tracker_run, of the fields that remain
   if (!b->robot_radius) return bad("robot_radius is NULL");
-  if (b->n_obstacles < 0) return bad("n_obstacles is negative");
-  if (b->n_obstacles > 0 && !b->obstacles) return bad("obstacles is NULL");
-  if (t->oi.mode == RRTX_OBSIDX_ON) {
-    if (const char* m = tracker_index_refusal(b)) return bad(m);
-  } else if (b->obs_offsets) {
-    if (!csr_ok(b->obs_offsets, n)) return bad("obs_offsets do not start at 0 or decrease");
-    if (b->obs_offsets[n] > b->n_obstacles) return bad("obs_offsets end beyond n_obstacles");
-    for (int64_t i = 0; i < n; i++)
-      if (b->obs_offsets[i + 1] - b->obs_offsets[i] > rppt::TPB) return bad("more than 64 obstacles in one list");
-  } else if (b->n_obstacles > rppt::TPB) {
-    return bad("more than 64 obstacles in one list");
-  }
+  if (int orc = tracker_check_obstacles(t, b, n, bad)) return orc;
   if (!track_params_ok(tp)) return bad(TRACK_PARAMS_MSG);
   const int64_t n_rr = b->robot_radius_per_course ? n : 1;
-  if (!all_finite(b->obstacles, 3 * b->n_obstacles)) return bad("an obstacle component is not finite");
-  if (!all_finite(b->robot_radius, n_rr)) return bad("a robot radius is not finite");
+  if (const char* m = obstacle_list_value_error(b->obstacles, b->n_obstacles, b->robot_radius, n_rr, TRACK_OBS_TEXT)) return bad(m);
   if (b->start_state && !all_finite(b->start_state, 4 * n)) return bad("a start state component is not finite");
   if (b->per_course && !all_finite(b->per_course, 3 * n)) return bad("a per-course value is not finite");
   if (!all_finite(&tp->target_speed, sizeof(*tp) / sizeof(double))) return bad("a parameter is not finite");
@@ -396,25 +409,6 @@ static int tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const 
     t->ran = true;
     return RRTX_OK;
   }
-  // obstacle table, as rrtx_tracker_run builds it
-  // (the index form reads none of it: its items hold the circles)
-  const int64_t rows = indexed ? 0 : b->obs_offsets ? b->obs_offsets[n] : b->n_obstacles;
-  const bool thr_per_course = !b->obs_offsets && b->robot_radius_per_course && rows > 0;
-  std::vector<double> ox((size_t)rows), oy((size_t)rows), othr((size_t)(thr_per_course ? rows * n : rows));
-  for (int64_t k = 0; k < rows; k++) {
-    ox[k] = b->obstacles[3 * k];
-    oy[k] = b->obstacles[3 * k + 1];
-  }
-  if (b->obs_offsets) {
-    for (int64_t i = 0; i < n; i++)
-      for (int64_t k = b->obs_offsets[i]; k < b->obs_offsets[i + 1]; k++)
-        othr[k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[b->robot_radius_per_course ? i : 0]);
-  } else if (thr_per_course) {
-    for (int64_t i = 0; i < n; i++)
-      for (int64_t k = 0; k < rows; k++) othr[i * rows + k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[i]);
-  } else {
-    for (int64_t k = 0; k < rows; k++) othr[k] = py_sq_host(b->obstacles[3 * k + 2] + b->robot_radius[0]);
-  }
   // the selection as the kernel reads it: the caller's mask, a steer's hits on the device, or a mask made of a spline's
   // hits (they live on the host, where a course without a sample is marked -2)
   int select = src->select;
@@ -441,40 +435,18 @@ static int tracker_run_from(rrtx_tracker* t, const rrtx_track_params* tp, const 
     d_off = t->off.as<const int64_t>();
   }
   if (select == RRTX_SELECT_MASK && (rc = t->upload(t->mask, h_mask, N))) return rc;
-  if (b->per_course && (rc = t->upload(t->per_course, b->per_course, sizeof(double) * 3 * N))) return rc;
-  if (b->start_state && (rc = t->upload(t->start, b->start_state, sizeof(double) * 4 * N))) return rc;
-  if ((rc = t->upload(t->ox, ox.data(), sizeof(double) * ox.size()))) return rc;
-  if ((rc = t->upload(t->oy, oy.data(), sizeof(double) * oy.size()))) return rc;
-  if ((rc = t->upload(t->othr, othr.data(), sizeof(double) * othr.size()))) return rc;
-  if (b->obs_offsets && (rc = t->upload(t->obs_off, b->obs_offsets, sizeof(int64_t) * (N + 1)))) return rc;
-  if ((rc = t->reserve(t->rec, sizeof(rppt::Record) * N))) return rc;
   if ((rc = t->reserve(t->goal, sizeof(double) * 3 * N))) return rc;
   if (g && (rc = t->reserve(t->winner, sizeof(int32_t) * (size_t)n_groups))) return rc;
   if (g && (rc = t->reserve(t->wgoal, sizeof(double) * 3 * (size_t)n_groups))) return rc;
-  if ((rc = t->reserve(t->counter, sizeof(int32_t)))) return rc;
-  if ((rc = t->reserve(t->slab, sizeof(double) * (size_t)blocks * 3 * rppt::SLAB_PTS))) return rc;
-  HIPCHK(t, hipMemsetAsync(t->counter.p, 0, sizeof(int32_t), t->stream));
 
   rppt::SourceArgs sa;
   memset(&sa, 0, sizeof(sa));
   rppt::CourseArgs& a = sa.c;
-  a.n = n;
+  if ((rc = tracker_common_args(t, tp, b, n, indexed, blocks, a))) return rc;
   a.off = d_off;
   a.x = v.x;
   a.y = v.y;
   a.yaw = v.yaw;
-  a.per_course = b->per_course ? t->per_course.as<const double>() : nullptr;
-  a.start = b->start_state ? t->start.as<const double>() : nullptr;
-  a.ox = t->ox.as<const double>();
-  a.oy = t->oy.as<const double>();
-  a.othr = t->othr.as<const double>();
-  a.obs_off = b->obs_offsets ? t->obs_off.as<const int64_t>() : nullptr;
-  a.thr_stride = thr_per_course ? rows : 0;
-  a.m_shared = b->obs_offsets ? 0 : (int32_t)rows;
-  memcpy(&a.P, tp, sizeof(a.P));
-  a.rec = t->rec.as<rppt::Record>();
-  a.counter = t->counter.as<int32_t>();
-  a.slab = t->slab.as<double>();
   sa.select = select;
   sa.hit = select == RRTX_SELECT_FREE ? v.d_hit : nullptr;
   sa.mask = select == RRTX_SELECT_MASK ? t->mask.as<const uint8_t>() : nullptr;

@@ -14,7 +14,9 @@
 #include <exception>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <utility>
+#include <vector>
 
 #include "../../include/rrtx.h"
 
@@ -46,6 +48,55 @@ inline bool csr_ok(const int64_t* off, int64_t n) {
   for (int64_t i = 0; i < n; i++)
     if (off[i + 1] < off[i]) return false;
   return true;
+}
+
+// An obstacle list as a caller hands it over: m rows (x, y, size) and the robot radius (or one radius per course).  The
+// checks come in two steps, because the entry points check other arguments between them; each returns the caller's own
+// text for the first thing that is wrong, or nullptr.
+struct ObsListText {
+  const char *negative, *too_many, *null, *row, *radius;
+};
+inline const char* obstacle_list_shape_error(const double* oxyr, int64_t m, int64_t m_max, const ObsListText& t) {
+  if (m < 0) return t.negative;
+  if (m > m_max) return t.too_many;
+  if (m > 0 && !oxyr) return t.null;
+  return nullptr;
+}
+// radius_first: which of the two a list with both faults is refused for
+inline const char* obstacle_list_value_error(const double* oxyr, int64_t m, const double* radius, int64_t n_radius,
+                                             const ObsListText& t, bool radius_first = false) {
+  if (radius_first && !all_finite(radius, n_radius)) return t.radius;
+  if (!all_finite(oxyr, 3 * m)) return t.row;
+  return all_finite(radius, n_radius) ? nullptr : t.radius;
+}
+
+// The rows as the kernels read them: (ox, oy, thr), thr = (size + robot_radius) ** 2 by the planners' routine
+inline void pack_obstacle_rows(const double* oxyr, int64_t m, double radius, std::vector<double>& rows) {
+  rows.resize(3 * (size_t)m);
+  for (int64_t k = 0; k < m; k++) {
+    rows[3 * k] = oxyr[3 * k];
+    rows[3 * k + 1] = oxyr[3 * k + 1];
+    rows[3 * k + 2] = py_sq_host(oxyr[3 * k + 2] + radius);
+  }
+}
+
+// The kernels with one lane per point of a curve come as <STORE, CHECK>, CHECK one of rppc::CHECK_* (curve_check.hip.h:
+// 0 none, 1 the linear loop, 2 the obstacle index).  Calls f with the pair as constants; one of store and check is wanted,
+// so <false, 0> does not exist: without either the call is f(false, 1).
+template <class F>
+void with_store_check(bool store, int check, F&& f) {
+  using std::bool_constant;
+  using std::integral_constant;
+  if (store && check == 2)
+    f(bool_constant<true>{}, integral_constant<int, 2>{});
+  else if (store && check)
+    f(bool_constant<true>{}, integral_constant<int, 1>{});
+  else if (store)
+    f(bool_constant<true>{}, integral_constant<int, 0>{});
+  else if (check == 2)
+    f(bool_constant<false>{}, integral_constant<int, 2>{});
+  else
+    f(bool_constant<false>{}, integral_constant<int, 1>{});
 }
 
 // the tracking parameters rrtx_track_planned and rrtx_tracker_run accept, and what they say otherwise

@@ -24,17 +24,14 @@
 // The coefficient table is eight planes of W doubles (W = waypoints of the batch), waypoint CSR layout:
 //   0 s (axis x's), 1 s (axis y's copy), 2 bx, 3 cx, 4 dx, 5 by, 6 cy, 7 dy;  a = the waypoints themselves.
 #pragma once
-#include "rpp_collide.h"
-#include "rpp_obsgrid.h"
+#include "curve_check.hip.h"
 #include "rpp_spline.h"
 
 namespace rppsp {
 
 constexpr int TPB = 256;
 constexpr int MAX_WAYPOINTS = 4096;   // per course: bounds one lane's sequential sweep (include/rrtx.h)
-// spline_eval_kernel's CHECK: no obstacle test, the linear loop (rpp::first_hit), or the obstacle index
-// (rppo::point_first_hit); a template parameter, so that a launch without the index carries none of its registers
-constexpr int CHECK_NONE = 0, CHECK_LINEAR = 1, CHECK_INDEX = 2;
+using rppc::CHECK_NONE, rppc::CHECK_LINEAR, rppc::CHECK_INDEX, rppc::csr_row;   // spline_eval_kernel's CHECK (curve_check.hip.h)
 
 struct Record {   // rrtx_spline_record
   int32_t status, reserved;
@@ -62,19 +59,6 @@ struct Args {
 
 __device__ inline double course_ds(const Args& a, int64_t c) { return a.ds[a.ds_per_course ? c : 0]; }
 
-// The row r of a CSR list with off[r] <= idx < off[r + 1], for 0 <= idx < off[n] (rows without entries are skipped over)
-__device__ inline int64_t csr_row(const int64_t* off, int64_t n, int64_t idx) {
-  int64_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int64_t mid = lo + (hi - lo) / 2;
-    if (off[mid] <= idx)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(TPB) void spline_fit_kernel(Args a) {
   const int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (idx >= 2 * a.n) return;
@@ -100,9 +84,7 @@ __global__ __launch_bounds__(TPB) void spline_fit_kernel(Args a) {
   if (a.hit) a.hit[c] = st == rpp::kSplineOk ? -1 : -2;
 }
 
-// With CHECK a lane past the last point does not leave: it stays as a copy of the last point (the same course, the same
-// answer), so every lane of a wave takes part in the shuffles below.  hit[] is read as unsigned for the minimum: -1
-// (free) is then the largest value, and -2 belongs to courses without points.
+// The lanes past the last point, and hit[]: curve_check.hip.h
 template <bool STORE, int CHECK>
 __global__ __launch_bounds__(TPB) void spline_eval_kernel(Args a) {
   int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -124,25 +106,7 @@ __global__ __launch_bounds__(TPB) void spline_eval_kernel(Args a) {
     for (int q = 0; q < 4; q++) a.out[q * total + idx] = p[q];
     a.out[4 * total + idx] = t;
   }
-  if (CHECK) {
-    const uint32_t NONE = 0xffffffffu;
-    const uint32_t h =
-        (uint32_t)(CHECK == CHECK_INDEX ? rppo::point_first_hit(a.omap, p[0], p[1]) : rpp::first_hit(a.obs, a.n_obs, p[0], p[1]));
-    if (!__any(h != NONE)) return;
-    uint32_t* out = (uint32_t*)a.hit;
-    const int course = (int)lo;   // n <= 2^30
-    const int course0 = __shfl(course, 0);
-    if (__all(course == course0)) {   // the wave lies within one course: one atomic
-      uint32_t m = h;
-      for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)m, off);
-        m = o < m ? o : m;
-      }
-      if ((threadIdx.x & 63) == 0) atomicMin(out + course0, m);
-    } else if (h != NONE) {
-      atomicMin(out + course, h);
-    }
-  }
+  if (CHECK) rppc::check_point<CHECK>(a.obs, a.n_obs, a.omap, a.hit, lo, p[0], p[1]);
 }
 
 struct QueryArgs {

@@ -41,10 +41,9 @@
 // for points and stage 2 runs with CHECK alone, so no point is ever written.
 // Product mode: pair p of ns x ng is (start p / ng, goal p % ng), formed here; the host never builds the product.
 #pragma once
+#include "curve_check.hip.h"
 #include "rpp_bezier.h"
-#include "rpp_collide.h"
 #include "rpp_lqr.h"
-#include "rpp_obsgrid.h"
 #include "rpp_rs.h"
 
 namespace rppsb {
@@ -57,9 +56,7 @@ constexpr int TPB = 256;            // steer_dubins_solve, steer_rs_course, stee
 constexpr int RS_TPB = 64;          // steer_rs_solve: one wave
 constexpr int RS_LANES = 16;        // lanes per pair
 constexpr int RS_PAIRS = RS_TPB / RS_LANES;
-// steer_fill's CHECK: no obstacle test, the linear loop over the rows (rpp::first_hit), or the obstacle index
-// (rppo::point_first_hit).  A template parameter and not a branch: a launch without the index carries none of its registers.
-constexpr int CHECK_NONE = 0, CHECK_LINEAR = 1, CHECK_INDEX = 2;
+using rppc::CHECK_NONE, rppc::CHECK_LINEAR, rppc::CHECK_INDEX, rppc::csr_row;   // steer_fill's CHECK (curve_check.hip.h)
 constexpr int RS_KEPT = 3;          // table state: set_path kept this candidate (0 none, 1 candidate, 2 step too large)
 
 struct Args {
@@ -113,18 +110,6 @@ __device__ inline void pair_poses(const Args& a, int64_t p, double* s, double* g
 __device__ inline double pair_curv(const Args& a, int64_t p) { return a.curv ? a.curv[p] : a.curv0; }
 // the pair whose poses and curvature record r is built from
 __device__ inline int64_t record_pair(const Args& a, int64_t r) { return a.cand_pair ? a.cand_pair[r] : r; }
-// the row r of a CSR offset array with off[r] <= idx < off[r + 1] (rows without entries are skipped over)
-__device__ inline int64_t csr_row(const int64_t* off, int64_t n, int64_t idx) {
-  int64_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int64_t mid = lo + (hi - lo) / 2;
-    if (off[mid] <= idx)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return lo;
-}
 __device__ inline void pair_xy(const Args& a, int64_t p, double* s, double* g) {   // LQR: rows (x, y)
   const int64_t si = a.product ? p / a.ng : p, gi = a.product ? p % a.ng : p;
   for (int i = 0; i < 2; i++) {
@@ -381,9 +366,7 @@ __global__ __launch_bounds__(TPB) void steer_bezier_solve(Args a) {
 }
 
 // ---- stage 2 -------------------------------------------------------------------------------------------------------
-// <KIND, true, CHECK_NONE> is the fill kernel alone.  With CHECK a lane past the last point does not leave: it stays as a copy
-// of the last point (the same pair, the same answer), so every lane of a wave takes part in the shuffles below.
-// hit[] is read as unsigned for the minimum: -1 (free) is then the largest value, and -2 belongs to pairs without points.
+// <KIND, true, CHECK_NONE> is the fill kernel alone.  The lanes past the last point, and hit[]: curve_check.hip.h.
 template <int KIND, bool STORE, int CHECK>
 __global__ __launch_bounds__(TPB) void steer_fill(Args a) {
   int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -423,27 +406,7 @@ __global__ __launch_bounds__(TPB) void steer_fill(Args a) {
     if (KIND != KIND_LQR) a.pyaw[idx] = yaw;   // an LQR course has no yaw
     if (KIND == KIND_BEZIER && a.pk) a.pk[idx] = kk;
   }
-  if (CHECK) {
-    // The obstacle index is the same in every lane still in first_hit's loop, and a lane leaves the loop at its first
-    // hit: the wave is done with the list as soon as all its lanes have one.
-    const uint32_t NONE = 0xffffffffu;
-    // With the index every lane walks the run of its own cell instead: the answer is the same int32.
-    const uint32_t h = (uint32_t)(CHECK == CHECK_INDEX ? rppo::point_first_hit(a.omap, x, y) : rpp::first_hit(a.obs, a.n_obs, x, y));
-    if (!__any(h != NONE)) return;
-    uint32_t* out = (uint32_t*)a.hit;
-    const int pair = (int)lo;   // n <= 2^30
-    const int pair0 = __shfl(pair, 0);
-    if (__all(pair == pair0)) {   // the wave lies within one curve (the common case for long curves): one atomic
-      uint32_t m = h;
-      for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)m, off);
-        m = o < m ? o : m;
-      }
-      if ((threadIdx.x & 63) == 0) atomicMin(out + pair0, m);
-    } else if (h != NONE) {
-      atomicMin(out + pair, h);
-    }
-  }
+  if (CHECK) rppc::check_point<CHECK>(a.obs, a.n_obs, a.omap, a.hit, lo, x, y);
 }
 
 // ---- every candidate curve of a pair, and the shortest one that is free -------------------------------------------------

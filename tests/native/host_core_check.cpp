@@ -163,6 +163,62 @@ static void the_shared_helpers() {
   CHECK(!track_params_ok(&tp));
 }
 
+// with_store_check reaches <STORE, CHECK> for the five pairs the kernels exist for; (false, none) falls to <false, linear>
+static void store_check_dispatch() {
+  const struct { bool store; int check; bool want_store; int want_check; } cases[6] = {
+      {true, 2, true, 2}, {true, 1, true, 1}, {true, 0, true, 0}, {false, 2, false, 2}, {false, 1, false, 1}, {false, 0, false, 1}};
+  for (const auto& c : cases) {
+    int calls = 0;
+    with_store_check(c.store, c.check, [&](auto st, auto ck) {
+      static_assert(decltype(st)::value || decltype(ck)::value != 0, "<false, none> is never instantiated");
+      calls++;
+      CHECK(decltype(st)::value == c.want_store && decltype(ck)::value == c.want_check);
+    });
+    CHECK(calls == 1);
+  }
+}
+
+static void obstacle_rows_are_packed() {
+  std::vector<double> rows(7, -1.0);
+  pack_obstacle_rows(nullptr, 0, 0.5, rows);
+  CHECK(rows.empty());
+  // one row; a negative size + radius; a size whose square overflows
+  const double one[3] = {1.5, -2.5, 0.75};
+  pack_obstacle_rows(one, 1, 0.25, rows);
+  CHECK(rows.size() == 3 && rows[0] == 1.5 && rows[1] == -2.5 && rows[2] == py_sq_host(0.75 + 0.25) && rows[2] == 1.0);
+  const double three[9] = {0.0, 1.0, 0.5, 2.0, 3.0, -1.0, 4.0, 5.0, 1e200};
+  pack_obstacle_rows(three, 3, -2.0, rows);
+  CHECK(rows.size() == 9);
+  for (int k = 0; k < 3; k++) {
+    CHECK(rows[3 * k] == three[3 * k] && rows[3 * k + 1] == three[3 * k + 1]);
+    CHECK(rows[3 * k + 2] == py_sq_host(three[3 * k + 2] + -2.0));
+  }
+  CHECK(rows[2] == 2.25 && rows[5] == 9.0 && std::isinf(rows[8]) && rows[8] > 0.0);
+}
+
+static void obstacle_list_checks_refuse_in_the_callers_words() {
+  const ObsListText t = {"negative", "too many", "null", "row", "radius"};
+  const double ok[6] = {0.0, 1.0, 0.5, 2.0, 3.0, 0.5}, nan_row[6] = {0.0, 1.0, 0.5, 2.0, NAN, 0.5};
+  const double r = 0.5, nan_r = NAN, rr[2] = {0.5, INFINITY};
+  const int64_t cap = 1LL << 20;
+  auto is = [](const char* got, const char* want) { return got && std::string(got) == want; };
+  CHECK(is(obstacle_list_shape_error(ok, -1, cap, t), "negative"));
+  CHECK(is(obstacle_list_shape_error(ok, cap + 1, cap, t), "too many"));
+  CHECK(is(obstacle_list_shape_error(nullptr, 1, cap, t), "null"));
+  CHECK(obstacle_list_shape_error(nullptr, 0, cap, t) == nullptr);   // no rows: no pointer needed
+  CHECK(obstacle_list_shape_error(ok, 2, cap, t) == nullptr && obstacle_list_shape_error(ok, cap, cap, t) == nullptr);
+  CHECK(obstacle_list_shape_error(ok, cap + 1, INT64_MAX, t) == nullptr);   // a caller without a limit of its own
+  CHECK(is(obstacle_list_value_error(nan_row, 2, &r, 1, t), "row"));
+  CHECK(is(obstacle_list_value_error(ok, 2, &nan_r, 1, t), "radius"));
+  CHECK(is(obstacle_list_value_error(ok, 2, rr, 2, t), "radius") && obstacle_list_value_error(ok, 2, rr, 1, t) == nullptr);
+  CHECK(obstacle_list_value_error(ok, 2, &r, 1, t) == nullptr && obstacle_list_value_error(nullptr, 0, &r, 1, t) == nullptr);
+  CHECK(obstacle_list_value_error(nan_row, 1, &r, 1, t) == nullptr);   // the NaN lies in the second row
+  // both wrong: the rows are named first, unless the caller checks the radius first
+  CHECK(is(obstacle_list_value_error(nan_row, 2, &nan_r, 1, t), "row"));
+  CHECK(is(obstacle_list_value_error(nan_row, 2, &nan_r, 1, t, true), "radius"));
+  CHECK(is(obstacle_list_value_error(nan_row, 2, &r, 1, t, true), "row"));
+}
+
 // what an object of the C ABI looks like to the shared lifecycle: a DevObj with buffers and a result flag
 struct Probe : DevObj {
   DevBuf b;
@@ -274,6 +330,9 @@ int main() {
   open_and_the_device_probe();
   timed_section();
   the_shared_helpers();
+  store_check_dispatch();
+  obstacle_rows_are_packed();
+  obstacle_list_checks_refuse_in_the_callers_words();
   create_object_refuses_and_creates();
   destroy_object_releases_in_order();
   guarded_entry_points();
