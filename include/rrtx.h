@@ -194,8 +194,9 @@ int rrtx_set_obstacles(rrtx_handle* h, const double* oxyr, int32_t m);
  * more than 256 obstacles (RRTX_ALGO_RS: 64); RRTX_E_STATE between rrtx_plan_begin and the end of that plan.  Workgroup
  * shapes and capacities follow the largest list; rrtx_smooth_planned smooths each path against its instance's list. */
 int rrtx_set_instance_obstacles(rrtx_handle* h, const int32_t* offsets, const double* oxyr);
-/* The obstacle map: any number of circles up to 2^20 for RRTX_ALGO_RRT and RRTX_ALGO_RRT_STAR (rrt_01 / rrt_02 / rrt_04),
- * shared by all instances.  rrtx_set_obstacles and rrtx_set_instance_obstacles keep their limits (256, RRTX_ALGO_RS 64): they
+/* The obstacle map: any number of circles up to 2^20 for RRTX_ALGO_RRT and RRTX_ALGO_RRT_STAR (rrt_01 / rrt_02 / rrt_04) and for
+ * RRTX_ALGO_RS (rrt_06, and rrt_10 with RRTX_RS_COST_PATH: see the end of this comment), shared by all instances.
+ * rrtx_set_obstacles and rrtx_set_instance_obstacles keep their limits (256, RRTX_ALGO_RS 64): they
  * stage the list in the kernels' obstacle tile.  This call builds, on the device, a uniform grid over the list instead (cells
  * over the sampling square of rand_min / rand_max, about one circle per cell; a circle is listed in every cell its square
  * [ox +- rho] x [oy +- rho] overlaps, rho = |size + robot_radius| rounded up, and in a "wide" list once it would cover more than
@@ -210,7 +211,12 @@ int rrtx_set_instance_obstacles(rrtx_handle* h, const int32_t* offsets, const do
  * device call.  A failure leaves the handle, and the map or lists it holds, as they were.
  * Not served while the handle holds a map (RRTX_E_STATE, the message names the map): rrtx_smooth_planned and rrtx_query_goals,
  * which read the obstacle table.  Test knobs: RRTX_OBSMAP_CELLS (cells per axis; 1 = every box streams the whole list),
- * RRTX_OBSMAP_TILE (records per tile, below 256). */
+ * RRTX_OBSMAP_TILE (records per tile, below 256).
+ * RRTX_ALGO_RS: the same grid (its geometry is the sampling square's; Reeds-Shepp arcs that leave the square and circles that
+ * lie outside it fall into the edge cells, which the rules cover).  The planner kernel has no tile to refill: every point of an
+ * edge asks the grid "does any circle hold this point" from the run of its own cell and the wide list, which is the verdict
+ * of rrt_06's check_collision :1748-1762.  rrtx_track_planned and rrtx_track_goals then test their roll-outs against the map
+ * as well; RRTX_OBSMAP_TILE is not read. */
 int rrtx_set_obstacle_map(rrtx_handle* h, const double* oxyr, int64_t m);
 typedef struct rrtx_obstacle_map_info {
   double x0, y0, cell;   /* origin of the grid and side of a cell */

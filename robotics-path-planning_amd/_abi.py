@@ -68,7 +68,8 @@ EXPORTS = ["rrtx_abi_version", "rrtx_device_count", "rrtx_create", "rrtx_set_obs
 OBSIDX_AUTO, OBSIDX_ON, OBSIDX_OFF, OBSIDX_MIN = 0, 1, 2, 256                          # include/rrtx.h: #define RRTX_OBSIDX_*
 OBSIDX_REASONS = ("used", "off", "below the threshold", "run too long", "non-finite reach", "empty")   # RRTX_OBSIDX_REASON_*
 OBSTACLE_TILE_MAX, OBSTACLE_MAP_MAX = 256, 1 << 20   # csrc MAX_OBS (rrtx_set_obstacles), rpp_obsgrid.h M_MAX (rrtx_set_obstacle_map)
-OBSTACLE_MAP_ALGOS = (0, 1)                          # RRTX_ALGO_RRT, RRTX_ALGO_RRT_STAR
+OBSTACLE_TILE_MAX_RS = 64                            # csrc rppr::MAX_OBS: the tile of RRTX_ALGO_RS (rrtx_set_obstacles)
+OBSTACLE_MAP_ALGOS = (0, 1, ALGO_RS)                 # RRTX_ALGO_RRT, RRTX_ALGO_RRT_STAR, RRTX_ALGO_RS
 STEER_DUBINS, STEER_RS = 0, 1                                                      # include/rrtx.h: #define RRTX_STEER_*
 STEER_LQR = 2   # this binding's own name for "solved by rrtx_steer_solve_lqr": the C ABI has an entry point, not a kind value
 STEER_BEZIER = 3   # likewise: rrtx_steer_solve_bezier / rrtx_steer_solve_bezier_cp
@@ -282,10 +283,11 @@ def obstacle_index_mode(obstacle_index):
 OBSTACLE_ITEM = np.dtype([("ox", np.float64), ("oy", np.float64), ("thr", np.float64), ("index", np.int64)])
 
 
-def use_obstacle_map(obstacle_map, n_obstacles):
-    """The `obstacle_map` keyword of the planners: None = the map when the list does not fit the tile, True, False."""
+def use_obstacle_map(obstacle_map, n_obstacles, limit=OBSTACLE_TILE_MAX):
+    """The `obstacle_map` keyword of the planners: None = the map when the list does not fit the tile (`limit` circles:
+    OBSTACLE_TILE_MAX, or OBSTACLE_TILE_MAX_RS for the Reeds-Shepp planners), True, False."""
     if obstacle_map is None:
-        return n_obstacles > OBSTACLE_TILE_MAX
+        return n_obstacles > limit
     if obstacle_map is True or obstacle_map is False:
         return obstacle_map
     raise ValueError("obstacle_map is None, True or False, got %r" % (obstacle_map,))
@@ -594,7 +596,8 @@ class Handle:
         self._chk(self.L.rrtx_set_obstacles(self._h, a.ctypes.data, len(a)), "rrtx_set_obstacles")
 
     def set_obstacle_map(self, obstacle_list):
-        """Any number of circles up to 2**20 through the obstacle map (rrtx_set_obstacle_map); "rrt" / "rrt_star" only."""
+        """Any number of circles up to 2**20 through the obstacle map (rrtx_set_obstacle_map); "rrt" / "rrt_star" and the
+        Reeds-Shepp planners ("rrt_star_reeds_shepp", "closed_loop_rrt_star") only."""
         a = np.ascontiguousarray(np.array([[float(v) for v in o] for o in obstacle_list], dtype=np.float64)
                                  .reshape(-1, 3))
         self._chk(self.L.rrtx_set_obstacle_map(self._h, a.ctypes.data if len(a) else None, len(a)), "rrtx_set_obstacle_map")

@@ -18,7 +18,8 @@
 //   -- the host takes the exclusive sum of len + 1 over the flagged queries (array_offsets) --
 //   goal_roll_kernel(store = 1) the winners again, their seven arrays stored with the goal pose behind x, y, yaw: memory is
 //                               bounded by the winners' lengths, not by 2 002 x 7 doubles per candidate
-// Capacities are track_roll_kernel's (LDS_PTS, SLAB_PTS, 64 obstacles); at most 2^24 candidates per call (host check).
+// Capacities are track_roll_kernel's (LDS_PTS, SLAB_PTS, 64 obstacles per instance, or the handle's obstacle map of any number
+// of circles); at most 2^24 candidates per call (host check).
 #pragma once
 #include "rpp_goaltrack.h"
 #include "rrt_track.hip.h"
@@ -89,8 +90,10 @@ __global__ __launch_bounds__(TPB) void goal_cand_kernel(GoalTrackArgs a, int fil
 }
 
 // store = 0: job j is candidate j (n_jobs of them), rec[j] written; store = 1: job j is query win_query[j] (counters[1] of
-// them), the winner's arrays written
-__global__ __launch_bounds__(TPB) void goal_roll_kernel(GoalTrackArgs a, int store) {
+// them), the winner's arrays written.
+// CHECK_INDEX: the handle holds an obstacle map (every instance's rows are empty); mp is that map, a.ox / oy / othr are not read
+template <int CHECK>
+__global__ __launch_bounds__(TPB) void goal_roll_kernel(GoalTrackArgs a, int store, rppo::Map mp) {
   __shared__ double lcx[rppt::LDS_PTS], lcy[rppt::LDS_PTS];
   __shared__ signed char lsp[rppt::SLAB_PTS];
   __shared__ int32_t s_job, s_n;
@@ -125,12 +128,15 @@ __global__ __launch_bounds__(TPB) void goal_roll_kernel(GoalTrackArgs a, int sto
     const int total = rppt::lay_course(a.parent, a.poff, a.plen, off, (int)a.stride, a.pool[3 * inst], a.pool[3 * inst + 1],
                                        a.pool[3 * inst + 2], node, I->start, gx, gy, gyaw, lcx, lcy, gcw, cx, cy, r);
     if (!r.ood) {
-      const int m = I->obs_m;
+      int m = 0;
       double obx = 0.0, oby = 0.0, obt = -1.0;
-      if (lane < m) {
-        obx = a.ox[I->obs_base + lane];
-        oby = a.oy[I->obs_base + lane];
-        obt = a.othr[I->obs_base + lane];
+      if constexpr (CHECK == rppt::CHECK_LINEAR) {
+        m = I->obs_m;
+        if (lane < m) {
+          obx = a.ox[I->obs_base + lane];
+          oby = a.oy[I->obs_base + lane];
+          obt = a.othr[I->obs_base + lane];
+        }
       }
       double* o7 = nullptr;
       int ocap = 0;
@@ -139,7 +145,7 @@ __global__ __launch_bounds__(TPB) void goal_roll_kernel(GoalTrackArgs a, int sto
         o7 = a.out + a.arr_off[q];
       }
       const rppt::State s0 = {-0.0, -0.0, 0.0, 0.0};   // :1309
-      rppt::roll_course<rppt::CHECK_LINEAR>(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, a.out_total, r);
+      rppt::roll_course<CHECK>(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, a.out_total, r, &mp);
       if (o7 && lane == 0 && r.find && r.n == ocap) {   // :1519-1521: the goal pose behind x, y, yaw; the other four end in NaN
         const double nan = rpp::b2d(0x7ff8000000000000ULL);
         o7[r.n] = gx;

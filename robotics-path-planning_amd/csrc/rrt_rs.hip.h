@@ -26,6 +26,7 @@
 // Scans use correctly rounded squares as a filter and the reference's pow-based distance for near-ties and hits.
 // Cost propagation is a level-synchronous sweep over the parent array.
 #pragma once
+#include "rpp_obsgrid.h"
 #include "rpp_rs.h"
 #include "rrt_dubins.hip.h"
 
@@ -80,9 +81,16 @@ __device__ __forceinline__ void wave_argmin(double& v, int& idx) {
   }
 }
 
+// rrt_rs_map_kernel's copy of its obstacle map (a launch argument), where the out-of-line edge routine reads it; ShR keeps
+// its layout and rrt_rs_kernel allocates none of it
+__shared__ rppo::Map rs_map_lds;
+
 // Cooperative steer (fx,fy,fyaw) -> (tx,ty,tyaw).  Wave-uniform return: 1 a node exists (course in sh.course, its
 // points written at px/py/pyaw when they fit `room`, *coll = check_collision fails, *npts = points), 0 steer
 // returns None, < 0 the reference raises (-3 ZeroDivisionError, -4 ValueError), -1 pool full.
+// m: the rows of the LDS tile to test; MAP: non-zero tests every point through the obstacle map instead (each lane walks the
+// run of its point's cell and the wide run, rpp_obsgrid.h point_first_hit), 0 tests nothing.
+template <bool MAP>
 __device__ __noinline__ int rs_edge(const DubArgs& da, int m, ShR& sh, double fx, double fy, double fyaw, double tx,
                                     double ty, double tyaw, double* __restrict__ px, double* __restrict__ py,
                                     double* __restrict__ pyaw, int64_t room, int* coll, int* npts) {
@@ -220,9 +228,13 @@ __device__ __noinline__ int rs_edge(const DubArgs& da, int m, ShR& sh, double fx
     px[k] = wx;
     py[k] = wy;
     pyaw[k] = wyaw;
-    for (int o = 0; o < m; o++) {
-      const double dx = sh.ox[o] - wx, dy = sh.oy[o] - wy;
-      if (dx * dx + dy * dy <= sh.othr[o]) hit = 1;
+    if constexpr (MAP) {
+      if (m && rppo::point_first_hit(rs_map_lds, wx, wy) >= 0) hit = 1;
+    } else {
+      for (int o = 0; o < m; o++) {
+        const double dx = sh.ox[o] - wx, dy = sh.oy[o] - wy;
+        if (dx * dx + dy * dy <= sh.othr[o]) hit = 1;
+      }
     }
     if (k == total - 1) {
       sh.ex = wx;
@@ -240,7 +252,11 @@ __device__ __noinline__ int rs_edge(const DubArgs& da, int m, ShR& sh, double fx
 #ifndef RS_WAVES
 #define RS_WAVES 4   // measured: 2 waves/SIMD (no spills) 3.3, 4 waves 5.8, 6 waves 6.5 plans/ms on the c6 workload
 #endif
-__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, RS_WAVES))) void rrt_rs_kernel(Ctx c, DubArgs da, int iters) {
+// The whole plan of one instance: the body of rrt_rs_kernel (MAP = false: the obstacles of an instance are the LDS tile, at
+// most MAX_OBS rows) and of rrt_rs_map_kernel (MAP = true: every instance's rows are empty and the edge routine asks the
+// obstacle map *mp, any number of circles).
+template <bool MAP>
+__device__ __forceinline__ void rrt_rs_body(Ctx c, DubArgs da, int iters, const rppo::Map* mp) {
   __shared__ ShR sh;
   const int inst = c.inst_map ? c.inst_map[blockIdx.x] : blockIdx.x;
   const int lane = threadIdx.x;
@@ -261,15 +277,19 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
   double* pool_x = da.pool_x + pslot * da.pool_cap;
   double* pool_y = da.pool_y + pslot * da.pool_cap;
   double* pool_w = da.pool_yaw + pslot * da.pool_cap;
-  const int ob = __builtin_amdgcn_readfirstlane(I->obs_base), m = __builtin_amdgcn_readfirstlane(I->obs_m);
+  const int ob = __builtin_amdgcn_readfirstlane(I->obs_base), mt = __builtin_amdgcn_readfirstlane(I->obs_m);
+  const int m = MAP ? 1 : mt;   // what rs_edge is told to test: the tile's rows, or "ask the map"
 
   for (int i = lane; i < 624; i += TPB) sh.rng.mt[i] = I->rng.mt[i];
-  for (int i = lane; i < m; i += TPB) {
+  for (int i = lane; i < mt; i += TPB) {   // with a map every instance has obs_m = 0 (rrtx_set_obstacle_map)
     sh.ox[i] = c.ox[ob + i];
     sh.oy[i] = c.oy[ob + i];
     sh.othr[i] = c.othr[ob + i];
   }
   if (lane == 0) sh.rng.pos = I->rng.pos;
+  if constexpr (MAP) {
+    if (lane == 0) rs_map_lds = *mp;
+  }
 #ifdef RRTX_PHASE_TIMERS
   if (lane < 16) sh.ph[lane] = 0;
   const int64_t tk0_ = (int64_t)__builtin_amdgcn_s_memtime();
@@ -402,7 +422,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
     RS_M(5);
     // ---------------- steer :1541 + check_collision :1543
     int coll = 0, np0 = 0;
-    const int ok0 = rs_edge(da, m, sh, x[ni], y[ni], yaw[ni], rx, ry, ryaw, pool_x + pool_used, pool_y + pool_used,
+    const int ok0 = rs_edge<MAP>(da, m, sh, x[ni], y[ni], yaw[ni], rx, ry, ryaw, pool_x + pool_used, pool_y + pool_used,
                             pool_w + pool_used, da.pool_cap - pool_used, &coll, &np0);
     if (fatal(ok0)) break;
     RS_M(6);
@@ -490,7 +510,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
         for (int p = 0; p < k; p++) {
           const int i = near[p];
           int cl = 0;
-          const int tk = rs_edge(da, m, sh, x[i], y[i], yaw[i], nx, ny, nyaw, pool_x + pool_used, pool_y + pool_used,
+          const int tk = rs_edge<MAP>(da, m, sh, x[i], y[i], yaw[i], nx, ny, nyaw, pool_x + pool_used, pool_y + pool_used,
                                  pool_w + pool_used, da.pool_cap - pool_used, &cl, &npt);
           if (fatal(tk)) break;
           s_e += tk ? 1 : 0;
@@ -524,7 +544,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
           if (bp == 0x7fffffff) break;   // every candidate tried: "There is no good path" :1805
           const int i = near[bp];
           int cl = 0;
-          const int tk = rs_edge(da, m, sh, x[i], y[i], yaw[i], nx, ny, nyaw, pool_x + pool_used, pool_y + pool_used,
+          const int tk = rs_edge<MAP>(da, m, sh, x[i], y[i], yaw[i], nx, ny, nyaw, pool_x + pool_used, pool_y + pool_used,
                                  pool_w + pool_used, da.pool_cap - pool_used, &cl, &npt);
           if (fatal(tk)) break;
           s_e += tk ? 1 : 0;
@@ -549,7 +569,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
         if (da.eager || da.rs_cost) {
           // the re-steer of :1810 (not collision-checked again); in the lazy order the winner is the edge just laid out
           int cl = 0;
-          const int bk = rs_edge(da, m, sh, x[min_ind], y[min_ind], yaw[min_ind], nx, ny, nyaw, pool_x + pool_used,
+          const int bk = rs_edge<MAP>(da, m, sh, x[min_ind], y[min_ind], yaw[min_ind], nx, ny, nyaw, pool_x + pool_used,
                                  pool_y + pool_used, pool_w + pool_used, da.pool_cap - pool_used, &cl, &npt);
           if (fatal(bk)) break;
           s_pts += bk ? npt : 0;
@@ -584,7 +604,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
           }
           const int i = near[p];
           int rc2 = 0, rn = 0;
-          const int ek = rs_edge(da, m, sh, x[me], y[me], yaw[me], x[i], y[i], yaw[i], pool_x + pool_used,
+          const int ek = rs_edge<MAP>(da, m, sh, x[me], y[me], yaw[me], x[i], y[i], yaw[i], pool_x + pool_used,
                                  pool_y + pool_used, pool_w + pool_used, da.pool_cap - pool_used, &rc2, &rn);
           if (fatal(ek)) break;
           s_e += ek ? 1 : 0;
@@ -628,7 +648,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
                     bm &= bm - 1ULL;
                     const int pj = parent[jj];
                     int pc = 0, pn = 0;
-                    const int pk = rs_edge(da, 0, sh, x[pj], y[pj], yaw[pj], x[jj], y[jj], yaw[jj], pool_x + pool_used,
+                    const int pk = rs_edge<MAP>(da, 0, sh, x[pj], y[pj], yaw[pj], x[jj], y[jj], yaw[jj], pool_x + pool_used,
                                            pool_y + pool_used, pool_w + pool_used, da.pool_cap - pool_used, &pc, &pn);
                     if (fatal(pk)) break;
                     const double nc = pk ? cost[pj] + sh.cost_len : rpp::dinf();
@@ -677,7 +697,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
         RS_M(10);
         // ---------------- try_goal_path :1572-1582
         int gc = 0, gn = 0;
-        const int gk = rs_edge(da, m, sh, x[me], y[me], yaw[me], gx, gy, gyaw, pool_x + pool_used,
+        const int gk = rs_edge<MAP>(da, m, sh, x[me], y[me], yaw[me], gx, gy, gyaw, pool_x + pool_used,
                                pool_y + pool_used, pool_w + pool_used, da.pool_cap - pool_used, &gc, &gn);
         if (fatal(gk)) break;
         s_e += gk ? 1 : 0;
@@ -749,6 +769,13 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, R
     I->phase[15] += (int64_t)__builtin_amdgcn_s_memtime() - tk0_;   // whole kernel
 #endif
   }
+}
+
+__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, RS_WAVES))) void rrt_rs_kernel(Ctx c, DubArgs da, int iters) {
+  rrt_rs_body<false>(c, da, iters, nullptr);
+}
+__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(RS_WAVES, RS_WAVES))) void rrt_rs_map_kernel(Ctx c, DubArgs da, int iters, rppo::Map mp) {
+  rrt_rs_body<true>(c, da, iters, &mp);
 }
 
 }  // namespace rppr

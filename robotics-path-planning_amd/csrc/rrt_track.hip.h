@@ -25,8 +25,9 @@
 //
 // Capacities: a course (with its extension) of up to LDS_PTS points is held in LDS (x, y; the speed profile always is, one
 // byte per point), up to SLAB_PTS points in the wave's global slab; a longer one sets RRTX_ST_OVERFLOW for the instance.
-// Obstacles: at most 64 per instance (the Reeds-Shepp planner's limit) in the lane-per-obstacle form (CHECK_LINEAR); the two
-// data kernels also come in an obstacle-index form (CHECK_INDEX) that takes a shared list of up to 2^20 circles.
+// Obstacles: at most 64 per instance (the Reeds-Shepp planner's tile) in the lane-per-obstacle form (CHECK_LINEAR); every
+// roll kernel also comes in an obstacle-index form (CHECK_INDEX) that takes a shared list of up to 2^20 circles: the data
+// kernels the tracker's obstacle index, track_roll_kernel and goal_roll_kernel the handle's obstacle map.
 #pragma once
 #include "curve_check.hip.h"
 #include "rpp_track.h"
@@ -270,8 +271,10 @@ __device__ __forceinline__ int lay_course(const int32_t* parent, const int64_t* 
 }
 
 // store = 0: jobs are (instance, candidate), counters[0] of them, records written; store = 1: jobs are the winners
-// (counters[2] of them), arrays written
-__global__ __launch_bounds__(TPB) void track_roll_kernel(TrackArgs a, int store) {
+// (counters[2] of them), arrays written.
+// CHECK_INDEX: the handle holds an obstacle map (every instance's rows are empty); mp is that map, a.ox / oy / othr are not read
+template <int CHECK>
+__global__ __launch_bounds__(TPB) void track_roll_kernel(TrackArgs a, int store, rppo::Map mp) {
   __shared__ double lcx[LDS_PTS], lcy[LDS_PTS];
   __shared__ signed char lsp[SLAB_PTS];
   __shared__ int32_t s_job, s_n;
@@ -297,12 +300,15 @@ __global__ __launch_bounds__(TPB) void track_roll_kernel(TrackArgs a, int store)
     const int total = lay_course(a.parent, a.poff, a.plen, off, (int)a.stride, a.pool[3 * inst], a.pool[3 * inst + 1], a.pool[3 * inst + 2],
                                  node, I->start, gx, gy, gyaw, lcx, lcy, gcw, cx, cy, r);
     if (!r.ood) {
-      const int m = I->obs_m;
+      int m = 0;
       double obx = 0.0, oby = 0.0, obt = -1.0;
-      if (lane < m) {
-        obx = a.ox[I->obs_base + lane];
-        oby = a.oy[I->obs_base + lane];
-        obt = a.othr[I->obs_base + lane];
+      if constexpr (CHECK == CHECK_LINEAR) {
+        m = I->obs_m;
+        if (lane < m) {
+          obx = a.ox[I->obs_base + lane];
+          oby = a.oy[I->obs_base + lane];
+          obt = a.othr[I->obs_base + lane];
+        }
       }
       double* o7 = nullptr;
       int ocap = 0;
@@ -312,7 +318,7 @@ __global__ __launch_bounds__(TPB) void track_roll_kernel(TrackArgs a, int store)
       }
       const int64_t os = (int64_t)ocap + 1;
       const State s0 = {-0.0, -0.0, 0.0, 0.0};
-      roll_course<CHECK_LINEAR>(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, os, r);
+      roll_course<CHECK>(cx, cy, gcw, lsp, &s_n, total, gx, gy, gyaw, lane < m, obx, oby, obt, P, s0, o7, ocap, os, r, &mp);
       if (o7 && lane == 0 && r.find && r.n == ocap) {   // :1519-1521: the goal pose behind x, y, yaw only
         o7[r.n] = gx;
         o7[os + r.n] = gy;

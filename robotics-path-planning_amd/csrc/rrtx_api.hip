@@ -53,6 +53,9 @@ struct ObsGrid {
   rppo::Geom g = {0.0, 0.0, 1.0, 0, 0};
   int64_t m = 0, n_items = 0, n_wide = 0;
   double build_ms = 0.0;
+
+  // the grid as the point-query kernels read it (rpp_obsgrid.h point_first_hit)
+  rppo::Map map() const { return rppo::Map{g, cell_start.as<const int32_t>(), items.as<const rppo::Item>()}; }
 };
 
 struct rrtx_handle : DevObj {
@@ -765,6 +768,8 @@ static void queue_main_kernel(rrtx_handle* h, const Ctx& c, int nblk, const rppd
                        h->d_iargs, h->cbest, h->chunk_iters, h->informed_eager);
   else if (is_dubins(c.algo))
     hipLaunchKernelGGL(rppd::rrt_dubins_kernel, dim3(nblk), dim3(rppd::TPB), 0, h->stream, c, da, h->chunk_iters);
+  else if (c.algo == RRTX_ALGO_RS && h->om.on)
+    hipLaunchKernelGGL(rppr::rrt_rs_map_kernel, dim3(nblk), dim3(rppr::TPB), 0, h->stream, c, da, h->chunk_iters, h->om.grid.map());
   else if (c.algo == RRTX_ALGO_RS)
     hipLaunchKernelGGL(rppr::rrt_rs_kernel, dim3(nblk), dim3(rppr::TPB), 0, h->stream, c, da, h->chunk_iters);
   else if (c.algo == RRTX_ALGO_LQR_RRT_STAR)
@@ -1638,9 +1643,9 @@ static int smooth_status_rc(const std::vector<int32_t>& st, std::string* err) {
 
 int rrtx_smooth_planned(rrtx_handle* h, int32_t max_iter) {
   if (!h || max_iter < 0) return RRTX_E_INVALID;
+  if (int rc = refuse_with_map(h, "rrtx_smooth_planned")) return rc;   // first: RRTX_E_STATE either way, and this one says why
   if (!h->planned || (h->p.algo != RRTX_ALGO_RRT && h->p.algo != RRTX_ALGO_RRT_STAR && h->p.algo != RRTX_ALGO_LQR_RRT_STAR))
     return RRTX_E_STATE;
-  if (int rc = refuse_with_map(h, "rrtx_smooth_planned")) return rc;
   if (h->m_max > rpps::MOB) return RRTX_E_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
   const int B = h->n_inst;
@@ -1755,10 +1760,15 @@ int rrtx_track_planned(rrtx_handle* h, const rrtx_track_params* tp) {
   a.out_off = K.out_off;
   K.h_outc.resize(B);
   K.h_off.assign(B, 0);
+  // with an obstacle map every instance's rows are empty: the roll-outs ask the map, whose thr carries robot_radius as the rows do
+  const rppo::Map mp = h->om.on ? h->om.grid.map() : rppo::Map{};
   float ms = 0.f;
   rc = h->timed(&ms, [&] {
     hipLaunchKernelGGL(rppt::track_list_kernel, dim3(B), dim3(rppt::TPB), 0, h->stream, a);
-    hipLaunchKernelGGL(rppt::track_roll_kernel, dim3(K.blocks), dim3(rppt::TPB), 0, h->stream, a, 0);
+    if (h->om.on)
+      hipLaunchKernelGGL((rppt::track_roll_kernel<rppt::CHECK_INDEX>), dim3(K.blocks), dim3(rppt::TPB), 0, h->stream, a, 0, mp);
+    else
+      hipLaunchKernelGGL((rppt::track_roll_kernel<rppt::CHECK_LINEAR>), dim3(K.blocks), dim3(rppt::TPB), 0, h->stream, a, 0, mp);
     hipLaunchKernelGGL(rppt::track_pick_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, a);
   }, [&]() -> int {
     HIPCHK(h, hipMemcpyAsync(K.h_outc.data(), K.outc, sizeof(rppt::Outcome) * B, hipMemcpyDeviceToHost, h->stream));
@@ -1782,7 +1792,11 @@ int rrtx_track_planned(rrtx_handle* h, const rrtx_track_params* tp) {
     HIPCHK(h, hipMemcpyAsync(K.out_off, K.h_off.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(K.counters + 1, 0, sizeof(int32_t), h->stream));
     rc = h->timed(&ms, [&] {
-      hipLaunchKernelGGL(rppt::track_roll_kernel, dim3(winners < K.blocks ? winners : K.blocks), dim3(rppt::TPB), 0, h->stream, a, 1);
+      const dim3 grid(winners < K.blocks ? winners : K.blocks);
+      if (h->om.on)
+        hipLaunchKernelGGL((rppt::track_roll_kernel<rppt::CHECK_INDEX>), grid, dim3(rppt::TPB), 0, h->stream, a, 1, mp);
+      else
+        hipLaunchKernelGGL((rppt::track_roll_kernel<rppt::CHECK_LINEAR>), grid, dim3(rppt::TPB), 0, h->stream, a, 1, mp);
     });
     if (rc) return rc;
     K.ms += ms;

@@ -103,10 +103,18 @@ static int track_goals(rrtx_handle* h, const rrtx_track_params* tp, int32_t n_go
     G.list_ms += ms;
   }
   // ---- roll and pick
+  // with an obstacle map every instance's rows are empty: the roll-outs ask the map, whose thr carries robot_radius as the rows do
+  const rppo::Map mp = h->om.on ? h->om.grid.map() : rppo::Map{};
+  auto roll = [&](int blocks, int store) {
+    if (h->om.on)
+      hipLaunchKernelGGL((rppgt::goal_roll_kernel<rppt::CHECK_INDEX>), dim3(blocks), dim3(rppgt::TPB), 0, h->stream, a, store, mp);
+    else
+      hipLaunchKernelGGL((rppgt::goal_roll_kernel<rppt::CHECK_LINEAR>), dim3(blocks), dim3(rppgt::TPB), 0, h->stream, a, store, mp);
+  };
   G.h_outc.resize(NQ);
   rc = h->timed(&ms,
                 [&] {
-                  if (tot > 0) hipLaunchKernelGGL(rppgt::goal_roll_kernel, dim3(roll_blocks), dim3(rppgt::TPB), 0, h->stream, a, 0);
+                  if (tot > 0) roll(roll_blocks, 0);
                   hipLaunchKernelGGL(rppgt::goal_pick_kernel, dim3((unsigned)((NQ + 255) / 256)), dim3(256), 0, h->stream, a);
                 },
                 [&]() -> int {
@@ -131,7 +139,7 @@ static int track_goals(rrtx_handle* h, const rrtx_track_params* tp, int32_t n_go
     a.arr_off = G.arr_off.as<const int64_t>();
     a.out_total = steps;
     const int blocks = (int)(winners < roll_blocks ? winners : roll_blocks);
-    rc = h->timed(&ms, [&] { hipLaunchKernelGGL(rppgt::goal_roll_kernel, dim3(blocks), dim3(rppgt::TPB), 0, h->stream, a, 1); });
+    rc = h->timed(&ms, [&] { roll(blocks, 1); });
     if (rc) return rc;   // the timed section waited: the array offsets have been read
     G.store_ms = ms;
   }

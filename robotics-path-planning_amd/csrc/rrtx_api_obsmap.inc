@@ -111,7 +111,7 @@ struct ObsIndex {
   int tried = 0;             // what building for `raw` gave: 0 not tried, else 1 + the reason (USED: `grid` holds it)
   ObsGrid grid;
 
-  rppo::Map map() const { return rppo::Map{grid.g, grid.cell_start.as<const int32_t>(), grid.items.as<const rppo::Item>()}; }
+  rppo::Map map() const { return grid.map(); }
 };
 
 // The decision for the list X holds, with a build where the mode wants one and none was tried for this list
@@ -195,8 +195,8 @@ static int obsindex_get_info(Obj* o, const ObsIndex* X, rrtx_obstacle_index_info
 static int set_obstacle_map(rrtx_handle* h, const double* oxyr, int64_t m) {
   const std::string fn = "rrtx_set_obstacle_map: ";
   if (!h) return fail(h, RRTX_E_INVALID, fn + "the handle is NULL");
-  if (h->p.algo != RRTX_ALGO_RRT && h->p.algo != RRTX_ALGO_RRT_STAR)
-    return fail(h, RRTX_E_INVALID, fn + "served for RRTX_ALGO_RRT and RRTX_ALGO_RRT_STAR only (every other planner keeps its obstacle limit)");
+  if (h->p.algo != RRTX_ALGO_RRT && h->p.algo != RRTX_ALGO_RRT_STAR && h->p.algo != RRTX_ALGO_RS)
+    return fail(h, RRTX_E_INVALID, fn + "served for RRTX_ALGO_RRT, RRTX_ALGO_RRT_STAR and RRTX_ALGO_RS only (every other planner keeps its obstacle limit)");
   if (m < 0) return fail(h, RRTX_E_INVALID, fn + "m < 0");
   if (m > rppo::M_MAX) return fail(h, RRTX_E_INVALID, fn + "more than 2^20 obstacles");
   if (m > 0 && !oxyr) return fail(h, RRTX_E_INVALID, fn + "oxyr is NULL");

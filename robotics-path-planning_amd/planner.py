@@ -443,7 +443,7 @@ class RRTStarDubins:
     def planning(self, animation=True, search_until_max_iter=True):
         h = self._make_handle(bool(search_until_max_iter))
         try:
-            h.set_obstacles(self.obstacle_list)
+            self._load_obstacles(h)
             st = random.getstate()
             h.set_rng_state(0, st)
             if self._trace:
@@ -488,6 +488,9 @@ class RRTStarDubins:
 
     def _after_plan(self, h):
         pass
+
+    def _load_obstacles(self, h):
+        h.set_obstacles(self.obstacle_list)   # the Dubins planners keep the tile
 
 
 class RRTDubins(RRTStarDubins):
@@ -539,6 +542,15 @@ class RRTStarReedsShepp(RRTStarDubins):
                          goal_xy_th=goal_xy_th, device=device)
         self.step_size = step_size
         self.path_yaw = None
+        # How planning() hands over obstacle_list (rrt_06, and rrt_10 below): None = through the obstacle map when the list
+        # has more than 64 circles, the Reeds-Shepp tile (rrtx_set_obstacle_map: any number up to 2**20), True = always,
+        # False = never, which fails beyond 64.  An attribute, set after construction: the constructors keep the
+        # reference's signatures.
+        self.obstacle_map = None
+
+    def _load_obstacles(self, h):
+        h.load_obstacles(self.obstacle_list, _abi.use_obstacle_map(self.obstacle_map, len(self.obstacle_list),
+                                                                   _abi.OBSTACLE_TILE_MAX_RS))
 
     def planning(self, animation=True, search_until_max_iter=True):
         self.path_yaw = None
@@ -1077,9 +1089,10 @@ class BatchPlanner:
         `devices`: HIP device ordinals to shard over (default: [device]).
         `instance_obstacles`: one obstacle list of (x, y, size) per instance, in place of the shared `obstacle_list`
         (which must then be None): a batch over many maps in one launch (rrtx_set_instance_obstacles).
-        `obstacle_map` ("rrt" and "rrt_star" only): None = the shared list goes through the obstacle map when it has more
-        than 256 circles (rrtx_set_obstacle_map: any number up to 2**20), True = always, False = never; every shard
-        builds its own map.  smooth() and query_goals() are not served with a map."""
+        `obstacle_map` ("rrt", "rrt_star", "rrt_star_reeds_shepp" and "closed_loop_rrt_star" only): None = the shared list
+        goes through the obstacle map when it does not fit the planner's tile -- more than 256 circles, 64 for the two
+        Reeds-Shepp planners -- (rrtx_set_obstacle_map: any number up to 2**20), True = always, False = never; every shard
+        builds its own map.  plan(), track() and track_goals() read it; smooth() and query_goals() are not served with a map."""
         from . import sharding
         a = {"rrt": _abi.ALGO_RRT, "rrt_star": _abi.ALGO_RRT_STAR, "rrt_dubins": _abi.ALGO_RRT_DUBINS,
              "rrt_star_dubins": _abi.ALGO_DUBINS, "rrt_star_reeds_shepp": _abi.ALGO_RS, "informed": _abi.ALGO_INFORMED,
@@ -1113,10 +1126,12 @@ class BatchPlanner:
         self.instance_obstacles = instance_obstacles
         self.obstacle_list = obstacle_list
         self.has_obstacle_map = False
+        self.obstacle_tile_max = _abi.OBSTACLE_TILE_MAX_RS if a == _abi.ALGO_RS else _abi.OBSTACLE_TILE_MAX
         if a in _abi.OBSTACLE_MAP_ALGOS and instance_obstacles is None:
-            self.has_obstacle_map = _abi.use_obstacle_map(obstacle_map, len(obstacle_list))
+            self.has_obstacle_map = _abi.use_obstacle_map(obstacle_map, len(obstacle_list), self.obstacle_tile_max)
         elif obstacle_map:
-            raise ValueError("BatchPlanner: obstacle_map serves the shared obstacle_list of \"rrt\" and \"rrt_star\" only")
+            raise ValueError("BatchPlanner: obstacle_map serves the shared obstacle_list of \"rrt\", \"rrt_star\", "
+                             "\"rrt_star_reeds_shepp\" and \"closed_loop_rrt_star\" only")
         self.devices = [int(device)] if devices is None else [int(d) for d in devices]
         if not self.devices or n < len(self.devices):
             raise ValueError("BatchPlanner: %d instances cannot be sharded over %d handles" % (n, len(self.devices)))
@@ -1269,7 +1284,8 @@ class BatchPlanner:
         result's `partial` is then True).  Served for "rrt_star", "rrt_star_dubins" and "rrt_star_reeds_shepp" (ValueError otherwise)."""
         if getattr(self, "has_obstacle_map", False):
             raise ValueError("BatchPlanner.query_goals: not served with an obstacle map (more than %d obstacles, or "
-                             "obstacle_map=True): it reads the obstacle tile" % _abi.OBSTACLE_TILE_MAX)
+                             "obstacle_map=True): it reads the obstacle tile"
+                             % getattr(self, "obstacle_tile_max", _abi.OBSTACLE_TILE_MAX))
         if self.algo not in (_abi.ALGO_RRT_STAR, _abi.ALGO_DUBINS, _abi.ALGO_RS) or getattr(self, "closed_loop", False):
             raise ValueError("BatchPlanner.query_goals: served for %s only (every other planner has another goal rule)"
                              % ", ".join(repr(a) for a in GOAL_QUERY_ALGOS))
@@ -1302,7 +1318,8 @@ class BatchPlanner:
         instance continuing its own random stream (as the driver does at :1558-1559), against its own obstacle list."""
         if getattr(self, "has_obstacle_map", False):
             raise ValueError("BatchPlanner.smooth: not served with an obstacle map (more than %d obstacles, or "
-                             "obstacle_map=True): it reads the obstacle tile" % _abi.OBSTACLE_TILE_MAX)
+                             "obstacle_map=True): it reads the obstacle tile"
+                             % getattr(self, "obstacle_tile_max", _abi.OBSTACLE_TILE_MAX))
         for h in self.handles:
             h.smooth_planned(max_iter)
         c = self.courses("smoothed")
